@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- Mpixels/s of the 3D-LUT apply hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  Everything else the benchmark
+measures (the other precision, the LDS-window statistics pass, the other content kinds, the strong-scaling
+pass, the timed lattice broadcast, BASELINE config 5's host pipeline, the host cost per apply and the CPU
+baseline) runs only with --full.  --dump-outputs DIR writes what the last timed step computed as float32
+DIR/<plane>.npy files (see dump_outputs); the inputs are seeded, so two builds can be compared file by file.
 
 With N > 1 and no WORLD_SIZE in the environment the script starts its own N ranks (one per GPU,
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` as a child
@@ -19,9 +25,9 @@ speed-up north_star words: the same FRAMES frames, rows split N ways.  The only 
 broadcast of the lattice at LUT load, reported in `collective`.
 
 Rank 0 prints ONE JSON line.  `value`, `ms_per_step`, `roofline` and `dtype` describe the STRICT kernels
-(`config.precision`): fp32 lattice, fp32 blend in FFmpeg's scalar-C order, bit-identical to the oracle.  The
-tolerance-bounded FAST kernels (fp16 lattice, <= 1 code from strict) are timed on the same batch and reported
-in `other_precision` with their own `kernel_ms` and dtype string -- never as `value`.
+(`config.precision`): fp32 lattice, fp32 blend in FFmpeg's scalar-C order, bit-identical to the oracle.  With
+--full the tolerance-bounded FAST kernels (fp16 lattice, <= 1 code from strict) are timed on the same batch and
+reported in `other_precision` with their own `kernel_ms` and dtype string -- never as `value`.
 `roofline.achieved` = algorithmic bytes per launch (6 B/px for yuv420p10le in+out, + the 431,244 B lattice)
 / the kernel's mean launch duration measured with HIP events on the launch stream.  `cpu_baseline` times the
 CPU oracle (kind "port": a restatement of FFmpeg lut3d, not FFmpeg) on the host cores.  `extra_Mpx_s` carries
@@ -102,10 +108,18 @@ def parse_args(argv=None):
     ap.add_argument("--no-host-cost", action="store_true", help="skip the host-microseconds-per-apply measurement")
     ap.add_argument("--lean", action="store_true",
                     help="the timed kernel(s) only: --no-cpu-baseline --no-extra --no-strong --pipeline hbm --no-host-cost (tools/)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (the other precision, LDS-window statistics, other "
+                         "content, strong scaling, host pipeline, host cost, CPU baseline; the --no-* options above trim it); "
+                         "without it a run is the headline alone, as with --lean --no-stats --no-other")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/<plane>.npy (float32)")
     args = ap.parse_args(argv)
-    if args.lean:
+    if args.lean or not args.full:
         args.no_cpu_baseline = args.no_extra = args.no_strong = args.no_host_cost = True
         args.pipeline = "hbm"
+    if not args.full:
+        args.no_stats = args.no_other = True
     return args
 
 
@@ -219,6 +233,38 @@ def alloc_out(eng, job, src, w, h):
     dt = torch.uint8 if pfo.depth <= 8 else torch.int16
     nf = src[0].shape[0]
     return [torch.empty((nf,) + pfo.plane_shape(i, w, h), dtype=dt, device=eng.device) for i in range(3)]
+
+
+DUMP_VALUES = 4 << 20          # codes per dumped plane at most: 16 MB of float32, 48 MB for three planes
+DUMP_SEED = 0xD0E5
+
+
+def dump_index(shape, plane):
+    """Sorted flat positions of the fixed, seeded sample --dump-outputs keeps of an output plane of this shape, the same in
+    every run; None when the plane holds at most DUMP_VALUES codes and is written whole."""
+    import numpy as np
+    n = int(np.prod(shape))
+    if n <= DUMP_VALUES:
+        return None
+    return np.sort(np.random.default_rng([DUMP_SEED, plane]).integers(0, n, DUMP_VALUES))
+
+
+def dump_outputs(outdir, pfo, dst, r0, r1):
+    """The output planes of the last timed step as float32 codes in outdir/<plane>.npy: the rows [r0, r1) this rank
+    computed, whole or at the positions dump_index draws."""
+    import numpy as np
+    import torch
+    names = {"yuv": ("y", "cb", "cr"), "gbr": ("g", "b", "r"), "packed": ("packed",)}[pfo.family]
+    outdir.mkdir(parents=True, exist_ok=True)
+    for i, (name, t) in enumerate(zip(names, dst)):
+        sy = pfo.csy if pfo.family == "yuv" and i > 0 else 0
+        t = t[:, r0 >> sy:(r1 + (1 << sy) - 1) >> sy]
+        idx = dump_index(t.shape, i)
+        if idx is not None:
+            t = t[tuple(torch.from_numpy(p).to(t.device) for p in np.unravel_index(idx, t.shape))]
+        if t.dtype == torch.int16:                 # 9- to 16-bit codes travel in int16 containers
+            t = t.to(torch.int32) & 0xFFFF
+        np.save(outdir / f"{name}.npy", t.float().cpu().numpy())
 
 
 PREWARM_MS = 0.0
@@ -481,18 +527,19 @@ def main():
     if world > 1:
         eng.set_lut_distributed(lut, src=0)                 # first use also builds the communicator
         torch.cuda.synchronize()
-        barrier(world)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        eng.set_lut_distributed(lut, src=0)                 # the steady-state cost of a LUT change
-        e1.record()
-        torch.cuda.synchronize()
         lat_bytes = eng.lattice_tensor().numel() * 4
         import torch.distributed as dist
         collective = {"backend": f"{dist.get_backend()}" + (" (RCCL over xGMI)" if dist.get_backend() == "nccl" else ""),
                       "world": dist.get_world_size(), "op": "broadcast(lattice), root 0, once per LUT load",
-                      "bcast_bytes": int(lat_bytes + 16), "bcast_us": round(e0.elapsed_time(e1) * 1e3, 1),
-                      "data_path_collectives": 0}
+                      "bcast_bytes": int(lat_bytes + 16), "data_path_collectives": 0}
+        if args.full:
+            barrier(world)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            eng.set_lut_distributed(lut, src=0)             # the steady-state cost of a LUT change
+            e1.record()
+            torch.cuda.synchronize()
+            collective["bcast_us"] = round(e0.elapsed_time(e1) * 1e3, 1)
     else:
         eng.set_lut(lut)
 
@@ -511,6 +558,8 @@ def main():
 
     wall, kern = time_steps(eng, job, src, dst, args.interp, args.steps, args.warmup, world, r0, r1 - r0)
     kernel_name = eng.last_kernel
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), pf_out, dst, r0, r1)
     tile_stats = None
     if ("tile" in kernel_name or "tube" in kernel_name) and not args.no_stats:   # one extra, untimed pass with the window counters armed
         eng.tile_stats(True)

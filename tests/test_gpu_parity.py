@@ -533,7 +533,7 @@ def test_bench_two_ranks_rehearsal():
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
     res = _torchrun(2, [str(root / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "2",
-                        "--size", "1080p", "--pipeline", "host", "--host-frames", "20"], {})
+                        "--size", "1080p", "--pipeline", "host", "--host-frames", "20", "--full"], {})
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

@@ -259,7 +259,7 @@ def test_bench_starts_its_own_ranks_and_reports_the_collective():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--frames", "2", "--size", "1080p"], env=env, capture_output=True, text=True, timeout=900)
+                          "--frames", "2", "--size", "1080p", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -272,7 +272,7 @@ def test_bench_starts_its_own_ranks_and_reports_the_collective():
 
 
 def test_bench_single_gpu_line_has_every_contract_field():
-    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--frames", "4",
+    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--frames", "4", "--full",
                           "--cpu-seconds", "1", "--pipeline", "host", "--host-frames", "16", "--range-src", "pc"],
                          capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]

@@ -205,12 +205,12 @@ def test_cli_precision_option(orc, cube_dir, tmp_path):
 
 # ------------------------------------------------------------------ bench.py: what the driver's default line must say
 def test_bench_default_line_is_strict_with_fast_beside_it_and_carries_config5():
-    """the default run reports the reference-precision kernel as `value` (dtype f32, config.precision
-    strict), the fp16-lattice kernel only in `other_precision` (own kernel_ms, own dtype string), both precisions on the other
-    content kinds, BASELINE config 5 (`host_pipeline`, pc->tv prologue) with the PCIe rates measured in the same run, and the
-    host cost per apply."""
+    """the run with the default options (and --full) reports the reference-precision kernel as `value`
+    (dtype f32, config.precision strict), the fp16-lattice kernel only in `other_precision` (own kernel_ms, own dtype
+    string), both precisions on the other content kinds, BASELINE config 5 (`host_pipeline`, pc->tv prologue) with the PCIe
+    rates measured in the same run, and the host cost per apply."""
     import json
-    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--frames", "4",
+    res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--frames", "4", "--full",
                           "--cpu-seconds", "1", "--host-frames", "16"], capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     d = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
@@ -238,7 +238,7 @@ def test_bench_four_rank_rehearsal_on_one_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-                          "--frames", "1", "--pipeline", "hbm"], env=env, capture_output=True, text=True, timeout=1100)
+                          "--frames", "1", "--pipeline", "hbm", "--full"], env=env, capture_output=True, text=True, timeout=1100)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     d = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
     assert d["n_gpus"] == 4 and d["collective"]["world"] == 4 and d["collective"]["data_path_collectives"] == 0
