@@ -234,8 +234,15 @@ int lutr_apply_yuv_dither(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, i
  * fp16 of value * (2^depth - 1), blend as a fused multiply-add chain with fp32 accumulation, truncation as in FFmpeg.
  * Output differs from STRICT by at most ONE code at 8 and at 10 bit (north_star allows 1 / 2 against FFmpeg).  It is
  * used where it applies (fused YUV launches on the LDS-window kernels, LUT depth 8 or 10, lattice inside [0, 1]);
- * everything else runs the strict kernels.  lutr_ctx_last_kernel() names what ran (",fast"). */
-enum lutr_precision { LUTR_PRECISION_STRICT = 0, LUTR_PRECISION_FAST = 1 };
+ * everything else runs the strict kernels.  lutr_ctx_last_kernel() names what ran (",fast").
+ * FMA32: the strict kernels' fp32 lattice, coordinates, weights, tap selection, truncation and YUV stages; only the blend
+ * rounds differently -- nodes pre-multiplied by 2^depth - 1 in fp32 (one rounding each), tetrahedral as
+ * fma(w3,c3, fma(w2,c2, fma(w1,c1, w0*c0))), trilinear lerps as fma(b - a, f, a), no final `* M`.  The value before
+ * truncation is within a few fp32 ulp of STRICT's, so output differs from STRICT by at most ONE code at every depth.
+ * It is used where it applies (fused YUV launches on the LDS-window kernels, LUT depth 8 or 10, lattice inside [0, 1], no
+ * prelut, no dither; nearest is identical to STRICT and runs its kernel); everything else runs the strict kernels.
+ * lutr_ctx_last_kernel() names what ran (",fma32"). */
+enum lutr_precision { LUTR_PRECISION_STRICT = 0, LUTR_PRECISION_FAST = 1, LUTR_PRECISION_FMA32 = 2 };
 int lutr_ctx_set_precision(lutr_ctx *ctx, int precision);
 
 /* ---- tuning / introspection (bench and tests) ---- */

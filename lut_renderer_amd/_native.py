@@ -20,7 +20,7 @@ MATRIX = {"bt709": 0, "smpte170m": 1, "bt470bg": 1, "bt601": 1, "bt2020nc": 2, "
 RANGE = {"tv": 0, "pc": 1}
 DITHER = {"none": 0, "error_diffusion": 1}
 VARIANT = {"auto": 0, "generic": 1, "vec_global": 2, "vec_lds": 3}
-PRECISION = {"strict": 0, "fast": 1}
+PRECISION = {"strict": 0, "fast": 1, "fma32": 2}
 BCAST_FORCE_PEER_COPY = 1
 
 #: every symbol include/lutr.h declares (tests check the library exports each one)

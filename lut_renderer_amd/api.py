@@ -119,7 +119,8 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     `precision` is an ENGINE setting, not one of the reference's (models.py:45-56 has no such field): "strict" (default)
     is the bit-exact restatement of FFmpeg's scalar C in fp32; "fast" allows the tolerance-bounded kernels whose lattice
     is fp16 (<= 1 code from strict at 8 and 10 bit) where they exist and silently runs strict elsewhere
-    (`engine.last_kernel` ends in `,fast` when they ran)."""
+    (`engine.last_kernel` ends in `,fast` when they ran); "fma32" keeps strict's fp32 lattice and fuses the blend's
+    multiply-adds (<= 1 code from strict), on the same terms (`,fma32`)."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -135,8 +136,8 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     kw = engine_call_for(plan, pix_fmt, out_pix_fmt)
     # ffmpeg.py:305-307: any value other than "error_diffusion" leaves the chain without a dither filter
     kw["dither"] = "error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none"
-    if precision not in ("strict", "fast"):
-        raise ValueError(f"unknown precision '{precision}' (strict | fast)")
+    if precision not in ("strict", "fast", "fma32"):
+        raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
     own = engine is None
     eng = engine if engine is not None else _cached_engine(devices)
     lut = None

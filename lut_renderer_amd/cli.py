@@ -52,9 +52,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--colorspace", default=None)
     ap.add_argument("--color-range", default=None)
     ap.add_argument("--fps", type=_rate, default=25.0, help="frame rate, a number or a rational like 30000/1001")
-    ap.add_argument("--precision", default="strict", choices=["strict", "fast"],
+    ap.add_argument("--precision", default="strict", choices=["strict", "fast", "fma32"],
                     help="engine setting (not one of the reference's options): strict = bit-exact fp32 restatement of FFmpeg's "
-                         "scalar C (default); fast = tolerance-bounded kernels with an fp16 lattice, <= 1 code from strict")
+                         "scalar C (default); fast = tolerance-bounded kernels with an fp16 lattice, <= 1 code from strict; "
+                         "fma32 = strict's fp32 lattice with a fused multiply-add blend, <= 1 code from strict")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("-y", action="store_true", help="overwrite the output (ffmpeg's -y)")

@@ -259,8 +259,8 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     `build_command`'s out-parameter.  The copy guard of ffmpeg.py:255-256 applies: a LUT stage cannot be a stream copy.
     `precision` is the engine's own setting (`--precision`, default strict; the reference's records have no such field)."""
     import sys as _sys
-    if precision not in ("strict", "fast"):
-        raise ValueError(f"unknown precision '{precision}' (strict | fast)")
+    if precision not in ("strict", "fast", "fma32"):
+        raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
     if lut_path is None:
         raise ValueError("engine_command renders the LUT stage: lut_path is required")
     if source_info is None or not source_info.pix_fmt or not source_info.width or not source_info.height:

@@ -179,6 +179,8 @@ struct lutr_ctx {
     // use per depth (index 0: 8 bit, 1: 10 bit) and dropped whenever the lattice changes
     int precision = LUTR_PRECISION_STRICT;
     uint2 *lat16[2] = {nullptr, nullptr};
+    // fma32 variant: fp32 copies of the lattice pre-multiplied by 2^depth - 1, per LUT depth (index depth - 8), same life cycle
+    float4 *latm[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // lut3d's prelut (lutr_ctx_set_prelut): the host copy, and per LUT depth a device table of the lattice coordinate of every
     // integer code -- the shaper, the scale and the clip folded into one lookup (pre_dev[depth - 8], 3 x pre_entries floats)
     std::vector<float> prelut;
@@ -205,9 +207,12 @@ static void wait_readers(lutr_ctx *c)
     c->readers.clear();
 }
 
+// (the fma32 copies too: every caller drops whatever was derived from the lattice)
 static void drop_lat16(lutr_ctx *c)
 {
     for (auto &p : c->lat16)
+        if (p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(p); p = nullptr; }
+    for (auto &p : c->latm)
         if (p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(p); p = nullptr; }
 }
 
@@ -330,7 +335,7 @@ int lutr_ctx_sync(lutr_ctx *c)
 
 int lutr_ctx_set_precision(lutr_ctx *c, int precision)
 {
-    if (!c || (precision != LUTR_PRECISION_STRICT && precision != LUTR_PRECISION_FAST)) {
+    if (!c || (precision != LUTR_PRECISION_STRICT && precision != LUTR_PRECISION_FAST && precision != LUTR_PRECISION_FMA32)) {
         set_error("bad precision %d", precision);
         return LUTR_EINVAL;
     }
@@ -650,6 +655,23 @@ static const uint2 *fast_lattice(lutr_ctx *c, int depth)
     return slot;
 }
 
+// The fma32 variant's lattice for `depth`, or nullptr when fma32 does not apply: another precision selected, or a lattice
+// outside [0, 1] (the fma32 kernels are clip-free).  No depth limit of its own -- the <= 1 code bound holds at every depth
+// (DESIGN.md 3.5); the tile kernels take it at the depths their coordinate table serves (8 to 10).
+static const float4 *fma32_lattice(lutr_ctx *c, int depth)
+{
+    if (c->precision != LUTR_PRECISION_FMA32 || !c->unit || depth < 8 || depth > 16) return nullptr;
+    float4 *&slot = c->latm[depth - 8];
+    if (!slot) {
+        const size_t nodes = c->lat_bytes / sizeof(float4);
+        void *p = nullptr;
+        if (hipMalloc(&p, nodes * sizeof(float4)) != hipSuccess) return nullptr;
+        slot = (float4 *)p;
+        launch_make_latm(c->stream, c->lat, slot, nodes, (float)((1 << depth) - 1));     // same stream as the apply that follows
+    }
+    return slot;
+}
+
 static int fill_lut(LutConsts *L, lutr_ctx *c, int depth)
 {
     const int maxi = (1 << depth) - 1;
@@ -657,6 +679,7 @@ static int fill_lut(LutConsts *L, lutr_ctx *c, int depth)
     if (rc) return rc;
     L->lat = c->lat;
     L->lat16 = nullptr;
+    L->latm = nullptr;
     L->n1 = c->n + 1;
     L->maxf = (float)maxi;
     L->unit = c->unit ? 1 : 0;
@@ -749,6 +772,7 @@ int lutr_apply_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int w, int
     LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
     L.lat16 = fast_lattice(c, p->lut_depth);
+    L.latm = fma32_lattice(c, p->lut_depth);
     fill_planes(&P, src, dst);
     return finish_launch(c, launch_yuv(c->stream, c->variant, L, K, P, G, LUTR_FMT_DEPTH(p->fmt_in),
                                        LUTR_FMT_DEPTH(p->fmt_out), p->lut_depth, csx, csy, interp, L.lat16 != nullptr,

@@ -28,6 +28,7 @@ namespace lutr {
 struct LutConsts {
     const float4 *lat;
     const uint2  *lat16;  // fast variant: the same nodes as fp16 {r, g, b, 0} of (value * (2^depth - 1)), or nullptr
+    const float4 *latm;   // fma32 variant: the same nodes as fp32 {r, g, b, 0} of (value * (2^depth - 1)), or nullptr
     int   n1;            // n + 1
     float scale_f;       // 1.0f / (2^depth - 1)
     float sc[3];         // scale.{r,g,b} * (n-1)
@@ -116,8 +117,9 @@ LUTR_T2_DECL(w00_c11) LUTR_T2_DECL(w00_c10) LUTR_T2_DECL(w00_c00)
 LUTR_T2_DECL(w11_c11) LUTR_T2_DECL(w11_c10) LUTR_T2_DECL(w11_c00)
 LUTR_T2_DECL(w10_c11) LUTR_T2_DECL(w10_c10) LUTR_T2_DECL(w10_c00)
 #undef LUTR_T2_DECL
-// fp16 lattice of the fast variant (lutr_lat16.hip)
+// fp16 lattice of the fast variant and fp32 pre-multiplied lattice of the fma32 variant (lutr_lat16.hip)
 void launch_make_lat16(hipStream_t st, const float4 *lat, uint2 *out, size_t nodes, float m);
+void launch_make_latm(hipStream_t st, const float4 *lat, float4 *out, size_t nodes, float m);
 
 // persistent LDS-window kernels (lutr_tile.hip); layout already checked by launch_rgb/launch_yuv
 const char *launch_rgb_tile(hipStream_t st, const LutConsts &L, const PlaneSet &P, const FrameGeom &G,

@@ -27,6 +27,9 @@
 //     float4 nodes pre-multiplied by M with plain v_fma_f32 -- full-rate VALU, but ds_read_b128 taps run into LDS bank
 //     conflicts: 403 vs 560 Gpx/s.)  |fast - strict| <= 1 code at 8 and 10 bit (tests/test_fast_variant.py, DESIGN.md
 //     3.4); the strict kernels stay bit-identical to the oracle.
+//   * FMA32 VARIANT (V = 4).  The strict kernels' nodes, layout and staging, read from a copy of the lattice pre-multiplied
+//     by 2^depth-1 in fp32 (LutConsts::latm); the blend is a chain of full-rate v_fma_f32 with no final `* M`.  Each step
+//     rounds once, so the value before truncation is within a few ulp of strict's: <= 1 code at every depth.
 //   * Input and output depth are independent (10-bit in, 8-bit out is the reference's libx264 default).
 //
 // Arithmetic of the strict variants: -ffp-contract=off, FFmpeg's scalar C order, bit-identical to the oracle.
@@ -112,7 +115,7 @@ extern __shared__ __attribute__((aligned(16))) char smem[];
 constexpr int kWaveScratch = LUTR_T2_WPB * 64;
 constexpr int kScratch = kWaveScratch + 128;
 
-enum { V_GEN = 0, V_TAB = 1, V_UNIT = 2, V_FAST = 3 };
+enum { V_GEN = 0, V_TAB = 1, V_UNIT = 2, V_FAST = 3, V_FMA32 = 4 };      // V >= V_UNIT: clip-free
 
 #define DEV __device__ __forceinline__
 
@@ -1070,6 +1073,32 @@ DEV Rgb3 px_blend(const LutConsts &L, const PxC &c, const Taps<LDS, INTERP, V> &
             v.b = mix_lo(w3, T.t[3].y, mix_lo(w2, T.t[2].y, mix_lo(w1, T.t[1].y, mix0_lo(w0, T.t[0].y))));
         }
         return v;
+    } else if constexpr (V == V_FMA32) {
+        // nodes are fp32 of (lattice * M), each a single rounding: the blend is the code before truncation, one rounding per
+        // step.  Same taps and weights as strict; FFmpeg's tetrahedral order w0 c000 + w1 cA + w2 cB + w3 c111, and its
+        // trilinear lerps as fma(v1 - v0, f, v0).
+        if constexpr (INTERP == LUTR_INTERP_NEAREST) {
+            v.r = T.t[0].x; v.g = T.t[0].y; v.b = T.t[0].z;
+        } else if constexpr (INTERP == LUTR_INTERP_TRILINEAR) {
+            const float dr = c.w01.x, dg = c.w01.y, db = c.w23.x;
+            auto lerp = [](float v0, float v1, float f) { return fma_(v1 - v0, f, v0); };
+#define TRI(ch, out) \
+            { \
+                const float c00 = lerp(T.t[0].ch, T.t[4].ch, dr), c10 = lerp(T.t[2].ch, T.t[6].ch, dr); \
+                const float c01 = lerp(T.t[1].ch, T.t[5].ch, dr), c11 = lerp(T.t[3].ch, T.t[7].ch, dr); \
+                const float c0 = lerp(c00, c10, dg), c1 = lerp(c01, c11, dg); \
+                out = lerp(c0, c1, db); \
+            }
+            // (one channel at a time: interleaved, 8-bit 4:2:0 with the prologue spilled five VGPRs)
+            TRI(x, v.r) __builtin_amdgcn_sched_barrier(0); TRI(y, v.g) __builtin_amdgcn_sched_barrier(0); TRI(z, v.b)
+#undef TRI
+        } else {
+            const float w0 = c.w01.x, w1 = c.w01.y, w2 = c.w23.x, w3 = c.w23.y;
+            v.r = fma_(w3, T.t[3].x, fma_(w2, T.t[2].x, fma_(w1, T.t[1].x, w0 * T.t[0].x)));
+            v.g = fma_(w3, T.t[3].y, fma_(w2, T.t[2].y, fma_(w1, T.t[1].y, w0 * T.t[0].y)));
+            v.b = fma_(w3, T.t[3].z, fma_(w2, T.t[2].z, fma_(w1, T.t[1].z, w0 * T.t[0].z)));
+        }
+        return v;
     } else {
         if constexpr (INTERP == LUTR_INTERP_NEAREST) {
             v.r = T.t[0].x; v.g = T.t[0].y; v.b = T.t[0].z;
@@ -1427,8 +1456,9 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
     using N = Node<INTERP, V>;
     // mixed tiles: the strict kernels (see the vote below); not trilinear with the prologue, whose body has no register left for the
     // lanes' verdict (it spilled three VGPRs to scratch inside the body)
-    // (likewise 8-bit 4:4:4 trilinear: eight spilled registers)
-    constexpr bool kMixed = LUTR_T2_MIXED && (V != V_FAST || LUTR_T2_MIXED_FAST) && !(INTERP == LUTR_INTERP_TRILINEAR && (PRE || (!WIN && !CSX)));
+    // (likewise 8-bit 4:4:4 trilinear: eight spilled registers, and fma32 trilinear: three in the headline layout)
+    constexpr bool kMixed = LUTR_T2_MIXED && (V != V_FAST || LUTR_T2_MIXED_FAST) &&
+                            !(INTERP == LUTR_INTERP_TRILINEAR && (PRE || (!WIN && !CSX) || V == V_FMA32));
     LutConsts L = L_;
     YuvConsts K = K_;
     // a wave-uniform constant used by several VALU ops per pixel is worth a VGPR (an SGPR operand halves the issue rate
@@ -1954,6 +1984,7 @@ static int tile2_variant(const LutConsts &L, const YuvConsts &K, int lut_depth, 
     const bool tab = eq && lut_depth <= 10 && (L.pre || !T2_KNOB("LUTR_NO_TAB"));
     const bool unit = L.unit && out_clip_dead(K, 1 << (csx + csy));
     if (fast && tab && unit && L.lat16 && !L.pre) return t2::V_FAST;      // (the fast variant is defined without a prelut: its CPU twin has none)
+    if (tab && unit && L.latm && !L.pre) return t2::V_FMA32;              // (likewise; any LUT depth the table serves)
     if (tab && unit) return t2::V_UNIT;
     if (tab) return t2::V_TAB;
     return t2::V_GEN;
@@ -1968,11 +1999,11 @@ const char *T2_ENTRY(hipStream_t st, const LutConsts &L, const YuvConsts &K, con
     const int pxt = win ? 8 : 16;
     const bool pre = K.pre != 0.0f;
     const int v = tile2_variant(L, K, lut_depth, csx, csy, fast);
-    if (pre && v != V_UNIT && v != V_FAST) return nullptr;
+    if (pre && v != V_UNIT && v != V_FAST && v != V_FMA32) return nullptr;
     if (L.pre && v < V_TAB) return nullptr;                   // a prelut lives in the coordinate table: the general variant computes
     // nearest has no blend to speed up and no prologue instances: strict clip-free kernel, or the round-1 path
     if (mode == LUTR_INTERP_NEAREST && pre) return nullptr;
-    const int vv = (mode == LUTR_INTERP_NEAREST && v == V_FAST) ? V_UNIT : v;
+    const int vv = (mode == LUTR_INTERP_NEAREST && (v == V_FAST || v == V_FMA32)) ? V_UNIT : v;      // (c * M rounds once either way)
     for (int i = 0; i < 3; i++)
         if (P.sfs[i] < 0 || P.dfs[i] < 0 || P.ss[i] < 0 || P.ds[i] < 0 || P.ss[i] >= (1 << 24) || P.ds[i] >= (1 << 24)) return nullptr;
 
@@ -2123,6 +2154,8 @@ const char *T2_ENTRY(hipStream_t st, const LutConsts &L, const YuvConsts &K, con
         TP.ss[i] = (unsigned)P.ss[i]; TP.ds[i] = (unsigned)P.ds[i];
         TP.sfs[i] = (unsigned long long)P.sfs[i]; TP.dfs[i] = (unsigned long long)P.dfs[i];
     }
+    LutConsts Lm = L;                         // the fma32 kernels read the pre-multiplied copy through the strict kernels' pointer
+    Lm.lat = L.latm;
     if (T2_KNOB("LUTR_DEBUG"))
         fprintf(stderr, "[lutr t2] nsx %d nry %d chunk %d chunks %d blocks %u lds/block %zu win_nodes %d tab %d variant %d tube h %d plane %d t %.1f\n",
                 tg.nsx, tg.nry, tg.ch, tg.nchunks, grid.x, lds, tg.win_nodes, tg.tab_entries, vv, tg.tube_h, tg.tube_plane, tg.tube_t);
@@ -2131,21 +2164,25 @@ const char *T2_ENTRY(hipStream_t st, const LutConsts &L, const YuvConsts &K, con
     do { \
         auto kern = k_yuv_tile2<WI, WO, X, Y, I, PR, VV>; \
         if (!allow_lds((const void *)kern, lds)) return nullptr; \
-        hipLaunchKernelGGL(kern, grid, block, lds, st, L, K, TP, G, tg); \
+        hipLaunchKernelGGL(kern, grid, block, lds, st, VV == V_FMA32 ? Lm : L, K, TP, G, tg); \
         return tg.whole ? NAME "+whole-lattice" : (tg.tube_h ? NAME "+tube" : NAME); \
     } while (0)
 #define T2_NAME(WI, WO, X, Y, I, SUF) "k_yuv_tile2<" #WI #WO "," #X #Y "," #I SUF ">"
 #define T2_CASE(WI, WO, X, Y, I) \
     if (mode == I) { \
         if (I == LUTR_INTERP_TETRAHEDRAL && whole16) {      /* (other I: the template argument falls back to an instance that exists anyway) */ \
+            if (pre && vv == V_FMA32) T2_LAUNCH(WI, WO, X, Y, (I == 2 ? T2_TET16 : 2), 1, V_FMA32, T2_NAME(WI, WO, X, Y, I, ",pre,tab,unit,fma32,n16")); \
             if (pre) T2_LAUNCH(WI, WO, X, Y, (I == 2 ? T2_TET16 : 2), 1, V_UNIT, T2_NAME(WI, WO, X, Y, I, ",pre,tab,unit,n16")); \
+            if (vv == V_FMA32) T2_LAUNCH(WI, WO, X, Y, (I == 2 ? T2_TET16 : 2), 0, V_FMA32, T2_NAME(WI, WO, X, Y, I, ",tab,unit,fma32,n16")); \
             if (vv == V_UNIT) T2_LAUNCH(WI, WO, X, Y, (I == 2 ? T2_TET16 : 2), 0, V_UNIT, T2_NAME(WI, WO, X, Y, I, ",tab,unit,n16")); \
             if (vv == V_TAB) T2_LAUNCH(WI, WO, X, Y, (I == 2 ? T2_TET16 : 2), 0, V_TAB, T2_NAME(WI, WO, X, Y, I, ",tab,n16")); \
         } \
         if (I != LUTR_INTERP_NEAREST) { \
             if (pre && vv == V_FAST) T2_LAUNCH(WI, WO, X, Y, (I == 0 ? 2 : I), 1, V_FAST, T2_NAME(WI, WO, X, Y, I, ",pre,tab,unit,fast")); \
+            if (pre && vv == V_FMA32) T2_LAUNCH(WI, WO, X, Y, (I == 0 ? 2 : I), 1, V_FMA32, T2_NAME(WI, WO, X, Y, I, ",pre,tab,unit,fma32")); \
             if (pre) T2_LAUNCH(WI, WO, X, Y, (I == 0 ? 2 : I), 1, V_UNIT, T2_NAME(WI, WO, X, Y, I, ",pre,tab,unit")); \
             if (vv == V_FAST) T2_LAUNCH(WI, WO, X, Y, (I == 0 ? 2 : I), 0, V_FAST, T2_NAME(WI, WO, X, Y, I, ",tab,unit,fast")); \
+            if (vv == V_FMA32) T2_LAUNCH(WI, WO, X, Y, (I == 0 ? 2 : I), 0, V_FMA32, T2_NAME(WI, WO, X, Y, I, ",tab,unit,fma32")); \
         } \
         if (vv == V_UNIT) T2_LAUNCH(WI, WO, X, Y, I, 0, V_UNIT, T2_NAME(WI, WO, X, Y, I, ",tab,unit")); \
         if (vv == V_TAB) T2_LAUNCH(WI, WO, X, Y, I, 0, V_TAB, T2_NAME(WI, WO, X, Y, I, ",tab")); \

@@ -236,9 +236,10 @@ class LutEngine:
 
     def set_precision(self, name: str) -> None:
         """"strict" (default): bit-exact with FFmpeg's scalar C.  "fast": allow the tolerance-bounded tile kernels
-        (<= 1 code from strict at 8 and 10 bit; include/lutr.h lutr_ctx_set_precision)."""
+        (<= 1 code from strict at 8 and 10 bit).  "fma32": strict's fp32 lattice with a fused multiply-add blend (<= 1 code
+        from strict at every depth).  include/lutr.h lutr_ctx_set_precision."""
         if name not in _native.PRECISION:
-            raise ValueError(f"unknown precision '{name}' (strict | fast)")
+            raise ValueError(f"unknown precision '{name}' ({' | '.join(_native.PRECISION)})")
         with self._lock:
             _native.check(self._lib.lutr_ctx_set_precision(self._ctx, _native.PRECISION[name]))
             self.precision = name

@@ -129,7 +129,7 @@ def main(argv=None) -> int:
     ap.add_argument("--info", required=True, help="VideoInfo fields as JSON: width, height, pix_fmt, fps, colorspace, ...")
     ap.add_argument("--ffmpeg", default="ffmpeg")
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--precision", default="strict", choices=["strict", "fast"], help="engine setting, see lut_renderer_amd.cli")
+    ap.add_argument("--precision", default="strict", choices=["strict", "fast", "fma32"], help="engine setting, see lut_renderer_amd.cli")
     a = ap.parse_args(argv)
     try:
         params = ProcessingParams.from_dict(json.loads(a.params))

@@ -5,7 +5,7 @@ The tube and the raw boxes rest on conservative bounds (csrc/lutr_tile2.hip map_
 optimistic a pixel would read a node that is not staged and come out wrong.  This drives the two kernels with frames built to
 sit ON those bounds -- chroma swept radially from neutral to far outside the tube in every direction, luma uniform over the
 whole code range (clipping included), random lattice sizes, domains, matrices, ranges, formats, depths, interpolations -- and
-compares every sample (and holds the fast kernels to one code from that).  Both sides are the product's strict kernels (GPU against GPU, so sizes can be large); the generic
+compares every sample (and holds the fast and fma32 kernels to one code from that).  Both sides are the product's strict kernels (GPU against GPU, so sizes can be large); the generic
 kernel is itself pinned against the oracle by tests/.
 """
 import sys
@@ -47,6 +47,7 @@ def main():
     eng = LutEngine(0)
     rng = np.random.default_rng(20261004)
     t0, runs, px, tube_tiles, tiles, fast_runs, pre_runs = time.time(), 0, 0, 0, 0, 0, 0
+    fma32_runs = 0
     fmts = [("yuv420p10le", 10, 1, 1), ("yuv420p", 8, 1, 1), ("yuv422p10le", 10, 1, 0), ("yuv444p10le", 10, 0, 0), ("yuv444p", 8, 0, 0)]
     while time.time() - t0 < budget:
         n = int(rng.choice([9, 17, 19, 20, 21, 22, 26, 29, 33, 33, 33, 37, 40, 41, 65]))      # (up to 21 / 25: the whole lattice in LDS)
@@ -107,11 +108,22 @@ def main():
                 tol = 1 if kw.get("lut_depth", depth) == depth else 4
                 if int(d.max()) > tol:
                     raise SystemExit(f"FAST MISMATCH run {runs}: n={n} {fmt} {kw} {eng.last_kernel} plane {i}: max {int(d.max())}")
+        # the fma32 kernels (strict staging, fused blend): at most one code from the strict result, the strict one itself elsewhere
+        eng.set_precision("fma32")
+        c = eng.apply_yuv(dev, **kw)
+        eng.set_precision("strict")
+        used = ",fma32" in eng.last_kernel
+        fma32_runs += used
+        for i, (x, y) in enumerate(zip(c, b)):
+            d = (x[:, rows_of(i)].to(torch.int32) - y.to(torch.int32)).abs()
+            tol = 0 if not used else (1 if kw.get("lut_depth", depth) == depth else 4)
+            if int(d.max()) > tol:
+                raise SystemExit(f"FMA32 MISMATCH run {runs}: n={n} {fmt} {kw} {eng.last_kernel} plane {i}: max {int(d.max())}")
         runs += 1
         px += 4 * w * h
         tube_tiles += st["tube_tiles"]
         tiles += st["tiles"]
-    print(f"soak ok: {runs} runs ({fast_runs} also with the fast kernels, {pre_runs} with a shared prelut), {px / 1e6:.0f} Mpx compared, {tiles} tiles "
+    print(f"soak ok: {runs} runs ({fast_runs} also with the fast kernels, {fma32_runs} with the fma32 kernels, {pre_runs} with a shared prelut), {px / 1e6:.0f} Mpx compared, {tiles} tiles "
           f"({tube_tiles} through the tube), {time.time() - t0:.0f} s")
 
 
