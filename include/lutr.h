@@ -218,6 +218,39 @@ int lutr_apply_packed_rgb(lutr_ctx *ctx, int pfmt, int interp, int w, int h, int
 int lutr_apply_yuv(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int w, int h, int nframes,
                    const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
 
+/* Chroma siting of the resampling around the LUT, named like ffprobe's chroma_location.
+ *   REPLICATE: each chroma sample is replicated over its block before the LUT and the block mean is taken after it
+ *              (lutr_apply_yuv's contract).
+ *   LEFT:      MPEG-2 / H.264 / HEVC default: horizontally co-sited, vertically interstitial.
+ *   CENTER:    JPEG / MPEG-1: interstitial on both axes.
+ *   TOPLEFT:   HEVC / BT.2020 type 2 (HDR10): co-sited on both axes.
+ * "Co-sited": chroma sample k sits on luma sample 2k; "interstitial": halfway between luma samples 2k and 2k+1. */
+enum lutr_chroma_loc {
+    LUTR_CHROMA_REPLICATE = 0,
+    LUTR_CHROMA_LEFT      = 1,
+    LUTR_CHROMA_CENTER    = 2,
+    LUTR_CHROMA_TOPLEFT   = 3
+};
+
+/* lutr_apply_yuv with sited bilinear chroma resampling: before YUV -> RGB each luma pixel takes a weighted sum of the
+ * (prologue'd) chroma codes around it, weights in quarters per subsampled axis (co-sited: 4 | 2 2, interstitial: 1 3 | 3 1);
+ * after lut3d each chroma sample is a weighted sum of the LUT's RGB output (co-sited axis: taps 2i-1, 2i, 2i+1 weighted
+ * 1 2 1; interstitial axis: taps 2i, 2i+1 weighted 1 1).  Every coordinate clamps to its plane.  All sums are exact
+ * integers in fp32; the rest is lutr_apply_yuv's arithmetic.  Always strict precision (fast / fma32 run strict here).
+ * chroma_loc == LUTR_CHROMA_REPLICATE and 4:4:4 formats are lutr_apply_yuv itself (same kernels, same bits).
+ * The up- and down-sampling read source rows and columns around the output region, including rows outside
+ * [row0, row0 + rows) of the full frame; only the shard is written.  In-place operation is not supported: the bounding
+ * byte range of every source plane (all its rows and frames) must be disjoint from that of every destination plane, else
+ * LUTR_EINVAL -- a conservative rule that also refuses planes interleaved row by row in one buffer.  That and an unknown
+ * chroma_loc are rejected before anything touches the device.  4:2:0 / 4:2:2 launches with equal input and output widths,
+ * a width that is a multiple of 4 and aligned, positive strides run the vector kernel (last kernel "k_yuv_sited_vec<..>"),
+ * every other layout the per-sample kernel ("k_yuv_sited<..>"); both compute the same bits. */
+int lutr_apply_yuv_sited(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int chroma_loc, int w, int h, int nframes,
+                         const lutr_planes *src, lutr_planes *dst, int row0, int rows);
+/* lutr_yuv_constants for lutr_apply_yuv_sited: the same block with the down-sampling's 1/n folded into cbr..crb
+ * (n = product of the tap sums of the subsampled axes: 2, 4, 8 or 16; formed in double, rounded once to float) */
+int lutr_yuv_constants_sited(const lutr_yuv_params *p, int chroma_loc, float out[32]);
+
 /* zscale_dither of the reference (models.py:46; the filter `zscale=dither=error_diffusion`, ffmpeg.py:305-307) */
 enum lutr_dither { LUTR_DITHER_NONE = 0, LUTR_DITHER_ERROR_DIFFUSION = 1 };
 

@@ -21,6 +21,9 @@ RANGE = {"tv": 0, "pc": 1}
 DITHER = {"none": 0, "error_diffusion": 1}
 VARIANT = {"auto": 0, "generic": 1, "vec_global": 2, "vec_lds": 3}
 PRECISION = {"strict": 0, "fast": 1, "fma32": 2}
+#: enum lutr_chroma_loc: ffprobe's chroma_location names (None = replicate, lutr_apply_yuv's contract)
+CHROMA_LOC = {"left": 1, "center": 2, "topleft": 3}
+CHROMA_REPLICATE = 0
 BCAST_FORCE_PEER_COPY = 1
 
 #: every symbol include/lutr.h declares (tests check the library exports each one)
@@ -31,6 +34,7 @@ SYMBOLS = (
     "lutr_ctx_set_lut", "lutr_ctx_lut_alloc", "lutr_ctx_lut_device", "lutr_ctx_lut_seal",
     "lutr_lattice_bytes", "lutr_lut_broadcast", "lutr_lut_broadcast_ex",
     "lutr_apply_planar_rgb", "lutr_apply_packed_rgb", "lutr_apply_yuv", "lutr_apply_yuv_dither",
+    "lutr_apply_yuv_sited", "lutr_yuv_constants_sited",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
 )
 
@@ -121,6 +125,9 @@ def load() -> C.CDLL:
                                    ci, ci]
     lib.lutr_apply_yuv_dither.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes),
                                           C.POINTER(Planes)]
+    lib.lutr_apply_yuv_sited.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes),
+                                         C.POINTER(Planes), ci, ci]
+    lib.lutr_yuv_constants_sited.argtypes = [C.POINTER(YuvParams), ci, C.POINTER(C.c_float)]
     lib.lutr_ctx_set_variant.argtypes = [vp, ci]
     lib.lutr_ctx_set_precision.argtypes = [vp, ci]
     lib.lutr_ctx_last_kernel.argtypes = [vp]

@@ -104,7 +104,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               height: Optional[int] = None, input_matrix: str = "auto", colorspace: Optional[str] = None,
               color_range: Optional[str] = None, output_tags: str = "bt709", out_pix_fmt: Optional[str] = None,
               zscale_dither: str = "none", out: Optional[Sequence] = None, engine=None,
-              devices: Sequence[int] = (0,), precision: str = "strict"):
+              devices: Sequence[int] = (0,), precision: str = "strict", chroma_loc: Optional[str] = None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  Returns (planes_out, tags) where `tags` is the colour
     metadata the reference would write for this policy (None = inherit / none).
@@ -120,7 +120,11 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     is the bit-exact restatement of FFmpeg's scalar C in fp32; "fast" allows the tolerance-bounded kernels whose lattice
     is fp16 (<= 1 code from strict at 8 and 10 bit) where they exist and silently runs strict elsewhere
     (`engine.last_kernel` ends in `,fast` when they ran); "fma32" keeps strict's fp32 lattice and fuses the blend's
-    multiply-adds (<= 1 code from strict), on the same terms (`,fma32`)."""
+    multiply-adds (<= 1 code from strict), on the same terms (`,fma32`).
+
+    `chroma_loc` is an engine setting too: None (default) replicates chroma over its block before the LUT and takes the
+    block mean after it; "left" | "center" | "topleft" (ffprobe's chroma_location) resample chroma bilinearly at that
+    siting (always strict arithmetic, no in-place output, not with error-diffusion dither)."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -138,6 +142,10 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     kw["dither"] = "error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none"
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
+    from .engine import check_chroma_loc
+    check_chroma_loc(chroma_loc, kw["dither"])
+    if chroma_loc is not None:
+        kw["chroma_loc"] = chroma_loc
     own = engine is None
     eng = engine if engine is not None else _cached_engine(devices)
     lut = None

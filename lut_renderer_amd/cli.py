@@ -56,6 +56,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="engine setting (not one of the reference's options): strict = bit-exact fp32 restatement of FFmpeg's "
                          "scalar C (default); fast = tolerance-bounded kernels with an fp16 lattice, <= 1 code from strict; "
                          "fma32 = strict's fp32 lattice with a fused multiply-add blend, <= 1 code from strict")
+    ap.add_argument("--chroma-loc", default=None, choices=["left", "center", "topleft"],
+                    help="engine setting: resample chroma bilinearly at this siting (ffprobe's chroma_location) instead of "
+                         "replicating it over its block; strict arithmetic")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("-y", action="store_true", help="overwrite the output (ffmpeg's -y)")
@@ -78,6 +81,10 @@ def plan_from_args(args):
     kw = engine_call_for(plan, args.pix_fmt, args.out_pix_fmt)
     if args.zscale_dither == "error_diffusion":
         kw["dither"] = "error_diffusion"
+    if getattr(args, "chroma_loc", None):
+        from .engine import check_chroma_loc
+        check_chroma_loc(args.chroma_loc, kw.get("dither", "none"))
+        kw["chroma_loc"] = args.chroma_loc
     return plan, kw, w, h
 
 

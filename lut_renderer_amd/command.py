@@ -250,17 +250,20 @@ def build_pipeline(task: Task, ffmpeg_bin: str = "ffmpeg") -> List[CommandStage]
 # ---------------------------------------------------------------- engine twin
 def engine_command(source: Path, output: Path, params: ProcessingParams, lut_path: Path,
                    source_info: VideoInfo, python_bin: Optional[str] = None, device: int = 0,
-                   notes: Optional[List[str]] = None, precision: str = "strict") -> List[str]:
+                   notes: Optional[List[str]] = None, precision: str = "strict", chroma_loc: Optional[str] = None) -> List[str]:
     """`build_command`'s twin for the LUT stage alone: the argv of the ENGINE CLI (`python -m lut_renderer_amd.cli`)
     that applies exactly the chain `build_command` would put into `-vf` -- the same `LutPlan`, rendered as CLI options
     instead of as a filter string (ffmpeg.py:195-247, :287-310).  `source` / `output` are rawvideo files (or `-`) in
     `source_info.pix_fmt` and the pixel format `resolve_pix_fmt` picks; `task_manager.py:145-151` can Popen the result
     unchanged (same `Duration:` / `time=` / exit-code / SIGTERM contract).  `notes` receives the plan's notes, like
     `build_command`'s out-parameter.  The copy guard of ffmpeg.py:255-256 applies: a LUT stage cannot be a stream copy.
-    `precision` is the engine's own setting (`--precision`, default strict; the reference's records have no such field)."""
+    `precision` is the engine's own setting (`--precision`, default strict; the reference's records have no such field), and
+    so is `chroma_loc` (`--chroma-loc`, rendered only when given: None keeps the replicating chroma contract)."""
     import sys as _sys
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
+    if chroma_loc is not None and chroma_loc not in ("left", "center", "topleft"):
+        raise ValueError(f"unknown chroma location '{chroma_loc}' (left | center | topleft)")
     if lut_path is None:
         raise ValueError("engine_command renders the LUT stage: lut_path is required")
     if source_info is None or not source_info.pix_fmt or not source_info.width or not source_info.height:
@@ -293,6 +296,10 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
         cmd += ["--device", str(int(device))]
     if precision != "strict":
         cmd += ["--precision", precision]
+    if chroma_loc is not None:
+        if "--zscale-dither" in cmd:
+            raise ValueError("error-diffusion dither is not defined with sited chroma resampling (chroma_loc)")
+        cmd += ["--chroma-loc", chroma_loc]
     return cmd
 
 

@@ -151,6 +151,31 @@ int make_yuv_consts(const lutr_yuv_params &p, YuvConsts *o)
     return LUTR_OK;
 }
 
+// down-sampling taps sum to 4 on a co-sited axis, 2 on an interstitial one, 1 on an axis that is not
+// subsampled; n is their product.  1/n is folded into cbr..crb like the block mean's 1/4 (formed in double, rounded once).
+int make_yuv_consts_sited(const lutr_yuv_params &p, int loc, YuvConsts *o)
+{
+    if (loc < LUTR_CHROMA_REPLICATE || loc > LUTR_CHROMA_TOPLEFT) {
+        set_error("unknown chroma location %d", loc);
+        return LUTR_EINVAL;
+    }
+    const int csx = LUTR_FMT_CSX(p.fmt_in), csy = LUTR_FMT_CSY(p.fmt_in);
+    const int rc = make_yuv_consts(p, o);
+    if (rc || loc == LUTR_CHROMA_REPLICATE || (csx == 0 && csy == 0)) return rc;
+    const int nx = csx ? (loc == LUTR_CHROMA_CENTER ? 2 : 4) : 1;
+    const int ny = csy ? (loc == LUTR_CHROMA_TOPLEFT ? 4 : 2) : 1;
+    lutr_yuv_params q = p;
+    q.fmt_in = LUTR_FMT(LUTR_FMT_DEPTH(p.fmt_in), 0, 0);
+    q.fmt_out = LUTR_FMT(LUTR_FMT_DEPTH(p.fmt_out), 0, 0);
+    YuvConsts k1;
+    if (const int rc1 = make_yuv_consts(q, &k1)) return rc1;
+    // n is a power of two: double(c) / n rounds to the same float as the 4:4:4 float times 1/n
+    const float inv = 1.0f / (float)(nx * ny);
+    o->cbr = k1.cbr * inv; o->cbg = k1.cbg * inv; o->cbb = k1.cbb * inv;
+    o->crr = k1.crr * inv; o->crg = k1.crg * inv; o->crb = k1.crb * inv;
+    return LUTR_OK;
+}
+
 }  // namespace lutr
 
 using namespace lutr;
@@ -777,6 +802,79 @@ int lutr_apply_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int w, int
     return finish_launch(c, launch_yuv(c->stream, c->variant, L, K, P, G, LUTR_FMT_DEPTH(p->fmt_in),
                                        LUTR_FMT_DEPTH(p->fmt_out), p->lut_depth, csx, csy, interp, L.lat16 != nullptr,
                                        c->stats, c->queue));
+}
+
+// Byte range [lo, hi) that `rows` rows of `row_bytes` bytes span in each of `nframes` frames.
+static void plane_span(const void *p, long long stride, long long fstride, int rows, long long row_bytes, int nframes,
+                       uintptr_t *lo, uintptr_t *hi)
+{
+    const long long r = (long long)(rows - 1) * stride, f = nframes > 1 ? (long long)(nframes - 1) * fstride : 0;
+    const long long a = (r < 0 ? r : 0) + (f < 0 ? f : 0), b = (r > 0 ? r : 0) + (f > 0 ? f : 0) + row_bytes;
+    *lo = (uintptr_t)p + (intptr_t)a;
+    *hi = (uintptr_t)p + (intptr_t)b;
+}
+
+int lutr_apply_yuv_sited(lutr_ctx *c, const lutr_yuv_params *p, int interp, int chroma_loc, int w, int h, int nframes,
+                         const lutr_planes *src, lutr_planes *dst, int row0, int rows)
+{
+    if (chroma_loc < LUTR_CHROMA_REPLICATE || chroma_loc > LUTR_CHROMA_TOPLEFT) {
+        set_error("unknown chroma location %d", chroma_loc);
+        return LUTR_EINVAL;
+    }
+    int rc = check_common(c, interp, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    const int csx = LUTR_FMT_CSX(p->fmt_in), csy = LUTR_FMT_CSY(p->fmt_in);
+    if (chroma_loc == LUTR_CHROMA_REPLICATE || (csx == 0 && csy == 0))
+        return lutr_apply_yuv(c, p, interp, w, h, nframes, src, dst, row0, rows);
+    YuvConsts K;
+    rc = make_yuv_consts_sited(*p, chroma_loc, &K);
+    if (rc) return rc;
+    const int bh = 1 << csy;
+    if (row0 % bh || (rows % bh && row0 + rows != h)) {
+        set_error("row0/rows must be multiples of the chroma block height %d", bh);
+        return LUTR_EINVAL;
+    }
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    for (int i = 0; i < 3; i++)
+        if (!src->data[i] || !dst->data[i]) { set_error("null plane %d", i); return LUTR_EINVAL; }
+    // the resampling reads around every output sample: a destination that overlaps a source would be read after being written
+    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
+    const int cw = (w + (1 << csx) - 1) >> csx, ch = (h + bh - 1) >> csy;
+    for (int i = 0; i < 3; i++) {
+        uintptr_t slo, shi;
+        plane_span(src->data[i], src->stride[i], src->frame_stride[i], i ? ch : h, (long long)(i ? cw : w) * (din > 8 ? 2 : 1),
+                   nframes, &slo, &shi);
+        for (int j = 0; j < 3; j++) {
+            uintptr_t dlo, dhi;
+            plane_span(dst->data[j], dst->stride[j], dst->frame_stride[j], j ? ch : h, (long long)(j ? cw : w) * (dout > 8 ? 2 : 1),
+                       nframes, &dlo, &dhi);
+            if (slo < dhi && dlo < shi) {
+                set_error("sited chroma resampling cannot run in place: the byte range of source plane %d overlaps that of destination plane %d (bounding ranges over all rows and frames must be disjoint)", i, j);
+                return LUTR_EINVAL;
+            }
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
+    fill_planes(&P, src, dst);
+    const char *name = launch_yuv_sited(c->stream, L, K, P, G, din, dout, csy, chroma_loc, interp);
+    if (!name) { set_error("launch too large for the sited kernels (split the batch)"); return LUTR_EINVAL; }
+    return finish_launch(c, name);
+}
+
+int lutr_yuv_constants_sited(const lutr_yuv_params *p, int chroma_loc, float out[32])
+{
+    if (!p || !out) {
+        set_error("lutr_yuv_constants_sited: null argument");
+        return LUTR_EINVAL;
+    }
+    YuvConsts k;
+    const int rc = make_yuv_consts_sited(*p, chroma_loc, &k);
+    if (rc) return rc;
+    std::memcpy(out, &k, sizeof(k));
+    return LUTR_OK;
 }
 
 int lutr_apply_yuv_dither(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dither, int w, int h, int nframes,

@@ -117,6 +117,10 @@ LUTR_T2_DECL(w00_c11) LUTR_T2_DECL(w00_c10) LUTR_T2_DECL(w00_c00)
 LUTR_T2_DECL(w11_c11) LUTR_T2_DECL(w11_c10) LUTR_T2_DECL(w11_c00)
 LUTR_T2_DECL(w10_c11) LUTR_T2_DECL(w10_c10) LUTR_T2_DECL(w10_c00)
 #undef LUTR_T2_DECL
+// sited chroma resampling (lutr_sited.hip): 4:2:0 / 4:2:2, loc = LUTR_CHROMA_LEFT / CENTER / TOPLEFT; K carries the
+// down-sampling's 1/n in cbr..crb (make_yuv_consts_sited); nullptr = the launch is too large
+const char *launch_yuv_sited(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
+                             int din, int dout, int csy, int loc, int mode);
 // fp16 lattice of the fast variant and fp32 pre-multiplied lattice of the fma32 variant (lutr_lat16.hip)
 void launch_make_lat16(hipStream_t st, const float4 *lat, uint2 *out, size_t nodes, float m);
 void launch_make_latm(hipStream_t st, const float4 *lat, float4 *out, size_t nodes, float m);
@@ -127,6 +131,7 @@ const char *launch_rgb_tile(hipStream_t st, const LutConsts &L, const PlaneSet &
 
 // host helpers (yuv_consts.cpp / cube_parse.cpp)
 int make_yuv_consts(const lutr_yuv_params &p, YuvConsts *out);
+int make_yuv_consts_sited(const lutr_yuv_params &p, int chroma_loc, YuvConsts *out);
 void set_error(const char *fmt, ...);
 
 }  // namespace lutr

@@ -68,6 +68,22 @@ def parse_pix_fmt(name: str) -> PixFmt:
     return PixFmt(name, "yuv", depth_i, csx, csy, fam == "yuvj")
 
 
+def chroma_loc_code(chroma_loc: Optional[str]) -> int:
+    """enum lutr_chroma_loc for a chroma_location name (None = replicate); ValueError for any other name."""
+    if chroma_loc is None:
+        return _native.CHROMA_REPLICATE
+    if chroma_loc not in _native.CHROMA_LOC:
+        raise ValueError(f"unknown chroma location '{chroma_loc}' (None | {' | '.join(_native.CHROMA_LOC)})")
+    return _native.CHROMA_LOC[chroma_loc]
+
+
+def check_chroma_loc(chroma_loc: Optional[str], dither: str = "none") -> None:
+    """The checks `apply_yuv` makes of `chroma_loc` before any GPU work: a known name, and no error-diffusion dither with it."""
+    chroma_loc_code(chroma_loc)
+    if chroma_loc is not None and dither != "none":
+        raise ValueError("error-diffusion dither is not defined with sited chroma resampling (chroma_loc)")
+
+
 def _check_planes(planes: Sequence[torch.Tensor], fmt: PixFmt, w: int, h: int, what: str) -> None:
     """The C-ABI takes bare pointers and cannot know buffer sizes: every plane must have exactly the shape and the
     element size `fmt` implies for a w x h frame, or the kernels would read or write outside it."""
@@ -325,11 +341,14 @@ class LutEngine:
                   pix_fmt: str, interp: str = "tetrahedral", matrix_in: str = "bt709",
                   matrix_out: Optional[str] = None, range_src: str = "tv", range_in: Optional[str] = None,
                   range_out: str = "tv", lut_depth: Optional[int] = None, out_pix_fmt: Optional[str] = None,
-                  row0: int = 0, rows: Optional[int] = None, dither: str = "none"):
+                  row0: int = 0, rows: Optional[int] = None, dither: str = "none", chroma_loc: Optional[str] = None):
         """Fused YUV -> RGB -> lut3d -> RGB -> YUV on planar frames (Y, Cb, Cr).
-        dither="error_diffusion" (the reference's `zscale_dither`) dithers the final quantisation; whole frames only."""
+        dither="error_diffusion" (the reference's `zscale_dither`) dithers the final quantisation; whole frames only.
+        chroma_loc ("left" | "center" | "topleft", ffprobe's chroma_location names) resamples chroma bilinearly at that
+        siting instead of replicating it (strict arithmetic, not in place, no dither).  None = replicate."""
         if dither not in _native.DITHER:
             raise ValueError(f"unknown dither mode '{dither}'")
+        check_chroma_loc(chroma_loc, dither)
         fin = parse_pix_fmt(pix_fmt)
         fout = parse_pix_fmt(out_pix_fmt or pix_fmt)
         if fin.family != "yuv" or fout.family != "yuv":
@@ -358,7 +377,11 @@ class LutEngine:
             raise ValueError("error-diffusion dither couples the rows of a frame: whole frames only")
         with self._lock:
             self._bind_stream()
-            if dither != "none":
+            if chroma_loc is not None:
+                _native.check(self._lib.lutr_apply_yuv_sited(
+                    self._ctx, C.byref(p), _native.INTERP[interp], chroma_loc_code(chroma_loc), w, h, nf, C.byref(s), C.byref(d),
+                    row0, rows))
+            elif dither != "none":
                 _native.check(self._lib.lutr_apply_yuv_dither(
                     self._ctx, C.byref(p), _native.INTERP[interp], _native.DITHER[dither], w, h, nf, C.byref(s), C.byref(d)))
             else:
@@ -374,6 +397,16 @@ def yuv_constants(**kw) -> np.ndarray:
         setattr(p, k, v)
     out = (C.c_float * 32)()
     _native.check(_native.load().lutr_yuv_constants(C.byref(p), out))
+    return np.array(list(out), dtype=np.float32)
+
+
+def yuv_constants_sited(chroma_loc: Optional[str], **kw) -> np.ndarray:
+    """`yuv_constants` with the sited down-sampling's 1/n folded into cbr..crb (lutr_yuv_constants_sited)."""
+    p = _native.YuvParams()
+    for k, v in kw.items():
+        setattr(p, k, v)
+    out = (C.c_float * 32)()
+    _native.check(_native.load().lutr_yuv_constants_sited(C.byref(p), chroma_loc_code(chroma_loc), out))
     return np.array(list(out), dtype=np.float32)
 
 

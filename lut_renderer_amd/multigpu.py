@@ -149,6 +149,21 @@ class LutEngineGroup:
             # another GPU: its row block travels there (peer copy), is processed as a frame of r1-r0 rows, and comes back
             c0, c1 = r0 >> fin.csy, (r1 + bh - 1) >> fin.csy
             rng = [(r0, r1), (c0, c1), (c0, c1)]
+            if kw.get("chroma_loc") is not None:
+                # sited resampling reads one chroma row (one chroma block row of luma) above and below the block: the slice
+                # that travels carries that halo, clipped to the frame, and the apply writes the block's rows inside it
+                ch = (h + bh - 1) >> fin.csy
+                h0, h1 = max(c0 - 1, 0), min(c1 + 1, ch)
+                srng = [(h0 * bh, min(h1 * bh, h)), (h0, h1), (h0, h1)]
+                with torch.cuda.device(eng.device):
+                    part = [p[..., a:b, :].to(eng.device, non_blocking=True, copy=True).contiguous()
+                            for p, (a, b) in zip(src, srng)]
+                    full = eng.apply_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0 - h0 * bh, rows=r1 - r0,
+                                         **kw)
+                    out = [o[..., a - sa:b - sa, :] for o, (a, b), (sa, _) in zip(full, rng, srng)]
+                self.last_remote += 1
+                pending.append((out, rng))
+                continue
             with torch.cuda.device(eng.device):
                 part = [p[..., a:b, :].to(eng.device, non_blocking=True, copy=True).contiguous()
                         for p, (a, b) in zip(src, rng)]

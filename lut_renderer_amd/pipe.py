@@ -46,12 +46,13 @@ class StageCommands:
 
 def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, lut_path: Path, source_info: VideoInfo,
                           ffmpeg_bin: str = "ffmpeg", python_bin: Optional[str] = None, device: int = 0,
-                          precision: str = "strict") -> StageCommands:
+                          precision: str = "strict", chroma_loc: Optional[str] = None) -> StageCommands:
     """The three argv lists of one LUT stage.  Raises what `build_command` / `engine_command` raise (copy guard, missing
-    geometry)."""
+    geometry).  `chroma_loc` goes to the engine (`--chroma-loc`) and, as `-chroma_sample_location`, to the encoder, so the
+    output stream declares the siting the engine assumed."""
     notes: List[str] = []
     engine = engine_command(Path("-"), Path("-"), params, lut_path, source_info, python_bin=python_bin, device=device, notes=notes,
-                            precision=precision)
+                            precision=precision, chroma_loc=chroma_loc)
     if source_info.duration:
         engine += ["--duration", f"{float(source_info.duration):.3f}"]
     decoder = [ffmpeg_bin, "-hide_banner", "-nostdin", "-i", str(source), "-map", "0:v:0", "-f", "rawvideo",
@@ -83,6 +84,8 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
     for flag in ("-color_primaries", "-color_trc", "-colorspace", "-color_range"):
         if flag in full:
             encoder[-1:-1] = [flag, full[full.index(flag) + 1]]
+    if chroma_loc is not None:
+        encoder[-1:-1] = ["-chroma_sample_location", chroma_loc]
     return StageCommands(decoder, engine, encoder, notes)
 
 
@@ -130,12 +133,13 @@ def main(argv=None) -> int:
     ap.add_argument("--ffmpeg", default="ffmpeg")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--precision", default="strict", choices=["strict", "fast", "fma32"], help="engine setting, see lut_renderer_amd.cli")
+    ap.add_argument("--chroma-loc", default=None, choices=["left", "center", "topleft"], help="engine setting, see lut_renderer_amd.cli")
     a = ap.parse_args(argv)
     try:
         params = ProcessingParams.from_dict(json.loads(a.params))
         info = VideoInfo(**json.loads(a.info))
         cmds = engine_stage_commands(Path(a.input), Path(a.output), params, Path(a.cube), info, ffmpeg_bin=a.ffmpeg, device=a.device,
-                                     precision=a.precision)
+                                     precision=a.precision, chroma_loc=a.chroma_loc)
     except Exception as exc:
         print(f"Error: {exc}", flush=True)
         return 1
