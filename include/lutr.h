@@ -251,6 +251,33 @@ int lutr_apply_yuv_sited(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, in
  * (n = product of the tap sums of the subsampled axes: 2, 4, 8 or 16; formed in double, rounded once to float) */
 int lutr_yuv_constants_sited(const lutr_yuv_params *p, int chroma_loc, float out[32]);
 
+/* ---- output resize (the reference's `-s WxH` after its -vf chain, ffmpeg.py:312-313) ---- */
+/* Separable bicubic, B = 0, C = 0.6 (libswscale's SWS_BICUBIC defaults, which the ffmpeg CLI uses for -s; FFmpeg recall, unpinned):
+ * k(t) = 1.4|t|^3 - 2.4|t|^2 + 1 (|t| < 1), -0.6|t|^3 + 3|t|^2 - 4.8|t| + 2.4 (1 <= |t| < 2), 0 otherwise.  Per axis, with
+ * f = src / dst of the LUMA sizes for every plane and stretch = max(1, f): chroma sample j sits at luma coordinate 2^cs j + o
+ * (o = 0 co-sited, (2^cs - 1) / 2 interstitial), is mapped through luma's x -> (x + 0.5) f - 0.5 and back to a source chroma
+ * index x; it reads n = 2 ceil(2 stretch) samples floor(x) - n/2 + 1 + k weighted k((x_k - x) / stretch), normalised in double,
+ * rounded to Q14 (floor(w 16384 + 0.5)) and the residue added to the largest tap (the first on a tie): every row sums to 16384.
+ * Limits per axis: 1/8 <= dst / src <= 16.  Integer arithmetic at output depth d:
+ *   t = (sum w s + 2^(d-3)) >> (d-2);  v = sum w t;  out = clamp((v + 2^(29-d)) >> (30-d), 0, 2^d - 1). */
+
+/* Host only (no context, no GPU): the table of one axis of one plane.  src / dst are luma sizes, cs = 0 | 1 the plane's log2
+ * subsampling on this axis, cosited = 1 for a co-sited chroma axis (ignored when cs == 0).  *ntaps = n; start (ceil(dst / 2^cs)
+ * entries: the first source index, unclamped) and weights (ceil(dst / 2^cs) * n, row-major) are filled when not NULL.
+ * LUTR_EINVAL outside the limits. */
+int lutr_resize_filter(int src, int dst, int cs, int cosited, int *start, int16_t *weights, int *ntaps);
+
+enum lutr_resize_family { LUTR_RESIZE_YUV = 0, LUTR_RESIZE_GBR = 1 };
+
+/* Resize nframes frames of three planes from sw x sh to dw x dh (luma sizes; chroma planes are ceil(size / 2^cs)) at `depth`
+ * (8 -> uint8, 9..16 -> uint16 LE).  family LUTR_RESIZE_YUV: planar 4:2:0 / 4:2:2 / 4:4:4 (csx, csy), chroma siting from
+ * chroma_loc per axis as in lutr_apply_yuv_sited (REPLICATE = interstitial on every subsampled axis); LUTR_RESIZE_GBR: gbrp,
+ * csx = csy = 0.  Source indices clamp to the plane.  Not in place: the bounding byte range of every source plane must be
+ * disjoint from that of every destination plane (the rule of lutr_apply_yuv_sited).  Tables are built on the host once per axis
+ * geometry and kept in the context.  Asynchronous on the context's stream; the last kernel is "k_resize<8|16>". */
+int lutr_resize_planes(lutr_ctx *ctx, int family, int depth, int csx, int csy, int chroma_loc, int sw, int sh, int dw, int dh,
+                       int nframes, const lutr_planes *src, lutr_planes *dst);
+
 /* zscale_dither of the reference (models.py:46; the filter `zscale=dither=error_diffusion`, ffmpeg.py:305-307) */
 enum lutr_dither { LUTR_DITHER_NONE = 0, LUTR_DITHER_ERROR_DIFFUSION = 1 };
 

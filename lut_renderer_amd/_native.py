@@ -25,6 +25,8 @@ PRECISION = {"strict": 0, "fast": 1, "fma32": 2}
 CHROMA_LOC = {"left": 1, "center": 2, "topleft": 3}
 CHROMA_REPLICATE = 0
 BCAST_FORCE_PEER_COPY = 1
+#: enum lutr_resize_family
+RESIZE_FAMILY = {"yuv": 0, "gbr": 1}
 
 #: every symbol include/lutr.h declares (tests check the library exports each one)
 SYMBOLS = (
@@ -34,7 +36,7 @@ SYMBOLS = (
     "lutr_ctx_set_lut", "lutr_ctx_lut_alloc", "lutr_ctx_lut_device", "lutr_ctx_lut_seal",
     "lutr_lattice_bytes", "lutr_lut_broadcast", "lutr_lut_broadcast_ex",
     "lutr_apply_planar_rgb", "lutr_apply_packed_rgb", "lutr_apply_yuv", "lutr_apply_yuv_dither",
-    "lutr_apply_yuv_sited", "lutr_yuv_constants_sited",
+    "lutr_apply_yuv_sited", "lutr_yuv_constants_sited", "lutr_resize_filter", "lutr_resize_planes",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
 )
 
@@ -128,6 +130,8 @@ def load() -> C.CDLL:
     lib.lutr_apply_yuv_sited.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes),
                                          C.POINTER(Planes), ci, ci]
     lib.lutr_yuv_constants_sited.argtypes = [C.POINTER(YuvParams), ci, C.POINTER(C.c_float)]
+    lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
+    lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]
     lib.lutr_ctx_set_variant.argtypes = [vp, ci]
     lib.lutr_ctx_set_precision.argtypes = [vp, ci]
     lib.lutr_ctx_last_kernel.argtypes = [vp]
@@ -136,6 +140,20 @@ def load() -> C.CDLL:
     lib.lutr_yuv_constants.argtypes = [C.POINTER(YuvParams), C.POINTER(C.c_float)]
     _lib = lib
     return lib
+
+
+def resize_filter(src: int, dst: int, cs: int = 0, cosited: bool = False):
+    """lutr_resize_filter (host only): (start [n_out] int32, weights [n_out, taps] int16) of one axis of one plane."""
+    import numpy as np
+    lib = load()
+    taps = C.c_int()
+    check(lib.lutr_resize_filter(src, dst, cs, int(cosited), None, None, C.byref(taps)))
+    n_out = (dst + (1 << cs) - 1) >> cs
+    start = np.zeros(n_out, np.int32)
+    w = np.zeros((n_out, taps.value), np.int16)
+    check(lib.lutr_resize_filter(src, dst, cs, int(cosited), start.ctypes.data_as(C.POINTER(C.c_int)),
+                                 w.ctypes.data_as(C.POINTER(C.c_int16)), C.byref(taps)))
+    return start, w
 
 
 def check(rc: int) -> None:

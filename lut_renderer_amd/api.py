@@ -104,7 +104,8 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               height: Optional[int] = None, input_matrix: str = "auto", colorspace: Optional[str] = None,
               color_range: Optional[str] = None, output_tags: str = "bt709", out_pix_fmt: Optional[str] = None,
               zscale_dither: str = "none", out: Optional[Sequence] = None, engine=None,
-              devices: Sequence[int] = (0,), precision: str = "strict", chroma_loc: Optional[str] = None):
+              devices: Sequence[int] = (0,), precision: str = "strict", chroma_loc: Optional[str] = None,
+              resolution: Optional[str] = None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  Returns (planes_out, tags) where `tags` is the colour
     metadata the reference would write for this policy (None = inherit / none).
@@ -124,10 +125,23 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
 
     `chroma_loc` is an engine setting too: None (default) replicates chroma over its block before the LUT and takes the
     block mean after it; "left" | "center" | "topleft" (ffprobe's chroma_location) resample chroma bilinearly at that
-    siting (always strict arithmetic, no in-place output, not with error-diffusion dither)."""
+    siting (always strict arithmetic, no in-place output, not with error-diffusion dither).
+
+    `resolution` is `ProcessingParams.resolution`, a "WxH" string as ffmpeg's `-s` takes it: the output planes are resized to
+    that size on the GPU after everything else, and `out` must have that size.  One device only (no
+    LutEngineGroup): a row-sharded resize would need halos between the devices."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
+    out_size = None
+    if resolution is not None:
+        from .engine import parse_size
+        if not isinstance(resolution, str):
+            raise ValueError(f"resolution is a 'WxH' string, got {resolution!r}")
+        out_size = parse_size(resolution)
+        from .multigpu import LutEngineGroup
+        if isinstance(engine, LutEngineGroup) or (engine is None and len(devices) > 1):
+            raise ValueError("resolution needs a single device")
     if width is not None and planes[0].shape[-1] != width or height is not None and planes[0].shape[-2] != height:
         raise ValueError("plane shape does not match width/height")
     params = ProcessingParams(lut_interp=interp, lut_input_matrix=input_matrix, lut_output_tags=output_tags,
@@ -146,6 +160,8 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     check_chroma_loc(chroma_loc, kw["dither"])
     if chroma_loc is not None:
         kw["chroma_loc"] = chroma_loc
+    if out_size is not None:
+        kw["out_size"] = out_size
     own = engine is None
     eng = engine if engine is not None else _cached_engine(devices)
     lut = None

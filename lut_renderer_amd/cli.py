@@ -59,6 +59,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--chroma-loc", default=None, choices=["left", "center", "topleft"],
                     help="engine setting: resample chroma bilinearly at this siting (ffprobe's chroma_location) instead of "
                          "replicating it over its block; strict arithmetic")
+    ap.add_argument("--out-size", default=None, metavar="WxH",
+                    help="engine setting: resize the output frames to WxH on the GPU after the LUT (the reference's -s, "
+                         "DESIGN.md 3.7); frames on -o have this size")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("-y", action="store_true", help="overwrite the output (ffmpeg's -y)")
@@ -85,6 +88,9 @@ def plan_from_args(args):
         from .engine import check_chroma_loc
         check_chroma_loc(args.chroma_loc, kw.get("dither", "none"))
         kw["chroma_loc"] = args.chroma_loc
+    if getattr(args, "out_size", None):
+        from .engine import parse_size
+        parse_size(args.out_size)
     return plan, kw, w, h
 
 
@@ -112,7 +118,7 @@ def main(argv=None) -> int:
         eng.set_precision(args.precision)
         eng.set_lut(read_lut(args.cube))
         pix_fmt, out_fmt = kw.pop("pix_fmt"), kw.pop("out_pix_fmt")
-        pipe = HostPipeline(eng, pix_fmt, w, h, batch=args.batch, out_pix_fmt=out_fmt, **kw)
+        pipe = HostPipeline(eng, pix_fmt, w, h, batch=args.batch, out_pix_fmt=out_fmt, out_size=args.out_size, **kw)
         fb = pipe.fin.frame_bytes
         if piped_in:
             total = None if args.duration is None else max(1, int(round(args.duration * args.fps)))

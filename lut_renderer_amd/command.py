@@ -250,7 +250,8 @@ def build_pipeline(task: Task, ffmpeg_bin: str = "ffmpeg") -> List[CommandStage]
 # ---------------------------------------------------------------- engine twin
 def engine_command(source: Path, output: Path, params: ProcessingParams, lut_path: Path,
                    source_info: VideoInfo, python_bin: Optional[str] = None, device: int = 0,
-                   notes: Optional[List[str]] = None, precision: str = "strict", chroma_loc: Optional[str] = None) -> List[str]:
+                   notes: Optional[List[str]] = None, precision: str = "strict", chroma_loc: Optional[str] = None,
+                   gpu_resize: bool = False) -> List[str]:
     """`build_command`'s twin for the LUT stage alone: the argv of the ENGINE CLI (`python -m lut_renderer_amd.cli`)
     that applies exactly the chain `build_command` would put into `-vf` -- the same `LutPlan`, rendered as CLI options
     instead of as a filter string (ffmpeg.py:195-247, :287-310).  `source` / `output` are rawvideo files (or `-`) in
@@ -258,7 +259,9 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     unchanged (same `Duration:` / `time=` / exit-code / SIGTERM contract).  `notes` receives the plan's notes, like
     `build_command`'s out-parameter.  The copy guard of ffmpeg.py:255-256 applies: a LUT stage cannot be a stream copy.
     `precision` is the engine's own setting (`--precision`, default strict; the reference's records have no such field), and
-    so is `chroma_loc` (`--chroma-loc`, rendered only when given: None keeps the replicating chroma contract)."""
+    so is `chroma_loc` (`--chroma-loc`, rendered only when given: None keeps the replicating chroma contract).
+    `gpu_resize` with `params.resolution` set moves the reference's `-s WxH` into the engine (`--out-size`); the
+    output format must then be planar (ValueError for packed formats).  False (default) leaves the argv as it was."""
     import sys as _sys
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
@@ -300,7 +303,19 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
         if "--zscale-dither" in cmd:
             raise ValueError("error-diffusion dither is not defined with sited chroma resampling (chroma_loc)")
         cmd += ["--chroma-loc", chroma_loc]
+    if gpu_resize and params.resolution:
+        out_fmt = pix_fmt or str(source_info.pix_fmt)
+        if not _PLANAR_RE.match(out_fmt):
+            raise ValueError(f"gpu_resize needs a planar output format, not '{out_fmt}' (keep -s on the encoder)")
+        if not _SIZE_RE.match(params.resolution):
+            raise ValueError(f"bad resolution '{params.resolution}' (expected WxH)")
+        cmd += ["--out-size", params.resolution]
     return cmd
+
+
+#: planar formats the engine's resize takes; packed RGB keeps -s on the encoder
+_PLANAR_RE = re.compile(r"^(yuvj?(420|422|444)p|gbrp)(\d+)?(le)?$")
+_SIZE_RE = re.compile(r"^[1-9][0-9]*x[1-9][0-9]*$")
 
 
 def fps_rational(fps) -> str:

@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -176,6 +177,69 @@ int make_yuv_consts_sited(const lutr_yuv_params &p, int loc, YuvConsts *o)
     return LUTR_OK;
 }
 
+
+// ---------------------------------------------------------------- output resize tables
+// The bicubic of libswscale's SWS_BICUBIC defaults (B = 0, C = 0.6).  Evaluated in this exact order: tests/_resize_twin.py
+// repeats it operation for operation in double.
+static double bicubic_k(double t)
+{
+    const double a = std::fabs(t);
+    if (a < 1.0) return 1.4 * a * a * a - 2.4 * a * a + 1.0;
+    if (a < 2.0) return -0.6 * a * a * a + 3.0 * a * a - 4.8 * a + 2.4;
+    return 0.0;
+}
+
+// Taps per output sample for a luma ratio src -> dst (no checks): 2 * ceil(2 * max(1, src / dst)).
+static int resize_taps(int src, int dst)
+{
+    const double f = (double)src / (double)dst, stretch = f > 1.0 ? f : 1.0;
+    return 2 * (int)std::ceil(2.0 * stretch);
+}
+
+// One axis of one plane: src / dst are LUMA sizes, cs = log2 subsampling of this plane's axis, cosited = chroma sample j sits on
+// luma 2^cs j (else halfway across its block).  start[dst_plane], w[dst_plane * taps].  LUTR_EINVAL when the limits fail.
+static int resize_table(int src, int dst, int cs, int cosited, std::vector<int> *start, std::vector<int> *w, int *taps)
+{
+    if (src < 1 || dst < 1 || cs < 0 || cs > 1 || (long long)dst * 8 < src || dst > 16LL * src) {
+        set_error("resize %d -> %d (subsampling %d) outside the limits 1/8 <= dst/src <= 16", src, dst, cs);
+        return LUTR_EINVAL;
+    }
+    const int n = resize_taps(src, dst);
+    const int dplane = (dst + (1 << cs) - 1) >> cs;
+    const double f = (double)src / (double)dst, stretch = f > 1.0 ? f : 1.0;
+    const double step = (double)(1 << cs), o = cosited ? 0.0 : (step - 1.0) / 2.0;
+    start->assign(dplane, 0);
+    w->assign((size_t)dplane * n, 0);
+    std::vector<double> wd(n);
+    for (int j = 0; j < dplane; j++) {
+        const double X = (step * j + o + 0.5) * f - 0.5;
+        const double x = (X - o) / step;
+        const int first = (int)std::floor(x) - n / 2 + 1;
+        double sum = 0.0;
+        for (int k = 0; k < n; k++) {
+            wd[k] = bicubic_k(((double)(first + k) - x) / stretch);
+            sum += wd[k];
+        }
+        int *q = w->data() + (size_t)j * n;
+        int total = 0, big = 0, mag = 0;
+        for (int k = 0; k < n; k++) {
+            q[k] = (int)std::floor(wd[k] / sum * 16384.0 + 0.5);
+            total += q[k];
+            if (q[k] > q[big]) big = k;
+        }
+        q[big] += 16384 - total;
+        for (int k = 0; k < n; k++) mag += q[k] < 0 ? -q[k] : q[k];
+        // |v| < 2^31 in the vertical pass needs sum |w| <= 1.35 * 2^14
+        if (mag > 22118) {
+            set_error("resize %d -> %d: weight magnitude %d exceeds 1.35 * 2^14", src, dst, mag);
+            return LUTR_EINVAL;
+        }
+        (*start)[j] = first;
+    }
+    *taps = n;
+    return LUTR_OK;
+}
+
 }  // namespace lutr
 
 using namespace lutr;
@@ -218,6 +282,13 @@ struct lutr_ctx {
     // lutr_lut_broadcast: copies other contexts are still reading out of THIS context's lattice (one event per receiver,
     // recorded on the receiver's stream behind its copy).  The lattice must not be overwritten or freed before they finish.
     std::vector<std::pair<int, hipEvent_t>> readers;      // (receiver's device, event)
+    // output resize (lutr_resize_planes): Q14 tables per axis geometry, uploaded once and kept
+    struct RzTable {
+        int src, dst, cs, cosited, taps;
+        int span64, span32, span16;  // most source samples an output tile of 64 (32, 16) samples reads
+        int *dev;                    // dst start words, then dst * taps weights (int32)
+    };
+    std::vector<RzTable> rz_tables;
 };
 
 // Wait for every peer copy that reads this context's lattice, then forget the events.
@@ -330,6 +401,7 @@ void lutr_ctx_destroy(lutr_ctx *c)
     if (c->lat) (void)hipFree(c->lat);
     if (c->stats) (void)hipFree(c->stats);
     if (c->fscratch) (void)hipFree(c->fscratch);
+    for (auto &t : c->rz_tables) (void)hipFree(t.dev);
     if (c->queue) (void)hipFree(c->queue);
     if (c->done) (void)hipEventDestroy(c->done);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -912,6 +984,146 @@ int lutr_apply_yuv_dither(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
     FloatPlanes F{c->fscratch, c->fscratch + ny, c->fscratch + ny + nc};
     return finish_launch(c, launch_yuv_dither(c->stream, L, K, P, G, F, LUTR_FMT_DEPTH(p->fmt_in),
                                               LUTR_FMT_DEPTH(p->fmt_out), csx, csy, interp));
+}
+
+
+int lutr_resize_filter(int src, int dst, int cs, int cosited, int *start, int16_t *weights, int *ntaps)
+{
+    if (!ntaps) { set_error("lutr_resize_filter: null ntaps"); return LUTR_EINVAL; }
+    std::vector<int> st, w;
+    int n = 0;
+    const int rc = resize_table(src, dst, cs, cosited, &st, &w, &n);
+    if (rc) return rc;
+    *ntaps = n;
+    if (start) std::memcpy(start, st.data(), st.size() * sizeof(int));
+    if (weights)
+        for (size_t i = 0; i < w.size(); i++) weights[i] = (int16_t)w[i];
+    return LUTR_OK;
+}
+
+// The device table of one axis geometry, built and uploaded on first use (asynchronously, on the context's stream; the host
+// copy is freed only after the upload has finished).
+static int rz_table(lutr_ctx *c, int src, int dst, int cs, int cosited, lutr_ctx::RzTable *out)
+{
+    for (auto &t : c->rz_tables)
+        if (t.src == src && t.dst == dst && t.cs == cs && t.cosited == cosited) { *out = t; return LUTR_OK; }
+    std::vector<int> st, w;
+    int n = 0;
+    if (const int rc = resize_table(src, dst, cs, cosited, &st, &w, &n)) return rc;
+    // start is non-decreasing: the first and the last sample of a tile decide its footprint
+    const int m = (int)st.size();
+    int span[3] = {0, 0, 0};
+    for (int e = 0; e < 3; e++)
+        for (int u0 = 0, len = 64 >> e; u0 < m; u0 += len) span[e] = std::max(span[e], st[std::min(u0 + len, m) - 1] + n - st[u0]);
+    std::vector<int> host(st);
+    host.insert(host.end(), w.begin(), w.end());
+    void *p = nullptr;
+    hipError_t e = hipMalloc(&p, host.size() * sizeof(int));
+    if (e != hipSuccess) { set_error("hipMalloc(resize table): %s", hipGetErrorString(e)); return LUTR_ENOMEM; }
+    e = hipMemcpy(p, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(p); return hip_fail(e, "hipMemcpy(resize table)"); }
+    c->rz_tables.push_back({src, dst, cs, cosited, n, span[0], span[1], span[2], (int *)p});
+    *out = c->rz_tables.back();
+    return LUTR_OK;
+}
+
+int lutr_resize_planes(lutr_ctx *c, int family, int depth, int csx, int csy, int chroma_loc, int sw, int sh, int dw, int dh,
+                       int nframes, const lutr_planes *src, lutr_planes *dst)
+{
+    if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
+    if (family != LUTR_RESIZE_YUV && family != LUTR_RESIZE_GBR) { set_error("unknown plane family %d", family); return LUTR_EINVAL; }
+    if (depth < 8 || depth > 16) { set_error("unsupported depth %d", depth); return LUTR_EINVAL; }
+    if (csx < 0 || csx > 1 || csy < 0 || csy > 1 || (family == LUTR_RESIZE_GBR && (csx || csy))) {
+        set_error("unsupported chroma subsampling %d x %d", csx, csy);
+        return LUTR_EINVAL;
+    }
+    if (chroma_loc < LUTR_CHROMA_REPLICATE || chroma_loc > LUTR_CHROMA_TOPLEFT) {
+        set_error("unknown chroma location %d", chroma_loc);
+        return LUTR_EINVAL;
+    }
+    if (sw < 1 || sh < 1 || dw < 1 || dh < 1 || nframes < 0) {
+        set_error("bad geometry %dx%d -> %dx%d, nframes %d", sw, sh, dw, dh, nframes);
+        return LUTR_EINVAL;
+    }
+    if ((long long)dw * 8 < sw || dw > 16LL * sw || (long long)dh * 8 < sh || dh > 16LL * sh) {
+        set_error("resize %dx%d -> %dx%d outside the limits 1/8 <= dst/src <= 16 per axis", sw, sh, dw, dh);
+        return LUTR_EINVAL;
+    }
+    if (nframes == 0) return LUTR_OK;
+    for (int i = 0; i < 3; i++)
+        if (!src->data[i] || !dst->data[i]) { set_error("null plane %d", i); return LUTR_EINVAL; }
+    const int es = depth > 8 ? 2 : 1;
+    int psw[3], psh[3], pdw[3], pdh[3];
+    for (int i = 0; i < 3; i++) {
+        const int cx = i ? csx : 0, cy = i ? csy : 0;
+        psw[i] = (sw + (1 << cx) - 1) >> cx; psh[i] = (sh + (1 << cy) - 1) >> cy;
+        pdw[i] = (dw + (1 << cx) - 1) >> cx; pdh[i] = (dh + (1 << cy) - 1) >> cy;
+    }
+    // every destination sample reads a neighbourhood of source samples: no destination may overlap a source
+    for (int i = 0; i < 3; i++) {
+        uintptr_t slo, shi;
+        plane_span(src->data[i], src->stride[i], src->frame_stride[i], psh[i], (long long)psw[i] * es, nframes, &slo, &shi);
+        for (int j = 0; j < 3; j++) {
+            uintptr_t dlo, dhi;
+            plane_span(dst->data[j], dst->stride[j], dst->frame_stride[j], pdh[j], (long long)pdw[j] * es, nframes, &dlo, &dhi);
+            if (slo < dhi && dlo < shi) {
+                set_error("resize cannot run in place: the byte range of source plane %d overlaps that of destination plane %d (bounding ranges over all rows and frames must be disjoint)", i, j);
+                return LUTR_EINVAL;
+            }
+        }
+    }
+    if (es == 2)
+        for (int i = 0; i < 3; i++)
+            if (((uintptr_t)src->data[i] | (uintptr_t)dst->data[i] | (uintptr_t)src->stride[i] | (uintptr_t)dst->stride[i] |
+                 (nframes > 1 ? (uintptr_t)src->frame_stride[i] | (uintptr_t)dst->frame_stride[i] : 0)) & 1) {
+                set_error("16-bit planes need 2-byte aligned rows");
+                return LUTR_EINVAL;
+            }
+    const int cox = chroma_loc == LUTR_CHROMA_LEFT || chroma_loc == LUTR_CHROMA_TOPLEFT;
+    const int coy = chroma_loc == LUTR_CHROMA_TOPLEFT;
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->rz_tables.size() > 58) {              // many geometries in one context: start over (a call adds at most 6 tables)
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (auto &t : c->rz_tables) (void)hipFree(t.dev);
+        c->rz_tables.clear();
+    }
+    RzArgs A{};
+    A.depth = depth;
+    lutr_ctx::RzTable tx[3], ty[3];
+    for (int i = 0; i < 3; i++) {
+        const int cx = i ? csx : 0, cy = i ? csy : 0;
+        if (const int rc = rz_table(c, sw, dw, cx, cx ? cox : 0, &tx[i])) return rc;
+        if (const int rc = rz_table(c, sh, dh, cy, cy ? coy : 0, &ty[i])) return rc;
+        A.spx = std::max(A.spx, tx[i].span64);
+        A.nx_max = std::max(A.nx_max, tx[i].taps);
+        A.ny_max = std::max(A.ny_max, ty[i].taps);
+    }
+    A.spx = (A.spx + 1) & ~1;
+    A.rows = 1;
+    // the tallest tile whose LDS stays within 40 KiB, so that several workgroups share a CU (64 rows on upscales, 32 for 2:1 and
+    // 3:1, 16 for stronger vertical reductions)
+    for (A.th = kRzTileHMax; ; A.th /= 2) {
+        A.spy = 0;
+        for (int i = 0; i < 3; i++) A.spy = std::max(A.spy, A.th == 64 ? ty[i].span64 : A.th == 32 ? ty[i].span32 : ty[i].span16);
+        if (A.th == 16 || resize_lds_bytes(A) <= 40960) break;
+    }
+    int tile0 = 0;
+    for (int i = 0; i < 3; i++) {
+        RzPlane &P = A.p[i];
+        P.s = (const uint8_t *)src->data[i]; P.d = (uint8_t *)dst->data[i];
+        P.ss = src->stride[i]; P.ds = dst->stride[i]; P.sfs = src->frame_stride[i]; P.dfs = dst->frame_stride[i];
+        P.sw = psw[i]; P.sh = psh[i]; P.dw = pdw[i]; P.dh = pdh[i];
+        P.nx = tx[i].taps; P.ny = ty[i].taps;
+        P.xs = tx[i].dev; P.xw = tx[i].dev + pdw[i];
+        P.ys = ty[i].dev; P.yw = ty[i].dev + pdh[i];
+        P.tiles_x = (pdw[i] + kRzTileW - 1) / kRzTileW;
+        P.tile0 = tile0;
+        tile0 += P.tiles_x * ((pdh[i] + A.th - 1) / A.th);
+    }
+    A.tiles_per_frame = tile0;
+    const char *name = launch_resize(c->stream, A, nframes);
+    if (!name) { set_error("resize launch too large (split the batch)"); return LUTR_EINVAL; }
+    return finish_launch(c, name);
 }
 
 }  // extern "C"

@@ -121,6 +121,32 @@ LUTR_T2_DECL(w10_c11) LUTR_T2_DECL(w10_c10) LUTR_T2_DECL(w10_c00)
 // down-sampling's 1/n in cbr..crb (make_yuv_consts_sited); nullptr = the launch is too large
 const char *launch_yuv_sited(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
                              int din, int dout, int csy, int loc, int mode);
+// output resize (lutr_resize.hip): one plane's geometry and Q14 tables (device), for a grid of output tiles of
+// 64 columns x RzArgs::th rows (64, 32 or 16: the tallest whose LDS fits)
+constexpr int kRzTileW = 64, kRzTileHMax = 64;
+constexpr int kRzRows = 8, kRzU = 4;     // staged source rows per wave and step (most); samples per lane and row in one load batch
+struct RzPlane {
+    const uint8_t *s;
+    uint8_t *d;
+    long long ss, ds, sfs, dfs;      // row / frame strides, bytes
+    int sw, sh, dw, dh;              // plane sizes, samples
+    const int *xs, *xw;              // per output column: first tap (unclamped), nx weights ([column][tap])
+    const int *ys, *yw;              // per output row: first tap, ny weights
+    int nx, ny;
+    int tiles_x, tile0;              // tile columns of this plane; index of its first tile inside a frame
+};
+struct RzArgs {
+    RzPlane p[3];
+    int tiles_per_frame;
+    int depth;                       // 8..16 (8: uint8 planes, else uint16)
+    int spx, spy;                    // largest footprint of a tile over the three planes: source columns, source rows
+    int nx_max, ny_max;
+    int th;                          // output rows per tile
+    int rows;                        // staged source rows per wave and step, 1..kRzRows (set by launch_resize)
+};
+size_t resize_lds_bytes(const RzArgs &A);
+// nullptr = too many tiles, or a footprint that does not fit the workgroup's LDS
+const char *launch_resize(hipStream_t st, RzArgs A, int nframes);
 // fp16 lattice of the fast variant and fp32 pre-multiplied lattice of the fma32 variant (lutr_lat16.hip)
 void launch_make_lat16(hipStream_t st, const float4 *lat, uint2 *out, size_t nodes, float m);
 void launch_make_latm(hipStream_t st, const float4 *lat, float4 *out, size_t nodes, float m);

@@ -84,6 +84,56 @@ def check_chroma_loc(chroma_loc: Optional[str], dither: str = "none") -> None:
         raise ValueError("error-diffusion dither is not defined with sited chroma resampling (chroma_loc)")
 
 
+#: frames per LUT launch when apply_yuv / apply_rgb resize (`out_size`): the LUT writes a chunk into the engine's scratch at the
+#: source size and the resize reads it back while it is still in the Infinity Cache.  LUTR_RESIZE_CHUNK overrides.
+RESIZE_CHUNK = 16
+
+
+def resize_chunk_default() -> int:
+    import os
+    v = os.environ.get("LUTR_RESIZE_CHUNK")
+    return max(1, int(v)) if v else RESIZE_CHUNK
+
+
+def parse_size(size) -> Tuple[int, int]:
+    """(w, h) from a (w, h) pair or a "WxH" string as ffmpeg's -s takes it; ValueError for anything else."""
+    if isinstance(size, str):
+        m = re.fullmatch(r"([1-9][0-9]*)x([1-9][0-9]*)", size)
+        if not m:
+            raise ValueError(f"bad size '{size}' (expected WxH, e.g. 1920x1080)")
+        return int(m.group(1)), int(m.group(2))
+    try:
+        w, h = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"bad size {size!r} (expected (w, h) or 'WxH')") from None
+    if w < 1 or h < 1:
+        raise ValueError(f"bad size {size!r}")
+    return w, h
+
+
+def _byte_range(t: torch.Tensor) -> Tuple[int, int]:
+    lo = hi = t.data_ptr()
+    for n, st in zip(t.shape, t.stride()):
+        if st >= 0:
+            hi += (n - 1) * st * t.element_size()
+        else:
+            lo += (n - 1) * st * t.element_size()
+    return lo, hi + t.element_size()
+
+
+def _check_not_in_place(src: Sequence[torch.Tensor], dst: Sequence[torch.Tensor]) -> None:
+    for a in src:
+        alo, ahi = _byte_range(a)
+        for b in dst:
+            blo, bhi = _byte_range(b)
+            if alo < bhi and blo < ahi:
+                raise ValueError("a resize cannot run in place: destination planes must not overlap the source planes")
+
+
+def _frames3(planes: Sequence[torch.Tensor]) -> list:
+    return [t if t.dim() == 3 else t.unsqueeze(0) for t in planes]
+
+
 def _check_planes(planes: Sequence[torch.Tensor], fmt: PixFmt, w: int, h: int, what: str) -> None:
     """The C-ABI takes bare pointers and cannot know buffer sizes: every plane must have exactly the shape and the
     element size `fmt` implies for a w x h frame, or the kernels would read or write outside it."""
@@ -153,6 +203,7 @@ class LutEngine:
         self._lock = threading.RLock()
         self.precision = "strict"
         self._applied_lut = None          # the CubeLut object apply_lut uploaded last (its upload-skipping shortcut)
+        self._rz_scratch = None           # source-size output of the LUT ahead of a resize: (key, [3 planes])
 
     # -- lifetime ---------------------------------------------------------
     def close(self) -> None:
@@ -281,14 +332,19 @@ class LutEngine:
 
     # -- apply ------------------------------------------------------------
     def apply_rgb(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *,
-                  depth: int, interp: str = "tetrahedral", row0: int = 0, rows: Optional[int] = None):
-        """lut3d on planar RGB; planes in gbrp order (G, B, R), each [H,W] or [F,H,W]."""
-        if dst is None:
-            dst = [torch.empty_like(t) for t in src]
+                  depth: int, interp: str = "tetrahedral", row0: int = 0, rows: Optional[int] = None,
+                  out_size=None, resize_chunk: Optional[int] = None):
+        """lut3d on planar RGB; planes in gbrp order (G, B, R), each [H,W] or [F,H,W].
+        out_size = (w, h) or "WxH" resizes the LUT's output to that size (whole frames, not in place)."""
         if not 8 <= int(depth) <= 16:
             raise ValueError(f"unsupported depth {depth}")
         h, w = src[0].shape[-2], src[0].shape[-1]
         fmt = PixFmt(f"gbrp{depth}", "gbr", int(depth), 0, 0, True)
+        if out_size is not None:
+            return self._lut_then_resize(src, dst, fmt, fmt, w, h, out_size, row0, rows, resize_chunk, None,
+                                         lambda s_, d_: self.apply_rgb(s_, d_, depth=depth, interp=interp))
+        if dst is None:
+            dst = [torch.empty_like(t) for t in src]
         _check_planes(src, fmt, w, h, "source")
         _check_planes(dst, fmt, w, h, "destination")
         s, nf = _planes_struct(src, self.device)
@@ -300,6 +356,70 @@ class LutEngine:
             self._bind_stream()
             _native.check(self._lib.lutr_apply_planar_rgb(
                 self._ctx, depth, _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(d), row0, rows))
+        return dst
+
+    # -- resize -----------------------------------------------------------
+    def resize(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, size,
+               chroma_loc: Optional[str] = None):
+        """Resize planar frames (Y, Cb, Cr or gbrp's G, B, R; each [H,W] or [F,H,W]) to `size` = (w, h) or "WxH" with the
+        engine's separable bicubic (lutr_resize_planes).  `chroma_loc` sites the chroma samples (None =
+        interstitial, the block centre).  Not in place; packed formats are a ValueError."""
+        fmt = parse_pix_fmt(pix_fmt.replace("yuvj", "yuv"))
+        loc = chroma_loc_code(chroma_loc)
+        dw, dh = parse_size(size)
+        sh, sw = src[0].shape[-2], src[0].shape[-1]
+        if dst is None:
+            dt = src[0].dtype
+            lead = tuple(src[0].shape[:-2])
+            dst = [torch.empty(lead + fmt.plane_shape(i, dw, dh), dtype=dt, device=self.device) for i in range(3)]
+        _check_planes(src, fmt, sw, sh, "source")
+        _check_planes(dst, fmt, dw, dh, "destination")
+        _check_not_in_place(src, dst)
+        s, nf = _planes_struct(src, self.device)
+        d, nfd = _planes_struct(dst, self.device)
+        if nf != nfd:
+            raise ValueError("src and dst disagree on the number of frames")
+        with self._lock:
+            self._bind_stream()
+            _native.check(self._lib.lutr_resize_planes(
+                self._ctx, _native.RESIZE_FAMILY[fmt.family], fmt.depth, fmt.csx, fmt.csy, loc, sw, sh, dw, dh, nf,
+                C.byref(s), C.byref(d)))
+        return dst
+
+    def _scratch(self, fmt: PixFmt, w: int, h: int, nframes: int, dtype) -> list:
+        """Engine-owned planes of `nframes` frames at w x h in `fmt` (kept for the next call of the same shape or smaller)."""
+        key = (fmt.name, w, h, dtype)
+        if self._rz_scratch is None or self._rz_scratch[0] != key or self._rz_scratch[1][0].shape[0] < nframes:
+            self._rz_scratch = (key, [torch.empty((nframes,) + fmt.plane_shape(i, w, h), dtype=dtype, device=self.device)
+                                      for i in range(3)])
+        return [t[:nframes] for t in self._rz_scratch[1]]
+
+    def _lut_then_resize(self, src, dst, fin: PixFmt, fout: PixFmt, w: int, h: int, out_size, row0: int, rows, chunk,
+                         chroma_loc, lut_call):
+        """The composition of DESIGN.md 3.7: the LUT into engine scratch at the source size, then the resize into dst, a chunk
+        of frames at a time, both on the engine's stream with no host wait in between."""
+        dw, dh = parse_size(out_size)
+        if row0 != 0 or (rows is not None and rows != h):
+            raise ValueError("a resize (out_size) takes whole frames: row0 / rows are not supported with it")
+        if dst is None:
+            dt = torch.uint8 if fout.depth <= 8 else src[0].dtype if src[0].element_size() == 2 else torch.int16
+            lead = tuple(src[0].shape[:-2])
+            dst = [torch.empty(lead + fout.plane_shape(i, dw, dh), dtype=dt, device=self.device) for i in range(3)]
+        _check_planes(src, fin, w, h, "source")
+        _check_planes(dst, fout, dw, dh, "destination")
+        _check_not_in_place(src, dst)
+        s3, d3 = _frames3(src), _frames3(dst)
+        nf = s3[0].shape[0]
+        if d3[0].shape[0] != nf:
+            raise ValueError("src and dst disagree on the number of frames")
+        chunk = resize_chunk_default() if chunk is None else max(1, int(chunk))
+        with self._lock:
+            tmp_all = self._scratch(fout, w, h, min(chunk, nf), d3[0].dtype)
+            for f0 in range(0, nf, chunk):
+                n = min(chunk, nf - f0)
+                tmp = [t[:n] for t in tmp_all]
+                lut_call([t[f0:f0 + n] for t in s3], tmp)
+                self.resize(tmp, [t[f0:f0 + n] for t in d3], pix_fmt=fout.name, size=(dw, dh), chroma_loc=chroma_loc)
         return dst
 
     def apply_packed(self, src: torch.Tensor, dst: Optional[torch.Tensor] = None, *, pix_fmt: str,
@@ -341,11 +461,15 @@ class LutEngine:
                   pix_fmt: str, interp: str = "tetrahedral", matrix_in: str = "bt709",
                   matrix_out: Optional[str] = None, range_src: str = "tv", range_in: Optional[str] = None,
                   range_out: str = "tv", lut_depth: Optional[int] = None, out_pix_fmt: Optional[str] = None,
-                  row0: int = 0, rows: Optional[int] = None, dither: str = "none", chroma_loc: Optional[str] = None):
+                  row0: int = 0, rows: Optional[int] = None, dither: str = "none", chroma_loc: Optional[str] = None,
+                  out_size=None, resize_chunk: Optional[int] = None):
         """Fused YUV -> RGB -> lut3d -> RGB -> YUV on planar frames (Y, Cb, Cr).
         dither="error_diffusion" (the reference's `zscale_dither`) dithers the final quantisation; whole frames only.
         chroma_loc ("left" | "center" | "topleft", ffprobe's chroma_location names) resamples chroma bilinearly at that
-        siting instead of replicating it (strict arithmetic, not in place, no dither).  None = replicate."""
+        siting instead of replicating it (strict arithmetic, not in place, no dither).  None = replicate.
+        out_size = (w, h) or "WxH" resizes the output planes to that size after everything else (the reference's `-s`,
+        DESIGN.md 3.7): the LUT writes `resize_chunk` frames at a time (default RESIZE_CHUNK) into engine scratch at the source
+        size and the resize reads them back; whole frames only, not in place.  The resize sites chroma by `chroma_loc`."""
         if dither not in _native.DITHER:
             raise ValueError(f"unknown dither mode '{dither}'")
         check_chroma_loc(chroma_loc, dither)
@@ -362,6 +486,12 @@ class LutEngine:
         p.range_in = _native.RANGE[range_in or range_src]
         p.range_out = _native.RANGE[range_out]
         h, w = src[0].shape[-2], src[0].shape[-1]
+        if out_size is not None:
+            kw = dict(pix_fmt=pix_fmt, interp=interp, matrix_in=matrix_in, matrix_out=matrix_out, range_src=range_src,
+                      range_in=range_in, range_out=range_out, lut_depth=lut_depth, out_pix_fmt=out_pix_fmt, dither=dither,
+                      chroma_loc=chroma_loc)
+            return self._lut_then_resize(src, dst, fin, fout, w, h, out_size, row0, rows, resize_chunk, chroma_loc,
+                                         lambda s_, d_: self.apply_yuv(s_, d_, **kw))
         if dst is None:
             dt = torch.uint8 if fout.depth <= 8 else src[0].dtype if src[0].element_size() == 2 else torch.int16
             lead = tuple(src[0].shape[:-2])

@@ -46,13 +46,15 @@ class StageCommands:
 
 def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, lut_path: Path, source_info: VideoInfo,
                           ffmpeg_bin: str = "ffmpeg", python_bin: Optional[str] = None, device: int = 0,
-                          precision: str = "strict", chroma_loc: Optional[str] = None) -> StageCommands:
+                          precision: str = "strict", chroma_loc: Optional[str] = None, gpu_resize: bool = False) -> StageCommands:
     """The three argv lists of one LUT stage.  Raises what `build_command` / `engine_command` raise (copy guard, missing
     geometry).  `chroma_loc` goes to the engine (`--chroma-loc`) and, as `-chroma_sample_location`, to the encoder, so the
-    output stream declares the siting the engine assumed."""
+    output stream declares the siting the engine assumed.  `gpu_resize` with `params.resolution` set resizes in the engine
+    (`--out-size`): the raw input's `-s` is then the target size and the encoder's own `-s` is dropped."""
     notes: List[str] = []
     engine = engine_command(Path("-"), Path("-"), params, lut_path, source_info, python_bin=python_bin, device=device, notes=notes,
-                            precision=precision, chroma_loc=chroma_loc)
+                            precision=precision, chroma_loc=chroma_loc, gpu_resize=gpu_resize)
+    resized = gpu_resize and bool(params.resolution)
     if source_info.duration:
         engine += ["--duration", f"{float(source_info.duration):.3f}"]
     decoder = [ffmpeg_bin, "-hide_banner", "-nostdin", "-i", str(source), "-map", "0:v:0", "-f", "rawvideo",
@@ -63,13 +65,17 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
         out_fmt = str(source_info.pix_fmt)
         if engine.count("--out-pix-fmt"):
             out_fmt = engine[engine.index("--out-pix-fmt") + 1]
-    raw_in = ["-f", "rawvideo", "-pix_fmt", out_fmt, "-s", f"{source_info.width}x{source_info.height}"]
+    raw_in = ["-f", "rawvideo", "-pix_fmt", out_fmt,
+              "-s", params.resolution if resized else f"{source_info.width}x{source_info.height}"]
     if source_info.fps:
         raw_in += ["-r", fps_rational(source_info.fps)]
     enc_notes: List[str] = []
     tail = build_command(Path("pipe:0"), output, params, lut_path=None, ffmpeg_bin=ffmpeg_bin, source_info=source_info,
                          notes=enc_notes)
     i = tail.index("-i")
+    if resized:                                   # the frames already have the size: no scaler on the encoder
+        j = tail.index("-s", i + 2)
+        del tail[j:j + 2]
     # input 0 = the engine's frames, input 1 = the source again for audio / subtitles / chapters / metadata (`?`: optional
     # streams; video is taken from the pipe only, so the source's picture is never decoded a second time)
     side = ["-i", str(source), "-map", "0:v:0", "-map", "1:a?", "-map", "1:s?", "-map_metadata", "1", "-map_chapters", "1"]
@@ -134,12 +140,13 @@ def main(argv=None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--precision", default="strict", choices=["strict", "fast", "fma32"], help="engine setting, see lut_renderer_amd.cli")
     ap.add_argument("--chroma-loc", default=None, choices=["left", "center", "topleft"], help="engine setting, see lut_renderer_amd.cli")
+    ap.add_argument("--gpu-resize", action="store_true", help="resize to the params' resolution in the engine (--out-size) instead of the encoder")
     a = ap.parse_args(argv)
     try:
         params = ProcessingParams.from_dict(json.loads(a.params))
         info = VideoInfo(**json.loads(a.info))
         cmds = engine_stage_commands(Path(a.input), Path(a.output), params, Path(a.cube), info, ffmpeg_bin=a.ffmpeg, device=a.device,
-                                     precision=a.precision, chroma_loc=a.chroma_loc)
+                                     precision=a.precision, chroma_loc=a.chroma_loc, gpu_resize=a.gpu_resize)
     except Exception as exc:
         print(f"Error: {exc}", flush=True)
         return 1

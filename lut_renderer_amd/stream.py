@@ -18,7 +18,7 @@ from typing import Callable, Iterable, Iterator, List, Optional
 import numpy as np
 import torch
 
-from .engine import LutEngine, PixFmt, parse_pix_fmt
+from .engine import LutEngine, PixFmt, parse_pix_fmt, parse_size
 
 
 @dataclass
@@ -60,12 +60,16 @@ class HostPipeline:
     """Apply the LUT to batches of host frames with copies overlapped against compute."""
 
     def __init__(self, engine: LutEngine, pix_fmt: str, width: int, height: int, batch: int = 8, slots: int = 3,
-                 out_pix_fmt: Optional[str] = None, **apply_kw):
+                 out_pix_fmt: Optional[str] = None, out_size=None, **apply_kw):
+        """`out_size` = (w, h) or "WxH": the engine resizes every frame to it and the output layout has that size."""
         self.eng = engine
         self.fin = FrameLayout(parse_pix_fmt(pix_fmt.replace("yuvj", "yuv")), width, height)
-        self.fout = FrameLayout(parse_pix_fmt(out_pix_fmt or pix_fmt.replace("yuvj", "yuv")), width, height)
+        ow, oh = (width, height) if out_size is None else parse_size(out_size)
+        self.fout = FrameLayout(parse_pix_fmt(out_pix_fmt or pix_fmt.replace("yuvj", "yuv")), ow, oh)
         self.batch, self.slots = int(batch), int(slots)
         self.kw = dict(apply_kw, pix_fmt=self.fin.fmt.name, out_pix_fmt=self.fout.fmt.name)
+        if out_size is not None:
+            self.kw["out_size"] = (ow, oh)
         dev = engine.device
         self.h_in = [torch.empty(self.batch * self.fin.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]
         self.h_out = [torch.empty(self.batch * self.fout.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]
