@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -279,6 +280,7 @@ struct lutr_ctx {
     int    pre_shared[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};     // per depth: the three tables agree and never fall (LutConsts::pre_shared)
     float  pre_kappa[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // ... and their largest step between neighbouring codes
     std::vector<float> pre_host[9];                         // ... and the shared table itself, codes 0 .. 2^depth - 1 (LutConsts::pre_host)
+    unsigned long long pre_gen[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // ... and its number (LutConsts::pre_gen, g_prelut_gen)
     // lutr_lut_broadcast: copies other contexts are still reading out of THIS context's lattice (one event per receiver,
     // recorded on the receiver's stream behind its copy).  The lattice must not be overwritten or freed before they finish.
     std::vector<std::pair<int, hipEvent_t>> readers;      // (receiver's device, event)
@@ -577,9 +579,15 @@ int lutr_ctx_set_prelut(lutr_ctx *c, const float *prelut, int size, const float 
 // The lattice coordinate of every integer code at this LUT depth with the prelut in front: FFmpeg's
 // prelut_interp_1d_linear on code * (1 / M), then * scale * (n - 1), clipped to [0, n - 1] -- per pixel in FFmpeg, per code here,
 // float for float the same operations (this file is compiled without contraction).  256 entries for 8-bit containers, else 65536.
-static int prelut_table(lutr_ctx *c, int depth, const float **dev, int *entries, int *shared, float *kappa, const float **host_tab)
+// Every table prelut_table builds gets a number of its own from this counter (never 0).  The tile launcher memoises the tube bound
+// it reads off a shared table under that number: a rebuilt table reuses the vector of the old one, and a new context may be handed
+// a freed one's memory, so the address says nothing about the contents.
+static std::atomic<unsigned long long> g_prelut_gen{0};
+
+static int prelut_table(lutr_ctx *c, int depth, const float **dev, int *entries, int *shared, float *kappa, const float **host_tab,
+                        unsigned long long *gen)
 {
-    *dev = nullptr; *entries = 0; *shared = 0; *kappa = 0.0f; *host_tab = nullptr;
+    *dev = nullptr; *entries = 0; *shared = 0; *kappa = 0.0f; *host_tab = nullptr; *gen = 0;
     if (!c->pre_size) return LUTR_OK;
     const int slot = depth - 8;
     if (slot < 0 || slot > 8) { set_error("prelut: LUT depth %d outside 8..16", depth); return LUTR_EINVAL; }
@@ -588,6 +596,7 @@ static int prelut_table(lutr_ctx *c, int depth, const float **dev, int *entries,
     if (c->pre_dev[slot]) {
         *dev = c->pre_dev[slot]; *shared = c->pre_shared[slot]; *kappa = c->pre_kappa[slot];
         *host_tab = c->pre_shared[slot] ? c->pre_host[slot].data() : nullptr;
+        *gen = c->pre_gen[slot];
         return LUTR_OK;
     }
     const int maxi = (1 << depth) - 1, pmax = c->pre_size - 1;
@@ -629,6 +638,8 @@ static int prelut_table(lutr_ctx *c, int depth, const float **dev, int *entries,
     if (same) c->pre_host[slot].assign(host.begin(), host.begin() + maxi + 1);
     *shared = c->pre_shared[slot]; *kappa = c->pre_kappa[slot];
     *host_tab = same ? c->pre_host[slot].data() : nullptr;
+    c->pre_gen[slot] = ++g_prelut_gen;
+    *gen = c->pre_gen[slot];
     return LUTR_OK;
 }
 
@@ -772,7 +783,8 @@ static const float4 *fma32_lattice(lutr_ctx *c, int depth)
 static int fill_lut(LutConsts *L, lutr_ctx *c, int depth)
 {
     const int maxi = (1 << depth) - 1;
-    const int rc = prelut_table(c, depth, &L->pre, &L->pre_stride, &L->pre_shared, &L->pre_kappa, &L->pre_host);
+    const int rc = prelut_table(c, depth, &L->pre, &L->pre_stride, &L->pre_shared, &L->pre_kappa, &L->pre_host,
+                                &L->pre_gen);
     if (rc) return rc;
     L->lat = c->lat;
     L->lat16 = nullptr;

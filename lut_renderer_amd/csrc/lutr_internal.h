@@ -41,6 +41,7 @@ struct LutConsts {
     int   pre_shared;    // 1: the three channels' tables are identical and non-decreasing over the codes 0 .. 2^depth - 1 (the usual
     float pre_kappa;     // cineSpace shaper): one coordinate table serves R, G and B; pre_kappa = the largest step between two codes (cells)
     const float *pre_host; // HOST copy of that shared table (2^depth entries; launcher only: the tube's bound is read off the curve itself)
+    unsigned long long pre_gen;  // a process-wide number of that table, new for every table built (launcher only: the key of the tube bound's memo)
 };
 
 // Constant block of the YUV contract; same fields, same order as the

@@ -1959,12 +1959,14 @@ static long long whole_strides(int n1, int node, long long room, int *A, int *B)
 // nearly flat inside a segment, a jump at every input point -- its largest step between two codes says nothing about the rise over
 // 100.  What the tube needs is D(d) = max over x of s(x + d) - s(x), the most the coordinate can rise over d codes: two channel codes at
 // most d apart then sit at most floor(D(d)) + 1 cells apart.  Returns the largest d with D(d) <= h - 0.002 (0 if none).
-static int prelut_tube_bound(const float *s, int maxi, int h)
+// The scan is O(2^depth * d), so the last result is kept, keyed by the table's number (LutConsts::pre_gen) -- not by its address,
+// which a context's next shaper at the same depth, or another context's table, may well reuse.
+static int prelut_tube_bound(const float *s, unsigned long long gen, int maxi, int h)
 {
-    struct Memo { const float *s; int maxi, h, d; float first, last; };
-    static thread_local Memo memo = {nullptr, 0, 0, 0, 0.0f, 0.0f};
+    struct Memo { unsigned long long gen; int maxi, h, d; };
+    static thread_local Memo memo = {0, 0, 0, 0};
     if (!s || maxi < 1) return 0;
-    if (memo.s == s && memo.maxi == maxi && memo.h == h && memo.first == s[1] && memo.last == s[maxi]) return memo.d;
+    if (gen && memo.gen == gen && memo.maxi == maxi && memo.h == h) return memo.d;
     const float lim = (float)h - 2e-3f;
     int d = 0;
     for (int cand = 1; cand <= maxi; cand++) {
@@ -1973,7 +1975,7 @@ static int prelut_tube_bound(const float *s, int maxi, int h)
         if (rise > lim) break;
         d = cand;
     }
-    memo = Memo{s, maxi, h, d, s[1], s[maxi]};
+    memo = Memo{gen, maxi, h, d};
     return d;
 }
 
@@ -2097,7 +2099,7 @@ const char *T2_ENTRY(hipStream_t st, const LutConsts &L, const YuvConsts &K, con
             const long long bytes = (long long)L.n1 * plane * node;
             const bool fits = bytes <= (long long)lds_block * tube_pct / 100 && (lds_block - bytes) / (node * LUTR_T2_WPB) >= min_win;
             float t = ((float)(h + 1) - slack) / kappa - 1.0f - eps;
-            if (L.pre) t = fits ? prelut_tube_bound(L.pre_host, (int)L.maxf, h) - 0.5f - eps : 0.0f;      // (a scan of the curve: memoised)
+            if (L.pre) t = fits ? prelut_tube_bound(L.pre_host, L.pre_gen, (int)L.maxf, h) - 0.5f - eps : 0.0f;      // (a scan of the curve: memoised)
             if (fits && t > 0.0f) {
                 tg.tube_h = h; tg.tube_t = t; tg.tube_plane = (int)plane; tube_bytes = bytes;
                 break;
