@@ -288,6 +288,29 @@ enum lutr_dither { LUTR_DITHER_NONE = 0, LUTR_DITHER_ERROR_DIFFUSION = 1 };
 int lutr_apply_yuv_dither(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int dither, int w, int h, int nframes,
                           const lutr_planes *src, const lutr_planes *dst);
 
+/* ---- chroma subsampling change (the reference's format=<pix_fmt> with another layout, ffmpeg.py:304-310) ---- */
+/* lutr_apply_yuv with fmt_in and fmt_out in any two of 4:2:0, 4:2:2 and 4:4:4 (4:4:0 is LUTR_EINVAL on either side), at any
+ * depth pair in 8..16.  Each source chroma sample is replicated over its INPUT block (sample x >> icsx, y >> icsy); each output
+ * chroma sample is the mean of the LUT's integer RGB over its OUTPUT block, the 1/n (n = 2^(ocsx + ocsy)) folded into cbr..crb
+ * (lutr_yuv_constants_xsub).  A partial output block at an odd edge takes the edge column / row again.  Everything else --
+ * prologue, matrices, ranges, LUT depth, truncation -- is lutr_apply_yuv's arithmetic.
+ * row0 and rows must be multiples of the union block height 2^max(icsy, ocsy) unless row0 + rows == h.
+ * dither: LUTR_DITHER_NONE, or LUTR_DITHER_ERROR_DIFFUSION on whole frames only (row0 = 0, rows = h; the scratch of
+ * lutr_apply_yuv_dither, sized by the output layout).
+ * Equal layouts are lutr_apply_yuv (or lutr_apply_yuv_dither when dithering) itself: same kernels, bits and last kernel.
+ * A layout change always runs strict precision (fast / fma32 run strict here, no suffix on the last kernel) and takes a
+ * .csp prelut.  Kernels: "k_yuv_xsub_vec<win,wout,icsx,icsy,ocsx,ocsy,interp>" (nearest / trilinear / tetrahedral; 8 -> 8,
+ * 16 -> 16 and 16 -> 8 bit containers; width a multiple of 8 luma samples, 4 for 16 -> 16; positive strides aligned to
+ * the accesses; row0 / rows multiples of the union block height), "k_yuv_xsub_generic" for everything else; a ragged
+ * width on aligned rows is split between the two; dithering runs "k_yuv_float+k_dither_ed".  Variants: auto and generic
+ * as for lutr_apply_yuv; vec_global fails with LUTR_EINVAL where the vector kernel cannot take the layout; vec_lds always
+ * fails with LUTR_EINVAL on a layout change (there is no LDS-window kernel for it). */
+int lutr_apply_yuv_xsub(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int dither, int w, int h, int nframes,
+                        const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
+/* lutr_yuv_constants for lutr_apply_yuv_xsub: the down-sampling's n is the OUTPUT block's size.  Same bits as
+ * lutr_yuv_constants when fmt_in and fmt_out share the layout.  Host only. */
+int lutr_yuv_constants_xsub(const lutr_yuv_params *p, float out[32]);
+
 /* ---- precision ---- */
 /* STRICT (default): every kernel is a bit-exact restatement of FFmpeg's scalar C lut3d (vf_lut3d.c order of operations,
  * no fused multiply-add in the blend).  FAST: permission to use the tolerance-bounded tile kernels -- lattice staged as

@@ -36,7 +36,8 @@ SYMBOLS = (
     "lutr_ctx_set_lut", "lutr_ctx_lut_alloc", "lutr_ctx_lut_device", "lutr_ctx_lut_seal",
     "lutr_lattice_bytes", "lutr_lut_broadcast", "lutr_lut_broadcast_ex",
     "lutr_apply_planar_rgb", "lutr_apply_packed_rgb", "lutr_apply_yuv", "lutr_apply_yuv_dither",
-    "lutr_apply_yuv_sited", "lutr_yuv_constants_sited", "lutr_resize_filter", "lutr_resize_planes",
+    "lutr_apply_yuv_sited", "lutr_yuv_constants_sited", "lutr_apply_yuv_xsub", "lutr_yuv_constants_xsub",
+    "lutr_resize_filter", "lutr_resize_planes",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
 )
 
@@ -130,6 +131,9 @@ def load() -> C.CDLL:
     lib.lutr_apply_yuv_sited.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes),
                                          C.POINTER(Planes), ci, ci]
     lib.lutr_yuv_constants_sited.argtypes = [C.POINTER(YuvParams), ci, C.POINTER(C.c_float)]
+    lib.lutr_apply_yuv_xsub.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes),
+                                        ci, ci]
+    lib.lutr_yuv_constants_xsub.argtypes = [C.POINTER(YuvParams), C.POINTER(C.c_float)]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]
     lib.lutr_ctx_set_variant.argtypes = [vp, ci]

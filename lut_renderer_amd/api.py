@@ -127,6 +127,9 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     block mean after it; "left" | "center" | "topleft" (ffprobe's chroma_location) resample chroma bilinearly at that
     siting (always strict arithmetic, no in-place output, not with error-diffusion dither).
 
+    `out_pix_fmt` may change the chroma subsampling (4:2:0 / 4:2:2 / 4:4:4 either way, DESIGN.md 3.8: the reference's final
+    `format=` with another layout, e.g. its ProRes 422 master of a 4:2:0 source); `chroma_loc` cannot be combined with that.
+
     `resolution` is `ProcessingParams.resolution`, a "WxH" string as ffmpeg's `-s` takes it: the output planes are resized to
     that size on the GPU after everything else, and `out` must have that size.  One device only (no
     LutEngineGroup): a row-sharded resize would need halos between the devices."""
@@ -157,7 +160,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
     from .engine import check_chroma_loc
-    check_chroma_loc(chroma_loc, kw["dither"])
+    check_chroma_loc(chroma_loc, kw["dither"], kw["pix_fmt"], kw["out_pix_fmt"])
     if chroma_loc is not None:
         kw["chroma_loc"] = chroma_loc
     if out_size is not None:

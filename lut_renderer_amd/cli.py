@@ -86,7 +86,7 @@ def plan_from_args(args):
         kw["dither"] = "error_diffusion"
     if getattr(args, "chroma_loc", None):
         from .engine import check_chroma_loc
-        check_chroma_loc(args.chroma_loc, kw.get("dither", "none"))
+        check_chroma_loc(args.chroma_loc, kw.get("dither", "none"), kw["pix_fmt"], kw["out_pix_fmt"])
         kw["chroma_loc"] = args.chroma_loc
     if getattr(args, "out_size", None):
         from .engine import parse_size

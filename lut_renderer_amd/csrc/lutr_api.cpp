@@ -55,19 +55,17 @@ static bool matrix_k(int m, double *kr, double *kb)
 }
 
 // DESIGN.md "YUV contract".  All coefficients are formed in double and rounded to
-// float once; the kernels then use exactly these floats.
-int make_yuv_consts(const lutr_yuv_params &p, YuvConsts *o)
+// float once; the kernels then use exactly these floats.  chroma_n: samples of one OUTPUT chroma block (the block mean's n,
+// folded into cbr..crb).
+static int yuv_consts_n(const lutr_yuv_params &p, int chroma_n, YuvConsts *o)
 {
     const int din = LUTR_FMT_DEPTH(p.fmt_in), dout = LUTR_FMT_DEPTH(p.fmt_out), dl = p.lut_depth;
     if (din < 8 || din > 16 || dout < 8 || dout > 16 || dl < 8 || dl > 16) {
         set_error("unsupported bit depth (in %d, lut %d, out %d)", din, dl, dout);
         return LUTR_EINVAL;
     }
-    if (LUTR_FMT_CSX(p.fmt_in) != LUTR_FMT_CSX(p.fmt_out) || LUTR_FMT_CSY(p.fmt_in) != LUTR_FMT_CSY(p.fmt_out)) {
-        set_error("fmt_in and fmt_out must share chroma subsampling");
-        return LUTR_EINVAL;
-    }
-    if (LUTR_FMT_CSX(p.fmt_in) == 0 && LUTR_FMT_CSY(p.fmt_in) == 1) {
+    if ((LUTR_FMT_CSX(p.fmt_in) == 0 && LUTR_FMT_CSY(p.fmt_in) == 1) ||
+        (LUTR_FMT_CSX(p.fmt_out) == 0 && LUTR_FMT_CSY(p.fmt_out) == 1)) {
         set_error("4:4:0 chroma layout is not supported");
         return LUTR_EINVAL;
     }
@@ -88,7 +86,6 @@ int make_yuv_consts(const lutr_yuv_params &p, YuvConsts *o)
         return LUTR_EINVAL;
     }
     std::memset(o, 0, sizeof(*o));
-    const int chroma_n = 1 << (LUTR_FMT_CSX(p.fmt_in) + LUTR_FMT_CSY(p.fmt_in));
 
     if (prologue) {
         const double mi = (double)((1 << din) - 1);
@@ -151,6 +148,22 @@ int make_yuv_consts(const lutr_yuv_params &p, YuvConsts *o)
         o->max_o = (float)mo;
     }
     return LUTR_OK;
+}
+
+// lutr_apply_yuv's constants: input and output share the chroma layout
+int make_yuv_consts(const lutr_yuv_params &p, YuvConsts *o)
+{
+    if (LUTR_FMT_CSX(p.fmt_in) != LUTR_FMT_CSX(p.fmt_out) || LUTR_FMT_CSY(p.fmt_in) != LUTR_FMT_CSY(p.fmt_out)) {
+        set_error("fmt_in and fmt_out must share chroma subsampling");
+        return LUTR_EINVAL;
+    }
+    return yuv_consts_n(p, 1 << (LUTR_FMT_CSX(p.fmt_in) + LUTR_FMT_CSY(p.fmt_in)), o);
+}
+
+// any pair of 4:2:0 / 4:2:2 / 4:4:4 layouts; the block mean is over the OUTPUT block, n = 2^(ocsx + ocsy)
+int make_yuv_consts_xsub(const lutr_yuv_params &p, YuvConsts *o)
+{
+    return yuv_consts_n(p, 1 << (LUTR_FMT_CSX(p.fmt_out) + LUTR_FMT_CSY(p.fmt_out)), o);
 }
 
 // down-sampling taps sum to 4 on a co-sited axis, 2 on an interstitial one, 1 on an axis that is not
@@ -995,7 +1008,72 @@ int lutr_apply_yuv_dither(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
     fill_planes(&P, src, dst);
     FloatPlanes F{c->fscratch, c->fscratch + ny, c->fscratch + ny + nc};
     return finish_launch(c, launch_yuv_dither(c->stream, L, K, P, G, F, LUTR_FMT_DEPTH(p->fmt_in),
-                                              LUTR_FMT_DEPTH(p->fmt_out), csx, csy, interp));
+                                              LUTR_FMT_DEPTH(p->fmt_out), csx, csy, interp, csx, csy));
+}
+
+int lutr_yuv_constants_xsub(const lutr_yuv_params *p, float out[32])
+{
+    if (!p || !out) {
+        set_error("lutr_yuv_constants_xsub: null argument");
+        return LUTR_EINVAL;
+    }
+    YuvConsts k;
+    const int rc = make_yuv_consts_xsub(*p, &k);
+    if (rc) return rc;
+    std::memcpy(out, &k, sizeof(k));
+    return LUTR_OK;
+}
+
+int lutr_apply_yuv_xsub(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dither, int w, int h, int nframes,
+                        const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+{
+    if (dither != LUTR_DITHER_NONE && dither != LUTR_DITHER_ERROR_DIFFUSION) { set_error("unknown dither mode %d", dither); return LUTR_EINVAL; }
+    int rc = check_common(c, interp, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    YuvConsts K;
+    rc = make_yuv_consts_xsub(*p, &K);
+    if (rc) return rc;
+    if (dither == LUTR_DITHER_ERROR_DIFFUSION && (row0 != 0 || rows != h)) {
+        set_error("error-diffusion dither couples the rows of a frame: whole frames only (row0 = 0, rows = h)");
+        return LUTR_EINVAL;
+    }
+    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
+    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
+    if (icsx == ocsx && icsy == ocsy)        // one layout: lutr_apply_yuv's contract, kernels and bits
+        return dither == LUTR_DITHER_NONE ? lutr_apply_yuv(c, p, interp, w, h, nframes, src, dst, row0, rows)
+                                          : lutr_apply_yuv_dither(c, p, interp, dither, w, h, nframes, src, dst);
+    const int bh = 1 << (icsy > ocsy ? icsy : ocsy);
+    if (row0 % bh || (rows % bh && row0 + rows != h)) {
+        set_error("row0/rows must be multiples of the union chroma block height %d", bh);
+        return LUTR_EINVAL;
+    }
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    for (int i = 0; i < 3; i++)
+        if (!src->data[i] || !dst->data[i]) { set_error("null plane %d", i); return LUTR_EINVAL; }
+    HIP_TRY(hipSetDevice(c->device));
+    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
+    LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
+    fill_planes(&P, src, dst);
+    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
+    if (dither == LUTR_DITHER_NONE)
+        return finish_launch(c, launch_yuv_xsub(c->stream, c->variant, L, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, interp));
+    const size_t cw = (size_t)((w + (1 << ocsx) - 1) >> ocsx), ch = (size_t)((h + (1 << ocsy) - 1) >> ocsy);
+    const size_t ny = (size_t)w * h * nframes, nc = cw * ch * nframes;
+    if (ny + 2 * nc > c->fscratch_floats) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->fscratch) (void)hipFree(c->fscratch);
+        c->fscratch = nullptr;
+        c->fscratch_floats = 0;
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, (ny + 2 * nc) * sizeof(float));
+        if (e != hipSuccess) { set_error("hipMalloc(%zu): %s", (ny + 2 * nc) * sizeof(float), hipGetErrorString(e)); return LUTR_ENOMEM; }
+        c->fscratch = (float *)q;
+        c->fscratch_floats = ny + 2 * nc;
+    }
+    FloatPlanes F{c->fscratch, c->fscratch + ny, c->fscratch + ny + nc};
+    return finish_launch(c, launch_yuv_dither(c->stream, L, K, P, G, F, din, dout, icsx, icsy, interp, ocsx, ocsy));
 }
 
 

@@ -11,7 +11,8 @@
 //
 // Two kernels:
 //   k_yuv_float   one thread per chroma block: YUV -> RGB -> lut3d -> unquantised YUV, written as float
-//                 planes into scratch (taps gathered from L2 like the generic kernel).
+//                 planes into scratch (taps gathered from L2 like the generic kernel).  With a chroma subsampling
+//                 change its twin k_yuv_float_xsub (lutr_xsub.hip) takes one thread per union block instead.
 //   k_dither_ed   the sequential part.  A pixel needs its left neighbour and three pixels of the row above,
 //                 so row r can run a few columns behind row r-1: a wave takes a band of 64 rows, lane r on row
 //                 r, skewed by 4 columns per lane (2 would do; 4 keeps all lanes on the same phase of a 4-column
@@ -215,14 +216,21 @@ __global__ __launch_bounds__(512) void k_dither_ed(FloatPlanes F, PlaneSet P, Fr
 
 // ---------------------------------------------------------------- launcher
 const char *launch_yuv_dither(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
-                              const FrameGeom &G, const FloatPlanes &F, int din, int dout, int csx, int csy, int mode)
+                              const FrameGeom &G, const FloatPlanes &F, int din, int dout, int csx, int csy, int mode,
+                              int ocsx, int ocsy)
 {
     const int win = din > 8, wout = dout > 8;
-    const long long blocks = (long long)((G.w + (1 << csx) - 1) >> csx) * ((G.h + (1 << csy) - 1) >> csy) * G.nframes;
-    long long gb = (blocks + 255) / 256;
-    if (gb < 1) gb = 1;
-    if (gb > 256 * 64) gb = 256 * 64;
-    hipLaunchKernelGGL(k_yuv_float, dim3((unsigned)gb), dim3(256), 0, st, L, K, P, G, F, win, csx, csy, mode);
+    if (ocsx != csx || ocsy != csy) {
+        // a subsampling change: pass 1 by union blocks (lutr_xsub.hip); pass 2 below sizes its planes from the output
+        launch_yuv_float_xsub(st, L, K, P, G, F, win, csx, csy, ocsx, ocsy, mode);
+    } else {
+        const long long blocks = (long long)((G.w + (1 << csx) - 1) >> csx) * ((G.h + (1 << csy) - 1) >> csy) * G.nframes;
+        long long gb = (blocks + 255) / 256;
+        if (gb < 1) gb = 1;
+        if (gb > 256 * 64) gb = 256 * 64;
+        hipLaunchKernelGGL(k_yuv_float, dim3((unsigned)gb), dim3(256), 0, st, L, K, P, G, F, win, csx, csy, mode);
+    }
+    // pass 2 works on the output planes: chroma sized from the output layout (ocsx, ocsy)
     // waves per workgroup = bands of one plane in flight: as many as the LDS error rows allow (144 KB of the
     // CU's 160 KB: one workgroup per CU, and a batch of 64 frames is 192 workgroups for 256 CUs), at most 8
     int nw = (int)((144 * 1024) / ((size_t)(G.w + 2) * sizeof(float) + sizeof(int)));
@@ -245,14 +253,14 @@ const char *launch_yuv_dither(hipStream_t st, const LutConsts &L, const YuvConst
         }
     }
     // packed path: every plane width a multiple of 4, destination rows aligned for 4-sample stores
-    const int cwid = (G.w + (1 << csx) - 1) >> csx;
+    const int cwid = (G.w + (1 << ocsx) - 1) >> ocsx;
     bool vec = G.w % 4 == 0 && cwid % 4 == 0;
     const uintptr_t al = wout ? 8 : 4;
     for (int c = 0; c < 3 && vec; c++)
         vec = ((uintptr_t)P.d[c] % al) == 0 && (P.ds[c] % (long long)al) == 0 && (G.nframes == 1 || P.dfs[c] % (long long)al == 0);
     const dim3 grid((unsigned)(3 * G.nframes)), block(64 * nw);
-    if (vec) hipLaunchKernelGGL((k_dither_ed<true>), grid, block, lds, st, F, P, G, csx, csy, K.max_o, wout);
-    else hipLaunchKernelGGL((k_dither_ed<false>), grid, block, lds, st, F, P, G, csx, csy, K.max_o, wout);
+    if (vec) hipLaunchKernelGGL((k_dither_ed<true>), grid, block, lds, st, F, P, G, ocsx, ocsy, K.max_o, wout);
+    else hipLaunchKernelGGL((k_dither_ed<false>), grid, block, lds, st, F, P, G, ocsx, ocsy, K.max_o, wout);
     return "k_yuv_float+k_dither_ed";
 }
 

@@ -104,9 +104,26 @@ const char *launch_packed(hipStream_t st, int variant, const LutConsts &L, const
 LUTR_R2_DECL(0) LUTR_R2_DECL(1) LUTR_R2_DECL(2) LUTR_R2_DECL(3) LUTR_R2_DECL(4) LUTR_R2_DECL(5) LUTR_R2_DECL(6) LUTR_R2_DECL(7)
 #undef LUTR_R2_DECL
 
-// error-diffusion dither path (lutr_dither.hip): whole frames, float planes in F
+// error-diffusion dither path (lutr_dither.hip): whole frames, float planes in F (chroma planes in the output layout ocsx, ocsy;
+// csx, csy are the input's)
 const char *launch_yuv_dither(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
-                              const FrameGeom &G, const FloatPlanes &F, int din, int dout, int csx, int csy, int interp);
+                              const FrameGeom &G, const FloatPlanes &F, int din, int dout, int csx, int csy, int interp,
+                              int ocsx, int ocsy);
+
+// chroma subsampling change (lutr_xsub.hip): input layout icsx, icsy, output layout ocsx, ocsy (they differ); K
+// carries the output block's 1/n.  nullptr = the variant cannot take the call (vec_lds always; vec_global on layouts the vector
+// kernel cannot take)
+const char *launch_yuv_xsub(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
+                            const FrameGeom &G, int din, int dout, int icsx, int icsy, int ocsx, int ocsy, int interp);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>): nullptr = not a cross pair / mode it has
+#define LUTR_XS_DECL(tag) \
+    const char *launch_yuv_xsub_vec_##tag(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, \
+                                          const FrameGeom &G, int icsx, int icsy, int ocsx, int ocsy, int interp);
+LUTR_XS_DECL(w00) LUTR_XS_DECL(w11) LUTR_XS_DECL(w10)
+#undef LUTR_XS_DECL
+// the dither path's unquantised pass for a subsampling change (k_yuv_float_xsub)
+void launch_yuv_float_xsub(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
+                           const FloatPlanes &F, int win, int icsx, int icsy, int ocsx, int ocsy, int interp);
 
 // round-2 tile kernels (lutr_tile2.hip, one translation unit per format: w<in wide><out wide>_c<csx><csy>); nullptr =
 // this combination is not built / cannot take the call, the caller falls back
@@ -158,6 +175,7 @@ const char *launch_rgb_tile(hipStream_t st, const LutConsts &L, const PlaneSet &
 
 // host helpers (yuv_consts.cpp / cube_parse.cpp)
 int make_yuv_consts(const lutr_yuv_params &p, YuvConsts *out);
+int make_yuv_consts_xsub(const lutr_yuv_params &p, YuvConsts *out);
 int make_yuv_consts_sited(const lutr_yuv_params &p, int chroma_loc, YuvConsts *out);
 void set_error(const char *fmt, ...);
 

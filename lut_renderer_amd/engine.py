@@ -77,11 +77,24 @@ def chroma_loc_code(chroma_loc: Optional[str]) -> int:
     return _native.CHROMA_LOC[chroma_loc]
 
 
-def check_chroma_loc(chroma_loc: Optional[str], dither: str = "none") -> None:
-    """The checks `apply_yuv` makes of `chroma_loc` before any GPU work: a known name, and no error-diffusion dither with it."""
+def check_chroma_loc(chroma_loc: Optional[str], dither: str = "none", pix_fmt: Optional[str] = None,
+                     out_pix_fmt: Optional[str] = None) -> None:
+    """The checks `apply_yuv` makes of `chroma_loc` before any GPU work: a known name, no error-diffusion dither with it, and
+    (given the two pixel formats) no chroma subsampling change with it -- sited resampling across layouts is not defined."""
     chroma_loc_code(chroma_loc)
     if chroma_loc is not None and dither != "none":
         raise ValueError("error-diffusion dither is not defined with sited chroma resampling (chroma_loc)")
+    if chroma_loc is not None and pix_fmt and out_pix_fmt and changes_subsampling(pix_fmt, out_pix_fmt):
+        raise ValueError(f"sited chroma resampling (chroma_loc) is not defined with a chroma subsampling change "
+                         f"('{pix_fmt}' -> '{out_pix_fmt}'); drop chroma_loc to replicate / average over the chroma blocks")
+
+
+def changes_subsampling(pix_fmt: str, out_pix_fmt: Optional[str]) -> bool:
+    """True when the two planar YUV formats differ in chroma subsampling."""
+    if not out_pix_fmt:
+        return False
+    a, b = parse_pix_fmt(pix_fmt.replace("yuvj", "yuv")), parse_pix_fmt(out_pix_fmt.replace("yuvj", "yuv"))
+    return (a.csx, a.csy) != (b.csx, b.csy)
 
 
 #: frames per LUT launch when apply_yuv / apply_rgb resize (`out_size`): the LUT writes a chunk into the engine's scratch at the
@@ -467,16 +480,19 @@ class LutEngine:
         dither="error_diffusion" (the reference's `zscale_dither`) dithers the final quantisation; whole frames only.
         chroma_loc ("left" | "center" | "topleft", ffprobe's chroma_location names) resamples chroma bilinearly at that
         siting instead of replicating it (strict arithmetic, not in place, no dither).  None = replicate.
+        `out_pix_fmt` may change the chroma subsampling (4:2:0 / 4:2:2 / 4:4:4 either way): input chroma is
+        replicated over its input block, output chroma is the mean over its output block; strict arithmetic, no chroma_loc.
         out_size = (w, h) or "WxH" resizes the output planes to that size after everything else (the reference's `-s`,
         DESIGN.md 3.7): the LUT writes `resize_chunk` frames at a time (default RESIZE_CHUNK) into engine scratch at the source
         size and the resize reads them back; whole frames only, not in place.  The resize sites chroma by `chroma_loc`."""
         if dither not in _native.DITHER:
             raise ValueError(f"unknown dither mode '{dither}'")
-        check_chroma_loc(chroma_loc, dither)
         fin = parse_pix_fmt(pix_fmt)
         fout = parse_pix_fmt(out_pix_fmt or pix_fmt)
         if fin.family != "yuv" or fout.family != "yuv":
             raise ValueError("apply_yuv takes planar YUV formats")
+        check_chroma_loc(chroma_loc, dither, fin.name, fout.name)
+        xsub = (fin.csx, fin.csy) != (fout.csx, fout.csy)
         p = _native.YuvParams()
         p.fmt_in, p.fmt_out = fin.code, fout.code
         p.lut_depth = lut_depth if lut_depth is not None else fin.depth
@@ -507,7 +523,11 @@ class LutEngine:
             raise ValueError("error-diffusion dither couples the rows of a frame: whole frames only")
         with self._lock:
             self._bind_stream()
-            if chroma_loc is not None:
+            if xsub:
+                _native.check(self._lib.lutr_apply_yuv_xsub(
+                    self._ctx, C.byref(p), _native.INTERP[interp], _native.DITHER[dither], w, h, nf, C.byref(s), C.byref(d),
+                    row0, rows))
+            elif chroma_loc is not None:
                 _native.check(self._lib.lutr_apply_yuv_sited(
                     self._ctx, C.byref(p), _native.INTERP[interp], chroma_loc_code(chroma_loc), w, h, nf, C.byref(s), C.byref(d),
                     row0, rows))
@@ -527,6 +547,16 @@ def yuv_constants(**kw) -> np.ndarray:
         setattr(p, k, v)
     out = (C.c_float * 32)()
     _native.check(_native.load().lutr_yuv_constants(C.byref(p), out))
+    return np.array(list(out), dtype=np.float32)
+
+
+def yuv_constants_xsub(**kw) -> np.ndarray:
+    """`yuv_constants` for a chroma subsampling change (lutr_yuv_constants_xsub): the block mean's n is the output block's."""
+    p = _native.YuvParams()
+    for k, v in kw.items():
+        setattr(p, k, v)
+    out = (C.c_float * 32)()
+    _native.check(_native.load().lutr_yuv_constants_xsub(C.byref(p), out))
     return np.array(list(out), dtype=np.float32)
 
 

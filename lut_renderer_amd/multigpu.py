@@ -134,7 +134,7 @@ class LutEngineGroup:
             dt = torch.uint8 if fout.depth <= 8 else (src[0].dtype if src[0].element_size() == 2 else torch.int16)
             lead = tuple(src[0].shape[:-2])
             dst = [torch.empty(lead + fout.plane_shape(i, w, h), dtype=dt, device=home) for i in range(3)]
-        bh = 1 << fin.csy
+        bh = 1 << max(fin.csy, fout.csy)                           # the union block: whole chroma rows on both sides
         blocks = row_blocks(h, len(self.engines), align=bh)
         self.last_blocks = blocks
         pending = []
@@ -146,9 +146,12 @@ class LutEngineGroup:
                 # same GPU: launch on the caller's planes, rows [r0, r1)
                 eng.apply_yuv(src, dst, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0, rows=r1 - r0, **kw)
                 continue
-            # another GPU: its row block travels there (peer copy), is processed as a frame of r1-r0 rows, and comes back
-            c0, c1 = r0 >> fin.csy, (r1 + bh - 1) >> fin.csy
-            rng = [(r0, r1), (c0, c1), (c0, c1)]
+            # another GPU: its row block travels there (peer copy), is processed as a frame of r1-r0 rows, and comes back.
+            # Source and destination chroma rows are counted in their own layouts.
+            c0, c1 = r0 >> fin.csy, (r1 + (1 << fin.csy) - 1) >> fin.csy
+            o0, o1 = r0 >> fout.csy, (r1 + (1 << fout.csy) - 1) >> fout.csy
+            src_rng = [(r0, r1), (c0, c1), (c0, c1)]
+            rng = [(r0, r1), (o0, o1), (o0, o1)]
             if kw.get("chroma_loc") is not None:
                 # sited resampling reads one chroma row (one chroma block row of luma) above and below the block: the slice
                 # that travels carries that halo, clipped to the frame, and the apply writes the block's rows inside it
@@ -166,7 +169,7 @@ class LutEngineGroup:
                 continue
             with torch.cuda.device(eng.device):
                 part = [p[..., a:b, :].to(eng.device, non_blocking=True, copy=True).contiguous()
-                        for p, (a, b) in zip(src, rng)]
+                        for p, (a, b) in zip(src, src_rng)]
                 out = eng.apply_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, **kw)
             self.last_remote += 1
             pending.append((out, rng))
