@@ -311,6 +311,39 @@ int lutr_apply_yuv_xsub(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int
  * lutr_yuv_constants when fmt_in and fmt_out share the layout.  Host only. */
 int lutr_yuv_constants_xsub(const lutr_yuv_params *p, float out[32]);
 
+/* ---- RGB sources with a YUV output (the reference's chain on a PNG / TIFF / DPX sequence or an RGB screen
+ *      recording: lut3d directly on the RGB frame, then format=<pix_fmt>, ffmpeg.py:246 and :304-310) ---- */
+/* `interp` value of lutr_apply_rgb_to_yuv that leaves lut3d out: the source codes go straight to the RGB -> YUV stage
+ * (the range-normalising stage ahead of lut3d that the reference puts in front of full-range sources, ffmpeg.py:212-233). */
+#define LUTR_INTERP_NONE (-1)
+/* Integer RGB at depth p->lut_depth -> lut3d at that depth (lutr_apply_planar_rgb / lutr_apply_packed_rgb's arithmetic, every
+ * interpolation mode, a .csp prelut taken) -> planar YUV p->fmt_out (4:2:0 / 4:2:2 / 4:4:4 at any depth in 8..16; 4:4:0 is
+ * LUTR_EINVAL) through the output stage of lutr_apply_yuv: Y per pixel, each chroma sample from the sum of the LUT's integer RGB
+ * over its OUTPUT block, 1/n (n = 2^(ocsx + ocsy)) folded into cbr..crb (lutr_yuv_constants_rgb2yuv); a partial block at an odd
+ * edge takes the edge column / row again.  Of *p only fmt_out, lut_depth, matrix_out and range_out are read.
+ * src_kind == 0: planar gbrp in src_planar (plane 0 = G, 1 = B, 2 = R; uint8 for lut_depth 8, else uint16 LE), src_packed unused.
+ * src_kind == LUTR_PK_* / LUTR_PACKED(...): one packed image in src_packed, src_planar unused; lut_depth must be the format's
+ *   bits (8 | 16); a fourth component (alpha / padding) is read past and dropped.  16-bit formats need 2-byte aligned rows.
+ * row0 and rows must be multiples of the output chroma block height 2^ocsy unless row0 + rows == h.
+ * dither: LUTR_DITHER_NONE, or LUTR_DITHER_ERROR_DIFFUSION on whole frames only (the scratch of lutr_apply_yuv_dither, sized by
+ * the output layout).  Always strict precision (fast / fma32 run strict here, no suffix on the last kernel).
+ * Not in place: the bounding byte range of every source plane / the source image (all rows and frames) must be disjoint from
+ * that of every destination plane (the rule of lutr_apply_yuv_sited), else LUTR_EINVAL before anything touches the device.
+ * Kernels: "k_rgb2yuv_vec<win,nc,wout,ocsx,ocsy,interp|nolut>" (nc = 1 planar, 3 | 4 packed components; nearest / trilinear /
+ * tetrahedral / no LUT; 8 -> 8, 16 -> 16 and 16 -> 8 bit containers; width a multiple of 8; positive strides; planar source
+ * planes aligned to 8 samples, a packed image to 4 bytes, destination planes to the 8 (chroma: 8 >> ocsx) samples a thread
+ * stores; 3-component sources in R G B or B G R order; row0 / rows multiples of 2^ocsy), "k_rgb2yuv_generic" for everything
+ * else; a ragged width on aligned rows is split between the two; dithering runs "k_rgb2yuv_float+k_dither_ed".  Variants: auto
+ * and generic as for lutr_apply_yuv; vec_global fails with LUTR_EINVAL where the vector kernel cannot take the layout; vec_lds
+ * always fails with LUTR_EINVAL (there is no LDS kernel for this path).
+ * Not covered: YUV in with RGB out, chroma siting, a tile (LDS) kernel. */
+int lutr_apply_rgb_to_yuv(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int dither, int src_kind, int w, int h, int nframes,
+                          const lutr_planes *src_planar, const lutr_packed *src_packed, const lutr_planes *dst, int row0, int rows);
+/* The constant block lutr_apply_rgb_to_yuv uses.  Its output-stage entries (cyr..crb, yob, cob, max_o) equal, bit for bit, those
+ * of lutr_yuv_constants_xsub for a 4:4:4 source at depth lut_depth with the same output side; the input-stage entries are not
+ * read by the kernels (they are filled from matrix_out / range_out).  Host only. */
+int lutr_yuv_constants_rgb2yuv(const lutr_yuv_params *p, float out[32]);
+
 /* ---- precision ---- */
 /* STRICT (default): every kernel is a bit-exact restatement of FFmpeg's scalar C lut3d (vf_lut3d.c order of operations,
  * no fused multiply-add in the blend).  FAST: permission to use the tolerance-bounded tile kernels -- lattice staged as

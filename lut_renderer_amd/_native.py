@@ -19,6 +19,8 @@ INTERP = {"nearest": 0, "trilinear": 1, "tetrahedral": 2, "pyramid": 3, "prism":
 MATRIX = {"bt709": 0, "smpte170m": 1, "bt470bg": 1, "bt601": 1, "bt2020nc": 2, "bt2020c": 2}
 RANGE = {"tv": 0, "pc": 1}
 DITHER = {"none": 0, "error_diffusion": 1}
+#: LUTR_INTERP_NONE: lutr_apply_rgb_to_yuv without lut3d
+INTERP_NONE = -1
 VARIANT = {"auto": 0, "generic": 1, "vec_global": 2, "vec_lds": 3}
 PRECISION = {"strict": 0, "fast": 1, "fma32": 2}
 #: enum lutr_chroma_loc: ffprobe's chroma_location names (None = replicate, lutr_apply_yuv's contract)
@@ -37,6 +39,7 @@ SYMBOLS = (
     "lutr_lattice_bytes", "lutr_lut_broadcast", "lutr_lut_broadcast_ex",
     "lutr_apply_planar_rgb", "lutr_apply_packed_rgb", "lutr_apply_yuv", "lutr_apply_yuv_dither",
     "lutr_apply_yuv_sited", "lutr_yuv_constants_sited", "lutr_apply_yuv_xsub", "lutr_yuv_constants_xsub",
+    "lutr_apply_rgb_to_yuv", "lutr_yuv_constants_rgb2yuv",
     "lutr_resize_filter", "lutr_resize_planes",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
 )
@@ -134,6 +137,9 @@ def load() -> C.CDLL:
     lib.lutr_apply_yuv_xsub.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes),
                                         ci, ci]
     lib.lutr_yuv_constants_xsub.argtypes = [C.POINTER(YuvParams), C.POINTER(C.c_float)]
+    lib.lutr_apply_rgb_to_yuv.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Packed),
+                                          C.POINTER(Planes), ci, ci]
+    lib.lutr_yuv_constants_rgb2yuv.argtypes = [C.POINTER(YuvParams), C.POINTER(C.c_float)]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]
     lib.lutr_ctx_set_variant.argtypes = [vp, ci]

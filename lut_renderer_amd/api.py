@@ -79,13 +79,34 @@ def _cached_cube(path: Path) -> CubeLut:
 
 
 def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = None) -> dict:
-    """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv."""
+    """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv -- or, for an RGB `pix_fmt` (gbrp* / a packed name) with
+    a YUV `out_pix_fmt`, of LutEngine.apply_rgb_to_yuv (`is_rgb_call(kw)` tells the two apart)."""
     from .engine import parse_pix_fmt
     if plan.interp not in _ENGINE_INTERP:
         raise ValueError(f"lut3d has no interpolation mode '{plan.interp}'")
+    from .engine import parse_rgb_source
+    rgb = parse_rgb_source(pix_fmt)
+    if rgb is not None:
+        # an RGB source (DESIGN.md 3.9): lut3d runs on the RGB frame itself, then format=<pix_fmt>.  The engine has no encoder to
+        # negotiate an output format with, so the caller names it.
+        if not out_pix_fmt:
+            raise ValueError("apply_lut takes planar YUV frames, or an RGB source with a YUV out_pix_fmt; for RGB output use "
+                             "LutEngine.apply_rgb for gbrp planes / LutEngine.apply_packed for packed images")
+        if parse_rgb_source(out_pix_fmt) is not None or parse_pix_fmt(out_pix_fmt.replace("yuvj", "yuv")).family != "yuv":
+            raise ValueError(f"an RGB source takes a planar YUV out_pix_fmt, not '{out_pix_fmt}'; for RGB output use "
+                             "LutEngine.apply_rgb for gbrp planes / LutEngine.apply_packed for packed images")
+        kw = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, interp=plan.interp, matrix_out=plan.matrix or "smpte170m",
+                  range_out="tv")
+        if plan.prologue:
+            # scale=in_range=pc:out_range=R, format=yuv4xxp (8 bit) AHEAD of lut3d: the two-stage composition of 3.9 point 6
+            kw.update(intermediate_pix_fmt=plan.intermediate_pix_fmt, prologue_out_range=plan.prologue_out_range)
+        return kw
     src = parse_pix_fmt(pix_fmt)
     if src.family != "yuv":
         raise ValueError("apply_lut takes planar YUV frames; use LutEngine.apply_rgb for gbrp planes")
+    if out_pix_fmt and parse_rgb_source(out_pix_fmt) is not None:
+        raise ValueError(f"YUV frames with an RGB out_pix_fmt ('{out_pix_fmt}') are not supported: nothing in the reference's "
+                         "chain produces them")
     matrix = plan.matrix or "smpte170m"
     kw = dict(pix_fmt=pix_fmt.replace("yuvj", "yuv"), interp=plan.interp, matrix_in=matrix, matrix_out=matrix,
               range_out="tv")
@@ -100,6 +121,12 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
     return kw
 
 
+def is_rgb_call(kw: dict) -> bool:
+    """True when `engine_call_for` returned arguments of `apply_rgb_to_yuv` (an RGB source)."""
+    from .engine import parse_rgb_source
+    return parse_rgb_source(kw.get("pix_fmt")) is not None
+
+
 def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: str, width: Optional[int] = None,
               height: Optional[int] = None, input_matrix: str = "auto", colorspace: Optional[str] = None,
               color_range: Optional[str] = None, output_tags: str = "bt709", out_pix_fmt: Optional[str] = None,
@@ -107,7 +134,9 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               devices: Sequence[int] = (0,), precision: str = "strict", chroma_loc: Optional[str] = None,
               resolution: Optional[str] = None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
-    engine's device, each [H,W] or [F,H,W].  Returns (planes_out, tags) where `tags` is the colour
+    engine's device, each [H,W] or [F,H,W].  With an RGB `pix_fmt` (gbrp* or a packed name such as rgb24) and a YUV
+    `out_pix_fmt` (required then), `planes` is the three gbrp planes (G, B, R) or the one [F,]H,W,C packed tensor and the
+    chain is lut3d on the RGB frame, then RGB -> YUV.  Returns (planes_out, tags) where `tags` is the colour
     metadata the reference would write for this policy (None = inherit / none).
 
     `engine` may be a LutEngine (or LutEngineGroup) that already holds the lattice (then `cube` may be
@@ -145,7 +174,13 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         from .multigpu import LutEngineGroup
         if isinstance(engine, LutEngineGroup) or (engine is None and len(devices) > 1):
             raise ValueError("resolution needs a single device")
-    if width is not None and planes[0].shape[-1] != width or height is not None and planes[0].shape[-2] != height:
+    from .engine import parse_rgb_source
+    rgb_src = parse_rgb_source(pix_fmt)
+    if rgb_src is not None and rgb_src.packed:
+        got_w, got_h = planes.shape[-2], planes.shape[-3]
+    else:
+        got_w, got_h = planes[0].shape[-1], planes[0].shape[-2]
+    if width is not None and got_w != width or height is not None and got_h != height:
         raise ValueError("plane shape does not match width/height")
     params = ProcessingParams(lut_interp=interp, lut_input_matrix=input_matrix, lut_output_tags=output_tags,
                               zscale_dither=zscale_dither)
@@ -160,7 +195,11 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
     from .engine import check_chroma_loc
-    check_chroma_loc(chroma_loc, kw["dither"], kw["pix_fmt"], kw["out_pix_fmt"])
+    if rgb_src is not None:
+        if chroma_loc is not None:
+            raise ValueError("chroma siting (chroma_loc) is not defined for an RGB source")
+    else:
+        check_chroma_loc(chroma_loc, kw["dither"], kw["pix_fmt"], kw["out_pix_fmt"])
     if chroma_loc is not None:
         kw["chroma_loc"] = chroma_loc
     if out_size is not None:
@@ -176,7 +215,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
             eng._applied_lut = lut
         if eng.precision != precision:
             eng.set_precision(precision)
-        result = eng.apply_yuv(planes, out, **kw)
+        result = eng.apply_rgb_to_yuv(planes, out, **kw) if rgb_src is not None else eng.apply_yuv(planes, out, **kw)
         if own:
             eng.sync()
     return result, output_color_tags(plan.output_policy)

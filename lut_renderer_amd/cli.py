@@ -42,7 +42,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("-i", "--input", required=True)
     ap.add_argument("-o", "--output", required=True)
     ap.add_argument("--size", required=True, help="WxH")
-    ap.add_argument("--pix-fmt", required=True)
+    ap.add_argument("--pix-fmt", required=True,
+                    help="planar YUV, or an RGB source (gbrp* / rgb24, bgr24, rgba .., rgb48le, rgba64le) with a YUV --out-pix-fmt")
     ap.add_argument("--out-pix-fmt", default=None)
     ap.add_argument("--cube", required=True)
     ap.add_argument("--interp", default="tetrahedral")
@@ -84,6 +85,9 @@ def plan_from_args(args):
     kw = engine_call_for(plan, args.pix_fmt, args.out_pix_fmt)
     if args.zscale_dither == "error_diffusion":
         kw["dither"] = "error_diffusion"
+    from .api import is_rgb_call
+    if getattr(args, "chroma_loc", None) and is_rgb_call(kw):
+        raise ValueError("chroma siting (--chroma-loc) is not defined for an RGB source")
     if getattr(args, "chroma_loc", None):
         from .engine import check_chroma_loc
         check_chroma_loc(args.chroma_loc, kw.get("dither", "none"), kw["pix_fmt"], kw["out_pix_fmt"])

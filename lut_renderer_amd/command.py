@@ -282,6 +282,13 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     cmd += ["-i", str(source), "-o", str(output), "--size", f"{source_info.width}x{source_info.height}",
             "--pix-fmt", source_info.pix_fmt]
     pix_fmt = resolve_pix_fmt(params, source_info, notes) if params.video_codec else ""
+    if _is_rgb_source(source_info.pix_fmt):
+        # an RGB source: the engine has no encoder to negotiate an output format with, and no chroma to site
+        if not pix_fmt:
+            raise ValueError(f"an RGB source ('{source_info.pix_fmt}') needs a resolved output pixel format (params.pix_fmt or a "
+                             "bit-depth policy that picks one): the engine cannot leave it to the encoder")
+        if chroma_loc is not None:
+            raise ValueError("chroma siting (chroma_loc) is not defined for an RGB source")
     if pix_fmt:
         cmd += ["--out-pix-fmt", pix_fmt]
     cmd += ["--cube", str(plan.lut_path), "--interp", plan.interp, "--input-matrix", plan.matrix_policy,
@@ -311,6 +318,13 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
             raise ValueError(f"bad resolution '{params.resolution}' (expected WxH)")
         cmd += ["--out-size", params.resolution]
     return cmd
+
+
+def _is_rgb_source(pix_fmt) -> bool:
+    """gbrp* or one of the packed RGB names the engine takes as a source (`_native.PACKED_FORMATS`)."""
+    from ._native import PACKED_FORMATS
+    name = str(pix_fmt or "")
+    return name in PACKED_FORMATS or bool(re.match(r"^gbrp(\d+)?(le)?$", name))
 
 
 #: planar formats the engine's resize takes (DESIGN.md 3.7); packed RGB keeps -s on the encoder

@@ -191,6 +191,18 @@ int make_yuv_consts_sited(const lutr_yuv_params &p, int loc, YuvConsts *o)
     return LUTR_OK;
 }
 
+// an RGB source at depth lut_depth.  Only the output side enters the kernels; matrix_in, range_src, range_in and
+// the depth of fmt_in are ignored (the block's input-stage entries are filled from the output side's matrix and range so that
+// the call cannot fail on them).  The output-stage entries are yuv_consts_n's for a 4:4:4 source at that depth.
+int make_yuv_consts_rgb2yuv(const lutr_yuv_params &p, YuvConsts *o)
+{
+    lutr_yuv_params q = p;
+    q.fmt_in = LUTR_FMT(p.lut_depth & 0xff, 0, 0);
+    q.matrix_in = p.matrix_out;
+    q.range_src = q.range_in = p.range_out;
+    return yuv_consts_n(q, 1 << (LUTR_FMT_CSX(p.fmt_out) + LUTR_FMT_CSY(p.fmt_out)), o);
+}
+
 
 // ---------------------------------------------------------------- output resize tables
 // The bicubic of libswscale's SWS_BICUBIC defaults (B = 0, C = 0.6).  Evaluated in this exact order: tests/_resize_twin.py
@@ -1076,6 +1088,123 @@ int lutr_apply_yuv_xsub(lutr_ctx *c, const lutr_yuv_params *p, int interp, int d
     return finish_launch(c, launch_yuv_dither(c->stream, L, K, P, G, F, din, dout, icsx, icsy, interp, ocsx, ocsy));
 }
 
+
+int lutr_yuv_constants_rgb2yuv(const lutr_yuv_params *p, float out[32])
+{
+    if (!p || !out) {
+        set_error("lutr_yuv_constants_rgb2yuv: null argument");
+        return LUTR_EINVAL;
+    }
+    YuvConsts k;
+    const int rc = make_yuv_consts_rgb2yuv(*p, &k);
+    if (rc) return rc;
+    std::memcpy(out, &k, sizeof(k));
+    return LUTR_OK;
+}
+
+int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dither, int src_kind, int w, int h, int nframes,
+                          const lutr_planes *src_planar, const lutr_packed *src_packed, const lutr_planes *dst, int row0, int rows)
+{
+    if (dither != LUTR_DITHER_NONE && dither != LUTR_DITHER_ERROR_DIFFUSION) { set_error("unknown dither mode %d", dither); return LUTR_EINVAL; }
+    const bool packed = src_kind != 0;
+    const void *src = packed ? (const void *)src_packed : (const void *)src_planar;
+    if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
+    if (interp != LUTR_INTERP_NONE && !c->lat) { set_error("no lattice set on this context (call lutr_ctx_set_lut first)"); return LUTR_EINVAL; }
+    if (interp < LUTR_INTERP_NONE || interp > LUTR_INTERP_PRISM) { set_error("unknown interpolation mode %d", interp); return LUTR_EINVAL; }
+    if (w < 0 || h < 0 || nframes < 0 || row0 < 0 || rows < 0 || row0 + rows > h) {
+        set_error("bad geometry w=%d h=%d nframes=%d row0=%d rows=%d", w, h, nframes, row0, rows);
+        return LUTR_EINVAL;
+    }
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    YuvConsts K;
+    int rc = make_yuv_consts_rgb2yuv(*p, &K);
+    if (rc) return rc;
+    const int dl = p->lut_depth, dout = LUTR_FMT_DEPTH(p->fmt_out);
+    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
+    RgbLayout Y{1, dl > 8, 0, 0, 0};
+    if (packed) {
+        const int bits = LUTR_PACKED_BITS(src_kind), nc = LUTR_PACKED_NCOMP(src_kind);
+        const int ro = LUTR_PACKED_RO(src_kind), go = LUTR_PACKED_GO(src_kind), bo = LUTR_PACKED_BO(src_kind);
+        if ((bits != 8 && bits != 16) || (nc != 3 && nc != 4) || (src_kind >> 24) || ro >= nc || go >= nc || bo >= nc ||
+            ro == go || go == bo || ro == bo) {
+            set_error("unsupported packed format 0x%x", src_kind);
+            return LUTR_EINVAL;
+        }
+        if (dl != bits) { set_error("lut_depth %d must be the packed source's depth %d", dl, bits); return LUTR_EINVAL; }
+        Y = RgbLayout{nc, bits == 16, ro, go, bo};
+    }
+    if (dither == LUTR_DITHER_ERROR_DIFFUSION && (row0 != 0 || rows != h)) {
+        set_error("error-diffusion dither couples the rows of a frame: whole frames only (row0 = 0, rows = h)");
+        return LUTR_EINVAL;
+    }
+    const int bh = 1 << ocsy;
+    if (row0 % bh || (rows % bh && row0 + rows != h)) {
+        set_error("row0/rows must be multiples of the output chroma block height %d", bh);
+        return LUTR_EINVAL;
+    }
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    // source streams in R, G, B order: gbrp planes are G, B, R
+    PlaneSet P{};
+    const long long bsi = Y.wide ? 2 : 1;
+    if (packed) {
+        if (!src_packed->data) { set_error("null image"); return LUTR_EINVAL; }
+        if (Y.wide && (((uintptr_t)src_packed->data | (uintptr_t)src_packed->stride |
+                        (nframes > 1 ? (uintptr_t)src_packed->frame_stride : 0)) & 1)) {
+            set_error("16-bit packed formats need 2-byte aligned rows");
+            return LUTR_EINVAL;
+        }
+        for (int k = 0; k < 3; k++) {
+            P.s[k] = (const uint8_t *)src_packed->data; P.ss[k] = src_packed->stride; P.sfs[k] = src_packed->frame_stride;
+        }
+    } else {
+        static const int gbr[3] = {2, 0, 1};              // R, G, B <- planes 2, 0, 1
+        for (int k = 0; k < 3; k++) {
+            if (!src_planar->data[gbr[k]]) { set_error("null plane %d", gbr[k]); return LUTR_EINVAL; }
+            P.s[k] = (const uint8_t *)src_planar->data[gbr[k]]; P.ss[k] = src_planar->stride[gbr[k]];
+            P.sfs[k] = src_planar->frame_stride[gbr[k]];
+        }
+    }
+    for (int i = 0; i < 3; i++) {
+        if (!dst->data[i]) { set_error("null plane %d", i); return LUTR_EINVAL; }
+        P.d[i] = (uint8_t *)dst->data[i]; P.ds[i] = dst->stride[i]; P.dfs[i] = dst->frame_stride[i];
+    }
+    // a chroma sample is written by one thread while another may still read the pixels of its block: no in-place operation
+    const int cw = (w + (1 << ocsx) - 1) >> ocsx, ch = (h + bh - 1) >> ocsy;
+    for (int i = 0; i < (packed ? 1 : 3); i++) {
+        uintptr_t slo, shi;
+        plane_span(P.s[i], P.ss[i], P.sfs[i], h, (long long)w * Y.step * bsi, nframes, &slo, &shi);
+        for (int j = 0; j < 3; j++) {
+            uintptr_t dlo, dhi;
+            plane_span(P.d[j], P.ds[j], P.dfs[j], j ? ch : h, (long long)(j ? cw : w) * (dout > 8 ? 2 : 1), nframes, &dlo, &dhi);
+            if (slo < dhi && dlo < shi) {
+                set_error("RGB -> YUV cannot run in place: the byte range of the source overlaps that of destination plane %d (bounding ranges over all rows and frames must be disjoint)", j);
+                return LUTR_EINVAL;
+            }
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
+    LutConsts L{};
+    FrameGeom G{w, h, row0, rows, nframes};
+    if (interp != LUTR_INTERP_NONE)
+        if (const int rc = fill_lut(&L, c, dl)) return rc;
+    if (dither == LUTR_DITHER_NONE)
+        return finish_launch(c, launch_rgb2yuv(c->stream, c->variant, L, K, P, Y, G, dout, ocsx, ocsy, interp));
+    const size_t ny = (size_t)w * h * nframes, nc = (size_t)cw * ch * nframes;
+    if (ny + 2 * nc > c->fscratch_floats) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (c->fscratch) (void)hipFree(c->fscratch);
+        c->fscratch = nullptr;
+        c->fscratch_floats = 0;
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, (ny + 2 * nc) * sizeof(float));
+        if (e != hipSuccess) { set_error("hipMalloc(%zu): %s", (ny + 2 * nc) * sizeof(float), hipGetErrorString(e)); return LUTR_ENOMEM; }
+        c->fscratch = (float *)q;
+        c->fscratch_floats = ny + 2 * nc;
+    }
+    FloatPlanes F{c->fscratch, c->fscratch + ny, c->fscratch + ny + nc};
+    return finish_launch(c, launch_rgb2yuv_dither(c->stream, L, K, P, Y, G, F, dout, ocsx, ocsy, interp));
+}
 
 int lutr_resize_filter(int src, int dst, int cs, int cosited, int *start, int16_t *weights, int *ntaps)
 {

@@ -230,7 +230,14 @@ const char *launch_yuv_dither(hipStream_t st, const LutConsts &L, const YuvConst
         if (gb > 256 * 64) gb = 256 * 64;
         hipLaunchKernelGGL(k_yuv_float, dim3((unsigned)gb), dim3(256), 0, st, L, K, P, G, F, win, csx, csy, mode);
     }
-    // pass 2 works on the output planes: chroma sized from the output layout (ocsx, ocsy)
+    return launch_dither_ed(st, K, P, G, F, wout, ocsx, ocsy) ? "k_yuv_float+k_dither_ed" : nullptr;
+}
+
+// pass 2 alone (also the RGB -> YUV path's, lutr_rgb2yuv.hip): the output planes, chroma sized from the output layout (ocsx, ocsy);
+// false = rows too wide for the LDS error rows
+bool launch_dither_ed(hipStream_t st, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const FloatPlanes &F, int wout,
+                      int ocsx, int ocsy)
+{
     // waves per workgroup = bands of one plane in flight: as many as the LDS error rows allow (144 KB of the
     // CU's 160 KB: one workgroup per CU, and a batch of 64 frames is 192 workgroups for 256 CUs), at most 8
     int nw = (int)((144 * 1024) / ((size_t)(G.w + 2) * sizeof(float) + sizeof(int)));
@@ -239,7 +246,7 @@ const char *launch_yuv_dither(hipStream_t st, const LutConsts &L, const YuvConst
     const int nbands = (G.h + 63) / 64;
     if (nw > nbands) nw = nbands;
     const size_t lds = (size_t)nw * ((size_t)(G.w + 2) * sizeof(float) + sizeof(int));
-    if (lds > 160 * 1024) return nullptr;                 // rows wider than ~40,000 samples: not supported
+    if (lds > 160 * 1024) return false;                   // rows wider than ~40,000 samples: not supported
     {   // dynamic LDS above 64 KB has to be allowed per kernel and device
         static std::set<int> done;
         static std::mutex mu;
@@ -261,7 +268,7 @@ const char *launch_yuv_dither(hipStream_t st, const LutConsts &L, const YuvConst
     const dim3 grid((unsigned)(3 * G.nframes)), block(64 * nw);
     if (vec) hipLaunchKernelGGL((k_dither_ed<true>), grid, block, lds, st, F, P, G, ocsx, ocsy, K.max_o, wout);
     else hipLaunchKernelGGL((k_dither_ed<false>), grid, block, lds, st, F, P, G, ocsx, ocsy, K.max_o, wout);
-    return "k_yuv_float+k_dither_ed";
+    return true;
 }
 
 }  // namespace lutr

@@ -125,6 +125,32 @@ LUTR_XS_DECL(w00) LUTR_XS_DECL(w11) LUTR_XS_DECL(w10)
 void launch_yuv_float_xsub(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
                            const FloatPlanes &F, int win, int icsx, int icsy, int ocsx, int ocsy, int interp);
 
+// pass 2 of the dither path alone (k_dither_ed on the float planes F, chroma planes in the output layout); false = rows too wide
+bool launch_dither_ed(hipStream_t st, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const FloatPlanes &F, int wout,
+                      int ocsx, int ocsy);
+
+// RGB source -> YUV output (lutr_rgb2yuv.hip).  The source travels in PlaneSet::s as three component streams in
+// R, G, B order: planar = the three planes (step 1, offsets 0); packed = the image's base three times, `step` components per
+// pixel, component index ro / go / bo inside a pixel.  PlaneSet::d is Y, Cb, Cr.
+struct RgbLayout {
+    int step;          // components per pixel in a stream: 1 planar, 3 | 4 packed
+    int wide;          // 16-bit container
+    int ro, go, bo;    // component index of R, G, B inside a pixel (0 for planar)
+};
+// mode: LUTR_INTERP_*, or -1 = no lut3d (the source codes go straight to the output stage).  nullptr = the variant cannot take
+// the call (vec_lds always; vec_global on layouts the vector kernel cannot take)
+const char *launch_rgb2yuv(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
+                           const RgbLayout &Y, const FrameGeom &G, int dout, int ocsx, int ocsy, int mode);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>): nullptr = not a layout / mode it has
+#define LUTR_R2Y_DECL(tag) \
+    const char *launch_rgb2yuv_vec_##tag(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, \
+                                         const RgbLayout &Y, const FrameGeom &G, int ocsx, int ocsy, int mode);
+LUTR_R2Y_DECL(w00) LUTR_R2Y_DECL(w11) LUTR_R2Y_DECL(w10)
+#undef LUTR_R2Y_DECL
+// the dither path: the unquantised pass by output blocks (k_rgb2yuv_float), then k_dither_ed; whole frames
+const char *launch_rgb2yuv_dither(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const RgbLayout &Y,
+                                  const FrameGeom &G, const FloatPlanes &F, int dout, int ocsx, int ocsy, int mode);
+
 // round-2 tile kernels (lutr_tile2.hip, one translation unit per format: w<in wide><out wide>_c<csx><csy>); nullptr =
 // this combination is not built / cannot take the call, the caller falls back
 #define LUTR_T2_DECL(tag) \
@@ -177,6 +203,7 @@ const char *launch_rgb_tile(hipStream_t st, const LutConsts &L, const PlaneSet &
 int make_yuv_consts(const lutr_yuv_params &p, YuvConsts *out);
 int make_yuv_consts_xsub(const lutr_yuv_params &p, YuvConsts *out);
 int make_yuv_consts_sited(const lutr_yuv_params &p, int chroma_loc, YuvConsts *out);
+int make_yuv_consts_rgb2yuv(const lutr_yuv_params &p, YuvConsts *out);
 void set_error(const char *fmt, ...);
 
 }  // namespace lutr

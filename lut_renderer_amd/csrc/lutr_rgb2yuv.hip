@@ -1,0 +1,338 @@
+// lutr_rgb2yuv.hip -- gfx950 kernels of the fused pass for RGB sources with a YUV output.
+//
+// What they replace: the reference's chain on an RGB source (a PNG / TIFF / DPX sequence, an RGB screen recording):
+//   lut3d=file=...:interp=...   directly on the RGB frame                 (ffmpeg.py:246)
+//   format=<pix_fmt>            RGB -> YUV at the output depth and layout (ffmpeg.py:304-310)
+// The contract is a composition of pinned pieces: 3.1 (lut3d on integer RGB at the source's depth) and the last stage of 3.2
+// (integer RGB -> YUV; Y per pixel, each chroma sample from the sum of the LUT's integer RGB over its OUTPUT block, 1/n folded
+// into cbr..crb; a partial block at an odd edge takes the edge column / row again).  mode = -1 leaves the LUT out: the source
+// codes go straight to the output stage (stage 0 of the full-range composition, 3.9 point 6).
+//
+// The source arrives as three component streams in R, G, B order (lutr_internal.h RgbLayout): planar gbrp, or one packed image.
+//
+// One source, two kinds of translation unit (Makefile R2Y_RULE), like lutr_xsub.hip:
+//   without LUTR_R2Y_WI   the generic kernel, the unquantised pass of the dither path and the launcher
+//   LUTR_R2Y_WI / _WO     the vector kernels of one container mix (8 -> 8, 16 -> 16, 16 -> 8): 3 source kinds x 3 layouts x 4 modes
+#include "lutr_device.h"
+
+namespace lutr {
+
+#ifdef LUTR_R2Y_WI
+// ================================================================= vector kernel, global gather
+// k_yuv_xsub_vec's structure with the input side replaced: whole-dword loads and stores, 8 luma samples per thread and row,
+// 2^OCSY rows per thread, lattice taps gathered from L1/L2.  NC = 1: three planes; 3 | 4: one packed image (8 pixels = 6, 8, 12 or
+// 16 dwords per row, unpacked as k_packed_vec does).  The component order of a packed source is a wave-uniform argument.
+
+// component `off` (runtime, wave-uniform) of pixel i of a 4-component run
+template <int WIDE>
+__device__ __forceinline__ float r2y_comp4(const uint32_t *w, int i, int off)
+{
+    if constexpr (WIDE) {
+        const unsigned long long pv = ((unsigned long long)w[2 * i + 1] << 32) | w[2 * i];
+        return (float)(unsigned)((pv >> (off * 16)) & 0xffffull);
+    } else {
+        return (float)((w[i] >> (off * 8)) & 0xffu);
+    }
+}
+
+template <int WIN, int NC>
+__device__ __forceinline__ Rgb r2y_pixel(const uint32_t *in, int i, const RgbLayout &Y)
+{
+    constexpr int SW = 8 * (WIN ? 2 : 1) / 4;             // dwords of 8 samples of one plane
+    if constexpr (NC == 1) {
+        return Rgb{word_sample<WIN>(in, i), word_sample<WIN>(in + SW, i), word_sample<WIN>(in + 2 * SW, i)};
+    } else if constexpr (NC == 3) {
+        const float c0 = word_sample<WIN>(in, i * 3), c1 = word_sample<WIN>(in, i * 3 + 1), c2 = word_sample<WIN>(in, i * 3 + 2);
+        const bool swap = Y.ro != 0;                      // bgr order
+        return Rgb{swap ? c2 : c0, c1, swap ? c0 : c2};
+    } else {
+        return Rgb{r2y_comp4<WIN>(in, i, Y.ro), r2y_comp4<WIN>(in, i, Y.go), r2y_comp4<WIN>(in, i, Y.bo)};
+    }
+}
+
+template <int WIN, int NC, int WOUT, int OCSX, int OCSY, int INTERP>
+__global__ __launch_bounds__(256) void k_rgb2yuv_vec(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, RgbLayout Y)
+{
+    constexpr int PXT = 8;                                        // luma samples per thread per row
+    constexpr int SW = PXT * (WIN ? 2 : 1) / 4;                   // dwords of 8 samples of one component
+    constexpr int NWI = (NC == 1 ? 3 : NC) * SW;                  // source dwords per thread per row
+    constexpr int YWO = PXT * (WOUT ? 2 : 1) / 4;                 // luma words out per thread per row
+    constexpr int BW = 1 << OCSX, BH = 1 << OCSY;                 // the output chroma block
+    constexpr int NB = PXT / BW;                                  // blocks per thread
+    constexpr int CWO = (PXT >> OCSX) * (WOUT ? 2 : 1) / 4;       // chroma words out per thread
+    static_assert(NB >= 1 && CWO >= 1 && YWO >= 1, "a thread must own whole words");
+    const GFetch f(L);
+    const unsigned uw = (unsigned)G.w / PXT;
+    const unsigned ub = (unsigned)G.rows >> OCSY;
+    const unsigned total = uw * ub * (unsigned)G.nframes;
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= total) return;
+    const unsigned xu = u % uw, t = u / uw;
+    const int y0 = ((G.row0 >> OCSY) + (int)(t % ub)) * BH;       // first luma row of the thread
+    const long long fr = t / ub;
+    const long long xo = (long long)xu * (YWO * 4), cxo = (long long)xu * (CWO * 4);
+
+    uint32_t in[BH][NWI];
+    uint32_t yo[BH][YWO], cbo[CWO], cro[CWO];
+#pragma unroll
+    for (int dy = 0; dy < BH; dy++) {
+        if constexpr (NC == 1) {
+#pragma unroll
+            for (int k = 0; k < 3; k++)
+                ld_words<SW>(in[dy] + k * SW, P.s[k] + fr * P.sfs[k] + (long long)(y0 + dy) * P.ss[k] + (long long)xu * (SW * 4));
+        } else {
+            const uint32_t *sp = (const uint32_t *)(P.s[0] + fr * P.sfs[0] + (long long)(y0 + dy) * P.ss[0]) + (size_t)xu * NWI;
+#pragma unroll
+            for (int k = 0; k < NWI; k++) in[dy][k] = sp[k];
+        }
+#pragma unroll
+        for (int k = 0; k < YWO; k++) yo[dy][k] = 0;
+    }
+#pragma unroll
+    for (int k = 0; k < CWO; k++) { cbo[k] = 0; cro[k] = 0; }
+
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+        float rs = 0.f, gs = 0.f, bs = 0.f;
+#pragma unroll
+        for (int dy = 0; dy < BH; dy++) {
+#pragma unroll
+            for (int dx = 0; dx < BW; dx++) {
+                const int i = j * BW + dx;
+                const Rgb q = r2y_pixel<WIN, NC>(in[dy], i, Y);
+                Rgb o;
+                if constexpr (INTERP < 0) o = q;
+                else o = lut3d_px<INTERP>(L, f, q.r, q.g, q.b);
+                rs += o.r; gs += o.g; bs += o.b;
+                word_put<WOUT>(yo[dy], i, rgb_to_y(K, o));
+            }
+        }
+        word_put<WOUT>(cbo, j, rgb_to_cb(K, rs, gs, bs));
+        word_put<WOUT>(cro, j, rgb_to_cr(K, rs, gs, bs));
+        // Zero-instruction fence (k_yuv_vec's): keeps hipcc from hoisting the coordinates and taps of every block of the thread
+        // to the top; with it the blocks are emitted one after the other.
+#pragma unroll
+        for (int dy = 0; dy < BH; dy++) {
+#pragma unroll
+            for (int k = 0; k < NWI; k++) asm volatile("" : "+v"(in[dy][k]));
+#pragma unroll
+            for (int k = 0; k < YWO; k++) asm volatile("" : "+v"(yo[dy][k]));
+        }
+#pragma unroll
+        for (int k = 0; k < CWO; k++) asm volatile("" : "+v"(cbo[k]), "+v"(cro[k]));
+    }
+#pragma unroll
+    for (int dy = 0; dy < BH; dy++)
+        st_words<YWO>(P.d[0] + fr * P.dfs[0] + (long long)(y0 + dy) * P.ds[0] + xo, yo[dy]);
+    const long long r = (long long)(y0 >> OCSY);
+    st_words<CWO>(P.d[1] + fr * P.dfs[1] + r * P.ds[1] + cxo, cbo);
+    st_words<CWO>(P.d[2] + fr * P.dfs[2] + r * P.ds[2] + cxo, cro);
+}
+
+#define R2Y_CAT2(a, b) a##b
+#define R2Y_CAT(a, b) R2Y_CAT2(a, b)
+#define R2Y_STR2(x) #x
+#define R2Y_STR(x) R2Y_STR2(x)
+
+// The vector kernels of this translation unit's container mix; the layout checks are the caller's (launch_rgb2yuv).
+const char *R2Y_CAT(R2Y_CAT(launch_rgb2yuv_vec_w, LUTR_R2Y_WI), LUTR_R2Y_WO)(hipStream_t st, const LutConsts &L, const YuvConsts &K,
+                                                                          const PlaneSet &P, const RgbLayout &Y, const FrameGeom &G,
+                                                                          int ocsx, int ocsy, int mode)
+{
+    constexpr int WI = LUTR_R2Y_WI, WO = LUTR_R2Y_WO;
+    const long long units = (long long)(G.w / 8) * (G.rows >> ocsy) * G.nframes;
+    const dim3 grid((unsigned)((units + 255) / 256)), block(256);
+#define R2Y_CASE(C, OX, OY, I, IN) \
+    if (Y.step == C && ocsx == OX && ocsy == OY && mode == I) { \
+        hipLaunchKernelGGL((k_rgb2yuv_vec<WI, C, WO, OX, OY, I>), grid, block, 0, st, L, K, P, G, Y); \
+        return "k_rgb2yuv_vec<" R2Y_STR(LUTR_R2Y_WI) "," #C "," R2Y_STR(LUTR_R2Y_WO) "," #OX "," #OY "," IN ">"; \
+    }
+#define R2Y_LAYOUT(C, OX, OY) R2Y_CASE(C, OX, OY, -1, "nolut") R2Y_CASE(C, OX, OY, 0, "0") R2Y_CASE(C, OX, OY, 1, "1") R2Y_CASE(C, OX, OY, 2, "2")
+#define R2Y_SRC(C) R2Y_LAYOUT(C, 1, 1) R2Y_LAYOUT(C, 1, 0) R2Y_LAYOUT(C, 0, 0)
+    R2Y_SRC(1) R2Y_SRC(3) R2Y_SRC(4)
+#undef R2Y_SRC
+#undef R2Y_LAYOUT
+#undef R2Y_CASE
+    return nullptr;
+}
+
+#else  // !LUTR_R2Y_WI
+// ================================================================= generic kernels
+// One thread per output chroma block; any depth, stride or alignment, odd sizes, all five modes and the LUT-free form.  A pixel
+// outside the frame is the edge pixel again, so a partial block sums the edge column / row twice, like np.pad(mode="edge"); only
+// pixels inside the planes are written.
+template <class Sink>
+__device__ __forceinline__ void r2y_block(const LutConsts &L, const GFetch &f, const PlaneSet &P, const RgbLayout &Y,
+                                          const FrameGeom &G, long long fr, int cx, int cy, int ocsx, int ocsy, int mode, Sink &sink)
+{
+    const int obw = 1 << ocsx, obh = 1 << ocsy;
+    float rs = 0.f, gs = 0.f, bs = 0.f;
+    for (int dy = 0; dy < obh; dy++) {
+        const int yy = cy * obh + dy;
+        const int y = yy < G.h ? yy : G.h - 1;
+        for (int dx = 0; dx < obw; dx++) {
+            const int xx = cx * obw + dx;
+            const int x = xx < G.w ? xx : G.w - 1;
+            const int e = x * Y.step;
+            const float r = ld_sample(P.s[0] + fr * P.sfs[0] + (long long)y * P.ss[0], e + Y.ro, Y.wide);
+            const float g = ld_sample(P.s[1] + fr * P.sfs[1] + (long long)y * P.ss[1], e + Y.go, Y.wide);
+            const float b = ld_sample(P.s[2] + fr * P.sfs[2] + (long long)y * P.ss[2], e + Y.bo, Y.wide);
+            const Rgb o = mode < 0 ? Rgb{r, g, b} : lut3d_px_rt(mode, L, f, r, g, b);
+            rs += o.r; gs += o.g; bs += o.b;
+            if (yy < G.h && xx < G.w) sink.luma(fr, x, y, o);
+        }
+    }
+    sink.chroma(fr, cx, cy, rs, gs, bs);
+}
+
+struct R2yPlaneSink {
+    const YuvConsts &K;
+    const PlaneSet &P;
+    int wout;
+    __device__ __forceinline__ void luma(long long fr, int x, int y, const Rgb &o)
+    {
+        st_sample(P.d[0] + fr * P.dfs[0] + (long long)y * P.ds[0], x, wout, rgb_to_y(K, o));
+    }
+    __device__ __forceinline__ void chroma(long long fr, int cx, int cy, float rs, float gs, float bs)
+    {
+        st_sample(P.d[1] + fr * P.dfs[1] + (long long)cy * P.ds[1], cx, wout, rgb_to_cb(K, rs, gs, bs));
+        st_sample(P.d[2] + fr * P.dfs[2] + (long long)cy * P.ds[2], cx, wout, rgb_to_cr(K, rs, gs, bs));
+    }
+};
+
+// the dither path's pass 1 (k_yuv_float's values, lutr_dither.hip): unquantised planes, densely packed per frame
+struct R2yFloatSink {
+    const YuvConsts &K;
+    const FloatPlanes &F;
+    const FrameGeom &G;
+    int cw, ch;
+    __device__ __forceinline__ void luma(long long fr, int x, int y, const Rgb &o)
+    {
+        F.y[(fr * G.h + y) * G.w + x] = fma_(K.cyr, o.r, fma_(K.cyg, o.g, fma_(K.cyb, o.b, K.yob))) - 0.5f;
+    }
+    __device__ __forceinline__ void chroma(long long fr, int cx, int cy, float rs, float gs, float bs)
+    {
+        F.cb[(fr * ch + cy) * cw + cx] = fma_(K.cbr, rs, fma_(K.cbg, gs, fma_(K.cbb, bs, K.cob))) - 0.5f;
+        F.cr[(fr * ch + cy) * cw + cx] = fma_(K.crr, rs, fma_(K.crg, gs, fma_(K.crb, bs, K.cob))) - 0.5f;
+    }
+};
+
+__global__ __launch_bounds__(256) void k_rgb2yuv_generic(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, RgbLayout Y, int wout,
+                                                         int ocsx, int ocsy, int mode)
+{
+    const GFetch f(L);
+    const int cw = (G.w + (1 << ocsx) - 1) >> ocsx;
+    const int cr0 = G.row0 >> ocsy;
+    const int crows = ((G.row0 + G.rows + (1 << ocsy) - 1) >> ocsy) - cr0;
+    const long long total = (long long)cw * crows * G.nframes;
+    R2yPlaneSink sink{K, P, wout};
+    for (long long u = blockIdx.x * 256ll + threadIdx.x; u < total; u += (long long)gridDim.x * 256ll) {
+        const int cx = (int)(u % cw);
+        const long long t = u / cw;
+        const int cy = cr0 + (int)(t % crows);
+        const long long fr = t / crows;
+        r2y_block(L, f, P, Y, G, fr, cx, cy, ocsx, ocsy, mode, sink);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_rgb2yuv_float(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, RgbLayout Y, FloatPlanes F,
+                                                       int ocsx, int ocsy, int mode)
+{
+    const GFetch f(L);
+    const int cw = (G.w + (1 << ocsx) - 1) >> ocsx, ch = (G.h + (1 << ocsy) - 1) >> ocsy;
+    const long long total = (long long)cw * ch * G.nframes;
+    R2yFloatSink sink{K, F, G, cw, ch};
+    for (long long u = blockIdx.x * 256ll + threadIdx.x; u < total; u += (long long)gridDim.x * 256ll) {
+        const int cx = (int)(u % cw);
+        const long long t = u / cw;
+        const int cy = (int)(t % ch);
+        const long long fr = t / ch;
+        r2y_block(L, f, P, Y, G, fr, cx, cy, ocsx, ocsy, mode, sink);
+    }
+}
+
+static unsigned r2y_grid(long long units)
+{
+    long long b = (units + 255) / 256;
+    if (b < 1) b = 1;
+    if (b > 256 * 64) b = 256 * 64;                       // grid-stride: enough blocks to fill 256 CUs x 8
+    return (unsigned)b;
+}
+
+const char *launch_rgb2yuv_dither(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const RgbLayout &Y,
+                                  const FrameGeom &G, const FloatPlanes &F, int dout, int ocsx, int ocsy, int mode)
+{
+    const long long units = (long long)((G.w + (1 << ocsx) - 1) >> ocsx) * ((G.h + (1 << ocsy) - 1) >> ocsy) * G.nframes;
+    hipLaunchKernelGGL(k_rgb2yuv_float, dim3(r2y_grid(units)), dim3(256), 0, st, L, K, P, G, Y, F, ocsx, ocsy, mode);
+    return launch_dither_ed(st, K, P, G, F, dout > 8, ocsx, ocsy) ? "k_rgb2yuv_float+k_dither_ed" : nullptr;
+}
+
+// ================================================================= launcher
+// a row set the vector kernel can address with `a`-byte accesses: positive stride, base, stride and (batches) frame stride aligned
+static bool r2y_plane_ok(const void *p, long long stride, long long fstride, long long a, bool batch)
+{
+    return stride > 0 && (uintptr_t)p % (uintptr_t)a == 0 && stride % a == 0 && (!batch || fstride % a == 0);
+}
+
+const char *launch_rgb2yuv(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
+                           const RgbLayout &Y, const FrameGeom &G, int dout, int ocsx, int ocsy, int mode)
+{
+    if (variant == VAR_VEC_LDS) return nullptr;          // no LDS kernel for this path
+    const int win = Y.wide, wout = dout > 8;
+    const int bh = 1 << ocsy;
+    // the vector kernels' unit: 8 luma samples per row; an 8-bit source written as 16 bit has none
+    const bool mix_ok = win == wout || (win && !wout);
+    const long long bsi = win ? 2 : 1, bso = wout ? 2 : 1;
+    const bool batch = G.nframes > 1;
+    // the 3-component vector body knows R G B and B G R order only
+    const bool order_ok = Y.step != 3 || (Y.go == 1 && ((Y.ro == 0 && Y.bo == 2) || (Y.ro == 2 && Y.bo == 0)));
+    auto vec_fits = [&](const PlaneSet &Q, const FrameGeom &H) {
+        if (!mix_ok || !order_ok || mode < -1 || mode > LUTR_INTERP_TETRAHEDRAL) return false;
+        if (H.w % 8 || H.row0 % bh || H.rows % bh) return false;
+        if ((long long)(H.w / 8) * (H.rows / bh) * H.nframes >= 0x7fffffffll) return false;
+        if (Y.step == 1) {
+            for (int c = 0; c < 3; c++)
+                if (!r2y_plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], 8 * bsi, batch)) return false;
+        } else if (!r2y_plane_ok(Q.s[0], Q.ss[0], Q.sfs[0], 4, batch)) {
+            return false;
+        }
+        if (!r2y_plane_ok(Q.d[0], Q.ds[0], Q.dfs[0], 8 * bso, batch)) return false;
+        for (int c = 1; c < 3; c++)
+            if (!r2y_plane_ok(Q.d[c], Q.ds[c], Q.dfs[c], (8 >> ocsx) * bso, batch)) return false;
+        return true;
+    };
+    auto vec = [&](const PlaneSet &Q, const FrameGeom &H) -> const char * {
+        if (win && wout) return launch_rgb2yuv_vec_w11(st, L, K, Q, Y, H, ocsx, ocsy, mode);
+        if (win) return launch_rgb2yuv_vec_w10(st, L, K, Q, Y, H, ocsx, ocsy, mode);
+        return launch_rgb2yuv_vec_w00(st, L, K, Q, Y, H, ocsx, ocsy, mode);
+    };
+    auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
+        const long long units = (long long)((H.w + (1 << ocsx) - 1) >> ocsx) * ((H.rows + bh - 1) >> ocsy) * H.nframes;
+        hipLaunchKernelGGL(k_rgb2yuv_generic, dim3(r2y_grid(units)), dim3(256), 0, st, L, K, Q, H, Y, wout, ocsx, ocsy, mode);
+        return "k_rgb2yuv_generic";
+    };
+    if (variant == VAR_GENERIC) return generic(P, G);
+    if (vec_fits(P, G)) return vec(P, G);
+    if (variant == VAR_VEC_GLOBAL) return nullptr;
+    // ragged width on aligned (padded) rows: the vector kernel up to the last whole unit, the generic kernel for the rest (the
+    // split falls on a chroma block boundary: the unit is 8 luma samples wide)
+    const int wv = G.w / 8 * 8;
+    if (wv > 0 && wv < G.w) {
+        FrameGeom Gv = G, Ge = G;
+        Gv.w = wv;
+        Ge.w = G.w - wv;
+        if (vec_fits(P, Gv)) {
+            PlaneSet Pe = P;
+            for (int c = 0; c < 3; c++) Pe.s[c] += (long long)wv * Y.step * bsi;
+            Pe.d[0] += wv * bso;
+            for (int c = 1; c < 3; c++) Pe.d[c] += (wv >> ocsx) * bso;
+            const char *name = vec(P, Gv);
+            generic(Pe, Ge);
+            return name;
+        }
+    }
+    return generic(P, G);
+}
+#endif  // LUTR_R2Y_WI
+
+}  // namespace lutr

@@ -68,6 +68,36 @@ def parse_pix_fmt(name: str) -> PixFmt:
     return PixFmt(name, "yuv", depth_i, csx, csy, fam == "yuvj")
 
 
+@dataclass(frozen=True)
+class RgbSource:
+    """An RGB source format of `LutEngine.apply_rgb_to_yuv`: planar `gbrp*` or a packed name of `_native.PACKED_FORMATS`."""
+    name: str
+    packed: bool
+    depth: int        # the depth lut3d runs at: the source's (packed: 8 or 16)
+    ncomp: int        # components per pixel of a packed image; 1 for planar
+    code: int         # src_kind of lutr_apply_rgb_to_yuv: 0 planar, else LUTR_PACKED(...)
+
+    @property
+    def itemsize(self) -> int:
+        return 1 if self.depth <= 8 else 2
+
+    def frame_bytes(self, w: int, h: int) -> int:
+        return h * w * (self.ncomp if self.packed else 3) * self.itemsize
+
+
+def parse_rgb_source(name: Optional[str]) -> Optional[RgbSource]:
+    """The RGB source `name` stands for, or None when it is not an RGB format the engine takes (`parse_pix_fmt` keeps rejecting
+    packed names: it describes planar frames)."""
+    if name in _native.PACKED_FORMATS:
+        bits, nc, ro, go, bo = _native.PACKED_FORMATS[name]
+        return RgbSource(name, True, bits, nc, _native.packed_code(bits, nc, ro, go, bo))
+    try:
+        fmt = parse_pix_fmt(name)
+    except ValueError:
+        return None
+    return RgbSource(name, False, fmt.depth, 1, 0) if fmt.family == "gbr" else None
+
+
 def chroma_loc_code(chroma_loc: Optional[str]) -> int:
     """enum lutr_chroma_loc for a chroma_location name (None = replicate); ValueError for any other name."""
     if chroma_loc is None:
@@ -141,6 +171,15 @@ def _check_not_in_place(src: Sequence[torch.Tensor], dst: Sequence[torch.Tensor]
             blo, bhi = _byte_range(b)
             if alo < bhi and blo < ahi:
                 raise ValueError("a resize cannot run in place: destination planes must not overlap the source planes")
+
+
+def _check_rgb_not_in_place(src, dst: Sequence[torch.Tensor]) -> None:
+    for a in ([src] if isinstance(src, torch.Tensor) else src):
+        alo, ahi = _byte_range(a)
+        for b in dst:
+            blo, bhi = _byte_range(b)
+            if alo < bhi and blo < ahi:
+                raise ValueError("RGB -> YUV cannot run in place: destination planes must not overlap the source")
 
 
 def _frames3(planes: Sequence[torch.Tensor]) -> list:
@@ -217,6 +256,7 @@ class LutEngine:
         self.precision = "strict"
         self._applied_lut = None          # the CubeLut object apply_lut uploaded last (its upload-skipping shortcut)
         self._rz_scratch = None           # source-size output of the LUT ahead of a resize: (key, [3 planes])
+        self._fr_scratch = None           # 8-bit YUV frames between the two stages of a full-range RGB source: (key, [3 planes])
 
     # -- lifetime ---------------------------------------------------------
     def close(self) -> None:
@@ -407,8 +447,8 @@ class LutEngine:
                                       for i in range(3)])
         return [t[:nframes] for t in self._rz_scratch[1]]
 
-    def _lut_then_resize(self, src, dst, fin: PixFmt, fout: PixFmt, w: int, h: int, out_size, row0: int, rows, chunk,
-                         chroma_loc, lut_call):
+    def _lut_then_resize(self, src, dst, fin: Optional[PixFmt], fout: PixFmt, w: int, h: int, out_size, row0: int, rows, chunk,
+                         chroma_loc, lut_call, src_frames=None):
         """The composition of DESIGN.md 3.7: the LUT into engine scratch at the source size, then the resize into dst, a chunk
         of frames at a time, both on the engine's stream with no host wait in between."""
         dw, dh = parse_size(out_size)
@@ -416,12 +456,13 @@ class LutEngine:
             raise ValueError("a resize (out_size) takes whole frames: row0 / rows are not supported with it")
         if dst is None:
             dt = torch.uint8 if fout.depth <= 8 else src[0].dtype if src[0].element_size() == 2 else torch.int16
-            lead = tuple(src[0].shape[:-2])
+            lead = tuple(src_frames[0].shape[:1]) if src_frames is not None else tuple(src[0].shape[:-2])
             dst = [torch.empty(lead + fout.plane_shape(i, dw, dh), dtype=dt, device=self.device) for i in range(3)]
-        _check_planes(src, fin, w, h, "source")
+        if src_frames is None:             # (a packed source comes checked, as a list of one [F,H,W,C] tensor, in src_frames)
+            _check_planes(src, fin, w, h, "source")
         _check_planes(dst, fout, dw, dh, "destination")
         _check_not_in_place(src, dst)
-        s3, d3 = _frames3(src), _frames3(dst)
+        s3, d3 = (_frames3(src) if src_frames is None else src_frames), _frames3(dst)
         nf = s3[0].shape[0]
         if d3[0].shape[0] != nf:
             raise ValueError("src and dst disagree on the number of frames")
@@ -539,6 +580,126 @@ class LutEngine:
                     self._ctx, C.byref(p), _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(d), row0, rows))
         return dst
 
+    # -- RGB source, YUV output --------------------------------
+    def _rgb_source(self, src, fmt: RgbSource):
+        """Validate an RGB source; returns (planar struct | None, packed struct | None, w, h, nframes, lead shape)."""
+        if not fmt.packed:
+            if isinstance(src, torch.Tensor) or len(src) != 3:
+                raise ValueError(f"'{fmt.name}' takes three planes (G, B, R)")
+            h, w = src[0].shape[-2], src[0].shape[-1]
+            _check_planes(src, PixFmt(fmt.name, "gbr", fmt.depth, 0, 0, True), w, h, "source")
+            st, nf = _planes_struct(src, self.device)
+            return st, None, w, h, nf, tuple(src[0].shape[:-2])
+        t = src
+        if not isinstance(t, torch.Tensor) or t.device != self.device:
+            raise ValueError("packed images must be torch tensors resident on the engine's GPU")
+        if t.dim() not in (3, 4) or t.shape[-1] != fmt.ncomp or t.is_floating_point() or t.element_size() * 8 != fmt.depth:
+            raise ValueError(f"'{fmt.name}' takes [H,W,{fmt.ncomp}] or [F,H,W,{fmt.ncomp}] tensors of {fmt.depth}-bit elements")
+        if t.stride(-1) != 1 or t.stride(-2) != fmt.ncomp:
+            raise ValueError("pixels must be dense along the row")
+        st = _native.Packed()
+        st.data = t.data_ptr()
+        st.stride = t.stride(-3) * t.element_size()
+        st.frame_stride = t.stride(0) * t.element_size() if t.dim() == 4 else 0
+        return None, st, t.shape[-2], t.shape[-3], (t.shape[0] if t.dim() == 4 else 1), tuple(t.shape[:-3])
+
+    def apply_rgb_to_yuv(self, src, dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: str,
+                         interp: str = "tetrahedral", matrix_out: str = "smpte170m", range_out: str = "tv", row0: int = 0,
+                         rows: Optional[int] = None, dither: str = "none", out_size=None, resize_chunk: Optional[int] = None,
+                         lut: bool = True, chroma_loc: Optional[str] = None, intermediate_pix_fmt: Optional[str] = None,
+                         prologue_out_range: Optional[str] = None):
+        """lut3d on an RGB source, then RGB -> YUV into planar `out_pix_fmt` (4:2:0 / 4:2:2 / 4:4:4, any depth), in one pass
+        (DESIGN.md 3.9).  `src` is three gbrp-ordered planes (G, B, R; `pix_fmt` = gbrp, gbrp9le .. gbrp16le) or one [F,]H,W,C
+        packed tensor (`pix_fmt` a name of `_native.PACKED_FORMATS`; a fourth component is dropped).  The LUT runs at the source's
+        depth; always strict arithmetic.  lut=False leaves lut3d out.  dither / out_size as for `apply_yuv`.  Not in place.
+        `intermediate_pix_fmt` / `prologue_out_range` (a LutPlan's fields for a source flagged full range) select the two-stage
+        composition of `apply_rgb_full_range`, with `matrix_out` as the plan's matrix."""
+        if dither not in _native.DITHER:
+            raise ValueError(f"unknown dither mode '{dither}'")
+        if chroma_loc is not None:
+            raise ValueError("chroma siting (chroma_loc) is not defined for an RGB source: it has no chroma samples to site")
+        fin = parse_rgb_source(pix_fmt)
+        if fin is None:
+            raise ValueError(f"apply_rgb_to_yuv takes gbrp* or packed RGB sources, not '{pix_fmt}'")
+        fout = parse_pix_fmt((out_pix_fmt or "").replace("yuvj", "yuv"))
+        if fout.family != "yuv":
+            raise ValueError("apply_rgb_to_yuv writes planar YUV formats; use apply_rgb / apply_packed for RGB output")
+        if intermediate_pix_fmt is not None:
+            return self.apply_rgb_full_range(src, dst, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt,
+                                             intermediate_pix_fmt=intermediate_pix_fmt, prologue_out_range=prologue_out_range,
+                                             matrix=matrix_out, interp=interp, range_out=range_out, row0=row0, rows=rows,
+                                             dither=dither, out_size=out_size, resize_chunk=resize_chunk)
+        planar, packed, w, h, nf, lead = self._rgb_source(src, fin)
+        if out_size is not None:
+            kw = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, interp=interp, matrix_out=matrix_out, range_out=range_out,
+                      dither=dither, lut=lut)
+            if fin.packed:
+                squeeze = src.dim() == 3
+                s4 = src.unsqueeze(0) if squeeze else src
+                d3 = dst if dst is None or not squeeze else [t.unsqueeze(0) for t in dst]
+                out = self._lut_then_resize([s4], d3, None, fout, w, h, out_size, row0, rows, resize_chunk, None,
+                                            lambda s_, d_: self.apply_rgb_to_yuv(s_[0], d_, **kw), src_frames=[s4])
+                return dst if dst is not None else [t[0] for t in out] if squeeze else out
+            return self._lut_then_resize(src, dst, PixFmt(fin.name, "gbr", fin.depth, 0, 0, True), fout, w, h, out_size, row0,
+                                         rows, resize_chunk, None, lambda s_, d_: self.apply_rgb_to_yuv(s_, d_, **kw))
+        if dst is None:
+            dt = torch.uint8 if fout.depth <= 8 else torch.int16
+            dst = [torch.empty(lead + fout.plane_shape(i, w, h), dtype=dt, device=self.device) for i in range(3)]
+        _check_planes(dst, fout, w, h, "destination")
+        d, nfd = _planes_struct(dst, self.device)
+        if nf != nfd:
+            raise ValueError("src and dst disagree on the number of frames")
+        rows = h - row0 if rows is None else rows
+        if dither != "none" and (row0 != 0 or rows != h):
+            raise ValueError("error-diffusion dither couples the rows of a frame: whole frames only")
+        _check_rgb_not_in_place(src if fin.packed else list(src), dst)
+        p = _native.YuvParams()
+        p.fmt_in, p.fmt_out = _native.fmt_code(fin.depth, 0, 0), fout.code
+        p.lut_depth = fin.depth
+        p.matrix_in = p.matrix_out = _native.MATRIX[matrix_out]
+        p.range_src = p.range_in = p.range_out = _native.RANGE[range_out]
+        mode = _native.INTERP[interp] if lut else _native.INTERP_NONE
+        with self._lock:
+            self._bind_stream()
+            _native.check(self._lib.lutr_apply_rgb_to_yuv(
+                self._ctx, C.byref(p), mode, _native.DITHER[dither], fin.code, w, h, nf,
+                C.byref(planar) if planar is not None else None, C.byref(packed) if packed is not None else None, C.byref(d),
+                row0, rows))
+        return dst
+
+    def apply_rgb_full_range(self, src, dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: str,
+                             intermediate_pix_fmt: str, prologue_out_range: Optional[str], matrix: Optional[str],
+                             interp: str = "tetrahedral", range_out: str = "tv", row0: int = 0, rows: Optional[int] = None,
+                             dither: str = "none", out_size=None, resize_chunk: Optional[int] = None):
+        """An RGB source flagged full range (DESIGN.md 3.9 point 6).  The reference puts `scale=in_range=pc:out_range=R,
+        format=<8-bit yuv>` AHEAD of lut3d for it (ffmpeg.py:212-233), so the LUT runs on an 8-bit YUV frame.  Kept by
+        composition, two launches on the engine's stream with no host wait: stage 0 is `apply_rgb_to_yuv` without the LUT into
+        engine-owned scratch (`intermediate_pix_fmt` at 8 bit, range R = `prologue_out_range`, matrix `matrix` or smpte170m),
+        then `apply_yuv` from that frame to `out_pix_fmt`.  The three plan fields are `LutPlan.intermediate_pix_fmt`,
+        `.prologue_out_range` and `.matrix`."""
+        fin = parse_rgb_source(pix_fmt)
+        if fin is None:
+            raise ValueError(f"apply_rgb_full_range takes gbrp* or packed RGB sources, not '{pix_fmt}'")
+        mid = parse_pix_fmt(intermediate_pix_fmt)
+        if mid.family != "yuv" or mid.depth != 8:
+            raise ValueError(f"the full-range intermediate is an 8-bit planar YUV format, not '{intermediate_pix_fmt}'")
+        rng = prologue_out_range or "pc"
+        if rng not in _native.RANGE:
+            raise ValueError(f"unknown range '{rng}'")
+        m = matrix or "smpte170m"
+        _, _, w, h, nf, lead = self._rgb_source(src, fin)
+        with self._lock:
+            key = (mid.name, w, h)
+            if self._fr_scratch is None or self._fr_scratch[0] != key or self._fr_scratch[1][0].shape[0] < nf:
+                self._fr_scratch = (key, [torch.empty((nf,) + mid.plane_shape(i, w, h), dtype=torch.uint8, device=self.device)
+                                          for i in range(3)])
+            tmp = [t[:nf] if len(lead) else t[0] for t in self._fr_scratch[1]]
+            self.apply_rgb_to_yuv(src, tmp, pix_fmt=pix_fmt, out_pix_fmt=mid.name, lut=False, matrix_out=m, range_out=rng,
+                                  row0=row0, rows=rows)
+            return self.apply_yuv(tmp, dst, pix_fmt=mid.name, out_pix_fmt=out_pix_fmt, interp=interp, matrix_in=m, matrix_out=m,
+                                  range_src=rng, range_in=rng, range_out=range_out, lut_depth=8, row0=row0, rows=rows,
+                                  dither=dither, out_size=out_size, resize_chunk=resize_chunk)
+
 
 def yuv_constants(**kw) -> np.ndarray:
     """The 32-float constant block liblutr derives for a lutr_yuv_params (host only, no GPU)."""
@@ -557,6 +718,16 @@ def yuv_constants_xsub(**kw) -> np.ndarray:
         setattr(p, k, v)
     out = (C.c_float * 32)()
     _native.check(_native.load().lutr_yuv_constants_xsub(C.byref(p), out))
+    return np.array(list(out), dtype=np.float32)
+
+
+def yuv_constants_rgb2yuv(**kw) -> np.ndarray:
+    """The constant block of `apply_rgb_to_yuv` (lutr_yuv_constants_rgb2yuv): fmt_out, lut_depth, matrix_out and range_out count."""
+    p = _native.YuvParams()
+    for k, v in kw.items():
+        setattr(p, k, v)
+    out = (C.c_float * 32)()
+    _native.check(_native.load().lutr_yuv_constants_rgb2yuv(C.byref(p), out))
     return np.array(list(out), dtype=np.float32)
 
 

@@ -28,7 +28,7 @@ import torch
 
 from . import _native
 from .cube import CubeLut, read_lut
-from .engine import LutEngine, parse_pix_fmt
+from .engine import LutEngine, parse_pix_fmt, parse_rgb_source
 from .shard import row_blocks
 
 
@@ -177,3 +177,54 @@ class LutEngineGroup:
             for d, o, (a, b) in zip(dst, out, rng):
                 d[..., a:b, :].copy_(o, non_blocking=True)
         return dst
+
+    def apply_rgb_to_yuv(self, src, dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: str, **kw):
+        """`LutEngine.apply_rgb_to_yuv` with the rows of every frame split over the group's devices: shards on
+        multiples of the output chroma block height, every source plane (or the packed image) counted in luma rows, no halo."""
+        with self._lock:
+            if kw.get("dither", "none") != "none":
+                raise ValueError("error-diffusion dither couples the rows of a frame: it cannot be row-sharded")
+            if "row0" in kw or "rows" in kw:
+                raise ValueError("the group owns the row partition")
+            if kw.get("out_size") is not None:
+                raise ValueError("a resize (out_size) needs a single device")
+            fin = parse_rgb_source(pix_fmt)
+            if fin is None:
+                raise ValueError(f"apply_rgb_to_yuv takes gbrp* or packed RGB sources, not '{pix_fmt}'")
+            fout = parse_pix_fmt(out_pix_fmt.replace("yuvj", "yuv"))
+            csy = fout.csy
+            if kw.get("intermediate_pix_fmt"):                     # the full-range composition: its 8-bit frame has chroma rows too
+                csy = max(csy, parse_pix_fmt(kw["intermediate_pix_fmt"]).csy)
+            first = src if fin.packed else src[0]
+            h, w = (first.shape[-3], first.shape[-2]) if fin.packed else (first.shape[-2], first.shape[-1])
+            lead = tuple(first.shape[:-3]) if fin.packed else tuple(first.shape[:-2])
+            home = first.device
+            if dst is None:
+                dt = torch.uint8 if fout.depth <= 8 else torch.int16
+                dst = [torch.empty(lead + fout.plane_shape(i, w, h), dtype=dt, device=home) for i in range(3)]
+
+            def rows_of(a, b):
+                return src[..., a:b, :, :] if fin.packed else [p[..., a:b, :] for p in src]
+
+            blocks = row_blocks(h, len(self.engines), align=1 << csy)
+            self.last_blocks = blocks
+            self.last_remote = 0
+            pending = []
+            for k, (eng, (r0, r1)) in enumerate(zip(self.engines, blocks)):
+                if r1 <= r0:
+                    continue
+                if eng.device == home and not (self.treat_as_remote and k > 0):
+                    eng.apply_rgb_to_yuv(src, dst, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0, rows=r1 - r0, **kw)
+                    continue
+                o0, o1 = r0 >> fout.csy, (r1 + (1 << fout.csy) - 1) >> fout.csy
+                with torch.cuda.device(eng.device):
+                    part = rows_of(r0, r1)
+                    part = part.to(eng.device, non_blocking=True, copy=True).contiguous() if fin.packed else \
+                        [p.to(eng.device, non_blocking=True, copy=True).contiguous() for p in part]
+                    out = eng.apply_rgb_to_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, **kw)
+                self.last_remote += 1
+                pending.append((out, [(r0, r1), (o0, o1), (o0, o1)]))
+            for out, rng in pending:                               # copies back: queued after every launch was issued
+                for d, o, (a, b) in zip(dst, out, rng):
+                    d[..., a:b, :].copy_(o, non_blocking=True)
+            return dst

@@ -18,7 +18,7 @@ from typing import Callable, Iterable, Iterator, List, Optional
 import numpy as np
 import torch
 
-from .engine import LutEngine, PixFmt, parse_pix_fmt, parse_size
+from .engine import LutEngine, PixFmt, RgbSource, parse_pix_fmt, parse_rgb_source, parse_size
 
 
 @dataclass
@@ -56,6 +56,36 @@ class FrameLayout:
         return out
 
 
+@dataclass
+class PackedFrameLayout:
+    """Byte layout of one packed RGB frame in a rawvideo stream: h x w pixels of `ncomp` components (input side only)."""
+    fmt: RgbSource
+    width: int
+    height: int
+
+    @property
+    def itemsize(self) -> int:
+        return self.fmt.itemsize
+
+    @property
+    def frame_bytes(self) -> int:
+        return self.height * self.width * self.fmt.ncomp * self.itemsize
+
+    def image_view(self, buf: torch.Tensor, nframes: int) -> torch.Tensor:
+        """The [F,H,W,C] view of `nframes` frames inside a flat uint8 buffer."""
+        dt = torch.uint8 if self.itemsize == 1 else torch.int16
+        n = nframes * self.frame_bytes // self.itemsize
+        return buf.view(dt)[:n].view(nframes, self.height, self.width, self.fmt.ncomp)
+
+
+def input_layout(pix_fmt: str, width: int, height: int):
+    """The layout of a rawvideo input: `PackedFrameLayout` for a packed RGB name, else `FrameLayout` (planar YUV or gbrp)."""
+    rgb = parse_rgb_source(pix_fmt)
+    if rgb is not None and rgb.packed:
+        return PackedFrameLayout(rgb, width, height)
+    return FrameLayout(parse_pix_fmt(pix_fmt.replace("yuvj", "yuv")), width, height)
+
+
 class HostPipeline:
     """Apply the LUT to batches of host frames with copies overlapped against compute."""
 
@@ -63,7 +93,10 @@ class HostPipeline:
                  out_pix_fmt: Optional[str] = None, out_size=None, **apply_kw):
         """`out_size` = (w, h) or "WxH": the engine resizes every frame to it and the output layout has that size."""
         self.eng = engine
-        self.fin = FrameLayout(parse_pix_fmt(pix_fmt.replace("yuvj", "yuv")), width, height)
+        self.fin = input_layout(pix_fmt, width, height)
+        self.rgb = parse_rgb_source(pix_fmt) is not None       # an RGB source: apply_rgb_to_yuv (DESIGN.md 3.9)
+        if self.rgb and not out_pix_fmt:
+            raise ValueError("an RGB source needs out_pix_fmt (a planar YUV format)")
         ow, oh = (width, height) if out_size is None else parse_size(out_size)
         self.fout = FrameLayout(parse_pix_fmt(out_pix_fmt or pix_fmt.replace("yuvj", "yuv")), ow, oh)
         self.batch, self.slots = int(batch), int(slots)
@@ -93,9 +126,13 @@ class HostPipeline:
             self.e_in[slot].record()
         with torch.cuda.stream(self.s_run):
             self.s_run.wait_event(self.e_in[slot])
-            src = self.fin.plane_views(self.d_in[slot], nframes)
             dst = self.fout.plane_views(self.d_out[slot], nframes)
-            self.eng.apply_yuv(src, dst, **self.kw)          # launches on the current (s_run) stream
+            if self.rgb:                                     # launches on the current (s_run) stream
+                src = self.fin.image_view(self.d_in[slot], nframes) if isinstance(self.fin, PackedFrameLayout) \
+                    else self.fin.plane_views(self.d_in[slot], nframes)
+                self.eng.apply_rgb_to_yuv(src, dst, **self.kw)
+            else:
+                self.eng.apply_yuv(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
             self.e_run[slot].record()
         with torch.cuda.stream(self.s_d2h):
             self.s_d2h.wait_event(self.e_run[slot])
