@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "lutr_internal.h"
+#include "lutr_launch.h"
 
 namespace lutr {
 
@@ -297,15 +298,19 @@ struct lutr_ctx {
     // fma32 variant: fp32 copies of the lattice pre-multiplied by 2^depth - 1, per LUT depth (index depth - 8), same life cycle
     float4 *latm[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // lut3d's prelut (lutr_ctx_set_prelut): the host copy, and per LUT depth a device table of the lattice coordinate of every
-    // integer code -- the shaper, the scale and the clip folded into one lookup (pre_dev[depth - 8], 3 x pre_entries floats)
+    // integer code -- the shaper, the scale and the clip folded into one lookup (pre_tab[depth - 8])
     std::vector<float> prelut;
     int pre_size = 0;
     float pre_min[3] = {0, 0, 0}, pre_scale[3] = {0, 0, 0};
-    float *pre_dev[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int    pre_shared[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};     // per depth: the three tables agree and never fall (LutConsts::pre_shared)
-    float  pre_kappa[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // ... and their largest step between neighbouring codes
-    std::vector<float> pre_host[9];                         // ... and the shared table itself, codes 0 .. 2^depth - 1 (LutConsts::pre_host)
-    unsigned long long pre_gen[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // ... and its number (LutConsts::pre_gen, g_prelut_gen)
+    struct PreTable {
+        float *dev = nullptr;            // 3 x entries floats, or nullptr: not built yet (everything below is then stale)
+        int entries = 0;                 // 256 for 8-bit containers, else 65536
+        int shared = 0;                  // the three tables agree and never fall (LutConsts::pre_shared)
+        float kappa = 0.0f;              // ... and their largest step between neighbouring codes
+        std::vector<float> host;         // ... and the shared table itself, codes 0 .. 2^depth - 1 (LutConsts::pre_host)
+        unsigned long long gen = 0;      // the table's number (LutConsts::pre_gen, g_prelut_gen)
+    };
+    PreTable pre_tab[9];
     // lutr_lut_broadcast: copies other contexts are still reading out of THIS context's lattice (one event per receiver,
     // recorded on the receiver's stream behind its copy).  The lattice must not be overwritten or freed before they finish.
     std::vector<std::pair<int, hipEvent_t>> readers;      // (receiver's device, event)
@@ -341,8 +346,38 @@ static void drop_lat16(lutr_ctx *c)
 
 static void drop_prelut_tables(lutr_ctx *c)
 {
-    for (auto &p : c->pre_dev)
-        if (p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(p); p = nullptr; }
+    for (auto &t : c->pre_tab)
+        if (t.dev) { (void)hipStreamSynchronize(c->stream); (void)hipFree(t.dev); t.dev = nullptr; }
+}
+
+// The body of the four lutr_yuv_constants* exports; make(YuvConsts *) is only called with p checked.
+template <class Make>
+static int export_consts(const char *entry, const lutr_yuv_params *p, float *out, Make make)
+{
+    if (!p || !out) {
+        set_error("%s: null argument", entry);
+        return LUTR_EINVAL;
+    }
+    YuvConsts k;
+    const int rc = make(&k);
+    if (rc) return rc;
+    std::memcpy(out, &k, sizeof(k));
+    return LUTR_OK;
+}
+
+// A copy of the lattice pre-multiplied by 2^depth - 1 in *slot, built on first use by `build` (nullptr: out of memory).
+template <class T>
+static const T *derived_lattice(lutr_ctx *c, T **slot, int depth,
+                                void (*build)(hipStream_t, const float4 *, T *, size_t, float))
+{
+    if (!*slot) {
+        const size_t nodes = c->lat_bytes / sizeof(float4);
+        void *p = nullptr;
+        if (hipMalloc(&p, nodes * sizeof(T)) != hipSuccess) return nullptr;
+        *slot = (T *)p;
+        build(c->stream, c->lat, *slot, nodes, (float)((1 << depth) - 1));   // same stream as the apply that follows
+    }
+    return *slot;
 }
 
 extern "C" {
@@ -359,15 +394,22 @@ size_t lutr_lattice_bytes(int n)
 
 int lutr_yuv_constants(const lutr_yuv_params *p, float out[32])
 {
-    if (!p || !out) {
-        set_error("lutr_yuv_constants: null argument");
-        return LUTR_EINVAL;
-    }
-    YuvConsts k;
-    const int rc = make_yuv_consts(*p, &k);
-    if (rc) return rc;
-    std::memcpy(out, &k, sizeof(k));
-    return LUTR_OK;
+    return export_consts("lutr_yuv_constants", p, out, [&](YuvConsts *k) { return make_yuv_consts(*p, k); });
+}
+
+int lutr_yuv_constants_sited(const lutr_yuv_params *p, int chroma_loc, float out[32])
+{
+    return export_consts("lutr_yuv_constants_sited", p, out, [&](YuvConsts *k) { return make_yuv_consts_sited(*p, chroma_loc, k); });
+}
+
+int lutr_yuv_constants_xsub(const lutr_yuv_params *p, float out[32])
+{
+    return export_consts("lutr_yuv_constants_xsub", p, out, [&](YuvConsts *k) { return make_yuv_consts_xsub(*p, k); });
+}
+
+int lutr_yuv_constants_rgb2yuv(const lutr_yuv_params *p, float out[32])
+{
+    return export_consts("lutr_yuv_constants_rgb2yuv", p, out, [&](YuvConsts *k) { return make_yuv_consts_rgb2yuv(*p, k); });
 }
 
 int lutr_ctx_create(int device, lutr_ctx **out)
@@ -391,28 +433,17 @@ int lutr_ctx_create(int device, lutr_ctx **out)
     HIP_TRY(hipSetDevice(device));
     lutr_ctx *c = new lutr_ctx();
     c->device = device;
+    const char *what = "hipStreamCreateWithFlags";
     e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete c;
-        return hip_fail(e, "hipStreamCreateWithFlags");
-    }
     c->stream = c->own_stream;
     // four words: {claims, waves done} of the round-3 tile kernels, which return them to zero themselves at the end of every launch
     // (no memset node per launch), word 2 for round 1's RGB kernel (set by its launcher), one spare
-    e = hipMalloc((void **)&c->queue, 4 * sizeof(unsigned));
+    if (e == hipSuccess) { what = "hipMalloc(queue)"; e = hipMalloc((void **)&c->queue, 4 * sizeof(unsigned)); }
     if (e == hipSuccess) e = hipMemset(c->queue, 0, 4 * sizeof(unsigned));
+    if (e == hipSuccess) { what = "hipEventCreateWithFlags"; e = hipEventCreateWithFlags(&c->done, hipEventDisableTiming); }
     if (e != hipSuccess) {
-        if (c->queue) (void)hipFree(c->queue);
-        (void)hipStreamDestroy(c->own_stream);
-        delete c;
-        return hip_fail(e, "hipMalloc(queue)");
-    }
-    e = hipEventCreateWithFlags(&c->done, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        (void)hipFree(c->queue);
-        (void)hipStreamDestroy(c->own_stream);
-        delete c;
-        return hip_fail(e, "hipEventCreateWithFlags");
+        lutr_ctx_destroy(c);             // it tolerates the members that were never made
+        return hip_fail(e, what);
     }
     *out = c;
     return LUTR_OK;
@@ -609,21 +640,18 @@ int lutr_ctx_set_prelut(lutr_ctx *c, const float *prelut, int size, const float 
 // a freed one's memory, so the address says nothing about the contents.
 static std::atomic<unsigned long long> g_prelut_gen{0};
 
-static int prelut_table(lutr_ctx *c, int depth, const float **dev, int *entries, int *shared, float *kappa, const float **host_tab,
-                        unsigned long long *gen)
+// *out: the table of `depth`, built on first use; an empty one (dev == nullptr) when the context has no prelut.
+static int prelut_table(lutr_ctx *c, int depth, const lutr_ctx::PreTable **out)
 {
-    *dev = nullptr; *entries = 0; *shared = 0; *kappa = 0.0f; *host_tab = nullptr; *gen = 0;
+    static const lutr_ctx::PreTable none;
+    *out = &none;
     if (!c->pre_size) return LUTR_OK;
     const int slot = depth - 8;
     if (slot < 0 || slot > 8) { set_error("prelut: LUT depth %d outside 8..16", depth); return LUTR_EINVAL; }
+    lutr_ctx::PreTable &t = c->pre_tab[slot];
+    *out = &t;
+    if (t.dev) return LUTR_OK;
     const int ne = depth <= 8 ? 256 : 65536;
-    *entries = ne;
-    if (c->pre_dev[slot]) {
-        *dev = c->pre_dev[slot]; *shared = c->pre_shared[slot]; *kappa = c->pre_kappa[slot];
-        *host_tab = c->pre_shared[slot] ? c->pre_host[slot].data() : nullptr;
-        *gen = c->pre_gen[slot];
-        return LUTR_OK;
-    }
     const int maxi = (1 << depth) - 1, pmax = c->pre_size - 1;
     const float scale_f = 1.0f / (float)maxi, lut_max = (float)(c->n - 1);
     std::vector<float> host((size_t)3 * ne);
@@ -646,8 +674,8 @@ static int prelut_table(lutr_ctx *c, int depth, const float **dev, int *entries,
     if (e != hipSuccess) { set_error("hipMalloc(prelut table): %s", hipGetErrorString(e)); return LUTR_ENOMEM; }
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-    c->pre_dev[slot] = (float *)p;
-    *dev = c->pre_dev[slot];
+    t.dev = (float *)p;
+    t.entries = ne;
     // one table for the three channels?  (what the fused YUV tile kernels can take: their coordinate table is indexed by code alone,
     // and their validity bounds want a monotone map with a known largest slope)
     bool same = true;
@@ -657,14 +685,11 @@ static int prelut_table(lutr_ctx *c, int depth, const float **dev, int *entries,
         same = host[(size_t)ne + code] == v && host[(size_t)2 * ne + code] == v;
         if (code) { const float d = v - host[code - 1]; if (d < 0.0f) same = false; else if (d > step) step = d; }
     }
-    c->pre_shared[slot] = same ? 1 : 0;
-    c->pre_kappa[slot] = same ? step : 0.0f;
-    c->pre_host[slot].clear();
-    if (same) c->pre_host[slot].assign(host.begin(), host.begin() + maxi + 1);
-    *shared = c->pre_shared[slot]; *kappa = c->pre_kappa[slot];
-    *host_tab = same ? c->pre_host[slot].data() : nullptr;
-    c->pre_gen[slot] = ++g_prelut_gen;
-    *gen = c->pre_gen[slot];
+    t.shared = same ? 1 : 0;
+    t.kappa = same ? step : 0.0f;
+    t.host.clear();
+    if (same) t.host.assign(host.begin(), host.begin() + maxi + 1);
+    t.gen = ++g_prelut_gen;
     return LUTR_OK;
 }
 
@@ -744,17 +769,68 @@ int lutr_ctx_lut_device(lutr_ctx *c, void **dptr, size_t *bytes)
     return LUTR_OK;
 }
 
-static int check_common(lutr_ctx *c, int interp, int w, int h, int nframes, const void *src,
-                        const void *dst, int row0, int rows)
+// min_interp: the lowest legal mode -- LUTR_INTERP_NEAREST, or LUTR_INTERP_NONE where the entry point can leave lut3d out
+// (no lattice is needed for that mode then)
+static int check_common(lutr_ctx *c, int interp, int min_interp, int w, int h, int nframes, const void *src, const void *dst,
+                        int row0, int rows)
 {
     if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
-    if (!c->lat) { set_error("no lattice set on this context (call lutr_ctx_set_lut first)"); return LUTR_EINVAL; }
-    if (interp < LUTR_INTERP_NEAREST || interp > LUTR_INTERP_PRISM) {
+    if (!c->lat && (interp != LUTR_INTERP_NONE || min_interp > LUTR_INTERP_NONE)) {
+        set_error("no lattice set on this context (call lutr_ctx_set_lut first)");
+        return LUTR_EINVAL;
+    }
+    if (interp < min_interp || interp > LUTR_INTERP_PRISM) {
         set_error("unknown interpolation mode %d", interp);
         return LUTR_EINVAL;
     }
     if (w < 0 || h < 0 || nframes < 0 || row0 < 0 || rows < 0 || row0 + rows > h) {
         set_error("bad geometry w=%d h=%d nframes=%d row0=%d rows=%d", w, h, nframes, row0, rows);
+        return LUTR_EINVAL;
+    }
+    return LUTR_OK;
+}
+
+// every plane of a (and of b, when given) has a base pointer
+static int check_planes_set(const lutr_planes *a, const lutr_planes *b)
+{
+    for (int i = 0; i < 3; i++)
+        if (!a->data[i] || (b && !b->data[i])) { set_error("null plane %d", i); return LUTR_EINVAL; }
+    return LUTR_OK;
+}
+
+// a row range made of whole chroma blocks of height bh (the frame's last block may be cut); `noun` names the block in the message
+static int check_row_blocks(int row0, int rows, int h, int bh, const char *noun)
+{
+    if (row0 % bh || (rows % bh && row0 + rows != h)) {
+        set_error("row0/rows must be multiples of the %s %d", noun, bh);
+        return LUTR_EINVAL;
+    }
+    return LUTR_OK;
+}
+
+static int check_dither(int dither)
+{
+    if (dither != LUTR_DITHER_NONE && dither != LUTR_DITHER_ERROR_DIFFUSION) { set_error("unknown dither mode %d", dither); return LUTR_EINVAL; }
+    return LUTR_OK;
+}
+
+static int check_dither_rows(int dither, int row0, int rows, int h)
+{
+    if (dither == LUTR_DITHER_ERROR_DIFFUSION && (row0 != 0 || rows != h)) {
+        set_error("error-diffusion dither couples the rows of a frame: whole frames only (row0 = 0, rows = h)");
+        return LUTR_EINVAL;
+    }
+    return LUTR_OK;
+}
+
+struct PackedFmt { int bits, nc, ro, go, bo; };
+
+static int decode_packed(int pfmt, PackedFmt *f)
+{
+    *f = PackedFmt{LUTR_PACKED_BITS(pfmt), LUTR_PACKED_NCOMP(pfmt), LUTR_PACKED_RO(pfmt), LUTR_PACKED_GO(pfmt), LUTR_PACKED_BO(pfmt)};
+    if ((f->bits != 8 && f->bits != 16) || (f->nc != 3 && f->nc != 4) || (pfmt >> 24) || f->ro >= f->nc || f->go >= f->nc ||
+        f->bo >= f->nc || f->ro == f->go || f->go == f->bo || f->ro == f->bo) {
+        set_error("unsupported packed format 0x%x", pfmt);
         return LUTR_EINVAL;
     }
     return LUTR_OK;
@@ -777,15 +853,7 @@ static void fill_planes(PlaneSet *P, const lutr_planes *src, const lutr_planes *
 static const uint2 *fast_lattice(lutr_ctx *c, int depth)
 {
     if (c->precision != LUTR_PRECISION_FAST || !c->unit || (depth != 8 && depth != 10)) return nullptr;
-    uint2 *&slot = c->lat16[depth == 8 ? 0 : 1];
-    if (!slot) {
-        const size_t nodes = c->lat_bytes / sizeof(float4);
-        void *p = nullptr;
-        if (hipMalloc(&p, nodes * sizeof(uint2)) != hipSuccess) return nullptr;
-        slot = (uint2 *)p;
-        launch_make_lat16(c->stream, c->lat, slot, nodes, (float)((1 << depth) - 1));   // same stream as the apply that follows
-    }
-    return slot;
+    return derived_lattice(c, &c->lat16[depth == 8 ? 0 : 1], depth, launch_make_lat16);
 }
 
 // The fma32 variant's lattice for `depth`, or nullptr when fma32 does not apply: another precision selected, or a lattice
@@ -794,23 +862,20 @@ static const uint2 *fast_lattice(lutr_ctx *c, int depth)
 static const float4 *fma32_lattice(lutr_ctx *c, int depth)
 {
     if (c->precision != LUTR_PRECISION_FMA32 || !c->unit || depth < 8 || depth > 16) return nullptr;
-    float4 *&slot = c->latm[depth - 8];
-    if (!slot) {
-        const size_t nodes = c->lat_bytes / sizeof(float4);
-        void *p = nullptr;
-        if (hipMalloc(&p, nodes * sizeof(float4)) != hipSuccess) return nullptr;
-        slot = (float4 *)p;
-        launch_make_latm(c->stream, c->lat, slot, nodes, (float)((1 << depth) - 1));     // same stream as the apply that follows
-    }
-    return slot;
+    return derived_lattice(c, &c->latm[depth - 8], depth, launch_make_latm);
 }
 
 static int fill_lut(LutConsts *L, lutr_ctx *c, int depth)
 {
     const int maxi = (1 << depth) - 1;
-    const int rc = prelut_table(c, depth, &L->pre, &L->pre_stride, &L->pre_shared, &L->pre_kappa, &L->pre_host,
-                                &L->pre_gen);
-    if (rc) return rc;
+    const lutr_ctx::PreTable *t;
+    if (const int rc = prelut_table(c, depth, &t)) return rc;
+    L->pre = t->dev;
+    L->pre_stride = t->entries;
+    L->pre_shared = t->shared;
+    L->pre_kappa = t->kappa;
+    L->pre_host = t->shared ? t->host.data() : nullptr;
+    L->pre_gen = t->gen;
     L->lat = c->lat;
     L->lat16 = nullptr;
     L->latm = nullptr;
@@ -840,12 +905,11 @@ static int finish_launch(lutr_ctx *c, const char *name)
 int lutr_apply_planar_rgb(lutr_ctx *c, int depth, int interp, int w, int h, int nframes,
                           const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
 {
-    int rc = check_common(c, interp, w, h, nframes, src, dst, row0, rows);
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, row0, rows);
     if (rc) return rc;
     if (depth < 8 || depth > 16) { set_error("unsupported depth %d", depth); return LUTR_EINVAL; }
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    for (int i = 0; i < 3; i++)
-        if (!src->data[i] || !dst->data[i]) { set_error("null plane %d", i); return LUTR_EINVAL; }
+    if (const int rc = check_planes_set(src, dst)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
     if (const int rc = fill_lut(&L, c, depth)) return rc;
@@ -856,18 +920,13 @@ int lutr_apply_planar_rgb(lutr_ctx *c, int depth, int interp, int w, int h, int 
 int lutr_apply_packed_rgb(lutr_ctx *c, int pfmt, int interp, int w, int h, int nframes,
                           const lutr_packed *src, const lutr_packed *dst, int row0, int rows)
 {
-    int rc = check_common(c, interp, w, h, nframes, src, dst, row0, rows);
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, row0, rows);
     if (rc) return rc;
-    const int bits = LUTR_PACKED_BITS(pfmt), nc = LUTR_PACKED_NCOMP(pfmt);
-    const int ro = LUTR_PACKED_RO(pfmt), go = LUTR_PACKED_GO(pfmt), bo = LUTR_PACKED_BO(pfmt);
-    if ((bits != 8 && bits != 16) || (nc != 3 && nc != 4) || (pfmt >> 24) || ro >= nc || go >= nc || bo >= nc ||
-        ro == go || go == bo || ro == bo) {
-        set_error("unsupported packed format 0x%x", pfmt);
-        return LUTR_EINVAL;
-    }
+    PackedFmt f;
+    if (const int rc = decode_packed(pfmt, &f)) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
     if (!src->data || !dst->data) { set_error("null image"); return LUTR_EINVAL; }
-    const int wide = bits == 16;
+    const int wide = f.bits == 16;
     if (wide && (((uintptr_t)src->data | (uintptr_t)dst->data | (uintptr_t)src->stride | (uintptr_t)dst->stride |
                   (nframes > 1 ? (uintptr_t)src->frame_stride | (uintptr_t)dst->frame_stride : 0)) & 1)) {
         set_error("16-bit packed formats need 2-byte aligned rows");
@@ -875,19 +934,19 @@ int lutr_apply_packed_rgb(lutr_ctx *c, int pfmt, int interp, int w, int h, int n
     }
     HIP_TRY(hipSetDevice(c->device));
     LutConsts L; FrameGeom G{w, h, row0, rows, nframes};
-    if (const int rc = fill_lut(&L, c, bits)) return rc;
+    if (const int rc = fill_lut(&L, c, f.bits)) return rc;
     PackedSet P;
     P.s = (const uint8_t *)src->data; P.d = (uint8_t *)dst->data;
     P.ss = src->stride; P.ds = dst->stride;
     P.sfs = src->frame_stride; P.dfs = dst->frame_stride;
-    P.ro = ro; P.go = go; P.bo = bo; P.ao = nc == 4 ? 6 - ro - go - bo : 3;
-    return finish_launch(c, launch_packed(c->stream, c->variant, L, P, G, wide, nc, interp, c->stats, c->queue));
+    P.ro = f.ro; P.go = f.go; P.bo = f.bo; P.ao = f.nc == 4 ? 6 - f.ro - f.go - f.bo : 3;
+    return finish_launch(c, launch_packed(c->stream, c->variant, L, P, G, wide, f.nc, interp, c->stats, c->queue));
 }
 
 int lutr_apply_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int w, int h, int nframes,
                    const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
 {
-    int rc = check_common(c, interp, w, h, nframes, src, dst, row0, rows);
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, row0, rows);
     if (rc) return rc;
     if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
     YuvConsts K;
@@ -895,13 +954,9 @@ int lutr_apply_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int w, int
     if (rc) return rc;
     const int csx = LUTR_FMT_CSX(p->fmt_in), csy = LUTR_FMT_CSY(p->fmt_in);
     const int bh = 1 << csy;
-    if (row0 % bh || (rows % bh && row0 + rows != h)) {
-        set_error("row0/rows must be multiples of the chroma block height %d", bh);
-        return LUTR_EINVAL;
-    }
+    if (const int rc = check_row_blocks(row0, rows, h, bh, "chroma block height")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    for (int i = 0; i < 3; i++)
-        if (!src->data[i] || !dst->data[i]) { set_error("null plane %d", i); return LUTR_EINVAL; }
+    if (const int rc = check_planes_set(src, dst)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
@@ -914,96 +969,32 @@ int lutr_apply_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int w, int
 }
 
 // Byte range [lo, hi) that `rows` rows of `row_bytes` bytes span in each of `nframes` frames.
-static void plane_span(const void *p, long long stride, long long fstride, int rows, long long row_bytes, int nframes,
-                       uintptr_t *lo, uintptr_t *hi)
+struct Span { uintptr_t lo, hi; };
+
+static Span plane_span(const void *p, long long stride, long long fstride, int rows, long long row_bytes, int nframes)
 {
     const long long r = (long long)(rows - 1) * stride, f = nframes > 1 ? (long long)(nframes - 1) * fstride : 0;
     const long long a = (r < 0 ? r : 0) + (f < 0 ? f : 0), b = (r > 0 ? r : 0) + (f > 0 ? f : 0) + row_bytes;
-    *lo = (uintptr_t)p + (intptr_t)a;
-    *hi = (uintptr_t)p + (intptr_t)b;
+    return Span{(uintptr_t)p + (intptr_t)a, (uintptr_t)p + (intptr_t)b};
 }
 
-int lutr_apply_yuv_sited(lutr_ctx *c, const lutr_yuv_params *p, int interp, int chroma_loc, int w, int h, int nframes,
-                         const lutr_planes *src, lutr_planes *dst, int row0, int rows)
+// No source span may overlap a destination span: `what` cannot run in place.  name_src: the message names the source plane.
+static int check_disjoint(const char *what, bool name_src, const Span *s, int ns, const Span *d, int nd)
 {
-    if (chroma_loc < LUTR_CHROMA_REPLICATE || chroma_loc > LUTR_CHROMA_TOPLEFT) {
-        set_error("unknown chroma location %d", chroma_loc);
-        return LUTR_EINVAL;
-    }
-    int rc = check_common(c, interp, w, h, nframes, src, dst, row0, rows);
-    if (rc) return rc;
-    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
-    const int csx = LUTR_FMT_CSX(p->fmt_in), csy = LUTR_FMT_CSY(p->fmt_in);
-    if (chroma_loc == LUTR_CHROMA_REPLICATE || (csx == 0 && csy == 0))
-        return lutr_apply_yuv(c, p, interp, w, h, nframes, src, dst, row0, rows);
-    YuvConsts K;
-    rc = make_yuv_consts_sited(*p, chroma_loc, &K);
-    if (rc) return rc;
-    const int bh = 1 << csy;
-    if (row0 % bh || (rows % bh && row0 + rows != h)) {
-        set_error("row0/rows must be multiples of the chroma block height %d", bh);
-        return LUTR_EINVAL;
-    }
-    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    for (int i = 0; i < 3; i++)
-        if (!src->data[i] || !dst->data[i]) { set_error("null plane %d", i); return LUTR_EINVAL; }
-    // the resampling reads around every output sample: a destination that overlaps a source would be read after being written
-    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
-    const int cw = (w + (1 << csx) - 1) >> csx, ch = (h + bh - 1) >> csy;
-    for (int i = 0; i < 3; i++) {
-        uintptr_t slo, shi;
-        plane_span(src->data[i], src->stride[i], src->frame_stride[i], i ? ch : h, (long long)(i ? cw : w) * (din > 8 ? 2 : 1),
-                   nframes, &slo, &shi);
-        for (int j = 0; j < 3; j++) {
-            uintptr_t dlo, dhi;
-            plane_span(dst->data[j], dst->stride[j], dst->frame_stride[j], j ? ch : h, (long long)(j ? cw : w) * (dout > 8 ? 2 : 1),
-                       nframes, &dlo, &dhi);
-            if (slo < dhi && dlo < shi) {
-                set_error("sited chroma resampling cannot run in place: the byte range of source plane %d overlaps that of destination plane %d (bounding ranges over all rows and frames must be disjoint)", i, j);
+    for (int i = 0; i < ns; i++)
+        for (int j = 0; j < nd; j++)
+            if (s[i].lo < d[j].hi && d[j].lo < s[i].hi) {
+                char src[32] = "the source";
+                if (name_src) std::snprintf(src, sizeof(src), "source plane %d", i);
+                set_error("%s cannot run in place: the byte range of %s overlaps that of destination plane %d (bounding ranges over all rows and frames must be disjoint)", what, src, j);
                 return LUTR_EINVAL;
             }
-        }
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
-    if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
-    fill_planes(&P, src, dst);
-    const char *name = launch_yuv_sited(c->stream, L, K, P, G, din, dout, csy, chroma_loc, interp);
-    if (!name) { set_error("launch too large for the sited kernels (split the batch)"); return LUTR_EINVAL; }
-    return finish_launch(c, name);
-}
-
-int lutr_yuv_constants_sited(const lutr_yuv_params *p, int chroma_loc, float out[32])
-{
-    if (!p || !out) {
-        set_error("lutr_yuv_constants_sited: null argument");
-        return LUTR_EINVAL;
-    }
-    YuvConsts k;
-    const int rc = make_yuv_consts_sited(*p, chroma_loc, &k);
-    if (rc) return rc;
-    std::memcpy(out, &k, sizeof(k));
     return LUTR_OK;
 }
 
-int lutr_apply_yuv_dither(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dither, int w, int h, int nframes,
-                          const lutr_planes *src, const lutr_planes *dst)
+// The dither path's float planes for ny luma and nc samples per chroma plane, out of the context's scratch (grown when too small).
+static int dither_scratch(lutr_ctx *c, size_t ny, size_t nc, FloatPlanes *F)
 {
-    if (dither == LUTR_DITHER_NONE) return lutr_apply_yuv(c, p, interp, w, h, nframes, src, dst, 0, h);
-    if (dither != LUTR_DITHER_ERROR_DIFFUSION) { set_error("unknown dither mode %d", dither); return LUTR_EINVAL; }
-    int rc = check_common(c, interp, w, h, nframes, src, dst, 0, h);
-    if (rc) return rc;
-    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
-    YuvConsts K;
-    rc = make_yuv_consts(*p, &K);
-    if (rc) return rc;
-    if (w == 0 || h == 0 || nframes == 0) return LUTR_OK;
-    for (int i = 0; i < 3; i++)
-        if (!src->data[i] || !dst->data[i]) { set_error("null plane %d", i); return LUTR_EINVAL; }
-    const int csx = LUTR_FMT_CSX(p->fmt_in), csy = LUTR_FMT_CSY(p->fmt_in);
-    const size_t cw = (size_t)((w + (1 << csx) - 1) >> csx), ch = (size_t)((h + (1 << csy) - 1) >> csy);
-    const size_t ny = (size_t)w * h * nframes, nc = cw * ch * nframes;
-    HIP_TRY(hipSetDevice(c->device));
     if (ny + 2 * nc > c->fscratch_floats) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (c->fscratch) (void)hipFree(c->fscratch);
@@ -1015,54 +1006,94 @@ int lutr_apply_yuv_dither(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
         c->fscratch = (float *)q;
         c->fscratch_floats = ny + 2 * nc;
     }
+    *F = FloatPlanes{c->fscratch, c->fscratch + ny, c->fscratch + ny + nc};
+    return LUTR_OK;
+}
+
+int lutr_apply_yuv_sited(lutr_ctx *c, const lutr_yuv_params *p, int interp, int chroma_loc, int w, int h, int nframes,
+                         const lutr_planes *src, lutr_planes *dst, int row0, int rows)
+{
+    if (chroma_loc < LUTR_CHROMA_REPLICATE || chroma_loc > LUTR_CHROMA_TOPLEFT) {
+        set_error("unknown chroma location %d", chroma_loc);
+        return LUTR_EINVAL;
+    }
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    const int csx = LUTR_FMT_CSX(p->fmt_in), csy = LUTR_FMT_CSY(p->fmt_in);
+    if (chroma_loc == LUTR_CHROMA_REPLICATE || (csx == 0 && csy == 0))
+        return lutr_apply_yuv(c, p, interp, w, h, nframes, src, dst, row0, rows);
+    YuvConsts K;
+    rc = make_yuv_consts_sited(*p, chroma_loc, &K);
+    if (rc) return rc;
+    const int bh = 1 << csy;
+    if (const int rc = check_row_blocks(row0, rows, h, bh, "chroma block height")) return rc;
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    if (const int rc = check_planes_set(src, dst)) return rc;
+    // the resampling reads around every output sample: a destination that overlaps a source would be read after being written
+    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
+    const int cw = (w + (1 << csx) - 1) >> csx, ch = (h + bh - 1) >> csy;
+    Span ss[3], ds[3];
+    for (int i = 0; i < 3; i++) {
+        ss[i] = plane_span(src->data[i], src->stride[i], src->frame_stride[i], i ? ch : h, (long long)(i ? cw : w) * (din > 8 ? 2 : 1), nframes);
+        ds[i] = plane_span(dst->data[i], dst->stride[i], dst->frame_stride[i], i ? ch : h, (long long)(i ? cw : w) * (dout > 8 ? 2 : 1), nframes);
+    }
+    if (const int rc = check_disjoint("sited chroma resampling", true, ss, 3, ds, 3)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
+    fill_planes(&P, src, dst);
+    const char *name = launch_yuv_sited(c->stream, L, K, P, G, din, dout, csy, chroma_loc, interp);
+    if (!name) { set_error("launch too large for the sited kernels (split the batch)"); return LUTR_EINVAL; }
+    return finish_launch(c, name);
+}
+
+int lutr_apply_yuv_dither(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dither, int w, int h, int nframes,
+                          const lutr_planes *src, const lutr_planes *dst)
+{
+    if (dither == LUTR_DITHER_NONE) return lutr_apply_yuv(c, p, interp, w, h, nframes, src, dst, 0, h);
+    if (dither != LUTR_DITHER_ERROR_DIFFUSION) { set_error("unknown dither mode %d", dither); return LUTR_EINVAL; }
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, 0, h);
+    if (rc) return rc;
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    YuvConsts K;
+    rc = make_yuv_consts(*p, &K);
+    if (rc) return rc;
+    if (w == 0 || h == 0 || nframes == 0) return LUTR_OK;
+    if (const int rc = check_planes_set(src, dst)) return rc;
+    const int csx = LUTR_FMT_CSX(p->fmt_in), csy = LUTR_FMT_CSY(p->fmt_in);
+    const size_t cw = (size_t)((w + (1 << csx) - 1) >> csx), ch = (size_t)((h + (1 << csy) - 1) >> csy);
+    const size_t ny = (size_t)w * h * nframes, nc = cw * ch * nframes;
+    HIP_TRY(hipSetDevice(c->device));
+    FloatPlanes F;
+    if (const int rc = dither_scratch(c, ny, nc, &F)) return rc;
     LutConsts L; PlaneSet P; FrameGeom G{w, h, 0, h, nframes};
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
     fill_planes(&P, src, dst);
-    FloatPlanes F{c->fscratch, c->fscratch + ny, c->fscratch + ny + nc};
     return finish_launch(c, launch_yuv_dither(c->stream, L, K, P, G, F, LUTR_FMT_DEPTH(p->fmt_in),
                                               LUTR_FMT_DEPTH(p->fmt_out), csx, csy, interp, csx, csy));
-}
-
-int lutr_yuv_constants_xsub(const lutr_yuv_params *p, float out[32])
-{
-    if (!p || !out) {
-        set_error("lutr_yuv_constants_xsub: null argument");
-        return LUTR_EINVAL;
-    }
-    YuvConsts k;
-    const int rc = make_yuv_consts_xsub(*p, &k);
-    if (rc) return rc;
-    std::memcpy(out, &k, sizeof(k));
-    return LUTR_OK;
 }
 
 int lutr_apply_yuv_xsub(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dither, int w, int h, int nframes,
                         const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
 {
-    if (dither != LUTR_DITHER_NONE && dither != LUTR_DITHER_ERROR_DIFFUSION) { set_error("unknown dither mode %d", dither); return LUTR_EINVAL; }
-    int rc = check_common(c, interp, w, h, nframes, src, dst, row0, rows);
+    if (const int rc = check_dither(dither)) return rc;
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, row0, rows);
     if (rc) return rc;
     if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
     YuvConsts K;
     rc = make_yuv_consts_xsub(*p, &K);
     if (rc) return rc;
-    if (dither == LUTR_DITHER_ERROR_DIFFUSION && (row0 != 0 || rows != h)) {
-        set_error("error-diffusion dither couples the rows of a frame: whole frames only (row0 = 0, rows = h)");
-        return LUTR_EINVAL;
-    }
+    if (const int rc = check_dither_rows(dither, row0, rows, h)) return rc;
     const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
     const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
     if (icsx == ocsx && icsy == ocsy)        // one layout: lutr_apply_yuv's contract, kernels and bits
         return dither == LUTR_DITHER_NONE ? lutr_apply_yuv(c, p, interp, w, h, nframes, src, dst, row0, rows)
                                           : lutr_apply_yuv_dither(c, p, interp, dither, w, h, nframes, src, dst);
     const int bh = 1 << (icsy > ocsy ? icsy : ocsy);
-    if (row0 % bh || (rows % bh && row0 + rows != h)) {
-        set_error("row0/rows must be multiples of the union chroma block height %d", bh);
-        return LUTR_EINVAL;
-    }
+    if (const int rc = check_row_blocks(row0, rows, h, bh, "union chroma block height")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    for (int i = 0; i < 3; i++)
-        if (!src->data[i] || !dst->data[i]) { set_error("null plane %d", i); return LUTR_EINVAL; }
+    if (const int rc = check_planes_set(src, dst)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
     LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
@@ -1073,75 +1104,36 @@ int lutr_apply_yuv_xsub(lutr_ctx *c, const lutr_yuv_params *p, int interp, int d
         return finish_launch(c, launch_yuv_xsub(c->stream, c->variant, L, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, interp));
     const size_t cw = (size_t)((w + (1 << ocsx) - 1) >> ocsx), ch = (size_t)((h + (1 << ocsy) - 1) >> ocsy);
     const size_t ny = (size_t)w * h * nframes, nc = cw * ch * nframes;
-    if (ny + 2 * nc > c->fscratch_floats) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->fscratch) (void)hipFree(c->fscratch);
-        c->fscratch = nullptr;
-        c->fscratch_floats = 0;
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, (ny + 2 * nc) * sizeof(float));
-        if (e != hipSuccess) { set_error("hipMalloc(%zu): %s", (ny + 2 * nc) * sizeof(float), hipGetErrorString(e)); return LUTR_ENOMEM; }
-        c->fscratch = (float *)q;
-        c->fscratch_floats = ny + 2 * nc;
-    }
-    FloatPlanes F{c->fscratch, c->fscratch + ny, c->fscratch + ny + nc};
+    FloatPlanes F;
+    if (const int rc = dither_scratch(c, ny, nc, &F)) return rc;
     return finish_launch(c, launch_yuv_dither(c->stream, L, K, P, G, F, din, dout, icsx, icsy, interp, ocsx, ocsy));
 }
 
 
-int lutr_yuv_constants_rgb2yuv(const lutr_yuv_params *p, float out[32])
-{
-    if (!p || !out) {
-        set_error("lutr_yuv_constants_rgb2yuv: null argument");
-        return LUTR_EINVAL;
-    }
-    YuvConsts k;
-    const int rc = make_yuv_consts_rgb2yuv(*p, &k);
-    if (rc) return rc;
-    std::memcpy(out, &k, sizeof(k));
-    return LUTR_OK;
-}
-
 int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dither, int src_kind, int w, int h, int nframes,
                           const lutr_planes *src_planar, const lutr_packed *src_packed, const lutr_planes *dst, int row0, int rows)
 {
-    if (dither != LUTR_DITHER_NONE && dither != LUTR_DITHER_ERROR_DIFFUSION) { set_error("unknown dither mode %d", dither); return LUTR_EINVAL; }
+    if (const int rc = check_dither(dither)) return rc;
     const bool packed = src_kind != 0;
     const void *src = packed ? (const void *)src_packed : (const void *)src_planar;
-    if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
-    if (interp != LUTR_INTERP_NONE && !c->lat) { set_error("no lattice set on this context (call lutr_ctx_set_lut first)"); return LUTR_EINVAL; }
-    if (interp < LUTR_INTERP_NONE || interp > LUTR_INTERP_PRISM) { set_error("unknown interpolation mode %d", interp); return LUTR_EINVAL; }
-    if (w < 0 || h < 0 || nframes < 0 || row0 < 0 || rows < 0 || row0 + rows > h) {
-        set_error("bad geometry w=%d h=%d nframes=%d row0=%d rows=%d", w, h, nframes, row0, rows);
-        return LUTR_EINVAL;
-    }
+    int rc = check_common(c, interp, LUTR_INTERP_NONE, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
     if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
     YuvConsts K;
-    int rc = make_yuv_consts_rgb2yuv(*p, &K);
+    rc = make_yuv_consts_rgb2yuv(*p, &K);
     if (rc) return rc;
     const int dl = p->lut_depth, dout = LUTR_FMT_DEPTH(p->fmt_out);
     const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
     RgbLayout Y{1, dl > 8, 0, 0, 0};
     if (packed) {
-        const int bits = LUTR_PACKED_BITS(src_kind), nc = LUTR_PACKED_NCOMP(src_kind);
-        const int ro = LUTR_PACKED_RO(src_kind), go = LUTR_PACKED_GO(src_kind), bo = LUTR_PACKED_BO(src_kind);
-        if ((bits != 8 && bits != 16) || (nc != 3 && nc != 4) || (src_kind >> 24) || ro >= nc || go >= nc || bo >= nc ||
-            ro == go || go == bo || ro == bo) {
-            set_error("unsupported packed format 0x%x", src_kind);
-            return LUTR_EINVAL;
-        }
-        if (dl != bits) { set_error("lut_depth %d must be the packed source's depth %d", dl, bits); return LUTR_EINVAL; }
-        Y = RgbLayout{nc, bits == 16, ro, go, bo};
+        PackedFmt f;
+        if (const int rc = decode_packed(src_kind, &f)) return rc;
+        if (dl != f.bits) { set_error("lut_depth %d must be the packed source's depth %d", dl, f.bits); return LUTR_EINVAL; }
+        Y = RgbLayout{f.nc, f.bits == 16, f.ro, f.go, f.bo};
     }
-    if (dither == LUTR_DITHER_ERROR_DIFFUSION && (row0 != 0 || rows != h)) {
-        set_error("error-diffusion dither couples the rows of a frame: whole frames only (row0 = 0, rows = h)");
-        return LUTR_EINVAL;
-    }
+    if (const int rc = check_dither_rows(dither, row0, rows, h)) return rc;
     const int bh = 1 << ocsy;
-    if (row0 % bh || (rows % bh && row0 + rows != h)) {
-        set_error("row0/rows must be multiples of the output chroma block height %d", bh);
-        return LUTR_EINVAL;
-    }
+    if (const int rc = check_row_blocks(row0, rows, h, bh, "output chroma block height")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
     // source streams in R, G, B order: gbrp planes are G, B, R
     PlaneSet P{};
@@ -1157,31 +1149,23 @@ int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
             P.s[k] = (const uint8_t *)src_packed->data; P.ss[k] = src_packed->stride; P.sfs[k] = src_packed->frame_stride;
         }
     } else {
-        static const int gbr[3] = {2, 0, 1};              // R, G, B <- planes 2, 0, 1
-        for (int k = 0; k < 3; k++) {
-            if (!src_planar->data[gbr[k]]) { set_error("null plane %d", gbr[k]); return LUTR_EINVAL; }
-            P.s[k] = (const uint8_t *)src_planar->data[gbr[k]]; P.ss[k] = src_planar->stride[gbr[k]];
-            P.sfs[k] = src_planar->frame_stride[gbr[k]];
+        for (int i = 0; i < 3; i++) {
+            P.s[i] = (const uint8_t *)src_planar->data[i]; P.ss[i] = src_planar->stride[i]; P.sfs[i] = src_planar->frame_stride[i];
         }
+        P = gbrp_to_rgb(P);
+        for (int k = 0; k < 3; k++)
+            if (!P.s[k]) { set_error("null plane %d", kGbrpToRgb[k]); return LUTR_EINVAL; }
     }
-    for (int i = 0; i < 3; i++) {
-        if (!dst->data[i]) { set_error("null plane %d", i); return LUTR_EINVAL; }
-        P.d[i] = (uint8_t *)dst->data[i]; P.ds[i] = dst->stride[i]; P.dfs[i] = dst->frame_stride[i];
-    }
+    if (const int rc = check_planes_set(dst, nullptr)) return rc;
+    for (int i = 0; i < 3; i++) { P.d[i] = (uint8_t *)dst->data[i]; P.ds[i] = dst->stride[i]; P.dfs[i] = dst->frame_stride[i]; }
     // a chroma sample is written by one thread while another may still read the pixels of its block: no in-place operation
     const int cw = (w + (1 << ocsx) - 1) >> ocsx, ch = (h + bh - 1) >> ocsy;
-    for (int i = 0; i < (packed ? 1 : 3); i++) {
-        uintptr_t slo, shi;
-        plane_span(P.s[i], P.ss[i], P.sfs[i], h, (long long)w * Y.step * bsi, nframes, &slo, &shi);
-        for (int j = 0; j < 3; j++) {
-            uintptr_t dlo, dhi;
-            plane_span(P.d[j], P.ds[j], P.dfs[j], j ? ch : h, (long long)(j ? cw : w) * (dout > 8 ? 2 : 1), nframes, &dlo, &dhi);
-            if (slo < dhi && dlo < shi) {
-                set_error("RGB -> YUV cannot run in place: the byte range of the source overlaps that of destination plane %d (bounding ranges over all rows and frames must be disjoint)", j);
-                return LUTR_EINVAL;
-            }
-        }
+    Span ss[3], ds[3];
+    for (int i = 0; i < 3; i++) {
+        ss[i] = plane_span(P.s[i], P.ss[i], P.sfs[i], h, (long long)w * Y.step * bsi, nframes);
+        ds[i] = plane_span(P.d[i], P.ds[i], P.dfs[i], i ? ch : h, (long long)(i ? cw : w) * (dout > 8 ? 2 : 1), nframes);
     }
+    if (const int rc = check_disjoint("RGB -> YUV", false, ss, packed ? 1 : 3, ds, 3)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
     LutConsts L{};
@@ -1191,18 +1175,8 @@ int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
     if (dither == LUTR_DITHER_NONE)
         return finish_launch(c, launch_rgb2yuv(c->stream, c->variant, L, K, P, Y, G, dout, ocsx, ocsy, interp));
     const size_t ny = (size_t)w * h * nframes, nc = (size_t)cw * ch * nframes;
-    if (ny + 2 * nc > c->fscratch_floats) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->fscratch) (void)hipFree(c->fscratch);
-        c->fscratch = nullptr;
-        c->fscratch_floats = 0;
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, (ny + 2 * nc) * sizeof(float));
-        if (e != hipSuccess) { set_error("hipMalloc(%zu): %s", (ny + 2 * nc) * sizeof(float), hipGetErrorString(e)); return LUTR_ENOMEM; }
-        c->fscratch = (float *)q;
-        c->fscratch_floats = ny + 2 * nc;
-    }
-    FloatPlanes F{c->fscratch, c->fscratch + ny, c->fscratch + ny + nc};
+    FloatPlanes F;
+    if (const int rc = dither_scratch(c, ny, nc, &F)) return rc;
     return finish_launch(c, launch_rgb2yuv_dither(c->stream, L, K, P, Y, G, F, dout, ocsx, ocsy, interp));
 }
 
@@ -1269,8 +1243,7 @@ int lutr_resize_planes(lutr_ctx *c, int family, int depth, int csx, int csy, int
         return LUTR_EINVAL;
     }
     if (nframes == 0) return LUTR_OK;
-    for (int i = 0; i < 3; i++)
-        if (!src->data[i] || !dst->data[i]) { set_error("null plane %d", i); return LUTR_EINVAL; }
+    if (const int rc = check_planes_set(src, dst)) return rc;
     const int es = depth > 8 ? 2 : 1;
     int psw[3], psh[3], pdw[3], pdh[3];
     for (int i = 0; i < 3; i++) {
@@ -1279,18 +1252,12 @@ int lutr_resize_planes(lutr_ctx *c, int family, int depth, int csx, int csy, int
         pdw[i] = (dw + (1 << cx) - 1) >> cx; pdh[i] = (dh + (1 << cy) - 1) >> cy;
     }
     // every destination sample reads a neighbourhood of source samples: no destination may overlap a source
+    Span ss[3], ds[3];
     for (int i = 0; i < 3; i++) {
-        uintptr_t slo, shi;
-        plane_span(src->data[i], src->stride[i], src->frame_stride[i], psh[i], (long long)psw[i] * es, nframes, &slo, &shi);
-        for (int j = 0; j < 3; j++) {
-            uintptr_t dlo, dhi;
-            plane_span(dst->data[j], dst->stride[j], dst->frame_stride[j], pdh[j], (long long)pdw[j] * es, nframes, &dlo, &dhi);
-            if (slo < dhi && dlo < shi) {
-                set_error("resize cannot run in place: the byte range of source plane %d overlaps that of destination plane %d (bounding ranges over all rows and frames must be disjoint)", i, j);
-                return LUTR_EINVAL;
-            }
-        }
+        ss[i] = plane_span(src->data[i], src->stride[i], src->frame_stride[i], psh[i], (long long)psw[i] * es, nframes);
+        ds[i] = plane_span(dst->data[i], dst->stride[i], dst->frame_stride[i], pdh[i], (long long)pdw[i] * es, nframes);
     }
+    if (const int rc = check_disjoint("resize", true, ss, 3, ds, 3)) return rc;
     if (es == 2)
         for (int i = 0; i < 3; i++)
             if (((uintptr_t)src->data[i] | (uintptr_t)dst->data[i] | (uintptr_t)src->stride[i] | (uintptr_t)dst->stride[i] |

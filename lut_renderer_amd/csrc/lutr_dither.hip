@@ -23,10 +23,8 @@
 //                 construction, so the wait cannot deadlock) trails it.  One workgroup per (frame, plane).
 //                 This is latency-bound integer/float bookkeeping -- no roofline claim; it exists so that the
 //                 option does something, at a rate far above the CPU's.
-#include <mutex>
-#include <set>
-
 #include "lutr_device.h"
+#include "lutr_launch.h"
 
 namespace lutr {
 
@@ -225,10 +223,7 @@ const char *launch_yuv_dither(hipStream_t st, const LutConsts &L, const YuvConst
         launch_yuv_float_xsub(st, L, K, P, G, F, win, csx, csy, ocsx, ocsy, mode);
     } else {
         const long long blocks = (long long)((G.w + (1 << csx) - 1) >> csx) * ((G.h + (1 << csy) - 1) >> csy) * G.nframes;
-        long long gb = (blocks + 255) / 256;
-        if (gb < 1) gb = 1;
-        if (gb > 256 * 64) gb = 256 * 64;
-        hipLaunchKernelGGL(k_yuv_float, dim3((unsigned)gb), dim3(256), 0, st, L, K, P, G, F, win, csx, csy, mode);
+        hipLaunchKernelGGL(k_yuv_float, dim3(grid_for(blocks, kGridStrideCap)), dim3(256), 0, st, L, K, P, G, F, win, csx, csy, mode);
     }
     return launch_dither_ed(st, K, P, G, F, wout, ocsx, ocsy) ? "k_yuv_float+k_dither_ed" : nullptr;
 }
@@ -247,18 +242,9 @@ bool launch_dither_ed(hipStream_t st, const YuvConsts &K, const PlaneSet &P, con
     if (nw > nbands) nw = nbands;
     const size_t lds = (size_t)nw * ((size_t)(G.w + 2) * sizeof(float) + sizeof(int));
     if (lds > 160 * 1024) return false;                   // rows wider than ~40,000 samples: not supported
-    {   // dynamic LDS above 64 KB has to be allowed per kernel and device
-        static std::set<int> done;
-        static std::mutex mu;
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        std::lock_guard<std::mutex> lock(mu);
-        if (!done.count(dev)) {
-            (void)hipFuncSetAttribute((const void *)k_dither_ed<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void *)k_dither_ed<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            done.insert(dev);
-        }
-    }
+    // dynamic LDS above 64 KB has to be allowed per kernel and device (whatever this launch needs: the next may need more)
+    (void)allow_lds((const void *)k_dither_ed<true>, 160 * 1024);
+    (void)allow_lds((const void *)k_dither_ed<false>, 160 * 1024);
     // packed path: every plane width a multiple of 4, destination rows aligned for 4-sample stores
     const int cwid = (G.w + (1 << ocsx) - 1) >> ocsx;
     bool vec = G.w % 4 == 0 && cwid % 4 == 0;

@@ -1,5 +1,5 @@
 // lutr_internal.h -- structures shared by the C-ABI layer (lutr_api.cpp) and the
-// gfx950 kernels (lutr_kernels.hip).  Not part of the public boundary.
+// gfx950 kernels (lutr_kernels.hip).  Not part of the public boundary.  The launchers' shared host helpers: lutr_launch.h.
 #pragma once
 
 #ifdef LUTR_HOST_ONLY
@@ -199,7 +199,7 @@ void launch_make_latm(hipStream_t st, const float4 *lat, float4 *out, size_t nod
 const char *launch_rgb_tile(hipStream_t st, const LutConsts &L, const PlaneSet &P, const FrameGeom &G,
                             int depth, int interp, unsigned *stats, unsigned *queue);
 
-// host helpers (yuv_consts.cpp / cube_parse.cpp)
+// host helpers (lutr_api.cpp)
 int make_yuv_consts(const lutr_yuv_params &p, YuvConsts *out);
 int make_yuv_consts_xsub(const lutr_yuv_params &p, YuvConsts *out);
 int make_yuv_consts_sited(const lutr_yuv_params &p, int chroma_loc, YuvConsts *out);

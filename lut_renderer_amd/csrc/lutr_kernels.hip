@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "lutr_device.h"
+#include "lutr_launch.h"
 
 namespace lutr {
 
@@ -193,43 +194,7 @@ __global__ __launch_bounds__(256) void k_yuv_vec(LutConsts L, YuvConsts K, Plane
 }
 
 // ================================================================= launchers
-static inline bool aligned_to(const void *p, long long a) { return ((uintptr_t)p % (uintptr_t)a) == 0; }
-
-static bool planes_aligned(const PlaneSet &P, int plane, long long a, bool batch)
-{
-    // the fast kernels address rows with 32-bit positive offsets; bottom-up (negative linesize) or
-    // huge strides go to the generic kernel, which does 64-bit signed arithmetic.  A tile kernel forms
-    // (row in tile) * stride + 16 * (unit in row) as one unsigned 32-bit offset with up to 31 rows and 63 units.
-    constexpr long long kMaxStride = (0xffffffffll - 64 * 16) / 32;
-    if (P.ss[plane] <= 0 || P.ds[plane] <= 0 || P.ss[plane] > kMaxStride || P.ds[plane] > kMaxStride) return false;
-    if (!aligned_to(P.s[plane], a) || !aligned_to(P.d[plane], a)) return false;
-    if (P.ss[plane] % a || P.ds[plane] % a) return false;
-    if (batch && (P.sfs[plane] % a || P.dfs[plane] % a)) return false;
-    return true;
-}
-
-// The persistent tile kernels pay a fixed start-up (coordinate table, tube staging, a wave's first tile at a quarter of the issue
-// rate) and end with a tail of partly idle CUs, so they only win on big launches.  Round 3, Gpx/s tile / plain vector kernels (taps
-// gathered from L1/L2, 5-8 waves per SIMD; profiles/r03_exp19_small_launches.txt), fused yuv420p10le strict: UHD 1 frame 181 / 272,
-// 2 frames 253 / 322, 4 frames 316 / 357, 8 frames 442 / 326, 16 frames 507 / 333, 64 frames 560 / 338; 1080p 8 frames 253 / 326,
-// 16 frames 337 / 300, 32 frames 424 / 324, 64 frames 478 / 329 -- the two-level chunk queue and its small chunks moved the
-// crossover of the fused kernels from 70 Mpx (round 2) to ~33 Mpx.  The RGB tile kernels keep 70 (their queue is round 1's).
-// LUTR_SMALL_JOB_MPX moves both boundaries (0 = never).
-static bool small_job(long long px, long long mpx = 70)
-{
-    if (const char *e = getenv("LUTR_SMALL_JOB_MPX")) { const long long v = atoll(e); if (v >= 0 && v <= 100000) mpx = v; }
-    return px < mpx * 1000000ll;
-}
-constexpr long long kSmallYuvMpx = 33;
-
-static unsigned grid_for(long long units, unsigned cap = 0x7fffffffu)
-{
-    long long b = (units + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > (long long)cap) b = cap;
-    return (unsigned)b;
-}
-
+// (layout predicates, grid sizing and the small-job boundary: lutr_launch.h)
 const char *launch_rgb(hipStream_t st, int variant, const LutConsts &L, const PlaneSet &P,
                        const FrameGeom &G, int depth, int mode, unsigned *stats, unsigned *queue)
 {
@@ -241,25 +206,19 @@ const char *launch_rgb(hipStream_t st, int variant, const LutConsts &L, const Pl
     bool vec_ok = (mode == LUTR_INTERP_NEAREST || mode == LUTR_INTERP_TRILINEAR || mode == LUTR_INTERP_TETRAHEDRAL) &&
                   G.w % pxt == 0 && px / pxt < 0x7fffffffll;
     for (int c = 0; c < 3 && vec_ok; c++)
-        vec_ok = planes_aligned(P, c, 16, G.nframes > 1);
+        vec_ok = planes_ok(P, c, 16, G.nframes > 1, kStrideTile, false);
     if (variant == VAR_GENERIC) vec_ok = false;
     // which LDS kernel would take the launch decides where "small" ends: the tube kernels have the two-level queue (33 Mpx), round 1's kernel not (70)
-    const char *pol0 = getenv("LUTR_RGB2");
-    const bool tube_first = !((pol0 && pol0[0] == '0') || getenv("LUTR_NO_RGB2")) &&
-                            ((pol0 && pol0[0] == 'a') || !tiles || mode != LUTR_INTERP_TRILINEAR);
-    if ((tiles || depth <= 10) && vec_ok && ((variant == VAR_AUTO && !small_job(px, tube_first ? kSmallYuvMpx : 70)) || variant == VAR_VEC_LDS)) {
+    const Rgb2Policy pol = rgb2_policy();
+    const bool tube_first = pol != RGB2_OFF && (pol == RGB2_ALL || !tiles || mode != LUTR_INTERP_TRILINEAR);
+    if ((tiles || depth <= 10) && vec_ok && ((variant == VAR_AUTO && !small_job(px, tube_first ? kSmallQueueMpx : kSmallTileMpx)) || variant == VAR_VEC_LDS)) {
         // round 3: the tube kernels (lutr_rgb2.hip) take the planes in (R, G, B) order; gbrp is (G, B, R)
         // Policy (profiles/r03_exp21_planar_rgb_tube_vs_round1.txt): with the two-level chunk queue the tube kernel wins every 4-tap and
         // nearest launch (gbrp10le tetrahedral 8 / 16 / 128 frames 359 / 412 / 432 vs 282 / 353 / 427 Gpx/s, gbrp 519 / 583 / 637 vs
         // 379 / 447 / 593, gbrp nearest 885 = 0.66 of the peak); trilinear's eight 16-byte taps stay on round 1's kernel, which is
         // 16-20 % faster there at 128 frames.  LUTR_RGB2=all sends everything it can take to the tube kernels, =0 nothing.
         if (tube_first) {
-            PlaneSet Q = P;
-            const int from[3] = {2, 0, 1};
-            for (int k = 0; k < 3; k++) {
-                Q.s[k] = P.s[from[k]]; Q.d[k] = P.d[from[k]]; Q.ss[k] = P.ss[from[k]]; Q.ds[k] = P.ds[from[k]];
-                Q.sfs[k] = P.sfs[from[k]]; Q.dfs[k] = P.dfs[from[k]];
-            }
+            const PlaneSet Q = gbrp_to_rgb(P);
             const char *name = wide ? launch_rgb_tube_ly1(st, L, Q, G, depth, mode, 0, stats, queue)
                                     : launch_rgb_tube_ly0(st, L, Q, G, depth, mode, 0, stats, queue);
             if (name) return name;
@@ -271,25 +230,25 @@ const char *launch_rgb(hipStream_t st, int variant, const LutConsts &L, const Pl
     // A ragged width on aligned (padded) rows: the fast kernel takes the columns up to the last multiple of
     // its unit, the scalar kernel the few that remain (each pixel is independent, so any split is exact).
     const int wv = G.w / pxt * pxt;
-    if (tiles && variant == VAR_AUTO && !vec_ok && wv > 0 && wv < G.w && !small_job(px) &&
+    if (tiles && variant == VAR_AUTO && !vec_ok && wv > 0 && wv < G.w && !small_job(px, kSmallTileMpx) &&
         (mode == LUTR_INTERP_NEAREST || mode == LUTR_INTERP_TRILINEAR || mode == LUTR_INTERP_TETRAHEDRAL) &&
         (long long)wv * G.rows * G.nframes / pxt < 0x7fffffffll &&
-        planes_aligned(P, 0, 16, G.nframes > 1) && planes_aligned(P, 1, 16, G.nframes > 1) &&
-        planes_aligned(P, 2, 16, G.nframes > 1)) {
+        planes_ok(P, 0, 16, G.nframes > 1, kStrideTile, false) && planes_ok(P, 1, 16, G.nframes > 1, kStrideTile, false) &&
+        planes_ok(P, 2, 16, G.nframes > 1, kStrideTile, false)) {
         FrameGeom Gv = G, Ge = G;
         Gv.w = wv;
         Ge.w = G.w - wv;
         PlaneSet Pe = P;
         for (int c = 0; c < 3; c++) { Pe.s[c] += (long long)wv * (wide ? 2 : 1); Pe.d[c] += (long long)wv * (wide ? 2 : 1); }
         const char *name = launch_rgb_tile(st, L, P, Gv, depth, mode, stats, queue);
-        hipLaunchKernelGGL(k_rgb_generic, dim3(grid_for((long long)Ge.w * G.rows * G.nframes, 256 * 64)), dim3(256), 0, st,
+        hipLaunchKernelGGL(k_rgb_generic, dim3(grid_for((long long)Ge.w * G.rows * G.nframes, kGridStrideCap)), dim3(256), 0, st,
                            L, Pe, Ge, wide, mode);
         return name;
     }
     if (!vec_ok) {
         if (variant == VAR_VEC_GLOBAL || variant == VAR_VEC_LDS) return nullptr;
         // grid-stride; enough blocks to fill 256 CUs x 8
-        hipLaunchKernelGGL(k_rgb_generic, dim3(grid_for(px, 256 * 64)), dim3(256), 0, st, L, P, G, wide, mode);
+        hipLaunchKernelGGL(k_rgb_generic, dim3(grid_for(px, kGridStrideCap)), dim3(256), 0, st, L, P, G, wide, mode);
         return "k_rgb_generic";
     }
     const dim3 grid(grid_for(px / (kVecBytes / (wide ? 2 : 1)))), block(256);
@@ -306,12 +265,6 @@ const char *launch_rgb(hipStream_t st, int variant, const LutConsts &L, const Pl
 
 // Round-2 tile kernels (lutr_tile2.hip): input and output depth are independent there, so source planes are checked
 // against the input unit (16 bytes of luma, the matching chroma bytes) and destination planes against the output unit.
-static bool plane_ok(const uint8_t *p, long long stride, long long fstride, long long a, bool batch)
-{
-    constexpr long long kMaxStride = (0xffffffffll - 64 * 32) / 32;
-    return stride > 0 && stride <= kMaxStride && aligned_to(p, a) && stride % a == 0 && (!batch || (fstride >= 0 && fstride % a == 0));
-}
-
 static const char *try_tile2(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
                              int din, int dout, int lut_depth, int csx, int csy, int mode, bool fast, unsigned *stats, unsigned *queue)
 {
@@ -326,9 +279,10 @@ static const char *try_tile2(hipStream_t st, const LutConsts &L, const YuvConsts
     const long long yi = 16, yo = (long long)pxt * (wout ? 2 : 1), ci = (long long)(pxt >> csx) * (win ? 2 : 1),
                     co = (long long)(pxt >> csx) * (wout ? 2 : 1);
     const bool batch = G.nframes > 1;
-    if (!plane_ok(P.s[0], P.ss[0], P.sfs[0], yi, batch) || !plane_ok(P.d[0], P.ds[0], P.dfs[0], yo > 16 ? 16 : yo, batch)) return nullptr;
-    for (int c = 1; c < 3; c++)
-        if (!plane_ok(P.s[c], P.ss[c], P.sfs[c], ci, batch) || !plane_ok(P.d[c], P.ds[c], P.dfs[c], co, batch)) return nullptr;
+    for (int c = 0; c < 3; c++)
+        if (!plane_ok(P.s[c], P.ss[c], P.sfs[c], c ? ci : yi, batch, kStrideTile2, true) ||
+            !plane_ok(P.d[c], P.ds[c], P.dfs[c], c ? co : (yo > 16 ? 16 : yo), batch, kStrideTile2, true))
+            return nullptr;
 #define T2_TRY(tag) return launch_yuv_tile2_##tag(st, L, K, P, G, din, dout, lut_depth, csx, csy, mode, fast, stats, queue)
     const int key = win * 1000 + wout * 100 + csx * 10 + csy;
     switch (key) {
@@ -354,7 +308,7 @@ const char *launch_yuv(hipStream_t st, int variant, const LutConsts &L, const Yu
     const int pxt = win ? 8 : 16;
     const int bh = 1 << csy;
     if (L.pre && !(L.pre_shared && lut_depth <= 10) && variant == VAR_VEC_LDS) variant = VAR_VEC_GLOBAL;   // a prelut the tile kernels cannot take
-    if (variant == VAR_VEC_LDS || (variant == VAR_AUTO && !small_job((long long)G.w * G.rows * G.nframes, kSmallYuvMpx))) {
+    if (variant == VAR_VEC_LDS || (variant == VAR_AUTO && !small_job((long long)G.w * G.rows * G.nframes, kSmallQueueMpx))) {
         if (const char *name = try_tile2(st, L, K, P, G, din, dout, lut_depth, csx, csy, mode, fast, stats, queue)) return name;
         if (variant == VAR_VEC_LDS) return nullptr;          // asked for the tile kernels, and they cannot take this call
     }
@@ -363,13 +317,12 @@ const char *launch_yuv(hipStream_t st, int variant, const LutConsts &L, const Yu
                   win == wout && G.w % pxt == 0 && G.row0 % bh == 0 && G.rows % bh == 0 &&
                   !(csx == 0 && csy == 1) &&
                   (long long)(G.w / pxt) * (G.rows >> csy) * G.nframes < 0x7fffffffll;
-    if (vec_ok) vec_ok = planes_aligned(P, 0, 16, G.nframes > 1) && planes_aligned(P, 1, cbytes, G.nframes > 1) &&
-                         planes_aligned(P, 2, cbytes, G.nframes > 1);
+    for (int c = 0; c < 3 && vec_ok; c++) vec_ok = planes_ok(P, c, c ? cbytes : 16, G.nframes > 1, kStrideTile, false);
     if (variant == VAR_GENERIC) vec_ok = false;
     // ragged width on aligned (padded) rows: tile kernel up to the last whole unit, scalar kernel for the rest
     // (the split falls on a chroma-block boundary: the unit is 8 or 16 luma samples wide)
     const int wv = G.w / pxt * pxt;
-    if (variant == VAR_AUTO && wv > 0 && wv < G.w && !small_job((long long)G.w * G.rows * G.nframes, kSmallYuvMpx)) {
+    if (variant == VAR_AUTO && wv > 0 && wv < G.w && !small_job((long long)G.w * G.rows * G.nframes, kSmallQueueMpx)) {
         FrameGeom Gv = G, Ge = G;
         Gv.w = wv;
         Ge.w = G.w - wv;
@@ -379,7 +332,7 @@ const char *launch_yuv(hipStream_t st, int variant, const LutConsts &L, const Yu
             Pe.s[0] += wv * bsi; Pe.d[0] += wv * bso;
             for (int c = 1; c < 3; c++) { Pe.s[c] += (wv >> csx) * bsi; Pe.d[c] += (wv >> csx) * bso; }
             const long long eb = (long long)((Ge.w + (1 << csx) - 1) >> csx) * ((G.rows + bh - 1) >> csy) * G.nframes;
-            hipLaunchKernelGGL(k_yuv_generic, dim3(grid_for(eb, 256 * 64)), dim3(256), 0, st, L, K, Pe, Ge, win, wout,
+            hipLaunchKernelGGL(k_yuv_generic, dim3(grid_for(eb, kGridStrideCap)), dim3(256), 0, st, L, K, Pe, Ge, win, wout,
                                csx, csy, mode);
             return name;
         }
@@ -389,9 +342,12 @@ const char *launch_yuv(hipStream_t st, int variant, const LutConsts &L, const Yu
         (mode == LUTR_INTERP_NEAREST || mode == LUTR_INTERP_TRILINEAR || mode == LUTR_INTERP_TETRAHEDRAL) &&
         G.w % 8 == 0 && G.row0 % bh == 0 && G.rows % bh == 0 && !(csx == 0 && csy == 1) &&
         (long long)(G.w / 8) * (G.rows >> csy) * G.nframes < 0x7fffffffll &&
-        plane_ok(P.s[0], P.ss[0], P.sfs[0], 16, G.nframes > 1) && plane_ok(P.d[0], P.ds[0], P.dfs[0], 8, G.nframes > 1) &&
-        plane_ok(P.s[1], P.ss[1], P.sfs[1], 16 >> csx, G.nframes > 1) && plane_ok(P.d[1], P.ds[1], P.dfs[1], 8 >> csx, G.nframes > 1) &&
-        plane_ok(P.s[2], P.ss[2], P.sfs[2], 16 >> csx, G.nframes > 1) && plane_ok(P.d[2], P.ds[2], P.dfs[2], 8 >> csx, G.nframes > 1)) {
+        plane_ok(P.s[0], P.ss[0], P.sfs[0], 16, G.nframes > 1, kStrideTile2, true) &&
+        plane_ok(P.d[0], P.ds[0], P.dfs[0], 8, G.nframes > 1, kStrideTile2, true) &&
+        plane_ok(P.s[1], P.ss[1], P.sfs[1], 16 >> csx, G.nframes > 1, kStrideTile2, true) &&
+        plane_ok(P.d[1], P.ds[1], P.dfs[1], 8 >> csx, G.nframes > 1, kStrideTile2, true) &&
+        plane_ok(P.s[2], P.ss[2], P.sfs[2], 16 >> csx, G.nframes > 1, kStrideTile2, true) &&
+        plane_ok(P.d[2], P.ds[2], P.dfs[2], 8 >> csx, G.nframes > 1, kStrideTile2, true)) {
         const dim3 grid(grid_for((long long)(G.w / 8) * (G.rows >> csy) * G.nframes)), block(256);
 #define YUV10_CASE(X, Y, I) \
         if (csx == X && csy == Y && mode == I) { \
@@ -406,7 +362,7 @@ const char *launch_yuv(hipStream_t st, int variant, const LutConsts &L, const Yu
     if (!vec_ok) {
         if (variant == VAR_VEC_GLOBAL || variant == VAR_VEC_LDS) return nullptr;
         const long long blocks = (long long)((G.w + (1 << csx) - 1) >> csx) * ((G.rows + bh - 1) >> csy) * G.nframes;
-        hipLaunchKernelGGL(k_yuv_generic, dim3(grid_for(blocks, 256 * 64)), dim3(256), 0, st, L, K, P, G, win, wout,
+        hipLaunchKernelGGL(k_yuv_generic, dim3(grid_for(blocks, kGridStrideCap)), dim3(256), 0, st, L, K, P, G, win, wout,
                            csx, csy, mode);
         return "k_yuv_generic";
     }

@@ -1,0 +1,121 @@
+// lutr_launch.h -- host-only helpers shared by the launchers in the .hip files: layout predicates, grid sizing, the
+// small-job boundary, the LUTR_RGB2 policy and per-device facts.  No device code.
+#pragma once
+
+#include <climits>
+#include <cstdlib>
+#include <mutex>
+#include <set>
+#include <utility>
+
+#include "lutr_internal.h"
+
+namespace lutr {
+
+// ---------------------------------------------------------------- plane alignment
+// Stride caps of plane_ok.  The fast kernels address rows with 32-bit positive offsets; bottom-up (negative linesize) or huge
+// strides go to the generic kernels, which do 64-bit signed arithmetic.
+constexpr long long kStrideAny = LLONG_MAX;     // xsub, rgb2yuv and sited vector kernels: 64-bit row offsets, no cap
+// k_rgb_tile (lutr_tile.hip) and the k_rgb_vec / k_yuv_vec kernels routed with it: a tile kernel forms
+// (row in tile) * stride + 16 * (unit in row) as one unsigned 32-bit offset with up to 31 rows and 63 units of 16 bytes
+constexpr long long kStrideTile = (0xffffffffll - 64 * 16) / 32;
+// k_yuv_tile2 (lutr_tile2.hip, Planes2's 32-bit strides) and the 16 -> 8 bit k_yuv_vec routed with it: the same offset with
+// units of up to 32 bytes
+constexpr long long kStrideTile2 = (0xffffffffll - 64 * 32) / 32;
+
+// A plane a kernel can address with `a`-byte accesses: positive stride up to `stride_cap`, base, stride and (batches) frame
+// stride aligned; fstride_nonneg also refuses a batch whose frames run backwards.  Every caller passes what its kernels need:
+// the caps and the frame-stride test differ on purpose, they decide which kernel a layout is routed to.
+inline bool plane_ok(const void *p, long long stride, long long fstride, long long a, bool batch, long long stride_cap,
+                     bool fstride_nonneg)
+{
+    return stride > 0 && stride <= stride_cap && (uintptr_t)p % (uintptr_t)a == 0 && stride % a == 0 &&
+           (!batch || ((!fstride_nonneg || fstride >= 0) && fstride % a == 0));
+}
+
+// source and destination plane `c` of P against the same unit
+inline bool planes_ok(const PlaneSet &P, int c, long long a, bool batch, long long stride_cap, bool fstride_nonneg)
+{
+    return plane_ok(P.s[c], P.ss[c], P.sfs[c], a, batch, stride_cap, fstride_nonneg) &&
+           plane_ok(P.d[c], P.ds[c], P.dfs[c], a, batch, stride_cap, fstride_nonneg);
+}
+
+// gbrp planes are (G, B, R); the tube kernels and the RGB -> YUV path take (R, G, B): slot k <- plane kGbrpToRgb[k]
+constexpr int kGbrpToRgb[3] = {2, 0, 1};
+inline PlaneSet gbrp_to_rgb(const PlaneSet &P)
+{
+    PlaneSet Q = P;
+    for (int k = 0; k < 3; k++) {
+        const int f = kGbrpToRgb[k];
+        Q.s[k] = P.s[f]; Q.d[k] = P.d[f]; Q.ss[k] = P.ss[f]; Q.ds[k] = P.ds[f]; Q.sfs[k] = P.sfs[f]; Q.dfs[k] = P.dfs[f];
+    }
+    return Q;
+}
+
+// ---------------------------------------------------------------- launch sizing
+// Blocks of 256 threads for `units` work items, at least one.  Grid-stride kernels pass kGridStrideCap: enough blocks to fill
+// 256 CUs x 8.
+constexpr unsigned kGridStrideCap = 256 * 64;
+inline unsigned grid_for(long long units, unsigned cap = 0x7fffffffu)
+{
+    long long b = (units + 255) / 256;
+    if (b < 1) b = 1;
+    if (b > (long long)cap) b = cap;
+    return (unsigned)b;
+}
+
+// The persistent tile kernels pay a fixed start-up (coordinate table, tube staging, a wave's first tile at a quarter of the issue
+// rate) and end with a tail of partly idle CUs, so they only win on big launches.  Round 3, Gpx/s tile / plain vector kernels (taps
+// gathered from L1/L2, 5-8 waves per SIMD; profiles/r03_exp19_small_launches.txt), fused yuv420p10le strict: UHD 1 frame 181 / 272,
+// 2 frames 253 / 322, 4 frames 316 / 357, 8 frames 442 / 326, 16 frames 507 / 333, 64 frames 560 / 338; 1080p 8 frames 253 / 326,
+// 16 frames 337 / 300, 32 frames 424 / 324, 64 frames 478 / 329 -- the two-level chunk queue and its small chunks moved the
+// crossover of the fused kernels and of the RGB tube kernels (8 UHD rgb24 frames: 480 vs 343 Gpx/s) from 70 Mpx (round 2) to
+// ~33 Mpx.  The RGB tile kernels keep 70 (their queue is round 1's).  LUTR_SMALL_JOB_MPX moves every boundary (0 = never).
+constexpr long long kSmallTileMpx = 70, kSmallQueueMpx = 33;
+inline bool small_job(long long px, long long mpx)
+{
+    if (const char *e = getenv("LUTR_SMALL_JOB_MPX")) { const long long v = atoll(e); if (v >= 0 && v <= 100000) mpx = v; }
+    return px < mpx * 1000000ll;
+}
+
+// LUTR_RGB2 / LUTR_NO_RGB2: which RGB launches the round-3 tube kernels (lutr_rgb2.hip) take.  LUTR_RGB2=0 or LUTR_NO_RGB2
+// set: none; LUTR_RGB2=all: everything they can; else the measured default of each launcher.
+enum Rgb2Policy { RGB2_OFF, RGB2_DEFAULT, RGB2_ALL };
+inline Rgb2Policy rgb2_policy()
+{
+    const char *e = getenv("LUTR_RGB2");
+    if ((e && e[0] == '0') || getenv("LUTR_NO_RGB2")) return RGB2_OFF;
+    return e && e[0] == 'a' ? RGB2_ALL : RGB2_DEFAULT;
+}
+
+// ---------------------------------------------------------------- per-device facts
+// Launchers may run on several threads at once (one context per thread): process-wide
+// state is initialised exactly once (function-local statics, call_once) or guarded by a mutex.
+inline int device_cus()
+{
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
+        return n > 0 ? n : 256;
+    }();
+    return cus;
+}
+
+// Blocks of more than 4 waves need more than the default 64 KB of dynamic LDS: allow it once per (device, kernel).
+// false: the runtime refused 160 KB of dynamic LDS for this kernel (the launch would fail).
+inline bool allow_lds(const void *kernel, size_t bytes)
+{
+    static std::set<std::pair<int, const void *>> done;      // the attribute is per device
+    static std::mutex mu;
+    if (bytes <= 65536) return true;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.count({dev, kernel})) return true;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
+    done.insert({dev, kernel});
+    return true;
+}
+
+}  // namespace lutr

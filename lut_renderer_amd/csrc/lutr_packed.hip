@@ -14,6 +14,7 @@
 // wave), lattice taps gathered from L2.  HBM-bound in principle (6 B/px rgb24); the
 // gather keeps it at the L2 rate, like k_rgb_vec.
 #include "lutr_device.h"
+#include "lutr_launch.h"
 
 namespace lutr {
 
@@ -107,21 +108,12 @@ __global__ __launch_bounds__(256) void k_packed_generic(LutConsts L, PackedSet P
 
 static inline bool mult4(long long v) { return (v & 3) == 0; }
 
-// launches under this many pixels stay on the plain vector kernel (no start-up cost); LUTR_SMALL_JOB_MPX as in lutr_kernels.hip
-static bool small_job_packed(long long px)
-{
-    long long mpx = 33;        // the tube kernels' crossover (two-level chunk queue): 8 UHD rgb24 frames run at 480 vs 343 Gpx/s
-    if (const char *e = getenv("LUTR_SMALL_JOB_MPX")) { const long long v = atoll(e); if (v >= 0 && v <= 100000) mpx = v; }
-    return px < mpx * 1000000ll;
-}
-
 const char *launch_packed(hipStream_t st, int variant, const LutConsts &L, const PackedSet &P, const FrameGeom &G,
                           int wide, int nc, int mode, unsigned *stats, unsigned *queue)
 {
     const long long px = (long long)G.w * G.rows * G.nframes;
     // round 3: the tube kernels (lutr_rgb2.hip) for the component orders that keep R, G, B adjacent: R G B [x], B G R [x], x R G B, x B G R
-    if ((variant == VAR_VEC_LDS || (variant == VAR_AUTO && !small_job_packed(px))) && !getenv("LUTR_NO_RGB2") &&
-        !(getenv("LUTR_RGB2") && getenv("LUTR_RGB2")[0] == '0')) {
+    if ((variant == VAR_VEC_LDS || (variant == VAR_AUTO && !small_job(px, kSmallQueueMpx))) && rgb2_policy() != RGB2_OFF) {
         const bool fwd = P.go == P.ro + 1 && P.bo == P.go + 1, bwd = P.go == P.bo + 1 && P.ro == P.go + 1;
         const int p0 = fwd ? P.ro : P.bo;
         if ((fwd || bwd) && (nc == 4 ? p0 <= 1 : p0 == 0)) {
@@ -147,10 +139,7 @@ const char *launch_packed(hipStream_t st, int variant, const LutConsts &L, const
     if (variant == VAR_GENERIC) vec_ok = false;
     if (!vec_ok) {
         if (variant == VAR_VEC_GLOBAL || variant == VAR_VEC_LDS) return nullptr;
-        long long b = (px + 255) / 256;
-        if (b < 1) b = 1;
-        if (b > 256 * 64) b = 256 * 64;
-        hipLaunchKernelGGL(k_packed_generic, dim3((unsigned)b), dim3(256), 0, st, L, P, G, wide, nc, mode);
+        hipLaunchKernelGGL(k_packed_generic, dim3(grid_for(px, kGridStrideCap)), dim3(256), 0, st, L, P, G, wide, nc, mode);
         return "k_packed_generic";
     }
     const dim3 grid((unsigned)((px / 4 + 255) / 256)), block(256);

@@ -30,6 +30,7 @@
 #include <utility>
 
 #include "lutr_internal.h"
+#include "lutr_launch.h"
 
 #ifndef LUTR_R2_LAYOUT
 #define LUTR_R2_LAYOUT 0
@@ -670,31 +671,6 @@ void k_rgb_tube(LutConsts L, Planes P, FrameGeom G, Geom TG)
 
 // ================================================================= launcher
 namespace {
-
-int device_cus()
-{
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        return n > 0 ? n : 256;
-    }();
-    return cus;
-}
-
-bool allow_lds(const void *kernel, size_t bytes)
-{
-    static std::set<std::pair<int, const void *>> done;      // the attribute is per device
-    static std::mutex mu;
-    if (bytes <= 65536) return true;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lock(mu);
-    if (done.count({dev, kernel})) return true;
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
-    done.insert({dev, kernel});
-    return true;
-}
 
 // see tube_plane_stride in lutr_tile2.hip: node index = pr * A + pg * B + pb, no collision mod 32 (mod 16 for the 16-byte nodes of
 // trilinear, read with ds_read_b128) for steps of +-1 (+-2 if possible)

@@ -14,6 +14,7 @@
 //   without LUTR_R2Y_WI   the generic kernel, the unquantised pass of the dither path and the launcher
 //   LUTR_R2Y_WI / _WO     the vector kernels of one container mix (8 -> 8, 16 -> 16, 16 -> 8): 3 source kinds x 3 layouts x 4 modes
 #include "lutr_device.h"
+#include "lutr_launch.h"
 
 namespace lutr {
 
@@ -251,29 +252,15 @@ __global__ __launch_bounds__(256) void k_rgb2yuv_float(LutConsts L, YuvConsts K,
     }
 }
 
-static unsigned r2y_grid(long long units)
-{
-    long long b = (units + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 256 * 64) b = 256 * 64;                       // grid-stride: enough blocks to fill 256 CUs x 8
-    return (unsigned)b;
-}
-
 const char *launch_rgb2yuv_dither(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const RgbLayout &Y,
                                   const FrameGeom &G, const FloatPlanes &F, int dout, int ocsx, int ocsy, int mode)
 {
     const long long units = (long long)((G.w + (1 << ocsx) - 1) >> ocsx) * ((G.h + (1 << ocsy) - 1) >> ocsy) * G.nframes;
-    hipLaunchKernelGGL(k_rgb2yuv_float, dim3(r2y_grid(units)), dim3(256), 0, st, L, K, P, G, Y, F, ocsx, ocsy, mode);
+    hipLaunchKernelGGL(k_rgb2yuv_float, dim3(grid_for(units, kGridStrideCap)), dim3(256), 0, st, L, K, P, G, Y, F, ocsx, ocsy, mode);
     return launch_dither_ed(st, K, P, G, F, dout > 8, ocsx, ocsy) ? "k_rgb2yuv_float+k_dither_ed" : nullptr;
 }
 
 // ================================================================= launcher
-// a row set the vector kernel can address with `a`-byte accesses: positive stride, base, stride and (batches) frame stride aligned
-static bool r2y_plane_ok(const void *p, long long stride, long long fstride, long long a, bool batch)
-{
-    return stride > 0 && (uintptr_t)p % (uintptr_t)a == 0 && stride % a == 0 && (!batch || fstride % a == 0);
-}
-
 const char *launch_rgb2yuv(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
                            const RgbLayout &Y, const FrameGeom &G, int dout, int ocsx, int ocsy, int mode)
 {
@@ -292,13 +279,13 @@ const char *launch_rgb2yuv(hipStream_t st, int variant, const LutConsts &L, cons
         if ((long long)(H.w / 8) * (H.rows / bh) * H.nframes >= 0x7fffffffll) return false;
         if (Y.step == 1) {
             for (int c = 0; c < 3; c++)
-                if (!r2y_plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], 8 * bsi, batch)) return false;
-        } else if (!r2y_plane_ok(Q.s[0], Q.ss[0], Q.sfs[0], 4, batch)) {
+                if (!plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], 8 * bsi, batch, kStrideAny, false)) return false;
+        } else if (!plane_ok(Q.s[0], Q.ss[0], Q.sfs[0], 4, batch, kStrideAny, false)) {
             return false;
         }
-        if (!r2y_plane_ok(Q.d[0], Q.ds[0], Q.dfs[0], 8 * bso, batch)) return false;
+        if (!plane_ok(Q.d[0], Q.ds[0], Q.dfs[0], 8 * bso, batch, kStrideAny, false)) return false;
         for (int c = 1; c < 3; c++)
-            if (!r2y_plane_ok(Q.d[c], Q.ds[c], Q.dfs[c], (8 >> ocsx) * bso, batch)) return false;
+            if (!plane_ok(Q.d[c], Q.ds[c], Q.dfs[c], (8 >> ocsx) * bso, batch, kStrideAny, false)) return false;
         return true;
     };
     auto vec = [&](const PlaneSet &Q, const FrameGeom &H) -> const char * {
@@ -308,7 +295,7 @@ const char *launch_rgb2yuv(hipStream_t st, int variant, const LutConsts &L, cons
     };
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
         const long long units = (long long)((H.w + (1 << ocsx) - 1) >> ocsx) * ((H.rows + bh - 1) >> ocsy) * H.nframes;
-        hipLaunchKernelGGL(k_rgb2yuv_generic, dim3(r2y_grid(units)), dim3(256), 0, st, L, K, Q, H, Y, wout, ocsx, ocsy, mode);
+        hipLaunchKernelGGL(k_rgb2yuv_generic, dim3(grid_for(units, kGridStrideCap)), dim3(256), 0, st, L, K, Q, H, Y, wout, ocsx, ocsy, mode);
         return "k_rgb2yuv_generic";
     };
     if (variant == VAR_GENERIC) return generic(P, G);

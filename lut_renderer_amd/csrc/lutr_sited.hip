@@ -26,6 +26,7 @@
 // Compiled with -ffp-contract=off like every strict kernel: the weighted sums are exact integers in fp32, the rest is the
 // arithmetic of lutr_device.h.
 #include "lutr_device.h"
+#include "lutr_launch.h"
 
 namespace lutr {
 
@@ -346,11 +347,6 @@ __global__ __launch_bounds__(256) void k_yuv_sited(LutConsts L, YuvConsts K, Pla
 
 // The vector instance's layout: every plane of src and dst aligned to the lane's access (4 luma samples, 2 chroma samples),
 // positive strides, and frame strides that keep the alignment.
-static bool sited_plane_ok(const uint8_t *p, long long stride, long long fstride, long long a, bool batch)
-{
-    return stride > 0 && (uintptr_t)p % (uintptr_t)a == 0 && stride % a == 0 && (!batch || fstride % a == 0);
-}
-
 const char *launch_yuv_sited(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
                              int din, int dout, int csy, int loc, int mode)
 {
@@ -370,7 +366,7 @@ const char *launch_yuv_sited(hipStream_t st, const LutConsts &L, const YuvConsts
     const bool batch = G.nframes > 1;
     for (int c = 0; c < 3 && vec; c++) {
         const long long a = c ? ca : ya;
-        vec = sited_plane_ok(P.s[c], P.ss[c], P.sfs[c], a, batch) && sited_plane_ok(P.d[c], P.ds[c], P.dfs[c], a, batch);
+        vec = planes_ok(P, c, a, batch, kStrideAny, false);
     }
 #define SITED_CASE(CSY, COX, COY, I, NAME) \
     if (csy == CSY && cox == COX && coy == COY && mode == I) { \

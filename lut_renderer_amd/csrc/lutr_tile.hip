@@ -29,7 +29,7 @@
 //     wave's first chunk by its id (no burst of atomics at start-up).
 //   * LDS nodes are 12 bytes {r,g,b} for the 4-tap modes, 16 for trilinear (DESIGN.md "Kernels").
 //   * Launches too small to fill this machinery go to the plain vector kernels instead
-//     (lutr_kernels.hip small_job()).
+//     (small_job(), lutr_launch.h).
 //
 // Arithmetic is the strict restatement (see lutr_kernels.hip): -ffp-contract=off, FFmpeg's
 // scalar C order, bit-identical to the oracle.
@@ -40,6 +40,7 @@
 #include <utility>
 
 #include "lutr_internal.h"
+#include "lutr_launch.h"
 #ifndef LUTR_NT
 #define LUTR_NT 1        // non-temporal stores: every output byte is written once (+0.3 % here; non-temporal LOADS cost 2.5 % on gbrp10le)
 #endif
@@ -760,20 +761,7 @@ void k_rgb_tile(LutConsts L_, TilePlanes P, FrameGeom G, TileGeom TG)
 }
 
 // ================================================================= launchers
-// Launchers may run on several threads at once (one context per thread): process-wide
-// state is initialised exactly once (function-local statics, call_once) or guarded by a mutex.
-static int device_cus()
-{
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            n = prop.multiProcessorCount;
-        return n > 0 ? n : 256;
-    }();
-    return cus;
-}
-
+// (device_cus, allow_lds: lutr_launch.h)
 // Split the 64 lanes of a wave between x (units of one row) and y (unit rows) so that a
 // row of `uw` units wastes as few lanes as possible; prefer wide tiles (longer bursts).
 static void plan_tiles(TileGeom *tg, int uw, int urows, int nframes, int win_nodes, int waves_per_cu, unsigned *stats,
@@ -842,21 +830,8 @@ static int plan_table(TileGeom *tg, const LutConsts &L, int kLN)
     return tg->tab_bytes;
 }
 
-// Blocks of more than 4 waves need more than the default 64 KB of dynamic LDS: allow it once per kernel.
-static void allow_lds(const void *kernel, size_t bytes)
-{
-    static std::set<std::pair<int, const void *>> done;      // the attribute is per device
-    static std::mutex mu;
-    if (bytes <= 65536) return;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lock(mu);
-    if (done.count({dev, kernel})) return;
-    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    done.insert({dev, kernel});
-}
 #define LUTR_LAUNCH_TILE(kernel, ...) \
-    do { allow_lds((const void *)(kernel), lds); hipLaunchKernelGGL((kernel), grid, block, lds, st, __VA_ARGS__); } while (0)
+    do { (void)allow_lds((const void *)(kernel), lds); hipLaunchKernelGGL((kernel), grid, block, lds, st, __VA_ARGS__); } while (0)
 
 const char *launch_rgb_tile(hipStream_t st, const LutConsts &L, const PlaneSet &P, const FrameGeom &G, int depth, int mode,
                             unsigned *stats, unsigned *queue)

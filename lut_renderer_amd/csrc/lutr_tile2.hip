@@ -41,6 +41,7 @@
 #include <utility>
 
 #include "lutr_internal.h"
+#include "lutr_launch.h"
 #ifndef LUTR_NT
 #define LUTR_NT 2        // 1: non-temporal stores, 2: and loads -- frames are read once and written once (+0.9 % / +0.5 % on 4:2:0, +1 % each on 4:4:4)
 #endif
@@ -225,7 +226,7 @@ struct Geom {
     unsigned *stats;      // optional device counters; nullptr = off
 };
 
-struct Planes2 {          // 32-bit strides: the launcher only sends layouts that fit (planes_aligned)
+struct Planes2 {          // 32-bit strides: the launcher only sends layouts that fit (plane_ok under kStrideTile2)
     const uint8_t *s[3];
     uint8_t       *d[3];
     unsigned ss[3], ds[3];
@@ -1835,32 +1836,6 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
 
 // ================================================================= launcher
 namespace {
-
-int device_cus()
-{
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        return n > 0 ? n : 256;
-    }();
-    return cus;
-}
-
-// false: the runtime refused 160 KB of dynamic LDS for this kernel (the launch would fail): the caller declines the call
-bool allow_lds(const void *kernel, size_t bytes)
-{
-    static std::set<std::pair<int, const void *>> done;      // the attribute is per device
-    static std::mutex mu;
-    if (bytes <= 65536) return true;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lock(mu);
-    if (done.count({dev, kernel})) return true;
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
-    done.insert({dev, kernel});
-    return true;
-}
 
 // Largest index (unsigned)(yy + {rv, gv, bu}) can take for raw codes in [0, 2^din - 1]: each sum is monotone in its inputs.
 int table_entries(const YuvConsts &K, int din)

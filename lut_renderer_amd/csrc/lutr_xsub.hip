@@ -13,6 +13,7 @@
 //   without LUTR_XS_WI   the generic kernel, the unquantised pass of the dither path and the launcher
 //   LUTR_XS_WI / _WO     the vector kernels of one container mix (8 -> 8, 16 -> 16, 16 -> 8): 6 layout pairs x 3 modes
 #include "lutr_device.h"
+#include "lutr_launch.h"
 
 namespace lutr {
 
@@ -262,29 +263,15 @@ __global__ __launch_bounds__(256) void k_yuv_float_xsub(LutConsts L, YuvConsts K
     }
 }
 
-static unsigned xs_grid(long long units)
-{
-    long long b = (units + 255) / 256;
-    if (b < 1) b = 1;
-    if (b > 256 * 64) b = 256 * 64;                       // grid-stride: enough blocks to fill 256 CUs x 8
-    return (unsigned)b;
-}
-
 void launch_yuv_float_xsub(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
                            const FloatPlanes &F, int win, int icsx, int icsy, int ocsx, int ocsy, int mode)
 {
     const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy);
     const long long units = (long long)((G.w + (1 << csx) - 1) >> csx) * ((G.h + (1 << csy) - 1) >> csy) * G.nframes;
-    hipLaunchKernelGGL(k_yuv_float_xsub, dim3(xs_grid(units)), dim3(256), 0, st, L, K, P, G, F, win, icsx, icsy, ocsx, ocsy, mode);
+    hipLaunchKernelGGL(k_yuv_float_xsub, dim3(grid_for(units, kGridStrideCap)), dim3(256), 0, st, L, K, P, G, F, win, icsx, icsy, ocsx, ocsy, mode);
 }
 
 // ================================================================= launcher
-// a plane the vector kernel can address with `a`-byte accesses: positive stride, base, stride and (batches) frame stride aligned
-static bool xs_plane_ok(const void *p, long long stride, long long fstride, long long a, bool batch)
-{
-    return stride > 0 && (uintptr_t)p % (uintptr_t)a == 0 && stride % a == 0 && (!batch || fstride % a == 0);
-}
-
 const char *launch_yuv_xsub(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
                             const FrameGeom &G, int din, int dout, int icsx, int icsy, int ocsx, int ocsy, int mode)
 {
@@ -300,11 +287,11 @@ const char *launch_yuv_xsub(hipStream_t st, int variant, const LutConsts &L, con
         if (!mix_ok || !(mode == LUTR_INTERP_NEAREST || mode == LUTR_INTERP_TRILINEAR || mode == LUTR_INTERP_TETRAHEDRAL)) return false;
         if (H.w % pxt || H.row0 % bh || H.rows % bh) return false;
         if ((long long)(H.w / pxt) * (H.rows / bh) * H.nframes >= 0x7fffffffll) return false;
-        if (!xs_plane_ok(Q.s[0], Q.ss[0], Q.sfs[0], pxt * bsi, batch) || !xs_plane_ok(Q.d[0], Q.ds[0], Q.dfs[0], pxt * bso, batch))
+        if (!plane_ok(Q.s[0], Q.ss[0], Q.sfs[0], pxt * bsi, batch, kStrideAny, false) || !plane_ok(Q.d[0], Q.ds[0], Q.dfs[0], pxt * bso, batch, kStrideAny, false))
             return false;
         for (int c = 1; c < 3; c++)
-            if (!xs_plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], (pxt >> icsx) * bsi, batch) ||
-                !xs_plane_ok(Q.d[c], Q.ds[c], Q.dfs[c], (pxt >> ocsx) * bso, batch))
+            if (!plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], (pxt >> icsx) * bsi, batch, kStrideAny, false) ||
+                !plane_ok(Q.d[c], Q.ds[c], Q.dfs[c], (pxt >> ocsx) * bso, batch, kStrideAny, false))
                 return false;
         return true;
     };
@@ -316,7 +303,7 @@ const char *launch_yuv_xsub(hipStream_t st, int variant, const LutConsts &L, con
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
         const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy);
         const long long units = (long long)((H.w + (1 << csx) - 1) >> csx) * ((H.rows + bh - 1) >> csy) * H.nframes;
-        hipLaunchKernelGGL(k_yuv_xsub_generic, dim3(xs_grid(units)), dim3(256), 0, st, L, K, Q, H, win, wout, icsx, icsy, ocsx, ocsy,
+        hipLaunchKernelGGL(k_yuv_xsub_generic, dim3(grid_for(units, kGridStrideCap)), dim3(256), 0, st, L, K, Q, H, win, wout, icsx, icsy, ocsx, ocsy,
                            mode);
         return "k_yuv_xsub_generic";
     };

@@ -164,22 +164,17 @@ def _byte_range(t: torch.Tensor) -> Tuple[int, int]:
     return lo, hi + t.element_size()
 
 
-def _check_not_in_place(src: Sequence[torch.Tensor], dst: Sequence[torch.Tensor]) -> None:
+_RESIZE_IN_PLACE = "a resize cannot run in place: destination planes must not overlap the source planes"
+_RGB2YUV_IN_PLACE = "RGB -> YUV cannot run in place: destination planes must not overlap the source"
+
+
+def _check_not_in_place(src: Sequence[torch.Tensor], dst: Sequence[torch.Tensor], message: str) -> None:
     for a in src:
         alo, ahi = _byte_range(a)
         for b in dst:
             blo, bhi = _byte_range(b)
             if alo < bhi and blo < ahi:
-                raise ValueError("a resize cannot run in place: destination planes must not overlap the source planes")
-
-
-def _check_rgb_not_in_place(src, dst: Sequence[torch.Tensor]) -> None:
-    for a in ([src] if isinstance(src, torch.Tensor) else src):
-        alo, ahi = _byte_range(a)
-        for b in dst:
-            blo, bhi = _byte_range(b)
-            if alo < bhi and blo < ahi:
-                raise ValueError("RGB -> YUV cannot run in place: destination planes must not overlap the source")
+                raise ValueError(message)
 
 
 def _frames3(planes: Sequence[torch.Tensor]) -> list:
@@ -233,6 +228,47 @@ def _planes_struct(planes: Sequence[torch.Tensor], device: torch.device) -> Tupl
     return st, nframes
 
 
+def _plane_pair(src: Sequence[torch.Tensor], dst: Sequence[torch.Tensor], device: torch.device):
+    """(struct of src, struct of dst, nframes) for a source and a destination that must agree on the number of frames."""
+    s, nf = _planes_struct(src, device)
+    d, nfd = _planes_struct(dst, device)
+    if nf != nfd:
+        raise ValueError("src and dst disagree on the number of frames")
+    return s, d, nf
+
+
+def _packed_struct(t, name: str, nc: int, bits: int, device: torch.device, integers_only: bool) -> _native.Packed:
+    """Describe one [H,W,C] or [F,H,W,C] packed image as struct lutr_packed.  integers_only: a floating-point tensor of the right
+    element size is refused too (apply_packed has always taken one as raw bits)."""
+    if not isinstance(t, torch.Tensor) or t.device != device:
+        raise ValueError("packed images must be torch tensors resident on the engine's GPU")
+    if (t.dim() not in (3, 4) or t.shape[-1] != nc or (integers_only and t.is_floating_point())
+            or t.element_size() * 8 != bits):
+        raise ValueError(f"'{name}' takes [H,W,{nc}] or [F,H,W,{nc}] tensors of {bits}-bit elements")
+    if t.stride(-1) != 1 or t.stride(-2) != nc:
+        raise ValueError("pixels must be dense along the row")
+    st = _native.Packed()
+    st.data = t.data_ptr()
+    st.stride = t.stride(-3) * t.element_size()
+    st.frame_stride = t.stride(0) * t.element_size() if t.dim() == 4 else 0
+    return st
+
+
+def _yuv_params(fmt_in: int, fmt_out: int, lut_depth: int, matrix_in: str, matrix_out: str, range_src: str, range_in: str,
+                range_out: str) -> _native.YuvParams:
+    p = _native.YuvParams()
+    p.fmt_in, p.fmt_out, p.lut_depth = fmt_in, fmt_out, lut_depth
+    p.matrix_in, p.matrix_out = _native.MATRIX[matrix_in], _native.MATRIX[matrix_out]
+    p.range_src, p.range_in, p.range_out = _native.RANGE[range_src], _native.RANGE[range_in], _native.RANGE[range_out]
+    return p
+
+
+def _yuv_out_dtype(depth: int, inherit: Optional[torch.dtype]) -> torch.dtype:
+    """dtype of freshly allocated YUV output planes: uint8 up to 8 bit; deeper outputs inherit a 16-bit source dtype, else (a
+    narrower source, or None: an RGB source) int16."""
+    return torch.uint8 if depth <= 8 else inherit if inherit is not None and inherit.itemsize == 2 else torch.int16
+
+
 class LutEngine:
     """One GPU context: a device lattice plus the stream its kernels run on."""
 
@@ -255,8 +291,9 @@ class LutEngine:
         self._lock = threading.RLock()
         self.precision = "strict"
         self._applied_lut = None          # the CubeLut object apply_lut uploaded last (its upload-skipping shortcut)
-        self._rz_scratch = None           # source-size output of the LUT ahead of a resize: (key, [3 planes])
-        self._fr_scratch = None           # 8-bit YUV frames between the two stages of a full-range RGB source: (key, [3 planes])
+        # grow-only plane caches of _scratch, (key, [3 planes]) per slot: "rz" = the source-size output of the LUT ahead of a
+        # resize, "fr" = the 8-bit YUV frames between the two stages of a full-range RGB source
+        self._scratch_slots = {}
 
     # -- lifetime ---------------------------------------------------------
     def close(self) -> None:
@@ -400,10 +437,7 @@ class LutEngine:
             dst = [torch.empty_like(t) for t in src]
         _check_planes(src, fmt, w, h, "source")
         _check_planes(dst, fmt, w, h, "destination")
-        s, nf = _planes_struct(src, self.device)
-        d, nfd = _planes_struct(dst, self.device)
-        if nf != nfd:
-            raise ValueError("src and dst disagree on the number of frames")
+        s, d, nf = _plane_pair(src, dst, self.device)
         rows = h - row0 if rows is None else rows
         with self._lock:
             self._bind_stream()
@@ -422,16 +456,11 @@ class LutEngine:
         dw, dh = parse_size(size)
         sh, sw = src[0].shape[-2], src[0].shape[-1]
         if dst is None:
-            dt = src[0].dtype
-            lead = tuple(src[0].shape[:-2])
-            dst = [torch.empty(lead + fmt.plane_shape(i, dw, dh), dtype=dt, device=self.device) for i in range(3)]
+            dst = self._new_planes(fmt, dw, dh, tuple(src[0].shape[:-2]), src[0].dtype)
         _check_planes(src, fmt, sw, sh, "source")
         _check_planes(dst, fmt, dw, dh, "destination")
-        _check_not_in_place(src, dst)
-        s, nf = _planes_struct(src, self.device)
-        d, nfd = _planes_struct(dst, self.device)
-        if nf != nfd:
-            raise ValueError("src and dst disagree on the number of frames")
+        _check_not_in_place(src, dst, _RESIZE_IN_PLACE)
+        s, d, nf = _plane_pair(src, dst, self.device)
         with self._lock:
             self._bind_stream()
             _native.check(self._lib.lutr_resize_planes(
@@ -439,13 +468,16 @@ class LutEngine:
                 C.byref(s), C.byref(d)))
         return dst
 
-    def _scratch(self, fmt: PixFmt, w: int, h: int, nframes: int, dtype) -> list:
-        """Engine-owned planes of `nframes` frames at w x h in `fmt` (kept for the next call of the same shape or smaller)."""
+    def _scratch(self, slot: str, fmt: PixFmt, w: int, h: int, nframes: int, dtype) -> list:
+        """Engine-owned planes of `nframes` frames at w x h in `fmt` (kept in `slot` for the next call of the same shape or smaller)."""
         key = (fmt.name, w, h, dtype)
-        if self._rz_scratch is None or self._rz_scratch[0] != key or self._rz_scratch[1][0].shape[0] < nframes:
-            self._rz_scratch = (key, [torch.empty((nframes,) + fmt.plane_shape(i, w, h), dtype=dtype, device=self.device)
-                                      for i in range(3)])
-        return [t[:nframes] for t in self._rz_scratch[1]]
+        cur = self._scratch_slots.get(slot)
+        if cur is None or cur[0] != key or cur[1][0].shape[0] < nframes:
+            cur = self._scratch_slots[slot] = (key, self._new_planes(fmt, w, h, (nframes,), dtype))
+        return [t[:nframes] for t in cur[1]]
+
+    def _new_planes(self, fmt: PixFmt, w: int, h: int, lead: tuple, dtype) -> list:
+        return [torch.empty(lead + fmt.plane_shape(i, w, h), dtype=dtype, device=self.device) for i in range(3)]
 
     def _lut_then_resize(self, src, dst, fin: Optional[PixFmt], fout: PixFmt, w: int, h: int, out_size, row0: int, rows, chunk,
                          chroma_loc, lut_call, src_frames=None):
@@ -455,20 +487,19 @@ class LutEngine:
         if row0 != 0 or (rows is not None and rows != h):
             raise ValueError("a resize (out_size) takes whole frames: row0 / rows are not supported with it")
         if dst is None:
-            dt = torch.uint8 if fout.depth <= 8 else src[0].dtype if src[0].element_size() == 2 else torch.int16
             lead = tuple(src_frames[0].shape[:1]) if src_frames is not None else tuple(src[0].shape[:-2])
-            dst = [torch.empty(lead + fout.plane_shape(i, dw, dh), dtype=dt, device=self.device) for i in range(3)]
+            dst = self._new_planes(fout, dw, dh, lead, _yuv_out_dtype(fout.depth, src[0].dtype))
         if src_frames is None:             # (a packed source comes checked, as a list of one [F,H,W,C] tensor, in src_frames)
             _check_planes(src, fin, w, h, "source")
         _check_planes(dst, fout, dw, dh, "destination")
-        _check_not_in_place(src, dst)
+        _check_not_in_place(src, dst, _RESIZE_IN_PLACE)
         s3, d3 = (_frames3(src) if src_frames is None else src_frames), _frames3(dst)
         nf = s3[0].shape[0]
         if d3[0].shape[0] != nf:
             raise ValueError("src and dst disagree on the number of frames")
         chunk = resize_chunk_default() if chunk is None else max(1, int(chunk))
         with self._lock:
-            tmp_all = self._scratch(fout, w, h, min(chunk, nf), d3[0].dtype)
+            tmp_all = self._scratch("rz", fout, w, h, min(chunk, nf), d3[0].dtype)
             for f0 in range(0, nf, chunk):
                 n = min(chunk, nf - f0)
                 tmp = [t[:n] for t in tmp_all]
@@ -486,19 +517,7 @@ class LutEngine:
         bits, nc, ro, go, bo = _native.PACKED_FORMATS[pix_fmt]
         if dst is None:
             dst = torch.empty_like(src)
-        descs = []
-        for t in (src, dst):
-            if not isinstance(t, torch.Tensor) or t.device != self.device:
-                raise ValueError("packed images must be torch tensors resident on the engine's GPU")
-            if t.dim() not in (3, 4) or t.shape[-1] != nc or t.element_size() * 8 != bits:
-                raise ValueError(f"'{pix_fmt}' takes [H,W,{nc}] or [F,H,W,{nc}] tensors of {bits}-bit elements")
-            if t.stride(-1) != 1 or t.stride(-2) != nc:
-                raise ValueError("pixels must be dense along the row")
-            st = _native.Packed()
-            st.data = t.data_ptr()
-            st.stride = t.stride(-3) * t.element_size()
-            st.frame_stride = t.stride(0) * t.element_size() if t.dim() == 4 else 0
-            descs.append(st)
+        descs = [_packed_struct(t, pix_fmt, nc, bits, self.device, False) for t in (src, dst)]
         if src.shape != dst.shape:
             raise ValueError("src and dst shapes differ")
         h, w = src.shape[-3], src.shape[-2]
@@ -534,14 +553,8 @@ class LutEngine:
             raise ValueError("apply_yuv takes planar YUV formats")
         check_chroma_loc(chroma_loc, dither, fin.name, fout.name)
         xsub = (fin.csx, fin.csy) != (fout.csx, fout.csy)
-        p = _native.YuvParams()
-        p.fmt_in, p.fmt_out = fin.code, fout.code
-        p.lut_depth = lut_depth if lut_depth is not None else fin.depth
-        p.matrix_in = _native.MATRIX[matrix_in]
-        p.matrix_out = _native.MATRIX[matrix_out or matrix_in]
-        p.range_src = _native.RANGE[range_src]
-        p.range_in = _native.RANGE[range_in or range_src]
-        p.range_out = _native.RANGE[range_out]
+        p = _yuv_params(fin.code, fout.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
+                        range_src, range_in or range_src, range_out)
         h, w = src[0].shape[-2], src[0].shape[-1]
         if out_size is not None:
             kw = dict(pix_fmt=pix_fmt, interp=interp, matrix_in=matrix_in, matrix_out=matrix_out, range_src=range_src,
@@ -550,15 +563,10 @@ class LutEngine:
             return self._lut_then_resize(src, dst, fin, fout, w, h, out_size, row0, rows, resize_chunk, chroma_loc,
                                          lambda s_, d_: self.apply_yuv(s_, d_, **kw))
         if dst is None:
-            dt = torch.uint8 if fout.depth <= 8 else src[0].dtype if src[0].element_size() == 2 else torch.int16
-            lead = tuple(src[0].shape[:-2])
-            dst = [torch.empty(lead + fout.plane_shape(i, w, h), dtype=dt, device=self.device) for i in range(3)]
+            dst = self._new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype))
         _check_planes(src, fin, w, h, "source")
         _check_planes(dst, fout, w, h, "destination")
-        s, nf = _planes_struct(src, self.device)
-        d, nfd = _planes_struct(dst, self.device)
-        if nf != nfd:
-            raise ValueError("src and dst disagree on the number of frames")
+        s, d, nf = _plane_pair(src, dst, self.device)
         rows = h - row0 if rows is None else rows
         if dither != "none" and (row0 != 0 or rows != h):
             raise ValueError("error-diffusion dither couples the rows of a frame: whole frames only")
@@ -591,16 +599,7 @@ class LutEngine:
             st, nf = _planes_struct(src, self.device)
             return st, None, w, h, nf, tuple(src[0].shape[:-2])
         t = src
-        if not isinstance(t, torch.Tensor) or t.device != self.device:
-            raise ValueError("packed images must be torch tensors resident on the engine's GPU")
-        if t.dim() not in (3, 4) or t.shape[-1] != fmt.ncomp or t.is_floating_point() or t.element_size() * 8 != fmt.depth:
-            raise ValueError(f"'{fmt.name}' takes [H,W,{fmt.ncomp}] or [F,H,W,{fmt.ncomp}] tensors of {fmt.depth}-bit elements")
-        if t.stride(-1) != 1 or t.stride(-2) != fmt.ncomp:
-            raise ValueError("pixels must be dense along the row")
-        st = _native.Packed()
-        st.data = t.data_ptr()
-        st.stride = t.stride(-3) * t.element_size()
-        st.frame_stride = t.stride(0) * t.element_size() if t.dim() == 4 else 0
+        st = _packed_struct(t, fmt.name, fmt.ncomp, fmt.depth, self.device, True)
         return None, st, t.shape[-2], t.shape[-3], (t.shape[0] if t.dim() == 4 else 1), tuple(t.shape[:-3])
 
     def apply_rgb_to_yuv(self, src, dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: str,
@@ -643,8 +642,7 @@ class LutEngine:
             return self._lut_then_resize(src, dst, PixFmt(fin.name, "gbr", fin.depth, 0, 0, True), fout, w, h, out_size, row0,
                                          rows, resize_chunk, None, lambda s_, d_: self.apply_rgb_to_yuv(s_, d_, **kw))
         if dst is None:
-            dt = torch.uint8 if fout.depth <= 8 else torch.int16
-            dst = [torch.empty(lead + fout.plane_shape(i, w, h), dtype=dt, device=self.device) for i in range(3)]
+            dst = self._new_planes(fout, w, h, lead, _yuv_out_dtype(fout.depth, None))      # (no dtype to inherit: int16)
         _check_planes(dst, fout, w, h, "destination")
         d, nfd = _planes_struct(dst, self.device)
         if nf != nfd:
@@ -652,12 +650,9 @@ class LutEngine:
         rows = h - row0 if rows is None else rows
         if dither != "none" and (row0 != 0 or rows != h):
             raise ValueError("error-diffusion dither couples the rows of a frame: whole frames only")
-        _check_rgb_not_in_place(src if fin.packed else list(src), dst)
-        p = _native.YuvParams()
-        p.fmt_in, p.fmt_out = _native.fmt_code(fin.depth, 0, 0), fout.code
-        p.lut_depth = fin.depth
-        p.matrix_in = p.matrix_out = _native.MATRIX[matrix_out]
-        p.range_src = p.range_in = p.range_out = _native.RANGE[range_out]
+        _check_not_in_place([src] if fin.packed else src, dst, _RGB2YUV_IN_PLACE)
+        p = _yuv_params(_native.fmt_code(fin.depth, 0, 0), fout.code, fin.depth, matrix_out, matrix_out, range_out, range_out,
+                        range_out)
         mode = _native.INTERP[interp] if lut else _native.INTERP_NONE
         with self._lock:
             self._bind_stream()
@@ -689,11 +684,9 @@ class LutEngine:
         m = matrix or "smpte170m"
         _, _, w, h, nf, lead = self._rgb_source(src, fin)
         with self._lock:
-            key = (mid.name, w, h)
-            if self._fr_scratch is None or self._fr_scratch[0] != key or self._fr_scratch[1][0].shape[0] < nf:
-                self._fr_scratch = (key, [torch.empty((nf,) + mid.plane_shape(i, w, h), dtype=torch.uint8, device=self.device)
-                                          for i in range(3)])
-            tmp = [t[:nf] if len(lead) else t[0] for t in self._fr_scratch[1]]
+            tmp = self._scratch("fr", mid, w, h, nf, torch.uint8)
+            if not lead:
+                tmp = [t[0] for t in tmp]
             self.apply_rgb_to_yuv(src, tmp, pix_fmt=pix_fmt, out_pix_fmt=mid.name, lut=False, matrix_out=m, range_out=rng,
                                   row0=row0, rows=rows)
             return self.apply_yuv(tmp, dst, pix_fmt=mid.name, out_pix_fmt=out_pix_fmt, interp=interp, matrix_in=m, matrix_out=m,
@@ -701,44 +694,33 @@ class LutEngine:
                                   dither=dither, out_size=out_size, resize_chunk=resize_chunk)
 
 
-def yuv_constants(**kw) -> np.ndarray:
-    """The 32-float constant block liblutr derives for a lutr_yuv_params (host only, no GPU)."""
+def _yuv_constants(entry: str, *extra, **kw) -> np.ndarray:
     p = _native.YuvParams()
     for k, v in kw.items():
         setattr(p, k, v)
     out = (C.c_float * 32)()
-    _native.check(_native.load().lutr_yuv_constants(C.byref(p), out))
+    _native.check(getattr(_native.load(), entry)(C.byref(p), *extra, out))
     return np.array(list(out), dtype=np.float32)
+
+
+def yuv_constants(**kw) -> np.ndarray:
+    """The 32-float constant block liblutr derives for a lutr_yuv_params (host only, no GPU)."""
+    return _yuv_constants("lutr_yuv_constants", **kw)
 
 
 def yuv_constants_xsub(**kw) -> np.ndarray:
     """`yuv_constants` for a chroma subsampling change (lutr_yuv_constants_xsub): the block mean's n is the output block's."""
-    p = _native.YuvParams()
-    for k, v in kw.items():
-        setattr(p, k, v)
-    out = (C.c_float * 32)()
-    _native.check(_native.load().lutr_yuv_constants_xsub(C.byref(p), out))
-    return np.array(list(out), dtype=np.float32)
+    return _yuv_constants("lutr_yuv_constants_xsub", **kw)
 
 
 def yuv_constants_rgb2yuv(**kw) -> np.ndarray:
     """The constant block of `apply_rgb_to_yuv` (lutr_yuv_constants_rgb2yuv): fmt_out, lut_depth, matrix_out and range_out count."""
-    p = _native.YuvParams()
-    for k, v in kw.items():
-        setattr(p, k, v)
-    out = (C.c_float * 32)()
-    _native.check(_native.load().lutr_yuv_constants_rgb2yuv(C.byref(p), out))
-    return np.array(list(out), dtype=np.float32)
+    return _yuv_constants("lutr_yuv_constants_rgb2yuv", **kw)
 
 
 def yuv_constants_sited(chroma_loc: Optional[str], **kw) -> np.ndarray:
     """`yuv_constants` with the sited down-sampling's 1/n folded into cbr..crb (lutr_yuv_constants_sited)."""
-    p = _native.YuvParams()
-    for k, v in kw.items():
-        setattr(p, k, v)
-    out = (C.c_float * 32)()
-    _native.check(_native.load().lutr_yuv_constants_sited(C.byref(p), chroma_loc_code(chroma_loc), out))
-    return np.array(list(out), dtype=np.float32)
+    return _yuv_constants("lutr_yuv_constants_sited", chroma_loc_code(chroma_loc), **kw)
 
 
 def _tensor_from_ptr(ptr: int, count: int, device: torch.device) -> torch.Tensor:
