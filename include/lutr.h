@@ -344,6 +344,36 @@ int lutr_apply_rgb_to_yuv(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, i
  * read by the kernels (they are filled from matrix_out / range_out).  Host only. */
 int lutr_yuv_constants_rgb2yuv(const lutr_yuv_params *p, float out[32]);
 
+/* ---- planar float RGB sources, gbrpf32le (what ffmpeg decodes an OpenEXR sequence to: lut3d's planar-float
+ *      path on the frame itself, then format=<pix_fmt>, ffmpeg.py:246 and :304-310) ---- */
+/* lut3d on planar float RGB, float in and float out.  src / dst: three planes of 32-bit floats in gbrp order (plane 0 = G,
+ * 1 = B, 2 = R); strides in bytes; base pointers, strides and (batches) frame strides must be multiples of 4, else LUTR_EINVAL.
+ * Per pixel and channel: the input is sanitised by its bit pattern (NaN -> 0, +inf -> FLT_MAX, -inf -> -FLT_MAX, vf_lut3d.c's
+ * sanitizef); a .csp prelut is interpolated PER PIXEL on the table lutr_ctx_set_prelut was given (prelut_interp_1d_linear:
+ * t = clip((x - min) * scale, 0, size - 1), lerp of tab[(int)t] and its neighbour); s = clip(x * (scale * (n - 1)), 0, n - 1);
+ * interp<mode> (all five modes); the three floats are stored as they are: no clip, no scaling -- values outside [0, 1] survive.
+ * Always strict precision (fast / fma32 run strict here, no suffix on the last kernel).  src == dst (in place) is allowed.
+ * Kernels: "k_rgbf_vec<interp>" (nearest / trilinear / tetrahedral; width a multiple of 4; positive strides; planes, strides and
+ * frame strides 16-byte aligned), "k_rgbf_generic" for everything else; a ragged width on aligned rows is split between the
+ * two.  Variants: auto and generic as for lutr_apply_yuv; vec_global fails with LUTR_EINVAL where the vector kernel cannot take
+ * the layout; vec_lds always fails with LUTR_EINVAL (there is no LDS kernel for this path). */
+int lutr_apply_planar_rgb_f32(lutr_ctx *ctx, int interp, int w, int h, int nframes, const lutr_planes *src, const lutr_planes *dst,
+                              int row0, int rows);
+/* Planar float RGB (src as for lutr_apply_planar_rgb_f32) -> lut3d as above -> each channel quantised to a 16-bit code,
+ * q = clip(rintf(v * 65535), 0, 65535) with round-half-to-even -> planar YUV p->fmt_out through the output stage of
+ * lutr_apply_rgb_to_yuv at lut_depth 16 (constants: lutr_yuv_constants_rgb2yuv; chroma from the block sum of q; a partial block
+ * takes the edge again; 4:4:0 is LUTR_EINVAL).  Reads of *p what lutr_apply_rgb_to_yuv reads; p->lut_depth must be 16, else
+ * LUTR_EINVAL.  interp == LUTR_INTERP_NONE leaves lut3d out: sanitise, quantise, convert.
+ * row0 and rows must be multiples of the output chroma block height 2^ocsy unless row0 + rows == h.
+ * dither: LUTR_DITHER_NONE, or LUTR_DITHER_ERROR_DIFFUSION on whole frames only (the scratch of lutr_apply_yuv_dither).
+ * Always strict precision.  Not in place: the byte-range rule of lutr_apply_rgb_to_yuv, checked before anything touches the device.
+ * Kernels: "k_rgbf2yuv_vec<wout,ocsx,ocsy,interp|nolut>" (nearest / trilinear / tetrahedral / no LUT; width a multiple of 8;
+ * positive strides; source planes 16-byte aligned, destination planes to the 8 (chroma: 8 >> ocsx) samples a thread stores;
+ * row0 / rows multiples of 2^ocsy), "k_rgbf2yuv_generic" for everything else; a ragged width on aligned rows is split between
+ * the two; dithering runs "k_rgbf2yuv_float+k_dither_ed".  Variants as for lutr_apply_planar_rgb_f32. */
+int lutr_apply_rgbf_to_yuv(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int dither, int w, int h, int nframes,
+                           const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
+
 /* ---- precision ---- */
 /* STRICT (default): every kernel is a bit-exact restatement of FFmpeg's scalar C lut3d (vf_lut3d.c order of operations,
  * no fused multiply-add in the blend).  FAST: permission to use the tolerance-bounded tile kernels -- lattice staged as

@@ -40,6 +40,7 @@ SYMBOLS = (
     "lutr_apply_planar_rgb", "lutr_apply_packed_rgb", "lutr_apply_yuv", "lutr_apply_yuv_dither",
     "lutr_apply_yuv_sited", "lutr_yuv_constants_sited", "lutr_apply_yuv_xsub", "lutr_yuv_constants_xsub",
     "lutr_apply_rgb_to_yuv", "lutr_yuv_constants_rgb2yuv",
+    "lutr_apply_planar_rgb_f32", "lutr_apply_rgbf_to_yuv",
     "lutr_resize_filter", "lutr_resize_planes",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
 )
@@ -79,6 +80,10 @@ PACKED_FORMATS = {
     "rgb48le": (16, 3, 0, 1, 2), "bgr48le": (16, 3, 2, 1, 0),
     "rgba64le": (16, 4, 0, 1, 2), "bgra64le": (16, 4, 2, 1, 0),
 }
+
+
+#: planar float RGB sources -> planes per frame (G, B, R[, A])
+FLOAT_FORMATS = {"gbrpf32le": 3, "gbrapf32le": 4}
 
 
 class LutrError(RuntimeError):
@@ -140,6 +145,9 @@ def load() -> C.CDLL:
     lib.lutr_apply_rgb_to_yuv.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Packed),
                                           C.POINTER(Planes), ci, ci]
     lib.lutr_yuv_constants_rgb2yuv.argtypes = [C.POINTER(YuvParams), C.POINTER(C.c_float)]
+    lib.lutr_apply_planar_rgb_f32.argtypes = [vp, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
+    lib.lutr_apply_rgbf_to_yuv.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes),
+                                           ci, ci]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]
     lib.lutr_ctx_set_variant.argtypes = [vp, ci]

@@ -79,13 +79,27 @@ def _cached_cube(path: Path) -> CubeLut:
 
 
 def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = None) -> dict:
-    """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv -- or, for an RGB `pix_fmt` (gbrp* / a packed name) with
-    a YUV `out_pix_fmt`, of LutEngine.apply_rgb_to_yuv (`is_rgb_call(kw)` tells the two apart)."""
+    """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv -- or, for an RGB `pix_fmt` (gbrp* / a packed name / a
+    float name) with a YUV `out_pix_fmt`, of LutEngine.apply_rgb_to_yuv (`is_rgb_call(kw)` tells the two apart).  A float
+    `pix_fmt` (gbrpf32le / gbrapf32le) without `out_pix_fmt`, or with a float one, stays float:
+    `is_float_out_call(kw)`, and LutEngine.apply_rgb_float takes `kw["interp"]`."""
     from .engine import parse_pix_fmt
     if plan.interp not in _ENGINE_INTERP:
         raise ValueError(f"lut3d has no interpolation mode '{plan.interp}'")
     from .engine import parse_rgb_source
     rgb = parse_rgb_source(pix_fmt)
+    if rgb is not None and rgb.floating:
+        out = parse_rgb_source(out_pix_fmt) if out_pix_fmt else rgb
+        if out is not None and out.floating:
+            # float in, float out: lut3d's float path alone, no format= behind it
+            if plan.prologue:
+                raise ValueError("a float source flagged full range has no float output: the reference converts it to 8-bit YUV "
+                                 "ahead of lut3d; name a YUV out_pix_fmt")
+            if out.nplanes > rgb.nplanes:
+                raise ValueError(f"'{pix_fmt}' has no alpha plane to carry into '{out_pix_fmt}'")
+            return dict(pix_fmt=pix_fmt, out_pix_fmt=out.name, interp=plan.interp)
+        if out is not None or parse_pix_fmt(out_pix_fmt.replace("yuvj", "yuv")).family != "yuv":
+            raise ValueError(f"a float RGB source takes a float or a planar YUV out_pix_fmt, not '{out_pix_fmt}'")
     if rgb is not None:
         # an RGB source (DESIGN.md 3.9): lut3d runs on the RGB frame itself, then format=<pix_fmt>.  The engine has no encoder to
         # negotiate an output format with, so the caller names it.
@@ -127,6 +141,13 @@ def is_rgb_call(kw: dict) -> bool:
     return parse_rgb_source(kw.get("pix_fmt")) is not None
 
 
+def is_float_out_call(kw: dict) -> bool:
+    """True when `engine_call_for` returned a float source with a float output (LutEngine.apply_rgb_float)."""
+    from .engine import parse_rgb_source
+    out = parse_rgb_source(kw.get("out_pix_fmt"))
+    return out is not None and out.floating
+
+
 def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: str, width: Optional[int] = None,
               height: Optional[int] = None, input_matrix: str = "auto", colorspace: Optional[str] = None,
               color_range: Optional[str] = None, output_tags: str = "bt709", out_pix_fmt: Optional[str] = None,
@@ -136,7 +157,9 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  With an RGB `pix_fmt` (gbrp* or a packed name such as rgb24) and a YUV
     `out_pix_fmt` (required then), `planes` is the three gbrp planes (G, B, R) or the one [F,]H,W,C packed tensor and the
-    chain is lut3d on the RGB frame, then RGB -> YUV.  Returns (planes_out, tags) where `tags` is the colour
+    chain is lut3d on the RGB frame, then RGB -> YUV.  `pix_fmt` = gbrpf32le / gbrapf32le takes float32 planes
+    (DESIGN.md 3.10): with a YUV `out_pix_fmt` the same chain, without one (or with a float one) float planes come back, an alpha
+    plane copied through (one device, no dither, no resolution).  Returns (planes_out, tags) where `tags` is the colour
     metadata the reference would write for this policy (None = inherit / none).
 
     `engine` may be a LutEngine (or LutEngineGroup) that already holds the lattice (then `cube` may be
@@ -204,6 +227,13 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         kw["chroma_loc"] = chroma_loc
     if out_size is not None:
         kw["out_size"] = out_size
+    float_out = is_float_out_call(kw)
+    if float_out:
+        from .multigpu import LutEngineGroup
+        if kw["dither"] != "none" or out_size is not None:
+            raise ValueError("a float output takes no dither and no resolution")
+        if isinstance(engine, LutEngineGroup) or (engine is None and len(devices) > 1):
+            raise ValueError("a float output needs a single device")
     own = engine is None
     eng = engine if engine is not None else _cached_engine(devices)
     lut = None
@@ -215,7 +245,11 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
             eng._applied_lut = lut
         if eng.precision != precision:
             eng.set_precision(precision)
-        result = eng.apply_rgb_to_yuv(planes, out, **kw) if rgb_src is not None else eng.apply_yuv(planes, out, **kw)
+        if float_out:
+            n_out = parse_rgb_source(kw["out_pix_fmt"]).nplanes
+            result = eng.apply_rgb_float(planes[:n_out], out, interp=kw["interp"])
+        else:
+            result = eng.apply_rgb_to_yuv(planes, out, **kw) if rgb_src is not None else eng.apply_yuv(planes, out, **kw)
         if own:
             eng.sync()
     return result, output_color_tags(plan.output_policy)

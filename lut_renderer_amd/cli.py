@@ -43,7 +43,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("-o", "--output", required=True)
     ap.add_argument("--size", required=True, help="WxH")
     ap.add_argument("--pix-fmt", required=True,
-                    help="planar YUV, or an RGB source (gbrp* / rgb24, bgr24, rgba .., rgb48le, rgba64le) with a YUV --out-pix-fmt")
+                    help="planar YUV, or an RGB source (gbrp* / rgb24, bgr24, rgba .., rgb48le, rgba64le) with a YUV --out-pix-fmt, "
+                         "or float RGB (gbrpf32le / gbrapf32le): float out without --out-pix-fmt, else a YUV one")
     ap.add_argument("--out-pix-fmt", default=None)
     ap.add_argument("--cube", required=True)
     ap.add_argument("--interp", default="tetrahedral")
@@ -83,6 +84,9 @@ def plan_from_args(args):
                      colorspace=args.colorspace, color_range=args.color_range)
     plan = resolve_lut_plan(params, args.cube, info)
     kw = engine_call_for(plan, args.pix_fmt, args.out_pix_fmt)
+    from .api import is_float_out_call
+    if is_float_out_call(kw) and (args.zscale_dither == "error_diffusion" or getattr(args, "out_size", None)):
+        raise ValueError("a float output takes no dither and no --out-size")
     if args.zscale_dither == "error_diffusion":
         kw["dither"] = "error_diffusion"
     from .api import is_rgb_call

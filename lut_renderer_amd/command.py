@@ -282,7 +282,11 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     cmd += ["-i", str(source), "-o", str(output), "--size", f"{source_info.width}x{source_info.height}",
             "--pix-fmt", source_info.pix_fmt]
     pix_fmt = resolve_pix_fmt(params, source_info, notes) if params.video_codec else ""
-    if _is_rgb_source(source_info.pix_fmt):
+    if _is_float_source(source_info.pix_fmt):
+        # a float source: without a resolved output format the stage stays float (no --out-pix-fmt, no dither)
+        if chroma_loc is not None:
+            raise ValueError("chroma siting (chroma_loc) is not defined for an RGB source")
+    elif _is_rgb_source(source_info.pix_fmt):
         # an RGB source: the engine has no encoder to negotiate an output format with, and no chroma to site
         if not pix_fmt:
             raise ValueError(f"an RGB source ('{source_info.pix_fmt}') needs a resolved output pixel format (params.pix_fmt or a "
@@ -325,6 +329,12 @@ def _is_rgb_source(pix_fmt) -> bool:
     from ._native import PACKED_FORMATS
     name = str(pix_fmt or "")
     return name in PACKED_FORMATS or bool(re.match(r"^gbrp(\d+)?(le)?$", name))
+
+
+def _is_float_source(pix_fmt) -> bool:
+    """gbrpf32le / gbrapf32le, the planar float RGB sources (`_native.FLOAT_FORMATS`)."""
+    from ._native import FLOAT_FORMATS
+    return str(pix_fmt or "") in FLOAT_FORMATS
 
 
 #: planar formats the engine's resize takes (DESIGN.md 3.7); packed RGB keeps -s on the encoder

@@ -311,6 +311,9 @@ struct lutr_ctx {
         unsigned long long gen = 0;      // the table's number (LutConsts::pre_gen, g_prelut_gen)
     };
     PreTable pre_tab[9];
+    // the float path interpolates the prelut per pixel: a device copy of `prelut` as it was given (3 x pre_size
+    // floats), uploaded on first use and dropped with the per-depth tables
+    float *pre_raw = nullptr;
     // lutr_lut_broadcast: copies other contexts are still reading out of THIS context's lattice (one event per receiver,
     // recorded on the receiver's stream behind its copy).  The lattice must not be overwritten or freed before they finish.
     std::vector<std::pair<int, hipEvent_t>> readers;      // (receiver's device, event)
@@ -348,6 +351,7 @@ static void drop_prelut_tables(lutr_ctx *c)
 {
     for (auto &t : c->pre_tab)
         if (t.dev) { (void)hipStreamSynchronize(c->stream); (void)hipFree(t.dev); t.dev = nullptr; }
+    if (c->pre_raw) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->pre_raw); c->pre_raw = nullptr; }
 }
 
 // The body of the four lutr_yuv_constants* exports; make(YuvConsts *) is only called with p checked.
@@ -865,17 +869,10 @@ static const float4 *fma32_lattice(lutr_ctx *c, int depth)
     return derived_lattice(c, &c->latm[depth - 8], depth, launch_make_latm);
 }
 
-static int fill_lut(LutConsts *L, lutr_ctx *c, int depth)
+// the lattice side of LutConsts (everything but the prelut's per-code table)
+static void fill_lattice(LutConsts *L, lutr_ctx *c, int depth)
 {
     const int maxi = (1 << depth) - 1;
-    const lutr_ctx::PreTable *t;
-    if (const int rc = prelut_table(c, depth, &t)) return rc;
-    L->pre = t->dev;
-    L->pre_stride = t->entries;
-    L->pre_shared = t->shared;
-    L->pre_kappa = t->kappa;
-    L->pre_host = t->shared ? t->host.data() : nullptr;
-    L->pre_gen = t->gen;
     L->lat = c->lat;
     L->lat16 = nullptr;
     L->latm = nullptr;
@@ -885,6 +882,43 @@ static int fill_lut(LutConsts *L, lutr_ctx *c, int depth)
     L->scale_f = 1.0f / (float)maxi;
     L->lut_max = (float)(c->n - 1);
     for (int i = 0; i < 3; i++) L->sc[i] = c->scale[i] * L->lut_max;
+}
+
+static int fill_lut(LutConsts *L, lutr_ctx *c, int depth)
+{
+    const lutr_ctx::PreTable *t;
+    if (const int rc = prelut_table(c, depth, &t)) return rc;
+    L->pre = t->dev;
+    L->pre_stride = t->entries;
+    L->pre_shared = t->shared;
+    L->pre_kappa = t->kappa;
+    L->pre_host = t->shared ? t->host.data() : nullptr;
+    L->pre_gen = t->gen;
+    fill_lattice(L, c, depth);
+    return LUTR_OK;
+}
+
+// The float path's constants: the lattice (at depth 16, which only sets fields these kernels do not read) and the prelut as the
+// raw table, uploaded on first use.  lut = false (LUTR_INTERP_NONE): neither is read.
+static int fill_lut_float(LutConsts *L, FloatPre *Q, lutr_ctx *c, bool lut)
+{
+    *L = LutConsts{};
+    *Q = FloatPre{};
+    if (!lut) return LUTR_OK;
+    fill_lattice(L, c, 16);
+    if (!c->pre_size) return LUTR_OK;
+    if (!c->pre_raw) {
+        void *p = nullptr;
+        hipError_t e = hipMalloc(&p, c->prelut.size() * sizeof(float));
+        if (e != hipSuccess) { set_error("hipMalloc(prelut): %s", hipGetErrorString(e)); return LUTR_ENOMEM; }
+        e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(p, c->prelut.data(), c->prelut.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(p); return hip_fail(e, "prelut upload"); }
+        c->pre_raw = (float *)p;
+    }
+    Q->tab = c->pre_raw;
+    Q->size = c->pre_size;
+    for (int i = 0; i < 3; i++) { Q->min[i] = c->pre_min[i]; Q->scale[i] = c->pre_scale[i]; }
     return LUTR_OK;
 }
 
@@ -1178,6 +1212,76 @@ int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
     FloatPlanes F;
     if (const int rc = dither_scratch(c, ny, nc, &F)) return rc;
     return finish_launch(c, launch_rgb2yuv_dither(c->stream, L, K, P, Y, G, F, dout, ocsx, ocsy, interp));
+}
+
+// gbrpf32 planes hold 4-byte samples: base pointers, row strides and (batches) frame strides must be multiples of 4
+static int check_float_planes(const lutr_planes *a, int nframes, const char *what)
+{
+    for (int i = 0; i < 3; i++)
+        if (((uintptr_t)a->data[i] | (uintptr_t)a->stride[i] | (nframes > 1 ? (uintptr_t)a->frame_stride[i] : 0)) & 3) {
+            set_error("float planes need 4-byte aligned rows: %s plane %d (pointer, stride and frame stride must be multiples of 4)", what, i);
+            return LUTR_EINVAL;
+        }
+    return LUTR_OK;
+}
+
+int lutr_apply_planar_rgb_f32(lutr_ctx *c, int interp, int w, int h, int nframes, const lutr_planes *src, const lutr_planes *dst,
+                              int row0, int rows)
+{
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    if (const int rc = check_planes_set(src, dst)) return rc;
+    if (const int rc = check_float_planes(src, nframes, "source")) return rc;
+    if (const int rc = check_float_planes(dst, nframes, "destination")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // always strict: no kernel of this path reads the fast / fma32 lattices
+    LutConsts L; FloatPre Q; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = fill_lut_float(&L, &Q, c, true)) return rc;
+    fill_planes(&P, src, dst);
+    return finish_launch(c, launch_rgbf(c->stream, c->variant, L, Q, gbrp_to_rgb(P), G, interp));
+}
+
+int lutr_apply_rgbf_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dither, int w, int h, int nframes,
+                           const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+{
+    if (const int rc = check_dither(dither)) return rc;
+    int rc = check_common(c, interp, LUTR_INTERP_NONE, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    if (p->lut_depth != 16) { set_error("lut_depth %d: a float source is quantised to 16-bit codes, lut_depth must be 16", p->lut_depth); return LUTR_EINVAL; }
+    YuvConsts K;
+    rc = make_yuv_consts_rgb2yuv(*p, &K);
+    if (rc) return rc;
+    const int dout = LUTR_FMT_DEPTH(p->fmt_out), ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
+    if (const int rc = check_dither_rows(dither, row0, rows, h)) return rc;
+    const int bh = 1 << ocsy;
+    if (const int rc = check_row_blocks(row0, rows, h, bh, "output chroma block height")) return rc;
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    if (const int rc = check_planes_set(src, dst)) return rc;
+    if (const int rc = check_float_planes(src, nframes, "source")) return rc;
+    PlaneSet P;
+    fill_planes(&P, src, dst);
+    // a chroma sample is written by one thread while another may still read the pixels of its block: no in-place operation
+    const int cw = (w + (1 << ocsx) - 1) >> ocsx, ch = (h + bh - 1) >> ocsy;
+    Span ss[3], ds[3];
+    for (int i = 0; i < 3; i++) {
+        ss[i] = plane_span(P.s[i], P.ss[i], P.sfs[i], h, (long long)w * 4, nframes);
+        ds[i] = plane_span(P.d[i], P.ds[i], P.dfs[i], i ? ch : h, (long long)(i ? cw : w) * (dout > 8 ? 2 : 1), nframes);
+    }
+    if (const int rc = check_disjoint("float RGB -> YUV", true, ss, 3, ds, 3)) return rc;
+    // source planes in R, G, B order (gbrp planes are G, B, R); the destination stays Y, Cb, Cr
+    const PlaneSet S = gbrp_to_rgb(P);
+    for (int k = 0; k < 3; k++) { P.s[k] = S.s[k]; P.ss[k] = S.ss[k]; P.sfs[k] = S.sfs[k]; }
+    HIP_TRY(hipSetDevice(c->device));
+    LutConsts L; FloatPre Q; FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = fill_lut_float(&L, &Q, c, interp != LUTR_INTERP_NONE)) return rc;
+    if (dither == LUTR_DITHER_NONE)
+        return finish_launch(c, launch_rgbf2yuv(c->stream, c->variant, L, Q, K, P, G, dout, ocsx, ocsy, interp));
+    const size_t ny = (size_t)w * h * nframes, nc = (size_t)cw * ch * nframes;
+    FloatPlanes F;
+    if (const int rc = dither_scratch(c, ny, nc, &F)) return rc;
+    return finish_launch(c, launch_rgbf2yuv_dither(c->stream, L, Q, K, P, G, F, dout, ocsx, ocsy, interp));
 }
 
 int lutr_resize_filter(int src, int dst, int cs, int cosited, int *start, int16_t *weights, int *ntaps)

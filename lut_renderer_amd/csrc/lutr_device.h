@@ -307,4 +307,39 @@ __device__ __forceinline__ void st_words(uint8_t *p, const uint32_t *w)
     }
 }
 
+// ---------------------------------------------------------------- output sinks of the by-block generic kernels
+// Where the generic kernels of the RGB-source paths (lutr_rgb2yuv.hip, lutr_rgbf.hip) put one output chroma block: luma() per
+// pixel inside the frame, chroma() once with the block's R, G, B sums.
+struct R2yPlaneSink {
+    const YuvConsts &K;
+    const PlaneSet &P;
+    int wout;
+    __device__ __forceinline__ void luma(long long fr, int x, int y, const Rgb &o)
+    {
+        st_sample(P.d[0] + fr * P.dfs[0] + (long long)y * P.ds[0], x, wout, rgb_to_y(K, o));
+    }
+    __device__ __forceinline__ void chroma(long long fr, int cx, int cy, float rs, float gs, float bs)
+    {
+        st_sample(P.d[1] + fr * P.dfs[1] + (long long)cy * P.ds[1], cx, wout, rgb_to_cb(K, rs, gs, bs));
+        st_sample(P.d[2] + fr * P.dfs[2] + (long long)cy * P.ds[2], cx, wout, rgb_to_cr(K, rs, gs, bs));
+    }
+};
+
+// the dither path's pass 1 (k_yuv_float's values, lutr_dither.hip): unquantised planes, densely packed per frame
+struct R2yFloatSink {
+    const YuvConsts &K;
+    const FloatPlanes &F;
+    const FrameGeom &G;
+    int cw, ch;
+    __device__ __forceinline__ void luma(long long fr, int x, int y, const Rgb &o)
+    {
+        F.y[(fr * G.h + y) * G.w + x] = fma_(K.cyr, o.r, fma_(K.cyg, o.g, fma_(K.cyb, o.b, K.yob))) - 0.5f;
+    }
+    __device__ __forceinline__ void chroma(long long fr, int cx, int cy, float rs, float gs, float bs)
+    {
+        F.cb[(fr * ch + cy) * cw + cx] = fma_(K.cbr, rs, fma_(K.cbg, gs, fma_(K.cbb, bs, K.cob))) - 0.5f;
+        F.cr[(fr * ch + cy) * cw + cx] = fma_(K.crr, rs, fma_(K.crg, gs, fma_(K.crb, bs, K.cob))) - 0.5f;
+    }
+};
+
 }  // namespace lutr

@@ -151,6 +151,31 @@ LUTR_R2Y_DECL(w00) LUTR_R2Y_DECL(w11) LUTR_R2Y_DECL(w10)
 const char *launch_rgb2yuv_dither(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const RgbLayout &Y,
                                   const FrameGeom &G, const FloatPlanes &F, int dout, int ocsx, int ocsy, int mode);
 
+// planar float RGB sources (lutr_rgbf.hip): gbrpf32 planes in PlaneSet::s in R, G, B order.  No per-code
+// coordinate table exists for a float input, so lut3d's prelut travels as the raw table lutr_ctx_set_prelut was given and is
+// applied per pixel (FFmpeg's prelut_interp_1d_linear); LutConsts::pre is not read by these kernels.
+struct FloatPre {
+    const float *tab;  // 3 x size floats (device), or nullptr: no prelut
+    int   size;
+    float min[3], scale[3];
+};
+// float in, float out (PlaneSet::d in R, G, B order too; may be the source).  nullptr as for launch_rgb2yuv
+const char *launch_rgbf(hipStream_t st, int variant, const LutConsts &L, const FloatPre &Q, const PlaneSet &P, const FrameGeom &G,
+                        int mode);
+// float in, Y / Cb / Cr out: the lattice's output quantised to 16-bit codes, then 3.9's output stage at lut_depth 16.  mode as for
+// launch_rgb2yuv (-1 = no lut3d)
+const char *launch_rgbf2yuv(hipStream_t st, int variant, const LutConsts &L, const FloatPre &Q, const YuvConsts &K, const PlaneSet &P,
+                            const FrameGeom &G, int dout, int ocsx, int ocsy, int mode);
+// its vector kernels, one translation unit per output container (w<out wide>)
+#define LUTR_RGBF_DECL(tag) \
+    const char *launch_rgbf2yuv_vec_##tag(hipStream_t st, const LutConsts &L, const FloatPre &Q, const YuvConsts &K, \
+                                          const PlaneSet &P, const FrameGeom &G, int ocsx, int ocsy, int mode);
+LUTR_RGBF_DECL(w0) LUTR_RGBF_DECL(w1)
+#undef LUTR_RGBF_DECL
+// the dither path: k_rgbf2yuv_float, then k_dither_ed; whole frames
+const char *launch_rgbf2yuv_dither(hipStream_t st, const LutConsts &L, const FloatPre &Q, const YuvConsts &K, const PlaneSet &P,
+                                   const FrameGeom &G, const FloatPlanes &F, int dout, int ocsx, int ocsy, int mode);
+
 // round-2 tile kernels (lutr_tile2.hip, one translation unit per format: w<in wide><out wide>_c<csx><csy>); nullptr =
 // this combination is not built / cannot take the call, the caller falls back
 #define LUTR_T2_DECL(tag) \

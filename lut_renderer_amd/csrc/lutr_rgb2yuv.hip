@@ -186,38 +186,7 @@ __device__ __forceinline__ void r2y_block(const LutConsts &L, const GFetch &f, c
     sink.chroma(fr, cx, cy, rs, gs, bs);
 }
 
-struct R2yPlaneSink {
-    const YuvConsts &K;
-    const PlaneSet &P;
-    int wout;
-    __device__ __forceinline__ void luma(long long fr, int x, int y, const Rgb &o)
-    {
-        st_sample(P.d[0] + fr * P.dfs[0] + (long long)y * P.ds[0], x, wout, rgb_to_y(K, o));
-    }
-    __device__ __forceinline__ void chroma(long long fr, int cx, int cy, float rs, float gs, float bs)
-    {
-        st_sample(P.d[1] + fr * P.dfs[1] + (long long)cy * P.ds[1], cx, wout, rgb_to_cb(K, rs, gs, bs));
-        st_sample(P.d[2] + fr * P.dfs[2] + (long long)cy * P.ds[2], cx, wout, rgb_to_cr(K, rs, gs, bs));
-    }
-};
-
-// the dither path's pass 1 (k_yuv_float's values, lutr_dither.hip): unquantised planes, densely packed per frame
-struct R2yFloatSink {
-    const YuvConsts &K;
-    const FloatPlanes &F;
-    const FrameGeom &G;
-    int cw, ch;
-    __device__ __forceinline__ void luma(long long fr, int x, int y, const Rgb &o)
-    {
-        F.y[(fr * G.h + y) * G.w + x] = fma_(K.cyr, o.r, fma_(K.cyg, o.g, fma_(K.cyb, o.b, K.yob))) - 0.5f;
-    }
-    __device__ __forceinline__ void chroma(long long fr, int cx, int cy, float rs, float gs, float bs)
-    {
-        F.cb[(fr * ch + cy) * cw + cx] = fma_(K.cbr, rs, fma_(K.cbg, gs, fma_(K.cbb, bs, K.cob))) - 0.5f;
-        F.cr[(fr * ch + cy) * cw + cx] = fma_(K.crr, rs, fma_(K.crg, gs, fma_(K.crb, bs, K.cob))) - 0.5f;
-    }
-};
-
+// (the sinks R2yPlaneSink / R2yFloatSink: lutr_device.h, shared with lutr_rgbf.hip)
 __global__ __launch_bounds__(256) void k_rgb2yuv_generic(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, RgbLayout Y, int wout,
                                                          int ocsx, int ocsy, int mode)
 {

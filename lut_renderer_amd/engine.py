@@ -70,19 +70,22 @@ def parse_pix_fmt(name: str) -> PixFmt:
 
 @dataclass(frozen=True)
 class RgbSource:
-    """An RGB source format of `LutEngine.apply_rgb_to_yuv`: planar `gbrp*` or a packed name of `_native.PACKED_FORMATS`."""
+    """An RGB source format of `LutEngine.apply_rgb_to_yuv`: planar `gbrp*`, a packed name of `_native.PACKED_FORMATS`, or a
+    planar float name of `_native.FLOAT_FORMATS`."""
     name: str
     packed: bool
-    depth: int        # the depth lut3d runs at: the source's (packed: 8 or 16)
+    depth: int        # the depth lut3d runs at: the source's (packed: 8 or 16); float: 16, the depth of the output stage's codes
     ncomp: int        # components per pixel of a packed image; 1 for planar
     code: int         # src_kind of lutr_apply_rgb_to_yuv: 0 planar, else LUTR_PACKED(...)
+    floating: bool = False   # 32-bit float planes: lutr_apply_planar_rgb_f32 / lutr_apply_rgbf_to_yuv
+    nplanes: int = 3         # planes per frame of a planar source (gbrapf32le: 4, the last one alpha)
 
     @property
     def itemsize(self) -> int:
-        return 1 if self.depth <= 8 else 2
+        return 4 if self.floating else 1 if self.depth <= 8 else 2
 
     def frame_bytes(self, w: int, h: int) -> int:
-        return h * w * (self.ncomp if self.packed else 3) * self.itemsize
+        return h * w * (self.ncomp if self.packed else self.nplanes) * self.itemsize
 
 
 def parse_rgb_source(name: Optional[str]) -> Optional[RgbSource]:
@@ -91,6 +94,8 @@ def parse_rgb_source(name: Optional[str]) -> Optional[RgbSource]:
     if name in _native.PACKED_FORMATS:
         bits, nc, ro, go, bo = _native.PACKED_FORMATS[name]
         return RgbSource(name, True, bits, nc, _native.packed_code(bits, nc, ro, go, bo))
+    if name in _native.FLOAT_FORMATS:
+        return RgbSource(name, False, 16, 1, 0, True, _native.FLOAT_FORMATS[name])
     try:
         fmt = parse_pix_fmt(name)
     except ValueError:
@@ -197,6 +202,22 @@ def _check_planes(planes: Sequence[torch.Tensor], fmt: PixFmt, w: int, h: int, w
         want = fmt.plane_shape(i, w, h)
         if tuple(t.shape[-2:]) != want:
             raise ValueError(f"{what} plane {i} is {tuple(t.shape[-2:])}, '{fmt.name}' at {w}x{h} needs {want}")
+
+
+def _check_float_planes(planes: Sequence[torch.Tensor], fmt: RgbSource, w: int, h: int, what: str) -> None:
+    """`_check_planes` for a float format: `fmt.nplanes` float32 planes of h x w (a three-plane list is taken for gbrapf32le too:
+    the alpha plane never reaches the kernels)."""
+    if isinstance(planes, torch.Tensor) or len(planes) not in (3, fmt.nplanes):
+        raise ValueError(f"'{fmt.name}' takes {fmt.nplanes} planes (G, B, R{', A' if fmt.nplanes == 4 else ''})")
+    for i, t in enumerate(planes):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("planes must be torch tensors resident on the engine's GPU")
+        if t.dim() not in (2, 3):
+            raise ValueError("planes must be [H,W] or [F,H,W]")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what} plane {i}: '{fmt.name}' takes float32 samples, got {t.dtype}")
+        if tuple(t.shape[-2:]) != (h, w):
+            raise ValueError(f"{what} plane {i} is {tuple(t.shape[-2:])}, '{fmt.name}' at {w}x{h} needs {(h, w)}")
 
 
 def _planes_struct(planes: Sequence[torch.Tensor], device: torch.device) -> Tuple[_native.Planes, int]:
@@ -445,6 +466,29 @@ class LutEngine:
                 self._ctx, depth, _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(d), row0, rows))
         return dst
 
+    def apply_rgb_float(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *,
+                        interp: str = "tetrahedral", row0: int = 0, rows: Optional[int] = None):
+        """lut3d on planar float RGB (gbrpf32le, DESIGN.md 3.10): float32 planes in gbrp order (G, B, R), each [H,W] or [F,H,W];
+        float in, float out, nothing clipped.  Input NaN -> 0 and +-inf -> +-FLT_MAX; a .csp prelut is applied per pixel; always
+        strict arithmetic.  `dst` may be `src` (in place).  A fourth plane (gbrapf32le's alpha) is copied through unchanged."""
+        fmt = parse_rgb_source("gbrapf32le" if len(src) == 4 else "gbrpf32le")
+        h, w = src[0].shape[-2], src[0].shape[-1]
+        if dst is None:
+            dst = [torch.empty_like(t) for t in src]
+        _check_float_planes(src, fmt, w, h, "source")
+        _check_float_planes(dst, fmt, w, h, "destination")
+        if len(dst) != len(src):
+            raise ValueError("src and dst disagree on the number of planes")
+        s, d, nf = _plane_pair(src[:3], dst[:3], self.device)
+        rows = h - row0 if rows is None else rows
+        with self._lock:
+            self._bind_stream()
+            _native.check(self._lib.lutr_apply_planar_rgb_f32(
+                self._ctx, _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(d), row0, rows))
+            if len(src) == 4 and dst[3].data_ptr() != src[3].data_ptr():      # (torch's current stream is the one just bound)
+                dst[3][..., row0:row0 + rows, :].copy_(src[3][..., row0:row0 + rows, :], non_blocking=True)
+        return dst
+
     # -- resize -----------------------------------------------------------
     def resize(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, size,
                chroma_loc: Optional[str] = None):
@@ -591,6 +635,13 @@ class LutEngine:
     # -- RGB source, YUV output --------------------------------
     def _rgb_source(self, src, fmt: RgbSource):
         """Validate an RGB source; returns (planar struct | None, packed struct | None, w, h, nframes, lead shape)."""
+        if fmt.floating:
+            if isinstance(src, torch.Tensor) or len(src) not in (3, fmt.nplanes):
+                raise ValueError(f"'{fmt.name}' takes {fmt.nplanes} planes (G, B, R{', A' if fmt.nplanes == 4 else ''})")
+            h, w = src[0].shape[-2], src[0].shape[-1]
+            _check_float_planes(src, fmt, w, h, "source")
+            st, nf = _planes_struct(src[:3], self.device)          # (an alpha plane is dropped for a YUV output)
+            return st, None, w, h, nf, tuple(src[0].shape[:-2])
         if not fmt.packed:
             if isinstance(src, torch.Tensor) or len(src) != 3:
                 raise ValueError(f"'{fmt.name}' takes three planes (G, B, R)")
@@ -610,7 +661,8 @@ class LutEngine:
         """lut3d on an RGB source, then RGB -> YUV into planar `out_pix_fmt` (4:2:0 / 4:2:2 / 4:4:4, any depth), in one pass
         (DESIGN.md 3.9).  `src` is three gbrp-ordered planes (G, B, R; `pix_fmt` = gbrp, gbrp9le .. gbrp16le) or one [F,]H,W,C
         packed tensor (`pix_fmt` a name of `_native.PACKED_FORMATS`; a fourth component is dropped).  The LUT runs at the source's
-        depth; always strict arithmetic.  lut=False leaves lut3d out.  dither / out_size as for `apply_yuv`.  Not in place.
+        depth; always strict arithmetic.  `pix_fmt` = gbrpf32le | gbrapf32le takes float32 planes (lut3d's float
+        path, its output quantised to 16-bit codes for the output stage; an alpha plane is dropped; no `out_size`).  lut=False leaves lut3d out.  dither / out_size as for `apply_yuv`.  Not in place.
         `intermediate_pix_fmt` / `prologue_out_range` (a LutPlan's fields for a source flagged full range) select the two-stage
         composition of `apply_rgb_full_range`, with `matrix_out` as the plan's matrix."""
         if dither not in _native.DITHER:
@@ -619,8 +671,10 @@ class LutEngine:
             raise ValueError("chroma siting (chroma_loc) is not defined for an RGB source: it has no chroma samples to site")
         fin = parse_rgb_source(pix_fmt)
         if fin is None:
-            raise ValueError(f"apply_rgb_to_yuv takes gbrp* or packed RGB sources, not '{pix_fmt}'")
+            raise ValueError(f"apply_rgb_to_yuv takes gbrp*, gbrpf32le or packed RGB sources, not '{pix_fmt}'")
         fout = parse_pix_fmt((out_pix_fmt or "").replace("yuvj", "yuv"))
+        if fin.floating and out_size is not None:
+            raise ValueError("a resize (out_size) is not supported with a float source")
         if fout.family != "yuv":
             raise ValueError("apply_rgb_to_yuv writes planar YUV formats; use apply_rgb / apply_packed for RGB output")
         if intermediate_pix_fmt is not None:
@@ -650,12 +704,16 @@ class LutEngine:
         rows = h - row0 if rows is None else rows
         if dither != "none" and (row0 != 0 or rows != h):
             raise ValueError("error-diffusion dither couples the rows of a frame: whole frames only")
-        _check_not_in_place([src] if fin.packed else src, dst, _RGB2YUV_IN_PLACE)
+        _check_not_in_place([src] if fin.packed else src[:3], dst, _RGB2YUV_IN_PLACE)
         p = _yuv_params(_native.fmt_code(fin.depth, 0, 0), fout.code, fin.depth, matrix_out, matrix_out, range_out, range_out,
                         range_out)
         mode = _native.INTERP[interp] if lut else _native.INTERP_NONE
         with self._lock:
             self._bind_stream()
+            if fin.floating:
+                _native.check(self._lib.lutr_apply_rgbf_to_yuv(
+                    self._ctx, C.byref(p), mode, _native.DITHER[dither], w, h, nf, C.byref(planar), C.byref(d), row0, rows))
+                return dst
             _native.check(self._lib.lutr_apply_rgb_to_yuv(
                 self._ctx, C.byref(p), mode, _native.DITHER[dither], fin.code, w, h, nf,
                 C.byref(planar) if planar is not None else None, C.byref(packed) if packed is not None else None, C.byref(d),
@@ -674,7 +732,7 @@ class LutEngine:
         `.prologue_out_range` and `.matrix`."""
         fin = parse_rgb_source(pix_fmt)
         if fin is None:
-            raise ValueError(f"apply_rgb_full_range takes gbrp* or packed RGB sources, not '{pix_fmt}'")
+            raise ValueError(f"apply_rgb_full_range takes gbrp*, gbrpf32le or packed RGB sources, not '{pix_fmt}'")
         mid = parse_pix_fmt(intermediate_pix_fmt)
         if mid.family != "yuv" or mid.depth != 8:
             raise ValueError(f"the full-range intermediate is an 8-bit planar YUV format, not '{intermediate_pix_fmt}'")

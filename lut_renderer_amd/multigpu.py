@@ -180,7 +180,8 @@ class LutEngineGroup:
 
     def apply_rgb_to_yuv(self, src, dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: str, **kw):
         """`LutEngine.apply_rgb_to_yuv` with the rows of every frame split over the group's devices: shards on
-        multiples of the output chroma block height, every source plane (or the packed image) counted in luma rows, no halo."""
+        multiples of the output chroma block height, every source plane (or the packed image) counted in luma rows, no halo.
+        Float sources (gbrpf32le / gbrapf32le) shard the same way."""
         with self._lock:
             if kw.get("dither", "none") != "none":
                 raise ValueError("error-diffusion dither couples the rows of a frame: it cannot be row-sharded")
@@ -190,7 +191,7 @@ class LutEngineGroup:
                 raise ValueError("a resize (out_size) needs a single device")
             fin = parse_rgb_source(pix_fmt)
             if fin is None:
-                raise ValueError(f"apply_rgb_to_yuv takes gbrp* or packed RGB sources, not '{pix_fmt}'")
+                raise ValueError(f"apply_rgb_to_yuv takes gbrp*, gbrpf32le or packed RGB sources, not '{pix_fmt}'")
             fout = parse_pix_fmt(out_pix_fmt.replace("yuvj", "yuv"))
             csy = fout.csy
             if kw.get("intermediate_pix_fmt"):                     # the full-range composition: its 8-bit frame has chroma rows too

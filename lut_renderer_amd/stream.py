@@ -78,11 +78,38 @@ class PackedFrameLayout:
         return buf.view(dt)[:n].view(nframes, self.height, self.width, self.fmt.ncomp)
 
 
+@dataclass
+class FloatFrameLayout:
+    """Byte layout of one planar float RGB frame (gbrpf32le / gbrapf32le) in a rawvideo stream: `fmt.nplanes` planes of h x w
+    32-bit floats, back to back (G, B, R[, A])."""
+    fmt: RgbSource
+    width: int
+    height: int
+
+    @property
+    def itemsize(self) -> int:
+        return 4
+
+    @property
+    def frame_bytes(self) -> int:
+        return self.fmt.nplanes * self.height * self.width * 4
+
+    def plane_views(self, buf: torch.Tensor, nframes: int) -> List[torch.Tensor]:
+        """[F,H,W] float32 views of the planes inside a flat uint8 buffer of `nframes` frames."""
+        h, w = self.height, self.width
+        typed = buf.view(torch.float32)
+        return [torch.as_strided(typed, (nframes, h, w), (self.fmt.nplanes * h * w, w, 1), i * h * w)
+                for i in range(self.fmt.nplanes)]
+
+
 def input_layout(pix_fmt: str, width: int, height: int):
-    """The layout of a rawvideo input: `PackedFrameLayout` for a packed RGB name, else `FrameLayout` (planar YUV or gbrp)."""
+    """The layout of a rawvideo input: `PackedFrameLayout` for a packed RGB name, `FloatFrameLayout` for a planar float one, else
+    `FrameLayout` (planar YUV or gbrp)."""
     rgb = parse_rgb_source(pix_fmt)
     if rgb is not None and rgb.packed:
         return PackedFrameLayout(rgb, width, height)
+    if rgb is not None and rgb.floating:
+        return FloatFrameLayout(rgb, width, height)
     return FrameLayout(parse_pix_fmt(pix_fmt.replace("yuvj", "yuv")), width, height)
 
 
@@ -94,11 +121,20 @@ class HostPipeline:
         """`out_size` = (w, h) or "WxH": the engine resizes every frame to it and the output layout has that size."""
         self.eng = engine
         self.fin = input_layout(pix_fmt, width, height)
-        self.rgb = parse_rgb_source(pix_fmt) is not None       # an RGB source: apply_rgb_to_yuv (DESIGN.md 3.9)
-        if self.rgb and not out_pix_fmt:
+        src_rgb = parse_rgb_source(pix_fmt)
+        self.rgb = src_rgb is not None                         # an RGB source: apply_rgb_to_yuv (DESIGN.md 3.9)
+        # a float source without an output format, or with a float one, stays float: apply_rgb_float (DESIGN.md 3.10)
+        out_rgb = parse_rgb_source(out_pix_fmt) if out_pix_fmt else src_rgb
+        self.float_out = self.rgb and src_rgb.floating and out_rgb is not None and out_rgb.floating
+        if self.rgb and not out_pix_fmt and not self.float_out:
             raise ValueError("an RGB source needs out_pix_fmt (a planar YUV format)")
         ow, oh = (width, height) if out_size is None else parse_size(out_size)
-        self.fout = FrameLayout(parse_pix_fmt(out_pix_fmt or pix_fmt.replace("yuvj", "yuv")), ow, oh)
+        if self.float_out:
+            if out_size is not None or out_rgb.nplanes > src_rgb.nplanes:
+                raise ValueError("a float output takes no out_size and cannot add an alpha plane")
+            self.fout = FloatFrameLayout(out_rgb, ow, oh)
+        else:
+            self.fout = FrameLayout(parse_pix_fmt(out_pix_fmt or pix_fmt.replace("yuvj", "yuv")), ow, oh)
         self.batch, self.slots = int(batch), int(slots)
         self.kw = dict(apply_kw, pix_fmt=self.fin.fmt.name, out_pix_fmt=self.fout.fmt.name)
         if out_size is not None:
@@ -127,7 +163,10 @@ class HostPipeline:
         with torch.cuda.stream(self.s_run):
             self.s_run.wait_event(self.e_in[slot])
             dst = self.fout.plane_views(self.d_out[slot], nframes)
-            if self.rgb:                                     # launches on the current (s_run) stream
+            if self.float_out:
+                src = self.fin.plane_views(self.d_in[slot], nframes)[:self.fout.fmt.nplanes]
+                self.eng.apply_rgb_float(src, dst, interp=self.kw.get("interp", "tetrahedral"))
+            elif self.rgb:                                   # launches on the current (s_run) stream
                 src = self.fin.image_view(self.d_in[slot], nframes) if isinstance(self.fin, PackedFrameLayout) \
                     else self.fin.plane_views(self.d_in[slot], nframes)
                 self.eng.apply_rgb_to_yuv(src, dst, **self.kw)
