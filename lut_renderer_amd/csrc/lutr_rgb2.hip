@@ -31,6 +31,7 @@
 
 #include "lutr_internal.h"
 #include "lutr_launch.h"
+#include "lutr_tube.h"
 
 #ifndef LUTR_R2_LAYOUT
 #define LUTR_R2_LAYOUT 0
@@ -38,25 +39,13 @@
 #ifndef LUTR_R2_WPB
 #define LUTR_R2_WPB 16
 #endif
-#ifndef LUTR_R2_INPLACE
-#define LUTR_R2_INPLACE 0         // 1: results overwrite the unit's input words and the rare gather path re-reads its unit (12 words
-                                  // back, 4-pixel coordinate groups everywhere).  Parity green, but measured 2-9 % SLOWER than separate
-                                  // output words (gbrp 605 vs 637, gbrp16le 383 vs 422 Gpx/s relative to the same reference kernel):
-                                  // every write becomes a read-modify-write of a word whose other samples are still live input
-#endif
-#ifndef LUTR_R2_TB0
-#define LUTR_R2_TB0 1             // tap batch of the computed-coordinate instances: 1 pixel (no spill) or 2
-#endif
-#ifndef LUTR_R2_NT
-#define LUTR_R2_NT 1              // 1: non-temporal stores, 2: and loads
-#endif
 
 namespace lutr {
 namespace r2 {
 
 extern __shared__ __attribute__((aligned(16))) char smem[];
 
-#define DEV __device__ __forceinline__
+using namespace tube;      // machine helpers, Crd, the chunk queue, the padded LDS layouts
 
 enum { LY_P8 = 0, LY_P16 = 1, LY_C3B = 2, LY_C3W = 3, LY_C4B0 = 4, LY_C4B1 = 5, LY_C4W0 = 6, LY_C4W1 = 7 };
 
@@ -73,15 +62,7 @@ template <> struct Lay<LY_C4B1> { static constexpr int PX = 8,  NPL = 1, NW = 8,
 template <> struct Lay<LY_C4W0> { static constexpr int PX = 4,  NPL = 1, NW = 8,  WIDE = 1, NC = 4, P0 = 0; };
 template <> struct Lay<LY_C4W1> { static constexpr int PX = 4,  NPL = 1, NW = 8,  WIDE = 1, NC = 4, P0 = 1; };
 
-DEV float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-DEV float med3(float a, float lo, float hi) { return __builtin_amdgcn_fmed3f(a, lo, hi); }
-DEV int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-DEV float vmin3(float a, float b, float c) { float o; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(o) : "v"(a), "v"(b), "v"(c)); return o; }
-DEV float vmax3(float a, float b, float c) { float o; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(o) : "v"(a), "v"(b), "v"(c)); return o; }
 DEV int lds_base() { return (int)(unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)smem; }
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2v __attribute__((ext_vector_type(2)));
 
 struct Geom {
     int lw_log2;          // lanes across x per tile row (the other lanes go down)
@@ -123,24 +104,20 @@ template <int WIDE> DEV unsigned code8(const uint32_t *w, int e, unsigned three)
     }
     return d;
 }
-// the code itself as a float
-template <int WIDE> DEV float codef(const uint32_t *w, int e)
-{
-    if constexpr (WIDE) return (float)((w[e >> 1] >> ((e & 1) * 16)) & 0xffffu);
-    else return (float)((w[e >> 2] >> ((e & 3) * 8)) & 0xffu);
-}
-// floor(v) (v >= 0) into sample e, the other samples of the word preserved; FIRST: the word's other samples are not live yet
-template <int WIDE, bool KEEP> DEV void put(uint32_t *w, int e, float v)
+// floor(v) for v >= 0 (negatives saturate to 0) into sample i, the word's other samples preserved: one SDWA conversion
+// (v_cvt_u32_f32 truncates) instead of convert + shift-or.  KEEP = false: sample 0 of a word is written first, while the word's
+// other samples are not live yet, so it takes the whole word.
+template <int WIDE, bool KEEP> DEV void put(uint32_t *w, int i, float v)
 {
     if constexpr (WIDE) {
-        uint32_t &d = w[e >> 1];
-        if ((e & 1) == 0) {
+        uint32_t &d = w[i >> 1];
+        if ((i & 1) == 0) {
             if constexpr (KEEP) asm("v_cvt_u32_f32_sdwa %0, %1 dst_sel:WORD_0 dst_unused:UNUSED_PRESERVE src0_sel:DWORD" : "+v"(d) : "v"(v));
             else d = (uint32_t)v;
         } else asm("v_cvt_u32_f32_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD" : "+v"(d) : "v"(v));
     } else {
-        uint32_t &d = w[e >> 2];
-        switch (e & 3) {
+        uint32_t &d = w[i >> 2];
+        switch (i & 3) {
         case 0:
             if constexpr (KEEP) asm("v_cvt_u32_f32_sdwa %0, %1 dst_sel:BYTE_0 dst_unused:UNUSED_PRESERVE src0_sel:DWORD" : "+v"(d) : "v"(v));
             else d = (uint32_t)v;
@@ -164,47 +141,23 @@ template <int LY> DEV int samp(int i, int k)
 }
 template <int LY> DEV int plane_of(int k) { return Lay<LY>::NC == 1 ? k : 0; }
 
+// plain loads, non-temporal stores (stw, lutr_tube.h); non-temporal loads too were measured behind a build switch and lost
 template <int NW> DEV void ldw(uint32_t *w, const uint8_t *p)
 {
     typedef unsigned nt4 __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int j = 0; j < NW / 4; j++) {
-#if LUTR_R2_NT >= 2
-        const nt4 v = __builtin_nontemporal_load((const nt4 *)(p + 16 * j));
-#else
         const nt4 v = *(const nt4 *)(p + 16 * j);
-#endif
         w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w;
-    }
-}
-template <int NW> DEV void stw(uint8_t *p, const uint32_t *w)
-{
-    typedef unsigned nt4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-    for (int j = 0; j < NW / 4; j++) {
-#if LUTR_R2_NT >= 1
-        __builtin_nontemporal_store(nt4{w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]}, (nt4 *)(p + 16 * j));
-#else
-        *(nt4 *)(p + 16 * j) = nt4{w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]};
-#endif
     }
 }
 
 // ---------------------------------------------------------------- coordinates
-struct Crd { float p, d; };
-
 template <int INTERP>
 DEV Crd crd_compute(const LutConsts &L, float code)
 {
     const float x = code * L.scale_f;
-    const float s = fminf(x * L.sc[0], L.lut_max);       // codes and scales are >= 0: only the upper clip can bind
-    Crd c;
-    if constexpr (INTERP == LUTR_INTERP_NEAREST) {        // NEAR(x) = (int)(x + .5) with a double .5 (lutr_device.h near_f)
-        const float fl = floorf(s);
-        c.p = (s - fl >= .5f) ? fl + 1.0f : fl;
-        c.d = 0.0f;
-    } else { c.p = floorf(s); c.d = s - c.p; }
-    return c;
+    return crd_split<INTERP>(fminf(x * L.sc[0], L.lut_max));       // codes and scales are >= 0: only the upper clip can bind
 }
 
 // coordinates of channel `ch` in the general case: a prelut (lut3d's 1D shaper, folded by the host into one lattice coordinate per
@@ -215,20 +168,7 @@ DEV Crd crd_general(const LutConsts &L, int ch, float code)
     float s;
     if (L.pre) s = L.pre[ch * L.pre_stride + min((int)code, L.pre_stride - 1)];
     else s = fminf((code * L.scale_f) * L.sc[ch], L.lut_max);
-    Crd c;
-    if constexpr (INTERP == LUTR_INTERP_NEAREST) {
-        const float fl = floorf(s);
-        c.p = (s - fl >= .5f) ? fl + 1.0f : fl;
-        c.d = 0.0f;
-    } else { c.p = floorf(s); c.d = s - c.p; }
-    return c;
-}
-
-typedef __attribute__((address_space(3))) const f2v *lds_f2p;
-DEV Crd crd_table8(unsigned off)
-{
-    const f2v e = *(lds_f2p)(uintptr_t)off;
-    return Crd{e.x, e.y};
+    return crd_split<INTERP>(s);
 }
 
 // lattice addressing of one body: byte strides of the three slots and of a node, base
@@ -237,19 +177,15 @@ struct Addr {
     int o0, o1, o2;               // byte steps of +1 along the slots
 };
 
-#ifndef LUTR_R2_TRI12
-#define LUTR_R2_TRI12 0           // 1: trilinear stages 12-byte nodes too (wider tube, 16 LDS reads per pixel instead of 8)
-#endif
-#ifndef LUTR_R2_NODE16
-#define LUTR_R2_NODE16 0          // 1: the 4-tap modes stage float4 nodes too (one ds_read_b128 per tap, 4 LDS cycles instead of 6; tube H = 7
-                                  // instead of 8 at 33^3): rgb24 608 vs 618, gbrp 646 vs 649, sigma-16 frames -5 % (profiles/r03_exp25): the
-                                  // LDS is not what these kernels wait for
-#endif
+// Node sizes: 12-byte {r, g, b} for the 4-tap modes, float4 for trilinear.  (Measured behind build switches and removed: trilinear on
+// 12-byte nodes -- wider tube, 16 LDS reads per pixel instead of 8: profiles/r03_exp24_rgb_trilinear_12byte_nodes.txt; float4 nodes for
+// the 4-tap modes -- one ds_read_b128 per tap, tube H = 7 instead of 8 at 33^3: rgb24 608 vs 618, gbrp 646 vs 649, sigma-16 frames
+// -5 %, profiles/r03_exp25_rgb_tube_16byte_nodes.txt: the LDS is not what these kernels wait for.)
 // INTERP as a template argument: lut3d's 0 / 1 / 2, and R2_TET16 = tetrahedral on float4 nodes, for the whole-lattice mode (one ds_read_b128
 // per tap, far fewer bank collisions between scattered taps; lutr_tile2.hip T2_TET16)
 constexpr int R2_TET16 = 3;
 template <int INTERP> struct NodeB {
-    static constexpr int lds = ((INTERP == LUTR_INTERP_TRILINEAR && !LUTR_R2_TRI12) || INTERP == R2_TET16 || (INTERP != LUTR_INTERP_TRILINEAR && LUTR_R2_NODE16)) ? 16 : 12;
+    static constexpr int lds = (INTERP == LUTR_INTERP_TRILINEAR || INTERP == R2_TET16) ? 16 : 12;
 };
 
 template <bool LDS, int NB> DEV f4 tap(const LutConsts &L, int a)
@@ -261,8 +197,6 @@ template <bool LDS, int NB> DEV f4 tap(const LutConsts &L, int a)
         return v;
     } else return *(const f4 *)((const char *)L.lat + a);
 }
-
-DEV float tlerp(float v0, float v1, float f) { return v0 + (v1 - v0) * f; }
 
 struct Rgb3 { float c0, c1, c2; };
 
@@ -358,8 +292,9 @@ DEV Rgb3 px_blend(const LutConsts &L, const Prep &c, const Taps<INTERP> &T, bool
 // is symmetric.  They come out of the table's `prev` values, whatever the taps read.
 struct Acc { float amin, amax, bmin, bmax; };
 
-// `out` may be `in` itself (LUTR_R2_INPLACE): a pixel's three samples are read before they are written, every write preserves the
-// other samples of its word, and groups run in program order.
+// (Measured behind a build switch and removed: results overwriting the unit's input words, the rare gather path re-reading its unit --
+// 12 words back, 4-pixel coordinate groups everywhere, and 2-9 % SLOWER: gbrp 605 vs 637, gbrp16le 383 vs 422 Gpx/s; every write becomes
+// a read-modify-write of a word whose other samples are still live input.  profiles/r03_exp43_rgb_four_pixel_groups.txt)
 template <bool LDS, int LY, int INTERP, int TAB, bool UNIT>
 DEV Acc tile_body(const LutConsts &L, const Addr &A, const Geom &TG, Unit<LY> &in, Unit<LY> &out)
 {
@@ -371,10 +306,10 @@ DEV Acc tile_body(const LutConsts &L, const Addr &A, const Geom &TG, Unit<LY> &i
     const bool swap = TG.rev != 0;
     // pixels whose coordinate reads are issued together: 4 where the registers allow (units of 8 words), else 2 -- a unit of 12
     // words in, 12 prefetched and 12 out leaves the tetrahedral body no room for 24 coordinates (one spilled register = scratch)
-    constexpr int GP = ((!LUTR_R2_INPLACE && Y::NPL * Y::NW >= 12) || (INTERP == LUTR_INTERP_TRILINEAR && Y::NW >= 12) || Y::PX < 4) ? 2 : 4;
+    constexpr int GP = (Y::NPL * Y::NW >= 12 || (INTERP == LUTR_INTERP_TRILINEAR && Y::NW >= 12) || Y::PX < 4) ? 2 : 4;
     // pixels whose taps are in flight together (the instances that compute their coordinates -- 14- and 16-bit data -- spilled 3-6 registers
-    // to scratch with two)
-    constexpr int TB = INTERP == LUTR_INTERP_TRILINEAR ? 1 : (INTERP == LUTR_INTERP_NEAREST ? GP : ((TAB == 0 && LUTR_R2_TB0 == 1 && Y::NPL * Y::NW >= 12) ? 1 : 2));
+    // to scratch with two: profiles/r03_exp42_rgb16_tap_batch.txt)
+    constexpr int TB = INTERP == LUTR_INTERP_TRILINEAR ? 1 : (INTERP == LUTR_INTERP_NEAREST ? GP : ((TAB == 0 && Y::NPL * Y::NW >= 12) ? 1 : 2));
 #pragma unroll
     for (int g = 0; g < Y::PX / GP; g++) {
         Crd q[GP][3];
@@ -390,8 +325,8 @@ DEV Acc tile_body(const LutConsts &L, const Addr &A, const Geom &TG, Unit<LY> &i
                     // slot k's channel: planar frames arrive as (R, G, B), packed ones in memory order
                     const unsigned tb = (unsigned)(swap ? 2 - k : k) * (unsigned)TG.tab_entries * 8u;
                     q[t][k] = crd_table8(code8<Y::WIDE>(in.w[plane_of<LY>(k)], e, three) + tb);
-                } else if constexpr (TAB == 3) q[t][k] = crd_general<INTERP>(L, swap ? 2 - k : k, codef<Y::WIDE>(in.w[plane_of<LY>(k)], e));
-                else q[t][k] = crd_compute<INTERP>(L, codef<Y::WIDE>(in.w[plane_of<LY>(k)], e));
+                } else if constexpr (TAB == 3) q[t][k] = crd_general<INTERP>(L, swap ? 2 - k : k, wsample<Y::WIDE>(in.w[plane_of<LY>(k)], e));
+                else q[t][k] = crd_compute<INTERP>(L, wsample<Y::WIDE>(in.w[plane_of<LY>(k)], e));
             }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (LDS) {
@@ -417,7 +352,7 @@ DEV Acc tile_body(const LutConsts &L, const Addr &A, const Geom &TG, Unit<LY> &i
             for (int t = 0; t < TB; t++) {
                 const int i = g * GP + tb + t;
                 const Rgb3 o = px_blend<LDS, INTERP, UNIT>(L, pc[t], tp[t], swap);
-                constexpr bool keep = Y::NC == 4 || LUTR_R2_INPLACE;   // the word holds alpha, or input samples still to be read
+                constexpr bool keep = Y::NC == 4;      // the word holds alpha
                 put<Y::WIDE, keep>(out.w[plane_of<LY>(0)], samp<LY>(i, 0), o.c0);
                 put<Y::WIDE, keep>(out.w[plane_of<LY>(1)], samp<LY>(i, 1), o.c1);
                 put<Y::WIDE, keep>(out.w[plane_of<LY>(2)], samp<LY>(i, 2), o.c2);
@@ -436,70 +371,6 @@ DEV Acc tile_body(const LutConsts &L, const Addr &A, const Geom &TG, Unit<LY> &i
         }
     }
     return acc;
-}
-
-// ---------------------------------------------------------------- work distribution (as lutr_tile2.hip)
-DEV bool chunk_at(const Geom &TG, unsigned c, int &fr, int &sx, int &ry, int &rem)
-{
-    if (c >= (unsigned)TG.nchunks) return false;
-    const int per_frame = TG.nrc * TG.nsx;
-    fr = (int)c / per_frame;
-    const int r = (int)c - fr * per_frame;
-    const int rc = r / TG.nsx;
-    sx = r - rc * TG.nsx;
-    ry = rc * TG.ch;
-    rem = min(TG.ch, TG.nry - ry);
-    return true;
-}
-// The two-level chunk queue of lutr_tile2.hip (claim_chunk there): a wave's first chunk is its id; after that it draws a ticket
-// from the workgroup's LDS counter, ticket 16 j + slot is chunk base[j] + slot, and the wave that draws slot 0 fetches
-// base[j] = atomicAdd(queue, 16) and publishes it.  LDS words at `wgq_off`: ticket at +0, base[8] at +32, ready[8] at +64.
-typedef __attribute__((address_space(3))) volatile unsigned *lds_vup;
-constexpr int kWgq = 128;
-DEV bool claim_chunk(const Geom &TG, int lane, int wgq_off, int &fr, int &sx, int &ry, int &rem, bool &first)
-{
-    unsigned c = 0;
-    if (first) {          // (a wave whose id is not a chunk has no work: the counter starts behind the ids; runs before the LDS words are initialised)
-        first = false;
-        c = (unsigned)((int)(blockIdx.x * LUTR_R2_WPB) + uni((int)(threadIdx.x >> 6)));
-        return chunk_at(TG, c, fr, sx, ry, rem);
-    }
-    const lds_vup q = (lds_vup)(uintptr_t)(unsigned)(lds_base() + wgq_off);
-    unsigned t = 0;
-    if (lane == 0) t = __hip_atomic_fetch_add((__attribute__((address_space(3))) unsigned *)q, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    t = (unsigned)uni((int)t);
-    const unsigned j = t >> 4, slot = t & 15u, r = j & 7u;
-    if (slot == 0) {
-        if (lane == 0) {
-            c = atomicAdd(TG.queue, 16u) + TG.qbase;
-            q[8 + r] = c;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            q[16 + r] = j + 1u;
-        }
-        c = (unsigned)uni((int)c);
-    } else {
-        while ((unsigned)uni((int)q[16 + r]) != j + 1u) __builtin_amdgcn_s_sleep(2);
-        c = (unsigned)uni((int)q[8 + r]) + slot;
-    }
-    return chunk_at(TG, c, fr, sx, ry, rem);
-}
-
-// a wave that will claim no more; the last one zeroes the two words for the next launch (no memset node per launch)
-DEV void queue_leave(const Geom &TG, int lane, int wgq_off)
-{
-    // two levels, like the claims: the waves of a workgroup count themselves out in LDS (word 24 of the allocator's block), the last one
-    // reports the workgroup -- 4096 atomics on one address at the end of a short launch cost it 15 us
-    if (lane == 0) {
-        const lds_vup q = (lds_vup)(uintptr_t)(unsigned)(lds_base() + wgq_off);
-        const unsigned left = __hip_atomic_fetch_add((__attribute__((address_space(3))) unsigned *)(q + 24), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (left == (unsigned)LUTR_R2_WPB - 1u) {
-            const unsigned done = atomicAdd(TG.queue + 1, 1u);
-            if (done == gridDim.x - 1u) {
-                __hip_atomic_store(TG.queue, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(TG.queue + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
 }
 
 template <int LY, int INTERP, int TAB, bool UNIT>
@@ -522,9 +393,9 @@ void k_rgb_tube(LutConsts L, Planes P, FrameGeom G, Geom TG)
             *(float2 *)(smem + q * 8) = make_float2(c.p, c.d);
         }
     }
-    const int wgq_off = (TAB == 3 ? 3 : 1) * TG.tab_entries * 8;                // the workgroup's chunk allocator (claim_chunk)
-    if (threadIdx.x < 24) ((unsigned *)(smem + wgq_off))[threadIdx.x + (threadIdx.x ? 7 : 0)] = 0u;
-    const int lat_off = wgq_off + kWgq;
+    const int wgq_off = (TAB == 3 ? 3 : 1) * TG.tab_entries * 8;                // the workgroup's chunk allocator (lutr_tube.h)
+    if (threadIdx.x < 24) ((unsigned *)(smem + wgq_off))[threadIdx.x + (threadIdx.x ? 7 : 0)] = 0u;      // queue words 0, 8..30 (lutr_tube.h)
+    const int lat_off = wgq_off + kQueueLds;
     const int nb = 2 * TG.tube_h + 3;
     {
         char *dst = smem + lat_off;
@@ -566,7 +437,7 @@ void k_rgb_tube(LutConsts L, Planes P, FrameGeom G, Geom TG)
     }
     int fr, sx, ry, rem;
     bool first = true;
-    if (!claim_chunk(TG, lane, wgq_off, fr, sx, ry, rem, first)) { queue_leave(TG, lane, wgq_off); return; }
+    if (!claim_chunk<LUTR_R2_WPB>(TG, lane, lds_base(), wgq_off, fr, sx, ry, rem, first)) { queue_leave<LUTR_R2_WPB>(TG, lane, lds_base(), wgq_off); return; }
     const int lw = 1 << TG.lw_log2, lh_log2 = 6 - TG.lw_log2;
     const int lx = lane & (lw - 1), ly = lane >> TG.lw_log2;
     constexpr int UB = Y::NW * 4;                       // bytes of a unit per plane
@@ -604,7 +475,7 @@ void k_rgb_tube(LutConsts L, Planes P, FrameGeom G, Geom TG)
         const TilePos cp = np;
         if (--rem > 0) { ry++; pos_down(np); }
         else {
-            more = claim_chunk(TG, lane, wgq_off, fr, sx, ry, rem, first);
+            more = claim_chunk<LUTR_R2_WPB>(TG, lane, lds_base(), wgq_off, fr, sx, ry, rem, first);
             if (more) np = pos_at(fr, sx, ry);
         }
         load_tile(nxt, np);
@@ -621,12 +492,8 @@ void k_rgb_tube(LutConsts L, Planes P, FrameGeom G, Geom TG)
             lane_ok = (acc & (hi | (hi << 16))) == 0u;
         }
         st_tiles++;
-#if LUTR_R2_INPLACE
-        Unit<LY> &out = in;
-#else
         Unit<LY> out;
         if constexpr (Y::NC == 4) out = in;
-#endif
         {
             // optimistic pass for every lane (a lane with illegal codes or colours outside the tube reads wherever its numbers
             // point -- LDS reads cannot fault -- and its result is thrown away)
@@ -641,17 +508,7 @@ void k_rgb_tube(LutConsts L, Planes P, FrameGeom G, Geom TG)
         else {
             st_gather++;
             if (!lane_ok) {
-#if LUTR_R2_INPLACE
-                // the optimistic pass has overwritten the unit: read it again (its own bytes: nothing has been stored over them yet,
-                // also when the caller works in place)
-                {
-                    const unsigned lxc = (unsigned)min(lx, cp.xlim), lyc = (unsigned)min(ly, cp.ylim);
-#pragma unroll
-                    for (int p = 0; p < Y::NPL; p++) ldw<Y::NW>(in.w[p], cp.s[p] + (__umul24(lyc, P.ss[p]) + lxc * UB));
-                }
-#else
                 if constexpr (Y::NC == 4) out = in;
-#endif
                 (void)tile_body<false, LY, INTERP, TAB, UNIT>(L, AG, TG, in, out);
             }
         }
@@ -661,7 +518,7 @@ void k_rgb_tube(LutConsts L, Planes P, FrameGeom G, Geom TG)
             for (int p = 0; p < Y::NPL; p++) stw<Y::NW>(cp.d[p] + (__umul24(lyc, P.ds[p]) + lxc * UB), out.w[p]);
         }
     }
-    queue_leave(TG, lane, wgq_off);
+    queue_leave<LUTR_R2_WPB>(TG, lane, lds_base(), wgq_off);
     if (TG.stats && lane == 0) {
         atomicAdd(&TG.stats[0], st_tiles); atomicAdd(&TG.stats[2], st_gather); atomicAdd(&TG.stats[12], st_tube);
     }
@@ -670,54 +527,9 @@ void k_rgb_tube(LutConsts L, Planes P, FrameGeom G, Geom TG)
 }  // namespace r2
 
 // ================================================================= launcher
-namespace {
-
-// see tube_plane_stride in lutr_tile2.hip: node index = pr * A + pg * B + pb, no collision mod 32 (mod 16 for the 16-byte nodes of
-// trilinear, read with ds_read_b128) for steps of +-1 (+-2 if possible)
-int tube_plane_stride(int nb, int node)
-{
-    const int mod = node == 16 ? 16 : 32;
-    int best = nb * nb, best_bad = 1 << 30;
-    for (int pad = 0; pad < 12; pad++) {
-        const int plane = nb * nb + pad, A = plane - nb, B = nb - 1;
-        int bad = 0;
-        for (int dr = -2; dr <= 2; dr++)
-            for (int dg = -2; dg <= 2; dg++)
-                for (int db = -2; db <= 2; db++) {
-                    if (!dr && !dg && !db) continue;
-                    if (((dr * A + dg * B + db) % mod + mod) % mod == 0) bad += (abs(dr) <= 1 && abs(dg) <= 1 && abs(db) <= 1) ? 100 : 1;
-                }
-        if (bad < best_bad) { best_bad = bad; best = plane; }
-        if (!bad) break;
-    }
-    return best;
-}
-// whole-lattice mode: row and plane strides of the (n+1)^3 copy, padded the same way (lutr_tile2.hip whole_strides); bytes, or 0 if none fits
-long long whole_strides(int n1, int node, long long room, int *A, int *B)
-{
-    const int mod = node == 16 ? 16 : 32;
-    long long best_bytes = 0;
-    int best_bad = 1 << 30;
-    for (int pb = 0; pb < 4; pb++)
-        for (int pa = 0; pa < 16; pa++) {
-            const int b = n1 + pb, a = n1 * b + pa;
-            const long long bytes = (long long)n1 * a * node;
-            if (bytes > room) continue;
-            int bad = 0;
-            for (int dr = -2; dr <= 2; dr++)
-                for (int dg = -2; dg <= 2; dg++)
-                    for (int db = -2; db <= 2; db++) {
-                        if (!dr && !dg && !db) continue;
-                        if (((dr * a + dg * b + db) % mod + mod) % mod == 0) bad += (abs(dr) <= 1 && abs(dg) <= 1 && abs(db) <= 1) ? 100 : 1;
-                    }
-            if (bad < best_bad || (bad == best_bad && bytes < best_bytes)) { best_bad = bad; best_bytes = bytes; *A = a; *B = b; }
-        }
-    return best_bytes;
-}
+// (tube_plane_stride, whole_strides: lutr_tube.h)
 // (17-node rows of 16-byte nodes collide on every g step whatever the plane stride; skipping H = 7 for H = 6 there measured WORSE --
 // gbrp trilinear 410 -> 379, rgb24 407 -> 369 Gpx/s: the wider tube is worth more than the conflicts cost)
-
-}  // namespace
 
 #define R2_CAT_(a) launch_rgb_tube_ly##a
 #define R2_CAT(a) R2_CAT_(a)
@@ -773,8 +585,8 @@ const char *R2_ENTRY(hipStream_t st, const LutConsts &L, const PlaneSet &P, cons
     tg.max_code = (1 << depth) - 1;
     tg.rev = rev;
     tg.three = three ? 1 : 0;
-    int node = ((mode == LUTR_INTERP_TRILINEAR && !LUTR_R2_TRI12) || (mode != LUTR_INTERP_TRILINEAR && LUTR_R2_NODE16)) ? 16 : 12;
-    const long long room = 163840 - (long long)(three ? 3 : 1) * tg.tab_entries * 8 - r2::kWgq;
+    int node = mode == LUTR_INTERP_TRILINEAR ? 16 : 12;      // NodeB::lds
+    const long long room = 163840 - (long long)(three ? 3 : 1) * tg.tab_entries * 8 - kQueueLds;
     // whole-lattice mode, strides padded; tetrahedral on float4 nodes when those fit too (R2_TET16)
     long long whole_bytes = 0;
     bool whole16 = false;
@@ -806,7 +618,7 @@ const char *R2_ENTRY(hipStream_t st, const LutConsts &L, const PlaneSet &P, cons
     tg.queue = queue; tg.stats = stats;
     const int waves = tg.nchunks < max_waves ? tg.nchunks : max_waves;
     const dim3 grid((waves + LUTR_R2_WPB - 1) / LUTR_R2_WPB), block(64 * LUTR_R2_WPB);
-    const size_t lds = (size_t)(three ? 3 : 1) * tg.tab_entries * 8 + kWgq + (size_t)lat_bytes;
+    const size_t lds = (size_t)(three ? 3 : 1) * tg.tab_entries * 8 + kQueueLds + (size_t)lat_bytes;
     Planes TP;
     for (int i = 0; i < 3; i++) {
         const int p = i < Y::NPL ? i : 0;

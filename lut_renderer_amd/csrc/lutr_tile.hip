@@ -41,10 +41,7 @@
 
 #include "lutr_internal.h"
 #include "lutr_launch.h"
-#ifndef LUTR_NT
-#define LUTR_NT 1        // non-temporal stores: every output byte is written once (+0.3 % here; non-temporal LOADS cost 2.5 % on gbrp10le)
-#endif
-
+#include "lutr_tube.h"
 
 // Waves per workgroup.  The waves of a block share one coordinate table, so bigger blocks leave more of the
 // CU's 160 KB to the windows (4 waves -> 512 nodes per wave at 10 bit, 8 -> 576, 16 -> 608; 8 measured best).
@@ -56,24 +53,10 @@ namespace lutr {
 
 extern __shared__ __attribute__((aligned(16))) char lutr_smem[];
 
-// ---------------------------------------------------------------- small math
-__device__ __forceinline__ float tmed3(float a, float lo, float hi) { return __builtin_amdgcn_fmed3f(a, lo, hi); }
-__device__ __forceinline__ float tfma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ float unif(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-
-__device__ __forceinline__ float wave_min(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-    return v;
-}
+// small math, Crd / crd_split, wsample, the non-temporal stw and chunk_at: lutr_tube.h
+using tube::med3; using tube::fma_; using tube::uni; using tube::unif; using tube::wave_min; using tube::wave_max;
+using tube::vmin3; using tube::vmax3; using tube::tlerp; using tube::f4; using tube::Crd; using tube::crd_split;
+using tube::wsample; using tube::stw; using tube::chunk_at;
 
 // A wave-uniform constant used by many full-rate VOP2 ops per pixel is worth a VGPR: an SGPR source
 // operand drops v_mul/v_add/v_fmac to the 0.62x issue class on gfx950 (tools/ubench/op_rates.hip).
@@ -130,10 +113,9 @@ __device__ __forceinline__ void bnd_reset(Bnd &b)
     b.rmax = b.gmax = b.bmax = -1e9f;
 }
 
-// A node is read as one 16-byte access.  Loading through the 4-wide ext_vector type keeps it a
+// A node is read as one 16-byte access.  Loading through the 4-wide ext_vector type f4 keeps it a
 // ds_read_b128 / global_load_dwordx4 even though .w is padding (a float4 struct load gets narrowed
 // to b96, which the LDS serves at 8 cycles per wave-instruction instead of 4; MI355X_MICROARCH.md).
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // bounds of the touched cells in sheared coordinates (r, g-r, b-r)
 __device__ __forceinline__ void bnd_update(Bnd &bn, float pr, float pg, float pb)
@@ -145,22 +127,8 @@ __device__ __forceinline__ void bnd_update(Bnd &bn, float pr, float pg, float pb
 }
 
 // Sheared cell coordinates of one pixel, and the bounds update for a PAIR of pixels: v_min3 / v_max3
-// fold two pixels per instruction (3 slow-class VALU per pixel instead of 6).  Written as asm because
-// hipcc only forms min3/max3 from some of the equivalent fminf/fmaxf chains.
+// fold two pixels per instruction (3 slow-class VALU per pixel instead of 6).
 struct Cell { float r, hg, hb; };
-
-__device__ __forceinline__ float vmin3(float a, float b, float c)
-{
-    float o;
-    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(o) : "v"(a), "v"(b), "v"(c));
-    return o;
-}
-__device__ __forceinline__ float vmax3(float a, float b, float c)
-{
-    float o;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(o) : "v"(a), "v"(b), "v"(c));
-    return o;
-}
 
 __device__ __forceinline__ void bnd_update2(Bnd &bn, const Cell &a, const Cell &b)
 {
@@ -195,8 +163,6 @@ __device__ __forceinline__ f4 tap(const float4 *__restrict__ lat, int a)
 
 struct Rgb3 { float r, g, b; };
 
-__device__ __forceinline__ float tlerp(float v0, float v1, float f) { return v0 + (v1 - v0) * f; }
-
 // One pixel of SURVEY A.3-A.5 against window W, in three stages so that a tile body can run each
 // stage for several pixels back to back (independent instructions; a lone dependent chain issues
 // one VALU per ~6 cycles on gfx950).  Integer codes in (as floats), integer codes out (as floats).
@@ -209,7 +175,6 @@ struct PxC {
 // (prev, frac) of one channel.  Computed form: FFmpeg's float ops on the code (A.3).  Table form:
 // the same ops were applied once per code when the kernel started (coord_table_fill), one
 // ds_read_b64 fetches the pair.  Both give identical bits.
-struct Crd { float p, d; };
 
 template <int INTERP>
 __device__ __forceinline__ Crd crd_compute(const LutConsts &L, float code, float sc)
@@ -217,15 +182,7 @@ __device__ __forceinline__ Crd crd_compute(const LutConsts &L, float code, float
     const float x = code * L.scale_f;
     // clipf(x*scale, 0, lut_max): codes and scales are >= 0, so only the upper bound can bind and a
     // plain v_min_f32 (full rate) replaces v_med3_f32 (0.62x rate on gfx950, tools/ubench/op_rates.hip)
-    const float s = fminf(x * sc, L.lut_max);
-    Crd c;
-    if constexpr (INTERP == LUTR_INTERP_NEAREST) {     // NEAR(x) with FFmpeg's double .5 (near_f, lutr_device.h)
-        const float fl = floorf(s);
-        c.p = (s - fl >= .5f) ? fl + 1.0f : fl;
-        c.d = 0.0f;
-    }
-    else { c.p = floorf(s); c.d = s - c.p; }
-    return c;
+    return crd_split<INTERP>(fminf(x * sc, L.lut_max));
 }
 
 __device__ __forceinline__ Crd crd_table(unsigned code)
@@ -253,7 +210,7 @@ __device__ __forceinline__ PxC px_finish(const LutConsts &L, const Win &W, const
     PxC c;
     if constexpr (LDS) {
         // exact in fp32: every term is an integer well below 2^24 for a window of <= 4096 nodes
-        c.a = (int)tfma(pr, W.fr, tfma(pg, W.fg, tfma(pb, W.fb, W.fc)));
+        c.a = (int)fma_(pr, W.fr, fma_(pg, W.fg, fma_(pb, W.fb, W.fc)));
         c.a = (int)min((unsigned)c.a, W.a_max);   // a stale window may not contain this cell: stay in LDS
     } else {
         c.a = (((int)pr * L.n1 + (int)pg) * L.n1 + (int)pb) * 16;
@@ -266,7 +223,7 @@ __device__ __forceinline__ PxC px_finish(const LutConsts &L, const Win &W, const
         // sorted form (see lutr_kernels.hip interp_tetrahedral for why this is bit-identical to
         // FFmpeg's six branches on a finite lattice)
         const float dr = cr.d, dg = cg.d, db = cb.d;
-        const float x = fmaxf(fmaxf(dr, dg), db), y = tmed3(dr, dg, db), z = fminf(fminf(dr, dg), db);
+        const float x = fmaxf(fmaxf(dr, dg), db), y = med3(dr, dg, db), z = fminf(fminf(dr, dg), db);
         const bool rg = dr > dg, gb = dg > db, rb = dr > db;
         // by-value copies: a ?: over struct members is an lvalue select, which pins W in scratch
         const int o_r = W.o_r, o_g = W.o_g, o_b = node_b<LDS, INTERP>();
@@ -347,9 +304,9 @@ __device__ __forceinline__ Rgb3 px_quant(const LutConsts &L, const Rgb3 &v)
         o.g = truncf(v.g * L.maxf);
         o.b = truncf(v.b * L.maxf);
     } else {
-        o.r = tmed3(truncf(v.r * L.maxf), 0.0f, L.maxf);
-        o.g = tmed3(truncf(v.g * L.maxf), 0.0f, L.maxf);
-        o.b = tmed3(truncf(v.b * L.maxf), 0.0f, L.maxf);
+        o.r = med3(truncf(v.r * L.maxf), 0.0f, L.maxf);
+        o.g = med3(truncf(v.g * L.maxf), 0.0f, L.maxf);
+        o.b = med3(truncf(v.b * L.maxf), 0.0f, L.maxf);
     }
     return o;
 }
@@ -457,13 +414,6 @@ struct WaveStats {
 
 // ---------------------------------------------------------------- sample helpers
 template <int WIDE>
-__device__ __forceinline__ float wsample(const uint32_t *w, int i)
-{
-    if constexpr (WIDE) return (float)((w[i >> 1] >> ((i & 1) * 16)) & 0xffffu);
-    else return (float)((w[i >> 2] >> ((i & 3) * 8)) & 0xffu);
-}
-
-template <int WIDE>
 __device__ __forceinline__ void wput(uint32_t *w, int i, float v)
 {
     const uint32_t u = (uint32_t)v;
@@ -471,36 +421,13 @@ __device__ __forceinline__ void wput(uint32_t *w, int i, float v)
     else w[i >> 2] |= u << ((i & 3) * 8);
 }
 
+// plain loads: non-temporal LOADS cost 2.5 % on gbrp10le; the stores are non-temporal (stw: +0.3 % here)
 template <int NW>
 __device__ __forceinline__ void ldw(uint32_t *w, const uint8_t *p)
 {
-#if LUTR_NT >= 2
-    typedef unsigned nt4 __attribute__((ext_vector_type(4)));
-    typedef unsigned nt2 __attribute__((ext_vector_type(2)));
-    if constexpr (NW == 4) { const nt4 v = __builtin_nontemporal_load((const nt4 *)p); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
-    else if constexpr (NW == 2) { const nt2 v = __builtin_nontemporal_load((const nt2 *)p); w[0] = v.x; w[1] = v.y; }
-    else w[0] = __builtin_nontemporal_load((const uint32_t *)p);
-#else
     if constexpr (NW == 4) { const uint4 v = *(const uint4 *)p; w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
     else if constexpr (NW == 2) { const uint2 v = *(const uint2 *)p; w[0] = v.x; w[1] = v.y; }
     else w[0] = *(const uint32_t *)p;
-#endif
-}
-
-template <int NW>
-__device__ __forceinline__ void stw(uint8_t *p, const uint32_t *w)
-{
-#if LUTR_NT
-    typedef unsigned nt4 __attribute__((ext_vector_type(4)));
-    typedef unsigned nt2 __attribute__((ext_vector_type(2)));
-    if constexpr (NW == 4) __builtin_nontemporal_store(nt4{w[0], w[1], w[2], w[3]}, (nt4 *)p);
-    else if constexpr (NW == 2) __builtin_nontemporal_store(nt2{w[0], w[1]}, (nt2 *)p);
-    else __builtin_nontemporal_store(w[0], (uint32_t *)p);
-#else
-    if constexpr (NW == 4) *(uint4 *)p = make_uint4(w[0], w[1], w[2], w[3]);
-    else if constexpr (NW == 2) *(uint2 *)p = make_uint2(w[0], w[1]);
-    else *(uint32_t *)p = w[0];
-#endif
 }
 
 // Zero-instruction ordering fence.  hipcc's instruction selection linearises an unrolled block
@@ -561,20 +488,6 @@ static inline TilePlanes tile_planes(const PlaneSet &P)
 #ifndef LUTR_TILE_WAVES_PER_EU
 #define LUTR_TILE_WAVES_PER_EU 4
 #endif
-
-// Position of chunk c on the batch; false when c is past the end.
-__device__ __forceinline__ bool chunk_at(const TileGeom &TG, unsigned c, int &fr, int &sx, int &ry, int &rem)
-{
-    if (c >= (unsigned)TG.nchunks) return false;
-    const int per_frame = TG.nrc * TG.nsx;
-    fr = (int)c / per_frame;
-    const int r = (int)c - fr * per_frame;
-    const int rc = r / TG.nsx;
-    sx = r - rc * TG.nsx;
-    ry = rc * TG.ch;
-    rem = min(TG.ch, TG.nry - ry);
-    return true;
-}
 
 // Claim the next chunk for this wave; returns false when the queue is drained.  The queue counter starts at
 // LUTR_STATIC_ROUNDS x the number of waves in the grid: wave w takes chunks w, w + waves, ... as its first ones

@@ -31,6 +31,9 @@
 //     by 2^depth-1 in fp32 (LutConsts::latm); the blend is a chain of full-rate v_fma_f32 with no final `* M`.  Each step
 //     rounds once, so the value before truncation is within a few ulp of strict's: <= 1 code at every depth.
 //   * Input and output depth are independent (10-bit in, 8-bit out is the reference's libx264 default).
+//   * SHARED WITH lutr_rgb2.hip (lutr_tube.h): the two-level chunk queue, the tube's axes and the plane strides padded against LDS
+//     bank conflicts, the small machine helpers.  Experiment variants that lost their measurement are not in this file: a
+//     one-line note stands where each would go, with the number and the profiles/ file or DESIGN.md section that holds it.
 //
 // Arithmetic of the strict variants: -ffp-contract=off, FFmpeg's scalar C order, bit-identical to the oracle.
 #include <cstdio>
@@ -42,9 +45,7 @@
 
 #include "lutr_internal.h"
 #include "lutr_launch.h"
-#ifndef LUTR_NT
-#define LUTR_NT 2        // 1: non-temporal stores, 2: and loads -- frames are read once and written once (+0.9 % / +0.5 % on 4:2:0, +1 % each on 4:4:4)
-#endif
+#include "lutr_tube.h"
 
 // One translation unit per (input width, output width, chroma layout): the Makefile compiles this file nine times
 // (-DLUTR_T2_WI=.. -DLUTR_T2_WO=.. -DLUTR_T2_X=.. -DLUTR_T2_Y=..), in parallel, each defining launch_yuv_tile2_w<WI><WO>_c<X><Y>.
@@ -64,47 +65,6 @@
 #ifndef LUTR_T2_WAVES_PER_EU
 #define LUTR_T2_WAVES_PER_EU 4
 #endif
-#ifndef LUTR_T2_PIN
-#define LUTR_T2_PIN 2             // wave-uniform constants copied to VGPRs: 1-2 kernel-wide (Y rows), 3-4 per tile (window, chroma rows)
-#endif
-#ifndef LUTR_T2_PK
-#define LUTR_T2_PK 0              // bit mask (1: luma add of R,G; 2: blends; 4: * M; 8: chroma sums; 15 = round 2's "1"): packed fp32 (v_pk_add/mul_f32) for the R,G pair of the strict blends, the luma add and the chroma
-                                  // sums -- bit-identical, 14 % fewer VALU instructions in the strict body (68.2 -> 58.7 per pixel), and
-                                  // 1-2 % SLOWER: a packed op holds the fp32 pipe as long as the two scalar ops it replaces (4.6 vs 2 x 2.5 cycles)
-#endif
-#ifndef LUTR_T2_TUBE_BG
-#define LUTR_T2_TUBE_BG 1         // the tube's second difference axis: 1 = (b - g), 0 = (b - r) as in round 2.  With BT.709 / 601 / 2020
-                                  // g - r is almost -Cr and b - g almost +Cb (dG = -0.21 cb - 2.33 cr, dBG = 2.33 cb + 0.53 cr at 10 bit),
-                                  // so the tube's cross-section is a near-square in the chroma plane; b - r = 2.12 cb - 1.80 cr makes it a
-                                  // parallelogram stretched along the magenta-green diagonal and thin along orange-blue, where video lives
-#endif
-#ifndef LUTR_T2_MIXED
-#define LUTR_T2_MIXED 1           // mixed tiles (see the vote in k_yuv_tile2)
-#endif
-#ifndef LUTR_T2_WIN_BG
-#define LUTR_T2_WIN_BG LUTR_T2_TUBE_BG      // the per-wave windows' second difference axis (independent of the tube's)
-#endif
-#ifndef LUTR_T2_WIN_PAD
-#define LUTR_T2_WIN_PAD 1         // 1: window plane strides padded against LDS bank collisions (win_plane_stride), 0: round 2's `| 1`
-#endif
-#ifndef LUTR_T2_PRIO
-#define LUTR_T2_PRIO 1            // s_setprio around the phases of a tile.  1: a wave between its body and the next one -- stores, chunk
-                                  // claim, the next tile's loads -- goes first, so memory operations leave as early as they can
-                                  // (strict 587-589 -> 593 Gpx/s, fast +0.1 %); 2: the body goes first (-1.7 %); 0: off
-#endif
-#ifndef LUTR_T2_MIXED_FAST
-#define LUTR_T2_MIXED_FAST 0      // 1: mixed tiles for the fast kernels too: sigma-16 frames 512 -> 537 Gpx/s, natural 662 -> 655, saturated 530 -> 522
-                                  // (10 more VGPRs in a kernel that has them to lose; profiles/r03_exp34_mixed_tiles_fast_kernels.txt): off
-#endif
-#ifndef LUTR_T2_TRIREC
-#define LUTR_T2_TRIREC 1          // 1: fast trilinear stages node + r-difference records (Node::rec)
-#endif
-#ifndef LUTR_T2_NODE16
-#define LUTR_T2_NODE16 0          // 1: strict 4-tap kernels stage float4 nodes (one ds_read_b128 per tap, 4 LDS cycles) instead of 12-byte ones (ds_read2_b32 + ds_read_b32, 6 cycles)
-#endif
-#ifndef LUTR_T2_PHASES
-#define LUTR_T2_PHASES 1          // scheduling barriers between the load and use phases of a pixel group (tile_body)
-#endif
 
 namespace lutr {
 namespace t2 {
@@ -112,19 +72,14 @@ namespace t2 {
 extern __shared__ __attribute__((aligned(16))) char smem[];
 
 // LDS behind the coordinate table: 64 bytes of scratch per wave (window cell ranges, raw box, counters), then the WORKGROUP's
-// chunk allocator (claim_chunk): {ticket} at +0, base[8] at +32, ready[8] at +64.
+// chunk allocator (the two-level queue of lutr_tube.h).
 constexpr int kWaveScratch = LUTR_T2_WPB * 64;
-constexpr int kScratch = kWaveScratch + 128;
+constexpr int kScratch = kWaveScratch + tube::kQueueLds;
 
 enum { V_GEN = 0, V_TAB = 1, V_UNIT = 2, V_FAST = 3, V_FMA32 = 4 };      // V >= V_UNIT: clip-free
 
-#define DEV __device__ __forceinline__
-
-// ---------------------------------------------------------------- small machine helpers
-DEV float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-DEV float med3(float a, float lo, float hi) { return __builtin_amdgcn_fmed3f(a, lo, hi); }
-DEV int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-DEV float unif(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+// ---------------------------------------------------------------- small machine helpers (more in lutr_tube.h)
+using namespace tube;
 DEV float in_vgpr(float s)
 {
     float v;
@@ -166,37 +121,11 @@ DEV u3 make_rec(uint2 a, uint2 b)
     return u3{a.x, (a.y & 0xffffu) | (dr << 16), dg | (db << 16)};
 }
 
-// {a.x + s, a.y + s} in one v_pk_add_f32: op_sel_hi makes the high half read the LOW dword of the second operand too (the
-// compiler scalarises a splat add).  The second operand is a register pair whose high half is never read.
-typedef float f2v __attribute__((ext_vector_type(2)));
-DEV f2v pk_add_lo(f2v a, float s)
-{
-    f2v b, d;
-    b.x = s;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-
-// a * w.lo / a * w.hi on both halves (the weight pair is shared by two such products, no register is wasted), a * s with s
-// broadcast from a scalar pair, and a + b / a - b as the compiler's own v_pk_add_f32.  Each half rounds exactly like the scalar op.
-template <int HI> DEV f2v pk_mul_w(f2v a, f2v w)
-{
-    f2v d;
-    if constexpr (HI) asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(d) : "v"(a), "v"(w));
-    else asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(d) : "v"(a), "v"(w));
-    return d;
-}
-DEV f2v pk_mul_lo(f2v a, float s)
-{
-    f2v b, d;
-    b.x = s;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-
+// (Measured and removed: packed fp32 -- v_pk_add/mul_f32 -- for the R,G pair of the strict blends, the luma add, `* M` and the chroma
+// sums, behind a build switch: bit-identical, 68.2 -> 58.7 VALU per pixel in the strict body, and 1-2 % SLOWER; part by part 573-594
+// against 595 Gpx/s: profiles/r03_exp37_packed_fp32_parts.txt)
 DEV int lds_base() { return (int)(unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)smem; }
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u2 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------- geometry shared with the launcher
@@ -247,8 +176,8 @@ template <int INTERP, int V> struct Node {
     // -- FFmpeg's first four lerps (along r) then take ONE v_fma_mix_f32 each instead of two, and a pixel reads 4 records instead of
     // 8 nodes.  (The strict kernels cannot afford it: fp32 records are 24 bytes, the tube would shrink to 4 cells and the windows to
     // nothing.)  The gather body rounds its differences to fp16 as well, so both paths compute the same number.
-    static constexpr bool rec = LUTR_T2_TRIREC && fast && INTERP == LUTR_INTERP_TRILINEAR;
-    static constexpr int lds = fast ? (rec ? 12 : 8) : ((INTERP == LUTR_INTERP_TRILINEAR || INTERP == T2_TET16 || LUTR_T2_NODE16) ? 16 : 12);
+    static constexpr bool rec = fast && INTERP == LUTR_INTERP_TRILINEAR;
+    static constexpr int lds = fast ? (rec ? 12 : 8) : ((INTERP == LUTR_INTERP_TRILINEAR || INTERP == T2_TET16) ? 16 : 12);
     static constexpr int glb = fast ? 8 : 16;                                              // bytes per node in HBM/L2
 };
 
@@ -270,21 +199,11 @@ DEV void box_store(int scratch_off, const Box &b)
 
 struct Ext { uint32_t ymin, ymax, cbmin, cbmax, crmin, crmax; };   // packed per-lane extremes of a unit
 
-// (prev, frac) of one channel
-struct Crd { float p, d; };
-
 template <int INTERP>
 DEV Crd crd_compute(const LutConsts &L, float code, float sc)
 {
     const float x = code * L.scale_f;
-    const float s = fminf(x * sc, L.lut_max);       // codes and scales are >= 0: only the upper clip can bind
-    Crd c;
-    if constexpr (INTERP == LUTR_INTERP_NEAREST) {  // NEAR(x) = (int)(x + .5) with a double .5 (lutr_device.h near_f)
-        const float fl = floorf(s);
-        c.p = (s - fl >= .5f) ? fl + 1.0f : fl;
-        c.d = 0.0f;
-    } else { c.p = floorf(s); c.d = s - c.p; }
-    return c;
+    return crd_split<INTERP>(fminf(x * sc, L.lut_max));       // codes and scales are >= 0: only the upper clip can bind
 }
 
 DEV Crd crd_table(unsigned idx)
@@ -295,15 +214,8 @@ DEV Crd crd_table(unsigned idx)
 // The per-pixel paths index the table by BYTE offset: their YUV -> RGB constants are pre-multiplied by 8 (KB in the kernel;
 // a power of two commutes with every rounding), so (unsigned)(8 * v) & ~7 == 8 * floor(v): the `* 8` that was a
 // quarter-rate v_lshl_add_u32 per channel is a v_and_b32 on the other pipe.
-// The table sits at LDS address 0 (the kernel has no static LDS, the dynamic block starts at 0 -- checked at kernel start):
-// the offset IS the address, no v_add of the block's base.
-typedef __attribute__((address_space(3))) const f2v *lds_f2p;
+// The table sits at LDS address 0 (checked at kernel start): the offset IS the address (crd_table8, lutr_tube.h).
 typedef __attribute__((address_space(3))) const float *lds_fp;
-DEV Crd crd_table8(unsigned off)
-{
-    const f2v e = *(lds_f2p)(uintptr_t)off;
-    return Crd{e.x, e.y};
-}
 
 // Entry i of the table = coordinates of code min(i, M): indices past M are what an out-of-gamut YUV triple produces
 // before FFmpeg's clip to the depth; the clip is folded into the table.
@@ -313,9 +225,7 @@ DEV void coord_table_fill(const LutConsts &L, int entries)
     for (int q = threadIdx.x; q < entries; q += 64 * LUTR_T2_WPB) {
         Crd c;
         if (L.pre) {                 // a shared prelut (LutConsts::pre_shared): the folded coordinate of the code, then prev / frac as ever
-            const float s = L.pre[min(q, (int)L.maxf)];
-            if constexpr (INTERP == LUTR_INTERP_NEAREST) { const float fl = floorf(s); c.p = (s - fl >= .5f) ? fl + 1.0f : fl; c.d = 0.0f; }
-            else { c.p = floorf(s); c.d = s - c.p; }
+            c = crd_split<INTERP>(L.pre[min(q, (int)L.maxf)]);
         } else c = crd_compute<INTERP>(L, fminf((float)q, L.maxf), L.sc[0]);
         *(float2 *)(smem + q * 8) = make_float2(c.p, c.d);
     }
@@ -335,15 +245,10 @@ struct Tile {
 template <int WIN, int WOUT, int CSX, int CSY> struct TileIn { using T = Tile<WIN, WOUT, CSX, CSY>; uint32_t y[T::BH][T::YWI], cb[T::CWI], cr[T::CWI]; };
 template <int WIN, int WOUT, int CSX, int CSY> struct TileOut { using T = Tile<WIN, WOUT, CSX, CSY>; uint32_t y[T::BH][T::YWO], cb[T::CWO], cr[T::CWO]; };
 
-template <int WIDE>
-DEV float wsample(const uint32_t *w, int i)
-{
-    if constexpr (WIDE) return (float)((w[i >> 1] >> ((i & 1) * 16)) & 0xffffu);
-    else return (float)((w[i >> 2] >> ((i & 3) * 8)) & 0xffu);
-}
-
+// (wsample and the non-temporal stw: lutr_tube.h)
 // floor(v) for v >= 0 (negatives saturate to 0) written into sample i of the word vector: one SDWA conversion
-// (v_cvt_u32_f32 truncates) instead of convert + shift-or.
+// (v_cvt_u32_f32 truncates) instead of convert + shift-or.  (lutr_rgb2.hip's `put` is the same idea; shared, the two compile to
+// differently scheduled code.)
 template <int WIDE>
 DEV void wput(uint32_t *w, int i, float v)
 {
@@ -361,35 +266,15 @@ DEV void wput(uint32_t *w, int i, float v)
     }
 }
 
+// Frames are read once and written once: the loads are non-temporal too (+0.9 % / +0.5 % on 4:2:0, +1 % each on 4:4:4 for stores / loads;
+// planar RGB loses 2.5 % with non-temporal loads, DESIGN.md 5.2 "Streaming accesses")
 template <int NW> DEV void ldw(uint32_t *w, const uint8_t *p)
 {
-#if LUTR_NT >= 2
     typedef unsigned nt4 __attribute__((ext_vector_type(4)));
     typedef unsigned nt2 __attribute__((ext_vector_type(2)));
     if constexpr (NW == 4) { const nt4 v = __builtin_nontemporal_load((const nt4 *)p); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
     else if constexpr (NW == 2) { const nt2 v = __builtin_nontemporal_load((const nt2 *)p); w[0] = v.x; w[1] = v.y; }
     else w[0] = __builtin_nontemporal_load((const uint32_t *)p);
-#else
-    if constexpr (NW == 4) { const uint4 v = *(const uint4 *)p; w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
-    else if constexpr (NW == 2) { const uint2 v = *(const uint2 *)p; w[0] = v.x; w[1] = v.y; }
-    else w[0] = *(const uint32_t *)p;
-#endif
-}
-template <int NW> DEV void stw(uint8_t *p, const uint32_t *w)
-{
-#if LUTR_NT
-    typedef unsigned nt4 __attribute__((ext_vector_type(4)));
-    typedef unsigned nt2 __attribute__((ext_vector_type(2)));
-    if constexpr (NW == 8) { __builtin_nontemporal_store(nt4{w[0], w[1], w[2], w[3]}, (nt4 *)p); __builtin_nontemporal_store(nt4{w[4], w[5], w[6], w[7]}, (nt4 *)(p + 16)); }
-    else if constexpr (NW == 4) __builtin_nontemporal_store(nt4{w[0], w[1], w[2], w[3]}, (nt4 *)p);
-    else if constexpr (NW == 2) __builtin_nontemporal_store(nt2{w[0], w[1]}, (nt2 *)p);
-    else __builtin_nontemporal_store(w[0], (uint32_t *)p);
-#else
-    if constexpr (NW == 8) { *(uint4 *)p = make_uint4(w[0], w[1], w[2], w[3]); *(uint4 *)(p + 16) = make_uint4(w[4], w[5], w[6], w[7]); }
-    else if constexpr (NW == 4) *(uint4 *)p = make_uint4(w[0], w[1], w[2], w[3]);
-    else if constexpr (NW == 2) *(uint2 *)p = make_uint2(w[0], w[1]);
-    else *(uint32_t *)p = w[0];
-#endif
 }
 
 template <int N> DEV void fence_words(uint32_t *w)
@@ -398,7 +283,6 @@ template <int N> DEV void fence_words(uint32_t *w)
     else if constexpr (N == 2) asm volatile("" : "+v"(w[0]), "+v"(w[1]));
     else if constexpr (N == 4) asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]));
     else if constexpr (N == 8) asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7]));
-    else if constexpr (N == 16) { fence_words<8>(w); fence_words<8>(w + 8); }
 }
 
 // ---------------------------------------------------------------- raw extremes of a unit
@@ -515,14 +399,14 @@ DEV Cells map_box(const LutConsts &L, const YuvConsts &K, const Geom &TG, float 
     const float pb0 = cell_of<INTERP, PRE, V>(L, qclip(vb0, m), 2, te), pb1 = cell_of<INTERP, PRE, V>(L, qclip(vb1, m), 2, te);
     Cells c;
     c.r0 = (int)pr0; c.r1 = (int)pr1;
-    // the second difference axis is (b - g) [LUTR_T2_WIN_BG] or (b - r)
+    // the second difference axis is (b - g), as the tube's (lutr_tube.h)
     float g_lo = pg0 - pr1, g_hi = pg1 - pr0;                                                   // interval arithmetic
-    float b_lo = LUTR_T2_WIN_BG ? pb0 - pg1 : pb0 - pr1, b_hi = LUTR_T2_WIN_BG ? pb1 - pg0 : pb1 - pr0;
+    float b_lo = pb0 - pg1, b_hi = pb1 - pg0;
     if (L.pre || (L.sc[0] == L.sc[1] && L.sc[1] == L.sc[2])) {
         // chroma-only difference terms at the corners that extremise them: gv - rv falls in cb and in cr;
-        // bu - rv rises in cb and falls in cr; bu - gv rises in both (gv1 = gv at (cb0, cr0), gv0 = gv at (cb1, cr1))
+        // bu - gv rises in both (gv1 = gv at (cb0, cr0), gv0 = gv at (cb1, cr1))
         float dg0 = gv0 - rv1, dg1 = gv1 - rv0;
-        float db0 = LUTR_T2_WIN_BG ? bu0 - gv1 : bu0 - rv1, db1 = LUTR_T2_WIN_BG ? bu1 - gv0 : bu1 - rv0;
+        float db0 = bu0 - gv1, db1 = bu1 - gv0;
         // (a shared prelut is a monotone map whose slope lies between 0 and pre_kappa cells per code: a code difference d moves the
         // cell by at most pre_kappa |d| and possibly not at all -- the same one-sided form as where the clip can bind)
         const bool clips = L.pre || vr0 < 0.0f || vg0 < 0.0f || vb0 < 0.0f || vr1 >= m + 1.0f || vg1 >= m + 1.0f || vb1 >= m + 1.0f;
@@ -545,9 +429,6 @@ DEV Cells map_box(const LutConsts &L, const YuvConsts &K, const Geom &TG, float 
 // computes what round 1 computed for every tile: the exact cells each pixel touches, min/max per lane, one vote against
 // the window's cell ranges.  ~18 VALU per pixel, paid only by the tiles that fail the cheap test.
 struct Bnd { float rmin, rmax, gmin, gmax, bmin, bmax; };
-
-DEV float vmin3(float a, float b, float c) { float o; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(o) : "v"(a), "v"(b), "v"(c)); return o; }
-DEV float vmax3(float a, float b, float c) { float o; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(o) : "v"(a), "v"(b), "v"(c)); return o; }
 
 template <int WIN, int WOUT, int CSX, int CSY, int INTERP, int PRE, int V>
 DEV Bnd tile_bounds(const LutConsts &L, const YuvConsts &K, const Geom &TG, TileIn<WIN, WOUT, CSX, CSY> &in)
@@ -585,11 +466,9 @@ DEV Bnd tile_bounds(const LutConsts &L, const YuvConsts &K, const Geom &TG, Tile
                 pb_[q] = crd_compute<INTERP>(L, cfloor(yy + bu, K.max_l), L.sc[2]).p;
             }
         }
-#if LUTR_T2_PHASES
         __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
-        for (int q = 0; q < NQ; q++) { hg[q] = pg_[q] - pr[q]; hb[q] = pb_[q] - (LUTR_T2_WIN_BG ? pg_[q] : pr[q]); }
+        for (int q = 0; q < NQ; q++) { hg[q] = pg_[q] - pr[q]; hb[q] = pb_[q] - pg_[q]; }
         if constexpr (T::BH * T::BW >= 2) {
 #pragma unroll
             for (int q = 0; q + 1 < T::BH * T::BW; q += 2) {
@@ -644,7 +523,7 @@ DEV bool tube_holds(const YuvConsts &K, const Geom &TG, const Ext &e)
     const float gv0 = fma_(K.kgu, cbd1, K.kgv * crd1), gv1 = fma_(K.kgu, cbd0, K.kgv * crd0);      // min, max
     // (b - g: bu - gv rises in cb and in cr, its extremes sit at the corners (cb0, cr0) and (cb1, cr1) where gv is gv1 and gv0)
     const float dg0 = gv0 - rv1, dg1 = gv1 - rv0;
-    const float db0 = LUTR_T2_TUBE_BG ? bu0 - gv1 : bu0 - rv1, db1 = LUTR_T2_TUBE_BG ? bu1 - gv0 : bu1 - rv0;
+    const float db0 = bu0 - gv1, db1 = bu1 - gv0;
     const float worst = vmax3(fmaxf(-dg0, dg1), -db0, db1);
     return worst <= TG.tube_t;          // per lane: the caller votes
 }
@@ -666,24 +545,13 @@ DEV bool tube_holds_samples(const YuvConsts &K, const Geom &TG, const TileIn<WIN
         }
         const float cbd = cbv - K.coff, crd = crv - K.coff;
         const float rv = K.krv * crd, gv = fma_(K.kgu, cbd, K.kgv * crd), bu = K.kbu * cbd;
-        worst = vmax3(worst, fabsf(gv - rv), fabsf(LUTR_T2_TUBE_BG ? bu - gv : bu - rv));
+        worst = vmax3(worst, fabsf(gv - rv), fabsf(bu - gv));
     }
     return worst <= TG.tube_t;          // per lane: the caller votes
 }
 
 // ---------------------------------------------------------------- restage
 DEV uint32_t shx(uint32_t v, int m) { return (uint32_t)__shfl_xor((int)v, m, 64); }
-DEV float wave_min(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fminf(v, __shfl_xor(v, m, 64));
-    return v;
-}
-DEV float wave_max(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-    return v;
-}
-
 template <int WIN> DEV int lo_of(uint32_t mn) { const int a = (int)(mn & 0xffffu), b = (int)(mn >> 16); const int v = a < b ? a : b; return WIN ? v : v >> 8; }
 template <int WIN> DEV int hi_of(uint32_t mx) { const int a = (int)(mx & 0xffffu), b = (int)(mx >> 16); const int v = a > b ? a : b; return WIN ? v : v >> 8; }
 template <int WIN> DEV uint32_t pack_lo(int v) { const uint32_t h = WIN ? (uint32_t)v : (uint32_t)v << 8; return h | (h << 16); }
@@ -742,10 +610,10 @@ DEV bool rebox(const LutConsts &L, const YuvConsts &K, const Geom &TG, const Ext
 // pay the second level).  Returns false (W untouched; the caller runs the global-gather body for this tile) when the
 // tile's colours do not fit a window, or a raw code lies above 2^din - 1.
 // Plane stride of a window: the smallest stride >= `nodes` for which cells one step apart on any axes never share an LDS bank
-// (see tube_plane_stride in the launcher: node index = pr * A + pg * B + pb, collision when dr A + dg B + db = 0 mod 32, i.e.
+// (see tube_plane_stride in lutr_tube.h: node index = pr * A + pg * B + pb, collision when dr A + dg B + db = 0 mod 32, i.e.
 // when A mod 32 lies within one of 0, +B or -B).  kGoodA[B mod 32] has bit (A mod 32) set for the strides that are fine; a
 // rotate and a find-first-set pick the padding -- this runs in every restage, and every wave starts with one (a search loop
-// here cost a short launch 30 us).
+// here cost a short launch 30 us).  (Round 2's `nodes | 1` instead: profiles/r03_exp15_window_shear_padding.txt.)
 __constant__ unsigned kGoodA[32] = {
     0x00000000u, 0x00000000u, 0x1ffffff0u, 0x0fffffe0u, 0x47ffffc4u, 0x63ffff8cu, 0x71ffff1cu, 0x78fffe3cu, 0x7c7ffc7cu, 0x7e3ff8fcu,
     0x7f1ff1fcu, 0x7f8fe3fcu, 0x7fc7c7fcu, 0x7fe38ffcu, 0x7ff11ffcu, 0x7ff83ffcu, 0x7ffc7ffcu, 0x7ff83ffcu, 0x7ff11ffcu, 0x7fe38ffcu,
@@ -756,9 +624,8 @@ __constant__ unsigned short kGoodA16[16] = {      // the same for 16-byte nodes 
 template <int NODE>
 DEV int win_plane_stride(int nodes, int nb)
 {
-    if (!LUTR_T2_WIN_PAD) return nodes | 1;
     constexpr int M = NODE == 16 ? 16 : 32;
-    const int B = LUTR_T2_WIN_BG ? nb - 1 : nb, a0 = (LUTR_T2_WIN_BG ? nodes - nb : nodes - nb - 1) & (M - 1);
+    const int B = nb - 1, a0 = (nodes - nb) & (M - 1);
     const unsigned m = NODE == 16 ? (unsigned)kGoodA16[B & 15] : kGoodA[B & 31];
     const unsigned r = a0 ? ((m >> a0) | (m << (M - a0))) & (NODE == 16 ? 0xffffu : 0xffffffffu) : m;      // bit k: padding k is fine
     return r ? nodes + __builtin_ctz(r) : (nodes | 1);
@@ -870,7 +737,7 @@ DEV bool restage(Win &W, const LutConsts &L, const YuvConsts &K, const Geom &TG,
             const int i = min(base + k * 64 + lane, total - 1);              // the last batch re-reads the final node: harmless
             const int ir = (int)(((float)i + 0.5f) * rcp_plane), rem = i - __mul24(ir, plane);
             const int ig = (int)(((float)rem + 0.5f) * rcp_nb), ib = rem - __mul24(ig, nb);
-            int r = r0 + ir, g = r + g0 + ig, b = (LUTR_T2_WIN_BG ? g : r) + b0 + ib;
+            int r = r0 + ir, g = r + g0 + ig, b = g + b0 + ib;
             // nodes outside the cube are never referenced by a valid pixel: clamp to stay inside the lattice
             r = min(max(r, 0), nmax); g = min(max(g, 0), nmax); b = min(max(b, 0), nmax);
             const int src = __mul24(__mul24(r, n1) + g, n1) + b;
@@ -892,9 +759,8 @@ DEV bool restage(Win &W, const LutConsts &L, const YuvConsts &K, const Geom &TG,
         *(float4 *)(smem + scratch_off) = make_float4((float)wr0, (float)wg0, (float)wb0, (float)wr1);
         *(float2 *)(smem + scratch_off + 16) = make_float2((float)wg1, (float)wb1);
     }
-    // node index = (pr-r0)*sr + (pg-pr-g0)*nb + (pb-pg-b0)     [(pb-pr-b0) without LUTR_T2_WIN_BG]
-    if (LUTR_T2_WIN_BG) { W.o_r = kLN * (sr - nb); W.o_g = kLN * (nb - 1); }
-    else { W.o_r = kLN * (sr - nb - 1); W.o_g = kLN * nb; }
+    // node index = (pr-r0)*sr + (pg-pr-g0)*nb + (pb-pg-b0)
+    W.o_r = kLN * (sr - nb); W.o_g = kLN * (nb - 1);
     W.fr = (float)W.o_r; W.fg = (float)W.o_g; W.fb = (float)kLN;
     W.fc = (float)(lds_base() + slice_off - kLN * (r0 * sr + g0 * nb + b0));
     if (lane == 0) {
@@ -972,8 +838,6 @@ DEV u2 tap16(const LutConsts &L, int a)
     if constexpr (LDS) return *(const __attribute__((address_space(3))) u2 *)(uintptr_t)(unsigned)a;
     else return *(const u2 *)((const char *)L.lat16 + a);
 }
-
-DEV float tlerp(float v0, float v1, float f) { return v0 + (v1 - v0) * f; }
 
 // The taps of one pixel, loaded in one go so that several pixels' reads are in flight together (tile_body phases).
 template <bool LDS, int INTERP, int V> struct Taps {
@@ -1105,28 +969,6 @@ DEV Rgb3 px_blend(const LutConsts &L, const PxC &c, const Taps<LDS, INTERP, V> &
             v.r = T.t[0].x; v.g = T.t[0].y; v.b = T.t[0].z;
         } else if constexpr (INTERP == LUTR_INTERP_TRILINEAR) {
             const float dr = c.w01.x, dg = c.w01.y, db = c.w23.x;
-#if LUTR_T2_PK & 2
-            // R and G ride in one register pair through FFmpeg's seven lerps (v0 + (v1 - v0) * f, each op rounded on its own, as
-            // the scalar code below): 21 packed + 21 scalar instructions instead of 63
-#define XY(k) f2v{T.t[k].x, T.t[k].y}
-            auto lerp2 = [](f2v v0, f2v v1, f2v w, auto hi) {
-                const f2v d = v1 - v0;
-                return v0 + pk_mul_w<decltype(hi)::value>(d, w);
-            };
-            using LO = std::integral_constant<int, 0>; using HI_ = std::integral_constant<int, 1>;
-            const f2v c00 = lerp2(XY(0), XY(4), c.w01, LO{}), c10 = lerp2(XY(2), XY(6), c.w01, LO{});
-            const f2v c01 = lerp2(XY(1), XY(5), c.w01, LO{}), c11 = lerp2(XY(3), XY(7), c.w01, LO{});
-            const f2v c0 = lerp2(c00, c10, c.w01, HI_{}), c1 = lerp2(c01, c11, c.w01, HI_{});
-            const f2v rg = lerp2(c0, c1, c.w23, LO{});
-#undef XY
-            v.r = rg.x; v.g = rg.y;
-            {
-                const float c00 = tlerp(T.t[0].z, T.t[4].z, dr), c10 = tlerp(T.t[2].z, T.t[6].z, dr);
-                const float c01 = tlerp(T.t[1].z, T.t[5].z, dr), c11 = tlerp(T.t[3].z, T.t[7].z, dr);
-                const float c0 = tlerp(c00, c10, dg), c1 = tlerp(c01, c11, dg);
-                v.b = tlerp(c0, c1, db);
-            }
-#else
 #define TRI(ch, out) \
             { \
                 const float c00 = tlerp(T.t[0].ch, T.t[4].ch, dr), c10 = tlerp(T.t[2].ch, T.t[6].ch, dr); \
@@ -1136,29 +978,12 @@ DEV Rgb3 px_blend(const LutConsts &L, const PxC &c, const Taps<LDS, INTERP, V> &
             }
             TRI(x, v.r) TRI(y, v.g) TRI(z, v.b)
 #undef TRI
-#endif
         } else {
             const float w0 = c.w01.x, w1 = c.w01.y, w2 = c.w23.x, w3 = c.w23.y;
-#if LUTR_T2_PK & 2
-            // FFmpeg's w0 c000 + w1 cA + w2 cB + w3 c111, left to right, products and sums rounded one by one: R and G as a pair
-            f2v rg = pk_mul_w<0>(f2v{T.t[0].x, T.t[0].y}, c.w01);
-            rg = rg + pk_mul_w<1>(f2v{T.t[1].x, T.t[1].y}, c.w01);
-            rg = rg + pk_mul_w<0>(f2v{T.t[2].x, T.t[2].y}, c.w23);
-            rg = rg + pk_mul_w<1>(f2v{T.t[3].x, T.t[3].y}, c.w23);
-            v.r = rg.x; v.g = rg.y;
-#else
             v.r = w0 * T.t[0].x + w1 * T.t[1].x + w2 * T.t[2].x + w3 * T.t[3].x;
             v.g = w0 * T.t[0].y + w1 * T.t[1].y + w2 * T.t[2].y + w3 * T.t[3].y;
-#endif
             v.b = w0 * T.t[0].z + w1 * T.t[1].z + w2 * T.t[2].z + w3 * T.t[3].z;
         }
-#if LUTR_T2_PK & 4
-        if constexpr (INTERP != LUTR_INTERP_NEAREST) {
-            const f2v rgm = pk_mul_lo(f2v{v.r, v.g}, L.maxf);
-            v.r = rgm.x; v.g = rgm.y; v.b *= L.maxf;
-            return v;
-        }
-#endif
         v.r *= L.maxf; v.g *= L.maxf; v.b *= L.maxf;
         return v;
     }
@@ -1189,7 +1014,6 @@ DEV void group_coords(const LutConsts &L, const YuvConsts &K, const Geom &TG, co
     using T = Tile<WIN, WOUT, CSX, CSY>;
     constexpr int GW = 4 / T::BH, NCG = (GW >> CSX) > 0 ? (GW >> CSX) : 1;
     float rv[NCG], gv[NCG], bu[NCG];
-    f2v rgv[NCG];                   // {rv, gv} as a register pair: one v_pk_add_f32 adds luma to both (LUTR_T2_PK)
 #pragma unroll
     for (int c = 0; c < NCG; c++) {
         const int j = g * NCG + c;
@@ -1200,7 +1024,6 @@ DEV void group_coords(const LutConsts &L, const YuvConsts &K, const Geom &TG, co
         }
         const float cbd = cbv - K.coff, crd = crv - K.coff;
         rv[c] = K.krv * crd; gv[c] = fma_(K.kgu, cbd, K.kgv * crd); bu[c] = K.kbu * cbd;
-        rgv[c].x = rv[c]; rgv[c].y = gv[c];
     }
 #pragma unroll
     for (int p = 0; p < 4; p++) {
@@ -1211,12 +1034,7 @@ DEV void group_coords(const LutConsts &L, const YuvConsts &K, const Geom &TG, co
         if constexpr (V >= V_TAB) {
             // clip(floor(v), 0, M): v_cvt_u32_f32 floors and saturates negatives to 0; the table is padded past M
             // K is the kernel's KB here: sums are 8 x the code, the masked conversion is the table's byte offset
-#if LUTR_T2_PK & 1
-            const f2v rg = pk_add_lo(rgv[c], yy);  // {rv + yy, gv + yy}: the same two roundings as the scalar adds
-            unsigned ri = (unsigned)rg.x & ~7u, gi = (unsigned)rg.y & ~7u, bi = (unsigned)(yy + bu[c]) & ~7u;
-#else
             unsigned ri = (unsigned)(yy + rv[c]) & ~7u, gi = (unsigned)(yy + gv[c]) & ~7u, bi = (unsigned)(yy + bu[c]) & ~7u;
-#endif
             if constexpr (!LDS) {           // the gather body also serves tiles with raw codes nobody vouched for
                 const unsigned top = (unsigned)(TG.tab_entries - 1) * 8u;
                 ri = min(ri, top); gi = min(gi, top); bi = min(bi, top);
@@ -1230,71 +1048,37 @@ DEV void group_coords(const LutConsts &L, const YuvConsts &K, const Geom &TG, co
     }
 }
 
-#ifndef LUTR_T2_PIPE
-#define LUTR_T2_PIPE 0            // 1: software pipeline across pixel groups (group g+1's coordinate reads before group g's blend): +4 % for the strict kernels while they had registers for it; with the tube state live it spills (-2.7 %)
-#endif
-#ifndef LUTR_T2_FENCE_ALL
-#define LUTR_T2_FENCE_ALL 0
-#endif
-#ifndef LUTR_T2_PIPE_FAST
-#define LUTR_T2_PIPE_FAST 0
-#endif
-#ifndef LUTR_T2_KARG
-#define LUTR_T2_KARG 1
-#endif
-#ifndef LUTR_T2_TUBE_SAMPLES
-#define LUTR_T2_TUBE_SAMPLES 1
-#endif
-#ifndef LUTR_T2_TB_FAST
-#define LUTR_T2_TB_FAST 4
-#endif
-
 // One tile.  Every LDS result is requested well before it is used, inside the wave: with four waves per SIMD (the
 // register budget) the hardware alone cannot hide an LDS round trip per pixel.  Order per group g:
-//   A(g+1)  coordinate reads of the next group      (12 ds_read_b64, consumed one group later)
+//   A(g)    coordinate reads of the group            (12 ds_read_b64)
 //   B(g)    tap addresses + weights, then tap reads  (TB pixels' taps in flight together)
 //   C(g)    blends, truncation, RGB -> YUV, packing
 // sched_barrier keeps the machine scheduler from sinking the reads back next to their uses; the zero-instruction
 // fences at the end of a group keep instruction selection from hoisting every group to the top (> 1000 spilled registers).
+// (Measured and removed, each behind a build switch: issuing A(g+1) before C(g) -- +4 % for the strict kernels while they had the
+// registers, with the tube state live it spills: -2.7 %, DESIGN.md 5.2 "Scheduling"; fencing every input and output word instead of
+// the live ones keeps 2 x 12 registers allocated through the tile; the window's address factors and the chroma rows copied to VGPRs
+// per tile: no gain)
 template <bool LDS, int WIN, int WOUT, int CSX, int CSY, int INTERP, int PRE, int V>
 DEV void tile_body(const LutConsts &L, const YuvConsts &K_, const Win &W_, const Geom &TG, TileIn<WIN, WOUT, CSX, CSY> &in,
                    TileOut<WIN, WOUT, CSX, CSY> &out)
 {
-    // the four address factors go to VGPRs for the length of the tile (three fma per pixel at full rate instead of the
-    // SGPR-operand rate); kernel-wide they would be live across the restage code, which has no registers to spare
-    Win W = W_;
-    if constexpr (LDS && LUTR_T2_PIN >= 3 && V == V_FAST && INTERP != LUTR_INTERP_TRILINEAR) {
-        W.fr = in_vgpr(W_.fr); W.fg = in_vgpr(W_.fg); W.fb = in_vgpr(W_.fb); W.fc = in_vgpr(W_.fc);
-    }
+    Win W = W_;              // (local copies: through the references alone every instance gets another register allocation)
     YuvConsts K = K_;
-    if constexpr (LDS && LUTR_T2_PIN >= 4 && V == V_FAST && INTERP != LUTR_INTERP_TRILINEAR) {
-        // the chroma terms and the RGB -> CbCr rows: 12 moves per tile buy 3 full-rate ops per pixel
-        K.krv = in_vgpr(K_.krv); K.kgu = in_vgpr(K_.kgu); K.kgv = in_vgpr(K_.kgv); K.kbu = in_vgpr(K_.kbu); K.coff = in_vgpr(K_.coff);
-        K.cbr = in_vgpr(K_.cbr); K.cbg = in_vgpr(K_.cbg); K.cbb = in_vgpr(K_.cbb); K.cob = in_vgpr(K_.cob);
-        K.crr = in_vgpr(K_.crr); K.crg = in_vgpr(K_.crg); K.crb = in_vgpr(K_.crb);
-    }
     using T = Tile<WIN, WOUT, CSX, CSY>;
     // a group = 4 pixels: all BH rows of GW columns; it owns NCG chroma samples
     constexpr int GW = 4 / T::BH, NG = T::PXT / GW, NCG = (GW >> CSX) > 0 ? (GW >> CSX) : 1;
     constexpr bool kDead = V >= V_UNIT;          // launcher checked the RGB->YUV maxima too (out_clip_dead)
-    // measured (UHD yuv420p10le tetrahedral, Gpx/s): strict 503 with the pipeline, 484 without; fast 458 with (the extra live
-    // coordinates push its 4-pixel tap batches into spills), 550-565 without
-    constexpr bool kPipe = LUTR_T2_PIPE && LDS && V >= V_TAB && (V != V_FAST || LUTR_T2_PIPE_FAST);
-    constexpr int TB = INTERP == LUTR_INTERP_TRILINEAR ? (V == V_FAST ? 2 : 1)
-                                                       : (INTERP == LUTR_INTERP_NEAREST ? 4 : (V == V_FAST ? LUTR_T2_TB_FAST : 2));
+    // tap batches of the fast 4-tap kernels: 4 pixels (2 and 1 were measured behind a build switch)
+    constexpr int TB = INTERP == LUTR_INTERP_TRILINEAR ? (V == V_FAST ? 2 : 1) : (INTERP == LUTR_INTERP_NEAREST ? 4 : (V == V_FAST ? 4 : 2));
+    // (two slots, one used: the second is what is left of the removed cross-group pipeline.  A single GroupCrd compiles the general
+    // 4:2:2 tetrahedral instances to three adds with their operands swapped, and this file's device code is held bit for bit.)
     GroupCrd cq[2];
-    if constexpr (kPipe) group_coords<LDS, WIN, WOUT, CSX, CSY, INTERP, PRE, V>(L, K, TG, in, 0, cq[0]);
 #pragma unroll
     for (int g = 0; g < NG; g++) {
-        GroupCrd &q = cq[kPipe ? (g & 1) : 0];
-        if constexpr (kPipe) {
-            if (g + 1 < NG) group_coords<LDS, WIN, WOUT, CSX, CSY, INTERP, PRE, V>(L, K, TG, in, g + 1, cq[(g + 1) & 1]);
-        } else {
-            group_coords<LDS, WIN, WOUT, CSX, CSY, INTERP, PRE, V>(L, K, TG, in, g, q);
-        }
-#if LUTR_T2_PHASES
+        GroupCrd &q = cq[0];
+        group_coords<LDS, WIN, WOUT, CSX, CSY, INTERP, PRE, V>(L, K, TG, in, g, q);
         __builtin_amdgcn_sched_barrier(0);
-#endif
         Rgb3 o[4];
 #pragma unroll
         for (int qb = 0; qb < 4; qb += TB) {
@@ -1305,28 +1089,16 @@ DEV void tile_body(const LutConsts &L, const YuvConsts &K_, const Win &W_, const
                 pc[t] = px_finish<LDS, INTERP, V>(L, W, q.r[qb + t], q.g[qb + t], q.b[qb + t]);
                 tp[t] = px_taps<LDS, INTERP, V>(L, W, pc[t]);
             }
-#if LUTR_T2_PHASES
             __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
             for (int t = 0; t < TB; t++) o[qb + t] = px_quant<INTERP, V>(L, px_blend<LDS, INTERP, V>(L, pc[t], tp[t]));
         }
         float rs[NCG], gs[NCG], bs[NCG];
-#if LUTR_T2_PK & 8
-        f2v rgs[NCG];               // chroma-block sums of R and G as a pair: one v_pk_add_f32 per pixel, same order of additions
-#endif
 #pragma unroll
         for (int p = 0; p < 4; p++) {
             const int dy = p / GW, i = g * GW + p % GW, c = (p % GW) >> CSX;
-#if LUTR_T2_PK & 8
-            const f2v orgp = {o[p].r, o[p].g};
-            if (dy == 0 && ((p % GW) & (T::BW - 1)) == 0) { rgs[c] = orgp; bs[c] = o[p].b; }
-            else { rgs[c] = rgs[c] + orgp; bs[c] += o[p].b; }
-            rs[c] = rgs[c].x; gs[c] = rgs[c].y;
-#else
             if (dy == 0 && ((p % GW) & (T::BW - 1)) == 0) { rs[c] = o[p].r; gs[c] = o[p].g; bs[c] = o[p].b; }
             else { rs[c] += o[p].r; gs[c] += o[p].g; bs[c] += o[p].b; }
-#endif
             wput<WOUT>(out.y[dy], i, ofloor<kDead>(fma_(K.cyr, o[p].r, fma_(K.cyg, o[p].g, fma_(K.cyb, o[p].b, K.yob))), K.max_o));
         }
 #pragma unroll
@@ -1335,14 +1107,6 @@ DEV void tile_body(const LutConsts &L, const YuvConsts &K_, const Win &W_, const
             wput<WOUT>(out.cb, j, ofloor<kDead>(fma_(K.cbr, rs[c], fma_(K.cbg, gs[c], fma_(K.cbb, bs[c], K.cob))), K.max_o));
             wput<WOUT>(out.cr, j, ofloor<kDead>(fma_(K.crr, rs[c], fma_(K.crg, gs[c], fma_(K.crb, bs[c], K.cob))), K.max_o));
         }
-#if LUTR_T2_FENCE_ALL
-        fence_words<T::YWI * T::BH>(&in.y[0][0]);
-        fence_words<T::CWI>(in.cb);
-        fence_words<T::CWI>(in.cr);
-        fence_words<T::YWO * T::BH>(&out.y[0][0]);
-        fence_words<T::CWO>(out.cb);
-        fence_words<T::CWO>(out.cr);
-#else
         // Only what is live anyway: the input words later groups still read (they cannot start before this point) and the
         // output words this group wrote (it cannot finish after it).  Fencing consumed input words or unborn output words
         // would keep 2 x 12 registers allocated through the whole tile.
@@ -1366,86 +1130,6 @@ DEV void tile_body(const LutConsts &L, const YuvConsts &K_, const Win &W_, const
 #pragma unroll
             for (int k = 0; k < T::CWO; k++) if (k >= c0 && k <= c1) { fence_words<1>(&out.cb[k]); fence_words<1>(&out.cr[k]); }
         }
-#endif
-    }
-}
-
-// ---------------------------------------------------------------- work distribution
-DEV bool chunk_at(const Geom &TG, unsigned c, int &fr, int &sx, int &ry, int &rem)
-{
-    if (c >= (unsigned)TG.nchunks) return false;
-    const int per_frame = TG.nrc * TG.nsx;
-    fr = (int)c / per_frame;
-    const int r = (int)c - fr * per_frame;
-    const int rc = r / TG.nsx;
-    sx = r - rc * TG.nsx;
-    ry = rc * TG.ch;
-    rem = min(TG.ch, TG.nry - ry);
-    return true;
-}
-
-// Every wave takes its first chunk by its id (a burst of atomics on one address at kernel start serialises in the L2).  After
-// that chunks come from a TWO-LEVEL queue: a wave draws a ticket from its workgroup's LDS counter (a ds_add_rtn, ~100 cycles on the
-// lgkm counter, the vector-memory pipeline keeps running); ticket 16 j + slot means chunk base[j] + slot, and the wave that draws
-// slot 0 fetches base[j] = atomicAdd(queue, 16) for the block and publishes it in LDS (the others of that block, if they arrive
-// before it has landed, spin on the ready tag -- all waves of a workgroup are resident, the publisher cannot be descheduled).  One
-// claim in sixteen pays the L2 round trip that round 2 paid on every claim (its phase timers: 9 % of a wave's time, with the memory
-// pipeline drained behind it), and the global counter sees a sixteenth of the traffic, so short launches can use smaller chunks.
-#ifndef LUTR_T2_QUEUE2
-#define LUTR_T2_QUEUE2 1
-#endif
-typedef __attribute__((address_space(3))) volatile unsigned *lds_vup;
-DEV bool claim_chunk(const Geom &TG, int lane, int wgq_off, int &fr, int &sx, int &ry, int &rem, bool &first)
-{
-    unsigned c = 0;
-    if (first) {
-        // (a wave whose id is not a chunk has no work at all: the counter starts behind the ids.  It must not touch the
-        // allocator's LDS words either -- this call runs before they are initialised.)
-        first = false;
-        c = (unsigned)((int)(blockIdx.x * LUTR_T2_WPB) + uni((int)(threadIdx.x >> 6)));
-        return chunk_at(TG, c, fr, sx, ry, rem);
-    }
-#if LUTR_T2_QUEUE2
-    const lds_vup q = (lds_vup)(uintptr_t)(unsigned)(lds_base() + wgq_off);
-    unsigned t = 0;
-    if (lane == 0) t = __hip_atomic_fetch_add((__attribute__((address_space(3))) unsigned *)q, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    t = (unsigned)uni((int)t);
-    const unsigned j = t >> 4, slot = t & 15u, r = j & 7u;
-    if (slot == 0) {
-        if (lane == 0) {
-            c = atomicAdd(TG.queue, 16u) + TG.qbase;
-            q[8 + r] = c;                                  // base[r]
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            q[16 + r] = j + 1u;                            // ready[r]
-        }
-        c = (unsigned)uni((int)c);
-    } else {
-        while ((unsigned)uni((int)q[16 + r]) != j + 1u) __builtin_amdgcn_s_sleep(2);
-        c = (unsigned)uni((int)q[8 + r]) + slot;
-    }
-#else
-    if (lane == 0) c = atomicAdd(TG.queue, 1u) + TG.qbase;
-    c = (unsigned)uni((int)c);
-#endif
-    return chunk_at(TG, c, fr, sx, ry, rem);
-}
-
-// Every wave calls this once, when it will claim no more: the last one puts the two words back to zero for the next launch.  (A wave's
-// claims have returned before it gets here -- it needed their values -- so the plain stores cannot overtake anybody's atomic.)
-DEV void queue_leave(const Geom &TG, int lane, int wgq_off)
-{
-    // two levels, like the claims: the waves of a workgroup count themselves out in LDS (word 24 of the allocator's block), the last one
-    // reports the workgroup -- 4096 atomics on one address at the end of a short launch cost it 15 us
-    if (lane == 0) {
-        const lds_vup q = (lds_vup)(uintptr_t)(unsigned)(lds_base() + wgq_off);
-        const unsigned left = __hip_atomic_fetch_add((__attribute__((address_space(3))) unsigned *)(q + 24), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (left == (unsigned)LUTR_T2_WPB - 1u) {
-            const unsigned done = atomicAdd(TG.queue + 1, 1u);
-            if (done == gridDim.x - 1u) {
-                __hip_atomic_store(TG.queue, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(TG.queue + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
     }
 }
 
@@ -1458,19 +1142,21 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
     // mixed tiles: the strict kernels (see the vote below); not trilinear with the prologue, whose body has no register left for the
     // lanes' verdict (it spilled three VGPRs to scratch inside the body)
     // (likewise 8-bit 4:4:4 trilinear: eight spilled registers, and fma32 trilinear: three in the headline layout)
-    constexpr bool kMixed = LUTR_T2_MIXED && (V != V_FAST || LUTR_T2_MIXED_FAST) &&
+    // (mixed tiles for the fast kernels too, measured behind a build switch: sigma-16 frames 512 -> 537 Gpx/s, natural 662 -> 655,
+    // saturated 530 -> 522, 10 more VGPRs: profiles/r03_exp34_mixed_tiles_fast_kernels.txt)
+    constexpr bool kMixed = V != V_FAST &&
                             !(INTERP == LUTR_INTERP_TRILINEAR && (PRE || (!WIN && !CSX) || V == V_FMA32));
     LutConsts L = L_;
     YuvConsts K = K_;
     // a wave-uniform constant used by several VALU ops per pixel is worth a VGPR (an SGPR operand halves the issue rate
     // of plain fp32 ops on gfx950, tools/ubench); the trilinear bodies have no registers to spare
-    if constexpr (INTERP != LUTR_INTERP_TRILINEAR && LUTR_T2_PIN >= 1) {
+    if constexpr (INTERP != LUTR_INTERP_TRILINEAR) {
         K.cyr = in_vgpr(K_.cyr); K.cyg = in_vgpr(K_.cyg); K.cyb = in_vgpr(K_.cyb);
-        if constexpr (LUTR_T2_PIN >= 2) { K.ky = in_vgpr(K_.ky); K.yb = in_vgpr(K_.yb); K.yob = in_vgpr(K_.yob); }
+        K.ky = in_vgpr(K_.ky); K.yb = in_vgpr(K_.yb); K.yob = in_vgpr(K_.yob);
         if constexpr (!N::fast) L.maxf = in_vgpr(L_.maxf);
     }
     if (lds_base() != 0) __builtin_trap();        // crd_table8 addresses the table absolutely
-#if LUTR_T2_KARG && defined(__HIP_DEVICE_COMPILE__)
+#ifdef __HIP_DEVICE_COMPILE__
     {   // pos_at reads the plane descriptors from the kernel-argument segment at the offset a struct of the parameters gives them:
         // make sure that IS where they are before any address is built from them
         struct KernArgsChk { LutConsts L; YuvConsts K; Planes2 P; FrameGeom G; Geom TG; };
@@ -1494,17 +1180,16 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
     const int tube_off = tab_bytes + kScratch;
     const int slice_off = tube_off + tube_nodes * N::lds + wib * TG.win_nodes * N::lds;
     Win Wt;                                                   // the tube as a window: same address form as a staged one
-    // index = pr * plane + (pg - pr + H + 1) * nb + (pb - pg + H + 1)   [(pb - pr + H + 1) without LUTR_T2_TUBE_BG]
-    if (LUTR_T2_TUBE_BG) { Wt.o_g = N::lds * (tube_nb - 1); Wt.o_r = N::lds * (TG.tube_plane - tube_nb); }
-    else { Wt.o_g = N::lds * tube_nb; Wt.o_r = N::lds * (TG.tube_plane - tube_nb - 1); }
+    // index = pr * plane + (pg - pr + H + 1) * nb + (pb - pg + H + 1)
+    Wt.o_g = N::lds * (tube_nb - 1); Wt.o_r = N::lds * (TG.tube_plane - tube_nb);
     Wt.fr = (float)Wt.o_r; Wt.fg = (float)Wt.o_g; Wt.fb = (float)N::lds;
     Wt.fc = (float)(lds_base() + tube_off + N::lds * ((TG.tube_h + 1) * tube_nb + TG.tube_h + 1));
     unsigned st_tube = 0, st_mixed = 0;
     int fr, sx, ry, rem;                                      // the tile being fetched next
     bool first = true;
     const int wgq_off = tab_bytes + kWaveScratch;             // the workgroup's chunk allocator (claim_chunk)
-    if (threadIdx.x < 24) ((unsigned *)(smem + wgq_off))[threadIdx.x + (threadIdx.x ? 7 : 0)] = 0u;      // ticket, base[8], ready[8]
-    const bool have_work = claim_chunk(TG, lane, wgq_off, fr, sx, ry, rem, first);      // (no atomic: a wave's first chunk is its id)
+    if (threadIdx.x < 24) ((unsigned *)(smem + wgq_off))[threadIdx.x + (threadIdx.x ? 7 : 0)] = 0u;      // queue words 0, 8..30 (lutr_tube.h)
+    const bool have_work = claim_chunk<LUTR_T2_WPB>(TG, lane, lds_base(), wgq_off, fr, sx, ry, rem, first);      // (no atomic: a wave's first chunk is its id)
     const int lw = 1 << TG.lw_log2, lh_log2 = 6 - TG.lw_log2;
     const int lx = lane & (lw - 1), ly = lane >> TG.lw_log2;
     const int cr0 = G.row0 >> CSY;                            // first unit row of this call's row range
@@ -1534,10 +1219,11 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
                    ystep_d2 = (unsigned)((int)P.ds[2] << lh_log2);
     // The plane bases and frame strides (24 SGPRs) are only needed here, once per chunk: read them from the kernel-argument
     // segment when they are, instead of keeping them resident (and spilled to VGPR lanes) through every tile
-    // (SGPR spills of the headline kernel 101 -> 82; the layout assumption is checked at kernel start).
+    // (SGPR spills of the headline kernel 101 -> 82, profiles/r03_exp39_strides_from_kernarg.txt; the layout assumption is checked at
+    // kernel start).
     auto pos_at = [&](int f, int tsx, int try_) {
         TilePos q;
-#if LUTR_T2_KARG && defined(__HIP_DEVICE_COMPILE__)
+#ifdef __HIP_DEVICE_COMPILE__
         struct KernArgs { LutConsts L; YuvConsts K; Planes2 P; FrameGeom G; Geom TG; };   // the kernel's parameter list
         typedef const __attribute__((address_space(4))) Planes2 *PlanesK;
         PlanesK Pk = (PlanesK)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(KernArgs, P));
@@ -1611,7 +1297,7 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
         __syncthreads();
     }
     if (TG.tube_h > 0) {
-        // node (ir, ig, ib) = lattice (r, g = r + ig - H - 1, b = g + ib - H - 1) [b = r + ib - H - 1 without LUTR_T2_TUBE_BG], clamped
+        // node (ir, ig, ib) = lattice (r, g = r + ig - H - 1, b = g + ib - H - 1), clamped
         // (a clamped node is never read by a valid pixel)
         char *dst = smem + TG.tab_entries * 8 + kScratch;
         const int plane = TG.tube_plane, nmax = L.n1 - 1;
@@ -1624,7 +1310,7 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
                 const int i = min(base + k * 64 * LUTR_T2_WPB, tube_nodes - 1);
                 const int ir = i / plane, rem = i - ir * plane, ig = min(rem / tube_nb, tube_nb - 1), ib = rem - ig * tube_nb;   // (padding: any node)
                 const int gq = ir + ig - TG.tube_h - 1;
-                const int g = min(max(gq, 0), nmax), b = min(max((LUTR_T2_TUBE_BG ? gq : ir) + ib - TG.tube_h - 1, 0), nmax);
+                const int g = min(max(gq, 0), nmax), b = min(max(gq + ib - TG.tube_h - 1, 0), nmax);
                 src[k] = (ir * L.n1 + g) * L.n1 + b;
                 src1[k] = (min(ir + 1, nmax) * L.n1 + g) * L.n1 + b;
             }
@@ -1648,7 +1334,7 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
         __syncthreads();
     }
     __syncthreads();                          // (the allocator's LDS words are initialised; the general variant has no other barrier)
-    if (!have_work) { queue_leave(TG, lane, wgq_off); return; }      // (after the barriers above: every wave of the workgroup takes part in the staging)
+    if (!have_work) { queue_leave<LUTR_T2_WPB>(TG, lane, lds_base(), wgq_off); return; }      // (after the barriers above: every wave of the workgroup takes part in the staging)
 
     for (bool more = true; more;) {
         TileIn<WIN, WOUT, CSX, CSY> in = nxt;
@@ -1658,19 +1344,15 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
         // fetched again, so every path has the same number of memory operations in flight.
         if (--rem > 0) { ry++; pos_down(np); }
         else {
-            more = claim_chunk(TG, lane, wgq_off, fr, sx, ry, rem, first);
+            more = claim_chunk<LUTR_T2_WPB>(TG, lane, lds_base(), wgq_off, fr, sx, ry, rem, first);
             if (more) np = pos_at(fr, sx, ry);
         }
         load_tile(nxt, np);
-#if LUTR_T2_PRIO == 1
+        // s_setprio around the phases of a tile: a wave between its body and the next one -- stores, chunk claim, the next tile's
+        // loads -- goes first, so memory operations leave as early as they can (strict 587-589 -> 593 Gpx/s, fast +0.1 %; the body
+        // first instead: -1.7 %; profiles/r03_exp22_setprio.txt)
         __builtin_amdgcn_s_setprio(0);
-#elif LUTR_T2_PRIO == 2
-        __builtin_amdgcn_s_setprio(3);
-#endif
 
-#ifndef LUTR_T2_EXP
-#define LUTR_T2_EXP 0             // timing experiments only (wrong pixels): 1 = trust the first window forever, 2 = + no stores, 3 = no body, 5.. = body repeated
-#endif
 #ifdef LUTR_T2_DEBUG_STATS
         TK(tk_store)                 // issuing the next tile's loads counts as store/loop time
         fence_words<T::YWI * T::BH>(&in.y[0][0]); fence_words<T::CWI>(in.cb); fence_words<T::CWI>(in.cr);
@@ -1690,7 +1372,7 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
                 // legal, but outside the interval: the bound itself.  Per sample for the strict kernels (their tube is 6 cells wide:
                 // sigma = 16 frames +9 %, natural -0.8 %, 3 x chroma -1.5 %); the fast kernels' 8-cell tube gains 1.7 % there and loses
                 // 1.4 % on 3 x chroma: corner form
-                if constexpr (T::NC <= 4 && V != V_FAST && LUTR_T2_TUBE_SAMPLES)
+                if constexpr (T::NC <= 4 && V != V_FAST)
                     lane_in = tube_holds_samples<WIN, WOUT, CSX, CSY, PRE>(K, TG, in);
                 else lane_in = tube_holds<WIN, PRE>(K, TG, e);
                 use_tube = __all(lane_in);
@@ -1709,7 +1391,6 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
             e.ymin = luma_min<WIN, WOUT, CSX, CSY>(in);
             use_lds = box_holds(scratch_off, e);               // first level: raw extremes against the window's raw box
         }
-        if (LUTR_T2_EXP >= 1 && have_win) use_lds = true;
         TK(tk_head)
         st_tiles++;
         if (TG.whole) {
@@ -1775,23 +1456,8 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
             }
         }
         TileOut<WIN, WOUT, CSX, CSY> out;
-        if (LUTR_T2_EXP == 3) {
-#pragma unroll
-            for (int dy = 0; dy < T::BH; dy++)
-#pragma unroll
-                for (int k = 0; k < T::YWO; k++) out.y[dy][k] = in.y[dy][k % T::YWI];
-#pragma unroll
-            for (int k = 0; k < T::CWO; k++) { out.cb[k] = in.cb[k % T::CWI]; out.cr[k] = in.cr[k % T::CWI]; }
-        } else
         if (use_lds) {
             tile_body<true, WIN, WOUT, CSX, CSY, INTERP, PRE, V>(L, KB, (use_tube || mixed) ? Wt : W, TG, in, out); TK(tk_body)
-            if constexpr (LUTR_T2_EXP >= 5) {      // the body again, EXP - 4 times, on inputs the compiler cannot tell are the same
-#pragma unroll 1
-                for (int rep = 0; rep < LUTR_T2_EXP - 4; rep++) {
-                    fence_words<T::YWI * T::BH>(&in.y[0][0]); fence_words<T::CWI>(in.cb); fence_words<T::CWI>(in.cr);
-                    tile_body<true, WIN, WOUT, CSX, CSY, INTERP, PRE, V>(L, KB, W, TG, in, out);
-                }
-            }
         }
         bool gather = !use_lds;                      // whole tiles (wave-uniform) ...
         if constexpr (kMixed) gather = gather || (mixed && !lane_in);     // ... or the outliers of a mixed tile (divergent)
@@ -1799,22 +1465,16 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
             tile_body<false, WIN, WOUT, CSX, CSY, INTERP, PRE, V>(L, KB, W, TG, in, out); TK(tk_gath)
         }
         if (!use_lds) T2_COUNT(8);
-#if LUTR_T2_PRIO == 1
         __builtin_amdgcn_s_setprio(3);      // stores, the queue and the next tile's loads go first
-#elif LUTR_T2_PRIO == 2
-        __builtin_amdgcn_s_setprio(0);
-#endif
         {
             // Idle lanes of edge tiles processed a duplicate of a valid unit of this tile (load_tile clamps), so they
             // store the same bytes to the same place as its owner: no branch, fixed store count.
             const unsigned lxc = (unsigned)min(lx, cp.xlim), lyc = (unsigned)min(ly, cp.ylim);
             const unsigned y0 = __umul24(lyc * T::BH, P.ds[0]) + lxc * YOB;
-            if (LUTR_T2_EXP != 2 || out.cb[0] == 0x12345u) {
 #pragma unroll
             for (int dy = 0; dy < T::BH; dy++) stw<T::YWO>(cp.d0 + (y0 + dy * P.ds[0]), out.y[dy]);
             stw<T::CWO>(cp.d1 + (__umul24(lyc, P.ds[1]) + lxc * COB), out.cb);
             stw<T::CWO>(cp.d2 + (__umul24(lyc, P.ds[2]) + lxc * COB), out.cr);
-            }
         }
         TK(tk_store)
     }
@@ -1824,7 +1484,7 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
         atomicAdd(&TG.stats[11], tk_wait >> 4); atomicAdd(&TG.stats[8], tk_body >> 4); atomicAdd(&TG.stats[9], tk_gath >> 4); atomicAdd(&TG.stats[10], tk_store >> 4);
     }
 #endif
-    queue_leave(TG, lane, wgq_off);
+    queue_leave<LUTR_T2_WPB>(TG, lane, lds_base(), wgq_off);
     if (TG.stats && lane == 0) {
         atomicAdd(&TG.stats[0], st_tiles); atomicAdd(&TG.stats[1], cnt[1]);
         atomicAdd(&TG.stats[2], cnt[8]); atomicAdd(&TG.stats[3], cnt[9]); atomicAdd(&TG.stats[6], cnt[0]);
@@ -1849,32 +1509,6 @@ int table_entries(const YuvConsts &K, int din)
     return ((int)top + 3) & ~1;           // even: the window slices behind the table stay 16-byte aligned (ds_read_b128)
 }
 
-// Nodes between two r planes of the tube.  The lanes of a wave read cells that are mostly one step apart (neighbouring pixels):
-// with node index = pr * A + pg * B + pb two of them collide in the LDS banks when dr * A + dg * B + db is a multiple of 32 (a tap
-// read is 32 lanes per pass, the bank is the dword address mod 32 or 64, node strides of 2 or 3 dwords are invertible mod 32).
-// The unpadded 15 x 15 and 17 x 17 planes of the strict kernels' tubes have exactly that for (dr, dg) = +-(1, 1): every luma step
-// that moves r and g but not b costs a second LDS pass.  A few nodes of padding per plane remove it.
-int tube_plane_stride(int nb, int node)
-{
-    // 16-byte nodes are read with ds_read_b128: 16 lanes per pass, bank = dword address mod 64, a node is four dwords -- two lanes
-    // collide when their node indices agree mod 16 (not 32)
-    const int mod = node == 16 ? 16 : 32;
-    int best = nb * nb, best_bad = 1 << 30;
-    for (int pad = 0; pad < 12; pad++) {
-        const int plane = nb * nb + pad;
-        const int A = LUTR_T2_TUBE_BG ? plane - nb : plane - nb - 1, B = LUTR_T2_TUBE_BG ? nb - 1 : nb;
-        int bad = 0;
-        for (int dr = -2; dr <= 2; dr++)
-            for (int dg = -2; dg <= 2; dg++)
-                for (int db = -2; db <= 2; db++) {
-                    if (!dr && !dg && !db) continue;
-                    if (((dr * A + dg * B + db) % mod + mod) % mod == 0) bad += (abs(dr) <= 1 && abs(dg) <= 1 && abs(db) <= 1) ? 100 : 1;
-                }
-        if (bad < best_bad) { best_bad = bad; best = plane; }
-        if (!bad) break;
-    }
-    return best;
-}
 bool out_clip_dead(const YuvConsts &K, int chroma_n)
 {
     const float m = K.max_l, mn = K.max_l * (float)chroma_n;
@@ -1888,10 +1522,6 @@ bool out_clip_dead(const YuvConsts &K, int chroma_n)
 
 }  // namespace
 
-#ifndef LUTR_T2_ONLY
-#define LUTR_T2_ONLY 0      // 1: build the headline instance alone (development)
-#endif
-
 // The LUTR_* tuning knobs of this launcher (tools/ only) are read ONCE per process: round 2 called getenv a dozen times per
 // launch, which a stream of single-frame applies pays every time (bench.py host_us_per_apply).
 namespace {
@@ -1903,31 +1533,6 @@ struct Knob {
 };
 #define T2_KNOB(NAME) ([]() -> const Knob & { static const Knob k(NAME); return k; }())
 }  // namespace
-
-// Whole-lattice mode: node (r, g, b) sits at index r * A + g * B + b.  With A = n1^2, B = n1 neighbouring cells collide in the LDS
-// banks for unlucky sizes (n1 = 20: A = 400 = 0 mod 16 -- every step along r lands in the same bank group of a ds_read_b128).  A few
-// nodes of padding per row and per plane remove that, as tube_plane_stride does for the tube.  Returns the bytes, or 0 if no layout fits.
-static long long whole_strides(int n1, int node, long long room, int *A, int *B)
-{
-    const int mod = node == 16 ? 16 : 32;
-    long long best_bytes = 0;
-    int best_bad = 1 << 30;
-    for (int pb = 0; pb < 4; pb++)
-        for (int pa = 0; pa < 16; pa++) {
-            const int b = n1 + pb, a = n1 * b + pa;
-            const long long bytes = (long long)n1 * a * node;
-            if (bytes > room) continue;
-            int bad = 0;
-            for (int dr = -2; dr <= 2; dr++)
-                for (int dg = -2; dg <= 2; dg++)
-                    for (int db = -2; db <= 2; db++) {
-                        if (!dr && !dg && !db) continue;
-                        if (((dr * a + dg * b + db) % mod + mod) % mod == 0) bad += (abs(dr) <= 1 && abs(dg) <= 1 && abs(db) <= 1) ? 100 : 1;
-                    }
-            if (bad < best_bad || (bad == best_bad && bytes < best_bytes)) { best_bad = bad; best_bytes = bytes; *A = a; *B = b; }
-        }
-    return best_bytes;
-}
 
 // The tube's chroma bound under a shared prelut (LutConsts::pre_shared).  FFmpeg resamples a cineSpace shaper WITHOUT normalising the
 // interpolation weight by the segment width (parse_cinespace: `mix = x - in_prelut[idx]`), so the curve lut3d applies is a staircase:
@@ -2015,15 +1620,13 @@ const char *T2_ENTRY(hipStream_t st, const LutConsts &L, const YuvConsts &K, con
     const int tile_px = pxt * (1 << csy) * 64;
     int ch = (4096 + tile_px - 1) / tile_px;
     if ((long long)G.nframes * tg.nsx * tg.nry < 64ll * max_waves) ch = (2048 + tile_px - 1) / tile_px;
-    if (!LUTR_T2_QUEUE2) { ch = 32 / (64 >> best); if (ch * tile_px < 8192) ch = (8192 + tile_px - 1) / tile_px; }
     if (ch < 1) ch = 1;
     if (const Knob &e = T2_KNOB("LUTR_CHUNK")) { const int c = e.num(); if (c >= 1 && c <= 256) ch = c; }
     while (ch > 1 && (long long)G.nframes * tg.nsx * ((tg.nry + ch - 1) / ch) < max_waves / 4) ch >>= 1;
     tg.ch = ch; tg.nrc = (tg.nry + ch - 1) / ch; tg.nchunks = G.nframes * tg.nrc * tg.nsx;
     tg.tab_entries = vv >= V_TAB ? table_entries(K, din) : 0;
     tg.max_raw = (1 << din) - 1;
-    const int node_ = vv == V_FAST ? ((LUTR_T2_TRIREC && mode == LUTR_INTERP_TRILINEAR) ? 12 : 8)
-                                   : ((mode == LUTR_INTERP_TRILINEAR || LUTR_T2_NODE16) ? 16 : 12);
+    const int node_ = vv == V_FAST ? (mode == LUTR_INTERP_TRILINEAR ? 12 : 8) : (mode == LUTR_INTERP_TRILINEAR ? 16 : 12);      // Node::lds
     const int blocks_per_cu = waves_per_cu / LUTR_T2_WPB > 0 ? waves_per_cu / LUTR_T2_WPB : 1;
     const int lds_block = 163840 / blocks_per_cu - tg.tab_entries * 8 - t2::kScratch;
     // whole-lattice mode: (N+1)^3 nodes behind the table in one workgroup's LDS, row and plane strides padded against bank conflicts.
@@ -2093,7 +1696,7 @@ const char *T2_ENTRY(hipStream_t st, const LutConsts &L, const YuvConsts &K, con
         // the square |cb' - coff|, |cr' - coff| <= R (after the prologue) inside the tube's chroma region: both differences are linear in
         // the two offsets, so their worst corners bound them; 1 % and one code of margin absorb the float rounding of the per-lane form
         const float s1 = fabsf(K.kgu) + fabsf(K.kgv - K.krv);
-        const float s2 = LUTR_T2_TUBE_BG ? fabsf(K.kbu - K.kgu) + fabsf(K.kgv) : fabsf(K.kbu) + fabsf(K.krv);
+        const float s2 = fabsf(K.kbu - K.kgu) + fabsf(K.kgv);
         const float R = floorf(0.99f * tg.tube_t / fmaxf(s1, s2)) - 1.0f;
         // (one entry of memory: a stream of applies repeats the same constants, and the scan is up to 65,536 codes long)
         struct Memo { float pre, pc, pcb, pre_max, coff, R; int max_raw, lo, hi; };
@@ -2165,13 +1768,9 @@ const char *T2_ENTRY(hipStream_t st, const LutConsts &L, const YuvConsts &K, con
         if (vv == V_TAB) T2_LAUNCH(WI, WO, X, Y, I, 0, V_TAB, T2_NAME(WI, WO, X, Y, I, ",tab")); \
         T2_LAUNCH(WI, WO, X, Y, I, 0, V_GEN, T2_NAME(WI, WO, X, Y, I, "")); \
     }
-#if LUTR_T2_ONLY
-    T2_CASE(LUTR_T2_WI, LUTR_T2_WO, LUTR_T2_X, LUTR_T2_Y, 2)
-#else
     T2_CASE(LUTR_T2_WI, LUTR_T2_WO, LUTR_T2_X, LUTR_T2_Y, 0)
     T2_CASE(LUTR_T2_WI, LUTR_T2_WO, LUTR_T2_X, LUTR_T2_Y, 1)
     T2_CASE(LUTR_T2_WI, LUTR_T2_WO, LUTR_T2_X, LUTR_T2_Y, 2)
-#endif
     return nullptr;
 }
 

@@ -1,6 +1,7 @@
 #!/bin/bash
 # tools/exp_build.sh NAME [-D...]: experimental liblutr_NAME.so whose headline tile kernels (10-bit 4:2:0) are compiled with
-# extra flags (the LUTR_T2_* knobs of lutr_tile2.hip).  Run with LUTR_LIBRARY=lut_renderer_amd/lib/liblutr_NAME.so.
+# extra flags.  The -D switches lutr_tile2.hip still has: LUTR_T2_WPB, LUTR_T2_WAVES_PER_EU, LUTR_T2_DEBUG_STATS (the settled experiment
+# switches were removed from the source; git history has them).  Run with LUTR_LIBRARY=lut_renderer_amd/lib/liblutr_NAME.so.
 set -e
 NAME=$1; shift
 cd "$(dirname "$0")/../lut_renderer_amd/csrc"

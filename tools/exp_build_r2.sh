@@ -1,6 +1,7 @@
 #!/bin/bash
 # tools/exp_build_r2.sh NAME [-D...]: experimental liblutr_NAME.so whose RGB tube kernels (lutr_rgb2.hip, every layout) are compiled
-# with extra flags (the LUTR_R2_* knobs).  Run with LUTR_LIBRARY=lut_renderer_amd/lib/liblutr_NAME.so.
+# with extra flags.  The one -D switch lutr_rgb2.hip still has is LUTR_R2_WPB (the settled experiment switches were removed from the
+# source; git history has them).  Run with LUTR_LIBRARY=lut_renderer_amd/lib/liblutr_NAME.so.
 set -e
 NAME=$1; shift
 cd "$(dirname "$0")/../lut_renderer_amd/csrc"

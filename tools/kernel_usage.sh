@@ -1,6 +1,7 @@
 #!/bin/bash
 # tools/kernel_usage.sh [-D...]: registers / spills / scratch of the headline tile kernels (10-bit 4:2:0) as the compiler reports them
-# (-Rpass-analysis=kernel-resource-usage), for a set of LUTR_T2_* flags.  CPU only (hipcc cross-compiles).
+# (-Rpass-analysis=kernel-resource-usage).  WI= WO= CX= CY= select the object; extra -D flags are passed on (lutr_tile2.hip still has
+# LUTR_T2_WPB, LUTR_T2_WAVES_PER_EU and LUTR_T2_DEBUG_STATS).  CPU only (hipcc cross-compiles).
 cd "$(dirname "$0")/../lut_renderer_amd/csrc"
 FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-honor-nans -fno-slp-vectorize -w --offload-arch=gfx950 -I../../include -I."
 mkdir -p build/exp
