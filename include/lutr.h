@@ -374,6 +374,44 @@ int lutr_apply_planar_rgb_f32(lutr_ctx *ctx, int interp, int w, int h, int nfram
 int lutr_apply_rgbf_to_yuv(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int dither, int w, int h, int nframes,
                            const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
 
+/* ---- semi-planar YUV frames: nv12 / nv21 / nv16 and p010le / p012le / p016le / p210le / p212le / p216le, what
+ *      hardware decoders write and hardware encoders read -- the frame the reference's chain (ffmpeg.py:246, :304-310) sees after
+ *      FFmpeg's scaler has unpacked it ---- */
+/* The container of one side of lutr_apply_yuv_semi.
+ *   semi  = 0: three planes, as lutr_apply_yuv takes them.
+ *   semi  = 1: data[0] is luma; data[1] holds ceil(w / 2) pairs of chroma samples per row, ceil(h / 2) rows for 4:2:0 and h
+ *              rows for 4:2:2, with stride[1] / frame_stride[1] in bytes; data[2] is ignored and may be NULL.
+ *   swap  = 1: Cr comes first in a pair (nv21).  Only with semi = 1.
+ *   shift    : left shift of the code inside its 16-bit word, 16 - depth (p010le: 6) or 0; always 0 for an 8-bit container.
+ *              On input the code is word >> shift whatever the low bits hold; on output the low bits are zero. */
+typedef struct lutr_yuv_layout {
+    int32_t semi;
+    int32_t swap;
+    int32_t shift;
+} lutr_yuv_layout;
+
+/* lutr_apply_yuv on frames whose source side, destination side or both are semi-planar; each side's container is its own.  The
+ * result is bit-identical to lutr_apply_yuv on the same samples held in three planes: everything *p expresses (depth change,
+ * the full-range prologue, matrices, ranges, lut_depth) and a .csp prelut are that call's arithmetic unchanged.
+ * fmt_in and fmt_out must have the same chroma subsampling, 4:2:0 or 4:2:2 when a side is semi-planar.  Row blocks follow the
+ * rule of lutr_apply_yuv.  When both layouts are planar with shift 0 this IS lutr_apply_yuv: same kernels, bits, last kernel.
+ * src == dst plane for plane (in place) is allowed when both sides have the same format; nothing else about overlap is checked.
+ * Always strict precision otherwise (fast / fma32 run strict here, no suffix on the last kernel).
+ * LUTR_EINVAL with a message, before anything touches the device: a shift other than 16 - depth or 0 on a 16-bit container, a
+ * non-zero shift on an 8-bit one, swap without semi, semi / swap outside 0 | 1, a semi-planar side that is 4:4:4, a null pointer
+ * where a plane is needed, 16-bit planes whose base, stride or (batches) frame stride is odd.
+ * Kernels: "k_yuv_semi_vec<win,wout,semi_in,semi_out,csx,csy,interp>" (nearest / trilinear / tetrahedral; 8 -> 8, 16 -> 16 and
+ * 16 -> 8 bit containers; at least one side semi-planar; width a multiple of 8 luma samples, 4 for 16 -> 16; positive strides
+ * aligned to the accesses -- a plane of pairs moves twice the bytes of a planar chroma plane per access; row0 / rows multiples
+ * of the chroma block height), "k_yuv_semi_generic" for everything else (one thread per chroma block; any depth 8..16, stride,
+ * alignment or size; all five modes); a ragged width on aligned rows is split between the two.  Variants: auto and generic as
+ * for lutr_apply_yuv; vec_global fails with LUTR_EINVAL where the vector kernel cannot take the layout; vec_lds always fails
+ * with LUTR_EINVAL (there is no LDS kernel for this path).
+ * Not covered: a subsampling change, chroma siting, dither, 4:4:4 semi-planar (nv24, p410le), big-endian containers. */
+int lutr_apply_yuv_semi(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, const lutr_yuv_layout *in_layout,
+                        const lutr_yuv_layout *out_layout, int w, int h, int nframes, const lutr_planes *src,
+                        const lutr_planes *dst, int row0, int rows);
+
 /* ---- precision ---- */
 /* STRICT (default): every kernel is a bit-exact restatement of FFmpeg's scalar C lut3d (vf_lut3d.c order of operations,
  * no fused multiply-add in the blend).  FAST: permission to use the tolerance-bounded tile kernels -- lattice staged as

@@ -40,7 +40,7 @@ SYMBOLS = (
     "lutr_apply_planar_rgb", "lutr_apply_packed_rgb", "lutr_apply_yuv", "lutr_apply_yuv_dither",
     "lutr_apply_yuv_sited", "lutr_yuv_constants_sited", "lutr_apply_yuv_xsub", "lutr_yuv_constants_xsub",
     "lutr_apply_rgb_to_yuv", "lutr_yuv_constants_rgb2yuv",
-    "lutr_apply_planar_rgb_f32", "lutr_apply_rgbf_to_yuv",
+    "lutr_apply_planar_rgb_f32", "lutr_apply_rgbf_to_yuv", "lutr_apply_yuv_semi",
     "lutr_resize_filter", "lutr_resize_planes",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
 )
@@ -62,6 +62,11 @@ class Planes(C.Structure):
     _fields_ = [("data", C.c_void_p * 3), ("stride", C.c_ssize_t * 3), ("frame_stride", C.c_int64 * 3)]
 
 
+class YuvLayout(C.Structure):
+    """struct lutr_yuv_layout: the container of one side of lutr_apply_yuv_semi"""
+    _fields_ = [("semi", C.c_int32), ("swap", C.c_int32), ("shift", C.c_int32)]
+
+
 class Packed(C.Structure):
     """struct lutr_packed"""
     _fields_ = [("data", C.c_void_p), ("stride", C.c_ssize_t), ("frame_stride", C.c_int64)]
@@ -79,6 +84,14 @@ PACKED_FORMATS = {
     "argb": (8, 4, 1, 2, 3), "0rgb": (8, 4, 1, 2, 3), "abgr": (8, 4, 3, 2, 1), "0bgr": (8, 4, 3, 2, 1),
     "rgb48le": (16, 3, 0, 1, 2), "bgr48le": (16, 3, 2, 1, 0),
     "rgba64le": (16, 4, 0, 1, 2), "bgra64le": (16, 4, 2, 1, 0),
+}
+
+
+#: semi-planar YUV formats -> (depth, csx, csy, swap: Cr first, shift of the code inside its container)
+SEMI_FORMATS = {
+    "nv12": (8, 1, 1, 0, 0), "nv21": (8, 1, 1, 1, 0), "nv16": (8, 1, 0, 0, 0),
+    "p010le": (10, 1, 1, 0, 6), "p012le": (12, 1, 1, 0, 4), "p016le": (16, 1, 1, 0, 0),
+    "p210le": (10, 1, 0, 0, 6), "p212le": (12, 1, 0, 0, 4), "p216le": (16, 1, 0, 0, 0),
 }
 
 
@@ -148,6 +161,8 @@ def load() -> C.CDLL:
     lib.lutr_apply_planar_rgb_f32.argtypes = [vp, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_apply_rgbf_to_yuv.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes),
                                            ci, ci]
+    lib.lutr_apply_yuv_semi.argtypes = [vp, C.POINTER(YuvParams), ci, C.POINTER(YuvLayout), C.POINTER(YuvLayout), ci, ci, ci,
+                                        C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]
     lib.lutr_ctx_set_variant.argtypes = [vp, ci]

@@ -79,7 +79,8 @@ def _cached_cube(path: Path) -> CubeLut:
 
 
 def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = None) -> dict:
-    """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv -- or, for an RGB `pix_fmt` (gbrp* / a packed name / a
+    """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv (`pix_fmt` / `out_pix_fmt` planar YUV or semi-planar names
+    such as nv12 / p010le; `out_pix_fmt` defaults to the source's own format) -- or, for an RGB `pix_fmt` (gbrp* / a packed name / a
     float name) with a YUV `out_pix_fmt`, of LutEngine.apply_rgb_to_yuv (`is_rgb_call(kw)` tells the two apart).  A float
     `pix_fmt` (gbrpf32le / gbrapf32le) without `out_pix_fmt`, or with a float one, stays float:
     `is_float_out_call(kw)`, and LutEngine.apply_rgb_float takes `kw["interp"]`."""
@@ -115,7 +116,10 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
             # scale=in_range=pc:out_range=R, format=yuv4xxp (8 bit) AHEAD of lut3d: the two-stage composition of 3.9 point 6
             kw.update(intermediate_pix_fmt=plan.intermediate_pix_fmt, prologue_out_range=plan.prologue_out_range)
         return kw
-    src = parse_pix_fmt(pix_fmt)
+    # a semi-planar source or output (nv12, p010le, ..) is the same chain on another container
+    from .engine import check_semi_options, parse_semi_fmt
+    semi_src = parse_semi_fmt(pix_fmt)
+    src = semi_src or parse_pix_fmt(pix_fmt)
     if src.family != "yuv":
         raise ValueError("apply_lut takes planar YUV frames; use LutEngine.apply_rgb for gbrp planes")
     if out_pix_fmt and parse_rgb_source(out_pix_fmt) is not None:
@@ -127,11 +131,13 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
     if plan.prologue:
         # scale=in_range=pc:out_range=R , format=yuv4xxp (8 bit): the LUT then runs at 8 bit
         kw.update(range_src="pc", range_in=plan.prologue_out_range, lut_depth=8)
-        default_out = plan.intermediate_pix_fmt
+        # (the plan reads the subsampling off a yuv4xx name; a semi-planar source names its planar 8-bit twin itself)
+        default_out = plan.intermediate_pix_fmt if semi_src is None else f"yuv{'420' if semi_src.csy else '422'}p"
     else:
         kw.update(range_src="tv", range_in="tv", lut_depth=src.depth)
         default_out = kw["pix_fmt"]
     kw["out_pix_fmt"] = out_pix_fmt or default_out
+    check_semi_options(kw["pix_fmt"], kw["out_pix_fmt"])         # one subsampling on both sides of a semi-planar call
     return kw
 
 
@@ -155,7 +161,9 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               devices: Sequence[int] = (0,), precision: str = "strict", chroma_loc: Optional[str] = None,
               resolution: Optional[str] = None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
-    engine's device, each [H,W] or [F,H,W].  With an RGB `pix_fmt` (gbrp* or a packed name such as rgb24) and a YUV
+    engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
+    3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
+    chroma_loc or resolution.  With an RGB `pix_fmt` (gbrp* or a packed name such as rgb24) and a YUV
     `out_pix_fmt` (required then), `planes` is the three gbrp planes (G, B, R) or the one [F,]H,W,C packed tensor and the
     chain is lut3d on the RGB frame, then RGB -> YUV.  `pix_fmt` = gbrpf32le / gbrapf32le takes float32 planes
     (DESIGN.md 3.10): with a YUV `out_pix_fmt` the same chain, without one (or with a float one) float planes come back, an alpha
@@ -207,7 +215,9 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         raise ValueError("plane shape does not match width/height")
     params = ProcessingParams(lut_interp=interp, lut_input_matrix=input_matrix, lut_output_tags=output_tags,
                               zscale_dither=zscale_dither)
-    info = VideoInfo(width=width, height=height, pix_fmt=pix_fmt, bit_depth=infer_bit_depth(pix_fmt),
+    from .engine import parse_semi_fmt
+    semi = parse_semi_fmt(pix_fmt)              # (p010le: the digits after the 'p' are not a depth)
+    info = VideoInfo(width=width, height=height, pix_fmt=pix_fmt, bit_depth=semi.depth if semi else infer_bit_depth(pix_fmt),
                      colorspace=colorspace, color_range=color_range)
     # (the plan only carries the path into the filter string / notes; a parsed CubeLut or an engine that already holds the
     # lattice has none)
@@ -222,7 +232,9 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         if chroma_loc is not None:
             raise ValueError("chroma siting (chroma_loc) is not defined for an RGB source")
     else:
-        check_chroma_loc(chroma_loc, kw["dither"], kw["pix_fmt"], kw["out_pix_fmt"])
+        from .engine import check_semi_options
+        if not check_semi_options(kw["pix_fmt"], kw["out_pix_fmt"], kw["dither"], chroma_loc, out_size):
+            check_chroma_loc(chroma_loc, kw["dither"], kw["pix_fmt"], kw["out_pix_fmt"])
     if chroma_loc is not None:
         kw["chroma_loc"] = chroma_loc
     if out_size is not None:

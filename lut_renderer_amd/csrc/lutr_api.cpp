@@ -1143,6 +1143,65 @@ int lutr_apply_yuv_xsub(lutr_ctx *c, const lutr_yuv_params *p, int interp, int d
     return finish_launch(c, launch_yuv_dither(c->stream, L, K, P, G, F, din, dout, icsx, icsy, interp, ocsx, ocsy));
 }
 
+// one side of lutr_apply_yuv_semi: the layout against the format's depth, the planes it needs and their alignment
+static int check_semi_side(const char *side, const lutr_yuv_layout *y, int fmt, const lutr_planes *pl, int nframes)
+{
+    const int depth = LUTR_FMT_DEPTH(fmt);
+    if ((y->semi != 0 && y->semi != 1) || (y->swap != 0 && y->swap != 1)) {
+        set_error("%s layout: semi and swap are 0 or 1 (got %d, %d)", side, y->semi, y->swap);
+        return LUTR_EINVAL;
+    }
+    if (y->swap && !y->semi) { set_error("%s layout: swap needs a semi-planar side", side); return LUTR_EINVAL; }
+    if (depth <= 8 ? y->shift != 0 : (y->shift != 0 && y->shift != 16 - depth)) {
+        if (depth <= 8) set_error("%s layout: an 8-bit container takes shift 0, not %d", side, y->shift);
+        else set_error("%s layout: shift is %d (16 - depth) or 0 at %d bit, not %d", side, 16 - depth, depth, y->shift);
+        return LUTR_EINVAL;
+    }
+    if (y->semi && !(LUTR_FMT_CSX(fmt) == 1)) {
+        set_error("%s layout: semi-planar frames are 4:2:0 or 4:2:2", side);
+        return LUTR_EINVAL;
+    }
+    const int np = y->semi ? 2 : 3;
+    for (int i = 0; i < np; i++) {
+        if (!pl->data[i]) { set_error("null %s plane %d", side, i); return LUTR_EINVAL; }
+        if (depth > 8 && (((uintptr_t)pl->data[i] | (uintptr_t)pl->stride[i] | (nframes > 1 ? (uintptr_t)pl->frame_stride[i] : 0)) & 1)) {
+            set_error("%s plane %d: 16-bit containers need 2-byte aligned rows", side, i);
+            return LUTR_EINVAL;
+        }
+    }
+    return LUTR_OK;
+}
+
+int lutr_apply_yuv_semi(lutr_ctx *c, const lutr_yuv_params *p, int interp, const lutr_yuv_layout *in_layout,
+                        const lutr_yuv_layout *out_layout, int w, int h, int nframes, const lutr_planes *src,
+                        const lutr_planes *dst, int row0, int rows)
+{
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!p || !in_layout || !out_layout) { set_error("null yuv params or layout"); return LUTR_EINVAL; }
+    if (!in_layout->semi && !out_layout->semi && !in_layout->swap && !out_layout->swap && !in_layout->shift && !out_layout->shift)
+        return lutr_apply_yuv(c, p, interp, w, h, nframes, src, dst, row0, rows);      // planar both ways: that call itself
+    YuvConsts K;
+    rc = make_yuv_consts(*p, &K);
+    if (rc) return rc;
+    if (const int rc = check_semi_side("source", in_layout, p->fmt_in, src, nframes)) return rc;
+    if (const int rc = check_semi_side("destination", out_layout, p->fmt_out, dst, nframes)) return rc;
+    const int csx = LUTR_FMT_CSX(p->fmt_in), csy = LUTR_FMT_CSY(p->fmt_in);
+    if (csx != 1) { set_error("a shifted planar container is taken at 4:2:0 / 4:2:2 only"); return LUTR_EINVAL; }
+    if (const int rc = check_row_blocks(row0, rows, h, 1 << csy, "chroma block height")) return rc;
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
+    LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
+    fill_planes(&P, src, dst);
+    if (in_layout->semi) { P.s[2] = nullptr; P.ss[2] = 0; P.sfs[2] = 0; }
+    if (out_layout->semi) { P.d[2] = nullptr; P.ds[2] = 0; P.dfs[2] = 0; }
+    const SemiArgs A{in_layout->semi, in_layout->swap, in_layout->shift, out_layout->semi, out_layout->swap, out_layout->shift};
+    return finish_launch(c, launch_yuv_semi(c->stream, c->variant, L, K, P, G, A, LUTR_FMT_DEPTH(p->fmt_in),
+                                            LUTR_FMT_DEPTH(p->fmt_out), csy, interp));
+}
+
 
 int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dither, int src_kind, int w, int h, int nframes,
                           const lutr_planes *src_planar, const lutr_packed *src_packed, const lutr_planes *dst, int row0, int rows)

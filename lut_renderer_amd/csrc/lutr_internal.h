@@ -125,6 +125,23 @@ LUTR_XS_DECL(w00) LUTR_XS_DECL(w11) LUTR_XS_DECL(w10)
 void launch_yuv_float_xsub(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
                            const FloatPlanes &F, int win, int icsx, int icsy, int ocsx, int ocsy, int interp);
 
+// semi-planar frames (lutr_semi.hip): the container of each side -- planar (three planes) or semi-planar (PlaneSet
+// slot 1 holds the Cb / Cr pairs, slot 2 is not read), Cr first with `swap`, 16-bit codes `shift` bits up in their words.  Both
+// sides are csx = 1 with the same csy.  nullptr = the variant cannot take the call (vec_lds always; vec_global on layouts the
+// vector kernel cannot take)
+struct SemiArgs {
+    int isemi, iswap, ishift;
+    int osemi, oswap, oshift;
+};
+const char *launch_yuv_semi(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
+                            const FrameGeom &G, const SemiArgs &A, int din, int dout, int csy, int interp);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>): nullptr = not a side pair / mode it has
+#define LUTR_SM_DECL(tag) \
+    const char *launch_yuv_semi_vec_##tag(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, \
+                                          const FrameGeom &G, const SemiArgs &A, int csy, int interp);
+LUTR_SM_DECL(w00) LUTR_SM_DECL(w11) LUTR_SM_DECL(w10)
+#undef LUTR_SM_DECL
+
 // pass 2 of the dither path alone (k_dither_ed on the float planes F, chroma planes in the output layout); false = rows too wide
 bool launch_dither_ed(hipStream_t st, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const FloatPlanes &F, int wout,
                       int ocsx, int ocsy);

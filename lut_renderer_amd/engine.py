@@ -49,6 +49,78 @@ class PixFmt:
             return h, w
         return (h + (1 << self.csy) - 1) >> self.csy, (w + (1 << self.csx) - 1) >> self.csx
 
+    nplanes = 3
+
+
+@dataclass(frozen=True)
+class SemiFmt:
+    """A semi-planar YUV format: a luma plane and one plane of interleaved chroma pairs."""
+    name: str
+    depth: int
+    csx: int
+    csy: int
+    swap: int         # 1: Cr comes first in a pair (nv21)
+    shift: int        # left shift of the code inside its 16-bit container (p010le: 6)
+
+    family = "yuv"
+    full_range = False
+    nplanes = 2
+
+    @property
+    def code(self) -> int:
+        return _native.fmt_code(self.depth, self.csx, self.csy)
+
+    @property
+    def np_dtype(self):
+        return np.uint8 if self.depth <= 8 else np.uint16
+
+    @property
+    def planar(self) -> str:
+        """The planar format that holds the same samples (nv12 -> yuv420p, p210le -> yuv422p10le)."""
+        return f"yuv{'420' if self.csy else '422'}p" + ("" if self.depth == 8 else f"{self.depth}le")
+
+    def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
+        """Plane 0: (h, w) luma samples; plane 1: (chroma rows, 2 * pairs per row) chroma samples."""
+        if plane == 0:
+            return h, w
+        return (h + (1 << self.csy) - 1) >> self.csy, 2 * ((w + 1) >> 1)
+
+
+def parse_semi_fmt(name: Optional[str]) -> Optional[SemiFmt]:
+    """The semi-planar format `name` stands for (a name of `_native.SEMI_FORMATS`), or None for any other name --
+    `parse_pix_fmt` keeps rejecting these: it describes three-plane frames."""
+    if name not in _native.SEMI_FORMATS:
+        return None
+    return SemiFmt(name, *_native.SEMI_FORMATS[name])
+
+
+def yuv_side(name: str):
+    """One side of `apply_yuv`: the `SemiFmt` or planar `PixFmt` of a YUV format name (yuvj* read as yuv*)."""
+    return parse_semi_fmt(name) or parse_pix_fmt((name or "").replace("yuvj", "yuv"))
+
+
+def check_semi_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
+                       out_size=None) -> bool:
+    """The checks `apply_yuv` makes before any GPU work when a side is semi-planar: both sides YUV with one
+    chroma subsampling, no chroma_loc, no error-diffusion dither, no out_size.  Returns False when neither side is semi-planar
+    (nothing checked), True otherwise."""
+    if parse_semi_fmt(pix_fmt) is None and parse_semi_fmt(out_pix_fmt or pix_fmt) is None:
+        return False
+    if parse_rgb_source(pix_fmt) is not None:
+        raise ValueError(f"an RGB source ('{pix_fmt}') takes a planar YUV out_pix_fmt, not the semi-planar '{out_pix_fmt}'")
+    a, b = yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt)
+    if a.family != "yuv" or b.family != "yuv":
+        raise ValueError(f"semi-planar frames go with YUV formats on both sides ('{pix_fmt}' -> '{out_pix_fmt}')")
+    if (a.csx, a.csy) != (b.csx, b.csy):
+        raise ValueError(f"a chroma subsampling change is not supported with a semi-planar side ('{pix_fmt}' -> '{out_pix_fmt}')")
+    if chroma_loc is not None:
+        raise ValueError("sited chroma resampling (chroma_loc) is not supported with a semi-planar side")
+    if dither != "none":
+        raise ValueError("error-diffusion dither is not supported with a semi-planar side")
+    if out_size is not None:
+        raise ValueError("a resize (out_size) is not supported with a semi-planar side")
+    return True
+
 
 def parse_pix_fmt(name: str) -> PixFmt:
     m = _PIXFMT_RE.match(name or "")
@@ -189,7 +261,10 @@ def _frames3(planes: Sequence[torch.Tensor]) -> list:
 def _check_planes(planes: Sequence[torch.Tensor], fmt: PixFmt, w: int, h: int, what: str) -> None:
     """The C-ABI takes bare pointers and cannot know buffer sizes: every plane must have exactly the shape and the
     element size `fmt` implies for a w x h frame, or the kernels would read or write outside it."""
-    if len(planes) != 3:
+    if fmt.nplanes == 2:
+        if isinstance(planes, torch.Tensor) or len(planes) != 2:
+            raise ValueError(f"'{fmt.name}' takes two planes: luma and the interleaved chroma pairs")
+    elif len(planes) != 3:
         raise ValueError("expected three planes")
     esize = 1 if fmt.depth <= 8 else 2
     for i, t in enumerate(planes):
@@ -220,10 +295,11 @@ def _check_float_planes(planes: Sequence[torch.Tensor], fmt: RgbSource, w: int, 
             raise ValueError(f"{what} plane {i} is {tuple(t.shape[-2:])}, '{fmt.name}' at {w}x{h} needs {(h, w)}")
 
 
-def _planes_struct(planes: Sequence[torch.Tensor], device: torch.device) -> Tuple[_native.Planes, int]:
-    """Describe three [H,W] or [F,H,W] tensors as struct lutr_planes; returns (struct, nframes)."""
-    if len(planes) != 3:
-        raise ValueError("expected three planes")
+def _planes_struct(planes: Sequence[torch.Tensor], device: torch.device, nplanes: int = 3) -> Tuple[_native.Planes, int]:
+    """Describe three [H,W] or [F,H,W] tensors as struct lutr_planes; returns (struct, nframes).  nplanes = 2: a semi-planar
+    side (luma, chroma pairs); slot 2 stays NULL."""
+    if len(planes) != nplanes:
+        raise ValueError("expected three planes" if nplanes == 3 else "expected two planes")
     st = _native.Planes()
     nframes = None
     for i, t in enumerate(planes):
@@ -581,6 +657,10 @@ class LutEngine:
                   row0: int = 0, rows: Optional[int] = None, dither: str = "none", chroma_loc: Optional[str] = None,
                   out_size=None, resize_chunk: Optional[int] = None):
         """Fused YUV -> RGB -> lut3d -> RGB -> YUV on planar frames (Y, Cb, Cr).
+        `pix_fmt` / `out_pix_fmt` may each name a semi-planar format instead (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
+        3.11): that side is a sequence of TWO tensors, y [..., h, w] and cbcr [..., ch, 2 * cw] (the pairs of a row side by side);
+        same subsampling on both sides, no dither / chroma_loc / out_size, strict arithmetic, `dst` may be `src` when the two
+        formats are the same.  The bits are those of the planar call on the same samples.
         dither="error_diffusion" (the reference's `zscale_dither`) dithers the final quantisation; whole frames only.
         chroma_loc ("left" | "center" | "topleft", ffprobe's chroma_location names) resamples chroma bilinearly at that
         siting instead of replicating it (strict arithmetic, not in place, no dither).  None = replicate.
@@ -591,6 +671,9 @@ class LutEngine:
         size and the resize reads them back; whole frames only, not in place.  The resize sites chroma by `chroma_loc`."""
         if dither not in _native.DITHER:
             raise ValueError(f"unknown dither mode '{dither}'")
+        if check_semi_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size):
+            return self._apply_yuv_semi(src, dst, yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt), interp, matrix_in,
+                                        matrix_out, range_src, range_in, range_out, lut_depth, row0, rows)
         fin = parse_pix_fmt(pix_fmt)
         fout = parse_pix_fmt(out_pix_fmt or pix_fmt)
         if fin.family != "yuv" or fout.family != "yuv":
@@ -630,6 +713,33 @@ class LutEngine:
             else:
                 _native.check(self._lib.lutr_apply_yuv(
                     self._ctx, C.byref(p), _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(d), row0, rows))
+        return dst
+
+    def _apply_yuv_semi(self, src, dst, fin, fout, interp, matrix_in, matrix_out, range_src, range_in, range_out, lut_depth,
+                        row0, rows):
+        """apply_yuv with a semi-planar side (lutr_apply_yuv_semi); the options were checked by `check_semi_options`."""
+        p = _yuv_params(fin.code, fout.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
+                        range_src, range_in or range_src, range_out)
+        if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
+            raise ValueError(f"'{fin.name}' takes {fin.nplanes} planes")
+        h, w = src[0].shape[-2], src[0].shape[-1]
+        if dst is None:
+            dt = _yuv_out_dtype(fout.depth, src[0].dtype)
+            dst = [torch.empty(tuple(src[0].shape[:-2]) + fout.plane_shape(i, w, h), dtype=dt, device=self.device)
+                   for i in range(fout.nplanes)]
+        _check_planes(src, fin, w, h, "source")
+        _check_planes(dst, fout, w, h, "destination")
+        s, nf = _planes_struct(src, self.device, fin.nplanes)
+        d, nfd = _planes_struct(dst, self.device, fout.nplanes)
+        if nf != nfd:
+            raise ValueError("src and dst disagree on the number of frames")
+        lay = [_native.YuvLayout(int(f.nplanes == 2), getattr(f, "swap", 0), getattr(f, "shift", 0)) for f in (fin, fout)]
+        rows = h - row0 if rows is None else rows
+        with self._lock:
+            self._bind_stream()
+            _native.check(self._lib.lutr_apply_yuv_semi(
+                self._ctx, C.byref(p), _native.INTERP[interp], C.byref(lay[0]), C.byref(lay[1]), w, h, nf, C.byref(s),
+                C.byref(d), row0, rows))
         return dst
 
     # -- RGB source, YUV output (DESIGN.md 3.9) --------------------------------

@@ -28,7 +28,7 @@ import torch
 
 from . import _native
 from .cube import CubeLut, read_lut
-from .engine import LutEngine, parse_pix_fmt, parse_rgb_source
+from .engine import LutEngine, check_semi_options, parse_pix_fmt, parse_rgb_source, yuv_side
 from .shard import row_blocks
 
 
@@ -127,13 +127,17 @@ class LutEngineGroup:
             raise ValueError("error-diffusion dither couples the rows of a frame: it cannot be row-sharded")
         if "row0" in kw or "rows" in kw:
             raise ValueError("the group owns the row partition")
-        fin, fout = parse_pix_fmt(pix_fmt), parse_pix_fmt(out_pix_fmt or pix_fmt)
+        if check_semi_options(pix_fmt, out_pix_fmt, "none", kw.get("chroma_loc"), kw.get("out_size")):
+            # a semi-planar side: two planes, the second with the chroma plane's rows -- the shard rule is unchanged
+            fin, fout = yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt)
+        else:
+            fin, fout = parse_pix_fmt(pix_fmt), parse_pix_fmt(out_pix_fmt or pix_fmt)
         h, w = src[0].shape[-2], src[0].shape[-1]
         home = src[0].device
         if dst is None:
             dt = torch.uint8 if fout.depth <= 8 else (src[0].dtype if src[0].element_size() == 2 else torch.int16)
             lead = tuple(src[0].shape[:-2])
-            dst = [torch.empty(lead + fout.plane_shape(i, w, h), dtype=dt, device=home) for i in range(3)]
+            dst = [torch.empty(lead + fout.plane_shape(i, w, h), dtype=dt, device=home) for i in range(fout.nplanes)]
         bh = 1 << max(fin.csy, fout.csy)                           # the union block: whole chroma rows on both sides
         blocks = row_blocks(h, len(self.engines), align=bh)
         self.last_blocks = blocks

@@ -18,7 +18,7 @@ from typing import Callable, Iterable, Iterator, List, Optional
 import numpy as np
 import torch
 
-from .engine import LutEngine, PixFmt, RgbSource, parse_pix_fmt, parse_rgb_source, parse_size
+from .engine import LutEngine, PixFmt, RgbSource, SemiFmt, parse_pix_fmt, parse_rgb_source, parse_semi_fmt, parse_size
 
 
 @dataclass
@@ -54,6 +54,45 @@ class FrameLayout:
             out.append(torch.as_strided(typed, (nframes, h, w), (fe, w, 1), off))
             off += nbytes // self.itemsize
         return out
+
+
+@dataclass
+class SemiFrameLayout:
+    """Byte layout of one semi-planar frame (nv12, p010le, ..) in a rawvideo stream: the luma plane, then the
+    plane of chroma pairs."""
+    fmt: SemiFmt
+    width: int
+    height: int
+
+    @property
+    def itemsize(self) -> int:
+        return 1 if self.fmt.depth <= 8 else 2
+
+    @property
+    def plane_shapes(self) -> List[tuple]:
+        return [self.fmt.plane_shape(i, self.width, self.height) for i in range(2)]
+
+    @property
+    def frame_bytes(self) -> int:
+        return sum(h * w for h, w in self.plane_shapes) * self.itemsize
+
+    def plane_views(self, buf: torch.Tensor, nframes: int) -> List[torch.Tensor]:
+        """[F,H,W] and [F,CH,2*CW] views of the two planes inside a flat uint8 buffer of `nframes` frames."""
+        typed = buf.view(torch.uint8 if self.itemsize == 1 else torch.int16)
+        fe = self.frame_bytes // self.itemsize
+        out, off = [], 0
+        for h, w in self.plane_shapes:
+            out.append(torch.as_strided(typed, (nframes, h, w), (fe, w, 1), off))
+            off += h * w
+        return out
+
+
+def yuv_layout(pix_fmt: str, width: int, height: int):
+    """`SemiFrameLayout` for a semi-planar name, else the planar `FrameLayout`."""
+    semi = parse_semi_fmt(pix_fmt)
+    if semi is not None:
+        return SemiFrameLayout(semi, width, height)
+    return FrameLayout(parse_pix_fmt(pix_fmt.replace("yuvj", "yuv")), width, height)
 
 
 @dataclass
@@ -103,14 +142,14 @@ class FloatFrameLayout:
 
 
 def input_layout(pix_fmt: str, width: int, height: int):
-    """The layout of a rawvideo input: `PackedFrameLayout` for a packed RGB name, `FloatFrameLayout` for a planar float one, else
-    `FrameLayout` (planar YUV or gbrp)."""
+    """The layout of a rawvideo input: `PackedFrameLayout` for a packed RGB name, `FloatFrameLayout` for a planar float one,
+    `SemiFrameLayout` for a semi-planar YUV one, else `FrameLayout` (planar YUV or gbrp)."""
     rgb = parse_rgb_source(pix_fmt)
     if rgb is not None and rgb.packed:
         return PackedFrameLayout(rgb, width, height)
     if rgb is not None and rgb.floating:
         return FloatFrameLayout(rgb, width, height)
-    return FrameLayout(parse_pix_fmt(pix_fmt.replace("yuvj", "yuv")), width, height)
+    return yuv_layout(pix_fmt, width, height)
 
 
 class HostPipeline:
@@ -134,7 +173,7 @@ class HostPipeline:
                 raise ValueError("a float output takes no out_size and cannot add an alpha plane")
             self.fout = FloatFrameLayout(out_rgb, ow, oh)
         else:
-            self.fout = FrameLayout(parse_pix_fmt(out_pix_fmt or pix_fmt.replace("yuvj", "yuv")), ow, oh)
+            self.fout = yuv_layout(out_pix_fmt or pix_fmt, ow, oh)
         self.batch, self.slots = int(batch), int(slots)
         self.kw = dict(apply_kw, pix_fmt=self.fin.fmt.name, out_pix_fmt=self.fout.fmt.name)
         if out_size is not None:
