@@ -1,6 +1,7 @@
-// lutr_device.h -- device-side pieces shared by the gfx950 kernels (lutr_kernels.hip,
-// lutr_packed.hip): the lut3d per-pixel restatement, the
-// YUV contract (DESIGN.md "YUV contract") and little sample/word accessors.
+// lutr_device.h -- device-side pieces shared by the gfx950 gather kernels (lutr_kernels.hip, lutr_packed.hip, lutr_sited.hip,
+// lutr_dither.hip, lutr_xsub.hip, lutr_rgb2yuv.hip, lutr_rgbf.hip, lutr_semi.hip): the lut3d per-pixel restatement (SURVEY.md
+// Appendix A.3-A.5), the YUV contract (DESIGN.md "YUV contract"), little sample/word accessors, the block walk, block
+// body and output sinks of the by-block generic kernels, and the vector kernels' unit size.
 //
 // Everything here rounds exactly like FFmpeg's scalar C (-ffp-contract=off; fused
 // multiply-adds only where written as __builtin_fmaf).
@@ -307,30 +308,60 @@ __device__ __forceinline__ void st_words(uint8_t *p, const uint32_t *w)
     }
 }
 
-// ---------------------------------------------------------------- output sinks of the by-block generic kernels
-// Where the generic kernels of the RGB-source paths (lutr_rgb2yuv.hip, lutr_rgbf.hip) put one output chroma block: luma() per
-// pixel inside the frame, chroma() once with the block's R, G, B sums.
-struct R2yPlaneSink {
+// ---------------------------------------------------------------- plane rows
+template <class Y>
+__device__ __forceinline__ const uint8_t *src_row(const PlaneSet &P, int c, long long fr, Y y)
+{
+    return P.s[c] + fr * P.sfs[c] + y * P.ss[c];
+}
+
+template <class Y>
+__device__ __forceinline__ uint8_t *dst_row(const PlaneSet &P, int c, long long fr, Y y)
+{
+    return P.d[c] + fr * P.dfs[c] + y * P.ds[c];
+}
+
+// ---------------------------------------------------------------- by-block generic kernels: the walk and the output sinks
+// Grid-stride walk of blocks of 2^csx x 2^csy luma samples, one thread per block: body(fr, cx, cy) for every block that touches
+// rows row0 .. row0 + rows of the frame (whole_frames: all of it, the dither path's pass 1)
+template <class Body>
+__device__ __forceinline__ void for_each_block(const FrameGeom &G, int csx, int csy, bool whole_frames, Body body)
+{
+    const int cw = (G.w + (1 << csx) - 1) >> csx;
+    const int cr0 = whole_frames ? 0 : G.row0 >> csy;
+    const int crows = (((whole_frames ? G.h : G.row0 + G.rows) + (1 << csy) - 1) >> csy) - cr0;
+    const long long total = (long long)cw * crows * G.nframes;
+    for (long long u = blockIdx.x * 256ll + threadIdx.x; u < total; u += (long long)gridDim.x * 256ll) {
+        const long long t = u / cw;
+        body(t / crows, (int)(u % cw), cr0 + (int)(t % crows));
+    }
+}
+
+// Where a generic kernel puts one output chroma block: luma() per pixel inside the frame, chroma() once with the block's R, G, B
+// sums.  PlaneSink: the quantised planes.
+struct PlaneSink {
     const YuvConsts &K;
     const PlaneSet &P;
     int wout;
     __device__ __forceinline__ void luma(long long fr, int x, int y, const Rgb &o)
     {
-        st_sample(P.d[0] + fr * P.dfs[0] + (long long)y * P.ds[0], x, wout, rgb_to_y(K, o));
+        st_sample(dst_row(P, 0, fr, y), x, wout, rgb_to_y(K, o));
     }
     __device__ __forceinline__ void chroma(long long fr, int cx, int cy, float rs, float gs, float bs)
     {
-        st_sample(P.d[1] + fr * P.dfs[1] + (long long)cy * P.ds[1], cx, wout, rgb_to_cb(K, rs, gs, bs));
-        st_sample(P.d[2] + fr * P.dfs[2] + (long long)cy * P.ds[2], cx, wout, rgb_to_cr(K, rs, gs, bs));
+        st_sample(dst_row(P, 1, fr, cy), cx, wout, rgb_to_cb(K, rs, gs, bs));
+        st_sample(dst_row(P, 2, fr, cy), cx, wout, rgb_to_cr(K, rs, gs, bs));
     }
 };
 
-// the dither path's pass 1 (k_yuv_float's values, lutr_dither.hip): unquantised planes, densely packed per frame
-struct R2yFloatSink {
+// FloatSink: the dither path's pass 1 -- unquantised planes, densely packed per frame, chroma in the layout csx, csy
+struct FloatSink {
     const YuvConsts &K;
     const FloatPlanes &F;
     const FrameGeom &G;
     int cw, ch;
+    __device__ __forceinline__ FloatSink(const YuvConsts &K, const FloatPlanes &F, const FrameGeom &G, int csx, int csy)
+        : K(K), F(F), G(G), cw((G.w + (1 << csx) - 1) >> csx), ch((G.h + (1 << csy) - 1) >> csy) {}
     __device__ __forceinline__ void luma(long long fr, int x, int y, const Rgb &o)
     {
         F.y[(fr * G.h + y) * G.w + x] = fma_(K.cyr, o.r, fma_(K.cyg, o.g, fma_(K.cyb, o.b, K.yob))) - 0.5f;
@@ -341,5 +372,40 @@ struct R2yFloatSink {
         F.cr[(fr * ch + cy) * cw + cx] = fma_(K.crr, rs, fma_(K.crg, gs, fma_(K.crb, bs, K.cob))) - 0.5f;
     }
 };
+
+// One chroma block of the fused YUV pass (k_yuv_generic, k_yuv_float).  A pixel outside the frame is the edge pixel again (odd
+// sizes: the edge column / row is summed twice); only pixels inside the frame are written.
+template <class Sink>
+__device__ __forceinline__ void yuv_block(const LutConsts &L, const GFetch &f, const YuvConsts &K, const PlaneSet &P,
+                                          const FrameGeom &G, long long fr, int cx, int cy, int win, int csx, int csy, int mode,
+                                          Sink &sink)
+{
+    const int bw = 1 << csx, bh = 1 << csy;
+    const Chroma c = chroma_terms(K, ld_sample(src_row(P, 1, fr, cy), cx, win), ld_sample(src_row(P, 2, fr, cy), cx, win));
+    float rs = 0.f, gs = 0.f, bs = 0.f;
+    for (int dy = 0; dy < bh; dy++) {
+        const int yy = cy * bh + dy;
+        const int y = yy < G.h ? yy : G.h - 1;
+        for (int dx = 0; dx < bw; dx++) {
+            const int xx = cx * bw + dx;
+            const int x = xx < G.w ? xx : G.w - 1;
+            const Rgb q = yuv_to_rgb(K, ld_sample(src_row(P, 0, fr, y), x, win), c);
+            const Rgb o = lut3d_px_rt(mode, L, f, q.r, q.g, q.b);
+            rs += o.r; gs += o.g; bs += o.b;
+            if (yy < G.h && xx < G.w) sink.luma(fr, x, y, o);
+        }
+    }
+    sink.chroma(fr, cx, cy, rs, gs, bs);
+}
+
+// ---------------------------------------------------------------- vector kernels, global gather
+// kVecBytes bytes per plane row and thread: with 16-byte accesses these kernels needed 256 VGPRs (one wave per SIMD); at 8 bytes
+// they keep several waves per SIMD, which is what a gather wants.
+constexpr int kVecBytes = 8;
+// WIN / WOUT: 16-bit containers in / out.  A 10-bit source written as 8 bit (the reference's libx264 default,
+// ffmpeg.py:287-302) takes 16 bytes of luma per thread and row so that its 8-bit chroma output is still a whole word.
+template <int WIN, int WOUT> constexpr int vec_bytes() { return (WIN && !WOUT) ? 16 : kVecBytes; }
+
+constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
 }  // namespace lutr

@@ -29,39 +29,13 @@
 namespace lutr {
 
 // ---------------------------------------------------------------- pass 1: unquantised YUV planes
+// (k_yuv_generic's walk and block body with the float sink: lutr_device.h)
 __global__ __launch_bounds__(256) void k_yuv_float(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, FloatPlanes F,
                                                    int win, int csx, int csy, int mode)
 {
     const GFetch f(L);
-    const int bw = 1 << csx, bh = 1 << csy;
-    const int cw = (G.w + bw - 1) >> csx, ch = (G.h + bh - 1) >> csy;
-    const long long total = (long long)cw * ch * G.nframes;
-    for (long long u = blockIdx.x * 256ll + threadIdx.x; u < total; u += (long long)gridDim.x * 256ll) {
-        const int cx = (int)(u % cw);
-        const long long t = u / cw;
-        const int cy = (int)(t % ch);
-        const long long fr = t / ch;
-        const float cbv = ld_sample(P.s[1] + fr * P.sfs[1] + (long long)cy * P.ss[1], cx, win);
-        const float crv = ld_sample(P.s[2] + fr * P.sfs[2] + (long long)cy * P.ss[2], cx, win);
-        const Chroma c = chroma_terms(K, cbv, crv);
-        float rs = 0.f, gs = 0.f, bs = 0.f;
-        for (int dy = 0; dy < bh; dy++) {
-            const int yy = cy * bh + dy;
-            const int y = yy < G.h ? yy : G.h - 1;
-            for (int dx = 0; dx < bw; dx++) {
-                const int xx = cx * bw + dx;
-                const int x = xx < G.w ? xx : G.w - 1;
-                const float yv = ld_sample(P.s[0] + fr * P.sfs[0] + (long long)y * P.ss[0], x, win);
-                const Rgb q = yuv_to_rgb(K, yv, c);
-                const Rgb o = lut3d_px_rt(mode, L, f, q.r, q.g, q.b);
-                rs += o.r; gs += o.g; bs += o.b;
-                if (yy < G.h && xx < G.w)
-                    F.y[(fr * G.h + y) * G.w + x] = fma_(K.cyr, o.r, fma_(K.cyg, o.g, fma_(K.cyb, o.b, K.yob))) - 0.5f;
-            }
-        }
-        F.cb[(fr * ch + cy) * cw + cx] = fma_(K.cbr, rs, fma_(K.cbg, gs, fma_(K.cbb, bs, K.cob))) - 0.5f;
-        F.cr[(fr * ch + cy) * cw + cx] = fma_(K.crr, rs, fma_(K.crg, gs, fma_(K.crb, bs, K.cob))) - 0.5f;
-    }
+    FloatSink sink(K, F, G, csx, csy);
+    for_each_block(G, csx, csy, true, [&](long long fr, int cx, int cy) { yuv_block(L, f, K, P, G, fr, cx, cy, win, csx, csy, mode, sink); });
 }
 
 // ---------------------------------------------------------------- pass 2: error diffusion
@@ -222,8 +196,7 @@ const char *launch_yuv_dither(hipStream_t st, const LutConsts &L, const YuvConst
         // a subsampling change: pass 1 by union blocks (lutr_xsub.hip); pass 2 below sizes its planes from the output
         launch_yuv_float_xsub(st, L, K, P, G, F, win, csx, csy, ocsx, ocsy, mode);
     } else {
-        const long long blocks = (long long)((G.w + (1 << csx) - 1) >> csx) * ((G.h + (1 << csy) - 1) >> csy) * G.nframes;
-        hipLaunchKernelGGL(k_yuv_float, dim3(grid_for(blocks, kGridStrideCap)), dim3(256), 0, st, L, K, P, G, F, win, csx, csy, mode);
+        hipLaunchKernelGGL(k_yuv_float, dim3(block_grid(G.w, G.h, G.nframes, csx, csy)), dim3(256), 0, st, L, K, P, G, F, win, csx, csy, mode);
     }
     return launch_dither_ed(st, K, P, G, F, wout, ocsx, ocsy) ? "k_yuv_float+k_dither_ed" : nullptr;
 }
@@ -246,7 +219,7 @@ bool launch_dither_ed(hipStream_t st, const YuvConsts &K, const PlaneSet &P, con
     (void)allow_lds((const void *)k_dither_ed<true>, 160 * 1024);
     (void)allow_lds((const void *)k_dither_ed<false>, 160 * 1024);
     // packed path: every plane width a multiple of 4, destination rows aligned for 4-sample stores
-    const int cwid = (G.w + (1 << ocsx) - 1) >> ocsx;
+    const int cwid = (int)blocks(G.w, ocsx);
     bool vec = G.w % 4 == 0 && cwid % 4 == 0;
     const uintptr_t al = wout ? 8 : 4;
     for (int c = 0; c < 3 && vec; c++)

@@ -32,59 +32,28 @@ __global__ __launch_bounds__(256) void k_rgb_generic(LutConsts L, PlaneSet P, Fr
         const long long t = u / G.w;
         const int y = G.row0 + (int)(t % G.rows);
         const long long fr = t / G.rows;
-        const float g = ld_sample(P.s[0] + fr * P.sfs[0] + y * P.ss[0], x, wide);
-        const float b = ld_sample(P.s[1] + fr * P.sfs[1] + y * P.ss[1], x, wide);
-        const float r = ld_sample(P.s[2] + fr * P.sfs[2] + y * P.ss[2], x, wide);
+        const float g = ld_sample(src_row(P, 0, fr, y), x, wide);
+        const float b = ld_sample(src_row(P, 1, fr, y), x, wide);
+        const float r = ld_sample(src_row(P, 2, fr, y), x, wide);
         const Rgb o = lut3d_px_rt(mode, L, f, r, g, b);
-        st_sample(P.d[0] + fr * P.dfs[0] + y * P.ds[0], x, wide, o.g);
-        st_sample(P.d[1] + fr * P.dfs[1] + y * P.ds[1], x, wide, o.b);
-        st_sample(P.d[2] + fr * P.dfs[2] + y * P.ds[2], x, wide, o.r);
+        st_sample(dst_row(P, 0, fr, y), x, wide, o.g);
+        st_sample(dst_row(P, 1, fr, y), x, wide, o.b);
+        st_sample(dst_row(P, 2, fr, y), x, wide, o.r);
     }
 }
 
+// (the block walk, the block body and the sink: lutr_device.h, shared with k_yuv_float of the dither path)
 __global__ __launch_bounds__(256) void k_yuv_generic(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G,
                                                      int win, int wout, int csx, int csy, int mode)
 {
     const GFetch f(L);
-    const int bw = 1 << csx, bh = 1 << csy;
-    const int cw = (G.w + bw - 1) >> csx;             // chroma blocks per row
-    const int cr0 = G.row0 >> csy;
-    const int crows = ((G.row0 + G.rows + bh - 1) >> csy) - cr0;
-    const long long total = (long long)cw * crows * G.nframes;
-    for (long long u = blockIdx.x * 256ll + threadIdx.x; u < total; u += (long long)gridDim.x * 256ll) {
-        const int cx = (int)(u % cw);
-        const long long t = u / cw;
-        const int cy = cr0 + (int)(t % crows);
-        const long long fr = t / crows;
-        const float cbv = ld_sample(P.s[1] + fr * P.sfs[1] + cy * P.ss[1], cx, win);
-        const float crv = ld_sample(P.s[2] + fr * P.sfs[2] + cy * P.ss[2], cx, win);
-        const Chroma c = chroma_terms(K, cbv, crv);
-        float rs = 0.f, gs = 0.f, bs = 0.f;
-        for (int dy = 0; dy < bh; dy++) {
-            const int yy = cy * bh + dy;
-            const int y = yy < G.h ? yy : G.h - 1;    // odd height: replicate the edge row into the block
-            for (int dx = 0; dx < bw; dx++) {
-                const int xx = cx * bw + dx;
-                const int x = xx < G.w ? xx : G.w - 1;
-                const float yv = ld_sample(P.s[0] + fr * P.sfs[0] + y * P.ss[0], x, win);
-                const Rgb q = yuv_to_rgb(K, yv, c);
-                const Rgb o = lut3d_px_rt(mode, L, f, q.r, q.g, q.b);
-                rs += o.r; gs += o.g; bs += o.b;
-                if (yy < G.h && xx < G.w)
-                    st_sample(P.d[0] + fr * P.dfs[0] + y * P.ds[0], x, wout, rgb_to_y(K, o));
-            }
-        }
-        st_sample(P.d[1] + fr * P.dfs[1] + cy * P.ds[1], cx, wout, rgb_to_cb(K, rs, gs, bs));
-        st_sample(P.d[2] + fr * P.dfs[2] + cy * P.ds[2], cx, wout, rgb_to_cr(K, rs, gs, bs));
-    }
+    PlaneSink sink{K, P, wout};
+    for_each_block(G, csx, csy, false, [&](long long fr, int cx, int cy) { yuv_block(L, f, K, P, G, fr, cx, cy, win, csx, csy, mode, sink); });
 }
 
 // ================================================================= vector kernels, global gather
-// The low-latency path of small launches (and the A/B reference of the LDS window).  kVecBytes bytes per
-// plane row and thread: 4 px (16-bit containers) or 8 px (8-bit).  With 16-byte accesses these kernels needed
-// 256 VGPRs (one wave per SIMD); at 8 bytes they keep several waves per SIMD, which is what a gather wants.
-constexpr int kVecBytes = 8;
-
+// The low-latency path of small launches (and the A/B reference of the LDS window).  kVecBytes bytes per plane row and thread:
+// 4 px (16-bit containers) or 8 px (8-bit); kVecBytes and vec_bytes<WIN, WOUT>(): lutr_device.h.
 template <int WIDE, int INTERP>
 __global__ __launch_bounds__(256) void k_rgb_vec(LutConsts L, PlaneSet P, FrameGeom G)
 {
@@ -101,9 +70,9 @@ __global__ __launch_bounds__(256) void k_rgb_vec(LutConsts L, PlaneSet P, FrameG
     uint32_t gw[NW], bw[NW], rw[NW], go[NW], bo[NW], ro[NW];
 #pragma unroll
     for (int k = 0; k < NW; k++) { go[k] = 0; bo[k] = 0; ro[k] = 0; }
-    ld_words<NW>(gw, P.s[0] + fr * P.sfs[0] + y * P.ss[0] + xo);
-    ld_words<NW>(bw, P.s[1] + fr * P.sfs[1] + y * P.ss[1] + xo);
-    ld_words<NW>(rw, P.s[2] + fr * P.sfs[2] + y * P.ss[2] + xo);
+    ld_words<NW>(gw, src_row(P, 0, fr, y) + xo);
+    ld_words<NW>(bw, src_row(P, 1, fr, y) + xo);
+    ld_words<NW>(rw, src_row(P, 2, fr, y) + xo);
 #pragma unroll
     for (int i = 0; i < PXT; i++) {
         const Rgb o = lut3d_px<INTERP>(L, f, word_sample<WIDE>(rw, i), word_sample<WIDE>(gw, i),
@@ -112,15 +81,15 @@ __global__ __launch_bounds__(256) void k_rgb_vec(LutConsts L, PlaneSet P, FrameG
         word_put<WIDE>(bo, i, o.b);
         word_put<WIDE>(ro, i, o.r);
     }
-    st_words<NW, true>(P.d[0] + fr * P.dfs[0] + y * P.ds[0] + xo, go);
-    st_words<NW, true>(P.d[1] + fr * P.dfs[1] + y * P.ds[1] + xo, bo);
-    st_words<NW, true>(P.d[2] + fr * P.dfs[2] + y * P.ds[2] + xo, ro);
+    st_words<NW, true>(dst_row(P, 0, fr, y) + xo, go);
+    st_words<NW, true>(dst_row(P, 1, fr, y) + xo, bo);
+    st_words<NW, true>(dst_row(P, 2, fr, y) + xo, ro);
 }
 
-// WIN / WOUT: 16-bit containers in / out.  A 10-bit source written as 8 bit (the reference's libx264 default,
-// ffmpeg.py:287-302) takes 16 bytes of luma per thread and row so that its 8-bit chroma output is still a whole word.
-template <int WIN, int WOUT> constexpr int vec_bytes() { return (WIN && !WOUT) ? 16 : kVecBytes; }
-
+// The fused vector kernels (this one and those of lutr_xsub.hip, lutr_rgb2yuv.hip, lutr_rgbf.hip, lutr_semi.hip) keep their frame
+// -- unit preamble, row addresses, fence, output stage -- written out: hipcc's schedule follows the order of the source, and each
+// shared form tried (src_row / dst_row, a fence helper, an output-stage struct, k_yuv_vec as the equal-layout instance of
+// k_yuv_xsub_vec's body) moved instructions in some instance.  tools/device_asm_diff.sh is the check for any change to them.
 template <int WIN, int WOUT, int CSX, int CSY, int INTERP>
 __global__ __launch_bounds__(256) void k_yuv_vec(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G)
 {
@@ -203,8 +172,8 @@ const char *launch_rgb(hipStream_t st, int variant, const LutConsts &L, const Pl
     const int wide = depth > 8;
     const int pxt = wide ? 8 : 16;
     const long long px = (long long)G.w * G.rows * G.nframes;
-    bool vec_ok = (mode == LUTR_INTERP_NEAREST || mode == LUTR_INTERP_TRILINEAR || mode == LUTR_INTERP_TETRAHEDRAL) &&
-                  G.w % pxt == 0 && px / pxt < 0x7fffffffll;
+    bool vec_ok = vec_mode(mode) &&
+                  G.w % pxt == 0 && units_fit(px / pxt);
     for (int c = 0; c < 3 && vec_ok; c++)
         vec_ok = planes_ok(P, c, 16, G.nframes > 1, kStrideTile, false);
     if (variant == VAR_GENERIC) vec_ok = false;
@@ -231,15 +200,15 @@ const char *launch_rgb(hipStream_t st, int variant, const LutConsts &L, const Pl
     // its unit, the scalar kernel the few that remain (each pixel is independent, so any split is exact).
     const int wv = G.w / pxt * pxt;
     if (tiles && variant == VAR_AUTO && !vec_ok && wv > 0 && wv < G.w && !small_job(px, kSmallTileMpx) &&
-        (mode == LUTR_INTERP_NEAREST || mode == LUTR_INTERP_TRILINEAR || mode == LUTR_INTERP_TETRAHEDRAL) &&
-        (long long)wv * G.rows * G.nframes / pxt < 0x7fffffffll &&
+        vec_mode(mode) &&
+        units_fit((long long)wv * G.rows * G.nframes / pxt) &&
         planes_ok(P, 0, 16, G.nframes > 1, kStrideTile, false) && planes_ok(P, 1, 16, G.nframes > 1, kStrideTile, false) &&
         planes_ok(P, 2, 16, G.nframes > 1, kStrideTile, false)) {
         FrameGeom Gv = G, Ge = G;
         Gv.w = wv;
         Ge.w = G.w - wv;
-        PlaneSet Pe = P;
-        for (int c = 0; c < 3; c++) { Pe.s[c] += (long long)wv * (wide ? 2 : 1); Pe.d[c] += (long long)wv * (wide ? 2 : 1); }
+        const long long eb = (long long)wv * (wide ? 2 : 1);
+        const PlaneSet Pe = advance_planes(P, eb, eb, eb, eb);
         const char *name = launch_rgb_tile(st, L, P, Gv, depth, mode, stats, queue);
         hipLaunchKernelGGL(k_rgb_generic, dim3(grid_for((long long)Ge.w * G.rows * G.nframes, kGridStrideCap)), dim3(256), 0, st,
                            L, Pe, Ge, wide, mode);
@@ -273,9 +242,9 @@ static const char *try_tile2(hipStream_t st, const LutConsts &L, const YuvConsts
     const char *nop = getenv("LUTR_NO_TILE2_PRELUT");
     if (getenv("LUTR_NO_TILE2") || (L.pre && (!L.pre_shared || lut_depth > 10 || (nop && nop[0] != '0')))) return nullptr;
     const int win = din > 8, wout = dout > 8, pxt = win ? 8 : 16, bh = 1 << csy;
-    if (!(mode == LUTR_INTERP_NEAREST || mode == LUTR_INTERP_TRILINEAR || mode == LUTR_INTERP_TETRAHEDRAL)) return nullptr;
+    if (!vec_mode(mode)) return nullptr;
     if (G.w % pxt || G.row0 % bh || G.rows % bh || (csx == 0 && csy == 1)) return nullptr;
-    if ((long long)(G.w / pxt) * (G.rows >> csy) * G.nframes >= 0x7fffffffll) return nullptr;
+    if (!units_fit((long long)(G.w / pxt) * (G.rows >> csy) * G.nframes)) return nullptr;
     const long long yi = 16, yo = (long long)pxt * (wout ? 2 : 1), ci = (long long)(pxt >> csx) * (win ? 2 : 1),
                     co = (long long)(pxt >> csx) * (wout ? 2 : 1);
     const bool batch = G.nframes > 1;
@@ -313,10 +282,10 @@ const char *launch_yuv(hipStream_t st, int variant, const LutConsts &L, const Yu
         if (variant == VAR_VEC_LDS) return nullptr;          // asked for the tile kernels, and they cannot take this call
     }
     const long long cbytes = (long long)(pxt >> csx) * (win ? 2 : 1);      // chroma bytes per thread
-    bool vec_ok = (mode == LUTR_INTERP_NEAREST || mode == LUTR_INTERP_TRILINEAR || mode == LUTR_INTERP_TETRAHEDRAL) &&
+    bool vec_ok = vec_mode(mode) &&
                   win == wout && G.w % pxt == 0 && G.row0 % bh == 0 && G.rows % bh == 0 &&
                   !(csx == 0 && csy == 1) &&
-                  (long long)(G.w / pxt) * (G.rows >> csy) * G.nframes < 0x7fffffffll;
+                  units_fit((long long)(G.w / pxt) * (G.rows >> csy) * G.nframes);
     for (int c = 0; c < 3 && vec_ok; c++) vec_ok = planes_ok(P, c, c ? cbytes : 16, G.nframes > 1, kStrideTile, false);
     if (variant == VAR_GENERIC) vec_ok = false;
     // ragged width on aligned (padded) rows: tile kernel up to the last whole unit, scalar kernel for the rest
@@ -327,21 +296,18 @@ const char *launch_yuv(hipStream_t st, int variant, const LutConsts &L, const Yu
         Gv.w = wv;
         Ge.w = G.w - wv;
         if (const char *name = try_tile2(st, L, K, P, Gv, din, dout, lut_depth, csx, csy, mode, fast, stats, queue)) {
-            PlaneSet Pe = P;
             const long long bsi = win ? 2 : 1, bso = wout ? 2 : 1;
-            Pe.s[0] += wv * bsi; Pe.d[0] += wv * bso;
-            for (int c = 1; c < 3; c++) { Pe.s[c] += (wv >> csx) * bsi; Pe.d[c] += (wv >> csx) * bso; }
-            const long long eb = (long long)((Ge.w + (1 << csx) - 1) >> csx) * ((G.rows + bh - 1) >> csy) * G.nframes;
-            hipLaunchKernelGGL(k_yuv_generic, dim3(grid_for(eb, kGridStrideCap)), dim3(256), 0, st, L, K, Pe, Ge, win, wout,
-                               csx, csy, mode);
+            const PlaneSet Pe = advance_planes(P, wv * bsi, (wv >> csx) * bsi, wv * bso, (wv >> csx) * bso);
+            hipLaunchKernelGGL(k_yuv_generic, dim3(block_grid(Ge.w, G.rows, G.nframes, csx, csy)), dim3(256), 0, st, L, K, Pe, Ge,
+                               win, wout, csx, csy, mode);
             return name;
         }
     }
     // 10-bit (or deeper) source written as 8 bit: the vector kernel with 16-byte luma units
     if (!vec_ok && variant != VAR_GENERIC && win == 1 && wout == 0 &&
-        (mode == LUTR_INTERP_NEAREST || mode == LUTR_INTERP_TRILINEAR || mode == LUTR_INTERP_TETRAHEDRAL) &&
+        vec_mode(mode) &&
         G.w % 8 == 0 && G.row0 % bh == 0 && G.rows % bh == 0 && !(csx == 0 && csy == 1) &&
-        (long long)(G.w / 8) * (G.rows >> csy) * G.nframes < 0x7fffffffll &&
+        units_fit((long long)(G.w / 8) * (G.rows >> csy) * G.nframes) &&
         plane_ok(P.s[0], P.ss[0], P.sfs[0], 16, G.nframes > 1, kStrideTile2, true) &&
         plane_ok(P.d[0], P.ds[0], P.dfs[0], 8, G.nframes > 1, kStrideTile2, true) &&
         plane_ok(P.s[1], P.ss[1], P.sfs[1], 16 >> csx, G.nframes > 1, kStrideTile2, true) &&
@@ -361,9 +327,8 @@ const char *launch_yuv(hipStream_t st, int variant, const LutConsts &L, const Yu
     }
     if (!vec_ok) {
         if (variant == VAR_VEC_GLOBAL || variant == VAR_VEC_LDS) return nullptr;
-        const long long blocks = (long long)((G.w + (1 << csx) - 1) >> csx) * ((G.rows + bh - 1) >> csy) * G.nframes;
-        hipLaunchKernelGGL(k_yuv_generic, dim3(grid_for(blocks, kGridStrideCap)), dim3(256), 0, st, L, K, P, G, win, wout,
-                           csx, csy, mode);
+        hipLaunchKernelGGL(k_yuv_generic, dim3(block_grid(G.w, G.rows, G.nframes, csx, csy)), dim3(256), 0, st, L, K, P, G, win,
+                           wout, csx, csy, mode);
         return "k_yuv_generic";
     }
     const long long units = (long long)(G.w / (kVecBytes / (win ? 2 : 1))) * (G.rows >> csy) * G.nframes;

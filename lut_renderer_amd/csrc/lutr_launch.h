@@ -10,12 +10,20 @@
 
 #include "lutr_internal.h"
 
+// names and strings built from a translation unit's -D switches
+#define LUTR_CAT2(a, b) a##b
+#define LUTR_CAT(a, b) LUTR_CAT2(a, b)
+#define LUTR_STR2(x) #x
+#define LUTR_STR(x) LUTR_STR2(x)
+
 namespace lutr {
 
 // ---------------------------------------------------------------- plane alignment
 // Stride caps of plane_ok.  The fast kernels address rows with 32-bit positive offsets; bottom-up (negative linesize) or huge
 // strides go to the generic kernels, which do 64-bit signed arithmetic.
-constexpr long long kStrideAny = LLONG_MAX;     // xsub, rgb2yuv and sited vector kernels: 64-bit row offsets, no cap
+// the global-gather vector kernels of lutr_xsub.hip, lutr_rgb2yuv.hip, lutr_rgbf.hip, lutr_semi.hip and lutr_sited.hip: 64-bit row
+// offsets, no cap
+constexpr long long kStrideAny = LLONG_MAX;
 // k_rgb_tile (lutr_tile.hip) and the k_rgb_vec / k_yuv_vec kernels routed with it: a tile kernel forms
 // (row in tile) * stride + 16 * (unit in row) as one unsigned 32-bit offset with up to 31 rows and 63 units of 16 bytes
 constexpr long long kStrideTile = (0xffffffffll - 64 * 16) / 32;
@@ -52,6 +60,23 @@ inline PlaneSet gbrp_to_rgb(const PlaneSet &P)
     return Q;
 }
 
+// P moved right by s0 / d0 bytes on plane 0 and sc / dc bytes on planes 1 and 2: the planes of the tail of a column split (a plane
+// a semi-planar side does not have stays null)
+inline PlaneSet advance_planes(PlaneSet P, long long s0, long long sc, long long d0, long long dc)
+{
+    for (int c = 0; c < 3; c++) {
+        if (P.s[c]) P.s[c] += c ? sc : s0;
+        if (P.d[c]) P.d[c] += c ? dc : d0;
+    }
+    return P;
+}
+
+// the modes the vector and tile kernels are instantiated for (the generic kernels have all five)
+inline bool vec_mode(int mode)
+{
+    return mode == LUTR_INTERP_NEAREST || mode == LUTR_INTERP_TRILINEAR || mode == LUTR_INTERP_TETRAHEDRAL;
+}
+
 // ---------------------------------------------------------------- launch sizing
 // Blocks of 256 threads for `units` work items, at least one.  Grid-stride kernels pass kGridStrideCap: enough blocks to fill
 // 256 CUs x 8.
@@ -62,6 +87,42 @@ inline unsigned grid_for(long long units, unsigned cap = 0x7fffffffu)
     if (b < 1) b = 1;
     if (b > (long long)cap) b = cap;
     return (unsigned)b;
+}
+
+// the one-thread-per-unit kernels index their units with 32 bits
+inline bool units_fit(long long units) { return units < 0x7fffffffll; }
+
+// blocks of 2^cs samples that cover n samples, and the grid of a by-block generic kernel (one thread per 2^csx x 2^csy block)
+inline long long blocks(int n, int cs) { return (n + (1 << cs) - 1) >> cs; }
+inline unsigned block_grid(int w, int rows, int nframes, int csx, int csy)
+{
+    return grid_for(blocks(w, csx) * blocks(rows, csy) * nframes, kGridStrideCap);
+}
+
+// The launch sequence of a path that has global-gather vector kernels and a generic kernel, no LDS kernel.  vec_fits(P, G): the
+// vector kernels can take these planes and this geometry; vec / generic launch and return the kernel's name; tail(wv): the planes
+// moved right by wv pixels.  A ragged width on aligned (padded) rows goes to the vector kernel up to the last whole unit of unit_px
+// columns and to the generic kernel for the rest (the unit is a whole number of chroma blocks, so the split falls between two).
+template <class Fits, class Vec, class Generic, class Tail>
+const char *launch_vec_or_generic(int variant, const PlaneSet &P, const FrameGeom &G, int unit_px, Fits vec_fits, Vec vec,
+                                  Generic generic, Tail tail)
+{
+    if (variant == VAR_VEC_LDS) return nullptr;
+    if (variant == VAR_GENERIC) return generic(P, G);
+    if (vec_fits(P, G)) return vec(P, G);
+    if (variant == VAR_VEC_GLOBAL) return nullptr;
+    const int wv = G.w / unit_px * unit_px;
+    if (wv > 0 && wv < G.w) {
+        FrameGeom Gv = G, Ge = G;
+        Gv.w = wv;
+        Ge.w = G.w - wv;
+        if (vec_fits(P, Gv)) {
+            const char *name = vec(P, Gv);
+            generic(tail(wv), Ge);
+            return name;
+        }
+    }
+    return generic(P, G);
 }
 
 // The persistent tile kernels pay a fixed start-up (coordinate table, tube staging, a wave's first tile at a quarter of the issue

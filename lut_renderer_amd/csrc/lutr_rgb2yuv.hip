@@ -10,7 +10,7 @@
 //
 // The source arrives as three component streams in R, G, B order (lutr_internal.h RgbLayout): planar gbrp, or one packed image.
 //
-// One source, two kinds of translation unit (Makefile R2Y_RULE), like lutr_xsub.hip:
+// One source, two kinds of translation unit (Makefile MIX_RULE), like lutr_xsub.hip:
 //   without LUTR_R2Y_WI   the generic kernel, the unquantised pass of the dither path and the launcher
 //   LUTR_R2Y_WI / _WO     the vector kernels of one container mix (8 -> 8, 16 -> 16, 16 -> 8): 3 source kinds x 3 layouts x 4 modes
 #include "lutr_device.h"
@@ -21,7 +21,7 @@ namespace lutr {
 #ifdef LUTR_R2Y_WI
 // ================================================================= vector kernel, global gather
 // k_yuv_xsub_vec's structure with the input side replaced: whole-dword loads and stores, 8 luma samples per thread and row,
-// 2^OCSY rows per thread, lattice taps gathered from L1/L2.  NC = 1: three planes; 3 | 4: one packed image (8 pixels = 6, 8, 12 or
+// 2^OCSY rows per thread, lattice taps gathered from L1/L2 (frame written out: see k_yuv_vec).  NC = 1: three planes; 3 | 4: one packed image (8 pixels = 6, 8, 12 or
 // 16 dwords per row, unpacked as k_packed_vec does).  The component order of a packed source is a wave-uniform argument.
 
 // component `off` (runtime, wave-uniform) of pixel i of a 4-component run
@@ -130,15 +130,10 @@ __global__ __launch_bounds__(256) void k_rgb2yuv_vec(LutConsts L, YuvConsts K, P
     st_words<CWO>(P.d[2] + fr * P.dfs[2] + r * P.ds[2] + cxo, cro);
 }
 
-#define R2Y_CAT2(a, b) a##b
-#define R2Y_CAT(a, b) R2Y_CAT2(a, b)
-#define R2Y_STR2(x) #x
-#define R2Y_STR(x) R2Y_STR2(x)
-
 // The vector kernels of this translation unit's container mix; the layout checks are the caller's (launch_rgb2yuv).
-const char *R2Y_CAT(R2Y_CAT(launch_rgb2yuv_vec_w, LUTR_R2Y_WI), LUTR_R2Y_WO)(hipStream_t st, const LutConsts &L, const YuvConsts &K,
-                                                                          const PlaneSet &P, const RgbLayout &Y, const FrameGeom &G,
-                                                                          int ocsx, int ocsy, int mode)
+const char *LUTR_CAT(LUTR_CAT(launch_rgb2yuv_vec_w, LUTR_R2Y_WI), LUTR_R2Y_WO)(hipStream_t st, const LutConsts &L, const YuvConsts &K,
+                                                                                const PlaneSet &P, const RgbLayout &Y,
+                                                                                const FrameGeom &G, int ocsx, int ocsy, int mode)
 {
     constexpr int WI = LUTR_R2Y_WI, WO = LUTR_R2Y_WO;
     const long long units = (long long)(G.w / 8) * (G.rows >> ocsy) * G.nframes;
@@ -146,7 +141,7 @@ const char *R2Y_CAT(R2Y_CAT(launch_rgb2yuv_vec_w, LUTR_R2Y_WI), LUTR_R2Y_WO)(hip
 #define R2Y_CASE(C, OX, OY, I, IN) \
     if (Y.step == C && ocsx == OX && ocsy == OY && mode == I) { \
         hipLaunchKernelGGL((k_rgb2yuv_vec<WI, C, WO, OX, OY, I>), grid, block, 0, st, L, K, P, G, Y); \
-        return "k_rgb2yuv_vec<" R2Y_STR(LUTR_R2Y_WI) "," #C "," R2Y_STR(LUTR_R2Y_WO) "," #OX "," #OY "," IN ">"; \
+        return "k_rgb2yuv_vec<" LUTR_STR(LUTR_R2Y_WI) "," #C "," LUTR_STR(LUTR_R2Y_WO) "," #OX "," #OY "," IN ">"; \
     }
 #define R2Y_LAYOUT(C, OX, OY) R2Y_CASE(C, OX, OY, -1, "nolut") R2Y_CASE(C, OX, OY, 0, "0") R2Y_CASE(C, OX, OY, 1, "1") R2Y_CASE(C, OX, OY, 2, "2")
 #define R2Y_SRC(C) R2Y_LAYOUT(C, 1, 1) R2Y_LAYOUT(C, 1, 0) R2Y_LAYOUT(C, 0, 0)
@@ -175,9 +170,9 @@ __device__ __forceinline__ void r2y_block(const LutConsts &L, const GFetch &f, c
             const int xx = cx * obw + dx;
             const int x = xx < G.w ? xx : G.w - 1;
             const int e = x * Y.step;
-            const float r = ld_sample(P.s[0] + fr * P.sfs[0] + (long long)y * P.ss[0], e + Y.ro, Y.wide);
-            const float g = ld_sample(P.s[1] + fr * P.sfs[1] + (long long)y * P.ss[1], e + Y.go, Y.wide);
-            const float b = ld_sample(P.s[2] + fr * P.sfs[2] + (long long)y * P.ss[2], e + Y.bo, Y.wide);
+            const float r = ld_sample(src_row(P, 0, fr, y), e + Y.ro, Y.wide);
+            const float g = ld_sample(src_row(P, 1, fr, y), e + Y.go, Y.wide);
+            const float b = ld_sample(src_row(P, 2, fr, y), e + Y.bo, Y.wide);
             const Rgb o = mode < 0 ? Rgb{r, g, b} : lut3d_px_rt(mode, L, f, r, g, b);
             rs += o.r; gs += o.g; bs += o.b;
             if (yy < G.h && xx < G.w) sink.luma(fr, x, y, o);
@@ -186,46 +181,27 @@ __device__ __forceinline__ void r2y_block(const LutConsts &L, const GFetch &f, c
     sink.chroma(fr, cx, cy, rs, gs, bs);
 }
 
-// (the sinks R2yPlaneSink / R2yFloatSink: lutr_device.h, shared with lutr_rgbf.hip)
+// (the walk over output blocks and the sinks: lutr_device.h)
 __global__ __launch_bounds__(256) void k_rgb2yuv_generic(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, RgbLayout Y, int wout,
                                                          int ocsx, int ocsy, int mode)
 {
     const GFetch f(L);
-    const int cw = (G.w + (1 << ocsx) - 1) >> ocsx;
-    const int cr0 = G.row0 >> ocsy;
-    const int crows = ((G.row0 + G.rows + (1 << ocsy) - 1) >> ocsy) - cr0;
-    const long long total = (long long)cw * crows * G.nframes;
-    R2yPlaneSink sink{K, P, wout};
-    for (long long u = blockIdx.x * 256ll + threadIdx.x; u < total; u += (long long)gridDim.x * 256ll) {
-        const int cx = (int)(u % cw);
-        const long long t = u / cw;
-        const int cy = cr0 + (int)(t % crows);
-        const long long fr = t / crows;
-        r2y_block(L, f, P, Y, G, fr, cx, cy, ocsx, ocsy, mode, sink);
-    }
+    PlaneSink sink{K, P, wout};
+    for_each_block(G, ocsx, ocsy, false, [&](long long fr, int cx, int cy) { r2y_block(L, f, P, Y, G, fr, cx, cy, ocsx, ocsy, mode, sink); });
 }
 
 __global__ __launch_bounds__(256) void k_rgb2yuv_float(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, RgbLayout Y, FloatPlanes F,
                                                        int ocsx, int ocsy, int mode)
 {
     const GFetch f(L);
-    const int cw = (G.w + (1 << ocsx) - 1) >> ocsx, ch = (G.h + (1 << ocsy) - 1) >> ocsy;
-    const long long total = (long long)cw * ch * G.nframes;
-    R2yFloatSink sink{K, F, G, cw, ch};
-    for (long long u = blockIdx.x * 256ll + threadIdx.x; u < total; u += (long long)gridDim.x * 256ll) {
-        const int cx = (int)(u % cw);
-        const long long t = u / cw;
-        const int cy = (int)(t % ch);
-        const long long fr = t / ch;
-        r2y_block(L, f, P, Y, G, fr, cx, cy, ocsx, ocsy, mode, sink);
-    }
+    FloatSink sink(K, F, G, ocsx, ocsy);
+    for_each_block(G, ocsx, ocsy, true, [&](long long fr, int cx, int cy) { r2y_block(L, f, P, Y, G, fr, cx, cy, ocsx, ocsy, mode, sink); });
 }
 
 const char *launch_rgb2yuv_dither(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const RgbLayout &Y,
                                   const FrameGeom &G, const FloatPlanes &F, int dout, int ocsx, int ocsy, int mode)
 {
-    const long long units = (long long)((G.w + (1 << ocsx) - 1) >> ocsx) * ((G.h + (1 << ocsy) - 1) >> ocsy) * G.nframes;
-    hipLaunchKernelGGL(k_rgb2yuv_float, dim3(grid_for(units, kGridStrideCap)), dim3(256), 0, st, L, K, P, G, Y, F, ocsx, ocsy, mode);
+    hipLaunchKernelGGL(k_rgb2yuv_float, dim3(block_grid(G.w, G.h, G.nframes, ocsx, ocsy)), dim3(256), 0, st, L, K, P, G, Y, F, ocsx, ocsy, mode);
     return launch_dither_ed(st, K, P, G, F, dout > 8, ocsx, ocsy) ? "k_rgb2yuv_float+k_dither_ed" : nullptr;
 }
 
@@ -233,7 +209,6 @@ const char *launch_rgb2yuv_dither(hipStream_t st, const LutConsts &L, const YuvC
 const char *launch_rgb2yuv(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
                            const RgbLayout &Y, const FrameGeom &G, int dout, int ocsx, int ocsy, int mode)
 {
-    if (variant == VAR_VEC_LDS) return nullptr;          // no LDS kernel for this path
     const int win = Y.wide, wout = dout > 8;
     const int bh = 1 << ocsy;
     // the vector kernels' unit: 8 luma samples per row; an 8-bit source written as 16 bit has none
@@ -243,9 +218,9 @@ const char *launch_rgb2yuv(hipStream_t st, int variant, const LutConsts &L, cons
     // the 3-component vector body knows R G B and B G R order only
     const bool order_ok = Y.step != 3 || (Y.go == 1 && ((Y.ro == 0 && Y.bo == 2) || (Y.ro == 2 && Y.bo == 0)));
     auto vec_fits = [&](const PlaneSet &Q, const FrameGeom &H) {
-        if (!mix_ok || !order_ok || mode < -1 || mode > LUTR_INTERP_TETRAHEDRAL) return false;
+        if (!mix_ok || !order_ok || !(mode == -1 || vec_mode(mode))) return false;
         if (H.w % 8 || H.row0 % bh || H.rows % bh) return false;
-        if ((long long)(H.w / 8) * (H.rows / bh) * H.nframes >= 0x7fffffffll) return false;
+        if (!units_fit((long long)(H.w / 8) * (H.rows / bh) * H.nframes)) return false;
         if (Y.step == 1) {
             for (int c = 0; c < 3; c++)
                 if (!plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], 8 * bsi, batch, kStrideAny, false)) return false;
@@ -263,31 +238,14 @@ const char *launch_rgb2yuv(hipStream_t st, int variant, const LutConsts &L, cons
         return launch_rgb2yuv_vec_w00(st, L, K, Q, Y, H, ocsx, ocsy, mode);
     };
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
-        const long long units = (long long)((H.w + (1 << ocsx) - 1) >> ocsx) * ((H.rows + bh - 1) >> ocsy) * H.nframes;
-        hipLaunchKernelGGL(k_rgb2yuv_generic, dim3(grid_for(units, kGridStrideCap)), dim3(256), 0, st, L, K, Q, H, Y, wout, ocsx, ocsy, mode);
+        hipLaunchKernelGGL(k_rgb2yuv_generic, dim3(block_grid(H.w, H.rows, H.nframes, ocsx, ocsy)), dim3(256), 0, st, L, K, Q, H, Y, wout, ocsx, ocsy, mode);
         return "k_rgb2yuv_generic";
     };
-    if (variant == VAR_GENERIC) return generic(P, G);
-    if (vec_fits(P, G)) return vec(P, G);
-    if (variant == VAR_VEC_GLOBAL) return nullptr;
-    // ragged width on aligned (padded) rows: the vector kernel up to the last whole unit, the generic kernel for the rest (the
-    // split falls on a chroma block boundary: the unit is 8 luma samples wide)
-    const int wv = G.w / 8 * 8;
-    if (wv > 0 && wv < G.w) {
-        FrameGeom Gv = G, Ge = G;
-        Gv.w = wv;
-        Ge.w = G.w - wv;
-        if (vec_fits(P, Gv)) {
-            PlaneSet Pe = P;
-            for (int c = 0; c < 3; c++) Pe.s[c] += (long long)wv * Y.step * bsi;
-            Pe.d[0] += wv * bso;
-            for (int c = 1; c < 3; c++) Pe.d[c] += (wv >> ocsx) * bso;
-            const char *name = vec(P, Gv);
-            generic(Pe, Ge);
-            return name;
-        }
-    }
-    return generic(P, G);
+    // (no LDS kernel for this path; the unit is 8 luma samples wide, whole chroma blocks)
+    return launch_vec_or_generic(variant, P, G, 8, vec_fits, vec, generic, [&](int wv) {
+        const long long sb = (long long)wv * Y.step * bsi;
+        return advance_planes(P, sb, sb, wv * bso, (wv >> ocsx) * bso);
+    });
 }
 #endif  // LUTR_R2Y_WI
 

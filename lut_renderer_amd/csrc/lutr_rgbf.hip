@@ -90,7 +90,7 @@ __device__ __forceinline__ Rgb rgbf_codes(const LutConsts &L, const FloatPre &Q,
 #ifdef LUTR_RGBF_WO
 // ================================================================= fused float -> YUV vector kernel, global gather
 // k_rgb2yuv_vec's structure with the input side replaced: a thread owns 8 luma samples by 2^OCSY rows, loads them as two dwordx4
-// per plane and row, and stores whole dwords of Y, Cb and Cr.
+// per plane and row, and stores whole dwords of Y, Cb and Cr.  (Frame written out: see k_yuv_vec.)
 template <int WOUT, int OCSX, int OCSY, int INTERP>
 __global__ __launch_bounds__(256) void k_rgbf2yuv_vec(LutConsts L, FloatPre Q, YuvConsts K, PlaneSet P, FrameGeom G)
 {
@@ -166,13 +166,8 @@ __global__ __launch_bounds__(256) void k_rgbf2yuv_vec(LutConsts L, FloatPre Q, Y
     st_words<CWO>(P.d[2] + fr * P.dfs[2] + r * P.ds[2] + cxo, cro);
 }
 
-#define RGBF_CAT2(a, b) a##b
-#define RGBF_CAT(a, b) RGBF_CAT2(a, b)
-#define RGBF_STR2(x) #x
-#define RGBF_STR(x) RGBF_STR2(x)
-
 // The vector kernels of this translation unit's output container; the layout checks are the caller's (launch_rgbf2yuv).
-const char *RGBF_CAT(launch_rgbf2yuv_vec_w, LUTR_RGBF_WO)(hipStream_t st, const LutConsts &L, const FloatPre &Q, const YuvConsts &K,
+const char *LUTR_CAT(launch_rgbf2yuv_vec_w, LUTR_RGBF_WO)(hipStream_t st, const LutConsts &L, const FloatPre &Q, const YuvConsts &K,
                                                          const PlaneSet &P, const FrameGeom &G, int ocsx, int ocsy, int mode)
 {
     constexpr int WO = LUTR_RGBF_WO;
@@ -181,7 +176,7 @@ const char *RGBF_CAT(launch_rgbf2yuv_vec_w, LUTR_RGBF_WO)(hipStream_t st, const 
 #define RGBF_CASE(OX, OY, I, IN) \
     if (ocsx == OX && ocsy == OY && mode == I) { \
         hipLaunchKernelGGL((k_rgbf2yuv_vec<WO, OX, OY, I>), grid, block, 0, st, L, Q, K, P, G); \
-        return "k_rgbf2yuv_vec<" RGBF_STR(LUTR_RGBF_WO) "," #OX "," #OY "," IN ">"; \
+        return "k_rgbf2yuv_vec<" LUTR_STR(LUTR_RGBF_WO) "," #OX "," #OY "," IN ">"; \
     }
 #define RGBF_LAYOUT(OX, OY) RGBF_CASE(OX, OY, -1, "nolut") RGBF_CASE(OX, OY, 0, "0") RGBF_CASE(OX, OY, 1, "1") RGBF_CASE(OX, OY, 2, "2")
     RGBF_LAYOUT(1, 1) RGBF_LAYOUT(1, 0) RGBF_LAYOUT(0, 0)
@@ -230,13 +225,13 @@ __global__ __launch_bounds__(256) void k_rgbf_generic(LutConsts L, FloatPre Q, P
         const int x = (int)(u % G.w);
         const long long t = u / G.w;
         const long long y = G.row0 + (int)(t % G.rows), fr = t / G.rows;
-        const float r = ((const float *)(P.s[0] + fr * P.sfs[0] + y * P.ss[0]))[x];
-        const float g = ((const float *)(P.s[1] + fr * P.sfs[1] + y * P.ss[1]))[x];
-        const float b = ((const float *)(P.s[2] + fr * P.sfs[2] + y * P.ss[2]))[x];
+        const float r = ((const float *)src_row(P, 0, fr, y))[x];
+        const float g = ((const float *)src_row(P, 1, fr, y))[x];
+        const float b = ((const float *)src_row(P, 2, fr, y))[x];
         const Rgb o = rgbf_px_rt(mode, L, Q, f, r, g, b);
-        ((float *)(P.d[0] + fr * P.dfs[0] + y * P.ds[0]))[x] = o.r;
-        ((float *)(P.d[1] + fr * P.dfs[1] + y * P.ds[1]))[x] = o.g;
-        ((float *)(P.d[2] + fr * P.dfs[2] + y * P.ds[2]))[x] = o.b;
+        ((float *)dst_row(P, 0, fr, y))[x] = o.r;
+        ((float *)dst_row(P, 1, fr, y))[x] = o.g;
+        ((float *)dst_row(P, 2, fr, y))[x] = o.b;
     }
 }
 
@@ -253,9 +248,9 @@ __device__ __forceinline__ void rgbf_block(const LutConsts &L, const FloatPre &Q
         for (int dx = 0; dx < obw; dx++) {
             const int xx = cx * obw + dx;
             const int x = xx < G.w ? xx : G.w - 1;
-            const float r = ((const float *)(P.s[0] + fr * P.sfs[0] + (long long)y * P.ss[0]))[x];
-            const float g = ((const float *)(P.s[1] + fr * P.sfs[1] + (long long)y * P.ss[1]))[x];
-            const float b = ((const float *)(P.s[2] + fr * P.sfs[2] + (long long)y * P.ss[2]))[x];
+            const float r = ((const float *)src_row(P, 0, fr, y))[x];
+            const float g = ((const float *)src_row(P, 1, fr, y))[x];
+            const float b = ((const float *)src_row(P, 2, fr, y))[x];
             const Rgb o = mode < 0 ? rgbf_codes<-1>(L, Q, f, r, g, b) : quant16(rgbf_px_rt(mode, L, Q, f, r, g, b));
             rs += o.r; gs += o.g; bs += o.b;
             if (yy < G.h && xx < G.w) sink.luma(fr, x, y, o);
@@ -264,22 +259,13 @@ __device__ __forceinline__ void rgbf_block(const LutConsts &L, const FloatPre &Q
     sink.chroma(fr, cx, cy, rs, gs, bs);
 }
 
+// (the walk over output blocks and the sinks: lutr_device.h)
 __global__ __launch_bounds__(256) void k_rgbf2yuv_generic(LutConsts L, FloatPre Q, YuvConsts K, PlaneSet P, FrameGeom G, int wout,
                                                           int ocsx, int ocsy, int mode)
 {
     const GFetch f(L);
-    const int cw = (G.w + (1 << ocsx) - 1) >> ocsx;
-    const int cr0 = G.row0 >> ocsy;
-    const int crows = ((G.row0 + G.rows + (1 << ocsy) - 1) >> ocsy) - cr0;
-    const long long total = (long long)cw * crows * G.nframes;
-    R2yPlaneSink sink{K, P, wout};
-    for (long long u = blockIdx.x * 256ll + threadIdx.x; u < total; u += (long long)gridDim.x * 256ll) {
-        const int cx = (int)(u % cw);
-        const long long t = u / cw;
-        const int cy = cr0 + (int)(t % crows);
-        const long long fr = t / crows;
-        rgbf_block(L, Q, f, P, G, fr, cx, cy, ocsx, ocsy, mode, sink);
-    }
+    PlaneSink sink{K, P, wout};
+    for_each_block(G, ocsx, ocsy, false, [&](long long fr, int cx, int cy) { rgbf_block(L, Q, f, P, G, fr, cx, cy, ocsx, ocsy, mode, sink); });
 }
 
 // the dither path's pass 1: unquantised Y, Cb, Cr of whole frames
@@ -287,27 +273,18 @@ __global__ __launch_bounds__(256) void k_rgbf2yuv_float(LutConsts L, FloatPre Q,
                                                         int ocsx, int ocsy, int mode)
 {
     const GFetch f(L);
-    const int cw = (G.w + (1 << ocsx) - 1) >> ocsx, ch = (G.h + (1 << ocsy) - 1) >> ocsy;
-    const long long total = (long long)cw * ch * G.nframes;
-    R2yFloatSink sink{K, F, G, cw, ch};
-    for (long long u = blockIdx.x * 256ll + threadIdx.x; u < total; u += (long long)gridDim.x * 256ll) {
-        const int cx = (int)(u % cw);
-        const long long t = u / cw;
-        const int cy = (int)(t % ch);
-        const long long fr = t / ch;
-        rgbf_block(L, Q, f, P, G, fr, cx, cy, ocsx, ocsy, mode, sink);
-    }
+    FloatSink sink(K, F, G, ocsx, ocsy);
+    for_each_block(G, ocsx, ocsy, true, [&](long long fr, int cx, int cy) { rgbf_block(L, Q, f, P, G, fr, cx, cy, ocsx, ocsy, mode, sink); });
 }
 
 // ================================================================= launchers
 const char *launch_rgbf(hipStream_t st, int variant, const LutConsts &L, const FloatPre &Q, const PlaneSet &P, const FrameGeom &G,
                         int mode)
 {
-    if (variant == VAR_VEC_LDS) return nullptr;          // no LDS kernel for this path
     const bool batch = G.nframes > 1;
     auto vec_fits = [&](const PlaneSet &S, const FrameGeom &H) {
-        if (mode < LUTR_INTERP_NEAREST || mode > LUTR_INTERP_TETRAHEDRAL || H.w % 4) return false;
-        if ((long long)(H.w / 4) * H.rows * H.nframes >= 0x7fffffffll) return false;
+        if (!vec_mode(mode) || H.w % 4) return false;
+        if (!units_fit((long long)(H.w / 4) * H.rows * H.nframes)) return false;
         for (int c = 0; c < 3; c++)
             if (!planes_ok(S, c, 16, batch, kStrideAny, false)) return false;
         return true;
@@ -325,46 +302,30 @@ const char *launch_rgbf(hipStream_t st, int variant, const LutConsts &L, const F
                            S, H, mode);
         return "k_rgbf_generic";
     };
-    if (variant == VAR_GENERIC) return generic(P, G);
-    if (vec_fits(P, G)) return vec(P, G);
-    if (variant == VAR_VEC_GLOBAL) return nullptr;
-    // ragged width on aligned (padded) rows: the vector kernel up to the last whole unit, the generic kernel for the rest
-    const int wv = G.w / 4 * 4;
-    if (wv > 0 && wv < G.w) {
-        FrameGeom Gv = G, Ge = G;
-        Gv.w = wv;
-        Ge.w = G.w - wv;
-        if (vec_fits(P, Gv)) {
-            PlaneSet Pe = P;
-            for (int c = 0; c < 3; c++) { Pe.s[c] += (long long)wv * 4; Pe.d[c] += (long long)wv * 4; }
-            const char *name = vec(P, Gv);
-            generic(Pe, Ge);
-            return name;
-        }
-    }
-    return generic(P, G);
+    // (no LDS kernel for this path; the unit is 4 pixels wide)
+    return launch_vec_or_generic(variant, P, G, 4, vec_fits, vec, generic, [&](int wv) {
+        return advance_planes(P, (long long)wv * 4, (long long)wv * 4, (long long)wv * 4, (long long)wv * 4);
+    });
 }
 
 const char *launch_rgbf2yuv_dither(hipStream_t st, const LutConsts &L, const FloatPre &Q, const YuvConsts &K, const PlaneSet &P,
                                    const FrameGeom &G, const FloatPlanes &F, int dout, int ocsx, int ocsy, int mode)
 {
-    const long long units = (long long)((G.w + (1 << ocsx) - 1) >> ocsx) * ((G.h + (1 << ocsy) - 1) >> ocsy) * G.nframes;
-    hipLaunchKernelGGL(k_rgbf2yuv_float, dim3(grid_for(units, kGridStrideCap)), dim3(256), 0, st, L, Q, K, P, G, F, ocsx, ocsy, mode);
+    hipLaunchKernelGGL(k_rgbf2yuv_float, dim3(block_grid(G.w, G.h, G.nframes, ocsx, ocsy)), dim3(256), 0, st, L, Q, K, P, G, F, ocsx, ocsy, mode);
     return launch_dither_ed(st, K, P, G, F, dout > 8, ocsx, ocsy) ? "k_rgbf2yuv_float+k_dither_ed" : nullptr;
 }
 
 const char *launch_rgbf2yuv(hipStream_t st, int variant, const LutConsts &L, const FloatPre &Q, const YuvConsts &K, const PlaneSet &P,
                             const FrameGeom &G, int dout, int ocsx, int ocsy, int mode)
 {
-    if (variant == VAR_VEC_LDS) return nullptr;          // no LDS kernel for this path
     const int wout = dout > 8;
     const int bh = 1 << ocsy;
     const long long bso = wout ? 2 : 1;
     const bool batch = G.nframes > 1;
     auto vec_fits = [&](const PlaneSet &S, const FrameGeom &H) {
-        if (mode < -1 || mode > LUTR_INTERP_TETRAHEDRAL) return false;
+        if (!(mode == -1 || vec_mode(mode))) return false;
         if (H.w % 8 || H.row0 % bh || H.rows % bh) return false;
-        if ((long long)(H.w / 8) * (H.rows / bh) * H.nframes >= 0x7fffffffll) return false;
+        if (!units_fit((long long)(H.w / 8) * (H.rows / bh) * H.nframes)) return false;
         for (int c = 0; c < 3; c++)
             if (!plane_ok(S.s[c], S.ss[c], S.sfs[c], 16, batch, kStrideAny, false)) return false;
         if (!plane_ok(S.d[0], S.ds[0], S.dfs[0], 8 * bso, batch, kStrideAny, false)) return false;
@@ -376,30 +337,13 @@ const char *launch_rgbf2yuv(hipStream_t st, int variant, const LutConsts &L, con
         return wout ? launch_rgbf2yuv_vec_w1(st, L, Q, K, S, H, ocsx, ocsy, mode) : launch_rgbf2yuv_vec_w0(st, L, Q, K, S, H, ocsx, ocsy, mode);
     };
     auto generic = [&](const PlaneSet &S, const FrameGeom &H) {
-        const long long units = (long long)((H.w + (1 << ocsx) - 1) >> ocsx) * ((H.rows + bh - 1) >> ocsy) * H.nframes;
-        hipLaunchKernelGGL(k_rgbf2yuv_generic, dim3(grid_for(units, kGridStrideCap)), dim3(256), 0, st, L, Q, K, S, H, wout, ocsx, ocsy, mode);
+        hipLaunchKernelGGL(k_rgbf2yuv_generic, dim3(block_grid(H.w, H.rows, H.nframes, ocsx, ocsy)), dim3(256), 0, st, L, Q, K, S, H, wout, ocsx, ocsy, mode);
         return "k_rgbf2yuv_generic";
     };
-    if (variant == VAR_GENERIC) return generic(P, G);
-    if (vec_fits(P, G)) return vec(P, G);
-    if (variant == VAR_VEC_GLOBAL) return nullptr;
-    // ragged width on aligned (padded) rows: the split falls on a chroma block boundary (the unit is 8 luma samples wide)
-    const int wv = G.w / 8 * 8;
-    if (wv > 0 && wv < G.w) {
-        FrameGeom Gv = G, Ge = G;
-        Gv.w = wv;
-        Ge.w = G.w - wv;
-        if (vec_fits(P, Gv)) {
-            PlaneSet Pe = P;
-            for (int c = 0; c < 3; c++) Pe.s[c] += (long long)wv * 4;
-            Pe.d[0] += wv * bso;
-            for (int c = 1; c < 3; c++) Pe.d[c] += (wv >> ocsx) * bso;
-            const char *name = vec(P, Gv);
-            generic(Pe, Ge);
-            return name;
-        }
-    }
-    return generic(P, G);
+    // (no LDS kernel for this path; the unit is 8 luma samples wide, whole chroma blocks)
+    return launch_vec_or_generic(variant, P, G, 8, vec_fits, vec, generic, [&](int wv) {
+        return advance_planes(P, (long long)wv * 4, (long long)wv * 4, wv * bso, (wv >> ocsx) * bso);
+    });
 }
 #endif  // LUTR_RGBF_WO
 

@@ -11,7 +11,7 @@
 //             code << shift on output (low bits zero)
 // Both sides have the same chroma subsampling (csx = 1); each side is planar or semi-planar on its own.
 //
-// One source, two kinds of translation unit (Makefile SM_RULE):
+// One source, two kinds of translation unit (Makefile MIX_RULE):
 //   without LUTR_SM_WI   the generic kernel and the launcher
 //   LUTR_SM_WI / _WO     the vector kernels of one container mix (8 -> 8, 16 -> 16, 16 -> 8): 3 side pairs x 2 layouts x 3 modes
 #include "lutr_device.h"
@@ -23,9 +23,8 @@ namespace lutr {
 // ================================================================= vector kernel, global gather
 // k_yuv_xsub_vec's structure (lutr_xsub.hip): whole-word loads and stores, VB bytes of luma per thread and row, 2^CSY luma rows
 // and one chroma row per thread, lattice taps gathered from L1/L2, the thread walks its chroma blocks one after the other.
-// A semi-planar side moves the thread's Cb and Cr in ONE access of twice the width; a planar side in two.
-template <int WIN, int WOUT> constexpr int semi_vec_bytes() { return (WIN && !WOUT) ? 16 : 8; }
-
+// A semi-planar side moves the thread's Cb and Cr in ONE access of twice the width; a planar side in two.  (Frame written out: see
+// k_yuv_vec.)
 // sample i of a word vector whose 16-bit codes sit `shift` bits up in their container: the shift rides in the bit-field extract
 // that unpacks the sample anyway
 template <int WIDE>
@@ -47,7 +46,7 @@ template <int WIN, int WOUT, int SI, int SO, int CSX, int CSY, int INTERP>
 __global__ __launch_bounds__(256) void k_yuv_semi_vec(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, SemiArgs A)
 {
     static_assert(CSX == 1, "semi-planar formats are 4:2:0 or 4:2:2");
-    constexpr int VB = semi_vec_bytes<WIN, WOUT>();
+    constexpr int VB = vec_bytes<WIN, WOUT>();
     constexpr int PXT = VB / (WIN ? 2 : 1);                       // luma samples per thread per row
     constexpr int YWI = VB / 4, YWO = PXT * (WOUT ? 2 : 1) / 4;   // luma words per thread per row, in / out
     constexpr int BH = 1 << CSY;                                  // the chroma block is 2 x BH
@@ -153,24 +152,19 @@ __global__ __launch_bounds__(256) void k_yuv_semi_vec(LutConsts L, YuvConsts K, 
     }
 }
 
-#define SM_CAT2(a, b) a##b
-#define SM_CAT(a, b) SM_CAT2(a, b)
-#define SM_STR2(x) #x
-#define SM_STR(x) SM_STR2(x)
-
 // The vector kernels of this translation unit's container mix; the layout checks are the caller's (launch_yuv_semi).
-const char *SM_CAT(SM_CAT(launch_yuv_semi_vec_w, LUTR_SM_WI), LUTR_SM_WO)(hipStream_t st, const LutConsts &L, const YuvConsts &K,
-                                                                         const PlaneSet &P, const FrameGeom &G, const SemiArgs &A,
-                                                                         int csy, int mode)
+const char *LUTR_CAT(LUTR_CAT(launch_yuv_semi_vec_w, LUTR_SM_WI), LUTR_SM_WO)(hipStream_t st, const LutConsts &L, const YuvConsts &K,
+                                                                               const PlaneSet &P, const FrameGeom &G,
+                                                                               const SemiArgs &A, int csy, int mode)
 {
     constexpr int WI = LUTR_SM_WI, WO = LUTR_SM_WO;
-    constexpr int PXT = semi_vec_bytes<WI, WO>() / (WI ? 2 : 1);
+    constexpr int PXT = vec_bytes<WI, WO>() / (WI ? 2 : 1);
     const long long units = (long long)(G.w / PXT) * (G.rows >> csy) * G.nframes;
     const dim3 grid((unsigned)((units + 255) / 256)), block(256);
 #define SM_CASE(SI, SO, Y, I) \
     if (A.isemi == SI && A.osemi == SO && csy == Y && mode == I) { \
         hipLaunchKernelGGL((k_yuv_semi_vec<WI, WO, SI, SO, 1, Y, I>), grid, block, 0, st, L, K, P, G, A); \
-        return "k_yuv_semi_vec<" SM_STR(LUTR_SM_WI) "," SM_STR(LUTR_SM_WO) "," #SI "," #SO ",1," #Y "," #I ">"; \
+        return "k_yuv_semi_vec<" LUTR_STR(LUTR_SM_WI) "," LUTR_STR(LUTR_SM_WO) "," #SI "," #SO ",1," #Y "," #I ">"; \
     }
 #define SM_SIDES(SI, SO) SM_CASE(SI, SO, 1, 0) SM_CASE(SI, SO, 1, 1) SM_CASE(SI, SO, 1, 2) \
                          SM_CASE(SI, SO, 0, 0) SM_CASE(SI, SO, 0, 1) SM_CASE(SI, SO, 0, 2)
@@ -198,6 +192,7 @@ __device__ __forceinline__ void st_code(uint8_t *row, long long x, int wide, int
     else row[x] = (uint8_t)u;
 }
 
+// (its own block walk, not for_each_block of lutr_device.h: with the shared walk it takes 73 VGPRs for 72, 6 waves per SIMD for 7)
 __global__ __launch_bounds__(256) void k_yuv_semi_generic(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, SemiArgs A, int win,
                                                           int wout, int csy, int mode)
 {
@@ -250,7 +245,6 @@ __global__ __launch_bounds__(256) void k_yuv_semi_generic(LutConsts L, YuvConsts
 const char *launch_yuv_semi(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
                             const FrameGeom &G, const SemiArgs &A, int din, int dout, int csy, int mode)
 {
-    if (variant == VAR_VEC_LDS) return nullptr;          // no LDS-window kernel for semi-planar frames
     const int win = din > 8, wout = dout > 8;
     const int bh = 1 << csy;
     // the vector kernels' unit: 8 bytes of luma per row (16 for a 16-bit source written as 8 bit); 8 -> 16 bit has none, nor has
@@ -260,9 +254,9 @@ const char *launch_yuv_semi(hipStream_t st, int variant, const LutConsts &L, con
     const long long bsi = win ? 2 : 1, bso = wout ? 2 : 1;
     const bool batch = G.nframes > 1;
     auto vec_fits = [&](const PlaneSet &Q, const FrameGeom &H) {
-        if (!mix_ok || !(mode == LUTR_INTERP_NEAREST || mode == LUTR_INTERP_TRILINEAR || mode == LUTR_INTERP_TETRAHEDRAL)) return false;
+        if (!mix_ok || !vec_mode(mode)) return false;
         if (H.w % pxt || H.row0 % bh || H.rows % bh) return false;
-        if ((long long)(H.w / pxt) * (H.rows / bh) * H.nframes >= 0x7fffffffll) return false;
+        if (!units_fit((long long)(H.w / pxt) * (H.rows / bh) * H.nframes)) return false;
         if (!plane_ok(Q.s[0], Q.ss[0], Q.sfs[0], pxt * bsi, batch, kStrideAny, false) || !plane_ok(Q.d[0], Q.ds[0], Q.dfs[0], pxt * bso, batch, kStrideAny, false))
             return false;
         // a plane of pairs moves pxt / 2 pairs = pxt samples per access, a planar chroma plane pxt / 2 samples
@@ -278,33 +272,13 @@ const char *launch_yuv_semi(hipStream_t st, int variant, const LutConsts &L, con
         return launch_yuv_semi_vec_w00(st, L, K, Q, H, A, csy, mode);
     };
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
-        const long long units = (long long)((H.w + 1) >> 1) * ((H.rows + bh - 1) >> csy) * H.nframes;
-        hipLaunchKernelGGL(k_yuv_semi_generic, dim3(grid_for(units, kGridStrideCap)), dim3(256), 0, st, L, K, Q, H, A, win, wout, csy, mode);
+        hipLaunchKernelGGL(k_yuv_semi_generic, dim3(block_grid(H.w, H.rows, H.nframes, 1, csy)), dim3(256), 0, st, L, K, Q, H, A, win, wout, csy, mode);
         return "k_yuv_semi_generic";
     };
-    if (variant == VAR_GENERIC) return generic(P, G);
-    if (vec_fits(P, G)) return vec(P, G);
-    if (variant == VAR_VEC_GLOBAL) return nullptr;
-    // ragged width on aligned (padded) rows: the vector kernel up to the last whole unit, the generic kernel for the rest (the
-    // split falls on a chroma-block boundary: the unit is 4 or 8 luma samples wide)
-    const int wv = G.w / pxt * pxt;
-    if (wv > 0 && wv < G.w) {
-        FrameGeom Gv = G, Ge = G;
-        Gv.w = wv;
-        Ge.w = G.w - wv;
-        if (vec_fits(P, Gv)) {
-            PlaneSet Pe = P;
-            Pe.s[0] += wv * bsi; Pe.d[0] += wv * bso;
-            for (int c = 1; c < 3; c++) {
-                if (Pe.s[c]) Pe.s[c] += (A.isemi ? wv : wv >> 1) * bsi;
-                if (Pe.d[c]) Pe.d[c] += (A.osemi ? wv : wv >> 1) * bso;
-            }
-            const char *name = vec(P, Gv);
-            generic(Pe, Ge);
-            return name;
-        }
-    }
-    return generic(P, G);
+    // (no LDS-window kernel for semi-planar frames; the unit is 4 or 8 luma samples wide, whole chroma blocks)
+    return launch_vec_or_generic(variant, P, G, pxt, vec_fits, vec, generic, [&](int wv) {
+        return advance_planes(P, wv * bsi, (A.isemi ? wv : wv >> 1) * bsi, wv * bso, (A.osemi ? wv : wv >> 1) * bso);
+    });
 }
 #endif  // LUTR_SM_WI
 

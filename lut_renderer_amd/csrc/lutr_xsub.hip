@@ -9,7 +9,7 @@
 // The unit of work is the union block, 2^max(icsx, ocsx) x 2^max(icsy, ocsy) luma samples: it holds whole input and whole
 // output chroma blocks.
 //
-// One source, two kinds of translation unit (Makefile XS_RULE):
+// One source, two kinds of translation unit (Makefile MIX_RULE):
 //   without LUTR_XS_WI   the generic kernel, the unquantised pass of the dither path and the launcher
 //   LUTR_XS_WI / _WO     the vector kernels of one container mix (8 -> 8, 16 -> 16, 16 -> 8): 6 layout pairs x 3 modes
 #include "lutr_device.h"
@@ -17,19 +17,15 @@
 
 namespace lutr {
 
-constexpr int cmax(int a, int b) { return a > b ? a : b; }
-
 #ifdef LUTR_XS_WI
 // ================================================================= vector kernel, global gather
 // k_yuv_vec's structure (lutr_kernels.hip): whole-word loads and stores, VB bytes of luma per thread and row, BH luma rows per
 // thread, lattice taps gathered from L1/L2.  The thread's input chroma rows (BH >> ICSY) and output chroma rows (BH >> OCSY)
-// are separate arrays; the thread walks its union blocks one after the other.
-template <int WIN, int WOUT> constexpr int xsub_vec_bytes() { return (WIN && !WOUT) ? 16 : 8; }
-
+// are separate arrays; the thread walks its union blocks one after the other.  (Frame written out: see k_yuv_vec.)
 template <int WIN, int WOUT, int ICSX, int ICSY, int OCSX, int OCSY, int INTERP>
 __global__ __launch_bounds__(256) void k_yuv_xsub_vec(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G)
 {
-    constexpr int VB = xsub_vec_bytes<WIN, WOUT>();
+    constexpr int VB = vec_bytes<WIN, WOUT>();
     constexpr int PXT = VB / (WIN ? 2 : 1);                       // luma samples per thread per row
     constexpr int YWI = VB / 4, YWO = PXT * (WOUT ? 2 : 1) / 4;   // luma words per thread per row, in / out
     constexpr int CSX = cmax(ICSX, OCSX), CSY = cmax(ICSY, OCSY);
@@ -130,25 +126,20 @@ __global__ __launch_bounds__(256) void k_yuv_xsub_vec(LutConsts L, YuvConsts K, 
     }
 }
 
-#define XS_CAT2(a, b) a##b
-#define XS_CAT(a, b) XS_CAT2(a, b)
-#define XS_STR2(x) #x
-#define XS_STR(x) XS_STR2(x)
-
 // The vector kernels of this translation unit's container mix; the layout checks are the caller's (launch_yuv_xsub).
-const char *XS_CAT(XS_CAT(launch_yuv_xsub_vec_w, LUTR_XS_WI), LUTR_XS_WO)(hipStream_t st, const LutConsts &L, const YuvConsts &K,
-                                                                         const PlaneSet &P, const FrameGeom &G, int icsx,
-                                                                         int icsy, int ocsx, int ocsy, int mode)
+const char *LUTR_CAT(LUTR_CAT(launch_yuv_xsub_vec_w, LUTR_XS_WI), LUTR_XS_WO)(hipStream_t st, const LutConsts &L, const YuvConsts &K,
+                                                                               const PlaneSet &P, const FrameGeom &G, int icsx,
+                                                                               int icsy, int ocsx, int ocsy, int mode)
 {
     constexpr int WI = LUTR_XS_WI, WO = LUTR_XS_WO;
-    constexpr int PXT = xsub_vec_bytes<WI, WO>() / (WI ? 2 : 1);
+    constexpr int PXT = vec_bytes<WI, WO>() / (WI ? 2 : 1);
     const int bh = 1 << cmax(icsy, ocsy);
     const long long units = (long long)(G.w / PXT) * (G.rows / bh) * G.nframes;
     const dim3 grid((unsigned)((units + 255) / 256)), block(256);
 #define XS_CASE(IX, IY, OX, OY, I) \
     if (icsx == IX && icsy == IY && ocsx == OX && ocsy == OY && mode == I) { \
         hipLaunchKernelGGL((k_yuv_xsub_vec<WI, WO, IX, IY, OX, OY, I>), grid, block, 0, st, L, K, P, G); \
-        return "k_yuv_xsub_vec<" XS_STR(LUTR_XS_WI) "," XS_STR(LUTR_XS_WO) "," #IX "," #IY "," #OX "," #OY "," #I ">"; \
+        return "k_yuv_xsub_vec<" LUTR_STR(LUTR_XS_WI) "," LUTR_STR(LUTR_XS_WO) "," #IX "," #IY "," #OX "," #OY "," #I ">"; \
     }
 #define XS_PAIR(IX, IY, OX, OY) XS_CASE(IX, IY, OX, OY, 0) XS_CASE(IX, IY, OX, OY, 1) XS_CASE(IX, IY, OX, OY, 2)
     XS_PAIR(1, 1, 1, 0) XS_PAIR(1, 1, 0, 0)
@@ -181,9 +172,9 @@ __device__ __forceinline__ void xsub_union_block(const LutConsts &L, const GFetc
                 for (int dx = 0; dx < obw; dx++) {
                     const int xx = ux * bw + ox + dx;
                     const int x = xx < G.w ? xx : G.w - 1;
-                    const float cbv = ld_sample(P.s[1] + fr * P.sfs[1] + (long long)(y >> icsy) * P.ss[1], x >> icsx, win);
-                    const float crv = ld_sample(P.s[2] + fr * P.sfs[2] + (long long)(y >> icsy) * P.ss[2], x >> icsx, win);
-                    const float yv = ld_sample(P.s[0] + fr * P.sfs[0] + (long long)y * P.ss[0], x, win);
+                    const float cbv = ld_sample(src_row(P, 1, fr, y >> icsy), x >> icsx, win);
+                    const float crv = ld_sample(src_row(P, 2, fr, y >> icsy), x >> icsx, win);
+                    const float yv = ld_sample(src_row(P, 0, fr, y), x, win);
                     const Rgb q = yuv_to_rgb(K, yv, chroma_terms(K, cbv, crv));
                     const Rgb o = lut3d_px_rt(mode, L, f, q.r, q.g, q.b);
                     rs += o.r; gs += o.g; bs += o.b;
@@ -191,102 +182,55 @@ __device__ __forceinline__ void xsub_union_block(const LutConsts &L, const GFetc
                 }
             }
             const int ocx = (ux * bw + ox) >> ocsx, ocy = (uy * bh + oy) >> ocsy;
-            if (ocx < cwo && ocy < cho) sink.chroma(fr, ocx, ocy, cwo, cho, rs, gs, bs);
+            if (ocx < cwo && ocy < cho) sink.chroma(fr, ocx, ocy, rs, gs, bs);
         }
     }
 }
 
-struct PlaneSink {
-    const YuvConsts &K;
-    const PlaneSet &P;
-    int wout;
-    __device__ __forceinline__ void luma(long long fr, int x, int y, const Rgb &o)
-    {
-        st_sample(P.d[0] + fr * P.dfs[0] + (long long)y * P.ds[0], x, wout, rgb_to_y(K, o));
-    }
-    __device__ __forceinline__ void chroma(long long fr, int cx, int cy, int, int, float rs, float gs, float bs)
-    {
-        st_sample(P.d[1] + fr * P.dfs[1] + (long long)cy * P.ds[1], cx, wout, rgb_to_cb(K, rs, gs, bs));
-        st_sample(P.d[2] + fr * P.dfs[2] + (long long)cy * P.ds[2], cx, wout, rgb_to_cr(K, rs, gs, bs));
-    }
-};
-
-// the dither path's pass 1 (k_yuv_float's values, lutr_dither.hip): unquantised planes, densely packed per frame
-struct FloatSink {
-    const YuvConsts &K;
-    const FloatPlanes &F;
-    const FrameGeom &G;
-    __device__ __forceinline__ void luma(long long fr, int x, int y, const Rgb &o)
-    {
-        F.y[(fr * G.h + y) * G.w + x] = fma_(K.cyr, o.r, fma_(K.cyg, o.g, fma_(K.cyb, o.b, K.yob))) - 0.5f;
-    }
-    __device__ __forceinline__ void chroma(long long fr, int cx, int cy, int cw, int ch, float rs, float gs, float bs)
-    {
-        F.cb[(fr * ch + cy) * cw + cx] = fma_(K.cbr, rs, fma_(K.cbg, gs, fma_(K.cbb, bs, K.cob))) - 0.5f;
-        F.cr[(fr * ch + cy) * cw + cx] = fma_(K.crr, rs, fma_(K.crg, gs, fma_(K.crb, bs, K.cob))) - 0.5f;
-    }
-};
-
+// (the walk over union blocks and the sinks: lutr_device.h)
 __global__ __launch_bounds__(256) void k_yuv_xsub_generic(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, int win, int wout,
                                                           int icsx, int icsy, int ocsx, int ocsy, int mode)
 {
     const GFetch f(L);
-    const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy);
-    const int uw = (G.w + (1 << csx) - 1) >> csx;
-    const int ur0 = G.row0 >> csy;
-    const int urows = ((G.row0 + G.rows + (1 << csy) - 1) >> csy) - ur0;
-    const long long total = (long long)uw * urows * G.nframes;
     PlaneSink sink{K, P, wout};
-    for (long long u = blockIdx.x * 256ll + threadIdx.x; u < total; u += (long long)gridDim.x * 256ll) {
-        const int ux = (int)(u % uw);
-        const long long t = u / uw;
-        const int uy = ur0 + (int)(t % urows);
-        const long long fr = t / urows;
+    for_each_block(G, cmax(icsx, ocsx), cmax(icsy, ocsy), false, [&](long long fr, int ux, int uy) {
         xsub_union_block(L, f, K, P, G, fr, ux, uy, win, icsx, icsy, ocsx, ocsy, mode, sink);
-    }
+    });
 }
 
+// the dither path's pass 1 (k_yuv_float's values, lutr_dither.hip): whole frames, chroma planes in the output layout
 __global__ __launch_bounds__(256) void k_yuv_float_xsub(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, FloatPlanes F, int win,
                                                         int icsx, int icsy, int ocsx, int ocsy, int mode)
 {
     const GFetch f(L);
-    const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy);
-    const int uw = (G.w + (1 << csx) - 1) >> csx, uh = (G.h + (1 << csy) - 1) >> csy;
-    const long long total = (long long)uw * uh * G.nframes;
-    FloatSink sink{K, F, G};
-    for (long long u = blockIdx.x * 256ll + threadIdx.x; u < total; u += (long long)gridDim.x * 256ll) {
-        const int ux = (int)(u % uw);
-        const long long t = u / uw;
-        const int uy = (int)(t % uh);
-        const long long fr = t / uh;
+    FloatSink sink(K, F, G, ocsx, ocsy);
+    for_each_block(G, cmax(icsx, ocsx), cmax(icsy, ocsy), true, [&](long long fr, int ux, int uy) {
         xsub_union_block(L, f, K, P, G, fr, ux, uy, win, icsx, icsy, ocsx, ocsy, mode, sink);
-    }
+    });
 }
 
 void launch_yuv_float_xsub(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
                            const FloatPlanes &F, int win, int icsx, int icsy, int ocsx, int ocsy, int mode)
 {
-    const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy);
-    const long long units = (long long)((G.w + (1 << csx) - 1) >> csx) * ((G.h + (1 << csy) - 1) >> csy) * G.nframes;
-    hipLaunchKernelGGL(k_yuv_float_xsub, dim3(grid_for(units, kGridStrideCap)), dim3(256), 0, st, L, K, P, G, F, win, icsx, icsy, ocsx, ocsy, mode);
+    hipLaunchKernelGGL(k_yuv_float_xsub, dim3(block_grid(G.w, G.h, G.nframes, cmax(icsx, ocsx), cmax(icsy, ocsy))), dim3(256), 0, st,
+                       L, K, P, G, F, win, icsx, icsy, ocsx, ocsy, mode);
 }
 
 // ================================================================= launcher
 const char *launch_yuv_xsub(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
                             const FrameGeom &G, int din, int dout, int icsx, int icsy, int ocsx, int ocsy, int mode)
 {
-    if (variant == VAR_VEC_LDS) return nullptr;          // no LDS-window kernel for a subsampling change
     const int win = din > 8, wout = dout > 8;
-    const int bh = 1 << cmax(icsy, ocsy);
+    const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy), bh = 1 << csy;
     // the vector kernels' unit: 8 bytes of luma per row (16 for a 16-bit source written as 8 bit); 8 -> 16 bit has none
     const bool mix_ok = win == wout || (win && !wout);
     const int pxt = (win && !wout) ? 8 : (win ? 4 : 8);
     const long long bsi = win ? 2 : 1, bso = wout ? 2 : 1;
     const bool batch = G.nframes > 1;
     auto vec_fits = [&](const PlaneSet &Q, const FrameGeom &H) {
-        if (!mix_ok || !(mode == LUTR_INTERP_NEAREST || mode == LUTR_INTERP_TRILINEAR || mode == LUTR_INTERP_TETRAHEDRAL)) return false;
+        if (!mix_ok || !vec_mode(mode)) return false;
         if (H.w % pxt || H.row0 % bh || H.rows % bh) return false;
-        if ((long long)(H.w / pxt) * (H.rows / bh) * H.nframes >= 0x7fffffffll) return false;
+        if (!units_fit((long long)(H.w / pxt) * (H.rows / bh) * H.nframes)) return false;
         if (!plane_ok(Q.s[0], Q.ss[0], Q.sfs[0], pxt * bsi, batch, kStrideAny, false) || !plane_ok(Q.d[0], Q.ds[0], Q.dfs[0], pxt * bso, batch, kStrideAny, false))
             return false;
         for (int c = 1; c < 3; c++)
@@ -301,32 +245,14 @@ const char *launch_yuv_xsub(hipStream_t st, int variant, const LutConsts &L, con
         return launch_yuv_xsub_vec_w00(st, L, K, Q, H, icsx, icsy, ocsx, ocsy, mode);
     };
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
-        const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy);
-        const long long units = (long long)((H.w + (1 << csx) - 1) >> csx) * ((H.rows + bh - 1) >> csy) * H.nframes;
-        hipLaunchKernelGGL(k_yuv_xsub_generic, dim3(grid_for(units, kGridStrideCap)), dim3(256), 0, st, L, K, Q, H, win, wout, icsx, icsy, ocsx, ocsy,
-                           mode);
+        hipLaunchKernelGGL(k_yuv_xsub_generic, dim3(block_grid(H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, K, Q, H, win,
+                           wout, icsx, icsy, ocsx, ocsy, mode);
         return "k_yuv_xsub_generic";
     };
-    if (variant == VAR_GENERIC) return generic(P, G);
-    if (vec_fits(P, G)) return vec(P, G);
-    if (variant == VAR_VEC_GLOBAL) return nullptr;
-    // ragged width on aligned (padded) rows: the vector kernel up to the last whole unit, the generic kernel for the rest (the
-    // split falls on a union-block boundary: the unit is 4, 8 or 16 luma samples wide)
-    const int wv = G.w / pxt * pxt;
-    if (wv > 0 && wv < G.w) {
-        FrameGeom Gv = G, Ge = G;
-        Gv.w = wv;
-        Ge.w = G.w - wv;
-        if (vec_fits(P, Gv)) {
-            PlaneSet Pe = P;
-            Pe.s[0] += wv * bsi; Pe.d[0] += wv * bso;
-            for (int c = 1; c < 3; c++) { Pe.s[c] += (wv >> icsx) * bsi; Pe.d[c] += (wv >> ocsx) * bso; }
-            const char *name = vec(P, Gv);
-            generic(Pe, Ge);
-            return name;
-        }
-    }
-    return generic(P, G);
+    // (no LDS-window kernel for a subsampling change; the unit is 4, 8 or 16 luma samples wide, whole union blocks)
+    return launch_vec_or_generic(variant, P, G, pxt, vec_fits, vec, generic, [&](int wv) {
+        return advance_planes(P, wv * bsi, (wv >> icsx) * bsi, wv * bso, (wv >> ocsx) * bso);
+    });
 }
 #endif  // LUTR_XS_WI
 
