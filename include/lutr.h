@@ -412,6 +412,54 @@ int lutr_apply_yuv_semi(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, con
                         const lutr_yuv_layout *out_layout, int w, int h, int nframes, const lutr_planes *src,
                         const lutr_planes *dst, int row0, int rows);
 
+/* ---- packed 4:2:2 YUV frames: yuyv422 / uyvy422 / yvyu422 and y210le / y212le / y216le, what capture cards,
+ *      V4L2 devices and 4:2:2 hardware decoders write -- the frame the reference's chain (ffmpeg.py:246, :304-310) sees after
+ *      FFmpeg's scaler has unpacked it to yuv422p* ---- */
+#define LUTR_PK_YUYV 0   /* Y0 Cb Y1 Cr: yuyv422, y210le, y212le, y216le */
+#define LUTR_PK_UYVY 1   /* Cb Y0 Cr Y1: uyvy422 */
+#define LUTR_PK_YVYU 2   /* Y0 Cr Y1 Cb: yvyu422 */
+/* The container of one side of lutr_apply_yuv_packed.
+ *   packed = 0: three planes, as lutr_apply_yuv takes them; order and shift must be 0.
+ *   packed = 1: data[0] holds ceil(w / 2) groups of four samples per row (two luma, one Cb / Cr pair), h rows, with stride[0] /
+ *               frame_stride[0] in bytes; data[1] and data[2] are ignored and may be NULL.
+ *   order     : LUTR_PK_YUYV | LUTR_PK_UYVY | LUTR_PK_YVYU, the samples of a group in memory order.
+ *   shift     : left shift of the code inside its 16-bit word, 16 - depth (y210le: 6) or 0; always 0 for an 8-bit container.
+ *               On input the code is word >> shift whatever the low bits hold; on output the low bits are zero.
+ * Odd width: the second luma sample of the last group is ignored on input and written as a copy of the last real luma sample
+ * on output; chroma follows the edge rule of lutr_apply_yuv (the edge column counts twice in the block mean). */
+typedef struct lutr_yuv_packing {
+    int32_t packed;
+    int32_t order;
+    int32_t shift;
+} lutr_yuv_packing;
+
+/* lutr_apply_yuv on frames whose source side, destination side or both are packed 4:2:2; each side's container is its own.
+ * A packed side's format (fmt_in / fmt_out of *p) is 4:2:2.  With 4:2:2 on both sides the result is bit-identical to
+ * lutr_apply_yuv on the same samples held in yuv422p* planes: everything *p expresses (depth change, the full-range prologue,
+ * matrices, ranges, lut_depth) and a .csp prelut are that call's arithmetic unchanged.  A packed source may also go to a PLANAR
+ * 4:2:0 or 4:4:4 destination: bit-identical to lutr_apply_yuv_xsub on the de-interleaved source.  Row blocks follow the rule of
+ * those calls (row0 / rows multiples of the destination's chroma block height).  When both sides are planar this IS
+ * lutr_apply_yuv / lutr_apply_yuv_xsub: same kernels, bits, last kernel.
+ * src == dst (in place) is allowed when both sides are the same packed container with the same strides; any other overlap of
+ * the source's and the destination's byte ranges fails.  Always strict precision (fast / fma32 run strict here, no suffix on
+ * the last kernel).
+ * LUTR_EINVAL with a message, before anything touches the device: packed outside 0 | 1, order outside 0..2, order or shift on a
+ * planar side, a shift other than 16 - depth or 0 on a 16-bit container, a non-zero shift on an 8-bit one, a packed side whose
+ * format is not 4:2:2, a packed destination whose fmt_in is not 4:2:2, a null pointer where a plane is needed, 16-bit containers
+ * whose base, stride or (batches) frame stride is odd, source and destination overlapping other than in place.
+ * Kernels: "k_yuv_pk_vec<win,wout,packed_in,packed_out,ocsy,interp>" (nearest / trilinear / tetrahedral; 8 -> 8, 16 -> 16 and
+ * 16 -> 8 bit containers; a 4:2:2 or planar 4:2:0 destination; width a multiple of 8 luma samples, 4 for 16 -> 16; positive
+ * strides; packed rows 16-byte aligned, planar rows aligned to k_yuv_vec's words; row0 / rows multiples of the destination's
+ * chroma block height), "k_yuv_pk_generic" for everything else (one thread per group; any depth 8..16, stride, alignment or
+ * size; all five modes; the planar 4:4:4 destination); a ragged width on aligned rows is split between the two.  Variants: auto
+ * and generic as for lutr_apply_yuv; vec_global fails with LUTR_EINVAL where the vector kernel cannot take the layout; vec_lds
+ * always fails with LUTR_EINVAL (there is no LDS kernel for this path).
+ * Not covered: a semi-planar side, a packed destination with a subsampling change, chroma siting, dither, resize, an RGB
+ * source, packed 4:4:4 (vuyx, xv30le, ayuv64le), big-endian containers. */
+int lutr_apply_yuv_packed(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, const lutr_yuv_packing *in,
+                          const lutr_yuv_packing *out, int w, int h, int nframes, const lutr_planes *src,
+                          const lutr_planes *dst, int row0, int rows);
+
 /* ---- precision ---- */
 /* STRICT (default): every kernel is a bit-exact restatement of FFmpeg's scalar C lut3d (vf_lut3d.c order of operations,
  * no fused multiply-add in the blend).  FAST: permission to use the tolerance-bounded tile kernels -- lattice staged as

@@ -40,7 +40,7 @@ SYMBOLS = (
     "lutr_apply_planar_rgb", "lutr_apply_packed_rgb", "lutr_apply_yuv", "lutr_apply_yuv_dither",
     "lutr_apply_yuv_sited", "lutr_yuv_constants_sited", "lutr_apply_yuv_xsub", "lutr_yuv_constants_xsub",
     "lutr_apply_rgb_to_yuv", "lutr_yuv_constants_rgb2yuv",
-    "lutr_apply_planar_rgb_f32", "lutr_apply_rgbf_to_yuv", "lutr_apply_yuv_semi",
+    "lutr_apply_planar_rgb_f32", "lutr_apply_rgbf_to_yuv", "lutr_apply_yuv_semi", "lutr_apply_yuv_packed",
     "lutr_resize_filter", "lutr_resize_planes",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
 )
@@ -65,6 +65,11 @@ class Planes(C.Structure):
 class YuvLayout(C.Structure):
     """struct lutr_yuv_layout: the container of one side of lutr_apply_yuv_semi"""
     _fields_ = [("semi", C.c_int32), ("swap", C.c_int32), ("shift", C.c_int32)]
+
+
+class YuvPacking(C.Structure):
+    """struct lutr_yuv_packing: the container of one side of lutr_apply_yuv_packed"""
+    _fields_ = [("packed", C.c_int32), ("order", C.c_int32), ("shift", C.c_int32)]
 
 
 class Packed(C.Structure):
@@ -92,6 +97,14 @@ SEMI_FORMATS = {
     "nv12": (8, 1, 1, 0, 0), "nv21": (8, 1, 1, 1, 0), "nv16": (8, 1, 0, 0, 0),
     "p010le": (10, 1, 1, 0, 6), "p012le": (12, 1, 1, 0, 4), "p016le": (16, 1, 1, 0, 0),
     "p210le": (10, 1, 0, 0, 6), "p212le": (12, 1, 0, 0, 4), "p216le": (16, 1, 0, 0, 0),
+}
+
+
+#: packed 4:2:2 YUV formats -> (depth, group order: 0 Y0 Cb Y1 Cr, 1 Cb Y0 Cr Y1, 2 Y0 Cr Y1 Cb, shift of the code
+#: inside its container)
+PACKED_YUV_FORMATS = {
+    "yuyv422": (8, 0, 0), "uyvy422": (8, 1, 0), "yvyu422": (8, 2, 0),
+    "y210le": (10, 0, 6), "y212le": (12, 0, 4), "y216le": (16, 0, 0),
 }
 
 
@@ -163,6 +176,8 @@ def load() -> C.CDLL:
                                            ci, ci]
     lib.lutr_apply_yuv_semi.argtypes = [vp, C.POINTER(YuvParams), ci, C.POINTER(YuvLayout), C.POINTER(YuvLayout), ci, ci, ci,
                                         C.POINTER(Planes), C.POINTER(Planes), ci, ci]
+    lib.lutr_apply_yuv_packed.argtypes = [vp, C.POINTER(YuvParams), ci, C.POINTER(YuvPacking), C.POINTER(YuvPacking), ci, ci, ci,
+                                          C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]
     lib.lutr_ctx_set_variant.argtypes = [vp, ci]

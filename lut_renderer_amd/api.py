@@ -79,8 +79,9 @@ def _cached_cube(path: Path) -> CubeLut:
 
 
 def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = None) -> dict:
-    """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv (`pix_fmt` / `out_pix_fmt` planar YUV or semi-planar names
-    such as nv12 / p010le; `out_pix_fmt` defaults to the source's own format) -- or, for an RGB `pix_fmt` (gbrp* / a packed name / a
+    """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv (`pix_fmt` / `out_pix_fmt` planar YUV, semi-planar names
+    such as nv12 / p010le, DESIGN.md 3.11, or packed 4:2:2 names such as uyvy422 / y210le; `out_pix_fmt` defaults
+    to the source's own format) -- or, for an RGB `pix_fmt` (gbrp* / a packed name / a
     float name) with a YUV `out_pix_fmt`, of LutEngine.apply_rgb_to_yuv (`is_rgb_call(kw)` tells the two apart).  A float
     `pix_fmt` (gbrpf32le / gbrapf32le) without `out_pix_fmt`, or with a float one, stays float:
     `is_float_out_call(kw)`, and LutEngine.apply_rgb_float takes `kw["interp"]`."""
@@ -117,8 +118,10 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
             kw.update(intermediate_pix_fmt=plan.intermediate_pix_fmt, prologue_out_range=plan.prologue_out_range)
         return kw
     # a semi-planar source or output (nv12, p010le, ..) is the same chain on another container
-    from .engine import check_semi_options, parse_semi_fmt
-    semi_src = parse_semi_fmt(pix_fmt)
+    # (so is a packed 4:2:2 one: uyvy422, y210le, ..)
+    from .engine import check_packed_options, check_semi_options, parse_packed_yuv_fmt, parse_semi_fmt
+    check_packed_options(pix_fmt, out_pix_fmt)                   # names the packings this path does not take
+    semi_src = parse_semi_fmt(pix_fmt) or parse_packed_yuv_fmt(pix_fmt)
     src = semi_src or parse_pix_fmt(pix_fmt)
     if src.family != "yuv":
         raise ValueError("apply_lut takes planar YUV frames; use LutEngine.apply_rgb for gbrp planes")
@@ -137,7 +140,8 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
         kw.update(range_src="tv", range_in="tv", lut_depth=src.depth)
         default_out = kw["pix_fmt"]
     kw["out_pix_fmt"] = out_pix_fmt or default_out
-    check_semi_options(kw["pix_fmt"], kw["out_pix_fmt"])         # one subsampling on both sides of a semi-planar call
+    if not check_packed_options(kw["pix_fmt"], kw["out_pix_fmt"]):
+        check_semi_options(kw["pix_fmt"], kw["out_pix_fmt"])     # one subsampling on both sides of a semi-planar call
     return kw
 
 
@@ -163,7 +167,9 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
-    chroma_loc or resolution.  With an RGB `pix_fmt` (gbrp* or a packed name such as rgb24) and a YUV
+    chroma_loc or resolution.  A packed 4:2:2 `pix_fmt` / `out_pix_fmt` (yuyv422, uyvy422, yvyu422, y210le, y212le, y216le;
+    DESIGN.md 3.12) makes that side ONE tensor [..., h, 4 * ceil(w / 2)], bare or in a one-element list (`width` names an odd
+    width); on the same terms, and a packed source may go to planar 4:2:0 / 4:4:4.  With an RGB `pix_fmt` (gbrp* or a packed name such as rgb24) and a YUV
     `out_pix_fmt` (required then), `planes` is the three gbrp planes (G, B, R) or the one [F,]H,W,C packed tensor and the
     chain is lut3d on the RGB frame, then RGB -> YUV.  `pix_fmt` = gbrpf32le / gbrapf32le takes float32 planes
     (DESIGN.md 3.10): with a YUV `out_pix_fmt` the same chain, without one (or with a float one) float planes come back, an alpha
@@ -205,18 +211,21 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         from .multigpu import LutEngineGroup
         if isinstance(engine, LutEngineGroup) or (engine is None and len(devices) > 1):
             raise ValueError("resolution needs a single device")
-    from .engine import parse_rgb_source
+    from .engine import packed_frame_width, parse_packed_yuv_fmt, parse_rgb_source
     rgb_src = parse_rgb_source(pix_fmt)
     if rgb_src is not None and rgb_src.packed:
         got_w, got_h = planes.shape[-2], planes.shape[-3]
     else:
-        got_w, got_h = planes[0].shape[-1], planes[0].shape[-2]
+        first = planes if hasattr(planes, "shape") else planes[0]
+        pk_src = parse_packed_yuv_fmt(pix_fmt)
+        got_w = packed_frame_width(pk_src, planes, width) if pk_src is not None else first.shape[-1]
+        got_h = first.shape[-2]
     if width is not None and got_w != width or height is not None and got_h != height:
         raise ValueError("plane shape does not match width/height")
     params = ProcessingParams(lut_interp=interp, lut_input_matrix=input_matrix, lut_output_tags=output_tags,
                               zscale_dither=zscale_dither)
     from .engine import parse_semi_fmt
-    semi = parse_semi_fmt(pix_fmt)              # (p010le: the digits after the 'p' are not a depth)
+    semi = parse_semi_fmt(pix_fmt) or parse_packed_yuv_fmt(pix_fmt)   # (p010le, y210le: the digits are not a depth after a 'p')
     info = VideoInfo(width=width, height=height, pix_fmt=pix_fmt, bit_depth=semi.depth if semi else infer_bit_depth(pix_fmt),
                      colorspace=colorspace, color_range=color_range)
     # (the plan only carries the path into the filter string / notes; a parsed CubeLut or an engine that already holds the
@@ -232,8 +241,10 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         if chroma_loc is not None:
             raise ValueError("chroma siting (chroma_loc) is not defined for an RGB source")
     else:
-        from .engine import check_semi_options
-        if not check_semi_options(kw["pix_fmt"], kw["out_pix_fmt"], kw["dither"], chroma_loc, out_size):
+        from .engine import check_packed_options, check_semi_options
+        if check_packed_options(kw["pix_fmt"], kw["out_pix_fmt"], kw["dither"], chroma_loc, out_size):
+            kw["width"] = got_w
+        elif not check_semi_options(kw["pix_fmt"], kw["out_pix_fmt"], kw["dither"], chroma_loc, out_size):
             check_chroma_loc(chroma_loc, kw["dither"], kw["pix_fmt"], kw["out_pix_fmt"])
     if chroma_loc is not None:
         kw["chroma_loc"] = chroma_loc

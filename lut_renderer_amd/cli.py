@@ -43,7 +43,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("-o", "--output", required=True)
     ap.add_argument("--size", required=True, help="WxH")
     ap.add_argument("--pix-fmt", required=True,
-                    help="planar YUV, semi-planar YUV (nv12, nv21, nv16, p010le .. p216le), or an RGB source (gbrp* / rgb24, bgr24, rgba .., rgb48le, rgba64le) with a YUV --out-pix-fmt, "
+                    help="planar YUV, semi-planar YUV (nv12, nv21, nv16, p010le .. p216le), packed 4:2:2 YUV (yuyv422, uyvy422, yvyu422, y210le, y212le, y216le), or an RGB source (gbrp* / rgb24, bgr24, rgba .., rgb48le, rgba64le) with a YUV --out-pix-fmt, "
                          "or float RGB (gbrpf32le / gbrapf32le): float out without --out-pix-fmt, else a YUV one")
     ap.add_argument("--out-pix-fmt", default=None)
     ap.add_argument("--cube", required=True)
@@ -80,8 +80,8 @@ def plan_from_args(args):
     w, h = (int(v) for v in args.size.lower().split("x"))
     params = ProcessingParams(lut_interp=args.interp, lut_input_matrix=args.input_matrix,
                               lut_output_tags=args.output_tags, zscale_dither=args.zscale_dither)
-    from .engine import parse_semi_fmt
-    semi = parse_semi_fmt(args.pix_fmt)         # (p010le: the digits after the 'p' are not a depth)
+    from .engine import parse_packed_yuv_fmt, parse_semi_fmt
+    semi = parse_semi_fmt(args.pix_fmt) or parse_packed_yuv_fmt(args.pix_fmt)   # (p010le, y210le: the digits are not a depth after a 'p')
     info = VideoInfo(width=w, height=h, pix_fmt=args.pix_fmt, bit_depth=semi.depth if semi else infer_bit_depth(args.pix_fmt),
                      colorspace=args.colorspace, color_range=args.color_range)
     plan = resolve_lut_plan(params, args.cube, info)
@@ -94,8 +94,9 @@ def plan_from_args(args):
     from .api import is_rgb_call
     if getattr(args, "chroma_loc", None) and is_rgb_call(kw):
         raise ValueError("chroma siting (--chroma-loc) is not defined for an RGB source")
-    from .engine import check_semi_options
-    if not is_rgb_call(kw):
+    from .engine import check_packed_options, check_semi_options
+    if not is_rgb_call(kw) and not check_packed_options(kw["pix_fmt"], kw["out_pix_fmt"], kw.get("dither", "none"),
+                                                        getattr(args, "chroma_loc", None), getattr(args, "out_size", None)):
         check_semi_options(kw["pix_fmt"], kw["out_pix_fmt"], kw.get("dither", "none"), getattr(args, "chroma_loc", None),
                            getattr(args, "out_size", None))
     if getattr(args, "chroma_loc", None):

@@ -1203,6 +1203,99 @@ int lutr_apply_yuv_semi(lutr_ctx *c, const lutr_yuv_params *p, int interp, const
 }
 
 
+// one side of lutr_apply_yuv_packed: the packing against the format, the planes it needs and their alignment
+static int check_packed_side(const char *side, const lutr_yuv_packing *y, int fmt, const lutr_planes *pl, int nframes)
+{
+    const int depth = LUTR_FMT_DEPTH(fmt);
+    if (y->packed != 0 && y->packed != 1) { set_error("%s packing: packed is 0 or 1 (got %d)", side, y->packed); return LUTR_EINVAL; }
+    if (y->order < LUTR_PK_YUYV || y->order > LUTR_PK_YVYU) {
+        set_error("%s packing: order is 0 (yuyv), 1 (uyvy) or 2 (yvyu), not %d", side, y->order);
+        return LUTR_EINVAL;
+    }
+    if (!y->packed && (y->order || y->shift)) { set_error("%s packing: a planar side takes order 0 and shift 0", side); return LUTR_EINVAL; }
+    if (depth <= 8 ? y->shift != 0 : (y->shift != 0 && y->shift != 16 - depth)) {
+        if (depth <= 8) set_error("%s packing: an 8-bit container takes shift 0, not %d", side, y->shift);
+        else set_error("%s packing: shift is %d (16 - depth) or 0 at %d bit, not %d", side, 16 - depth, depth, y->shift);
+        return LUTR_EINVAL;
+    }
+    if (y->packed && !(LUTR_FMT_CSX(fmt) == 1 && LUTR_FMT_CSY(fmt) == 0)) {
+        set_error("%s packing: packed frames are 4:2:2", side);
+        return LUTR_EINVAL;
+    }
+    const int np = y->packed ? 1 : 3;
+    for (int i = 0; i < np; i++) {
+        if (!pl->data[i]) { set_error("null %s plane %d", side, i); return LUTR_EINVAL; }
+        if (depth > 8 && (((uintptr_t)pl->data[i] | (uintptr_t)pl->stride[i] | (nframes > 1 ? (uintptr_t)pl->frame_stride[i] : 0)) & 1)) {
+            set_error("%s plane %d: 16-bit containers need 2-byte aligned rows", side, i);
+            return LUTR_EINVAL;
+        }
+    }
+    return LUTR_OK;
+}
+
+// the byte ranges of one side of lutr_apply_yuv_packed over all rows and frames; returns their number
+static int packed_side_spans(const lutr_yuv_packing *y, int fmt, const lutr_planes *pl, int w, int h, int nframes, Span *out)
+{
+    const long long bs = LUTR_FMT_DEPTH(fmt) > 8 ? 2 : 1;
+    if (y->packed) {
+        out[0] = plane_span(pl->data[0], pl->stride[0], pl->frame_stride[0], h, 4ll * ((w + 1) >> 1) * bs, nframes);
+        return 1;
+    }
+    const int csx = LUTR_FMT_CSX(fmt), csy = LUTR_FMT_CSY(fmt);
+    const int cw = (w + (1 << csx) - 1) >> csx, ch = (h + (1 << csy) - 1) >> csy;
+    for (int i = 0; i < 3; i++)
+        out[i] = plane_span(pl->data[i], pl->stride[i], pl->frame_stride[i], i ? ch : h, (long long)(i ? cw : w) * bs, nframes);
+    return 3;
+}
+
+int lutr_apply_yuv_packed(lutr_ctx *c, const lutr_yuv_params *p, int interp, const lutr_yuv_packing *in,
+                          const lutr_yuv_packing *out, int w, int h, int nframes, const lutr_planes *src,
+                          const lutr_planes *dst, int row0, int rows)
+{
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!p || !in || !out) { set_error("null yuv params or packing"); return LUTR_EINVAL; }
+    if (!in->packed && !out->packed && !in->order && !out->order && !in->shift && !out->shift)
+        return lutr_apply_yuv_xsub(c, p, interp, LUTR_DITHER_NONE, w, h, nframes, src, dst, row0, rows);   // planar both ways: that call itself
+    YuvConsts K;
+    rc = make_yuv_consts_xsub(*p, &K);           // (one layout on both sides: lutr_apply_yuv's own constants)
+    if (rc) return rc;
+    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
+    if (!(LUTR_FMT_CSX(p->fmt_in) == 1 && LUTR_FMT_CSY(p->fmt_in) == 0)) {
+        set_error(out->packed ? "a packed destination takes a 4:2:2 source (no subsampling change into a packed frame)"
+                              : "the source of a packed call is 4:2:2");
+        return LUTR_EINVAL;
+    }
+    if (!((ocsx == 1 && ocsy <= 1) || (ocsx == 0 && ocsy == 0))) { set_error("the destination is 4:2:2, 4:2:0 or 4:4:4"); return LUTR_EINVAL; }
+    if (const int rc = check_packed_side("source", in, p->fmt_in, src, nframes)) return rc;
+    if (const int rc = check_packed_side("destination", out, p->fmt_out, dst, nframes)) return rc;
+    if (const int rc = check_row_blocks(row0, rows, h, 1 << ocsy, "chroma block height")) return rc;
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    // in place: the same packed container, the same bytes.  Anything else must not overlap at all
+    const bool in_place = in->packed && out->packed && in->order == out->order && in->shift == out->shift &&
+                          LUTR_FMT_DEPTH(p->fmt_in) == LUTR_FMT_DEPTH(p->fmt_out) && src->data[0] == dst->data[0] &&
+                          src->stride[0] == dst->stride[0] && (nframes <= 1 || src->frame_stride[0] == dst->frame_stride[0]);
+    if (!in_place) {
+        Span ss[3], ds[3];
+        const int ns = packed_side_spans(in, p->fmt_in, src, w, h, nframes, ss);
+        const int nd = packed_side_spans(out, p->fmt_out, dst, w, h, nframes, ds);
+        if (const int rc = check_disjoint("a packed 4:2:2 call between different buffers or containers", true, ss, ns, ds, nd)) return rc;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
+    LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
+    fill_planes(&P, src, dst);
+    for (int i = 1; i < 3; i++) {
+        if (in->packed) { P.s[i] = nullptr; P.ss[i] = 0; P.sfs[i] = 0; }
+        if (out->packed) { P.d[i] = nullptr; P.ds[i] = 0; P.dfs[i] = 0; }
+    }
+    const PkArgs A{in->packed, in->order == LUTR_PK_UYVY, in->order == LUTR_PK_YVYU, in->shift,
+                   out->packed, out->order == LUTR_PK_UYVY, out->order == LUTR_PK_YVYU, out->shift};
+    return finish_launch(c, launch_yuv_packed(c->stream, c->variant, L, K, P, G, A, LUTR_FMT_DEPTH(p->fmt_in),
+                                              LUTR_FMT_DEPTH(p->fmt_out), ocsx, ocsy, interp));
+}
+
 int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dither, int src_kind, int w, int h, int nframes,
                           const lutr_planes *src_planar, const lutr_packed *src_packed, const lutr_planes *dst, int row0, int rows)
 {

@@ -142,6 +142,24 @@ const char *launch_yuv_semi(hipStream_t st, int variant, const LutConsts &L, con
 LUTR_SM_DECL(w00) LUTR_SM_DECL(w11) LUTR_SM_DECL(w10)
 #undef LUTR_SM_DECL
 
+// packed 4:2:2 frames (lutr_pkyuv.hip): the container of each side -- planar (three planes) or packed (PlaneSet
+// slot 0 holds the groups, slots 1 and 2 are not read); cf: chroma first in a group (uyvy422), csw: Cr ahead of Cb (yvyu422),
+// 16-bit codes `shift` bits up in their words.  The source is 4:2:2; the destination is 4:2:2, or planar with the layout ocsx,
+// ocsy (K then carries the output block's 1/n).  nullptr = the variant cannot take the call (vec_lds always; vec_global on layouts
+// the vector kernel cannot take)
+struct PkArgs {
+    int ipk, icf, icsw, ishift;
+    int opk, ocf, ocsw, oshift;
+};
+const char *launch_yuv_packed(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
+                              const FrameGeom &G, const PkArgs &A, int din, int dout, int ocsx, int ocsy, int interp);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>): nullptr = not a side pair / mode it has
+#define LUTR_PK_DECL(tag) \
+    const char *launch_yuv_pk_vec_##tag(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, \
+                                        const FrameGeom &G, const PkArgs &A, int ocsy, int interp);
+LUTR_PK_DECL(w00) LUTR_PK_DECL(w11) LUTR_PK_DECL(w10)
+#undef LUTR_PK_DECL
+
 // pass 2 of the dither path alone (k_dither_ed on the float planes F, chroma planes in the output layout); false = rows too wide
 bool launch_dither_ed(hipStream_t st, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const FloatPlanes &F, int wout,
                       int ocsx, int ocsy);

@@ -86,6 +86,100 @@ class SemiFmt:
         return (h + (1 << self.csy) - 1) >> self.csy, 2 * ((w + 1) >> 1)
 
 
+@dataclass(frozen=True)
+class PackedYuvFmt:
+    """A packed 4:2:2 YUV format: one buffer, rows of ceil(w / 2) groups of four samples."""
+    name: str
+    depth: int
+    order: int        # the samples of a group in memory: 0 Y0 Cb Y1 Cr, 1 Cb Y0 Cr Y1 (uyvy422), 2 Y0 Cr Y1 Cb (yvyu422)
+    shift: int        # left shift of the code inside its 16-bit container (y210le: 6)
+
+    family = "yuv"
+    full_range = False
+    nplanes = 1
+    csx, csy = 1, 0
+
+    @property
+    def code(self) -> int:
+        return _native.fmt_code(self.depth, self.csx, self.csy)
+
+    @property
+    def np_dtype(self):
+        return np.uint8 if self.depth <= 8 else np.uint16
+
+    @property
+    def planar(self) -> str:
+        """The planar format that holds the same samples (uyvy422 -> yuv422p, y210le -> yuv422p10le)."""
+        return "yuv422p" + ("" if self.depth == 8 else f"{self.depth}le")
+
+    def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
+        """The one buffer: (h, 4 * groups per row) samples."""
+        return h, 4 * ((w + 1) >> 1)
+
+
+def parse_packed_yuv_fmt(name: Optional[str]) -> Optional[PackedYuvFmt]:
+    """The packed 4:2:2 format `name` stands for (a name of `_native.PACKED_YUV_FORMATS`), or None for any other name --
+    `parse_pix_fmt` keeps rejecting these and `parse_semi_fmt` keeps returning None for them."""
+    if name not in _native.PACKED_YUV_FORMATS:
+        return None
+    return PackedYuvFmt(name, *_native.PACKED_YUV_FORMATS[name])
+
+
+#: packed YUV names FFmpeg has that this path does not take: 4:4:4 packings and big-endian containers
+_PACKED_YUV_UNSUPPORTED = ("vuyx", "vuya", "ayuv", "uyva", "xv30le", "xv36le", "xv48le", "ayuv64le", "v30xle", "y210be", "y212be",
+                           "y216be", "xv30be", "xv36be", "xv48be", "ayuv64be")
+
+
+def check_packed_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
+                         out_size=None) -> bool:
+    """The checks `apply_yuv` makes before any GPU work when a side is packed 4:2:2: no semi-planar or RGB
+    side, a 4:2:2 source, a subsampling change only into a planar destination, no chroma_loc, no error-diffusion dither, no
+    out_size.  Returns False when neither side is packed (nothing checked), True otherwise."""
+    out_name = out_pix_fmt or pix_fmt
+    for name in (pix_fmt, out_name):
+        if name in _PACKED_YUV_UNSUPPORTED:
+            raise ValueError(f"'{name}' is not supported: packed YUV frames are taken as little-endian 4:2:2 "
+                             f"({', '.join(_native.PACKED_YUV_FORMATS)})")
+    a, b = parse_packed_yuv_fmt(pix_fmt), parse_packed_yuv_fmt(out_name)
+    if a is None and b is None:
+        return False
+    if parse_rgb_source(pix_fmt) is not None:
+        raise ValueError(f"an RGB source ('{pix_fmt}') takes a planar YUV out_pix_fmt, not the packed '{out_pix_fmt}'")
+    if parse_semi_fmt(pix_fmt) is not None or parse_semi_fmt(out_name) is not None:
+        raise ValueError(f"a semi-planar side together with a packed side is not supported ('{pix_fmt}' -> '{out_name}')")
+    a = a or parse_pix_fmt((pix_fmt or "").replace("yuvj", "yuv"))
+    b = b or parse_pix_fmt(out_name.replace("yuvj", "yuv"))
+    if a.family != "yuv" or b.family != "yuv":
+        raise ValueError(f"packed 4:2:2 frames go with YUV formats on both sides ('{pix_fmt}' -> '{out_name}')")
+    if (a.csx, a.csy) != (1, 0):
+        raise ValueError(f"a packed destination takes a 4:2:2 source: no chroma subsampling change into '{out_name}' "
+                         f"('{pix_fmt}' -> '{out_name}')")
+    if chroma_loc is not None:
+        raise ValueError("sited chroma resampling (chroma_loc) is not supported with a packed 4:2:2 side")
+    if dither != "none":
+        raise ValueError("error-diffusion dither is not supported with a packed 4:2:2 side")
+    if out_size is not None:
+        raise ValueError("a resize (out_size) is not supported with a packed 4:2:2 side")
+    return True
+
+
+def packed_frame_width(fmt, planes, width: Optional[int] = None) -> int:
+    """The frame width of one side's planes: a packed buffer holds 4 * ceil(w / 2) samples per row, so an odd width has to be
+    named (`width`); every other side tells it itself."""
+    first = planes if isinstance(planes, torch.Tensor) else planes[0]
+    if fmt.nplanes != 1:
+        w = first.shape[-1]
+    else:
+        if first.shape[-1] % 4:
+            raise ValueError(f"'{fmt.name}' rows hold whole groups of four samples, got {first.shape[-1]} samples")
+        w = first.shape[-1] // 2 if width is None else int(width)
+        if 4 * ((w + 1) >> 1) != first.shape[-1]:
+            raise ValueError(f"width {w} does not match '{fmt.name}' rows of {first.shape[-1]} samples")
+    if width is not None and int(width) != w:
+        raise ValueError(f"width {width} does not match the planes ({w})")
+    return w
+
+
 def parse_semi_fmt(name: Optional[str]) -> Optional[SemiFmt]:
     """The semi-planar format `name` stands for (a name of `_native.SEMI_FORMATS`), or None for any other name --
     `parse_pix_fmt` keeps rejecting these: it describes three-plane frames."""
@@ -95,8 +189,8 @@ def parse_semi_fmt(name: Optional[str]) -> Optional[SemiFmt]:
 
 
 def yuv_side(name: str):
-    """One side of `apply_yuv`: the `SemiFmt` or planar `PixFmt` of a YUV format name (yuvj* read as yuv*)."""
-    return parse_semi_fmt(name) or parse_pix_fmt((name or "").replace("yuvj", "yuv"))
+    """One side of `apply_yuv`: the `SemiFmt`, `PackedYuvFmt` or planar `PixFmt` of a YUV format name (yuvj* read as yuv*)."""
+    return parse_semi_fmt(name) or parse_packed_yuv_fmt(name) or parse_pix_fmt((name or "").replace("yuvj", "yuv"))
 
 
 def check_semi_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
@@ -264,6 +358,9 @@ def _check_planes(planes: Sequence[torch.Tensor], fmt: PixFmt, w: int, h: int, w
     if fmt.nplanes == 2:
         if isinstance(planes, torch.Tensor) or len(planes) != 2:
             raise ValueError(f"'{fmt.name}' takes two planes: luma and the interleaved chroma pairs")
+    elif fmt.nplanes == 1:
+        if isinstance(planes, torch.Tensor) or len(planes) != 1:
+            raise ValueError(f"'{fmt.name}' takes one buffer of packed groups")
     elif len(planes) != 3:
         raise ValueError("expected three planes")
     esize = 1 if fmt.depth <= 8 else 2
@@ -297,9 +394,9 @@ def _check_float_planes(planes: Sequence[torch.Tensor], fmt: RgbSource, w: int, 
 
 def _planes_struct(planes: Sequence[torch.Tensor], device: torch.device, nplanes: int = 3) -> Tuple[_native.Planes, int]:
     """Describe three [H,W] or [F,H,W] tensors as struct lutr_planes; returns (struct, nframes).  nplanes = 2: a semi-planar
-    side (luma, chroma pairs); slot 2 stays NULL."""
+    side (luma, chroma pairs); slot 2 stays NULL.  nplanes = 1: a packed 4:2:2 side; slots 1 and 2 stay NULL."""
     if len(planes) != nplanes:
-        raise ValueError("expected three planes" if nplanes == 3 else "expected two planes")
+        raise ValueError(f"expected {('one plane', 'two planes', 'three planes')[nplanes - 1]}")
     st = _native.Planes()
     nframes = None
     for i, t in enumerate(planes):
@@ -655,8 +752,13 @@ class LutEngine:
                   matrix_out: Optional[str] = None, range_src: str = "tv", range_in: Optional[str] = None,
                   range_out: str = "tv", lut_depth: Optional[int] = None, out_pix_fmt: Optional[str] = None,
                   row0: int = 0, rows: Optional[int] = None, dither: str = "none", chroma_loc: Optional[str] = None,
-                  out_size=None, resize_chunk: Optional[int] = None):
+                  out_size=None, resize_chunk: Optional[int] = None, width: Optional[int] = None):
         """Fused YUV -> RGB -> lut3d -> RGB -> YUV on planar frames (Y, Cb, Cr).
+        `pix_fmt` / `out_pix_fmt` may each name a packed 4:2:2 format (yuyv422, uyvy422, yvyu422, y210le, y212le, y216le;
+        DESIGN.md 3.12): that side is ONE tensor [..., h, 4 * ceil(w / 2)] (bare or in a one-element list), uint8, or int16 as for
+        planar 16-bit; `width` names an odd frame width a packed source cannot tell.  The other side may be planar 4:2:2, and a
+        planar destination also 4:2:0 or 4:4:4; no dither / chroma_loc / out_size, strict arithmetic, `dst` may be `src` when
+        both sides are the same packed format.  The bits are those of the planar call on the de-interleaved samples.
         `pix_fmt` / `out_pix_fmt` may each name a semi-planar format instead (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
         3.11): that side is a sequence of TWO tensors, y [..., h, w] and cbcr [..., ch, 2 * cw] (the pairs of a row side by side);
         same subsampling on both sides, no dither / chroma_loc / out_size, strict arithmetic, `dst` may be `src` when the two
@@ -671,6 +773,11 @@ class LutEngine:
         size and the resize reads them back; whole frames only, not in place.  The resize sites chroma by `chroma_loc`."""
         if dither not in _native.DITHER:
             raise ValueError(f"unknown dither mode '{dither}'")
+        if check_packed_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size):
+            return self._apply_yuv_packed(src, dst, yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt), interp, matrix_in,
+                                          matrix_out, range_src, range_in, range_out, lut_depth, row0, rows, width)
+        if width is not None:
+            raise ValueError("width is for a packed 4:2:2 side; planar and semi-planar frames tell their own")
         if check_semi_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size):
             return self._apply_yuv_semi(src, dst, yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt), interp, matrix_in,
                                         matrix_out, range_src, range_in, range_out, lut_depth, row0, rows)
@@ -741,6 +848,38 @@ class LutEngine:
                 self._ctx, C.byref(p), _native.INTERP[interp], C.byref(lay[0]), C.byref(lay[1]), w, h, nf, C.byref(s),
                 C.byref(d), row0, rows))
         return dst
+
+    def _apply_yuv_packed(self, src, dst, fin, fout, interp, matrix_in, matrix_out, range_src, range_in, range_out, lut_depth,
+                          row0, rows, width):
+        """apply_yuv with a packed 4:2:2 side (lutr_apply_yuv_packed); the options were checked by `check_packed_options`."""
+        p = _yuv_params(fin.code, fout.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
+                        range_src, range_in or range_src, range_out)
+        bare = isinstance(dst, torch.Tensor)
+        if isinstance(src, torch.Tensor):
+            src = [src]
+        if bare:
+            dst = [dst]
+        if len(src) != fin.nplanes:
+            raise ValueError(f"'{fin.name}' takes {fin.nplanes} plane{'s' if fin.nplanes > 1 else ''}")
+        w, h = packed_frame_width(fin, src, width), src[0].shape[-2]
+        if dst is None:
+            dt = _yuv_out_dtype(fout.depth, src[0].dtype)
+            dst = [torch.empty(tuple(src[0].shape[:-2]) + fout.plane_shape(i, w, h), dtype=dt, device=self.device)
+                   for i in range(fout.nplanes)]
+        _check_planes(src, fin, w, h, "source")
+        _check_planes(dst, fout, w, h, "destination")
+        s, nf = _planes_struct(src, self.device, fin.nplanes)
+        d, nfd = _planes_struct(dst, self.device, fout.nplanes)
+        if nf != nfd:
+            raise ValueError("src and dst disagree on the number of frames")
+        pk = [_native.YuvPacking(int(f.nplanes == 1), getattr(f, "order", 0), getattr(f, "shift", 0)) for f in (fin, fout)]
+        rows = h - row0 if rows is None else rows
+        with self._lock:
+            self._bind_stream()
+            _native.check(self._lib.lutr_apply_yuv_packed(
+                self._ctx, C.byref(p), _native.INTERP[interp], C.byref(pk[0]), C.byref(pk[1]), w, h, nf, C.byref(s),
+                C.byref(d), row0, rows))
+        return dst[0] if bare else dst
 
     # -- RGB source, YUV output (DESIGN.md 3.9) --------------------------------
     def _rgb_source(self, src, fmt: RgbSource):

@@ -28,7 +28,8 @@ import torch
 
 from . import _native
 from .cube import CubeLut, read_lut
-from .engine import LutEngine, check_semi_options, parse_pix_fmt, parse_rgb_source, yuv_side
+from .engine import (LutEngine, check_packed_options, check_semi_options, packed_frame_width, parse_pix_fmt, parse_rgb_source,
+                     yuv_side)
 from .shard import row_blocks
 
 
@@ -127,12 +128,20 @@ class LutEngineGroup:
             raise ValueError("error-diffusion dither couples the rows of a frame: it cannot be row-sharded")
         if "row0" in kw or "rows" in kw:
             raise ValueError("the group owns the row partition")
-        if check_semi_options(pix_fmt, out_pix_fmt, "none", kw.get("chroma_loc"), kw.get("out_size")):
+        bare = False
+        if check_packed_options(pix_fmt, out_pix_fmt, "none", kw.get("chroma_loc"), kw.get("out_size")):
+            # a packed 4:2:2 side: one buffer with the frame's rows -- any row for a 4:2:2 destination, even
+            # rows for a planar 4:2:0 one, which is the union block rule below
+            fin, fout = yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt)
+            bare = isinstance(dst, torch.Tensor)
+            src = [src] if isinstance(src, torch.Tensor) else src
+            dst = [dst] if bare else dst
+        elif check_semi_options(pix_fmt, out_pix_fmt, "none", kw.get("chroma_loc"), kw.get("out_size")):
             # a semi-planar side: two planes, the second with the chroma plane's rows -- the shard rule is unchanged
             fin, fout = yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt)
         else:
             fin, fout = parse_pix_fmt(pix_fmt), parse_pix_fmt(out_pix_fmt or pix_fmt)
-        h, w = src[0].shape[-2], src[0].shape[-1]
+        h, w = src[0].shape[-2], packed_frame_width(fin, src, kw.get("width"))
         home = src[0].device
         if dst is None:
             dt = torch.uint8 if fout.depth <= 8 else (src[0].dtype if src[0].element_size() == 2 else torch.int16)
@@ -180,7 +189,7 @@ class LutEngineGroup:
         for out, rng in pending:                                   # copies back: queued after every launch was issued
             for d, o, (a, b) in zip(dst, out, rng):
                 d[..., a:b, :].copy_(o, non_blocking=True)
-        return dst
+        return dst[0] if bare else dst
 
     def apply_rgb_to_yuv(self, src, dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: str, **kw):
         """`LutEngine.apply_rgb_to_yuv` with the rows of every frame split over the group's devices: shards on

@@ -18,7 +18,8 @@ from typing import Callable, Iterable, Iterator, List, Optional
 import numpy as np
 import torch
 
-from .engine import LutEngine, PixFmt, RgbSource, SemiFmt, parse_pix_fmt, parse_rgb_source, parse_semi_fmt, parse_size
+from .engine import (LutEngine, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, parse_packed_yuv_fmt, parse_pix_fmt, parse_rgb_source,
+                     parse_semi_fmt, parse_size)
 
 
 @dataclass
@@ -87,11 +88,42 @@ class SemiFrameLayout:
         return out
 
 
+@dataclass
+class PackedYuvFrameLayout:
+    """Byte layout of one packed 4:2:2 frame (uyvy422, y210le, ..) in a rawvideo stream: h rows of ceil(w / 2)
+    groups of four samples."""
+    fmt: PackedYuvFmt
+    width: int
+    height: int
+
+    @property
+    def itemsize(self) -> int:
+        return 1 if self.fmt.depth <= 8 else 2
+
+    @property
+    def plane_shapes(self) -> List[tuple]:
+        return [self.fmt.plane_shape(0, self.width, self.height)]
+
+    @property
+    def frame_bytes(self) -> int:
+        h, w = self.plane_shapes[0]
+        return h * w * self.itemsize
+
+    def plane_views(self, buf: torch.Tensor, nframes: int) -> List[torch.Tensor]:
+        """The one [F,H,4*G] view of the frames inside a flat uint8 buffer of `nframes` frames."""
+        typed = buf.view(torch.uint8 if self.itemsize == 1 else torch.int16)
+        h, w = self.plane_shapes[0]
+        return [torch.as_strided(typed, (nframes, h, w), (h * w, w, 1), 0)]
+
+
 def yuv_layout(pix_fmt: str, width: int, height: int):
-    """`SemiFrameLayout` for a semi-planar name, else the planar `FrameLayout`."""
+    """`SemiFrameLayout` for a semi-planar name, `PackedYuvFrameLayout` for a packed 4:2:2 one, else the planar `FrameLayout`."""
     semi = parse_semi_fmt(pix_fmt)
     if semi is not None:
         return SemiFrameLayout(semi, width, height)
+    packed = parse_packed_yuv_fmt(pix_fmt)
+    if packed is not None:
+        return PackedYuvFrameLayout(packed, width, height)
     return FrameLayout(parse_pix_fmt(pix_fmt.replace("yuvj", "yuv")), width, height)
 
 
@@ -143,7 +175,8 @@ class FloatFrameLayout:
 
 def input_layout(pix_fmt: str, width: int, height: int):
     """The layout of a rawvideo input: `PackedFrameLayout` for a packed RGB name, `FloatFrameLayout` for a planar float one,
-    `SemiFrameLayout` for a semi-planar YUV one, else `FrameLayout` (planar YUV or gbrp)."""
+    `SemiFrameLayout` for a semi-planar YUV one, `PackedYuvFrameLayout` for a packed 4:2:2 YUV one, else `FrameLayout` (planar
+    YUV or gbrp)."""
     rgb = parse_rgb_source(pix_fmt)
     if rgb is not None and rgb.packed:
         return PackedFrameLayout(rgb, width, height)
@@ -178,6 +211,8 @@ class HostPipeline:
         self.kw = dict(apply_kw, pix_fmt=self.fin.fmt.name, out_pix_fmt=self.fout.fmt.name)
         if out_size is not None:
             self.kw["out_size"] = (ow, oh)
+        if isinstance(self.fin, PackedYuvFrameLayout) or isinstance(self.fout, PackedYuvFrameLayout):
+            self.kw["width"] = width                           # (a packed row cannot tell an odd width)
         dev = engine.device
         self.h_in = [torch.empty(self.batch * self.fin.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]
         self.h_out = [torch.empty(self.batch * self.fout.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]
