@@ -22,7 +22,7 @@ from pathlib import Path
 from typing import Dict, Optional, Sequence, Tuple
 
 from .cube import CubeLut, read_cube, read_lut
-from .params import ProcessingParams, VideoInfo, infer_bit_depth
+from .params import ProcessingParams, VideoInfo
 from .plan import LutPlan, output_color_tags, resolve_lut_plan
 
 #: FFmpeg lut3d has no "cubic"; the reference whitelists it anyway (ffmpeg.py:243) and ffmpeg
@@ -119,8 +119,8 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
         return kw
     # a semi-planar source or output (nv12, p010le, ..) is the same chain on another container
     # (so is a packed 4:2:2 one: uyvy422, y210le, ..)
-    from .engine import check_packed_options, check_semi_options, parse_packed_yuv_fmt, parse_semi_fmt
-    check_packed_options(pix_fmt, out_pix_fmt)                   # names the packings this path does not take
+    from .engine import check_container_options, parse_packed_yuv_fmt, parse_semi_fmt
+    check_container_options(pix_fmt, out_pix_fmt, kinds=("packed",))     # names the packings this path does not take
     semi_src = parse_semi_fmt(pix_fmt) or parse_packed_yuv_fmt(pix_fmt)
     src = semi_src or parse_pix_fmt(pix_fmt)
     if src.family != "yuv":
@@ -140,8 +140,7 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
         kw.update(range_src="tv", range_in="tv", lut_depth=src.depth)
         default_out = kw["pix_fmt"]
     kw["out_pix_fmt"] = out_pix_fmt or default_out
-    if not check_packed_options(kw["pix_fmt"], kw["out_pix_fmt"]):
-        check_semi_options(kw["pix_fmt"], kw["out_pix_fmt"])     # one subsampling on both sides of a semi-planar call
+    check_container_options(kw["pix_fmt"], kw["out_pix_fmt"])    # (one subsampling on both sides of a semi-planar call)
     return kw
 
 
@@ -211,7 +210,8 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         from .multigpu import LutEngineGroup
         if isinstance(engine, LutEngineGroup) or (engine is None and len(devices) > 1):
             raise ValueError("resolution needs a single device")
-    from .engine import packed_frame_width, parse_packed_yuv_fmt, parse_rgb_source
+    from .engine import (check_chroma_loc, check_container_options, packed_frame_width, parse_packed_yuv_fmt, parse_rgb_source,
+                         source_bit_depth)
     rgb_src = parse_rgb_source(pix_fmt)
     if rgb_src is not None and rgb_src.packed:
         got_w, got_h = planes.shape[-2], planes.shape[-3]
@@ -224,10 +224,8 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         raise ValueError("plane shape does not match width/height")
     params = ProcessingParams(lut_interp=interp, lut_input_matrix=input_matrix, lut_output_tags=output_tags,
                               zscale_dither=zscale_dither)
-    from .engine import parse_semi_fmt
-    semi = parse_semi_fmt(pix_fmt) or parse_packed_yuv_fmt(pix_fmt)   # (p010le, y210le: the digits are not a depth after a 'p')
-    info = VideoInfo(width=width, height=height, pix_fmt=pix_fmt, bit_depth=semi.depth if semi else infer_bit_depth(pix_fmt),
-                     colorspace=colorspace, color_range=color_range)
+    info = VideoInfo(width=width, height=height, pix_fmt=pix_fmt, bit_depth=source_bit_depth(pix_fmt), colorspace=colorspace,
+                     color_range=color_range)
     # (the plan only carries the path into the filter string / notes; a parsed CubeLut or an engine that already holds the
     # lattice has none)
     plan = resolve_lut_plan(params, cube if isinstance(cube, (str, Path)) else "engine.cube", info)
@@ -236,15 +234,14 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     kw["dither"] = "error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none"
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
-    from .engine import check_chroma_loc
     if rgb_src is not None:
         if chroma_loc is not None:
             raise ValueError("chroma siting (chroma_loc) is not defined for an RGB source")
     else:
-        from .engine import check_packed_options, check_semi_options
-        if check_packed_options(kw["pix_fmt"], kw["out_pix_fmt"], kw["dither"], chroma_loc, out_size):
+        kind = check_container_options(kw["pix_fmt"], kw["out_pix_fmt"], kw["dither"], chroma_loc, out_size)
+        if kind == "packed":
             kw["width"] = got_w
-        elif not check_semi_options(kw["pix_fmt"], kw["out_pix_fmt"], kw["dither"], chroma_loc, out_size):
+        elif kind is None:
             check_chroma_loc(chroma_loc, kw["dither"], kw["pix_fmt"], kw["out_pix_fmt"])
     if chroma_loc is not None:
         kw["chroma_loc"] = chroma_loc

@@ -75,14 +75,13 @@ def build_parser() -> argparse.ArgumentParser:
 def plan_from_args(args):
     """The LutPlan and engine call the options select -- the same resolution `build_command` performs (plan.py)."""
     from .api import engine_call_for
-    from .params import ProcessingParams, VideoInfo, infer_bit_depth
+    from .engine import check_container_options, source_bit_depth
+    from .params import ProcessingParams, VideoInfo
     from .plan import resolve_lut_plan
     w, h = (int(v) for v in args.size.lower().split("x"))
     params = ProcessingParams(lut_interp=args.interp, lut_input_matrix=args.input_matrix,
                               lut_output_tags=args.output_tags, zscale_dither=args.zscale_dither)
-    from .engine import parse_packed_yuv_fmt, parse_semi_fmt
-    semi = parse_semi_fmt(args.pix_fmt) or parse_packed_yuv_fmt(args.pix_fmt)   # (p010le, y210le: the digits are not a depth after a 'p')
-    info = VideoInfo(width=w, height=h, pix_fmt=args.pix_fmt, bit_depth=semi.depth if semi else infer_bit_depth(args.pix_fmt),
+    info = VideoInfo(width=w, height=h, pix_fmt=args.pix_fmt, bit_depth=source_bit_depth(args.pix_fmt),
                      colorspace=args.colorspace, color_range=args.color_range)
     plan = resolve_lut_plan(params, args.cube, info)
     kw = engine_call_for(plan, args.pix_fmt, args.out_pix_fmt)
@@ -94,11 +93,9 @@ def plan_from_args(args):
     from .api import is_rgb_call
     if getattr(args, "chroma_loc", None) and is_rgb_call(kw):
         raise ValueError("chroma siting (--chroma-loc) is not defined for an RGB source")
-    from .engine import check_packed_options, check_semi_options
-    if not is_rgb_call(kw) and not check_packed_options(kw["pix_fmt"], kw["out_pix_fmt"], kw.get("dither", "none"),
-                                                        getattr(args, "chroma_loc", None), getattr(args, "out_size", None)):
-        check_semi_options(kw["pix_fmt"], kw["out_pix_fmt"], kw.get("dither", "none"), getattr(args, "chroma_loc", None),
-                           getattr(args, "out_size", None))
+    if not is_rgb_call(kw):
+        check_container_options(kw["pix_fmt"], kw["out_pix_fmt"], kw.get("dither", "none"), getattr(args, "chroma_loc", None),
+                                getattr(args, "out_size", None))
     if getattr(args, "chroma_loc", None):
         from .engine import check_chroma_loc
         check_chroma_loc(args.chroma_loc, kw.get("dither", "none"), kw["pix_fmt"], kw["out_pix_fmt"])

@@ -840,6 +840,24 @@ static int decode_packed(int pfmt, PackedFmt *f)
     return LUTR_OK;
 }
 
+// Samples of a chroma plane along an axis of n luma samples at log2 subsampling cs.
+static int chroma_dim(int n, int cs) { return (n + (1 << cs) - 1) >> cs; }
+
+// True when a base pointer, its row stride and (batches) its frame stride have none of `mask`'s bits set.
+static bool check_aligned(const void *ptr, long long stride, long long frame_stride, int nframes, unsigned mask)
+{
+    return !(((uintptr_t)ptr | (uintptr_t)stride | (nframes > 1 ? (uintptr_t)frame_stride : 0)) & mask);
+}
+
+// The source (src = true) or destination side of P has planes [0, k) only: slots [k, 3) are cleared.
+static void clear_planes(PlaneSet *P, bool src, int k)
+{
+    for (int i = k; i < 3; i++) {
+        if (src) { P->s[i] = nullptr; P->ss[i] = 0; P->sfs[i] = 0; }
+        else { P->d[i] = nullptr; P->ds[i] = 0; P->dfs[i] = 0; }
+    }
+}
+
 static void fill_planes(PlaneSet *P, const lutr_planes *src, const lutr_planes *dst)
 {
     for (int i = 0; i < 3; i++) {
@@ -961,8 +979,8 @@ int lutr_apply_packed_rgb(lutr_ctx *c, int pfmt, int interp, int w, int h, int n
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
     if (!src->data || !dst->data) { set_error("null image"); return LUTR_EINVAL; }
     const int wide = f.bits == 16;
-    if (wide && (((uintptr_t)src->data | (uintptr_t)dst->data | (uintptr_t)src->stride | (uintptr_t)dst->stride |
-                  (nframes > 1 ? (uintptr_t)src->frame_stride | (uintptr_t)dst->frame_stride : 0)) & 1)) {
+    if (wide && !(check_aligned(src->data, src->stride, src->frame_stride, nframes, 1) &&
+                  check_aligned(dst->data, dst->stride, dst->frame_stride, nframes, 1))) {
         set_error("16-bit packed formats need 2-byte aligned rows");
         return LUTR_EINVAL;
     }
@@ -1012,6 +1030,14 @@ static Span plane_span(const void *p, long long stride, long long fstride, int r
     return Span{(uintptr_t)p + (intptr_t)a, (uintptr_t)p + (intptr_t)b};
 }
 
+// The three spans of a planar side: w x h samples of luma, chroma planes subsampled by 2^csx x 2^csy.
+static void planar_spans(const lutr_planes *pl, int csx, int csy, int w, int h, int bytes_per_sample, int nframes, Span out[3])
+{
+    for (int i = 0; i < 3; i++)
+        out[i] = plane_span(pl->data[i], pl->stride[i], pl->frame_stride[i], i ? chroma_dim(h, csy) : h,
+                            (long long)(i ? chroma_dim(w, csx) : w) * bytes_per_sample, nframes);
+}
+
 // No source span may overlap a destination span: `what` cannot run in place.  name_src: the message names the source plane.
 static int check_disjoint(const char *what, bool name_src, const Span *s, int ns, const Span *d, int nd)
 {
@@ -1026,9 +1052,11 @@ static int check_disjoint(const char *what, bool name_src, const Span *s, int ns
     return LUTR_OK;
 }
 
-// The dither path's float planes for ny luma and nc samples per chroma plane, out of the context's scratch (grown when too small).
-static int dither_scratch(lutr_ctx *c, size_t ny, size_t nc, FloatPlanes *F)
+// The dither path's float planes for the whole frames of G with output chroma subsampled by 2^csx x 2^csy, out of the context's
+// scratch (grown when too small).
+static int dither_scratch(lutr_ctx *c, const FrameGeom &G, int csx, int csy, FloatPlanes *F)
 {
+    const size_t ny = (size_t)G.w * G.h * G.nframes, nc = (size_t)chroma_dim(G.w, csx) * chroma_dim(G.h, csy) * G.nframes;
     if (ny + 2 * nc > c->fscratch_floats) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (c->fscratch) (void)hipFree(c->fscratch);
@@ -1066,12 +1094,9 @@ int lutr_apply_yuv_sited(lutr_ctx *c, const lutr_yuv_params *p, int interp, int 
     if (const int rc = check_planes_set(src, dst)) return rc;
     // the resampling reads around every output sample: a destination that overlaps a source would be read after being written
     const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
-    const int cw = (w + (1 << csx) - 1) >> csx, ch = (h + bh - 1) >> csy;
     Span ss[3], ds[3];
-    for (int i = 0; i < 3; i++) {
-        ss[i] = plane_span(src->data[i], src->stride[i], src->frame_stride[i], i ? ch : h, (long long)(i ? cw : w) * (din > 8 ? 2 : 1), nframes);
-        ds[i] = plane_span(dst->data[i], dst->stride[i], dst->frame_stride[i], i ? ch : h, (long long)(i ? cw : w) * (dout > 8 ? 2 : 1), nframes);
-    }
+    planar_spans(src, csx, csy, w, h, din > 8 ? 2 : 1, nframes, ss);
+    planar_spans(dst, csx, csy, w, h, dout > 8 ? 2 : 1, nframes, ds);
     if (const int rc = check_disjoint("sited chroma resampling", true, ss, 3, ds, 3)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
@@ -1096,12 +1121,10 @@ int lutr_apply_yuv_dither(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
     if (w == 0 || h == 0 || nframes == 0) return LUTR_OK;
     if (const int rc = check_planes_set(src, dst)) return rc;
     const int csx = LUTR_FMT_CSX(p->fmt_in), csy = LUTR_FMT_CSY(p->fmt_in);
-    const size_t cw = (size_t)((w + (1 << csx) - 1) >> csx), ch = (size_t)((h + (1 << csy) - 1) >> csy);
-    const size_t ny = (size_t)w * h * nframes, nc = cw * ch * nframes;
     HIP_TRY(hipSetDevice(c->device));
-    FloatPlanes F;
-    if (const int rc = dither_scratch(c, ny, nc, &F)) return rc;
-    LutConsts L; PlaneSet P; FrameGeom G{w, h, 0, h, nframes};
+    FloatPlanes F; FrameGeom G{w, h, 0, h, nframes};
+    if (const int rc = dither_scratch(c, G, csx, csy, &F)) return rc;
+    LutConsts L; PlaneSet P;
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
     fill_planes(&P, src, dst);
     return finish_launch(c, launch_yuv_dither(c->stream, L, K, P, G, F, LUTR_FMT_DEPTH(p->fmt_in),
@@ -1136,40 +1159,43 @@ int lutr_apply_yuv_xsub(lutr_ctx *c, const lutr_yuv_params *p, int interp, int d
     const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
     if (dither == LUTR_DITHER_NONE)
         return finish_launch(c, launch_yuv_xsub(c->stream, c->variant, L, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, interp));
-    const size_t cw = (size_t)((w + (1 << ocsx) - 1) >> ocsx), ch = (size_t)((h + (1 << ocsy) - 1) >> ocsy);
-    const size_t ny = (size_t)w * h * nframes, nc = cw * ch * nframes;
     FloatPlanes F;
-    if (const int rc = dither_scratch(c, ny, nc, &F)) return rc;
+    if (const int rc = dither_scratch(c, G, ocsx, ocsy, &F)) return rc;
     return finish_launch(c, launch_yuv_dither(c->stream, L, K, P, G, F, din, dout, icsx, icsy, interp, ocsx, ocsy));
 }
 
-// one side of lutr_apply_yuv_semi: the layout against the format's depth, the planes it needs and their alignment
-static int check_semi_side(const char *side, const lutr_yuv_layout *y, int fmt, const lutr_planes *pl, int nframes)
+// What a semi-planar and a packed side share: `noun` ("layout" | "packing") names the struct in the messages; the shift against
+// the format's depth, then `bad_shape` (the side's own refusal of the format's subsampling, or nullptr -- it has always come
+// between the two), then the `nplanes` planes the side has and their alignment.
+static int check_container_side(const char *side, const char *noun, int shift, int depth, int nplanes, const lutr_planes *pl,
+                                int nframes, const char *bad_shape)
 {
-    const int depth = LUTR_FMT_DEPTH(fmt);
-    if ((y->semi != 0 && y->semi != 1) || (y->swap != 0 && y->swap != 1)) {
-        set_error("%s layout: semi and swap are 0 or 1 (got %d, %d)", side, y->semi, y->swap);
+    if (depth <= 8 ? shift != 0 : (shift != 0 && shift != 16 - depth)) {
+        if (depth <= 8) set_error("%s %s: an 8-bit container takes shift 0, not %d", side, noun, shift);
+        else set_error("%s %s: shift is %d (16 - depth) or 0 at %d bit, not %d", side, noun, 16 - depth, depth, shift);
         return LUTR_EINVAL;
     }
-    if (y->swap && !y->semi) { set_error("%s layout: swap needs a semi-planar side", side); return LUTR_EINVAL; }
-    if (depth <= 8 ? y->shift != 0 : (y->shift != 0 && y->shift != 16 - depth)) {
-        if (depth <= 8) set_error("%s layout: an 8-bit container takes shift 0, not %d", side, y->shift);
-        else set_error("%s layout: shift is %d (16 - depth) or 0 at %d bit, not %d", side, 16 - depth, depth, y->shift);
-        return LUTR_EINVAL;
-    }
-    if (y->semi && !(LUTR_FMT_CSX(fmt) == 1)) {
-        set_error("%s layout: semi-planar frames are 4:2:0 or 4:2:2", side);
-        return LUTR_EINVAL;
-    }
-    const int np = y->semi ? 2 : 3;
-    for (int i = 0; i < np; i++) {
+    if (bad_shape) { set_error("%s %s: %s", side, noun, bad_shape); return LUTR_EINVAL; }
+    for (int i = 0; i < nplanes; i++) {
         if (!pl->data[i]) { set_error("null %s plane %d", side, i); return LUTR_EINVAL; }
-        if (depth > 8 && (((uintptr_t)pl->data[i] | (uintptr_t)pl->stride[i] | (nframes > 1 ? (uintptr_t)pl->frame_stride[i] : 0)) & 1)) {
+        if (depth > 8 && !check_aligned(pl->data[i], pl->stride[i], pl->frame_stride[i], nframes, 1)) {
             set_error("%s plane %d: 16-bit containers need 2-byte aligned rows", side, i);
             return LUTR_EINVAL;
         }
     }
     return LUTR_OK;
+}
+
+// one side of lutr_apply_yuv_semi: the layout against the format, the planes it needs and their alignment
+static int check_semi_side(const char *side, const lutr_yuv_layout *y, int fmt, const lutr_planes *pl, int nframes)
+{
+    if ((y->semi != 0 && y->semi != 1) || (y->swap != 0 && y->swap != 1)) {
+        set_error("%s layout: semi and swap are 0 or 1 (got %d, %d)", side, y->semi, y->swap);
+        return LUTR_EINVAL;
+    }
+    if (y->swap && !y->semi) { set_error("%s layout: swap needs a semi-planar side", side); return LUTR_EINVAL; }
+    return check_container_side(side, "layout", y->shift, LUTR_FMT_DEPTH(fmt), y->semi ? 2 : 3, pl, nframes,
+                                y->semi && LUTR_FMT_CSX(fmt) != 1 ? "semi-planar frames are 4:2:0 or 4:2:2" : nullptr);
 }
 
 int lutr_apply_yuv_semi(lutr_ctx *c, const lutr_yuv_params *p, int interp, const lutr_yuv_layout *in_layout,
@@ -1195,8 +1221,8 @@ int lutr_apply_yuv_semi(lutr_ctx *c, const lutr_yuv_params *p, int interp, const
     LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
     fill_planes(&P, src, dst);
-    if (in_layout->semi) { P.s[2] = nullptr; P.ss[2] = 0; P.sfs[2] = 0; }
-    if (out_layout->semi) { P.d[2] = nullptr; P.ds[2] = 0; P.dfs[2] = 0; }
+    if (in_layout->semi) clear_planes(&P, true, 2);
+    if (out_layout->semi) clear_planes(&P, false, 2);
     const SemiArgs A{in_layout->semi, in_layout->swap, in_layout->shift, out_layout->semi, out_layout->swap, out_layout->shift};
     return finish_launch(c, launch_yuv_semi(c->stream, c->variant, L, K, P, G, A, LUTR_FMT_DEPTH(p->fmt_in),
                                             LUTR_FMT_DEPTH(p->fmt_out), csy, interp));
@@ -1206,31 +1232,14 @@ int lutr_apply_yuv_semi(lutr_ctx *c, const lutr_yuv_params *p, int interp, const
 // one side of lutr_apply_yuv_packed: the packing against the format, the planes it needs and their alignment
 static int check_packed_side(const char *side, const lutr_yuv_packing *y, int fmt, const lutr_planes *pl, int nframes)
 {
-    const int depth = LUTR_FMT_DEPTH(fmt);
     if (y->packed != 0 && y->packed != 1) { set_error("%s packing: packed is 0 or 1 (got %d)", side, y->packed); return LUTR_EINVAL; }
     if (y->order < LUTR_PK_YUYV || y->order > LUTR_PK_YVYU) {
         set_error("%s packing: order is 0 (yuyv), 1 (uyvy) or 2 (yvyu), not %d", side, y->order);
         return LUTR_EINVAL;
     }
     if (!y->packed && (y->order || y->shift)) { set_error("%s packing: a planar side takes order 0 and shift 0", side); return LUTR_EINVAL; }
-    if (depth <= 8 ? y->shift != 0 : (y->shift != 0 && y->shift != 16 - depth)) {
-        if (depth <= 8) set_error("%s packing: an 8-bit container takes shift 0, not %d", side, y->shift);
-        else set_error("%s packing: shift is %d (16 - depth) or 0 at %d bit, not %d", side, 16 - depth, depth, y->shift);
-        return LUTR_EINVAL;
-    }
-    if (y->packed && !(LUTR_FMT_CSX(fmt) == 1 && LUTR_FMT_CSY(fmt) == 0)) {
-        set_error("%s packing: packed frames are 4:2:2", side);
-        return LUTR_EINVAL;
-    }
-    const int np = y->packed ? 1 : 3;
-    for (int i = 0; i < np; i++) {
-        if (!pl->data[i]) { set_error("null %s plane %d", side, i); return LUTR_EINVAL; }
-        if (depth > 8 && (((uintptr_t)pl->data[i] | (uintptr_t)pl->stride[i] | (nframes > 1 ? (uintptr_t)pl->frame_stride[i] : 0)) & 1)) {
-            set_error("%s plane %d: 16-bit containers need 2-byte aligned rows", side, i);
-            return LUTR_EINVAL;
-        }
-    }
-    return LUTR_OK;
+    return check_container_side(side, "packing", y->shift, LUTR_FMT_DEPTH(fmt), y->packed ? 1 : 3, pl, nframes,
+                                y->packed && !(LUTR_FMT_CSX(fmt) == 1 && LUTR_FMT_CSY(fmt) == 0) ? "packed frames are 4:2:2" : nullptr);
 }
 
 // the byte ranges of one side of lutr_apply_yuv_packed over all rows and frames; returns their number
@@ -1241,10 +1250,7 @@ static int packed_side_spans(const lutr_yuv_packing *y, int fmt, const lutr_plan
         out[0] = plane_span(pl->data[0], pl->stride[0], pl->frame_stride[0], h, 4ll * ((w + 1) >> 1) * bs, nframes);
         return 1;
     }
-    const int csx = LUTR_FMT_CSX(fmt), csy = LUTR_FMT_CSY(fmt);
-    const int cw = (w + (1 << csx) - 1) >> csx, ch = (h + (1 << csy) - 1) >> csy;
-    for (int i = 0; i < 3; i++)
-        out[i] = plane_span(pl->data[i], pl->stride[i], pl->frame_stride[i], i ? ch : h, (long long)(i ? cw : w) * bs, nframes);
+    planar_spans(pl, LUTR_FMT_CSX(fmt), LUTR_FMT_CSY(fmt), w, h, (int)bs, nframes, out);
     return 3;
 }
 
@@ -1286,10 +1292,8 @@ int lutr_apply_yuv_packed(lutr_ctx *c, const lutr_yuv_params *p, int interp, con
     LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
     fill_planes(&P, src, dst);
-    for (int i = 1; i < 3; i++) {
-        if (in->packed) { P.s[i] = nullptr; P.ss[i] = 0; P.sfs[i] = 0; }
-        if (out->packed) { P.d[i] = nullptr; P.ds[i] = 0; P.dfs[i] = 0; }
-    }
+    if (in->packed) clear_planes(&P, true, 1);
+    if (out->packed) clear_planes(&P, false, 1);
     const PkArgs A{in->packed, in->order == LUTR_PK_UYVY, in->order == LUTR_PK_YVYU, in->shift,
                    out->packed, out->order == LUTR_PK_UYVY, out->order == LUTR_PK_YVYU, out->shift};
     return finish_launch(c, launch_yuv_packed(c->stream, c->variant, L, K, P, G, A, LUTR_FMT_DEPTH(p->fmt_in),
@@ -1326,8 +1330,7 @@ int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
     const long long bsi = Y.wide ? 2 : 1;
     if (packed) {
         if (!src_packed->data) { set_error("null image"); return LUTR_EINVAL; }
-        if (Y.wide && (((uintptr_t)src_packed->data | (uintptr_t)src_packed->stride |
-                        (nframes > 1 ? (uintptr_t)src_packed->frame_stride : 0)) & 1)) {
+        if (Y.wide && !check_aligned(src_packed->data, src_packed->stride, src_packed->frame_stride, nframes, 1)) {
             set_error("16-bit packed formats need 2-byte aligned rows");
             return LUTR_EINVAL;
         }
@@ -1345,12 +1348,9 @@ int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
     if (const int rc = check_planes_set(dst, nullptr)) return rc;
     for (int i = 0; i < 3; i++) { P.d[i] = (uint8_t *)dst->data[i]; P.ds[i] = dst->stride[i]; P.dfs[i] = dst->frame_stride[i]; }
     // a chroma sample is written by one thread while another may still read the pixels of its block: no in-place operation
-    const int cw = (w + (1 << ocsx) - 1) >> ocsx, ch = (h + bh - 1) >> ocsy;
     Span ss[3], ds[3];
-    for (int i = 0; i < 3; i++) {
-        ss[i] = plane_span(P.s[i], P.ss[i], P.sfs[i], h, (long long)w * Y.step * bsi, nframes);
-        ds[i] = plane_span(P.d[i], P.ds[i], P.dfs[i], i ? ch : h, (long long)(i ? cw : w) * (dout > 8 ? 2 : 1), nframes);
-    }
+    for (int i = 0; i < 3; i++) ss[i] = plane_span(P.s[i], P.ss[i], P.sfs[i], h, (long long)w * Y.step * bsi, nframes);
+    planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
     if (const int rc = check_disjoint("RGB -> YUV", false, ss, packed ? 1 : 3, ds, 3)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
@@ -1360,9 +1360,8 @@ int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
         if (const int rc = fill_lut(&L, c, dl)) return rc;
     if (dither == LUTR_DITHER_NONE)
         return finish_launch(c, launch_rgb2yuv(c->stream, c->variant, L, K, P, Y, G, dout, ocsx, ocsy, interp));
-    const size_t ny = (size_t)w * h * nframes, nc = (size_t)cw * ch * nframes;
     FloatPlanes F;
-    if (const int rc = dither_scratch(c, ny, nc, &F)) return rc;
+    if (const int rc = dither_scratch(c, G, ocsx, ocsy, &F)) return rc;
     return finish_launch(c, launch_rgb2yuv_dither(c->stream, L, K, P, Y, G, F, dout, ocsx, ocsy, interp));
 }
 
@@ -1370,7 +1369,7 @@ int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
 static int check_float_planes(const lutr_planes *a, int nframes, const char *what)
 {
     for (int i = 0; i < 3; i++)
-        if (((uintptr_t)a->data[i] | (uintptr_t)a->stride[i] | (nframes > 1 ? (uintptr_t)a->frame_stride[i] : 0)) & 3) {
+        if (!check_aligned(a->data[i], a->stride[i], a->frame_stride[i], nframes, 3)) {
             set_error("float planes need 4-byte aligned rows: %s plane %d (pointer, stride and frame stride must be multiples of 4)", what, i);
             return LUTR_EINVAL;
         }
@@ -1415,12 +1414,9 @@ int lutr_apply_rgbf_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, in
     PlaneSet P;
     fill_planes(&P, src, dst);
     // a chroma sample is written by one thread while another may still read the pixels of its block: no in-place operation
-    const int cw = (w + (1 << ocsx) - 1) >> ocsx, ch = (h + bh - 1) >> ocsy;
     Span ss[3], ds[3];
-    for (int i = 0; i < 3; i++) {
-        ss[i] = plane_span(P.s[i], P.ss[i], P.sfs[i], h, (long long)w * 4, nframes);
-        ds[i] = plane_span(P.d[i], P.ds[i], P.dfs[i], i ? ch : h, (long long)(i ? cw : w) * (dout > 8 ? 2 : 1), nframes);
-    }
+    planar_spans(src, 0, 0, w, h, 4, nframes, ss);
+    planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
     if (const int rc = check_disjoint("float RGB -> YUV", true, ss, 3, ds, 3)) return rc;
     // source planes in R, G, B order (gbrp planes are G, B, R); the destination stays Y, Cb, Cr
     const PlaneSet S = gbrp_to_rgb(P);
@@ -1430,9 +1426,8 @@ int lutr_apply_rgbf_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, in
     if (const int rc = fill_lut_float(&L, &Q, c, interp != LUTR_INTERP_NONE)) return rc;
     if (dither == LUTR_DITHER_NONE)
         return finish_launch(c, launch_rgbf2yuv(c->stream, c->variant, L, Q, K, P, G, dout, ocsx, ocsy, interp));
-    const size_t ny = (size_t)w * h * nframes, nc = (size_t)cw * ch * nframes;
     FloatPlanes F;
-    if (const int rc = dither_scratch(c, ny, nc, &F)) return rc;
+    if (const int rc = dither_scratch(c, G, ocsx, ocsy, &F)) return rc;
     return finish_launch(c, launch_rgbf2yuv_dither(c->stream, L, Q, K, P, G, F, dout, ocsx, ocsy, interp));
 }
 
@@ -1504,20 +1499,18 @@ int lutr_resize_planes(lutr_ctx *c, int family, int depth, int csx, int csy, int
     int psw[3], psh[3], pdw[3], pdh[3];
     for (int i = 0; i < 3; i++) {
         const int cx = i ? csx : 0, cy = i ? csy : 0;
-        psw[i] = (sw + (1 << cx) - 1) >> cx; psh[i] = (sh + (1 << cy) - 1) >> cy;
-        pdw[i] = (dw + (1 << cx) - 1) >> cx; pdh[i] = (dh + (1 << cy) - 1) >> cy;
+        psw[i] = chroma_dim(sw, cx); psh[i] = chroma_dim(sh, cy);
+        pdw[i] = chroma_dim(dw, cx); pdh[i] = chroma_dim(dh, cy);
     }
     // every destination sample reads a neighbourhood of source samples: no destination may overlap a source
     Span ss[3], ds[3];
-    for (int i = 0; i < 3; i++) {
-        ss[i] = plane_span(src->data[i], src->stride[i], src->frame_stride[i], psh[i], (long long)psw[i] * es, nframes);
-        ds[i] = plane_span(dst->data[i], dst->stride[i], dst->frame_stride[i], pdh[i], (long long)pdw[i] * es, nframes);
-    }
+    planar_spans(src, csx, csy, sw, sh, es, nframes, ss);
+    planar_spans(dst, csx, csy, dw, dh, es, nframes, ds);
     if (const int rc = check_disjoint("resize", true, ss, 3, ds, 3)) return rc;
     if (es == 2)
         for (int i = 0; i < 3; i++)
-            if (((uintptr_t)src->data[i] | (uintptr_t)dst->data[i] | (uintptr_t)src->stride[i] | (uintptr_t)dst->stride[i] |
-                 (nframes > 1 ? (uintptr_t)src->frame_stride[i] | (uintptr_t)dst->frame_stride[i] : 0)) & 1) {
+            if (!(check_aligned(src->data[i], src->stride[i], src->frame_stride[i], nframes, 1) &&
+                  check_aligned(dst->data[i], dst->stride[i], dst->frame_stride[i], nframes, 1))) {
                 set_error("16-bit planes need 2-byte aligned rows");
                 return LUTR_EINVAL;
             }

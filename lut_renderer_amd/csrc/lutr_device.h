@@ -398,6 +398,20 @@ __device__ __forceinline__ void yuv_block(const LutConsts &L, const GFetch &f, c
     sink.chroma(fr, cx, cy, rs, gs, bs);
 }
 
+// A code inside a container at run-time width: sample x of `row`, `shift` bits up inside a 16-bit word (p010le, y210le: 6); the
+// generic kernels of the semi-planar and packed 4:2:2 paths (lutr_semi.hip, lutr_pkyuv.hip).
+__device__ __forceinline__ float ld_code(const uint8_t *row, long long x, int wide, int shift)
+{
+    return wide ? (float)(((const uint16_t *)row)[x] >> shift) : (float)row[x];
+}
+
+__device__ __forceinline__ void st_code(uint8_t *row, long long x, int wide, int shift, float v)
+{
+    const unsigned u = (unsigned)v;
+    if (wide) ((uint16_t *)row)[x] = (uint16_t)(u << shift);
+    else row[x] = (uint8_t)u;
+}
+
 // ---------------------------------------------------------------- vector kernels, global gather
 // kVecBytes bytes per plane row and thread: with 16-byte accesses these kernels needed 256 VGPRs (one wave per SIMD); at 8 bytes
 // they keep several waves per SIMD, which is what a gather wants.

@@ -218,18 +218,6 @@ const char *LUTR_CAT(LUTR_CAT(launch_yuv_pk_vec_w, LUTR_PK_WI), LUTR_PK_WO)(hipS
 // sums its pixels row by row.  A pixel outside the frame is the edge pixel again, so a partial block sums the edge column / row twice, like
 // np.pad(mode="edge"), and the second luma sample of an odd-width packed row comes out as a copy of the last real one.  The
 // block's codes are all read before anything is stored: a destination that is the source sees its own input.
-__device__ __forceinline__ float ld_code(const uint8_t *row, long long x, int wide, int shift)
-{
-    return wide ? (float)(((const uint16_t *)row)[x] >> shift) : (float)row[x];
-}
-
-__device__ __forceinline__ void st_code(uint8_t *row, long long x, int wide, int shift, float v)
-{
-    const unsigned u = (unsigned)v;
-    if (wide) ((uint16_t *)row)[x] = (uint16_t)(u << shift);
-    else row[x] = (uint8_t)u;
-}
-
 __global__ __launch_bounds__(256) void k_yuv_pk_generic(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, PkArgs A, int win,
                                                         int wout, int ocsx, int ocsy, int mode)
 {

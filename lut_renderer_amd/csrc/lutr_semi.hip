@@ -180,18 +180,6 @@ const char *LUTR_CAT(LUTR_CAT(launch_yuv_semi_vec_w, LUTR_SM_WI), LUTR_SM_WO)(hi
 // modes.  A pixel outside the frame is the edge pixel again, so a partial block sums the edge column / row twice, like
 // np.pad(mode="edge"); only samples inside the planes are written.  The block's codes are all read before anything is stored:
 // a destination that is the source plane for plane sees its own input.
-__device__ __forceinline__ float ld_code(const uint8_t *row, long long x, int wide, int shift)
-{
-    return wide ? (float)(((const uint16_t *)row)[x] >> shift) : (float)row[x];
-}
-
-__device__ __forceinline__ void st_code(uint8_t *row, long long x, int wide, int shift, float v)
-{
-    const unsigned u = (unsigned)v;
-    if (wide) ((uint16_t *)row)[x] = (uint16_t)(u << shift);
-    else row[x] = (uint8_t)u;
-}
-
 // (its own block walk, not for_each_block of lutr_device.h: with the shared walk it takes 73 VGPRs for 72, 6 waves per SIMD for 7)
 __global__ __launch_bounds__(256) void k_yuv_semi_generic(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, SemiArgs A, int win,
                                                           int wout, int csy, int mode)

@@ -26,8 +26,39 @@ from .cube import CubeLut, read_cube, read_lut
 _PIXFMT_RE = re.compile(r"^(yuvj?|gbr)(420|422|444)?p(\d+)?(le)?$")
 
 
+class _YuvSide:
+    """What the three format classes share: one side of a YUV call, from the `depth`, `csx`, `csy` of its container."""
+
+    @property
+    def code(self) -> int:
+        return _native.fmt_code(self.depth, self.csx, self.csy)
+
+    @property
+    def np_dtype(self):
+        return np.uint8 if self.depth <= 8 else np.uint16
+
+    def layout(self) -> _native.YuvLayout:
+        """This side as lutr_apply_yuv_semi takes it (here: three planes)."""
+        return _native.YuvLayout(0, 0, 0)
+
+    def packing(self) -> _native.YuvPacking:
+        """This side as lutr_apply_yuv_packed takes it (here: three planes)."""
+        return _native.YuvPacking(0, 0, 0)
+
+
+class _YuvContainer(_YuvSide):
+    """A YUV container that is not three planes: always YUV, never yuvj*, and with a planar twin."""
+    family = "yuv"
+    full_range = False
+
+    @property
+    def planar(self) -> str:
+        """The planar format that holds the same samples (nv12 -> yuv420p, p210le -> yuv422p10le, uyvy422 -> yuv422p)."""
+        return f"yuv{'420' if self.csy else '422'}p" + ("" if self.depth == 8 else f"{self.depth}le")
+
+
 @dataclass(frozen=True)
-class PixFmt:
+class PixFmt(_YuvSide):
     """Parsed FFmpeg planar pixel-format name (the ones this path can meet)."""
     name: str
     family: str      # "yuv" or "gbr"
@@ -36,24 +67,16 @@ class PixFmt:
     csy: int
     full_range: bool  # yuvj* (legacy full-range marker, media_info.py:145-147)
 
-    @property
-    def code(self) -> int:
-        return _native.fmt_code(self.depth, self.csx, self.csy)
-
-    @property
-    def np_dtype(self):
-        return np.uint8 if self.depth <= 8 else np.uint16
+    nplanes = 3
 
     def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
         if self.family == "gbr" or plane == 0:
             return h, w
         return (h + (1 << self.csy) - 1) >> self.csy, (w + (1 << self.csx) - 1) >> self.csx
 
-    nplanes = 3
-
 
 @dataclass(frozen=True)
-class SemiFmt:
+class SemiFmt(_YuvContainer):
     """A semi-planar YUV format: a luma plane and one plane of interleaved chroma pairs."""
     name: str
     depth: int
@@ -62,22 +85,10 @@ class SemiFmt:
     swap: int         # 1: Cr comes first in a pair (nv21)
     shift: int        # left shift of the code inside its 16-bit container (p010le: 6)
 
-    family = "yuv"
-    full_range = False
     nplanes = 2
 
-    @property
-    def code(self) -> int:
-        return _native.fmt_code(self.depth, self.csx, self.csy)
-
-    @property
-    def np_dtype(self):
-        return np.uint8 if self.depth <= 8 else np.uint16
-
-    @property
-    def planar(self) -> str:
-        """The planar format that holds the same samples (nv12 -> yuv420p, p210le -> yuv422p10le)."""
-        return f"yuv{'420' if self.csy else '422'}p" + ("" if self.depth == 8 else f"{self.depth}le")
+    def layout(self) -> _native.YuvLayout:
+        return _native.YuvLayout(1, self.swap, self.shift)
 
     def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
         """Plane 0: (h, w) luma samples; plane 1: (chroma rows, 2 * pairs per row) chroma samples."""
@@ -87,30 +98,18 @@ class SemiFmt:
 
 
 @dataclass(frozen=True)
-class PackedYuvFmt:
+class PackedYuvFmt(_YuvContainer):
     """A packed 4:2:2 YUV format: one buffer, rows of ceil(w / 2) groups of four samples."""
     name: str
     depth: int
     order: int        # the samples of a group in memory: 0 Y0 Cb Y1 Cr, 1 Cb Y0 Cr Y1 (uyvy422), 2 Y0 Cr Y1 Cb (yvyu422)
     shift: int        # left shift of the code inside its 16-bit container (y210le: 6)
 
-    family = "yuv"
-    full_range = False
     nplanes = 1
     csx, csy = 1, 0
 
-    @property
-    def code(self) -> int:
-        return _native.fmt_code(self.depth, self.csx, self.csy)
-
-    @property
-    def np_dtype(self):
-        return np.uint8 if self.depth <= 8 else np.uint16
-
-    @property
-    def planar(self) -> str:
-        """The planar format that holds the same samples (uyvy422 -> yuv422p, y210le -> yuv422p10le)."""
-        return "yuv422p" + ("" if self.depth == 8 else f"{self.depth}le")
+    def packing(self) -> _native.YuvPacking:
+        return _native.YuvPacking(1, self.order, self.shift)
 
     def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
         """The one buffer: (h, 4 * groups per row) samples."""
@@ -125,42 +124,91 @@ def parse_packed_yuv_fmt(name: Optional[str]) -> Optional[PackedYuvFmt]:
     return PackedYuvFmt(name, *_native.PACKED_YUV_FORMATS[name])
 
 
+def parse_semi_fmt(name: Optional[str]) -> Optional[SemiFmt]:
+    """The semi-planar format `name` stands for (a name of `_native.SEMI_FORMATS`), or None for any other name --
+    `parse_pix_fmt` keeps rejecting these: it describes three-plane frames."""
+    if name not in _native.SEMI_FORMATS:
+        return None
+    return SemiFmt(name, *_native.SEMI_FORMATS[name])
+
+
+def yuv_side(name: str):
+    """One side of `apply_yuv`: the `SemiFmt`, `PackedYuvFmt` or planar `PixFmt` of a YUV format name (yuvj* read as yuv*)."""
+    return parse_semi_fmt(name) or parse_packed_yuv_fmt(name) or parse_pix_fmt((name or "").replace("yuvj", "yuv"))
+
+
 #: packed YUV names FFmpeg has that this path does not take: 4:4:4 packings and big-endian containers
 _PACKED_YUV_UNSUPPORTED = ("vuyx", "vuya", "ayuv", "uyva", "xv30le", "xv36le", "xv48le", "ayuv64le", "v30xle", "y210be", "y212be",
                            "y216be", "xv30be", "xv36be", "xv48be", "ayuv64be")
 
 
+#: container kind -> (its parser, what the RGB refusal calls it, what every other refusal calls it)
+_CONTAINER_KINDS = {"packed": (parse_packed_yuv_fmt, "packed", "packed 4:2:2"),
+                    "semi": (parse_semi_fmt, "semi-planar", "semi-planar")}
+
+
+def source_bit_depth(name: Optional[str]) -> Optional[int]:
+    """`params.infer_bit_depth` for a source name that may be a container: p010le and y210le say their depth themselves (the
+    digits are not a depth after a 'p')."""
+    from .params import infer_bit_depth
+    side = parse_semi_fmt(name) or parse_packed_yuv_fmt(name)
+    return side.depth if side else infer_bit_depth(name)
+
+
+def check_container_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
+                            out_size=None, kinds=("packed", "semi"), width: Optional[int] = None) -> Optional[str]:
+    """The checks `apply_yuv` makes before any GPU work when a side is not three planes: "packed" when a side is packed 4:2:2
+    (DESIGN.md 3.12), "semi" when one is semi-planar, None when both are planar (nothing checked but the
+    packed names this path does not take).  Refused: an RGB side, a packed side together with a semi-planar one, a
+    subsampling change (packed: only a source that is not 4:2:2), chroma_loc, error-diffusion dither, out_size, and a `width`
+    (`apply_yuv`'s, for odd packed rows) when no side is packed."""
+    out_name = out_pix_fmt or pix_fmt
+    for kind in kinds:
+        parse, short, noun = _CONTAINER_KINDS[kind]
+        packed = kind == "packed"
+        if not packed and width is not None:
+            raise ValueError("width is for a packed 4:2:2 side; planar and semi-planar frames tell their own")
+        for name in (pix_fmt, out_name) if packed else ():
+            if name in _PACKED_YUV_UNSUPPORTED:
+                raise ValueError(f"'{name}' is not supported: packed YUV frames are taken as little-endian 4:2:2 "
+                                 f"({', '.join(_native.PACKED_YUV_FORMATS)})")
+        if parse(pix_fmt) is None and parse(out_name) is None:
+            continue
+        if parse_rgb_source(pix_fmt) is not None:
+            raise ValueError(f"an RGB source ('{pix_fmt}') takes a planar YUV out_pix_fmt, not the {short} '{out_pix_fmt}'")
+        if packed and (parse_semi_fmt(pix_fmt) is not None or parse_semi_fmt(out_name) is not None):
+            raise ValueError(f"a semi-planar side together with a packed side is not supported ('{pix_fmt}' -> '{out_name}')")
+        a, b = yuv_side(pix_fmt), yuv_side(out_name)
+        if a.family != "yuv" or b.family != "yuv":
+            raise ValueError(f"{noun} frames go with YUV formats on both sides "
+                             f"('{pix_fmt}' -> '{out_name if packed else out_pix_fmt}')")
+        if packed and (a.csx, a.csy) != (1, 0):
+            raise ValueError(f"a packed destination takes a 4:2:2 source: no chroma subsampling change into '{out_name}' "
+                             f"('{pix_fmt}' -> '{out_name}')")
+        if not packed and (a.csx, a.csy) != (b.csx, b.csy):
+            raise ValueError(f"a chroma subsampling change is not supported with a semi-planar side "
+                             f"('{pix_fmt}' -> '{out_pix_fmt}')")
+        if chroma_loc is not None:
+            raise ValueError(f"sited chroma resampling (chroma_loc) is not supported with a {noun} side")
+        if dither != "none":
+            raise ValueError(f"error-diffusion dither is not supported with a {noun} side")
+        if out_size is not None:
+            raise ValueError(f"a resize (out_size) is not supported with a {noun} side")
+        return kind
+    return None
+
+
 def check_packed_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
                          out_size=None) -> bool:
-    """The checks `apply_yuv` makes before any GPU work when a side is packed 4:2:2: no semi-planar or RGB
-    side, a 4:2:2 source, a subsampling change only into a planar destination, no chroma_loc, no error-diffusion dither, no
-    out_size.  Returns False when neither side is packed (nothing checked), True otherwise."""
-    out_name = out_pix_fmt or pix_fmt
-    for name in (pix_fmt, out_name):
-        if name in _PACKED_YUV_UNSUPPORTED:
-            raise ValueError(f"'{name}' is not supported: packed YUV frames are taken as little-endian 4:2:2 "
-                             f"({', '.join(_native.PACKED_YUV_FORMATS)})")
-    a, b = parse_packed_yuv_fmt(pix_fmt), parse_packed_yuv_fmt(out_name)
-    if a is None and b is None:
-        return False
-    if parse_rgb_source(pix_fmt) is not None:
-        raise ValueError(f"an RGB source ('{pix_fmt}') takes a planar YUV out_pix_fmt, not the packed '{out_pix_fmt}'")
-    if parse_semi_fmt(pix_fmt) is not None or parse_semi_fmt(out_name) is not None:
-        raise ValueError(f"a semi-planar side together with a packed side is not supported ('{pix_fmt}' -> '{out_name}')")
-    a = a or parse_pix_fmt((pix_fmt or "").replace("yuvj", "yuv"))
-    b = b or parse_pix_fmt(out_name.replace("yuvj", "yuv"))
-    if a.family != "yuv" or b.family != "yuv":
-        raise ValueError(f"packed 4:2:2 frames go with YUV formats on both sides ('{pix_fmt}' -> '{out_name}')")
-    if (a.csx, a.csy) != (1, 0):
-        raise ValueError(f"a packed destination takes a 4:2:2 source: no chroma subsampling change into '{out_name}' "
-                         f"('{pix_fmt}' -> '{out_name}')")
-    if chroma_loc is not None:
-        raise ValueError("sited chroma resampling (chroma_loc) is not supported with a packed 4:2:2 side")
-    if dither != "none":
-        raise ValueError("error-diffusion dither is not supported with a packed 4:2:2 side")
-    if out_size is not None:
-        raise ValueError("a resize (out_size) is not supported with a packed 4:2:2 side")
-    return True
+    """`check_container_options` for the packed 4:2:2 kind alone: False when neither side is packed, True otherwise."""
+    return check_container_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size, ("packed",)) is not None
+
+
+def check_semi_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
+                       out_size=None) -> bool:
+    """`check_container_options` for the semi-planar kind alone (a packed side is not looked at): False when neither side is
+    semi-planar, True otherwise."""
+    return check_container_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size, ("semi",)) is not None
 
 
 def packed_frame_width(fmt, planes, width: Optional[int] = None) -> int:
@@ -178,42 +226,6 @@ def packed_frame_width(fmt, planes, width: Optional[int] = None) -> int:
     if width is not None and int(width) != w:
         raise ValueError(f"width {width} does not match the planes ({w})")
     return w
-
-
-def parse_semi_fmt(name: Optional[str]) -> Optional[SemiFmt]:
-    """The semi-planar format `name` stands for (a name of `_native.SEMI_FORMATS`), or None for any other name --
-    `parse_pix_fmt` keeps rejecting these: it describes three-plane frames."""
-    if name not in _native.SEMI_FORMATS:
-        return None
-    return SemiFmt(name, *_native.SEMI_FORMATS[name])
-
-
-def yuv_side(name: str):
-    """One side of `apply_yuv`: the `SemiFmt`, `PackedYuvFmt` or planar `PixFmt` of a YUV format name (yuvj* read as yuv*)."""
-    return parse_semi_fmt(name) or parse_packed_yuv_fmt(name) or parse_pix_fmt((name or "").replace("yuvj", "yuv"))
-
-
-def check_semi_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
-                       out_size=None) -> bool:
-    """The checks `apply_yuv` makes before any GPU work when a side is semi-planar: both sides YUV with one
-    chroma subsampling, no chroma_loc, no error-diffusion dither, no out_size.  Returns False when neither side is semi-planar
-    (nothing checked), True otherwise."""
-    if parse_semi_fmt(pix_fmt) is None and parse_semi_fmt(out_pix_fmt or pix_fmt) is None:
-        return False
-    if parse_rgb_source(pix_fmt) is not None:
-        raise ValueError(f"an RGB source ('{pix_fmt}') takes a planar YUV out_pix_fmt, not the semi-planar '{out_pix_fmt}'")
-    a, b = yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt)
-    if a.family != "yuv" or b.family != "yuv":
-        raise ValueError(f"semi-planar frames go with YUV formats on both sides ('{pix_fmt}' -> '{out_pix_fmt}')")
-    if (a.csx, a.csy) != (b.csx, b.csy):
-        raise ValueError(f"a chroma subsampling change is not supported with a semi-planar side ('{pix_fmt}' -> '{out_pix_fmt}')")
-    if chroma_loc is not None:
-        raise ValueError("sited chroma resampling (chroma_loc) is not supported with a semi-planar side")
-    if dither != "none":
-        raise ValueError("error-diffusion dither is not supported with a semi-planar side")
-    if out_size is not None:
-        raise ValueError("a resize (out_size) is not supported with a semi-planar side")
-    return True
 
 
 def parse_pix_fmt(name: str) -> PixFmt:
@@ -463,6 +475,11 @@ def _yuv_out_dtype(depth: int, inherit: Optional[torch.dtype]) -> torch.dtype:
     return torch.uint8 if depth <= 8 else inherit if inherit is not None and inherit.itemsize == 2 else torch.int16
 
 
+def _new_planes(fmt, w: int, h: int, lead: tuple, dtype, device) -> list:
+    """Fresh planes of one side: `fmt.nplanes` tensors of `lead + fmt.plane_shape(i, w, h)`."""
+    return [torch.empty(lead + fmt.plane_shape(i, w, h), dtype=dtype, device=device) for i in range(fmt.nplanes)]
+
+
 class LutEngine:
     """One GPU context: a device lattice plus the stream its kernels run on."""
 
@@ -673,7 +690,7 @@ class LutEngine:
         dw, dh = parse_size(size)
         sh, sw = src[0].shape[-2], src[0].shape[-1]
         if dst is None:
-            dst = self._new_planes(fmt, dw, dh, tuple(src[0].shape[:-2]), src[0].dtype)
+            dst = _new_planes(fmt, dw, dh, tuple(src[0].shape[:-2]), src[0].dtype, self.device)
         _check_planes(src, fmt, sw, sh, "source")
         _check_planes(dst, fmt, dw, dh, "destination")
         _check_not_in_place(src, dst, _RESIZE_IN_PLACE)
@@ -690,11 +707,8 @@ class LutEngine:
         key = (fmt.name, w, h, dtype)
         cur = self._scratch_slots.get(slot)
         if cur is None or cur[0] != key or cur[1][0].shape[0] < nframes:
-            cur = self._scratch_slots[slot] = (key, self._new_planes(fmt, w, h, (nframes,), dtype))
+            cur = self._scratch_slots[slot] = (key, _new_planes(fmt, w, h, (nframes,), dtype, self.device))
         return [t[:nframes] for t in cur[1]]
-
-    def _new_planes(self, fmt: PixFmt, w: int, h: int, lead: tuple, dtype) -> list:
-        return [torch.empty(lead + fmt.plane_shape(i, w, h), dtype=dtype, device=self.device) for i in range(3)]
 
     def _lut_then_resize(self, src, dst, fin: Optional[PixFmt], fout: PixFmt, w: int, h: int, out_size, row0: int, rows, chunk,
                          chroma_loc, lut_call, src_frames=None):
@@ -705,7 +719,7 @@ class LutEngine:
             raise ValueError("a resize (out_size) takes whole frames: row0 / rows are not supported with it")
         if dst is None:
             lead = tuple(src_frames[0].shape[:1]) if src_frames is not None else tuple(src[0].shape[:-2])
-            dst = self._new_planes(fout, dw, dh, lead, _yuv_out_dtype(fout.depth, src[0].dtype))
+            dst = _new_planes(fout, dw, dh, lead, _yuv_out_dtype(fout.depth, src[0].dtype), self.device)
         if src_frames is None:             # (a packed source comes checked, as a list of one [F,H,W,C] tensor, in src_frames)
             _check_planes(src, fin, w, h, "source")
         _check_planes(dst, fout, dw, dh, "destination")
@@ -773,14 +787,11 @@ class LutEngine:
         size and the resize reads them back; whole frames only, not in place.  The resize sites chroma by `chroma_loc`."""
         if dither not in _native.DITHER:
             raise ValueError(f"unknown dither mode '{dither}'")
-        if check_packed_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size):
-            return self._apply_yuv_packed(src, dst, yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt), interp, matrix_in,
-                                          matrix_out, range_src, range_in, range_out, lut_depth, row0, rows, width)
-        if width is not None:
-            raise ValueError("width is for a packed 4:2:2 side; planar and semi-planar frames tell their own")
-        if check_semi_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size):
-            return self._apply_yuv_semi(src, dst, yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt), interp, matrix_in,
-                                        matrix_out, range_src, range_in, range_out, lut_depth, row0, rows)
+        kind = check_container_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size, width=width)
+        if kind is not None:
+            return self._apply_yuv_container(kind == "packed", src, dst, yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt),
+                                             interp, matrix_in, matrix_out, range_src, range_in, range_out, lut_depth, row0, rows,
+                                             width)
         fin = parse_pix_fmt(pix_fmt)
         fout = parse_pix_fmt(out_pix_fmt or pix_fmt)
         if fin.family != "yuv" or fout.family != "yuv":
@@ -797,7 +808,7 @@ class LutEngine:
             return self._lut_then_resize(src, dst, fin, fout, w, h, out_size, row0, rows, resize_chunk, chroma_loc,
                                          lambda s_, d_: self.apply_yuv(s_, d_, **kw))
         if dst is None:
-            dst = self._new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype))
+            dst = _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), self.device)
         _check_planes(src, fin, w, h, "source")
         _check_planes(dst, fout, w, h, "destination")
         s, d, nf = _plane_pair(src, dst, self.device)
@@ -822,63 +833,35 @@ class LutEngine:
                     self._ctx, C.byref(p), _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(d), row0, rows))
         return dst
 
-    def _apply_yuv_semi(self, src, dst, fin, fout, interp, matrix_in, matrix_out, range_src, range_in, range_out, lut_depth,
-                        row0, rows):
-        """apply_yuv with a semi-planar side (lutr_apply_yuv_semi); the options were checked by `check_semi_options`."""
+    def _apply_yuv_container(self, packed, src, dst, fin, fout, interp, matrix_in, matrix_out, range_src, range_in, range_out,
+                             lut_depth, row0, rows, width):
+        """apply_yuv with a semi-planar side (lutr_apply_yuv_semi) or, `packed`, a packed 4:2:2 side (lutr_apply_yuv_packed: a
+        side may be a bare tensor, and `width` names an odd width); the options were checked by `check_container_options`."""
         p = _yuv_params(fin.code, fout.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
                         range_src, range_in or range_src, range_out)
-        if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
-            raise ValueError(f"'{fin.name}' takes {fin.nplanes} planes")
-        h, w = src[0].shape[-2], src[0].shape[-1]
-        if dst is None:
-            dt = _yuv_out_dtype(fout.depth, src[0].dtype)
-            dst = [torch.empty(tuple(src[0].shape[:-2]) + fout.plane_shape(i, w, h), dtype=dt, device=self.device)
-                   for i in range(fout.nplanes)]
-        _check_planes(src, fin, w, h, "source")
-        _check_planes(dst, fout, w, h, "destination")
-        s, nf = _planes_struct(src, self.device, fin.nplanes)
-        d, nfd = _planes_struct(dst, self.device, fout.nplanes)
-        if nf != nfd:
-            raise ValueError("src and dst disagree on the number of frames")
-        lay = [_native.YuvLayout(int(f.nplanes == 2), getattr(f, "swap", 0), getattr(f, "shift", 0)) for f in (fin, fout)]
-        rows = h - row0 if rows is None else rows
-        with self._lock:
-            self._bind_stream()
-            _native.check(self._lib.lutr_apply_yuv_semi(
-                self._ctx, C.byref(p), _native.INTERP[interp], C.byref(lay[0]), C.byref(lay[1]), w, h, nf, C.byref(s),
-                C.byref(d), row0, rows))
-        return dst
-
-    def _apply_yuv_packed(self, src, dst, fin, fout, interp, matrix_in, matrix_out, range_src, range_in, range_out, lut_depth,
-                          row0, rows, width):
-        """apply_yuv with a packed 4:2:2 side (lutr_apply_yuv_packed); the options were checked by `check_packed_options`."""
-        p = _yuv_params(fin.code, fout.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
-                        range_src, range_in or range_src, range_out)
-        bare = isinstance(dst, torch.Tensor)
-        if isinstance(src, torch.Tensor):
+        bare = packed and isinstance(dst, torch.Tensor)
+        if packed and isinstance(src, torch.Tensor):
             src = [src]
         if bare:
             dst = [dst]
-        if len(src) != fin.nplanes:
+        if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
             raise ValueError(f"'{fin.name}' takes {fin.nplanes} plane{'s' if fin.nplanes > 1 else ''}")
         w, h = packed_frame_width(fin, src, width), src[0].shape[-2]
         if dst is None:
-            dt = _yuv_out_dtype(fout.depth, src[0].dtype)
-            dst = [torch.empty(tuple(src[0].shape[:-2]) + fout.plane_shape(i, w, h), dtype=dt, device=self.device)
-                   for i in range(fout.nplanes)]
+            dst = _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), self.device)
         _check_planes(src, fin, w, h, "source")
         _check_planes(dst, fout, w, h, "destination")
         s, nf = _planes_struct(src, self.device, fin.nplanes)
         d, nfd = _planes_struct(dst, self.device, fout.nplanes)
         if nf != nfd:
             raise ValueError("src and dst disagree on the number of frames")
-        pk = [_native.YuvPacking(int(f.nplanes == 1), getattr(f, "order", 0), getattr(f, "shift", 0)) for f in (fin, fout)]
+        entry = self._lib.lutr_apply_yuv_packed if packed else self._lib.lutr_apply_yuv_semi
+        sides = [f.packing() if packed else f.layout() for f in (fin, fout)]
         rows = h - row0 if rows is None else rows
         with self._lock:
             self._bind_stream()
-            _native.check(self._lib.lutr_apply_yuv_packed(
-                self._ctx, C.byref(p), _native.INTERP[interp], C.byref(pk[0]), C.byref(pk[1]), w, h, nf, C.byref(s),
-                C.byref(d), row0, rows))
+            _native.check(entry(self._ctx, C.byref(p), _native.INTERP[interp], C.byref(sides[0]), C.byref(sides[1]), w, h, nf,
+                                C.byref(s), C.byref(d), row0, rows))
         return dst[0] if bare else dst
 
     # -- RGB source, YUV output (DESIGN.md 3.9) --------------------------------
@@ -945,7 +928,7 @@ class LutEngine:
             return self._lut_then_resize(src, dst, PixFmt(fin.name, "gbr", fin.depth, 0, 0, True), fout, w, h, out_size, row0,
                                          rows, resize_chunk, None, lambda s_, d_: self.apply_rgb_to_yuv(s_, d_, **kw))
         if dst is None:
-            dst = self._new_planes(fout, w, h, lead, _yuv_out_dtype(fout.depth, None))      # (no dtype to inherit: int16)
+            dst = _new_planes(fout, w, h, lead, _yuv_out_dtype(fout.depth, None), self.device)      # (no dtype to inherit: int16)
         _check_planes(dst, fout, w, h, "destination")
         d, nfd = _planes_struct(dst, self.device)
         if nf != nfd:

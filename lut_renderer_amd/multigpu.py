@@ -28,8 +28,8 @@ import torch
 
 from . import _native
 from .cube import CubeLut, read_lut
-from .engine import (LutEngine, check_packed_options, check_semi_options, packed_frame_width, parse_pix_fmt, parse_rgb_source,
-                     yuv_side)
+from .engine import (LutEngine, _new_planes, _yuv_out_dtype, check_container_options, packed_frame_width, parse_pix_fmt,
+                     parse_rgb_source, yuv_side)
 from .shard import row_blocks
 
 
@@ -128,25 +128,22 @@ class LutEngineGroup:
             raise ValueError("error-diffusion dither couples the rows of a frame: it cannot be row-sharded")
         if "row0" in kw or "rows" in kw:
             raise ValueError("the group owns the row partition")
-        bare = False
-        if check_packed_options(pix_fmt, out_pix_fmt, "none", kw.get("chroma_loc"), kw.get("out_size")):
-            # a packed 4:2:2 side: one buffer with the frame's rows -- any row for a 4:2:2 destination, even
-            # rows for a planar 4:2:0 one, which is the union block rule below
+        # a semi-planar side is two planes, the second with the chroma plane's rows: the shard rule is unchanged.
+        # A packed 4:2:2 side (3.12) is one buffer with the frame's rows -- any row for a 4:2:2 destination, even rows for a
+        # planar 4:2:0 one, which is the union block rule below
+        kind = check_container_options(pix_fmt, out_pix_fmt, "none", kw.get("chroma_loc"), kw.get("out_size"))
+        if kind is None:
+            fin, fout = parse_pix_fmt(pix_fmt), parse_pix_fmt(out_pix_fmt or pix_fmt)
+        else:
             fin, fout = yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt)
-            bare = isinstance(dst, torch.Tensor)
+        bare = kind == "packed" and isinstance(dst, torch.Tensor)
+        if kind == "packed":
             src = [src] if isinstance(src, torch.Tensor) else src
             dst = [dst] if bare else dst
-        elif check_semi_options(pix_fmt, out_pix_fmt, "none", kw.get("chroma_loc"), kw.get("out_size")):
-            # a semi-planar side: two planes, the second with the chroma plane's rows -- the shard rule is unchanged
-            fin, fout = yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt)
-        else:
-            fin, fout = parse_pix_fmt(pix_fmt), parse_pix_fmt(out_pix_fmt or pix_fmt)
         h, w = src[0].shape[-2], packed_frame_width(fin, src, kw.get("width"))
         home = src[0].device
         if dst is None:
-            dt = torch.uint8 if fout.depth <= 8 else (src[0].dtype if src[0].element_size() == 2 else torch.int16)
-            lead = tuple(src[0].shape[:-2])
-            dst = [torch.empty(lead + fout.plane_shape(i, w, h), dtype=dt, device=home) for i in range(fout.nplanes)]
+            dst = _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), home)
         bh = 1 << max(fin.csy, fout.csy)                           # the union block: whole chroma rows on both sides
         blocks = row_blocks(h, len(self.engines), align=bh)
         self.last_blocks = blocks
@@ -214,8 +211,7 @@ class LutEngineGroup:
             lead = tuple(first.shape[:-3]) if fin.packed else tuple(first.shape[:-2])
             home = first.device
             if dst is None:
-                dt = torch.uint8 if fout.depth <= 8 else torch.int16
-                dst = [torch.empty(lead + fout.plane_shape(i, w, h), dtype=dt, device=home) for i in range(3)]
+                dst = _new_planes(fout, w, h, lead, _yuv_out_dtype(fout.depth, None), home)
 
             def rows_of(a, b):
                 return src[..., a:b, :, :] if fin.packed else [p[..., a:b, :] for p in src]

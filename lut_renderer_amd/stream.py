@@ -18,14 +18,14 @@ from typing import Callable, Iterable, Iterator, List, Optional
 import numpy as np
 import torch
 
-from .engine import (LutEngine, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, parse_packed_yuv_fmt, parse_pix_fmt, parse_rgb_source,
-                     parse_semi_fmt, parse_size)
+from .engine import LutEngine, RgbSource, parse_rgb_source, parse_size, yuv_side
 
 
 @dataclass
 class FrameLayout:
-    """Byte layout of one planar frame in a rawvideo stream."""
-    fmt: PixFmt
+    """Byte layout of one YUV (or gbrp) frame in a rawvideo stream: the planes of `fmt` back to back -- three for a planar
+    format, luma then the chroma pairs for a semi-planar one, the one buffer of a packed 4:2:2 one (3.12)."""
+    fmt: object      # PixFmt | SemiFmt | PackedYuvFmt
     width: int
     height: int
 
@@ -35,7 +35,7 @@ class FrameLayout:
 
     @property
     def plane_shapes(self) -> List[tuple]:
-        return [self.fmt.plane_shape(i, self.width, self.height) for i in range(3)]
+        return [self.fmt.plane_shape(i, self.width, self.height) for i in range(self.fmt.nplanes)]
 
     @property
     def plane_bytes(self) -> List[int]:
@@ -46,7 +46,7 @@ class FrameLayout:
         return sum(self.plane_bytes)
 
     def plane_views(self, buf: torch.Tensor, nframes: int) -> List[torch.Tensor]:
-        """[F,H,W] views of the three planes inside a flat uint8 buffer of `nframes` frames."""
+        """[F,H,W] views of the planes inside a flat uint8 buffer of `nframes` frames."""
         dt = torch.uint8 if self.itemsize == 1 else torch.int16
         typed = buf.view(dt)
         fe = self.frame_bytes // self.itemsize
@@ -57,74 +57,9 @@ class FrameLayout:
         return out
 
 
-@dataclass
-class SemiFrameLayout:
-    """Byte layout of one semi-planar frame (nv12, p010le, ..) in a rawvideo stream: the luma plane, then the
-    plane of chroma pairs."""
-    fmt: SemiFmt
-    width: int
-    height: int
-
-    @property
-    def itemsize(self) -> int:
-        return 1 if self.fmt.depth <= 8 else 2
-
-    @property
-    def plane_shapes(self) -> List[tuple]:
-        return [self.fmt.plane_shape(i, self.width, self.height) for i in range(2)]
-
-    @property
-    def frame_bytes(self) -> int:
-        return sum(h * w for h, w in self.plane_shapes) * self.itemsize
-
-    def plane_views(self, buf: torch.Tensor, nframes: int) -> List[torch.Tensor]:
-        """[F,H,W] and [F,CH,2*CW] views of the two planes inside a flat uint8 buffer of `nframes` frames."""
-        typed = buf.view(torch.uint8 if self.itemsize == 1 else torch.int16)
-        fe = self.frame_bytes // self.itemsize
-        out, off = [], 0
-        for h, w in self.plane_shapes:
-            out.append(torch.as_strided(typed, (nframes, h, w), (fe, w, 1), off))
-            off += h * w
-        return out
-
-
-@dataclass
-class PackedYuvFrameLayout:
-    """Byte layout of one packed 4:2:2 frame (uyvy422, y210le, ..) in a rawvideo stream: h rows of ceil(w / 2)
-    groups of four samples."""
-    fmt: PackedYuvFmt
-    width: int
-    height: int
-
-    @property
-    def itemsize(self) -> int:
-        return 1 if self.fmt.depth <= 8 else 2
-
-    @property
-    def plane_shapes(self) -> List[tuple]:
-        return [self.fmt.plane_shape(0, self.width, self.height)]
-
-    @property
-    def frame_bytes(self) -> int:
-        h, w = self.plane_shapes[0]
-        return h * w * self.itemsize
-
-    def plane_views(self, buf: torch.Tensor, nframes: int) -> List[torch.Tensor]:
-        """The one [F,H,4*G] view of the frames inside a flat uint8 buffer of `nframes` frames."""
-        typed = buf.view(torch.uint8 if self.itemsize == 1 else torch.int16)
-        h, w = self.plane_shapes[0]
-        return [torch.as_strided(typed, (nframes, h, w), (h * w, w, 1), 0)]
-
-
-def yuv_layout(pix_fmt: str, width: int, height: int):
-    """`SemiFrameLayout` for a semi-planar name, `PackedYuvFrameLayout` for a packed 4:2:2 one, else the planar `FrameLayout`."""
-    semi = parse_semi_fmt(pix_fmt)
-    if semi is not None:
-        return SemiFrameLayout(semi, width, height)
-    packed = parse_packed_yuv_fmt(pix_fmt)
-    if packed is not None:
-        return PackedYuvFrameLayout(packed, width, height)
-    return FrameLayout(parse_pix_fmt(pix_fmt.replace("yuvj", "yuv")), width, height)
+def yuv_layout(pix_fmt: str, width: int, height: int) -> FrameLayout:
+    """The `FrameLayout` of a planar, semi-planar or packed 4:2:2 YUV name (or gbrp)."""
+    return FrameLayout(yuv_side(pix_fmt), width, height)
 
 
 @dataclass
@@ -175,8 +110,7 @@ class FloatFrameLayout:
 
 def input_layout(pix_fmt: str, width: int, height: int):
     """The layout of a rawvideo input: `PackedFrameLayout` for a packed RGB name, `FloatFrameLayout` for a planar float one,
-    `SemiFrameLayout` for a semi-planar YUV one, `PackedYuvFrameLayout` for a packed 4:2:2 YUV one, else `FrameLayout` (planar
-    YUV or gbrp)."""
+    else `FrameLayout` (planar, semi-planar or packed 4:2:2 YUV, or gbrp)."""
     rgb = parse_rgb_source(pix_fmt)
     if rgb is not None and rgb.packed:
         return PackedFrameLayout(rgb, width, height)
@@ -211,7 +145,7 @@ class HostPipeline:
         self.kw = dict(apply_kw, pix_fmt=self.fin.fmt.name, out_pix_fmt=self.fout.fmt.name)
         if out_size is not None:
             self.kw["out_size"] = (ow, oh)
-        if isinstance(self.fin, PackedYuvFrameLayout) or isinstance(self.fout, PackedYuvFrameLayout):
+        if self.fin.fmt.nplanes == 1 or self.fout.fmt.nplanes == 1:
             self.kw["width"] = width                           # (a packed row cannot tell an odd width)
         dev = engine.device
         self.h_in = [torch.empty(self.batch * self.fin.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]

@@ -116,18 +116,20 @@ def test_odd_width_and_low_bits():
 # ------------------------------------------------------------------ rawvideo layouts
 def test_input_layouts():
     import torch
-    from lut_renderer_amd.stream import FrameLayout, PackedYuvFrameLayout, SemiFrameLayout, input_layout
+    from lut_renderer_amd.engine import PackedYuvFmt, PixFmt, SemiFmt
+    from lut_renderer_amd.stream import FrameLayout, input_layout
     lay = input_layout("uyvy422", 65, 33)
-    assert isinstance(lay, PackedYuvFrameLayout) and lay.frame_bytes == 33 * 4 * 33 and lay.fmt.name == "uyvy422"
+    assert isinstance(lay, FrameLayout) and isinstance(lay.fmt, PackedYuvFmt)
+    assert lay.frame_bytes == 33 * 4 * 33 and lay.fmt.name == "uyvy422"
     v = lay.plane_views(torch.zeros(2 * lay.frame_bytes, dtype=torch.uint8), 2)
     assert [tuple(t.shape) for t in v] == [(2, 33, 132)] and v[0].dtype == torch.uint8
     lay = input_layout("y210le", 64, 8)
-    assert isinstance(lay, PackedYuvFrameLayout) and lay.frame_bytes == 2 * 8 * 128 and lay.itemsize == 2
+    assert isinstance(lay.fmt, PackedYuvFmt) and lay.frame_bytes == 2 * 8 * 128 and lay.itemsize == 2
     buf = torch.arange(2 * lay.frame_bytes // 2, dtype=torch.int32).to(torch.int16).view(torch.uint8)
     v = lay.plane_views(buf, 2)
     assert [tuple(t.shape) for t in v] == [(2, 8, 128)] and v[0].dtype == torch.int16
     assert int(v[0][1, 0, 0]) == 8 * 128 and int(v[0][1, 2, 5]) == 8 * 128 + 2 * 128 + 5
-    assert isinstance(input_layout("yuv422p", 65, 33), FrameLayout) and isinstance(input_layout("nv16", 65, 33), SemiFrameLayout)
+    assert isinstance(input_layout("yuv422p", 65, 33).fmt, PixFmt) and isinstance(input_layout("nv16", 65, 33).fmt, SemiFmt)
 
 
 # ------------------------------------------------------------------ routing

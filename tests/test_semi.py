@@ -97,19 +97,21 @@ def test_words_of_p010le_and_pairs_of_nv21():
 # ------------------------------------------------------------------ rawvideo layouts
 def test_input_layouts():
     import torch
-    from lut_renderer_amd.stream import FrameLayout, SemiFrameLayout, input_layout
+    from lut_renderer_amd.engine import PixFmt, SemiFmt
+    from lut_renderer_amd.stream import FrameLayout, input_layout
     lay = input_layout("nv12", 65, 33)
-    assert isinstance(lay, SemiFrameLayout) and lay.frame_bytes == 65 * 33 + 2 * 33 * 17 and lay.fmt.name == "nv12"
+    assert isinstance(lay, FrameLayout) and isinstance(lay.fmt, SemiFmt)
+    assert lay.frame_bytes == 65 * 33 + 2 * 33 * 17 and lay.fmt.name == "nv12"
     v = lay.plane_views(torch.zeros(2 * lay.frame_bytes, dtype=torch.uint8), 2)
     assert [tuple(t.shape) for t in v] == [(2, 33, 65), (2, 17, 66)] and all(t.dtype == torch.uint8 for t in v)
     lay = input_layout("p210le", 65, 33)
-    assert isinstance(lay, SemiFrameLayout) and lay.frame_bytes == 2 * (65 * 33 + 2 * 33 * 33) and lay.itemsize == 2
+    assert isinstance(lay.fmt, SemiFmt) and lay.frame_bytes == 2 * (65 * 33 + 2 * 33 * 33) and lay.itemsize == 2
     buf = torch.arange(2 * lay.frame_bytes // 2, dtype=torch.int32).to(torch.int16).view(torch.uint8)
     v = lay.plane_views(buf, 2)
     assert [tuple(t.shape) for t in v] == [(2, 33, 65), (2, 33, 66)] and all(t.dtype == torch.int16 for t in v)
     fe = lay.frame_bytes // 2
     assert int(v[0][1, 0, 0]) == np.int16(fe) and int(v[1][0, 0, 0]) == 65 * 33 and int(v[1][1, 2, 5]) == np.int16(fe + 65 * 33 + 2 * 66 + 5)
-    assert isinstance(input_layout("yuv420p", 65, 33), FrameLayout)
+    assert isinstance(input_layout("yuv420p", 65, 33), FrameLayout) and isinstance(input_layout("yuv420p", 65, 33).fmt, PixFmt)
 
 
 # ------------------------------------------------------------------ routing
