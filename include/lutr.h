@@ -460,6 +460,36 @@ int lutr_apply_yuv_packed(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, c
                           const lutr_yuv_packing *out, int w, int h, int nframes, const lutr_planes *src,
                           const lutr_planes *dst, int row0, int rows);
 
+/* ---- two outputs from one pass (the reference's "pro" mode, ffmpeg.py:417-472: a ProRes 422 HQ master with the
+ *      LUT in yuv422p10le, then the delivery file in the user's pix_fmt -- both from the same lut3d result) ---- */
+/* lutr_apply_yuv_xsub with a second destination: planar YUV in, TWO planar YUV frames out.  fmt_out2 (a LUTR_FMT code) may differ
+ * from p->fmt_out in depth (8..16) and chroma subsampling (4:2:0 / 4:2:2 / 4:4:4); both outputs share matrix_out and range_out.
+ * dst is bit-identical to what lutr_apply_yuv_xsub(ctx, p, ...) writes (lutr_apply_yuv when fmt_in and fmt_out share the layout),
+ * dst2 to the same call with fmt_out2 in place of fmt_out: everything *p expresses on the input side (the full-range prologue,
+ * matrices, ranges, lut_depth), a .csp prelut and all five interpolation modes are that call's arithmetic unchanged.  The source
+ * is read once and lut3d evaluated once per pixel; the output stage runs twice.  Chroma is replicated over its INPUT block; each
+ * output's chroma sample is the mean of the LUT's integer RGB over that output's OWN block (constants: the output-stage entries
+ * of lutr_yuv_constants_xsub for fmt_out and for fmt_out2); a partial block at an odd edge takes the edge column / row again.
+ * row0 and rows must be multiples of the union block height 2^max(icsy, csy of fmt_out, csy of fmt_out2) unless row0 + rows == h.
+ * Always strict precision (fast / fma32 run strict here, no suffix on the last kernel).
+ * Not in place: the bounding byte ranges (all rows and frames) of the source planes, of dst's planes and of dst2's planes must
+ * all be disjoint from one another (the rule of lutr_apply_yuv_sited).
+ * LUTR_EINVAL with a message, before anything touches the device: a bad fmt_out2 (depth outside 8..16, 4:4:0), a null pointer
+ * where a plane is needed, 16-bit planes whose base, stride or (batches) frame stride is odd, row0 / rows off the union block,
+ * any overlap, variant vec_lds (there is no LDS kernel for this path).  Variant vec_global where the vector kernel cannot take
+ * the call is LUTR_EINVAL too, found where the kernel is chosen, as in the sibling entry points: the device is selected and a
+ * .csp prelut's table may have been uploaded by then, no kernel has run and nothing is written.
+ * Kernels: "k_yuv_dual_vec<win,wa,wb,icsx,icsy,bcsx,bcsy,interp>" (nearest / trilinear / tetrahedral; output A is the 4:2:2 one
+ * -- dst2 when only it is 4:2:2 -- and B the other, in the container mixes 16 -> 16+16, 16 -> 16+8 and 8 -> 8+8 bit; width a
+ * multiple of 8 luma samples, 4 for 16 -> 16+16; positive strides aligned to the accesses; row0 / rows multiples of the union
+ * block height), "k_yuv_dual_generic" for everything else (one thread per union block; any depth 8..16, stride, alignment or
+ * size; all five modes; an 8-bit source with a 16-bit output; two outputs of which neither is 4:2:2); a ragged width on aligned
+ * rows is split between the two.  Variants: auto and generic as for lutr_apply_yuv.
+ * Not covered: dither, chroma siting or a resize on either output, semi-planar / packed / RGB / float sides, different matrices
+ * or ranges per output, more than two outputs, a tile (LDS) kernel. */
+int lutr_apply_yuv_dual(lutr_ctx *ctx, const lutr_yuv_params *p, int fmt_out2, int interp, int w, int h, int nframes,
+                        const lutr_planes *src, const lutr_planes *dst, const lutr_planes *dst2, int row0, int rows);
+
 /* ---- precision ---- */
 /* STRICT (default): every kernel is a bit-exact restatement of FFmpeg's scalar C lut3d (vf_lut3d.c order of operations,
  * no fused multiply-add in the blend).  FAST: permission to use the tolerance-bounded tile kernels -- lattice staged as

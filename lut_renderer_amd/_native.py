@@ -41,6 +41,7 @@ SYMBOLS = (
     "lutr_apply_yuv_sited", "lutr_yuv_constants_sited", "lutr_apply_yuv_xsub", "lutr_yuv_constants_xsub",
     "lutr_apply_rgb_to_yuv", "lutr_yuv_constants_rgb2yuv",
     "lutr_apply_planar_rgb_f32", "lutr_apply_rgbf_to_yuv", "lutr_apply_yuv_semi", "lutr_apply_yuv_packed",
+    "lutr_apply_yuv_dual",
     "lutr_resize_filter", "lutr_resize_planes",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
 )
@@ -178,6 +179,8 @@ def load() -> C.CDLL:
                                         C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_apply_yuv_packed.argtypes = [vp, C.POINTER(YuvParams), ci, C.POINTER(YuvPacking), C.POINTER(YuvPacking), ci, ci, ci,
                                           C.POINTER(Planes), C.POINTER(Planes), ci, ci]
+    lib.lutr_apply_yuv_dual.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes),
+                                        C.POINTER(Planes), ci, ci]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]
     lib.lutr_ctx_set_variant.argtypes = [vp, ci]

@@ -144,6 +144,17 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
     return kw
 
 
+def dual_call_for(kw: dict, second_pix_fmt: str, chroma_loc: Optional[str] = None, out_size=None) -> dict:
+    """Keyword arguments of LutEngine.apply_yuv_dual from those `engine_call_for` returned for the first output
+    (with `dither` filled in, if any) and the name of the second one.  ValueError for an RGB / float / semi-planar / packed side,
+    dither, chroma_loc and a resize."""
+    from .engine import check_dual_options
+    check_dual_options(kw.get("pix_fmt"), kw.get("out_pix_fmt"), second_pix_fmt, kw.get("dither", "none"), chroma_loc, out_size)
+    dual = {k: v for k, v in kw.items() if k != "dither"}
+    dual["out2_pix_fmt"] = second_pix_fmt.replace("yuvj", "yuv")
+    return dual
+
+
 def is_rgb_call(kw: dict) -> bool:
     """True when `engine_call_for` returned arguments of `apply_rgb_to_yuv` (an RGB source)."""
     from .engine import parse_rgb_source
@@ -162,7 +173,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               color_range: Optional[str] = None, output_tags: str = "bt709", out_pix_fmt: Optional[str] = None,
               zscale_dither: str = "none", out: Optional[Sequence] = None, engine=None,
               devices: Sequence[int] = (0,), precision: str = "strict", chroma_loc: Optional[str] = None,
-              resolution: Optional[str] = None):
+              resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -197,7 +208,12 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
 
     `resolution` is `ProcessingParams.resolution`, a "WxH" string as ffmpeg's `-s` takes it: the output planes are resized to
     that size on the GPU after everything else, and `out` must have that size.  One device only (no
-    LutEngineGroup): a row-sharded resize would need halos between the devices."""
+    LutEngineGroup): a row-sharded resize would need halos between the devices.
+
+    `second_pix_fmt` asks for a SECOND planar YUV output from the same pass (the reference's "pro" mode: the
+    yuv422p10le master and the delivery format): the return value is then ((planes_out, planes_out2), tags), and `out`, if
+    given, is the pair (planes, planes2).  Planar YUV on all three sides; no RGB / float / semi-planar / packed side, no dither,
+    chroma_loc or resolution."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -234,7 +250,11 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     kw["dither"] = "error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none"
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
-    if rgb_src is not None:
+    if second_pix_fmt is not None:
+        # the second format is resolved beside engine_call_for's: the same chain, one more output stage; dual_call_for makes
+        # every check of the formats and options
+        kw = dual_call_for(kw, second_pix_fmt, chroma_loc, out_size)
+    elif rgb_src is not None:
         if chroma_loc is not None:
             raise ValueError("chroma siting (chroma_loc) is not defined for an RGB source")
     else:
@@ -268,6 +288,9 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         if float_out:
             n_out = parse_rgb_source(kw["out_pix_fmt"]).nplanes
             result = eng.apply_rgb_float(planes[:n_out], out, interp=kw["interp"])
+        elif second_pix_fmt is not None:
+            o1, o2 = out if out is not None else (None, None)
+            result = eng.apply_yuv_dual(planes, o1, o2, **kw)
         else:
             result = eng.apply_rgb_to_yuv(planes, out, **kw) if rgb_src is not None else eng.apply_yuv(planes, out, **kw)
         if own:

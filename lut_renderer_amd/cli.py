@@ -64,6 +64,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--out-size", default=None, metavar="WxH",
                     help="engine setting: resize the output frames to WxH on the GPU after the LUT (the reference's -s, "
                          "DESIGN.md 3.7); frames on -o have this size")
+    ap.add_argument("--second-output", default=None, metavar="PATH",
+                    help="engine setting: write a second rawvideo output from the same LUT pass (DESIGN.md 3.13) to this file or "
+                         "FIFO (not -); needs --second-pix-fmt")
+    ap.add_argument("--second-pix-fmt", default=None, metavar="FMT",
+                    help="planar YUV format of --second-output; it may differ from --out-pix-fmt in depth and chroma subsampling")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("-y", action="store_true", help="overwrite the output (ffmpeg's -y)")
@@ -103,6 +108,16 @@ def plan_from_args(args):
     if getattr(args, "out_size", None):
         from .engine import parse_size
         parse_size(args.out_size)
+    second_out, second_fmt = getattr(args, "second_output", None), getattr(args, "second_pix_fmt", None)
+    if (second_out is None) != (second_fmt is None):
+        raise ValueError("--second-output and --second-pix-fmt go together: give both or neither")
+    if second_out is not None:
+        if second_out == "-":
+            raise ValueError("--second-output is a file or FIFO, not '-': stdout carries the first output or the report")
+        if args.output != "-" and os.path.realpath(second_out) == os.path.realpath(args.output):
+            raise ValueError("--second-output names the same file as -o: the two outputs need a file each")
+        from .api import dual_call_for
+        kw = dual_call_for(kw, second_fmt, kw.get("chroma_loc"), getattr(args, "out_size", None))
     return plan, kw, w, h
 
 
@@ -122,6 +137,9 @@ def main(argv=None) -> int:
         if not piped_out and os.path.exists(args.output) and not args.y:
             raise FileExistsError(f"{args.output} exists (pass -y to overwrite)")
         plan, kw, w, h = plan_from_args(args)
+        second = args.second_output
+        if second is not None and os.path.isfile(second) and not args.y:
+            raise FileExistsError(f"{second} exists (pass -y to overwrite)")
         from .cube import read_lut
         from .engine import LutEngine
         from .stream import HostPipeline
@@ -130,7 +148,9 @@ def main(argv=None) -> int:
         eng.set_precision(args.precision)
         eng.set_lut(read_lut(args.cube))
         pix_fmt, out_fmt = kw.pop("pix_fmt"), kw.pop("out_pix_fmt")
-        pipe = HostPipeline(eng, pix_fmt, w, h, batch=args.batch, out_pix_fmt=out_fmt, out_size=args.out_size, **kw)
+        second_fmt = kw.pop("out2_pix_fmt", None)
+        pipe = HostPipeline(eng, pix_fmt, w, h, batch=args.batch, out_pix_fmt=out_fmt, out_size=args.out_size,
+                            second_pix_fmt=second_fmt, **kw)
         fb = pipe.fin.frame_bytes
         if piped_in:
             total = None if args.duration is None else max(1, int(round(args.duration * args.fps)))
@@ -149,7 +169,11 @@ def main(argv=None) -> int:
         state = {"done": 0}
         fi = sys.stdin.buffer if piped_in else open(args.input, "rb")
         fo = sys.stdout.buffer if piped_out else open(args.output, "wb")
+        fo2 = None
         try:
+            if second is not None:
+                fo2 = open(second, "wb")
+
             def fill(buf, max_frames):
                 view, got = memoryview(buf)[: max_frames * fb], 0
                 while got < len(view):                       # a pipe returns short reads: collect the whole batch (or EOF)
@@ -165,9 +189,12 @@ def main(argv=None) -> int:
                 el = max(time.time() - t0, 1e-9)
                 say(f"frame={state['done']:6d} fps={state['done'] / el:7.1f} time={_hms(state['done'] / args.fps)}")
 
-            pipe.run(fill, drain, total_frames=None if piped_in else total, stop=lambda: stop["flag"])
+            pipe.run(fill, drain, total_frames=None if piped_in else total, stop=lambda: stop["flag"],
+                     drain2=None if fo2 is None else lambda buf, n: fo2.write(memoryview(buf)))
             fo.flush()
         finally:
+            if fo2 is not None:
+                fo2.close()
             if not piped_in:
                 fi.close()
             if not piped_out:

@@ -251,7 +251,8 @@ def build_pipeline(task: Task, ffmpeg_bin: str = "ffmpeg") -> List[CommandStage]
 def engine_command(source: Path, output: Path, params: ProcessingParams, lut_path: Path,
                    source_info: VideoInfo, python_bin: Optional[str] = None, device: int = 0,
                    notes: Optional[List[str]] = None, precision: str = "strict", chroma_loc: Optional[str] = None,
-                   gpu_resize: bool = False) -> List[str]:
+                   gpu_resize: bool = False, second_output: Optional[Path] = None,
+                   second_pix_fmt: Optional[str] = None) -> List[str]:
     """`build_command`'s twin for the LUT stage alone: the argv of the ENGINE CLI (`python -m lut_renderer_amd.cli`)
     that applies exactly the chain `build_command` would put into `-vf` -- the same `LutPlan`, rendered as CLI options
     instead of as a filter string (ffmpeg.py:195-247, :287-310).  `source` / `output` are rawvideo files (or `-`) in
@@ -261,7 +262,10 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     `precision` is the engine's own setting (`--precision`, default strict; the reference's records have no such field), and
     so is `chroma_loc` (`--chroma-loc`, rendered only when given: None keeps the replicating chroma contract).
     `gpu_resize` with `params.resolution` set moves the reference's `-s WxH` into the engine (`--out-size`); the
-    output format must then be planar (ValueError for packed formats).  False (default) leaves the argv as it was."""
+    output format must then be planar (ValueError for packed formats).  False (default) leaves the argv as it was.
+    `second_output` / `second_pix_fmt` (both or neither) add a second rawvideo output from the same LUT pass (`--second-output`,
+    `--second-pix-fmt`, DESIGN.md 3.13: the master and the delivery format of the "pro" mode together); rendered only when given.
+    Planar YUV on every side; not with dither, `chroma_loc` or `gpu_resize`."""
     import sys as _sys
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
@@ -321,6 +325,16 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
         if not _SIZE_RE.match(params.resolution):
             raise ValueError(f"bad resolution '{params.resolution}' (expected WxH)")
         cmd += ["--out-size", params.resolution]
+    if (second_output is None) != (second_pix_fmt is None):
+        raise ValueError("second_output and second_pix_fmt go together: give both or neither")
+    if second_output is not None:
+        if str(second_output) == "-":
+            raise ValueError("second_output is a file or FIFO, not '-'")
+        from .engine import check_dual_options
+        check_dual_options(str(source_info.pix_fmt), pix_fmt or None, second_pix_fmt,
+                           "error_diffusion" if "--zscale-dither" in cmd else "none", chroma_loc,
+                           params.resolution if "--out-size" in cmd else None)
+        cmd += ["--second-output", str(second_output), "--second-pix-fmt", second_pix_fmt]
     return cmd
 
 

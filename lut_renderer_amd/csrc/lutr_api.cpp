@@ -1164,6 +1164,71 @@ int lutr_apply_yuv_xsub(lutr_ctx *c, const lutr_yuv_params *p, int interp, int d
     return finish_launch(c, launch_yuv_dither(c->stream, L, K, P, G, F, din, dout, icsx, icsy, interp, ocsx, ocsy));
 }
 
+// lutr_apply_yuv_xsub's pass with a second destination.  Each output's constants are the block
+// make_yuv_consts_xsub forms for it (the input-stage entries of the two agree: they do not depend on fmt_out).
+int lutr_apply_yuv_dual(lutr_ctx *c, const lutr_yuv_params *p, int fmt_out2, int interp, int w, int h, int nframes,
+                        const lutr_planes *src, const lutr_planes *dst, const lutr_planes *dst2, int row0, int rows)
+{
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!dst2) { set_error("null argument"); return LUTR_EINVAL; }
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    YuvConsts K1, K2;
+    rc = make_yuv_consts_xsub(*p, &K1);
+    if (rc) return rc;
+    lutr_yuv_params p2 = *p;
+    p2.fmt_out = fmt_out2;
+    if ((fmt_out2 >> 10) || make_yuv_consts_xsub(p2, &K2)) {
+        set_error("bad fmt_out2 0x%x: the second output is planar 4:2:0 / 4:2:2 / 4:4:4 at a depth of 8 to 16 bit", fmt_out2);
+        return LUTR_EINVAL;
+    }
+    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
+    const int csx1 = LUTR_FMT_CSX(p->fmt_out), csy1 = LUTR_FMT_CSY(p->fmt_out);
+    const int csx2 = LUTR_FMT_CSX(fmt_out2), csy2 = LUTR_FMT_CSY(fmt_out2);
+    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout1 = LUTR_FMT_DEPTH(p->fmt_out), dout2 = LUTR_FMT_DEPTH(fmt_out2);
+    const int bh = 1 << std::max(icsy, std::max(csy1, csy2));
+    if (const int rc = check_row_blocks(row0, rows, h, bh, "union chroma block height")) return rc;
+    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for two outputs"); return LUTR_EINVAL; }
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    if (const int rc = check_planes_set(src, dst)) return rc;
+    if (const int rc = check_planes_set(dst2, nullptr)) return rc;
+    const struct { const char *side; const lutr_planes *pl; int depth; } sides[3] = {
+        {"source", src, din}, {"destination", dst, dout1}, {"second destination", dst2, dout2}};
+    for (const auto &s : sides)
+        for (int i = 0; i < 3; i++)
+            if (s.depth > 8 && !check_aligned(s.pl->data[i], s.pl->stride[i], s.pl->frame_stride[i], nframes, 1)) {
+                set_error("%s plane %d: 16-bit planes need 2-byte aligned rows", s.side, i);
+                return LUTR_EINVAL;
+            }
+    // one pass writes both outputs while it still reads the source: nothing may overlap anything
+    Span ss[3], d1[3], d2[3];
+    planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
+    planar_spans(dst, csx1, csy1, w, h, dout1 > 8 ? 2 : 1, nframes, d1);
+    planar_spans(dst2, csx2, csy2, w, h, dout2 > 8 ? 2 : 1, nframes, d2);
+    if (const int rc = check_disjoint("the two-output pass", true, ss, 3, d1, 3)) return rc;
+    if (check_disjoint("the two-output pass", true, ss, 3, d2, 3)) {
+        const std::string m = g_last_error;
+        set_error("%s (the second destination)", m.c_str());
+        return LUTR_EINVAL;
+    }
+    if (check_disjoint("", false, d1, 3, d2, 3)) {
+        set_error("the two destinations overlap: their byte ranges over all rows and frames must be disjoint");
+        return LUTR_EINVAL;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
+    LutConsts L; PlaneSet P; DstPlanes D2; FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
+    fill_planes(&P, src, dst);
+    for (int i = 0; i < 3; i++) {
+        D2.d[i] = (uint8_t *)dst2->data[i];
+        D2.ds[i] = dst2->stride[i];
+        D2.dfs[i] = dst2->frame_stride[i];
+    }
+    return finish_launch(c, launch_yuv_dual(c->stream, c->variant, L, K1, K2, P, D2, G, din, dout1, csx1, csy1, dout2, csx2, csy2,
+                                            icsx, icsy, interp));
+}
+
 // What a semi-planar and a packed side share: `noun` ("layout" | "packing") names the struct in the messages; the shift against
 // the format's depth, then `bad_shape` (the side's own refusal of the format's subsampling, or nullptr -- it has always come
 // between the two), then the `nplanes` planes the side has and their alignment.

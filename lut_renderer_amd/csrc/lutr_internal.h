@@ -65,6 +65,12 @@ struct PlaneSet {
     long long sfs[3], dfs[3];        // frame strides, bytes
 };
 
+// the planes of a second destination (lutr_dual.hip)
+struct DstPlanes {
+    uint8_t  *d[3];
+    long long ds[3], dfs[3];         // row / frame strides, bytes
+};
+
 // one interleaved image (or batch): component offsets in units of one component
 struct PackedSet {
     const uint8_t *s;
@@ -124,6 +130,21 @@ LUTR_XS_DECL(w00) LUTR_XS_DECL(w11) LUTR_XS_DECL(w10)
 // the dither path's unquantised pass for a subsampling change (k_yuv_float_xsub)
 void launch_yuv_float_xsub(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
                            const FloatPlanes &F, int win, int icsx, int icsy, int ocsx, int ocsy, int interp);
+
+// two outputs from one pass (lutr_dual.hip): input layout icsx, icsy; output 1 in P.d (depth dout1, layout csx1, csy1,
+// constants K1), output 2 in D2 (dout2, csx2, csy2, K2); K1 and K2 share the input stage.  nullptr = the variant cannot take the
+// call (vec_lds always; vec_global on layouts the vector kernel cannot take)
+const char *launch_yuv_dual(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K1, const YuvConsts &K2,
+                            const PlaneSet &P, const DstPlanes &D2, const FrameGeom &G, int din, int dout1, int csx1, int csy1,
+                            int dout2, int csx2, int csy2, int icsx, int icsy, int interp);
+// its vector kernels, one translation unit per container mix (w<in wide><A wide><B wide>): output A (P.d, KA) is 4:2:2, output B
+// has the layout bcsx, bcsy; nullptr = not a layout / mode it has
+#define LUTR_DU_DECL(tag) \
+    const char *launch_yuv_dual_vec_##tag(hipStream_t st, const LutConsts &L, const YuvConsts &KA, const YuvConsts &KB, \
+                                          const PlaneSet &P, const DstPlanes &B, const FrameGeom &G, int icsx, int icsy, int bcsx, \
+                                          int bcsy, int interp);
+LUTR_DU_DECL(w111) LUTR_DU_DECL(w110) LUTR_DU_DECL(w000)
+#undef LUTR_DU_DECL
 
 // semi-planar frames (lutr_semi.hip): the container of each side -- planar (three planes) or semi-planar (PlaneSet
 // slot 1 holds the Cb / Cr pairs, slot 2 is not read), Cr first with `swap`, 16-bit codes `shift` bits up in their words.  Both

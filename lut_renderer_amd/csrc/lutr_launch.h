@@ -103,8 +103,9 @@ inline unsigned block_grid(int w, int rows, int nframes, int csx, int csy)
 // vector kernels can take these planes and this geometry; vec / generic launch and return the kernel's name; tail(wv): the planes
 // moved right by wv pixels.  A ragged width on aligned (padded) rows goes to the vector kernel up to the last whole unit of unit_px
 // columns and to the generic kernel for the rest (the unit is a whole number of chroma blocks, so the split falls between two).
-template <class Fits, class Vec, class Generic, class Tail>
-const char *launch_vec_or_generic(int variant, const PlaneSet &P, const FrameGeom &G, int unit_px, Fits vec_fits, Vec vec,
+// Planes: PlaneSet, or whatever a path with more sides hands through to its own callbacks (lutr_dual.hip).
+template <class Planes, class Fits, class Vec, class Generic, class Tail>
+const char *launch_vec_or_generic(int variant, const Planes &P, const FrameGeom &G, int unit_px, Fits vec_fits, Vec vec,
                                   Generic generic, Tail tail)
 {
     if (variant == VAR_VEC_LDS) return nullptr;

@@ -310,6 +310,67 @@ def changes_subsampling(pix_fmt: str, out_pix_fmt: Optional[str]) -> bool:
     return (a.csx, a.csy) != (b.csx, b.csy)
 
 
+#: keywords of `apply_yuv` that the two-output pass does not take
+_DUAL_NOT_TAKEN = {"dither": "error-diffusion dither", "chroma_loc": "sited chroma resampling (chroma_loc)",
+                   "out_size": "a resize (out_size)", "resize_chunk": "a resize (out_size)",
+                   "width": "a packed side (width)"}
+
+
+def dual_side(name: Optional[str], what: str) -> PixFmt:
+    """One side of `apply_yuv_dual`, a planar YUV format (yuvj* read as yuv*); ValueError for RGB, float, semi-planar and packed
+    names.  `what` names the argument in the message."""
+    if not name:
+        raise ValueError(f"the two-output pass needs {what}")
+    if parse_semi_fmt(name) is not None or parse_packed_yuv_fmt(name) is not None or name in _PACKED_YUV_UNSUPPORTED:
+        raise ValueError(f"the two-output pass takes planar YUV on every side: {what} '{name}' is a semi-planar or packed container")
+    if parse_rgb_source(name) is not None:
+        raise ValueError(f"the two-output pass takes planar YUV on every side: {what} '{name}' is an RGB format")
+    fmt = parse_pix_fmt(name.replace("yuvj", "yuv"))
+    if fmt.family != "yuv":
+        raise ValueError(f"the two-output pass takes planar YUV on every side: {what} '{name}' is an RGB format")
+    return fmt
+
+
+def check_dual_options(pix_fmt: str, out_pix_fmt: Optional[str], out2_pix_fmt: Optional[str], dither: str = "none",
+                       chroma_loc: Optional[str] = None, out_size=None) -> Tuple[PixFmt, PixFmt, PixFmt]:
+    """The checks `apply_yuv_dual` makes of its formats and options before any GPU work: three planar YUV
+    sides, no dither, chroma_loc or out_size.  Returns the three parsed formats (source, first output, second output)."""
+    fin = dual_side(pix_fmt, "pix_fmt")
+    f1 = dual_side(out_pix_fmt or pix_fmt, "out_pix_fmt")
+    f2 = dual_side(out2_pix_fmt, "out2_pix_fmt")
+    if dither != "none":
+        raise ValueError("error-diffusion dither is not supported with a second output")
+    if chroma_loc is not None:
+        raise ValueError("sited chroma resampling (chroma_loc) is not supported with a second output")
+    if out_size is not None:
+        raise ValueError("a resize (out_size) is not supported with a second output")
+    return fin, f1, f2
+
+
+def refuse_dual_keywords(kw: dict) -> None:
+    """ValueError when `kw` holds a keyword of `apply_yuv` that the two-output pass does not take, whatever its value."""
+    for k, what in _DUAL_NOT_TAKEN.items():
+        if k in kw:
+            raise ValueError(f"{what} is not supported with a second output: apply_yuv_dual takes no '{k}'")
+
+
+def dual_args(src, dst, dst2, pix_fmt, out_pix_fmt, out2_pix_fmt):
+    """What `apply_yuv_dual` checks of its formats and planes before it touches the engine: the three formats, and the shapes
+    and dtypes of the planes given.  Returns (fin, f1, f2, w, h)."""
+    fin, f1, f2 = check_dual_options(pix_fmt, out_pix_fmt, out2_pix_fmt)
+    if isinstance(src, torch.Tensor) or len(src) != 3:
+        raise ValueError("expected three planes")
+    if not isinstance(src[0], torch.Tensor):
+        raise TypeError("planes must be torch tensors resident on the engine's GPU")
+    h, w = src[0].shape[-2], src[0].shape[-1]
+    _check_planes(src, fin, w, h, "source")
+    if dst is not None:
+        _check_planes(dst, f1, w, h, "destination")
+    if dst2 is not None:
+        _check_planes(dst2, f2, w, h, "second destination")
+    return fin, f1, f2, w, h
+
+
 #: frames per LUT launch when apply_yuv / apply_rgb resize (`out_size`): the LUT writes a chunk into the engine's scratch at the
 #: source size and the resize reads it back while it is still in the Infinity Cache (DESIGN.md 3.7).  LUTR_RESIZE_CHUNK overrides.
 RESIZE_CHUNK = 16
@@ -832,6 +893,40 @@ class LutEngine:
                 _native.check(self._lib.lutr_apply_yuv(
                     self._ctx, C.byref(p), _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(d), row0, rows))
         return dst
+
+    def apply_yuv_dual(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None,
+                       dst2: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: Optional[str] = None,
+                       out2_pix_fmt: str, interp: str = "tetrahedral", matrix_in: str = "bt709",
+                       matrix_out: Optional[str] = None, range_src: str = "tv", range_in: Optional[str] = None,
+                       range_out: str = "tv", lut_depth: Optional[int] = None, row0: int = 0, rows: Optional[int] = None,
+                       **other):
+        """`apply_yuv` with TWO planar YUV outputs from one pass (the reference's "pro" mode: a yuv422p10le
+        master and the delivery format): the source is read once and lut3d evaluated once per pixel; `out_pix_fmt` and
+        `out2_pix_fmt` may differ in depth and chroma subsampling and share `matrix_out` / `range_out`.  Each output has the bits
+        of `apply_yuv(..., out_pix_fmt=<its format>)` alone.  Always strict arithmetic; no dither, chroma_loc or out_size;
+        nothing may overlap (not in place).  row0 / rows are multiples of the union block height of the three layouts.
+        Returns (planes, planes2)."""
+        refuse_dual_keywords(other)
+        if other:
+            raise TypeError(f"apply_yuv_dual() got an unexpected keyword argument '{next(iter(other))}'")
+        fin, f1, f2, w, h = dual_args(src, dst, dst2, pix_fmt, out_pix_fmt, out2_pix_fmt)
+        p = _yuv_params(fin.code, f1.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
+                        range_src, range_in or range_src, range_out)
+        lead = tuple(src[0].shape[:-2])
+        if dst is None:
+            dst = _new_planes(f1, w, h, lead, _yuv_out_dtype(f1.depth, src[0].dtype), self.device)
+        if dst2 is None:
+            dst2 = _new_planes(f2, w, h, lead, _yuv_out_dtype(f2.depth, src[0].dtype), self.device)
+        s, d, nf = _plane_pair(src, dst, self.device)
+        d2, nf2 = _planes_struct(dst2, self.device)
+        if nf != nf2:
+            raise ValueError("src and dst2 disagree on the number of frames")
+        rows = h - row0 if rows is None else rows
+        with self._lock:
+            self._bind_stream()
+            _native.check(self._lib.lutr_apply_yuv_dual(
+                self._ctx, C.byref(p), f2.code, _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(d), C.byref(d2), row0, rows))
+        return dst, dst2
 
     def _apply_yuv_container(self, packed, src, dst, fin, fout, interp, matrix_in, matrix_out, range_src, range_in, range_out,
                              lut_depth, row0, rows, width):

@@ -28,8 +28,8 @@ import torch
 
 from . import _native
 from .cube import CubeLut, read_lut
-from .engine import (LutEngine, _new_planes, _yuv_out_dtype, check_container_options, packed_frame_width, parse_pix_fmt,
-                     parse_rgb_source, yuv_side)
+from .engine import (LutEngine, _new_planes, _yuv_out_dtype, check_container_options, dual_args, packed_frame_width, parse_pix_fmt,
+                     parse_rgb_source, refuse_dual_keywords, yuv_side)
 from .shard import row_blocks
 
 
@@ -187,6 +187,49 @@ class LutEngineGroup:
             for d, o, (a, b) in zip(dst, out, rng):
                 d[..., a:b, :].copy_(o, non_blocking=True)
         return dst[0] if bare else dst
+
+    def apply_yuv_dual(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None,
+                       dst2: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: Optional[str] = None,
+                       out2_pix_fmt: str, **kw):
+        """`LutEngine.apply_yuv_dual` with the rows of every frame split over the group's devices: shards on
+        multiples of the union block height of the three layouts, each side's chroma rows counted in its own layout, no halo."""
+        with self._lock:
+            if "row0" in kw or "rows" in kw:
+                raise ValueError("the group owns the row partition")
+            refuse_dual_keywords(kw)
+            fin, f1, f2, w, h = dual_args(src, dst, dst2, pix_fmt, out_pix_fmt, out2_pix_fmt)
+            home, lead = src[0].device, tuple(src[0].shape[:-2])
+            if dst is None:
+                dst = _new_planes(f1, w, h, lead, _yuv_out_dtype(f1.depth, src[0].dtype), home)
+            if dst2 is None:
+                dst2 = _new_planes(f2, w, h, lead, _yuv_out_dtype(f2.depth, src[0].dtype), home)
+            names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, out2_pix_fmt=out2_pix_fmt)
+            blocks = row_blocks(h, len(self.engines), align=1 << max(fin.csy, f1.csy, f2.csy))
+            self.last_blocks = blocks
+            self.last_remote = 0
+            pending = []
+
+            def rng_of(fmt, r0, r1):
+                c0, c1 = r0 >> fmt.csy, (r1 + (1 << fmt.csy) - 1) >> fmt.csy
+                return [(r0, r1), (c0, c1), (c0, c1)]
+
+            for k, (eng, (r0, r1)) in enumerate(zip(self.engines, blocks)):
+                if r1 <= r0:
+                    continue
+                if eng.device == home and not (self.treat_as_remote and k > 0):
+                    eng.apply_yuv_dual(src, dst, dst2, row0=r0, rows=r1 - r0, **names, **kw)
+                    continue
+                with torch.cuda.device(eng.device):
+                    part = [p[..., a:b, :].to(eng.device, non_blocking=True, copy=True).contiguous()
+                            for p, (a, b) in zip(src, rng_of(fin, r0, r1))]
+                    out, out2 = eng.apply_yuv_dual(part, None, None, **names, **kw)
+                self.last_remote += 1
+                pending.append((dst, out, rng_of(f1, r0, r1)))
+                pending.append((dst2, out2, rng_of(f2, r0, r1)))
+            for to, out, rng in pending:                           # copies back: queued after every launch was issued
+                for d, o, (a, b) in zip(to, out, rng):
+                    d[..., a:b, :].copy_(o, non_blocking=True)
+            return dst, dst2
 
     def apply_rgb_to_yuv(self, src, dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: str, **kw):
         """`LutEngine.apply_rgb_to_yuv` with the rows of every frame split over the group's devices: shards on

@@ -119,12 +119,27 @@ def input_layout(pix_fmt: str, width: int, height: int):
     return yuv_layout(pix_fmt, width, height)
 
 
+def dual_layout(pix_fmt: str, out_pix_fmt: Optional[str], second_pix_fmt: Optional[str], width: int, height: int, out_size=None,
+                apply_kw: Optional[dict] = None) -> Optional[FrameLayout]:
+    """The layout of `HostPipeline`'s second output ring, or None without `second_pix_fmt`.  Planar YUV on
+    every side, no dither, chroma_loc or out_size (ValueError, `engine.check_dual_options`)."""
+    if second_pix_fmt is None:
+        return None
+    from .engine import check_dual_options
+    kw = apply_kw or {}
+    _, _, f2 = check_dual_options(pix_fmt, out_pix_fmt, second_pix_fmt, kw.get("dither", "none"), kw.get("chroma_loc"), out_size)
+    return FrameLayout(f2, width, height)
+
+
 class HostPipeline:
     """Apply the LUT to batches of host frames with copies overlapped against compute."""
 
     def __init__(self, engine: LutEngine, pix_fmt: str, width: int, height: int, batch: int = 8, slots: int = 3,
-                 out_pix_fmt: Optional[str] = None, out_size=None, **apply_kw):
-        """`out_size` = (w, h) or "WxH": the engine resizes every frame to it and the output layout has that size."""
+                 out_pix_fmt: Optional[str] = None, out_size=None, second_pix_fmt: Optional[str] = None, **apply_kw):
+        """`out_size` = (w, h) or "WxH": the engine resizes every frame to it and the output layout has that size.
+        `second_pix_fmt`: a second planar YUV output from the same pass with a pinned output ring of its own
+        (`fout2`); `run` then takes a second drain."""
+        self.fout2 = dual_layout(pix_fmt, out_pix_fmt, second_pix_fmt, width, height, out_size, apply_kw)
         self.eng = engine
         self.fin = input_layout(pix_fmt, width, height)
         src_rgb = parse_rgb_source(pix_fmt)
@@ -152,6 +167,11 @@ class HostPipeline:
         self.h_out = [torch.empty(self.batch * self.fout.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]
         self.d_in = [torch.empty(self.batch * self.fin.frame_bytes, dtype=torch.uint8, device=dev) for _ in range(slots)]
         self.d_out = [torch.empty(self.batch * self.fout.frame_bytes, dtype=torch.uint8, device=dev) for _ in range(slots)]
+        if self.fout2 is not None:
+            self.kw = {k: v for k, v in self.kw.items() if k != "dither"}
+            self.kw["out2_pix_fmt"] = self.fout2.fmt.name
+            self.h_out2 = [torch.empty(self.batch * self.fout2.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]
+            self.d_out2 = [torch.empty(self.batch * self.fout2.frame_bytes, dtype=torch.uint8, device=dev) for _ in range(slots)]
         self.s_h2d, self.s_run, self.s_d2h = (torch.cuda.Stream(dev) for _ in range(3))
         self.e_in = [torch.cuda.Event() for _ in range(slots)]
         self.e_run = [torch.cuda.Event() for _ in range(slots)]
@@ -163,6 +183,9 @@ class HostPipeline:
     def host_out(self, slot: int) -> np.ndarray:
         return self.h_out[slot].numpy()
 
+    def host_out2(self, slot: int) -> np.ndarray:
+        return self.h_out2[slot].numpy()
+
     def _submit(self, slot: int, nframes: int) -> None:
         nb_in, nb_out = nframes * self.fin.frame_bytes, nframes * self.fout.frame_bytes
         with torch.cuda.stream(self.s_h2d):
@@ -171,7 +194,10 @@ class HostPipeline:
         with torch.cuda.stream(self.s_run):
             self.s_run.wait_event(self.e_in[slot])
             dst = self.fout.plane_views(self.d_out[slot], nframes)
-            if self.float_out:
+            if self.fout2 is not None:
+                self.eng.apply_yuv_dual(self.fin.plane_views(self.d_in[slot], nframes), dst,
+                                        self.fout2.plane_views(self.d_out2[slot], nframes), **self.kw)
+            elif self.float_out:
                 src = self.fin.plane_views(self.d_in[slot], nframes)[:self.fout.fmt.nplanes]
                 self.eng.apply_rgb_float(src, dst, interp=self.kw.get("interp", "tetrahedral"))
             elif self.rgb:                                   # launches on the current (s_run) stream
@@ -184,23 +210,37 @@ class HostPipeline:
         with torch.cuda.stream(self.s_d2h):
             self.s_d2h.wait_event(self.e_run[slot])
             self.h_out[slot][:nb_out].copy_(self.d_out[slot][:nb_out], non_blocking=True)
+            if self.fout2 is not None:
+                nb2 = nframes * self.fout2.frame_bytes
+                self.h_out2[slot][:nb2].copy_(self.d_out2[slot][:nb2], non_blocking=True)
             self.e_out[slot].record()
 
     def run(self, fill: Callable[[np.ndarray, int], int], drain: Callable[[np.ndarray, int], None],
-            total_frames: Optional[int] = None, stop: Optional[Callable[[], bool]] = None) -> int:
+            total_frames: Optional[int] = None, stop: Optional[Callable[[], bool]] = None,
+            drain2: Optional[Callable[[np.ndarray, int], None]] = None) -> int:
         """`fill(host_in_bytes, max_frames) -> frames written` (0 = end of stream) produces input,
-        `drain(host_out_bytes, nframes)` consumes output, both on the calling thread.  Returns the
-        number of frames processed."""
+        `drain(host_out_bytes, nframes)` consumes output, both on the calling thread.  With a second output
+        (`second_pix_fmt`), `drain2(host_out2_bytes, nframes)` consumes it, called right before `drain` for the same
+        batch: when neither drain raises, both have seen the same frames at every return (a stop included).  If `drain`
+        raises (a closed pipe, say), `drain2` has already taken that batch and is one batch ahead.
+        Returns the number of frames processed."""
+        if (drain2 is not None) != (self.fout2 is not None):
+            raise ValueError("drain2 goes with second_pix_fmt: give both or neither")
+
+        def retire(s, n):               # hand a finished batch over: the second output first, `drain` counts progress
+            self.e_out[s].synchronize()
+            if drain2 is not None:
+                drain2(self.host_out2(s)[: n * self.fout2.frame_bytes], n)
+            drain(self.host_out(s)[: n * self.fout.frame_bytes], n)
+            return n
+
         pending: List[tuple] = []       # (slot, nframes) in submission order
         done = 0
         i = 0
         while True:
             slot = i % self.slots
             if len(pending) == self.slots:                       # ring full: retire the oldest first
-                s, n = pending.pop(0)
-                self.e_out[s].synchronize()
-                drain(self.host_out(s)[: n * self.fout.frame_bytes], n)
-                done += n
+                done += retire(*pending.pop(0))
             if stop is not None and stop():
                 break
             want = self.batch if total_frames is None else min(self.batch, total_frames - done - sum(n for _, n in pending))
@@ -213,7 +253,5 @@ class HostPipeline:
             pending.append((slot, n))
             i += 1
         for s, n in pending:
-            self.e_out[s].synchronize()
-            drain(self.host_out(s)[: n * self.fout.frame_bytes], n)
-            done += n
+            done += retire(s, n)
         return done
