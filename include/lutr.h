@@ -460,6 +460,42 @@ int lutr_apply_yuv_packed(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, c
                           const lutr_yuv_packing *out, int w, int h, int nframes, const lutr_planes *src,
                           const lutr_planes *dst, int row0, int rows);
 
+/* ---- v210 frames: the 10-bit 4:2:2 container of SDI capture and play-out cards and of QuickTime / AVI files
+ *      with FourCC 'v210' -- the frame the reference's chain sees after FFmpeg's v210 decoder has unpacked it to yuv422p10le ---- */
+/* lutr_apply_yuv on frames whose source side (in_v210 = 1), destination side (out_v210 = 1) or both are v210; the other side is
+ * three planes as lutr_apply_yuv takes them.  Both flags 0 is LUTR_EINVAL (that is lutr_apply_yuv / lutr_apply_yuv_xsub).
+ * A v210 side uses data[0] / stride[0] / frame_stride[0] only (data[1], data[2] are ignored and may be NULL) and its format
+ * (fmt_in / fmt_out of *p) is LUTR_FMT(10, 1, 0).  A row is ceil(w / 6) groups of four little-endian 32-bit words; a word holds
+ * three 10-bit codes, slot a in bits 0-9, b in bits 10-19, c in bits 20-29:
+ *      word 0: Cb0 Y0 Cr0    word 1: Y1 Cb1 Y2    word 2: Cr1 Y3 Cb2    word 3: Y4 Cr2 Y5
+ * pair k (Cbk, Crk) belongs to luma samples 2k and 2k + 1 of the group.  The usual row stride is 128 * ceil(w / 48) bytes; any
+ * stride that is a multiple of 4 and at least 16 * ceil(w / 6) in magnitude is taken.
+ * Input: a code is its 10 bits whatever bits 30-31 hold; slots of samples beyond the frame (luma x >= w, pair k >= ceil(w / 2))
+ * are ignored.  Output: bits 30-31 are zero; a luma slot beyond the frame repeats the last real luma sample of the row, a pair
+ * beyond it the last real pair; bytes of a row past its last group are never written.  Odd w: chroma follows the edge rule of
+ * lutr_apply_yuv (the edge column counts twice in the block mean).
+ * With 4:2:2 on both sides the result is bit-identical to lutr_apply_yuv on the same codes held in yuv422p10le planes: everything
+ * *p expresses (depth change, the full-range prologue, matrices, ranges, lut_depth) and a .csp prelut are that call's arithmetic
+ * unchanged.  A v210 source may also go to a PLANAR 4:2:0 or 4:4:4 destination: bit-identical to lutr_apply_yuv_xsub on the
+ * unpacked source.  Row blocks follow the rule of those calls (row0 / rows multiples of the destination's chroma block height).
+ * src == dst (in place) is allowed when both sides are v210 with the same strides; any other overlap of the source's and the
+ * destination's byte ranges fails.  Always strict precision (fast / fma32 run strict here, no suffix on the last kernel).
+ * LUTR_EINVAL with a message, before anything touches the device: a flag outside 0 | 1, both flags 0, a v210 side whose format
+ * is not 10-bit 4:2:2, a v210 destination whose fmt_in is not 4:2:2, a v210 stride below 16 * ceil(w / 6) or not a multiple of
+ * 4, a v210 base that is not 4-byte aligned, a null pointer where a plane is needed, 16-bit planes whose base or stride is odd,
+ * overlap other than in place, row0 / rows off the chroma block.
+ * Kernels: "k_yuv_v210_vec<planar_wide,v210_in,v210_out,ocsy,interp>" (nearest / trilinear / tetrahedral; v210 -> v210, v210 ->
+ * planar 16 or 8 bit 4:2:2 / 4:2:0, planar 16 bit -> v210; 6, 12 (16-bit planes) or 24 (8-bit planes) luma samples per thread;
+ * v210 rows 16-byte aligned with positive strides, planar rows 4-byte aligned), "k_yuv_v210_generic" for everything else (one
+ * thread per group of six luma samples; any stride, planar depth 8..16 or alignment, any size; all five modes; the planar 4:4:4
+ * destination; an 8-bit planar source); a width that is not a whole number of units is split between the two.  Variants: auto
+ * and generic as for lutr_apply_yuv; vec_global fails with LUTR_EINVAL where the vector kernel cannot take the layout; vec_lds
+ * always fails with LUTR_EINVAL (there is no LDS kernel for this path).
+ * Not covered: a semi-planar or packed 4:2:2 side, a subsampling change into v210, chroma siting, dither, resize, the two-output
+ * pass, an RGB source, v210x / v410 / r210, big-endian variants. */
+int lutr_apply_yuv_v210(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int in_v210, int out_v210, int w, int h,
+                        int nframes, const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
+
 /* ---- two outputs from one pass (the reference's "pro" mode, ffmpeg.py:417-472: a ProRes 422 HQ master with the
  *      LUT in yuv422p10le, then the delivery file in the user's pix_fmt -- both from the same lut3d result) ---- */
 /* lutr_apply_yuv_xsub with a second destination: planar YUV in, TWO planar YUV frames out.  fmt_out2 (a LUTR_FMT code) may differ

@@ -41,7 +41,7 @@ SYMBOLS = (
     "lutr_apply_yuv_sited", "lutr_yuv_constants_sited", "lutr_apply_yuv_xsub", "lutr_yuv_constants_xsub",
     "lutr_apply_rgb_to_yuv", "lutr_yuv_constants_rgb2yuv",
     "lutr_apply_planar_rgb_f32", "lutr_apply_rgbf_to_yuv", "lutr_apply_yuv_semi", "lutr_apply_yuv_packed",
-    "lutr_apply_yuv_dual",
+    "lutr_apply_yuv_dual", "lutr_apply_yuv_v210",
     "lutr_resize_filter", "lutr_resize_planes",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
 )
@@ -107,6 +107,10 @@ PACKED_YUV_FORMATS = {
     "yuyv422": (8, 0, 0), "uyvy422": (8, 1, 0), "yvyu422": (8, 2, 0),
     "y210le": (10, 0, 6), "y212le": (12, 0, 4), "y216le": (16, 0, 0),
 }
+
+
+#: v210: 10-bit 4:2:2, three codes per 32-bit word, six luma samples per group of four words -> (depth,)
+V210_FORMATS = {"v210": (10,)}
 
 
 #: planar float RGB sources -> planes per frame (G, B, R[, A])
@@ -179,6 +183,7 @@ def load() -> C.CDLL:
                                         C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_apply_yuv_packed.argtypes = [vp, C.POINTER(YuvParams), ci, C.POINTER(YuvPacking), C.POINTER(YuvPacking), ci, ci, ci,
                                           C.POINTER(Planes), C.POINTER(Planes), ci, ci]
+    lib.lutr_apply_yuv_v210.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_apply_yuv_dual.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes),
                                         C.POINTER(Planes), ci, ci]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]

@@ -119,9 +119,10 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
         return kw
     # a semi-planar source or output (nv12, p010le, ..) is the same chain on another container
     # (so is a packed 4:2:2 one: uyvy422, y210le, ..)
-    from .engine import check_container_options, parse_packed_yuv_fmt, parse_semi_fmt
-    check_container_options(pix_fmt, out_pix_fmt, kinds=("packed",))     # names the packings this path does not take
-    semi_src = parse_semi_fmt(pix_fmt) or parse_packed_yuv_fmt(pix_fmt)
+    # (and v210)
+    from .engine import check_container_options, parse_packed_yuv_fmt, parse_semi_fmt, parse_v210_fmt
+    check_container_options(pix_fmt, out_pix_fmt, kinds=("v210", "packed"))     # names the packings this path does not take
+    semi_src = parse_semi_fmt(pix_fmt) or parse_packed_yuv_fmt(pix_fmt) or parse_v210_fmt(pix_fmt)
     src = semi_src or parse_pix_fmt(pix_fmt)
     if src.family != "yuv":
         raise ValueError("apply_lut takes planar YUV frames; use LutEngine.apply_rgb for gbrp planes")
@@ -179,7 +180,9 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
     chroma_loc or resolution.  A packed 4:2:2 `pix_fmt` / `out_pix_fmt` (yuyv422, uyvy422, yvyu422, y210le, y212le, y216le;
     DESIGN.md 3.12) makes that side ONE tensor [..., h, 4 * ceil(w / 2)], bare or in a one-element list (`width` names an odd
-    width); on the same terms, and a packed source may go to planar 4:2:0 / 4:4:4.  With an RGB `pix_fmt` (gbrp* or a packed name such as rgb24) and a YUV
+    width); on the same terms, and a packed source may go to planar 4:2:0 / 4:4:4.  `pix_fmt` / `out_pix_fmt` = "v210" (DESIGN.md
+    3.14) makes that side ONE int32 tensor [..., h, 32 * ceil(w / 48)] of 32-bit words, on the terms of a packed side; `width` is
+    required when no planar side tells it, and `out_pix_fmt` defaults to v210.  With an RGB `pix_fmt` (gbrp* or a packed name such as rgb24) and a YUV
     `out_pix_fmt` (required then), `planes` is the three gbrp planes (G, B, R) or the one [F,]H,W,C packed tensor and the
     chain is lut3d on the RGB frame, then RGB -> YUV.  `pix_fmt` = gbrpf32le / gbrapf32le takes float32 planes
     (DESIGN.md 3.10): with a YUV `out_pix_fmt` the same chain, without one (or with a float one) float planes come back, an alpha
@@ -227,14 +230,19 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         if isinstance(engine, LutEngineGroup) or (engine is None and len(devices) > 1):
             raise ValueError("resolution needs a single device")
     from .engine import (check_chroma_loc, check_container_options, packed_frame_width, parse_packed_yuv_fmt, parse_rgb_source,
-                         source_bit_depth)
+                         parse_v210_fmt, source_bit_depth, v210_frame_width, yuv_side)
     rgb_src = parse_rgb_source(pix_fmt)
     if rgb_src is not None and rgb_src.packed:
         got_w, got_h = planes.shape[-2], planes.shape[-3]
     else:
         first = planes if hasattr(planes, "shape") else planes[0]
         pk_src = parse_packed_yuv_fmt(pix_fmt)
-        got_w = packed_frame_width(pk_src, planes, width) if pk_src is not None else first.shape[-1]
+        if parse_v210_fmt(pix_fmt) is not None:                # (padded rows: `width`, or the planes of a planar `out`, tell it)
+            fout = None if out_pix_fmt is None or parse_rgb_source(out_pix_fmt) is not None else yuv_side(out_pix_fmt)
+            got_w = v210_frame_width(parse_v210_fmt(pix_fmt), fout if fout is not None else parse_v210_fmt(pix_fmt), planes,
+                                     out if fout is not None and not hasattr(out, "shape") else None, width)
+        else:
+            got_w = packed_frame_width(pk_src, planes, width) if pk_src is not None else first.shape[-1]
         got_h = first.shape[-2]
     if width is not None and got_w != width or height is not None and got_h != height:
         raise ValueError("plane shape does not match width/height")
@@ -259,7 +267,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
             raise ValueError("chroma siting (chroma_loc) is not defined for an RGB source")
     else:
         kind = check_container_options(kw["pix_fmt"], kw["out_pix_fmt"], kw["dither"], chroma_loc, out_size)
-        if kind == "packed":
+        if kind in ("packed", "v210"):
             kw["width"] = got_w
         elif kind is None:
             check_chroma_loc(chroma_loc, kw["dither"], kw["pix_fmt"], kw["out_pix_fmt"])

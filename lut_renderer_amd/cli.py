@@ -43,7 +43,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("-o", "--output", required=True)
     ap.add_argument("--size", required=True, help="WxH")
     ap.add_argument("--pix-fmt", required=True,
-                    help="planar YUV, semi-planar YUV (nv12, nv21, nv16, p010le .. p216le), packed 4:2:2 YUV (yuyv422, uyvy422, yvyu422, y210le, y212le, y216le), or an RGB source (gbrp* / rgb24, bgr24, rgba .., rgb48le, rgba64le) with a YUV --out-pix-fmt, "
+                    help="planar YUV, semi-planar YUV (nv12, nv21, nv16, p010le .. p216le), packed 4:2:2 YUV (yuyv422, uyvy422, yvyu422, y210le, y212le, y216le), v210 (10-bit 4:2:2 in 32-bit words, rows of 128 * ceil(w / 48) bytes; in FFmpeg a codec / FourCC name, not a pix_fmt: its bytes are what `-c:v v210 -f rawvideo` writes), or an RGB source (gbrp* / rgb24, bgr24, rgba .., rgb48le, rgba64le) with a YUV --out-pix-fmt, "
                          "or float RGB (gbrpf32le / gbrapf32le): float out without --out-pix-fmt, else a YUV one")
     ap.add_argument("--out-pix-fmt", default=None)
     ap.add_argument("--cube", required=True)

@@ -1365,6 +1365,96 @@ int lutr_apply_yuv_packed(lutr_ctx *c, const lutr_yuv_params *p, int interp, con
                                               LUTR_FMT_DEPTH(p->fmt_out), ocsx, ocsy, interp));
 }
 
+// bytes of a v210 row that hold groups: 16 for every six luma samples, the last group whole
+static long long v210_row_bytes(int w) { return 16ll * ((w + 5) / 6); }
+
+// one side of lutr_apply_yuv_v210: a v210 side's format, plane, alignment and stride; a planar side's three planes
+static int check_v210_side(const char *side, int v210, int fmt, const lutr_planes *pl, int w, int nframes)
+{
+    if (!v210) {
+        for (int i = 0; i < 3; i++) {
+            if (!pl->data[i]) { set_error("null %s plane %d", side, i); return LUTR_EINVAL; }
+            if (LUTR_FMT_DEPTH(fmt) > 8 && !check_aligned(pl->data[i], pl->stride[i], pl->frame_stride[i], nframes, 1)) {
+                set_error("%s plane %d: 16-bit containers need 2-byte aligned rows", side, i);
+                return LUTR_EINVAL;
+            }
+        }
+        return LUTR_OK;
+    }
+    if (fmt != LUTR_FMT(10, 1, 0)) { set_error("%s: a v210 frame is 10-bit 4:2:2 (format 0x%x)", side, fmt); return LUTR_EINVAL; }
+    if (!pl->data[0]) { set_error("null %s plane 0", side); return LUTR_EINVAL; }
+    if (!check_aligned(pl->data[0], pl->stride[0], pl->frame_stride[0], nframes, 3)) {
+        set_error("%s: v210 rows are 32-bit words: base, stride and frame stride must be 4-byte aligned", side);
+        return LUTR_EINVAL;
+    }
+    const long long st = pl->stride[0] < 0 ? -(long long)pl->stride[0] : (long long)pl->stride[0];
+    if (st < v210_row_bytes(w)) {
+        set_error("%s: a v210 row of %d samples takes %lld bytes, the stride is %lld", side, w, v210_row_bytes(w), (long long)pl->stride[0]);
+        return LUTR_EINVAL;
+    }
+    return LUTR_OK;
+}
+
+// the byte ranges of one side of lutr_apply_yuv_v210 over all rows and frames; returns their number
+static int v210_side_spans(int v210, int fmt, const lutr_planes *pl, int w, int h, int nframes, Span *out)
+{
+    if (v210) {
+        out[0] = plane_span(pl->data[0], pl->stride[0], pl->frame_stride[0], h, v210_row_bytes(w), nframes);
+        return 1;
+    }
+    planar_spans(pl, LUTR_FMT_CSX(fmt), LUTR_FMT_CSY(fmt), w, h, LUTR_FMT_DEPTH(fmt) > 8 ? 2 : 1, nframes, out);
+    return 3;
+}
+
+int lutr_apply_yuv_v210(lutr_ctx *c, const lutr_yuv_params *p, int interp, int in_v210, int out_v210, int w, int h, int nframes,
+                        const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+{
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    if ((in_v210 != 0 && in_v210 != 1) || (out_v210 != 0 && out_v210 != 1)) {
+        set_error("in_v210 and out_v210 are 0 or 1 (got %d, %d)", in_v210, out_v210);
+        return LUTR_EINVAL;
+    }
+    if (!in_v210 && !out_v210) {
+        set_error("neither side is v210: planar frames on both sides are lutr_apply_yuv / lutr_apply_yuv_xsub");
+        return LUTR_EINVAL;
+    }
+    // (the container's own refusals first: they name the side; then the constants, which check depths, matrices and ranges)
+    if (const int rc = check_v210_side("source", in_v210, p->fmt_in, src, w, nframes)) return rc;
+    if (!(LUTR_FMT_CSX(p->fmt_in) == 1 && LUTR_FMT_CSY(p->fmt_in) == 0)) {
+        set_error("a v210 destination takes a 4:2:2 source (no subsampling change into a v210 frame)");
+        return LUTR_EINVAL;
+    }
+    if (const int rc = check_v210_side("destination", out_v210, p->fmt_out, dst, w, nframes)) return rc;
+    YuvConsts K;
+    rc = make_yuv_consts_xsub(*p, &K);           // (one layout on both sides: lutr_apply_yuv's own constants)
+    if (rc) return rc;
+    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
+    if (!((ocsx == 1 && ocsy <= 1) || (ocsx == 0 && ocsy == 0))) { set_error("the destination is 4:2:2, 4:2:0 or 4:4:4"); return LUTR_EINVAL; }
+    if (const int rc = check_row_blocks(row0, rows, h, 1 << ocsy, "chroma block height")) return rc;
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    // in place: v210 on both sides, the same bytes.  Anything else must not overlap at all
+    const bool in_place = in_v210 && out_v210 && src->data[0] == dst->data[0] && src->stride[0] == dst->stride[0] &&
+                          (nframes <= 1 || src->frame_stride[0] == dst->frame_stride[0]);
+    if (!in_place) {
+        Span ss[3], ds[3];
+        const int ns = v210_side_spans(in_v210, p->fmt_in, src, w, h, nframes, ss);
+        const int nd = v210_side_spans(out_v210, p->fmt_out, dst, w, h, nframes, ds);
+        if (const int rc = check_disjoint("a v210 call between different buffers or containers", true, ss, ns, ds, nd)) return rc;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
+    LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
+    fill_planes(&P, src, dst);
+    if (in_v210) clear_planes(&P, true, 1);
+    if (out_v210) clear_planes(&P, false, 1);
+    const V210Args A{in_v210, out_v210};
+    return finish_launch(c, launch_yuv_v210(c->stream, c->variant, L, K, P, G, A, LUTR_FMT_DEPTH(p->fmt_in),
+                                            LUTR_FMT_DEPTH(p->fmt_out), ocsx, ocsy, interp));
+}
+
 int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dither, int src_kind, int w, int h, int nframes,
                           const lutr_planes *src_planar, const lutr_packed *src_packed, const lutr_planes *dst, int row0, int rows)
 {

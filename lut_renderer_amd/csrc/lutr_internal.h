@@ -181,6 +181,25 @@ const char *launch_yuv_packed(hipStream_t st, int variant, const LutConsts &L, c
 LUTR_PK_DECL(w00) LUTR_PK_DECL(w11) LUTR_PK_DECL(w10)
 #undef LUTR_PK_DECL
 
+// v210 frames (lutr_v210.hip): the container of each side -- planar (three planes) or v210 (PlaneSet slot 0 holds the
+// groups of four words, slots 1 and 2 are not read).  A v210 side is 10-bit 4:2:2; the source is 4:2:2; the destination is 4:2:2,
+// or planar with the layout ocsx, ocsy (K then carries the output block's 1/n).  din / dout: the depths of the two sides (10 for a
+// v210 one).  nullptr = the variant cannot take the call (vec_lds always; vec_global on layouts the vector kernel cannot take)
+struct V210Args {
+    int iv, ov;
+};
+// luma samples a thread of the vector kernels takes per row: whole groups that make whole words on the planar side (wp: it is 16 bit)
+inline int v210_unit_px(const V210Args &A, int wp) { return (A.iv && A.ov) ? 6 : (wp ? 12 : 24); }
+const char *launch_yuv_v210(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
+                            const FrameGeom &G, const V210Args &A, int din, int dout, int ocsx, int ocsy, int interp);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>, a v210 side counted as wide): nullptr = not a
+// side pair / mode it has
+#define LUTR_V2_DECL(tag) \
+    const char *launch_yuv_v210_vec_##tag(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, \
+                                          const FrameGeom &G, const V210Args &A, int ocsy, int interp);
+LUTR_V2_DECL(w11) LUTR_V2_DECL(w10)
+#undef LUTR_V2_DECL
+
 // pass 2 of the dither path alone (k_dither_ed on the float planes F, chroma planes in the output layout); false = rows too wide
 bool launch_dither_ed(hipStream_t st, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const FloatPlanes &F, int wout,
                       int ocsx, int ocsy);

@@ -116,6 +116,39 @@ class PackedYuvFmt(_YuvContainer):
         return h, 4 * ((w + 1) >> 1)
 
 
+@dataclass(frozen=True)
+class V210Fmt(_YuvContainer):
+    """v210: one buffer of 32-bit words, rows of ceil(w / 6) groups of four words, three 10-bit codes a word."""
+    name: str
+    depth: int
+
+    nplanes = 1
+    csx, csy = 1, 0
+    itemsize = 4      # the buffer's elements are the words (torch.int32)
+
+    @staticmethod
+    def groups(w: int) -> int:
+        """Groups of six luma samples in a row."""
+        return (w + 5) // 6
+
+    @staticmethod
+    def row_bytes(w: int) -> int:
+        """The default row stride: rows are padded to whole blocks of 128 bytes (48 luma samples)."""
+        return 128 * ((w + 47) // 48)
+
+    def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
+        """The one buffer at the default stride: (h, 32 * ceil(w / 48)) words."""
+        return h, self.row_bytes(w) // 4
+
+
+def parse_v210_fmt(name: Optional[str]) -> Optional[V210Fmt]:
+    """The `V210Fmt` of a name of `_native.V210_FORMATS` ("v210"), or None for any other name -- `parse_pix_fmt` rejects the name
+    and `parse_semi_fmt` / `parse_packed_yuv_fmt` return None for it."""
+    if name not in _native.V210_FORMATS:
+        return None
+    return V210Fmt(name, *_native.V210_FORMATS[name])
+
+
 def parse_packed_yuv_fmt(name: Optional[str]) -> Optional[PackedYuvFmt]:
     """The packed 4:2:2 format `name` stands for (a name of `_native.PACKED_YUV_FORMATS`), or None for any other name --
     `parse_pix_fmt` keeps rejecting these and `parse_semi_fmt` keeps returning None for them."""
@@ -133,8 +166,10 @@ def parse_semi_fmt(name: Optional[str]) -> Optional[SemiFmt]:
 
 
 def yuv_side(name: str):
-    """One side of `apply_yuv`: the `SemiFmt`, `PackedYuvFmt` or planar `PixFmt` of a YUV format name (yuvj* read as yuv*)."""
-    return parse_semi_fmt(name) or parse_packed_yuv_fmt(name) or parse_pix_fmt((name or "").replace("yuvj", "yuv"))
+    """One side of `apply_yuv`: the `SemiFmt`, `PackedYuvFmt`, `V210Fmt` or planar `PixFmt` of a YUV format name (yuvj* read as
+    yuv*)."""
+    return parse_semi_fmt(name) or parse_packed_yuv_fmt(name) or parse_v210_fmt(name) or \
+        parse_pix_fmt((name or "").replace("yuvj", "yuv"))
 
 
 #: packed YUV names FFmpeg has that this path does not take: 4:4:4 packings and big-endian containers
@@ -143,49 +178,62 @@ _PACKED_YUV_UNSUPPORTED = ("vuyx", "vuya", "ayuv", "uyva", "xv30le", "xv36le", "
 
 
 #: container kind -> (its parser, what the RGB refusal calls it, what every other refusal calls it)
-_CONTAINER_KINDS = {"packed": (parse_packed_yuv_fmt, "packed", "packed 4:2:2"),
+_CONTAINER_KINDS = {"v210": (parse_v210_fmt, "v210", "v210"),
+                    "packed": (parse_packed_yuv_fmt, "packed", "packed 4:2:2"),
                     "semi": (parse_semi_fmt, "semi-planar", "semi-planar")}
+
+#: v210's relatives FFmpeg knows as codecs, which this path does not take
+_V210_UNSUPPORTED = ("v210x", "v410", "v308", "v408", "r210", "r10k")
 
 
 def source_bit_depth(name: Optional[str]) -> Optional[int]:
     """`params.infer_bit_depth` for a source name that may be a container: p010le and y210le say their depth themselves (the
     digits are not a depth after a 'p')."""
     from .params import infer_bit_depth
-    side = parse_semi_fmt(name) or parse_packed_yuv_fmt(name)
+    side = parse_semi_fmt(name) or parse_packed_yuv_fmt(name) or parse_v210_fmt(name)
     return side.depth if side else infer_bit_depth(name)
 
 
 def check_container_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
-                            out_size=None, kinds=("packed", "semi"), width: Optional[int] = None) -> Optional[str]:
-    """The checks `apply_yuv` makes before any GPU work when a side is not three planes: "packed" when a side is packed 4:2:2
-    (DESIGN.md 3.12), "semi" when one is semi-planar, None when both are planar (nothing checked but the
-    packed names this path does not take).  Refused: an RGB side, a packed side together with a semi-planar one, a
-    subsampling change (packed: only a source that is not 4:2:2), chroma_loc, error-diffusion dither, out_size, and a `width`
-    (`apply_yuv`'s, for odd packed rows) when no side is packed."""
+                            out_size=None, kinds=("v210", "packed", "semi"), width: Optional[int] = None) -> Optional[str]:
+    """The checks `apply_yuv` makes before any GPU work when a side is not three planes: "v210" when a side is v210 (DESIGN.md
+    3.14), "packed" when a side is packed 4:2:2, "semi" when one is semi-planar, None when both
+    are planar (nothing checked but the packed names this path does not take).  Refused: an RGB side, two kinds of container in
+    one call, a subsampling change (packed and v210: only a source that is not 4:2:2), chroma_loc, error-diffusion dither,
+    out_size, and a `width` (`apply_yuv`'s, for rows that cannot tell it) when no side is packed or v210."""
     out_name = out_pix_fmt or pix_fmt
     for kind in kinds:
         parse, short, noun = _CONTAINER_KINDS[kind]
-        packed = kind == "packed"
-        if not packed and width is not None:
+        packed, v210 = kind == "packed", kind == "v210"
+        if kind == "semi" and width is not None:
             raise ValueError("width is for a packed 4:2:2 side; planar and semi-planar frames tell their own")
         for name in (pix_fmt, out_name) if packed else ():
             if name in _PACKED_YUV_UNSUPPORTED:
                 raise ValueError(f"'{name}' is not supported: packed YUV frames are taken as little-endian 4:2:2 "
                                  f"({', '.join(_native.PACKED_YUV_FORMATS)})")
+        for name in (pix_fmt, out_name) if v210 else ():
+            if name in _V210_UNSUPPORTED:
+                raise ValueError(f"'{name}' is not supported: of this family only v210 is taken")
         if parse(pix_fmt) is None and parse(out_name) is None:
             continue
         if parse_rgb_source(pix_fmt) is not None:
             raise ValueError(f"an RGB source ('{pix_fmt}') takes a planar YUV out_pix_fmt, not the {short} '{out_pix_fmt}'")
+        if v210:
+            if parse_rgb_source(out_name) is not None:
+                raise ValueError(f"v210 frames go with YUV formats on both sides ('{pix_fmt}' -> '{out_name}')")
+            for other, what in ((parse_semi_fmt, "semi-planar"), (parse_packed_yuv_fmt, "packed 4:2:2")):
+                if other(pix_fmt) is not None or other(out_name) is not None:
+                    raise ValueError(f"a {what} side together with a v210 side is not supported ('{pix_fmt}' -> '{out_name}')")
         if packed and (parse_semi_fmt(pix_fmt) is not None or parse_semi_fmt(out_name) is not None):
             raise ValueError(f"a semi-planar side together with a packed side is not supported ('{pix_fmt}' -> '{out_name}')")
         a, b = yuv_side(pix_fmt), yuv_side(out_name)
         if a.family != "yuv" or b.family != "yuv":
             raise ValueError(f"{noun} frames go with YUV formats on both sides "
-                             f"('{pix_fmt}' -> '{out_name if packed else out_pix_fmt}')")
-        if packed and (a.csx, a.csy) != (1, 0):
-            raise ValueError(f"a packed destination takes a 4:2:2 source: no chroma subsampling change into '{out_name}' "
+                             f"('{pix_fmt}' -> '{out_name if packed or v210 else out_pix_fmt}')")
+        if (packed or v210) and (a.csx, a.csy) != (1, 0):
+            raise ValueError(f"a {short} destination takes a 4:2:2 source: no chroma subsampling change into '{out_name}' "
                              f"('{pix_fmt}' -> '{out_name}')")
-        if not packed and (a.csx, a.csy) != (b.csx, b.csy):
+        if kind == "semi" and (a.csx, a.csy) != (b.csx, b.csy):
             raise ValueError(f"a chroma subsampling change is not supported with a semi-planar side "
                              f"('{pix_fmt}' -> '{out_pix_fmt}')")
         if chroma_loc is not None:
@@ -225,6 +273,24 @@ def packed_frame_width(fmt, planes, width: Optional[int] = None) -> int:
             raise ValueError(f"width {w} does not match '{fmt.name}' rows of {first.shape[-1]} samples")
     if width is not None and int(width) != w:
         raise ValueError(f"width {width} does not match the planes ({w})")
+    return w
+
+
+def v210_frame_width(fin, fout, src, dst, width: Optional[int] = None) -> int:
+    """The frame width of a call with a v210 side: a planar side tells it (the source's planes, else the destination's when
+    given); v210 rows are padded, so with none `width` is required.  Either way the v210 rows must hold it."""
+    told = None
+    if fin.nplanes == 3:
+        told = src[0].shape[-1]
+    elif fout.nplanes == 3 and dst is not None:
+        told = dst[0].shape[-1]
+    if told is None and width is None:
+        raise ValueError("width is required with v210 frames when no planar side tells it: v210 rows are padded")
+    if told is not None and width is not None and int(width) != told:
+        raise ValueError(f"width {width} does not match the planes ({told})")
+    w = told if told is not None else int(width)
+    if w < 1:
+        raise ValueError(f"bad width {w}")
     return w
 
 
@@ -323,6 +389,8 @@ def dual_side(name: Optional[str], what: str) -> PixFmt:
         raise ValueError(f"the two-output pass needs {what}")
     if parse_semi_fmt(name) is not None or parse_packed_yuv_fmt(name) is not None or name in _PACKED_YUV_UNSUPPORTED:
         raise ValueError(f"the two-output pass takes planar YUV on every side: {what} '{name}' is a semi-planar or packed container")
+    if parse_v210_fmt(name) is not None:
+        raise ValueError(f"the two-output pass takes planar YUV on every side: {what} '{name}' is a v210 container")
     if parse_rgb_source(name) is not None:
         raise ValueError(f"the two-output pass takes planar YUV on every side: {what} '{name}' is an RGB format")
     fmt = parse_pix_fmt(name.replace("yuvj", "yuv"))
@@ -436,7 +504,7 @@ def _check_planes(planes: Sequence[torch.Tensor], fmt: PixFmt, w: int, h: int, w
             raise ValueError(f"'{fmt.name}' takes one buffer of packed groups")
     elif len(planes) != 3:
         raise ValueError("expected three planes")
-    esize = 1 if fmt.depth <= 8 else 2
+    esize = getattr(fmt, "itemsize", 1 if fmt.depth <= 8 else 2)
     for i, t in enumerate(planes):
         if not isinstance(t, torch.Tensor):
             raise TypeError("planes must be torch tensors resident on the engine's GPU")
@@ -445,7 +513,11 @@ def _check_planes(planes: Sequence[torch.Tensor], fmt: PixFmt, w: int, h: int, w
         if t.is_floating_point() or t.element_size() != esize:
             raise ValueError(f"{what} plane {i}: '{fmt.name}' takes {8 * esize}-bit integer samples, got {t.dtype}")
         want = fmt.plane_shape(i, w, h)
-        if tuple(t.shape[-2:]) != want:
+        if isinstance(fmt, V210Fmt):                           # any row that holds the groups (FFmpeg's custom_stride)
+            if t.shape[-2] != h or t.shape[-1] < 4 * fmt.groups(w):
+                raise ValueError(f"{what} plane {i} is {tuple(t.shape[-2:])}, '{fmt.name}' at {w}x{h} needs {want} words "
+                                 f"(at least {4 * fmt.groups(w)} a row)")
+        elif tuple(t.shape[-2:]) != want:
             raise ValueError(f"{what} plane {i} is {tuple(t.shape[-2:])}, '{fmt.name}' at {w}x{h} needs {want}")
 
 
@@ -849,6 +921,9 @@ class LutEngine:
         if dither not in _native.DITHER:
             raise ValueError(f"unknown dither mode '{dither}'")
         kind = check_container_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size, width=width)
+        if kind == "v210":
+            return self._apply_yuv_v210(src, dst, yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt), interp, matrix_in, matrix_out,
+                                        range_src, range_in, range_out, lut_depth, row0, rows, width)
         if kind is not None:
             return self._apply_yuv_container(kind == "packed", src, dst, yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt),
                                              interp, matrix_in, matrix_out, range_src, range_in, range_out, lut_depth, row0, rows,
@@ -957,6 +1032,39 @@ class LutEngine:
             self._bind_stream()
             _native.check(entry(self._ctx, C.byref(p), _native.INTERP[interp], C.byref(sides[0]), C.byref(sides[1]), w, h, nf,
                                 C.byref(s), C.byref(d), row0, rows))
+        return dst[0] if bare else dst
+
+    def _apply_yuv_v210(self, src, dst, fin, fout, interp, matrix_in, matrix_out, range_src, range_in, range_out, lut_depth, row0,
+                        rows, width):
+        """apply_yuv with a v210 side (lutr_apply_yuv_v210): that side is ONE int32 tensor [..., h, words] (bare
+        or in a one-element list), 32 * ceil(w / 48) words a row by default; the options were checked by
+        `check_container_options`."""
+        p = _yuv_params(fin.code, fout.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
+                        range_src, range_in or range_src, range_out)
+        vi, vo = isinstance(fin, V210Fmt), isinstance(fout, V210Fmt)
+        bare = vo and isinstance(dst, torch.Tensor)
+        if vi and isinstance(src, torch.Tensor):
+            src = [src]
+        if bare:
+            dst = [dst]
+        if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
+            raise ValueError(f"'{fin.name}' takes {fin.nplanes} plane{'s' if fin.nplanes > 1 else ''}")
+        w, h = v210_frame_width(fin, fout, src, dst, width), src[0].shape[-2]
+        if dst is None:
+            # (a fresh v210 buffer is zeroed: the kernels never write the padding of a row)
+            dst = [torch.zeros(tuple(src[0].shape[:-2]) + fout.plane_shape(0, w, h), dtype=torch.int32, device=self.device)] if vo \
+                else _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), self.device)
+        _check_planes(src, fin, w, h, "source")
+        _check_planes(dst, fout, w, h, "destination")
+        s, nf = _planes_struct(src, self.device, fin.nplanes)
+        d, nfd = _planes_struct(dst, self.device, fout.nplanes)
+        if nf != nfd:
+            raise ValueError("src and dst disagree on the number of frames")
+        rows = h - row0 if rows is None else rows
+        with self._lock:
+            self._bind_stream()
+            _native.check(self._lib.lutr_apply_yuv_v210(self._ctx, C.byref(p), _native.INTERP[interp], int(vi), int(vo), w, h, nf,
+                                                        C.byref(s), C.byref(d), row0, rows))
         return dst[0] if bare else dst
 
     # -- RGB source, YUV output (DESIGN.md 3.9) --------------------------------

@@ -29,7 +29,7 @@ import torch
 from . import _native
 from .cube import CubeLut, read_lut
 from .engine import (LutEngine, _new_planes, _yuv_out_dtype, check_container_options, dual_args, packed_frame_width, parse_pix_fmt,
-                     parse_rgb_source, refuse_dual_keywords, yuv_side)
+                     parse_rgb_source, refuse_dual_keywords, v210_frame_width, yuv_side)
 from .shard import row_blocks
 
 
@@ -136,14 +136,22 @@ class LutEngineGroup:
             fin, fout = parse_pix_fmt(pix_fmt), parse_pix_fmt(out_pix_fmt or pix_fmt)
         else:
             fin, fout = yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt)
-        bare = kind == "packed" and isinstance(dst, torch.Tensor)
-        if kind == "packed":
+        # (v210, 3.14, shards like a packed side; its words are int32 and its width is named or told by the planar side)
+        bare = kind in ("packed", "v210") and isinstance(dst, torch.Tensor)
+        if kind in ("packed", "v210"):
             src = [src] if isinstance(src, torch.Tensor) else src
             dst = [dst] if bare else dst
-        h, w = src[0].shape[-2], packed_frame_width(fin, src, kw.get("width"))
+        if kind == "v210":
+            h, w = src[0].shape[-2], v210_frame_width(fin, fout, src, dst, kw.get("width"))
+            kw = dict(kw, width=w)
+        else:
+            h, w = src[0].shape[-2], packed_frame_width(fin, src, kw.get("width"))
         home = src[0].device
         if dst is None:
-            dst = _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), home)
+            # (a fresh v210 buffer is zeroed: the kernels never write the padding of a row)
+            dst = [torch.zeros(tuple(src[0].shape[:-2]) + fout.plane_shape(0, w, h), dtype=torch.int32, device=home)] \
+                if kind == "v210" and fout.nplanes == 1 else \
+                _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), home)
         bh = 1 << max(fin.csy, fout.csy)                           # the union block: whole chroma rows on both sides
         blocks = row_blocks(h, len(self.engines), align=bh)
         self.last_blocks = blocks

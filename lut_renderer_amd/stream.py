@@ -24,14 +24,15 @@ from .engine import LutEngine, RgbSource, parse_rgb_source, parse_size, yuv_side
 @dataclass
 class FrameLayout:
     """Byte layout of one YUV (or gbrp) frame in a rawvideo stream: the planes of `fmt` back to back -- three for a planar
-    format, luma then the chroma pairs for a semi-planar one, the one buffer of a packed 4:2:2 one (3.12)."""
-    fmt: object      # PixFmt | SemiFmt | PackedYuvFmt
+    format, luma then the chroma pairs for a semi-planar one, the one buffer of a packed 4:2:2 one (3.12) or of
+    v210 (3.14: 32-bit words, rows of 128 * ceil(w / 48) bytes)."""
+    fmt: object      # PixFmt | SemiFmt | PackedYuvFmt | V210Fmt
     width: int
     height: int
 
     @property
     def itemsize(self) -> int:
-        return 1 if self.fmt.depth <= 8 else 2
+        return getattr(self.fmt, "itemsize", 1 if self.fmt.depth <= 8 else 2)
 
     @property
     def plane_shapes(self) -> List[tuple]:
@@ -47,7 +48,7 @@ class FrameLayout:
 
     def plane_views(self, buf: torch.Tensor, nframes: int) -> List[torch.Tensor]:
         """[F,H,W] views of the planes inside a flat uint8 buffer of `nframes` frames."""
-        dt = torch.uint8 if self.itemsize == 1 else torch.int16
+        dt = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[self.itemsize]
         typed = buf.view(dt)
         fe = self.frame_bytes // self.itemsize
         out, off = [], 0
@@ -58,7 +59,7 @@ class FrameLayout:
 
 
 def yuv_layout(pix_fmt: str, width: int, height: int) -> FrameLayout:
-    """The `FrameLayout` of a planar, semi-planar or packed 4:2:2 YUV name (or gbrp)."""
+    """The `FrameLayout` of a planar, semi-planar, packed 4:2:2 or v210 YUV name (or gbrp)."""
     return FrameLayout(yuv_side(pix_fmt), width, height)
 
 
@@ -166,7 +167,8 @@ class HostPipeline:
         self.h_in = [torch.empty(self.batch * self.fin.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]
         self.h_out = [torch.empty(self.batch * self.fout.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]
         self.d_in = [torch.empty(self.batch * self.fin.frame_bytes, dtype=torch.uint8, device=dev) for _ in range(slots)]
-        self.d_out = [torch.empty(self.batch * self.fout.frame_bytes, dtype=torch.uint8, device=dev) for _ in range(slots)]
+        # (zeroed once: a v210 output's row padding is never written by the kernels and goes out with the frame)
+        self.d_out = [torch.zeros(self.batch * self.fout.frame_bytes, dtype=torch.uint8, device=dev) for _ in range(slots)]
         if self.fout2 is not None:
             self.kw = {k: v for k, v in self.kw.items() if k != "dither"}
             self.kw["out2_pix_fmt"] = self.fout2.fmt.name
