@@ -279,12 +279,29 @@ int lutr_resize_planes(lutr_ctx *ctx, int family, int depth, int csx, int csy, i
                        int nframes, const lutr_planes *src, lutr_planes *dst);
 
 /* zscale_dither of the reference (models.py:46; the filter `zscale=dither=error_diffusion`, ffmpeg.py:305-307) */
-enum lutr_dither { LUTR_DITHER_NONE = 0, LUTR_DITHER_ERROR_DIFFUSION = 1 };
+enum lutr_dither {
+    LUTR_DITHER_NONE = 0,
+    LUTR_DITHER_ERROR_DIFFUSION = 1,
+    /* An engine setting, not one of the reference's options: a threshold dither with a 64 x 64 void-and-cluster
+     * ("blue-noise") mask, fused into the output stage.  Every output sample is q = clip(floor(c + d), 0, max_o): c is the fp32
+     * value the output stage floors without dither (its 0.5 included), d = (2 * rank - 4095) / 8192 with rank the mask entry
+     * [(y + OY[p]) & 63][(x + OX[p]) & 63], OX = (0, 24, 40), OY = (0, 37, 11) for plane p = Y, Cb, Cr; (x, y) are the sample's
+     * coordinates in its own output plane, counted from the top-left of the full frame.  One fp32 add, rounded once.  The same
+     * pattern for every frame; no scratch; rows and frames are independent, so row shards and batches give the bits of the whole
+     * call.  Always strict arithmetic.  A context's first call in this mode allocates and uploads the 16 KB table of d; later
+     * calls only launch. */
+    LUTR_DITHER_BLUE_NOISE = 2
+};
+
+/* The mask of LUTR_DITHER_BLUE_NOISE: 4096 ranks, a permutation of 0 .. 4095, row-major [y][x].  Host only, no context, no GPU.
+ * LUTR_EINVAL for a null pointer. */
+int lutr_dither_mask(uint16_t out[4096]);
 
 /* lutr_apply_yuv with the final quantisation dithered: Floyd-Steinberg error diffusion per output plane
  * (rows top to bottom, left to right).  Rows are coupled, so this takes whole frames only;
  * shard a batch over GPUs by frames.  dither == LUTR_DITHER_NONE is lutr_apply_yuv on rows [0, h).
- * Uses context-owned device scratch of 4 bytes per output sample of the batch. */
+ * Uses context-owned device scratch of 4 bytes per output sample of the batch.
+ * dither == LUTR_DITHER_BLUE_NOISE is lutr_apply_yuv_xsub's blue-noise call on rows [0, h): same kernels, no scratch. */
 int lutr_apply_yuv_dither(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int dither, int w, int h, int nframes,
                           const lutr_planes *src, const lutr_planes *dst);
 
@@ -296,8 +313,11 @@ int lutr_apply_yuv_dither(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, i
  * prologue, matrices, ranges, LUT depth, truncation -- is lutr_apply_yuv's arithmetic.
  * row0 and rows must be multiples of the union block height 2^max(icsy, ocsy) unless row0 + rows == h.
  * dither: LUTR_DITHER_NONE, or LUTR_DITHER_ERROR_DIFFUSION on whole frames only (row0 = 0, rows = h; the scratch of
- * lutr_apply_yuv_dither, sized by the output layout).
- * Equal layouts are lutr_apply_yuv (or lutr_apply_yuv_dither when dithering) itself: same kernels, bits and last kernel.
+ * lutr_apply_yuv_dither, sized by the output layout), or LUTR_DITHER_BLUE_NOISE on any row range the block rule allows.
+ * Equal layouts are lutr_apply_yuv (or lutr_apply_yuv_dither for error diffusion) itself: same kernels, bits and last kernel.
+ * LUTR_DITHER_BLUE_NOISE does not forward: all nine layout pairs, the equal ones included, run "k_yuv_bn_vec<win,wout,icsx,
+ * icsy,ocsx,ocsy,interp>" under k_yuv_xsub_vec's conditions and "k_yuv_bn_generic" for everything else (any depth pair, 8 -> 16
+ * bit, all five modes), a ragged width split between the two; strict arithmetic, a .csp prelut taken; variants as below.
  * A layout change always runs strict precision (fast / fma32 run strict here, no suffix on the last kernel) and takes a
  * .csp prelut.  Kernels: "k_yuv_xsub_vec<win,wout,icsx,icsy,ocsx,ocsy,interp>" (nearest / trilinear / tetrahedral; 8 -> 8,
  * 16 -> 16 and 16 -> 8 bit containers; width a multiple of 8 luma samples, 4 for 16 -> 16; positive strides aligned to
@@ -326,7 +346,9 @@ int lutr_yuv_constants_xsub(const lutr_yuv_params *p, float out[32]);
  *   bits (8 | 16); a fourth component (alpha / padding) is read past and dropped.  16-bit formats need 2-byte aligned rows.
  * row0 and rows must be multiples of the output chroma block height 2^ocsy unless row0 + rows == h.
  * dither: LUTR_DITHER_NONE, or LUTR_DITHER_ERROR_DIFFUSION on whole frames only (the scratch of lutr_apply_yuv_dither, sized by
- * the output layout).  Always strict precision (fast / fma32 run strict here, no suffix on the last kernel).
+ * the output layout), or LUTR_DITHER_BLUE_NOISE on any row range the block rule allows: "k_rgb2yuv_bn_generic" (no vector kernel
+ * yet: vec_global and vec_lds fail with LUTR_EINVAL).  Always strict precision (fast / fma32 run strict here, no suffix on the
+ * last kernel).
  * Not in place: the bounding byte range of every source plane / the source image (all rows and frames) must be disjoint from
  * that of every destination plane (the rule of lutr_apply_yuv_sited), else LUTR_EINVAL before anything touches the device.
  * Kernels: "k_rgb2yuv_vec<win,nc,wout,ocsx,ocsy,interp|nolut>" (nc = 1 planar, 3 | 4 packed components; nearest / trilinear /
@@ -365,7 +387,9 @@ int lutr_apply_planar_rgb_f32(lutr_ctx *ctx, int interp, int w, int h, int nfram
  * takes the edge again; 4:4:0 is LUTR_EINVAL).  Reads of *p what lutr_apply_rgb_to_yuv reads; p->lut_depth must be 16, else
  * LUTR_EINVAL.  interp == LUTR_INTERP_NONE leaves lut3d out: sanitise, quantise, convert.
  * row0 and rows must be multiples of the output chroma block height 2^ocsy unless row0 + rows == h.
- * dither: LUTR_DITHER_NONE, or LUTR_DITHER_ERROR_DIFFUSION on whole frames only (the scratch of lutr_apply_yuv_dither).
+ * dither: LUTR_DITHER_NONE, or LUTR_DITHER_ERROR_DIFFUSION on whole frames only (the scratch of lutr_apply_yuv_dither), or
+ * LUTR_DITHER_BLUE_NOISE on any row range the block rule allows: "k_rgbf2yuv_bn_generic" (no vector kernel yet: vec_global and
+ * vec_lds fail with LUTR_EINVAL).
  * Always strict precision.  Not in place: the byte-range rule of lutr_apply_rgb_to_yuv, checked before anything touches the device.
  * Kernels: "k_rgbf2yuv_vec<wout,ocsx,ocsy,interp|nolut>" (nearest / trilinear / tetrahedral / no LUT; width a multiple of 8;
  * positive strides; source planes 16-byte aligned, destination planes to the 8 (chroma: 8 >> ocsx) samples a thread stores;

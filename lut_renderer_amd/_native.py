@@ -18,7 +18,7 @@ OK, ENOENT, EIO, ENOMEM, EINVAL, EILSEQ = 0, -2, -5, -12, -22, -84
 INTERP = {"nearest": 0, "trilinear": 1, "tetrahedral": 2, "pyramid": 3, "prism": 4}
 MATRIX = {"bt709": 0, "smpte170m": 1, "bt470bg": 1, "bt601": 1, "bt2020nc": 2, "bt2020c": 2}
 RANGE = {"tv": 0, "pc": 1}
-DITHER = {"none": 0, "error_diffusion": 1}
+DITHER = {"none": 0, "error_diffusion": 1, "blue_noise": 2}
 #: LUTR_INTERP_NONE: lutr_apply_rgb_to_yuv without lut3d
 INTERP_NONE = -1
 VARIANT = {"auto": 0, "generic": 1, "vec_global": 2, "vec_lds": 3}
@@ -42,7 +42,7 @@ SYMBOLS = (
     "lutr_apply_rgb_to_yuv", "lutr_yuv_constants_rgb2yuv",
     "lutr_apply_planar_rgb_f32", "lutr_apply_rgbf_to_yuv", "lutr_apply_yuv_semi", "lutr_apply_yuv_packed",
     "lutr_apply_yuv_dual", "lutr_apply_yuv_v210",
-    "lutr_resize_filter", "lutr_resize_planes",
+    "lutr_resize_filter", "lutr_resize_planes", "lutr_dither_mask",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
 )
 
@@ -186,6 +186,7 @@ def load() -> C.CDLL:
     lib.lutr_apply_yuv_v210.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_apply_yuv_dual.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes),
                                         C.POINTER(Planes), ci, ci]
+    lib.lutr_dither_mask.argtypes = [C.POINTER(C.c_uint16)]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]
     lib.lutr_ctx_set_variant.argtypes = [vp, ci]
@@ -196,6 +197,14 @@ def load() -> C.CDLL:
     lib.lutr_yuv_constants.argtypes = [C.POINTER(YuvParams), C.POINTER(C.c_float)]
     _lib = lib
     return lib
+
+
+def dither_mask():
+    """lutr_dither_mask (host only): the 64 x 64 ranks of the blue-noise dither, uint16 [y, x]."""
+    import numpy as np
+    rank = np.zeros((64, 64), np.uint16)
+    check(load().lutr_dither_mask(rank.ctypes.data_as(C.POINTER(C.c_uint16))))
+    return rank
 
 
 def resize_filter(src: int, dst: int, cs: int = 0, cosited: bool = False):

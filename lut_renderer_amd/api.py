@@ -169,12 +169,22 @@ def is_float_out_call(kw: dict) -> bool:
     return out is not None and out.floating
 
 
+def resolve_engine_dither(engine_dither: str, dither: str = "none") -> str:
+    """The `dither` keyword of an engine call for the engine setting `engine_dither` beside the one
+    `zscale_dither` selected: "blue_noise", or ValueError for an unknown value or for two dithers at once."""
+    if engine_dither != "blue_noise":
+        raise ValueError(f"unknown engine_dither '{engine_dither}' (blue_noise)")
+    if dither == "error_diffusion":
+        raise ValueError("two dithers were asked for: engine_dither='blue_noise' and zscale_dither='error_diffusion'")
+    return "blue_noise"
+
+
 def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: str, width: Optional[int] = None,
               height: Optional[int] = None, input_matrix: str = "auto", colorspace: Optional[str] = None,
               color_range: Optional[str] = None, output_tags: str = "bt709", out_pix_fmt: Optional[str] = None,
               zscale_dither: str = "none", out: Optional[Sequence] = None, engine=None,
               devices: Sequence[int] = (0,), precision: str = "strict", chroma_loc: Optional[str] = None,
-              resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None):
+              resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -201,6 +211,11 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     is fp16 (<= 1 code from strict at 8 and 10 bit) where they exist and silently runs strict elsewhere
     (`engine.last_kernel` ends in `,fast` when they ran); "fma32" keeps strict's fp32 lattice and fuses the blend's
     multiply-adds (<= 1 code from strict), on the same terms (`,fma32`).
+
+    `engine_dither` is an engine setting too (DESIGN.md 3.15): None (default) leaves the quantisation to `zscale_dither`;
+    "blue_noise" quantises every output sample against a 64 x 64 void-and-cluster mask inside the LUT pass -- no scratch, rows
+    and frames independent (a LutEngineGroup row-shards it), always strict arithmetic.  It is not `zscale_dither`, which keeps
+    the reference's meaning; asking for both dithers is a ValueError, and so is any other value.
 
     `chroma_loc` is an engine setting too: None (default) replicates chroma over its block before the LUT and takes the
     block mean after it; "left" | "center" | "topleft" (ffprobe's chroma_location) resample chroma bilinearly at that
@@ -256,6 +271,8 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     kw = engine_call_for(plan, pix_fmt, out_pix_fmt)
     # ffmpeg.py:305-307: any value other than "error_diffusion" leaves the chain without a dither filter
     kw["dither"] = "error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none"
+    if engine_dither is not None:
+        kw["dither"] = resolve_engine_dither(engine_dither, kw["dither"])
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
     if second_pix_fmt is not None:

@@ -61,6 +61,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--chroma-loc", default=None, choices=["left", "center", "topleft"],
                     help="engine setting: resample chroma bilinearly at this siting (ffprobe's chroma_location) instead of "
                          "replicating it over its block; strict arithmetic")
+    ap.add_argument("--engine-dither", default=None, choices=["blue_noise"],
+                    help="engine setting: quantise the output against a 64 x 64 blue-noise mask inside the LUT pass (DESIGN.md "
+                         "3.15); not together with --zscale-dither error_diffusion")
     ap.add_argument("--out-size", default=None, metavar="WxH",
                     help="engine setting: resize the output frames to WxH on the GPU after the LUT (the reference's -s, "
                          "DESIGN.md 3.7); frames on -o have this size")
@@ -91,10 +94,14 @@ def plan_from_args(args):
     plan = resolve_lut_plan(params, args.cube, info)
     kw = engine_call_for(plan, args.pix_fmt, args.out_pix_fmt)
     from .api import is_float_out_call
-    if is_float_out_call(kw) and (args.zscale_dither == "error_diffusion" or getattr(args, "out_size", None)):
+    engine_dither = getattr(args, "engine_dither", None)
+    if is_float_out_call(kw) and (args.zscale_dither == "error_diffusion" or engine_dither or getattr(args, "out_size", None)):
         raise ValueError("a float output takes no dither and no --out-size")
     if args.zscale_dither == "error_diffusion":
         kw["dither"] = "error_diffusion"
+    if engine_dither:
+        from .api import resolve_engine_dither
+        kw["dither"] = resolve_engine_dither(engine_dither, kw.get("dither", "none"))
     from .api import is_rgb_call
     if getattr(args, "chroma_loc", None) and is_rgb_call(kw):
         raise ValueError("chroma siting (--chroma-loc) is not defined for an RGB source")

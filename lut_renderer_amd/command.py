@@ -252,7 +252,7 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                    source_info: VideoInfo, python_bin: Optional[str] = None, device: int = 0,
                    notes: Optional[List[str]] = None, precision: str = "strict", chroma_loc: Optional[str] = None,
                    gpu_resize: bool = False, second_output: Optional[Path] = None,
-                   second_pix_fmt: Optional[str] = None) -> List[str]:
+                   second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None) -> List[str]:
     """`build_command`'s twin for the LUT stage alone: the argv of the ENGINE CLI (`python -m lut_renderer_amd.cli`)
     that applies exactly the chain `build_command` would put into `-vf` -- the same `LutPlan`, rendered as CLI options
     instead of as a filter string (ffmpeg.py:195-247, :287-310).  `source` / `output` are rawvideo files (or `-`) in
@@ -265,7 +265,9 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     output format must then be planar (ValueError for packed formats).  False (default) leaves the argv as it was.
     `second_output` / `second_pix_fmt` (both or neither) add a second rawvideo output from the same LUT pass (`--second-output`,
     `--second-pix-fmt`, DESIGN.md 3.13: the master and the delivery format of the "pro" mode together); rendered only when given.
-    Planar YUV on every side; not with dither, `chroma_loc` or `gpu_resize`."""
+    Planar YUV on every side; not with dither, `chroma_loc` or `gpu_resize`.
+    `engine_dither` ("blue_noise", DESIGN.md 3.15) is an engine setting as well (`--engine-dither`, rendered only when given);
+    not together with `params.zscale_dither` = error_diffusion, `chroma_loc` or a second output."""
     import sys as _sys
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
@@ -314,8 +316,14 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
         cmd += ["--device", str(int(device))]
     if precision != "strict":
         cmd += ["--precision", precision]
+    if engine_dither is not None:
+        from .api import resolve_engine_dither
+        resolve_engine_dither(engine_dither, "error_diffusion" if "--zscale-dither" in cmd else "none")
+        if not pix_fmt and _is_float_source(source_info.pix_fmt):
+            raise ValueError("a float output takes no dither")
+        cmd += ["--engine-dither", engine_dither]
     if chroma_loc is not None:
-        if "--zscale-dither" in cmd:
+        if "--zscale-dither" in cmd or "--engine-dither" in cmd:
             raise ValueError("error-diffusion dither is not defined with sited chroma resampling (chroma_loc)")
         cmd += ["--chroma-loc", chroma_loc]
     if gpu_resize and params.resolution:
@@ -332,7 +340,7 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
             raise ValueError("second_output is a file or FIFO, not '-'")
         from .engine import check_dual_options
         check_dual_options(str(source_info.pix_fmt), pix_fmt or None, second_pix_fmt,
-                           "error_diffusion" if "--zscale-dither" in cmd else "none", chroma_loc,
+                           "error_diffusion" if "--zscale-dither" in cmd else ("blue_noise" if "--engine-dither" in cmd else "none"), chroma_loc,
                            params.resolution if "--out-size" in cmd else None)
         cmd += ["--second-output", str(second_output), "--second-pix-fmt", second_pix_fmt]
     return cmd

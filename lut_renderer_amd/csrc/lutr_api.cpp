@@ -17,6 +17,7 @@
 
 #include "lutr_internal.h"
 #include "lutr_launch.h"
+#include "lutr_bn_mask.h"
 
 namespace lutr {
 
@@ -284,6 +285,7 @@ struct lutr_ctx {
     bool unit = false;               // every lattice node known to lie in [0, 1]
     unsigned *queue = nullptr;       // work-queue words of the tile kernels (device, 4 words: see lutr_ctx_create)
     float *fscratch = nullptr;       // float planes of the dither path
+    float *bn_tab = nullptr;         // blue-noise dither: the 64 x 64 offsets d, uploaded on first use and kept
     size_t fscratch_floats = 0;
     unsigned *stats = nullptr;       // 8 device counters (4 reported + clock stamps), see lutr_ctx_tile_stats
     // The queue counter, the dither scratch and the stats block are per context, not per stream: launches of one
@@ -463,6 +465,7 @@ void lutr_ctx_destroy(lutr_ctx *c)
     if (c->lat) (void)hipFree(c->lat);
     if (c->stats) (void)hipFree(c->stats);
     if (c->fscratch) (void)hipFree(c->fscratch);
+    if (c->bn_tab) (void)hipFree(c->bn_tab);
     for (auto &t : c->rz_tables) (void)hipFree(t.dev);
     if (c->queue) (void)hipFree(c->queue);
     if (c->done) (void)hipEventDestroy(c->done);
@@ -814,7 +817,10 @@ static int check_row_blocks(int row0, int rows, int h, int bh, const char *noun)
 
 static int check_dither(int dither)
 {
-    if (dither != LUTR_DITHER_NONE && dither != LUTR_DITHER_ERROR_DIFFUSION) { set_error("unknown dither mode %d", dither); return LUTR_EINVAL; }
+    if (dither != LUTR_DITHER_NONE && dither != LUTR_DITHER_ERROR_DIFFUSION && dither != LUTR_DITHER_BLUE_NOISE) {
+        set_error("unknown dither mode %d", dither);
+        return LUTR_EINVAL;
+    }
     return LUTR_OK;
 }
 
@@ -1072,6 +1078,23 @@ static int dither_scratch(lutr_ctx *c, const FrameGeom &G, int csx, int csy, Flo
     return LUTR_OK;
 }
 
+// The blue-noise table of the context's device: d = (2 rank - 4095) / 8192 per mask cell, exact in fp32.
+static int bn_table(lutr_ctx *c, const float **out)
+{
+    if (!c->bn_tab) {
+        std::vector<float> d(64 * 64);
+        for (int i = 0; i < 64 * 64; i++) d[i] = (float)(2 * (int)kLutrBnMask[i] - 4095) / 8192.0f;
+        void *p = nullptr;
+        hipError_t e = hipMalloc(&p, d.size() * sizeof(float));
+        if (e != hipSuccess) { set_error("hipMalloc(dither table): %s", hipGetErrorString(e)); return LUTR_ENOMEM; }
+        e = hipMemcpy(p, d.data(), d.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(p); return hip_fail(e, "dither table upload"); }
+        c->bn_tab = (float *)p;
+    }
+    *out = c->bn_tab;
+    return LUTR_OK;
+}
+
 int lutr_apply_yuv_sited(lutr_ctx *c, const lutr_yuv_params *p, int interp, int chroma_loc, int w, int h, int nframes,
                          const lutr_planes *src, lutr_planes *dst, int row0, int rows)
 {
@@ -1111,6 +1134,7 @@ int lutr_apply_yuv_dither(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
                           const lutr_planes *src, const lutr_planes *dst)
 {
     if (dither == LUTR_DITHER_NONE) return lutr_apply_yuv(c, p, interp, w, h, nframes, src, dst, 0, h);
+    if (dither == LUTR_DITHER_BLUE_NOISE) return lutr_apply_yuv_xsub(c, p, interp, dither, w, h, nframes, src, dst, 0, h);
     if (dither != LUTR_DITHER_ERROR_DIFFUSION) { set_error("unknown dither mode %d", dither); return LUTR_EINVAL; }
     int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, 0, h);
     if (rc) return rc;
@@ -1144,7 +1168,7 @@ int lutr_apply_yuv_xsub(lutr_ctx *c, const lutr_yuv_params *p, int interp, int d
     if (const int rc = check_dither_rows(dither, row0, rows, h)) return rc;
     const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
     const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
-    if (icsx == ocsx && icsy == ocsy)        // one layout: lutr_apply_yuv's contract, kernels and bits
+    if (icsx == ocsx && icsy == ocsy && dither != LUTR_DITHER_BLUE_NOISE)        // one layout: lutr_apply_yuv's contract, kernels and bits
         return dither == LUTR_DITHER_NONE ? lutr_apply_yuv(c, p, interp, w, h, nframes, src, dst, row0, rows)
                                           : lutr_apply_yuv_dither(c, p, interp, dither, w, h, nframes, src, dst);
     const int bh = 1 << (icsy > ocsy ? icsy : ocsy);
@@ -1159,6 +1183,11 @@ int lutr_apply_yuv_xsub(lutr_ctx *c, const lutr_yuv_params *p, int interp, int d
     const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
     if (dither == LUTR_DITHER_NONE)
         return finish_launch(c, launch_yuv_xsub(c->stream, c->variant, L, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, interp));
+    if (dither == LUTR_DITHER_BLUE_NOISE) {
+        const float *bn;
+        if (const int rc = bn_table(c, &bn)) return rc;
+        return finish_launch(c, launch_yuv_bn(c->stream, c->variant, L, K, P, G, bn, din, dout, icsx, icsy, ocsx, ocsy, interp));
+    }
     FloatPlanes F;
     if (const int rc = dither_scratch(c, G, ocsx, ocsy, &F)) return rc;
     return finish_launch(c, launch_yuv_dither(c->stream, L, K, P, G, F, din, dout, icsx, icsy, interp, ocsx, ocsy));
@@ -1515,6 +1544,11 @@ int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
         if (const int rc = fill_lut(&L, c, dl)) return rc;
     if (dither == LUTR_DITHER_NONE)
         return finish_launch(c, launch_rgb2yuv(c->stream, c->variant, L, K, P, Y, G, dout, ocsx, ocsy, interp));
+    if (dither == LUTR_DITHER_BLUE_NOISE) {
+        const float *bn;
+        if (const int rc = bn_table(c, &bn)) return rc;
+        return finish_launch(c, launch_rgb2yuv_bn(c->stream, c->variant, L, K, P, Y, G, bn, dout, ocsx, ocsy, interp));
+    }
     FloatPlanes F;
     if (const int rc = dither_scratch(c, G, ocsx, ocsy, &F)) return rc;
     return finish_launch(c, launch_rgb2yuv_dither(c->stream, L, K, P, Y, G, F, dout, ocsx, ocsy, interp));
@@ -1581,9 +1615,21 @@ int lutr_apply_rgbf_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, in
     if (const int rc = fill_lut_float(&L, &Q, c, interp != LUTR_INTERP_NONE)) return rc;
     if (dither == LUTR_DITHER_NONE)
         return finish_launch(c, launch_rgbf2yuv(c->stream, c->variant, L, Q, K, P, G, dout, ocsx, ocsy, interp));
+    if (dither == LUTR_DITHER_BLUE_NOISE) {
+        const float *bn;
+        if (const int rc = bn_table(c, &bn)) return rc;
+        return finish_launch(c, launch_rgbf2yuv_bn(c->stream, c->variant, L, Q, K, P, G, bn, dout, ocsx, ocsy, interp));
+    }
     FloatPlanes F;
     if (const int rc = dither_scratch(c, G, ocsx, ocsy, &F)) return rc;
     return finish_launch(c, launch_rgbf2yuv_dither(c->stream, L, Q, K, P, G, F, dout, ocsx, ocsy, interp));
+}
+
+int lutr_dither_mask(uint16_t out[4096])
+{
+    if (!out) { set_error("lutr_dither_mask: null out pointer"); return LUTR_EINVAL; }
+    std::memcpy(out, kLutrBnMask, sizeof(kLutrBnMask));
+    return LUTR_OK;
 }
 
 int lutr_resize_filter(int src, int dst, int cs, int cosited, int *start, int16_t *weights, int *ntaps)

@@ -1,5 +1,5 @@
 // lutr_device.h -- device-side pieces shared by the gfx950 gather kernels (lutr_kernels.hip, lutr_packed.hip, lutr_sited.hip,
-// lutr_dither.hip, lutr_xsub.hip, lutr_rgb2yuv.hip, lutr_rgbf.hip, lutr_semi.hip): the lut3d per-pixel restatement (SURVEY.md
+// lutr_dither.hip, lutr_xsub.hip, lutr_bnd.hip, lutr_rgb2yuv.hip, lutr_rgbf.hip, lutr_semi.hip): the lut3d per-pixel restatement (SURVEY.md
 // Appendix A.3-A.5), the YUV contract (DESIGN.md "YUV contract"), little sample/word accessors, the block walk, block
 // body and output sinks of the by-block generic kernels, and the vector kernels' unit size.
 //
@@ -12,6 +12,7 @@
 namespace lutr {
 
 // ---------------------------------------------------------------- small math
+constexpr int cmax(int a, int b) { return a > b ? a : b; }
 __device__ __forceinline__ float med3(float a, float lo, float hi) { return __builtin_amdgcn_fmed3f(a, lo, hi); }
 __device__ __forceinline__ float max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 __device__ __forceinline__ float min3(float a, float b, float c) { return fminf(fminf(a, b), c); }
@@ -373,6 +374,53 @@ struct FloatSink {
     }
 };
 
+// ---------------------------------------------------------------- blue-noise dither
+// bn: the 64 x 64 table of offsets d = (2 rank - 4095) / 8192, row-major.  Sample (x, y) of output plane `plane` (0 = Y, 1 = Cb,
+// 2 = Cr; the plane's own coordinates, counted from the top-left of the full frame) takes bn[(y + OY) & 63][(x + OX) & 63].  The x
+// shifts are multiples of 8: an aligned run of up to 8 samples is contiguous in the table and never wraps.
+__device__ __forceinline__ int bn_ox(int plane) { return plane == 0 ? 0 : (plane == 1 ? 24 : 40); }
+__device__ __forceinline__ int bn_oy(int plane) { return plane == 0 ? 0 : (plane == 1 ? 37 : 11); }
+
+__device__ __forceinline__ float bn_offset(const float *__restrict__ bn, int plane, int x, int y)
+{
+    return bn[(((y + bn_oy(plane)) & 63) << 6) | ((x + bn_ox(plane)) & 63)];
+}
+
+// the output stage with the offset in front of clip_floor: one fp32 add, rounded once (d = 0 gives rgb_to_y / _cb / _cr above)
+__device__ __forceinline__ float rgb_to_y(const YuvConsts &K, const Rgb &q, float d)
+{
+    return clip_floor(fma_(K.cyr, q.r, fma_(K.cyg, q.g, fma_(K.cyb, q.b, K.yob))) + d, K.max_o);
+}
+
+__device__ __forceinline__ float rgb_to_cb(const YuvConsts &K, float rs, float gs, float bs, float d)
+{
+    return clip_floor(fma_(K.cbr, rs, fma_(K.cbg, gs, fma_(K.cbb, bs, K.cob))) + d, K.max_o);
+}
+
+__device__ __forceinline__ float rgb_to_cr(const YuvConsts &K, float rs, float gs, float bs, float d)
+{
+    return clip_floor(fma_(K.crr, rs, fma_(K.crg, gs, fma_(K.crb, bs, K.cob))) + d, K.max_o);
+}
+
+// DitherSink: PlaneSink with the table.  x0 / cx0: where column 0 of the planes lies in the frame (luma / output chroma samples;
+// the generic tail of a column split starts to the right of the vector kernel's part); rows already count from the frame's top.
+struct DitherSink {
+    const YuvConsts &K;
+    const PlaneSet &P;
+    int wout;
+    const float *__restrict__ bn;
+    int x0, cx0;
+    __device__ __forceinline__ void luma(long long fr, int x, int y, const Rgb &o)
+    {
+        st_sample(dst_row(P, 0, fr, y), x, wout, rgb_to_y(K, o, bn_offset(bn, 0, x0 + x, y)));
+    }
+    __device__ __forceinline__ void chroma(long long fr, int cx, int cy, float rs, float gs, float bs)
+    {
+        st_sample(dst_row(P, 1, fr, cy), cx, wout, rgb_to_cb(K, rs, gs, bs, bn_offset(bn, 1, cx0 + cx, cy)));
+        st_sample(dst_row(P, 2, fr, cy), cx, wout, rgb_to_cr(K, rs, gs, bs, bn_offset(bn, 2, cx0 + cx, cy)));
+    }
+};
+
 // One chroma block of the fused YUV pass (k_yuv_generic, k_yuv_float).  A pixel outside the frame is the edge pixel again (odd
 // sizes: the edge column / row is summed twice); only pixels inside the frame are written.
 template <class Sink>
@@ -398,6 +446,42 @@ __device__ __forceinline__ void yuv_block(const LutConsts &L, const GFetch &f, c
     sink.chroma(fr, cx, cy, rs, gs, bs);
 }
 
+// One union block of a pass that changes the chroma subsampling (k_yuv_xsub_generic, k_yuv_float_xsub,
+// k_yuv_bn_generic).  The block is walked one OUTPUT
+// chroma block at a time (its sum is then one set of three accumulators); every pixel reads the input chroma sample of its
+// own input block.  A pixel outside the frame is the edge pixel again (its luma and its chroma), so a partial output block
+// sums the edge column / row twice, like np.pad(mode="edge"); only pixels and chroma samples inside the planes are written.
+template <class Sink>
+__device__ __forceinline__ void xsub_union_block(const LutConsts &L, const GFetch &f, const YuvConsts &K, const PlaneSet &P,
+                                                 const FrameGeom &G, long long fr, int ux, int uy, int win, int icsx, int icsy,
+                                                 int ocsx, int ocsy, int mode, Sink &sink)
+{
+    const int bw = 1 << cmax(icsx, ocsx), bh = 1 << cmax(icsy, ocsy), obw = 1 << ocsx, obh = 1 << ocsy;
+    const int cwo = (G.w + obw - 1) >> ocsx, cho = (G.h + obh - 1) >> ocsy;
+    for (int oy = 0; oy < bh; oy += obh) {
+        for (int ox = 0; ox < bw; ox += obw) {
+            float rs = 0.f, gs = 0.f, bs = 0.f;
+            for (int dy = 0; dy < obh; dy++) {
+                const int yy = uy * bh + oy + dy;
+                const int y = yy < G.h ? yy : G.h - 1;
+                for (int dx = 0; dx < obw; dx++) {
+                    const int xx = ux * bw + ox + dx;
+                    const int x = xx < G.w ? xx : G.w - 1;
+                    const float cbv = ld_sample(src_row(P, 1, fr, y >> icsy), x >> icsx, win);
+                    const float crv = ld_sample(src_row(P, 2, fr, y >> icsy), x >> icsx, win);
+                    const float yv = ld_sample(src_row(P, 0, fr, y), x, win);
+                    const Rgb q = yuv_to_rgb(K, yv, chroma_terms(K, cbv, crv));
+                    const Rgb o = lut3d_px_rt(mode, L, f, q.r, q.g, q.b);
+                    rs += o.r; gs += o.g; bs += o.b;
+                    if (yy < G.h && xx < G.w) sink.luma(fr, x, y, o);
+                }
+            }
+            const int ocx = (ux * bw + ox) >> ocsx, ocy = (uy * bh + oy) >> ocsy;
+            if (ocx < cwo && ocy < cho) sink.chroma(fr, ocx, ocy, rs, gs, bs);
+        }
+    }
+}
+
 // A code inside a container at run-time width: sample x of `row`, `shift` bits up inside a 16-bit word (p010le, y210le: 6); the
 // generic kernels of the semi-planar and packed 4:2:2 paths (lutr_semi.hip, lutr_pkyuv.hip).
 __device__ __forceinline__ float ld_code(const uint8_t *row, long long x, int wide, int shift)
@@ -420,6 +504,151 @@ constexpr int kVecBytes = 8;
 // ffmpeg.py:287-302) takes 16 bytes of luma per thread and row so that its 8-bit chroma output is still a whole word.
 template <int WIN, int WOUT> constexpr int vec_bytes() { return (WIN && !WOUT) ? 16 : kVecBytes; }
 
-constexpr int cmax(int a, int b) { return a > b ? a : b; }
+
+// ---------------------------------------------------------------- the vector body of a subsampling change (3.8) and of blue-noise dither (3.15)
+// N offsets of one table row for the samples x .. x + N - 1 of a plane (x a multiple of min(N, 4); ox a multiple of 8): aligned
+// 16-byte (8-byte for N = 2) loads, each inside one row of the table.
+template <int N>
+__device__ __forceinline__ void ld_bn(float *d, const float *__restrict__ row, int x, int ox)
+{
+    if constexpr (N >= 4) {
+#pragma unroll
+        for (int k = 0; k < N; k += 4) {
+            const float4 v = *(const float4 *)(row + ((x + k + ox) & 63));
+            d[k] = v.x; d[k + 1] = v.y; d[k + 2] = v.z; d[k + 3] = v.w;
+        }
+    } else {
+        static_assert(N == 2, "a thread owns 2, 4 or 8 samples of a plane row");
+        const float2 v = *(const float2 *)(row + ((x + ox) & 63));
+        d[0] = v.x; d[1] = v.y;
+    }
+}
+
+// k_yuv_vec's structure (lutr_kernels.hip): whole-word loads and stores, VB bytes of luma per thread and row, BH luma rows per
+// thread, lattice taps gathered from L1/L2.  The thread's input chroma rows (BH >> ICSY) and output chroma rows (BH >> OCSY)
+// are separate arrays; the thread walks its union blocks one after the other.  (Frame written out: see k_yuv_vec.)  The body of
+// k_yuv_xsub_vec (lutr_xsub.hip, BN = false: bn is not read) and of k_yuv_bn_vec (lutr_bnd.hip, BN = true: the offsets of the
+// thread's output samples are loaded beside its source words, PXT floats per luma row, PXT >> OCSX per output chroma row and
+// plane; the table, 16 KB, stays in L1 / L2).
+template <int WIN, int WOUT, int ICSX, int ICSY, int OCSX, int OCSY, int INTERP, bool BN>
+__device__ __forceinline__ void yuv_xsub_vec_body(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G,
+                                                   const float *__restrict__ bn)
+{
+    constexpr int VB = vec_bytes<WIN, WOUT>();
+    constexpr int PXT = VB / (WIN ? 2 : 1);                       // luma samples per thread per row
+    constexpr int YWI = VB / 4, YWO = PXT * (WOUT ? 2 : 1) / 4;   // luma words per thread per row, in / out
+    constexpr int CSX = cmax(ICSX, OCSX), CSY = cmax(ICSY, OCSY);
+    constexpr int BW = 1 << CSX, BH = 1 << CSY;                   // the union block
+    constexpr int NB = PXT / BW;                                  // union blocks per thread
+    constexpr int IRH = BH >> ICSY, ORH = BH >> OCSY;             // chroma rows per thread, in / out
+    constexpr int IBX = BW >> ICSX, OBX = BW >> OCSX;             // chroma samples per union block and row, in / out
+    constexpr int CWI = (PXT >> ICSX) * (WIN ? 2 : 1) / 4, CWO = (PXT >> OCSX) * (WOUT ? 2 : 1) / 4;
+    constexpr int CPX = PXT >> OCSX;                              // output chroma samples per thread per row
+    static_assert(NB >= 1 && CWI >= 1 && CWO >= 1 && YWO >= 1, "a thread must own whole words");
+    const GFetch f(L);
+    const unsigned uw = (unsigned)G.w / PXT;
+    const unsigned ub = (unsigned)G.rows >> CSY;
+    const unsigned total = uw * ub * (unsigned)G.nframes;
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= total) return;
+    const unsigned xu = u % uw, t = u / uw;
+    const int y0 = ((G.row0 >> CSY) + (int)(t % ub)) * BH;        // first luma row of the thread
+    const long long fr = t / ub;
+    const long long xi = (long long)xu * VB, xo = (long long)xu * (YWO * 4), cxi = (long long)xu * (CWI * 4),
+                    cxo = (long long)xu * (CWO * 4);
+
+    uint32_t yw[BH][YWI], cbw[IRH][CWI], crw[IRH][CWI];
+    uint32_t yo[BH][YWO], cbo[ORH][CWO], cro[ORH][CWO];
+    float dy_[BH][BN ? PXT : 1], dcb[ORH][BN ? CPX : 1], dcr[ORH][BN ? CPX : 1];   // the offsets of the thread's output samples
+#pragma unroll
+    for (int dy = 0; dy < BH; dy++) {
+        ld_words<YWI>(yw[dy], P.s[0] + fr * P.sfs[0] + (long long)(y0 + dy) * P.ss[0] + xi);
+        if constexpr (BN) ld_bn<PXT>(dy_[dy], bn + (((y0 + dy + bn_oy(0)) & 63) << 6), (int)xu * PXT, bn_ox(0));
+#pragma unroll
+        for (int k = 0; k < YWO; k++) yo[dy][k] = 0;
+    }
+#pragma unroll
+    for (int iy = 0; iy < IRH; iy++) {
+        const long long r = (long long)((y0 >> ICSY) + iy);
+        ld_words<CWI>(cbw[iy], P.s[1] + fr * P.sfs[1] + r * P.ss[1] + cxi);
+        ld_words<CWI>(crw[iy], P.s[2] + fr * P.sfs[2] + r * P.ss[2] + cxi);
+    }
+#pragma unroll
+    for (int oy = 0; oy < ORH; oy++) {
+        if constexpr (BN) {
+            const int r = (y0 >> OCSY) + oy;
+            ld_bn<CPX>(dcb[oy], bn + (((r + bn_oy(1)) & 63) << 6), (int)xu * CPX, bn_ox(1));
+            ld_bn<CPX>(dcr[oy], bn + (((r + bn_oy(2)) & 63) << 6), (int)xu * CPX, bn_ox(2));
+        }
+#pragma unroll
+        for (int k = 0; k < CWO; k++) { cbo[oy][k] = 0; cro[oy][k] = 0; }
+    }
+
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+        Chroma c[IRH][IBX];
+#pragma unroll
+        for (int iy = 0; iy < IRH; iy++)
+#pragma unroll
+            for (int ix = 0; ix < IBX; ix++)
+                c[iy][ix] = chroma_terms(K, word_sample<WIN>(cbw[iy], j * IBX + ix), word_sample<WIN>(crw[iy], j * IBX + ix));
+        float rs[ORH][OBX], gs[ORH][OBX], bs[ORH][OBX];
+#pragma unroll
+        for (int oy = 0; oy < ORH; oy++)
+#pragma unroll
+            for (int ox = 0; ox < OBX; ox++) { rs[oy][ox] = 0.f; gs[oy][ox] = 0.f; bs[oy][ox] = 0.f; }
+#pragma unroll
+        for (int dy = 0; dy < BH; dy++) {
+#pragma unroll
+            for (int dx = 0; dx < BW; dx++) {
+                const int i = j * BW + dx;
+                const Rgb q = yuv_to_rgb(K, word_sample<WIN>(yw[dy], i), c[dy >> ICSY][dx >> ICSX]);
+                const Rgb o = lut3d_px<INTERP>(L, f, q.r, q.g, q.b);
+                rs[dy >> OCSY][dx >> OCSX] += o.r; gs[dy >> OCSY][dx >> OCSX] += o.g; bs[dy >> OCSY][dx >> OCSX] += o.b;
+                if constexpr (BN) word_put<WOUT>(yo[dy], i, rgb_to_y(K, o, dy_[dy][i]));
+                else word_put<WOUT>(yo[dy], i, rgb_to_y(K, o));
+            }
+        }
+#pragma unroll
+        for (int oy = 0; oy < ORH; oy++)
+#pragma unroll
+            for (int ox = 0; ox < OBX; ox++) {
+                const int i = j * OBX + ox;
+                if constexpr (BN) {
+                    word_put<WOUT>(cbo[oy], i, rgb_to_cb(K, rs[oy][ox], gs[oy][ox], bs[oy][ox], dcb[oy][i]));
+                    word_put<WOUT>(cro[oy], i, rgb_to_cr(K, rs[oy][ox], gs[oy][ox], bs[oy][ox], dcr[oy][i]));
+                } else {
+                    word_put<WOUT>(cbo[oy], i, rgb_to_cb(K, rs[oy][ox], gs[oy][ox], bs[oy][ox]));
+                    word_put<WOUT>(cro[oy], i, rgb_to_cr(K, rs[oy][ox], gs[oy][ox], bs[oy][ox]));
+                }
+            }
+        // Zero-instruction fence (k_yuv_vec's): keeps hipcc from hoisting the coordinates and taps of every union block of the
+        // thread to the top; with it the blocks are emitted one after the other.
+#pragma unroll
+        for (int dy = 0; dy < BH; dy++) {
+#pragma unroll
+            for (int k = 0; k < YWI; k++) asm volatile("" : "+v"(yw[dy][k]));
+#pragma unroll
+            for (int k = 0; k < YWO; k++) asm volatile("" : "+v"(yo[dy][k]));
+        }
+#pragma unroll
+        for (int iy = 0; iy < IRH; iy++)
+#pragma unroll
+            for (int k = 0; k < CWI; k++) asm volatile("" : "+v"(cbw[iy][k]), "+v"(crw[iy][k]));
+#pragma unroll
+        for (int oy = 0; oy < ORH; oy++)
+#pragma unroll
+            for (int k = 0; k < CWO; k++) asm volatile("" : "+v"(cbo[oy][k]), "+v"(cro[oy][k]));
+    }
+#pragma unroll
+    for (int dy = 0; dy < BH; dy++)
+        st_words<YWO>(P.d[0] + fr * P.dfs[0] + (long long)(y0 + dy) * P.ds[0] + xo, yo[dy]);
+#pragma unroll
+    for (int oy = 0; oy < ORH; oy++) {
+        const long long r = (long long)((y0 >> OCSY) + oy);
+        st_words<CWO>(P.d[1] + fr * P.dfs[1] + r * P.ds[1] + cxo, cbo[oy]);
+        st_words<CWO>(P.d[2] + fr * P.dfs[2] + r * P.ds[2] + cxo, cro[oy]);
+    }
+}
 
 }  // namespace lutr

@@ -131,6 +131,18 @@ LUTR_XS_DECL(w00) LUTR_XS_DECL(w11) LUTR_XS_DECL(w10)
 void launch_yuv_float_xsub(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
                            const FloatPlanes &F, int win, int icsx, int icsy, int ocsx, int ocsy, int interp);
 
+// blue-noise dither in the output stage (lutr_bnd.hip): launch_yuv_xsub's call for any pair of layouts, the equal
+// ones included; bn = the 64 x 64 table of offsets (device).  nullptr = the variant cannot take the call (vec_lds always;
+// vec_global on layouts the vector kernel cannot take)
+const char *launch_yuv_bn(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
+                          const float *bn, int din, int dout, int icsx, int icsy, int ocsx, int ocsy, int interp);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>): nullptr = not a mode it has
+#define LUTR_BN_DECL(tag) \
+    const char *launch_yuv_bn_vec_##tag(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, \
+                                        const FrameGeom &G, const float *bn, int icsx, int icsy, int ocsx, int ocsy, int interp);
+LUTR_BN_DECL(w00) LUTR_BN_DECL(w11) LUTR_BN_DECL(w10)
+#undef LUTR_BN_DECL
+
 // two outputs from one pass (lutr_dual.hip): input layout icsx, icsy; output 1 in P.d (depth dout1, layout csx1, csy1,
 // constants K1), output 2 in D2 (dout2, csx2, csy2, K2); K1 and K2 share the input stage.  nullptr = the variant cannot take the
 // call (vec_lds always; vec_global on layouts the vector kernel cannot take)
@@ -226,6 +238,11 @@ LUTR_R2Y_DECL(w00) LUTR_R2Y_DECL(w11) LUTR_R2Y_DECL(w10)
 const char *launch_rgb2yuv_dither(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const RgbLayout &Y,
                                   const FrameGeom &G, const FloatPlanes &F, int dout, int ocsx, int ocsy, int mode);
 
+// the blue-noise path: the generic kernel with a DitherSink, row shards allowed; nullptr = a vector variant was
+// asked for (this path has no vector kernel yet)
+const char *launch_rgb2yuv_bn(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
+                              const RgbLayout &Y, const FrameGeom &G, const float *bn, int dout, int ocsx, int ocsy, int mode);
+
 // planar float RGB sources (lutr_rgbf.hip): gbrpf32 planes in PlaneSet::s in R, G, B order.  No per-code
 // coordinate table exists for a float input, so lut3d's prelut travels as the raw table lutr_ctx_set_prelut was given and is
 // applied per pixel (FFmpeg's prelut_interp_1d_linear); LutConsts::pre is not read by these kernels.
@@ -250,6 +267,10 @@ LUTR_RGBF_DECL(w0) LUTR_RGBF_DECL(w1)
 // the dither path: k_rgbf2yuv_float, then k_dither_ed; whole frames
 const char *launch_rgbf2yuv_dither(hipStream_t st, const LutConsts &L, const FloatPre &Q, const YuvConsts &K, const PlaneSet &P,
                                    const FrameGeom &G, const FloatPlanes &F, int dout, int ocsx, int ocsy, int mode);
+
+// the blue-noise path: as launch_rgb2yuv_bn
+const char *launch_rgbf2yuv_bn(hipStream_t st, int variant, const LutConsts &L, const FloatPre &Q, const YuvConsts &K,
+                               const PlaneSet &P, const FrameGeom &G, const float *bn, int dout, int ocsx, int ocsy, int mode);
 
 // round-2 tile kernels (lutr_tile2.hip, one translation unit per format: w<in wide><out wide>_c<csx><csy>); nullptr =
 // this combination is not built / cannot take the call, the caller falls back

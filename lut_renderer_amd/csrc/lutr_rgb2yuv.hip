@@ -205,6 +205,24 @@ const char *launch_rgb2yuv_dither(hipStream_t st, const LutConsts &L, const YuvC
     return launch_dither_ed(st, K, P, G, F, dout > 8, ocsx, ocsy) ? "k_rgb2yuv_float+k_dither_ed" : nullptr;
 }
 
+// blue-noise dither: the same walk with a DitherSink; rows of any shard, no scratch
+__global__ __launch_bounds__(256) void k_rgb2yuv_bn_generic(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, RgbLayout Y,
+                                                            const float *__restrict__ bn, int wout, int ocsx, int ocsy, int mode)
+{
+    const GFetch f(L);
+    DitherSink sink{K, P, wout, bn, 0, 0};
+    for_each_block(G, ocsx, ocsy, false, [&](long long fr, int cx, int cy) { r2y_block(L, f, P, Y, G, fr, cx, cy, ocsx, ocsy, mode, sink); });
+}
+
+const char *launch_rgb2yuv_bn(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
+                              const RgbLayout &Y, const FrameGeom &G, const float *bn, int dout, int ocsx, int ocsy, int mode)
+{
+    if (variant == VAR_VEC_GLOBAL || variant == VAR_VEC_LDS) return nullptr;
+    hipLaunchKernelGGL(k_rgb2yuv_bn_generic, dim3(block_grid(G.w, G.rows, G.nframes, ocsx, ocsy)), dim3(256), 0, st, L, K, P, G, Y, bn,
+                       dout > 8, ocsx, ocsy, mode);
+    return "k_rgb2yuv_bn_generic";
+}
+
 // ================================================================= launcher
 const char *launch_rgb2yuv(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
                            const RgbLayout &Y, const FrameGeom &G, int dout, int ocsx, int ocsy, int mode)

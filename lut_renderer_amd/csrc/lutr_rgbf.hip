@@ -277,6 +277,15 @@ __global__ __launch_bounds__(256) void k_rgbf2yuv_float(LutConsts L, FloatPre Q,
     for_each_block(G, ocsx, ocsy, true, [&](long long fr, int cx, int cy) { rgbf_block(L, Q, f, P, G, fr, cx, cy, ocsx, ocsy, mode, sink); });
 }
 
+// blue-noise dither: the same walk with a DitherSink; rows of any shard, no scratch
+__global__ __launch_bounds__(256) void k_rgbf2yuv_bn_generic(LutConsts L, FloatPre Q, YuvConsts K, PlaneSet P, FrameGeom G,
+                                                             const float *__restrict__ bn, int wout, int ocsx, int ocsy, int mode)
+{
+    const GFetch f(L);
+    DitherSink sink{K, P, wout, bn, 0, 0};
+    for_each_block(G, ocsx, ocsy, false, [&](long long fr, int cx, int cy) { rgbf_block(L, Q, f, P, G, fr, cx, cy, ocsx, ocsy, mode, sink); });
+}
+
 // ================================================================= launchers
 const char *launch_rgbf(hipStream_t st, int variant, const LutConsts &L, const FloatPre &Q, const PlaneSet &P, const FrameGeom &G,
                         int mode)
@@ -313,6 +322,15 @@ const char *launch_rgbf2yuv_dither(hipStream_t st, const LutConsts &L, const Flo
 {
     hipLaunchKernelGGL(k_rgbf2yuv_float, dim3(block_grid(G.w, G.h, G.nframes, ocsx, ocsy)), dim3(256), 0, st, L, Q, K, P, G, F, ocsx, ocsy, mode);
     return launch_dither_ed(st, K, P, G, F, dout > 8, ocsx, ocsy) ? "k_rgbf2yuv_float+k_dither_ed" : nullptr;
+}
+
+const char *launch_rgbf2yuv_bn(hipStream_t st, int variant, const LutConsts &L, const FloatPre &Q, const YuvConsts &K,
+                               const PlaneSet &P, const FrameGeom &G, const float *bn, int dout, int ocsx, int ocsy, int mode)
+{
+    if (variant == VAR_VEC_GLOBAL || variant == VAR_VEC_LDS) return nullptr;
+    hipLaunchKernelGGL(k_rgbf2yuv_bn_generic, dim3(block_grid(G.w, G.rows, G.nframes, ocsx, ocsy)), dim3(256), 0, st, L, Q, K, P, G, bn,
+                       dout > 8, ocsx, ocsy, mode);
+    return "k_rgbf2yuv_bn_generic";
 }
 
 const char *launch_rgbf2yuv(hipStream_t st, int variant, const LutConsts &L, const FloatPre &Q, const YuvConsts &K, const PlaneSet &P,

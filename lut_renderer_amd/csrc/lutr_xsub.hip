@@ -19,111 +19,11 @@ namespace lutr {
 
 #ifdef LUTR_XS_WI
 // ================================================================= vector kernel, global gather
-// k_yuv_vec's structure (lutr_kernels.hip): whole-word loads and stores, VB bytes of luma per thread and row, BH luma rows per
-// thread, lattice taps gathered from L1/L2.  The thread's input chroma rows (BH >> ICSY) and output chroma rows (BH >> OCSY)
-// are separate arrays; the thread walks its union blocks one after the other.  (Frame written out: see k_yuv_vec.)
+// (the body, shared with the blue-noise kernels of lutr_bnd.hip: yuv_xsub_vec_body, lutr_device.h)
 template <int WIN, int WOUT, int ICSX, int ICSY, int OCSX, int OCSY, int INTERP>
 __global__ __launch_bounds__(256) void k_yuv_xsub_vec(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G)
 {
-    constexpr int VB = vec_bytes<WIN, WOUT>();
-    constexpr int PXT = VB / (WIN ? 2 : 1);                       // luma samples per thread per row
-    constexpr int YWI = VB / 4, YWO = PXT * (WOUT ? 2 : 1) / 4;   // luma words per thread per row, in / out
-    constexpr int CSX = cmax(ICSX, OCSX), CSY = cmax(ICSY, OCSY);
-    constexpr int BW = 1 << CSX, BH = 1 << CSY;                   // the union block
-    constexpr int NB = PXT / BW;                                  // union blocks per thread
-    constexpr int IRH = BH >> ICSY, ORH = BH >> OCSY;             // chroma rows per thread, in / out
-    constexpr int IBX = BW >> ICSX, OBX = BW >> OCSX;             // chroma samples per union block and row, in / out
-    constexpr int CWI = (PXT >> ICSX) * (WIN ? 2 : 1) / 4, CWO = (PXT >> OCSX) * (WOUT ? 2 : 1) / 4;
-    static_assert(NB >= 1 && CWI >= 1 && CWO >= 1 && YWO >= 1, "a thread must own whole words");
-    const GFetch f(L);
-    const unsigned uw = (unsigned)G.w / PXT;
-    const unsigned ub = (unsigned)G.rows >> CSY;
-    const unsigned total = uw * ub * (unsigned)G.nframes;
-    const unsigned u = blockIdx.x * 256u + threadIdx.x;
-    if (u >= total) return;
-    const unsigned xu = u % uw, t = u / uw;
-    const int y0 = ((G.row0 >> CSY) + (int)(t % ub)) * BH;        // first luma row of the thread
-    const long long fr = t / ub;
-    const long long xi = (long long)xu * VB, xo = (long long)xu * (YWO * 4), cxi = (long long)xu * (CWI * 4),
-                    cxo = (long long)xu * (CWO * 4);
-
-    uint32_t yw[BH][YWI], cbw[IRH][CWI], crw[IRH][CWI];
-    uint32_t yo[BH][YWO], cbo[ORH][CWO], cro[ORH][CWO];
-#pragma unroll
-    for (int dy = 0; dy < BH; dy++) {
-        ld_words<YWI>(yw[dy], P.s[0] + fr * P.sfs[0] + (long long)(y0 + dy) * P.ss[0] + xi);
-#pragma unroll
-        for (int k = 0; k < YWO; k++) yo[dy][k] = 0;
-    }
-#pragma unroll
-    for (int iy = 0; iy < IRH; iy++) {
-        const long long r = (long long)((y0 >> ICSY) + iy);
-        ld_words<CWI>(cbw[iy], P.s[1] + fr * P.sfs[1] + r * P.ss[1] + cxi);
-        ld_words<CWI>(crw[iy], P.s[2] + fr * P.sfs[2] + r * P.ss[2] + cxi);
-    }
-#pragma unroll
-    for (int oy = 0; oy < ORH; oy++)
-#pragma unroll
-        for (int k = 0; k < CWO; k++) { cbo[oy][k] = 0; cro[oy][k] = 0; }
-
-#pragma unroll
-    for (int j = 0; j < NB; j++) {
-        Chroma c[IRH][IBX];
-#pragma unroll
-        for (int iy = 0; iy < IRH; iy++)
-#pragma unroll
-            for (int ix = 0; ix < IBX; ix++)
-                c[iy][ix] = chroma_terms(K, word_sample<WIN>(cbw[iy], j * IBX + ix), word_sample<WIN>(crw[iy], j * IBX + ix));
-        float rs[ORH][OBX], gs[ORH][OBX], bs[ORH][OBX];
-#pragma unroll
-        for (int oy = 0; oy < ORH; oy++)
-#pragma unroll
-            for (int ox = 0; ox < OBX; ox++) { rs[oy][ox] = 0.f; gs[oy][ox] = 0.f; bs[oy][ox] = 0.f; }
-#pragma unroll
-        for (int dy = 0; dy < BH; dy++) {
-#pragma unroll
-            for (int dx = 0; dx < BW; dx++) {
-                const int i = j * BW + dx;
-                const Rgb q = yuv_to_rgb(K, word_sample<WIN>(yw[dy], i), c[dy >> ICSY][dx >> ICSX]);
-                const Rgb o = lut3d_px<INTERP>(L, f, q.r, q.g, q.b);
-                rs[dy >> OCSY][dx >> OCSX] += o.r; gs[dy >> OCSY][dx >> OCSX] += o.g; bs[dy >> OCSY][dx >> OCSX] += o.b;
-                word_put<WOUT>(yo[dy], i, rgb_to_y(K, o));
-            }
-        }
-#pragma unroll
-        for (int oy = 0; oy < ORH; oy++)
-#pragma unroll
-            for (int ox = 0; ox < OBX; ox++) {
-                word_put<WOUT>(cbo[oy], j * OBX + ox, rgb_to_cb(K, rs[oy][ox], gs[oy][ox], bs[oy][ox]));
-                word_put<WOUT>(cro[oy], j * OBX + ox, rgb_to_cr(K, rs[oy][ox], gs[oy][ox], bs[oy][ox]));
-            }
-        // Zero-instruction fence (k_yuv_vec's): keeps hipcc from hoisting the coordinates and taps of every union block of the
-        // thread to the top; with it the blocks are emitted one after the other.
-#pragma unroll
-        for (int dy = 0; dy < BH; dy++) {
-#pragma unroll
-            for (int k = 0; k < YWI; k++) asm volatile("" : "+v"(yw[dy][k]));
-#pragma unroll
-            for (int k = 0; k < YWO; k++) asm volatile("" : "+v"(yo[dy][k]));
-        }
-#pragma unroll
-        for (int iy = 0; iy < IRH; iy++)
-#pragma unroll
-            for (int k = 0; k < CWI; k++) asm volatile("" : "+v"(cbw[iy][k]), "+v"(crw[iy][k]));
-#pragma unroll
-        for (int oy = 0; oy < ORH; oy++)
-#pragma unroll
-            for (int k = 0; k < CWO; k++) asm volatile("" : "+v"(cbo[oy][k]), "+v"(cro[oy][k]));
-    }
-#pragma unroll
-    for (int dy = 0; dy < BH; dy++)
-        st_words<YWO>(P.d[0] + fr * P.dfs[0] + (long long)(y0 + dy) * P.ds[0] + xo, yo[dy]);
-#pragma unroll
-    for (int oy = 0; oy < ORH; oy++) {
-        const long long r = (long long)((y0 >> OCSY) + oy);
-        st_words<CWO>(P.d[1] + fr * P.dfs[1] + r * P.ds[1] + cxo, cbo[oy]);
-        st_words<CWO>(P.d[2] + fr * P.dfs[2] + r * P.ds[2] + cxo, cro[oy]);
-    }
+    yuv_xsub_vec_body<WIN, WOUT, ICSX, ICSY, OCSX, OCSY, INTERP, false>(L, K, P, G, nullptr);
 }
 
 // The vector kernels of this translation unit's container mix; the layout checks are the caller's (launch_yuv_xsub).
@@ -152,42 +52,8 @@ const char *LUTR_CAT(LUTR_CAT(launch_yuv_xsub_vec_w, LUTR_XS_WI), LUTR_XS_WO)(hi
 
 #else  // !LUTR_XS_WI
 // ================================================================= generic kernels
-// One thread per union block; any depth, stride or alignment, odd sizes, all five modes.  The block is walked one OUTPUT
-// chroma block at a time (its sum is then one set of three accumulators); every pixel reads the input chroma sample of its
-// own input block.  A pixel outside the frame is the edge pixel again (its luma and its chroma), so a partial output block
-// sums the edge column / row twice, like np.pad(mode="edge"); only pixels and chroma samples inside the planes are written.
-template <class Sink>
-__device__ __forceinline__ void xsub_union_block(const LutConsts &L, const GFetch &f, const YuvConsts &K, const PlaneSet &P,
-                                                 const FrameGeom &G, long long fr, int ux, int uy, int win, int icsx, int icsy,
-                                                 int ocsx, int ocsy, int mode, Sink &sink)
-{
-    const int bw = 1 << cmax(icsx, ocsx), bh = 1 << cmax(icsy, ocsy), obw = 1 << ocsx, obh = 1 << ocsy;
-    const int cwo = (G.w + obw - 1) >> ocsx, cho = (G.h + obh - 1) >> ocsy;
-    for (int oy = 0; oy < bh; oy += obh) {
-        for (int ox = 0; ox < bw; ox += obw) {
-            float rs = 0.f, gs = 0.f, bs = 0.f;
-            for (int dy = 0; dy < obh; dy++) {
-                const int yy = uy * bh + oy + dy;
-                const int y = yy < G.h ? yy : G.h - 1;
-                for (int dx = 0; dx < obw; dx++) {
-                    const int xx = ux * bw + ox + dx;
-                    const int x = xx < G.w ? xx : G.w - 1;
-                    const float cbv = ld_sample(src_row(P, 1, fr, y >> icsy), x >> icsx, win);
-                    const float crv = ld_sample(src_row(P, 2, fr, y >> icsy), x >> icsx, win);
-                    const float yv = ld_sample(src_row(P, 0, fr, y), x, win);
-                    const Rgb q = yuv_to_rgb(K, yv, chroma_terms(K, cbv, crv));
-                    const Rgb o = lut3d_px_rt(mode, L, f, q.r, q.g, q.b);
-                    rs += o.r; gs += o.g; bs += o.b;
-                    if (yy < G.h && xx < G.w) sink.luma(fr, x, y, o);
-                }
-            }
-            const int ocx = (ux * bw + ox) >> ocsx, ocy = (uy * bh + oy) >> ocsy;
-            if (ocx < cwo && ocy < cho) sink.chroma(fr, ocx, ocy, rs, gs, bs);
-        }
-    }
-}
-
-// (the walk over union blocks and the sinks: lutr_device.h)
+// One thread per union block; any depth, stride or alignment, odd sizes, all five modes.
+// (the walk over union blocks, the block body xsub_union_block and the sinks: lutr_device.h)
 __global__ __launch_bounds__(256) void k_yuv_xsub_generic(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, int win, int wout,
                                                           int icsx, int icsy, int ocsx, int ocsy, int mode)
 {

@@ -911,6 +911,8 @@ class LutEngine:
         same subsampling on both sides, no dither / chroma_loc / out_size, strict arithmetic, `dst` may be `src` when the two
         formats are the same.  The bits are those of the planar call on the same samples.
         dither="error_diffusion" (the reference's `zscale_dither`) dithers the final quantisation; whole frames only.
+        dither="blue_noise" (an engine setting) quantises every output sample against a 64 x 64 void-and-cluster
+        mask anchored to the frame, inside the LUT pass: any layout pair, row0 / rows as without dither, strict arithmetic.
         chroma_loc ("left" | "center" | "topleft", ffprobe's chroma_location names) resamples chroma bilinearly at that
         siting instead of replicating it (strict arithmetic, not in place, no dither).  None = replicate.
         `out_pix_fmt` may change the chroma subsampling (4:2:0 / 4:2:2 / 4:4:4 either way): input chroma is
@@ -949,11 +951,11 @@ class LutEngine:
         _check_planes(dst, fout, w, h, "destination")
         s, d, nf = _plane_pair(src, dst, self.device)
         rows = h - row0 if rows is None else rows
-        if dither != "none" and (row0 != 0 or rows != h):
+        if dither == "error_diffusion" and (row0 != 0 or rows != h):
             raise ValueError("error-diffusion dither couples the rows of a frame: whole frames only")
         with self._lock:
             self._bind_stream()
-            if xsub:
+            if xsub or dither == "blue_noise":
                 _native.check(self._lib.lutr_apply_yuv_xsub(
                     self._ctx, C.byref(p), _native.INTERP[interp], _native.DITHER[dither], w, h, nf, C.byref(s), C.byref(d),
                     row0, rows))
@@ -1137,7 +1139,7 @@ class LutEngine:
         if nf != nfd:
             raise ValueError("src and dst disagree on the number of frames")
         rows = h - row0 if rows is None else rows
-        if dither != "none" and (row0 != 0 or rows != h):
+        if dither == "error_diffusion" and (row0 != 0 or rows != h):
             raise ValueError("error-diffusion dither couples the rows of a frame: whole frames only")
         _check_not_in_place([src] if fin.packed else src[:3], dst, _RGB2YUV_IN_PLACE)
         p = _yuv_params(_native.fmt_code(fin.depth, 0, 0), fout.code, fin.depth, matrix_out, matrix_out, range_out, range_out,

@@ -33,6 +33,14 @@ from .engine import (LutEngine, _new_planes, _yuv_out_dtype, check_container_opt
 from .shard import row_blocks
 
 
+def _bn_anchor(r0: int, ocsy: int) -> int:
+    """The last luma row at or above `r0` where the blue-noise pattern of every output plane starts over: a
+    multiple of the mask's 64 rows in luma and, with chroma rows subsampled by 2^ocsy, in chroma.  A slice of the frame that
+    begins there and is processed as a frame of its own gets the pattern of the full frame."""
+    period = 64 << ocsy
+    return r0 // period * period
+
+
 class LutEngineGroup:
     """Contexts on `devices` (repeats allowed: two contexts on one GPU split its frames in two launches)."""
 
@@ -124,14 +132,14 @@ class LutEngineGroup:
                    out_pix_fmt: Optional[str] = None, **kw):
         """`LutEngine.apply_yuv` with the rows of every frame split over the group's devices.
         `src` planes live on one device (any); `dst`, if given, on the same one."""
-        if kw.get("dither", "none") != "none":
+        if kw.get("dither", "none") == "error_diffusion":
             raise ValueError("error-diffusion dither couples the rows of a frame: it cannot be row-sharded")
         if "row0" in kw or "rows" in kw:
             raise ValueError("the group owns the row partition")
         # a semi-planar side (DESIGN.md 3.11) is two planes, the second with the chroma plane's rows: the shard rule is unchanged.
         # A packed 4:2:2 side (3.12) is one buffer with the frame's rows -- any row for a 4:2:2 destination, even rows for a
         # planar 4:2:0 one, which is the union block rule below
-        kind = check_container_options(pix_fmt, out_pix_fmt, "none", kw.get("chroma_loc"), kw.get("out_size"))
+        kind = check_container_options(pix_fmt, out_pix_fmt, kw.get("dither", "none"), kw.get("chroma_loc"), kw.get("out_size"))
         if kind is None:
             fin, fout = parse_pix_fmt(pix_fmt), parse_pix_fmt(out_pix_fmt or pix_fmt)
         else:
@@ -182,6 +190,19 @@ class LutEngineGroup:
                     full = eng.apply_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0 - h0 * bh, rows=r1 - r0,
                                          **kw)
                     out = [o[..., a - sa:b - sa, :] for o, (a, b), (sa, _) in zip(full, rng, srng)]
+                self.last_remote += 1
+                pending.append((out, rng))
+                continue
+            if kw.get("dither", "none") == "blue_noise":
+                # the mask is anchored to the frame's top: the slice that travels starts at a row where the
+                # pattern of every output plane starts over, and the apply writes the block's rows inside it
+                h0 = _bn_anchor(r0, fout.csy)
+                srng = [(h0, r1), (h0 >> fin.csy, c1), (h0 >> fin.csy, c1)]
+                with torch.cuda.device(eng.device):
+                    part = [p[..., a:b, :].to(eng.device, non_blocking=True, copy=True).contiguous()
+                            for p, (a, b) in zip(src, srng)]
+                    full = eng.apply_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0 - h0, rows=r1 - r0, **kw)
+                    out = [o[..., a - sa:b - sa, :] for o, (a, b), sa in zip(full, rng, (h0, h0 >> fout.csy, h0 >> fout.csy))]
                 self.last_remote += 1
                 pending.append((out, rng))
                 continue
@@ -244,7 +265,7 @@ class LutEngineGroup:
         multiples of the output chroma block height, every source plane (or the packed image) counted in luma rows, no halo.
         Float sources (gbrpf32le / gbrapf32le) shard the same way."""
         with self._lock:
-            if kw.get("dither", "none") != "none":
+            if kw.get("dither", "none") == "error_diffusion":
                 raise ValueError("error-diffusion dither couples the rows of a frame: it cannot be row-sharded")
             if "row0" in kw or "rows" in kw:
                 raise ValueError("the group owns the row partition")
@@ -278,11 +299,17 @@ class LutEngineGroup:
                     eng.apply_rgb_to_yuv(src, dst, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0, rows=r1 - r0, **kw)
                     continue
                 o0, o1 = r0 >> fout.csy, (r1 + (1 << fout.csy) - 1) >> fout.csy
+                # (blue-noise dither: the slice starts where the pattern of every output plane starts over, as in _apply_yuv)
+                h0 = _bn_anchor(r0, fout.csy) if kw.get("dither", "none") == "blue_noise" else r0
                 with torch.cuda.device(eng.device):
-                    part = rows_of(r0, r1)
+                    part = rows_of(h0, r1)
                     part = part.to(eng.device, non_blocking=True, copy=True).contiguous() if fin.packed else \
                         [p.to(eng.device, non_blocking=True, copy=True).contiguous() for p in part]
-                    out = eng.apply_rgb_to_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, **kw)
+                    if h0 == r0:
+                        out = eng.apply_rgb_to_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, **kw)
+                    else:
+                        full = eng.apply_rgb_to_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0 - h0, rows=r1 - r0, **kw)
+                        out = [o[..., a - sa:, :] for o, a, sa in zip(full, (r0, o0, o0), (h0, h0 >> fout.csy, h0 >> fout.csy))]
                 self.last_remote += 1
                 pending.append((out, [(r0, r1), (o0, o1), (o0, o1)]))
             for out, rng in pending:                               # copies back: queued after every launch was issued

@@ -46,14 +46,16 @@ class StageCommands:
 
 def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, lut_path: Path, source_info: VideoInfo,
                           ffmpeg_bin: str = "ffmpeg", python_bin: Optional[str] = None, device: int = 0,
-                          precision: str = "strict", chroma_loc: Optional[str] = None, gpu_resize: bool = False) -> StageCommands:
+                          precision: str = "strict", chroma_loc: Optional[str] = None, gpu_resize: bool = False,
+                          engine_dither: Optional[str] = None) -> StageCommands:
     """The three argv lists of one LUT stage.  Raises what `build_command` / `engine_command` raise (copy guard, missing
     geometry).  `chroma_loc` goes to the engine (`--chroma-loc`) and, as `-chroma_sample_location`, to the encoder, so the
     output stream declares the siting the engine assumed.  `gpu_resize` with `params.resolution` set resizes in the engine
-    (`--out-size`): the raw input's `-s` is then the target size and the encoder's own `-s` is dropped."""
+    (`--out-size`): the raw input's `-s` is then the target size and the encoder's own `-s` is dropped.  `engine_dither` goes to
+    the engine (`--engine-dither`)."""
     notes: List[str] = []
     engine = engine_command(Path("-"), Path("-"), params, lut_path, source_info, python_bin=python_bin, device=device, notes=notes,
-                            precision=precision, chroma_loc=chroma_loc, gpu_resize=gpu_resize)
+                            precision=precision, chroma_loc=chroma_loc, gpu_resize=gpu_resize, engine_dither=engine_dither)
     resized = gpu_resize and bool(params.resolution)
     if source_info.duration:
         engine += ["--duration", f"{float(source_info.duration):.3f}"]
@@ -140,13 +142,15 @@ def main(argv=None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--precision", default="strict", choices=["strict", "fast", "fma32"], help="engine setting, see lut_renderer_amd.cli")
     ap.add_argument("--chroma-loc", default=None, choices=["left", "center", "topleft"], help="engine setting, see lut_renderer_amd.cli")
+    ap.add_argument("--engine-dither", default=None, choices=["blue_noise"], help="engine setting, see lut_renderer_amd.cli")
     ap.add_argument("--gpu-resize", action="store_true", help="resize to the params' resolution in the engine (--out-size) instead of the encoder")
     a = ap.parse_args(argv)
     try:
         params = ProcessingParams.from_dict(json.loads(a.params))
         info = VideoInfo(**json.loads(a.info))
         cmds = engine_stage_commands(Path(a.input), Path(a.output), params, Path(a.cube), info, ffmpeg_bin=a.ffmpeg, device=a.device,
-                                     precision=a.precision, chroma_loc=a.chroma_loc, gpu_resize=a.gpu_resize)
+                                     precision=a.precision, chroma_loc=a.chroma_loc, gpu_resize=a.gpu_resize,
+                                     engine_dither=a.engine_dither)
     except Exception as exc:
         print(f"Error: {exc}", flush=True)
         return 1
