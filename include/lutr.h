@@ -550,6 +550,57 @@ int lutr_apply_yuv_v210(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int
 int lutr_apply_yuv_dual(lutr_ctx *ctx, const lutr_yuv_params *p, int fmt_out2, int interp, int w, int h, int nframes,
                         const lutr_planes *src, const lutr_planes *dst, const lutr_planes *dst2, int row0, int rows);
 
+/* ---- the alpha plane of yuva* / gbrap* frames: ProRes 4444 (yuva444p10le / 12le), VP8 / VP9 with alpha
+ *      (yuva420p), PNG / TIFF / EXR sequences with alpha (rgba, rgba64le, gbrap*, gbrapf32le).  In the reference's chain lut3d
+ *      copies the alpha plane through and format=<pix_fmt> keeps, converts, drops or makes it (ffmpeg.py:246, :304-310) ---- */
+enum lutr_alpha_kind {
+    LUTR_ALPHA_NONE  = 0,    /* the source has no alpha: the destination plane is filled with 2^dout - 1 (opaque) */
+    LUTR_ALPHA_INT   = 1,    /* integer samples at `depth` bits: uint8 for depth 8, else uint16 LE */
+    LUTR_ALPHA_FLOAT = 2     /* 32-bit float samples, 1.0 = opaque (gbrapf32le) */
+};
+/* Where the alpha samples of a frame (or a batch) are.  Sample x of row y of frame f is element x * step + offset of the row at
+ * data + f * frame_stride + y * stride; an element is 1 byte (LUTR_ALPHA_INT, depth 8), 2 bytes (depth 9..16) or 4 bytes
+ * (LUTR_ALPHA_FLOAT).  A plane has step 1, offset 0; the A of a packed rgba / bgra image has step 4, offset 3, of argb / abgr
+ * step 4, offset 0, of rgba64le / bgra64le step 4, offset 3 at depth 16.  With LUTR_ALPHA_NONE only `kind` is read. */
+typedef struct lutr_alpha_src {
+    int32_t     kind;            /* enum lutr_alpha_kind */
+    int32_t     depth;           /* LUTR_ALPHA_INT: 8..16 */
+    const void *data;
+    ptrdiff_t   stride;          /* bytes between rows */
+    int64_t     frame_stride;    /* bytes between frames of a batch (ignored when nframes == 1) */
+    int32_t     step;            /* elements between two samples of a row, >= 1 */
+    int32_t     offset;          /* element index of the sample inside its pixel, 0 .. step - 1 */
+} lutr_alpha_src;
+
+/* Writes rows [row0, row0 + rows) of the alpha plane `dst` (w x h samples at `dout` bits, 8 -> uint8, 9..16 -> uint16 LE; dst_stride
+ * / dst_frame_stride in bytes) of each of nframes frames; rows outside the range are not written.  Alpha and colour are
+ * independent: nothing of a context's lattice, precision, matrices, ranges or dither reaches this call, alpha is never dithered and
+ * is treated as straight (a premultiplied source keeps its alpha while the LUT runs on its premultiplied colour, as ffmpeg's
+ * chain gives it).  No lattice is needed.
+ *   LUTR_ALPHA_INT, depth == dout: the words are copied as they are.
+ *   LUTR_ALPHA_INT, depth != dout: with Mi = 2^depth - 1, Mo = 2^dout - 1: a = min(word, Mi), a' = floor((2 a Mo + Mi) / (2 Mi)) --
+ *     the nearest code (Mi is odd: no ties); 0 -> 0, Mi -> Mo, monotone, 8 -> 16 bit is a * 257, up then down is the identity.
+ *   LUTR_ALPHA_FLOAT: q = clip(rintf(a * (float)Mo), 0, Mo): one fp32 multiply, round half to even, NaN -> 0 by its bit pattern.
+ *   LUTR_ALPHA_NONE: every sample is Mo.
+ * The source plane as the destination plane (same pointer, strides and depth, step 1) is allowed and does nothing (the last
+ * kernel is then "k_alpha_nop").  Any other overlap of the two bounding byte ranges (all rows and frames) is LUTR_EINVAL.
+ * LUTR_EINVAL with a message, before anything touches the device: a null context, descriptor or destination, a null source
+ * pointer with a kind other than LUTR_ALPHA_NONE, a kind outside 0..2, depth or dout outside 8..16, step < 1 or offset outside
+ * 0 .. step - 1, 16-bit samples whose base, stride or (batches) frame stride is odd, float samples not 4-byte aligned, negative
+ * sizes or rows outside the frame, overlap other than the no-op.
+ * Kernels: "k_alpha_vec<src,wout>" (src 0 = 8-bit, 1 = 16-bit, 2 = float source words, wout = 16-bit destination words; a plane
+ * source (step 1); width a multiple of 8 samples, 16 for 8 -> 8 bit; positive strides; both planes aligned to what a thread moves:
+ * 16 bytes on a 16-bit or float side, 8 on an 8-bit side next to one of those, 16 for 8 -> 8 bit; fewer than 2^31 units),
+ * "k_alpha_generic" for everything else (one sample per thread; any stride, negative included, any alignment allowed above, odd
+ * sizes, packed sources); a ragged width on aligned rows is split between the two; "k_alpha_fill" for LUTR_ALPHA_NONE (16-byte
+ * stores under the vector kernel's conditions on the destination, one sample per thread otherwise, split likewise).
+ * Variants: auto and generic as for lutr_apply_yuv; vec_global fails with LUTR_EINVAL where the vector kernel cannot take the
+ * layout; vec_lds always fails with LUTR_EINVAL (there is no LDS kernel for this path).  Asynchronous on the context's stream.
+ * Not covered: unpremultiply / premultiply, an alpha resize, alpha inside semi-planar / packed YUV / v210 containers (ayuv64le,
+ * vuya), a float alpha destination. */
+int lutr_alpha_plane(lutr_ctx *ctx, const lutr_alpha_src *src, int dout, void *dst, ptrdiff_t dst_stride, int64_t dst_frame_stride,
+                     int w, int h, int nframes, int row0, int rows);
+
 /* ---- precision ---- */
 /* STRICT (default): every kernel is a bit-exact restatement of FFmpeg's scalar C lut3d (vf_lut3d.c order of operations,
  * no fused multiply-add in the blend).  FAST: permission to use the tolerance-bounded tile kernels -- lattice staged as

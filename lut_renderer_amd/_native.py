@@ -41,7 +41,7 @@ SYMBOLS = (
     "lutr_apply_yuv_sited", "lutr_yuv_constants_sited", "lutr_apply_yuv_xsub", "lutr_yuv_constants_xsub",
     "lutr_apply_rgb_to_yuv", "lutr_yuv_constants_rgb2yuv",
     "lutr_apply_planar_rgb_f32", "lutr_apply_rgbf_to_yuv", "lutr_apply_yuv_semi", "lutr_apply_yuv_packed",
-    "lutr_apply_yuv_dual", "lutr_apply_yuv_v210",
+    "lutr_apply_yuv_dual", "lutr_apply_yuv_v210", "lutr_alpha_plane",
     "lutr_resize_filter", "lutr_resize_planes", "lutr_dither_mask",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
 )
@@ -78,6 +78,16 @@ class Packed(C.Structure):
     _fields_ = [("data", C.c_void_p), ("stride", C.c_ssize_t), ("frame_stride", C.c_int64)]
 
 
+class AlphaSrc(C.Structure):
+    """struct lutr_alpha_src: where the alpha samples of lutr_alpha_plane's source are"""
+    _fields_ = [("kind", C.c_int32), ("depth", C.c_int32), ("data", C.c_void_p), ("stride", C.c_ssize_t),
+                ("frame_stride", C.c_int64), ("step", C.c_int32), ("offset", C.c_int32)]
+
+
+#: enum lutr_alpha_kind
+ALPHA_NONE, ALPHA_INT, ALPHA_FLOAT = 0, 1, 2
+
+
 def packed_code(bits: int, ncomp: int, ro: int, go: int, bo: int) -> int:
     """LUTR_PACKED(bits, ncomp, ro, go, bo)"""
     return bits | (ncomp << 8) | (ro << 12) | (go << 16) | (bo << 20)
@@ -91,6 +101,11 @@ PACKED_FORMATS = {
     "rgb48le": (16, 3, 0, 1, 2), "bgr48le": (16, 3, 2, 1, 0),
     "rgba64le": (16, 4, 0, 1, 2), "bgra64le": (16, 4, 2, 1, 0),
 }
+
+
+#: the packed RGB names whose fourth component is a real alpha -> its component index; the pad byte of rgb0 / bgr0 /
+#: 0rgb / 0bgr is not alpha
+PACKED_ALPHA = {"rgba": 3, "bgra": 3, "argb": 0, "abgr": 0, "rgba64le": 3, "bgra64le": 3}
 
 
 #: semi-planar YUV formats -> (depth, csx, csy, swap: Cr first, shift of the code inside its container)
@@ -186,6 +201,7 @@ def load() -> C.CDLL:
     lib.lutr_apply_yuv_v210.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_apply_yuv_dual.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes),
                                         C.POINTER(Planes), ci, ci]
+    lib.lutr_alpha_plane.argtypes = [vp, C.POINTER(AlphaSrc), ci, vp, C.c_ssize_t, C.c_int64, ci, ci, ci, ci, ci]
     lib.lutr_dither_mask.argtypes = [C.POINTER(C.c_uint16)]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]

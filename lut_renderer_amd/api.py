@@ -79,7 +79,9 @@ def _cached_cube(path: Path) -> CubeLut:
 
 
 def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = None) -> dict:
-    """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv (`pix_fmt` / `out_pix_fmt` planar YUV, semi-planar names
+    """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv (`pix_fmt` / `out_pix_fmt` planar YUV -- yuva* too, DESIGN.md
+    3.16: without `out_pix_fmt` the source's format, alpha included, is kept; a named output without alpha drops it, one with alpha
+    on a source without is filled opaque; the full-range prologue's default output stays the 8-bit yuv4xxp -- , semi-planar names
     such as nv12 / p010le, DESIGN.md 3.11, or packed 4:2:2 names such as uyvy422 / y210le; `out_pix_fmt` defaults
     to the source's own format) -- or, for an RGB `pix_fmt` (gbrp* / a packed name / a
     float name) with a YUV `out_pix_fmt`, of LutEngine.apply_rgb_to_yuv (`is_rgb_call(kw)` tells the two apart).  A float
@@ -228,6 +230,12 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     that size on the GPU after everything else, and `out` must have that size.  One device only (no
     LutEngineGroup): a row-sharded resize would need halos between the devices.
 
+    An alpha-carrying `pix_fmt` / `out_pix_fmt` (yuva420p .. yuva444p16le, gbrap .. gbrap16le) makes that side FOUR
+    planes, the last one alpha at the luma size and the format's depth.  Alpha never meets the LUT: it is copied, converted to the
+    output depth (nearest code), dropped when `out_pix_fmt` has none, or filled opaque when only `out_pix_fmt` has it; it is
+    treated as straight (a premultiplied source gets the LUT on its premultiplied colour, as in ffmpeg's chain).  Planar sides
+    only; `resolution` with an alpha-carrying output is a ValueError.
+
     `second_pix_fmt` asks for a SECOND planar YUV output from the same pass (the reference's "pro" mode: the
     yuv422p10le master and the delivery format): the return value is then ((planes_out, planes_out2), tags), and `out`, if
     given, is the pair (planes, planes2).  Planar YUV on all three sides; no RGB / float / semi-planar / packed side, no dither,
@@ -269,6 +277,8 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     # lattice has none)
     plan = resolve_lut_plan(params, cube if isinstance(cube, (str, Path)) else "engine.cube", info)
     kw = engine_call_for(plan, pix_fmt, out_pix_fmt)
+    from .engine import refuse_alpha_resize
+    refuse_alpha_resize(kw.get("out_pix_fmt"), out_size)        # (the resize takes three planes)
     # ffmpeg.py:305-307: any value other than "error_diffusion" leaves the chain without a dither filter
     kw["dither"] = "error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none"
     if engine_dither is not None:

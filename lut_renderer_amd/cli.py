@@ -43,7 +43,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("-o", "--output", required=True)
     ap.add_argument("--size", required=True, help="WxH")
     ap.add_argument("--pix-fmt", required=True,
-                    help="planar YUV, semi-planar YUV (nv12, nv21, nv16, p010le .. p216le), packed 4:2:2 YUV (yuyv422, uyvy422, yvyu422, y210le, y212le, y216le), v210 (10-bit 4:2:2 in 32-bit words, rows of 128 * ceil(w / 48) bytes; in FFmpeg a codec / FourCC name, not a pix_fmt: its bytes are what `-c:v v210 -f rawvideo` writes), or an RGB source (gbrp* / rgb24, bgr24, rgba .., rgb48le, rgba64le) with a YUV --out-pix-fmt, "
+                    help="planar YUV (yuva* too: four planes, alpha last, kept unless --out-pix-fmt has none), semi-planar YUV (nv12, nv21, nv16, p010le .. p216le), packed 4:2:2 YUV (yuyv422, uyvy422, yvyu422, y210le, y212le, y216le), v210 (10-bit 4:2:2 in 32-bit words, rows of 128 * ceil(w / 48) bytes; in FFmpeg a codec / FourCC name, not a pix_fmt: its bytes are what `-c:v v210 -f rawvideo` writes), or an RGB source (gbrp* / gbrap* / rgb24, bgr24, rgba .., rgb48le, rgba64le) with a YUV --out-pix-fmt, "
                          "or float RGB (gbrpf32le / gbrapf32le): float out without --out-pix-fmt, else a YUV one")
     ap.add_argument("--out-pix-fmt", default=None)
     ap.add_argument("--cube", required=True)
@@ -113,8 +113,9 @@ def plan_from_args(args):
         check_chroma_loc(args.chroma_loc, kw.get("dither", "none"), kw["pix_fmt"], kw["out_pix_fmt"])
         kw["chroma_loc"] = args.chroma_loc
     if getattr(args, "out_size", None):
-        from .engine import parse_size
+        from .engine import parse_size, refuse_alpha_resize
         parse_size(args.out_size)
+        refuse_alpha_resize(kw.get("out_pix_fmt"), args.out_size)
     second_out, second_fmt = getattr(args, "second_output", None), getattr(args, "second_pix_fmt", None)
     if (second_out is None) != (second_fmt is None):
         raise ValueError("--second-output and --second-pix-fmt go together: give both or neither")

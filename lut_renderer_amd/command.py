@@ -347,10 +347,10 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
 
 
 def _is_rgb_source(pix_fmt) -> bool:
-    """gbrp* or one of the packed RGB names the engine takes as a source (`_native.PACKED_FORMATS`)."""
+    """gbrp* / gbrap* or one of the packed RGB names the engine takes as a source (`_native.PACKED_FORMATS`)."""
     from ._native import PACKED_FORMATS
     name = str(pix_fmt or "")
-    return name in PACKED_FORMATS or bool(re.match(r"^gbrp(\d+)?(le)?$", name))
+    return name in PACKED_FORMATS or bool(re.match(r"^gbra?p(\d+)?(le)?$", name))
 
 
 def _is_float_source(pix_fmt) -> bool:

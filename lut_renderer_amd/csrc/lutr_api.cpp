@@ -1625,6 +1625,67 @@ int lutr_apply_rgbf_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, in
     return finish_launch(c, launch_rgbf2yuv_dither(c->stream, L, Q, K, P, G, F, dout, ocsx, ocsy, interp));
 }
 
+int lutr_alpha_plane(lutr_ctx *c, const lutr_alpha_src *src, int dout, void *dst, ptrdiff_t dst_stride, int64_t dst_frame_stride,
+                     int w, int h, int nframes, int row0, int rows)
+{
+    if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
+    const int kind = src->kind;
+    if (kind != LUTR_ALPHA_NONE && kind != LUTR_ALPHA_INT && kind != LUTR_ALPHA_FLOAT) {
+        set_error("unknown alpha source kind %d", kind);
+        return LUTR_EINVAL;
+    }
+    if (dout < 8 || dout > 16) { set_error("unsupported alpha depth %d on the destination", dout); return LUTR_EINVAL; }
+    if (kind == LUTR_ALPHA_INT && (src->depth < 8 || src->depth > 16)) {
+        set_error("unsupported alpha depth %d on the source", (int)src->depth);
+        return LUTR_EINVAL;
+    }
+    if (w < 0 || h < 0 || nframes < 0 || row0 < 0 || rows < 0 || row0 + rows > h) {
+        set_error("bad geometry w=%d h=%d nframes=%d row0=%d rows=%d", w, h, nframes, row0, rows);
+        return LUTR_EINVAL;
+    }
+    const int din = kind == LUTR_ALPHA_INT ? src->depth : 0;
+    const long long sb = kind == LUTR_ALPHA_FLOAT ? 4 : din > 8 ? 2 : 1, db = dout > 8 ? 2 : 1;
+    if (kind != LUTR_ALPHA_NONE) {
+        if (!src->data) { set_error("null alpha source plane"); return LUTR_EINVAL; }
+        if (src->step < 1 || src->offset < 0 || src->offset >= src->step) {
+            set_error("bad alpha source step %d / offset %d", (int)src->step, (int)src->offset);
+            return LUTR_EINVAL;
+        }
+        if (!check_aligned(src->data, src->stride, src->frame_stride, nframes, (unsigned)sb - 1)) {
+            set_error(kind == LUTR_ALPHA_FLOAT ? "float alpha planes need 4-byte aligned base pointers and strides"
+                                               : "16-bit alpha planes need 2-byte aligned base pointers and strides");
+            return LUTR_EINVAL;
+        }
+    }
+    if (!check_aligned(dst, dst_stride, dst_frame_stride, nframes, (unsigned)db - 1)) {
+        set_error("16-bit alpha planes need 2-byte aligned base pointers and strides");
+        return LUTR_EINVAL;
+    }
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    if (kind != LUTR_ALPHA_NONE) {
+        const bool same = kind == LUTR_ALPHA_INT && din == dout && src->step == 1 && src->data == dst && src->stride == dst_stride &&
+                          (nframes == 1 || src->frame_stride == dst_frame_stride);
+        if (same) { c->last_kernel = "k_alpha_nop"; return LUTR_OK; }
+        const Span s = plane_span(src->data, src->stride, src->frame_stride, h, (long long)w * src->step * sb, nframes);
+        const Span d = plane_span(dst, dst_stride, dst_frame_stride, h, (long long)w * db, nframes);
+        if (s.lo < d.hi && d.lo < s.hi) {
+            set_error("the alpha source overlaps the alpha destination other than as the same plane at the same depth (bounding "
+                      "byte ranges over all rows and frames must be disjoint)");
+            return LUTR_EINVAL;
+        }
+    }
+    AlphaArgs A{};
+    if (!alpha_consts(&A, kind, din, dout)) { set_error("no alpha multiplier for %d -> %d bit", din, dout); return LUTR_EINVAL; }
+    A.s = kind == LUTR_ALPHA_NONE ? nullptr : (const uint8_t *)src->data;
+    A.d = (uint8_t *)dst;
+    A.ss = kind == LUTR_ALPHA_NONE ? 0 : src->stride; A.ds = dst_stride;
+    A.sfs = kind == LUTR_ALPHA_NONE ? 0 : src->frame_stride; A.dfs = dst_frame_stride;
+    A.step = kind == LUTR_ALPHA_NONE ? 1 : src->step;
+    A.off = kind == LUTR_ALPHA_NONE ? 0 : src->offset;
+    HIP_TRY(hipSetDevice(c->device));
+    return finish_launch(c, launch_alpha(c->stream, c->variant, A, FrameGeom{w, h, row0, rows, nframes}));
+}
+
 int lutr_dither_mask(uint16_t out[4096])
 {
     if (!out) { set_error("lutr_dither_mask: null out pointer"); return LUTR_EINVAL; }

@@ -272,6 +272,24 @@ const char *launch_rgbf2yuv_dither(hipStream_t st, const LutConsts &L, const Flo
 const char *launch_rgbf2yuv_bn(hipStream_t st, int variant, const LutConsts &L, const FloatPre &Q, const YuvConsts &K,
                                const PlaneSet &P, const FrameGeom &G, const float *bn, int dout, int ocsx, int ocsy, int mode);
 
+// the alpha plane of yuva* / gbrap* frames (lutr_alpha.hip): one plane in (none for a fill), one plane out
+struct AlphaArgs {
+    const uint8_t *s;                // nullptr with kind 0
+    uint8_t       *d;
+    long long ss, ds, sfs, dfs;      // row / frame strides, bytes
+    int kind;                        // LUTR_ALPHA_NONE (fill) | LUTR_ALPHA_INT | LUTR_ALPHA_FLOAT
+    int swide, wout;                 // 16-bit words on the integer source / on the destination
+    int step, off;                   // source sample of pixel x: element x * step + off of its row (a plane: 1, 0)
+    int copy;                        // integer source at the destination's depth: the words are copied
+    unsigned mi, mo;                 // 2^din - 1 (integer source), 2^dout - 1
+    unsigned long long k;            // a' = (min(word, mi) * k + 2^39) >> 40
+    float mof;                       // (float)mo
+};
+// fills everything of A but the planes and step / off; false = no multiplier passed the host's check of the depth pair
+bool alpha_consts(AlphaArgs *A, int kind, int din, int dout);
+// nullptr = the variant cannot take the call (vec_lds always; vec_global on layouts the vector kernel cannot take)
+const char *launch_alpha(hipStream_t st, int variant, const AlphaArgs &A, const FrameGeom &G);
+
 // round-2 tile kernels (lutr_tile2.hip, one translation unit per format: w<in wide><out wide>_c<csx><csy>); nullptr =
 // this combination is not built / cannot take the call, the caller falls back
 #define LUTR_T2_DECL(tag) \

@@ -23,7 +23,7 @@ import torch
 from . import _native
 from .cube import CubeLut, read_cube, read_lut
 
-_PIXFMT_RE = re.compile(r"^(yuvj?|gbr)(420|422|444)?p(\d+)?(le)?$")
+_PIXFMT_RE = re.compile(r"^(yuvj?|yuva|gbra?)(420|422|444)?p(\d+)?(le)?$")
 
 
 class _YuvSide:
@@ -66,11 +66,21 @@ class PixFmt(_YuvSide):
     csx: int
     csy: int
     full_range: bool  # yuvj* (legacy full-range marker, media_info.py:145-147)
+    alpha: bool = False  # yuva* / gbrap*: a fourth, luma-sized plane at the same depth
 
-    nplanes = 3
+    @property
+    def nplanes(self) -> int:
+        return 4 if self.alpha else 3
+
+    @property
+    def colour(self) -> "PixFmt":
+        """The three-plane format of the same colour planes (yuva420p10le -> yuv420p10le, gbrap -> gbrp); itself without alpha."""
+        if not self.alpha:
+            return self
+        return parse_pix_fmt(self.name.replace("yuva", "yuv", 1).replace("gbrap", "gbrp", 1))
 
     def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
-        if self.family == "gbr" or plane == 0:
+        if self.family == "gbr" or plane in (0, 3):
             return h, w
         return (h + (1 << self.csy) - 1) >> self.csy, (w + (1 << self.csx) - 1) >> self.csx
 
@@ -227,6 +237,8 @@ def check_container_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: st
         if packed and (parse_semi_fmt(pix_fmt) is not None or parse_semi_fmt(out_name) is not None):
             raise ValueError(f"a semi-planar side together with a packed side is not supported ('{pix_fmt}' -> '{out_name}')")
         a, b = yuv_side(pix_fmt), yuv_side(out_name)
+        if getattr(a, "alpha", False) or getattr(b, "alpha", False):
+            raise ValueError(f"alpha is carried between planar sides only, not with a {noun} side ('{pix_fmt}' -> '{out_name}')")
         if a.family != "yuv" or b.family != "yuv":
             raise ValueError(f"{noun} frames go with YUV formats on both sides "
                              f"('{pix_fmt}' -> '{out_name if packed or v210 else out_pix_fmt}')")
@@ -302,14 +314,14 @@ def parse_pix_fmt(name: str) -> PixFmt:
     depth_i = int(depth) if depth else 8
     if not 8 <= depth_i <= 16:
         raise ValueError(f"unsupported bit depth in '{name}'")
-    if fam == "gbr":
+    if fam in ("gbr", "gbra"):
         if sub:
             raise ValueError(f"unsupported pixel format '{name}'")
-        return PixFmt(name, "gbr", depth_i, 0, 0, True)
+        return PixFmt(name, "gbr", depth_i, 0, 0, True, fam == "gbra")
     if not sub:
         raise ValueError(f"unsupported pixel format '{name}'")
     csx, csy = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}[sub]
-    return PixFmt(name, "yuv", depth_i, csx, csy, fam == "yuvj")
+    return PixFmt(name, "yuv", depth_i, csx, csy, fam == "yuvj", fam == "yuva")
 
 
 @dataclass(frozen=True)
@@ -322,7 +334,13 @@ class RgbSource:
     ncomp: int        # components per pixel of a packed image; 1 for planar
     code: int         # src_kind of lutr_apply_rgb_to_yuv: 0 planar, else LUTR_PACKED(...)
     floating: bool = False   # 32-bit float planes: lutr_apply_planar_rgb_f32 / lutr_apply_rgbf_to_yuv
-    nplanes: int = 3         # planes per frame of a planar source (gbrapf32le: 4, the last one alpha)
+    nplanes: int = 3         # planes per frame of a planar source (gbrap*, gbrapf32le: 4, the last one alpha)
+
+    @property
+    def alpha_slot(self) -> Optional[int]:
+        """The component index of a packed format's real alpha (rgba: 3, argb: 0), None for every other format -- rgb0's pad byte
+        is not alpha."""
+        return _native.PACKED_ALPHA.get(self.name) if self.packed else None
 
     @property
     def itemsize(self) -> int:
@@ -344,7 +362,7 @@ def parse_rgb_source(name: Optional[str]) -> Optional[RgbSource]:
         fmt = parse_pix_fmt(name)
     except ValueError:
         return None
-    return RgbSource(name, False, fmt.depth, 1, 0) if fmt.family == "gbr" else None
+    return RgbSource(name, False, fmt.depth, 1, 0, False, fmt.nplanes) if fmt.family == "gbr" else None
 
 
 def chroma_loc_code(chroma_loc: Optional[str]) -> int:
@@ -426,8 +444,8 @@ def dual_args(src, dst, dst2, pix_fmt, out_pix_fmt, out2_pix_fmt):
     """What `apply_yuv_dual` checks of its formats and planes before it touches the engine: the three formats, and the shapes
     and dtypes of the planes given.  Returns (fin, f1, f2, w, h)."""
     fin, f1, f2 = check_dual_options(pix_fmt, out_pix_fmt, out2_pix_fmt)
-    if isinstance(src, torch.Tensor) or len(src) != 3:
-        raise ValueError("expected three planes")
+    if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
+        raise ValueError(_PLANE_COUNT[fin.nplanes].format(fin.name))
     if not isinstance(src[0], torch.Tensor):
         raise TypeError("planes must be torch tensors resident on the engine's GPU")
     h, w = src[0].shape[-2], src[0].shape[-1]
@@ -489,8 +507,48 @@ def _check_not_in_place(src: Sequence[torch.Tensor], dst: Sequence[torch.Tensor]
                 raise ValueError(message)
 
 
+_ALPHA_OVERLAP = ("the alpha source overlaps {}: alpha may run in place only as the same plane at the same depth, and must not "
+                  "share memory with any other destination plane")
+
+
+def _check_alpha_overlap(a_src: Optional[torch.Tensor], din: int, dst: Sequence[torch.Tensor], dout: int) -> None:
+    """What lutr_alpha_plane would refuse, found before the colour pass is launched: the alpha source (a plane,
+    or the packed image that holds it; None = fill) against the alpha destination `dst[3]` -- the same plane at the same depth
+    is the no-op, any other overlap of the byte ranges is refused -- and against the colour destinations `dst[:3]`, which the
+    colour pass would overwrite before alpha is read."""
+    if a_src is None:
+        return
+    alo, ahi = _byte_range(a_src)
+    for i, d in enumerate(dst):
+        blo, bhi = _byte_range(d)
+        if not (alo < bhi and blo < ahi):
+            continue
+        same = (i == 3 and din == dout and a_src.dtype == d.dtype and a_src.data_ptr() == d.data_ptr() and a_src.shape == d.shape
+                and a_src.stride() == d.stride())
+        if not same:
+            raise ValueError(_ALPHA_OVERLAP.format("the alpha destination" if i == 3 else f"destination plane {i}"))
+
+
 def _frames3(planes: Sequence[torch.Tensor]) -> list:
     return [t if t.dim() == 3 else t.unsqueeze(0) for t in planes]
+
+
+#: what a planar side with the wrong number of planes is told
+_PLANE_COUNT = {3: "expected three planes", 4: "'{}' takes four planes: the three colour planes and alpha"}
+_ALPHA_RESIZE = "a resize (out_size) is not supported with an alpha-carrying output ('{}'): the resize takes three planes"
+
+
+def refuse_alpha_resize(out_pix_fmt: Optional[str], out_size) -> None:
+    """ValueError for a resize (`out_size` / `resolution`) into an alpha-carrying planar output; any other name
+    passes, whatever it is."""
+    if out_size is None or not out_pix_fmt:
+        return
+    try:
+        fmt = parse_pix_fmt(out_pix_fmt)
+    except ValueError:
+        return
+    if fmt.alpha:
+        raise ValueError(_ALPHA_RESIZE.format(out_pix_fmt))
 
 
 def _check_planes(planes: Sequence[torch.Tensor], fmt: PixFmt, w: int, h: int, what: str) -> None:
@@ -502,8 +560,8 @@ def _check_planes(planes: Sequence[torch.Tensor], fmt: PixFmt, w: int, h: int, w
     elif fmt.nplanes == 1:
         if isinstance(planes, torch.Tensor) or len(planes) != 1:
             raise ValueError(f"'{fmt.name}' takes one buffer of packed groups")
-    elif len(planes) != 3:
-        raise ValueError("expected three planes")
+    elif len(planes) != fmt.nplanes:
+        raise ValueError(_PLANE_COUNT[fmt.nplanes].format(fmt.name))
     esize = getattr(fmt, "itemsize", 1 if fmt.depth <= 8 else 2)
     for i, t in enumerate(planes):
         if not isinstance(t, torch.Tensor):
@@ -512,6 +570,8 @@ def _check_planes(planes: Sequence[torch.Tensor], fmt: PixFmt, w: int, h: int, w
             raise ValueError("planes must be [H,W] or [F,H,W]")
         if t.is_floating_point() or t.element_size() != esize:
             raise ValueError(f"{what} plane {i}: '{fmt.name}' takes {8 * esize}-bit integer samples, got {t.dtype}")
+        if i == 3 and t.stride(-1) != 1:                       # (the colour planes: _planes_struct; alpha goes its own way)
+            raise ValueError("planes must be dense along the row")
         want = fmt.plane_shape(i, w, h)
         if isinstance(fmt, V210Fmt):                           # any row that holds the groups (FFmpeg's custom_stride)
             if t.shape[-2] != h or t.shape[-1] < 4 * fmt.groups(w):
@@ -535,6 +595,8 @@ def _check_float_planes(planes: Sequence[torch.Tensor], fmt: RgbSource, w: int, 
             raise ValueError(f"{what} plane {i}: '{fmt.name}' takes float32 samples, got {t.dtype}")
         if tuple(t.shape[-2:]) != (h, w):
             raise ValueError(f"{what} plane {i} is {tuple(t.shape[-2:])}, '{fmt.name}' at {w}x{h} needs {(h, w)}")
+        if i == 3 and t.stride(-1) != 1:                       # (the colour planes: _planes_struct; alpha goes its own way)
+            raise ValueError("planes must be dense along the row")
 
 
 def _planes_struct(planes: Sequence[torch.Tensor], device: torch.device, nplanes: int = 3) -> Tuple[_native.Planes, int]:
@@ -638,6 +700,8 @@ class LutEngine:
         # grow-only plane caches of _scratch, (key, [3 planes]) per slot: "rz" = the source-size output of the LUT ahead of a
         # resize, "fr" = the 8-bit YUV frames between the two stages of a full-range RGB source
         self._scratch_slots = {}
+        # (raw name of the last alpha kernel, the joined name `last_kernel` reports for it) after an alpha-carrying call, else None
+        self._alpha_kernels = None
 
     # -- lifetime ---------------------------------------------------------
     def close(self) -> None:
@@ -747,7 +811,48 @@ class LutEngine:
 
     @property
     def last_kernel(self) -> str:
-        return self._lib.lutr_ctx_last_kernel(self._ctx).decode()
+        """The kernel of the last call; after an alpha-carrying call "<colour kernel>+<alpha kernel>" (DESIGN.md 3.16)."""
+        name = self._lib.lutr_ctx_last_kernel(self._ctx).decode()
+        joined = self._alpha_kernels
+        return joined[1] if joined is not None and joined[0] == name else name
+
+    def _alpha_plane(self, src, dst: torch.Tensor, din: int, dout: int, w: int, h: int, row0: int, rows: Optional[int],
+                     slot: Optional[int] = None, after: Optional[str] = None) -> None:
+        """The alpha plane of an alpha-carrying call (lutr_alpha_plane), launched on the engine's stream right
+        after the colour pass: `src` is the source's alpha plane ([H,W] / [F,H,W], integer at `din` bits or float32), a packed
+        image whose component `slot` is alpha ([H,W,C] / [F,H,W,C]), or None (no alpha on the source: `dst` is filled).
+        `after`: what `last_kernel` read before this launch; it then reads "<after>+<alpha kernel>" (None: the alpha kernel)."""
+        a = _native.AlphaSrc()
+        a.kind, a.depth, a.step, a.offset = _native.ALPHA_NONE, 0, 1, 0
+        if src is not None:
+            if not isinstance(src, torch.Tensor):
+                raise TypeError("planes must be torch tensors resident on the engine's GPU")
+            if src.stride(-1) != 1 or (slot is not None and src.stride(-2) != src.shape[-1]):
+                raise ValueError("planes must be dense along the row")
+            if src.device != self.device:
+                raise ValueError("planes must be torch tensors resident on the engine's GPU")
+            lead = src.dim() - (2 if slot is None else 3)
+            a.kind = _native.ALPHA_FLOAT if src.dtype == torch.float32 else _native.ALPHA_INT
+            a.depth = 0 if a.kind == _native.ALPHA_FLOAT else din
+            a.data = src.data_ptr()
+            a.stride = src.stride(lead) * src.element_size()
+            a.frame_stride = src.stride(0) * src.element_size() if lead else 0
+            if slot is not None:
+                a.step, a.offset = src.shape[-1], slot
+            if (src.shape[0] if lead else 1) != (dst.shape[0] if dst.dim() == 3 else 1):
+                raise ValueError("src and dst disagree on the number of frames")
+        if dst.device != self.device or dst.stride(-1) != 1:
+            raise ValueError("planes must be dense along the row and resident on the engine's GPU")
+        nf, dfs = (dst.shape[0], dst.stride(0) * dst.element_size()) if dst.dim() == 3 else (1, 0)
+        rows = h - row0 if rows is None else rows
+        with self._lock:
+            self._bind_stream()
+            _native.check(self._lib.lutr_alpha_plane(
+                self._ctx, C.byref(a), dout, C.c_void_p(dst.data_ptr()), dst.stride(-2) * dst.element_size(), dfs, w, h, nf,
+                row0, rows))
+            if after is not None and w and rows and nf:          # (an empty call launches nothing and names nothing)
+                name = self._lib.lutr_ctx_last_kernel(self._ctx).decode()
+                self._alpha_kernels = (name, f"{after}+{name}")
 
     def tile_stats(self, enable: bool = True) -> dict:
         """Counters of the LDS-window kernels since the previous call; (re)arms collection."""
@@ -760,6 +865,7 @@ class LutEngine:
         _native.check(self._lib.lutr_ctx_sync(self._ctx))
 
     def _bind_stream(self) -> None:
+        self._alpha_kernels = None        # (every launch binds first: a joined alpha name never outlives the call that made it)
         if self.use_torch_stream:
             stream = torch.cuda.current_stream(self.device).cuda_stream
             _native.check(self._lib.lutr_ctx_set_stream(self._ctx, C.c_void_p(stream)))
@@ -768,11 +874,25 @@ class LutEngine:
     def apply_rgb(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *,
                   depth: int, interp: str = "tetrahedral", row0: int = 0, rows: Optional[int] = None,
                   out_size=None, resize_chunk: Optional[int] = None):
-        """lut3d on planar RGB; planes in gbrp order (G, B, R), each [H,W] or [F,H,W].
+        """lut3d on planar RGB; planes in gbrp order (G, B, R), each [H,W] or [F,H,W].  A fourth plane (gbrap*'s alpha, DESIGN.md
+        3.16) is copied to a fourth destination plane; no out_size then.
         out_size = (w, h) or "WxH" resizes the LUT's output to that size (whole frames, not in place)."""
         if not 8 <= int(depth) <= 16:
             raise ValueError(f"unsupported depth {depth}")
         h, w = src[0].shape[-2], src[0].shape[-1]
+        if not isinstance(src, torch.Tensor) and len(src) == 4:      # gbrap*: the alpha plane is copied (DESIGN.md 3.16)
+            fmt = PixFmt(f"gbrap{depth}", "gbr", int(depth), 0, 0, True, True)
+            if out_size is not None:
+                raise ValueError(_ALPHA_RESIZE.format(fmt.name))
+            if dst is None:
+                dst = [torch.empty_like(t) for t in src]
+            _check_planes(src, fmt, w, h, "source")
+            _check_planes(dst, fmt, w, h, "destination")
+            _check_alpha_overlap(src[3], int(depth), dst, int(depth))
+            with self._lock:
+                self.apply_rgb(src[:3], dst[:3], depth=depth, interp=interp, row0=row0, rows=rows)
+                self._alpha_plane(src[3], dst[3], int(depth), int(depth), w, h, row0, rows, after=self.last_kernel)
+            return dst
         fmt = PixFmt(f"gbrp{depth}", "gbr", int(depth), 0, 0, True)
         if out_size is not None:
             return self._lut_then_resize(src, dst, fmt, fmt, w, h, out_size, row0, rows, resize_chunk, None,
@@ -901,6 +1021,14 @@ class LutEngine:
                   row0: int = 0, rows: Optional[int] = None, dither: str = "none", chroma_loc: Optional[str] = None,
                   out_size=None, resize_chunk: Optional[int] = None, width: Optional[int] = None):
         """Fused YUV -> RGB -> lut3d -> RGB -> YUV on planar frames (Y, Cb, Cr).
+        `pix_fmt` / `out_pix_fmt` may each name an alpha-carrying format (yuva420p .. yuva444p16le): that side is
+        FOUR planes, the last one alpha at the luma size and the format's depth.  The colour planes are this call on the first three
+        under the three-plane names, bit for bit, with every option below; alpha never meets the LUT -- it is copied, converted to
+        the output depth (nearest code), dropped when the output has none (the plane is still checked), or filled opaque when
+        only the output has it or the call has a prologue (range_src != range_in, or lut_depth other than the source's depth: the
+        reference's 8-bit intermediate has no alpha), and is treated as straight.  The alpha source must be dense along the row and
+        may overlap the destination only as the same plane at the same depth.  Planar sides only; `out_size` with an alpha-carrying output is a
+        ValueError.  `last_kernel` is then "<colour kernel>+<alpha kernel>".
         `pix_fmt` / `out_pix_fmt` may each name a packed 4:2:2 format (yuyv422, uyvy422, yvyu422, y210le, y212le, y216le;
         DESIGN.md 3.12): that side is ONE tensor [..., h, 4 * ceil(w / 2)] (bare or in a one-element list), uint8, or int16 as for
         planar 16-bit; `width` names an odd frame width a packed source cannot tell.  The other side may be planar 4:2:2, and a
@@ -934,6 +1062,33 @@ class LutEngine:
         fout = parse_pix_fmt(out_pix_fmt or pix_fmt)
         if fin.family != "yuv" or fout.family != "yuv":
             raise ValueError("apply_yuv takes planar YUV formats")
+        if fin.alpha or fout.alpha:
+            # yuva*: the colour planes through this very call under their three-plane names, then the alpha plane on the same
+            # stream
+            if out_size is not None and fout.alpha:
+                raise ValueError(_ALPHA_RESIZE.format(fout.name))
+            check_chroma_loc(chroma_loc, dither, fin.colour.name, fout.colour.name)
+            if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
+                raise ValueError(_PLANE_COUNT[fin.nplanes].format(fin.name))
+            h, w = src[0].shape[-2], src[0].shape[-1]
+            _check_planes(src, fin, w, h, "source")
+            if dst is None and out_size is None:
+                dst = _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), self.device)
+            if dst is not None and out_size is None:
+                _check_planes(dst, fout, w, h, "destination")
+            # a prologue call fills: the reference's 8-bit yuv4xxp intermediate has no alpha to carry
+            prologue = (range_in or range_src) != range_src or (lut_depth is not None and lut_depth != fin.depth)
+            a_src = src[3] if fin.alpha and not prologue else None
+            if fout.alpha and dst is not None:
+                _check_alpha_overlap(a_src, fin.depth, dst, fout.depth)
+            with self._lock:
+                out = self.apply_yuv(src[:3], None if dst is None else dst[:3], pix_fmt=fin.colour.name, interp=interp,
+                                     matrix_in=matrix_in, matrix_out=matrix_out, range_src=range_src, range_in=range_in,
+                                     range_out=range_out, lut_depth=lut_depth, out_pix_fmt=fout.colour.name, row0=row0, rows=rows,
+                                     dither=dither, chroma_loc=chroma_loc, out_size=out_size, resize_chunk=resize_chunk)
+                if fout.alpha:
+                    self._alpha_plane(a_src, dst[3], fin.depth, fout.depth, w, h, row0, rows, after=self.last_kernel)
+            return out if dst is None else dst
         check_chroma_loc(chroma_loc, dither, fin.name, fout.name)
         xsub = (fin.csx, fin.csy) != (fout.csx, fout.csy)
         p = _yuv_params(fin.code, fout.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
@@ -987,6 +1142,30 @@ class LutEngine:
         if other:
             raise TypeError(f"apply_yuv_dual() got an unexpected keyword argument '{next(iter(other))}'")
         fin, f1, f2, w, h = dual_args(src, dst, dst2, pix_fmt, out_pix_fmt, out2_pix_fmt)
+        if fin.alpha or f1.alpha or f2.alpha:
+            # each output carries, fills or drops alpha on its own; the colour planes through this very call
+            lead, dt = tuple(src[0].shape[:-2]), src[0].dtype
+            if dst is None:
+                dst = _new_planes(f1, w, h, lead, _yuv_out_dtype(f1.depth, dt), self.device)
+            if dst2 is None:
+                dst2 = _new_planes(f2, w, h, lead, _yuv_out_dtype(f2.depth, dt), self.device)
+            # (a prologue call fills, as in apply_yuv)
+            prologue = (range_in or range_src) != range_src or (lut_depth is not None and lut_depth != fin.depth)
+            a_src = src[3] if fin.alpha and not prologue else None
+            for f, d in ((f1, dst), (f2, dst2)):
+                _check_alpha_overlap(a_src, fin.depth, list(d[:3]) + ([d[3]] if f.alpha else []), f.depth)
+            if f1.alpha and f2.alpha:
+                _check_not_in_place([dst[3]], list(dst2), "the two outputs' planes must not overlap")
+                _check_not_in_place([dst2[3]], list(dst), "the two outputs' planes must not overlap")
+            with self._lock:
+                self.apply_yuv_dual(src[:3], dst[:3], dst2[:3], pix_fmt=fin.colour.name, out_pix_fmt=f1.colour.name,
+                                    out2_pix_fmt=f2.colour.name, interp=interp, matrix_in=matrix_in, matrix_out=matrix_out,
+                                    range_src=range_src, range_in=range_in, range_out=range_out, lut_depth=lut_depth, row0=row0,
+                                    rows=rows)
+                for f, d in ((f1, dst), (f2, dst2)):
+                    if f.alpha:
+                        self._alpha_plane(a_src, d[3], fin.depth, f.depth, w, h, row0, rows, after=self.last_kernel)
+            return dst, dst2
         p = _yuv_params(fin.code, f1.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
                         range_src, range_in or range_src, range_out)
         lead = tuple(src[0].shape[:-2])
@@ -1080,11 +1259,12 @@ class LutEngine:
             st, nf = _planes_struct(src[:3], self.device)          # (an alpha plane is dropped for a YUV output)
             return st, None, w, h, nf, tuple(src[0].shape[:-2])
         if not fmt.packed:
-            if isinstance(src, torch.Tensor) or len(src) != 3:
-                raise ValueError(f"'{fmt.name}' takes three planes (G, B, R)")
+            if isinstance(src, torch.Tensor) or len(src) != fmt.nplanes:
+                raise ValueError(f"'{fmt.name}' takes four planes (G, B, R, A)" if fmt.nplanes == 4 else
+                                 f"'{fmt.name}' takes three planes (G, B, R)")
             h, w = src[0].shape[-2], src[0].shape[-1]
-            _check_planes(src, PixFmt(fmt.name, "gbr", fmt.depth, 0, 0, True), w, h, "source")
-            st, nf = _planes_struct(src, self.device)
+            _check_planes(src, PixFmt(fmt.name, "gbr", fmt.depth, 0, 0, True, fmt.nplanes == 4), w, h, "source")
+            st, nf = _planes_struct(src[:3], self.device)          # (an alpha plane goes its own way: _alpha_plane)
             return st, None, w, h, nf, tuple(src[0].shape[:-2])
         t = src
         st = _packed_struct(t, fmt.name, fmt.ncomp, fmt.depth, self.device, True)
@@ -1099,7 +1279,10 @@ class LutEngine:
         (DESIGN.md 3.9).  `src` is three gbrp-ordered planes (G, B, R; `pix_fmt` = gbrp, gbrp9le .. gbrp16le) or one [F,]H,W,C
         packed tensor (`pix_fmt` a name of `_native.PACKED_FORMATS`; a fourth component is dropped).  The LUT runs at the source's
         depth; always strict arithmetic.  `pix_fmt` = gbrpf32le | gbrapf32le takes float32 planes (lut3d's float
-        path, its output quantised to 16-bit codes for the output stage; an alpha plane is dropped; no `out_size`).  lut=False leaves lut3d out.  dither / out_size as for `apply_yuv`.  Not in place.
+        path, its output quantised to 16-bit codes for the output stage; an alpha plane is dropped; no `out_size`).  A yuva*
+        `out_pix_fmt` takes its alpha from the fourth plane of `gbrap*` / `gbrapf32le` or from the real A of a packed
+        name (rgba, bgra, argb, abgr, rgba64le, bgra64le) at the output depth; any other source, and the full-range composition,
+        fill it opaque; `gbrap*` with an output without alpha drops the plane.  lut=False leaves lut3d out.  dither / out_size as for `apply_yuv`.  Not in place.
         `intermediate_pix_fmt` / `prologue_out_range` (a LutPlan's fields for a source flagged full range) select the two-stage
         composition of `apply_rgb_full_range`, with `matrix_out` as the plan's matrix."""
         if dither not in _native.DITHER:
@@ -1114,6 +1297,28 @@ class LutEngine:
             raise ValueError("a resize (out_size) is not supported with a float source")
         if fout.family != "yuv":
             raise ValueError("apply_rgb_to_yuv writes planar YUV formats; use apply_rgb / apply_packed for RGB output")
+        if fout.alpha:
+            # a yuva* output: the colour planes through this very call, then alpha from gbrap*'s fourth plane, a
+            # packed name's real A or gbrapf32le's fourth plane -- any other source, and the full-range prologue, fill it
+            if out_size is not None:
+                raise ValueError(_ALPHA_RESIZE.format(fout.name))
+            _, _, w, h, _, lead = self._rgb_source(src, fin)
+            if dst is None:
+                dst = _new_planes(fout, w, h, lead, _yuv_out_dtype(fout.depth, None), self.device)
+            _check_planes(dst, fout, w, h, "destination")
+            a_src, slot = None, None
+            if intermediate_pix_fmt is None:
+                if fin.packed and fin.alpha_slot is not None:
+                    a_src, slot = src, fin.alpha_slot
+                elif not fin.packed and fin.nplanes == 4 and len(src) == 4:
+                    a_src = src[3]
+            _check_alpha_overlap(a_src, fin.depth, dst, fout.depth)
+            with self._lock:
+                self.apply_rgb_to_yuv(src, dst[:3], pix_fmt=pix_fmt, out_pix_fmt=fout.colour.name, interp=interp,
+                                      matrix_out=matrix_out, range_out=range_out, row0=row0, rows=rows, dither=dither, lut=lut,
+                                      intermediate_pix_fmt=intermediate_pix_fmt, prologue_out_range=prologue_out_range)
+                self._alpha_plane(a_src, dst[3], fin.depth, fout.depth, w, h, row0, rows, slot, after=self.last_kernel)
+            return dst
         if intermediate_pix_fmt is not None:
             return self.apply_rgb_full_range(src, dst, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt,
                                              intermediate_pix_fmt=intermediate_pix_fmt, prologue_out_range=prologue_out_range,

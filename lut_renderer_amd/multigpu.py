@@ -176,20 +176,22 @@ class LutEngineGroup:
             # Source and destination chroma rows are counted in their own layouts.
             c0, c1 = r0 >> fin.csy, (r1 + (1 << fin.csy) - 1) >> fin.csy
             o0, o1 = r0 >> fout.csy, (r1 + (1 << fout.csy) - 1) >> fout.csy
-            src_rng = [(r0, r1), (c0, c1), (c0, c1)]
-            rng = [(r0, r1), (o0, o1), (o0, o1)]
+            # (an alpha plane, DESIGN.md 3.16, is sharded with the luma rows on either side)
+            a_in, a_out = getattr(fin, "alpha", False), getattr(fout, "alpha", False)
+            src_rng = [(r0, r1), (c0, c1), (c0, c1)] + [(r0, r1)] * a_in
+            rng = [(r0, r1), (o0, o1), (o0, o1)] + [(r0, r1)] * a_out
             if kw.get("chroma_loc") is not None:
                 # sited resampling reads one chroma row (one chroma block row of luma) above and below the block: the slice
                 # that travels carries that halo, clipped to the frame, and the apply writes the block's rows inside it
                 ch = (h + bh - 1) >> fin.csy
                 h0, h1 = max(c0 - 1, 0), min(c1 + 1, ch)
-                srng = [(h0 * bh, min(h1 * bh, h)), (h0, h1), (h0, h1)]
+                srng = [(h0 * bh, min(h1 * bh, h)), (h0, h1), (h0, h1)] + [(h0 * bh, min(h1 * bh, h))] * a_in
                 with torch.cuda.device(eng.device):
                     part = [p[..., a:b, :].to(eng.device, non_blocking=True, copy=True).contiguous()
                             for p, (a, b) in zip(src, srng)]
                     full = eng.apply_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0 - h0 * bh, rows=r1 - r0,
                                          **kw)
-                    out = [o[..., a - sa:b - sa, :] for o, (a, b), (sa, _) in zip(full, rng, srng)]
+                    out = [o[..., a - sa:b - sa, :] for o, (a, b), sa in zip(full, rng, (h0 * bh, h0, h0, h0 * bh))]
                 self.last_remote += 1
                 pending.append((out, rng))
                 continue
@@ -197,12 +199,12 @@ class LutEngineGroup:
                 # the mask is anchored to the frame's top: the slice that travels starts at a row where the
                 # pattern of every output plane starts over, and the apply writes the block's rows inside it
                 h0 = _bn_anchor(r0, fout.csy)
-                srng = [(h0, r1), (h0 >> fin.csy, c1), (h0 >> fin.csy, c1)]
+                srng = [(h0, r1), (h0 >> fin.csy, c1), (h0 >> fin.csy, c1)] + [(h0, r1)] * a_in
                 with torch.cuda.device(eng.device):
                     part = [p[..., a:b, :].to(eng.device, non_blocking=True, copy=True).contiguous()
                             for p, (a, b) in zip(src, srng)]
                     full = eng.apply_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0 - h0, rows=r1 - r0, **kw)
-                    out = [o[..., a - sa:b - sa, :] for o, (a, b), sa in zip(full, rng, (h0, h0 >> fout.csy, h0 >> fout.csy))]
+                    out = [o[..., a - sa:b - sa, :] for o, (a, b), sa in zip(full, rng, (h0, h0 >> fout.csy, h0 >> fout.csy, h0))]
                 self.last_remote += 1
                 pending.append((out, rng))
                 continue
@@ -240,7 +242,7 @@ class LutEngineGroup:
 
             def rng_of(fmt, r0, r1):
                 c0, c1 = r0 >> fmt.csy, (r1 + (1 << fmt.csy) - 1) >> fmt.csy
-                return [(r0, r1), (c0, c1), (c0, c1)]
+                return [(r0, r1), (c0, c1), (c0, c1)] + [(r0, r1)] * fmt.alpha      # (alpha rows go with the luma rows)
 
             for k, (eng, (r0, r1)) in enumerate(zip(self.engines, blocks)):
                 if r1 <= r0:
@@ -309,9 +311,9 @@ class LutEngineGroup:
                         out = eng.apply_rgb_to_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, **kw)
                     else:
                         full = eng.apply_rgb_to_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0 - h0, rows=r1 - r0, **kw)
-                        out = [o[..., a - sa:, :] for o, a, sa in zip(full, (r0, o0, o0), (h0, h0 >> fout.csy, h0 >> fout.csy))]
+                        out = [o[..., a - sa:, :] for o, a, sa in zip(full, (r0, o0, o0, r0), (h0, h0 >> fout.csy, h0 >> fout.csy, h0))]
                 self.last_remote += 1
-                pending.append((out, [(r0, r1), (o0, o1), (o0, o1)]))
+                pending.append((out, [(r0, r1), (o0, o1), (o0, o1)] + [(r0, r1)] * fout.alpha))      # (alpha rows: the luma rows)
             for out, rng in pending:                               # copies back: queued after every launch was issued
                 for d, o, (a, b) in zip(dst, out, rng):
                     d[..., a:b, :].copy_(o, non_blocking=True)

@@ -18,13 +18,13 @@ from typing import Callable, Iterable, Iterator, List, Optional
 import numpy as np
 import torch
 
-from .engine import LutEngine, RgbSource, parse_rgb_source, parse_size, yuv_side
+from .engine import LutEngine, RgbSource, parse_rgb_source, parse_size, refuse_alpha_resize, yuv_side
 
 
 @dataclass
 class FrameLayout:
     """Byte layout of one YUV (or gbrp) frame in a rawvideo stream: the planes of `fmt` back to back -- three for a planar
-    format, luma then the chroma pairs for a semi-planar one, the one buffer of a packed 4:2:2 one (3.12) or of
+    format (four for yuva* / gbrap*, alpha last: ffmpeg's rawvideo order), luma then the chroma pairs for a semi-planar one, the one buffer of a packed 4:2:2 one (3.12) or of
     v210 (3.14: 32-bit words, rows of 128 * ceil(w / 48) bytes)."""
     fmt: object      # PixFmt | SemiFmt | PackedYuvFmt | V210Fmt
     width: int
@@ -151,6 +151,7 @@ class HostPipeline:
         if self.rgb and not out_pix_fmt and not self.float_out:
             raise ValueError("an RGB source needs out_pix_fmt (a planar YUV format)")
         ow, oh = (width, height) if out_size is None else parse_size(out_size)
+        refuse_alpha_resize(out_pix_fmt or pix_fmt, out_size)
         if self.float_out:
             if out_size is not None or out_rgb.nplanes > src_rgb.nplanes:
                 raise ValueError("a float output takes no out_size and cannot add an alpha plane")
