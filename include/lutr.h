@@ -176,6 +176,10 @@ int  lutr_ctx_set_lut(lutr_ctx *ctx, const float *rgb, int n, const float scale[
  * through FFmpeg's apply_prelut (linear interpolation in the 1D table) before the cube.  With a prelut the calls run on the
  * generic / vector kernels (the LDS tile kernels and the fast precision do not take one). */
 int  lutr_ctx_set_prelut(lutr_ctx *ctx, const float *prelut, int size, const float prelut_min[3], const float prelut_scale[3]);
+/* the SECOND lattice of lutr_apply_yuv_chain (layout of lutr_cube_parse; finite nodes, like lutr_ctx_set_lut); rgb NULL or n 0
+ * removes it.  It lives in a device buffer of its own in the first lattice's layout, (n+1)^3 float4 nodes; it has no prelut.
+ * lutr_ctx_set_lut / lutr_ctx_lut_alloc / lutr_lut_broadcast leave it alone, and no other entry point reads it. */
+int  lutr_ctx_set_lut2(lutr_ctx *ctx, const float *rgb, int n, const float scale[3]);
 /* multi-GPU: a non-root rank allocates the device lattice without filling it, the host
  * broadcasts into the pointer returned by lutr_ctx_lut_device (RCCL, root = the rank that
  * called lutr_ctx_set_lut), then every rank may apply. */
@@ -549,6 +553,34 @@ int lutr_apply_yuv_v210(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int
  * or ranges per output, more than two outputs, a tile (LDS) kernel. */
 int lutr_apply_yuv_dual(lutr_ctx *ctx, const lutr_yuv_params *p, int fmt_out2, int interp, int w, int h, int nframes,
                         const lutr_planes *src, const lutr_planes *dst, const lutr_planes *dst2, int row0, int rows);
+
+/* Two lut3d stages in one pass: `lut3d=file=A:interp=ia,lut3d=file=B:interp=ib,format=<pix_fmt>`, a technical
+ * LUT followed by a creative look.  Both lut3d instances negotiate the same RGB format, so the frame stays integer RGB at
+ * p->lut_depth between them.  Planar YUV in, planar YUV out, any of 4:2:0 / 4:2:2 / 4:4:4 at 8..16 bit on either side:
+ *   q0 = YUV -> integer RGB (lutr_apply_yuv's stage 1, the full-range prologue included; chroma replicated over its INPUT block)
+ *   q1 = lut3d of the context's first lattice on q0: `interp`, its scale, its .csp prelut if set; clip((int)(v * M), 0, M)
+ *   q2 = lut3d of the second lattice (lutr_ctx_set_lut2) on q1: `interp2`, its own n and scale; the codes q1 enter it exactly as
+ *        source codes enter the first
+ *   out = integer RGB -> YUV from q2 (lutr_apply_yuv_xsub's stage 3: chroma = the mean over its OUTPUT block, a partial block at
+ *        an odd edge takes the edge column / row again; constants: lutr_yuv_constants_xsub)
+ * row0 and rows must be multiples of the union block height 2^max(icsy, ocsy) unless row0 + rows == h.
+ * Always strict precision (fast / fma32 run strict here, no suffix on the last kernel).
+ * Not in place: the bounding byte ranges (all rows and frames) of the source planes and of the destination planes must be
+ * disjoint (the rule of lutr_apply_yuv_sited).
+ * LUTR_EINVAL with a message, before anything touches the device: no first or no second lattice, the format errors of
+ * lutr_apply_yuv_xsub (4:4:0, a depth outside 8..16), a null plane, 16-bit planes whose base, stride or (batches) frame stride is
+ * odd, row0 / rows off the union block, any overlap, variant vec_lds (there is no LDS kernel for this path).  Variant vec_global
+ * where the vector kernel cannot take the call is LUTR_EINVAL too, found where the kernel is chosen, as in the sibling entry
+ * points: no kernel has run and nothing is written.
+ * Kernels: "k_yuv_chain_vec<win,wout,icsx,icsy,ocsx,ocsy,interp>" (interp == interp2, nearest / trilinear / tetrahedral; the
+ * container mixes 8 -> 8, 16 -> 16 and 16 -> 8 bit; width a multiple of 8 luma samples, 4 for 16 -> 16; positive strides aligned to
+ * the accesses; row0 / rows multiples of the union block height), "k_yuv_chain_generic" for everything else (one thread per union
+ * block; any depth, stride, alignment or size; all five modes and any pair of them; an 8-bit source with a 16-bit output); a
+ * ragged width on aligned rows is split between the two and named "<vector kernel>+k_yuv_chain_generic".
+ * Not covered: a prelut on the second LUT, more than two LUTs, RGB / float / alpha / semi-planar / packed / v210 sides, dither,
+ * chroma siting, a resize, the two-output pass, a tile (LDS) kernel. */
+int lutr_apply_yuv_chain(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int interp2, int w, int h, int nframes,
+                         const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
 
 /* ---- the alpha plane of yuva* / gbrap* frames: ProRes 4444 (yuva444p10le / 12le), VP8 / VP9 with alpha
  *      (yuva420p), PNG / TIFF / EXR sequences with alpha (rgba, rgba64le, gbrap*, gbrapf32le).  In the reference's chain lut3d

@@ -158,6 +158,23 @@ def dual_call_for(kw: dict, second_pix_fmt: str, chroma_loc: Optional[str] = Non
     return dual
 
 
+def chain_call_for(kw: dict, interp2: Optional[str] = None, chroma_loc: Optional[str] = None, out_size=None,
+                   second_pix_fmt: Optional[str] = None) -> dict:
+    """Keyword arguments of LutEngine.apply_yuv_chain from those `engine_call_for` returned (with `dither` filled
+    in, if any).  `interp2` goes through the whitelist / fallback `interp` went through (plan.py; None = the first LUT's mode).
+    ValueError for an alpha / RGB / float / semi-planar / packed / v210 side, dither, chroma_loc, a resize and a second output."""
+    from .engine import check_chain_options
+    from .plan import INTERP_WHITELIST
+    check_chain_options(kw.get("pix_fmt"), kw.get("out_pix_fmt"), kw.get("dither", "none"), chroma_loc, out_size, second_pix_fmt)
+    chain = {k: v for k, v in kw.items() if k != "dither"}
+    if interp2 is not None:
+        mode = interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
+        if mode not in _ENGINE_INTERP:
+            raise ValueError(f"lut3d has no interpolation mode '{mode}'")
+        chain["interp2"] = mode
+    return chain
+
+
 def is_rgb_call(kw: dict) -> bool:
     """True when `engine_call_for` returned arguments of `apply_rgb_to_yuv` (an RGB source)."""
     from .engine import parse_rgb_source
@@ -186,7 +203,8 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               color_range: Optional[str] = None, output_tags: str = "bt709", out_pix_fmt: Optional[str] = None,
               zscale_dither: str = "none", out: Optional[Sequence] = None, engine=None,
               devices: Sequence[int] = (0,), precision: str = "strict", chroma_loc: Optional[str] = None,
-              resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None):
+              resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
+              cube2=None, interp2: Optional[str] = None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -239,7 +257,12 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     `second_pix_fmt` asks for a SECOND planar YUV output from the same pass (the reference's "pro" mode: the
     yuv422p10le master and the delivery format): the return value is then ((planes_out, planes_out2), tags), and `out`, if
     given, is the pair (planes, planes2).  Planar YUV on all three sides; no RGB / float / semi-planar / packed side, no dither,
-    chroma_loc or resolution."""
+    chroma_loc or resolution.
+
+    `cube2` (a path or a parsed CubeLut) applies a SECOND LUT behind the first in the same pass (ffmpeg's
+    `lut3d=file=A,lut3d=file=B`: a technical LUT, then a look): the frame stays integer RGB at the LUT depth between the two and
+    is converted to YUV once.  `interp2` is the second LUT's mode (None = `interp`).  Planar YUV without alpha on both sides; the
+    second LUT carries no prelut; no dither, chroma_loc, resolution or second output.  `interp2` without `cube2` is a ValueError."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -285,7 +308,11 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         kw["dither"] = resolve_engine_dither(engine_dither, kw["dither"])
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
-    if second_pix_fmt is not None:
+    if cube2 is None and interp2 is not None:
+        raise ValueError("interp2 is the mode of the second LUT: it needs cube2")
+    if cube2 is not None:
+        kw = chain_call_for(kw, interp2, chroma_loc, out_size, second_pix_fmt)
+    elif second_pix_fmt is not None:
         # the second format is resolved beside engine_call_for's: the same chain, one more output stage; dual_call_for makes
         # every check of the formats and options
         kw = dual_call_for(kw, second_pix_fmt, chroma_loc, out_size)
@@ -311,18 +338,27 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
             raise ValueError("a float output needs a single device")
     own = engine is None
     eng = engine if engine is not None else _cached_engine(devices)
-    lut = None
+    lut = lut2 = None
     if cube is not None:
         lut = cube if isinstance(cube, CubeLut) else _cached_cube(Path(cube))
+    if cube2 is not None:
+        from .engine import check_lut2
+        lut2 = cube2 if isinstance(cube2, CubeLut) else _cached_cube(Path(cube2))
+        check_lut2(lut2)
     with eng._lock:                 # upload, precision and launch of ONE task: no other thread's call gets in between
         if lut is not None and eng._applied_lut is not lut:      # same parsed LUT as last time: the device copy stands
             eng.set_lut(lut)                                     # (set_lut itself clears the marker)
             eng._applied_lut = lut
+        if lut2 is not None and eng._applied_lut2 is not lut2:   # the same shortcut for the second LUT, on its own marker
+            eng.set_lut2(lut2)
+            eng._applied_lut2 = lut2
         if eng.precision != precision:
             eng.set_precision(precision)
         if float_out:
             n_out = parse_rgb_source(kw["out_pix_fmt"]).nplanes
             result = eng.apply_rgb_float(planes[:n_out], out, interp=kw["interp"])
+        elif cube2 is not None:
+            result = eng.apply_yuv_chain(planes, out, **kw)
         elif second_pix_fmt is not None:
             o1, o2 = out if out is not None else (None, None)
             result = eng.apply_yuv_dual(planes, o1, o2, **kw)

@@ -72,6 +72,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "FIFO (not -); needs --second-pix-fmt")
     ap.add_argument("--second-pix-fmt", default=None, metavar="FMT",
                     help="planar YUV format of --second-output; it may differ from --out-pix-fmt in depth and chroma subsampling")
+    ap.add_argument("--cube2", default=None, metavar="PATH",
+                    help="engine setting: a second LUT applied behind --cube in the same pass (DESIGN.md 3.17; ffmpeg's "
+                         "lut3d=A,lut3d=B): planar YUV without alpha on both sides, no prelut on this LUT, no dither, "
+                         "--chroma-loc, --out-size or --second-output")
+    ap.add_argument("--interp2", default=None, metavar="MODE", help="interpolation mode of --cube2 (default: --interp)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("-y", action="store_true", help="overwrite the output (ffmpeg's -y)")
@@ -125,7 +130,15 @@ def plan_from_args(args):
         if args.output != "-" and os.path.realpath(second_out) == os.path.realpath(args.output):
             raise ValueError("--second-output names the same file as -o: the two outputs need a file each")
         from .api import dual_call_for
-        kw = dual_call_for(kw, second_fmt, kw.get("chroma_loc"), getattr(args, "out_size", None))
+        if getattr(args, "cube2", None) is None:
+            kw = dual_call_for(kw, second_fmt, kw.get("chroma_loc"), getattr(args, "out_size", None))
+    cube2, interp2 = getattr(args, "cube2", None), getattr(args, "interp2", None)
+    if cube2 is None and interp2 is not None:
+        raise ValueError("--interp2 is the mode of the second LUT: it needs --cube2")
+    if cube2 is not None:
+        from .api import chain_call_for
+        chroma_loc = kw.pop("chroma_loc", None)
+        kw = chain_call_for(kw, interp2, chroma_loc, getattr(args, "out_size", None), second_fmt)
     return plan, kw, w, h
 
 
@@ -149,16 +162,20 @@ def main(argv=None) -> int:
         if second is not None and os.path.isfile(second) and not args.y:
             raise FileExistsError(f"{second} exists (pass -y to overwrite)")
         from .cube import read_lut
-        from .engine import LutEngine
+        from .engine import LutEngine, check_lut2
         from .stream import HostPipeline
 
+        lut2 = None if args.cube2 is None else read_lut(args.cube2)
+        check_lut2(lut2)
         eng = LutEngine(args.device)
         eng.set_precision(args.precision)
         eng.set_lut(read_lut(args.cube))
+        if lut2 is not None:
+            eng.set_lut2(lut2)
         pix_fmt, out_fmt = kw.pop("pix_fmt"), kw.pop("out_pix_fmt")
         second_fmt = kw.pop("out2_pix_fmt", None)
         pipe = HostPipeline(eng, pix_fmt, w, h, batch=args.batch, out_pix_fmt=out_fmt, out_size=args.out_size,
-                            second_pix_fmt=second_fmt, **kw)
+                            second_pix_fmt=second_fmt, chain=lut2 is not None, **kw)
         fb = pipe.fin.frame_bytes
         if piped_in:
             total = None if args.duration is None else max(1, int(round(args.duration * args.fps)))

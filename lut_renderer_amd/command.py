@@ -252,7 +252,8 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                    source_info: VideoInfo, python_bin: Optional[str] = None, device: int = 0,
                    notes: Optional[List[str]] = None, precision: str = "strict", chroma_loc: Optional[str] = None,
                    gpu_resize: bool = False, second_output: Optional[Path] = None,
-                   second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None) -> List[str]:
+                   second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
+                   cube2: Optional[Path] = None, interp2: Optional[str] = None) -> List[str]:
     """`build_command`'s twin for the LUT stage alone: the argv of the ENGINE CLI (`python -m lut_renderer_amd.cli`)
     that applies exactly the chain `build_command` would put into `-vf` -- the same `LutPlan`, rendered as CLI options
     instead of as a filter string (ffmpeg.py:195-247, :287-310).  `source` / `output` are rawvideo files (or `-`) in
@@ -267,7 +268,10 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     `--second-pix-fmt`, DESIGN.md 3.13: the master and the delivery format of the "pro" mode together); rendered only when given.
     Planar YUV on every side; not with dither, `chroma_loc` or `gpu_resize`.
     `engine_dither` ("blue_noise", DESIGN.md 3.15) is an engine setting as well (`--engine-dither`, rendered only when given);
-    not together with `params.zscale_dither` = error_diffusion, `chroma_loc` or a second output."""
+    not together with `params.zscale_dither` = error_diffusion, `chroma_loc` or a second output.
+    `cube2` / `interp2` add a second LUT behind the first in the same pass (`--cube2`, `--interp2`, DESIGN.md 3.17: a technical LUT,
+    then a look); rendered only when given, `interp2` through the whitelist of `interp`.  Planar YUV without alpha on both sides;
+    not with dither, `chroma_loc`, `gpu_resize` or a second output."""
     import sys as _sys
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
@@ -343,6 +347,17 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                            "error_diffusion" if "--zscale-dither" in cmd else ("blue_noise" if "--engine-dither" in cmd else "none"), chroma_loc,
                            params.resolution if "--out-size" in cmd else None)
         cmd += ["--second-output", str(second_output), "--second-pix-fmt", second_pix_fmt]
+    if cube2 is None and interp2 is not None:
+        raise ValueError("interp2 is the mode of the second LUT: it needs cube2")
+    if cube2 is not None:
+        from .engine import check_chain_options
+        from .plan import INTERP_WHITELIST
+        check_chain_options(str(source_info.pix_fmt), pix_fmt or None,
+                            "error_diffusion" if "--zscale-dither" in cmd else ("blue_noise" if "--engine-dither" in cmd else "none"),
+                            chroma_loc, params.resolution if "--out-size" in cmd else None, second_pix_fmt)
+        cmd += ["--cube2", str(cube2)]
+        if interp2 is not None:
+            cmd += ["--interp2", interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"]
     return cmd
 
 

@@ -326,6 +326,12 @@ struct lutr_ctx {
         int *dev;                    // dst start words, then dst * taps weights (int32)
     };
     std::vector<RzTable> rz_tables;
+    // the second lattice of lutr_apply_yuv_chain (lutr_ctx_set_lut2): a buffer of its own in `lat`'s layout; no
+    // prelut, no derived copies.  Nothing but that entry point reads it
+    float4 *lat2 = nullptr;
+    size_t lat2_bytes = 0;
+    int n2 = 0;
+    float scale2[3] = {1.f, 1.f, 1.f};
 };
 
 // Wait for every peer copy that reads this context's lattice, then forget the events.
@@ -463,6 +469,7 @@ void lutr_ctx_destroy(lutr_ctx *c)
     drop_lat16(c);
     drop_prelut_tables(c);
     if (c->lat) (void)hipFree(c->lat);
+    if (c->lat2) (void)hipFree(c->lat2);
     if (c->stats) (void)hipFree(c->stats);
     if (c->fscratch) (void)hipFree(c->fscratch);
     if (c->bn_tab) (void)hipFree(c->bn_tab);
@@ -586,21 +593,24 @@ static int alloc_lattice(lutr_ctx *c, int n, const float scale[3])
 
 int lutr_ctx_lut_alloc(lutr_ctx *c, int n, const float scale[3]) { return alloc_lattice(c, n, scale); }
 
-int lutr_ctx_set_lut(lutr_ctx *c, const float *rgb, int n, const float scale[3])
+// the nodes of a host lattice are finite (*unit: and all inside [0, 1]); nothing is looked at for a size alloc_lattice refuses
+static int scan_lattice(const float *rgb, int n, bool *unit)
 {
-    if (!rgb) { set_error("null lattice"); return LUTR_EINVAL; }
     const size_t count = (size_t)(n > 0 ? n : 0) * n * n * 3;
-    bool unit = true;
+    *unit = true;
     for (size_t i = 0; i < count && n >= 2 && n <= 256; i++) {
         if (!std::isfinite(rgb[i])) {
             set_error("non-finite lattice value at float %zu", i);
             return LUTR_EINVAL;
         }
-        unit = unit && rgb[i] >= 0.0f && rgb[i] <= 1.0f;
+        *unit = *unit && rgb[i] >= 0.0f && rgb[i] <= 1.0f;
     }
-    const int rc = alloc_lattice(c, n, scale);
-    if (rc) return rc;
-    // pack [r][g][b][3] -> (n+1)^3 float4 with the last node replicated on each axis
+    return LUTR_OK;
+}
+
+// pack [r][g][b][3] -> (n+1)^3 float4 with the last node replicated on each axis
+static std::vector<float4> pack_lattice(const float *rgb, int n)
+{
     const int n1 = n + 1;
     std::vector<float4> host((size_t)n1 * n1 * n1);
     for (int r = 0; r < n1; r++) {
@@ -614,9 +624,59 @@ int lutr_ctx_set_lut(lutr_ctx *c, const float *rgb, int n, const float scale[3])
             }
         }
     }
+    return host;
+}
+
+int lutr_ctx_set_lut(lutr_ctx *c, const float *rgb, int n, const float scale[3])
+{
+    if (!rgb) { set_error("null lattice"); return LUTR_EINVAL; }
+    bool unit;
+    if (const int rc = scan_lattice(rgb, n, &unit)) return rc;
+    const int rc = alloc_lattice(c, n, scale);
+    if (rc) return rc;
+    const std::vector<float4> host = pack_lattice(rgb, n);
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(c->lat, host.data(), c->lat_bytes, hipMemcpyHostToDevice));
     c->unit = unit;
+    return LUTR_OK;
+}
+
+int lutr_ctx_set_lut2(lutr_ctx *c, const float *rgb, int n, const float scale[3])
+{
+    if (!c) { set_error("null context"); return LUTR_EINVAL; }
+    if (!rgb || n == 0) {                // remove the second lattice
+        HIP_TRY(hipSetDevice(c->device));
+        if (c->lat2) { HIP_TRY(hipStreamSynchronize(c->stream)); (void)hipFree(c->lat2); }
+        c->lat2 = nullptr; c->lat2_bytes = 0; c->n2 = 0;
+        return LUTR_OK;
+    }
+    if (!scale) { set_error("null argument"); return LUTR_EINVAL; }
+    if (n < 2 || n > 256) {
+        set_error("too large or invalid 3D LUT size %d", n);
+        return LUTR_EINVAL;
+    }
+    for (int i = 0; i < 3; i++)
+        if (!(scale[i] >= 0.f && scale[i] <= 1.f)) {
+            set_error("scale[%d] = %g outside [0,1]", i, (double)scale[i]);
+            return LUTR_EINVAL;
+        }
+    bool unit;
+    if (const int rc = scan_lattice(rgb, n, &unit)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = lutr_lattice_bytes(n);
+    HIP_TRY(hipStreamSynchronize(c->stream));        // a chain launch may still be reading the old nodes
+    if (bytes != c->lat2_bytes) {
+        if (c->lat2) { (void)hipFree(c->lat2); c->lat2 = nullptr; c->lat2_bytes = 0; c->n2 = 0; }
+        void *p = nullptr;
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) { set_error("hipMalloc(%zu): %s", bytes, hipGetErrorString(e)); return LUTR_ENOMEM; }
+        c->lat2 = (float4 *)p;
+        c->lat2_bytes = bytes;
+    }
+    const std::vector<float4> host = pack_lattice(rgb, n);
+    HIP_TRY(hipMemcpy(c->lat2, host.data(), bytes, hipMemcpyHostToDevice));
+    c->n2 = n;
+    std::memcpy(c->scale2, scale, sizeof(c->scale2));
     return LUTR_OK;
 }
 
@@ -1256,6 +1316,55 @@ int lutr_apply_yuv_dual(lutr_ctx *c, const lutr_yuv_params *p, int fmt_out2, int
     }
     return finish_launch(c, launch_yuv_dual(c->stream, c->variant, L, K1, K2, P, D2, G, din, dout1, csx1, csy1, dout2, csx2, csy2,
                                             icsx, icsy, interp));
+}
+
+// lutr_apply_yuv_xsub's pass for any pair of layouts with the second lattice behind the first.
+int lutr_apply_yuv_chain(lutr_ctx *c, const lutr_yuv_params *p, int interp, int interp2, int w, int h, int nframes,
+                         const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+{
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!c->lat2) { set_error("no second lattice set on this context (call lutr_ctx_set_lut2 first)"); return LUTR_EINVAL; }
+    if (interp2 < LUTR_INTERP_NEAREST || interp2 > LUTR_INTERP_PRISM) {
+        set_error("unknown interpolation mode %d for the second LUT", interp2);
+        return LUTR_EINVAL;
+    }
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    YuvConsts K;
+    rc = make_yuv_consts_xsub(*p, &K);
+    if (rc) return rc;
+    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
+    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
+    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
+    if (const int rc = check_row_blocks(row0, rows, h, 1 << std::max(icsy, ocsy), "union chroma block height")) return rc;
+    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for two LUTs in one pass"); return LUTR_EINVAL; }
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    if (const int rc = check_planes_set(src, dst)) return rc;
+    const struct { const char *side; const lutr_planes *pl; int depth; } sides[2] = {{"source", src, din}, {"destination", dst, dout}};
+    for (const auto &s : sides)
+        for (int i = 0; i < 3; i++)
+            if (s.depth > 8 && !check_aligned(s.pl->data[i], s.pl->stride[i], s.pl->frame_stride[i], nframes, 1)) {
+                set_error("%s plane %d: 16-bit planes need 2-byte aligned rows", s.side, i);
+                return LUTR_EINVAL;
+            }
+    Span ss[3], ds[3];
+    planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
+    planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
+    if (const int rc = check_disjoint("the two-LUT pass", true, ss, 3, ds, 3)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
+    LutConsts L, L2{}; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
+    // the second lattice at the same depth: its own size and scale, no prelut (L2.pre stays null), never the clip-free path
+    const int maxi = (1 << p->lut_depth) - 1;
+    L2.lat = c->lat2;
+    L2.n1 = c->n2 + 1;
+    L2.maxf = (float)maxi;
+    L2.scale_f = 1.0f / (float)maxi;
+    L2.lut_max = (float)(c->n2 - 1);
+    for (int i = 0; i < 3; i++) L2.sc[i] = c->scale2[i] * L2.lut_max;
+    fill_planes(&P, src, dst);
+    return finish_launch(c, launch_yuv_chain(c->stream, c->variant, L, L2, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, interp, interp2));
 }
 
 // What a semi-planar and a packed side share: `noun` ("layout" | "packing") names the struct in the messages; the shift against

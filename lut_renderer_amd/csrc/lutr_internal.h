@@ -131,6 +131,20 @@ LUTR_XS_DECL(w00) LUTR_XS_DECL(w11) LUTR_XS_DECL(w10)
 void launch_yuv_float_xsub(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
                            const FloatPlanes &F, int win, int icsx, int icsy, int ocsx, int ocsy, int interp);
 
+// two lut3d stages in one pass (lutr_chain.hip): launch_yuv_xsub's call for any pair of layouts, the equal ones
+// included, with a second lattice L2 (no prelut) and its mode behind the first.  nullptr = the variant cannot take the call
+// (vec_lds always; vec_global on layouts the vector kernel cannot take and on a pair of different modes)
+const char *launch_yuv_chain(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const YuvConsts &K,
+                             const PlaneSet &P, const FrameGeom &G, int din, int dout, int icsx, int icsy, int ocsx, int ocsy,
+                             int interp, int interp2);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>): nullptr = not a mode it has
+#define LUTR_CH_DECL(tag) \
+    const char *launch_yuv_chain_vec_##tag(hipStream_t st, const LutConsts &L, const LutConsts &L2, const YuvConsts &K, \
+                                           const PlaneSet &P, const FrameGeom &G, int icsx, int icsy, int ocsx, int ocsy, \
+                                           int interp);
+LUTR_CH_DECL(w00) LUTR_CH_DECL(w11) LUTR_CH_DECL(w10)
+#undef LUTR_CH_DECL
+
 // blue-noise dither in the output stage (lutr_bnd.hip): launch_yuv_xsub's call for any pair of layouts, the equal
 // ones included; bn = the 64 x 64 table of offsets (device).  nullptr = the variant cannot take the call (vec_lds always;
 // vec_global on layouts the vector kernel cannot take)

@@ -457,6 +457,88 @@ def dual_args(src, dst, dst2, pix_fmt, out_pix_fmt, out2_pix_fmt):
     return fin, f1, f2, w, h
 
 
+#: keywords of `apply_yuv` that the two-LUT pass does not take
+_CHAIN_NOT_TAKEN = {"dither": "dither", "chroma_loc": "sited chroma resampling (chroma_loc)", "out_size": "a resize (out_size)",
+                    "resize_chunk": "a resize (out_size)", "width": "a packed side (width)",
+                    "out2_pix_fmt": "a second output (out2_pix_fmt)", "dst2": "a second output (dst2)"}
+
+
+def chain_side(name: Optional[str], what: str) -> PixFmt:
+    """One side of `apply_yuv_chain`, a planar YUV format without alpha (yuvj* read as yuv*); ValueError for alpha, RGB, float,
+    semi-planar, packed and v210 names.  `what` names the argument in the message."""
+    head = f"the two-LUT pass takes planar YUV on both sides: {what} '{name}'"
+    if not name:
+        raise ValueError(f"the two-LUT pass needs {what}")
+    if parse_semi_fmt(name) is not None:
+        raise ValueError(f"{head} is a semi-planar container")
+    if parse_packed_yuv_fmt(name) is not None or name in _PACKED_YUV_UNSUPPORTED:
+        raise ValueError(f"{head} is a packed container")
+    if parse_v210_fmt(name) is not None or name in _V210_UNSUPPORTED:
+        raise ValueError(f"{head} is a v210 container")
+    rgb = parse_rgb_source(name)
+    if rgb is not None:
+        raise ValueError(f"{head} is a float RGB format" if rgb.floating else f"{head} is an RGB format")
+    fmt = parse_pix_fmt(name.replace("yuvj", "yuv"))
+    if fmt.alpha:
+        raise ValueError(f"{head} carries alpha")
+    return fmt
+
+
+def check_chain_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
+                        out_size=None, second_pix_fmt: Optional[str] = None) -> Tuple[PixFmt, PixFmt]:
+    """The checks `apply_yuv_chain` makes of its formats and options before any GPU work: two planar YUV sides
+    without alpha, no dither, chroma_loc, out_size or second output.  Returns the two parsed formats."""
+    fin = chain_side(pix_fmt, "pix_fmt")
+    fout = chain_side(out_pix_fmt or pix_fmt, "out_pix_fmt")
+    if dither != "none":
+        raise ValueError("dither is not supported with a second LUT")
+    if chroma_loc is not None:
+        raise ValueError("sited chroma resampling (chroma_loc) is not supported with a second LUT")
+    if out_size is not None:
+        raise ValueError("a resize (out_size) is not supported with a second LUT")
+    if second_pix_fmt is not None:
+        raise ValueError("a second output is not supported with a second LUT")
+    return fin, fout
+
+
+def refuse_chain_keywords(kw: dict) -> None:
+    """ValueError when `kw` holds a keyword of `apply_yuv` / `apply_yuv_dual` that the two-LUT pass does not take, whatever its
+    value."""
+    for k, what in _CHAIN_NOT_TAKEN.items():
+        if k in kw:
+            raise ValueError(f"{what} is not supported with a second LUT: apply_yuv_chain takes no '{k}'")
+
+
+def check_lut2(lut) -> None:
+    """ValueError for a second LUT that carries a prelut (a .csp shaper): lut3d's prelut is only taken on the first LUT."""
+    if lut is not None and getattr(lut, "prelut", None) is not None:
+        raise ValueError("the second LUT carries a prelut (a .csp shaper): a prelut is only supported on the first LUT")
+
+
+def chain_interp(interp: str, interp2: Optional[str]) -> Tuple[int, int]:
+    """The two mode codes of `apply_yuv_chain` (`interp2` None = `interp`); ValueError for a name lut3d does not have."""
+    for name in (interp, interp2):
+        if name is not None and name not in _native.INTERP:
+            raise ValueError(f"lut3d has no interpolation mode '{name}'")
+    return _native.INTERP[interp], _native.INTERP[interp if interp2 is None else interp2]
+
+
+def chain_args(src, dst, pix_fmt, out_pix_fmt, interp, interp2):
+    """What `apply_yuv_chain` checks of its formats, modes and planes before it touches the engine.  Returns (fin, fout, w, h,
+    mode, mode2)."""
+    fin, fout = check_chain_options(pix_fmt, out_pix_fmt)
+    mode, mode2 = chain_interp(interp, interp2)
+    if isinstance(src, torch.Tensor) or len(src) != 3:
+        raise ValueError(_PLANE_COUNT[3])
+    if not isinstance(src[0], torch.Tensor):
+        raise TypeError("planes must be torch tensors resident on the engine's GPU")
+    h, w = src[0].shape[-2], src[0].shape[-1]
+    _check_planes(src, fin, w, h, "source")
+    if dst is not None:
+        _check_planes(dst, fout, w, h, "destination")
+    return fin, fout, w, h, mode, mode2
+
+
 #: frames per LUT launch when apply_yuv / apply_rgb resize (`out_size`): the LUT writes a chunk into the engine's scratch at the
 #: source size and the resize reads it back while it is still in the Infinity Cache (DESIGN.md 3.7).  LUTR_RESIZE_CHUNK overrides.
 RESIZE_CHUNK = 16
@@ -697,6 +779,8 @@ class LutEngine:
         self._lock = threading.RLock()
         self.precision = "strict"
         self._applied_lut = None          # the CubeLut object apply_lut uploaded last (its upload-skipping shortcut)
+        self._applied_lut2 = None         # ... and the second LUT of apply_lut(cube2=)
+        self.n2 = 0
         # grow-only plane caches of _scratch, (key, [3 planes]) per slot: "rz" = the source-size output of the LUT ahead of a
         # resize, "fr" = the 8-bit YUV frames between the two stages of a full-range RGB source
         self._scratch_slots = {}
@@ -747,6 +831,27 @@ class LutEngine:
     def load_cube(self, path) -> CubeLut:
         lut = read_lut(path)
         self.set_lut(lut)
+        return lut
+
+    def set_lut2(self, lut: Optional[CubeLut]) -> None:
+        """The SECOND LUT of `apply_yuv_chain`, or None to remove it.  It lives beside the first lattice: `set_lut`
+        / `load_cube` leave it alone and no other call reads it.  A LUT that carries a prelut (a .csp shaper) is a ValueError."""
+        check_lut2(lut)
+        with self._lock:
+            self._applied_lut2 = None     # any direct upload invalidates apply_lut's "same second LUT as last time" shortcut
+            if lut is None:
+                _native.check(self._lib.lutr_ctx_set_lut2(self._ctx, None, 0, None))
+                self.n2 = 0
+                return
+            table = np.ascontiguousarray(lut.table, dtype=np.float32)
+            scale = (C.c_float * 3)(*[float(v) for v in lut.scale])
+            _native.check(self._lib.lutr_ctx_set_lut2(
+                self._ctx, table.ctypes.data_as(C.POINTER(C.c_float)), int(lut.n), scale))
+            self.n2 = int(lut.n)
+
+    def load_cube2(self, path) -> CubeLut:
+        lut = read_lut(path)
+        self.set_lut2(lut)
         return lut
 
     def lattice_tensor(self) -> torch.Tensor:
@@ -1183,6 +1288,32 @@ class LutEngine:
             _native.check(self._lib.lutr_apply_yuv_dual(
                 self._ctx, C.byref(p), f2.code, _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(d), C.byref(d2), row0, rows))
         return dst, dst2
+
+    def apply_yuv_chain(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str,
+                        out_pix_fmt: Optional[str] = None, interp: str = "tetrahedral", interp2: Optional[str] = None,
+                        matrix_in: str = "bt709", matrix_out: Optional[str] = None, range_src: str = "tv",
+                        range_in: Optional[str] = None, range_out: str = "tv", lut_depth: Optional[int] = None, row0: int = 0,
+                        rows: Optional[int] = None, **other):
+        """`apply_yuv` with TWO LUTs in one pass (ffmpeg's `lut3d=A:interp=ia,lut3d=B:interp=ib,format=...`): the
+        first LUT (`set_lut`, its prelut included) in mode `interp`, then the second (`set_lut2`) in mode `interp2` (None =
+        `interp`) on the first one's integer RGB at the LUT depth, then RGB -> YUV once.  Planar YUV without alpha on both
+        sides, any pair of 4:2:0 / 4:2:2 / 4:4:4 at 8..16 bit.  Always strict arithmetic; no dither, chroma_loc, out_size or
+        second output; not in place.  row0 / rows are multiples of the union block height of the two layouts."""
+        refuse_chain_keywords(other)
+        if other:
+            raise TypeError(f"apply_yuv_chain() got an unexpected keyword argument '{next(iter(other))}'")
+        fin, fout, w, h, mode, mode2 = chain_args(src, dst, pix_fmt, out_pix_fmt, interp, interp2)
+        p = _yuv_params(fin.code, fout.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
+                        range_src, range_in or range_src, range_out)
+        if dst is None:
+            dst = _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), self.device)
+        s, d, nf = _plane_pair(src, dst, self.device)
+        rows = h - row0 if rows is None else rows
+        with self._lock:
+            self._bind_stream()
+            _native.check(self._lib.lutr_apply_yuv_chain(
+                self._ctx, C.byref(p), mode, mode2, w, h, nf, C.byref(s), C.byref(d), row0, rows))
+        return dst
 
     def _apply_yuv_container(self, packed, src, dst, fin, fout, interp, matrix_in, matrix_out, range_src, range_in, range_out,
                              lut_depth, row0, rows, width):

@@ -28,8 +28,8 @@ import torch
 
 from . import _native
 from .cube import CubeLut, read_lut
-from .engine import (LutEngine, _new_planes, _yuv_out_dtype, check_container_options, dual_args, packed_frame_width, parse_pix_fmt,
-                     parse_rgb_source, refuse_dual_keywords, v210_frame_width, yuv_side)
+from .engine import (LutEngine, _new_planes, _yuv_out_dtype, chain_args, check_container_options, check_lut2, dual_args, packed_frame_width, parse_pix_fmt,
+                     parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords, v210_frame_width, yuv_side)
 from .shard import row_blocks
 
 
@@ -56,6 +56,7 @@ class LutEngineGroup:
             else bool(treat_as_remote)
         self._lock = threading.RLock()
         self._applied_lut = None
+        self._applied_lut2 = None
         self.precision = "strict"
         self.engines: List[LutEngine] = []
         try:
@@ -103,6 +104,19 @@ class LutEngineGroup:
     def load_cube(self, path) -> CubeLut:
         lut = read_lut(path)
         self.set_lut(lut)
+        return lut
+
+    def set_lut2(self, lut: Optional[CubeLut]) -> None:
+        """The second LUT of `apply_yuv_chain`, uploaded from the host to every engine (None removes it)."""
+        check_lut2(lut)
+        with self._lock:
+            self._applied_lut2 = None
+            for e in self.engines:
+                e.set_lut2(lut)
+
+    def load_cube2(self, path) -> CubeLut:
+        lut = read_lut(path)
+        self.set_lut2(lut)
         return lut
 
     def set_variant(self, name: str) -> None:
@@ -261,6 +275,45 @@ class LutEngineGroup:
                 for d, o, (a, b) in zip(to, out, rng):
                     d[..., a:b, :].copy_(o, non_blocking=True)
             return dst, dst2
+
+    def apply_yuv_chain(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str,
+                        out_pix_fmt: Optional[str] = None, interp: str = "tetrahedral", interp2: Optional[str] = None, **kw):
+        """`LutEngine.apply_yuv_chain` with the rows of every frame split over the group's devices: shards on
+        multiples of the union block height of the two layouts, each side's chroma rows counted in its own layout, no halo."""
+        with self._lock:
+            if "row0" in kw or "rows" in kw:
+                raise ValueError("the group owns the row partition")
+            refuse_chain_keywords(kw)
+            fin, fout, w, h, _, _ = chain_args(src, dst, pix_fmt, out_pix_fmt, interp, interp2)
+            home = src[0].device
+            if dst is None:
+                dst = _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), home)
+            names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, interp=interp, interp2=interp2)
+            blocks = row_blocks(h, len(self.engines), align=1 << max(fin.csy, fout.csy))
+            self.last_blocks = blocks
+            self.last_remote = 0
+            pending = []
+
+            def rng_of(fmt, r0, r1):
+                c0, c1 = r0 >> fmt.csy, (r1 + (1 << fmt.csy) - 1) >> fmt.csy
+                return [(r0, r1), (c0, c1), (c0, c1)]
+
+            for k, (eng, (r0, r1)) in enumerate(zip(self.engines, blocks)):
+                if r1 <= r0:
+                    continue
+                if eng.device == home and not (self.treat_as_remote and k > 0):
+                    eng.apply_yuv_chain(src, dst, row0=r0, rows=r1 - r0, **names, **kw)
+                    continue
+                with torch.cuda.device(eng.device):
+                    part = [p[..., a:b, :].to(eng.device, non_blocking=True, copy=True).contiguous()
+                            for p, (a, b) in zip(src, rng_of(fin, r0, r1))]
+                    out = eng.apply_yuv_chain(part, None, **names, **kw)
+                self.last_remote += 1
+                pending.append((out, rng_of(fout, r0, r1)))
+            for out, rng in pending:                               # copies back: queued after every launch was issued
+                for d, o, (a, b) in zip(dst, out, rng):
+                    d[..., a:b, :].copy_(o, non_blocking=True)
+            return dst
 
     def apply_rgb_to_yuv(self, src, dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: str, **kw):
         """`LutEngine.apply_rgb_to_yuv` with the rows of every frame split over the group's devices: shards on

@@ -136,10 +136,18 @@ class HostPipeline:
     """Apply the LUT to batches of host frames with copies overlapped against compute."""
 
     def __init__(self, engine: LutEngine, pix_fmt: str, width: int, height: int, batch: int = 8, slots: int = 3,
-                 out_pix_fmt: Optional[str] = None, out_size=None, second_pix_fmt: Optional[str] = None, **apply_kw):
+                 out_pix_fmt: Optional[str] = None, out_size=None, second_pix_fmt: Optional[str] = None, chain: bool = False, **apply_kw):
         """`out_size` = (w, h) or "WxH": the engine resizes every frame to it and the output layout has that size.
         `second_pix_fmt`: a second planar YUV output from the same pass with a pinned output ring of its own
-        (`fout2`); `run` then takes a second drain."""
+        (`fout2`); `run` then takes a second drain.
+        `chain`: the engine holds a second LUT (`set_lut2`) and every batch goes through `apply_yuv_chain` (DESIGN.md 3.17);
+        `apply_kw` may carry `interp2`.  Planar YUV without alpha on both sides, no dither, chroma_loc, out_size or second output."""
+        self.chain = bool(chain)
+        if self.chain:
+            from .engine import check_chain_options
+            check_chain_options(pix_fmt, out_pix_fmt, apply_kw.get("dither", "none"), apply_kw.get("chroma_loc"), out_size,
+                                second_pix_fmt)
+            apply_kw = {k: v for k, v in apply_kw.items() if k != "dither"}
         self.fout2 = dual_layout(pix_fmt, out_pix_fmt, second_pix_fmt, width, height, out_size, apply_kw)
         self.eng = engine
         self.fin = input_layout(pix_fmt, width, height)
@@ -197,7 +205,9 @@ class HostPipeline:
         with torch.cuda.stream(self.s_run):
             self.s_run.wait_event(self.e_in[slot])
             dst = self.fout.plane_views(self.d_out[slot], nframes)
-            if self.fout2 is not None:
+            if self.chain:
+                self.eng.apply_yuv_chain(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
+            elif self.fout2 is not None:
                 self.eng.apply_yuv_dual(self.fin.plane_views(self.d_in[slot], nframes), dst,
                                         self.fout2.plane_views(self.d_out2[slot], nframes), **self.kw)
             elif self.float_out:
