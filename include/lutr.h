@@ -628,10 +628,64 @@ typedef struct lutr_alpha_src {
  * stores under the vector kernel's conditions on the destination, one sample per thread otherwise, split likewise).
  * Variants: auto and generic as for lutr_apply_yuv; vec_global fails with LUTR_EINVAL where the vector kernel cannot take the
  * layout; vec_lds always fails with LUTR_EINVAL (there is no LDS kernel for this path).  Asynchronous on the context's stream.
- * Not covered: unpremultiply / premultiply, an alpha resize, alpha inside semi-planar / packed YUV / v210 containers (ayuv64le,
- * vuya), a float alpha destination. */
+ * Not covered: an alpha resize, alpha inside semi-planar / packed YUV / v210 containers (ayuv64le, vuya), a float alpha
+ * destination.  (Premultiplied colour: lutr_apply_yuv_premul / lutr_apply_planar_rgb_f32_premul below; this call is the same.) */
 int lutr_alpha_plane(lutr_ctx *ctx, const lutr_alpha_src *src, int dout, void *dst, ptrdiff_t dst_stride, int64_t dst_frame_stride,
                      int w, int h, int nframes, int row0, int rows);
+
+/* ---- premultiplied alpha: unpremultiply, lut3d, premultiply in one pass.  OpenEXR is premultiplied by
+ *      specification (gbrapf32le), ProRes 4444 elements (yuva444p10le / 12le) usually are; a non-linear LUT on premultiplied
+ *      colour is wrong wherever 0 < alpha < 1.  An engine setting: ffmpeg's chain has no such step. ---- */
+/* lutr_apply_yuv_xsub's pass (planar YUV in and out, any pair of 4:2:0 / 4:2:2 / 4:4:4, the equal pairs included, 8..16 bit on
+ * either side) on the colour planes `src` -> `dst` of a source whose alpha plane is `alpha`: kind LUTR_ALPHA_INT, depth equal to the
+ * depth of p->fmt_in, step 1, offset 0 (a luma-sized plane).  Per luma position, with a = min(alpha word, Ma), Ma = 2^din - 1,
+ * Ml = 2^lut_depth - 1:
+ *   q   = YUV -> integer RGB (lutr_apply_yuv's stage 1; chroma replicated over its INPUT block)
+ *   S   = min(Ml, floor((q * Ma + floor(a / 2)) / a)) per channel for a > 0, S = q for a == 0 (exact integers)
+ *   o   = lut3d on S: `interp` (all five modes), the context's scale, its .csp prelut if set; clip((int)(v * Ml), 0, Ml)
+ *   P   = floor((o * a + floor(Ma / 2)) / Ma) per channel
+ *   out = integer RGB -> YUV from P (lutr_apply_yuv_xsub's stage 3: chroma = the mean over its OUTPUT block, a partial block at an
+ *         odd edge takes the edge column / row again; constants: lutr_yuv_constants_xsub)
+ * a == Ma makes both steps the identity (the bits of the straight call), a == 0 gives P == 0.  The destination's alpha plane is
+ * not written here: lutr_alpha_plane copies or converts it afterwards, as for a straight call.
+ * row0 and rows must be multiples of the union block height 2^max(icsy, ocsy) unless row0 + rows == h.
+ * Always strict precision (fast / fma32 run strict here, no suffix on the last kernel).
+ * Not in place: the bounding byte ranges (all rows and frames) of the source planes and of the alpha source must be disjoint from
+ * those of the destination planes (the rule of lutr_apply_rgb_to_yuv; the alpha source is named source plane 3).
+ * LUTR_EINVAL with a message, before anything touches the device: no lattice, a null argument or plane, the format errors of
+ * lutr_apply_yuv_xsub (4:4:0, a depth outside 8..16), a prologue (range_src != range_in, or lut_depth other than the source's
+ * depth: such a call has no alpha to carry), an alpha source of another kind, depth, step or offset, 16-bit planes whose base,
+ * stride or (batches) frame stride is odd, row0 / rows off the union block, any overlap, variant vec_lds (there is no LDS kernel
+ * for this path).  Variant vec_global where the vector kernel cannot take the call is LUTR_EINVAL too, found where the kernel is
+ * chosen, as in the sibling entry points: no kernel has run and nothing is written.
+ * Kernels: "k_yuva_premul_vec<win,wout,icsx,icsy,ocsx,ocsy,interp>" (nearest / trilinear / tetrahedral; the container mixes
+ * 8 -> 8, 16 -> 16 and 16 -> 8 bit; width a multiple of 8 luma samples, 4 for 16 -> 16; positive strides aligned to the accesses,
+ * the alpha plane like luma; row0 / rows multiples of the union block height), "k_yuva_premul_generic" for everything else (one
+ * thread per union block; any depth, stride, alignment or size; all five modes; an 8-bit source with a 16-bit output); a ragged
+ * width on aligned rows is split between the two and named "<vector kernel>+k_yuva_premul_generic".
+ * Not covered: dither, chroma siting, a resize, the two-output pass, the two-LUT chain, integer RGB sources (PNG / TIFF are
+ * straight), an RGB source into yuva* (EXR -> yuva444p*), semi-planar / packed / v210 sides, a tile (LDS) kernel. */
+int lutr_apply_yuv_premul(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int w, int h, int nframes, const lutr_planes *src,
+                          const lutr_alpha_src *alpha, const lutr_planes *dst, int row0, int rows);
+
+/* lutr_apply_planar_rgb_f32's pass (gbrpf32 planes G, B, R in `src` and `dst`) on the colour planes of a gbrapf32le source whose
+ * alpha plane is `alpha`: kind LUTR_ALPHA_FLOAT, step 1, offset 0.  Per pixel, with a the alpha float:
+ *   t  = clamp(a, 0, 1); NaN -> 0 by its bit pattern, -0 -> +0
+ *   S  = sanitize(c) / t for t > 0, sanitize(c) for t == 0: one IEEE fp32 division (round to nearest even, subnormals kept),
+ *        then sanitised again (an overflow to +-inf becomes +-FLT_MAX)
+ *   L  = lutr_apply_planar_rgb_f32's lut3d on S (the prelut per pixel, nothing clipped)
+ *   out = L * t: one fp32 multiply
+ * t == 1 reproduces lutr_apply_planar_rgb_f32 bit for bit.  The alpha plane itself is the caller's to copy.
+ * `dst` may be `src` (in place); the alpha source must not overlap a destination plane.  Always strict precision.
+ * LUTR_EINVAL with a message, before anything touches the device: what lutr_apply_planar_rgb_f32 refuses, a null alpha
+ * descriptor or plane, an alpha source of another kind, step or offset or not 4-byte aligned, the alpha source overlapping a
+ * destination plane, variant vec_lds.  Variant vec_global where the vector kernel cannot take the layout is LUTR_EINVAL too.
+ * Kernels: "k_rgbaf_premul_vec<interp>" (nearest / trilinear / tetrahedral; width a multiple of 4; the four source planes and
+ * the three destination planes 16-byte aligned, positive strides), "k_rgbaf_premul_generic" for everything else (one pixel per
+ * thread; all five modes); a ragged width on aligned rows is split between the two and named with both.
+ * Not covered: a float source with an integer or YUV output (EXR -> yuva444p*). */
+int lutr_apply_planar_rgb_f32_premul(lutr_ctx *ctx, int interp, int w, int h, int nframes, const lutr_planes *src,
+                                     const lutr_alpha_src *alpha, const lutr_planes *dst, int row0, int rows);
 
 /* ---- precision ---- */
 /* STRICT (default): every kernel is a bit-exact restatement of FFmpeg's scalar C lut3d (vf_lut3d.c order of operations,

@@ -42,6 +42,7 @@ SYMBOLS = (
     "lutr_apply_rgb_to_yuv", "lutr_yuv_constants_rgb2yuv",
     "lutr_apply_planar_rgb_f32", "lutr_apply_rgbf_to_yuv", "lutr_apply_yuv_semi", "lutr_apply_yuv_packed",
     "lutr_apply_yuv_dual", "lutr_apply_yuv_v210", "lutr_alpha_plane", "lutr_ctx_set_lut2", "lutr_apply_yuv_chain",
+    "lutr_apply_yuv_premul", "lutr_apply_planar_rgb_f32_premul",
     "lutr_resize_filter", "lutr_resize_planes", "lutr_dither_mask",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
 )
@@ -204,6 +205,10 @@ def load() -> C.CDLL:
     lib.lutr_ctx_set_lut2.argtypes = [vp, C.POINTER(C.c_float), ci, C.POINTER(C.c_float)]
     lib.lutr_apply_yuv_chain.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_alpha_plane.argtypes = [vp, C.POINTER(AlphaSrc), ci, vp, C.c_ssize_t, C.c_int64, ci, ci, ci, ci, ci]
+    lib.lutr_apply_yuv_premul.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(AlphaSrc),
+                                          C.POINTER(Planes), ci, ci]
+    lib.lutr_apply_planar_rgb_f32_premul.argtypes = [vp, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(AlphaSrc), C.POINTER(Planes),
+                                                     ci, ci]
     lib.lutr_dither_mask.argtypes = [C.POINTER(C.c_uint16)]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]

@@ -78,7 +78,7 @@ def _cached_cube(path: Path) -> CubeLut:
     return lut
 
 
-def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = None) -> dict:
+def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = None, alpha_mode: str = "straight") -> dict:
     """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv (`pix_fmt` / `out_pix_fmt` planar YUV -- yuva* too, DESIGN.md
     3.16: without `out_pix_fmt` the source's format, alpha included, is kept; a named output without alpha drops it, one with alpha
     on a source without is filled opaque; the full-range prologue's default output stays the 8-bit yuv4xxp -- , semi-planar names
@@ -86,12 +86,18 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
     to the source's own format) -- or, for an RGB `pix_fmt` (gbrp* / a packed name / a
     float name) with a YUV `out_pix_fmt`, of LutEngine.apply_rgb_to_yuv (`is_rgb_call(kw)` tells the two apart).  A float
     `pix_fmt` (gbrpf32le / gbrapf32le) without `out_pix_fmt`, or with a float one, stays float:
-    `is_float_out_call(kw)`, and LutEngine.apply_rgb_float takes `kw["interp"]`."""
-    from .engine import parse_pix_fmt
+    `is_float_out_call(kw)`, and LutEngine.apply_rgb_float takes `kw["interp"]`.
+    alpha_mode="premultiplied"  adds `alpha_mode` to the arguments of a yuva* -> planar YUV call or of a gbrapf32le
+    float call and is a ValueError for every other call; "straight" (the default) returns what it always returned."""
+    from .engine import check_alpha_mode, check_premul_options, parse_pix_fmt
     if plan.interp not in _ENGINE_INTERP:
         raise ValueError(f"lut3d has no interpolation mode '{plan.interp}'")
     from .engine import parse_rgb_source
+    premul = check_alpha_mode(alpha_mode)
     rgb = parse_rgb_source(pix_fmt)
+    if premul and rgb is not None:
+        out_rgb = parse_rgb_source(out_pix_fmt) if out_pix_fmt else rgb
+        check_premul_options(pix_fmt, out_pix_fmt, to_yuv=not (out_rgb is not None and out_rgb.floating))
     if rgb is not None and rgb.floating:
         out = parse_rgb_source(out_pix_fmt) if out_pix_fmt else rgb
         if out is not None and out.floating:
@@ -101,7 +107,10 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
                                  "ahead of lut3d; name a YUV out_pix_fmt")
             if out.nplanes > rgb.nplanes:
                 raise ValueError(f"'{pix_fmt}' has no alpha plane to carry into '{out_pix_fmt}'")
-            return dict(pix_fmt=pix_fmt, out_pix_fmt=out.name, interp=plan.interp)
+            kw = dict(pix_fmt=pix_fmt, out_pix_fmt=out.name, interp=plan.interp)
+            if premul:
+                kw["alpha_mode"] = alpha_mode
+            return kw
         if out is not None or parse_pix_fmt(out_pix_fmt.replace("yuvj", "yuv")).family != "yuv":
             raise ValueError(f"a float RGB source takes a float or a planar YUV out_pix_fmt, not '{out_pix_fmt}'")
     if rgb is not None:
@@ -144,6 +153,10 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
         default_out = kw["pix_fmt"]
     kw["out_pix_fmt"] = out_pix_fmt or default_out
     check_container_options(kw["pix_fmt"], kw["out_pix_fmt"])    # (one subsampling on both sides of a semi-planar call)
+    if premul:
+        check_premul_options(kw["pix_fmt"], kw["out_pix_fmt"], range_src=kw["range_src"], range_in=kw["range_in"],
+                             lut_depth=kw["lut_depth"])
+        kw["alpha_mode"] = alpha_mode
     return kw
 
 
@@ -204,7 +217,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               zscale_dither: str = "none", out: Optional[Sequence] = None, engine=None,
               devices: Sequence[int] = (0,), precision: str = "strict", chroma_loc: Optional[str] = None,
               resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
-              cube2=None, interp2: Optional[str] = None):
+              cube2=None, interp2: Optional[str] = None, alpha_mode: str = "straight"):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -254,6 +267,12 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     treated as straight (a premultiplied source gets the LUT on its premultiplied colour, as in ffmpeg's chain).  Planar sides
     only; `resolution` with an alpha-carrying output is a ValueError.
 
+    `alpha_mode` is an engine setting: "straight" (default) is the paragraph above; "premultiplied" says the colour
+    of a yuva* or gbrapf32le source is premultiplied by its alpha (OpenEXR by specification, ProRes 4444 elements usually): the
+    colour is divided by alpha in front of lut3d and multiplied by it behind, inside the LUT pass, and the alpha plane is written
+    as before.  Planar yuva* in with planar YUV out, or gbrapf32le in and out; no prologue (a full-range source), dither,
+    chroma_loc, resolution, second output or second LUT, and no RGB source into YUV: each is a ValueError, as is any other value.
+
     `second_pix_fmt` asks for a SECOND planar YUV output from the same pass (the reference's "pro" mode: the
     yuv422p10le master and the delivery format): the return value is then ((planes_out, planes_out2), tags), and `out`, if
     given, is the pair (planes, planes2).  Planar YUV on all three sides; no RGB / float / semi-planar / packed side, no dither,
@@ -299,7 +318,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     # (the plan only carries the path into the filter string / notes; a parsed CubeLut or an engine that already holds the
     # lattice has none)
     plan = resolve_lut_plan(params, cube if isinstance(cube, (str, Path)) else "engine.cube", info)
-    kw = engine_call_for(plan, pix_fmt, out_pix_fmt)
+    kw = engine_call_for(plan, pix_fmt, out_pix_fmt, alpha_mode)
     from .engine import refuse_alpha_resize
     refuse_alpha_resize(kw.get("out_pix_fmt"), out_size)        # (the resize takes three planes)
     # ffmpeg.py:305-307: any value other than "error_diffusion" leaves the chain without a dither filter
@@ -310,6 +329,11 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
     if cube2 is None and interp2 is not None:
         raise ValueError("interp2 is the mode of the second LUT: it needs cube2")
+    if "alpha_mode" in kw:
+        from .engine import check_premul_options
+        check_premul_options(kw["pix_fmt"], kw["out_pix_fmt"], dither=kw["dither"], chroma_loc=chroma_loc, out_size=out_size,
+                             range_src=kw.get("range_src", "tv"), range_in=kw.get("range_in"), lut_depth=kw.get("lut_depth"),
+                             out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None)
     if cube2 is not None:
         kw = chain_call_for(kw, interp2, chroma_loc, out_size, second_pix_fmt)
     elif second_pix_fmt is not None:
@@ -356,7 +380,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
             eng.set_precision(precision)
         if float_out:
             n_out = parse_rgb_source(kw["out_pix_fmt"]).nplanes
-            result = eng.apply_rgb_float(planes[:n_out], out, interp=kw["interp"])
+            result = eng.apply_rgb_float(planes[:n_out], out, interp=kw["interp"], alpha_mode=kw.get("alpha_mode", "straight"))
         elif cube2 is not None:
             result = eng.apply_yuv_chain(planes, out, **kw)
         elif second_pix_fmt is not None:

@@ -64,6 +64,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--engine-dither", default=None, choices=["blue_noise"],
                     help="engine setting: quantise the output against a 64 x 64 blue-noise mask inside the LUT pass (DESIGN.md "
                          "3.15); not together with --zscale-dither error_diffusion")
+    ap.add_argument("--alpha-mode", default="straight", choices=["straight", "premultiplied"],
+                    help="engine setting: how the colour of a yuva* / gbrapf32le source stands to its alpha (DESIGN.md 3.18). "
+                         "premultiplied = divide by alpha in front of lut3d and multiply behind it, inside the LUT pass (OpenEXR, "
+                         "most ProRes 4444 elements); not with dither, --chroma-loc, --out-size, --second-output, --cube2, a "
+                         "full-range source or an RGB source into YUV")
     ap.add_argument("--out-size", default=None, metavar="WxH",
                     help="engine setting: resize the output frames to WxH on the GPU after the LUT (the reference's -s, "
                          "DESIGN.md 3.7); frames on -o have this size")
@@ -97,9 +102,17 @@ def plan_from_args(args):
     info = VideoInfo(width=w, height=h, pix_fmt=args.pix_fmt, bit_depth=source_bit_depth(args.pix_fmt),
                      colorspace=args.colorspace, color_range=args.color_range)
     plan = resolve_lut_plan(params, args.cube, info)
-    kw = engine_call_for(plan, args.pix_fmt, args.out_pix_fmt)
+    alpha_mode = getattr(args, "alpha_mode", None) or "straight"
+    kw = engine_call_for(plan, args.pix_fmt, args.out_pix_fmt, alpha_mode)
     from .api import is_float_out_call
     engine_dither = getattr(args, "engine_dither", None)
+    if "alpha_mode" in kw:
+        from .engine import check_premul_options
+        check_premul_options(kw["pix_fmt"], kw["out_pix_fmt"], chroma_loc=getattr(args, "chroma_loc", None),
+                             dither="error_diffusion" if args.zscale_dither == "error_diffusion" else engine_dither or "none",
+                             out_size=getattr(args, "out_size", None), range_src=kw.get("range_src", "tv"),
+                             range_in=kw.get("range_in"), lut_depth=kw.get("lut_depth"),
+                             out2_pix_fmt=getattr(args, "second_pix_fmt", None), lut2=getattr(args, "cube2", None) is not None)
     if is_float_out_call(kw) and (args.zscale_dither == "error_diffusion" or engine_dither or getattr(args, "out_size", None)):
         raise ValueError("a float output takes no dither and no --out-size")
     if args.zscale_dither == "error_diffusion":

@@ -253,7 +253,7 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                    notes: Optional[List[str]] = None, precision: str = "strict", chroma_loc: Optional[str] = None,
                    gpu_resize: bool = False, second_output: Optional[Path] = None,
                    second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
-                   cube2: Optional[Path] = None, interp2: Optional[str] = None) -> List[str]:
+                   cube2: Optional[Path] = None, interp2: Optional[str] = None, alpha_mode: str = "straight") -> List[str]:
     """`build_command`'s twin for the LUT stage alone: the argv of the ENGINE CLI (`python -m lut_renderer_amd.cli`)
     that applies exactly the chain `build_command` would put into `-vf` -- the same `LutPlan`, rendered as CLI options
     instead of as a filter string (ffmpeg.py:195-247, :287-310).  `source` / `output` are rawvideo files (or `-`) in
@@ -271,8 +271,13 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     not together with `params.zscale_dither` = error_diffusion, `chroma_loc` or a second output.
     `cube2` / `interp2` add a second LUT behind the first in the same pass (`--cube2`, `--interp2`, DESIGN.md 3.17: a technical LUT,
     then a look); rendered only when given, `interp2` through the whitelist of `interp`.  Planar YUV without alpha on both sides;
-    not with dither, `chroma_loc`, `gpu_resize` or a second output."""
+    not with dither, `chroma_loc`, `gpu_resize` or a second output.
+    `alpha_mode` ("premultiplied") is an engine setting too (`--alpha-mode`, rendered only when premultiplied:
+    "straight" keeps the argv as it was): a yuva* source with a planar YUV output or gbrapf32le kept float; not with a full-range
+    prologue, dither, `chroma_loc`, `gpu_resize`, a second output or a second LUT.  ffmpeg's chain has no such step."""
     import sys as _sys
+    if alpha_mode not in ("straight", "premultiplied"):
+        raise ValueError(f"unknown alpha_mode '{alpha_mode}' (straight | premultiplied)")
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
     if chroma_loc is not None and chroma_loc not in ("left", "center", "topleft"):
@@ -358,6 +363,16 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
         cmd += ["--cube2", str(cube2)]
         if interp2 is not None:
             cmd += ["--interp2", interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"]
+    if alpha_mode == "premultiplied":
+        from .engine import check_premul_options
+        src_fmt = str(source_info.pix_fmt).replace("yuvj", "yuv")
+        check_premul_options(src_fmt, pix_fmt or None,
+                             dither="error_diffusion" if "--zscale-dither" in cmd else ("blue_noise" if "--engine-dither" in cmd else "none"),
+                             chroma_loc=chroma_loc, out_size=params.resolution if "--out-size" in cmd else None,
+                             range_src="pc" if plan.prologue else "tv", range_in=plan.prologue_out_range if plan.prologue else "tv",
+                             lut_depth=8 if plan.prologue else None, out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None,
+                             to_yuv=_is_rgb_source(src_fmt) or (_is_float_source(src_fmt) and bool(pix_fmt) and not _is_float_source(pix_fmt)))
+        cmd += ["--alpha-mode", "premultiplied"]
     return cmd
 
 

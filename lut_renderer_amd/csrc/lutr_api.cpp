@@ -1795,6 +1795,111 @@ int lutr_alpha_plane(lutr_ctx *c, const lutr_alpha_src *src, int dout, void *dst
     return finish_launch(c, launch_alpha(c->stream, c->variant, A, FrameGeom{w, h, row0, rows, nframes}));
 }
 
+// the alpha plane a premultiplied call reads beside the colour planes -- a plane (step 1, offset 0) of `kind`,
+// aligned to its samples; an integer one at the source's depth `din`.  `entry` opens the messages.
+static int check_premul_alpha(const char *entry, const lutr_alpha_src *a, int kind, int din, int nframes)
+{
+    if (a->kind != kind) {
+        set_error("%s: the alpha source must be %s (kind %d), got kind %d -- premultiplied alpha is defined only for a source that "
+                  "carries alpha", entry, kind == LUTR_ALPHA_INT ? "an integer plane" : "a float plane", kind, (int)a->kind);
+        return LUTR_EINVAL;
+    }
+    if (kind == LUTR_ALPHA_INT && a->depth != din) {
+        set_error("%s: the alpha plane has the source's depth %d, not %d", entry, din, (int)a->depth);
+        return LUTR_EINVAL;
+    }
+    if (a->step != 1 || a->offset != 0) {
+        set_error("%s: the alpha source must be a plane (step 1, offset 0), got step %d / offset %d", entry, (int)a->step, (int)a->offset);
+        return LUTR_EINVAL;
+    }
+    if (!a->data) { set_error("%s: null alpha source plane", entry); return LUTR_EINVAL; }
+    const unsigned sb = kind == LUTR_ALPHA_FLOAT ? 4 : din > 8 ? 2 : 1;
+    if (!check_aligned(a->data, a->stride, a->frame_stride, nframes, sb - 1)) {
+        set_error(kind == LUTR_ALPHA_FLOAT ? "%s: float alpha planes need 4-byte aligned base pointers and strides"
+                                           : "%s: 16-bit alpha planes need 2-byte aligned base pointers and strides", entry);
+        return LUTR_EINVAL;
+    }
+    return LUTR_OK;
+}
+
+// lutr_apply_yuv_xsub's pass for any pair of layouts with unpremultiply / premultiply around lut3d.
+int lutr_apply_yuv_premul(lutr_ctx *c, const lutr_yuv_params *p, int interp, int w, int h, int nframes, const lutr_planes *src,
+                          const lutr_alpha_src *alpha, const lutr_planes *dst, int row0, int rows)
+{
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    if (!alpha) { set_error("null alpha source"); return LUTR_EINVAL; }
+    YuvConsts K;
+    rc = make_yuv_consts_xsub(*p, &K);
+    if (rc) return rc;
+    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
+    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
+    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
+    if (p->range_src != p->range_in || p->lut_depth != din) {
+        set_error("premultiplied alpha: a call with a prologue (range_src != range_in, or lut_depth %d other than the source's depth "
+                  "%d) has no alpha to carry", p->lut_depth, din);
+        return LUTR_EINVAL;
+    }
+    if (const int rc = check_premul_alpha("premultiplied alpha", alpha, LUTR_ALPHA_INT, din, nframes)) return rc;
+    if (const int rc = check_row_blocks(row0, rows, h, 1 << std::max(icsy, ocsy), "union chroma block height")) return rc;
+    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for premultiplied alpha"); return LUTR_EINVAL; }
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    if (const int rc = check_planes_set(src, dst)) return rc;
+    const struct { const char *side; const lutr_planes *pl; int depth; } sides[2] = {{"source", src, din}, {"destination", dst, dout}};
+    for (const auto &s : sides)
+        for (int i = 0; i < 3; i++)
+            if (s.depth > 8 && !check_aligned(s.pl->data[i], s.pl->stride[i], s.pl->frame_stride[i], nframes, 1)) {
+                set_error("%s plane %d: 16-bit planes need 2-byte aligned rows", s.side, i);
+                return LUTR_EINVAL;
+            }
+    // not in place: the three colour planes and the alpha plane (source plane 3 in the message) against every colour destination
+    Span ss[4], ds[3];
+    planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
+    ss[3] = plane_span(alpha->data, alpha->stride, alpha->frame_stride, h, (long long)w * (din > 8 ? 2 : 1), nframes);
+    planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
+    if (const int rc = check_disjoint("the premultiplied-alpha pass", true, ss, 4, ds, 3)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
+    LutConsts L; PremulPlanes P; FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
+    fill_planes(&P.p, src, dst);
+    P.a = AlphaIn{(const uint8_t *)alpha->data, (long long)alpha->stride, (long long)alpha->frame_stride};
+    return finish_launch(c, launch_yuva_premul(c->stream, c->variant, L, K, P, G, din, dout, p->lut_depth, icsx, icsy, ocsx, ocsy, interp));
+}
+
+// lutr_apply_planar_rgb_f32's pass with the division by alpha in front of lut3d and the multiplication behind it.
+int lutr_apply_planar_rgb_f32_premul(lutr_ctx *c, int interp, int w, int h, int nframes, const lutr_planes *src,
+                                     const lutr_alpha_src *alpha, const lutr_planes *dst, int row0, int rows)
+{
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!alpha) { set_error("null alpha source"); return LUTR_EINVAL; }
+    if (const int rc = check_premul_alpha("premultiplied alpha", alpha, LUTR_ALPHA_FLOAT, 0, nframes)) return rc;
+    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for premultiplied alpha"); return LUTR_EINVAL; }
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    if (const int rc = check_planes_set(src, dst)) return rc;
+    if (const int rc = check_float_planes(src, nframes, "source")) return rc;
+    if (const int rc = check_float_planes(dst, nframes, "destination")) return rc;
+    // dst == src is pixelwise and fine; the alpha plane is read by every colour plane's pixel and must not be written
+    Span as = plane_span(alpha->data, alpha->stride, alpha->frame_stride, h, (long long)w * 4, nframes), ds[3];
+    planar_spans(dst, 0, 0, w, h, 4, nframes, ds);
+    for (int j = 0; j < 3; j++)
+        if (as.lo < ds[j].hi && ds[j].lo < as.hi) {
+            set_error("premultiplied alpha: the byte range of the alpha source overlaps that of destination plane %d (bounding ranges "
+                      "over all rows and frames must be disjoint)", j);
+            return LUTR_EINVAL;
+        }
+    HIP_TRY(hipSetDevice(c->device));
+    // always strict: no kernel of this path reads the fast / fma32 lattices
+    LutConsts L; FloatPre Q; PremulPlanes P; FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = fill_lut_float(&L, &Q, c, true)) return rc;
+    fill_planes(&P.p, src, dst);
+    P.p = gbrp_to_rgb(P.p);
+    P.a = AlphaIn{(const uint8_t *)alpha->data, (long long)alpha->stride, (long long)alpha->frame_stride};
+    return finish_launch(c, launch_rgbaf_premul(c->stream, c->variant, L, Q, P, G, interp));
+}
+
 int lutr_dither_mask(uint16_t out[4096])
 {
     if (!out) { set_error("lutr_dither_mask: null out pointer"); return LUTR_EINVAL; }

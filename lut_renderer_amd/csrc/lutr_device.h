@@ -651,4 +651,48 @@ __device__ __forceinline__ void yuv_xsub_vec_body(LutConsts L, YuvConsts K, Plan
     }
 }
 
+// ---------------------------------------------------------------- premultiplied alpha
+// a * b + c for a, b below 2^24 and a sum below 2^32: v_mad_u32_u24, full rate (a 32-bit multiply is quarter rate)
+__host__ __device__ __forceinline__ uint32_t mad24(uint32_t a, uint32_t b, uint32_t c)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul24(a, b) + c;
+#else
+    return a * b + c;
+#endif
+}
+
+// floor(num / den) for 1 <= den < 2^16 and a quotient below 2^16; rcp = 1 / den to within 2 ulp.  The fp32 estimate is off by
+// less than 2^16 * (2^-24 + 2^-22) + 2^-8 < 2^-5 of the true ratio; biased up by 2^-5 its floor is the quotient or one above it,
+// and one multiply-subtract decides.
+__host__ __device__ __forceinline__ uint32_t div_q16(uint32_t num, uint32_t den, float rcp)
+{
+    const uint32_t q = (uint32_t)__builtin_fmaf((float)num, rcp, 0.03125f);
+    const int32_t r = (int32_t)(num - mad24(q, den, 0u));
+    return q + (uint32_t)(r >> 31);                               // r < 0: one too many
+}
+
+// What the three channels of a pixel share in the unpremultiply step.  den = a, or Ma for a == 0: floor(C * Ma / Ma) is the
+// contract's S = C with no select.  lim = Ml * den: a numerator at or above it gives Ml.
+struct UnpremulPx {
+    uint32_t den, half, lim;
+    float rcp;                       // 1 / den (v_rcp_f32: 1 ulp)
+};
+
+// S = min(Ml, floor((c * ma + floor(a / 2)) / a)) for a > 0, c for a == 0; c <= ml <= ma < 2^16 (the numerator stays below 2^32).
+// The clamp goes first, on the numerator: floor(lim / den) is Ml exactly, and the division only sees quotients up to Ml.
+__host__ __device__ __forceinline__ uint32_t unpremul_code(uint32_t c, const UnpremulPx &u, uint32_t ma)
+{
+    const uint32_t num = mad24(c, ma, u.half);
+    return div_q16(num < u.lim ? num : u.lim, u.den, u.rcp);
+}
+
+// P = floor((c * a + floor(ma / 2)) / ma), ma = 2^d - 1, c and a up to ma: x / (2^d - 1) = (x + (x >> d) + 1) >> d for every
+// x below 2^2d - 1, and x is at most ma * ma + ma / 2.
+__host__ __device__ __forceinline__ uint32_t premul_code(uint32_t c, uint32_t a, uint32_t ma, int d)
+{
+    const uint32_t x = mad24(c, a, ma >> 1);
+    return (x + (x >> d) + 1u) >> d;
+}
+
 }  // namespace lutr

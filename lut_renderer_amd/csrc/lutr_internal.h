@@ -304,6 +304,37 @@ bool alpha_consts(AlphaArgs *A, int kind, int din, int dout);
 // nullptr = the variant cannot take the call (vec_lds always; vec_global on layouts the vector kernel cannot take)
 const char *launch_alpha(hipStream_t st, int variant, const AlphaArgs &A, const FrameGeom &G);
 
+// premultiplied alpha (lutr_premul.hip): the source's alpha plane beside its colour planes -- luma-sized, one
+// element per pixel, at the source's depth (integer YUV) or float32 (float RGB)
+struct AlphaIn {
+    const uint8_t *a;
+    long long as, afs;               // row / frame strides, bytes
+};
+// the colour planes and the alpha plane of one call: what launch_vec_or_generic hands through to this path's callbacks
+struct PremulPlanes {
+    PlaneSet p;
+    AlphaIn  a;
+};
+struct PremulConsts {
+    uint32_t ma, ml;                 // 2^din - 1 (alpha has the source's depth), 2^lut_depth - 1 (<= ma: the callers keep them equal)
+    int      din;                    // the alpha depth: ma = 2^din - 1
+};
+// launch_yuv_xsub's call for any pair of layouts, the equal ones included, with unpremultiply / premultiply around lut3d.
+// nullptr = the variant cannot take the call (vec_lds always; vec_global on layouts the vector kernel cannot take)
+const char *launch_yuva_premul(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PremulPlanes &P,
+                               const FrameGeom &G, int din, int dout, int lut_depth, int icsx, int icsy, int ocsx, int ocsy,
+                               int interp);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>): nullptr = not a mode it has
+#define LUTR_PM_DECL(tag) \
+    const char *launch_yuva_premul_vec_##tag(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PremulConsts &M, \
+                                             const PremulPlanes &P, const FrameGeom &G, int icsx, int icsy, int ocsx, int ocsy, \
+                                             int interp);
+LUTR_PM_DECL(w00) LUTR_PM_DECL(w11) LUTR_PM_DECL(w10)
+#undef LUTR_PM_DECL
+// launch_rgbf's call (planes in R, G, B order, the destination may be the source) with the float alpha plane as a fourth stream
+const char *launch_rgbaf_premul(hipStream_t st, int variant, const LutConsts &L, const FloatPre &Q, const PremulPlanes &P,
+                                const FrameGeom &G, int interp);
+
 // round-2 tile kernels (lutr_tile2.hip, one translation unit per format: w<in wide><out wide>_c<csx><csy>); nullptr =
 // this combination is not built / cannot take the call, the caller falls back
 #define LUTR_T2_DECL(tag) \

@@ -544,6 +544,92 @@ def chain_args(src, dst, pix_fmt, out_pix_fmt, interp, interp2):
 RESIZE_CHUNK = 16
 
 
+#: how the colour planes of an alpha-carrying source stand to their alpha
+ALPHA_MODES = ("straight", "premultiplied")
+
+
+def check_alpha_mode(alpha_mode) -> bool:
+    """True for "premultiplied", False for "straight" (the default everywhere: today's paths, bit for bit); ValueError for any
+    other value."""
+    if alpha_mode not in ALPHA_MODES:
+        raise ValueError(f"unknown alpha_mode '{alpha_mode}' ({' | '.join(ALPHA_MODES)})")
+    return alpha_mode == "premultiplied"
+
+
+def check_premul_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = None, *, dither: str = "none",
+                         chroma_loc: Optional[str] = None, out_size=None, range_src: str = "tv", range_in: Optional[str] = None,
+                         lut_depth: Optional[int] = None, out2_pix_fmt: Optional[str] = None, lut2: bool = False,
+                         to_yuv: bool = False) -> str:
+    """The checks every layer makes of alpha_mode="premultiplied" before any GPU work: "yuv" for a planar yuva*
+    source with a planar YUV output, "float" for gbrapf32le in and out; ValueError for everything the contract does not define.
+    `to_yuv`: the call is `apply_rgb_to_yuv`'s; `lut2`: a second LUT is set for the call; `out2_pix_fmt`: a second output."""
+    head = "alpha_mode='premultiplied'"
+    src = parse_rgb_source(pix_fmt)
+    if src is not None and not src.floating:
+        raise ValueError(f"{head} is not defined for the integer RGB source '{pix_fmt}': PNG / TIFF alpha is straight by "
+                         f"specification")
+    if src is not None:
+        if src.nplanes != 4:
+            raise ValueError(f"{head} needs a source that carries alpha: '{pix_fmt}' has none")
+    else:
+        try:
+            side = yuv_side(pix_fmt)
+        except ValueError:
+            raise ValueError(f"{head} needs a source that carries alpha: '{pix_fmt}' is not one the engine takes") from None
+        if not getattr(side, "alpha", False):
+            raise ValueError(f"{head} needs a source that carries alpha: '{pix_fmt}' has none")
+    if out2_pix_fmt is not None:
+        raise ValueError(f"{head} is not supported with the two-output pass (out2_pix_fmt)")
+    if lut2:
+        raise ValueError(f"{head} is not supported with the two-LUT chain (a second LUT)")
+    if dither != "none":
+        raise ValueError(f"{head} is not supported with dither ('{dither}')")
+    if chroma_loc is not None:
+        raise ValueError(f"{head} is not supported with sited chroma resampling (chroma_loc)")
+    if out_size is not None:
+        raise ValueError(f"{head} is not supported with a resize (out_size / resolution)")
+    out_name = out_pix_fmt or pix_fmt
+    if src is not None:
+        if to_yuv or out_name != pix_fmt:
+            raise ValueError(f"{head}: a float source with an integer or YUV output ('{pix_fmt}' -> '{out_name}') is not "
+                             f"supported; '{pix_fmt}' in and out is")
+        return "float"
+    if to_yuv:
+        raise ValueError(f"{head} is not supported from an RGB source into YUV (apply_rgb_to_yuv)")
+    try:
+        out = yuv_side(out_name)
+    except ValueError:
+        out = None
+    if not isinstance(out, PixFmt) or out.family != "yuv":
+        raise ValueError(f"{head} takes a planar YUV output (yuv* / yuva*), not '{out_name}'")
+    if (range_in or range_src) != range_src or (lut_depth is not None and int(lut_depth) != side.depth):
+        raise ValueError(f"{head} is not defined for a call with a prologue (range_src != range_in, or lut_depth other than the "
+                         f"source's depth {side.depth}): such a call has no alpha to carry")
+    return "yuv"
+
+
+def alpha_src_struct(t: torch.Tensor, depth: int, device: torch.device) -> _native.AlphaSrc:
+    """struct lutr_alpha_src for the alpha plane `t` ([H,W] / [F,H,W]) of a premultiplied call: integer at `depth` bits, or float32."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("planes must be torch tensors resident on the engine's GPU")
+    if t.device != device:
+        raise ValueError(f"the alpha plane is on {t.device}, engine is on {device}")
+    if t.stride(-1) != 1:
+        raise ValueError("planes must be dense along the row")
+    a = _native.AlphaSrc()
+    a.kind = _native.ALPHA_FLOAT if t.dtype == torch.float32 else _native.ALPHA_INT
+    a.depth = 0 if a.kind == _native.ALPHA_FLOAT else depth
+    a.data = t.data_ptr()
+    a.stride = t.stride(-2) * t.element_size()
+    a.frame_stride = t.stride(0) * t.element_size() if t.dim() == 3 else 0
+    a.step, a.offset = 1, 0
+    return a
+
+
+_PREMUL_IN_PLACE = ("the premultiplied-alpha pass cannot run in place: destination planes must not overlap the source planes or "
+                    "the alpha source")
+
+
 def resize_chunk_default() -> int:
     import os
     v = os.environ.get("LUTR_RESIZE_CHUNK")
@@ -1015,10 +1101,15 @@ class LutEngine:
         return dst
 
     def apply_rgb_float(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *,
-                        interp: str = "tetrahedral", row0: int = 0, rows: Optional[int] = None):
+                        interp: str = "tetrahedral", row0: int = 0, rows: Optional[int] = None, alpha_mode: str = "straight"):
         """lut3d on planar float RGB (gbrpf32le, DESIGN.md 3.10): float32 planes in gbrp order (G, B, R), each [H,W] or [F,H,W];
         float in, float out, nothing clipped.  Input NaN -> 0 and +-inf -> +-FLT_MAX; a .csp prelut is applied per pixel; always
-        strict arithmetic.  `dst` may be `src` (in place).  A fourth plane (gbrapf32le's alpha) is copied through unchanged."""
+        strict arithmetic.  `dst` may be `src` (in place).  A fourth plane (gbrapf32le's alpha) is copied through unchanged.
+        alpha_mode="premultiplied" (four planes only) divides the colour by t = clamp(alpha, 0, 1) in front of
+        lut3d and multiplies by it behind, in the same kernel; t == 1 gives the bits of the straight call."""
+        premul = check_alpha_mode(alpha_mode)
+        if premul and len(src) != 4:
+            raise ValueError("alpha_mode='premultiplied' needs a source that carries alpha: 'gbrpf32le' has none")
         fmt = parse_rgb_source("gbrapf32le" if len(src) == 4 else "gbrpf32le")
         h, w = src[0].shape[-2], src[0].shape[-1]
         if dst is None:
@@ -1029,10 +1120,19 @@ class LutEngine:
             raise ValueError("src and dst disagree on the number of planes")
         s, d, nf = _plane_pair(src[:3], dst[:3], self.device)
         rows = h - row0 if rows is None else rows
+        if premul:
+            _check_alpha_overlap(src[3], 0, dst, 0)
+            a = alpha_src_struct(src[3], 0, self.device)
+            if (src[3].shape[0] if src[3].dim() == 3 else 1) != nf:
+                raise ValueError("planes disagree on the number of frames")
         with self._lock:
             self._bind_stream()
-            _native.check(self._lib.lutr_apply_planar_rgb_f32(
-                self._ctx, _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(d), row0, rows))
+            if premul:
+                _native.check(self._lib.lutr_apply_planar_rgb_f32_premul(
+                    self._ctx, _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(a), C.byref(d), row0, rows))
+            else:
+                _native.check(self._lib.lutr_apply_planar_rgb_f32(
+                    self._ctx, _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(d), row0, rows))
             if len(src) == 4 and dst[3].data_ptr() != src[3].data_ptr():      # (torch's current stream is the one just bound)
                 dst[3][..., row0:row0 + rows, :].copy_(src[3][..., row0:row0 + rows, :], non_blocking=True)
         return dst
@@ -1124,7 +1224,8 @@ class LutEngine:
                   matrix_out: Optional[str] = None, range_src: str = "tv", range_in: Optional[str] = None,
                   range_out: str = "tv", lut_depth: Optional[int] = None, out_pix_fmt: Optional[str] = None,
                   row0: int = 0, rows: Optional[int] = None, dither: str = "none", chroma_loc: Optional[str] = None,
-                  out_size=None, resize_chunk: Optional[int] = None, width: Optional[int] = None):
+                  out_size=None, resize_chunk: Optional[int] = None, width: Optional[int] = None,
+                  alpha_mode: str = "straight"):
         """Fused YUV -> RGB -> lut3d -> RGB -> YUV on planar frames (Y, Cb, Cr).
         `pix_fmt` / `out_pix_fmt` may each name an alpha-carrying format (yuva420p .. yuva444p16le): that side is
         FOUR planes, the last one alpha at the luma size and the format's depth.  The colour planes are this call on the first three
@@ -1134,6 +1235,11 @@ class LutEngine:
         reference's 8-bit intermediate has no alpha), and is treated as straight.  The alpha source must be dense along the row and
         may overlap the destination only as the same plane at the same depth.  Planar sides only; `out_size` with an alpha-carrying output is a
         ValueError.  `last_kernel` is then "<colour kernel>+<alpha kernel>".
+        alpha_mode="premultiplied" (a yuva* source, planar YUV out with or without alpha) divides the integer RGB
+        by the source's alpha in front of lut3d and multiplies by it behind, inside one kernel family of its own
+        (lutr_apply_yuv_premul; any layout pair, row0 / rows on the union block, strict arithmetic, not in place); the output's
+        alpha plane is written as for a straight call.  Opaque pixels give the straight call's bits.  Not with a prologue, dither,
+        chroma_loc or out_size.  "straight" (the default) is every path described here, unchanged.
         `pix_fmt` / `out_pix_fmt` may each name a packed 4:2:2 format (yuyv422, uyvy422, yvyu422, y210le, y212le, y216le;
         DESIGN.md 3.12): that side is ONE tensor [..., h, 4 * ceil(w / 2)] (bare or in a one-element list), uint8, or int16 as for
         planar 16-bit; `width` names an odd frame width a packed source cannot tell.  The other side may be planar 4:2:2, and a
@@ -1155,6 +1261,10 @@ class LutEngine:
         size and the resize reads them back; whole frames only, not in place.  The resize sites chroma by `chroma_loc`."""
         if dither not in _native.DITHER:
             raise ValueError(f"unknown dither mode '{dither}'")
+        premul = check_alpha_mode(alpha_mode)
+        if premul:
+            check_premul_options(pix_fmt, out_pix_fmt, dither=dither, chroma_loc=chroma_loc, out_size=out_size, range_src=range_src,
+                                 range_in=range_in, lut_depth=lut_depth)
         kind = check_container_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size, width=width)
         if kind == "v210":
             return self._apply_yuv_v210(src, dst, yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt), interp, matrix_in, matrix_out,
@@ -1186,6 +1296,25 @@ class LutEngine:
             a_src = src[3] if fin.alpha and not prologue else None
             if fout.alpha and dst is not None:
                 _check_alpha_overlap(a_src, fin.depth, dst, fout.depth)
+            if premul:
+                # the colour planes through lutr_apply_yuv_premul with the source's alpha beside them, then the alpha plane exactly
+                # as for a straight call
+                _check_alpha_overlap(a_src, fin.depth, dst[:3], fout.depth)
+                _check_not_in_place(src, dst[:3], _PREMUL_IN_PLACE)
+                s, d, nf = _plane_pair(src[:3], dst[:3], self.device)
+                a = alpha_src_struct(src[3], fin.depth, self.device)
+                if (src[3].shape[0] if src[3].dim() == 3 else 1) != nf:
+                    raise ValueError("planes disagree on the number of frames")
+                p = _yuv_params(fin.colour.code, fout.colour.code, fin.depth, matrix_in, matrix_out or matrix_in, range_src,
+                                range_src, range_out)
+                with self._lock:
+                    self._bind_stream()
+                    _native.check(self._lib.lutr_apply_yuv_premul(
+                        self._ctx, C.byref(p), _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(a), C.byref(d), row0,
+                        h - row0 if rows is None else rows))
+                    if fout.alpha:
+                        self._alpha_plane(a_src, dst[3], fin.depth, fout.depth, w, h, row0, rows, after=self.last_kernel)
+                return dst
             with self._lock:
                 out = self.apply_yuv(src[:3], None if dst is None else dst[:3], pix_fmt=fin.colour.name, interp=interp,
                                      matrix_in=matrix_in, matrix_out=matrix_out, range_src=range_src, range_in=range_in,

@@ -28,7 +28,7 @@ import torch
 
 from . import _native
 from .cube import CubeLut, read_lut
-from .engine import (LutEngine, _new_planes, _yuv_out_dtype, chain_args, check_container_options, check_lut2, dual_args, packed_frame_width, parse_pix_fmt,
+from .engine import (LutEngine, _new_planes, _yuv_out_dtype, chain_args, check_alpha_mode, check_premul_options, check_container_options, check_lut2, dual_args, packed_frame_width, parse_pix_fmt,
                      parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords, v210_frame_width, yuv_side)
 from .shard import row_blocks
 
@@ -150,6 +150,11 @@ class LutEngineGroup:
             raise ValueError("error-diffusion dither couples the rows of a frame: it cannot be row-sharded")
         if "row0" in kw or "rows" in kw:
             raise ValueError("the group owns the row partition")
+        # premultiplied alpha is passed on: shards fall on the union block, alpha rows go with the luma rows
+        if check_alpha_mode(kw.get("alpha_mode", "straight")):
+            check_premul_options(pix_fmt, out_pix_fmt, dither=kw.get("dither", "none"), chroma_loc=kw.get("chroma_loc"),
+                                 out_size=kw.get("out_size"), range_src=kw.get("range_src", "tv"), range_in=kw.get("range_in"),
+                                 lut_depth=kw.get("lut_depth"))
         # a semi-planar side is two planes, the second with the chroma plane's rows: the shard rule is unchanged.
         # A packed 4:2:2 side (3.12) is one buffer with the frame's rows -- any row for a 4:2:2 destination, even rows for a
         # planar 4:2:0 one, which is the union block rule below

@@ -143,6 +143,17 @@ class HostPipeline:
         `chain`: the engine holds a second LUT (`set_lut2`) and every batch goes through `apply_yuv_chain` (DESIGN.md 3.17);
         `apply_kw` may carry `interp2`.  Planar YUV without alpha on both sides, no dither, chroma_loc, out_size or second output."""
         self.chain = bool(chain)
+        # premultiplied alpha (DESIGN.md 3.18) travels in apply_kw like chroma_loc; "straight" is not passed on (today's calls)
+        from .engine import check_alpha_mode, check_premul_options
+        premul = check_alpha_mode(apply_kw.get("alpha_mode", "straight"))
+        if premul:
+            src_, out_ = parse_rgb_source(pix_fmt), parse_rgb_source(out_pix_fmt) if out_pix_fmt else parse_rgb_source(pix_fmt)
+            check_premul_options(pix_fmt, out_pix_fmt, dither=apply_kw.get("dither", "none"), chroma_loc=apply_kw.get("chroma_loc"),
+                                 out_size=out_size, range_src=apply_kw.get("range_src", "tv"), range_in=apply_kw.get("range_in"),
+                                 lut_depth=apply_kw.get("lut_depth"), out2_pix_fmt=second_pix_fmt, lut2=self.chain,
+                                 to_yuv=src_ is not None and not (out_ is not None and out_.floating))
+        else:
+            apply_kw = {k: v for k, v in apply_kw.items() if k != "alpha_mode"}
         if self.chain:
             from .engine import check_chain_options
             check_chain_options(pix_fmt, out_pix_fmt, apply_kw.get("dither", "none"), apply_kw.get("chroma_loc"), out_size,
@@ -212,7 +223,8 @@ class HostPipeline:
                                         self.fout2.plane_views(self.d_out2[slot], nframes), **self.kw)
             elif self.float_out:
                 src = self.fin.plane_views(self.d_in[slot], nframes)[:self.fout.fmt.nplanes]
-                self.eng.apply_rgb_float(src, dst, interp=self.kw.get("interp", "tetrahedral"))
+                self.eng.apply_rgb_float(src, dst, interp=self.kw.get("interp", "tetrahedral"),
+                                         alpha_mode=self.kw.get("alpha_mode", "straight"))
             elif self.rgb:                                   # launches on the current (s_run) stream
                 src = self.fin.image_view(self.d_in[slot], nframes) if isinstance(self.fin, PackedFrameLayout) \
                     else self.fin.plane_views(self.d_in[slot], nframes)
