@@ -145,7 +145,7 @@ struct Geom {
                           // need no window at all; the per-wave windows serve the saturated rest.
     int tube_plane;       // nodes from one r plane of the tube to the next: (2 tube_h + 3)^2 plus a few nodes of padding chosen by the
                           // launcher so that cells one step apart on any two axes never share an LDS bank (tube_plane_stride)
-    int mix_max;          // a tile with at most this many lanes outside the tube runs as a MIXED tile (tube body + gather for the outliers)
+    int mix_max;          // a tile with at most this many lanes outside the tube runs as a MIXED tile (tube body, the outliers' taps from the global lattice)
     float tube_t;         // the test: |gv - rv| and |bu - rv| (RGB codes, chroma only) must stay <= tube_t over the lane's unit
     unsigned tube_rlo, tube_rhi;   // a raw chroma interval [lo, hi] (packed like the window boxes) that implies the test for both planes:
                                    // four saturating subtractions instead of ~35 VALU for the tiles that fit it (tube_rlo > tube_rhi: none)
@@ -531,11 +531,13 @@ DEV bool tube_holds(const YuvConsts &K, const Geom &TG, const Ext &e)
 // The same bound sample by sample, for units with at most four chroma samples (4:2:0 and 4:2:2 at 10 bit): a pixel's chroma IS one
 // of them, so no pairing of one sample's Cb with another's Cr inflates the differences.  About the cost of the corner form; under
 // per-sample chroma noise it keeps more tiles in the tube (sigma = 16, strict kernels' H = 6: 17 % -> 32 % of the tiles).
+// Returns the samples OUTSIDE the bound, bit j = chroma sample j of the lane's unit (0: the lane is inside; the caller votes): a
+// mixed tile patches only the pixel groups that own such a sample (tile_body, MIX).
 template <int WIN, int WOUT, int CSX, int CSY, int PRE>
-DEV bool tube_holds_samples(const YuvConsts &K, const Geom &TG, const TileIn<WIN, WOUT, CSX, CSY> &in)
+DEV unsigned tube_outside_samples(const YuvConsts &K, const Geom &TG, const TileIn<WIN, WOUT, CSX, CSY> &in)
 {
     using T = Tile<WIN, WOUT, CSX, CSY>;
-    float worst = 0.0f;
+    unsigned bad = 0u;
 #pragma unroll
     for (int j = 0; j < T::NC; j++) {
         float cbv = wsample<WIN>(in.cb, j), crv = wsample<WIN>(in.cr, j);
@@ -545,9 +547,9 @@ DEV bool tube_holds_samples(const YuvConsts &K, const Geom &TG, const TileIn<WIN
         }
         const float cbd = cbv - K.coff, crd = crv - K.coff;
         const float rv = K.krv * crd, gv = fma_(K.kgu, cbd, K.kgv * crd), bu = K.kbu * cbd;
-        worst = vmax3(worst, fabsf(gv - rv), fabsf(bu - gv));
+        if (!(fmaxf(fabsf(gv - rv), fabsf(bu - gv)) <= TG.tube_t)) bad |= 1u << j;
     }
-    return worst <= TG.tube_t;          // per lane: the caller votes
+    return bad;
 }
 
 // ---------------------------------------------------------------- restage
@@ -881,6 +883,39 @@ DEV Taps<LDS, INTERP, V> px_taps(const LutConsts &L, const Win &W, const PxC &c)
     }
 }
 
+// MIXED tiles: a lane outside the tube computed its coordinates, fractions and weights like every other lane -- none of that depends
+// on where the nodes live -- but its LDS reads returned whatever its address pointed at.  Fetch the pixel's taps from the global
+// lattice (float4 nodes, blue fastest: the gather body's index) over the LDS results; the blend and everything after it run once.
+// A and the steps are exact: prev <= N - 1 in the (N + 1)^3 copy, every product below 2^24.  12 bytes per tap: {r, g, b}.
+template <int INTERP, int V>
+DEV void patch_taps(const LutConsts &L, const Crd &cr, const Crd &cg, const Crd &cb, Taps<true, INTERP, V> &T)
+{
+    static_assert(V != V_FAST, "the fast kernels have no mixed tiles");
+    unsigned n1 = (unsigned)L.n1;
+    asm volatile("" : "+s"(n1));      // (opaque: the steps are two scalar instructions here; hoisted out of the tile loop they are spilled SGPRs)
+    const unsigned o_g = 16u * n1, o_r = o_g * n1, o_b = 16u;
+    const unsigned a = (__umul24(__umul24((unsigned)cr.p, n1) + (unsigned)cg.p, n1) + (unsigned)cb.p) << 4;
+    auto ld = [&](unsigned off, f4 &t) {
+        const float *p = (const float *)((const char *)L.lat + off);
+        t.x = p[0]; t.y = p[1]; t.z = p[2];
+    };
+    if constexpr (INTERP == LUTR_INTERP_NEAREST) {
+        ld(a, T.t[0]);
+    } else if constexpr (INTERP == LUTR_INTERP_TRILINEAR) {
+        const unsigned ag = a + o_g, ar = a + o_r, arg = ar + o_g;
+        ld(a, T.t[0]); ld(a + o_b, T.t[1]); ld(ag, T.t[2]); ld(ag + o_b, T.t[3]);
+        ld(ar, T.t[4]); ld(ar + o_b, T.t[5]); ld(arg, T.t[6]); ld(arg + o_b, T.t[7]);
+    } else {
+        // px_finish's two selects with the global steps
+        const float dr = cr.d, dg = cg.d, db = cb.d;
+        const bool rg = dr > dg, gb = dg > db, rb = dr > db;
+        const unsigned oa = (rg && rb) ? o_r : (gb ? o_g : o_b);
+        const unsigned a111 = a + (o_r + o_g + o_b);
+        const unsigned az = a111 - ((gb && rb) ? o_b : (rg ? o_g : o_r));       // c111 minus the step of the smallest fraction
+        ld(a, T.t[0]); ld(a + oa, T.t[1]); ld(az, T.t[2]); ld(a111, T.t[3]);
+    }
+}
+
 // lattice value as the integer code it quantises to, held as float
 template <bool LDS, int INTERP, int V>
 DEV Rgb3 px_blend(const LutConsts &L, const PxC &c, const Taps<LDS, INTERP, V> &T)
@@ -1059,10 +1094,14 @@ DEV void group_coords(const LutConsts &L, const YuvConsts &K, const Geom &TG, co
 // registers, with the tube state live it spills: -2.7 %, DESIGN.md 5.2 "Scheduling"; fencing every input and output word instead of
 // the live ones keeps 2 x 12 registers allocated through the tile; the window's address factors and the chroma rows copied to VGPRs
 // per tile: no gain)
-template <bool LDS, int WIN, int WOUT, int CSX, int CSY, int INTERP, int PRE, int V>
+// MIX (the LDS body of a mixed tile): `outside` has bit j set when chroma sample j of the lane's unit is outside the tube (all bits where
+// the test has the lane's verdict only).  A group whose samples are inside needs nothing; elsewhere the lane re-reads the taps of the
+// batch from the global lattice (patch_taps) under a divergent branch the wave skips when no lane wants it.
+template <bool LDS, int WIN, int WOUT, int CSX, int CSY, int INTERP, int PRE, int V, bool MIX = false>
 DEV void tile_body(const LutConsts &L, const YuvConsts &K_, const Win &W_, const Geom &TG, TileIn<WIN, WOUT, CSX, CSY> &in,
-                   TileOut<WIN, WOUT, CSX, CSY> &out)
+                   TileOut<WIN, WOUT, CSX, CSY> &out, unsigned outside = 0u)
 {
+    static_assert(LDS || !MIX, "the patch belongs to the LDS body");
     Win W = W_;              // (local copies: through the references alone every instance gets another register allocation)
     YuvConsts K = K_;
     using T = Tile<WIN, WOUT, CSX, CSY>;
@@ -1089,9 +1128,23 @@ DEV void tile_body(const LutConsts &L, const YuvConsts &K_, const Win &W_, const
                 pc[t] = px_finish<LDS, INTERP, V>(L, W, q.r[qb + t], q.g[qb + t], q.b[qb + t]);
                 tp[t] = px_taps<LDS, INTERP, V>(L, W, pc[t]);
             }
+            if constexpr (MIX) {
+                // (opaque per batch: the batches of a group test the same bits, and merged under one branch their taps -- four
+                // pixels' -- would all be live at once)
+                unsigned want = (outside >> (g * NCG)) & ((1u << NCG) - 1u);
+                asm volatile("" : "+v"(want));
+                if (want) {
+#pragma unroll
+                    for (int t = 0; t < TB; t++) patch_taps<INTERP, V>(L, q.r[qb + t], q.g[qb + t], q.b[qb + t], tp[t]);
+                }
+            }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int t = 0; t < TB; t++) o[qb + t] = px_quant<INTERP, V>(L, px_blend<LDS, INTERP, V>(L, pc[t], tp[t]));
+            for (int t = 0; t < TB; t++) {
+                o[qb + t] = px_quant<INTERP, V>(L, px_blend<LDS, INTERP, V>(L, pc[t], tp[t]));
+                // (the patch's branch ends a basic block: keep this batch's blend in front of the next one's)
+                if constexpr (MIX) asm volatile("" : "+v"(o[qb + t].r), "+v"(o[qb + t].g), "+v"(o[qb + t].b));
+            }
         }
         float rs[NCG], gs[NCG], bs[NCG];
 #pragma unroll
@@ -1144,8 +1197,13 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
     // (likewise 8-bit 4:4:4 trilinear: eight spilled registers, and fma32 trilinear: three in the headline layout)
     // (mixed tiles for the fast kernels too, measured behind a build switch: sigma-16 frames 512 -> 537 Gpx/s, natural 662 -> 655,
     // saturated 530 -> 522, 10 more VGPRs: profiles/r03_exp34_mixed_tiles_fast_kernels.txt)
-    constexpr bool kMixed = V != V_FAST &&
+    // (only the table variants ever stage a tube, and T2_TET16 is the whole-lattice mode: no tube, no mixed tiles)
+    constexpr bool kMixed = V != V_FAST && V >= V_TAB && INTERP != T2_TET16 &&
                             !(INTERP == LUTR_INTERP_TRILINEAR && (PRE || (!WIN && !CSX) || V == V_FMA32));
+    // A mixed tile runs ONE body: the tube body with the outliers' taps patched from the global lattice (tile_body, MIX).  Not where
+    // the patching body spills: 8-bit 4:4:4 (12-22 VGPRs, at one pixel per tap batch too) and 16-bit trilinear in 4:2:0 and 4:4:4
+    // (4 and 2) keep the second pass, the gather body under a divergent branch for the outlier lanes.
+    constexpr bool kPatch = kMixed && !(!WIN && !CSX) && !(INTERP == LUTR_INTERP_TRILINEAR && WIN && WOUT && CSX == CSY);
     LutConsts L = L_;
     YuvConsts K = K_;
     // a wave-uniform constant used by several VALU ops per pixel is worth a VGPR (an SGPR operand halves the issue rate
@@ -1360,6 +1418,7 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
 #endif
         Ext e = extremes<WIN, WOUT, CSX, CSY>(in);             // without the luma minimum: see below
         bool use_tube = false, mixed = false, lane_in = true;
+        unsigned outside = 0u;                 // chroma samples of the lane's unit outside the tube (tile_body, MIX)
         if (TG.tube_h > 0) {
             // level 0: the tile's chroma keeps it inside the workgroup's grey tube (and its raw codes are legal for the clamp-free body)
             const uint32_t top = pack_hi<WIN>(TG.max_raw);
@@ -1372,14 +1431,19 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
                 // legal, but outside the interval: the bound itself.  Per sample for the strict kernels (their tube is 6 cells wide:
                 // sigma = 16 frames +9 %, natural -0.8 %, 3 x chroma -1.5 %); the fast kernels' 8-cell tube gains 1.7 % there and loses
                 // 1.4 % on 3 x chroma: corner form
-                if constexpr (T::NC <= 4 && V != V_FAST)
-                    lane_in = tube_holds_samples<WIN, WOUT, CSX, CSY, PRE>(K, TG, in);
-                else lane_in = tube_holds<WIN, PRE>(K, TG, e);
+                if constexpr (T::NC <= 4 && V != V_FAST) {
+                    outside = tube_outside_samples<WIN, WOUT, CSX, CSY, PRE>(K, TG, in);
+                    lane_in = outside == 0u;
+                } else {
+                    lane_in = tube_holds<WIN, PRE>(K, TG, e);
+                    outside = lane_in ? 0u : ~0u;
+                }
                 use_tube = __all(lane_in);
                 // MIXED tile: a few lanes outside the tube (sensor noise: one outlier unit in 64 sends a whole tile away).  Every
-                // lane runs the tube body -- an outlier reads wherever its numbers point, LDS reads cannot fault -- and the
-                // outliers alone run the gather body afterwards, under a divergent branch: its instructions issue once for the
-                // wave, its memory requests (what a gather costs) shrink to those lanes.
+                // lane runs the tube body -- an outlier reads wherever its numbers point, LDS reads cannot fault -- and where a
+                // sample is outside, the lane fetches those pixels' taps from the global lattice inside the same body: coordinates,
+                // weights, blend, RGB -> YUV and packing run once.  (Raw codes are legal here -- the vote above -- so the body's
+                // clamp-free table reads hold for the outliers too.)
                 // (strict kernels only: with a cheap restage -- win_plane_stride -- the fast kernels' H = 8 tube and 367-node windows do as
                 // well or better without it: three times the chroma 540 vs 518 Gpx/s, sigma-16 526 vs 539, profiles/r03_exp16_*.txt)
                 if constexpr (kMixed)
@@ -1456,13 +1520,16 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
             }
         }
         TileOut<WIN, WOUT, CSX, CSY> out;
-        if (use_lds) {
+        if (use_lds && !(kPatch && mixed)) {
             tile_body<true, WIN, WOUT, CSX, CSY, INTERP, PRE, V>(L, KB, (use_tube || mixed) ? Wt : W, TG, in, out); TK(tk_body)
         }
-        bool gather = !use_lds;                      // whole tiles (wave-uniform) ...
-        if constexpr (kMixed) gather = gather || (mixed && !lane_in);     // ... or the outliers of a mixed tile (divergent)
+        bool gather = !use_lds;                      // whole tiles only (wave-uniform)
+        if constexpr (kMixed && !kPatch) gather = gather || (mixed && !lane_in);
         if (gather) {
             tile_body<false, WIN, WOUT, CSX, CSY, INTERP, PRE, V>(L, KB, W, TG, in, out); TK(tk_gath)
+        }
+        if (kPatch && mixed) {
+            tile_body<true, WIN, WOUT, CSX, CSY, INTERP, PRE, V, kPatch>(L, KB, Wt, TG, in, out, outside); TK(tk_body)
         }
         if (!use_lds) T2_COUNT(8);
         __builtin_amdgcn_s_setprio(3);      // stores, the queue and the next tile's loads go first
@@ -1689,6 +1756,9 @@ const char *T2_ENTRY(hipStream_t st, const LutConsts &L, const YuvConsts &K, con
     // Measured for the strict kernels (64 UHD frames, Gpx/s, profiles/r03_exp16_mixed_tiles_cheap_restage.txt): sigma-16 frames
     // 409 without mixed tiles, 423 / 426 / 428 / 435 at 8 / 16 / 32 / 63 lanes; sigma-8 498 -> 510; natural and saturated frames +-1 %.
     // (profiles/r03_exp7_mixed_tiles.txt shows 286 -> 402: that build still paid 30 us of stride search per restage.)
+    // With the outliers patched inside the tube body (tile_body, MIX) a mixed tile is cheaper still, and 63 wins everywhere, at
+    // 8 / 16 / 32 / 63 lanes: natural 585 / 589 / 598 / 601, sigma-8 512 / 519 / 525 / 548, sigma-16 434 / 443 / 450 / 479, three times
+    // the chroma 458 / 460 / 468 / 477 (profiles/mixed_patch_ab.txt).
     tg.mix_max = 63;
     if (const Knob &e = T2_KNOB("LUTR_MIX_MAX")) { const int c = e.num(); if (c >= 0 && c <= 63) tg.mix_max = c; }
     tg.tube_rlo = 0xffffffffu; tg.tube_rhi = 0u;
