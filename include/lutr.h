@@ -720,6 +720,11 @@ const char *lutr_ctx_last_kernel(lutr_ctx *ctx);
 int lutr_ctx_tile_stats(lutr_ctx *ctx, int enable, uint64_t out[8]);
 /* the constant block the YUV kernels use, for cross-checking against the oracle: 32 floats */
 int lutr_yuv_constants(const lutr_yuv_params *p, float out[32]);
+/* Host only, for tests: the wave count a persistent tile launcher works with when the environment variable LUTR_MAX_WAVES
+ * holds `text` (NULL = unset), its workgroups have `waves_per_block` waves and the device fits `uncapped` of them.  The
+ * launchers call the same function: `text` counts only as a plain positive decimal multiple of waves_per_block that is
+ * not above `uncapped`; anything else returns `uncapped`. */
+int lutr_max_waves_knob(const char *text, int waves_per_block, int uncapped);
 
 #ifdef __cplusplus
 }

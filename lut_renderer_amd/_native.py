@@ -45,6 +45,7 @@ SYMBOLS = (
     "lutr_apply_yuv_premul", "lutr_apply_planar_rgb_f32_premul",
     "lutr_resize_filter", "lutr_resize_planes", "lutr_dither_mask",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
+    "lutr_max_waves_knob",
 )
 
 
@@ -218,6 +219,7 @@ def load() -> C.CDLL:
     lib.lutr_ctx_last_kernel.restype = cp
     lib.lutr_ctx_tile_stats.argtypes = [vp, ci, C.POINTER(C.c_uint64)]
     lib.lutr_yuv_constants.argtypes = [C.POINTER(YuvParams), C.POINTER(C.c_float)]
+    lib.lutr_max_waves_knob.argtypes = [cp, ci, ci]
     _lib = lib
     return lib
 
@@ -228,6 +230,11 @@ def dither_mask():
     rank = np.zeros((64, 64), np.uint16)
     check(load().lutr_dither_mask(rank.ctypes.data_as(C.POINTER(C.c_uint16))))
     return rank
+
+
+def max_waves_knob(text, waves_per_block: int, uncapped: int) -> int:
+    """lutr_max_waves_knob (host only): what the tile launchers make of LUTR_MAX_WAVES = `text` (None = unset)."""
+    return load().lutr_max_waves_knob(None if text is None else str(text).encode(), waves_per_block, uncapped)
 
 
 def resize_filter(src: int, dst: int, cs: int = 0, cosited: bool = False):

@@ -404,6 +404,11 @@ size_t lutr_lattice_bytes(int n)
     return n1 * n1 * n1 * sizeof(float4);
 }
 
+int lutr_max_waves_knob(const char *text, int waves_per_block, int uncapped)
+{
+    return capped_waves(text, waves_per_block, uncapped);
+}
+
 int lutr_yuv_constants(const lutr_yuv_params *p, float out[32])
 {
     return export_consts("lutr_yuv_constants", p, out, [&](YuvConsts *k) { return make_yuv_consts(*p, k); });

@@ -14,8 +14,15 @@ __global__ __launch_bounds__(256) void k_make_lat16(const float4 *__restrict__ l
     const size_t i = blockIdx.x * 256ull + threadIdx.x;
     if (i >= nodes) return;
     const float4 v = lat[i];
-    const unsigned r = __half_as_ushort(__float2half_rn(v.x * m)), g = __half_as_ushort(__float2half_rn(v.y * m));
-    const unsigned b = __half_as_ushort(__float2half_rn(v.z * m));
+    // Two roundings, as the CPU twin has them (oracle/lut3d_oracle.c: f2h_rne(rgb * m) on an fp32 product): the product to fp32,
+    // then fp32 to fp16.  Left to itself the compiler fuses `(half)(v * m)` into v_fma_mixlo_f16, which rounds the exact product
+    // once -- a different node wherever the fp32 product lands on an fp16 tie (9 of 107,811 values of a 33^3 test lattice), and
+    // every pixel blended from such a node can come out one code away from the twin.  The empty asm keeps the product a value
+    // of its own.
+    float pr = v.x * m, pg = v.y * m, pb = v.z * m;
+    asm volatile("" : "+v"(pr), "+v"(pg), "+v"(pb));
+    const unsigned r = __half_as_ushort(__float2half_rn(pr)), g = __half_as_ushort(__float2half_rn(pg));
+    const unsigned b = __half_as_ushort(__float2half_rn(pb));
     out[i] = make_uint2(r | (g << 16), b);
 }
 

@@ -164,6 +164,23 @@ inline int device_cus()
     return cus;
 }
 
+// LUTR_MAX_WAVES (tests and tools only): a cap on the waves of a persistent grid, so that a frame of a few megapixels runs as
+// many tiles per wave and draws as many tickets per workgroup as a long launch does.  `text` is the variable's value (or null),
+// `wpb` the launcher's waves per workgroup, `uncapped` its device_cus() * waves per CU.  Accepted only as a plain positive
+// decimal multiple of `wpb` that is not above `uncapped`; anything else leaves `uncapped`.  Everything a launcher derives from
+// its wave count (the tube and chunk thresholds, the chunk shrink loop, the grid, qbase) follows from the value returned.
+inline int capped_waves(const char *text, int wpb, int uncapped)
+{
+    if (!text || !*text || wpb < 1) return uncapped;
+    long long v = 0;
+    for (const char *c = text; *c; c++) {
+        if (*c < '0' || *c > '9') return uncapped;
+        v = v * 10 + (*c - '0');
+        if (v > uncapped) return uncapped;
+    }
+    return v > 0 && v % wpb == 0 ? (int)v : uncapped;
+}
+
 // Blocks of more than 4 waves need more than the default 64 KB of dynamic LDS: allow it once per (device, kernel).
 // false: the runtime refused 160 KB of dynamic LDS for this kernel (the launch would fail).
 inline bool allow_lds(const void *kernel, size_t bytes)

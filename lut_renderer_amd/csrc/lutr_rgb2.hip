@@ -572,7 +572,7 @@ const char *R2_ENTRY(hipStream_t st, const LutConsts &L, const PlaneSet &P, cons
     tg.lw_log2 = best; tg.uw = uw; tg.urows = G.rows;
     tg.nsx = (uw + (1 << best) - 1) >> best;
     tg.nry = (G.rows + (64 >> best) - 1) / (64 >> best);
-    const int max_waves = device_cus() * LUTR_R2_WPB;
+    const int max_waves = capped_waves(getenv("LUTR_MAX_WAVES"), LUTR_R2_WPB, device_cus() * LUTR_R2_WPB);
     const int tile_px = Y::PX * 64;
     // 4096 pixels per claim, 2048 when a wave gets fewer than 64 tiles (the two-level queue makes small chunks free, lutr_tile2.hip)
     int ch = (4096 + tile_px - 1) / tile_px;
@@ -627,8 +627,9 @@ const char *R2_ENTRY(hipStream_t st, const LutConsts &L, const PlaneSet &P, cons
         TP.sfs[i] = (unsigned long long)P.sfs[p]; TP.dfs[i] = (unsigned long long)P.dfs[p];
     }
     if (getenv("LUTR_DEBUG"))
-        fprintf(stderr, "[lutr r2] layout %d nsx %d nry %d chunk %d chunks %d blocks %u lds %zu tab %d whole %d tube h %d plane %d rev %d\n",
-                LY, tg.nsx, tg.nry, tg.ch, tg.nchunks, grid.x, lds, tg.tab_entries, tg.whole, tg.tube_h, tg.tube_plane, rev);
+        fprintf(stderr, "[lutr r2] layout %d nsx %d nry %d chunk %d chunks %d blocks %u lds %zu tab %d whole %d tube h %d plane %d t %.1f rev %d\n",
+                LY, tg.nsx, tg.nry, tg.ch, tg.nchunks, grid.x, lds, tg.tab_entries, tg.whole, tg.tube_h, tg.tube_plane,
+                (double)tg.tube_h, rev);      // (t: the bound a lane's cell differences are held to -- cells, not codes as in k_yuv_tile2)
     tg.qbase = grid.x * LUTR_R2_WPB;      // (the counter is at zero: the previous launch left it so)
     const bool unit = L.unit != 0;
 

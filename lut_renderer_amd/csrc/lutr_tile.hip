@@ -675,6 +675,22 @@ void k_rgb_tile(LutConsts L_, TilePlanes P, FrameGeom G, TileGeom TG)
 
 // ================================================================= launchers
 // (device_cus, allow_lds: lutr_launch.h)
+static int g_win_nodes = 1024;       // 10 KB per wave, 40 KB per 256-thread block, 4 blocks per CU = all 160 KB
+static int g_waves_per_cu = 16;
+static const char *g_max_waves_text = nullptr;      // LUTR_MAX_WAVES as given (capped_waves, lutr_launch.h, judges it)
+static bool g_debug = false;
+static std::once_flag g_env_once;
+
+static void read_env_tuning()
+{
+    std::call_once(g_env_once, [] {
+        if (const char *e = getenv("LUTR_WIN_NODES")) { const int v = atoi(e); if (v >= 64 && v <= 2048) g_win_nodes = v; }
+        if (const char *e = getenv("LUTR_WAVES_PER_CU")) { const int v = atoi(e); if (v >= 4 && v <= 32) g_waves_per_cu = v; }
+        g_max_waves_text = getenv("LUTR_MAX_WAVES");
+        g_debug = getenv("LUTR_DEBUG") != nullptr;
+    });
+}
+
 // Split the 64 lanes of a wave between x (units of one row) and y (unit rows) so that a
 // row of `uw` units wastes as few lanes as possible; prefer wide tiles (longer bursts).
 static void plan_tiles(TileGeom *tg, int uw, int urows, int nframes, int win_nodes, int waves_per_cu, unsigned *stats,
@@ -698,7 +714,7 @@ static void plan_tiles(TileGeom *tg, int uw, int urows, int nframes, int win_nod
     tg->tiles = nframes * tg->nsx * tg->nry;
     // chunk height: 16 tile rows (a staged window is reused ~15 times); only jobs too small to give
     // half the resident waves a chunk get shorter chunks (each chunk start costs a window miss)
-    const int max_waves = device_cus() * waves_per_cu;
+    const int max_waves = capped_waves(g_max_waves_text, LUTR_WPB, device_cus() * waves_per_cu);
     int ch = 16;
     if (const char *e = getenv("LUTR_CHUNK")) { const int v = atoi(e); if (v >= 2 && v <= 256) ch = v; }
     int shrink_div = 4;
@@ -713,21 +729,9 @@ static void plan_tiles(TileGeom *tg, int uw, int urows, int nframes, int win_nod
 // persistent grid: as many waves as fit on the chip, or one per chunk if there are fewer chunks
 static int tile_blocks(const TileGeom &tg, int waves_per_cu)
 {
-    const int max_waves = device_cus() * waves_per_cu;
+    const int max_waves = capped_waves(g_max_waves_text, LUTR_WPB, device_cus() * waves_per_cu);
     const int waves = tg.nchunks < max_waves ? tg.nchunks : max_waves;
     return (waves + LUTR_WPB - 1) / LUTR_WPB;
-}
-
-static int g_win_nodes = 1024;       // 10 KB per wave, 40 KB per 256-thread block, 4 blocks per CU = all 160 KB
-static int g_waves_per_cu = 16;
-static std::once_flag g_env_once;
-
-static void read_env_tuning()
-{
-    std::call_once(g_env_once, [] {
-        if (const char *e = getenv("LUTR_WIN_NODES")) { const int v = atoi(e); if (v >= 64 && v <= 2048) g_win_nodes = v; }
-        if (const char *e = getenv("LUTR_WAVES_PER_CU")) { const int v = atoi(e); if (v >= 4 && v <= 32) g_waves_per_cu = v; }
-    });
 }
 
 // The per-code coordinate table needs equal per-channel scales (one table serves R, G and B) and a
@@ -762,6 +766,9 @@ const char *launch_rgb_tile(hipStream_t st, const LutConsts &L, const PlaneSet &
     const bool tab = plan_table(&tg, L, lds_node_rt(mode)) != 0;
     const TilePlanes TP = tile_planes(P);
     const size_t lds = (size_t)tg.tab_bytes + (size_t)LUTR_WPB * tg.win_nodes * lds_node_rt(mode);
+    if (g_debug)      // (no tube in this kernel: h, plane and t are 0)
+        fprintf(stderr, "[lutr t1] nsx %d nry %d chunk %d chunks %d blocks %u lds/block %zu win_nodes %d tab %d tube h 0 plane 0 t 0.0\n",
+                tg.nsx, tg.nry, tg.ch, tg.nchunks, grid.x, lds, tg.win_nodes, tg.tab_bytes / 8);
 #define RGB_CASE(W, I) \
     if (wide == W && mode == I) { \
         if (tab && L.unit) LUTR_LAUNCH_TILE((k_rgb_tile<W, I, 2>), L, TP, G, tg); \

@@ -1677,7 +1677,7 @@ const char *T2_ENTRY(hipStream_t st, const LutConsts &L, const YuvConsts &K, con
     tg.nry = (urows + (64 >> best) - 1) / (64 >> best);
     int waves_per_cu = 16;
     if (const Knob &e = T2_KNOB("LUTR_WAVES_PER_CU")) { const int c = e.num(); if (c >= LUTR_T2_WPB && c <= 32 && c % LUTR_T2_WPB == 0) waves_per_cu = c; }
-    const int max_waves = device_cus() * waves_per_cu;
+    const int max_waves = capped_waves(T2_KNOB("LUTR_MAX_WAVES").v, LUTR_T2_WPB, device_cus() * waves_per_cu);
     // Chunk = `ch` consecutive tile rows of a strip.  Round 2's single counter capped the claim rate (4096 waves got ~85 M atomic adds
     // per second out of it: UHD 10-bit throughput was proportional to the chunk height up to 7 tiles -- 348 / 434 / 515 / 585 Gpx/s at
     // 4 / 5 / 6 / 7 -- and flat from 8), so chunks were at least 8192 pixels.  With the two-level queue (claim_chunk: one global atomic
@@ -1717,7 +1717,7 @@ const char *T2_ENTRY(hipStream_t st, const LutConsts &L, const YuvConsts &K, con
     // The grey tube (Geom::tube_h): all of r, |g - r| and |b - r| up to H cells.  Needs the table variants (equal channel scales: the
     // chroma-only bound of map_box), a blend (nearest rounds to a node, the bound is for floor), and room left for windows.
     // H: as wide as 70 % of the block's LDS allows while every wave keeps a window of 256 nodes, at most 8 cells of a 33^3 lattice
-    // (+-64 8-bit codes of G-R and B-R; 34 x 19 x 19 fp16 nodes = 98 KB, windows of 367 nodes).  Measured, UHD yuv420p10le fast,
+    // (+-64 8-bit codes of G-R and B-R; 34 x 19 x 19 fp16 nodes = 98 KB, windows of 366 nodes).  Measured, UHD yuv420p10le fast,
     // H = 5 / 7 / 8 / 9: natural frames 611 / 620 / 628 / 636 Gpx/s, three times the chroma 516 / 521 / 530 / 519, sigma = 8 noise
     // 503 / 543 / 550 / 569, sigma = 16 250 / 388 / 481 / 500: the tube, not the windows, is what carries natural content; 9 leaves
     // windows of 197 nodes and starts to cost saturated frames.  The strict kernels (12-byte nodes) get H = 7 (below).
@@ -1733,8 +1733,8 @@ const char *T2_ENTRY(hipStream_t st, const LutConsts &L, const YuvConsts &K, con
         const float kappa = L.pre ? fmaxf(L.pre_kappa, 1e-6f) : L.sc[0] * L.scale_f;   // cells per code, at most (a shared prelut: its largest step)
         const float eps = K.max_l * (1.0f / 2097152.0f) + 1e-3f;                 // as map_box
         const float slack = 1.0f + 2.0f * L.lut_max * (1.0f / 2097152.0f) + 2e-3f;
-        // fast (8-byte nodes): at most 70 % of the block's LDS and windows of >= 256 nodes (H = 8 / 367 at 33^3).  The strict 4-tap
-        // kernels' 12-byte nodes do not fit that at H = 7; they trade window size for tube width (H = 7, 16 windows of 139 nodes
+        // fast (8-byte nodes): at most 70 % of the block's LDS and windows of >= 256 nodes (H = 8 / 366 at 33^3).  The strict 4-tap
+        // kernels' 12-byte nodes do not fit that at H = 7; they trade window size for tube width (H = 7, 16 windows of 134 nodes
         // instead of H = 6 / 277): natural +2 %, sigma-8 +0 %, sigma-16 +43 %, three times the chroma -7 % (profiles/r03_exp4.txt)
         int min_win = node == 12 ? 128 : 256, tube_pct = node == 12 ? 85 : 70;
         if (const Knob &e = T2_KNOB("LUTR_MIN_WIN")) { const int c = e.num(); if (c >= 128 && c <= 4096) min_win = c; }

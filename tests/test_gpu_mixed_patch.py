@@ -13,27 +13,13 @@ from lut_renderer_amd import cube, frames
 from lut_renderer_amd.engine import LutEngine
 from tests import _fma32_twin
 from tests._csp_files import write_csp_with_prelut
+from tests._deep_content import ramp_yuv, unit_lattice as _unit_lattice
 
 F = np.float32
 MODES = ("tetrahedral", "nearest", "trilinear")
 
 
 # ------------------------------------------------------------------ content
-def ramp_yuv(w, h, depth, csx, csy, seed, full_range=False):
-    """Natural luma; Cb runs linearly from mid - 160 to mid + 160 codes (10-bit scale) across the width, Cr the same down the
-    height; Gaussian noise of sigma 6 (10-bit scale) on every chroma sample.  Seeded."""
-    rng = np.random.default_rng(770000 + seed)
-    s = float(1 << depth) / 1024.0
-    mid = float(1 << (depth - 1))
-    ch, cw = frames.chroma_shape(w, h, csx, csy)
-    y = frames.natural_yuv(w, h, depth, csx, csy, k=seed, full_range=full_range)[0]
-    cb = mid + s * np.linspace(-160.0, 160.0, cw)[None, :] + rng.normal(0.0, 6.0 * s, size=(ch, cw))
-    cr = mid + s * np.linspace(-160.0, 160.0, ch)[:, None] + rng.normal(0.0, 6.0 * s, size=(ch, cw))
-    top = (1 << depth) - 1
-    dt = np.uint16 if depth > 8 else np.uint8
-    return [y, np.clip(np.rint(cb), 1, top - 1).astype(dt), np.clip(np.rint(cr), 1, top - 1).astype(dt)]
-
-
 def _content(name, w, h, depth, csx, csy, seed, full_range=False):
     if name == "ramp":
         return ramp_yuv(w, h, depth, csx, csy, seed, full_range)
@@ -88,13 +74,6 @@ def _eq(got, want, what):
             bad = np.argwhere(diff > 0)
             raise AssertionError(f"{what}: plane {i} differs at {len(bad)} samples, max |d|={diff.max()}, "
                                  f"first {bad[0].tolist()} got {a[tuple(bad[0])]} want {b[tuple(bad[0])]}")
-
-
-def _unit_lattice(n, seed):
-    """Every node in [0, 1] (the clip-free and fma32 kernels apply) and no two nodes alike: a wrong tap shows."""
-    t = 0.6 * cube.log709_lattice(n) + 0.4 * cube.identity_lattice(n)
-    rng = np.random.default_rng(4200 + seed)
-    return np.clip(t + rng.uniform(-0.02, 0.02, size=t.shape), 0.0, 1.0).astype(F)
 
 
 def _lut(table, prelut=None):
