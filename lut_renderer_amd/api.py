@@ -22,6 +22,10 @@ from pathlib import Path
 from typing import Dict, Optional, Sequence, Tuple
 
 from .cube import CubeLut, read_cube, read_lut
+from .formats import (check_alpha_mode, check_chain_options, check_chroma_loc, check_container_options, check_dual_options,
+                      check_lut2, check_premul_options, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt, parse_rgb_source,
+                      parse_semi_fmt, parse_size, parse_v210_fmt, premul_to_yuv, refuse_alpha_resize, source_bit_depth,
+                      v210_frame_width, yuv_side)
 from .params import ProcessingParams, VideoInfo
 from .plan import LutPlan, output_color_tags, resolve_lut_plan
 
@@ -89,15 +93,12 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
     `is_float_out_call(kw)`, and LutEngine.apply_rgb_float takes `kw["interp"]`.
     alpha_mode="premultiplied"  adds `alpha_mode` to the arguments of a yuva* -> planar YUV call or of a gbrapf32le
     float call and is a ValueError for every other call; "straight" (the default) returns what it always returned."""
-    from .engine import check_alpha_mode, check_premul_options, parse_pix_fmt
     if plan.interp not in _ENGINE_INTERP:
         raise ValueError(f"lut3d has no interpolation mode '{plan.interp}'")
-    from .engine import parse_rgb_source
     premul = check_alpha_mode(alpha_mode)
     rgb = parse_rgb_source(pix_fmt)
     if premul and rgb is not None:
-        out_rgb = parse_rgb_source(out_pix_fmt) if out_pix_fmt else rgb
-        check_premul_options(pix_fmt, out_pix_fmt, to_yuv=not (out_rgb is not None and out_rgb.floating))
+        check_premul_options(pix_fmt, out_pix_fmt, to_yuv=premul_to_yuv(pix_fmt, out_pix_fmt))
     if rgb is not None and rgb.floating:
         out = parse_rgb_source(out_pix_fmt) if out_pix_fmt else rgb
         if out is not None and out.floating:
@@ -131,7 +132,6 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
     # a semi-planar source or output (nv12, p010le, ..) is the same chain on another container
     # (so is a packed 4:2:2 one: uyvy422, y210le, ..)
     # (and v210)
-    from .engine import check_container_options, parse_packed_yuv_fmt, parse_semi_fmt, parse_v210_fmt
     check_container_options(pix_fmt, out_pix_fmt, kinds=("v210", "packed"))     # names the packings this path does not take
     semi_src = parse_semi_fmt(pix_fmt) or parse_packed_yuv_fmt(pix_fmt) or parse_v210_fmt(pix_fmt)
     src = semi_src or parse_pix_fmt(pix_fmt)
@@ -164,7 +164,6 @@ def dual_call_for(kw: dict, second_pix_fmt: str, chroma_loc: Optional[str] = Non
     """Keyword arguments of LutEngine.apply_yuv_dual from those `engine_call_for` returned for the first output
     (with `dither` filled in, if any) and the name of the second one.  ValueError for an RGB / float / semi-planar / packed side,
     dither, chroma_loc and a resize."""
-    from .engine import check_dual_options
     check_dual_options(kw.get("pix_fmt"), kw.get("out_pix_fmt"), second_pix_fmt, kw.get("dither", "none"), chroma_loc, out_size)
     dual = {k: v for k, v in kw.items() if k != "dither"}
     dual["out2_pix_fmt"] = second_pix_fmt.replace("yuvj", "yuv")
@@ -176,7 +175,6 @@ def chain_call_for(kw: dict, interp2: Optional[str] = None, chroma_loc: Optional
     """Keyword arguments of LutEngine.apply_yuv_chain from those `engine_call_for` returned (with `dither` filled
     in, if any).  `interp2` goes through the whitelist / fallback `interp` went through (plan.py; None = the first LUT's mode).
     ValueError for an alpha / RGB / float / semi-planar / packed / v210 side, dither, chroma_loc, a resize and a second output."""
-    from .engine import check_chain_options
     from .plan import INTERP_WHITELIST
     check_chain_options(kw.get("pix_fmt"), kw.get("out_pix_fmt"), kw.get("dither", "none"), chroma_loc, out_size, second_pix_fmt)
     chain = {k: v for k, v in kw.items() if k != "dither"}
@@ -190,13 +188,11 @@ def chain_call_for(kw: dict, interp2: Optional[str] = None, chroma_loc: Optional
 
 def is_rgb_call(kw: dict) -> bool:
     """True when `engine_call_for` returned arguments of `apply_rgb_to_yuv` (an RGB source)."""
-    from .engine import parse_rgb_source
     return parse_rgb_source(kw.get("pix_fmt")) is not None
 
 
 def is_float_out_call(kw: dict) -> bool:
     """True when `engine_call_for` returned a float source with a float output (LutEngine.apply_rgb_float)."""
-    from .engine import parse_rgb_source
     out = parse_rgb_source(kw.get("out_pix_fmt"))
     return out is not None and out.floating
 
@@ -287,15 +283,12 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         raise ValueError("devices must name at least one GPU")
     out_size = None
     if resolution is not None:
-        from .engine import parse_size
         if not isinstance(resolution, str):
             raise ValueError(f"resolution is a 'WxH' string, got {resolution!r}")
         out_size = parse_size(resolution)
         from .multigpu import LutEngineGroup
         if isinstance(engine, LutEngineGroup) or (engine is None and len(devices) > 1):
             raise ValueError("resolution needs a single device")
-    from .engine import (check_chroma_loc, check_container_options, packed_frame_width, parse_packed_yuv_fmt, parse_rgb_source,
-                         parse_v210_fmt, source_bit_depth, v210_frame_width, yuv_side)
     rgb_src = parse_rgb_source(pix_fmt)
     if rgb_src is not None and rgb_src.packed:
         got_w, got_h = planes.shape[-2], planes.shape[-3]
@@ -319,7 +312,6 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     # lattice has none)
     plan = resolve_lut_plan(params, cube if isinstance(cube, (str, Path)) else "engine.cube", info)
     kw = engine_call_for(plan, pix_fmt, out_pix_fmt, alpha_mode)
-    from .engine import refuse_alpha_resize
     refuse_alpha_resize(kw.get("out_pix_fmt"), out_size)        # (the resize takes three planes)
     # ffmpeg.py:305-307: any value other than "error_diffusion" leaves the chain without a dither filter
     kw["dither"] = "error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none"
@@ -330,7 +322,6 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     if cube2 is None and interp2 is not None:
         raise ValueError("interp2 is the mode of the second LUT: it needs cube2")
     if "alpha_mode" in kw:
-        from .engine import check_premul_options
         check_premul_options(kw["pix_fmt"], kw["out_pix_fmt"], dither=kw["dither"], chroma_loc=chroma_loc, out_size=out_size,
                              range_src=kw.get("range_src", "tv"), range_in=kw.get("range_in"), lut_depth=kw.get("lut_depth"),
                              out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None)
@@ -366,7 +357,6 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     if cube is not None:
         lut = cube if isinstance(cube, CubeLut) else _cached_cube(Path(cube))
     if cube2 is not None:
-        from .engine import check_lut2
         lut2 = cube2 if isinstance(cube2, CubeLut) else _cached_cube(Path(cube2))
         check_lut2(lut2)
     with eng._lock:                 # upload, precision and launch of ONE task: no other thread's call gets in between

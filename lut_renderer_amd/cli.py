@@ -20,6 +20,9 @@ import signal
 import sys
 import time
 
+from .formats import (check_chroma_loc, check_container_options, check_lut2, check_premul_options, parse_size, refuse_alpha_resize,
+                      source_bit_depth)
+
 
 def _hms(seconds: float) -> str:
     seconds = max(0.0, seconds)
@@ -93,7 +96,6 @@ def build_parser() -> argparse.ArgumentParser:
 def plan_from_args(args):
     """The LutPlan and engine call the options select -- the same resolution `build_command` performs (plan.py)."""
     from .api import engine_call_for
-    from .engine import check_container_options, source_bit_depth
     from .params import ProcessingParams, VideoInfo
     from .plan import resolve_lut_plan
     w, h = (int(v) for v in args.size.lower().split("x"))
@@ -107,7 +109,6 @@ def plan_from_args(args):
     from .api import is_float_out_call
     engine_dither = getattr(args, "engine_dither", None)
     if "alpha_mode" in kw:
-        from .engine import check_premul_options
         check_premul_options(kw["pix_fmt"], kw["out_pix_fmt"], chroma_loc=getattr(args, "chroma_loc", None),
                              dither="error_diffusion" if args.zscale_dither == "error_diffusion" else engine_dither or "none",
                              out_size=getattr(args, "out_size", None), range_src=kw.get("range_src", "tv"),
@@ -127,11 +128,9 @@ def plan_from_args(args):
         check_container_options(kw["pix_fmt"], kw["out_pix_fmt"], kw.get("dither", "none"), getattr(args, "chroma_loc", None),
                                 getattr(args, "out_size", None))
     if getattr(args, "chroma_loc", None):
-        from .engine import check_chroma_loc
         check_chroma_loc(args.chroma_loc, kw.get("dither", "none"), kw["pix_fmt"], kw["out_pix_fmt"])
         kw["chroma_loc"] = args.chroma_loc
     if getattr(args, "out_size", None):
-        from .engine import parse_size, refuse_alpha_resize
         parse_size(args.out_size)
         refuse_alpha_resize(kw.get("out_pix_fmt"), args.out_size)
     second_out, second_fmt = getattr(args, "second_output", None), getattr(args, "second_pix_fmt", None)
@@ -175,7 +174,7 @@ def main(argv=None) -> int:
         if second is not None and os.path.isfile(second) and not args.y:
             raise FileExistsError(f"{second} exists (pass -y to overwrite)")
         from .cube import read_lut
-        from .engine import LutEngine, check_lut2
+        from .engine import LutEngine
         from .stream import HostPipeline
 
         lut2 = None if args.cube2 is None else read_lut(args.cube2)

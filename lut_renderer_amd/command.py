@@ -19,6 +19,8 @@ from dataclasses import dataclass, field
 from pathlib import Path
 from typing import List, Optional, Tuple
 
+from .formats import (check_alpha_mode, check_chain_options, check_dual_options, check_premul_options, parse_rgb_source,
+                      premul_to_yuv)
 from .params import ProcessingParams, Task, VideoInfo
 from .plan import LutPlan, output_color_tags, resolve_lut_plan, resolve_pix_fmt
 
@@ -276,8 +278,7 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     "straight" keeps the argv as it was): a yuva* source with a planar YUV output or gbrapf32le kept float; not with a full-range
     prologue, dither, `chroma_loc`, `gpu_resize`, a second output or a second LUT.  ffmpeg's chain has no such step."""
     import sys as _sys
-    if alpha_mode not in ("straight", "premultiplied"):
-        raise ValueError(f"unknown alpha_mode '{alpha_mode}' (straight | premultiplied)")
+    premul = check_alpha_mode(alpha_mode)
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
     if chroma_loc is not None and chroma_loc not in ("left", "center", "topleft"):
@@ -297,7 +298,9 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     cmd += ["-i", str(source), "-o", str(output), "--size", f"{source_info.width}x{source_info.height}",
             "--pix-fmt", source_info.pix_fmt]
     pix_fmt = resolve_pix_fmt(params, source_info, notes) if params.video_codec else ""
-    if _is_float_source(source_info.pix_fmt):
+    src_rgb = parse_rgb_source(str(source_info.pix_fmt))
+    float_src = src_rgb is not None and src_rgb.floating
+    if float_src:
         # a float source: without a resolved output format the stage stays float (no --out-pix-fmt, no dither)
         if chroma_loc is not None:
             raise ValueError("chroma siting (chroma_loc) is not defined for an RGB source")
@@ -328,9 +331,11 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     if engine_dither is not None:
         from .api import resolve_engine_dither
         resolve_engine_dither(engine_dither, "error_diffusion" if "--zscale-dither" in cmd else "none")
-        if not pix_fmt and _is_float_source(source_info.pix_fmt):
+        if not pix_fmt and float_src:
             raise ValueError("a float output takes no dither")
         cmd += ["--engine-dither", engine_dither]
+    # (the dither of the call, as the checks below take it: rendered into cmd above)
+    dither = "error_diffusion" if "--zscale-dither" in cmd else ("blue_noise" if "--engine-dither" in cmd else "none")
     if chroma_loc is not None:
         if "--zscale-dither" in cmd or "--engine-dither" in cmd:
             raise ValueError("error-diffusion dither is not defined with sited chroma resampling (chroma_loc)")
@@ -347,46 +352,35 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     if second_output is not None:
         if str(second_output) == "-":
             raise ValueError("second_output is a file or FIFO, not '-'")
-        from .engine import check_dual_options
-        check_dual_options(str(source_info.pix_fmt), pix_fmt or None, second_pix_fmt,
-                           "error_diffusion" if "--zscale-dither" in cmd else ("blue_noise" if "--engine-dither" in cmd else "none"), chroma_loc,
+        check_dual_options(str(source_info.pix_fmt), pix_fmt or None, second_pix_fmt, dither, chroma_loc,
                            params.resolution if "--out-size" in cmd else None)
         cmd += ["--second-output", str(second_output), "--second-pix-fmt", second_pix_fmt]
     if cube2 is None and interp2 is not None:
         raise ValueError("interp2 is the mode of the second LUT: it needs cube2")
     if cube2 is not None:
-        from .engine import check_chain_options
         from .plan import INTERP_WHITELIST
-        check_chain_options(str(source_info.pix_fmt), pix_fmt or None,
-                            "error_diffusion" if "--zscale-dither" in cmd else ("blue_noise" if "--engine-dither" in cmd else "none"),
-                            chroma_loc, params.resolution if "--out-size" in cmd else None, second_pix_fmt)
+        check_chain_options(str(source_info.pix_fmt), pix_fmt or None, dither, chroma_loc,
+                            params.resolution if "--out-size" in cmd else None, second_pix_fmt)
         cmd += ["--cube2", str(cube2)]
         if interp2 is not None:
             cmd += ["--interp2", interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"]
-    if alpha_mode == "premultiplied":
-        from .engine import check_premul_options
+    if premul:
         src_fmt = str(source_info.pix_fmt).replace("yuvj", "yuv")
-        check_premul_options(src_fmt, pix_fmt or None,
-                             dither="error_diffusion" if "--zscale-dither" in cmd else ("blue_noise" if "--engine-dither" in cmd else "none"),
-                             chroma_loc=chroma_loc, out_size=params.resolution if "--out-size" in cmd else None,
+        check_premul_options(src_fmt, pix_fmt or None, dither=dither, chroma_loc=chroma_loc,
+                             out_size=params.resolution if "--out-size" in cmd else None,
                              range_src="pc" if plan.prologue else "tv", range_in=plan.prologue_out_range if plan.prologue else "tv",
                              lut_depth=8 if plan.prologue else None, out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None,
-                             to_yuv=_is_rgb_source(src_fmt) or (_is_float_source(src_fmt) and bool(pix_fmt) and not _is_float_source(pix_fmt)))
+                             to_yuv=premul_to_yuv(src_fmt, pix_fmt or None))
         cmd += ["--alpha-mode", "premultiplied"]
     return cmd
 
 
 def _is_rgb_source(pix_fmt) -> bool:
-    """gbrp* / gbrap* or one of the packed RGB names the engine takes as a source (`_native.PACKED_FORMATS`)."""
+    """gbrp* / gbrap* at any number of bits, or one of the packed RGB names the engine takes as a source
+    (`_native.PACKED_FORMATS`).  Not `parse_rgb_source`: that one takes the float names too and no depth outside 8..16."""
     from ._native import PACKED_FORMATS
     name = str(pix_fmt or "")
     return name in PACKED_FORMATS or bool(re.match(r"^gbra?p(\d+)?(le)?$", name))
-
-
-def _is_float_source(pix_fmt) -> bool:
-    """gbrpf32le / gbrapf32le, the planar float RGB sources (`_native.FLOAT_FORMATS`)."""
-    from ._native import FLOAT_FORMATS
-    return str(pix_fmt or "") in FLOAT_FORMATS
 
 
 #: planar formats the engine's resize takes (DESIGN.md 3.7); packed RGB keeps -s on the encoder

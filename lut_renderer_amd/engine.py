@@ -12,9 +12,7 @@ Replaces: the `ffmpeg` child process the reference starts per task
 from __future__ import annotations
 
 import ctypes as C
-import re
 import threading
-from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -22,434 +20,35 @@ import torch
 
 from . import _native
 from .cube import CubeLut, read_cube, read_lut
-
-_PIXFMT_RE = re.compile(r"^(yuvj?|yuva|gbra?)(420|422|444)?p(\d+)?(le)?$")
-
-
-class _YuvSide:
-    """What the three format classes share: one side of a YUV call, from the `depth`, `csx`, `csy` of its container."""
-
-    @property
-    def code(self) -> int:
-        return _native.fmt_code(self.depth, self.csx, self.csy)
-
-    @property
-    def np_dtype(self):
-        return np.uint8 if self.depth <= 8 else np.uint16
-
-    def layout(self) -> _native.YuvLayout:
-        """This side as lutr_apply_yuv_semi takes it (here: three planes)."""
-        return _native.YuvLayout(0, 0, 0)
-
-    def packing(self) -> _native.YuvPacking:
-        """This side as lutr_apply_yuv_packed takes it (here: three planes)."""
-        return _native.YuvPacking(0, 0, 0)
-
-
-class _YuvContainer(_YuvSide):
-    """A YUV container that is not three planes: always YUV, never yuvj*, and with a planar twin."""
-    family = "yuv"
-    full_range = False
-
-    @property
-    def planar(self) -> str:
-        """The planar format that holds the same samples (nv12 -> yuv420p, p210le -> yuv422p10le, uyvy422 -> yuv422p)."""
-        return f"yuv{'420' if self.csy else '422'}p" + ("" if self.depth == 8 else f"{self.depth}le")
-
-
-@dataclass(frozen=True)
-class PixFmt(_YuvSide):
-    """Parsed FFmpeg planar pixel-format name (the ones this path can meet)."""
-    name: str
-    family: str      # "yuv" or "gbr"
-    depth: int
-    csx: int
-    csy: int
-    full_range: bool  # yuvj* (legacy full-range marker, media_info.py:145-147)
-    alpha: bool = False  # yuva* / gbrap*: a fourth, luma-sized plane at the same depth (DESIGN.md 3.16)
-
-    @property
-    def nplanes(self) -> int:
-        return 4 if self.alpha else 3
-
-    @property
-    def colour(self) -> "PixFmt":
-        """The three-plane format of the same colour planes (yuva420p10le -> yuv420p10le, gbrap -> gbrp); itself without alpha."""
-        if not self.alpha:
-            return self
-        return parse_pix_fmt(self.name.replace("yuva", "yuv", 1).replace("gbrap", "gbrp", 1))
-
-    def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
-        if self.family == "gbr" or plane in (0, 3):
-            return h, w
-        return (h + (1 << self.csy) - 1) >> self.csy, (w + (1 << self.csx) - 1) >> self.csx
-
-
-@dataclass(frozen=True)
-class SemiFmt(_YuvContainer):
-    """A semi-planar YUV format: a luma plane and one plane of interleaved chroma pairs."""
-    name: str
-    depth: int
-    csx: int
-    csy: int
-    swap: int         # 1: Cr comes first in a pair (nv21)
-    shift: int        # left shift of the code inside its 16-bit container (p010le: 6)
-
-    nplanes = 2
-
-    def layout(self) -> _native.YuvLayout:
-        return _native.YuvLayout(1, self.swap, self.shift)
-
-    def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
-        """Plane 0: (h, w) luma samples; plane 1: (chroma rows, 2 * pairs per row) chroma samples."""
-        if plane == 0:
-            return h, w
-        return (h + (1 << self.csy) - 1) >> self.csy, 2 * ((w + 1) >> 1)
-
-
-@dataclass(frozen=True)
-class PackedYuvFmt(_YuvContainer):
-    """A packed 4:2:2 YUV format: one buffer, rows of ceil(w / 2) groups of four samples."""
-    name: str
-    depth: int
-    order: int        # the samples of a group in memory: 0 Y0 Cb Y1 Cr, 1 Cb Y0 Cr Y1 (uyvy422), 2 Y0 Cr Y1 Cb (yvyu422)
-    shift: int        # left shift of the code inside its 16-bit container (y210le: 6)
-
-    nplanes = 1
-    csx, csy = 1, 0
-
-    def packing(self) -> _native.YuvPacking:
-        return _native.YuvPacking(1, self.order, self.shift)
-
-    def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
-        """The one buffer: (h, 4 * groups per row) samples."""
-        return h, 4 * ((w + 1) >> 1)
-
-
-@dataclass(frozen=True)
-class V210Fmt(_YuvContainer):
-    """v210: one buffer of 32-bit words, rows of ceil(w / 6) groups of four words, three 10-bit codes a word."""
-    name: str
-    depth: int
-
-    nplanes = 1
-    csx, csy = 1, 0
-    itemsize = 4      # the buffer's elements are the words (torch.int32)
-
-    @staticmethod
-    def groups(w: int) -> int:
-        """Groups of six luma samples in a row."""
-        return (w + 5) // 6
-
-    @staticmethod
-    def row_bytes(w: int) -> int:
-        """The default row stride: rows are padded to whole blocks of 128 bytes (48 luma samples)."""
-        return 128 * ((w + 47) // 48)
-
-    def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
-        """The one buffer at the default stride: (h, 32 * ceil(w / 48)) words."""
-        return h, self.row_bytes(w) // 4
-
-
-def parse_v210_fmt(name: Optional[str]) -> Optional[V210Fmt]:
-    """The `V210Fmt` of a name of `_native.V210_FORMATS` ("v210"), or None for any other name -- `parse_pix_fmt` rejects the name
-    and `parse_semi_fmt` / `parse_packed_yuv_fmt` return None for it."""
-    if name not in _native.V210_FORMATS:
-        return None
-    return V210Fmt(name, *_native.V210_FORMATS[name])
-
-
-def parse_packed_yuv_fmt(name: Optional[str]) -> Optional[PackedYuvFmt]:
-    """The packed 4:2:2 format `name` stands for (a name of `_native.PACKED_YUV_FORMATS`), or None for any other name --
-    `parse_pix_fmt` keeps rejecting these and `parse_semi_fmt` keeps returning None for them."""
-    if name not in _native.PACKED_YUV_FORMATS:
-        return None
-    return PackedYuvFmt(name, *_native.PACKED_YUV_FORMATS[name])
-
-
-def parse_semi_fmt(name: Optional[str]) -> Optional[SemiFmt]:
-    """The semi-planar format `name` stands for (a name of `_native.SEMI_FORMATS`), or None for any other name --
-    `parse_pix_fmt` keeps rejecting these: it describes three-plane frames."""
-    if name not in _native.SEMI_FORMATS:
-        return None
-    return SemiFmt(name, *_native.SEMI_FORMATS[name])
-
-
-def yuv_side(name: str):
-    """One side of `apply_yuv`: the `SemiFmt`, `PackedYuvFmt`, `V210Fmt` or planar `PixFmt` of a YUV format name (yuvj* read as
-    yuv*)."""
-    return parse_semi_fmt(name) or parse_packed_yuv_fmt(name) or parse_v210_fmt(name) or \
-        parse_pix_fmt((name or "").replace("yuvj", "yuv"))
-
-
-#: packed YUV names FFmpeg has that this path does not take: 4:4:4 packings and big-endian containers
-_PACKED_YUV_UNSUPPORTED = ("vuyx", "vuya", "ayuv", "uyva", "xv30le", "xv36le", "xv48le", "ayuv64le", "v30xle", "y210be", "y212be",
-                           "y216be", "xv30be", "xv36be", "xv48be", "ayuv64be")
-
-
-#: container kind -> (its parser, what the RGB refusal calls it, what every other refusal calls it)
-_CONTAINER_KINDS = {"v210": (parse_v210_fmt, "v210", "v210"),
-                    "packed": (parse_packed_yuv_fmt, "packed", "packed 4:2:2"),
-                    "semi": (parse_semi_fmt, "semi-planar", "semi-planar")}
-
-#: v210's relatives FFmpeg knows as codecs, which this path does not take
-_V210_UNSUPPORTED = ("v210x", "v410", "v308", "v408", "r210", "r10k")
-
-
-def source_bit_depth(name: Optional[str]) -> Optional[int]:
-    """`params.infer_bit_depth` for a source name that may be a container: p010le and y210le say their depth themselves (the
-    digits are not a depth after a 'p')."""
-    from .params import infer_bit_depth
-    side = parse_semi_fmt(name) or parse_packed_yuv_fmt(name) or parse_v210_fmt(name)
-    return side.depth if side else infer_bit_depth(name)
-
-
-def check_container_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
-                            out_size=None, kinds=("v210", "packed", "semi"), width: Optional[int] = None) -> Optional[str]:
-    """The checks `apply_yuv` makes before any GPU work when a side is not three planes: "v210" when a side is v210 (DESIGN.md
-    3.14), "packed" when a side is packed 4:2:2, "semi" when one is semi-planar, None when both
-    are planar (nothing checked but the packed names this path does not take).  Refused: an RGB side, two kinds of container in
-    one call, a subsampling change (packed and v210: only a source that is not 4:2:2), chroma_loc, error-diffusion dither,
-    out_size, and a `width` (`apply_yuv`'s, for rows that cannot tell it) when no side is packed or v210."""
-    out_name = out_pix_fmt or pix_fmt
-    for kind in kinds:
-        parse, short, noun = _CONTAINER_KINDS[kind]
-        packed, v210 = kind == "packed", kind == "v210"
-        if kind == "semi" and width is not None:
-            raise ValueError("width is for a packed 4:2:2 side; planar and semi-planar frames tell their own")
-        for name in (pix_fmt, out_name) if packed else ():
-            if name in _PACKED_YUV_UNSUPPORTED:
-                raise ValueError(f"'{name}' is not supported: packed YUV frames are taken as little-endian 4:2:2 "
-                                 f"({', '.join(_native.PACKED_YUV_FORMATS)})")
-        for name in (pix_fmt, out_name) if v210 else ():
-            if name in _V210_UNSUPPORTED:
-                raise ValueError(f"'{name}' is not supported: of this family only v210 is taken")
-        if parse(pix_fmt) is None and parse(out_name) is None:
-            continue
-        if parse_rgb_source(pix_fmt) is not None:
-            raise ValueError(f"an RGB source ('{pix_fmt}') takes a planar YUV out_pix_fmt, not the {short} '{out_pix_fmt}'")
-        if v210:
-            if parse_rgb_source(out_name) is not None:
-                raise ValueError(f"v210 frames go with YUV formats on both sides ('{pix_fmt}' -> '{out_name}')")
-            for other, what in ((parse_semi_fmt, "semi-planar"), (parse_packed_yuv_fmt, "packed 4:2:2")):
-                if other(pix_fmt) is not None or other(out_name) is not None:
-                    raise ValueError(f"a {what} side together with a v210 side is not supported ('{pix_fmt}' -> '{out_name}')")
-        if packed and (parse_semi_fmt(pix_fmt) is not None or parse_semi_fmt(out_name) is not None):
-            raise ValueError(f"a semi-planar side together with a packed side is not supported ('{pix_fmt}' -> '{out_name}')")
-        a, b = yuv_side(pix_fmt), yuv_side(out_name)
-        if getattr(a, "alpha", False) or getattr(b, "alpha", False):
-            raise ValueError(f"alpha is carried between planar sides only, not with a {noun} side ('{pix_fmt}' -> '{out_name}')")
-        if a.family != "yuv" or b.family != "yuv":
-            raise ValueError(f"{noun} frames go with YUV formats on both sides "
-                             f"('{pix_fmt}' -> '{out_name if packed or v210 else out_pix_fmt}')")
-        if (packed or v210) and (a.csx, a.csy) != (1, 0):
-            raise ValueError(f"a {short} destination takes a 4:2:2 source: no chroma subsampling change into '{out_name}' "
-                             f"('{pix_fmt}' -> '{out_name}')")
-        if kind == "semi" and (a.csx, a.csy) != (b.csx, b.csy):
-            raise ValueError(f"a chroma subsampling change is not supported with a semi-planar side "
-                             f"('{pix_fmt}' -> '{out_pix_fmt}')")
-        if chroma_loc is not None:
-            raise ValueError(f"sited chroma resampling (chroma_loc) is not supported with a {noun} side")
-        if dither != "none":
-            raise ValueError(f"error-diffusion dither is not supported with a {noun} side")
-        if out_size is not None:
-            raise ValueError(f"a resize (out_size) is not supported with a {noun} side")
-        return kind
-    return None
-
-
-def check_packed_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
-                         out_size=None) -> bool:
-    """`check_container_options` for the packed 4:2:2 kind alone: False when neither side is packed, True otherwise."""
-    return check_container_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size, ("packed",)) is not None
-
-
-def check_semi_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
-                       out_size=None) -> bool:
-    """`check_container_options` for the semi-planar kind alone (a packed side is not looked at): False when neither side is
-    semi-planar, True otherwise."""
-    return check_container_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size, ("semi",)) is not None
-
-
-def packed_frame_width(fmt, planes, width: Optional[int] = None) -> int:
-    """The frame width of one side's planes: a packed buffer holds 4 * ceil(w / 2) samples per row, so an odd width has to be
-    named (`width`); every other side tells it itself."""
-    first = planes if isinstance(planes, torch.Tensor) else planes[0]
-    if fmt.nplanes != 1:
-        w = first.shape[-1]
-    else:
-        if first.shape[-1] % 4:
-            raise ValueError(f"'{fmt.name}' rows hold whole groups of four samples, got {first.shape[-1]} samples")
-        w = first.shape[-1] // 2 if width is None else int(width)
-        if 4 * ((w + 1) >> 1) != first.shape[-1]:
-            raise ValueError(f"width {w} does not match '{fmt.name}' rows of {first.shape[-1]} samples")
-    if width is not None and int(width) != w:
-        raise ValueError(f"width {width} does not match the planes ({w})")
-    return w
-
-
-def v210_frame_width(fin, fout, src, dst, width: Optional[int] = None) -> int:
-    """The frame width of a call with a v210 side: a planar side tells it (the source's planes, else the destination's when
-    given); v210 rows are padded, so with none `width` is required.  Either way the v210 rows must hold it."""
-    told = None
-    if fin.nplanes == 3:
-        told = src[0].shape[-1]
-    elif fout.nplanes == 3 and dst is not None:
-        told = dst[0].shape[-1]
-    if told is None and width is None:
-        raise ValueError("width is required with v210 frames when no planar side tells it: v210 rows are padded")
-    if told is not None and width is not None and int(width) != told:
-        raise ValueError(f"width {width} does not match the planes ({told})")
-    w = told if told is not None else int(width)
-    if w < 1:
-        raise ValueError(f"bad width {w}")
-    return w
-
-
-def parse_pix_fmt(name: str) -> PixFmt:
-    m = _PIXFMT_RE.match(name or "")
-    if not m:
-        raise ValueError(f"unsupported pixel format '{name}'")
-    fam, sub, depth, _le = m.groups()
-    depth_i = int(depth) if depth else 8
-    if not 8 <= depth_i <= 16:
-        raise ValueError(f"unsupported bit depth in '{name}'")
-    if fam in ("gbr", "gbra"):
-        if sub:
-            raise ValueError(f"unsupported pixel format '{name}'")
-        return PixFmt(name, "gbr", depth_i, 0, 0, True, fam == "gbra")
-    if not sub:
-        raise ValueError(f"unsupported pixel format '{name}'")
-    csx, csy = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}[sub]
-    return PixFmt(name, "yuv", depth_i, csx, csy, fam == "yuvj", fam == "yuva")
-
-
-@dataclass(frozen=True)
-class RgbSource:
-    """An RGB source format of `LutEngine.apply_rgb_to_yuv`: planar `gbrp*`, a packed name of `_native.PACKED_FORMATS`, or a
-    planar float name of `_native.FLOAT_FORMATS`."""
-    name: str
-    packed: bool
-    depth: int        # the depth lut3d runs at: the source's (packed: 8 or 16); float: 16, the depth of the output stage's codes
-    ncomp: int        # components per pixel of a packed image; 1 for planar
-    code: int         # src_kind of lutr_apply_rgb_to_yuv: 0 planar, else LUTR_PACKED(...)
-    floating: bool = False   # 32-bit float planes: lutr_apply_planar_rgb_f32 / lutr_apply_rgbf_to_yuv
-    nplanes: int = 3         # planes per frame of a planar source (gbrap*, gbrapf32le: 4, the last one alpha)
-
-    @property
-    def alpha_slot(self) -> Optional[int]:
-        """The component index of a packed format's real alpha (rgba: 3, argb: 0), None for every other format -- rgb0's pad byte
-        is not alpha."""
-        return _native.PACKED_ALPHA.get(self.name) if self.packed else None
-
-    @property
-    def itemsize(self) -> int:
-        return 4 if self.floating else 1 if self.depth <= 8 else 2
-
-    def frame_bytes(self, w: int, h: int) -> int:
-        return h * w * (self.ncomp if self.packed else self.nplanes) * self.itemsize
-
-
-def parse_rgb_source(name: Optional[str]) -> Optional[RgbSource]:
-    """The RGB source `name` stands for, or None when it is not an RGB format the engine takes (`parse_pix_fmt` keeps rejecting
-    packed names: it describes planar frames)."""
-    if name in _native.PACKED_FORMATS:
-        bits, nc, ro, go, bo = _native.PACKED_FORMATS[name]
-        return RgbSource(name, True, bits, nc, _native.packed_code(bits, nc, ro, go, bo))
-    if name in _native.FLOAT_FORMATS:
-        return RgbSource(name, False, 16, 1, 0, True, _native.FLOAT_FORMATS[name])
-    try:
-        fmt = parse_pix_fmt(name)
-    except ValueError:
-        return None
-    return RgbSource(name, False, fmt.depth, 1, 0, False, fmt.nplanes) if fmt.family == "gbr" else None
-
-
-def chroma_loc_code(chroma_loc: Optional[str]) -> int:
-    """enum lutr_chroma_loc for a chroma_location name (None = replicate); ValueError for any other name."""
-    if chroma_loc is None:
-        return _native.CHROMA_REPLICATE
-    if chroma_loc not in _native.CHROMA_LOC:
-        raise ValueError(f"unknown chroma location '{chroma_loc}' (None | {' | '.join(_native.CHROMA_LOC)})")
-    return _native.CHROMA_LOC[chroma_loc]
-
-
-def check_chroma_loc(chroma_loc: Optional[str], dither: str = "none", pix_fmt: Optional[str] = None,
-                     out_pix_fmt: Optional[str] = None) -> None:
-    """The checks `apply_yuv` makes of `chroma_loc` before any GPU work: a known name, no error-diffusion dither with it, and
-    (given the two pixel formats) no chroma subsampling change with it -- sited resampling across layouts is not defined."""
-    chroma_loc_code(chroma_loc)
-    if chroma_loc is not None and dither != "none":
-        raise ValueError("error-diffusion dither is not defined with sited chroma resampling (chroma_loc)")
-    if chroma_loc is not None and pix_fmt and out_pix_fmt and changes_subsampling(pix_fmt, out_pix_fmt):
-        raise ValueError(f"sited chroma resampling (chroma_loc) is not defined with a chroma subsampling change "
-                         f"('{pix_fmt}' -> '{out_pix_fmt}'); drop chroma_loc to replicate / average over the chroma blocks")
-
-
-def changes_subsampling(pix_fmt: str, out_pix_fmt: Optional[str]) -> bool:
-    """True when the two planar YUV formats differ in chroma subsampling."""
-    if not out_pix_fmt:
-        return False
-    a, b = parse_pix_fmt(pix_fmt.replace("yuvj", "yuv")), parse_pix_fmt(out_pix_fmt.replace("yuvj", "yuv"))
-    return (a.csx, a.csy) != (b.csx, b.csy)
-
-
-#: keywords of `apply_yuv` that the two-output pass does not take (DESIGN.md 3.13)
-_DUAL_NOT_TAKEN = {"dither": "error-diffusion dither", "chroma_loc": "sited chroma resampling (chroma_loc)",
-                   "out_size": "a resize (out_size)", "resize_chunk": "a resize (out_size)",
-                   "width": "a packed side (width)"}
-
-
-def dual_side(name: Optional[str], what: str) -> PixFmt:
-    """One side of `apply_yuv_dual`, a planar YUV format (yuvj* read as yuv*); ValueError for RGB, float, semi-planar and packed
-    names.  `what` names the argument in the message."""
-    if not name:
-        raise ValueError(f"the two-output pass needs {what}")
-    if parse_semi_fmt(name) is not None or parse_packed_yuv_fmt(name) is not None or name in _PACKED_YUV_UNSUPPORTED:
-        raise ValueError(f"the two-output pass takes planar YUV on every side: {what} '{name}' is a semi-planar or packed container")
-    if parse_v210_fmt(name) is not None:
-        raise ValueError(f"the two-output pass takes planar YUV on every side: {what} '{name}' is a v210 container")
-    if parse_rgb_source(name) is not None:
-        raise ValueError(f"the two-output pass takes planar YUV on every side: {what} '{name}' is an RGB format")
-    fmt = parse_pix_fmt(name.replace("yuvj", "yuv"))
-    if fmt.family != "yuv":
-        raise ValueError(f"the two-output pass takes planar YUV on every side: {what} '{name}' is an RGB format")
-    return fmt
-
-
-def check_dual_options(pix_fmt: str, out_pix_fmt: Optional[str], out2_pix_fmt: Optional[str], dither: str = "none",
-                       chroma_loc: Optional[str] = None, out_size=None) -> Tuple[PixFmt, PixFmt, PixFmt]:
-    """The checks `apply_yuv_dual` makes of its formats and options before any GPU work: three planar YUV
-    sides, no dither, chroma_loc or out_size.  Returns the three parsed formats (source, first output, second output)."""
-    fin = dual_side(pix_fmt, "pix_fmt")
-    f1 = dual_side(out_pix_fmt or pix_fmt, "out_pix_fmt")
-    f2 = dual_side(out2_pix_fmt, "out2_pix_fmt")
-    if dither != "none":
-        raise ValueError("error-diffusion dither is not supported with a second output")
-    if chroma_loc is not None:
-        raise ValueError("sited chroma resampling (chroma_loc) is not supported with a second output")
-    if out_size is not None:
-        raise ValueError("a resize (out_size) is not supported with a second output")
-    return fin, f1, f2
-
-
-def refuse_dual_keywords(kw: dict) -> None:
-    """ValueError when `kw` holds a keyword of `apply_yuv` that the two-output pass does not take, whatever its value."""
-    for k, what in _DUAL_NOT_TAKEN.items():
-        if k in kw:
-            raise ValueError(f"{what} is not supported with a second output: apply_yuv_dual takes no '{k}'")
+# (the formats and the checks of names and options live in formats.py; the names callers have always imported from here stay)
+from .formats import (_ALPHA_RESIZE, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, V210Fmt, chain_interp, chain_side,  # noqa: F401
+                      changes_subsampling, check_alpha_mode, check_chain_options, check_chroma_loc, check_container_options,
+                      check_dual_options, check_lut2, check_packed_options, check_premul_options, check_semi_options,
+                      chroma_loc_code, dual_side, has_prologue, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt,
+                      parse_rgb_source, parse_semi_fmt, parse_size, parse_v210_fmt, refuse_alpha_resize, refuse_chain_keywords,
+                      refuse_dual_keywords, source_bit_depth, v210_frame_width, yuv_side)
+
+_NOT_TENSORS = "planes must be torch tensors resident on the engine's GPU"
+#: what a planar side with the wrong number of planes is told
+_PLANE_COUNT = {3: "expected three planes", 4: "'{}' takes four planes: the three colour planes and alpha"}
+
+
+def _source_frame(src, fin: PixFmt) -> Tuple[int, int]:
+    """(w, h) of the planar source of a two-output or two-LUT call, its planes checked against `fin`."""
+    if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
+        raise ValueError(_PLANE_COUNT[fin.nplanes].format(fin.name))
+    if not isinstance(src[0], torch.Tensor):
+        raise TypeError(_NOT_TENSORS)
+    h, w = src[0].shape[-2], src[0].shape[-1]
+    _check_planes(src, fin, w, h, "source")
+    return w, h
 
 
 def dual_args(src, dst, dst2, pix_fmt, out_pix_fmt, out2_pix_fmt):
     """What `apply_yuv_dual` checks of its formats and planes before it touches the engine: the three formats, and the shapes
     and dtypes of the planes given.  Returns (fin, f1, f2, w, h)."""
     fin, f1, f2 = check_dual_options(pix_fmt, out_pix_fmt, out2_pix_fmt)
-    if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
-        raise ValueError(_PLANE_COUNT[fin.nplanes].format(fin.name))
-    if not isinstance(src[0], torch.Tensor):
-        raise TypeError("planes must be torch tensors resident on the engine's GPU")
-    h, w = src[0].shape[-2], src[0].shape[-1]
-    _check_planes(src, fin, w, h, "source")
+    w, h = _source_frame(src, fin)
     if dst is not None:
         _check_planes(dst, f1, w, h, "destination")
     if dst2 is not None:
@@ -457,83 +56,12 @@ def dual_args(src, dst, dst2, pix_fmt, out_pix_fmt, out2_pix_fmt):
     return fin, f1, f2, w, h
 
 
-#: keywords of `apply_yuv` that the two-LUT pass does not take
-_CHAIN_NOT_TAKEN = {"dither": "dither", "chroma_loc": "sited chroma resampling (chroma_loc)", "out_size": "a resize (out_size)",
-                    "resize_chunk": "a resize (out_size)", "width": "a packed side (width)",
-                    "out2_pix_fmt": "a second output (out2_pix_fmt)", "dst2": "a second output (dst2)"}
-
-
-def chain_side(name: Optional[str], what: str) -> PixFmt:
-    """One side of `apply_yuv_chain`, a planar YUV format without alpha (yuvj* read as yuv*); ValueError for alpha, RGB, float,
-    semi-planar, packed and v210 names.  `what` names the argument in the message."""
-    head = f"the two-LUT pass takes planar YUV on both sides: {what} '{name}'"
-    if not name:
-        raise ValueError(f"the two-LUT pass needs {what}")
-    if parse_semi_fmt(name) is not None:
-        raise ValueError(f"{head} is a semi-planar container")
-    if parse_packed_yuv_fmt(name) is not None or name in _PACKED_YUV_UNSUPPORTED:
-        raise ValueError(f"{head} is a packed container")
-    if parse_v210_fmt(name) is not None or name in _V210_UNSUPPORTED:
-        raise ValueError(f"{head} is a v210 container")
-    rgb = parse_rgb_source(name)
-    if rgb is not None:
-        raise ValueError(f"{head} is a float RGB format" if rgb.floating else f"{head} is an RGB format")
-    fmt = parse_pix_fmt(name.replace("yuvj", "yuv"))
-    if fmt.alpha:
-        raise ValueError(f"{head} carries alpha")
-    return fmt
-
-
-def check_chain_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
-                        out_size=None, second_pix_fmt: Optional[str] = None) -> Tuple[PixFmt, PixFmt]:
-    """The checks `apply_yuv_chain` makes of its formats and options before any GPU work: two planar YUV sides
-    without alpha, no dither, chroma_loc, out_size or second output.  Returns the two parsed formats."""
-    fin = chain_side(pix_fmt, "pix_fmt")
-    fout = chain_side(out_pix_fmt or pix_fmt, "out_pix_fmt")
-    if dither != "none":
-        raise ValueError("dither is not supported with a second LUT")
-    if chroma_loc is not None:
-        raise ValueError("sited chroma resampling (chroma_loc) is not supported with a second LUT")
-    if out_size is not None:
-        raise ValueError("a resize (out_size) is not supported with a second LUT")
-    if second_pix_fmt is not None:
-        raise ValueError("a second output is not supported with a second LUT")
-    return fin, fout
-
-
-def refuse_chain_keywords(kw: dict) -> None:
-    """ValueError when `kw` holds a keyword of `apply_yuv` / `apply_yuv_dual` that the two-LUT pass does not take, whatever its
-    value."""
-    for k, what in _CHAIN_NOT_TAKEN.items():
-        if k in kw:
-            raise ValueError(f"{what} is not supported with a second LUT: apply_yuv_chain takes no '{k}'")
-
-
-def check_lut2(lut) -> None:
-    """ValueError for a second LUT that carries a prelut (a .csp shaper): lut3d's prelut is only taken on the first LUT."""
-    if lut is not None and getattr(lut, "prelut", None) is not None:
-        raise ValueError("the second LUT carries a prelut (a .csp shaper): a prelut is only supported on the first LUT")
-
-
-def chain_interp(interp: str, interp2: Optional[str]) -> Tuple[int, int]:
-    """The two mode codes of `apply_yuv_chain` (`interp2` None = `interp`); ValueError for a name lut3d does not have."""
-    for name in (interp, interp2):
-        if name is not None and name not in _native.INTERP:
-            raise ValueError(f"lut3d has no interpolation mode '{name}'")
-    return _native.INTERP[interp], _native.INTERP[interp if interp2 is None else interp2]
-
-
 def chain_args(src, dst, pix_fmt, out_pix_fmt, interp, interp2):
     """What `apply_yuv_chain` checks of its formats, modes and planes before it touches the engine.  Returns (fin, fout, w, h,
     mode, mode2)."""
     fin, fout = check_chain_options(pix_fmt, out_pix_fmt)
     mode, mode2 = chain_interp(interp, interp2)
-    if isinstance(src, torch.Tensor) or len(src) != 3:
-        raise ValueError(_PLANE_COUNT[3])
-    if not isinstance(src[0], torch.Tensor):
-        raise TypeError("planes must be torch tensors resident on the engine's GPU")
-    h, w = src[0].shape[-2], src[0].shape[-1]
-    _check_planes(src, fin, w, h, "source")
+    w, h = _source_frame(src, fin)
     if dst is not None:
         _check_planes(dst, fout, w, h, "destination")
     return fin, fout, w, h, mode, mode2
@@ -544,112 +72,44 @@ def chain_args(src, dst, pix_fmt, out_pix_fmt, interp, interp2):
 RESIZE_CHUNK = 16
 
 
-#: how the colour planes of an alpha-carrying source stand to their alpha
-ALPHA_MODES = ("straight", "premultiplied")
-
-
-def check_alpha_mode(alpha_mode) -> bool:
-    """True for "premultiplied", False for "straight" (the default everywhere: today's paths, bit for bit); ValueError for any
-    other value."""
-    if alpha_mode not in ALPHA_MODES:
-        raise ValueError(f"unknown alpha_mode '{alpha_mode}' ({' | '.join(ALPHA_MODES)})")
-    return alpha_mode == "premultiplied"
-
-
-def check_premul_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = None, *, dither: str = "none",
-                         chroma_loc: Optional[str] = None, out_size=None, range_src: str = "tv", range_in: Optional[str] = None,
-                         lut_depth: Optional[int] = None, out2_pix_fmt: Optional[str] = None, lut2: bool = False,
-                         to_yuv: bool = False) -> str:
-    """The checks every layer makes of alpha_mode="premultiplied" before any GPU work: "yuv" for a planar yuva*
-    source with a planar YUV output, "float" for gbrapf32le in and out; ValueError for everything the contract does not define.
-    `to_yuv`: the call is `apply_rgb_to_yuv`'s; `lut2`: a second LUT is set for the call; `out2_pix_fmt`: a second output."""
-    head = "alpha_mode='premultiplied'"
-    src = parse_rgb_source(pix_fmt)
-    if src is not None and not src.floating:
-        raise ValueError(f"{head} is not defined for the integer RGB source '{pix_fmt}': PNG / TIFF alpha is straight by "
-                         f"specification")
-    if src is not None:
-        if src.nplanes != 4:
-            raise ValueError(f"{head} needs a source that carries alpha: '{pix_fmt}' has none")
-    else:
-        try:
-            side = yuv_side(pix_fmt)
-        except ValueError:
-            raise ValueError(f"{head} needs a source that carries alpha: '{pix_fmt}' is not one the engine takes") from None
-        if not getattr(side, "alpha", False):
-            raise ValueError(f"{head} needs a source that carries alpha: '{pix_fmt}' has none")
-    if out2_pix_fmt is not None:
-        raise ValueError(f"{head} is not supported with the two-output pass (out2_pix_fmt)")
-    if lut2:
-        raise ValueError(f"{head} is not supported with the two-LUT chain (a second LUT)")
-    if dither != "none":
-        raise ValueError(f"{head} is not supported with dither ('{dither}')")
-    if chroma_loc is not None:
-        raise ValueError(f"{head} is not supported with sited chroma resampling (chroma_loc)")
-    if out_size is not None:
-        raise ValueError(f"{head} is not supported with a resize (out_size / resolution)")
-    out_name = out_pix_fmt or pix_fmt
-    if src is not None:
-        if to_yuv or out_name != pix_fmt:
-            raise ValueError(f"{head}: a float source with an integer or YUV output ('{pix_fmt}' -> '{out_name}') is not "
-                             f"supported; '{pix_fmt}' in and out is")
-        return "float"
-    if to_yuv:
-        raise ValueError(f"{head} is not supported from an RGB source into YUV (apply_rgb_to_yuv)")
-    try:
-        out = yuv_side(out_name)
-    except ValueError:
-        out = None
-    if not isinstance(out, PixFmt) or out.family != "yuv":
-        raise ValueError(f"{head} takes a planar YUV output (yuv* / yuva*), not '{out_name}'")
-    if (range_in or range_src) != range_src or (lut_depth is not None and int(lut_depth) != side.depth):
-        raise ValueError(f"{head} is not defined for a call with a prologue (range_src != range_in, or lut_depth other than the "
-                         f"source's depth {side.depth}): such a call has no alpha to carry")
-    return "yuv"
-
-
-def alpha_src_struct(t: torch.Tensor, depth: int, device: torch.device) -> _native.AlphaSrc:
-    """struct lutr_alpha_src for the alpha plane `t` ([H,W] / [F,H,W]) of a premultiplied call: integer at `depth` bits, or float32."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("planes must be torch tensors resident on the engine's GPU")
-    if t.device != device:
-        raise ValueError(f"the alpha plane is on {t.device}, engine is on {device}")
-    if t.stride(-1) != 1:
-        raise ValueError("planes must be dense along the row")
-    a = _native.AlphaSrc()
-    a.kind = _native.ALPHA_FLOAT if t.dtype == torch.float32 else _native.ALPHA_INT
-    a.depth = 0 if a.kind == _native.ALPHA_FLOAT else depth
-    a.data = t.data_ptr()
-    a.stride = t.stride(-2) * t.element_size()
-    a.frame_stride = t.stride(0) * t.element_size() if t.dim() == 3 else 0
-    a.step, a.offset = 1, 0
-    return a
-
-
-_PREMUL_IN_PLACE = ("the premultiplied-alpha pass cannot run in place: destination planes must not overlap the source planes or "
-                    "the alpha source")
-
-
 def resize_chunk_default() -> int:
     import os
     v = os.environ.get("LUTR_RESIZE_CHUNK")
     return max(1, int(v)) if v else RESIZE_CHUNK
 
 
-def parse_size(size) -> Tuple[int, int]:
-    """(w, h) from a (w, h) pair or a "WxH" string as ffmpeg's -s takes it; ValueError for anything else."""
-    if isinstance(size, str):
-        m = re.fullmatch(r"([1-9][0-9]*)x([1-9][0-9]*)", size)
-        if not m:
-            raise ValueError(f"bad size '{size}' (expected WxH, e.g. 1920x1080)")
-        return int(m.group(1)), int(m.group(2))
-    try:
-        w, h = (int(v) for v in size)
-    except (TypeError, ValueError):
-        raise ValueError(f"bad size {size!r} (expected (w, h) or 'WxH')") from None
-    if w < 1 or h < 1:
-        raise ValueError(f"bad size {size!r}")
-    return w, h
+def _alpha_src(t, depth: int, eng, nframes: int, slot: Optional[int] = None, premul: bool = False) -> _native.AlphaSrc:
+    """struct lutr_alpha_src for the alpha source `t` of a call of `nframes` frames on the engine `eng`: a plane ([H,W] / [F,H,W],
+    integer at `depth` bits or float32), a packed image whose component `slot` is alpha ([H,W,C] / [F,H,W,C]), or None
+    (ALPHA_NONE: the destination is filled).  `premul`: the source travels beside the colour planes of a premultiplied call
+    (DESIGN.md 3.18), which words two of the refusals its own way."""
+    a = _native.AlphaSrc()
+    a.kind, a.depth, a.step, a.offset = _native.ALPHA_NONE, 0, 1, 0
+    if t is None:
+        return a
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(_NOT_TENSORS)
+    if premul and t.device != eng.device:
+        raise ValueError(f"the alpha plane is on {t.device}, engine is on {eng.device}")
+    if t.stride(-1) != 1 or (slot is not None and t.stride(-2) != t.shape[-1]):
+        raise ValueError("planes must be dense along the row")
+    if t.device != eng.device:
+        raise ValueError(_NOT_TENSORS)
+    lead = t.dim() - (2 if slot is None else 3)
+    a.kind = _native.ALPHA_FLOAT if t.dtype == torch.float32 else _native.ALPHA_INT
+    a.depth = 0 if a.kind == _native.ALPHA_FLOAT else depth
+    a.data = t.data_ptr()
+    a.stride = t.stride(lead) * t.element_size()
+    a.frame_stride = t.stride(0) * t.element_size() if lead else 0
+    if slot is not None:
+        a.step, a.offset = t.shape[-1], slot
+    if (t.shape[0] if lead else 1) != nframes:
+        raise ValueError("planes disagree on the number of frames" if premul else "src and dst disagree on the number of frames")
+    return a
+
+
+_PREMUL_IN_PLACE = ("the premultiplied-alpha pass cannot run in place: destination planes must not overlap the source planes or "
+                    "the alpha source")
 
 
 def _byte_range(t: torch.Tensor) -> Tuple[int, int]:
@@ -701,23 +161,6 @@ def _frames3(planes: Sequence[torch.Tensor]) -> list:
     return [t if t.dim() == 3 else t.unsqueeze(0) for t in planes]
 
 
-#: what a planar side with the wrong number of planes is told
-_PLANE_COUNT = {3: "expected three planes", 4: "'{}' takes four planes: the three colour planes and alpha"}
-_ALPHA_RESIZE = "a resize (out_size) is not supported with an alpha-carrying output ('{}'): the resize takes three planes"
-
-
-def refuse_alpha_resize(out_pix_fmt: Optional[str], out_size) -> None:
-    """ValueError for a resize (`out_size` / `resolution`) into an alpha-carrying planar output; any other name
-    passes, whatever it is."""
-    if out_size is None or not out_pix_fmt:
-        return
-    try:
-        fmt = parse_pix_fmt(out_pix_fmt)
-    except ValueError:
-        return
-    if fmt.alpha:
-        raise ValueError(_ALPHA_RESIZE.format(out_pix_fmt))
-
 
 def _check_planes(planes: Sequence[torch.Tensor], fmt: PixFmt, w: int, h: int, what: str) -> None:
     """The C-ABI takes bare pointers and cannot know buffer sizes: every plane must have exactly the shape and the
@@ -733,7 +176,7 @@ def _check_planes(planes: Sequence[torch.Tensor], fmt: PixFmt, w: int, h: int, w
     esize = getattr(fmt, "itemsize", 1 if fmt.depth <= 8 else 2)
     for i, t in enumerate(planes):
         if not isinstance(t, torch.Tensor):
-            raise TypeError("planes must be torch tensors resident on the engine's GPU")
+            raise TypeError(_NOT_TENSORS)
         if t.dim() not in (2, 3):
             raise ValueError("planes must be [H,W] or [F,H,W]")
         if t.is_floating_point() or t.element_size() != esize:
@@ -756,7 +199,7 @@ def _check_float_planes(planes: Sequence[torch.Tensor], fmt: RgbSource, w: int, 
         raise ValueError(f"'{fmt.name}' takes {fmt.nplanes} planes (G, B, R{', A' if fmt.nplanes == 4 else ''})")
     for i, t in enumerate(planes):
         if not isinstance(t, torch.Tensor):
-            raise TypeError("planes must be torch tensors resident on the engine's GPU")
+            raise TypeError(_NOT_TENSORS)
         if t.dim() not in (2, 3):
             raise ValueError("planes must be [H,W] or [F,H,W]")
         if t.dtype != torch.float32:
@@ -776,7 +219,7 @@ def _planes_struct(planes: Sequence[torch.Tensor], device: torch.device, nplanes
     nframes = None
     for i, t in enumerate(planes):
         if not isinstance(t, torch.Tensor):
-            raise TypeError("planes must be torch tensors resident on the engine's GPU")
+            raise TypeError(_NOT_TENSORS)
         if t.device != device:
             raise ValueError(f"plane {i} is on {t.device}, engine is on {device}")
         if t.dim() == 2:
@@ -832,6 +275,14 @@ def _yuv_params(fmt_in: int, fmt_out: int, lut_depth: int, matrix_in: str, matri
     return p
 
 
+def _yuv_call_params(fin, fout, lut_depth: Optional[int], matrix_in: str, matrix_out: Optional[str], range_src: str,
+                     range_in: Optional[str], range_out: str) -> _native.YuvParams:
+    """`_yuv_params` from the keyword values of a YUV call: the LUT runs at the source's depth, the output keeps the input's
+    matrix and the LUT sees the source's range unless the call says otherwise."""
+    return _yuv_params(fin.code, fout.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
+                       range_src, range_in or range_src, range_out)
+
+
 def _yuv_out_dtype(depth: int, inherit: Optional[torch.dtype]) -> torch.dtype:
     """dtype of freshly allocated YUV output planes: uint8 up to 8 bit; deeper outputs inherit a 16-bit source dtype, else (a
     narrower source, or None: an RGB source) int16."""
@@ -841,6 +292,15 @@ def _yuv_out_dtype(depth: int, inherit: Optional[torch.dtype]) -> torch.dtype:
 def _new_planes(fmt, w: int, h: int, lead: tuple, dtype, device) -> list:
     """Fresh planes of one side: `fmt.nplanes` tensors of `lead + fmt.plane_shape(i, w, h)`."""
     return [torch.empty(lead + fmt.plane_shape(i, w, h), dtype=dtype, device=device) for i in range(fmt.nplanes)]
+
+
+def _fresh_planes(fmt, w: int, h: int, like: torch.Tensor, device) -> list:
+    """Fresh output planes of the YUV side `fmt` for a w x h call whose first source plane is `like`: its leading dimensions, and
+    its dtype where a 16-bit output inherits one.  A v210 buffer is zeroed: the kernels never write the padding of a row."""
+    lead = tuple(like.shape[:-2])
+    if isinstance(fmt, V210Fmt):
+        return [torch.zeros(lead + fmt.plane_shape(0, w, h), dtype=torch.int32, device=device)]
+    return _new_planes(fmt, w, h, lead, _yuv_out_dtype(fmt.depth, like.dtype), device)
 
 
 class LutEngine:
@@ -1013,25 +473,7 @@ class LutEngine:
         after the colour pass: `src` is the source's alpha plane ([H,W] / [F,H,W], integer at `din` bits or float32), a packed
         image whose component `slot` is alpha ([H,W,C] / [F,H,W,C]), or None (no alpha on the source: `dst` is filled).
         `after`: what `last_kernel` read before this launch; it then reads "<after>+<alpha kernel>" (None: the alpha kernel)."""
-        a = _native.AlphaSrc()
-        a.kind, a.depth, a.step, a.offset = _native.ALPHA_NONE, 0, 1, 0
-        if src is not None:
-            if not isinstance(src, torch.Tensor):
-                raise TypeError("planes must be torch tensors resident on the engine's GPU")
-            if src.stride(-1) != 1 or (slot is not None and src.stride(-2) != src.shape[-1]):
-                raise ValueError("planes must be dense along the row")
-            if src.device != self.device:
-                raise ValueError("planes must be torch tensors resident on the engine's GPU")
-            lead = src.dim() - (2 if slot is None else 3)
-            a.kind = _native.ALPHA_FLOAT if src.dtype == torch.float32 else _native.ALPHA_INT
-            a.depth = 0 if a.kind == _native.ALPHA_FLOAT else din
-            a.data = src.data_ptr()
-            a.stride = src.stride(lead) * src.element_size()
-            a.frame_stride = src.stride(0) * src.element_size() if lead else 0
-            if slot is not None:
-                a.step, a.offset = src.shape[-1], slot
-            if (src.shape[0] if lead else 1) != (dst.shape[0] if dst.dim() == 3 else 1):
-                raise ValueError("src and dst disagree on the number of frames")
+        a = _alpha_src(src, din, self, dst.shape[0] if dst.dim() == 3 else 1, slot)
         if dst.device != self.device or dst.stride(-1) != 1:
             raise ValueError("planes must be dense along the row and resident on the engine's GPU")
         nf, dfs = (dst.shape[0], dst.stride(0) * dst.element_size()) if dst.dim() == 3 else (1, 0)
@@ -1044,6 +486,18 @@ class LutEngine:
             if after is not None and w and rows and nf:          # (an empty call launches nothing and names nothing)
                 name = self._lib.lutr_ctx_last_kernel(self._ctx).decode()
                 self._alpha_kernels = (name, f"{after}+{name}")
+
+    def _alpha_tail(self, colour, outputs, a_src, din: int, w: int, h: int, row0: int, rows: Optional[int],
+                    slot: Optional[int] = None):
+        """An alpha-carrying call: `colour()` launches the colour planes, then every output of `outputs` --
+        (its format, its planes) -- that carries alpha gets its fourth plane from `a_src` (`_alpha_plane`: a plane at `din` bits,
+        a packed image with `slot`, or None), all under the lock.  Returns what `colour()` returned."""
+        with self._lock:
+            out = colour()
+            for fmt, planes in outputs:
+                if fmt.alpha:
+                    self._alpha_plane(a_src, planes[3], din, fmt.depth, w, h, row0, rows, slot, after=self.last_kernel)
+        return out
 
     def tile_stats(self, enable: bool = True) -> dict:
         """Counters of the LDS-window kernels since the previous call; (re)arms collection."""
@@ -1080,9 +534,8 @@ class LutEngine:
             _check_planes(src, fmt, w, h, "source")
             _check_planes(dst, fmt, w, h, "destination")
             _check_alpha_overlap(src[3], int(depth), dst, int(depth))
-            with self._lock:
-                self.apply_rgb(src[:3], dst[:3], depth=depth, interp=interp, row0=row0, rows=rows)
-                self._alpha_plane(src[3], dst[3], int(depth), int(depth), w, h, row0, rows, after=self.last_kernel)
+            self._alpha_tail(lambda: self.apply_rgb(src[:3], dst[:3], depth=depth, interp=interp, row0=row0, rows=rows),
+                             [(fmt, dst)], src[3], int(depth), w, h, row0, rows)
             return dst
         fmt = PixFmt(f"gbrp{depth}", "gbr", int(depth), 0, 0, True)
         if out_size is not None:
@@ -1122,9 +575,7 @@ class LutEngine:
         rows = h - row0 if rows is None else rows
         if premul:
             _check_alpha_overlap(src[3], 0, dst, 0)
-            a = alpha_src_struct(src[3], 0, self.device)
-            if (src[3].shape[0] if src[3].dim() == 3 else 1) != nf:
-                raise ValueError("planes disagree on the number of frames")
+            a = _alpha_src(src[3], 0, self, nf, premul=True)
         with self._lock:
             self._bind_stream()
             if premul:
@@ -1266,13 +717,9 @@ class LutEngine:
             check_premul_options(pix_fmt, out_pix_fmt, dither=dither, chroma_loc=chroma_loc, out_size=out_size, range_src=range_src,
                                  range_in=range_in, lut_depth=lut_depth)
         kind = check_container_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size, width=width)
-        if kind == "v210":
-            return self._apply_yuv_v210(src, dst, yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt), interp, matrix_in, matrix_out,
-                                        range_src, range_in, range_out, lut_depth, row0, rows, width)
         if kind is not None:
-            return self._apply_yuv_container(kind == "packed", src, dst, yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt),
-                                             interp, matrix_in, matrix_out, range_src, range_in, range_out, lut_depth, row0, rows,
-                                             width)
+            return self._apply_yuv_container(kind, src, dst, yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt), interp, matrix_in,
+                                             matrix_out, range_src, range_in, range_out, lut_depth, row0, rows, width)
         fin = parse_pix_fmt(pix_fmt)
         fout = parse_pix_fmt(out_pix_fmt or pix_fmt)
         if fin.family != "yuv" or fout.family != "yuv":
@@ -1288,12 +735,11 @@ class LutEngine:
             h, w = src[0].shape[-2], src[0].shape[-1]
             _check_planes(src, fin, w, h, "source")
             if dst is None and out_size is None:
-                dst = _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), self.device)
+                dst = _fresh_planes(fout, w, h, src[0], self.device)
             if dst is not None and out_size is None:
                 _check_planes(dst, fout, w, h, "destination")
             # a prologue call fills: the reference's 8-bit yuv4xxp intermediate has no alpha to carry
-            prologue = (range_in or range_src) != range_src or (lut_depth is not None and lut_depth != fin.depth)
-            a_src = src[3] if fin.alpha and not prologue else None
+            a_src = src[3] if fin.alpha and not has_prologue(fin.depth, range_src, range_in, lut_depth) else None
             if fout.alpha and dst is not None:
                 _check_alpha_overlap(a_src, fin.depth, dst, fout.depth)
             if premul:
@@ -1302,31 +748,26 @@ class LutEngine:
                 _check_alpha_overlap(a_src, fin.depth, dst[:3], fout.depth)
                 _check_not_in_place(src, dst[:3], _PREMUL_IN_PLACE)
                 s, d, nf = _plane_pair(src[:3], dst[:3], self.device)
-                a = alpha_src_struct(src[3], fin.depth, self.device)
-                if (src[3].shape[0] if src[3].dim() == 3 else 1) != nf:
-                    raise ValueError("planes disagree on the number of frames")
-                p = _yuv_params(fin.colour.code, fout.colour.code, fin.depth, matrix_in, matrix_out or matrix_in, range_src,
-                                range_src, range_out)
-                with self._lock:
+                a = _alpha_src(src[3], fin.depth, self, nf, premul=True)
+                p = _yuv_call_params(fin.colour, fout.colour, None, matrix_in, matrix_out, range_src, None, range_out)
+
+                def colour():
                     self._bind_stream()
                     _native.check(self._lib.lutr_apply_yuv_premul(
                         self._ctx, C.byref(p), _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(a), C.byref(d), row0,
                         h - row0 if rows is None else rows))
-                    if fout.alpha:
-                        self._alpha_plane(a_src, dst[3], fin.depth, fout.depth, w, h, row0, rows, after=self.last_kernel)
-                return dst
-            with self._lock:
-                out = self.apply_yuv(src[:3], None if dst is None else dst[:3], pix_fmt=fin.colour.name, interp=interp,
-                                     matrix_in=matrix_in, matrix_out=matrix_out, range_src=range_src, range_in=range_in,
-                                     range_out=range_out, lut_depth=lut_depth, out_pix_fmt=fout.colour.name, row0=row0, rows=rows,
-                                     dither=dither, chroma_loc=chroma_loc, out_size=out_size, resize_chunk=resize_chunk)
-                if fout.alpha:
-                    self._alpha_plane(a_src, dst[3], fin.depth, fout.depth, w, h, row0, rows, after=self.last_kernel)
+            else:
+                def colour():
+                    return self.apply_yuv(src[:3], None if dst is None else dst[:3], pix_fmt=fin.colour.name, interp=interp,
+                                          matrix_in=matrix_in, matrix_out=matrix_out, range_src=range_src, range_in=range_in,
+                                          range_out=range_out, lut_depth=lut_depth, out_pix_fmt=fout.colour.name, row0=row0,
+                                          rows=rows, dither=dither, chroma_loc=chroma_loc, out_size=out_size,
+                                          resize_chunk=resize_chunk)
+            out = self._alpha_tail(colour, [(fout, dst)], a_src, fin.depth, w, h, row0, rows)
             return out if dst is None else dst
         check_chroma_loc(chroma_loc, dither, fin.name, fout.name)
         xsub = (fin.csx, fin.csy) != (fout.csx, fout.csy)
-        p = _yuv_params(fin.code, fout.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
-                        range_src, range_in or range_src, range_out)
+        p = _yuv_call_params(fin, fout, lut_depth, matrix_in, matrix_out, range_src, range_in, range_out)
         h, w = src[0].shape[-2], src[0].shape[-1]
         if out_size is not None:
             kw = dict(pix_fmt=pix_fmt, interp=interp, matrix_in=matrix_in, matrix_out=matrix_out, range_src=range_src,
@@ -1335,7 +776,7 @@ class LutEngine:
             return self._lut_then_resize(src, dst, fin, fout, w, h, out_size, row0, rows, resize_chunk, chroma_loc,
                                          lambda s_, d_: self.apply_yuv(s_, d_, **kw))
         if dst is None:
-            dst = _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), self.device)
+            dst = _fresh_planes(fout, w, h, src[0], self.device)
         _check_planes(src, fin, w, h, "source")
         _check_planes(dst, fout, w, h, "destination")
         s, d, nf = _plane_pair(src, dst, self.device)
@@ -1378,35 +819,28 @@ class LutEngine:
         fin, f1, f2, w, h = dual_args(src, dst, dst2, pix_fmt, out_pix_fmt, out2_pix_fmt)
         if fin.alpha or f1.alpha or f2.alpha:
             # each output carries, fills or drops alpha on its own; the colour planes through this very call
-            lead, dt = tuple(src[0].shape[:-2]), src[0].dtype
             if dst is None:
-                dst = _new_planes(f1, w, h, lead, _yuv_out_dtype(f1.depth, dt), self.device)
+                dst = _fresh_planes(f1, w, h, src[0], self.device)
             if dst2 is None:
-                dst2 = _new_planes(f2, w, h, lead, _yuv_out_dtype(f2.depth, dt), self.device)
+                dst2 = _fresh_planes(f2, w, h, src[0], self.device)
             # (a prologue call fills, as in apply_yuv)
-            prologue = (range_in or range_src) != range_src or (lut_depth is not None and lut_depth != fin.depth)
-            a_src = src[3] if fin.alpha and not prologue else None
+            a_src = src[3] if fin.alpha and not has_prologue(fin.depth, range_src, range_in, lut_depth) else None
             for f, d in ((f1, dst), (f2, dst2)):
                 _check_alpha_overlap(a_src, fin.depth, list(d[:3]) + ([d[3]] if f.alpha else []), f.depth)
             if f1.alpha and f2.alpha:
                 _check_not_in_place([dst[3]], list(dst2), "the two outputs' planes must not overlap")
                 _check_not_in_place([dst2[3]], list(dst), "the two outputs' planes must not overlap")
-            with self._lock:
-                self.apply_yuv_dual(src[:3], dst[:3], dst2[:3], pix_fmt=fin.colour.name, out_pix_fmt=f1.colour.name,
-                                    out2_pix_fmt=f2.colour.name, interp=interp, matrix_in=matrix_in, matrix_out=matrix_out,
-                                    range_src=range_src, range_in=range_in, range_out=range_out, lut_depth=lut_depth, row0=row0,
-                                    rows=rows)
-                for f, d in ((f1, dst), (f2, dst2)):
-                    if f.alpha:
-                        self._alpha_plane(a_src, d[3], fin.depth, f.depth, w, h, row0, rows, after=self.last_kernel)
+            self._alpha_tail(lambda: self.apply_yuv_dual(
+                src[:3], dst[:3], dst2[:3], pix_fmt=fin.colour.name, out_pix_fmt=f1.colour.name, out2_pix_fmt=f2.colour.name,
+                interp=interp, matrix_in=matrix_in, matrix_out=matrix_out, range_src=range_src, range_in=range_in,
+                range_out=range_out, lut_depth=lut_depth, row0=row0, rows=rows), [(f1, dst), (f2, dst2)], a_src, fin.depth, w, h,
+                row0, rows)
             return dst, dst2
-        p = _yuv_params(fin.code, f1.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
-                        range_src, range_in or range_src, range_out)
-        lead = tuple(src[0].shape[:-2])
+        p = _yuv_call_params(fin, f1, lut_depth, matrix_in, matrix_out, range_src, range_in, range_out)
         if dst is None:
-            dst = _new_planes(f1, w, h, lead, _yuv_out_dtype(f1.depth, src[0].dtype), self.device)
+            dst = _fresh_planes(f1, w, h, src[0], self.device)
         if dst2 is None:
-            dst2 = _new_planes(f2, w, h, lead, _yuv_out_dtype(f2.depth, src[0].dtype), self.device)
+            dst2 = _fresh_planes(f2, w, h, src[0], self.device)
         s, d, nf = _plane_pair(src, dst, self.device)
         d2, nf2 = _planes_struct(dst2, self.device)
         if nf != nf2:
@@ -1432,10 +866,9 @@ class LutEngine:
         if other:
             raise TypeError(f"apply_yuv_chain() got an unexpected keyword argument '{next(iter(other))}'")
         fin, fout, w, h, mode, mode2 = chain_args(src, dst, pix_fmt, out_pix_fmt, interp, interp2)
-        p = _yuv_params(fin.code, fout.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
-                        range_src, range_in or range_src, range_out)
+        p = _yuv_call_params(fin, fout, lut_depth, matrix_in, matrix_out, range_src, range_in, range_out)
         if dst is None:
-            dst = _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), self.device)
+            dst = _fresh_planes(fout, w, h, src[0], self.device)
         s, d, nf = _plane_pair(src, dst, self.device)
         rows = h - row0 if rows is None else rows
         with self._lock:
@@ -1444,69 +877,43 @@ class LutEngine:
                 self._ctx, C.byref(p), mode, mode2, w, h, nf, C.byref(s), C.byref(d), row0, rows))
         return dst
 
-    def _apply_yuv_container(self, packed, src, dst, fin, fout, interp, matrix_in, matrix_out, range_src, range_in, range_out,
+    def _apply_yuv_container(self, kind, src, dst, fin, fout, interp, matrix_in, matrix_out, range_src, range_in, range_out,
                              lut_depth, row0, rows, width):
-        """apply_yuv with a semi-planar side (lutr_apply_yuv_semi) or, `packed`, a packed 4:2:2 side (lutr_apply_yuv_packed: a
-        side may be a bare tensor, and `width` names an odd width); the options were checked by `check_container_options`."""
-        p = _yuv_params(fin.code, fout.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
-                        range_src, range_in or range_src, range_out)
-        bare = packed and isinstance(dst, torch.Tensor)
-        if packed and isinstance(src, torch.Tensor):
+        """apply_yuv with a side that is not three planes, `kind` as `check_container_options` told it after checking the options:
+        "semi" (lutr_apply_yuv_semi), "packed" (lutr_apply_yuv_packed: a side may be a bare tensor, and `width` names an odd
+        width) or "v210" (lutr_apply_yuv_v210, DESIGN.md 3.14: that side is ONE int32 tensor [..., h, words], bare or in a
+        one-element list, 32 * ceil(w / 48) words a row by default; a planar side or `width` tells the width)."""
+        p = _yuv_call_params(fin, fout, lut_depth, matrix_in, matrix_out, range_src, range_in, range_out)
+        vi, vo = isinstance(fin, V210Fmt), isinstance(fout, V210Fmt)
+        bare = (kind == "packed" or vo) and isinstance(dst, torch.Tensor)
+        if (kind == "packed" or vi) and isinstance(src, torch.Tensor):
             src = [src]
         if bare:
             dst = [dst]
         if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
             raise ValueError(f"'{fin.name}' takes {fin.nplanes} plane{'s' if fin.nplanes > 1 else ''}")
-        w, h = packed_frame_width(fin, src, width), src[0].shape[-2]
+        w = v210_frame_width(fin, fout, src, dst, width) if kind == "v210" else packed_frame_width(fin, src, width)
+        h = src[0].shape[-2]
         if dst is None:
-            dst = _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), self.device)
+            dst = _fresh_planes(fout, w, h, src[0], self.device)
         _check_planes(src, fin, w, h, "source")
         _check_planes(dst, fout, w, h, "destination")
         s, nf = _planes_struct(src, self.device, fin.nplanes)
         d, nfd = _planes_struct(dst, self.device, fout.nplanes)
         if nf != nfd:
             raise ValueError("src and dst disagree on the number of frames")
-        entry = self._lib.lutr_apply_yuv_packed if packed else self._lib.lutr_apply_yuv_semi
-        sides = [f.packing() if packed else f.layout() for f in (fin, fout)]
+        if kind == "v210":
+            entry, sides = self._lib.lutr_apply_yuv_v210, (int(vi), int(vo))
+        elif kind == "packed":
+            entry, sides = self._lib.lutr_apply_yuv_packed, (C.byref(fin.packing()), C.byref(fout.packing()))
+        else:
+            entry, sides = self._lib.lutr_apply_yuv_semi, (C.byref(fin.layout()), C.byref(fout.layout()))
         rows = h - row0 if rows is None else rows
         with self._lock:
             self._bind_stream()
-            _native.check(entry(self._ctx, C.byref(p), _native.INTERP[interp], C.byref(sides[0]), C.byref(sides[1]), w, h, nf,
-                                C.byref(s), C.byref(d), row0, rows))
+            _native.check(entry(self._ctx, C.byref(p), _native.INTERP[interp], *sides, w, h, nf, C.byref(s), C.byref(d), row0, rows))
         return dst[0] if bare else dst
 
-    def _apply_yuv_v210(self, src, dst, fin, fout, interp, matrix_in, matrix_out, range_src, range_in, range_out, lut_depth, row0,
-                        rows, width):
-        """apply_yuv with a v210 side (lutr_apply_yuv_v210): that side is ONE int32 tensor [..., h, words] (bare
-        or in a one-element list), 32 * ceil(w / 48) words a row by default; the options were checked by
-        `check_container_options`."""
-        p = _yuv_params(fin.code, fout.code, lut_depth if lut_depth is not None else fin.depth, matrix_in, matrix_out or matrix_in,
-                        range_src, range_in or range_src, range_out)
-        vi, vo = isinstance(fin, V210Fmt), isinstance(fout, V210Fmt)
-        bare = vo and isinstance(dst, torch.Tensor)
-        if vi and isinstance(src, torch.Tensor):
-            src = [src]
-        if bare:
-            dst = [dst]
-        if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
-            raise ValueError(f"'{fin.name}' takes {fin.nplanes} plane{'s' if fin.nplanes > 1 else ''}")
-        w, h = v210_frame_width(fin, fout, src, dst, width), src[0].shape[-2]
-        if dst is None:
-            # (a fresh v210 buffer is zeroed: the kernels never write the padding of a row)
-            dst = [torch.zeros(tuple(src[0].shape[:-2]) + fout.plane_shape(0, w, h), dtype=torch.int32, device=self.device)] if vo \
-                else _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), self.device)
-        _check_planes(src, fin, w, h, "source")
-        _check_planes(dst, fout, w, h, "destination")
-        s, nf = _planes_struct(src, self.device, fin.nplanes)
-        d, nfd = _planes_struct(dst, self.device, fout.nplanes)
-        if nf != nfd:
-            raise ValueError("src and dst disagree on the number of frames")
-        rows = h - row0 if rows is None else rows
-        with self._lock:
-            self._bind_stream()
-            _native.check(self._lib.lutr_apply_yuv_v210(self._ctx, C.byref(p), _native.INTERP[interp], int(vi), int(vo), w, h, nf,
-                                                        C.byref(s), C.byref(d), row0, rows))
-        return dst[0] if bare else dst
 
     # -- RGB source, YUV output (DESIGN.md 3.9) --------------------------------
     def _rgb_source(self, src, fmt: RgbSource):
@@ -1573,11 +980,10 @@ class LutEngine:
                 elif not fin.packed and fin.nplanes == 4 and len(src) == 4:
                     a_src = src[3]
             _check_alpha_overlap(a_src, fin.depth, dst, fout.depth)
-            with self._lock:
-                self.apply_rgb_to_yuv(src, dst[:3], pix_fmt=pix_fmt, out_pix_fmt=fout.colour.name, interp=interp,
-                                      matrix_out=matrix_out, range_out=range_out, row0=row0, rows=rows, dither=dither, lut=lut,
-                                      intermediate_pix_fmt=intermediate_pix_fmt, prologue_out_range=prologue_out_range)
-                self._alpha_plane(a_src, dst[3], fin.depth, fout.depth, w, h, row0, rows, slot, after=self.last_kernel)
+            self._alpha_tail(lambda: self.apply_rgb_to_yuv(
+                src, dst[:3], pix_fmt=pix_fmt, out_pix_fmt=fout.colour.name, interp=interp, matrix_out=matrix_out,
+                range_out=range_out, row0=row0, rows=rows, dither=dither, lut=lut, intermediate_pix_fmt=intermediate_pix_fmt,
+                prologue_out_range=prologue_out_range), [(fout, dst)], a_src, fin.depth, w, h, row0, rows, slot)
             return dst
         if intermediate_pix_fmt is not None:
             return self.apply_rgb_full_range(src, dst, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt,

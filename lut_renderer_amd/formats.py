@@ -1,0 +1,600 @@
+"""Pixel-format descriptions and the checks that look only at names and options.
+
+Nothing here needs torch or a GPU: the argv builder (`command.py`), the numpy container helpers (`semiplanar.py`,
+`packedyuv.py`, `v210.py`) and every layer above the engine read formats and refuse option combinations from this module; the
+engine (`engine.py`) adds the checks that look at tensors.
+"""
+from __future__ import annotations
+
+import re
+from dataclasses import dataclass
+from typing import Optional, Tuple
+
+import numpy as np
+
+from . import _native
+
+_PIXFMT_RE = re.compile(r"^(yuvj?|yuva|gbra?)(420|422|444)?p(\d+)?(le)?$")
+
+
+class _YuvSide:
+    """What the three format classes share: one side of a YUV call, from the `depth`, `csx`, `csy` of its container."""
+
+    @property
+    def code(self) -> int:
+        return _native.fmt_code(self.depth, self.csx, self.csy)
+
+    @property
+    def np_dtype(self):
+        return np.uint8 if self.depth <= 8 else np.uint16
+
+    def layout(self) -> _native.YuvLayout:
+        """This side as lutr_apply_yuv_semi takes it (here: three planes)."""
+        return _native.YuvLayout(0, 0, 0)
+
+    def packing(self) -> _native.YuvPacking:
+        """This side as lutr_apply_yuv_packed takes it (here: three planes)."""
+        return _native.YuvPacking(0, 0, 0)
+
+
+class _YuvContainer(_YuvSide):
+    """A YUV container that is not three planes: always YUV, never yuvj*, and with a planar twin."""
+    family = "yuv"
+    full_range = False
+
+    @property
+    def planar(self) -> str:
+        """The planar format that holds the same samples (nv12 -> yuv420p, p210le -> yuv422p10le, uyvy422 -> yuv422p)."""
+        return f"yuv{'420' if self.csy else '422'}p" + ("" if self.depth == 8 else f"{self.depth}le")
+
+
+@dataclass(frozen=True)
+class PixFmt(_YuvSide):
+    """Parsed FFmpeg planar pixel-format name (the ones this path can meet)."""
+    name: str
+    family: str      # "yuv" or "gbr"
+    depth: int
+    csx: int
+    csy: int
+    full_range: bool  # yuvj* (legacy full-range marker, media_info.py:145-147)
+    alpha: bool = False  # yuva* / gbrap*: a fourth, luma-sized plane at the same depth
+
+    @property
+    def nplanes(self) -> int:
+        return 4 if self.alpha else 3
+
+    @property
+    def colour(self) -> "PixFmt":
+        """The three-plane format of the same colour planes (yuva420p10le -> yuv420p10le, gbrap -> gbrp); itself without alpha."""
+        if not self.alpha:
+            return self
+        return parse_pix_fmt(self.name.replace("yuva", "yuv", 1).replace("gbrap", "gbrp", 1))
+
+    def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
+        if self.family == "gbr" or plane in (0, 3):
+            return h, w
+        return (h + (1 << self.csy) - 1) >> self.csy, (w + (1 << self.csx) - 1) >> self.csx
+
+
+@dataclass(frozen=True)
+class SemiFmt(_YuvContainer):
+    """A semi-planar YUV format: a luma plane and one plane of interleaved chroma pairs."""
+    name: str
+    depth: int
+    csx: int
+    csy: int
+    swap: int         # 1: Cr comes first in a pair (nv21)
+    shift: int        # left shift of the code inside its 16-bit container (p010le: 6)
+
+    nplanes = 2
+
+    def layout(self) -> _native.YuvLayout:
+        return _native.YuvLayout(1, self.swap, self.shift)
+
+    def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
+        """Plane 0: (h, w) luma samples; plane 1: (chroma rows, 2 * pairs per row) chroma samples."""
+        if plane == 0:
+            return h, w
+        return (h + (1 << self.csy) - 1) >> self.csy, 2 * ((w + 1) >> 1)
+
+
+@dataclass(frozen=True)
+class PackedYuvFmt(_YuvContainer):
+    """A packed 4:2:2 YUV format: one buffer, rows of ceil(w / 2) groups of four samples."""
+    name: str
+    depth: int
+    order: int        # the samples of a group in memory: 0 Y0 Cb Y1 Cr, 1 Cb Y0 Cr Y1 (uyvy422), 2 Y0 Cr Y1 Cb (yvyu422)
+    shift: int        # left shift of the code inside its 16-bit container (y210le: 6)
+
+    nplanes = 1
+    csx, csy = 1, 0
+
+    def packing(self) -> _native.YuvPacking:
+        return _native.YuvPacking(1, self.order, self.shift)
+
+    def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
+        """The one buffer: (h, 4 * groups per row) samples."""
+        return h, 4 * ((w + 1) >> 1)
+
+
+@dataclass(frozen=True)
+class V210Fmt(_YuvContainer):
+    """v210: one buffer of 32-bit words, rows of ceil(w / 6) groups of four words, three 10-bit codes a word."""
+    name: str
+    depth: int
+
+    nplanes = 1
+    csx, csy = 1, 0
+    itemsize = 4      # the buffer's elements are the words (torch.int32)
+
+    @staticmethod
+    def groups(w: int) -> int:
+        """Groups of six luma samples in a row."""
+        return (w + 5) // 6
+
+    @staticmethod
+    def row_bytes(w: int) -> int:
+        """The default row stride: rows are padded to whole blocks of 128 bytes (48 luma samples)."""
+        return 128 * ((w + 47) // 48)
+
+    def plane_shape(self, plane: int, w: int, h: int) -> Tuple[int, int]:
+        """The one buffer at the default stride: (h, 32 * ceil(w / 48)) words."""
+        return h, self.row_bytes(w) // 4
+
+
+def parse_v210_fmt(name: Optional[str]) -> Optional[V210Fmt]:
+    """The `V210Fmt` of a name of `_native.V210_FORMATS` ("v210"), or None for any other name -- `parse_pix_fmt` rejects the name
+    and `parse_semi_fmt` / `parse_packed_yuv_fmt` return None for it."""
+    if name not in _native.V210_FORMATS:
+        return None
+    return V210Fmt(name, *_native.V210_FORMATS[name])
+
+
+def parse_packed_yuv_fmt(name: Optional[str]) -> Optional[PackedYuvFmt]:
+    """The packed 4:2:2 format `name` stands for (a name of `_native.PACKED_YUV_FORMATS`), or None for any other name --
+    `parse_pix_fmt` keeps rejecting these and `parse_semi_fmt` keeps returning None for them."""
+    if name not in _native.PACKED_YUV_FORMATS:
+        return None
+    return PackedYuvFmt(name, *_native.PACKED_YUV_FORMATS[name])
+
+
+def parse_semi_fmt(name: Optional[str]) -> Optional[SemiFmt]:
+    """The semi-planar format `name` stands for (a name of `_native.SEMI_FORMATS`), or None for any other name --
+    `parse_pix_fmt` keeps rejecting these: it describes three-plane frames."""
+    if name not in _native.SEMI_FORMATS:
+        return None
+    return SemiFmt(name, *_native.SEMI_FORMATS[name])
+
+
+def yuv_side(name: str):
+    """One side of `apply_yuv`: the `SemiFmt`, `PackedYuvFmt`, `V210Fmt` or planar `PixFmt` of a YUV format name (yuvj* read as
+    yuv*)."""
+    return parse_semi_fmt(name) or parse_packed_yuv_fmt(name) or parse_v210_fmt(name) or \
+        parse_pix_fmt((name or "").replace("yuvj", "yuv"))
+
+
+#: packed YUV names FFmpeg has that this path does not take: 4:4:4 packings and big-endian containers
+_PACKED_YUV_UNSUPPORTED = ("vuyx", "vuya", "ayuv", "uyva", "xv30le", "xv36le", "xv48le", "ayuv64le", "v30xle", "y210be", "y212be",
+                           "y216be", "xv30be", "xv36be", "xv48be", "ayuv64be")
+
+
+#: container kind -> (its parser, what the RGB refusal calls it, what every other refusal calls it)
+_CONTAINER_KINDS = {"v210": (parse_v210_fmt, "v210", "v210"),
+                    "packed": (parse_packed_yuv_fmt, "packed", "packed 4:2:2"),
+                    "semi": (parse_semi_fmt, "semi-planar", "semi-planar")}
+
+#: v210's relatives FFmpeg knows as codecs, which this path does not take
+_V210_UNSUPPORTED = ("v210x", "v410", "v308", "v408", "r210", "r10k")
+
+
+def source_bit_depth(name: Optional[str]) -> Optional[int]:
+    """`params.infer_bit_depth` for a source name that may be a container: p010le and y210le say their depth themselves (the
+    digits are not a depth after a 'p')."""
+    from .params import infer_bit_depth
+    side = parse_semi_fmt(name) or parse_packed_yuv_fmt(name) or parse_v210_fmt(name)
+    return side.depth if side else infer_bit_depth(name)
+
+
+def check_container_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
+                            out_size=None, kinds=("v210", "packed", "semi"), width: Optional[int] = None) -> Optional[str]:
+    """The checks `apply_yuv` makes before any GPU work when a side is not three planes: "v210" when a side is v210 (DESIGN.md
+    3.14), "packed" when a side is packed 4:2:2, "semi" when one is semi-planar, None when both
+    are planar (nothing checked but the packed names this path does not take).  Refused: an RGB side, two kinds of container in
+    one call, a subsampling change (packed and v210: only a source that is not 4:2:2), chroma_loc, error-diffusion dither,
+    out_size, and a `width` (`apply_yuv`'s, for rows that cannot tell it) when no side is packed or v210."""
+    out_name = out_pix_fmt or pix_fmt
+    for kind in kinds:
+        parse, short, noun = _CONTAINER_KINDS[kind]
+        packed, v210 = kind == "packed", kind == "v210"
+        if kind == "semi" and width is not None:
+            raise ValueError("width is for a packed 4:2:2 side; planar and semi-planar frames tell their own")
+        for name in (pix_fmt, out_name) if packed else ():
+            if name in _PACKED_YUV_UNSUPPORTED:
+                raise ValueError(f"'{name}' is not supported: packed YUV frames are taken as little-endian 4:2:2 "
+                                 f"({', '.join(_native.PACKED_YUV_FORMATS)})")
+        for name in (pix_fmt, out_name) if v210 else ():
+            if name in _V210_UNSUPPORTED:
+                raise ValueError(f"'{name}' is not supported: of this family only v210 is taken")
+        if parse(pix_fmt) is None and parse(out_name) is None:
+            continue
+        if parse_rgb_source(pix_fmt) is not None:
+            raise ValueError(f"an RGB source ('{pix_fmt}') takes a planar YUV out_pix_fmt, not the {short} '{out_pix_fmt}'")
+        if v210:
+            if parse_rgb_source(out_name) is not None:
+                raise ValueError(f"v210 frames go with YUV formats on both sides ('{pix_fmt}' -> '{out_name}')")
+            for other, what in ((parse_semi_fmt, "semi-planar"), (parse_packed_yuv_fmt, "packed 4:2:2")):
+                if other(pix_fmt) is not None or other(out_name) is not None:
+                    raise ValueError(f"a {what} side together with a v210 side is not supported ('{pix_fmt}' -> '{out_name}')")
+        if packed and (parse_semi_fmt(pix_fmt) is not None or parse_semi_fmt(out_name) is not None):
+            raise ValueError(f"a semi-planar side together with a packed side is not supported ('{pix_fmt}' -> '{out_name}')")
+        a, b = yuv_side(pix_fmt), yuv_side(out_name)
+        if getattr(a, "alpha", False) or getattr(b, "alpha", False):
+            raise ValueError(f"alpha is carried between planar sides only, not with a {noun} side ('{pix_fmt}' -> '{out_name}')")
+        if a.family != "yuv" or b.family != "yuv":
+            raise ValueError(f"{noun} frames go with YUV formats on both sides "
+                             f"('{pix_fmt}' -> '{out_name if packed or v210 else out_pix_fmt}')")
+        if (packed or v210) and (a.csx, a.csy) != (1, 0):
+            raise ValueError(f"a {short} destination takes a 4:2:2 source: no chroma subsampling change into '{out_name}' "
+                             f"('{pix_fmt}' -> '{out_name}')")
+        if kind == "semi" and (a.csx, a.csy) != (b.csx, b.csy):
+            raise ValueError(f"a chroma subsampling change is not supported with a semi-planar side "
+                             f"('{pix_fmt}' -> '{out_pix_fmt}')")
+        if chroma_loc is not None:
+            raise ValueError(f"sited chroma resampling (chroma_loc) is not supported with a {noun} side")
+        if dither != "none":
+            raise ValueError(f"error-diffusion dither is not supported with a {noun} side")
+        if out_size is not None:
+            raise ValueError(f"a resize (out_size) is not supported with a {noun} side")
+        return kind
+    return None
+
+
+def check_packed_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
+                         out_size=None) -> bool:
+    """`check_container_options` for the packed 4:2:2 kind alone: False when neither side is packed, True otherwise."""
+    return check_container_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size, ("packed",)) is not None
+
+
+def check_semi_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
+                       out_size=None) -> bool:
+    """`check_container_options` for the semi-planar kind alone (a packed side is not looked at): False when neither side is
+    semi-planar, True otherwise."""
+    return check_container_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size, ("semi",)) is not None
+
+
+def packed_frame_width(fmt, planes, width: Optional[int] = None) -> int:
+    """The frame width of one side's planes: a packed buffer holds 4 * ceil(w / 2) samples per row, so an odd width has to be
+    named (`width`); every other side tells it itself."""
+    first = planes if hasattr(planes, "shape") else planes[0]
+    if fmt.nplanes != 1:
+        w = first.shape[-1]
+    else:
+        if first.shape[-1] % 4:
+            raise ValueError(f"'{fmt.name}' rows hold whole groups of four samples, got {first.shape[-1]} samples")
+        w = first.shape[-1] // 2 if width is None else int(width)
+        if 4 * ((w + 1) >> 1) != first.shape[-1]:
+            raise ValueError(f"width {w} does not match '{fmt.name}' rows of {first.shape[-1]} samples")
+    if width is not None and int(width) != w:
+        raise ValueError(f"width {width} does not match the planes ({w})")
+    return w
+
+
+def v210_frame_width(fin, fout, src, dst, width: Optional[int] = None) -> int:
+    """The frame width of a call with a v210 side: a planar side tells it (the source's planes, else the destination's when
+    given); v210 rows are padded, so with none `width` is required.  Either way the v210 rows must hold it."""
+    told = None
+    if fin.nplanes == 3:
+        told = src[0].shape[-1]
+    elif fout.nplanes == 3 and dst is not None:
+        told = dst[0].shape[-1]
+    if told is None and width is None:
+        raise ValueError("width is required with v210 frames when no planar side tells it: v210 rows are padded")
+    if told is not None and width is not None and int(width) != told:
+        raise ValueError(f"width {width} does not match the planes ({told})")
+    w = told if told is not None else int(width)
+    if w < 1:
+        raise ValueError(f"bad width {w}")
+    return w
+
+
+def parse_pix_fmt(name: str) -> PixFmt:
+    m = _PIXFMT_RE.match(name or "")
+    if not m:
+        raise ValueError(f"unsupported pixel format '{name}'")
+    fam, sub, depth, _le = m.groups()
+    depth_i = int(depth) if depth else 8
+    if not 8 <= depth_i <= 16:
+        raise ValueError(f"unsupported bit depth in '{name}'")
+    if fam in ("gbr", "gbra"):
+        if sub:
+            raise ValueError(f"unsupported pixel format '{name}'")
+        return PixFmt(name, "gbr", depth_i, 0, 0, True, fam == "gbra")
+    if not sub:
+        raise ValueError(f"unsupported pixel format '{name}'")
+    csx, csy = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}[sub]
+    return PixFmt(name, "yuv", depth_i, csx, csy, fam == "yuvj", fam == "yuva")
+
+
+@dataclass(frozen=True)
+class RgbSource:
+    """An RGB source format of `LutEngine.apply_rgb_to_yuv`: planar `gbrp*`, a packed name of `_native.PACKED_FORMATS`, or a
+    planar float name of `_native.FLOAT_FORMATS`."""
+    name: str
+    packed: bool
+    depth: int        # the depth lut3d runs at: the source's (packed: 8 or 16); float: 16, the depth of the output stage's codes
+    ncomp: int        # components per pixel of a packed image; 1 for planar
+    code: int         # src_kind of lutr_apply_rgb_to_yuv: 0 planar, else LUTR_PACKED(...)
+    floating: bool = False   # 32-bit float planes: lutr_apply_planar_rgb_f32 / lutr_apply_rgbf_to_yuv
+    nplanes: int = 3         # planes per frame of a planar source (gbrap*, gbrapf32le: 4, the last one alpha)
+
+    @property
+    def alpha_slot(self) -> Optional[int]:
+        """The component index of a packed format's real alpha (rgba: 3, argb: 0), None for every other format -- rgb0's pad byte
+        is not alpha."""
+        return _native.PACKED_ALPHA.get(self.name) if self.packed else None
+
+    @property
+    def itemsize(self) -> int:
+        return 4 if self.floating else 1 if self.depth <= 8 else 2
+
+    def frame_bytes(self, w: int, h: int) -> int:
+        return h * w * (self.ncomp if self.packed else self.nplanes) * self.itemsize
+
+
+def parse_rgb_source(name: Optional[str]) -> Optional[RgbSource]:
+    """The RGB source `name` stands for, or None when it is not an RGB format the engine takes (`parse_pix_fmt` keeps rejecting
+    packed names: it describes planar frames)."""
+    if name in _native.PACKED_FORMATS:
+        bits, nc, ro, go, bo = _native.PACKED_FORMATS[name]
+        return RgbSource(name, True, bits, nc, _native.packed_code(bits, nc, ro, go, bo))
+    if name in _native.FLOAT_FORMATS:
+        return RgbSource(name, False, 16, 1, 0, True, _native.FLOAT_FORMATS[name])
+    try:
+        fmt = parse_pix_fmt(name)
+    except ValueError:
+        return None
+    return RgbSource(name, False, fmt.depth, 1, 0, False, fmt.nplanes) if fmt.family == "gbr" else None
+
+
+def chroma_loc_code(chroma_loc: Optional[str]) -> int:
+    """enum lutr_chroma_loc for a chroma_location name (None = replicate); ValueError for any other name."""
+    if chroma_loc is None:
+        return _native.CHROMA_REPLICATE
+    if chroma_loc not in _native.CHROMA_LOC:
+        raise ValueError(f"unknown chroma location '{chroma_loc}' (None | {' | '.join(_native.CHROMA_LOC)})")
+    return _native.CHROMA_LOC[chroma_loc]
+
+
+def check_chroma_loc(chroma_loc: Optional[str], dither: str = "none", pix_fmt: Optional[str] = None,
+                     out_pix_fmt: Optional[str] = None) -> None:
+    """The checks `apply_yuv` makes of `chroma_loc` before any GPU work: a known name, no error-diffusion dither with it, and
+    (given the two pixel formats) no chroma subsampling change with it -- sited resampling across layouts is not defined."""
+    chroma_loc_code(chroma_loc)
+    if chroma_loc is not None and dither != "none":
+        raise ValueError("error-diffusion dither is not defined with sited chroma resampling (chroma_loc)")
+    if chroma_loc is not None and pix_fmt and out_pix_fmt and changes_subsampling(pix_fmt, out_pix_fmt):
+        raise ValueError(f"sited chroma resampling (chroma_loc) is not defined with a chroma subsampling change "
+                         f"('{pix_fmt}' -> '{out_pix_fmt}'); drop chroma_loc to replicate / average over the chroma blocks")
+
+
+def changes_subsampling(pix_fmt: str, out_pix_fmt: Optional[str]) -> bool:
+    """True when the two planar YUV formats differ in chroma subsampling."""
+    if not out_pix_fmt:
+        return False
+    a, b = parse_pix_fmt(pix_fmt.replace("yuvj", "yuv")), parse_pix_fmt(out_pix_fmt.replace("yuvj", "yuv"))
+    return (a.csx, a.csy) != (b.csx, b.csy)
+
+
+#: keywords of `apply_yuv` that the two-output pass does not take, and what its refusals call them
+_DUAL_NOT_TAKEN = {"dither": "error-diffusion dither", "chroma_loc": "sited chroma resampling (chroma_loc)",
+                   "out_size": "a resize (out_size)", "resize_chunk": "a resize (out_size)",
+                   "width": "a packed side (width)"}
+#: ... and of `apply_yuv` / `apply_yuv_dual` that the two-LUT pass does not take
+_CHAIN_NOT_TAKEN = dict(_DUAL_NOT_TAKEN, dither="dither", out2_pix_fmt="a second output (out2_pix_fmt)",
+                        dst2="a second output (dst2)")
+
+
+def _pass_side(name: Optional[str], what: str, noun: str, sides: str, fine: bool) -> PixFmt:
+    """One side of the two-output or the two-LUT pass (`noun`), a planar YUV format (yuvj* read as yuv*); ValueError for RGB,
+    float, semi-planar, packed and v210 names.  `what` names the argument in the message.  `fine`: the two-LUT pass's
+    refusals -- it tells semi-planar from packed and float from integer RGB, and takes neither v210's relatives nor alpha."""
+    if not name:
+        raise ValueError(f"the {noun} pass needs {what}")
+    head = f"the {noun} pass takes planar YUV on {sides}: {what} '{name}'"
+    semi = parse_semi_fmt(name) is not None
+    if semi or parse_packed_yuv_fmt(name) is not None or name in _PACKED_YUV_UNSUPPORTED:
+        kind = "semi-planar or packed" if not fine else "semi-planar" if semi else "packed"
+        raise ValueError(f"{head} is a {kind} container")
+    if parse_v210_fmt(name) is not None or (fine and name in _V210_UNSUPPORTED):
+        raise ValueError(f"{head} is a v210 container")
+    rgb = parse_rgb_source(name)
+    if rgb is not None:
+        raise ValueError(f"{head} is a float RGB format" if fine and rgb.floating else f"{head} is an RGB format")
+    fmt = parse_pix_fmt(name.replace("yuvj", "yuv"))
+    if fine and fmt.alpha:
+        raise ValueError(f"{head} carries alpha")
+    return fmt
+
+
+def _refuse_pass_options(not_taken: dict, tail: str, dither: str, chroma_loc: Optional[str], out_size) -> None:
+    """ValueError for dither, chroma_loc or out_size with a second output / a second LUT (`tail`), in the words of `not_taken`."""
+    for k, given in (("dither", dither != "none"), ("chroma_loc", chroma_loc is not None), ("out_size", out_size is not None)):
+        if given:
+            raise ValueError(f"{not_taken[k]} is not supported with {tail}")
+
+
+def _refuse_keywords(kw: dict, not_taken: dict, tail: str, method: str) -> None:
+    for k, what in not_taken.items():
+        if k in kw:
+            raise ValueError(f"{what} is not supported with {tail}: {method} takes no '{k}'")
+
+
+def dual_side(name: Optional[str], what: str) -> PixFmt:
+    """One side of `apply_yuv_dual`, a planar YUV format (yuvj* read as yuv*); ValueError for RGB, float, semi-planar and packed
+    names.  `what` names the argument in the message."""
+    return _pass_side(name, what, "two-output", "every side", False)
+
+
+def check_dual_options(pix_fmt: str, out_pix_fmt: Optional[str], out2_pix_fmt: Optional[str], dither: str = "none",
+                       chroma_loc: Optional[str] = None, out_size=None) -> Tuple[PixFmt, PixFmt, PixFmt]:
+    """The checks `apply_yuv_dual` makes of its formats and options before any GPU work: three planar YUV
+    sides, no dither, chroma_loc or out_size.  Returns the three parsed formats (source, first output, second output)."""
+    fin = dual_side(pix_fmt, "pix_fmt")
+    f1 = dual_side(out_pix_fmt or pix_fmt, "out_pix_fmt")
+    f2 = dual_side(out2_pix_fmt, "out2_pix_fmt")
+    _refuse_pass_options(_DUAL_NOT_TAKEN, "a second output", dither, chroma_loc, out_size)
+    return fin, f1, f2
+
+
+def refuse_dual_keywords(kw: dict) -> None:
+    """ValueError when `kw` holds a keyword of `apply_yuv` that the two-output pass does not take, whatever its value."""
+    _refuse_keywords(kw, _DUAL_NOT_TAKEN, "a second output", "apply_yuv_dual")
+
+
+def chain_side(name: Optional[str], what: str) -> PixFmt:
+    """One side of `apply_yuv_chain`, a planar YUV format without alpha (yuvj* read as yuv*); ValueError for alpha, RGB, float,
+    semi-planar, packed and v210 names.  `what` names the argument in the message."""
+    return _pass_side(name, what, "two-LUT", "both sides", True)
+
+
+def check_chain_options(pix_fmt: str, out_pix_fmt: Optional[str], dither: str = "none", chroma_loc: Optional[str] = None,
+                        out_size=None, second_pix_fmt: Optional[str] = None) -> Tuple[PixFmt, PixFmt]:
+    """The checks `apply_yuv_chain` makes of its formats and options before any GPU work: two planar YUV sides
+    without alpha, no dither, chroma_loc, out_size or second output.  Returns the two parsed formats."""
+    fin = chain_side(pix_fmt, "pix_fmt")
+    fout = chain_side(out_pix_fmt or pix_fmt, "out_pix_fmt")
+    _refuse_pass_options(_CHAIN_NOT_TAKEN, "a second LUT", dither, chroma_loc, out_size)
+    if second_pix_fmt is not None:
+        raise ValueError("a second output is not supported with a second LUT")
+    return fin, fout
+
+
+def refuse_chain_keywords(kw: dict) -> None:
+    """ValueError when `kw` holds a keyword of `apply_yuv` / `apply_yuv_dual` that the two-LUT pass does not take, whatever its
+    value."""
+    _refuse_keywords(kw, _CHAIN_NOT_TAKEN, "a second LUT", "apply_yuv_chain")
+
+
+def check_lut2(lut) -> None:
+    """ValueError for a second LUT that carries a prelut (a .csp shaper): lut3d's prelut is only taken on the first LUT."""
+    if lut is not None and getattr(lut, "prelut", None) is not None:
+        raise ValueError("the second LUT carries a prelut (a .csp shaper): a prelut is only supported on the first LUT")
+
+
+def chain_interp(interp: str, interp2: Optional[str]) -> Tuple[int, int]:
+    """The two mode codes of `apply_yuv_chain` (`interp2` None = `interp`); ValueError for a name lut3d does not have."""
+    for name in (interp, interp2):
+        if name is not None and name not in _native.INTERP:
+            raise ValueError(f"lut3d has no interpolation mode '{name}'")
+    return _native.INTERP[interp], _native.INTERP[interp if interp2 is None else interp2]
+
+
+
+#: how the colour planes of an alpha-carrying source stand to their alpha
+ALPHA_MODES = ("straight", "premultiplied")
+
+
+def check_alpha_mode(alpha_mode) -> bool:
+    """True for "premultiplied", False for "straight" (the default everywhere: today's paths, bit for bit); ValueError for any
+    other value."""
+    if alpha_mode not in ALPHA_MODES:
+        raise ValueError(f"unknown alpha_mode '{alpha_mode}' ({' | '.join(ALPHA_MODES)})")
+    return alpha_mode == "premultiplied"
+
+
+def has_prologue(depth: int, range_src: str = "tv", range_in: Optional[str] = None, lut_depth: Optional[int] = None) -> bool:
+    """True when a YUV call from a source of `depth` bits has a prologue: a range conversion ahead of the LUT (range_in other
+    than range_src) or a LUT depth other than the source's.  The reference's 8-bit intermediate has no alpha to carry."""
+    return (range_in or range_src) != range_src or (lut_depth is not None and int(lut_depth) != depth)
+
+
+def premul_to_yuv(pix_fmt: Optional[str], out_pix_fmt: Optional[str]) -> bool:
+    """`check_premul_options`' `to_yuv` for a pair of format names: an RGB source whose output (`out_pix_fmt`, None = the
+    source's) is not float."""
+    src = parse_rgb_source(pix_fmt)
+    out = parse_rgb_source(out_pix_fmt) if out_pix_fmt else src
+    return src is not None and not (out is not None and out.floating)
+
+
+def check_premul_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = None, *, dither: str = "none",
+                         chroma_loc: Optional[str] = None, out_size=None, range_src: str = "tv", range_in: Optional[str] = None,
+                         lut_depth: Optional[int] = None, out2_pix_fmt: Optional[str] = None, lut2: bool = False,
+                         to_yuv: bool = False) -> str:
+    """The checks every layer makes of alpha_mode="premultiplied" before any GPU work: "yuv" for a planar yuva*
+    source with a planar YUV output, "float" for gbrapf32le in and out; ValueError for everything the contract does not define.
+    `to_yuv`: the call is `apply_rgb_to_yuv`'s; `lut2`: a second LUT is set for the call; `out2_pix_fmt`: a second output."""
+    head = "alpha_mode='premultiplied'"
+    src = parse_rgb_source(pix_fmt)
+    if src is not None and not src.floating:
+        raise ValueError(f"{head} is not defined for the integer RGB source '{pix_fmt}': PNG / TIFF alpha is straight by "
+                         f"specification")
+    if src is not None:
+        if src.nplanes != 4:
+            raise ValueError(f"{head} needs a source that carries alpha: '{pix_fmt}' has none")
+    else:
+        try:
+            side = yuv_side(pix_fmt)
+        except ValueError:
+            raise ValueError(f"{head} needs a source that carries alpha: '{pix_fmt}' is not one the engine takes") from None
+        if not getattr(side, "alpha", False):
+            raise ValueError(f"{head} needs a source that carries alpha: '{pix_fmt}' has none")
+    if out2_pix_fmt is not None:
+        raise ValueError(f"{head} is not supported with the two-output pass (out2_pix_fmt)")
+    if lut2:
+        raise ValueError(f"{head} is not supported with the two-LUT chain (a second LUT)")
+    if dither != "none":
+        raise ValueError(f"{head} is not supported with dither ('{dither}')")
+    if chroma_loc is not None:
+        raise ValueError(f"{head} is not supported with sited chroma resampling (chroma_loc)")
+    if out_size is not None:
+        raise ValueError(f"{head} is not supported with a resize (out_size / resolution)")
+    out_name = out_pix_fmt or pix_fmt
+    if src is not None:
+        if to_yuv or out_name != pix_fmt:
+            raise ValueError(f"{head}: a float source with an integer or YUV output ('{pix_fmt}' -> '{out_name}') is not "
+                             f"supported; '{pix_fmt}' in and out is")
+        return "float"
+    if to_yuv:
+        raise ValueError(f"{head} is not supported from an RGB source into YUV (apply_rgb_to_yuv)")
+    try:
+        out = yuv_side(out_name)
+    except ValueError:
+        out = None
+    if not isinstance(out, PixFmt) or out.family != "yuv":
+        raise ValueError(f"{head} takes a planar YUV output (yuv* / yuva*), not '{out_name}'")
+    if has_prologue(side.depth, range_src, range_in, lut_depth):
+        raise ValueError(f"{head} is not defined for a call with a prologue (range_src != range_in, or lut_depth other than the "
+                         f"source's depth {side.depth}): such a call has no alpha to carry")
+    return "yuv"
+
+
+def parse_size(size) -> Tuple[int, int]:
+    """(w, h) from a (w, h) pair or a "WxH" string as ffmpeg's -s takes it; ValueError for anything else."""
+    if isinstance(size, str):
+        m = re.fullmatch(r"([1-9][0-9]*)x([1-9][0-9]*)", size)
+        if not m:
+            raise ValueError(f"bad size '{size}' (expected WxH, e.g. 1920x1080)")
+        return int(m.group(1)), int(m.group(2))
+    try:
+        w, h = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"bad size {size!r} (expected (w, h) or 'WxH')") from None
+    if w < 1 or h < 1:
+        raise ValueError(f"bad size {size!r}")
+    return w, h
+
+
+_ALPHA_RESIZE = "a resize (out_size) is not supported with an alpha-carrying output ('{}'): the resize takes three planes"
+
+
+def refuse_alpha_resize(out_pix_fmt: Optional[str], out_size) -> None:
+    """ValueError for a resize (`out_size` / `resolution`) into an alpha-carrying planar output; any other name
+    passes, whatever it is."""
+    if out_size is None or not out_pix_fmt:
+        return
+    try:
+        fmt = parse_pix_fmt(out_pix_fmt)
+    except ValueError:
+        return
+    if fmt.alpha:
+        raise ValueError(_ALPHA_RESIZE.format(out_pix_fmt))

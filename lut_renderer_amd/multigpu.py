@@ -28,9 +28,28 @@ import torch
 
 from . import _native
 from .cube import CubeLut, read_lut
-from .engine import (LutEngine, _new_planes, _yuv_out_dtype, chain_args, check_alpha_mode, check_premul_options, check_container_options, check_lut2, dual_args, packed_frame_width, parse_pix_fmt,
-                     parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords, v210_frame_width, yuv_side)
+from .engine import LutEngine, _fresh_planes, _new_planes, _yuv_out_dtype, chain_args, dual_args
+from .formats import (check_alpha_mode, check_container_options, check_lut2, check_premul_options, packed_frame_width, parse_pix_fmt,
+                      parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords, v210_frame_width, yuv_side)
 from .shard import row_blocks
+
+
+def _row_ranges(fmt, r0: int, r1: int) -> list:
+    """The rows of every plane of side `fmt` that hold the luma rows [r0, r1): luma, chroma, chroma -- counted in the side's own
+    layout -- and alpha with the luma rows.  A side of fewer planes reads the front of the list."""
+    c0, c1 = r0 >> fmt.csy, (r1 + (1 << fmt.csy) - 1) >> fmt.csy
+    return [(r0, r1), (c0, c1), (c0, c1)] + [(r0, r1)] * getattr(fmt, "alpha", False)
+
+
+def _travel(planes, rng, device) -> list:
+    """The rows `rng` of `planes`, copied to `device` (the peer copy: asynchronous, ordered by torch's streams)."""
+    return [p[..., a:b, :].to(device, non_blocking=True, copy=True).contiguous() for p, (a, b) in zip(planes, rng)]
+
+
+def _crop(full, fmt, s0: int, r0: int, r1: int):
+    """(the rows [r0, r1) of the output planes `full` of a slice that began at luma row s0, their row ranges in the frame)."""
+    rng = _row_ranges(fmt, r0, r1)
+    return [o[..., a - sa:b - sa, :] for o, (a, b), (sa, _) in zip(full, rng, _row_ranges(fmt, s0, r1))], rng
 
 
 def _bn_anchor(r0: int, ocsy: int) -> int:
@@ -137,6 +156,29 @@ class LutEngineGroup:
             e.sync()
 
     # -- apply ------------------------------------------------------------
+    def _shard(self, h: int, align: int, home, local, remote) -> None:
+        """The one loop over the group's row blocks (`shard.row_blocks`, on multiples of `align` rows; empty blocks are skipped).
+        A block whose engine sits on `home`, the device of the caller's planes, is launched on those planes: `local(eng, r0, r1)`.
+        A block of another GPU travels there (peer copy), is processed as a short frame of its own and comes back:
+        `remote(eng, r0, r1)` runs with that GPU current and returns (destination planes, output planes, row ranges) per output;
+        the copies back are queued after every launch was issued."""
+        blocks = row_blocks(h, len(self.engines), align=align)
+        self.last_blocks = blocks
+        self.last_remote = 0                                       # row blocks that took the copy-there-and-back path
+        pending = []
+        for k, (eng, (r0, r1)) in enumerate(zip(self.engines, blocks)):
+            if r1 <= r0:
+                continue
+            if eng.device == home and not (self.treat_as_remote and k > 0):
+                local(eng, r0, r1)
+                continue
+            with torch.cuda.device(eng.device):
+                pending += remote(eng, r0, r1)
+            self.last_remote += 1
+        for to, out, rng in pending:
+            for d, o, (a, b) in zip(to, out, rng):
+                d[..., a:b, :].copy_(o, non_blocking=True)
+
     def apply_yuv(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str,
                   out_pix_fmt: Optional[str] = None, **kw):
         with self._lock:
@@ -175,67 +217,30 @@ class LutEngineGroup:
             h, w = src[0].shape[-2], packed_frame_width(fin, src, kw.get("width"))
         home = src[0].device
         if dst is None:
-            # (a fresh v210 buffer is zeroed: the kernels never write the padding of a row)
-            dst = [torch.zeros(tuple(src[0].shape[:-2]) + fout.plane_shape(0, w, h), dtype=torch.int32, device=home)] \
-                if kind == "v210" and fout.nplanes == 1 else \
-                _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), home)
+            dst = _fresh_planes(fout, w, h, src[0], home)
+        names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt)
         bh = 1 << max(fin.csy, fout.csy)                           # the union block: whole chroma rows on both sides
-        blocks = row_blocks(h, len(self.engines), align=bh)
-        self.last_blocks = blocks
-        pending = []
-        self.last_remote = 0                                       # row blocks that took the copy-there-and-back path
-        for k, (eng, (r0, r1)) in enumerate(zip(self.engines, blocks)):
-            if r1 <= r0:
-                continue
-            if eng.device == home and not (self.treat_as_remote and k > 0):
-                # same GPU: launch on the caller's planes, rows [r0, r1)
-                eng.apply_yuv(src, dst, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0, rows=r1 - r0, **kw)
-                continue
-            # another GPU: its row block travels there (peer copy), is processed as a frame of r1-r0 rows, and comes back.
-            # Source and destination chroma rows are counted in their own layouts.
-            c0, c1 = r0 >> fin.csy, (r1 + (1 << fin.csy) - 1) >> fin.csy
-            o0, o1 = r0 >> fout.csy, (r1 + (1 << fout.csy) - 1) >> fout.csy
-            # (an alpha plane, DESIGN.md 3.16, is sharded with the luma rows on either side)
-            a_in, a_out = getattr(fin, "alpha", False), getattr(fout, "alpha", False)
-            src_rng = [(r0, r1), (c0, c1), (c0, c1)] + [(r0, r1)] * a_in
-            rng = [(r0, r1), (o0, o1), (o0, o1)] + [(r0, r1)] * a_out
+
+        def local(eng, r0, r1):
+            eng.apply_yuv(src, dst, row0=r0, rows=r1 - r0, **names, **kw)
+
+        def remote(eng, r0, r1):
+            # the slice that travels is the luma rows [s0, s1) with the chroma rows of the source's own layout; the apply writes the
+            # block's rows inside it (row0 = r0 - s0: 0 for a slice that is just the block)
+            s0, s1 = r0, r1
             if kw.get("chroma_loc") is not None:
                 # sited resampling reads one chroma row (one chroma block row of luma) above and below the block: the slice
-                # that travels carries that halo, clipped to the frame, and the apply writes the block's rows inside it
-                ch = (h + bh - 1) >> fin.csy
-                h0, h1 = max(c0 - 1, 0), min(c1 + 1, ch)
-                srng = [(h0 * bh, min(h1 * bh, h)), (h0, h1), (h0, h1)] + [(h0 * bh, min(h1 * bh, h))] * a_in
-                with torch.cuda.device(eng.device):
-                    part = [p[..., a:b, :].to(eng.device, non_blocking=True, copy=True).contiguous()
-                            for p, (a, b) in zip(src, srng)]
-                    full = eng.apply_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0 - h0 * bh, rows=r1 - r0,
-                                         **kw)
-                    out = [o[..., a - sa:b - sa, :] for o, (a, b), sa in zip(full, rng, (h0 * bh, h0, h0, h0 * bh))]
-                self.last_remote += 1
-                pending.append((out, rng))
-                continue
-            if kw.get("dither", "none") == "blue_noise":
-                # the mask is anchored to the frame's top: the slice that travels starts at a row where the
-                # pattern of every output plane starts over, and the apply writes the block's rows inside it
-                h0 = _bn_anchor(r0, fout.csy)
-                srng = [(h0, r1), (h0 >> fin.csy, c1), (h0 >> fin.csy, c1)] + [(h0, r1)] * a_in
-                with torch.cuda.device(eng.device):
-                    part = [p[..., a:b, :].to(eng.device, non_blocking=True, copy=True).contiguous()
-                            for p, (a, b) in zip(src, srng)]
-                    full = eng.apply_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0 - h0, rows=r1 - r0, **kw)
-                    out = [o[..., a - sa:b - sa, :] for o, (a, b), sa in zip(full, rng, (h0, h0 >> fout.csy, h0 >> fout.csy, h0))]
-                self.last_remote += 1
-                pending.append((out, rng))
-                continue
-            with torch.cuda.device(eng.device):
-                part = [p[..., a:b, :].to(eng.device, non_blocking=True, copy=True).contiguous()
-                        for p, (a, b) in zip(src, src_rng)]
-                out = eng.apply_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, **kw)
-            self.last_remote += 1
-            pending.append((out, rng))
-        for out, rng in pending:                                   # copies back: queued after every launch was issued
-            for d, o, (a, b) in zip(dst, out, rng):
-                d[..., a:b, :].copy_(o, non_blocking=True)
+                # carries that halo, clipped to the frame
+                c0, c1 = _row_ranges(fin, r0, r1)[1]
+                s0, s1 = max(c0 - 1, 0) * bh, min((c1 + 1) * bh, h)
+            elif kw.get("dither", "none") == "blue_noise":
+                # the mask is anchored to the frame's top: the slice starts at a row where the pattern of every
+                # output plane starts over
+                s0 = _bn_anchor(r0, fout.csy)
+            full = eng.apply_yuv(_travel(src, _row_ranges(fin, s0, s1), eng.device), None, row0=r0 - s0, rows=r1 - r0, **names, **kw)
+            return [(dst, *_crop(full, fout, s0, r0, r1))]
+
+        self._shard(h, bh, home, local, remote)
         return dst[0] if bare else dst
 
     def apply_yuv_dual(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None,
@@ -248,37 +253,21 @@ class LutEngineGroup:
                 raise ValueError("the group owns the row partition")
             refuse_dual_keywords(kw)
             fin, f1, f2, w, h = dual_args(src, dst, dst2, pix_fmt, out_pix_fmt, out2_pix_fmt)
-            home, lead = src[0].device, tuple(src[0].shape[:-2])
+            home = src[0].device
             if dst is None:
-                dst = _new_planes(f1, w, h, lead, _yuv_out_dtype(f1.depth, src[0].dtype), home)
+                dst = _fresh_planes(f1, w, h, src[0], home)
             if dst2 is None:
-                dst2 = _new_planes(f2, w, h, lead, _yuv_out_dtype(f2.depth, src[0].dtype), home)
+                dst2 = _fresh_planes(f2, w, h, src[0], home)
             names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, out2_pix_fmt=out2_pix_fmt)
-            blocks = row_blocks(h, len(self.engines), align=1 << max(fin.csy, f1.csy, f2.csy))
-            self.last_blocks = blocks
-            self.last_remote = 0
-            pending = []
 
-            def rng_of(fmt, r0, r1):
-                c0, c1 = r0 >> fmt.csy, (r1 + (1 << fmt.csy) - 1) >> fmt.csy
-                return [(r0, r1), (c0, c1), (c0, c1)] + [(r0, r1)] * fmt.alpha      # (alpha rows go with the luma rows)
+            def local(eng, r0, r1):
+                eng.apply_yuv_dual(src, dst, dst2, row0=r0, rows=r1 - r0, **names, **kw)
 
-            for k, (eng, (r0, r1)) in enumerate(zip(self.engines, blocks)):
-                if r1 <= r0:
-                    continue
-                if eng.device == home and not (self.treat_as_remote and k > 0):
-                    eng.apply_yuv_dual(src, dst, dst2, row0=r0, rows=r1 - r0, **names, **kw)
-                    continue
-                with torch.cuda.device(eng.device):
-                    part = [p[..., a:b, :].to(eng.device, non_blocking=True, copy=True).contiguous()
-                            for p, (a, b) in zip(src, rng_of(fin, r0, r1))]
-                    out, out2 = eng.apply_yuv_dual(part, None, None, **names, **kw)
-                self.last_remote += 1
-                pending.append((dst, out, rng_of(f1, r0, r1)))
-                pending.append((dst2, out2, rng_of(f2, r0, r1)))
-            for to, out, rng in pending:                           # copies back: queued after every launch was issued
-                for d, o, (a, b) in zip(to, out, rng):
-                    d[..., a:b, :].copy_(o, non_blocking=True)
+            def remote(eng, r0, r1):
+                out, out2 = eng.apply_yuv_dual(_travel(src, _row_ranges(fin, r0, r1), eng.device), None, None, **names, **kw)
+                return [(dst, out, _row_ranges(f1, r0, r1)), (dst2, out2, _row_ranges(f2, r0, r1))]
+
+            self._shard(h, 1 << max(fin.csy, f1.csy, f2.csy), home, local, remote)
             return dst, dst2
 
     def apply_yuv_chain(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str,
@@ -292,32 +281,17 @@ class LutEngineGroup:
             fin, fout, w, h, _, _ = chain_args(src, dst, pix_fmt, out_pix_fmt, interp, interp2)
             home = src[0].device
             if dst is None:
-                dst = _new_planes(fout, w, h, tuple(src[0].shape[:-2]), _yuv_out_dtype(fout.depth, src[0].dtype), home)
+                dst = _fresh_planes(fout, w, h, src[0], home)
             names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, interp=interp, interp2=interp2)
-            blocks = row_blocks(h, len(self.engines), align=1 << max(fin.csy, fout.csy))
-            self.last_blocks = blocks
-            self.last_remote = 0
-            pending = []
 
-            def rng_of(fmt, r0, r1):
-                c0, c1 = r0 >> fmt.csy, (r1 + (1 << fmt.csy) - 1) >> fmt.csy
-                return [(r0, r1), (c0, c1), (c0, c1)]
+            def local(eng, r0, r1):
+                eng.apply_yuv_chain(src, dst, row0=r0, rows=r1 - r0, **names, **kw)
 
-            for k, (eng, (r0, r1)) in enumerate(zip(self.engines, blocks)):
-                if r1 <= r0:
-                    continue
-                if eng.device == home and not (self.treat_as_remote and k > 0):
-                    eng.apply_yuv_chain(src, dst, row0=r0, rows=r1 - r0, **names, **kw)
-                    continue
-                with torch.cuda.device(eng.device):
-                    part = [p[..., a:b, :].to(eng.device, non_blocking=True, copy=True).contiguous()
-                            for p, (a, b) in zip(src, rng_of(fin, r0, r1))]
-                    out = eng.apply_yuv_chain(part, None, **names, **kw)
-                self.last_remote += 1
-                pending.append((out, rng_of(fout, r0, r1)))
-            for out, rng in pending:                               # copies back: queued after every launch was issued
-                for d, o, (a, b) in zip(dst, out, rng):
-                    d[..., a:b, :].copy_(o, non_blocking=True)
+            def remote(eng, r0, r1):
+                out = eng.apply_yuv_chain(_travel(src, _row_ranges(fin, r0, r1), eng.device), None, **names, **kw)
+                return [(dst, out, _row_ranges(fout, r0, r1))]
+
+            self._shard(h, 1 << max(fin.csy, fout.csy), home, local, remote)
             return dst
 
     def apply_rgb_to_yuv(self, src, dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: str, **kw):
@@ -344,35 +318,20 @@ class LutEngineGroup:
             home = first.device
             if dst is None:
                 dst = _new_planes(fout, w, h, lead, _yuv_out_dtype(fout.depth, None), home)
+            names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt)
 
-            def rows_of(a, b):
-                return src[..., a:b, :, :] if fin.packed else [p[..., a:b, :] for p in src]
+            def local(eng, r0, r1):
+                eng.apply_rgb_to_yuv(src, dst, row0=r0, rows=r1 - r0, **names, **kw)
 
-            blocks = row_blocks(h, len(self.engines), align=1 << csy)
-            self.last_blocks = blocks
-            self.last_remote = 0
-            pending = []
-            for k, (eng, (r0, r1)) in enumerate(zip(self.engines, blocks)):
-                if r1 <= r0:
-                    continue
-                if eng.device == home and not (self.treat_as_remote and k > 0):
-                    eng.apply_rgb_to_yuv(src, dst, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0, rows=r1 - r0, **kw)
-                    continue
-                o0, o1 = r0 >> fout.csy, (r1 + (1 << fout.csy) - 1) >> fout.csy
+            def remote(eng, r0, r1):
                 # (blue-noise dither: the slice starts where the pattern of every output plane starts over, as in _apply_yuv)
-                h0 = _bn_anchor(r0, fout.csy) if kw.get("dither", "none") == "blue_noise" else r0
-                with torch.cuda.device(eng.device):
-                    part = rows_of(h0, r1)
-                    part = part.to(eng.device, non_blocking=True, copy=True).contiguous() if fin.packed else \
-                        [p.to(eng.device, non_blocking=True, copy=True).contiguous() for p in part]
-                    if h0 == r0:
-                        out = eng.apply_rgb_to_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, **kw)
-                    else:
-                        full = eng.apply_rgb_to_yuv(part, None, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, row0=r0 - h0, rows=r1 - r0, **kw)
-                        out = [o[..., a - sa:, :] for o, a, sa in zip(full, (r0, o0, o0, r0), (h0, h0 >> fout.csy, h0 >> fout.csy, h0))]
-                self.last_remote += 1
-                pending.append((out, [(r0, r1), (o0, o1), (o0, o1)] + [(r0, r1)] * fout.alpha))      # (alpha rows: the luma rows)
-            for out, rng in pending:                               # copies back: queued after every launch was issued
-                for d, o, (a, b) in zip(dst, out, rng):
-                    d[..., a:b, :].copy_(o, non_blocking=True)
+                s0 = _bn_anchor(r0, fout.csy) if kw.get("dither", "none") == "blue_noise" else r0
+                if fin.packed:
+                    part = src[..., s0:r1, :, :].to(eng.device, non_blocking=True, copy=True).contiguous()
+                else:
+                    part = _travel(src, [(s0, r1)] * len(src), eng.device)
+                full = eng.apply_rgb_to_yuv(part, None, row0=r0 - s0, rows=r1 - r0, **names, **kw)
+                return [(dst, *_crop(full, fout, s0, r0, r1))]
+
+            self._shard(h, 1 << csy, home, local, remote)
             return dst

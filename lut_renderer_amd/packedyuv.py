@@ -12,7 +12,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from .engine import PackedYuvFmt, parse_packed_yuv_fmt
+from .formats import PackedYuvFmt, parse_packed_yuv_fmt
 from .semiplanar import _is_np, _shl, _shr
 
 #: position of (Y0, Y1, Cb, Cr) inside a group, by `PackedYuvFmt.order`

@@ -11,7 +11,7 @@ from typing import List, Sequence
 
 import numpy as np
 
-from .engine import SemiFmt, parse_semi_fmt
+from .formats import SemiFmt, parse_semi_fmt
 
 
 def _fmt(name: str) -> SemiFmt:

@@ -18,7 +18,9 @@ from typing import Callable, Iterable, Iterator, List, Optional
 import numpy as np
 import torch
 
-from .engine import LutEngine, RgbSource, parse_rgb_source, parse_size, refuse_alpha_resize, yuv_side
+from .engine import LutEngine
+from .formats import (RgbSource, check_alpha_mode, check_chain_options, check_dual_options, check_premul_options, parse_rgb_source,
+                      parse_size, premul_to_yuv, refuse_alpha_resize, yuv_side)
 
 
 @dataclass
@@ -123,10 +125,9 @@ def input_layout(pix_fmt: str, width: int, height: int):
 def dual_layout(pix_fmt: str, out_pix_fmt: Optional[str], second_pix_fmt: Optional[str], width: int, height: int, out_size=None,
                 apply_kw: Optional[dict] = None) -> Optional[FrameLayout]:
     """The layout of `HostPipeline`'s second output ring, or None without `second_pix_fmt`.  Planar YUV on
-    every side, no dither, chroma_loc or out_size (ValueError, `engine.check_dual_options`)."""
+    every side, no dither, chroma_loc or out_size (ValueError, `formats.check_dual_options`)."""
     if second_pix_fmt is None:
         return None
-    from .engine import check_dual_options
     kw = apply_kw or {}
     _, _, f2 = check_dual_options(pix_fmt, out_pix_fmt, second_pix_fmt, kw.get("dither", "none"), kw.get("chroma_loc"), out_size)
     return FrameLayout(f2, width, height)
@@ -144,18 +145,15 @@ class HostPipeline:
         `apply_kw` may carry `interp2`.  Planar YUV without alpha on both sides, no dither, chroma_loc, out_size or second output."""
         self.chain = bool(chain)
         # premultiplied alpha (DESIGN.md 3.18) travels in apply_kw like chroma_loc; "straight" is not passed on (today's calls)
-        from .engine import check_alpha_mode, check_premul_options
         premul = check_alpha_mode(apply_kw.get("alpha_mode", "straight"))
         if premul:
-            src_, out_ = parse_rgb_source(pix_fmt), parse_rgb_source(out_pix_fmt) if out_pix_fmt else parse_rgb_source(pix_fmt)
             check_premul_options(pix_fmt, out_pix_fmt, dither=apply_kw.get("dither", "none"), chroma_loc=apply_kw.get("chroma_loc"),
                                  out_size=out_size, range_src=apply_kw.get("range_src", "tv"), range_in=apply_kw.get("range_in"),
                                  lut_depth=apply_kw.get("lut_depth"), out2_pix_fmt=second_pix_fmt, lut2=self.chain,
-                                 to_yuv=src_ is not None and not (out_ is not None and out_.floating))
+                                 to_yuv=premul_to_yuv(pix_fmt, out_pix_fmt))
         else:
             apply_kw = {k: v for k, v in apply_kw.items() if k != "alpha_mode"}
         if self.chain:
-            from .engine import check_chain_options
             check_chain_options(pix_fmt, out_pix_fmt, apply_kw.get("dither", "none"), apply_kw.get("chroma_loc"), out_size,
                                 second_pix_fmt)
             apply_kw = {k: v for k, v in apply_kw.items() if k != "dither"}

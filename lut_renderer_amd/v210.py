@@ -22,7 +22,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from .engine import V210Fmt
+from .formats import V210Fmt
 from .semiplanar import _is_np
 
 #: slot of a group -> (word, bit offset): luma samples 0..5, Cb of pairs 0..2, Cr of pairs 0..2

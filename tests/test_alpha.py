@@ -336,3 +336,23 @@ def test_abi_symbol_struct_and_null_context():
     a = _native.AlphaSrc()
     assert lib.lutr_alpha_plane(None, C.byref(a), 10, None, 0, 0, 8, 6, 1, 0, 6) == _native.EINVAL
     assert b"null argument" in lib.lutr_last_error()
+
+
+def test_alpha_plane_source_refusals_keep_their_words():
+    """`_alpha_plane`'s checks of its source, in order: dense along the row, on the engine's device, as many frames as the
+    destination (host only: an engine object without a context)."""
+    import torch
+    from lut_renderer_amd.engine import LutEngine
+    eng = object.__new__(LutEngine)
+    eng.device = torch.device("cpu")
+    dst = torch.zeros((2, 6, 8), dtype=torch.int16)
+    with pytest.raises(ValueError, match="^planes must be dense along the row$"):
+        eng._alpha_plane(torch.zeros((2, 6, 16), dtype=torch.int16, device="meta")[..., ::2], dst, 10, 10, 8, 6, 0, None)
+    with pytest.raises(ValueError, match="^planes must be torch tensors resident on the engine's GPU$"):
+        eng._alpha_plane(torch.zeros((2, 6, 8), dtype=torch.int16, device="meta"), dst, 10, 10, 8, 6, 0, None)
+    with pytest.raises(ValueError, match="^src and dst disagree on the number of frames$"):
+        eng._alpha_plane(torch.zeros((6, 8), dtype=torch.int16), dst, 10, 10, 8, 6, 0, None)
+    with pytest.raises(ValueError, match="^src and dst disagree on the number of frames$"):
+        eng._alpha_plane(torch.zeros((3, 6, 8, 4), dtype=torch.uint8), dst, 8, 10, 8, 6, 0, None, 3)
+    with pytest.raises(ValueError, match="^planes must be dense along the row and resident on the engine's GPU$"):
+        eng._alpha_plane(None, torch.zeros((2, 6, 8), dtype=torch.int16, device="meta"), 10, 10, 8, 6, 0, None)

@@ -405,3 +405,39 @@ def test_host_pipeline_checks_a_chain_before_it_allocates():
                         (dict(out_size=(8, 4)), "resize"), (dict(dither="blue_noise"), "dither")):
         with pytest.raises(ValueError, match=message):
             HostPipeline(SimpleNamespace(), "yuv420p10le", 16, 8, chain=True, **kw)
+
+
+def test_two_lut_side_and_option_refusals_keep_their_words():
+    """Every refusal of `chain_side`, `check_chain_options` and `refuse_chain_keywords`, whole, and the order they fire in."""
+    from lut_renderer_amd.engine import refuse_chain_keywords
+    head = "the two-LUT pass takes planar YUV on both sides: out_pix_fmt"
+    for name, tail in (("nv12", "is a semi-planar container"), ("uyvy422", "is a packed container"), ("vuya", "is a packed container"),
+                       ("v210", "is a v210 container"), ("v410", "is a v210 container"), ("rgb24", "is an RGB format"),
+                       ("gbrap10le", "is an RGB format"), ("gbrapf32le", "is a float RGB format"), ("yuva444p12le", "carries alpha")):
+        with pytest.raises(ValueError) as e:
+            chain_side(name, "out_pix_fmt")
+        assert str(e.value) == f"{head} '{name}' {tail}"
+    for name in (None, ""):
+        with pytest.raises(ValueError) as e:
+            chain_side(name, "out_pix_fmt")
+        assert str(e.value) == "the two-LUT pass needs out_pix_fmt"
+    assert chain_side("yuvj420p", "pix_fmt").name == "yuv420p"
+    # a bad side goes before a bad option, and the options in the order dither, chroma_loc, out_size, second output
+    with pytest.raises(ValueError, match="^the two-LUT pass takes planar YUV on both sides: pix_fmt 'nv12'"):
+        check_chain_options("nv12", "yuva420p", "blue_noise", "left", (8, 4), "yuv420p")
+    for args, text in ((("blue_noise", "left", (8, 4), "yuv420p"), "dither is not supported with a second LUT"),
+                       (("none", "left", (8, 4), "yuv420p"), "sited chroma resampling (chroma_loc) is not supported with a second LUT"),
+                       (("none", None, (8, 4), "yuv420p"), "a resize (out_size) is not supported with a second LUT"),
+                       (("none", None, None, "yuv420p"), "a second output is not supported with a second LUT")):
+        with pytest.raises(ValueError) as e:
+            check_chain_options("yuv420p", "yuv422p10le", *args)
+        assert str(e.value) == text
+    with pytest.raises(ValueError) as e:
+        refuse_chain_keywords(dict(dst2=None, out2_pix_fmt="yuv420p", width=16))
+    assert str(e.value) == "a packed side (width) is not supported with a second LUT: apply_yuv_chain takes no 'width'"
+    with pytest.raises(ValueError) as e:
+        refuse_chain_keywords(dict(dst2=None, out2_pix_fmt="yuv420p"))
+    assert str(e.value) == "a second output (out2_pix_fmt) is not supported with a second LUT: apply_yuv_chain takes no 'out2_pix_fmt'"
+    with pytest.raises(ValueError) as e:
+        refuse_chain_keywords(dict(dst2=None))
+    assert str(e.value) == "a second output (dst2) is not supported with a second LUT: apply_yuv_chain takes no 'dst2'"

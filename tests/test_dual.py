@@ -291,3 +291,43 @@ def test_run_hands_both_outputs_of_a_batch_over_the_second_first():
     with pytest.raises(BrokenPipeError):
         HostPipeline.run(fake, lambda buf, n: n, broken, total_frames=4, drain2=lambda buf, n: seen.append(n))
     assert seen == [2]
+
+
+def test_two_output_side_and_option_refusals_keep_their_words():
+    """Every refusal of `dual_side`, `check_dual_options` and `refuse_dual_keywords`, whole, and the order they fire in."""
+    from lut_renderer_amd.engine import refuse_dual_keywords
+    head = "the two-output pass takes planar YUV on every side: out2_pix_fmt"
+    for name, tail in (("nv12", "is a semi-planar or packed container"), ("uyvy422", "is a semi-planar or packed container"),
+                       ("vuya", "is a semi-planar or packed container"), ("v210", "is a v210 container"),
+                       ("rgb24", "is an RGB format"), ("gbrap10le", "is an RGB format"), ("gbrpf32le", "is an RGB format")):
+        with pytest.raises(ValueError) as e:
+            dual_side(name, "out2_pix_fmt")
+        assert str(e.value) == f"{head} '{name}' {tail}"
+    for name in (None, ""):
+        with pytest.raises(ValueError) as e:
+            dual_side(name, "out2_pix_fmt")
+        assert str(e.value) == "the two-output pass needs out2_pix_fmt"
+    with pytest.raises(ValueError, match="unsupported pixel format 'v410'"):
+        dual_side("v410", "pix_fmt")                              # (v210's relatives are no name at all here)
+    assert dual_side("yuvj420p", "pix_fmt").name == "yuv420p" and dual_side("yuva444p12le", "pix_fmt").alpha
+    # a bad side goes before a bad option, and the options in the order dither, chroma_loc, out_size
+    with pytest.raises(ValueError, match="^the two-output pass takes planar YUV on every side: pix_fmt 'nv12'"):
+        check_dual_options("nv12", "p010le", "rgb24", "error_diffusion", "left", (8, 4))
+    with pytest.raises(ValueError, match="^the two-output pass takes planar YUV on every side: out_pix_fmt 'p010le'"):
+        check_dual_options("yuv420p", "p010le", "rgb24", "error_diffusion", "left", (8, 4))
+    for args, text in ((("blue_noise", "left", (8, 4)), "error-diffusion dither is not supported with a second output"),
+                       (("none", "left", (8, 4)), "sited chroma resampling (chroma_loc) is not supported with a second output"),
+                       (("none", None, (8, 4)), "a resize (out_size) is not supported with a second output")):
+        with pytest.raises(ValueError) as e:
+            check_dual_options("yuv420p", None, "yuv422p10le", *args)
+        assert str(e.value) == text
+    with pytest.raises(ValueError) as e:
+        refuse_dual_keywords(dict(width=16, resize_chunk=2, out_size=None))
+    assert str(e.value) == "a resize (out_size) is not supported with a second output: apply_yuv_dual takes no 'out_size'"
+    with pytest.raises(ValueError) as e:
+        refuse_dual_keywords(dict(width=16, resize_chunk=2))
+    assert str(e.value) == "a resize (out_size) is not supported with a second output: apply_yuv_dual takes no 'resize_chunk'"
+    with pytest.raises(ValueError) as e:
+        refuse_dual_keywords(dict(width=16))
+    assert str(e.value) == "a packed side (width) is not supported with a second output: apply_yuv_dual takes no 'width'"
+    refuse_dual_keywords(dict(dst2=None, out2_pix_fmt="yuv420p", interp="nearest"))

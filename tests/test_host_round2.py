@@ -182,3 +182,32 @@ def test_engine_command_precision_is_an_engine_option_with_a_strict_default():
     assert args.precision == "fast" and args.fps == 25.0
     assert cli.build_parser().parse_args(base[3:]).precision == "strict"
     assert abs(cli.build_parser().parse_args(base[3:] + ["--fps", "30000/1001"]).fps - 29.97002997) < 1e-6
+
+
+def test_planes_that_are_not_tensors_are_a_typeerror_at_every_site():
+    """The one TypeError text of every place that meets a plane: the three plane checks here, and (through a host-only engine
+    object) the two-output pass, the two-LUT pass and the alpha plane."""
+    from lut_renderer_amd.engine import LutEngine, _check_float_planes, _planes_struct, parse_rgb_source
+    text = "^planes must be torch tensors resident on the engine's GPU$"
+    cpu = torch.device("cpu")
+    with pytest.raises(TypeError, match=text):
+        _check_planes([None] * 3, parse_pix_fmt("yuv420p"), 8, 6, "source")
+    with pytest.raises(TypeError, match=text):
+        _check_float_planes([None] * 3, parse_rgb_source("gbrpf32le"), 8, 6, "source")
+    with pytest.raises(TypeError, match=text):
+        _planes_struct([None] * 3, cpu)
+    eng = object.__new__(LutEngine)
+    eng.device = cpu
+    with pytest.raises(TypeError, match=text):
+        eng.apply_yuv_dual([None] * 3, pix_fmt="yuv420p", out2_pix_fmt="yuv422p")
+    with pytest.raises(TypeError, match=text):
+        eng.apply_yuv_chain([None] * 3, pix_fmt="yuv420p")
+    with pytest.raises(TypeError, match=text):
+        eng._alpha_plane(np.zeros((6, 8), np.uint8), torch.zeros((6, 8), dtype=torch.uint8), 8, 8, 8, 6, 0, None)
+    # the plane-count refusals in front of it
+    with pytest.raises(ValueError, match="^expected three planes$"):
+        eng.apply_yuv_dual([None] * 2, pix_fmt="yuv420p", out2_pix_fmt="yuv422p")
+    with pytest.raises(ValueError, match="^'yuva420p' takes four planes: the three colour planes and alpha$"):
+        eng.apply_yuv_dual([None] * 3, pix_fmt="yuva420p", out2_pix_fmt="yuv422p")
+    with pytest.raises(ValueError, match="^expected three planes$"):
+        eng.apply_yuv_chain(torch.zeros((3, 6, 8), dtype=torch.uint8), pix_fmt="yuv420p")

@@ -301,3 +301,25 @@ def test_apply_lut_prologue_for_every_source_family():
                        ([torch.zeros((4, 8), dtype=torch.float32)] * 3, dict(pix_fmt="gbrpf32le"))):
         with pytest.raises(Reached):
             apply_lut(planes, cube=None, engine=Engine(), **kw)
+
+
+def test_container_sides_with_the_wrong_number_of_planes_keep_their_words():
+    """What `apply_yuv` says of a semi-planar, packed or v210 call whose source has the wrong number of planes, before it looks
+    at anything else (host only: an engine object without a context)."""
+    import torch
+    from lut_renderer_amd.engine import LutEngine
+    eng = object.__new__(LutEngine)
+    eng.device = torch.device("cpu")
+    y = torch.zeros((4, 16), dtype=torch.uint8)
+    for planes, kw, text in (([y], dict(pix_fmt="nv12"), "'nv12' takes 2 planes"),
+                             (y, dict(pix_fmt="nv12"), "'nv12' takes 2 planes"),
+                             ([y, y, y], dict(pix_fmt="nv12", out_pix_fmt="yuv420p"), "'nv12' takes 2 planes"),
+                             ([y, y], dict(pix_fmt="yuv420p", out_pix_fmt="nv12"), "'yuv420p' takes 3 planes"),
+                             ([y, y], dict(pix_fmt="uyvy422"), "'uyvy422' takes 1 plane"),
+                             (y, dict(pix_fmt="yuv422p", out_pix_fmt="uyvy422"), "'yuv422p' takes 3 planes"),
+                             ([y, y], dict(pix_fmt="v210", width=6), "'v210' takes 1 plane"),
+                             (y, dict(pix_fmt="yuv422p10le", out_pix_fmt="v210"), "'yuv422p10le' takes 3 planes"),
+                             ([y, y], dict(pix_fmt="yuv422p10le", out_pix_fmt="v210"), "'yuv422p10le' takes 3 planes")):
+        with pytest.raises(ValueError) as e:
+            eng.apply_yuv(planes, **kw)
+        assert str(e.value) == text, (kw, str(e.value))

@@ -335,3 +335,24 @@ def test_symbols_refuse_null_arguments():
     assert lib.lutr_apply_planar_rgb_f32_premul(None, 2, 8, 6, 1, None, None, None, 0, 6) == _native.EINVAL
     header = (Path(__file__).resolve().parent.parent / "include" / "lutr.h").read_text()
     assert "int lutr_apply_yuv_premul(" in header and "int lutr_apply_planar_rgb_f32_premul(" in header
+
+
+def test_premultiplied_alpha_source_refusals_keep_their_words():
+    """The alpha plane beside the colour planes of a premultiplied call: on the engine's device and with the colour planes'
+    number of frames, for the YUV pass and the float pass alike (host only: an engine object without a context)."""
+    import torch
+    from lut_renderer_amd.engine import LutEngine
+    eng = object.__new__(LutEngine)
+    eng.device = torch.device("cpu")
+    h, w = 6, 8
+
+    def planes(dtype, alpha, n=4):
+        return [torch.zeros((2, h, w), dtype=dtype) for _ in range(3)] + [alpha][:n - 3]
+
+    for call, dtype, kw in ((eng.apply_yuv, torch.int16, dict(pix_fmt="yuva444p10le")), (eng.apply_rgb_float, torch.float32, {})):
+        with pytest.raises(ValueError, match="^the alpha plane is on meta, engine is on cpu$"):
+            call(planes(dtype, torch.zeros((2, h, w), dtype=dtype, device="meta")), planes(dtype, torch.zeros((2, h, w), dtype=dtype)),
+                 alpha_mode="premultiplied", **kw)
+        with pytest.raises(ValueError, match="^planes disagree on the number of frames$"):
+            call(planes(dtype, torch.zeros((h, w), dtype=dtype)), planes(dtype, torch.zeros((2, h, w), dtype=dtype)),
+                 alpha_mode="premultiplied", **kw)

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """tools/record_container_options.py [OUT.json]: records what the option checks of the YUV containers do (CPU only, no GPU).
 
-For every ordered pair of NAMES, crossed with dither x chroma_loc x out_size, what `engine.check_semi_options` and
-`engine.check_packed_options` return or raise; for every pair (and a source without an out_pix_fmt), what
+For every ordered pair of NAMES, crossed with dither x chroma_loc x out_size, what `formats.check_semi_options` and
+`formats.check_packed_options` return or raise; for every pair (and a source without an out_pix_fmt), what
 `api.engine_call_for` returns or raises with a default plan and with a full-range plan; and, for every semi-planar and packed
 name plus yuv420p / yuv422p10le at 7x5 and 8x6, `frame_bytes` and the shapes, strides and storage offsets of `plane_views`
 over 2 frames of the stream layout.  tests/test_container_options.py replays all of it against the checked-in recording
