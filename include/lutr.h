@@ -582,6 +582,58 @@ int lutr_apply_yuv_dual(lutr_ctx *ctx, const lutr_yuv_params *p, int fmt_out2, i
 int lutr_apply_yuv_chain(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int interp2, int w, int h, int nframes,
                          const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
 
+/* ---- ASC CDL in front of lut3d: the per-clip colour decision (slope, offset, power, saturation; ASC CDL v1.2,
+ *      the numbers of a .cc / .ccc / .cdl file) on the log image ahead of the shared show LUT, in one pass.  An engine setting:
+ *      ffmpeg has no CDL filter. ---- */
+typedef struct lutr_cdl {
+    float slope[3], offset[3], power[3];   /* R, G, B; identity 1, 0, 1 */
+    float saturation;                      /* identity 1 */
+} lutr_cdl;
+
+/* Host only, no context and no device: stage A of lutr_apply_yuv_cdl for one channel (0 = R, 1 = G, 2 = B) at `depth` bits
+ * (8..16), 2^depth floats into `out`.  With M = 2^depth - 1, for every integer code k = 0 .. M, in double:
+ *   x = (double)((float)k * (float)(1 / M))        the float lut3d forms from a code (lutr_apply_planar_rgb)
+ *   t = clamp(x * slope + offset, 0, 1)            the product is exact in double, the sum is rounded once
+ *   out[k] = (float)(power == 1 ? t : pow(t, power))
+ * The identity CDL gives out[k] = (float)k * (float)(1 / M).  LUTR_EINVAL with a message: a null argument, a depth outside 8..16, a
+ * channel outside 0..2, or a CDL lutr_apply_yuv_cdl refuses. */
+int lutr_cdl_table(const lutr_cdl *cdl, int depth, int channel, float *out);
+
+/* lutr_apply_yuv_xsub's pass (planar YUV in and out, any pair of 4:2:0 / 4:2:2 / 4:4:4, the equal pairs included, 8..16 bit on
+ * either side) with the CDL between its YUV -> RGB stage and lut3d.  Per luma position, M = 2^lut_depth - 1:
+ *   q   = YUV -> integer RGB (lutr_apply_yuv's stage 1, the full-range prologue included; chroma replicated over its INPUT block)
+ *   T_c = lutr_cdl_table(cdl, lut_depth, c)[q_c]: slope, offset, clamp and power, tabulated per code on the host (the device
+ *         never calls pow)
+ *   o_c = med3(l + sat * (T_c - l), 0, 1) with l = (0.2126f * T_R + 0.7152f * T_G) + 0.0722f * T_B: fp32, every product and sum
+ *         rounded on its own; skipped when sat == 1 (o_c = T_c)
+ *   v   = lut3d on o: s_c = med3(o_c * scale_c * (n - 1), 0, n - 1), `interp` (all five modes), clip((int)(v * M), 0, M)
+ *   out = integer RGB -> YUV from v (lutr_apply_yuv_xsub's stage 3: chroma = the mean over its OUTPUT block, a partial block at an
+ *         odd edge takes the edge column / row again; constants: lutr_yuv_constants_xsub)
+ * The identity CDL (1, 0, 1, saturation 1) gives lutr_apply_yuv_xsub's bits; saturation 0 feeds the lattice R = G = B; slope 0
+ * feeds it the constant clamp(offset)^power.
+ * The device table is kept in the context under (slope, offset, power, lut_depth) and rebuilt when they change: the upload is
+ * ordered on the context's stream behind the kernels that still read the old table and returns once the host copy is consumed.
+ * row0 and rows must be multiples of the union block height 2^max(icsy, ocsy) unless row0 + rows == h.
+ * Always strict precision (fast / fma32 run strict here, no suffix on the last kernel).
+ * Not in place: the bounding byte ranges (all rows and frames) of the source planes and of the destination planes must be
+ * disjoint (the rule of lutr_apply_yuv_sited).
+ * LUTR_EINVAL with a message, before anything touches the device: no lattice, a null argument or plane, a CDL with a number that is
+ * not finite, a negative slope, a power that is not above 0 or a negative saturation, a .csp prelut on the context (its folded
+ * table is per code, and the CDL's output is not a code), the format errors of lutr_apply_yuv_xsub (4:4:0, a depth outside
+ * 8..16), 16-bit planes whose base, stride or (batches) frame stride is odd, row0 / rows off the union block, any overlap, variant
+ * vec_lds (there is no LDS kernel for this path).  Variant vec_global where the vector kernel cannot take the call is LUTR_EINVAL
+ * too, found where the kernel is chosen, as in the sibling entry points: the table may have been uploaded by then, no kernel has
+ * run and nothing is written.
+ * Kernels: "k_yuv_cdl_vec<win,wout,icsx,icsy,ocsx,ocsy,interp>" (nearest / trilinear / tetrahedral; the container mixes 8 -> 8,
+ * 16 -> 16 and 16 -> 8 bit; width a multiple of 8 luma samples, 4 for 16 -> 16; positive strides aligned to the accesses; row0 /
+ * rows multiples of the union block height), "k_yuv_cdl_generic" for everything else (one thread per union block; any depth,
+ * stride, alignment or size; all five modes; an 8-bit source with a 16-bit output); a ragged width on aligned rows is split
+ * between the two and named "<vector kernel>+k_yuv_cdl_generic".
+ * Not covered: a prelut, dither, chroma siting, a resize, the two-output pass, the two-LUT chain, premultiplied alpha, RGB / float
+ * / semi-planar / packed / v210 sides, a tile (LDS) kernel. */
+int lutr_apply_yuv_cdl(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, const lutr_cdl *cdl, int w, int h, int nframes,
+                       const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
+
 /* ---- the alpha plane of yuva* / gbrap* frames: ProRes 4444 (yuva444p10le / 12le), VP8 / VP9 with alpha
  *      (yuva420p), PNG / TIFF / EXR sequences with alpha (rgba, rgba64le, gbrap*, gbrapf32le).  In the reference's chain lut3d
  *      copies the alpha plane through and format=<pix_fmt> keeps, converts, drops or makes it (ffmpeg.py:246, :304-310) ---- */

@@ -42,7 +42,7 @@ SYMBOLS = (
     "lutr_apply_rgb_to_yuv", "lutr_yuv_constants_rgb2yuv",
     "lutr_apply_planar_rgb_f32", "lutr_apply_rgbf_to_yuv", "lutr_apply_yuv_semi", "lutr_apply_yuv_packed",
     "lutr_apply_yuv_dual", "lutr_apply_yuv_v210", "lutr_alpha_plane", "lutr_ctx_set_lut2", "lutr_apply_yuv_chain",
-    "lutr_apply_yuv_premul", "lutr_apply_planar_rgb_f32_premul",
+    "lutr_apply_yuv_premul", "lutr_apply_planar_rgb_f32_premul", "lutr_cdl_table", "lutr_apply_yuv_cdl",
     "lutr_resize_filter", "lutr_resize_planes", "lutr_dither_mask",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
     "lutr_max_waves_knob",
@@ -84,6 +84,20 @@ class AlphaSrc(C.Structure):
     """struct lutr_alpha_src: where the alpha samples of lutr_alpha_plane's source are"""
     _fields_ = [("kind", C.c_int32), ("depth", C.c_int32), ("data", C.c_void_p), ("stride", C.c_ssize_t),
                 ("frame_stride", C.c_int64), ("step", C.c_int32), ("offset", C.c_int32)]
+
+
+class CdlStruct(C.Structure):
+    """struct lutr_cdl: an ASC CDL"""
+    _fields_ = [("slope", C.c_float * 3), ("offset", C.c_float * 3), ("power", C.c_float * 3), ("saturation", C.c_float)]
+
+
+def cdl_struct(cdl) -> CdlStruct:
+    """struct lutr_cdl from a `cdl.Cdl` (its numbers rounded to float32, as the C-ABI carries them)."""
+    st = CdlStruct()
+    for i in range(3):
+        st.slope[i], st.offset[i], st.power[i] = cdl.slope[i], cdl.offset[i], cdl.power[i]
+    st.saturation = cdl.saturation
+    return st
 
 
 #: enum lutr_alpha_kind
@@ -210,6 +224,9 @@ def load() -> C.CDLL:
                                           C.POINTER(Planes), ci, ci]
     lib.lutr_apply_planar_rgb_f32_premul.argtypes = [vp, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(AlphaSrc), C.POINTER(Planes),
                                                      ci, ci]
+    lib.lutr_cdl_table.argtypes = [C.POINTER(CdlStruct), ci, ci, C.POINTER(C.c_float)]
+    lib.lutr_apply_yuv_cdl.argtypes = [vp, C.POINTER(YuvParams), ci, C.POINTER(CdlStruct), ci, ci, ci, C.POINTER(Planes),
+                                       C.POINTER(Planes), ci, ci]
     lib.lutr_dither_mask.argtypes = [C.POINTER(C.c_uint16)]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]
@@ -230,6 +247,17 @@ def dither_mask():
     rank = np.zeros((64, 64), np.uint16)
     check(load().lutr_dither_mask(rank.ctypes.data_as(C.POINTER(C.c_uint16))))
     return rank
+
+
+def cdl_table(cdl, depth: int):
+    """lutr_cdl_table (host only): stage A of the CDL pass for the three channels, float32 [3, 2^depth] -- the
+    value of every integer code after slope, offset, clamp and power."""
+    import numpy as np
+    st = cdl_struct(cdl)
+    out = np.zeros((3, 1 << int(depth)), np.float32)
+    for ch in range(3):
+        check(load().lutr_cdl_table(C.byref(st), int(depth), ch, out[ch].ctypes.data_as(C.POINTER(C.c_float))))
+    return out
 
 
 def max_waves_knob(text, waves_per_block: int, uncapped: int) -> int:

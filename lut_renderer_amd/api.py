@@ -21,11 +21,12 @@ import threading
 from pathlib import Path
 from typing import Dict, Optional, Sequence, Tuple
 
+from .cdl import as_cdl
 from .cube import CubeLut, read_cube, read_lut
-from .formats import (check_alpha_mode, check_chain_options, check_chroma_loc, check_container_options, check_dual_options,
-                      check_lut2, check_premul_options, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt, parse_rgb_source,
-                      parse_semi_fmt, parse_size, parse_v210_fmt, premul_to_yuv, refuse_alpha_resize, source_bit_depth,
-                      v210_frame_width, yuv_side)
+from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc, check_container_options,
+                      check_dual_options, check_lut2, check_premul_options, packed_frame_width, parse_packed_yuv_fmt,
+                      parse_pix_fmt, parse_rgb_source, parse_semi_fmt, parse_size, parse_v210_fmt, premul_to_yuv,
+                      refuse_alpha_resize, source_bit_depth, v210_frame_width, yuv_side)
 from .params import ProcessingParams, VideoInfo
 from .plan import LutPlan, output_color_tags, resolve_lut_plan
 
@@ -213,7 +214,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               zscale_dither: str = "none", out: Optional[Sequence] = None, engine=None,
               devices: Sequence[int] = (0,), precision: str = "strict", chroma_loc: Optional[str] = None,
               resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
-              cube2=None, interp2: Optional[str] = None, alpha_mode: str = "straight"):
+              cube2=None, interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None, cdl_id: Optional[str] = None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -277,7 +278,14 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     `cube2` (a path or a parsed CubeLut) applies a SECOND LUT behind the first in the same pass (ffmpeg's
     `lut3d=file=A,lut3d=file=B`: a technical LUT, then a look): the frame stays integer RGB at the LUT depth between the two and
     is converted to YUV once.  `interp2` is the second LUT's mode (None = `interp`).  Planar YUV without alpha on both sides; the
-    second LUT carries no prelut; no dither, chroma_loc, resolution or second output.  `interp2` without `cube2` is a ValueError."""
+    second LUT carries no prelut; no dither, chroma_loc, resolution or second output.  `interp2` without `cube2` is a ValueError.
+
+    `cdl` (a `cdl.Cdl`, or the path of a .cc / .ccc / .cdl file with `cdl_id` naming the correction in it) applies an ASC CDL --
+    slope, offset, power per channel, then saturation -- to the integer RGB ahead of `cube`, in the same pass (DESIGN.md 3.19:
+    the per-clip colour decision in front of the show LUT).  Planar YUV on both sides (yuva* with straight alpha included), a
+    LutEngineGroup row-shards it, always strict arithmetic; the identity CDL gives the bits of the call without it.  No LUT with
+    a .csp prelut, dither, chroma_loc, resolution, second output, second LUT, premultiplied alpha, RGB / float / semi-planar /
+    packed / v210 side: each is a ValueError naming it."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -325,6 +333,16 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         check_premul_options(kw["pix_fmt"], kw["out_pix_fmt"], dither=kw["dither"], chroma_loc=chroma_loc, out_size=out_size,
                              range_src=kw.get("range_src", "tv"), range_in=kw.get("range_in"), lut_depth=kw.get("lut_depth"),
                              out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None)
+    if cdl is None and cdl_id is not None:
+        raise ValueError("cdl_id names a correction inside a CDL file: it needs cdl")
+    if cdl is not None:
+        cdl = as_cdl(cdl, cdl_id)
+        # (a parsed LUT tells whether it carries a prelut; an engine that already holds the lattice knows it of its own)
+        held = cube if isinstance(cube, CubeLut) else _cached_cube(Path(cube)) if cube is not None else None
+        prelut = getattr(held, "prelut", None) is not None if held is not None else bool(getattr(engine, "_has_prelut", False))
+        check_cdl_options(kw["pix_fmt"], kw["out_pix_fmt"], dither=kw["dither"], chroma_loc=chroma_loc, out_size=out_size,
+                          alpha_mode=alpha_mode, out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None, prelut=prelut)
+        kw["cdl"] = cdl
     if cube2 is not None:
         kw = chain_call_for(kw, interp2, chroma_loc, out_size, second_pix_fmt)
     elif second_pix_fmt is not None:

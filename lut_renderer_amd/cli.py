@@ -20,8 +20,8 @@ import signal
 import sys
 import time
 
-from .formats import (check_chroma_loc, check_container_options, check_lut2, check_premul_options, parse_size, refuse_alpha_resize,
-                      source_bit_depth)
+from .formats import (check_cdl_options, check_chroma_loc, check_container_options, check_lut2, check_premul_options, parse_size,
+                      refuse_alpha_resize, source_bit_depth)
 
 
 def _hms(seconds: float) -> str:
@@ -85,12 +85,35 @@ def build_parser() -> argparse.ArgumentParser:
                          "lut3d=A,lut3d=B): planar YUV without alpha on both sides, no prelut on this LUT, no dither, "
                          "--chroma-loc, --out-size or --second-output")
     ap.add_argument("--interp2", default=None, metavar="MODE", help="interpolation mode of --cube2 (default: --interp)")
+    ap.add_argument("--cdl", default=None, metavar="FILE",
+                    help="engine setting: an ASC CDL (.cc / .ccc / .cdl) applied to the RGB ahead of --cube in the same pass "
+                         "(DESIGN.md 3.19): planar YUV on both sides, no .csp prelut, dither, --chroma-loc, --out-size, "
+                         "--second-output, --cube2 or --alpha-mode premultiplied")
+    ap.add_argument("--cdl-id", default=None, metavar="ID", help="the id of the ColorCorrection to take from --cdl")
+    ap.add_argument("--cdl-sop", default=None, metavar="\"S S S O O O P P P\"",
+                    help="the CDL as literal values instead of a file: slope R G B, offset R G B, power R G B")
+    ap.add_argument("--cdl-sat", default=None, type=float, metavar="X", help="the CDL's saturation as a literal value (default 1)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("-y", action="store_true", help="overwrite the output (ffmpeg's -y)")
     ap.add_argument("--duration", type=float, default=None,
                     help="seconds of video, for the Duration: line when the input is a pipe (-i -) and cannot be measured")
     return ap
+
+
+def cdl_from_args(args):
+    """The `cdl.Cdl` the options name, or None: --cdl FILE [--cdl-id ID], or --cdl-sop / --cdl-sat; a file and literal values
+    together are an error."""
+    path, cc_id = getattr(args, "cdl", None), getattr(args, "cdl_id", None)
+    sop, sat = getattr(args, "cdl_sop", None), getattr(args, "cdl_sat", None)
+    if path is not None and (sop is not None or sat is not None):
+        raise ValueError("--cdl names a file and --cdl-sop / --cdl-sat give literal values: use one or the other")
+    if cc_id is not None and path is None:
+        raise ValueError("--cdl-id names a correction inside a CDL file: it needs --cdl")
+    if path is None and sop is None and sat is None:
+        return None
+    from .cdl import Cdl, read_cdl
+    return read_cdl(path, cc_id) if path is not None else Cdl.from_sop_text(sop, sat)
 
 
 def plan_from_args(args):
@@ -114,6 +137,22 @@ def plan_from_args(args):
                              out_size=getattr(args, "out_size", None), range_src=kw.get("range_src", "tv"),
                              range_in=kw.get("range_in"), lut_depth=kw.get("lut_depth"),
                              out2_pix_fmt=getattr(args, "second_pix_fmt", None), lut2=getattr(args, "cube2", None) is not None)
+    cdl = cdl_from_args(args)
+    if cdl is not None:
+        prelut = False
+        if os.path.isfile(args.cube):                         # (a LUT that is not there yet is met again where it is loaded)
+            from pathlib import Path
+            # torch first, as everywhere else: parsing loads liblutr, which must find the HIP runtime torch brings and not load
+            # a second one into the process (the second cannot open the device)
+            from . import engine  # noqa: F401
+            from .api import _cached_cube
+            prelut = getattr(_cached_cube(Path(args.cube)), "prelut", None) is not None
+        check_cdl_options(kw["pix_fmt"], kw["out_pix_fmt"], chroma_loc=getattr(args, "chroma_loc", None),
+                          dither="error_diffusion" if args.zscale_dither == "error_diffusion" else engine_dither or "none",
+                          out_size=getattr(args, "out_size", None), alpha_mode=alpha_mode,
+                          out2_pix_fmt=getattr(args, "second_pix_fmt", None), lut2=getattr(args, "cube2", None) is not None,
+                          prelut=prelut)
+        kw["cdl"] = cdl
     if is_float_out_call(kw) and (args.zscale_dither == "error_diffusion" or engine_dither or getattr(args, "out_size", None)):
         raise ValueError("a float output takes no dither and no --out-size")
     if args.zscale_dither == "error_diffusion":

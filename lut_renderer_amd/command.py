@@ -19,8 +19,8 @@ from dataclasses import dataclass, field
 from pathlib import Path
 from typing import List, Optional, Tuple
 
-from .formats import (check_alpha_mode, check_chain_options, check_dual_options, check_premul_options, parse_rgb_source,
-                      premul_to_yuv)
+from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options, check_premul_options,
+                      parse_rgb_source, premul_to_yuv)
 from .params import ProcessingParams, Task, VideoInfo
 from .plan import LutPlan, output_color_tags, resolve_lut_plan, resolve_pix_fmt
 
@@ -255,7 +255,8 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                    notes: Optional[List[str]] = None, precision: str = "strict", chroma_loc: Optional[str] = None,
                    gpu_resize: bool = False, second_output: Optional[Path] = None,
                    second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
-                   cube2: Optional[Path] = None, interp2: Optional[str] = None, alpha_mode: str = "straight") -> List[str]:
+                   cube2: Optional[Path] = None, interp2: Optional[str] = None, alpha_mode: str = "straight",
+                   cdl=None, cdl_id: Optional[str] = None) -> List[str]:
     """`build_command`'s twin for the LUT stage alone: the argv of the ENGINE CLI (`python -m lut_renderer_amd.cli`)
     that applies exactly the chain `build_command` would put into `-vf` -- the same `LutPlan`, rendered as CLI options
     instead of as a filter string (ffmpeg.py:195-247, :287-310).  `source` / `output` are rawvideo files (or `-`) in
@@ -276,7 +277,11 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     not with dither, `chroma_loc`, `gpu_resize` or a second output.
     `alpha_mode` ("premultiplied") is an engine setting too (`--alpha-mode`, rendered only when premultiplied:
     "straight" keeps the argv as it was): a yuva* source with a planar YUV output or gbrapf32le kept float; not with a full-range
-    prologue, dither, `chroma_loc`, `gpu_resize`, a second output or a second LUT.  ffmpeg's chain has no such step."""
+    prologue, dither, `chroma_loc`, `gpu_resize`, a second output or a second LUT.  ffmpeg's chain has no such step.
+    `cdl` puts an ASC CDL in front of the LUT in the same pass, an engine setting as well: the path of a .cc / .ccc
+    / .cdl file (`--cdl`, with `cdl_id` as `--cdl-id`) or a `cdl.Cdl` (`--cdl-sop`, and `--cdl-sat` unless it is 1); rendered only
+    when given.  Planar YUV on both sides; not with dither, `chroma_loc`, `gpu_resize`, a second output, a second LUT or
+    premultiplied alpha.  A LUT with a .csp prelut is refused where the LUT is loaded."""
     import sys as _sys
     premul = check_alpha_mode(alpha_mode)
     if precision not in ("strict", "fast", "fma32"):
@@ -372,6 +377,25 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                              lut_depth=8 if plan.prologue else None, out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None,
                              to_yuv=premul_to_yuv(src_fmt, pix_fmt or None))
         cmd += ["--alpha-mode", "premultiplied"]
+    if cdl is None and cdl_id is not None:
+        raise ValueError("cdl_id names a correction inside a CDL file: it needs cdl")
+    if cdl is not None:
+        from .cdl import Cdl
+        check_cdl_options(str(source_info.pix_fmt).replace("yuvj", "yuv"), pix_fmt or None, dither=dither, chroma_loc=chroma_loc,
+                          out_size=params.resolution if "--out-size" in cmd else None, alpha_mode=alpha_mode,
+                          out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None)
+        if isinstance(cdl, Cdl):
+            if cdl_id is not None:
+                raise ValueError("cdl_id names a correction inside a CDL file, and cdl is a set of values")
+            cmd += ["--cdl-sop", cdl.sop_text()]
+            if cdl.saturation != 1.0:
+                cmd += ["--cdl-sat", repr(cdl.saturation)]
+        elif isinstance(cdl, (str, Path)):
+            cmd += ["--cdl", str(cdl)]
+            if cdl_id is not None:
+                cmd += ["--cdl-id", str(cdl_id)]
+        else:
+            raise TypeError(f"cdl must be a Cdl or the path of a .cc / .ccc / .cdl file, not {type(cdl).__name__}")
     return cmd
 
 

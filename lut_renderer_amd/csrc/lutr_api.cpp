@@ -332,6 +332,13 @@ struct lutr_ctx {
     size_t lat2_bytes = 0;
     int n2 = 0;
     float scale2[3] = {1.f, 1.f, 1.f};
+    // the ASC CDL's per-code table (lutr_apply_yuv_cdl): 3 x 2^cdl_depth floats on the device, built for the slope,
+    // offset and power in cdl_key; cdl_depth 0: nothing valid is there.  Per-clip use replaces it while the previous call's kernel
+    // may still read it: see cdl_device_table
+    float *cdl_tab = nullptr;
+    size_t cdl_cap = 0;              // floats allocated
+    int cdl_depth = 0;
+    float cdl_key[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 // Wait for every peer copy that reads this context's lattice, then forget the events.
@@ -478,6 +485,7 @@ void lutr_ctx_destroy(lutr_ctx *c)
     if (c->stats) (void)hipFree(c->stats);
     if (c->fscratch) (void)hipFree(c->fscratch);
     if (c->bn_tab) (void)hipFree(c->bn_tab);
+    if (c->cdl_tab) (void)hipFree(c->cdl_tab);
     for (auto &t : c->rz_tables) (void)hipFree(t.dev);
     if (c->queue) (void)hipFree(c->queue);
     if (c->done) (void)hipEventDestroy(c->done);
@@ -1370,6 +1378,127 @@ int lutr_apply_yuv_chain(lutr_ctx *c, const lutr_yuv_params *p, int interp, int 
     for (int i = 0; i < 3; i++) L2.sc[i] = c->scale2[i] * L2.lut_max;
     fill_planes(&P, src, dst);
     return finish_launch(c, launch_yuv_chain(c->stream, c->variant, L, L2, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, interp, interp2));
+}
+
+// ---- ASC CDL in front of lut3d
+// what both entry points refuse in a CDL: a number that is not finite, a negative slope or saturation, a power that is not above 0
+static int check_cdl(const lutr_cdl *d)
+{
+    static const char *const ch[3] = {"R", "G", "B"};
+    for (int i = 0; i < 3; i++) {
+        if (!std::isfinite(d->slope[i]) || !std::isfinite(d->offset[i]) || !std::isfinite(d->power[i])) {
+            set_error("CDL: slope, offset or power of %s is not finite (%g, %g, %g)", ch[i], (double)d->slope[i], (double)d->offset[i],
+                      (double)d->power[i]);
+            return LUTR_EINVAL;
+        }
+        if (d->slope[i] < 0.0f) { set_error("CDL: slope of %s is negative (%g)", ch[i], (double)d->slope[i]); return LUTR_EINVAL; }
+        if (!(d->power[i] > 0.0f)) { set_error("CDL: power of %s must be above 0 (%g)", ch[i], (double)d->power[i]); return LUTR_EINVAL; }
+    }
+    if (!std::isfinite(d->saturation)) { set_error("CDL: saturation is not finite (%g)", (double)d->saturation); return LUTR_EINVAL; }
+    if (d->saturation < 0.0f) { set_error("CDL: saturation is negative (%g)", (double)d->saturation); return LUTR_EINVAL; }
+    return LUTR_OK;
+}
+
+// Stage A for one channel, codes 0 .. 2^depth - 1 (the entry past M of a depth below 16 does not exist: 2^depth - 1 = M).  In
+// double: the product of two floats is exact there, the sum is rounded once.
+static void cdl_channel_table(const lutr_cdl &d, int depth, int ch, float *out)
+{
+    const int maxi = (1 << depth) - 1;
+    const float scale_f = 1.0f / (float)maxi;
+    const double slope = d.slope[ch], offset = d.offset[ch], power = d.power[ch];
+    for (int k = 0; k <= maxi; k++) {
+        const double x = (double)((float)k * scale_f);
+        const double v = x * slope + offset;
+        const double t = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
+        out[k] = (float)(power == 1.0 ? t : std::pow(t, power));
+    }
+}
+
+// The device table of (slope, offset, power) at `depth`, rebuilt when that key changes.  The kernel of the previous call may
+// still be reading the old contents, so the copy goes on the context's stream, behind it; hipMemcpyWithStream returns when the
+// copy is done, so the host table (a local) is never rewritten or freed under a pending copy.
+static int cdl_device_table(lutr_ctx *c, const lutr_cdl &d, int depth, CdlConsts *C)
+{
+    const size_t ne = (size_t)1 << depth, n = 3 * ne;
+    float key[9];
+    std::memcpy(key, d.slope, sizeof(key));          // slope, offset, power: the first nine floats of lutr_cdl
+    if (!c->cdl_tab || c->cdl_depth != depth || std::memcmp(key, c->cdl_key, sizeof(key)) != 0) {
+        c->cdl_depth = 0;
+        if (c->cdl_cap < n) {
+            void *p = nullptr;
+            const hipError_t e = hipMalloc(&p, n * sizeof(float));
+            if (e != hipSuccess) { set_error("hipMalloc(CDL table): %s", hipGetErrorString(e)); return LUTR_ENOMEM; }
+            if (c->cdl_tab) {
+                HIP_TRY(hipStreamSynchronize(c->stream));    // a launch may still be reading the smaller table
+                (void)hipFree(c->cdl_tab);
+            }
+            c->cdl_tab = (float *)p;
+            c->cdl_cap = n;
+        }
+        std::vector<float> host(n);
+        for (int ch = 0; ch < 3; ch++) cdl_channel_table(d, depth, ch, &host[(size_t)ch * ne]);
+        HIP_TRY(hipMemcpyWithStream(c->cdl_tab, host.data(), n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        std::memcpy(c->cdl_key, key, sizeof(key));
+        c->cdl_depth = depth;
+    }
+    C->tab = c->cdl_tab;
+    C->stride = (int)ne;
+    C->sat = d.saturation;
+    return LUTR_OK;
+}
+
+int lutr_cdl_table(const lutr_cdl *cdl, int depth, int channel, float *out)
+{
+    if (!cdl || !out) { set_error("lutr_cdl_table: null argument"); return LUTR_EINVAL; }
+    if (depth < 8 || depth > 16) { set_error("lutr_cdl_table: depth %d outside 8..16", depth); return LUTR_EINVAL; }
+    if (channel < 0 || channel > 2) { set_error("lutr_cdl_table: channel %d outside 0..2", channel); return LUTR_EINVAL; }
+    if (const int rc = check_cdl(cdl)) return rc;
+    cdl_channel_table(*cdl, depth, channel, out);
+    return LUTR_OK;
+}
+
+// lutr_apply_yuv_xsub's pass for any pair of layouts with the CDL between its first stage and the lattice.
+int lutr_apply_yuv_cdl(lutr_ctx *c, const lutr_yuv_params *p, int interp, const lutr_cdl *cdl, int w, int h, int nframes,
+                       const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+{
+    int rc = check_common(c, interp, LUTR_INTERP_NEAREST, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!cdl) { set_error("null CDL"); return LUTR_EINVAL; }
+    if (const int rc = check_cdl(cdl)) return rc;
+    if (c->pre_size) {
+        set_error("CDL: the LUT has a .csp prelut; its table is indexed by integer codes, and the CDL's output is not a code");
+        return LUTR_EINVAL;
+    }
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    YuvConsts K;
+    rc = make_yuv_consts_xsub(*p, &K);
+    if (rc) return rc;
+    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
+    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
+    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
+    if (p->lut_depth < 8 || p->lut_depth > 16) { set_error("CDL: LUT depth %d outside 8..16", p->lut_depth); return LUTR_EINVAL; }
+    if (const int rc = check_row_blocks(row0, rows, h, 1 << std::max(icsy, ocsy), "union chroma block height")) return rc;
+    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for the CDL pass"); return LUTR_EINVAL; }
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    if (const int rc = check_planes_set(src, dst)) return rc;
+    const struct { const char *side; const lutr_planes *pl; int depth; } sides[2] = {{"source", src, din}, {"destination", dst, dout}};
+    for (const auto &s : sides)
+        for (int i = 0; i < 3; i++)
+            if (s.depth > 8 && !check_aligned(s.pl->data[i], s.pl->stride[i], s.pl->frame_stride[i], nframes, 1)) {
+                set_error("%s plane %d: 16-bit planes need 2-byte aligned rows", s.side, i);
+                return LUTR_EINVAL;
+            }
+    Span ss[3], ds[3];
+    planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
+    planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
+    if (const int rc = check_disjoint("the CDL pass", true, ss, 3, ds, 3)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
+    LutConsts L; CdlConsts C; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
+    if (const int rc = cdl_device_table(c, *cdl, p->lut_depth, &C)) return rc;
+    fill_planes(&P, src, dst);
+    return finish_launch(c, launch_yuv_cdl(c->stream, c->variant, L, C, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, interp));
 }
 
 // What a semi-planar and a packed side share: `noun` ("layout" | "packing") names the struct in the messages; the shift against

@@ -202,6 +202,53 @@ __device__ __forceinline__ Rgb lut3d_px_rt(int mode, const LutConsts &L, const F
     }
 }
 
+// lut3d_px from its scale step on, for a pixel that arrives as unit floats instead of integer codes (the ASC CDL's output,
+// DESIGN.md 3.19): clip of the coordinates, blend, truncation toward zero and clip to [0, M] as above.  No prelut: a per-code
+// table has nothing to index with.
+template <int INTERP, class F>
+__device__ __forceinline__ Rgb lut3d_unit(const LutConsts &L, const F &f, const Rgb &x)
+{
+    const float sr = med3(x.r * L.sc[0], 0.0f, L.lut_max);
+    const float sg = med3(x.g * L.sc[1], 0.0f, L.lut_max);
+    const float sb = med3(x.b * L.sc[2], 0.0f, L.lut_max);
+    const Rgb v = interp<INTERP>(f, sr, sg, sb);
+    Rgb o;
+    o.r = med3(truncf(v.r * L.maxf), 0.0f, L.maxf);
+    o.g = med3(truncf(v.g * L.maxf), 0.0f, L.maxf);
+    o.b = med3(truncf(v.b * L.maxf), 0.0f, L.maxf);
+    return o;
+}
+
+template <class F>
+__device__ __forceinline__ Rgb lut3d_unit_rt(int mode, const LutConsts &L, const F &f, const Rgb &x)
+{
+    switch (mode) {
+    case LUTR_INTERP_NEAREST:   return lut3d_unit<LUTR_INTERP_NEAREST>(L, f, x);
+    case LUTR_INTERP_TRILINEAR: return lut3d_unit<LUTR_INTERP_TRILINEAR>(L, f, x);
+    case LUTR_INTERP_PYRAMID:   return lut3d_unit<LUTR_INTERP_PYRAMID>(L, f, x);
+    case LUTR_INTERP_PRISM:     return lut3d_unit<LUTR_INTERP_PRISM>(L, f, x);
+    default:                    return lut3d_unit<LUTR_INTERP_TETRAHEDRAL>(L, f, x);
+    }
+}
+
+// Stages A and B of the ASC CDL on one pixel of integer codes held as floats: the host's per-code table of
+// clamp(x * slope + offset)^power per channel, then the saturation mix around Rec.709 luma -- every product and sum rounded on
+// its own (this code is compiled without contraction).  mix = (C.sat != 1), decided once per kernel.
+__device__ __forceinline__ Rgb cdl_px(const CdlConsts &C, bool mix, const Rgb &q)
+{
+    Rgb t;
+    t.r = C.tab[(int)q.r];
+    t.g = C.tab[C.stride + (int)q.g];
+    t.b = C.tab[2 * C.stride + (int)q.b];
+    if (mix) {
+        const float l = (0.2126f * t.r + 0.7152f * t.g) + 0.0722f * t.b;
+        t.r = med3(l + C.sat * (t.r - l), 0.0f, 1.0f);
+        t.g = med3(l + C.sat * (t.g - l), 0.0f, 1.0f);
+        t.b = med3(l + C.sat * (t.b - l), 0.0f, 1.0f);
+    }
+    return t;
+}
+
 // ---------------------------------------------------------------- YUV contract pieces
 struct Chroma { float rv, gv, bu; };
 

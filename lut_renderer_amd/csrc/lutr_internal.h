@@ -145,6 +145,25 @@ const char *launch_yuv_chain(hipStream_t st, int variant, const LutConsts &L, co
 LUTR_CH_DECL(w00) LUTR_CH_DECL(w11) LUTR_CH_DECL(w10)
 #undef LUTR_CH_DECL
 
+// ASC CDL in front of lut3d (lutr_cdl.hip): the per-code table of slope, offset, clamp and power (device; the
+// value of integer code i of channel c is tab[c * stride + i], stride = 2^lut_depth) and the saturation
+struct CdlConsts {
+    const float *tab;
+    int   stride;
+    float sat;
+};
+// launch_yuv_xsub's call for any pair of layouts, the equal ones included, with the CDL between the YUV -> RGB stage and the
+// lattice (L.pre is not read).  nullptr = the variant cannot take the call (vec_lds always; vec_global on layouts the vector
+// kernel cannot take)
+const char *launch_yuv_cdl(hipStream_t st, int variant, const LutConsts &L, const CdlConsts &C, const YuvConsts &K, const PlaneSet &P,
+                           const FrameGeom &G, int din, int dout, int icsx, int icsy, int ocsx, int ocsy, int interp);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>): nullptr = not a mode it has
+#define LUTR_CD_DECL(tag) \
+    const char *launch_yuv_cdl_vec_##tag(hipStream_t st, const LutConsts &L, const CdlConsts &C, const YuvConsts &K, \
+                                         const PlaneSet &P, const FrameGeom &G, int icsx, int icsy, int ocsx, int ocsy, int interp);
+LUTR_CD_DECL(w00) LUTR_CD_DECL(w11) LUTR_CD_DECL(w10)
+#undef LUTR_CD_DECL
+
 // blue-noise dither in the output stage (lutr_bnd.hip): launch_yuv_xsub's call for any pair of layouts, the equal
 // ones included; bn = the 64 x 64 table of offsets (device).  nullptr = the variant cannot take the call (vec_lds always;
 // vec_global on layouts the vector kernel cannot take)

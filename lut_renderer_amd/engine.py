@@ -19,10 +19,12 @@ import numpy as np
 import torch
 
 from . import _native
+from .cdl import Cdl
 from .cube import CubeLut, read_cube, read_lut
 # (the formats and the checks of names and options live in formats.py; the names callers have always imported from here stay)
 from .formats import (_ALPHA_RESIZE, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, V210Fmt, chain_interp, chain_side,  # noqa: F401
-                      changes_subsampling, check_alpha_mode, check_chain_options, check_chroma_loc, check_container_options,
+                      changes_subsampling, check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc,
+                      check_container_options,
                       check_dual_options, check_lut2, check_packed_options, check_premul_options, check_semi_options,
                       chroma_loc_code, dual_side, has_prologue, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt,
                       parse_rgb_source, parse_semi_fmt, parse_size, parse_v210_fmt, refuse_alpha_resize, refuse_chain_keywords,
@@ -122,6 +124,7 @@ def _byte_range(t: torch.Tensor) -> Tuple[int, int]:
     return lo, hi + t.element_size()
 
 
+_CDL_IN_PLACE = "the CDL pass cannot run in place: destination planes must not overlap the source planes"
 _RESIZE_IN_PLACE = "a resize cannot run in place: destination planes must not overlap the source planes"
 _RGB2YUV_IN_PLACE = "RGB -> YUV cannot run in place: destination planes must not overlap the source"
 
@@ -332,6 +335,7 @@ class LutEngine:
         self._scratch_slots = {}
         # (raw name of the last alpha kernel, the joined name `last_kernel` reports for it) after an alpha-carrying call, else None
         self._alpha_kernels = None
+        self._has_prelut = False          # the lattice carries a .csp prelut (what a CDL in front of it refuses)
 
     # -- lifetime ---------------------------------------------------------
     def close(self) -> None:
@@ -365,6 +369,7 @@ class LutEngine:
     def set_prelut(self, pre) -> None:
         """lut3d's prelut (a cineSpace shaper, `cube.Prelut`) for the lattice just set, or None to remove it.  Uploading a
         lattice drops the prelut of the previous one."""
+        self._has_prelut = pre is not None
         if pre is None:
             _native.check(self._lib.lutr_ctx_set_prelut(self._ctx, None, 0, None, None))
             return
@@ -676,8 +681,14 @@ class LutEngine:
                   range_out: str = "tv", lut_depth: Optional[int] = None, out_pix_fmt: Optional[str] = None,
                   row0: int = 0, rows: Optional[int] = None, dither: str = "none", chroma_loc: Optional[str] = None,
                   out_size=None, resize_chunk: Optional[int] = None, width: Optional[int] = None,
-                  alpha_mode: str = "straight"):
+                  alpha_mode: str = "straight", cdl: Optional[Cdl] = None):
         """Fused YUV -> RGB -> lut3d -> RGB -> YUV on planar frames (Y, Cb, Cr).
+        `cdl` (a `cdl.Cdl`) applies an ASC CDL -- slope, offset, power per channel, then saturation -- to the
+        integer RGB ahead of lut3d, in the same pass (lutr_apply_yuv_cdl): planar YUV on both sides (yuva* with straight alpha
+        included), any layout pair at 8..16 bit, all five modes, the full-range prologue, row0 / rows on the union block, strict
+        arithmetic, not in place.  The identity CDL gives the bits of the call without it.  Not with a LUT that carries a .csp
+        prelut, dither, chroma_loc, out_size, alpha_mode="premultiplied" or a semi-planar / packed / v210 side.  None (the
+        default) is every path described here, unchanged.
         `pix_fmt` / `out_pix_fmt` may each name an alpha-carrying format (yuva420p .. yuva444p16le): that side is
         FOUR planes, the last one alpha at the luma size and the format's depth.  The colour planes are this call on the first three
         under the three-plane names, bit for bit, with every option below; alpha never meets the LUT -- it is copied, converted to
@@ -716,6 +727,11 @@ class LutEngine:
         if premul:
             check_premul_options(pix_fmt, out_pix_fmt, dither=dither, chroma_loc=chroma_loc, out_size=out_size, range_src=range_src,
                                  range_in=range_in, lut_depth=lut_depth)
+        if cdl is not None:
+            if not isinstance(cdl, Cdl):
+                raise TypeError(f"cdl must be a lut_renderer_amd.cdl.Cdl, not {type(cdl).__name__}")
+            check_cdl_options(pix_fmt, out_pix_fmt, dither=dither, chroma_loc=chroma_loc, out_size=out_size, alpha_mode=alpha_mode,
+                              prelut=bool(getattr(self, "_has_prelut", False)))
         kind = check_container_options(pix_fmt, out_pix_fmt, dither, chroma_loc, out_size, width=width)
         if kind is not None:
             return self._apply_yuv_container(kind, src, dst, yuv_side(pix_fmt), yuv_side(out_pix_fmt or pix_fmt), interp, matrix_in,
@@ -762,7 +778,7 @@ class LutEngine:
                                           matrix_in=matrix_in, matrix_out=matrix_out, range_src=range_src, range_in=range_in,
                                           range_out=range_out, lut_depth=lut_depth, out_pix_fmt=fout.colour.name, row0=row0,
                                           rows=rows, dither=dither, chroma_loc=chroma_loc, out_size=out_size,
-                                          resize_chunk=resize_chunk)
+                                          resize_chunk=resize_chunk, cdl=cdl)
             out = self._alpha_tail(colour, [(fout, dst)], a_src, fin.depth, w, h, row0, rows)
             return out if dst is None else dst
         check_chroma_loc(chroma_loc, dither, fin.name, fout.name)
@@ -783,9 +799,15 @@ class LutEngine:
         rows = h - row0 if rows is None else rows
         if dither == "error_diffusion" and (row0 != 0 or rows != h):
             raise ValueError("error-diffusion dither couples the rows of a frame: whole frames only")
+        if cdl is not None:
+            _check_not_in_place(src, dst, _CDL_IN_PLACE)
+            k = _native.cdl_struct(cdl)
         with self._lock:
             self._bind_stream()
-            if xsub or dither == "blue_noise":
+            if cdl is not None:
+                _native.check(self._lib.lutr_apply_yuv_cdl(
+                    self._ctx, C.byref(p), _native.INTERP[interp], C.byref(k), w, h, nf, C.byref(s), C.byref(d), row0, rows))
+            elif xsub or dither == "blue_noise":
                 _native.check(self._lib.lutr_apply_yuv_xsub(
                     self._ctx, C.byref(p), _native.INTERP[interp], _native.DITHER[dither], w, h, nf, C.byref(s), C.byref(d),
                     row0, rows))

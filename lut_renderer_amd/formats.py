@@ -394,7 +394,7 @@ _CHAIN_NOT_TAKEN = dict(_DUAL_NOT_TAKEN, dither="dither", out2_pix_fmt="a second
                         dst2="a second output (dst2)")
 
 
-def _pass_side(name: Optional[str], what: str, noun: str, sides: str, fine: bool) -> PixFmt:
+def _pass_side(name: Optional[str], what: str, noun: str, sides: str, fine: bool, alpha_ok: bool = False) -> PixFmt:
     """One side of the two-output or the two-LUT pass (`noun`), a planar YUV format (yuvj* read as yuv*); ValueError for RGB,
     float, semi-planar, packed and v210 names.  `what` names the argument in the message.  `fine`: the two-LUT pass's
     refusals -- it tells semi-planar from packed and float from integer RGB, and takes neither v210's relatives nor alpha."""
@@ -411,7 +411,7 @@ def _pass_side(name: Optional[str], what: str, noun: str, sides: str, fine: bool
     if rgb is not None:
         raise ValueError(f"{head} is a float RGB format" if fine and rgb.floating else f"{head} is an RGB format")
     fmt = parse_pix_fmt(name.replace("yuvj", "yuv"))
-    if fine and fmt.alpha:
+    if fine and fmt.alpha and not alpha_ok:
         raise ValueError(f"{head} carries alpha")
     return fmt
 
@@ -488,6 +488,40 @@ def chain_interp(interp: str, interp2: Optional[str]) -> Tuple[int, int]:
             raise ValueError(f"lut3d has no interpolation mode '{name}'")
     return _native.INTERP[interp], _native.INTERP[interp if interp2 is None else interp2]
 
+
+
+def check_cdl_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = None, *, dither: str = "none",
+                      chroma_loc: Optional[str] = None, out_size=None, alpha_mode: str = "straight",
+                      out2_pix_fmt: Optional[str] = None, lut2: bool = False, prelut: bool = False,
+                      variant: Optional[str] = None) -> Tuple[PixFmt, PixFmt]:
+    """The checks every layer makes of a CDL in front of the LUT before any GPU work, the one copy of its
+    refusals: planar YUV on both sides (yuva* with straight alpha included), no .csp prelut on the LUT (`prelut`), no dither,
+    chroma_loc or out_size, no second output (`out2_pix_fmt`), no second LUT (`lut2`), no premultiplied alpha, not the vec_lds
+    variant.  Returns the two parsed formats."""
+    tail = "a CDL"
+    fin = _pass_side(pix_fmt, "pix_fmt", "CDL", "both sides", True, alpha_ok=True)
+    fout = _pass_side(out_pix_fmt or pix_fmt, "out_pix_fmt", "CDL", "both sides", True, alpha_ok=True)
+    if fin.family != "yuv" or fout.family != "yuv":
+        bad, what = (pix_fmt, "pix_fmt") if fin.family != "yuv" else (out_pix_fmt, "out_pix_fmt")
+        raise ValueError(f"the CDL pass takes planar YUV on both sides: {what} '{bad}' is an RGB format")
+    if prelut:
+        raise ValueError(f"a LUT with a .csp prelut is not supported with {tail}: the prelut's table is indexed by integer codes, "
+                         f"and the CDL's output is not a code")
+    if dither != "none":
+        raise ValueError(f"dither ('{dither}') is not supported with {tail}")
+    if chroma_loc is not None:
+        raise ValueError(f"sited chroma resampling (chroma_loc) is not supported with {tail}")
+    if out_size is not None:
+        raise ValueError(f"a resize (out_size / resolution) is not supported with {tail}")
+    if out2_pix_fmt is not None:
+        raise ValueError(f"the two-output pass (out2_pix_fmt) is not supported with {tail}")
+    if lut2:
+        raise ValueError(f"the two-LUT chain (a second LUT) is not supported with {tail}")
+    if alpha_mode != "straight":
+        raise ValueError(f"alpha_mode='{alpha_mode}' is not supported with {tail}")
+    if variant == "vec_lds":
+        raise ValueError(f"variant vec_lds is not supported with {tail}: there is no LDS-window kernel for the CDL pass")
+    return fin, fout
 
 
 #: how the colour planes of an alpha-carrying source stand to their alpha (DESIGN.md 3.18)

@@ -29,8 +29,9 @@ import torch
 from . import _native
 from .cube import CubeLut, read_lut
 from .engine import LutEngine, _fresh_planes, _new_planes, _yuv_out_dtype, chain_args, dual_args
-from .formats import (check_alpha_mode, check_container_options, check_lut2, check_premul_options, packed_frame_width, parse_pix_fmt,
-                      parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords, v210_frame_width, yuv_side)
+from .formats import (check_alpha_mode, check_cdl_options, check_container_options, check_lut2, check_premul_options,
+                      packed_frame_width, parse_pix_fmt, parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords,
+                      v210_frame_width, yuv_side)
 from .shard import row_blocks
 
 
@@ -148,6 +149,10 @@ class LutEngineGroup:
         self.precision = name
 
     @property
+    def _has_prelut(self) -> bool:
+        return bool(self.engines) and self.engines[0]._has_prelut
+
+    @property
     def last_kernels(self) -> List[str]:
         return [e.last_kernel for e in self.engines]
 
@@ -197,6 +202,11 @@ class LutEngineGroup:
             check_premul_options(pix_fmt, out_pix_fmt, dither=kw.get("dither", "none"), chroma_loc=kw.get("chroma_loc"),
                                  out_size=kw.get("out_size"), range_src=kw.get("range_src", "tv"), range_in=kw.get("range_in"),
                                  lut_depth=kw.get("lut_depth"))
+        # a CDL in front of the LUT is passed on too: per-pixel work, shards on the union block, no halo
+        if kw.get("cdl") is not None:
+            check_cdl_options(pix_fmt, out_pix_fmt, dither=kw.get("dither", "none"), chroma_loc=kw.get("chroma_loc"),
+                              out_size=kw.get("out_size"), alpha_mode=kw.get("alpha_mode", "straight"),
+                              prelut=bool(getattr(self, "_has_prelut", False)))
         # a semi-planar side is two planes, the second with the chroma plane's rows: the shard rule is unchanged.
         # A packed 4:2:2 side (3.12) is one buffer with the frame's rows -- any row for a 4:2:2 destination, even rows for a
         # planar 4:2:0 one, which is the union block rule below

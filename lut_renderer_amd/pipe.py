@@ -48,18 +48,20 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
                           ffmpeg_bin: str = "ffmpeg", python_bin: Optional[str] = None, device: int = 0,
                           precision: str = "strict", chroma_loc: Optional[str] = None, gpu_resize: bool = False,
                           engine_dither: Optional[str] = None, cube2: Optional[Path] = None,
-                          interp2: Optional[str] = None, alpha_mode: str = "straight") -> StageCommands:
+                          interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None,
+                          cdl_id: Optional[str] = None) -> StageCommands:
     """The three argv lists of one LUT stage.  Raises what `build_command` / `engine_command` raise (copy guard, missing
     geometry).  `chroma_loc` goes to the engine (`--chroma-loc`) and, as `-chroma_sample_location`, to the encoder, so the
     output stream declares the siting the engine assumed.  `gpu_resize` with `params.resolution` set resizes in the engine
     (`--out-size`): the raw input's `-s` is then the target size and the encoder's own `-s` is dropped.  `engine_dither` goes to
     the engine (`--engine-dither`), and so do `cube2` / `interp2` (`--cube2`, `--interp2`: a second LUT in the same
     pass).  `alpha_mode` ("premultiplied") goes to the engine alone (`--alpha-mode`): ffmpeg's chain
-    has no such step, so the decoder and encoder argv are untouched."""
+    has no such step, so the decoder and encoder argv are untouched.  The same holds for `cdl` / `cdl_id` (an ASC CDL ahead of the
+    LUT, DESIGN.md 3.19: `--cdl` / `--cdl-id`, or `--cdl-sop` / `--cdl-sat` for a `cdl.Cdl`)."""
     notes: List[str] = []
     engine = engine_command(Path("-"), Path("-"), params, lut_path, source_info, python_bin=python_bin, device=device, notes=notes,
                             precision=precision, chroma_loc=chroma_loc, gpu_resize=gpu_resize, engine_dither=engine_dither,
-                            cube2=cube2, interp2=interp2, alpha_mode=alpha_mode)
+                            cube2=cube2, interp2=interp2, alpha_mode=alpha_mode, cdl=cdl, cdl_id=cdl_id)
     resized = gpu_resize and bool(params.resolution)
     if source_info.duration:
         engine += ["--duration", f"{float(source_info.duration):.3f}"]
@@ -150,15 +152,25 @@ def main(argv=None) -> int:
     ap.add_argument("--cube2", default=None, help="engine setting: a second LUT behind --cube in the same pass, see lut_renderer_amd.cli")
     ap.add_argument("--interp2", default=None, help="interpolation mode of --cube2, see lut_renderer_amd.cli")
     ap.add_argument("--alpha-mode", default="straight", choices=["straight", "premultiplied"], help="engine setting, see lut_renderer_amd.cli")
+    ap.add_argument("--cdl", default=None, help="engine setting: an ASC CDL file (.cc / .ccc / .cdl) ahead of --cube, see lut_renderer_amd.cli")
+    ap.add_argument("--cdl-id", default=None, help="the id of the ColorCorrection to take from --cdl")
+    ap.add_argument("--cdl-sop", default=None, help="the CDL as nine literal values, see lut_renderer_amd.cli")
+    ap.add_argument("--cdl-sat", default=None, type=float, help="the CDL's saturation as a literal value")
     ap.add_argument("--gpu-resize", action="store_true", help="resize to the params' resolution in the engine (--out-size) instead of the encoder")
     a = ap.parse_args(argv)
     try:
         params = ProcessingParams.from_dict(json.loads(a.params))
         info = VideoInfo(**json.loads(a.info))
+        if a.cdl is not None and (a.cdl_sop is not None or a.cdl_sat is not None):
+            raise ValueError("--cdl names a file and --cdl-sop / --cdl-sat give literal values: use one or the other")
+        cdl = Path(a.cdl) if a.cdl is not None else None
+        if a.cdl_sop is not None or a.cdl_sat is not None:
+            from .cdl import Cdl
+            cdl = Cdl.from_sop_text(a.cdl_sop, a.cdl_sat)
         cmds = engine_stage_commands(Path(a.input), Path(a.output), params, Path(a.cube), info, ffmpeg_bin=a.ffmpeg, device=a.device,
                                      precision=a.precision, chroma_loc=a.chroma_loc, gpu_resize=a.gpu_resize,
                                      engine_dither=a.engine_dither, cube2=None if a.cube2 is None else Path(a.cube2),
-                                     interp2=a.interp2, alpha_mode=a.alpha_mode)
+                                     interp2=a.interp2, alpha_mode=a.alpha_mode, cdl=cdl, cdl_id=a.cdl_id)
     except Exception as exc:
         print(f"Error: {exc}", flush=True)
         return 1

@@ -19,8 +19,8 @@ import numpy as np
 import torch
 
 from .engine import LutEngine
-from .formats import (RgbSource, check_alpha_mode, check_chain_options, check_dual_options, check_premul_options, parse_rgb_source,
-                      parse_size, premul_to_yuv, refuse_alpha_resize, yuv_side)
+from .formats import (RgbSource, check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options,
+                      check_premul_options, parse_rgb_source, parse_size, premul_to_yuv, refuse_alpha_resize, yuv_side)
 
 
 @dataclass
@@ -153,6 +153,13 @@ class HostPipeline:
                                  to_yuv=premul_to_yuv(pix_fmt, out_pix_fmt))
         else:
             apply_kw = {k: v for k, v in apply_kw.items() if k != "alpha_mode"}
+        # a CDL in front of the LUT travels in apply_kw too, as a `cdl.Cdl`; None is not passed on
+        if apply_kw.get("cdl") is not None:
+            check_cdl_options(pix_fmt, out_pix_fmt, dither=apply_kw.get("dither", "none"), chroma_loc=apply_kw.get("chroma_loc"),
+                              out_size=out_size, alpha_mode=apply_kw.get("alpha_mode", "straight"), out2_pix_fmt=second_pix_fmt,
+                              lut2=self.chain, prelut=bool(getattr(engine, "_has_prelut", False)))
+        else:
+            apply_kw = {k: v for k, v in apply_kw.items() if k != "cdl"}
         if self.chain:
             check_chain_options(pix_fmt, out_pix_fmt, apply_kw.get("dither", "none"), apply_kw.get("chroma_loc"), out_size,
                                 second_pix_fmt)
