@@ -182,8 +182,16 @@ template <int INTERP, int V> struct Node {
 };
 
 // ---------------------------------------------------------------- window (wave-uniform)
+// The cells are integers (CrdI), and the tap address is still three full-rate fma -- with NO conversion at either end: the bits of an
+// integer 0 <= k < 2^24 read as a float are k * 2^-149 (a denormal, or the first normal binade: the spacing is 2^-149 throughout), the
+// kernels run with fp32 denormals on (the compiler's default for gfx9, spelled out in the Makefile: -fno-gpu-flush-denormals-to-zero;
+// the code object says .amdhsa_float_denorm_mode_32 3), v_fma_f32 honours them at full rate, the steps fr / fg / fb are ordinary
+// floats holding integers, so every product and sum below is an integer multiple of 2^-149 of magnitude below 2^24 * 2^-149, hence
+// exact, and the bits of the (non-negative) result are the address.  (Measured instead: three v_mad_u32_u24 -- one instruction
+// fewer still, all of them on the quarter-rate unit: 1.0 % slower than the parent, profiles/tile_cuts_ab.txt.)
+DEV float as_tiny(int k) { return k >= 0 ? __int_as_float(k) : -__int_as_float(-k); }      // k * 2^-149, |k| < 2^24
 struct Win {
-    float fr, fg, fb, fc;        // LDS byte address of the c000 tap: (int) fma(pr, fr, fma(pg, fg, fma(pb, fb, fc)))
+    float fr, fg, fb, fc;        // LDS byte address of the c000 tap: bits of fma(tiny(pr), fr, fma(tiny(pg), fg, fma(tiny(pb), fb, fc))), fc = tiny(base)
     int   o_r, o_g;              // byte steps of +1 along r and g (blue is one node)
 };
 // The raw-code box a window is good for lives in the wave's LDS scratch, not in registers: {ylo, yhi, cblo, cbhi} at +32,
@@ -197,7 +205,9 @@ DEV void box_store(int scratch_off, const Box &b)
     *(uint2 *)(smem + scratch_off + 48) = make_uint2(b.crlo, b.crhi);
 }
 
-struct Ext { uint32_t ymin, ymax, cbmin, cbmax, crmin, crmax; };   // packed per-lane extremes of a unit
+// packed per-lane extremes of a unit.  yor: the OR of the luma words -- all the legality test wants (or_words); ymin and ymax are
+// filled in by the tiles that go on to the window's raw box (luma_min, luma_max)
+struct Ext { uint32_t ymin, ymax, cbmin, cbmax, crmin, crmax, yor; };
 
 template <int INTERP>
 DEV Crd crd_compute(const LutConsts &L, float code, float sc)
@@ -206,16 +216,20 @@ DEV Crd crd_compute(const LutConsts &L, float code, float sc)
     return crd_split<INTERP>(fminf(x * sc, L.lut_max));       // codes and scales are >= 0: only the upper clip can bind
 }
 
-DEV Crd crd_table(unsigned idx)
+// The kernels carry the cell as an integer (CrdI, lutr_tube.h): the table stores it so, the computed coordinates of the general
+// variant are converted once, where they are made.
+DEV CrdI crd_int(const Crd &c) { return CrdI{(int)c.p, c.d}; }
+
+DEV CrdI crd_table(unsigned idx)
 {
-    const float2 e = *(const float2 *)(smem + idx * 8u);
-    return Crd{e.x, e.y};
+    const uint2 e = *(const uint2 *)(smem + idx * 8u);
+    return CrdI{(int)e.x, __uint_as_float(e.y)};
 }
 // The per-pixel paths index the table by BYTE offset: their YUV -> RGB constants are pre-multiplied by 8 (KB in the kernel;
 // a power of two commutes with every rounding), so (unsigned)(8 * v) & ~7 == 8 * floor(v): the `* 8` that was a
 // quarter-rate v_lshl_add_u32 per channel is a v_and_b32 on the other pipe.
 // The table sits at LDS address 0 (checked at kernel start): the offset IS the address (crd_table8, lutr_tube.h).
-typedef __attribute__((address_space(3))) const float *lds_fp;
+typedef __attribute__((address_space(3))) const int *lds_ip;        // the cell of an entry alone (tile_bounds)
 
 // Entry i of the table = coordinates of code min(i, M): indices past M are what an out-of-gamut YUV triple produces
 // before FFmpeg's clip to the depth; the clip is folded into the table.
@@ -227,7 +241,7 @@ DEV void coord_table_fill(const LutConsts &L, int entries)
         if (L.pre) {                 // a shared prelut (LutConsts::pre_shared): the folded coordinate of the code, then prev / frac as ever
             c = crd_split<INTERP>(L.pre[min(q, (int)L.maxf)]);
         } else c = crd_compute<INTERP>(L, fminf((float)q, L.maxf), L.sc[0]);
-        *(float2 *)(smem + q * 8) = make_float2(c.p, c.d);
+        *(uint2 *)(smem + q * 8) = make_uint2((unsigned)(int)c.p, __float_as_uint(c.d));      // {int32 prev, float frac}
     }
     __syncthreads();
 }
@@ -322,15 +336,34 @@ DEV void min_words(const uint32_t *w, uint32_t &mn, bool first)
     }
 }
 
-// everything but the luma minimum (luma_min below)
+// "No sample above 2^k - 1" does not need the maximum: it holds exactly when the OR of the words has no bit above k set, i.e. when
+// the OR itself, half by half, is not above 2^k - 1 (the launcher checks that max_raw + 1 is a power of two): the OR takes the
+// maximum's place in the saturating subtraction.  Three v_or3_b32 and a v_or_b32 instead of seven v_pk_max_u16 per tile.
+template <int N>
+DEV void or_words(const uint32_t *w, uint32_t &o, bool first)
+{
+#pragma unroll
+    for (int k = 0; k < N; k++) o = (first && k == 0) ? w[0] : (o | w[k]);
+}
+// non-zero where a luma sample of the unit is above the top code (`top` = pack_hi(max_raw)).  8-bit planes: every byte is a legal
+// code, there is no test.
+template <int WIN> DEV uint32_t luma_illegal(uint32_t yor, uint32_t top)
+{
+    if constexpr (WIN) return pk_subsat_vs(yor, top);
+    else return 0u;
+}
+
+// the chroma extremes and the OR of the luma words; the luma extremes come later, for the tiles that want them (luma_min, luma_max)
 template <int WIN, int WOUT, int CSX, int CSY>
 DEV Ext extremes(const TileIn<WIN, WOUT, CSX, CSY> &in)
 {
     using T = Tile<WIN, WOUT, CSX, CSY>;
     Ext e;
-    e.ymin = 0u;
+    e.ymin = e.ymax = e.yor = 0u;
+    if constexpr (WIN) {
 #pragma unroll
-    for (int dy = 0; dy < T::BH; dy++) max_words<WIN, T::YWI>(in.y[dy], e.ymax, dy == 0);
+        for (int dy = 0; dy < T::BH; dy++) or_words<T::YWI>(in.y[dy], e.yor, dy == 0);
+    }
     ext_words<WIN, T::CWI>(in.cb, e.cbmin, e.cbmax, true);
     ext_words<WIN, T::CWI>(in.cr, e.crmin, e.crmax, true);
     return e;
@@ -343,6 +376,15 @@ DEV uint32_t luma_min(const TileIn<WIN, WOUT, CSX, CSY> &in)
 #pragma unroll
     for (int dy = 0; dy < T::BH; dy++) min_words<WIN, T::YWI>(in.y[dy], mn, dy == 0);
     return mn;
+}
+template <int WIN, int WOUT, int CSX, int CSY>
+DEV uint32_t luma_max(const TileIn<WIN, WOUT, CSX, CSY> &in)
+{
+    using T = Tile<WIN, WOUT, CSX, CSY>;
+    uint32_t mx = 0u;
+#pragma unroll
+    for (int dy = 0; dy < T::BH; dy++) max_words<WIN, T::YWI>(in.y[dy], mx, dy == 0);
+    return mx;
 }
 
 DEV uint32_t pk_subsat(uint32_t a, uint32_t b) { uint32_t o; asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(o) : "v"(a), "v"(b)); return o; }
@@ -371,7 +413,7 @@ struct Cells { int r0, r1, g0, g1, b0, b1; };
 template <int INTERP, int PRE, int V>
 DEV float cell_of(const LutConsts &L, float q, int ch, int tab_entries)
 {
-    if constexpr (V >= V_TAB) { (void)ch; (void)tab_entries; return crd_table((unsigned)q).p; }
+    if constexpr (V >= V_TAB) { (void)ch; (void)tab_entries; return (float)crd_table((unsigned)q).p; }
     else { (void)tab_entries; return crd_compute<INTERP>(L, q, L.sc[ch]).p; }
 }
 
@@ -428,15 +470,31 @@ DEV Cells map_box(const LutConsts &L, const YuvConsts &K, const Geom &TG, float 
 // description (uncorrelated sensor noise in Cb and Cr spans a box whose corners no pixel reaches).  The second level
 // computes what round 1 computed for every tile: the exact cells each pixel touches, min/max per lane, one vote against
 // the window's cell ranges.  ~18 VALU per pixel, paid only by the tiles that fail the cheap test.
-struct Bnd { float rmin, rmax, gmin, gmax, bmin, bmax; };
+struct Bnd { int rmin, rmax, gmin, gmax, bmin, bmax; };
+constexpr int kBndNone = 1 << 30;       // rmin = ... = kBndNone, rmax = ... = -kBndNone: no cell yet
+// (written as asm like the float forms in lutr_tube.h)
+DEV int vmin3i(int a, int b, int c) { int o; asm("v_min3_i32 %0, %1, %2, %3" : "=v"(o) : "v"(a), "v"(b), "v"(c)); return o; }
+DEV int vmax3i(int a, int b, int c) { int o; asm("v_max3_i32 %0, %1, %2, %3" : "=v"(o) : "v"(a), "v"(b), "v"(c)); return o; }
+DEV int wave_min_i(int v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m, 64));
+    return v;
+}
+DEV int wave_max_i(int v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m, 64));
+    return v;
+}
 
 template <int WIN, int WOUT, int CSX, int CSY, int INTERP, int PRE, int V>
 DEV Bnd tile_bounds(const LutConsts &L, const YuvConsts &K, const Geom &TG, TileIn<WIN, WOUT, CSX, CSY> &in)
 {
     using T = Tile<WIN, WOUT, CSX, CSY>;
     Bnd bn;
-    bn.rmin = bn.gmin = bn.bmin = 1e9f;
-    bn.rmax = bn.gmax = bn.bmax = -1e9f;
+    bn.rmin = bn.gmin = bn.bmin = kBndNone;
+    bn.rmax = bn.gmax = bn.bmax = -kBndNone;
 #pragma unroll
     for (int j = 0; j < T::NC; j++) {
         float cbv = wsample<WIN>(in.cb, j), crv = wsample<WIN>(in.cr, j);
@@ -447,7 +505,7 @@ DEV Bnd tile_bounds(const LutConsts &L, const YuvConsts &K, const Geom &TG, Tile
         const float cbd = cbv - K.coff, crd = crv - K.coff;
         const float rv = K.krv * crd, gv = fma_(K.kgu, cbd, K.kgv * crd), bu = K.kbu * cbd;
         constexpr int NQ = T::BH * T::BW;
-        float pr[NQ], pg_[NQ], pb_[NQ], hg[NQ], hb[NQ];
+        int pr[NQ], pg_[NQ], pb_[NQ], hg[NQ], hb[NQ];
         // all table reads of the chroma block first, then their uses (one LDS round trip per block, not per pixel)
 #pragma unroll
         for (int q = 0; q < NQ; q++) {
@@ -457,13 +515,13 @@ DEV Bnd tile_bounds(const LutConsts &L, const YuvConsts &K, const Geom &TG, Tile
             const float yy = fma_(K.ky, yv, K.yb);
             if constexpr (V >= V_TAB) {
                 // K is the kernel's KB; the caller has checked that every raw code is legal, so the padded table covers the sums
-                pr[q] = *(lds_fp)(uintptr_t)((unsigned)(yy + rv) & ~7u);
-                pg_[q] = *(lds_fp)(uintptr_t)((unsigned)(yy + gv) & ~7u);
-                pb_[q] = *(lds_fp)(uintptr_t)((unsigned)(yy + bu) & ~7u);
+                pr[q] = *(lds_ip)(uintptr_t)((unsigned)(yy + rv) & ~7u);
+                pg_[q] = *(lds_ip)(uintptr_t)((unsigned)(yy + gv) & ~7u);
+                pb_[q] = *(lds_ip)(uintptr_t)((unsigned)(yy + bu) & ~7u);
             } else {
-                pr[q] = crd_compute<INTERP>(L, cfloor(yy + rv, K.max_l), L.sc[0]).p;
-                pg_[q] = crd_compute<INTERP>(L, cfloor(yy + gv, K.max_l), L.sc[1]).p;
-                pb_[q] = crd_compute<INTERP>(L, cfloor(yy + bu, K.max_l), L.sc[2]).p;
+                pr[q] = (int)crd_compute<INTERP>(L, cfloor(yy + rv, K.max_l), L.sc[0]).p;
+                pg_[q] = (int)crd_compute<INTERP>(L, cfloor(yy + gv, K.max_l), L.sc[1]).p;
+                pb_[q] = (int)crd_compute<INTERP>(L, cfloor(yy + bu, K.max_l), L.sc[2]).p;
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -472,14 +530,14 @@ DEV Bnd tile_bounds(const LutConsts &L, const YuvConsts &K, const Geom &TG, Tile
         if constexpr (T::BH * T::BW >= 2) {
 #pragma unroll
             for (int q = 0; q + 1 < T::BH * T::BW; q += 2) {
-                bn.rmin = vmin3(bn.rmin, pr[q], pr[q + 1]); bn.rmax = vmax3(bn.rmax, pr[q], pr[q + 1]);
-                bn.gmin = vmin3(bn.gmin, hg[q], hg[q + 1]); bn.gmax = vmax3(bn.gmax, hg[q], hg[q + 1]);
-                bn.bmin = vmin3(bn.bmin, hb[q], hb[q + 1]); bn.bmax = vmax3(bn.bmax, hb[q], hb[q + 1]);
+                bn.rmin = vmin3i(bn.rmin, pr[q], pr[q + 1]); bn.rmax = vmax3i(bn.rmax, pr[q], pr[q + 1]);
+                bn.gmin = vmin3i(bn.gmin, hg[q], hg[q + 1]); bn.gmax = vmax3i(bn.gmax, hg[q], hg[q + 1]);
+                bn.bmin = vmin3i(bn.bmin, hb[q], hb[q + 1]); bn.bmax = vmax3i(bn.bmax, hb[q], hb[q + 1]);
             }
         } else {
-            bn.rmin = fminf(bn.rmin, pr[0]); bn.rmax = fmaxf(bn.rmax, pr[0]);
-            bn.gmin = fminf(bn.gmin, hg[0]); bn.gmax = fmaxf(bn.gmax, hg[0]);
-            bn.bmin = fminf(bn.bmin, hb[0]); bn.bmax = fmaxf(bn.bmax, hb[0]);
+            bn.rmin = min(bn.rmin, pr[0]); bn.rmax = max(bn.rmax, pr[0]);
+            bn.gmin = min(bn.gmin, hg[0]); bn.gmax = max(bn.gmax, hg[0]);
+            bn.bmin = min(bn.bmin, hb[0]); bn.bmax = max(bn.bmax, hb[0]);
         }
         // keep the blocks in program order (see tile_body): the fences do not change the words
         fence_words<T::YWI * T::BH>(&in.y[0][0]);
@@ -493,8 +551,8 @@ DEV Bnd tile_bounds(const LutConsts &L, const YuvConsts &K, const Geom &TG, Tile
 // the window's cell ranges live in the wave's 64-byte LDS scratch (they are only read on the second-level path)
 DEV bool cells_hold(int scratch_off, const Bnd &b)
 {
-    const float4 lo = *(const float4 *)(smem + scratch_off);        // r_lo, g_lo, b_lo, r_hi
-    const float2 hi = *(const float2 *)(smem + scratch_off + 16);   // g_hi, b_hi
+    const int4 lo = *(const int4 *)(smem + scratch_off);            // r_lo, g_lo, b_lo, r_hi
+    const int2 hi = *(const int2 *)(smem + scratch_off + 16);       // g_hi, b_hi
     const bool ok = b.rmin >= lo.x && b.rmax <= lo.w && b.gmin >= lo.y && b.gmax <= hi.x && b.bmin >= lo.z && b.bmax <= hi.y;
     return __all(ok);
 }
@@ -578,9 +636,9 @@ DEV bool rebox(const LutConsts &L, const YuvConsts &K, const Geom &TG, const Ext
     const int cb0 = uni(lo_of<WIN>(e.cbmin)), cb1 = uni(hi_of<WIN>(e.cbmax));
     const int cr0 = uni(lo_of<WIN>(e.crmin)), cr1 = uni(hi_of<WIN>(e.crmax));
     const int mr = TG.max_raw;
-    const float4 lo = *(const float4 *)(smem + scratch_off);        // r_lo, g_lo, b_lo, r_hi
-    const float2 hi = *(const float2 *)(smem + scratch_off + 16);   // g_hi, b_hi
-    const int wr0 = uni((int)lo.x), wg0 = uni((int)lo.y), wb0 = uni((int)lo.z), wr1 = uni((int)lo.w), wg1 = uni((int)hi.x), wb1 = uni((int)hi.y);
+    const int4 lo = *(const int4 *)(smem + scratch_off);            // r_lo, g_lo, b_lo, r_hi
+    const int2 hi = *(const int2 *)(smem + scratch_off + 16);       // g_hi, b_hi
+    const int wr0 = uni(lo.x), wg0 = uni(lo.y), wb0 = uni(lo.z), wr1 = uni(lo.w), wg1 = uni(hi.x), wb1 = uni(hi.y);
     const float cell_y = L.maxf / (L.lut_max * K.ky * (PRE ? K.py : 1.0f));
     const int unit = (mr + 1) >> 8;
 #pragma unroll 1
@@ -702,9 +760,9 @@ DEV bool restage(Win &W, const LutConsts &L, const YuvConsts &K, const Geom &TG,
         // (2) The raw box is too loose a description of this tile (an edge between two colours: Cb and Cr move together,
         //     the box spans every combination).  Stage around the tile's EXACT cells; the first-level box stays empty and
         //     the tiles that follow are vouched for by the second-level test.
-        const int rmin = uni((int)wave_min(bn.rmin)), rmax = uni((int)wave_max(bn.rmax));
-        const int gmin = uni((int)wave_min(bn.gmin)), gmax = uni((int)wave_max(bn.gmax));
-        const int bmin = uni((int)wave_min(bn.bmin)), bmax = uni((int)wave_max(bn.bmax));
+        const int rmin = uni(wave_min_i(bn.rmin)), rmax = uni(wave_max_i(bn.rmax));
+        const int gmin = uni(wave_min_i(bn.gmin)), gmax = uni(wave_max_i(bn.gmax));
+        const int bmin = uni(wave_min_i(bn.bmin)), bmax = uni(wave_max_i(bn.bmax));
         const int need_r = rmax - rmin + 2, need_g = gmax - gmin + 3, need_b = bmax - bmin + 3;
         int spare = 1;
         for (;;) {                                   // one spare cell on each side of the chroma-like axes if it fits
@@ -758,13 +816,13 @@ DEV bool restage(Win &W, const LutConsts &L, const YuvConsts &K, const Geom &TG,
         }
     }
     if (lane == 0) {
-        *(float4 *)(smem + scratch_off) = make_float4((float)wr0, (float)wg0, (float)wb0, (float)wr1);
-        *(float2 *)(smem + scratch_off + 16) = make_float2((float)wg1, (float)wb1);
+        *(int4 *)(smem + scratch_off) = make_int4(wr0, wg0, wb0, wr1);
+        *(int2 *)(smem + scratch_off + 16) = make_int2(wg1, wb1);
     }
     // node index = (pr-r0)*sr + (pg-pr-g0)*nb + (pb-pg-b0)
     W.o_r = kLN * (sr - nb); W.o_g = kLN * (nb - 1);
     W.fr = (float)W.o_r; W.fg = (float)W.o_g; W.fb = (float)kLN;
-    W.fc = (float)(lds_base() + slice_off - kLN * (r0 * sr + g0 * nb + b0));
+    W.fc = as_tiny(lds_base() + slice_off - kLN * (r0 * sr + g0 * nb + b0));
     if (lane == 0) {
         Box bx;
         if (by1 >= by0) {
@@ -788,16 +846,16 @@ struct PxC {
 struct Rgb3 { float r, g, b; };
 
 template <bool LDS, int INTERP, int V>
-DEV PxC px_finish(const LutConsts &L, const Win &W, const Crd &cr, const Crd &cg, const Crd &cb)
+DEV PxC px_finish(const LutConsts &L, const Win &W, const CrdI &cr, const CrdI &cg, const CrdI &cb)
 {
     using N = Node<INTERP, V>;
     constexpr int nb_ = LDS ? N::lds : N::glb;
     PxC c;
     if constexpr (LDS) {
-        // exact in fp32: every term is an integer well below 2^24; the box test guarantees the address is inside the slice
-        c.a = (int)fma_(cr.p, W.fr, fma_(cg.p, W.fg, fma_(cb.p, W.fb, W.fc)));
+        // exact (Win): the cells' bits are the operands, the result's bits are the address; the box test guarantees it is inside the slice
+        c.a = __float_as_int(fma_(__int_as_float(cr.p), W.fr, fma_(__int_as_float(cg.p), W.fg, fma_(__int_as_float(cb.p), W.fb, W.fc))));
     } else {
-        c.a = (((int)cr.p * L.n1 + (int)cg.p) * L.n1 + (int)cb.p) * nb_;
+        c.a = ((cr.p * L.n1 + cg.p) * L.n1 + cb.p) * nb_;
     }
     c.oa = c.oz = 0;
     c.w01 = f2v{0.0f, 0.0f}; c.w23 = f2v{0.0f, 0.0f};
@@ -888,7 +946,7 @@ DEV Taps<LDS, INTERP, V> px_taps(const LutConsts &L, const Win &W, const PxC &c)
 // lattice (float4 nodes, blue fastest: the gather body's index) over the LDS results; the blend and everything after it run once.
 // A and the steps are exact: prev <= N - 1 in the (N + 1)^3 copy, every product below 2^24.  12 bytes per tap: {r, g, b}.
 template <int INTERP, int V>
-DEV void patch_taps(const LutConsts &L, const Crd &cr, const Crd &cg, const Crd &cb, Taps<true, INTERP, V> &T)
+DEV void patch_taps(const LutConsts &L, const CrdI &cr, const CrdI &cg, const CrdI &cb, Taps<true, INTERP, V> &T)
 {
     static_assert(V != V_FAST, "the fast kernels have no mixed tiles");
     unsigned n1 = (unsigned)L.n1;
@@ -1041,7 +1099,7 @@ template <bool DEAD> DEV float ofloor(float v, float hi) { if constexpr (DEAD) r
 
 // ---------------------------------------------------------------- tile body
 // Coordinates of the four pixels of a group (phase A): twelve table reads (or their computed twins) issued back to back.
-struct GroupCrd { Crd r[4], g[4], b[4]; };
+struct GroupCrd { CrdI r[4], g[4], b[4]; };
 
 template <bool LDS, int WIN, int WOUT, int CSX, int CSY, int INTERP, int PRE, int V>
 DEV void group_coords(const LutConsts &L, const YuvConsts &K, const Geom &TG, const TileIn<WIN, WOUT, CSX, CSY> &in, int g, GroupCrd &q)
@@ -1074,11 +1132,11 @@ DEV void group_coords(const LutConsts &L, const YuvConsts &K, const Geom &TG, co
                 const unsigned top = (unsigned)(TG.tab_entries - 1) * 8u;
                 ri = min(ri, top); gi = min(gi, top); bi = min(bi, top);
             }
-            q.r[p] = crd_table8(ri); q.g[p] = crd_table8(gi); q.b[p] = crd_table8(bi);
+            q.r[p] = crd_table8i(ri); q.g[p] = crd_table8i(gi); q.b[p] = crd_table8i(bi);
         } else {
             const float rq = cfloor(yy + rv[c], K.max_l), gq = cfloor(yy + gv[c], K.max_l), bq = cfloor(yy + bu[c], K.max_l);
-            q.r[p] = crd_compute<INTERP>(L, rq, L.sc[0]); q.g[p] = crd_compute<INTERP>(L, gq, L.sc[1]);
-            q.b[p] = crd_compute<INTERP>(L, bq, L.sc[2]);
+            q.r[p] = crd_int(crd_compute<INTERP>(L, rq, L.sc[0])); q.g[p] = crd_int(crd_compute<INTERP>(L, gq, L.sc[1]));
+            q.b[p] = crd_int(crd_compute<INTERP>(L, bq, L.sc[2]));
         }
     }
 }
@@ -1241,7 +1299,7 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
     // index = pr * plane + (pg - pr + H + 1) * nb + (pb - pg + H + 1)
     Wt.o_g = N::lds * (tube_nb - 1); Wt.o_r = N::lds * (TG.tube_plane - tube_nb);
     Wt.fr = (float)Wt.o_r; Wt.fg = (float)Wt.o_g; Wt.fb = (float)N::lds;
-    Wt.fc = (float)(lds_base() + tube_off + N::lds * ((TG.tube_h + 1) * tube_nb + TG.tube_h + 1));
+    Wt.fc = as_tiny(lds_base() + tube_off + N::lds * ((TG.tube_h + 1) * tube_nb + TG.tube_h + 1));
     unsigned st_tube = 0, st_mixed = 0;
     int fr, sx, ry, rem;                                      // the tile being fetched next
     bool first = true;
@@ -1263,7 +1321,7 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
         // lattice layout of the global copy ((N+1)^3 nodes, blue fastest, index N replicates N-1): prev + 1 is always staged
         W.o_r = N::lds * TG.whole_a; W.o_g = N::lds * TG.whole_b;
         W.fr = (float)W.o_r; W.fg = (float)W.o_g; W.fb = (float)N::lds;
-        W.fc = (float)(lds_base() + tab_bytes + kScratch);
+        W.fc = as_tiny(lds_base() + tab_bytes + kScratch);
     }
     constexpr int YIB = T::YWI * 4, YOB = T::YWO * 4, CIB = T::CWI * 4, COB = T::CWO * 4;
 
@@ -1416,14 +1474,14 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
         fence_words<T::YWI * T::BH>(&in.y[0][0]); fence_words<T::CWI>(in.cb); fence_words<T::CWI>(in.cr);
         TK(tk_wait)                  // ... and this is the wait for this tile's own loads
 #endif
-        Ext e = extremes<WIN, WOUT, CSX, CSY>(in);             // without the luma minimum: see below
+        Ext e = extremes<WIN, WOUT, CSX, CSY>(in);             // without the luma extremes: see below
         bool use_tube = false, mixed = false, lane_in = true;
         unsigned outside = 0u;                 // chroma samples of the lane's unit outside the tube (tile_body, MIX)
         if (TG.tube_h > 0) {
             // level 0: the tile's chroma keeps it inside the workgroup's grey tube (and its raw codes are legal for the clamp-free body)
             const uint32_t top = pack_hi<WIN>(TG.max_raw);
             // one vote for the common case: chroma inside the raw interval (which lies inside the legal codes) and luma legal
-            const uint32_t ybits = pk_subsat_vs(e.ymax, top);
+            const uint32_t ybits = luma_illegal<WIN>(e.yor, top);
             const uint32_t rbits = pk_subsat_sv(TG.tube_rlo, e.cbmin) | pk_subsat_vs(e.cbmax, TG.tube_rhi) |
                                    pk_subsat_sv(TG.tube_rlo, e.crmin) | pk_subsat_vs(e.crmax, TG.tube_rhi);
             if (__all((ybits | rbits) == 0u)) use_tube = true;
@@ -1453,6 +1511,7 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
         bool use_lds = use_tube || mixed;
         if (!use_lds && !TG.whole) {
             e.ymin = luma_min<WIN, WOUT, CSX, CSY>(in);
+            e.ymax = luma_max<WIN, WOUT, CSX, CSY>(in);
             use_lds = box_holds(scratch_off, e);               // first level: raw extremes against the window's raw box
         }
         TK(tk_head)
@@ -1460,7 +1519,7 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
         if (TG.whole) {
             // every cell is in LDS; only raw codes above 2^din - 1 (which the padded table does not cover) need the clamping body
             const uint32_t top = pack_hi<WIN>(TG.max_raw);
-            use_lds = __all((pk_subsat_vs(e.ymax, top) | pk_subsat_vs(e.cbmax, top) | pk_subsat_vs(e.crmax, top)) == 0u);
+            use_lds = __all((luma_illegal<WIN>(e.yor, top) | pk_subsat_vs(e.cbmax, top) | pk_subsat_vs(e.crmax, top)) == 0u);
         } else if (use_tube) {
             st_tube++;
         } else if (mixed) {
@@ -1495,9 +1554,9 @@ void k_yuv_tile2(LutConsts L_, YuvConsts K_, Planes2 P, FrameGeom G, Geom TG)
             // second level: exact cells against the window's cell ranges.  Raw codes must be legal (<= 2^din - 1) for the
             // clamp-free table reads of tile_bounds and of the LDS body; a tile with wild container values takes the gather body.
             const uint32_t top = pack_hi<WIN>(TG.max_raw);
-            const bool legal = __all((pk_subsat_vs(e.ymax, top) | pk_subsat_vs(e.cbmax, top) | pk_subsat_vs(e.crmax, top)) == 0u);
+            const bool legal = __all((luma_illegal<WIN>(e.yor, top) | pk_subsat_vs(e.cbmax, top) | pk_subsat_vs(e.crmax, top)) == 0u);
             Bnd bn;
-            bn.rmin = bn.gmin = bn.bmin = 1e9f; bn.rmax = bn.gmax = bn.bmax = -1e9f;
+            bn.rmin = bn.gmin = bn.bmin = kBndNone; bn.rmax = bn.gmax = bn.bmax = -kBndNone;
             if (legal) bn = tile_bounds<WIN, WOUT, CSX, CSY, INTERP, PRE, V>(L, KB, TG, in);
             use_lds = have_win && legal && cells_hold(scratch_off, bn);
             TK(tk_l2)
@@ -1693,6 +1752,7 @@ const char *T2_ENTRY(hipStream_t st, const LutConsts &L, const YuvConsts &K, con
     tg.ch = ch; tg.nrc = (tg.nry + ch - 1) / ch; tg.nchunks = G.nframes * tg.nrc * tg.nsx;
     tg.tab_entries = vv >= V_TAB ? table_entries(K, din) : 0;
     tg.max_raw = (1 << din) - 1;
+    if ((tg.max_raw & (tg.max_raw + 1)) != 0) return nullptr;      // the kernels test legality by OR (or_words): 2^k - 1 only
     const int node_ = vv == V_FAST ? (mode == LUTR_INTERP_TRILINEAR ? 12 : 8) : (mode == LUTR_INTERP_TRILINEAR ? 16 : 12);      // Node::lds
     const int blocks_per_cu = waves_per_cu / LUTR_T2_WPB > 0 ? waves_per_cu / LUTR_T2_WPB : 1;
     const int lds_block = 163840 / blocks_per_cu - tg.tab_entries * 8 - t2::kScratch;

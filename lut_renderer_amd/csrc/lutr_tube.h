@@ -83,6 +83,17 @@ DEV Crd crd_table8(unsigned off)
     const f2v e = *(lds_f2p)(uintptr_t)off;
     return Crd{e.x, e.y};
 }
+// The YUV tile kernels (lutr_tile2.hip) keep the cell as an INTEGER, in the table ({int32 prev, float frac}) and from there on: the tap
+// address is then three fma on the cells' bits, with no conversion (struct Win there), and nothing downstream converts.  The RGB tube kernels
+// (lutr_rgb2.hip) keep the float pair above: their bodies subtract cells per pixel pair (the tube test), in fp32 as ever.
+struct CrdI { int p; float d; };
+typedef unsigned u2v_ __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) const u2v_ *lds_u2p;
+DEV CrdI crd_table8i(unsigned off)
+{
+    const u2v_ e = *(lds_u2p)(uintptr_t)off;
+    return CrdI{(int)e.x, __uint_as_float(e.y)};
+}
 
 // ---------------------------------------------------------------- work distribution
 // Work is handed out in chunks of `ch` consecutive tile rows of one strip; chunk id = (frame * nrc + row chunk) * nsx + strip, so

@@ -5,7 +5,7 @@
 set -e
 NAME=$1; shift
 cd "$(dirname "$0")/../lut_renderer_amd/csrc"
-FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-honor-nans -fno-slp-vectorize -w --offload-arch=gfx950 -I../../include -I."
+FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-honor-nans -fno-slp-vectorize -fno-gpu-flush-denormals-to-zero -w --offload-arch=gfx950 -I../../include -I."
 mkdir -p build/exp
 R2=""
 for l in 0 1 2 3 4 5 6 7; do

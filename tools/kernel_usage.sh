@@ -3,7 +3,7 @@
 # (-Rpass-analysis=kernel-resource-usage).  WI= WO= CX= CY= select the object; extra -D flags are passed on (lutr_tile2.hip still has
 # LUTR_T2_WPB, LUTR_T2_WAVES_PER_EU and LUTR_T2_DEBUG_STATS).  CPU only (hipcc cross-compiles).
 cd "$(dirname "$0")/../lut_renderer_amd/csrc"
-FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-honor-nans -fno-slp-vectorize -w --offload-arch=gfx950 -I../../include -I."
+FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-honor-nans -fno-slp-vectorize -fno-gpu-flush-denormals-to-zero -w --offload-arch=gfx950 -I../../include -I."
 mkdir -p build/exp
 /opt/rocm/bin/hipcc $FLAGS -DLUTR_T2_WI=${WI:-1} -DLUTR_T2_WO=${WO:-1} -DLUTR_T2_X=${CX:-1} -DLUTR_T2_Y=${CY:-1} "$@" -S --cuda-device-only -Rpass-analysis=kernel-resource-usage \
     lutr_tile2.hip -o build/exp/usage.s 2>&1 | python3 -c "
