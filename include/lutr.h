@@ -634,6 +634,84 @@ int lutr_cdl_table(const lutr_cdl *cdl, int depth, int channel, float *out);
 int lutr_apply_yuv_cdl(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, const lutr_cdl *cdl, int w, int h, int nframes,
                        const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
 
+/* ---- 1D LUT files: ffmpeg's lut1d, alone or ahead of lut3d in the fused pass -- the per-channel transform a
+ *      camera vendor or a grading tool exports as a .cube with LUT_1D_SIZE (log to display gamma, legal to full, printer-light
+ *      trims): `lut1d=file=tech.cube,lut3d=file=look.cube`.  The semantics restate FFmpeg's published vf_lut3d.c; they are
+ *      unpinned, like the other file formats. ---- */
+enum lutr_interp1d {
+    LUTR_INTERP1D_NEAREST = 0,
+    LUTR_INTERP1D_LINEAR  = 1,   /* lut1d's default */
+    LUTR_INTERP1D_COSINE  = 2,
+    LUTR_INTERP1D_CUBIC   = 3,
+    LUTR_INTERP1D_SPLINE  = 4
+};
+
+/* Parse a .cube file with LUT_1D_SIZE n, 2 <= n <= 65536, followed by n rows of three floats.  *lut receives 3 x n floats,
+ * channel c (0 = R, 1 = G, 2 = B) at [c * n]; free it with lutr_cube_free.  Lines are handled as lutr_cube_parse handles them
+ * (comments, blank lines, TITLE, DOMAIN_MIN / DOMAIN_MAX between the size line and the last row, non-finite numbers refused),
+ * plus `LUT_1D_INPUT_RANGE a b`, which sets min and max of all three channels.  scale[c] = clip(1 / (max[c] - min[c]), 0, 1), the
+ * subtraction in float.  Errors name the file: a file that also carries LUT_3D_SIZE (a shaper ahead of a cube: not supported yet)
+ * and a bad size are LUTR_EINVAL; fewer than n rows, a row with fewer than three numbers, no LUT_1D_SIZE are LUTR_EILSEQ.
+ * lutr_cube_parse / lutr_lut_parse keep refusing 1D files.  Not covered: 1D .csp. */
+int lutr_lut1d_parse(const char *path, float **lut, int *size, float scale[3]);
+
+/* Host only, no context and no device: the per-code table of channel `channel` at `depth` bits (8..16), 2^depth entries into
+ * `out`.  M = 2^depth - 1, factor = (float)M, sc = (scale[c] / factor) * (float)(size - 1); every operation rounded to fp32, no
+ * contraction.  For every code k = 0 .. M: s = (float)k * sc, prev = (int)s, next = min(prev + 1, size - 1), mu = s - prev, p =
+ * lut[c][prev], q = lut[c][next], and v by `interp1d` (FFmpeg's interp_1d_*):
+ *   nearest  lut[c][(int)((double)s + .5)]
+ *   linear   p + (q - p) * mu
+ *   cosine   m = (1.f - cosf((float)(mu * M_PI))) * .5f;  p + (q - p) * m     (the one mode that depends on the C library's cosf)
+ *   cubic    y0 = lut[max(prev - 1, 0)], y1 = p, y2 = q, y3 = lut[min(next + 1, size - 1)]; mu2 = mu * mu; a0 = y3 - y2 - y0 + y1,
+ *            a1 = y0 - y1 - a0, a2 = y2 - y0, a3 = y1; a0 * mu * mu2 + a1 * mu2 + a2 * mu + a3, left to right
+ *   spline   c0 = y1, c1 = .5f * (y2 - y0), c2 = y0 - 2.5f * y1 + 2.f * y2 - .5f * y3, c3 = .5f * (y3 - y0) + 1.5f * (y1 - y2);
+ *            ((c3 * mu + c2) * mu + c1) * mu + c0
+ * out[k] = (int)med3(v * factor, 0, factor): truncation; the clamp in float ahead of the conversion is the engine's own rule.
+ * LUTR_EINVAL with a message: a null argument, size outside 2..65536, an unknown mode, depth outside 8..16, channel outside 0..2,
+ * scale[channel] outside [0, 1], a node that is not finite. */
+int lutr_lut1d_table(const float *lut, int size, const float scale[3], int interp1d, int depth, int channel, uint16_t *out);
+
+/* The context's 1D LUT (layout of lutr_lut1d_parse) and its mode; lut NULL or size 0 removes it.  It lives beside the lattices:
+ * lutr_ctx_set_lut, lutr_ctx_set_lut2, the broadcast and every other entry point leave it alone, and only the two entry points
+ * below read it.  The device tables are built per depth at first use and uploaded on the context's stream, behind the kernels that
+ * still read the previous one; they are told apart by a generation number taken here, never by the host address. */
+int lutr_ctx_set_lut1d(lutr_ctx *ctx, const float *lut, int size, const float scale[3], int interp1d);
+
+/* lutr_apply_yuv_xsub's pass (planar YUV in and out, any pair of 4:2:0 / 4:2:2 / 4:4:4, the equal pairs included, 8..16 bit on
+ * either side) with the context's 1D LUT between its YUV -> RGB stage and lut3d.  Per luma position:
+ *   q    = YUV -> integer RGB at lut_depth (lutr_apply_yuv's stage 1, the full-range prologue included; chroma replicated over
+ *          its INPUT block)
+ *   q'_c = lutr_lut1d_table(..., lut_depth, c)[q_c]
+ *   v    = lut3d on the codes q' (`interp`, all five modes; a .csp prelut on the lattice is taken: q' is a code), or q' itself
+ *          with interp == LUTR_INTERP_NONE (lut1d alone; no lattice needed)
+ *   out  = integer RGB -> YUV from v (lutr_apply_yuv_xsub's stage 3; constants: lutr_yuv_constants_xsub)
+ * The frame is integer RGB at lut_depth between the two filters, as it is between ffmpeg's lut1d and lut3d.  The identity 1D LUT
+ * (lut[c][i] = i / (n - 1), n = 2^lut_depth, linear) gives the bits of the call without it.
+ * row0 and rows must be multiples of the union block height 2^max(icsy, ocsy) unless row0 + rows == h.  Always strict precision,
+ * no suffix on the last kernel.  Not in place (the overlap rule of lutr_apply_yuv_sited).
+ * LUTR_EINVAL with a message, before anything touches the device: no 1D LUT set, no lattice (unless LUTR_INTERP_NONE), a null
+ * argument or plane, the format errors of lutr_apply_yuv_xsub, 16-bit planes at odd addresses, row0 / rows off the union block,
+ * any overlap, variant vec_lds.  Variant vec_global where the vector kernel cannot take the call is LUTR_EINVAL too, found where
+ * the kernel is chosen.
+ * Kernels: "k_yuv_l1d_vec<win,wout,icsx,icsy,ocsx,ocsy,interp>" (none (-1) / nearest / trilinear / tetrahedral; 8 -> 8, 16 -> 16
+ * and 16 -> 8 bit containers; the layout rules of k_yuv_cdl_vec), a grid-stride walk whose workgroups stage the table into LDS
+ * once when 3 * 2^lut_depth * 2 bytes <= 24 KB and LUTR_L1D_LDS is not 0, and read it from global memory otherwise -- the bits do
+ * not depend on that; "k_yuv_l1d_generic" for everything else; a ragged width is split and named
+ * "<vector kernel>+k_yuv_l1d_generic".
+ * Not covered: cosine anywhere but the host table, a 1D LUT behind lut3d, float sources, the container formats of DESIGN.md
+ * 3.11 - 3.14, dither, chroma siting, a resize, a CDL, the chain, two outputs, premultiplied alpha, a tile (LDS window) kernel. */
+int lutr_apply_yuv_lut1d(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int w, int h, int nframes, const lutr_planes *src,
+                         const lutr_planes *dst, int row0, int rows);
+
+/* lut1d alone on planar RGB (gbrp order: plane 0 = G, 1 = B, 2 = R) at `depth` bits (8: uint8, 9..16: uint16 LE):
+ * out_c = lutr_lut1d_table(..., depth, c)[min(code_c, 2^depth - 1)] -- the clamp of container values above M is the engine's own
+ * rule.  In place is allowed: each sample is read and written by one lane.  Kernels: "k_rgb_l1d<wide>" (whole-dword loads and
+ * stores: bases and strides multiples of 4; the table in LDS or global memory on lutr_apply_yuv_lut1d's terms), "k_rgb_l1d_generic"
+ * for unaligned planes and the columns past the last whole dword ("k_rgb_l1d<wide>+k_rgb_l1d_generic").  vec_lds is LUTR_EINVAL; vec_global is LUTR_EINVAL where the dword kernel cannot take the
+ * whole call. */
+int lutr_apply_planar_rgb_lut1d(lutr_ctx *ctx, int depth, int w, int h, int nframes, const lutr_planes *src, const lutr_planes *dst,
+                                int row0, int rows);
+
 /* ---- the alpha plane of yuva* / gbrap* frames: ProRes 4444 (yuva444p10le / 12le), VP8 / VP9 with alpha
  *      (yuva420p), PNG / TIFF / EXR sequences with alpha (rgba, rgba64le, gbrap*, gbrapf32le).  In the reference's chain lut3d
  *      copies the alpha plane through and format=<pix_fmt> keeps, converts, drops or makes it (ffmpeg.py:246, :304-310) ---- */

@@ -16,6 +16,8 @@ LIB_PATH = _PKG / "lib" / "liblutr.so"
 OK, ENOENT, EIO, ENOMEM, EINVAL, EILSEQ = 0, -2, -5, -12, -22, -84
 
 INTERP = {"nearest": 0, "trilinear": 1, "tetrahedral": 2, "pyramid": 3, "prism": 4}
+#: enum lutr_interp1d: lut1d's modes
+INTERP1D = {"nearest": 0, "linear": 1, "cosine": 2, "cubic": 3, "spline": 4}
 MATRIX = {"bt709": 0, "smpte170m": 1, "bt470bg": 1, "bt601": 1, "bt2020nc": 2, "bt2020c": 2}
 RANGE = {"tv": 0, "pc": 1}
 DITHER = {"none": 0, "error_diffusion": 1, "blue_noise": 2}
@@ -43,6 +45,7 @@ SYMBOLS = (
     "lutr_apply_planar_rgb_f32", "lutr_apply_rgbf_to_yuv", "lutr_apply_yuv_semi", "lutr_apply_yuv_packed",
     "lutr_apply_yuv_dual", "lutr_apply_yuv_v210", "lutr_alpha_plane", "lutr_ctx_set_lut2", "lutr_apply_yuv_chain",
     "lutr_apply_yuv_premul", "lutr_apply_planar_rgb_f32_premul", "lutr_cdl_table", "lutr_apply_yuv_cdl",
+    "lutr_lut1d_parse", "lutr_lut1d_table", "lutr_ctx_set_lut1d", "lutr_apply_yuv_lut1d", "lutr_apply_planar_rgb_lut1d",
     "lutr_resize_filter", "lutr_resize_planes", "lutr_dither_mask",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
     "lutr_max_waves_knob",
@@ -227,6 +230,11 @@ def load() -> C.CDLL:
     lib.lutr_cdl_table.argtypes = [C.POINTER(CdlStruct), ci, ci, C.POINTER(C.c_float)]
     lib.lutr_apply_yuv_cdl.argtypes = [vp, C.POINTER(YuvParams), ci, C.POINTER(CdlStruct), ci, ci, ci, C.POINTER(Planes),
                                        C.POINTER(Planes), ci, ci]
+    lib.lutr_lut1d_parse.argtypes = lib.lutr_cube_parse.argtypes
+    lib.lutr_lut1d_table.argtypes = [C.POINTER(C.c_float), ci, C.POINTER(C.c_float), ci, ci, ci, C.POINTER(C.c_uint16)]
+    lib.lutr_ctx_set_lut1d.argtypes = [vp, C.POINTER(C.c_float), ci, C.POINTER(C.c_float), ci]
+    lib.lutr_apply_yuv_lut1d.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
+    lib.lutr_apply_planar_rgb_lut1d.argtypes = [vp, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_dither_mask.argtypes = [C.POINTER(C.c_uint16)]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]
@@ -257,6 +265,27 @@ def cdl_table(cdl, depth: int):
     out = np.zeros((3, 1 << int(depth)), np.float32)
     for ch in range(3):
         check(load().lutr_cdl_table(C.byref(st), int(depth), ch, out[ch].ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
+def interp1d_code(name) -> int:
+    """enum lutr_interp1d of a lut1d mode name; ValueError for an unknown one."""
+    if name not in INTERP1D:
+        raise ValueError(f"unknown interp1d '{name}' ({' | '.join(INTERP1D)})")
+    return INTERP1D[name]
+
+
+def lut1d_table(lut1d, interp1d: str, depth: int):
+    """lutr_lut1d_table (host only): the per-code table of a `cube.Lut1D` for the three channels, uint16
+    [3, 2^depth] -- the output code of every integer code."""
+    import numpy as np
+    mode = interp1d_code(interp1d)
+    tab = np.ascontiguousarray(lut1d.table, dtype=np.float32)
+    scale = (C.c_float * 3)(*[float(v) for v in lut1d.scale])
+    out = np.zeros((3, 1 << int(depth)), np.uint16)
+    for ch in range(3):
+        check(load().lutr_lut1d_table(tab.ctypes.data_as(C.POINTER(C.c_float)), int(tab.shape[1]), scale, mode, int(depth), ch,
+                                      out[ch].ctypes.data_as(C.POINTER(C.c_uint16))))
     return out
 
 

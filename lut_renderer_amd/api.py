@@ -22,9 +22,9 @@ from pathlib import Path
 from typing import Dict, Optional, Sequence, Tuple
 
 from .cdl import as_cdl
-from .cube import CubeLut, read_cube, read_lut
+from .cube import CubeLut, as_lut1d, read_cube, read_lut, read_lut1d
 from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc, check_container_options,
-                      check_dual_options, check_lut2, check_premul_options, packed_frame_width, parse_packed_yuv_fmt,
+                      check_dual_options, check_lut1d_options, check_lut2, check_premul_options, packed_frame_width, parse_packed_yuv_fmt,
                       parse_pix_fmt, parse_rgb_source, parse_semi_fmt, parse_size, parse_v210_fmt, premul_to_yuv,
                       refuse_alpha_resize, source_bit_depth, v210_frame_width, yuv_side)
 from .params import ProcessingParams, VideoInfo
@@ -34,7 +34,7 @@ from .plan import LutPlan, output_color_tags, resolve_lut_plan
 #: would reject the filtergraph.  The engine mirrors that as an error.
 _ENGINE_INTERP = ("nearest", "trilinear", "tetrahedral", "pyramid", "prism")
 
-_lut_cache: Dict[Tuple[str, float, int], CubeLut] = {}
+_lut_cache: Dict[tuple, object] = {}
 # engines apply_lut creates for itself, kept per device tuple: a context holds a stream, the device lattice and the
 # kernels' work queue, and the reference calls the path once per task, not once per frame
 _engine_cache: Dict[Tuple[int, ...], object] = {}
@@ -69,13 +69,14 @@ import atexit  # noqa: E402
 atexit.register(close_cached_engines)
 
 
-def _cached_cube(path: Path) -> CubeLut:
+def _cached_cube(path: Path, reader=read_lut) -> CubeLut:
+    """The parsed file, kept per (path, mtime, size); `reader` = `read_lut1d` for a 1D LUT file (a `Lut1D`; a path names one kind)."""
     st = path.stat()
-    key = (str(path), st.st_mtime, st.st_size)
+    key = (str(path), st.st_mtime, st.st_size) if reader is read_lut else (str(path), st.st_mtime, st.st_size, "1d")
     with _cache_lock:
         lut = _lut_cache.get(key)
     if lut is None:
-        lut = read_lut(path)                   # parsed outside the lock: two tasks may parse two files at once
+        lut = reader(path)                     # parsed outside the lock: two tasks may parse two files at once
         with _cache_lock:
             if len(_lut_cache) >= 16:          # up to 16 concurrent tasks (task_manager.py:229-235), each with its own LUT
                 _lut_cache.clear()
@@ -214,7 +215,8 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               zscale_dither: str = "none", out: Optional[Sequence] = None, engine=None,
               devices: Sequence[int] = (0,), precision: str = "strict", chroma_loc: Optional[str] = None,
               resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
-              cube2=None, interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None, cdl_id: Optional[str] = None):
+              cube2=None, interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None, cdl_id: Optional[str] = None,
+              lut1d=None, interp1d: str = "linear"):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -285,7 +287,14 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     the per-clip colour decision in front of the show LUT).  Planar YUV on both sides (yuva* with straight alpha included), a
     LutEngineGroup row-shards it, always strict arithmetic; the identity CDL gives the bits of the call without it.  No LUT with
     a .csp prelut, dither, chroma_loc, resolution, second output, second LUT, premultiplied alpha, RGB / float / semi-planar /
-    packed / v210 side: each is a ValueError naming it."""
+    packed / v210 side: each is a ValueError naming it.
+
+    `lut1d` (a `cube.Lut1D`, or the path of a .cube file with LUT_1D_SIZE) applies a 1D LUT to the integer RGB ahead of `cube`, in
+    the same pass (ffmpeg's `lut1d=file=A,lut3d=file=B`), with lut1d's mode `interp1d` (nearest | linear | cosine
+    | cubic | spline).  `cube=None` together with `lut1d` is lut1d alone.  Planar YUV on both sides (yuva* with straight alpha
+    included), a LutEngineGroup row-shards it, always strict arithmetic; the identity 1D LUT gives the bits of the call without
+    it.  No dither, chroma_loc, resolution, CDL, second LUT, second output, premultiplied alpha, RGB / float / semi-planar /
+    packed / v210 side: each is a ValueError naming it.  Without `lut1d` the function is unchanged."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -333,6 +342,12 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         check_premul_options(kw["pix_fmt"], kw["out_pix_fmt"], dither=kw["dither"], chroma_loc=chroma_loc, out_size=out_size,
                              range_src=kw.get("range_src", "tv"), range_in=kw.get("range_in"), lut_depth=kw.get("lut_depth"),
                              out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None)
+    if lut1d is not None:
+        check_lut1d_options(kw["pix_fmt"], kw["out_pix_fmt"], interp1d=interp1d, dither=kw["dither"], chroma_loc=chroma_loc,
+                            out_size=out_size, alpha_mode=alpha_mode, out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None,
+                            cdl=cdl is not None)
+        # (a file is parsed once and kept, like `cube`: the same object the next time, so the device table stands)
+        lut1d = _cached_cube(Path(lut1d), read_lut1d) if isinstance(lut1d, (str, Path)) and Path(lut1d).is_file() else as_lut1d(lut1d)
     if cdl is None and cdl_id is not None:
         raise ValueError("cdl_id names a correction inside a CDL file: it needs cdl")
     if cdl is not None:
@@ -386,7 +401,15 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
             eng._applied_lut2 = lut2
         if eng.precision != precision:
             eng.set_precision(precision)
-        if float_out:
+        if lut1d is not None:
+            held = eng._applied_lut1d                            # the same parsed 1D LUT and mode as last time: the table stands
+            if not (held is not None and held[0] is lut1d and held[1] == interp1d):
+                eng.set_lut1d(lut1d, interp1d)                   # (set_lut1d itself clears the marker)
+                eng._applied_lut1d = (lut1d, interp1d)
+            # (cube=None with a 1D LUT is lut1d alone, whatever lattice the engine holds)
+            kw1 = {k: v for k, v in kw.items() if k != "dither"}
+            result = eng.apply_yuv_lut1d(planes, out, **dict(kw1, interp=kw1["interp"] if cube is not None else None))
+        elif float_out:
             n_out = parse_rgb_source(kw["out_pix_fmt"]).nplanes
             result = eng.apply_rgb_float(planes[:n_out], out, interp=kw["interp"], alpha_mode=kw.get("alpha_mode", "straight"))
         elif cube2 is not None:

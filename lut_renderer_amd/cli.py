@@ -20,8 +20,8 @@ import signal
 import sys
 import time
 
-from .formats import (check_cdl_options, check_chroma_loc, check_container_options, check_lut2, check_premul_options, parse_size,
-                      refuse_alpha_resize, source_bit_depth)
+from .formats import (check_cdl_options, check_chroma_loc, check_container_options, check_lut1d_options, check_lut2,
+                      check_premul_options, parse_size, refuse_alpha_resize, source_bit_depth)
 
 
 def _hms(seconds: float) -> str:
@@ -49,7 +49,7 @@ def build_parser() -> argparse.ArgumentParser:
                     help="planar YUV (yuva* too: four planes, alpha last, kept unless --out-pix-fmt has none), semi-planar YUV (nv12, nv21, nv16, p010le .. p216le), packed 4:2:2 YUV (yuyv422, uyvy422, yvyu422, y210le, y212le, y216le), v210 (10-bit 4:2:2 in 32-bit words, rows of 128 * ceil(w / 48) bytes; in FFmpeg a codec / FourCC name, not a pix_fmt: its bytes are what `-c:v v210 -f rawvideo` writes), or an RGB source (gbrp* / gbrap* / rgb24, bgr24, rgba .., rgb48le, rgba64le) with a YUV --out-pix-fmt, "
                          "or float RGB (gbrpf32le / gbrapf32le): float out without --out-pix-fmt, else a YUV one")
     ap.add_argument("--out-pix-fmt", default=None)
-    ap.add_argument("--cube", required=True)
+    ap.add_argument("--cube", default=None, help="the 3D LUT; required unless --lut1d is given (lut1d alone)")
     ap.add_argument("--interp", default="tetrahedral")
     ap.add_argument("--input-matrix", default="auto")
     ap.add_argument("--output-tags", default="bt709")
@@ -93,6 +93,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--cdl-sop", default=None, metavar="\"S S S O O O P P P\"",
                     help="the CDL as literal values instead of a file: slope R G B, offset R G B, power R G B")
     ap.add_argument("--cdl-sat", default=None, type=float, metavar="X", help="the CDL's saturation as a literal value (default 1)")
+    ap.add_argument("--lut1d", default=None, metavar="PATH",
+                    help="engine setting: a 1D LUT (.cube with LUT_1D_SIZE) applied to the RGB ahead of --cube in the same pass "
+                         "(DESIGN.md 3.20; ffmpeg's lut1d=A,lut3d=B), or alone without --cube: planar YUV on both sides, no dither, "
+                         "--chroma-loc, --out-size, --cdl, --cube2, --second-output or --alpha-mode premultiplied")
+    ap.add_argument("--interp1d", default="linear", metavar="MODE",
+                    help="interpolation mode of --lut1d: nearest | linear | cosine | cubic | spline (default linear)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("-y", action="store_true", help="overwrite the output (ffmpeg's -y)")
@@ -126,7 +132,10 @@ def plan_from_args(args):
                               lut_output_tags=args.output_tags, zscale_dither=args.zscale_dither)
     info = VideoInfo(width=w, height=h, pix_fmt=args.pix_fmt, bit_depth=source_bit_depth(args.pix_fmt),
                      colorspace=args.colorspace, color_range=args.color_range)
-    plan = resolve_lut_plan(params, args.cube, info)
+    lut1d = getattr(args, "lut1d", None)
+    if args.cube is None and lut1d is None:
+        raise ValueError("--cube is required unless --lut1d is given")
+    plan = resolve_lut_plan(params, args.cube if args.cube is not None else "engine.cube", info)
     alpha_mode = getattr(args, "alpha_mode", None) or "straight"
     kw = engine_call_for(plan, args.pix_fmt, args.out_pix_fmt, alpha_mode)
     from .api import is_float_out_call
@@ -138,6 +147,15 @@ def plan_from_args(args):
                              range_in=kw.get("range_in"), lut_depth=kw.get("lut_depth"),
                              out2_pix_fmt=getattr(args, "second_pix_fmt", None), lut2=getattr(args, "cube2", None) is not None)
     cdl = cdl_from_args(args)
+    if lut1d is not None:
+        check_lut1d_options(kw["pix_fmt"], kw["out_pix_fmt"], interp1d=getattr(args, "interp1d", None) or "linear",
+                            chroma_loc=getattr(args, "chroma_loc", None),
+                            dither="error_diffusion" if args.zscale_dither == "error_diffusion" else engine_dither or "none",
+                            out_size=getattr(args, "out_size", None), alpha_mode=alpha_mode,
+                            out2_pix_fmt=getattr(args, "second_pix_fmt", None), lut2=getattr(args, "cube2", None) is not None,
+                            cdl=cdl is not None)
+        if args.cube is None:
+            kw["interp"] = None                               # lut1d alone
     if cdl is not None:
         prelut = False
         if os.path.isfile(args.cube):                         # (a LUT that is not there yet is met again where it is loaded)
@@ -194,7 +212,10 @@ def plan_from_args(args):
 
 
 def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.cube is None and args.lut1d is None:
+        ap.error("the following arguments are required: --cube (or --lut1d for a 1D LUT alone)")
 
     stop = {"flag": False}
     signal.signal(signal.SIGTERM, lambda *_: stop.__setitem__("flag", True))
@@ -212,7 +233,7 @@ def main(argv=None) -> int:
         second = args.second_output
         if second is not None and os.path.isfile(second) and not args.y:
             raise FileExistsError(f"{second} exists (pass -y to overwrite)")
-        from .cube import read_lut
+        from .cube import read_lut, read_lut1d
         from .engine import LutEngine
         from .stream import HostPipeline
 
@@ -220,13 +241,16 @@ def main(argv=None) -> int:
         check_lut2(lut2)
         eng = LutEngine(args.device)
         eng.set_precision(args.precision)
-        eng.set_lut(read_lut(args.cube))
+        if args.cube is not None:
+            eng.set_lut(read_lut(args.cube))
         if lut2 is not None:
             eng.set_lut2(lut2)
+        if args.lut1d is not None:
+            eng.set_lut1d(read_lut1d(args.lut1d), args.interp1d)
         pix_fmt, out_fmt = kw.pop("pix_fmt"), kw.pop("out_pix_fmt")
         second_fmt = kw.pop("out2_pix_fmt", None)
         pipe = HostPipeline(eng, pix_fmt, w, h, batch=args.batch, out_pix_fmt=out_fmt, out_size=args.out_size,
-                            second_pix_fmt=second_fmt, chain=lut2 is not None, **kw)
+                            second_pix_fmt=second_fmt, chain=lut2 is not None, lut1d=args.lut1d is not None, **kw)
         fb = pipe.fin.frame_bytes
         if piped_in:
             total = None if args.duration is None else max(1, int(round(args.duration * args.fps)))

@@ -19,8 +19,8 @@ from dataclasses import dataclass, field
 from pathlib import Path
 from typing import List, Optional, Tuple
 
-from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options, check_premul_options,
-                      parse_rgb_source, premul_to_yuv)
+from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options, check_lut1d_options,
+                      check_premul_options, parse_rgb_source, premul_to_yuv)
 from .params import ProcessingParams, Task, VideoInfo
 from .plan import LutPlan, output_color_tags, resolve_lut_plan, resolve_pix_fmt
 
@@ -256,7 +256,8 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                    gpu_resize: bool = False, second_output: Optional[Path] = None,
                    second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
                    cube2: Optional[Path] = None, interp2: Optional[str] = None, alpha_mode: str = "straight",
-                   cdl=None, cdl_id: Optional[str] = None) -> List[str]:
+                   cdl=None, cdl_id: Optional[str] = None, lut1d: Optional[Path] = None,
+                   interp1d: Optional[str] = None) -> List[str]:
     """`build_command`'s twin for the LUT stage alone: the argv of the ENGINE CLI (`python -m lut_renderer_amd.cli`)
     that applies exactly the chain `build_command` would put into `-vf` -- the same `LutPlan`, rendered as CLI options
     instead of as a filter string (ffmpeg.py:195-247, :287-310).  `source` / `output` are rawvideo files (or `-`) in
@@ -281,7 +282,11 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     `cdl` puts an ASC CDL in front of the LUT in the same pass, an engine setting as well: the path of a .cc / .ccc
     / .cdl file (`--cdl`, with `cdl_id` as `--cdl-id`) or a `cdl.Cdl` (`--cdl-sop`, and `--cdl-sat` unless it is 1); rendered only
     when given.  Planar YUV on both sides; not with dither, `chroma_loc`, `gpu_resize`, a second output, a second LUT or
-    premultiplied alpha.  A LUT with a .csp prelut is refused where the LUT is loaded."""
+    premultiplied alpha.  A LUT with a .csp prelut is refused where the LUT is loaded.
+    `lut1d` / `interp1d` put a 1D LUT file in front of the LUT in the same pass (`--lut1d`, and `--interp1d` when
+    given: ffmpeg's `lut1d=file=A,lut3d=file=B`); rendered only when given.  Planar YUV on both sides; not with dither,
+    `chroma_loc`, `gpu_resize`, a CDL, a second LUT, a second output or premultiplied alpha.  `interp1d` without `lut1d` is a
+    ValueError."""
     import sys as _sys
     premul = check_alpha_mode(alpha_mode)
     if precision not in ("strict", "fast", "fma32"):
@@ -396,6 +401,17 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                 cmd += ["--cdl-id", str(cdl_id)]
         else:
             raise TypeError(f"cdl must be a Cdl or the path of a .cc / .ccc / .cdl file, not {type(cdl).__name__}")
+    if lut1d is None and interp1d is not None:
+        raise ValueError("interp1d is the mode of the 1D LUT: it needs lut1d")
+    if lut1d is not None:
+        if not isinstance(lut1d, (str, Path)):
+            raise TypeError(f"lut1d must be the path of a 1D .cube file, not {type(lut1d).__name__}")
+        check_lut1d_options(str(source_info.pix_fmt).replace("yuvj", "yuv"), pix_fmt or None, interp1d=interp1d or "linear",
+                            dither=dither, chroma_loc=chroma_loc, out_size=params.resolution if "--out-size" in cmd else None,
+                            alpha_mode=alpha_mode, out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None, cdl=cdl is not None)
+        cmd += ["--lut1d", str(lut1d)]
+        if interp1d is not None:
+            cmd += ["--interp1d", interp1d]
     return cmd
 
 

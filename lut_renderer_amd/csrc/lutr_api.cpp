@@ -339,6 +339,19 @@ struct lutr_ctx {
     size_t cdl_cap = 0;              // floats allocated
     int cdl_depth = 0;
     float cdl_key[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // the 1D LUT of lutr_apply_yuv_lut1d / lutr_apply_planar_rgb_lut1d (lutr_ctx_set_lut1d): the host copy as it
+    // was given (3 x l1d_size floats; size 0: none set), and per depth a device table of 3 x 2^depth codes (l1d_tab[depth - 8]),
+    // built at first use.  l1d_gen counts the calls of lutr_ctx_set_lut1d; a device table is current when it carries that number
+    std::vector<float> l1d;
+    int l1d_size = 0;
+    float l1d_scale[3] = {1.f, 1.f, 1.f};
+    int l1d_interp = LUTR_INTERP1D_LINEAR;
+    unsigned long long l1d_gen = 0;
+    struct L1dTable {
+        uint16_t *dev = nullptr;         // 3 x 2^depth entries, allocated once per depth and kept
+        unsigned long long gen = 0;      // the l1d_gen its contents were built from (0: never)
+    };
+    L1dTable l1d_tab[9];
 };
 
 // Wait for every peer copy that reads this context's lattice, then forget the events.
@@ -486,6 +499,8 @@ void lutr_ctx_destroy(lutr_ctx *c)
     if (c->fscratch) (void)hipFree(c->fscratch);
     if (c->bn_tab) (void)hipFree(c->bn_tab);
     if (c->cdl_tab) (void)hipFree(c->cdl_tab);
+    for (auto &t : c->l1d_tab)
+        if (t.dev) (void)hipFree(t.dev);
     for (auto &t : c->rz_tables) (void)hipFree(t.dev);
     if (c->queue) (void)hipFree(c->queue);
     if (c->done) (void)hipEventDestroy(c->done);
@@ -1499,6 +1514,122 @@ int lutr_apply_yuv_cdl(lutr_ctx *c, const lutr_yuv_params *p, int interp, const 
     if (const int rc = cdl_device_table(c, *cdl, p->lut_depth, &C)) return rc;
     fill_planes(&P, src, dst);
     return finish_launch(c, launch_yuv_cdl(c->stream, c->variant, L, C, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, interp));
+}
+
+// ---- 1D LUT alone or in front of lut3d
+int lutr_ctx_set_lut1d(lutr_ctx *c, const float *lut, int size, const float scale[3], int interp1d)
+{
+    if (!c) { set_error("null context"); return LUTR_EINVAL; }
+    if (!lut || size == 0) {             // remove it; the device tables stay allocated and go stale with the generation
+        c->l1d.clear();
+        c->l1d_size = 0;
+        c->l1d_gen++;
+        return LUTR_OK;
+    }
+    if (!scale) { set_error("null argument"); return LUTR_EINVAL; }
+    // the table builder's own checks (size, mode, scale, finite nodes), on a depth-8 table of every channel
+    uint16_t probe[256];
+    for (int ch = 0; ch < 3; ch++)
+        if (const int rc = lutr_lut1d_table(lut, size, scale, interp1d, 8, ch, probe)) return rc;
+    c->l1d.assign(lut, lut + (size_t)3 * size);
+    c->l1d_size = size;
+    std::memcpy(c->l1d_scale, scale, sizeof(c->l1d_scale));
+    c->l1d_interp = interp1d;
+    c->l1d_gen++;
+    return LUTR_OK;
+}
+
+// The device table of the context's 1D LUT at `depth`, rebuilt when lutr_ctx_set_lut1d has run since it was built.  The kernel of
+// the previous call may still be reading the old contents, so the copy goes on the context's stream, behind it;
+// hipMemcpyWithStream returns when the copy is done, so the host table (a local) is never freed under a pending copy.
+static int l1d_device_table(lutr_ctx *c, int depth, L1dConsts *C)
+{
+    if (!c->l1d_size) { set_error("no 1D LUT set on this context (call lutr_ctx_set_lut1d first)"); return LUTR_EINVAL; }
+    const size_t ne = (size_t)1 << depth, n = 3 * ne;
+    lutr_ctx::L1dTable &t = c->l1d_tab[depth - 8];
+    if (!t.dev) {
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, n * sizeof(uint16_t));
+        if (e != hipSuccess) { set_error("hipMalloc(1D LUT table): %s", hipGetErrorString(e)); return LUTR_ENOMEM; }
+        t.dev = (uint16_t *)p;
+        t.gen = 0;
+    }
+    if (t.gen != c->l1d_gen) {
+        std::vector<uint16_t> host(n);
+        for (int ch = 0; ch < 3; ch++)
+            if (const int rc = lutr_lut1d_table(c->l1d.data(), c->l1d_size, c->l1d_scale, c->l1d_interp, depth, ch, &host[(size_t)ch * ne]))
+                return rc;
+        t.gen = 0;
+        HIP_TRY(hipMemcpyWithStream(t.dev, host.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+        t.gen = c->l1d_gen;
+    }
+    C->tab = t.dev;
+    C->stride = (int)ne;
+    return LUTR_OK;
+}
+
+// lutr_apply_yuv_cdl's pass with the 1D table in the CDL's place; interp LUTR_INTERP_NONE leaves lut3d out.
+int lutr_apply_yuv_lut1d(lutr_ctx *c, const lutr_yuv_params *p, int interp, int w, int h, int nframes, const lutr_planes *src,
+                         const lutr_planes *dst, int row0, int rows)
+{
+    int rc = check_common(c, interp, LUTR_INTERP_NONE, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!c->l1d_size) { set_error("no 1D LUT set on this context (call lutr_ctx_set_lut1d first)"); return LUTR_EINVAL; }
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    YuvConsts K;
+    rc = make_yuv_consts_xsub(*p, &K);
+    if (rc) return rc;
+    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
+    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
+    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
+    if (p->lut_depth < 8 || p->lut_depth > 16) { set_error("lut1d: LUT depth %d outside 8..16", p->lut_depth); return LUTR_EINVAL; }
+    if (const int rc = check_row_blocks(row0, rows, h, 1 << std::max(icsy, ocsy), "union chroma block height")) return rc;
+    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for the lut1d pass"); return LUTR_EINVAL; }
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    if (const int rc = check_planes_set(src, dst)) return rc;
+    const struct { const char *side; const lutr_planes *pl; int depth; } sides[2] = {{"source", src, din}, {"destination", dst, dout}};
+    for (const auto &s : sides)
+        for (int i = 0; i < 3; i++)
+            if (s.depth > 8 && !check_aligned(s.pl->data[i], s.pl->stride[i], s.pl->frame_stride[i], nframes, 1)) {
+                set_error("%s plane %d: 16-bit planes need 2-byte aligned rows", s.side, i);
+                return LUTR_EINVAL;
+            }
+    Span ss[3], ds[3];
+    planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
+    planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
+    if (const int rc = check_disjoint("the lut1d pass", true, ss, 3, ds, 3)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
+    LutConsts L{}; L1dConsts C; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    if (interp != LUTR_INTERP_NONE)
+        if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
+    if (const int rc = l1d_device_table(c, p->lut_depth, &C)) return rc;
+    fill_planes(&P, src, dst);
+    return finish_launch(c, launch_yuv_l1d(c->stream, c->variant, L, C, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, interp));
+}
+
+int lutr_apply_planar_rgb_lut1d(lutr_ctx *c, int depth, int w, int h, int nframes, const lutr_planes *src, const lutr_planes *dst,
+                                int row0, int rows)
+{
+    int rc = check_common(c, LUTR_INTERP_NONE, LUTR_INTERP_NONE, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!c->l1d_size) { set_error("no 1D LUT set on this context (call lutr_ctx_set_lut1d first)"); return LUTR_EINVAL; }
+    if (depth < 8 || depth > 16) { set_error("unsupported depth %d", depth); return LUTR_EINVAL; }
+    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for the lut1d pass"); return LUTR_EINVAL; }
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    if (const int rc = check_planes_set(src, dst)) return rc;
+    if (depth > 8)
+        for (int i = 0; i < 3; i++)
+            if (!check_aligned(src->data[i], src->stride[i], src->frame_stride[i], nframes, 1) ||
+                !check_aligned(dst->data[i], dst->stride[i], dst->frame_stride[i], nframes, 1)) {
+                set_error("plane %d: 16-bit planes need 2-byte aligned rows", i);
+                return LUTR_EINVAL;
+            }
+    HIP_TRY(hipSetDevice(c->device));
+    L1dConsts C; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = l1d_device_table(c, depth, &C)) return rc;
+    fill_planes(&P, src, dst);
+    return finish_launch(c, launch_rgb_l1d(c->stream, c->variant, C, P, G, depth));
 }
 
 // What a semi-planar and a packed side share: `noun` ("layout" | "packing") names the struct in the messages; the shift against

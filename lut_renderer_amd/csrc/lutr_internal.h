@@ -164,6 +164,27 @@ const char *launch_yuv_cdl(hipStream_t st, int variant, const LutConsts &L, cons
 LUTR_CD_DECL(w00) LUTR_CD_DECL(w11) LUTR_CD_DECL(w10)
 #undef LUTR_CD_DECL
 
+// 1D LUT ahead of lut3d (lutr_l1d.hip): the per-code table (device; the output code of integer code i of channel
+// c is tab[c * stride + i], stride = 2^lut_depth)
+struct L1dConsts {
+    const uint16_t *tab;
+    int stride;
+};
+// launch_yuv_cdl's call with the 1D table in the CDL's place; interp LUTR_INTERP_NONE = lut1d alone (L is not read).  nullptr =
+// the variant cannot take the call (vec_lds always; vec_global on layouts the vector kernel cannot take)
+const char *launch_yuv_l1d(hipStream_t st, int variant, const LutConsts &L, const L1dConsts &C, const YuvConsts &K, const PlaneSet &P,
+                           const FrameGeom &G, int din, int dout, int icsx, int icsy, int ocsx, int ocsy, int interp);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>); lds: stage the table per workgroup.
+// nullptr = not a mode it has
+#define LUTR_L1_DECL(tag) \
+    const char *launch_yuv_l1d_vec_##tag(hipStream_t st, const LutConsts &L, const L1dConsts &C, const YuvConsts &K, \
+                                         const PlaneSet &P, const FrameGeom &G, int icsx, int icsy, int ocsx, int ocsy, int interp, \
+                                         bool lds);
+LUTR_L1_DECL(w00) LUTR_L1_DECL(w11) LUTR_L1_DECL(w10)
+#undef LUTR_L1_DECL
+// lut1d alone on planar RGB: P in gbrp order (G, B, R), planes of `depth` bits.  nullptr as above
+const char *launch_rgb_l1d(hipStream_t st, int variant, const L1dConsts &C, const PlaneSet &P, const FrameGeom &G, int depth);
+
 // blue-noise dither in the output stage (lutr_bnd.hip): launch_yuv_xsub's call for any pair of layouts, the equal
 // ones included; bn = the 64 x 64 table of offsets (device).  nullptr = the variant cannot take the call (vec_lds always;
 // vec_global on layouts the vector kernel cannot take)

@@ -52,6 +52,75 @@ class CubeLut:
             raise ValueError(f"table shape {self.table.shape} does not match n={self.n}")
 
 
+@dataclass
+class Lut1D:
+    """A parsed 1D LUT (a .cube file with LUT_1D_SIZE): `table[c, i]`, c = R, G, B."""
+    table: np.ndarray      # float32[3, n]
+    scale: np.ndarray      # float32[3] = clip(1/(max-min), 0, 1) of DOMAIN_MIN / DOMAIN_MAX or LUT_1D_INPUT_RANGE
+
+    def __post_init__(self) -> None:
+        self.table = np.ascontiguousarray(self.table, dtype=np.float32)
+        self.scale = np.ascontiguousarray(self.scale, dtype=np.float32)
+        if self.table.ndim != 2 or self.table.shape[0] != 3 or not 2 <= self.table.shape[1] <= 65536:
+            raise ValueError(f"1D LUT table shape {self.table.shape}, expected (3, n) with 2 <= n <= 65536")
+        if self.scale.shape != (3,):
+            raise ValueError(f"1D LUT scale shape {self.scale.shape}, expected (3,)")
+
+    @property
+    def n(self) -> int:
+        return int(self.table.shape[1])
+
+    @classmethod
+    def identity(cls, n: int) -> "Lut1D":
+        """lut[c][i] = i / (n - 1): with n = 2^depth and linear interpolation, the table T[k] = k."""
+        ax = (np.arange(n, dtype=np.float64) / (n - 1)).astype(np.float32)
+        return cls(np.stack([ax, ax, ax]), np.ones(3, np.float32))
+
+
+def read_lut1d(path) -> Lut1D:
+    """Parse a 1D .cube file (LUT_1D_SIZE 2..65536) with liblutr (FFmpeg's parse_cube_1d semantics).  Raises LutrError; a file
+    that carries a 3D LUT as well is refused.  `read_lut` keeps refusing 1D files."""
+    lib = _native.load()
+    lut = C.POINTER(C.c_float)()
+    n = C.c_int(0)
+    scale = (C.c_float * 3)()
+    _native.check(lib.lutr_lut1d_parse(str(path).encode(), C.byref(lut), C.byref(n), scale))
+    try:
+        table = np.ctypeslib.as_array(lut, shape=(3 * n.value,)).astype(np.float32, copy=True)
+    finally:
+        lib.lutr_cube_free(lut)
+    return Lut1D(table.reshape(3, n.value), np.array(list(scale), dtype=np.float32))
+
+
+def as_lut1d(lut1d) -> Optional[Lut1D]:
+    """What the public entry points make of their `lut1d` argument: None, a Lut1D, or the path of a 1D .cube file."""
+    if lut1d is None or isinstance(lut1d, Lut1D):
+        return lut1d
+    if isinstance(lut1d, (str, Path)):
+        return read_lut1d(lut1d)
+    raise TypeError(f"lut1d must be a Lut1D or the path of a 1D .cube file, not {type(lut1d).__name__}")
+
+
+def write_lut1d(path, table: np.ndarray, *, title: Optional[str] = None, domain_min: Optional[Sequence[float]] = None,
+                domain_max: Optional[Sequence[float]] = None, input_range: Optional[Sequence[float]] = None,
+                fmt: str = "%.9g") -> Path:
+    """Write `table[c, i]` (c = R, G, B) as a 1D .cube."""
+    table = np.asarray(table, dtype=np.float32)
+    path = Path(path)
+    with open(path, "w") as f:
+        if title is not None:
+            f.write(f'TITLE "{title}"\n')
+        f.write(f"LUT_1D_SIZE {table.shape[1]}\n")
+        if domain_min is not None:
+            f.write("DOMAIN_MIN " + " ".join(fmt % v for v in domain_min) + "\n")
+        if domain_max is not None:
+            f.write("DOMAIN_MAX " + " ".join(fmt % v for v in domain_max) + "\n")
+        if input_range is not None:
+            f.write("LUT_1D_INPUT_RANGE " + " ".join(fmt % v for v in input_range) + "\n")
+        np.savetxt(f, table.T, fmt=fmt)
+    return path
+
+
 def read_cube(path) -> CubeLut:
     """Parse `path` with liblutr (FFmpeg parse_cube semantics).  Raises LutrError."""
     return _read_with("lutr_cube_parse", path)

@@ -20,10 +20,11 @@ import torch
 
 from . import _native
 from .cdl import Cdl
-from .cube import CubeLut, read_cube, read_lut
+from .cube import CubeLut, Lut1D, read_cube, read_lut, read_lut1d
 # (the formats and the checks of names and options live in formats.py; the names callers have always imported from here stay)
 from .formats import (_ALPHA_RESIZE, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, V210Fmt, chain_interp, chain_side,  # noqa: F401
                       changes_subsampling, check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc,
+                      check_lut1d_options,
                       check_container_options,
                       check_dual_options, check_lut2, check_packed_options, check_premul_options, check_semi_options,
                       chroma_loc_code, dual_side, has_prologue, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt,
@@ -125,6 +126,7 @@ def _byte_range(t: torch.Tensor) -> Tuple[int, int]:
 
 
 _CDL_IN_PLACE = "the CDL pass cannot run in place: destination planes must not overlap the source planes"
+_LUT1D_IN_PLACE = "the lut1d pass cannot run in place: destination planes must not overlap the source planes"
 _RESIZE_IN_PLACE = "a resize cannot run in place: destination planes must not overlap the source planes"
 _RGB2YUV_IN_PLACE = "RGB -> YUV cannot run in place: destination planes must not overlap the source"
 
@@ -330,6 +332,8 @@ class LutEngine:
         self._applied_lut = None          # the CubeLut object apply_lut uploaded last (its upload-skipping shortcut)
         self._applied_lut2 = None         # ... and the second LUT of apply_lut(cube2=)
         self.n2 = 0
+        self._applied_lut1d = None        # ... and the (1D LUT, mode) of apply_lut(lut1d=)
+        self.n1d = 0                      # rows of the 1D LUT set_lut1d holds (0: none)
         # grow-only plane caches of _scratch, (key, [3 planes]) per slot: "rz" = the source-size output of the LUT ahead of a
         # resize, "fr" = the 8-bit YUV frames between the two stages of a full-range RGB source
         self._scratch_slots = {}
@@ -404,6 +408,30 @@ class LutEngine:
         lut = read_lut(path)
         self.set_lut2(lut)
         return lut
+
+    def set_lut1d(self, lut1d: Optional[Lut1D], interp: str = "linear") -> None:
+        """The 1D LUT of `apply_yuv_lut1d` / `apply_rgb_lut1d` (a `cube.Lut1D`) and lut1d's mode for it (nearest |
+        linear | cosine | cubic | spline), or None to remove it.  It lives beside the lattices: `set_lut` / `load_cube` / `set_lut2`
+        leave it alone and no other call reads it."""
+        mode = _native.interp1d_code(interp)
+        if lut1d is not None and not isinstance(lut1d, Lut1D):
+            raise TypeError(f"lut1d must be a lut_renderer_amd.cube.Lut1D, not {type(lut1d).__name__}")
+        with self._lock:
+            self._applied_lut1d = None    # any direct upload invalidates apply_lut's "same 1D LUT as last time" shortcut
+            if lut1d is None:
+                _native.check(self._lib.lutr_ctx_set_lut1d(self._ctx, None, 0, None, mode))
+                self.n1d = 0
+                return
+            table = np.ascontiguousarray(lut1d.table, dtype=np.float32)
+            scale = (C.c_float * 3)(*[float(v) for v in lut1d.scale])
+            _native.check(self._lib.lutr_ctx_set_lut1d(
+                self._ctx, table.ctypes.data_as(C.POINTER(C.c_float)), int(table.shape[1]), scale, mode))
+            self.n1d = int(table.shape[1])
+
+    def load_lut1d(self, path, interp: str = "linear") -> Lut1D:
+        lut1d = read_lut1d(path)
+        self.set_lut1d(lut1d, interp)
+        return lut1d
 
     def lattice_tensor(self) -> torch.Tensor:
         """The device lattice viewed as a float32 tensor [(n+1)^3 * 4] (no copy)."""
@@ -821,6 +849,92 @@ class LutEngine:
             else:
                 _native.check(self._lib.lutr_apply_yuv(
                     self._ctx, C.byref(p), _native.INTERP[interp], w, h, nf, C.byref(s), C.byref(d), row0, rows))
+        return dst
+
+    def apply_yuv_lut1d(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str,
+                        out_pix_fmt: Optional[str] = None, interp: Optional[str] = "tetrahedral", matrix_in: str = "bt709",
+                        matrix_out: Optional[str] = None, range_src: str = "tv", range_in: Optional[str] = None,
+                        range_out: str = "tv", lut_depth: Optional[int] = None, row0: int = 0, rows: Optional[int] = None,
+                        **other):
+        """`apply_yuv` with the engine's 1D LUT (`set_lut1d`) on the integer RGB ahead of lut3d, in the same pass
+        (lutr_apply_yuv_lut1d; ffmpeg's `lut1d=file=A,lut3d=file=B`): planar YUV on both sides (yuva* with straight alpha
+        included), any layout pair at 8..16 bit, the full-range prologue, a .csp prelut on the 3D LUT, row0 / rows on the union
+        block, strict arithmetic, not in place.  `interp` is lut3d's mode, or None for lut1d alone (no 3D LUT needed).  The
+        identity 1D LUT gives the bits of `apply_yuv(out_pix_fmt=...)`.  No dither, chroma_loc, out_size, cdl, premultiplied alpha,
+        second LUT or second output, and no RGB / float / semi-planar / packed / v210 side: each is a ValueError naming it."""
+        for k in other:
+            if k not in ("dither", "chroma_loc", "out_size", "alpha_mode", "cdl", "out2_pix_fmt", "cube2", "lut2"):
+                raise TypeError(f"apply_yuv_lut1d() got an unexpected keyword argument '{k}'")
+        lut2 = other.get("cube2") is not None or bool(other.get("lut2"))
+        check_lut1d_options(pix_fmt, out_pix_fmt, dither=other.get("dither", "none"), chroma_loc=other.get("chroma_loc"),
+                            out_size=other.get("out_size"), alpha_mode=other.get("alpha_mode", "straight"),
+                            out2_pix_fmt=other.get("out2_pix_fmt"), lut2=lut2, cdl=other.get("cdl") is not None,
+                            loaded=bool(getattr(self, "n1d", 0)))
+        if interp is not None and interp not in _native.INTERP:
+            raise ValueError(f"lut3d has no interpolation mode '{interp}'")
+        mode = _native.INTERP_NONE if interp is None else _native.INTERP[interp]
+        fin = parse_pix_fmt(pix_fmt.replace("yuvj", "yuv"))
+        fout = parse_pix_fmt((out_pix_fmt or pix_fmt).replace("yuvj", "yuv"))
+        if fin.alpha or fout.alpha:
+            # yuva*: the colour planes through this very call under their three-plane names, then the alpha plane on the same
+            # stream, exactly as the CDL call does (DESIGN.md 3.16)
+            if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
+                raise ValueError(_PLANE_COUNT[fin.nplanes].format(fin.name))
+            h, w = src[0].shape[-2], src[0].shape[-1]
+            _check_planes(src, fin, w, h, "source")
+            if dst is None:
+                dst = _fresh_planes(fout, w, h, src[0], self.device)
+            _check_planes(dst, fout, w, h, "destination")
+            a_src = src[3] if fin.alpha and not has_prologue(fin.depth, range_src, range_in, lut_depth) else None
+            if fout.alpha:
+                _check_alpha_overlap(a_src, fin.depth, dst, fout.depth)
+            self._alpha_tail(lambda: self.apply_yuv_lut1d(
+                src[:3], dst[:3], pix_fmt=fin.colour.name, out_pix_fmt=fout.colour.name, interp=interp, matrix_in=matrix_in,
+                matrix_out=matrix_out, range_src=range_src, range_in=range_in, range_out=range_out, lut_depth=lut_depth, row0=row0,
+                rows=rows), [(fout, dst)], a_src, fin.depth, w, h, row0, rows)
+            return dst
+        p = _yuv_call_params(fin, fout, lut_depth, matrix_in, matrix_out, range_src, range_in, range_out)
+        h, w = src[0].shape[-2], src[0].shape[-1]
+        if dst is None:
+            dst = _fresh_planes(fout, w, h, src[0], self.device)
+        _check_planes(src, fin, w, h, "source")
+        _check_planes(dst, fout, w, h, "destination")
+        _check_not_in_place(src, dst, _LUT1D_IN_PLACE)
+        s, d, nf = _plane_pair(src, dst, self.device)
+        rows = h - row0 if rows is None else rows
+        with self._lock:
+            self._bind_stream()
+            _native.check(self._lib.lutr_apply_yuv_lut1d(
+                self._ctx, C.byref(p), mode, w, h, nf, C.byref(s), C.byref(d), row0, rows))
+        return dst
+
+    def apply_rgb_lut1d(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, depth: int,
+                        interp: Optional[str] = None, row0: int = 0, rows: Optional[int] = None):
+        """The engine's 1D LUT (`set_lut1d`) on planar RGB; planes in gbrp order (G, B, R), each [H,W] or [F,H,W]:
+        every sample through its channel's per-code table, a container value above 2^depth - 1 taken as that.  `dst` may be `src`
+        (in place).  `interp` = a lut3d mode runs today's `apply_rgb` in place on `dst` behind it (ffmpeg's `lut1d,lut3d`): two
+        launches on the engine's stream with no host wait in between."""
+        if not 8 <= int(depth) <= 16:
+            raise ValueError(f"unsupported depth {depth}")
+        if interp is not None and interp not in _native.INTERP:
+            raise ValueError(f"lut3d has no interpolation mode '{interp}'")
+        if not getattr(self, "n1d", 0):
+            raise ValueError("no 1D LUT is loaded: call set_lut1d / load_lut1d first, or pass lut1d")
+        if isinstance(src, torch.Tensor) or len(src) != 3:
+            raise ValueError("apply_rgb_lut1d takes three planes (G, B, R)")
+        h, w = src[0].shape[-2], src[0].shape[-1]
+        fmt = PixFmt(f"gbrp{depth}", "gbr", int(depth), 0, 0, True)
+        if dst is None:
+            dst = [torch.empty_like(t) for t in src]
+        _check_planes(src, fmt, w, h, "source")
+        _check_planes(dst, fmt, w, h, "destination")
+        s, d, nf = _plane_pair(src, dst, self.device)
+        n_rows = h - row0 if rows is None else rows
+        with self._lock:
+            self._bind_stream()
+            _native.check(self._lib.lutr_apply_planar_rgb_lut1d(self._ctx, int(depth), w, h, nf, C.byref(s), C.byref(d), row0, n_rows))
+            if interp is not None:
+                self.apply_rgb(dst, dst, depth=depth, interp=interp, row0=row0, rows=rows)
         return dst
 
     def apply_yuv_dual(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None,

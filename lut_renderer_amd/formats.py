@@ -524,6 +524,47 @@ def check_cdl_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = None,
     return fin, fout
 
 
+def check_lut1d_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = None, *, interp1d: str = "linear",
+                        dither: str = "none", chroma_loc: Optional[str] = None, out_size=None, alpha_mode: str = "straight",
+                        out2_pix_fmt: Optional[str] = None, lut2: bool = False, cdl: bool = False, loaded: bool = True,
+                        variant: Optional[str] = None) -> Tuple[PixFmt, PixFmt]:
+    """The checks every layer makes of a 1D LUT, alone or in front of the 3D LUT, before any GPU work, the one
+    copy of its refusals: planar YUV on both sides (yuva* with straight alpha included; packed RGB, float, semi-planar, packed
+    4:2:2 and v210 names refused, and an RGB source with a YUV output), a mode lut1d has (`interp1d`), no dither, chroma_loc or
+    out_size, no CDL (`cdl`), no second LUT (`lut2`), no second output (`out2_pix_fmt`), no premultiplied alpha, not the vec_lds
+    variant, and a 1D LUT to apply (`loaded`).  Returns the two parsed formats."""
+    tail = "a 1D LUT"
+    if interp1d not in _native.INTERP1D:
+        raise ValueError(f"lut1d has no interpolation mode '{interp1d}' ({' | '.join(_native.INTERP1D)})")
+    src = parse_rgb_source(pix_fmt)
+    if src is not None and parse_rgb_source(out_pix_fmt or pix_fmt) is None:
+        raise ValueError(f"an RGB source with a YUV output ('{pix_fmt}' -> '{out_pix_fmt}') is not supported with {tail}")
+    fin = _pass_side(pix_fmt, "pix_fmt", "lut1d", "both sides", True, alpha_ok=True)
+    fout = _pass_side(out_pix_fmt or pix_fmt, "out_pix_fmt", "lut1d", "both sides", True, alpha_ok=True)
+    if fin.family != "yuv" or fout.family != "yuv":
+        bad, what = (pix_fmt, "pix_fmt") if fin.family != "yuv" else (out_pix_fmt, "out_pix_fmt")
+        raise ValueError(f"the lut1d pass takes planar YUV on both sides: {what} '{bad}' is an RGB format")
+    if dither != "none":
+        raise ValueError(f"dither ('{dither}') is not supported with {tail}")
+    if chroma_loc is not None:
+        raise ValueError(f"sited chroma resampling (chroma_loc) is not supported with {tail}")
+    if out_size is not None:
+        raise ValueError(f"a resize (out_size / resolution) is not supported with {tail}")
+    if cdl:
+        raise ValueError(f"a CDL is not supported with {tail}")
+    if lut2:
+        raise ValueError(f"the two-LUT chain (a second LUT) is not supported with {tail}")
+    if out2_pix_fmt is not None:
+        raise ValueError(f"the two-output pass (out2_pix_fmt) is not supported with {tail}")
+    if alpha_mode != "straight":
+        raise ValueError(f"alpha_mode='{alpha_mode}' is not supported with {tail}")
+    if variant == "vec_lds":
+        raise ValueError(f"variant vec_lds is not supported with {tail}: there is no LDS-window kernel for the lut1d pass")
+    if not loaded:
+        raise ValueError("no 1D LUT is loaded: call set_lut1d / load_lut1d first, or pass lut1d")
+    return fin, fout
+
+
 #: how the colour planes of an alpha-carrying source stand to their alpha (DESIGN.md 3.18)
 ALPHA_MODES = ("straight", "premultiplied")
 

@@ -27,9 +27,10 @@ import numpy as np
 import torch
 
 from . import _native
-from .cube import CubeLut, read_lut
+from .cube import CubeLut, read_lut, read_lut1d
 from .engine import LutEngine, _fresh_planes, _new_planes, _yuv_out_dtype, chain_args, dual_args
-from .formats import (check_alpha_mode, check_cdl_options, check_container_options, check_lut2, check_premul_options,
+from .formats import (check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2,
+                      check_premul_options,
                       packed_frame_width, parse_pix_fmt, parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords,
                       v210_frame_width, yuv_side)
 from .shard import row_blocks
@@ -77,6 +78,7 @@ class LutEngineGroup:
         self._lock = threading.RLock()
         self._applied_lut = None
         self._applied_lut2 = None
+        self._applied_lut1d = None
         self.precision = "strict"
         self.engines: List[LutEngine] = []
         try:
@@ -302,6 +304,77 @@ class LutEngineGroup:
                 return [(dst, out, _row_ranges(fout, r0, r1))]
 
             self._shard(h, 1 << max(fin.csy, fout.csy), home, local, remote)
+            return dst
+
+    def set_lut1d(self, lut1d, interp: str = "linear") -> None:
+        """The 1D LUT of `apply_yuv_lut1d` / `apply_rgb_lut1d`, set from the host on every engine (None removes
+        it)."""
+        with self._lock:
+            self._applied_lut1d = None
+            for e in self.engines:
+                e.set_lut1d(lut1d, interp)
+
+    def load_lut1d(self, path, interp: str = "linear"):
+        lut1d = read_lut1d(path)
+        self.set_lut1d(lut1d, interp)
+        return lut1d
+
+    @property
+    def n1d(self) -> int:
+        return self.engines[0].n1d if self.engines else 0
+
+    def apply_yuv_lut1d(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str,
+                        out_pix_fmt: Optional[str] = None, **kw):
+        """`LutEngine.apply_yuv_lut1d` with the rows of every frame split over the group's devices: shards on
+        multiples of the union block height of the two layouts, as for a CDL; alpha rows go with the luma rows, no halo."""
+        with self._lock:
+            if "row0" in kw or "rows" in kw:
+                raise ValueError("the group owns the row partition")
+            lut2 = kw.get("cube2") is not None or bool(kw.get("lut2"))
+            fin, fout = check_lut1d_options(pix_fmt, out_pix_fmt, dither=kw.get("dither", "none"), chroma_loc=kw.get("chroma_loc"),
+                                            out_size=kw.get("out_size"), alpha_mode=kw.get("alpha_mode", "straight"),
+                                            out2_pix_fmt=kw.get("out2_pix_fmt"), lut2=lut2, cdl=kw.get("cdl") is not None,
+                                            loaded=bool(self.n1d))
+            h, w = src[0].shape[-2], src[0].shape[-1]
+            home = src[0].device
+            if dst is None:
+                dst = _fresh_planes(fout, w, h, src[0], home)
+            names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt)
+
+            def local(eng, r0, r1):
+                eng.apply_yuv_lut1d(src, dst, row0=r0, rows=r1 - r0, **names, **kw)
+
+            def remote(eng, r0, r1):
+                out = eng.apply_yuv_lut1d(_travel(src, _row_ranges(fin, r0, r1), eng.device), None, **names, **kw)
+                return [(dst, out, _row_ranges(fout, r0, r1))]
+
+            self._shard(h, 1 << max(fin.csy, fout.csy), home, local, remote)
+            return dst
+
+    def apply_rgb_lut1d(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, depth: int,
+                        interp: Optional[str] = None, **kw):
+        """`LutEngine.apply_rgb_lut1d` with the rows of every frame split over the group's devices (any row)."""
+        with self._lock:
+            if "row0" in kw or "rows" in kw:
+                raise ValueError("the group owns the row partition")
+            if kw:
+                raise TypeError(f"apply_rgb_lut1d() got an unexpected keyword argument '{next(iter(kw))}'")
+            if not self.n1d:
+                raise ValueError("no 1D LUT is loaded: call set_lut1d / load_lut1d first, or pass lut1d")
+            h = src[0].shape[-2]
+            home = src[0].device
+            if dst is None:
+                dst = [torch.empty_like(t) for t in src]
+
+            def local(eng, r0, r1):
+                eng.apply_rgb_lut1d(src, dst, depth=depth, interp=interp, row0=r0, rows=r1 - r0)
+
+            def remote(eng, r0, r1):
+                rng = [(r0, r1)] * 3
+                out = eng.apply_rgb_lut1d(_travel(src, rng, eng.device), None, depth=depth, interp=interp)
+                return [(dst, out, rng)]
+
+            self._shard(h, 1, home, local, remote)
             return dst
 
     def apply_rgb_to_yuv(self, src, dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: str, **kw):

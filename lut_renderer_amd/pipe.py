@@ -49,7 +49,8 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
                           precision: str = "strict", chroma_loc: Optional[str] = None, gpu_resize: bool = False,
                           engine_dither: Optional[str] = None, cube2: Optional[Path] = None,
                           interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None,
-                          cdl_id: Optional[str] = None) -> StageCommands:
+                          cdl_id: Optional[str] = None, lut1d: Optional[Path] = None,
+                          interp1d: Optional[str] = None) -> StageCommands:
     """The three argv lists of one LUT stage.  Raises what `build_command` / `engine_command` raise (copy guard, missing
     geometry).  `chroma_loc` goes to the engine (`--chroma-loc`) and, as `-chroma_sample_location`, to the encoder, so the
     output stream declares the siting the engine assumed.  `gpu_resize` with `params.resolution` set resizes in the engine
@@ -57,11 +58,13 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
     the engine (`--engine-dither`), and so do `cube2` / `interp2` (`--cube2`, `--interp2`: a second LUT in the same
     pass).  `alpha_mode` ("premultiplied") goes to the engine alone (`--alpha-mode`): ffmpeg's chain
     has no such step, so the decoder and encoder argv are untouched.  The same holds for `cdl` / `cdl_id` (an ASC CDL ahead of the
-    LUT, DESIGN.md 3.19: `--cdl` / `--cdl-id`, or `--cdl-sop` / `--cdl-sat` for a `cdl.Cdl`)."""
+    LUT, DESIGN.md 3.19: `--cdl` / `--cdl-id`, or `--cdl-sop` / `--cdl-sat` for a `cdl.Cdl`) and for `lut1d` / `interp1d` (a 1D LUT
+    file ahead of the LUT, DESIGN.md 3.20: `--lut1d` / `--interp1d`)."""
     notes: List[str] = []
     engine = engine_command(Path("-"), Path("-"), params, lut_path, source_info, python_bin=python_bin, device=device, notes=notes,
                             precision=precision, chroma_loc=chroma_loc, gpu_resize=gpu_resize, engine_dither=engine_dither,
-                            cube2=cube2, interp2=interp2, alpha_mode=alpha_mode, cdl=cdl, cdl_id=cdl_id)
+                            cube2=cube2, interp2=interp2, alpha_mode=alpha_mode, cdl=cdl, cdl_id=cdl_id, lut1d=lut1d,
+                            interp1d=interp1d)
     resized = gpu_resize and bool(params.resolution)
     if source_info.duration:
         engine += ["--duration", f"{float(source_info.duration):.3f}"]
@@ -156,6 +159,8 @@ def main(argv=None) -> int:
     ap.add_argument("--cdl-id", default=None, help="the id of the ColorCorrection to take from --cdl")
     ap.add_argument("--cdl-sop", default=None, help="the CDL as nine literal values, see lut_renderer_amd.cli")
     ap.add_argument("--cdl-sat", default=None, type=float, help="the CDL's saturation as a literal value")
+    ap.add_argument("--lut1d", default=None, help="engine setting: a 1D LUT file ahead of --cube, see lut_renderer_amd.cli")
+    ap.add_argument("--interp1d", default=None, help="interpolation mode of --lut1d, see lut_renderer_amd.cli")
     ap.add_argument("--gpu-resize", action="store_true", help="resize to the params' resolution in the engine (--out-size) instead of the encoder")
     a = ap.parse_args(argv)
     try:
@@ -170,7 +175,8 @@ def main(argv=None) -> int:
         cmds = engine_stage_commands(Path(a.input), Path(a.output), params, Path(a.cube), info, ffmpeg_bin=a.ffmpeg, device=a.device,
                                      precision=a.precision, chroma_loc=a.chroma_loc, gpu_resize=a.gpu_resize,
                                      engine_dither=a.engine_dither, cube2=None if a.cube2 is None else Path(a.cube2),
-                                     interp2=a.interp2, alpha_mode=a.alpha_mode, cdl=cdl, cdl_id=a.cdl_id)
+                                     interp2=a.interp2, alpha_mode=a.alpha_mode, cdl=cdl, cdl_id=a.cdl_id,
+                                     lut1d=None if a.lut1d is None else Path(a.lut1d), interp1d=a.interp1d)
     except Exception as exc:
         print(f"Error: {exc}", flush=True)
         return 1

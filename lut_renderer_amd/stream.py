@@ -20,6 +20,7 @@ import torch
 
 from .engine import LutEngine
 from .formats import (RgbSource, check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options,
+                      check_lut1d_options,
                       check_premul_options, parse_rgb_source, parse_size, premul_to_yuv, refuse_alpha_resize, yuv_side)
 
 
@@ -137,13 +138,16 @@ class HostPipeline:
     """Apply the LUT to batches of host frames with copies overlapped against compute."""
 
     def __init__(self, engine: LutEngine, pix_fmt: str, width: int, height: int, batch: int = 8, slots: int = 3,
-                 out_pix_fmt: Optional[str] = None, out_size=None, second_pix_fmt: Optional[str] = None, chain: bool = False, **apply_kw):
+                 out_pix_fmt: Optional[str] = None, out_size=None, second_pix_fmt: Optional[str] = None, chain: bool = False, lut1d: bool = False, **apply_kw):
         """`out_size` = (w, h) or "WxH": the engine resizes every frame to it and the output layout has that size.
         `second_pix_fmt`: a second planar YUV output from the same pass with a pinned output ring of its own
         (`fout2`); `run` then takes a second drain.
         `chain`: the engine holds a second LUT (`set_lut2`) and every batch goes through `apply_yuv_chain` (DESIGN.md 3.17);
         `apply_kw` may carry `interp2`.  Planar YUV without alpha on both sides, no dither, chroma_loc, out_size or second output."""
         self.chain = bool(chain)
+        # `lut1d`: the engine holds a 1D LUT (`set_lut1d`) and every batch goes through `apply_yuv_lut1d` (DESIGN.md 3.20);
+        # `apply_kw["interp"]` None is lut1d alone
+        self.lut1d = bool(lut1d)
         # premultiplied alpha (DESIGN.md 3.18) travels in apply_kw like chroma_loc; "straight" is not passed on (today's calls)
         premul = check_alpha_mode(apply_kw.get("alpha_mode", "straight"))
         if premul:
@@ -160,6 +164,11 @@ class HostPipeline:
                               lut2=self.chain, prelut=bool(getattr(engine, "_has_prelut", False)))
         else:
             apply_kw = {k: v for k, v in apply_kw.items() if k != "cdl"}
+        if self.lut1d:
+            check_lut1d_options(pix_fmt, out_pix_fmt, dither=apply_kw.get("dither", "none"), chroma_loc=apply_kw.get("chroma_loc"),
+                                out_size=out_size, alpha_mode=apply_kw.get("alpha_mode", "straight"), out2_pix_fmt=second_pix_fmt,
+                                lut2=self.chain, cdl=apply_kw.get("cdl") is not None, loaded=bool(getattr(engine, "n1d", 0)))
+            apply_kw = {k: v for k, v in apply_kw.items() if k != "dither"}
         if self.chain:
             check_chain_options(pix_fmt, out_pix_fmt, apply_kw.get("dither", "none"), apply_kw.get("chroma_loc"), out_size,
                                 second_pix_fmt)
@@ -221,7 +230,9 @@ class HostPipeline:
         with torch.cuda.stream(self.s_run):
             self.s_run.wait_event(self.e_in[slot])
             dst = self.fout.plane_views(self.d_out[slot], nframes)
-            if self.chain:
+            if self.lut1d:
+                self.eng.apply_yuv_lut1d(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
+            elif self.chain:
                 self.eng.apply_yuv_chain(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
             elif self.fout2 is not None:
                 self.eng.apply_yuv_dual(self.fin.plane_views(self.d_in[slot], nframes), dst,
