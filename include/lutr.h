@@ -629,8 +629,8 @@ int lutr_cdl_table(const lutr_cdl *cdl, int depth, int channel, float *out);
  * rows multiples of the union block height), "k_yuv_cdl_generic" for everything else (one thread per union block; any depth,
  * stride, alignment or size; all five modes; an 8-bit source with a 16-bit output); a ragged width on aligned rows is split
  * between the two and named "<vector kernel>+k_yuv_cdl_generic".
- * Not covered: a prelut, dither, chroma siting, a resize, the two-output pass, the two-LUT chain, premultiplied alpha, RGB / float
- * / semi-planar / packed / v210 sides, a tile (LDS) kernel. */
+ * Not covered: a prelut, dither, chroma siting, a resize, the two-output pass, premultiplied alpha, RGB / float / semi-planar /
+ * packed / v210 sides, a tile (LDS) kernel.  The CDL together with the two-LUT chain or a 1D LUT is lutr_apply_yuv_stack's. */
 int lutr_apply_yuv_cdl(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, const lutr_cdl *cdl, int w, int h, int nframes,
                        const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
 
@@ -698,8 +698,9 @@ int lutr_ctx_set_lut1d(lutr_ctx *ctx, const float *lut, int size, const float sc
  * once when 3 * 2^lut_depth * 2 bytes <= 24 KB and LUTR_L1D_LDS is not 0, and read it from global memory otherwise -- the bits do
  * not depend on that; "k_yuv_l1d_generic" for everything else; a ragged width is split and named
  * "<vector kernel>+k_yuv_l1d_generic".
- * Not covered: cosine anywhere but the host table, a 1D LUT behind lut3d, float sources, the container formats of DESIGN.md
- * 3.11 - 3.14, dither, chroma siting, a resize, a CDL, the chain, two outputs, premultiplied alpha, a tile (LDS window) kernel. */
+ * Not covered: cosine anywhere but the host table, float sources, the container formats of DESIGN.md 3.11 - 3.14, dither, chroma
+ * siting, a resize, two outputs, premultiplied alpha, a tile (LDS window) kernel.  A 1D LUT behind lut3d, or together with a CDL
+ * or the chain, is lutr_apply_yuv_stack's. */
 int lutr_apply_yuv_lut1d(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int w, int h, int nframes, const lutr_planes *src,
                          const lutr_planes *dst, int row0, int rows);
 
@@ -711,6 +712,59 @@ int lutr_apply_yuv_lut1d(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, in
  * whole call. */
 int lutr_apply_planar_rgb_lut1d(lutr_ctx *ctx, int depth, int w, int h, int nframes, const lutr_planes *src, const lutr_planes *dst,
                                 int row0, int rows);
+
+/* ---- an ordered stack of lut1d / CDL / lut3d stages in one fused pass: what a dailies or finishing pipeline
+ *      stacks between decode and encode -- input transform, per-clip CDL, show LUT; grade, technical LUT, look; look, output
+ *      curve -- without a trip through YUV between the operators. ---- */
+enum lutr_stage_kind {
+    LUTR_STAGE_LUT3D   = 1,   /* the context's first lattice (lutr_ctx_set_lut), its .csp prelut taken where the pixel is a code */
+    LUTR_STAGE_LUT3D_2 = 2,   /* the second lattice (lutr_ctx_set_lut2); never a prelut */
+    LUTR_STAGE_LUT1D   = 3,   /* the context's 1D LUT (lutr_ctx_set_lut1d) */
+    LUTR_STAGE_CDL     = 4    /* the `cdl` argument of the call */
+};
+typedef struct lutr_stage {
+    int32_t kind;             /* enum lutr_stage_kind */
+    int32_t interp;           /* enum lutr_interp of a LUTR_STAGE_LUT3D / _LUT3D_2 stage (all five modes); not read for the others */
+} lutr_stage;
+
+/* lutr_apply_yuv_xsub's pass (planar YUV in and out, any pair of 4:2:0 / 4:2:2 / 4:4:4, the equal pairs included, 8..16 bit on
+ * either side) with `nstages` stages, 1..4, each kind at most once, in the order given, between its YUV -> RGB stage and its RGB
+ * -> YUV stage.  M = 2^lut_depth - 1.  A pixel travels between stages as CODES (integer R, G, B in [0, M] held as floats: what
+ * stage 1 of lutr_apply_yuv produces) or as UNIT floats in [0, 1] (what the CDL produces):
+ *   LUTR_STAGE_LUT1D     codes -> codes: q'_c = lutr_lut1d_table(..., lut_depth, c)[q_c]
+ *   LUTR_STAGE_CDL       codes -> unit: T_c = lutr_cdl_table(cdl, lut_depth, c)[q_c], then the saturation mix of
+ *                        lutr_apply_yuv_cdl (skipped when saturation == 1)
+ *   LUTR_STAGE_LUT3D(_2) codes -> codes: lut3d as in lutr_apply_yuv (scale, the first lattice's prelut, `interp`, clip((int)(v * M),
+ *                        0, M)); unit -> codes: lut3d as in lutr_apply_yuv_cdl (s_c = med3(o_c * scale_c * (n - 1), 0, n - 1), ...)
+ *   unit -> codes        where a unit pixel meets LUTR_STAGE_LUT1D or the end of the list: q_c = (int)((o_c * (float)M) + 0.5f),
+ *                        fp32, the product and the sum each rounded on their own; o_c in [0, 1] gives [0, M] without a clip
+ * The RGB -> YUV stage takes codes (chroma = the mean over its OUTPUT block; constants: lutr_yuv_constants_xsub).
+ * Bit for bit: {LUT3D} is lutr_apply_yuv_xsub without dither, {CDL, LUT3D} is lutr_apply_yuv_cdl, {LUT1D, LUT3D} is
+ * lutr_apply_yuv_lut1d and {LUT1D} is that call with LUTR_INTERP_NONE, {LUT3D, LUT3D_2} is lutr_apply_yuv_chain.  {CDL} with the
+ * identity CDL is the source through the two conversion stages alone at every depth 8..16.
+ * The call is asynchronous on the context's stream and reuses the context's resources unchanged: both lattices, the CDL table
+ * keyed by (slope, offset, power, lut_depth) with its stream-ordered upload, the 1D tables keyed by generation.
+ * row0 and rows must be multiples of the union block height 2^max(icsy, ocsy) unless row0 + rows == h.  Always strict precision
+ * (fast / fma32 run strict here, no suffix on the last kernel).  Not in place (the overlap rule of lutr_apply_yuv_sited).
+ * LUTR_EINVAL with a message, before anything touches the device: a null argument or plane; nstages outside 1..4, an unknown
+ * kind, a kind twice, an unknown mode on a lut3d stage; a stage whose resource is missing (no lattice, no second lattice, no 1D
+ * LUT, a CDL stage with cdl == NULL) or a cdl without a CDL stage; a CDL lutr_apply_yuv_cdl refuses; LUTR_STAGE_LUT3D directly
+ * behind LUTR_STAGE_CDL on a context with a .csp prelut; the format errors of lutr_apply_yuv_xsub; a lut_depth outside 8..16;
+ * 16-bit planes at odd addresses; row0 / rows off the union block; any overlap; variant vec_lds.  Variant vec_global where the
+ * vector kernel cannot take the call (layout, 8 -> 16 bit, a pyramid or prism stage) is LUTR_EINVAL too, found where the kernel
+ * is chosen: tables may have been uploaded by then, no kernel has run and nothing is written.
+ * Kernels, as lutr_ctx_last_kernel names them: "k_yuv_stack_vec<win,wout,icsx,icsy,ocsx,ocsy,tri,lds>[stages]" (nearest / trilinear /
+ * tetrahedral stages; tri = 1 when a stage is trilinear, lds = 1 when the tables are staged in LDS; the layout rules of
+ * k_yuv_cdl_vec), a grid-stride walk whose workgroups
+ * stage the CDL and 1D tables the stack uses into LDS once when they fit 24 KB together (3 * 2^lut_depth * 4 bytes for the CDL, 3 *
+ * 2^lut_depth * 2 for the 1D LUT) and LUTR_STACK_LDS is not 0, and read them from global memory otherwise -- the bits do not depend
+ * on that; "k_yuv_stack_generic[stages]" for everything else; a ragged width is split and named
+ * "<vector kernel>+k_yuv_stack_generic[stages]".  [stages] is the list as given, comma separated: lut3d:<interp>, lut3d2:<interp>,
+ * lut1d, cdl -- for example "k_yuv_stack_vec<1,1,1,1,1,0,0,1>[lut1d,cdl,lut3d:2]".
+ * Not covered: more than one stage of a kind, a tile (LDS window) kernel, RGB / float / alpha / semi-planar / packed / v210 sides,
+ * dither, chroma siting, a resize, the two-output pass, premultiplied alpha. */
+int lutr_apply_yuv_stack(lutr_ctx *ctx, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl, int w,
+                         int h, int nframes, const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
 
 /* ---- the alpha plane of yuva* / gbrap* frames: ProRes 4444 (yuva444p10le / 12le), VP8 / VP9 with alpha
  *      (yuva420p), PNG / TIFF / EXR sequences with alpha (rgba, rgba64le, gbrap*, gbrapf32le).  In the reference's chain lut3d

@@ -18,6 +18,8 @@ OK, ENOENT, EIO, ENOMEM, EINVAL, EILSEQ = 0, -2, -5, -12, -22, -84
 INTERP = {"nearest": 0, "trilinear": 1, "tetrahedral": 2, "pyramid": 3, "prism": 4}
 #: enum lutr_interp1d: lut1d's modes
 INTERP1D = {"nearest": 0, "linear": 1, "cosine": 2, "cubic": 3, "spline": 4}
+#: enum lutr_stage_kind: the stage kinds of a stack
+STAGE_KINDS = {"lut3d": 1, "lut3d2": 2, "lut1d": 3, "cdl": 4}
 MATRIX = {"bt709": 0, "smpte170m": 1, "bt470bg": 1, "bt601": 1, "bt2020nc": 2, "bt2020c": 2}
 RANGE = {"tv": 0, "pc": 1}
 DITHER = {"none": 0, "error_diffusion": 1, "blue_noise": 2}
@@ -46,6 +48,7 @@ SYMBOLS = (
     "lutr_apply_yuv_dual", "lutr_apply_yuv_v210", "lutr_alpha_plane", "lutr_ctx_set_lut2", "lutr_apply_yuv_chain",
     "lutr_apply_yuv_premul", "lutr_apply_planar_rgb_f32_premul", "lutr_cdl_table", "lutr_apply_yuv_cdl",
     "lutr_lut1d_parse", "lutr_lut1d_table", "lutr_ctx_set_lut1d", "lutr_apply_yuv_lut1d", "lutr_apply_planar_rgb_lut1d",
+    "lutr_apply_yuv_stack",
     "lutr_resize_filter", "lutr_resize_planes", "lutr_dither_mask",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
     "lutr_max_waves_knob",
@@ -92,6 +95,20 @@ class AlphaSrc(C.Structure):
 class CdlStruct(C.Structure):
     """struct lutr_cdl: an ASC CDL"""
     _fields_ = [("slope", C.c_float * 3), ("offset", C.c_float * 3), ("power", C.c_float * 3), ("saturation", C.c_float)]
+
+
+class StageStruct(C.Structure):
+    """struct lutr_stage: one stage of a stack"""
+    _fields_ = [("kind", C.c_int32), ("interp", C.c_int32)]
+
+
+def stage_array(stages):
+    """lutr_stage[] from parsed stages ((kind name, lut3d mode name or None), ...; `formats.parse_stages`)."""
+    arr = (StageStruct * len(stages))()
+    for i, (kind, mode) in enumerate(stages):
+        arr[i].kind = STAGE_KINDS[kind]
+        arr[i].interp = 0 if mode is None else INTERP[mode]
+    return arr
 
 
 def cdl_struct(cdl) -> CdlStruct:
@@ -235,6 +252,8 @@ def load() -> C.CDLL:
     lib.lutr_ctx_set_lut1d.argtypes = [vp, C.POINTER(C.c_float), ci, C.POINTER(C.c_float), ci]
     lib.lutr_apply_yuv_lut1d.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_apply_planar_rgb_lut1d.argtypes = [vp, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
+    lib.lutr_apply_yuv_stack.argtypes = [vp, C.POINTER(YuvParams), C.POINTER(StageStruct), ci, C.POINTER(CdlStruct), ci, ci, ci,
+                                         C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_dither_mask.argtypes = [C.POINTER(C.c_uint16)]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]

@@ -24,8 +24,8 @@ from typing import Dict, Optional, Sequence, Tuple
 from .cdl import as_cdl
 from .cube import CubeLut, as_lut1d, read_cube, read_lut, read_lut1d
 from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc, check_container_options,
-                      check_dual_options, check_lut1d_options, check_lut2, check_premul_options, packed_frame_width, parse_packed_yuv_fmt,
-                      parse_pix_fmt, parse_rgb_source, parse_semi_fmt, parse_size, parse_v210_fmt, premul_to_yuv,
+                      check_dual_options, check_lut1d_options, check_lut2, check_premul_options, check_stack_options, packed_frame_width, parse_packed_yuv_fmt,
+                      parse_pix_fmt, parse_rgb_source, parse_semi_fmt, parse_size, parse_stages, parse_v210_fmt, premul_to_yuv,
                       refuse_alpha_resize, source_bit_depth, v210_frame_width, yuv_side)
 from .params import ProcessingParams, VideoInfo
 from .plan import LutPlan, output_color_tags, resolve_lut_plan
@@ -209,6 +209,61 @@ def resolve_engine_dither(engine_dither: str, dither: str = "none") -> str:
     return "blue_noise"
 
 
+def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, engine, devices, precision,
+                 chroma_loc, out_size, alpha_mode, second_pix_fmt):
+    """`apply_lut(stages=...)`: load what the list names, with the caches the single-feature routes use, and
+    route to `apply_yuv_stack`.  `kw` is what `engine_call_for` returned, with `dither` filled in."""
+    from .plan import INTERP_WHITELIST
+    from . import _native
+    mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
+    st = parse_stages(stages, interp=kw.get("interp"), interp2=mode2)
+    kinds = [k for k, _m in st]
+    if interp1d not in _native.INTERP1D:
+        raise ValueError(f"lut1d has no interpolation mode '{interp1d}' ({' | '.join(_native.INTERP1D)})")
+    for name, given, kind in (("cube", cube, "lut3d"), ("cube2", cube2, "lut3d2"), ("lut1d", lut1d, "lut1d"), ("cdl", cdl, "cdl")):
+        if given is not None and kind not in kinds:
+            raise ValueError(f"{name} is given and the stage list has no '{kind}' stage")
+    if interp2 is not None and "lut3d2" not in kinds:
+        raise ValueError("interp2 is the mode of the second LUT: the stage list has no 'lut3d2' stage")
+    if cdl is None and cdl_id is not None:
+        raise ValueError("cdl_id names a correction inside a CDL file: it needs cdl")
+    lut = None if cube is None else cube if isinstance(cube, CubeLut) else _cached_cube(Path(cube))
+    lut2 = None if cube2 is None else cube2 if isinstance(cube2, CubeLut) else _cached_cube(Path(cube2))
+    check_lut2(lut2)
+    if lut1d is not None:
+        lut1d = _cached_cube(Path(lut1d), read_lut1d) if isinstance(lut1d, (str, Path)) and Path(lut1d).is_file() else as_lut1d(lut1d)
+    if cdl is not None:
+        cdl = as_cdl(cdl, cdl_id)
+    first = engine.engines[0] if engine is not None and hasattr(engine, "engines") else engine
+    held = lambda name: bool(getattr(first, name, 0))                                  # noqa: E731
+    prelut = getattr(lut, "prelut", None) is not None if lut is not None else held("_has_prelut")
+    check_stack_options(kw["pix_fmt"], kw["out_pix_fmt"], stages=st, cdl=cdl is not None, lut=lut is not None or held("n"),
+                        lut2=lut2 is not None or held("n2"), lut1d=lut1d is not None or held("n1d"), prelut=prelut,
+                        dither=kw.get("dither", "none"), chroma_loc=chroma_loc, out_size=out_size, alpha_mode=alpha_mode,
+                        out2_pix_fmt=second_pix_fmt)
+    own = engine is None
+    eng = engine if engine is not None else _cached_engine(devices)
+    call = {k: v for k, v in kw.items() if k not in ("dither", "interp", "alpha_mode")}
+    with eng._lock:                 # uploads, precision and launch of ONE task, as in apply_lut
+        if lut is not None and eng._applied_lut is not lut:
+            eng.set_lut(lut)
+            eng._applied_lut = lut
+        if lut2 is not None and eng._applied_lut2 is not lut2:
+            eng.set_lut2(lut2)
+            eng._applied_lut2 = lut2
+        if lut1d is not None:
+            had = eng._applied_lut1d
+            if not (had is not None and had[0] is lut1d and had[1] == interp1d):
+                eng.set_lut1d(lut1d, interp1d)
+                eng._applied_lut1d = (lut1d, interp1d)
+        if eng.precision != precision:
+            eng.set_precision(precision)
+        result = eng.apply_yuv_stack(planes, out, stages=st, cdl=cdl, **call)
+        if own:
+            eng.sync()
+    return result
+
+
 def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: str, width: Optional[int] = None,
               height: Optional[int] = None, input_matrix: str = "auto", colorspace: Optional[str] = None,
               color_range: Optional[str] = None, output_tags: str = "bt709", out_pix_fmt: Optional[str] = None,
@@ -216,7 +271,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               devices: Sequence[int] = (0,), precision: str = "strict", chroma_loc: Optional[str] = None,
               resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
               cube2=None, interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None, cdl_id: Optional[str] = None,
-              lut1d=None, interp1d: str = "linear"):
+              lut1d=None, interp1d: str = "linear", stages=None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -294,7 +349,15 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     | cubic | spline).  `cube=None` together with `lut1d` is lut1d alone.  Planar YUV on both sides (yuva* with straight alpha
     included), a LutEngineGroup row-shards it, always strict arithmetic; the identity 1D LUT gives the bits of the call without
     it.  No dither, chroma_loc, resolution, CDL, second LUT, second output, premultiplied alpha, RGB / float / semi-planar /
-    packed / v210 side: each is a ValueError naming it.  Without `lut1d` the function is unchanged."""
+    packed / v210 side: each is a ValueError naming it.  Without `lut1d` the function is unchanged.
+
+    `stages` (a sequence or comma string: "lut3d", "lut3d2", "lut1d", "cdl", a lut3d stage optionally with its mode as ("lut3d",
+    "trilinear") or "lut3d:trilinear") runs `cube`, `cube2`, `lut1d` (+ `interp1d`) and `cdl` (+ `cdl_id`) in that
+    order in ONE pass (LutEngine.apply_yuv_stack); `interp` / `interp2` are the modes of the two lut3d stages that spell none.
+    Only with `stages` may these be combined freely.  Every stage listed needs its file (or an `engine` that holds it) and every
+    file given needs its stage: anything else is a ValueError.  Planar YUV on both sides (yuva* with straight alpha included), a
+    LutEngineGroup row-shards it, always strict arithmetic; no dither, chroma_loc, resolution, second output or premultiplied
+    alpha.  Without `stages` the function is unchanged."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -342,6 +405,10 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         check_premul_options(kw["pix_fmt"], kw["out_pix_fmt"], dither=kw["dither"], chroma_loc=chroma_loc, out_size=out_size,
                              range_src=kw.get("range_src", "tv"), range_in=kw.get("range_in"), lut_depth=kw.get("lut_depth"),
                              out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None)
+    if stages is not None:
+        result = _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, engine, devices, precision,
+                              chroma_loc, out_size, alpha_mode, second_pix_fmt)
+        return result, output_color_tags(plan.output_policy)
     if lut1d is not None:
         check_lut1d_options(kw["pix_fmt"], kw["out_pix_fmt"], interp1d=interp1d, dither=kw["dither"], chroma_loc=chroma_loc,
                             out_size=out_size, alpha_mode=alpha_mode, out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None,

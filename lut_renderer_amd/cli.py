@@ -20,7 +20,7 @@ import signal
 import sys
 import time
 
-from .formats import (check_cdl_options, check_chroma_loc, check_container_options, check_lut1d_options, check_lut2,
+from .formats import (check_cdl_options, check_chroma_loc, check_container_options, check_lut1d_options, check_lut2, check_stack_options, parse_stages,
                       check_premul_options, parse_size, refuse_alpha_resize, source_bit_depth)
 
 
@@ -101,6 +101,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="interpolation mode of --lut1d: nearest | linear | cosine | cubic | spline (default linear)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--stages", default=None, metavar="LIST",
+                    help="engine setting: run --cube (lut3d), --cube2 (lut3d2), --lut1d (lut1d) and --cdl / --cdl-sop / --cdl-sat (cdl) "
+                         "as an ordered stack in ONE pass (DESIGN.md 3.21), e.g. lut1d,cdl,lut3d:trilinear; each kind once, 1 to 4 "
+                         "stages, a lut3d stage without a mode takes --interp / --interp2; every stage needs its file and every "
+                         "file its stage; planar YUV on both sides, no dither, --chroma-loc, --out-size, --second-output or "
+                         "--alpha-mode premultiplied")
     ap.add_argument("-y", action="store_true", help="overwrite the output (ffmpeg's -y)")
     ap.add_argument("--duration", type=float, default=None,
                     help="seconds of video, for the Duration: line when the input is a pipe (-i -) and cannot be measured")
@@ -122,6 +128,47 @@ def cdl_from_args(args):
     return read_cdl(path, cc_id) if path is not None else Cdl.from_sop_text(sop, sat)
 
 
+def stack_call_from_args(args, kw: dict, cdl) -> dict:
+    """The keyword arguments of `apply_yuv_stack` for --stages from those `engine_call_for` returned: the stage
+    list parsed with --interp / --interp2 as the lut3d stages' defaults, every refusal of `check_stack_options`, and a file for
+    every stage and a stage for every file."""
+    from .plan import INTERP_WHITELIST
+    interp2 = getattr(args, "interp2", None)
+    mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
+    st = parse_stages(args.stages, interp=kw.get("interp"), interp2=mode2)
+    kinds = [k for k, _m in st]
+    cube2, lut1d = getattr(args, "cube2", None), getattr(args, "lut1d", None)
+    for flag, given, kind in (("--cube", args.cube, "lut3d"), ("--cube2", cube2, "lut3d2"), ("--lut1d", lut1d, "lut1d"),
+                              ("--cdl / --cdl-sop / --cdl-sat", cdl, "cdl")):
+        if given is not None and kind not in kinds:
+            raise ValueError(f"{flag} is given and --stages has no '{kind}' stage")
+    if interp2 is not None and "lut3d2" not in kinds:
+        raise ValueError("--interp2 is the mode of the second LUT: --stages has no 'lut3d2' stage")
+    interp1d = getattr(args, "interp1d", None) or "linear"
+    from . import _native
+    if interp1d not in _native.INTERP1D:
+        raise ValueError(f"lut1d has no interpolation mode '{interp1d}' ({' | '.join(_native.INTERP1D)})")
+    prelut = False
+    if "cdl" in kinds and args.cube is not None and os.path.isfile(args.cube):
+        from pathlib import Path
+        from . import engine  # noqa: F401  (torch first, as in plan_from_args)
+        from .api import _cached_cube
+        prelut = getattr(_cached_cube(Path(args.cube)), "prelut", None) is not None
+    second_out, second_fmt = getattr(args, "second_output", None), getattr(args, "second_pix_fmt", None)
+    engine_dither = getattr(args, "engine_dither", None)
+    check_stack_options(kw["pix_fmt"], kw["out_pix_fmt"], stages=st, cdl=cdl is not None, lut=args.cube is not None,
+                        lut2=cube2 is not None, lut1d=lut1d is not None, prelut=prelut,
+                        dither="error_diffusion" if args.zscale_dither == "error_diffusion" else engine_dither or "none",
+                        chroma_loc=getattr(args, "chroma_loc", None), out_size=getattr(args, "out_size", None),
+                        alpha_mode=getattr(args, "alpha_mode", None) or "straight",
+                        out2_pix_fmt=second_fmt if second_fmt is not None else second_out)
+    call = {k: v for k, v in kw.items() if k not in ("interp", "alpha_mode", "dither")}
+    call["stages"] = st
+    if cdl is not None:
+        call["cdl"] = cdl
+    return call
+
+
 def plan_from_args(args):
     """The LutPlan and engine call the options select -- the same resolution `build_command` performs (plan.py)."""
     from .api import engine_call_for
@@ -133,7 +180,8 @@ def plan_from_args(args):
     info = VideoInfo(width=w, height=h, pix_fmt=args.pix_fmt, bit_depth=source_bit_depth(args.pix_fmt),
                      colorspace=args.colorspace, color_range=args.color_range)
     lut1d = getattr(args, "lut1d", None)
-    if args.cube is None and lut1d is None:
+    stages = getattr(args, "stages", None)
+    if args.cube is None and lut1d is None and stages is None:
         raise ValueError("--cube is required unless --lut1d is given")
     plan = resolve_lut_plan(params, args.cube if args.cube is not None else "engine.cube", info)
     alpha_mode = getattr(args, "alpha_mode", None) or "straight"
@@ -147,6 +195,8 @@ def plan_from_args(args):
                              range_in=kw.get("range_in"), lut_depth=kw.get("lut_depth"),
                              out2_pix_fmt=getattr(args, "second_pix_fmt", None), lut2=getattr(args, "cube2", None) is not None)
     cdl = cdl_from_args(args)
+    if stages is not None:
+        return plan, stack_call_from_args(args, kw, cdl), w, h
     if lut1d is not None:
         check_lut1d_options(kw["pix_fmt"], kw["out_pix_fmt"], interp1d=getattr(args, "interp1d", None) or "linear",
                             chroma_loc=getattr(args, "chroma_loc", None),
@@ -214,7 +264,7 @@ def plan_from_args(args):
 def main(argv=None) -> int:
     ap = build_parser()
     args = ap.parse_args(argv)
-    if args.cube is None and args.lut1d is None:
+    if args.cube is None and args.lut1d is None and args.stages is None:
         ap.error("the following arguments are required: --cube (or --lut1d for a 1D LUT alone)")
 
     stop = {"flag": False}
@@ -250,7 +300,8 @@ def main(argv=None) -> int:
         pix_fmt, out_fmt = kw.pop("pix_fmt"), kw.pop("out_pix_fmt")
         second_fmt = kw.pop("out2_pix_fmt", None)
         pipe = HostPipeline(eng, pix_fmt, w, h, batch=args.batch, out_pix_fmt=out_fmt, out_size=args.out_size,
-                            second_pix_fmt=second_fmt, chain=lut2 is not None, lut1d=args.lut1d is not None, **kw)
+                            second_pix_fmt=second_fmt, chain=lut2 is not None and args.stages is None,
+                            lut1d=args.lut1d is not None and args.stages is None, **kw)
         fb = pipe.fin.frame_bytes
         if piped_in:
             total = None if args.duration is None else max(1, int(round(args.duration * args.fps)))

@@ -20,7 +20,7 @@ from pathlib import Path
 from typing import List, Optional, Tuple
 
 from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options, check_lut1d_options,
-                      check_premul_options, parse_rgb_source, premul_to_yuv)
+                      check_premul_options, check_stack_options, parse_stages, stages_string, parse_rgb_source, premul_to_yuv)
 from .params import ProcessingParams, Task, VideoInfo
 from .plan import LutPlan, output_color_tags, resolve_lut_plan, resolve_pix_fmt
 
@@ -257,7 +257,7 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                    second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
                    cube2: Optional[Path] = None, interp2: Optional[str] = None, alpha_mode: str = "straight",
                    cdl=None, cdl_id: Optional[str] = None, lut1d: Optional[Path] = None,
-                   interp1d: Optional[str] = None) -> List[str]:
+                   interp1d: Optional[str] = None, stages=None) -> List[str]:
     """`build_command`'s twin for the LUT stage alone: the argv of the ENGINE CLI (`python -m lut_renderer_amd.cli`)
     that applies exactly the chain `build_command` would put into `-vf` -- the same `LutPlan`, rendered as CLI options
     instead of as a filter string (ffmpeg.py:195-247, :287-310).  `source` / `output` are rawvideo files (or `-`) in
@@ -286,7 +286,11 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     `lut1d` / `interp1d` put a 1D LUT file in front of the LUT in the same pass (`--lut1d`, and `--interp1d` when
     given: ffmpeg's `lut1d=file=A,lut3d=file=B`); rendered only when given.  Planar YUV on both sides; not with dither,
     `chroma_loc`, `gpu_resize`, a CDL, a second LUT, a second output or premultiplied alpha.  `interp1d` without `lut1d` is a
-    ValueError."""
+    ValueError.
+    `stages` (a sequence or comma string as `LutEngine.apply_yuv_stack` takes it) runs the LUT, `cube2`, `lut1d`
+    and `cdl` as an ordered stack in one pass (`--stages`, every lut3d stage with its mode spelled out); rendered only when
+    given, and only then may those be combined.  The list names `lut3d` (the LUT this stage renders) and a stage for every file
+    given, and every other stage has its file; the refusals are `formats.check_stack_options`'s."""
     import sys as _sys
     premul = check_alpha_mode(alpha_mode)
     if precision not in ("strict", "fast", "fma32"):
@@ -367,10 +371,12 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
         cmd += ["--second-output", str(second_output), "--second-pix-fmt", second_pix_fmt]
     if cube2 is None and interp2 is not None:
         raise ValueError("interp2 is the mode of the second LUT: it needs cube2")
+    stack = stages is not None               # the pairwise refusals below give way to check_stack_options at the end
     if cube2 is not None:
         from .plan import INTERP_WHITELIST
-        check_chain_options(str(source_info.pix_fmt), pix_fmt or None, dither, chroma_loc,
-                            params.resolution if "--out-size" in cmd else None, second_pix_fmt)
+        if not stack:
+            check_chain_options(str(source_info.pix_fmt), pix_fmt or None, dither, chroma_loc,
+                                params.resolution if "--out-size" in cmd else None, second_pix_fmt)
         cmd += ["--cube2", str(cube2)]
         if interp2 is not None:
             cmd += ["--interp2", interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"]
@@ -386,9 +392,10 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
         raise ValueError("cdl_id names a correction inside a CDL file: it needs cdl")
     if cdl is not None:
         from .cdl import Cdl
-        check_cdl_options(str(source_info.pix_fmt).replace("yuvj", "yuv"), pix_fmt or None, dither=dither, chroma_loc=chroma_loc,
-                          out_size=params.resolution if "--out-size" in cmd else None, alpha_mode=alpha_mode,
-                          out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None)
+        if not stack:
+            check_cdl_options(str(source_info.pix_fmt).replace("yuvj", "yuv"), pix_fmt or None, dither=dither, chroma_loc=chroma_loc,
+                              out_size=params.resolution if "--out-size" in cmd else None, alpha_mode=alpha_mode,
+                              out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None)
         if isinstance(cdl, Cdl):
             if cdl_id is not None:
                 raise ValueError("cdl_id names a correction inside a CDL file, and cdl is a set of values")
@@ -406,12 +413,30 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     if lut1d is not None:
         if not isinstance(lut1d, (str, Path)):
             raise TypeError(f"lut1d must be the path of a 1D .cube file, not {type(lut1d).__name__}")
-        check_lut1d_options(str(source_info.pix_fmt).replace("yuvj", "yuv"), pix_fmt or None, interp1d=interp1d or "linear",
-                            dither=dither, chroma_loc=chroma_loc, out_size=params.resolution if "--out-size" in cmd else None,
-                            alpha_mode=alpha_mode, out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None, cdl=cdl is not None)
+        if not stack:
+            check_lut1d_options(str(source_info.pix_fmt).replace("yuvj", "yuv"), pix_fmt or None, interp1d=interp1d or "linear",
+                                dither=dither, chroma_loc=chroma_loc, out_size=params.resolution if "--out-size" in cmd else None,
+                                alpha_mode=alpha_mode, out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None, cdl=cdl is not None)
         cmd += ["--lut1d", str(lut1d)]
         if interp1d is not None:
             cmd += ["--interp1d", interp1d]
+    if stack:
+        from . import _native
+        from .plan import INTERP_WHITELIST
+        mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
+        st = parse_stages(stages, interp=plan.interp, interp2=mode2)
+        kinds = [k for k, _m in st]
+        if (interp1d or "linear") not in _native.INTERP1D:
+            raise ValueError(f"lut1d has no interpolation mode '{interp1d}' ({' | '.join(_native.INTERP1D)})")
+        for name, given, kind in (("the LUT", lut_path, "lut3d"), ("cube2", cube2, "lut3d2"), ("lut1d", lut1d, "lut1d"),
+                                  ("cdl", cdl, "cdl")):
+            if given is not None and kind not in kinds:
+                raise ValueError(f"{name} is given and the stage list has no '{kind}' stage")
+        check_stack_options(str(source_info.pix_fmt).replace("yuvj", "yuv"), pix_fmt or None, stages=st, cdl=cdl is not None,
+                            lut=True, lut2=cube2 is not None, lut1d=lut1d is not None, dither=dither, chroma_loc=chroma_loc,
+                            out_size=params.resolution if "--out-size" in cmd else None, alpha_mode=alpha_mode,
+                            out2_pix_fmt=second_pix_fmt)
+        cmd += ["--stages", stages_string(st)]
     return cmd
 
 

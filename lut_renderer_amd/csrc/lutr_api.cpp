@@ -1608,6 +1608,142 @@ int lutr_apply_yuv_lut1d(lutr_ctx *c, const lutr_yuv_params *p, int interp, int 
     return finish_launch(c, launch_yuv_l1d(c->stream, c->variant, L, C, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, interp));
 }
 
+// ---- an ordered stack of lut1d / CDL / lut3d stages
+// lutr_apply_yuv_cdl's pass with the stage list compiled into steps: the pixel's state (codes or unit) is followed here, so the
+// kernels are told which form of a lattice stage to run and where the rounding goes.
+int lutr_apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl, int w,
+                         int h, int nframes, const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+{
+    if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
+    if (nstages < 1 || nstages > 4) { set_error("stack: %d stages; a stack has 1 to 4", nstages); return LUTR_EINVAL; }
+    if (!stages) { set_error("stack: null stage list"); return LUTR_EINVAL; }
+    static const char *const kind_name[5] = {"", "lut3d", "lut3d2", "lut1d", "cdl"};
+    bool seen[5] = {false, false, false, false, false};
+    std::string list;
+    for (int i = 0; i < nstages; i++) {
+        const int k = stages[i].kind;
+        if (k < LUTR_STAGE_LUT3D || k > LUTR_STAGE_CDL) { set_error("stack: stage %d has unknown kind %d", i, k); return LUTR_EINVAL; }
+        if (seen[k]) { set_error("stack: stage kind %s is listed twice; each kind may appear once", kind_name[k]); return LUTR_EINVAL; }
+        seen[k] = true;
+        if (i) list += ",";
+        list += kind_name[k];
+        if (k == LUTR_STAGE_LUT3D || k == LUTR_STAGE_LUT3D_2) {
+            if (stages[i].interp < LUTR_INTERP_NEAREST || stages[i].interp > LUTR_INTERP_PRISM) {
+                set_error("stack: unknown interpolation mode %d on stage %d (%s)", stages[i].interp, i, kind_name[k]);
+                return LUTR_EINVAL;
+            }
+            list += ":" + std::to_string(stages[i].interp);
+        }
+    }
+    if (seen[LUTR_STAGE_LUT3D] && !c->lat) { set_error("stack: no lattice set on this context (call lutr_ctx_set_lut first)"); return LUTR_EINVAL; }
+    if (seen[LUTR_STAGE_LUT3D_2] && !c->lat2) {
+        set_error("stack: no second lattice set on this context (call lutr_ctx_set_lut2 first)");
+        return LUTR_EINVAL;
+    }
+    if (seen[LUTR_STAGE_LUT1D] && !c->l1d_size) {
+        set_error("stack: no 1D LUT set on this context (call lutr_ctx_set_lut1d first)");
+        return LUTR_EINVAL;
+    }
+    if (seen[LUTR_STAGE_CDL] && !cdl) { set_error("stack: a cdl stage is listed and the CDL is null"); return LUTR_EINVAL; }
+    if (!seen[LUTR_STAGE_CDL] && cdl) { set_error("stack: a CDL is given and no cdl stage is listed"); return LUTR_EINVAL; }
+    if (cdl)
+        if (const int rc = check_cdl(cdl)) return rc;
+    if (w < 0 || h < 0 || nframes < 0 || row0 < 0 || rows < 0 || row0 + rows > h) {
+        set_error("bad geometry w=%d h=%d nframes=%d row0=%d rows=%d", w, h, nframes, row0, rows);
+        return LUTR_EINVAL;
+    }
+    // the steps: a unit pixel is rounded to codes ahead of lut1d and at the end of the list
+    unsigned long long ops = 0;
+    int nops = 0;
+    bool unit = false;
+    auto push = [&](int op, int mode) { ops |= (unsigned long long)(op | (mode << 4)) << (8 * nops++); };
+    for (int i = 0; i < nstages; i++) {
+        switch (stages[i].kind) {
+        case LUTR_STAGE_LUT1D:
+            if (unit) push(STACK_OP_ROUND, 0);
+            push(STACK_OP_L1D, 0);
+            unit = false;
+            break;
+        case LUTR_STAGE_CDL:
+            push(STACK_OP_CDL, 0);       // each kind once: the pixel is a code here
+            unit = true;
+            break;
+        case LUTR_STAGE_LUT3D:
+            if (unit && c->pre_size) {
+                set_error("stack: lut3d directly behind cdl, and the LUT has a .csp prelut; its table is indexed by integer codes, and "
+                          "the CDL's output is not a code");
+                return LUTR_EINVAL;
+            }
+            push(unit ? STACK_OP_LAT_UNIT : STACK_OP_LAT_CODES, stages[i].interp);
+            unit = false;
+            break;
+        default:
+            push(unit ? STACK_OP_LAT2_UNIT : STACK_OP_LAT2_CODES, stages[i].interp);
+            unit = false;
+            break;
+        }
+    }
+    if (unit) push(STACK_OP_ROUND, 0);
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    YuvConsts K;
+    if (const int rc = make_yuv_consts_xsub(*p, &K)) return rc;
+    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
+    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
+    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
+    if (p->lut_depth < 8 || p->lut_depth > 16) { set_error("stack: LUT depth %d outside 8..16", p->lut_depth); return LUTR_EINVAL; }
+    if (const int rc = check_row_blocks(row0, rows, h, 1 << std::max(icsy, ocsy), "union chroma block height")) return rc;
+    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for the stack pass"); return LUTR_EINVAL; }
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    if (const int rc = check_planes_set(src, dst)) return rc;
+    const struct { const char *side; const lutr_planes *pl; int depth; } sides[2] = {{"source", src, din}, {"destination", dst, dout}};
+    for (const auto &s : sides)
+        for (int i = 0; i < 3; i++)
+            if (s.depth > 8 && !check_aligned(s.pl->data[i], s.pl->stride[i], s.pl->frame_stride[i], nframes, 1)) {
+                set_error("%s plane %d: 16-bit planes need 2-byte aligned rows", s.side, i);
+                return LUTR_EINVAL;
+            }
+    Span ss[3], ds[3];
+    planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
+    planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
+    if (const int rc = check_disjoint("the stack pass", true, ss, 3, ds, 3)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
+    LutConsts L{}, L2{}; StackConsts S{}; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    const int maxi = (1 << p->lut_depth) - 1;
+    if (seen[LUTR_STAGE_LUT3D])
+        if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
+    if (seen[LUTR_STAGE_LUT3D_2]) {      // lutr_apply_yuv_chain's second lattice: its own size and scale, no prelut
+        L2.lat = c->lat2;
+        L2.n1 = c->n2 + 1;
+        L2.maxf = (float)maxi;
+        L2.scale_f = 1.0f / (float)maxi;
+        L2.lut_max = (float)(c->n2 - 1);
+        for (int i = 0; i < 3; i++) L2.sc[i] = c->scale2[i] * L2.lut_max;
+    }
+    S.ops = ops;
+    S.stride = 1 << p->lut_depth;
+    S.sat = 1.0f;
+    S.maxf = (float)maxi;
+    if (cdl) {
+        CdlConsts C;
+        if (const int rc = cdl_device_table(c, *cdl, p->lut_depth, &C)) return rc;
+        S.cdl_tab = C.tab;
+        S.sat = C.sat;
+        S.lds_cdl_words = 3 * S.stride;
+    }
+    if (seen[LUTR_STAGE_LUT1D]) {
+        L1dConsts C1;
+        if (const int rc = l1d_device_table(c, p->lut_depth, &C1)) return rc;
+        S.l1d_tab = C1.tab;
+        S.lds_l1d_words = 3 * (S.stride >> 1);
+    }
+    fill_planes(&P, src, dst);
+    const char *name = launch_yuv_stack(c->stream, c->variant, L, L2, S, K, P, G, din, dout, icsx, icsy, ocsx, ocsy);
+    if (!name) return finish_launch(c, nullptr);
+    const std::string full = std::string(name) + "[" + list + "]";
+    return finish_launch(c, full.c_str());
+}
+
 int lutr_apply_planar_rgb_lut1d(lutr_ctx *c, int depth, int w, int h, int nframes, const lutr_planes *src, const lutr_planes *dst,
                                 int row0, int rows)
 {

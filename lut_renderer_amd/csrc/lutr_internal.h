@@ -185,6 +185,43 @@ LUTR_L1_DECL(w00) LUTR_L1_DECL(w11) LUTR_L1_DECL(w10)
 // lut1d alone on planar RGB: P in gbrp order (G, B, R), planes of `depth` bits.  nullptr as above
 const char *launch_rgb_l1d(hipStream_t st, int variant, const L1dConsts &C, const PlaneSet &P, const FrameGeom &G, int depth);
 
+// an ordered stack of lut1d / CDL / lut3d stages (lutr_stack.hip).  The stage list compiled into steps, one byte
+// each from the low end of `ops`, a zero byte ends it: bits 0..3 the step, bits 4..7 the interpolation mode of a lattice step.
+// A pixel is integer codes held as floats, or unit floats behind the CDL; the list says which at every step.
+enum StackOp {
+    STACK_OP_END        = 0,
+    STACK_OP_LAT_CODES  = 1,     // the first lattice on codes: lut3d_px (prelut taken)
+    STACK_OP_LAT_UNIT   = 2,     // the first lattice on unit floats: lut3d_unit
+    STACK_OP_LAT2_CODES = 3,     // the second lattice, the same two forms
+    STACK_OP_LAT2_UNIT  = 4,
+    STACK_OP_L1D        = 5,     // codes -> codes through the 1D table
+    STACK_OP_CDL        = 6,     // codes -> unit: cdl_px
+    STACK_OP_ROUND      = 7      // unit -> codes: (int)(o * maxf + 0.5f)
+};
+struct StackConsts {
+    unsigned long long ops;      // at most 5 steps: four stages and one rounding
+    const float    *cdl_tab;     // CdlConsts::tab, or nullptr when no step reads it
+    const uint16_t *l1d_tab;     // L1dConsts::tab, likewise
+    int   stride;                // 2^lut_depth
+    float sat;                   // the CDL's saturation (1 without one)
+    float maxf;                  // (float)(2^lut_depth - 1)
+    int   lds_cdl_words;         // 32-bit words of the tables the stack uses (0: not used): what an LDS placement stages
+    int   lds_l1d_words;
+};
+// launch_yuv_chain's call with the step list; L / L2 are read by the lattice steps only.  nullptr = the variant cannot take the
+// call (vec_lds always; vec_global on layouts the vector kernel cannot take and on pyramid / prism stages)
+const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
+                             const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int din, int dout, int icsx, int icsy,
+                             int ocsx, int ocsy);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>); tri: some lattice step is trilinear; lds:
+// stage the tables per workgroup
+#define LUTR_SK_DECL(tag) \
+    const char *launch_yuv_stack_vec_##tag(hipStream_t st, const LutConsts &L, const LutConsts &L2, const StackConsts &S, \
+                                           const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int icsx, int icsy, int ocsx, \
+                                           int ocsy, bool tri, bool lds);
+LUTR_SK_DECL(w00) LUTR_SK_DECL(w11) LUTR_SK_DECL(w10)
+#undef LUTR_SK_DECL
+
 // blue-noise dither in the output stage (lutr_bnd.hip): launch_yuv_xsub's call for any pair of layouts, the equal
 // ones included; bn = the 64 x 64 table of offsets (device).  nullptr = the variant cannot take the call (vec_lds always;
 // vec_global on layouts the vector kernel cannot take)

@@ -1,0 +1,380 @@
+// lutr_stack.hip -- gfx950 kernels of the fused YUV pass with an ordered stack of lut1d / CDL / lut3d stages.
+//
+// What they compute: between the YUV -> RGB stage (3.2) and the RGB -> YUV stage (3.2 / 3.8) a pixel walks a list of up to four
+// stages, each kind at most once: the first lattice, the second lattice (3.17), the per-code 1D table (3.20), the ASC CDL (3.19).
+// It travels as integer codes in [0, M] held as floats, or -- behind the CDL only -- as unit floats:
+//   lut1d            codes -> codes   q'_c = tab[c][q_c]
+//   cdl              codes -> unit    cdl_px (stages A and B of 3.19)
+//   lut3d / lut3d2   codes -> codes   lut3d_px (the prelut taken), or unit -> codes: lut3d_unit
+//   round            unit -> codes    q_c = (int)(o_c * M + 0.5f), where a unit pixel meets lut1d or the end of the list
+// The host compiles the stage list into a word of step bytes (StackConsts::ops): the pixel's state follows from the list, so the
+// rounding is a step of its own and a lattice step says which of its two forms it is.  The word is a kernel argument; the kernels
+// walk it with wave-uniform branches.  Nothing is templated on the order.
+//
+// The unit of work is 3.8's union block for every pair of layouts, the equal ones included.  The vector kernels walk their units
+// with a grid stride, so that a workgroup can stage the CDL and 1D tables into LDS once (LDS = true); LDS = false reads them from
+// global memory through L1.  Both read the same entries: the bits do not depend on the choice.
+//
+// One source, two kinds of translation unit (Makefile MIX_RULE):
+//   without LUTR_SK_WI   the generic kernel and the launcher
+//   LUTR_SK_WI / _WO     the vector kernels of one container mix (8 -> 8, 16 -> 16, 16 -> 8): 9 layout pairs x (any stage
+//                        trilinear) x 2 placements
+#include <string>
+
+#include "lutr_device.h"
+#include "lutr_launch.h"
+
+namespace lutr {
+
+// the 1D lookup of 3.20 on one pixel of codes
+__device__ __forceinline__ Rgb stack_l1d_px(const uint16_t *tab, int stride, const Rgb &q)
+{
+    Rgb t;
+    t.r = (float)tab[(int)q.r];
+    t.g = (float)tab[stride + (int)q.g];
+    t.b = (float)tab[2 * stride + (int)q.b];
+    return t;
+}
+
+// unit -> codes: the product and the sum each rounded on their own (no contraction); o in [0, 1] gives [0, M] without a clip
+__device__ __forceinline__ Rgb stack_round_px(float maxf, const Rgb &o)
+{
+    Rgb q;
+    q.r = (float)(int)(o.r * maxf + 0.5f);
+    q.g = (float)(int)(o.g * maxf + 0.5f);
+    q.b = (float)(int)(o.b * maxf + 0.5f);
+    return q;
+}
+
+#ifdef LUTR_SK_WI
+// ================================================================= vector kernel
+
+extern __shared__ uint32_t stack_lds[];                           // the staged tables: the CDL's floats, then the 1D table's uint16
+
+// The tables the stack uses into LDS, once per workgroup, as whole words (3 * stride floats; 3 * stride uint16 = 3 * stride / 2
+// words, stride = 2^depth >= 256); the launcher sized the dynamic LDS to that.  Every thread of the workgroup must arrive here.
+__device__ __forceinline__ void stack_stage_tables(const StackConsts &S)
+{
+    const uint32_t *__restrict__ a = (const uint32_t *)S.cdl_tab;
+    const uint32_t *__restrict__ b = (const uint32_t *)S.l1d_tab;
+    for (int i = threadIdx.x; i < S.lds_cdl_words; i += 256) stack_lds[i] = a[i];
+    for (int i = threadIdx.x; i < S.lds_l1d_words; i += 256) stack_lds[S.lds_cdl_words + i] = b[i];
+    __syncthreads();
+}
+
+template <int INTERP, int N>
+__device__ __forceinline__ void stack_lattice(bool unit, const LutConsts &X, const GFetch &fx, Rgb (&px)[N])
+{
+    if (unit) {
+#pragma unroll
+        for (int i = 0; i < N; i++) px[i] = lut3d_unit<INTERP>(X, fx, px[i]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; i++) px[i] = lut3d_px<INTERP>(X, fx, px[i].r, px[i].g, px[i].b);
+    }
+}
+
+// The pixels of one union block through the step list.  Every branch depends on kernel arguments only.
+template <bool TRI, int N>
+__device__ __forceinline__ void stack_block(const StackConsts &S, const CdlConsts &C, const uint16_t *l1d, const LutConsts &L,
+                                            const LutConsts &L2, Rgb (&px)[N])
+{
+    const bool mix = S.sat != 1.0f;
+#pragma nounroll
+    for (unsigned long long ops = S.ops; ops & 0xffull; ops >>= 8) {
+        const int op = (int)(ops & 15u), mode = (int)((ops >> 4) & 15u);
+        if (op == STACK_OP_L1D) {
+#pragma unroll
+            for (int i = 0; i < N; i++) px[i] = stack_l1d_px(l1d, S.stride, px[i]);
+        } else if (op == STACK_OP_CDL) {
+#pragma unroll
+            for (int i = 0; i < N; i++) px[i] = cdl_px(C, mix, px[i]);
+        } else if (op == STACK_OP_ROUND) {
+#pragma unroll
+            for (int i = 0; i < N; i++) px[i] = stack_round_px(S.maxf, px[i]);
+        } else {
+            const bool second = op == STACK_OP_LAT2_CODES || op == STACK_OP_LAT2_UNIT;
+            const bool unit = op == STACK_OP_LAT_UNIT || op == STACK_OP_LAT2_UNIT;
+            const LutConsts X = second ? L2 : L;
+            const GFetch fx(X);                                   // each lattice its own fetch; a pixel holds one set of taps
+            if (mode == LUTR_INTERP_TETRAHEDRAL) stack_lattice<LUTR_INTERP_TETRAHEDRAL>(unit, X, fx, px);
+            else if (TRI && mode == LUTR_INTERP_TRILINEAR) stack_lattice<LUTR_INTERP_TRILINEAR>(unit, X, fx, px);
+            else stack_lattice<LUTR_INTERP_NEAREST>(unit, X, fx, px);
+        }
+    }
+}
+
+// k_yuv_l1d_vec's structure (lutr_l1d.hip) with the step walk as the per-block middle.  TRI: some stage is trilinear (a stack of
+// nearest / tetrahedral stages does not carry trilinear's registers).  No thread leaves before the barrier behind the staging.
+template <int WIN, int WOUT, int ICSX, int ICSY, int OCSX, int OCSY, bool TRI, bool LDS>
+__global__ __launch_bounds__(256) void k_yuv_stack_vec(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P, FrameGeom G)
+{
+    constexpr int VB = vec_bytes<WIN, WOUT>();
+    constexpr int PXT = VB / (WIN ? 2 : 1);                       // luma samples per thread per row
+    constexpr int YWI = VB / 4, YWO = PXT * (WOUT ? 2 : 1) / 4;   // luma words per thread per row, in / out
+    constexpr int CSX = cmax(ICSX, OCSX), CSY = cmax(ICSY, OCSY);
+    constexpr int BW = 1 << CSX, BH = 1 << CSY;                   // the union block
+    constexpr int NB = PXT / BW;                                  // union blocks per thread
+    constexpr int IRH = BH >> ICSY, ORH = BH >> OCSY;             // chroma rows per thread, in / out
+    constexpr int IBX = BW >> ICSX, OBX = BW >> OCSX;             // chroma samples per union block and row, in / out
+    constexpr int CWI = (PXT >> ICSX) * (WIN ? 2 : 1) / 4, CWO = (PXT >> OCSX) * (WOUT ? 2 : 1) / 4;
+    static_assert(NB >= 1 && CWI >= 1 && CWO >= 1 && YWO >= 1, "a thread must own whole words");
+    CdlConsts C{S.cdl_tab, S.stride, S.sat};
+    const uint16_t *l1d = S.l1d_tab;
+    if constexpr (LDS) {
+        stack_stage_tables(S);
+        C.tab = (const float *)stack_lds;
+        l1d = (const uint16_t *)(stack_lds + S.lds_cdl_words);
+    }
+    const unsigned uw = (unsigned)G.w / PXT;
+    const unsigned ub = (unsigned)G.rows >> CSY;
+    const unsigned total = uw * ub * (unsigned)G.nframes;
+    for (unsigned u = blockIdx.x * 256u + threadIdx.x; u < total; u += gridDim.x * 256u) {
+        const unsigned xu = u % uw, t = u / uw;
+        const int y0 = ((G.row0 >> CSY) + (int)(t % ub)) * BH;    // first luma row of the thread
+        const long long fr = t / ub;
+        const long long xi = (long long)xu * VB, xo = (long long)xu * (YWO * 4), cxi = (long long)xu * (CWI * 4),
+                        cxo = (long long)xu * (CWO * 4);
+
+        uint32_t yw[BH][YWI], cbw[IRH][CWI], crw[IRH][CWI];
+        uint32_t yo[BH][YWO], cbo[ORH][CWO], cro[ORH][CWO];
+#pragma unroll
+        for (int dy = 0; dy < BH; dy++) {
+            ld_words<YWI>(yw[dy], P.s[0] + fr * P.sfs[0] + (long long)(y0 + dy) * P.ss[0] + xi);
+#pragma unroll
+            for (int k = 0; k < YWO; k++) yo[dy][k] = 0;
+        }
+#pragma unroll
+        for (int iy = 0; iy < IRH; iy++) {
+            const long long r = (long long)((y0 >> ICSY) + iy);
+            ld_words<CWI>(cbw[iy], P.s[1] + fr * P.sfs[1] + r * P.ss[1] + cxi);
+            ld_words<CWI>(crw[iy], P.s[2] + fr * P.sfs[2] + r * P.ss[2] + cxi);
+        }
+#pragma unroll
+        for (int oy = 0; oy < ORH; oy++)
+#pragma unroll
+            for (int k = 0; k < CWO; k++) { cbo[oy][k] = 0; cro[oy][k] = 0; }
+
+#pragma unroll
+        for (int j = 0; j < NB; j++) {
+            Chroma c[IRH][IBX];
+#pragma unroll
+            for (int iy = 0; iy < IRH; iy++)
+#pragma unroll
+                for (int ix = 0; ix < IBX; ix++)
+                    c[iy][ix] = chroma_terms(K, word_sample<WIN>(cbw[iy], j * IBX + ix), word_sample<WIN>(crw[iy], j * IBX + ix));
+            Rgb px[BH * BW];
+#pragma unroll
+            for (int dy = 0; dy < BH; dy++)
+#pragma unroll
+                for (int dx = 0; dx < BW; dx++)
+                    px[dy * BW + dx] = yuv_to_rgb(K, word_sample<WIN>(yw[dy], j * BW + dx), c[dy >> ICSY][dx >> ICSX]);
+            stack_block<TRI>(S, C, l1d, L, L2, px);
+            float rs[ORH][OBX], gs[ORH][OBX], bs[ORH][OBX];
+#pragma unroll
+            for (int oy = 0; oy < ORH; oy++)
+#pragma unroll
+                for (int ox = 0; ox < OBX; ox++) { rs[oy][ox] = 0.f; gs[oy][ox] = 0.f; bs[oy][ox] = 0.f; }
+#pragma unroll
+            for (int dy = 0; dy < BH; dy++) {
+#pragma unroll
+                for (int dx = 0; dx < BW; dx++) {
+                    const Rgb o = px[dy * BW + dx];
+                    rs[dy >> OCSY][dx >> OCSX] += o.r; gs[dy >> OCSY][dx >> OCSX] += o.g; bs[dy >> OCSY][dx >> OCSX] += o.b;
+                    word_put<WOUT>(yo[dy], j * BW + dx, rgb_to_y(K, o));
+                }
+            }
+#pragma unroll
+            for (int oy = 0; oy < ORH; oy++)
+#pragma unroll
+                for (int ox = 0; ox < OBX; ox++) {
+                    const int i = j * OBX + ox;
+                    word_put<WOUT>(cbo[oy], i, rgb_to_cb(K, rs[oy][ox], gs[oy][ox], bs[oy][ox]));
+                    word_put<WOUT>(cro[oy], i, rgb_to_cr(K, rs[oy][ox], gs[oy][ox], bs[oy][ox]));
+                }
+            // Zero-instruction fence (k_yuv_vec's): keeps hipcc from hoisting the coordinates and taps of every union block of the
+            // thread to the top; with it the blocks are emitted one after the other.
+#pragma unroll
+            for (int dy = 0; dy < BH; dy++) {
+#pragma unroll
+                for (int k = 0; k < YWI; k++) asm volatile("" : "+v"(yw[dy][k]));
+#pragma unroll
+                for (int k = 0; k < YWO; k++) asm volatile("" : "+v"(yo[dy][k]));
+            }
+#pragma unroll
+            for (int iy = 0; iy < IRH; iy++)
+#pragma unroll
+                for (int k = 0; k < CWI; k++) asm volatile("" : "+v"(cbw[iy][k]), "+v"(crw[iy][k]));
+#pragma unroll
+            for (int oy = 0; oy < ORH; oy++)
+#pragma unroll
+                for (int k = 0; k < CWO; k++) asm volatile("" : "+v"(cbo[oy][k]), "+v"(cro[oy][k]));
+        }
+#pragma unroll
+        for (int dy = 0; dy < BH; dy++)
+            st_words<YWO>(P.d[0] + fr * P.dfs[0] + (long long)(y0 + dy) * P.ds[0] + xo, yo[dy]);
+#pragma unroll
+        for (int oy = 0; oy < ORH; oy++) {
+            const long long r = (long long)((y0 >> OCSY) + oy);
+            st_words<CWO>(P.d[1] + fr * P.dfs[1] + r * P.ds[1] + cxo, cbo[oy]);
+            st_words<CWO>(P.d[2] + fr * P.dfs[2] + r * P.ds[2] + cxo, cro[oy]);
+        }
+    }
+}
+
+// The vector kernels of this translation unit's container mix; the layout checks are the caller's (launch_yuv_stack).  The grid:
+// with tables in LDS, eight workgroups a CU, each staging once and walking its share of the units; without, the usual cap.
+const char *LUTR_CAT(LUTR_CAT(launch_yuv_stack_vec_w, LUTR_SK_WI), LUTR_SK_WO)(hipStream_t st, const LutConsts &L, const LutConsts &L2,
+                                                                                const StackConsts &S, const YuvConsts &K,
+                                                                                const PlaneSet &P, const FrameGeom &G, int icsx,
+                                                                                int icsy, int ocsx, int ocsy, bool tri, bool lds)
+{
+    constexpr int WI = LUTR_SK_WI, WO = LUTR_SK_WO;
+    constexpr int PXT = vec_bytes<WI, WO>() / (WI ? 2 : 1);
+    const int bh = 1 << cmax(icsy, ocsy);
+    const long long units = (long long)(G.w / PXT) * (G.rows / bh) * G.nframes;
+    const dim3 grid(grid_for(units, lds ? (unsigned)device_cus() * 8u : kGridStrideCap)), block(256);
+    const size_t lds_bytes = lds ? (size_t)(S.lds_cdl_words + S.lds_l1d_words) * sizeof(uint32_t) : 0;
+#define SK_CASE(IX, IY, OX, OY, T) \
+    if (icsx == IX && icsy == IY && ocsx == OX && ocsy == OY && tri == (T != 0)) { \
+        if (lds) hipLaunchKernelGGL((k_yuv_stack_vec<WI, WO, IX, IY, OX, OY, T != 0, true>), grid, block, lds_bytes, st, L, L2, S, K, P, G); \
+        else hipLaunchKernelGGL((k_yuv_stack_vec<WI, WO, IX, IY, OX, OY, T != 0, false>), grid, block, 0, st, L, L2, S, K, P, G); \
+        return lds ? "k_yuv_stack_vec<" LUTR_STR(LUTR_SK_WI) "," LUTR_STR(LUTR_SK_WO) "," #IX "," #IY "," #OX "," #OY "," #T ",1>" \
+                   : "k_yuv_stack_vec<" LUTR_STR(LUTR_SK_WI) "," LUTR_STR(LUTR_SK_WO) "," #IX "," #IY "," #OX "," #OY "," #T ",0>"; \
+    }
+#define SK_PAIR(IX, IY, OX, OY) SK_CASE(IX, IY, OX, OY, 0) SK_CASE(IX, IY, OX, OY, 1)
+    SK_PAIR(1, 1, 1, 1) SK_PAIR(1, 1, 1, 0) SK_PAIR(1, 1, 0, 0)
+    SK_PAIR(1, 0, 1, 1) SK_PAIR(1, 0, 1, 0) SK_PAIR(1, 0, 0, 0)
+    SK_PAIR(0, 0, 1, 1) SK_PAIR(0, 0, 1, 0) SK_PAIR(0, 0, 0, 0)
+#undef SK_PAIR
+#undef SK_CASE
+    return nullptr;
+}
+
+#else  // !LUTR_SK_WI
+// ================================================================= generic kernel
+// One thread per union block; any depth, stride or alignment, odd sizes, all five modes on either lattice.  k_yuv_cdl_generic's
+// walk with the step list per pixel (the tables read from global memory): a pixel outside the frame is the edge pixel again, only
+// pixels and chroma samples inside the planes are written.
+__global__ __launch_bounds__(256) void k_yuv_stack_generic(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P,
+                                                           FrameGeom G, int win, int wout, int icsx, int icsy, int ocsx, int ocsy)
+{
+    const GFetch f(L), f2(L2);
+    PlaneSink sink{K, P, wout};
+    const CdlConsts C{S.cdl_tab, S.stride, S.sat};
+    const bool mix = S.sat != 1.0f;
+    const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy);
+    const int bw = 1 << csx, bh = 1 << csy, obw = 1 << ocsx, obh = 1 << ocsy;
+    const int cwo = (G.w + obw - 1) >> ocsx, cho = (G.h + obh - 1) >> ocsy;
+    for_each_block(G, csx, csy, false, [&](long long fr, int ux, int uy) {
+        for (int oy = 0; oy < bh; oy += obh) {
+            for (int ox = 0; ox < bw; ox += obw) {
+                float rs = 0.f, gs = 0.f, bs = 0.f;
+                for (int dy = 0; dy < obh; dy++) {
+                    const int yy = uy * bh + oy + dy;
+                    const int y = yy < G.h ? yy : G.h - 1;
+                    for (int dx = 0; dx < obw; dx++) {
+                        const int xx = ux * bw + ox + dx;
+                        const int x = xx < G.w ? xx : G.w - 1;
+                        const float cbv = ld_sample(src_row(P, 1, fr, y >> icsy), x >> icsx, win);
+                        const float crv = ld_sample(src_row(P, 2, fr, y >> icsy), x >> icsx, win);
+                        const float yv = ld_sample(src_row(P, 0, fr, y), x, win);
+                        Rgb o = yuv_to_rgb(K, yv, chroma_terms(K, cbv, crv));
+#pragma nounroll
+                        for (unsigned long long ops = S.ops; ops & 0xffull; ops >>= 8) {
+                            const int op = (int)(ops & 15u), mode = (int)((ops >> 4) & 15u);
+                            switch (op) {
+                            case STACK_OP_L1D:        o = stack_l1d_px(S.l1d_tab, S.stride, o); break;
+                            case STACK_OP_CDL:        o = cdl_px(C, mix, o); break;
+                            case STACK_OP_ROUND:      o = stack_round_px(S.maxf, o); break;
+                            case STACK_OP_LAT_CODES:  o = lut3d_px_rt(mode, L, f, o.r, o.g, o.b); break;
+                            case STACK_OP_LAT_UNIT:   o = lut3d_unit_rt(mode, L, f, o); break;
+                            case STACK_OP_LAT2_CODES: o = lut3d_px_rt(mode, L2, f2, o.r, o.g, o.b); break;
+                            default:                  o = lut3d_unit_rt(mode, L2, f2, o); break;
+                            }
+                        }
+                        rs += o.r; gs += o.g; bs += o.b;
+                        if (yy < G.h && xx < G.w) sink.luma(fr, x, y, o);
+                    }
+                }
+                const int ocx = (ux * bw + ox) >> ocsx, ocy = (uy * bh + oy) >> ocsy;
+                if (ocx < cwo && ocy < cho) sink.chroma(fr, ocx, ocy, rs, gs, bs);
+            }
+        }
+    });
+}
+
+// ================================================================= launcher
+// LUTR_STACK_LDS=0 / 1: where the vector kernels read the CDL and 1D tables (tests and tools; unset: the default below).  The
+// tables the stack uses go to LDS together or not at all: above 24 KB in sum they are read from global memory.  The default follows
+// 3.20's measurement of the 1D table.
+constexpr size_t kStackLdsBytes = 24 * 1024;
+constexpr bool kStackLdsDefault = true;
+static bool stack_in_lds(const StackConsts &S)
+{
+    const size_t bytes = (size_t)(S.lds_cdl_words + S.lds_l1d_words) * sizeof(uint32_t);
+    if (bytes == 0 || bytes > kStackLdsBytes) return false;
+    if (const char *e = getenv("LUTR_STACK_LDS")) {
+        if (e[0] == '0' && !e[1]) return false;
+        if (e[0] == '1' && !e[1]) return true;
+    }
+    return kStackLdsDefault;
+}
+
+const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
+                             const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int din, int dout, int icsx, int icsy,
+                             int ocsx, int ocsy)
+{
+    const int win = din > 8, wout = dout > 8;
+    const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy), bh = 1 << csy;
+    // the vector kernels' unit: 8 bytes of luma per row (16 for a 16-bit source written as 8 bit); 8 -> 16 bit has none
+    const bool mix_ok = win == wout || (win && !wout);
+    const int pxt = (win && !wout) ? 8 : (win ? 4 : 8);
+    const long long bsi = win ? 2 : 1, bso = wout ? 2 : 1;
+    const bool batch = G.nframes > 1;
+    const bool lds = stack_in_lds(S);
+    // the lattice steps' modes: the vector kernels have nearest / trilinear / tetrahedral
+    bool modes_ok = true, tri = false;
+    for (unsigned long long ops = S.ops; ops & 0xffull; ops >>= 8) {
+        const int op = (int)(ops & 15u), mode = (int)((ops >> 4) & 15u);
+        if (op == STACK_OP_L1D || op == STACK_OP_CDL || op == STACK_OP_ROUND) continue;
+        modes_ok = modes_ok && vec_mode(mode);
+        tri = tri || mode == LUTR_INTERP_TRILINEAR;
+    }
+    int ran = 0;                                 // bit 0: a vector kernel was launched, bit 1: the generic one
+    auto vec_fits = [&](const PlaneSet &Q, const FrameGeom &H) {
+        if (!mix_ok || !modes_ok) return false;
+        if (H.w % pxt || H.row0 % bh || H.rows % bh) return false;
+        if (!units_fit((long long)(H.w / pxt) * (H.rows / bh) * H.nframes)) return false;
+        if (!plane_ok(Q.s[0], Q.ss[0], Q.sfs[0], pxt * bsi, batch, kStrideAny, false) || !plane_ok(Q.d[0], Q.ds[0], Q.dfs[0], pxt * bso, batch, kStrideAny, false))
+            return false;
+        for (int c = 1; c < 3; c++)
+            if (!plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], (pxt >> icsx) * bsi, batch, kStrideAny, false) ||
+                !plane_ok(Q.d[c], Q.ds[c], Q.dfs[c], (pxt >> ocsx) * bso, batch, kStrideAny, false))
+                return false;
+        return true;
+    };
+    auto vec = [&](const PlaneSet &Q, const FrameGeom &H) -> const char * {
+        ran |= 1;
+        if (win && wout) return launch_yuv_stack_vec_w11(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds);
+        if (win) return launch_yuv_stack_vec_w10(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds);
+        return launch_yuv_stack_vec_w00(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds);
+    };
+    auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
+        ran |= 2;
+        hipLaunchKernelGGL(k_yuv_stack_generic, dim3(block_grid(H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, L2, S, K, Q, H,
+                           win, wout, icsx, icsy, ocsx, ocsy);
+        return "k_yuv_stack_generic";
+    };
+    const char *name = launch_vec_or_generic(variant, P, G, pxt, vec_fits, vec, generic, [&](int wv) {
+        return advance_planes(P, wv * bsi, (wv >> icsx) * bsi, wv * bso, (wv >> ocsx) * bso);
+    });
+    if (!name || ran != 3) return name;
+    // a ragged width split between the two kernels: both are named
+    static thread_local std::string both;
+    both = std::string(name) + "+k_yuv_stack_generic";
+    return both.c_str();
+}
+#endif  // LUTR_SK_WI
+
+}  // namespace lutr

@@ -24,7 +24,7 @@ from .cube import CubeLut, Lut1D, read_cube, read_lut, read_lut1d
 # (the formats and the checks of names and options live in formats.py; the names callers have always imported from here stay)
 from .formats import (_ALPHA_RESIZE, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, V210Fmt, chain_interp, chain_side,  # noqa: F401
                       changes_subsampling, check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc,
-                      check_lut1d_options,
+                      check_lut1d_options, check_stack_options,
                       check_container_options,
                       check_dual_options, check_lut2, check_packed_options, check_premul_options, check_semi_options,
                       chroma_loc_code, dual_side, has_prologue, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt,
@@ -126,6 +126,7 @@ def _byte_range(t: torch.Tensor) -> Tuple[int, int]:
 
 
 _CDL_IN_PLACE = "the CDL pass cannot run in place: destination planes must not overlap the source planes"
+_STACK_IN_PLACE = "the stack pass cannot run in place: destination planes must not overlap the source planes"
 _LUT1D_IN_PLACE = "the lut1d pass cannot run in place: destination planes must not overlap the source planes"
 _RESIZE_IN_PLACE = "a resize cannot run in place: destination planes must not overlap the source planes"
 _RGB2YUV_IN_PLACE = "RGB -> YUV cannot run in place: destination planes must not overlap the source"
@@ -906,6 +907,65 @@ class LutEngine:
             self._bind_stream()
             _native.check(self._lib.lutr_apply_yuv_lut1d(
                 self._ctx, C.byref(p), mode, w, h, nf, C.byref(s), C.byref(d), row0, rows))
+        return dst
+
+    def apply_yuv_stack(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str,
+                        out_pix_fmt: Optional[str] = None, stages, cdl: Optional[Cdl] = None, matrix_in: str = "bt709",
+                        matrix_out: Optional[str] = None, range_src: str = "tv", range_in: Optional[str] = None,
+                        range_out: str = "tv", lut_depth: Optional[int] = None, row0: int = 0, rows: Optional[int] = None,
+                        **other):
+        """`apply_yuv` with an ordered stack of 1..4 stages between its YUV -> RGB and RGB -> YUV stages, in one pass
+        (lutr_apply_yuv_stack).  `stages` is a sequence of "lut3d" (`set_lut`), "lut3d2" (`set_lut2`), "lut1d"
+        (`set_lut1d`), "cdl" (the `cdl` argument), each at most once; a lut3d stage may be a pair ("lut3d", "trilinear") -- the
+        default mode is tetrahedral -- and a comma string "lut1d,cdl,lut3d:trilinear" is read the same way.  Planar YUV on both
+        sides (yuva* with straight alpha included), any layout pair at 8..16 bit, the full-range prologue, row0 / rows on the union
+        block, strict arithmetic, not in place.  ("lut3d",) gives the bits of `apply_yuv(out_pix_fmt=...)`, ("cdl", "lut3d") those
+        of `apply_yuv(cdl=...)`, ("lut1d", "lut3d") those of `apply_yuv_lut1d`, ("lut3d", "lut3d2") those of `apply_yuv_chain`.  No
+        dither, chroma_loc, out_size, premultiplied alpha or second output, and no RGB / float / semi-planar / packed / v210 side:
+        each is a ValueError naming it (`formats.check_stack_options`)."""
+        for k in other:
+            if k not in ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt"):
+                raise TypeError(f"apply_yuv_stack() got an unexpected keyword argument '{k}'")
+        if cdl is not None and not isinstance(cdl, Cdl):
+            raise TypeError(f"cdl must be a lut_renderer_amd.cdl.Cdl, not {type(cdl).__name__}")
+        st, fin, fout = check_stack_options(
+            pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(self, "n", 0)),
+            lut2=bool(getattr(self, "n2", 0)), lut1d=bool(getattr(self, "n1d", 0)), prelut=bool(getattr(self, "_has_prelut", False)),
+            dither=other.get("dither", "none"), chroma_loc=other.get("chroma_loc"), out_size=other.get("out_size"),
+            alpha_mode=other.get("alpha_mode", "straight"), out2_pix_fmt=other.get("out2_pix_fmt"))
+        if fin.alpha or fout.alpha:
+            # yuva*: the colour planes through this very call under their three-plane names, then the alpha plane on the same
+            # stream, exactly as the CDL call does (DESIGN.md 3.16)
+            if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
+                raise ValueError(_PLANE_COUNT[fin.nplanes].format(fin.name))
+            h, w = src[0].shape[-2], src[0].shape[-1]
+            _check_planes(src, fin, w, h, "source")
+            if dst is None:
+                dst = _fresh_planes(fout, w, h, src[0], self.device)
+            _check_planes(dst, fout, w, h, "destination")
+            a_src = src[3] if fin.alpha and not has_prologue(fin.depth, range_src, range_in, lut_depth) else None
+            if fout.alpha:
+                _check_alpha_overlap(a_src, fin.depth, dst, fout.depth)
+            self._alpha_tail(lambda: self.apply_yuv_stack(
+                src[:3], dst[:3], pix_fmt=fin.colour.name, out_pix_fmt=fout.colour.name, stages=st, cdl=cdl, matrix_in=matrix_in,
+                matrix_out=matrix_out, range_src=range_src, range_in=range_in, range_out=range_out, lut_depth=lut_depth, row0=row0,
+                rows=rows), [(fout, dst)], a_src, fin.depth, w, h, row0, rows)
+            return dst
+        p = _yuv_call_params(fin, fout, lut_depth, matrix_in, matrix_out, range_src, range_in, range_out)
+        h, w = src[0].shape[-2], src[0].shape[-1]
+        if dst is None:
+            dst = _fresh_planes(fout, w, h, src[0], self.device)
+        _check_planes(src, fin, w, h, "source")
+        _check_planes(dst, fout, w, h, "destination")
+        _check_not_in_place(src, dst, _STACK_IN_PLACE)
+        s, d, nf = _plane_pair(src, dst, self.device)
+        rows = h - row0 if rows is None else rows
+        arr = _native.stage_array(st)
+        k = None if cdl is None else C.byref(_native.cdl_struct(cdl))
+        with self._lock:
+            self._bind_stream()
+            _native.check(self._lib.lutr_apply_yuv_stack(
+                self._ctx, C.byref(p), arr, len(st), k, w, h, nf, C.byref(s), C.byref(d), row0, rows))
         return dst
 
     def apply_rgb_lut1d(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, depth: int,

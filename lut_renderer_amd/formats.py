@@ -565,6 +565,100 @@ def check_lut1d_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = Non
     return fin, fout
 
 
+#: the stage kinds of a stack and enum lutr_stage_kind
+STAGE_KINDS = _native.STAGE_KINDS
+MAX_STAGES = 4
+
+
+def parse_stages(stages, interp: Optional[str] = None, interp2: Optional[str] = None) -> Tuple[Tuple[str, Optional[str]], ...]:
+    """The one parser of a stage list.  `stages` is a comma string ("lut1d,cdl,lut3d:trilinear") or a sequence
+    of names and (name, mode) pairs.  Returns ((kind, mode), ...): mode is a lut3d mode name for the two lut3d kinds -- the
+    stage's own, else `interp` (lut3d) / `interp2` (lut3d2; None = `interp`), else tetrahedral -- and None for lut1d and cdl.
+    ValueError: an empty list, more than four stages, an unknown kind, a kind twice, a mode on lut1d / cdl, an unknown mode."""
+    if isinstance(stages, str):
+        items = [s.strip() for s in stages.split(",")] if stages.strip() else []
+    elif stages is None:
+        items = []
+    else:
+        items = list(stages)
+    if not items:
+        raise ValueError("the stage list is empty: a stack has 1 to 4 stages (lut3d | lut3d2 | lut1d | cdl)")
+    if len(items) > MAX_STAGES:
+        raise ValueError(f"the stage list has {len(items)} stages: a stack has 1 to {MAX_STAGES}")
+    out = []
+    for item in items:
+        if isinstance(item, str):
+            kind, colon, mode = (part.strip() for part in item.partition(":"))
+            if colon and not mode:
+                raise ValueError(f"stage '{item}' names no mode after ':'")
+            mode = mode or None
+        else:
+            try:
+                kind, mode = item
+            except (TypeError, ValueError):
+                raise ValueError(f"a stage is a name or a (name, mode) pair, not {item!r}") from None
+        if kind not in STAGE_KINDS:
+            raise ValueError(f"unknown stage kind '{kind}' ({' | '.join(STAGE_KINDS)})")
+        if any(kind == k for k, _m in out):
+            raise ValueError(f"stage kind '{kind}' is listed twice: each kind may appear once")
+        if kind in ("lut3d", "lut3d2"):
+            if mode is None:
+                mode = (interp if kind == "lut3d" else (interp2 or interp)) or "tetrahedral"
+            if mode not in _native.INTERP:
+                raise ValueError(f"lut3d has no interpolation mode '{mode}' (stage '{kind}')")
+        elif mode is not None:
+            raise ValueError(f"stage '{kind}' takes no mode ('{mode}')")
+        out.append((kind, mode))
+    return tuple(out)
+
+
+def stages_string(stages) -> str:
+    """The comma string of a parsed stage list, every lut3d stage with its mode: what `--stages` carries."""
+    return ",".join(k if m is None else f"{k}:{m}" for k, m in parse_stages(stages))
+
+
+def check_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = None, *, stages, cdl: bool = False,
+                        lut: bool = True, lut2: bool = True, lut1d: bool = True, prelut: bool = False, dither: str = "none",
+                        chroma_loc: Optional[str] = None, out_size=None, alpha_mode: str = "straight",
+                        out2_pix_fmt: Optional[str] = None, variant: Optional[str] = None):
+    """The checks every layer makes of a stage stack before any GPU work, the one copy of its refusals: a stage
+    list `parse_stages` takes; every listed stage's resource there (`lut`, `lut2`, `lut1d`: a first / second lattice, a 1D LUT is
+    loaded; `cdl`: a CDL is given) and no CDL without a cdl stage; no lut3d directly behind cdl when the first LUT carries a .csp
+    prelut (`prelut`); planar YUV on both sides (yuva* with straight alpha included); no dither, chroma_loc, out_size, second
+    output or premultiplied alpha; not the vec_lds variant.  Returns (parsed stages, source format, output format)."""
+    tail = "a stage stack"
+    st = parse_stages(stages)
+    kinds = [k for k, _m in st]
+    if "lut3d" in kinds and not lut:
+        raise ValueError("stage 'lut3d' is listed and no 3D LUT is loaded: call set_lut / load_cube first, or pass cube")
+    if "lut3d2" in kinds and not lut2:
+        raise ValueError("stage 'lut3d2' is listed and no second LUT is loaded: call set_lut2 / load_cube2 first, or pass cube2")
+    if "lut1d" in kinds and not lut1d:
+        raise ValueError("stage 'lut1d' is listed and no 1D LUT is loaded: call set_lut1d / load_lut1d first, or pass lut1d")
+    if "cdl" in kinds and not cdl:
+        raise ValueError("stage 'cdl' is listed and no CDL is given: pass cdl")
+    if cdl and "cdl" not in kinds:
+        raise ValueError("a CDL is given and the stage list has no 'cdl' stage")
+    if prelut and "cdl" in kinds and kinds.index("cdl") + 1 < len(kinds) and kinds[kinds.index("cdl") + 1] == "lut3d":
+        raise ValueError("stage 'lut3d' directly behind 'cdl' is not supported with a LUT that carries a .csp prelut: the prelut's "
+                         "table is indexed by integer codes, and the CDL's output is not a code")
+    fin = _pass_side(pix_fmt, "pix_fmt", "stack", "both sides", True, alpha_ok=True)
+    fout = _pass_side(out_pix_fmt or pix_fmt, "out_pix_fmt", "stack", "both sides", True, alpha_ok=True)
+    if dither != "none":
+        raise ValueError(f"dither ('{dither}') is not supported with {tail}")
+    if chroma_loc is not None:
+        raise ValueError(f"sited chroma resampling (chroma_loc) is not supported with {tail}")
+    if out_size is not None:
+        raise ValueError(f"a resize (out_size / resolution) is not supported with {tail}")
+    if out2_pix_fmt is not None:
+        raise ValueError(f"the two-output pass (out2_pix_fmt) is not supported with {tail}")
+    if alpha_mode != "straight":
+        raise ValueError(f"alpha_mode='{alpha_mode}' is not supported with {tail}")
+    if variant == "vec_lds":
+        raise ValueError(f"variant vec_lds is not supported with {tail}: there is no LDS-window kernel for the stack pass")
+    return st, fin, fout
+
+
 #: how the colour planes of an alpha-carrying source stand to their alpha (DESIGN.md 3.18)
 ALPHA_MODES = ("straight", "premultiplied")
 

@@ -29,7 +29,7 @@ import torch
 from . import _native
 from .cube import CubeLut, read_lut, read_lut1d
 from .engine import LutEngine, _fresh_planes, _new_planes, _yuv_out_dtype, chain_args, dual_args
-from .formats import (check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2,
+from .formats import (check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2, check_stack_options,
                       check_premul_options,
                       packed_frame_width, parse_pix_fmt, parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords,
                       v210_frame_width, yuv_side)
@@ -346,6 +346,36 @@ class LutEngineGroup:
 
             def remote(eng, r0, r1):
                 out = eng.apply_yuv_lut1d(_travel(src, _row_ranges(fin, r0, r1), eng.device), None, **names, **kw)
+                return [(dst, out, _row_ranges(fout, r0, r1))]
+
+            self._shard(h, 1 << max(fin.csy, fout.csy), home, local, remote)
+            return dst
+
+    def apply_yuv_stack(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str,
+                        out_pix_fmt: Optional[str] = None, stages, cdl=None, **kw):
+        """`LutEngine.apply_yuv_stack` with the rows of every frame split over the group's devices: the lattices
+        and the 1D LUT are on every engine through the group's setters, the CDL travels with the call; shards on multiples of the
+        union block height of the two layouts, alpha rows go with the luma rows, no halo."""
+        with self._lock:
+            if "row0" in kw or "rows" in kw:
+                raise ValueError("the group owns the row partition")
+            e0 = self.engines[0]
+            st, fin, fout = check_stack_options(
+                pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(e0, "n", 0)),
+                lut2=bool(getattr(e0, "n2", 0)), lut1d=bool(self.n1d), prelut=bool(getattr(e0, "_has_prelut", False)),
+                dither=kw.get("dither", "none"), chroma_loc=kw.get("chroma_loc"), out_size=kw.get("out_size"),
+                alpha_mode=kw.get("alpha_mode", "straight"), out2_pix_fmt=kw.get("out2_pix_fmt"))
+            h, w = src[0].shape[-2], src[0].shape[-1]
+            home = src[0].device
+            if dst is None:
+                dst = _fresh_planes(fout, w, h, src[0], home)
+            names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, stages=st, cdl=cdl)
+
+            def local(eng, r0, r1):
+                eng.apply_yuv_stack(src, dst, row0=r0, rows=r1 - r0, **names, **kw)
+
+            def remote(eng, r0, r1):
+                out = eng.apply_yuv_stack(_travel(src, _row_ranges(fin, r0, r1), eng.device), None, **names, **kw)
                 return [(dst, out, _row_ranges(fout, r0, r1))]
 
             self._shard(h, 1 << max(fin.csy, fout.csy), home, local, remote)

@@ -50,7 +50,7 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
                           engine_dither: Optional[str] = None, cube2: Optional[Path] = None,
                           interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None,
                           cdl_id: Optional[str] = None, lut1d: Optional[Path] = None,
-                          interp1d: Optional[str] = None) -> StageCommands:
+                          interp1d: Optional[str] = None, stages=None) -> StageCommands:
     """The three argv lists of one LUT stage.  Raises what `build_command` / `engine_command` raise (copy guard, missing
     geometry).  `chroma_loc` goes to the engine (`--chroma-loc`) and, as `-chroma_sample_location`, to the encoder, so the
     output stream declares the siting the engine assumed.  `gpu_resize` with `params.resolution` set resizes in the engine
@@ -59,12 +59,13 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
     pass).  `alpha_mode` ("premultiplied") goes to the engine alone (`--alpha-mode`): ffmpeg's chain
     has no such step, so the decoder and encoder argv are untouched.  The same holds for `cdl` / `cdl_id` (an ASC CDL ahead of the
     LUT, DESIGN.md 3.19: `--cdl` / `--cdl-id`, or `--cdl-sop` / `--cdl-sat` for a `cdl.Cdl`) and for `lut1d` / `interp1d` (a 1D LUT
-    file ahead of the LUT, DESIGN.md 3.20: `--lut1d` / `--interp1d`)."""
+    file ahead of the LUT, DESIGN.md 3.20: `--lut1d` / `--interp1d`), and for `stages` (these operators as an ordered stack in one
+    pass, DESIGN.md 3.21: `--stages`, rendered only when given)."""
     notes: List[str] = []
     engine = engine_command(Path("-"), Path("-"), params, lut_path, source_info, python_bin=python_bin, device=device, notes=notes,
                             precision=precision, chroma_loc=chroma_loc, gpu_resize=gpu_resize, engine_dither=engine_dither,
                             cube2=cube2, interp2=interp2, alpha_mode=alpha_mode, cdl=cdl, cdl_id=cdl_id, lut1d=lut1d,
-                            interp1d=interp1d)
+                            interp1d=interp1d, **({} if stages is None else {"stages": stages}))
     resized = gpu_resize and bool(params.resolution)
     if source_info.duration:
         engine += ["--duration", f"{float(source_info.duration):.3f}"]
@@ -161,6 +162,7 @@ def main(argv=None) -> int:
     ap.add_argument("--cdl-sat", default=None, type=float, help="the CDL's saturation as a literal value")
     ap.add_argument("--lut1d", default=None, help="engine setting: a 1D LUT file ahead of --cube, see lut_renderer_amd.cli")
     ap.add_argument("--interp1d", default=None, help="interpolation mode of --lut1d, see lut_renderer_amd.cli")
+    ap.add_argument("--stages", default=None, help="engine setting: the operators as an ordered stack, see lut_renderer_amd.cli")
     ap.add_argument("--gpu-resize", action="store_true", help="resize to the params' resolution in the engine (--out-size) instead of the encoder")
     a = ap.parse_args(argv)
     try:
@@ -176,7 +178,8 @@ def main(argv=None) -> int:
                                      precision=a.precision, chroma_loc=a.chroma_loc, gpu_resize=a.gpu_resize,
                                      engine_dither=a.engine_dither, cube2=None if a.cube2 is None else Path(a.cube2),
                                      interp2=a.interp2, alpha_mode=a.alpha_mode, cdl=cdl, cdl_id=a.cdl_id,
-                                     lut1d=None if a.lut1d is None else Path(a.lut1d), interp1d=a.interp1d)
+                                     lut1d=None if a.lut1d is None else Path(a.lut1d), interp1d=a.interp1d,
+                                     stages=a.stages)
     except Exception as exc:
         print(f"Error: {exc}", flush=True)
         return 1

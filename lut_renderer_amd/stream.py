@@ -20,7 +20,7 @@ import torch
 
 from .engine import LutEngine
 from .formats import (RgbSource, check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options,
-                      check_lut1d_options,
+                      check_lut1d_options, check_stack_options,
                       check_premul_options, parse_rgb_source, parse_size, premul_to_yuv, refuse_alpha_resize, yuv_side)
 
 
@@ -144,6 +144,20 @@ class HostPipeline:
         (`fout2`); `run` then takes a second drain.
         `chain`: the engine holds a second LUT (`set_lut2`) and every batch goes through `apply_yuv_chain` (DESIGN.md 3.17);
         `apply_kw` may carry `interp2`.  Planar YUV without alpha on both sides, no dither, chroma_loc, out_size or second output."""
+        # `apply_kw["stages"]`: every batch goes through `apply_yuv_stack` (DESIGN.md 3.21) with the lattices and the 1D LUT the
+        # engine holds and `apply_kw["cdl"]`; `chain` / `lut1d` are not set then
+        stages = apply_kw.get("stages")
+        self.stack = stages is not None
+        if self.stack:
+            if chain or lut1d:
+                raise ValueError("a stage stack names its lut3d2 / lut1d stages itself: chain / lut1d are not set with stages")
+            check_stack_options(pix_fmt, out_pix_fmt, stages=stages, cdl=apply_kw.get("cdl") is not None,
+                                lut=bool(getattr(engine, "n", 0)), lut2=bool(getattr(engine, "n2", 0)),
+                                lut1d=bool(getattr(engine, "n1d", 0)), prelut=bool(getattr(engine, "_has_prelut", False)),
+                                dither=apply_kw.get("dither", "none"), chroma_loc=apply_kw.get("chroma_loc"), out_size=out_size,
+                                alpha_mode=apply_kw.get("alpha_mode", "straight"), out2_pix_fmt=second_pix_fmt)
+            apply_kw = {k: v for k, v in apply_kw.items() if k not in ("dither", "alpha_mode", "interp") and
+                        not (k == "cdl" and v is None)}
         self.chain = bool(chain)
         # `lut1d`: the engine holds a 1D LUT (`set_lut1d`) and every batch goes through `apply_yuv_lut1d` (DESIGN.md 3.20);
         # `apply_kw["interp"]` None is lut1d alone
@@ -158,7 +172,9 @@ class HostPipeline:
         else:
             apply_kw = {k: v for k, v in apply_kw.items() if k != "alpha_mode"}
         # a CDL in front of the LUT travels in apply_kw too, as a `cdl.Cdl`; None is not passed on
-        if apply_kw.get("cdl") is not None:
+        if self.stack:                                         # (checked above: the CDL is a stage of the stack)
+            pass
+        elif apply_kw.get("cdl") is not None:
             check_cdl_options(pix_fmt, out_pix_fmt, dither=apply_kw.get("dither", "none"), chroma_loc=apply_kw.get("chroma_loc"),
                               out_size=out_size, alpha_mode=apply_kw.get("alpha_mode", "straight"), out2_pix_fmt=second_pix_fmt,
                               lut2=self.chain, prelut=bool(getattr(engine, "_has_prelut", False)))
@@ -230,7 +246,9 @@ class HostPipeline:
         with torch.cuda.stream(self.s_run):
             self.s_run.wait_event(self.e_in[slot])
             dst = self.fout.plane_views(self.d_out[slot], nframes)
-            if self.lut1d:
+            if self.stack:
+                self.eng.apply_yuv_stack(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
+            elif self.lut1d:
                 self.eng.apply_yuv_lut1d(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
             elif self.chain:
                 self.eng.apply_yuv_chain(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
