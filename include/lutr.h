@@ -766,6 +766,30 @@ typedef struct lutr_stage {
 int lutr_apply_yuv_stack(lutr_ctx *ctx, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl, int w,
                          int h, int nframes, const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
 
+/* ---- LUT strength: the "intensity" / "opacity" / key-gain control of a grade -- the graded pixel mixed with the
+ *      source behind the stage list, in the one place where both are in registers as RGB codes. ----
+ * lutr_apply_yuv_stack's pass with one step behind the list.  With M = 2^lut_depth - 1, q0_c the pixel's codes behind the YUV -> RGB
+ * stage, q1_c the codes the list ends with (behind the closing unit -> codes rounding) and s the strength of the pixel's frame, in
+ * fp32 with every operation rounded on its own:
+ *   s'  = fminf(fmaxf(s, 0), 1), a NaN taken as 0
+ *   q_c = (int)((q0_c + s' * (q1_c - q0_c)) + 0.5f)        the difference is exact; product, sum, sum: three roundings
+ * and q_c feeds the RGB -> YUV stage as q1_c does in lutr_apply_yuv_stack.  q_c lies between q0_c and q1_c: no clip.  s = 1 gives
+ * lutr_apply_yuv_stack's output bit for bit, s = 0 gives the source through the two conversion stages alone ({CDL} with the
+ * identity CDL).
+ * `frame_strength` = NULL: every frame takes `strength`.  Otherwise it points to nframes floats in device memory, read by the
+ * kernel on the context's stream (the caller keeps them alive, as it does the planes): frame f of the call takes
+ * frame_strength[f], f counted from the first frame of the call whatever row0 / rows are -- row shards give the bits of the whole
+ * call -- and `strength` is not read.
+ * Every refusal of lutr_apply_yuv_stack, and LUTR_EINVAL for a `strength` that is NaN or outside [0, 1] when frame_strength is
+ * NULL (the values of the array cannot be seen from the host: the kernels clamp them).
+ * Kernels: always the mix forms, at strength 1 as well -- "k_yuv_stack_mix_vec<win,wout,icsx,icsy,ocsx,ocsy,tri,lds>[stages]",
+ * "k_yuv_stack_mix_generic[stages]", "<vector kernel>+k_yuv_stack_mix_generic[stages]" for a ragged width, chosen by the rules of
+ * lutr_apply_yuv_stack; both table placements give the same bits.
+ * Not covered: what lutr_apply_yuv_stack does not cover; a tile (LDS window) kernel; a strength per pixel (a matte). */
+int lutr_apply_yuv_stack_mix(lutr_ctx *ctx, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                             float strength, const float *frame_strength, int w, int h, int nframes, const lutr_planes *src,
+                             const lutr_planes *dst, int row0, int rows);
+
 /* ---- the alpha plane of yuva* / gbrap* frames: ProRes 4444 (yuva444p10le / 12le), VP8 / VP9 with alpha
  *      (yuva420p), PNG / TIFF / EXR sequences with alpha (rgba, rgba64le, gbrap*, gbrapf32le).  In the reference's chain lut3d
  *      copies the alpha plane through and format=<pix_fmt> keeps, converts, drops or makes it (ffmpeg.py:246, :304-310) ---- */

@@ -24,7 +24,7 @@ from typing import Dict, Optional, Sequence, Tuple
 from .cdl import as_cdl
 from .cube import CubeLut, as_lut1d, read_cube, read_lut, read_lut1d
 from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc, check_container_options,
-                      check_dual_options, check_lut1d_options, check_lut2, check_premul_options, check_stack_options, packed_frame_width, parse_packed_yuv_fmt,
+                      check_dual_options, check_lut1d_options, check_lut2, check_premul_options, check_stack_options, implied_stages, packed_frame_width, parse_packed_yuv_fmt,
                       parse_pix_fmt, parse_rgb_source, parse_semi_fmt, parse_size, parse_stages, parse_v210_fmt, premul_to_yuv,
                       refuse_alpha_resize, source_bit_depth, v210_frame_width, yuv_side)
 from .params import ProcessingParams, VideoInfo
@@ -210,12 +210,15 @@ def resolve_engine_dither(engine_dither: str, dither: str = "none") -> str:
 
 
 def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, engine, devices, precision,
-                 chroma_loc, out_size, alpha_mode, second_pix_fmt):
+                 chroma_loc, out_size, alpha_mode, second_pix_fmt, strength=None):
     """`apply_lut(stages=...)`: load what the list names, with the caches the single-feature routes use, and
-    route to `apply_yuv_stack`.  `kw` is what `engine_call_for` returned, with `dither` filled in."""
+    route to `apply_yuv_stack`.  `kw` is what `engine_call_for` returned, with `dither` filled in.  `strength`
+    travels to the engine; `stages` None is then the list the other options imply."""
     from .plan import INTERP_WHITELIST
     from . import _native
     mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
+    if stages is None:
+        stages = implied_stages(cube is not None, cube2 is not None, lut1d is not None, cdl is not None)
     st = parse_stages(stages, interp=kw.get("interp"), interp2=mode2)
     kinds = [k for k, _m in st]
     if interp1d not in _native.INTERP1D:
@@ -240,7 +243,7 @@ def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d,
     check_stack_options(kw["pix_fmt"], kw["out_pix_fmt"], stages=st, cdl=cdl is not None, lut=lut is not None or held("n"),
                         lut2=lut2 is not None or held("n2"), lut1d=lut1d is not None or held("n1d"), prelut=prelut,
                         dither=kw.get("dither", "none"), chroma_loc=chroma_loc, out_size=out_size, alpha_mode=alpha_mode,
-                        out2_pix_fmt=second_pix_fmt)
+                        out2_pix_fmt=second_pix_fmt, strength=strength, precision=precision)
     own = engine is None
     eng = engine if engine is not None else _cached_engine(devices)
     call = {k: v for k, v in kw.items() if k not in ("dither", "interp", "alpha_mode")}
@@ -258,6 +261,8 @@ def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d,
                 eng._applied_lut1d = (lut1d, interp1d)
         if eng.precision != precision:
             eng.set_precision(precision)
+        if strength is not None:
+            call["strength"] = strength
         result = eng.apply_yuv_stack(planes, out, stages=st, cdl=cdl, **call)
         if own:
             eng.sync()
@@ -271,7 +276,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               devices: Sequence[int] = (0,), precision: str = "strict", chroma_loc: Optional[str] = None,
               resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
               cube2=None, interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None, cdl_id: Optional[str] = None,
-              lut1d=None, interp1d: str = "linear", stages=None):
+              lut1d=None, interp1d: str = "linear", stages=None, strength=None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -357,7 +362,16 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     Only with `stages` may these be combined freely.  Every stage listed needs its file (or an `engine` that holds it) and every
     file given needs its stage: anything else is a ValueError.  Planar YUV on both sides (yuva* with straight alpha included), a
     LutEngineGroup row-shards it, always strict arithmetic; no dither, chroma_loc, resolution, second output or premultiplied
-    alpha.  Without `stages` the function is unchanged."""
+    alpha.  Without `stages` the function is unchanged.
+
+    `strength` (the intensity / opacity control of a grade) mixes the graded pixel with the source behind the
+    stages, as RGB codes, in the same pass: a number in [0, 1] for every frame, or a sequence / NumPy array / CPU tensor of one
+    number per frame (a ramp).  1 gives the bits of the call without it, 0 the source through the two conversion stages.  It runs
+    the stage stack: with `stages` that list, without it the list the other options imply -- lut1d, cdl, lut3d, lut3d2 in that
+    order, so `cube` is ("lut3d",), `cdl` + `cube` ("cdl", "lut3d"), `lut1d` + `cube` ("lut1d", "lut3d"), `lut1d` alone ("lut1d",),
+    `cube` + `cube2` ("lut3d", "lut3d2") -- on the stack's terms: whatever the stack refuses is refused with `strength`, in a
+    message that names both, and so is a `precision` other than strict.  A plain `cube` with a strength therefore runs the
+    stack's gather kernel, not the LDS-window tile kernel.  None (default) leaves every route as it is."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -405,9 +419,9 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         check_premul_options(kw["pix_fmt"], kw["out_pix_fmt"], dither=kw["dither"], chroma_loc=chroma_loc, out_size=out_size,
                              range_src=kw.get("range_src", "tv"), range_in=kw.get("range_in"), lut_depth=kw.get("lut_depth"),
                              out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None)
-    if stages is not None:
+    if stages is not None or strength is not None:
         result = _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, engine, devices, precision,
-                              chroma_loc, out_size, alpha_mode, second_pix_fmt)
+                              chroma_loc, out_size, alpha_mode, second_pix_fmt, strength)
         return result, output_color_tags(plan.output_policy)
     if lut1d is not None:
         check_lut1d_options(kw["pix_fmt"], kw["out_pix_fmt"], interp1d=interp1d, dither=kw["dither"], chroma_loc=chroma_loc,

@@ -20,7 +20,7 @@ import signal
 import sys
 import time
 
-from .formats import (check_cdl_options, check_chroma_loc, check_container_options, check_lut1d_options, check_lut2, check_stack_options, parse_stages,
+from .formats import (check_cdl_options, check_chroma_loc, check_container_options, check_lut1d_options, check_lut2, check_stack_options, implied_stages, parse_stages,
                       check_premul_options, parse_size, refuse_alpha_resize, source_bit_depth)
 
 
@@ -107,6 +107,16 @@ def build_parser() -> argparse.ArgumentParser:
                          "stages, a lut3d stage without a mode takes --interp / --interp2; every stage needs its file and every "
                          "file its stage; planar YUV on both sides, no dither, --chroma-loc, --out-size, --second-output or "
                          "--alpha-mode premultiplied")
+    mix = ap.add_mutually_exclusive_group()
+    mix.add_argument("--strength", default=None, type=float, metavar="X",
+                     help="engine setting: LUT strength in [0, 1] (DESIGN.md 3.22; the intensity / opacity control of a grade) -- "
+                          "the graded pixel is mixed with the source as RGB codes behind the stages, in the same pass: 1 = the "
+                          "look, 0 = the source.  Runs the stage stack: with --stages that list, without it the list the other "
+                          "options imply (lut1d, cdl, lut3d, lut3d2 in that order), on the stack's terms")
+    mix.add_argument("--strength-keys", default=None, metavar="F:S,F:S,...",
+                     help="engine setting: LUT strength by key frames -- frame F of the stream (counted from 0 across batches) "
+                          "takes strength S, linear between the keys, held before the first and behind the last; e.g. 0:0,24:1 "
+                          "ramps the look in over the first second.  Not together with --strength")
     ap.add_argument("-y", action="store_true", help="overwrite the output (ffmpeg's -y)")
     ap.add_argument("--duration", type=float, default=None,
                     help="seconds of video, for the Duration: line when the input is a pipe (-i -) and cannot be measured")
@@ -131,13 +141,18 @@ def cdl_from_args(args):
 def stack_call_from_args(args, kw: dict, cdl) -> dict:
     """The keyword arguments of `apply_yuv_stack` for --stages from those `engine_call_for` returned: the stage
     list parsed with --interp / --interp2 as the lut3d stages' defaults, every refusal of `check_stack_options`, and a file for
-    every stage and a stage for every file."""
+    every stage and a stage for every file.  With --strength / --strength-keys and no --stages the list is the
+    one the other options imply (`formats.implied_stages`); `strength` or `strength_keys` (the parsed callable) go into the call."""
     from .plan import INTERP_WHITELIST
     interp2 = getattr(args, "interp2", None)
     mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
-    st = parse_stages(args.stages, interp=kw.get("interp"), interp2=mode2)
-    kinds = [k for k, _m in st]
     cube2, lut1d = getattr(args, "cube2", None), getattr(args, "lut1d", None)
+    strength, keys = strength_from_args(args)
+    listed = getattr(args, "stages", None)
+    if listed is None:
+        listed = implied_stages(args.cube is not None, cube2 is not None, lut1d is not None, cdl is not None)
+    st = parse_stages(listed, interp=kw.get("interp"), interp2=mode2)
+    kinds = [k for k, _m in st]
     for flag, given, kind in (("--cube", args.cube, "lut3d"), ("--cube2", cube2, "lut3d2"), ("--lut1d", lut1d, "lut1d"),
                               ("--cdl / --cdl-sop / --cdl-sat", cdl, "cdl")):
         if given is not None and kind not in kinds:
@@ -161,12 +176,29 @@ def stack_call_from_args(args, kw: dict, cdl) -> dict:
                         dither="error_diffusion" if args.zscale_dither == "error_diffusion" else engine_dither or "none",
                         chroma_loc=getattr(args, "chroma_loc", None), out_size=getattr(args, "out_size", None),
                         alpha_mode=getattr(args, "alpha_mode", None) or "straight",
-                        out2_pix_fmt=second_fmt if second_fmt is not None else second_out)
+                        out2_pix_fmt=second_fmt if second_fmt is not None else second_out,
+                        strength=strength if keys is None else 1.0, precision=getattr(args, "precision", None))
     call = {k: v for k, v in kw.items() if k not in ("interp", "alpha_mode", "dither")}
     call["stages"] = st
     if cdl is not None:
         call["cdl"] = cdl
+    if strength is not None:
+        call["strength"] = strength
+    if keys is not None:
+        call["strength_keys"] = keys
     return call
+
+
+def strength_from_args(args):
+    """(--strength as a float or None, --strength-keys as `params.strength_keys`' callable or None); both together are an error
+    (the parser refuses them already; a namespace made by hand gets here)."""
+    strength, text = getattr(args, "strength", None), getattr(args, "strength_keys", None)
+    if strength is not None and text is not None:
+        raise ValueError("--strength and --strength-keys are mutually exclusive")
+    if text is None:
+        return strength, None
+    from .params import strength_keys
+    return None, strength_keys(text)
 
 
 def plan_from_args(args):
@@ -195,7 +227,8 @@ def plan_from_args(args):
                              range_in=kw.get("range_in"), lut_depth=kw.get("lut_depth"),
                              out2_pix_fmt=getattr(args, "second_pix_fmt", None), lut2=getattr(args, "cube2", None) is not None)
     cdl = cdl_from_args(args)
-    if stages is not None:
+    mixed = getattr(args, "strength", None) is not None or getattr(args, "strength_keys", None) is not None
+    if stages is not None or mixed:
         return plan, stack_call_from_args(args, kw, cdl), w, h
     if lut1d is not None:
         check_lut1d_options(kw["pix_fmt"], kw["out_pix_fmt"], interp1d=getattr(args, "interp1d", None) or "linear",
@@ -300,8 +333,8 @@ def main(argv=None) -> int:
         pix_fmt, out_fmt = kw.pop("pix_fmt"), kw.pop("out_pix_fmt")
         second_fmt = kw.pop("out2_pix_fmt", None)
         pipe = HostPipeline(eng, pix_fmt, w, h, batch=args.batch, out_pix_fmt=out_fmt, out_size=args.out_size,
-                            second_pix_fmt=second_fmt, chain=lut2 is not None and args.stages is None,
-                            lut1d=args.lut1d is not None and args.stages is None, **kw)
+                            second_pix_fmt=second_fmt, chain=lut2 is not None and "stages" not in kw,
+                            lut1d=args.lut1d is not None and "stages" not in kw, **kw)
         fb = pipe.fin.frame_bytes
         if piped_in:
             total = None if args.duration is None else max(1, int(round(args.duration * args.fps)))

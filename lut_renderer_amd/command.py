@@ -20,7 +20,7 @@ from pathlib import Path
 from typing import List, Optional, Tuple
 
 from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options, check_lut1d_options,
-                      check_premul_options, check_stack_options, parse_stages, stages_string, parse_rgb_source, premul_to_yuv)
+                      check_premul_options, check_stack_options, implied_stages, parse_stages, stages_string, parse_rgb_source, premul_to_yuv)
 from .params import ProcessingParams, Task, VideoInfo
 from .plan import LutPlan, output_color_tags, resolve_lut_plan, resolve_pix_fmt
 
@@ -257,7 +257,8 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                    second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
                    cube2: Optional[Path] = None, interp2: Optional[str] = None, alpha_mode: str = "straight",
                    cdl=None, cdl_id: Optional[str] = None, lut1d: Optional[Path] = None,
-                   interp1d: Optional[str] = None, stages=None) -> List[str]:
+                   interp1d: Optional[str] = None, stages=None, strength: Optional[float] = None,
+                   strength_keys: Optional[str] = None) -> List[str]:
     """`build_command`'s twin for the LUT stage alone: the argv of the ENGINE CLI (`python -m lut_renderer_amd.cli`)
     that applies exactly the chain `build_command` would put into `-vf` -- the same `LutPlan`, rendered as CLI options
     instead of as a filter string (ffmpeg.py:195-247, :287-310).  `source` / `output` are rawvideo files (or `-`) in
@@ -290,7 +291,11 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     `stages` (a sequence or comma string as `LutEngine.apply_yuv_stack` takes it) runs the LUT, `cube2`, `lut1d`
     and `cdl` as an ordered stack in one pass (`--stages`, every lut3d stage with its mode spelled out); rendered only when
     given, and only then may those be combined.  The list names `lut3d` (the LUT this stage renders) and a stage for every file
-    given, and every other stage has its file; the refusals are `formats.check_stack_options`'s."""
+    given, and every other stage has its file; the refusals are `formats.check_stack_options`'s.
+    `strength` (a number in [0, 1]) or `strength_keys` ("F:S,F:S,...", `params.strength_keys`) are engine settings
+    beside `engine_dither` -- the reference's `ProcessingParams` has no such field: the graded frame mixed with the source in the
+    same pass (`--strength` / `--strength-keys`, rendered only when given, never both).  They run the stage stack, with `stages`
+    or with the list the other options imply, and on its terms: the refusals are `check_stack_options`'s and name the strength."""
     import sys as _sys
     premul = check_alpha_mode(alpha_mode)
     if precision not in ("strict", "fast", "fma32"):
@@ -371,7 +376,10 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
         cmd += ["--second-output", str(second_output), "--second-pix-fmt", second_pix_fmt]
     if cube2 is None and interp2 is not None:
         raise ValueError("interp2 is the mode of the second LUT: it needs cube2")
-    stack = stages is not None               # the pairwise refusals below give way to check_stack_options at the end
+    if strength is not None and strength_keys is not None:
+        raise ValueError("strength and strength_keys are mutually exclusive: give one or neither")
+    mixed = strength is not None or strength_keys is not None
+    stack = stages is not None or mixed      # the pairwise refusals below give way to check_stack_options at the end
     if cube2 is not None:
         from .plan import INTERP_WHITELIST
         if not stack:
@@ -424,7 +432,8 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
         from . import _native
         from .plan import INTERP_WHITELIST
         mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
-        st = parse_stages(stages, interp=plan.interp, interp2=mode2)
+        listed = stages if stages is not None else implied_stages(True, cube2 is not None, lut1d is not None, cdl is not None)
+        st = parse_stages(listed, interp=plan.interp, interp2=mode2)
         kinds = [k for k, _m in st]
         if (interp1d or "linear") not in _native.INTERP1D:
             raise ValueError(f"lut1d has no interpolation mode '{interp1d}' ({' | '.join(_native.INTERP1D)})")
@@ -435,8 +444,16 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
         check_stack_options(str(source_info.pix_fmt).replace("yuvj", "yuv"), pix_fmt or None, stages=st, cdl=cdl is not None,
                             lut=True, lut2=cube2 is not None, lut1d=lut1d is not None, dither=dither, chroma_loc=chroma_loc,
                             out_size=params.resolution if "--out-size" in cmd else None, alpha_mode=alpha_mode,
-                            out2_pix_fmt=second_pix_fmt)
-        cmd += ["--stages", stages_string(st)]
+                            out2_pix_fmt=second_pix_fmt, strength=(strength if strength_keys is None else 1.0) if mixed else None,
+                            precision=precision)
+        if stages is not None:
+            cmd += ["--stages", stages_string(st)]
+        if strength is not None:
+            cmd += ["--strength", repr(float(strength))]
+        if strength_keys is not None:
+            from .params import strength_keys as parse_keys
+            parse_keys(strength_keys)
+            cmd += ["--strength-keys", str(strength_keys)]
     return cmd
 
 

@@ -1611,8 +1611,10 @@ int lutr_apply_yuv_lut1d(lutr_ctx *c, const lutr_yuv_params *p, int interp, int 
 // ---- an ordered stack of lut1d / CDL / lut3d stages
 // lutr_apply_yuv_cdl's pass with the stage list compiled into steps: the pixel's state (codes or unit) is followed here, so the
 // kernels are told which form of a lattice stage to run and where the rounding goes.
-int lutr_apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl, int w,
-                         int h, int nframes, const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+// `mix`: nullptr for lutr_apply_yuv_stack, the strength for lutr_apply_yuv_stack_mix.
+static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                           const MixConsts *mix, int w, int h, int nframes, const lutr_planes *src, const lutr_planes *dst, int row0,
+                           int rows)
 {
     if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
     if (nstages < 1 || nstages > 4) { set_error("stack: %d stages; a stack has 1 to 4", nstages); return LUTR_EINVAL; }
@@ -1738,10 +1740,32 @@ int lutr_apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage
         S.lds_l1d_words = 3 * (S.stride >> 1);
     }
     fill_planes(&P, src, dst);
-    const char *name = launch_yuv_stack(c->stream, c->variant, L, L2, S, K, P, G, din, dout, icsx, icsy, ocsx, ocsy);
+    const char *name = launch_yuv_stack(c->stream, c->variant, L, L2, S, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, mix);
     if (!name) return finish_launch(c, nullptr);
     const std::string full = std::string(name) + "[" + list + "]";
     return finish_launch(c, full.c_str());
+}
+
+int lutr_apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl, int w,
+                         int h, int nframes, const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+{
+    return apply_yuv_stack(c, p, stages, nstages, cdl, nullptr, w, h, nframes, src, dst, row0, rows);
+}
+
+// ---- the stack with a strength behind it: the same pass, the mix kernels whatever the strength
+int lutr_apply_yuv_stack_mix(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                             float strength, const float *frame_strength, int w, int h, int nframes, const lutr_planes *src,
+                             const lutr_planes *dst, int row0, int rows)
+{
+    // the scalar is read only without the array; a NaN is found by its bits (this file is built without honouring NaNs)
+    uint32_t bits;
+    memcpy(&bits, &strength, sizeof bits);
+    if (!frame_strength && ((bits & 0x7fffffffu) > 0x7f800000u || strength < 0.0f || strength > 1.0f)) {
+        set_error("stack: strength %g outside [0, 1]", (double)strength);
+        return LUTR_EINVAL;
+    }
+    const MixConsts M{frame_strength, frame_strength ? 1.0f : strength};
+    return apply_yuv_stack(c, p, stages, nstages, cdl, &M, w, h, nframes, src, dst, row0, rows);
 }
 
 int lutr_apply_planar_rgb_lut1d(lutr_ctx *c, int depth, int w, int h, int nframes, const lutr_planes *src, const lutr_planes *dst,

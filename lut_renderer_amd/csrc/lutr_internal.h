@@ -210,15 +210,28 @@ struct StackConsts {
 };
 // launch_yuv_chain's call with the step list; L / L2 are read by the lattice steps only.  nullptr = the variant cannot take the
 // call (vec_lds always; vec_global on layouts the vector kernel cannot take and on pyramid / prism stages)
+// The strength mix behind the list: frame f of the call takes frame[f] (device memory, nframes floats) when
+// `frame` is set, else the scalar s; the kernels clamp either to [0, 1], NaN to 0.
+struct MixConsts {
+    const float *frame;
+    float s;
+};
+// M = nullptr: the kernels of 3.21; else their mix forms (k_yuv_stack_mix_vec / k_yuv_stack_mix_generic), whatever the strength
 const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
                              const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int din, int dout, int icsx, int icsy,
-                             int ocsx, int ocsy);
-// its vector kernels, one translation unit per container mix (w<in wide><out wide>); tri: some lattice step is trilinear; lds:
-// stage the tables per workgroup
+                             int ocsx, int ocsy, const MixConsts *M);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>) and form; tri: some lattice step is
+// trilinear; lds: stage the tables per workgroup
+const char *launch_yuv_stack_mix_generic(hipStream_t st, unsigned grid, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
+                                         const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const MixConsts &M, int win,
+                                         int wout, int icsx, int icsy, int ocsx, int ocsy);
 #define LUTR_SK_DECL(tag) \
     const char *launch_yuv_stack_vec_##tag(hipStream_t st, const LutConsts &L, const LutConsts &L2, const StackConsts &S, \
                                            const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int icsx, int icsy, int ocsx, \
-                                           int ocsy, bool tri, bool lds);
+                                           int ocsy, bool tri, bool lds); \
+    const char *launch_yuv_stack_mix_vec_##tag(hipStream_t st, const LutConsts &L, const LutConsts &L2, const StackConsts &S, \
+                                               const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int icsx, int icsy, \
+                                               int ocsx, int ocsy, bool tri, bool lds, MixConsts M);
 LUTR_SK_DECL(w00) LUTR_SK_DECL(w11) LUTR_SK_DECL(w10)
 #undef LUTR_SK_DECL
 

@@ -19,7 +19,34 @@
 //   without LUTR_SK_WI   the generic kernel and the launcher
 //   LUTR_SK_WI / _WO     the vector kernels of one container mix (8 -> 8, 16 -> 16, 16 -> 8): 9 layout pairs x (any stage
 //                        trilinear) x 2 placements
+//   LUTR_SKM_WI / _WO    the same set in its MIX form: k_yuv_stack_mix_vec
+//   LUTR_SKM_GENERIC     the generic kernel in its MIX form: k_yuv_stack_mix_generic
+//
+// MIX is a compile-time parameter of the translation unit, LUTR_SK_MIX: the same kernel text, with the pixel's
+// codes behind the YUV -> RGB stage (q0) kept across the step walk, or evaluated again behind it, and
+// q = (int)((q0 + s * (q1 - q0)) + 0.5f) sent to the RGB -> YUV stage; s is the strength of the pixel's frame, clamped to [0, 1].
+// A translation unit without it holds nothing of the mix: the kernels of 3.21 keep their code, registers and names.
 #include <string>
+#if defined(LUTR_SKM_WI)
+#define LUTR_SK_WI LUTR_SKM_WI
+#define LUTR_SK_WO LUTR_SKM_WO
+#endif
+#if defined(LUTR_SKM_WI) || defined(LUTR_SKM_GENERIC)
+#define LUTR_SK_MIX 1
+#define SK_MIX_PARAM , MixConsts M
+#define SK_MIX_ARG , M
+#define SK_VEC k_yuv_stack_mix_vec
+#define SK_VEC_NAME "k_yuv_stack_mix_vec<"
+#define SK_VEC_LAUNCH launch_yuv_stack_mix_vec_w
+#define SK_GENERIC k_yuv_stack_mix_generic
+#else
+#define SK_MIX_PARAM
+#define SK_MIX_ARG
+#define SK_VEC k_yuv_stack_vec
+#define SK_VEC_NAME "k_yuv_stack_vec<"
+#define SK_VEC_LAUNCH launch_yuv_stack_vec_w
+#define SK_GENERIC k_yuv_stack_generic
+#endif
 
 #include "lutr_device.h"
 #include "lutr_launch.h"
@@ -45,6 +72,27 @@ __device__ __forceinline__ Rgb stack_round_px(float maxf, const Rgb &o)
     q.b = (float)(int)(o.b * maxf + 0.5f);
     return q;
 }
+
+#ifdef LUTR_SK_MIX
+// The strength of frame fr: one dword of the per-frame array, or the call's scalar.  A NaN is 0, found by its bits (the build does
+// not honour NaNs in float compares); then the clamp.
+__device__ __forceinline__ float mix_strength(const MixConsts &M, long long fr)
+{
+    float s = M.frame ? M.frame[fr] : M.s;
+    if ((__float_as_uint(s) & 0x7fffffffu) > 0x7f800000u) s = 0.0f;
+    return fminf(fmaxf(s, 0.0f), 1.0f);
+}
+
+// q0 + s * (q1 - q0) rounded to a code: the difference is exact; the product and the two sums are each rounded on their own
+__device__ __forceinline__ Rgb mix_px(float s, const Rgb &q0, const Rgb &q1)
+{
+    Rgb q;
+    q.r = (float)(int)((q0.r + s * (q1.r - q0.r)) + 0.5f);
+    q.g = (float)(int)((q0.g + s * (q1.g - q0.g)) + 0.5f);
+    q.b = (float)(int)((q0.b + s * (q1.b - q0.b)) + 0.5f);
+    return q;
+}
+#endif
 
 #ifdef LUTR_SK_WI
 // ================================================================= vector kernel
@@ -107,7 +155,7 @@ __device__ __forceinline__ void stack_block(const StackConsts &S, const CdlConst
 // k_yuv_l1d_vec's structure (lutr_l1d.hip) with the step walk as the per-block middle.  TRI: some stage is trilinear (a stack of
 // nearest / tetrahedral stages does not carry trilinear's registers).  No thread leaves before the barrier behind the staging.
 template <int WIN, int WOUT, int ICSX, int ICSY, int OCSX, int OCSY, bool TRI, bool LDS>
-__global__ __launch_bounds__(256) void k_yuv_stack_vec(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P, FrameGeom G)
+__global__ __launch_bounds__(256) void SK_VEC(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P, FrameGeom G SK_MIX_PARAM)
 {
     constexpr int VB = vec_bytes<WIN, WOUT>();
     constexpr int PXT = VB / (WIN ? 2 : 1);                       // luma samples per thread per row
@@ -135,6 +183,9 @@ __global__ __launch_bounds__(256) void k_yuv_stack_vec(LutConsts L, LutConsts L2
         const long long fr = t / ub;
         const long long xi = (long long)xu * VB, xo = (long long)xu * (YWO * 4), cxi = (long long)xu * (CWI * 4),
                         cxo = (long long)xu * (CWO * 4);
+#ifdef LUTR_SK_MIX
+        const float strength = mix_strength(M, fr);
+#endif
 
         uint32_t yw[BH][YWI], cbw[IRH][CWI], crw[IRH][CWI];
         uint32_t yo[BH][YWO], cbo[ORH][CWO], cro[ORH][CWO];
@@ -169,7 +220,37 @@ __global__ __launch_bounds__(256) void k_yuv_stack_vec(LutConsts L, LutConsts L2
 #pragma unroll
                 for (int dx = 0; dx < BW; dx++)
                     px[dy * BW + dx] = yuv_to_rgb(K, word_sample<WIN>(yw[dy], j * BW + dx), c[dy >> ICSY][dx >> ICSX]);
+#ifdef LUTR_SK_MIX
+            // q0 across the step walk.  A copy of the block (Rgb px0[BH * BW]) is 12 VGPRs at 4:2:0 and takes the tetrahedral
+            // instances from 4 waves to 3 (DESIGN.md 3.22 point 5).  Where the block's chroma terms are fewer than its pixels, q0 is
+            // evaluated again behind the walk instead -- from the luma words, which stay live for the thread's other blocks anyway,
+            // and the chroma terms: the same operations on the same inputs, so the same bits.  The fence keeps hipcc from reusing
+            // the first evaluation, which would keep the copy alive after all.
+            constexpr bool AGAIN = IRH * IBX < BH * BW;
+            Rgb px0[AGAIN ? 1 : BH * BW];
+            if constexpr (!AGAIN) {
+#pragma unroll
+                for (int i = 0; i < BH * BW; i++) px0[i] = px[i];
+            }
+#endif
             stack_block<TRI>(S, C, l1d, L, L2, px);
+#ifdef LUTR_SK_MIX
+            if constexpr (AGAIN) {
+#pragma unroll
+                for (int dy = 0; dy < BH; dy++) {
+#pragma unroll
+                    for (int k = 0; k < YWI; k++) asm volatile("" : "+v"(yw[dy][k]));
+#pragma unroll
+                    for (int dx = 0; dx < BW; dx++) {
+                        const Rgb q0 = yuv_to_rgb(K, word_sample<WIN>(yw[dy], j * BW + dx), c[dy >> ICSY][dx >> ICSX]);
+                        px[dy * BW + dx] = mix_px(strength, q0, px[dy * BW + dx]);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < BH * BW; i++) px[i] = mix_px(strength, px0[i], px[i]);
+            }
+#endif
             float rs[ORH][OBX], gs[ORH][OBX], bs[ORH][OBX];
 #pragma unroll
             for (int oy = 0; oy < ORH; oy++)
@@ -224,10 +305,10 @@ __global__ __launch_bounds__(256) void k_yuv_stack_vec(LutConsts L, LutConsts L2
 
 // The vector kernels of this translation unit's container mix; the layout checks are the caller's (launch_yuv_stack).  The grid:
 // with tables in LDS, eight workgroups a CU, each staging once and walking its share of the units; without, the usual cap.
-const char *LUTR_CAT(LUTR_CAT(launch_yuv_stack_vec_w, LUTR_SK_WI), LUTR_SK_WO)(hipStream_t st, const LutConsts &L, const LutConsts &L2,
-                                                                                const StackConsts &S, const YuvConsts &K,
-                                                                                const PlaneSet &P, const FrameGeom &G, int icsx,
-                                                                                int icsy, int ocsx, int ocsy, bool tri, bool lds)
+const char *LUTR_CAT(LUTR_CAT(SK_VEC_LAUNCH, LUTR_SK_WI), LUTR_SK_WO)(hipStream_t st, const LutConsts &L, const LutConsts &L2,
+                                                                      const StackConsts &S, const YuvConsts &K, const PlaneSet &P,
+                                                                      const FrameGeom &G, int icsx, int icsy, int ocsx, int ocsy,
+                                                                      bool tri, bool lds SK_MIX_PARAM)
 {
     constexpr int WI = LUTR_SK_WI, WO = LUTR_SK_WO;
     constexpr int PXT = vec_bytes<WI, WO>() / (WI ? 2 : 1);
@@ -237,10 +318,10 @@ const char *LUTR_CAT(LUTR_CAT(launch_yuv_stack_vec_w, LUTR_SK_WI), LUTR_SK_WO)(h
     const size_t lds_bytes = lds ? (size_t)(S.lds_cdl_words + S.lds_l1d_words) * sizeof(uint32_t) : 0;
 #define SK_CASE(IX, IY, OX, OY, T) \
     if (icsx == IX && icsy == IY && ocsx == OX && ocsy == OY && tri == (T != 0)) { \
-        if (lds) hipLaunchKernelGGL((k_yuv_stack_vec<WI, WO, IX, IY, OX, OY, T != 0, true>), grid, block, lds_bytes, st, L, L2, S, K, P, G); \
-        else hipLaunchKernelGGL((k_yuv_stack_vec<WI, WO, IX, IY, OX, OY, T != 0, false>), grid, block, 0, st, L, L2, S, K, P, G); \
-        return lds ? "k_yuv_stack_vec<" LUTR_STR(LUTR_SK_WI) "," LUTR_STR(LUTR_SK_WO) "," #IX "," #IY "," #OX "," #OY "," #T ",1>" \
-                   : "k_yuv_stack_vec<" LUTR_STR(LUTR_SK_WI) "," LUTR_STR(LUTR_SK_WO) "," #IX "," #IY "," #OX "," #OY "," #T ",0>"; \
+        if (lds) hipLaunchKernelGGL((SK_VEC<WI, WO, IX, IY, OX, OY, T != 0, true>), grid, block, lds_bytes, st, L, L2, S, K, P, G SK_MIX_ARG); \
+        else hipLaunchKernelGGL((SK_VEC<WI, WO, IX, IY, OX, OY, T != 0, false>), grid, block, 0, st, L, L2, S, K, P, G SK_MIX_ARG); \
+        return lds ? SK_VEC_NAME LUTR_STR(LUTR_SK_WI) "," LUTR_STR(LUTR_SK_WO) "," #IX "," #IY "," #OX "," #OY "," #T ",1>" \
+                   : SK_VEC_NAME LUTR_STR(LUTR_SK_WI) "," LUTR_STR(LUTR_SK_WO) "," #IX "," #IY "," #OX "," #OY "," #T ",0>"; \
     }
 #define SK_PAIR(IX, IY, OX, OY) SK_CASE(IX, IY, OX, OY, 0) SK_CASE(IX, IY, OX, OY, 1)
     SK_PAIR(1, 1, 1, 1) SK_PAIR(1, 1, 1, 0) SK_PAIR(1, 1, 0, 0)
@@ -256,8 +337,8 @@ const char *LUTR_CAT(LUTR_CAT(launch_yuv_stack_vec_w, LUTR_SK_WI), LUTR_SK_WO)(h
 // One thread per union block; any depth, stride or alignment, odd sizes, all five modes on either lattice.  k_yuv_cdl_generic's
 // walk with the step list per pixel (the tables read from global memory): a pixel outside the frame is the edge pixel again, only
 // pixels and chroma samples inside the planes are written.
-__global__ __launch_bounds__(256) void k_yuv_stack_generic(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P,
-                                                           FrameGeom G, int win, int wout, int icsx, int icsy, int ocsx, int ocsy)
+__global__ __launch_bounds__(256) void SK_GENERIC(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P, FrameGeom G SK_MIX_PARAM,
+                                                  int win, int wout, int icsx, int icsy, int ocsx, int ocsy)
 {
     const GFetch f(L), f2(L2);
     PlaneSink sink{K, P, wout};
@@ -267,6 +348,9 @@ __global__ __launch_bounds__(256) void k_yuv_stack_generic(LutConsts L, LutConst
     const int bw = 1 << csx, bh = 1 << csy, obw = 1 << ocsx, obh = 1 << ocsy;
     const int cwo = (G.w + obw - 1) >> ocsx, cho = (G.h + obh - 1) >> ocsy;
     for_each_block(G, csx, csy, false, [&](long long fr, int ux, int uy) {
+#ifdef LUTR_SK_MIX
+        const float strength = mix_strength(M, fr);
+#endif
         for (int oy = 0; oy < bh; oy += obh) {
             for (int ox = 0; ox < bw; ox += obw) {
                 float rs = 0.f, gs = 0.f, bs = 0.f;
@@ -280,6 +364,9 @@ __global__ __launch_bounds__(256) void k_yuv_stack_generic(LutConsts L, LutConst
                         const float crv = ld_sample(src_row(P, 2, fr, y >> icsy), x >> icsx, win);
                         const float yv = ld_sample(src_row(P, 0, fr, y), x, win);
                         Rgb o = yuv_to_rgb(K, yv, chroma_terms(K, cbv, crv));
+#ifdef LUTR_SK_MIX
+                        const Rgb o0 = o;
+#endif
 #pragma nounroll
                         for (unsigned long long ops = S.ops; ops & 0xffull; ops >>= 8) {
                             const int op = (int)(ops & 15u), mode = (int)((ops >> 4) & 15u);
@@ -293,6 +380,9 @@ __global__ __launch_bounds__(256) void k_yuv_stack_generic(LutConsts L, LutConst
                             default:                  o = lut3d_unit_rt(mode, L2, f2, o); break;
                             }
                         }
+#ifdef LUTR_SK_MIX
+                        o = mix_px(strength, o0, o);
+#endif
                         rs += o.r; gs += o.g; bs += o.b;
                         if (yy < G.h && xx < G.w) sink.luma(fr, x, y, o);
                     }
@@ -304,6 +394,16 @@ __global__ __launch_bounds__(256) void k_yuv_stack_generic(LutConsts L, LutConst
     });
 }
 
+#ifdef LUTR_SK_MIX
+// the MIX form's launch, for the launcher in the translation unit without LUTR_SK_MIX
+const char *launch_yuv_stack_mix_generic(hipStream_t st, unsigned grid, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
+                                         const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const MixConsts &M, int win,
+                                         int wout, int icsx, int icsy, int ocsx, int ocsy)
+{
+    hipLaunchKernelGGL(k_yuv_stack_mix_generic, dim3(grid), dim3(256), 0, st, L, L2, S, K, P, G, M, win, wout, icsx, icsy, ocsx, ocsy);
+    return "k_yuv_stack_mix_generic";
+}
+#else
 // ================================================================= launcher
 // LUTR_STACK_LDS=0 / 1: where the vector kernels read the CDL and 1D tables (tests and tools; unset: the default below).  The
 // tables the stack uses go to LDS together or not at all: above 24 KB in sum they are read from global memory.  The default follows
@@ -323,7 +423,7 @@ static bool stack_in_lds(const StackConsts &S)
 
 const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
                              const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int din, int dout, int icsx, int icsy,
-                             int ocsx, int ocsy)
+                             int ocsx, int ocsy, const MixConsts *M)
 {
     const int win = din > 8, wout = dout > 8;
     const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy), bh = 1 << csy;
@@ -356,12 +456,20 @@ const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, co
     };
     auto vec = [&](const PlaneSet &Q, const FrameGeom &H) -> const char * {
         ran |= 1;
+        if (M) {
+            if (win && wout) return launch_yuv_stack_mix_vec_w11(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M);
+            if (win) return launch_yuv_stack_mix_vec_w10(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M);
+            return launch_yuv_stack_mix_vec_w00(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M);
+        }
         if (win && wout) return launch_yuv_stack_vec_w11(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds);
         if (win) return launch_yuv_stack_vec_w10(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds);
         return launch_yuv_stack_vec_w00(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds);
     };
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
         ran |= 2;
+        if (M)
+            return launch_yuv_stack_mix_generic(st, block_grid(H.w, H.rows, H.nframes, csx, csy), L, L2, S, K, Q, H, *M, win, wout, icsx,
+                                                icsy, ocsx, ocsy);
         hipLaunchKernelGGL(k_yuv_stack_generic, dim3(block_grid(H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, L2, S, K, Q, H,
                            win, wout, icsx, icsy, ocsx, ocsy);
         return "k_yuv_stack_generic";
@@ -372,9 +480,10 @@ const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, co
     if (!name || ran != 3) return name;
     // a ragged width split between the two kernels: both are named
     static thread_local std::string both;
-    both = std::string(name) + "+k_yuv_stack_generic";
+    both = std::string(name) + (M ? "+k_yuv_stack_mix_generic" : "+k_yuv_stack_generic");
     return both.c_str();
 }
+#endif  // LUTR_SK_MIX
 #endif  // LUTR_SK_WI
 
 }  // namespace lutr

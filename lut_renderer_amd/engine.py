@@ -24,7 +24,7 @@ from .cube import CubeLut, Lut1D, read_cube, read_lut, read_lut1d
 # (the formats and the checks of names and options live in formats.py; the names callers have always imported from here stay)
 from .formats import (_ALPHA_RESIZE, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, V210Fmt, chain_interp, chain_side,  # noqa: F401
                       changes_subsampling, check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc,
-                      check_lut1d_options, check_stack_options,
+                      check_lut1d_options, check_stack_options, check_strength,
                       check_container_options,
                       check_dual_options, check_lut2, check_packed_options, check_premul_options, check_semi_options,
                       chroma_loc_code, dual_side, has_prologue, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt,
@@ -330,6 +330,7 @@ class LutEngine:
         # set_lut + apply so that a cached engine cannot render one task with another task's lattice.
         self._lock = threading.RLock()
         self.precision = "strict"
+        self._frame_strength = None       # the per-frame strengths of the last apply_yuv_stack(strength=[...])
         self._applied_lut = None          # the CubeLut object apply_lut uploaded last (its upload-skipping shortcut)
         self._applied_lut2 = None         # ... and the second LUT of apply_lut(cube2=)
         self.n2 = 0
@@ -913,7 +914,7 @@ class LutEngine:
                         out_pix_fmt: Optional[str] = None, stages, cdl: Optional[Cdl] = None, matrix_in: str = "bt709",
                         matrix_out: Optional[str] = None, range_src: str = "tv", range_in: Optional[str] = None,
                         range_out: str = "tv", lut_depth: Optional[int] = None, row0: int = 0, rows: Optional[int] = None,
-                        **other):
+                        strength=None, **other):
         """`apply_yuv` with an ordered stack of 1..4 stages between its YUV -> RGB and RGB -> YUV stages, in one pass
         (lutr_apply_yuv_stack).  `stages` is a sequence of "lut3d" (`set_lut`), "lut3d2" (`set_lut2`), "lut1d"
         (`set_lut1d`), "cdl" (the `cdl` argument), each at most once; a lut3d stage may be a pair ("lut3d", "trilinear") -- the
@@ -922,7 +923,13 @@ class LutEngine:
         block, strict arithmetic, not in place.  ("lut3d",) gives the bits of `apply_yuv(out_pix_fmt=...)`, ("cdl", "lut3d") those
         of `apply_yuv(cdl=...)`, ("lut1d", "lut3d") those of `apply_yuv_lut1d`, ("lut3d", "lut3d2") those of `apply_yuv_chain`.  No
         dither, chroma_loc, out_size, premultiplied alpha or second output, and no RGB / float / semi-planar / packed / v210 side:
-        each is a ValueError naming it (`formats.check_stack_options`)."""
+        each is a ValueError naming it (`formats.check_stack_options`).
+        `strength`: None runs the pass above unchanged.  A number in [0, 1] mixes the graded pixel with the source
+        behind the list, q = (int)((q0 + s * (q1 - q0)) + 0.5f) on the RGB codes, in the same pass (lutr_apply_yuv_stack_mix): 1
+        gives the bits of the call without it, 0 those of the two conversion stages alone.  A sequence, NumPy array or CPU tensor
+        of one number per frame gives every frame of the call its own strength (frame 0 = the first frame of `src`, whatever
+        row0 / rows are): it is checked on the host (length, finite, in [0, 1]; a ValueError names the index and the value),
+        uploaded on the engine's stream and held by the engine until the next such call replaces it."""
         for k in other:
             if k not in ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt"):
                 raise TypeError(f"apply_yuv_stack() got an unexpected keyword argument '{k}'")
@@ -932,10 +939,10 @@ class LutEngine:
             pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(self, "n", 0)),
             lut2=bool(getattr(self, "n2", 0)), lut1d=bool(getattr(self, "n1d", 0)), prelut=bool(getattr(self, "_has_prelut", False)),
             dither=other.get("dither", "none"), chroma_loc=other.get("chroma_loc"), out_size=other.get("out_size"),
-            alpha_mode=other.get("alpha_mode", "straight"), out2_pix_fmt=other.get("out2_pix_fmt"))
+            alpha_mode=other.get("alpha_mode", "straight"), out2_pix_fmt=other.get("out2_pix_fmt"), strength=strength)
         if fin.alpha or fout.alpha:
             # yuva*: the colour planes through this very call under their three-plane names, then the alpha plane on the same
-            # stream, exactly as the CDL call does
+            # stream, exactly as the CDL call does; straight alpha goes past the mix unchanged
             if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
                 raise ValueError(_PLANE_COUNT[fin.nplanes].format(fin.name))
             h, w = src[0].shape[-2], src[0].shape[-1]
@@ -949,7 +956,7 @@ class LutEngine:
             self._alpha_tail(lambda: self.apply_yuv_stack(
                 src[:3], dst[:3], pix_fmt=fin.colour.name, out_pix_fmt=fout.colour.name, stages=st, cdl=cdl, matrix_in=matrix_in,
                 matrix_out=matrix_out, range_src=range_src, range_in=range_in, range_out=range_out, lut_depth=lut_depth, row0=row0,
-                rows=rows), [(fout, dst)], a_src, fin.depth, w, h, row0, rows)
+                rows=rows, strength=strength), [(fout, dst)], a_src, fin.depth, w, h, row0, rows)
             return dst
         p = _yuv_call_params(fin, fout, lut_depth, matrix_in, matrix_out, range_src, range_in, range_out)
         h, w = src[0].shape[-2], src[0].shape[-1]
@@ -962,10 +969,25 @@ class LutEngine:
         rows = h - row0 if rows is None else rows
         arr = _native.stage_array(st)
         k = None if cdl is None else C.byref(_native.cdl_struct(cdl))
+        strength = check_strength(strength, nf)
         with self._lock:
             self._bind_stream()
-            _native.check(self._lib.lutr_apply_yuv_stack(
-                self._ctx, C.byref(p), arr, len(st), k, w, h, nf, C.byref(s), C.byref(d), row0, rows))
+            if strength is None:
+                _native.check(self._lib.lutr_apply_yuv_stack(
+                    self._ctx, C.byref(p), arr, len(st), k, w, h, nf, C.byref(s), C.byref(d), row0, rows))
+            elif isinstance(strength, float):
+                _native.check(self._lib.lutr_apply_yuv_stack_mix(
+                    self._ctx, C.byref(p), arr, len(st), k, strength, None, w, h, nf, C.byref(s), C.byref(d), row0, rows))
+            else:
+                # one float per frame, on the stream the kernel reads it from; the engine keeps it until the next one replaces it
+                # (torch's allocator hands the old one's memory out again in stream order; a context on a stream of its own is
+                # waited for first)
+                if not self.use_torch_stream and self._frame_strength is not None:
+                    self.sync()
+                self._frame_strength = torch.from_numpy(strength).to(self.device)
+                _native.check(self._lib.lutr_apply_yuv_stack_mix(
+                    self._ctx, C.byref(p), arr, len(st), k, 1.0, C.c_void_p(self._frame_strength.data_ptr()), w, h, nf,
+                    C.byref(s), C.byref(d), row0, rows))
         return dst
 
     def apply_rgb_lut1d(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, depth: int,

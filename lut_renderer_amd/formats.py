@@ -617,16 +617,65 @@ def stages_string(stages) -> str:
     return ",".join(k if m is None else f"{k}:{m}" for k, m in parse_stages(stages))
 
 
+def check_strength(strength, nframes: Optional[int] = None):
+    """The `strength` argument of a stage stack, checked on the host: None stays None (no mix); a number gives a
+    float in [0, 1]; a sequence, NumPy array or CPU tensor gives a float32 array of one strength per frame -- of `nframes` entries
+    when that is known -- each finite and in [0, 1].  ValueError otherwise, naming the index and the value."""
+    if strength is None:
+        return None
+    if isinstance(strength, (bool, str, bytes)):
+        raise ValueError(f"strength is a number in [0, 1] or one per frame, not {strength!r}")
+    try:
+        arr = np.asarray(strength.detach().cpu().numpy() if hasattr(strength, "detach") else strength, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"strength is a number in [0, 1] or one per frame, not {strength!r}") from None
+    if arr.ndim == 0:
+        s = float(arr)
+        if not (np.isfinite(s) and 0.0 <= s <= 1.0):
+            raise ValueError(f"strength {s!r} is outside [0, 1]")
+        return s
+    if arr.ndim != 1:
+        raise ValueError(f"strength per frame is a flat sequence, not an array of shape {arr.shape}")
+    if nframes is not None and arr.shape[0] != nframes:
+        raise ValueError(f"strength has {arr.shape[0]} entries for {nframes} frames: a per-frame strength has one per frame")
+    bad = np.flatnonzero(~(np.isfinite(arr) & (arr >= 0.0) & (arr <= 1.0)))
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError(f"strength[{i}] = {float(arr[i])!r} is outside [0, 1]")
+    return arr.astype(np.float32)
+
+
+def implied_stages(cube: bool, cube2: bool = False, lut1d: bool = False, cdl: bool = False) -> Tuple[str, ...]:
+    """The stage list the options of a call without `stages` imply when a strength sends it to the stack: the
+    order of the dedicated routes -- lut1d, cdl, lut3d, lut3d2.  A 1D LUT without `cube` is lut1d alone, as in `apply_lut`;
+    otherwise the first lattice is listed whether it comes with the call or the engine holds it."""
+    st = []
+    if lut1d:
+        st.append("lut1d")
+    if cdl:
+        st.append("cdl")
+    if cube or not lut1d:
+        st.append("lut3d")
+    if cube2:
+        st.append("lut3d2")
+    return tuple(st)
+
+
 def check_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = None, *, stages, cdl: bool = False,
                         lut: bool = True, lut2: bool = True, lut1d: bool = True, prelut: bool = False, dither: str = "none",
                         chroma_loc: Optional[str] = None, out_size=None, alpha_mode: str = "straight",
-                        out2_pix_fmt: Optional[str] = None, variant: Optional[str] = None):
+                        out2_pix_fmt: Optional[str] = None, variant: Optional[str] = None, strength=None,
+                        precision: Optional[str] = None):
     """The checks every layer makes of a stage stack before any GPU work, the one copy of its refusals: a stage
     list `parse_stages` takes; every listed stage's resource there (`lut`, `lut2`, `lut1d`: a first / second lattice, a 1D LUT is
     loaded; `cdl`: a CDL is given) and no CDL without a cdl stage; no lut3d directly behind cdl when the first LUT carries a .csp
     prelut (`prelut`); planar YUV on both sides (yuva* with straight alpha included); no dither, chroma_loc, out_size, second
-    output or premultiplied alpha; not the vec_lds variant.  Returns (parsed stages, source format, output format)."""
-    tail = "a stage stack"
+    output or premultiplied alpha; not the vec_lds variant.  With a `strength` (anything but None) every message
+    names it beside the option, the strength itself is checked (`check_strength`) and a `precision` other than strict is refused.
+    Returns (parsed stages, source format, output format)."""
+    mixed = strength is not None
+    tail = "a stage stack with strength" if mixed else "a stage stack"
+    noun = "stack (strength)" if mixed else "stack"
     st = parse_stages(stages)
     kinds = [k for k, _m in st]
     if "lut3d" in kinds and not lut:
@@ -642,8 +691,8 @@ def check_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = Non
     if prelut and "cdl" in kinds and kinds.index("cdl") + 1 < len(kinds) and kinds[kinds.index("cdl") + 1] == "lut3d":
         raise ValueError("stage 'lut3d' directly behind 'cdl' is not supported with a LUT that carries a .csp prelut: the prelut's "
                          "table is indexed by integer codes, and the CDL's output is not a code")
-    fin = _pass_side(pix_fmt, "pix_fmt", "stack", "both sides", True, alpha_ok=True)
-    fout = _pass_side(out_pix_fmt or pix_fmt, "out_pix_fmt", "stack", "both sides", True, alpha_ok=True)
+    fin = _pass_side(pix_fmt, "pix_fmt", noun, "both sides", True, alpha_ok=True)
+    fout = _pass_side(out_pix_fmt or pix_fmt, "out_pix_fmt", noun, "both sides", True, alpha_ok=True)
     if dither != "none":
         raise ValueError(f"dither ('{dither}') is not supported with {tail}")
     if chroma_loc is not None:
@@ -656,6 +705,10 @@ def check_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = Non
         raise ValueError(f"alpha_mode='{alpha_mode}' is not supported with {tail}")
     if variant == "vec_lds":
         raise ValueError(f"variant vec_lds is not supported with {tail}: there is no LDS-window kernel for the stack pass")
+    if mixed:
+        if precision not in (None, "strict"):
+            raise ValueError(f"precision='{precision}' is not supported with strength: the mix is defined on the strict path only")
+        check_strength(strength)
     return st, fin, fout
 
 

@@ -29,7 +29,7 @@ import torch
 from . import _native
 from .cube import CubeLut, read_lut, read_lut1d
 from .engine import LutEngine, _fresh_planes, _new_planes, _yuv_out_dtype, chain_args, dual_args
-from .formats import (check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2, check_stack_options,
+from .formats import (check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2, check_stack_options, check_strength,
                       check_premul_options,
                       packed_frame_width, parse_pix_fmt, parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords,
                       v210_frame_width, yuv_side)
@@ -355,7 +355,8 @@ class LutEngineGroup:
                         out_pix_fmt: Optional[str] = None, stages, cdl=None, **kw):
         """`LutEngine.apply_yuv_stack` with the rows of every frame split over the group's devices: the lattices
         and the 1D LUT are on every engine through the group's setters, the CDL travels with the call; shards on multiples of the
-        union block height of the two layouts, alpha rows go with the luma rows, no halo."""
+        union block height of the two layouts, alpha rows go with the luma rows, no halo.  `strength` as the
+        engine takes it: a per-frame array goes to every device once, and the shards give the bits of the whole call."""
         with self._lock:
             if "row0" in kw or "rows" in kw:
                 raise ValueError("the group owns the row partition")
@@ -364,7 +365,11 @@ class LutEngineGroup:
                 pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(e0, "n", 0)),
                 lut2=bool(getattr(e0, "n2", 0)), lut1d=bool(self.n1d), prelut=bool(getattr(e0, "_has_prelut", False)),
                 dither=kw.get("dither", "none"), chroma_loc=kw.get("chroma_loc"), out_size=kw.get("out_size"),
-                alpha_mode=kw.get("alpha_mode", "straight"), out2_pix_fmt=kw.get("out2_pix_fmt"))
+                alpha_mode=kw.get("alpha_mode", "straight"), out2_pix_fmt=kw.get("out2_pix_fmt"), strength=kw.get("strength"))
+            if kw.get("strength") is not None:
+                # checked once for the whole call; every engine uploads its own copy of a per-frame array, and a shard's frame
+                # 0 is the call's frame 0 (rows are split, frames are not)
+                kw = dict(kw, strength=check_strength(kw["strength"], src[0].shape[0] if len(src[0].shape) == 3 else 1))
             h, w = src[0].shape[-2], src[0].shape[-1]
             home = src[0].device
             if dst is None:

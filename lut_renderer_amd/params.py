@@ -153,3 +153,58 @@ class Task:
 
     def display_name(self) -> str:
         return self.source_path.name
+
+
+def strength_keys(text: str):
+    """Key frames of a LUT strength: "F:S,F:S,..." -- frame number F (an integer >= 0, counted over the whole
+    stream) takes strength S in [0, 1].  Returns a callable (first_frame, n) -> float32[n], the strengths of frames first_frame ..
+    first_frame + n - 1: piecewise linear in the absolute frame number between the keys, held before the first key and behind
+    the last, evaluated in float64 and cast once.  ValueError naming the text and the fault: no key, a malformed key, a frame
+    number that is negative, repeated or out of order, a strength that is not finite or outside [0, 1]."""
+    import math
+
+    import numpy as np
+
+    if not isinstance(text, str):
+        raise ValueError(f"strength keys {text!r}: expected a string 'F:S,F:S,...'")
+
+    def fault(what: str) -> ValueError:
+        return ValueError(f"strength keys '{text}': {what}")
+
+    items = [item.strip() for item in text.split(",")]
+    if not text.strip():
+        raise fault("no key given (F:S,F:S,...)")
+    frames, values = [], []
+    for item in items:
+        head, colon, tail = (part.strip() for part in item.partition(":"))
+        if not colon or not head or not tail:
+            raise fault(f"key '{item}' is malformed (a key is F:S)")
+        try:
+            f = int(head, 10)
+        except ValueError:
+            raise fault(f"key '{item}' is malformed: frame number '{head}' is not an integer") from None
+        try:
+            s = float(tail)
+        except ValueError:
+            raise fault(f"key '{item}' is malformed: strength '{tail}' is not a number") from None
+        if f < 0:
+            raise fault(f"frame number {f} is negative")
+        if not (math.isfinite(s) and 0.0 <= s <= 1.0):
+            raise fault(f"strength {s!r} at frame {f} is outside [0, 1]")
+        if frames and f == frames[-1] or f in frames:
+            raise fault(f"frame {f} is a duplicate: it is keyed twice")
+        if frames and f < frames[-1]:
+            raise fault(f"the keys are unsorted: frame {f} follows frame {frames[-1]}")
+        frames.append(f)
+        values.append(s)
+    xs = np.asarray(frames, dtype=np.float64)
+    ys = np.asarray(values, dtype=np.float64)
+
+    def strengths(first_frame: int, n: int):
+        if first_frame < 0 or n < 0:
+            raise ValueError(f"strength keys '{text}': frames {first_frame} .. {first_frame + n - 1} asked for")
+        at = np.arange(first_frame, first_frame + n, dtype=np.float64)
+        return np.interp(at, xs, ys).astype(np.float32)     # (np.interp holds the end values outside the keys)
+
+    strengths.text = text
+    return strengths

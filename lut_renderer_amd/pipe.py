@@ -50,7 +50,8 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
                           engine_dither: Optional[str] = None, cube2: Optional[Path] = None,
                           interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None,
                           cdl_id: Optional[str] = None, lut1d: Optional[Path] = None,
-                          interp1d: Optional[str] = None, stages=None) -> StageCommands:
+                          interp1d: Optional[str] = None, stages=None, strength: Optional[float] = None,
+                          strength_keys: Optional[str] = None) -> StageCommands:
     """The three argv lists of one LUT stage.  Raises what `build_command` / `engine_command` raise (copy guard, missing
     geometry).  `chroma_loc` goes to the engine (`--chroma-loc`) and, as `-chroma_sample_location`, to the encoder, so the
     output stream declares the siting the engine assumed.  `gpu_resize` with `params.resolution` set resizes in the engine
@@ -60,12 +61,15 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
     has no such step, so the decoder and encoder argv are untouched.  The same holds for `cdl` / `cdl_id` (an ASC CDL ahead of the
     LUT, DESIGN.md 3.19: `--cdl` / `--cdl-id`, or `--cdl-sop` / `--cdl-sat` for a `cdl.Cdl`) and for `lut1d` / `interp1d` (a 1D LUT
     file ahead of the LUT, DESIGN.md 3.20: `--lut1d` / `--interp1d`), and for `stages` (these operators as an ordered stack in one
-    pass, DESIGN.md 3.21: `--stages`, rendered only when given)."""
+    pass, DESIGN.md 3.21: `--stages`, rendered only when given), and for `strength` / `strength_keys` (the LUT's strength, DESIGN.md
+    3.22: `--strength` / `--strength-keys`, rendered only when given; the key frames count the frames of the stream)."""
     notes: List[str] = []
     engine = engine_command(Path("-"), Path("-"), params, lut_path, source_info, python_bin=python_bin, device=device, notes=notes,
                             precision=precision, chroma_loc=chroma_loc, gpu_resize=gpu_resize, engine_dither=engine_dither,
                             cube2=cube2, interp2=interp2, alpha_mode=alpha_mode, cdl=cdl, cdl_id=cdl_id, lut1d=lut1d,
-                            interp1d=interp1d, **({} if stages is None else {"stages": stages}))
+                            interp1d=interp1d, **({} if stages is None else {"stages": stages}),
+                            **({} if strength is None else {"strength": strength}),
+                            **({} if strength_keys is None else {"strength_keys": strength_keys}))
     resized = gpu_resize and bool(params.resolution)
     if source_info.duration:
         engine += ["--duration", f"{float(source_info.duration):.3f}"]
@@ -163,6 +167,9 @@ def main(argv=None) -> int:
     ap.add_argument("--lut1d", default=None, help="engine setting: a 1D LUT file ahead of --cube, see lut_renderer_amd.cli")
     ap.add_argument("--interp1d", default=None, help="interpolation mode of --lut1d, see lut_renderer_amd.cli")
     ap.add_argument("--stages", default=None, help="engine setting: the operators as an ordered stack, see lut_renderer_amd.cli")
+    mix = ap.add_mutually_exclusive_group()
+    mix.add_argument("--strength", default=None, type=float, help="engine setting: LUT strength in [0, 1], see lut_renderer_amd.cli")
+    mix.add_argument("--strength-keys", default=None, help="engine setting: LUT strength by key frames F:S,F:S,..., see lut_renderer_amd.cli")
     ap.add_argument("--gpu-resize", action="store_true", help="resize to the params' resolution in the engine (--out-size) instead of the encoder")
     a = ap.parse_args(argv)
     try:
@@ -179,7 +186,7 @@ def main(argv=None) -> int:
                                      engine_dither=a.engine_dither, cube2=None if a.cube2 is None else Path(a.cube2),
                                      interp2=a.interp2, alpha_mode=a.alpha_mode, cdl=cdl, cdl_id=a.cdl_id,
                                      lut1d=None if a.lut1d is None else Path(a.lut1d), interp1d=a.interp1d,
-                                     stages=a.stages)
+                                     stages=a.stages, strength=a.strength, strength_keys=a.strength_keys)
     except Exception as exc:
         print(f"Error: {exc}", flush=True)
         return 1

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .engine import LutEngine
+from .params import strength_keys
 from .formats import (RgbSource, check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options,
                       check_lut1d_options, check_stack_options,
                       check_premul_options, parse_rgb_source, parse_size, premul_to_yuv, refuse_alpha_resize, yuv_side)
@@ -146,8 +147,21 @@ class HostPipeline:
         `apply_kw` may carry `interp2`.  Planar YUV without alpha on both sides, no dither, chroma_loc, out_size or second output."""
         # `apply_kw["stages"]`: every batch goes through `apply_yuv_stack` (DESIGN.md 3.21) with the lattices and the 1D LUT the
         # engine holds and `apply_kw["cdl"]`; `chain` / `lut1d` are not set then
+        # `apply_kw["strength"]` (a number) or `apply_kw["strength_keys"]` ("F:S,..." or `params.strength_keys`' callable) mix the
+        # graded frame with the source (DESIGN.md 3.22): the keys are read at the frame's number in the stream, counted here
+        # across the batches
         stages = apply_kw.get("stages")
         self.stack = stages is not None
+        keys = apply_kw.pop("strength_keys", None)
+        if keys is not None and apply_kw.get("strength") is not None:
+            raise ValueError("strength and strength_keys are mutually exclusive")
+        self.strength_keys = strength_keys(keys) if isinstance(keys, str) else keys
+        self.frames_submitted = 0
+        if apply_kw.get("strength") is None:
+            apply_kw.pop("strength", None)
+        mixed = keys is not None or "strength" in apply_kw
+        if mixed and not self.stack:
+            raise ValueError("strength runs in the stage stack: it needs stages")
         if self.stack:
             if chain or lut1d:
                 raise ValueError("a stage stack names its lut3d2 / lut1d stages itself: chain / lut1d are not set with stages")
@@ -155,7 +169,8 @@ class HostPipeline:
                                 lut=bool(getattr(engine, "n", 0)), lut2=bool(getattr(engine, "n2", 0)),
                                 lut1d=bool(getattr(engine, "n1d", 0)), prelut=bool(getattr(engine, "_has_prelut", False)),
                                 dither=apply_kw.get("dither", "none"), chroma_loc=apply_kw.get("chroma_loc"), out_size=out_size,
-                                alpha_mode=apply_kw.get("alpha_mode", "straight"), out2_pix_fmt=second_pix_fmt)
+                                alpha_mode=apply_kw.get("alpha_mode", "straight"), out2_pix_fmt=second_pix_fmt,
+                                strength=apply_kw.get("strength", 1.0 if mixed else None))
             apply_kw = {k: v for k, v in apply_kw.items() if k not in ("dither", "alpha_mode", "interp") and
                         not (k == "cdl" and v is None)}
         self.chain = bool(chain)
@@ -238,6 +253,15 @@ class HostPipeline:
     def host_out2(self, slot: int) -> np.ndarray:
         return self.h_out2[slot].numpy()
 
+    def _run_stack(self, src, dst, nframes: int) -> None:
+        """One batch through the stage stack; with key frames every frame takes the strength of its number in the
+        stream, counted here across the batches."""
+        kw = self.kw
+        if self.strength_keys is not None:
+            kw = dict(kw, strength=self.strength_keys(self.frames_submitted, nframes))
+        self.frames_submitted += nframes
+        self.eng.apply_yuv_stack(src, dst, **kw)
+
     def _submit(self, slot: int, nframes: int) -> None:
         nb_in, nb_out = nframes * self.fin.frame_bytes, nframes * self.fout.frame_bytes
         with torch.cuda.stream(self.s_h2d):
@@ -247,7 +271,7 @@ class HostPipeline:
             self.s_run.wait_event(self.e_in[slot])
             dst = self.fout.plane_views(self.d_out[slot], nframes)
             if self.stack:
-                self.eng.apply_yuv_stack(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
+                self._run_stack(self.fin.plane_views(self.d_in[slot], nframes), dst, nframes)
             elif self.lut1d:
                 self.eng.apply_yuv_lut1d(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
             elif self.chain:
