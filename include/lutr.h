@@ -785,10 +785,48 @@ int lutr_apply_yuv_stack(lutr_ctx *ctx, const lutr_yuv_params *p, const lutr_sta
  * Kernels: always the mix forms, at strength 1 as well -- "k_yuv_stack_mix_vec<win,wout,icsx,icsy,ocsx,ocsy,tri,lds>[stages]",
  * "k_yuv_stack_mix_generic[stages]", "<vector kernel>+k_yuv_stack_mix_generic[stages]" for a ragged width, chosen by the rules of
  * lutr_apply_yuv_stack; both table placements give the same bits.
- * Not covered: what lutr_apply_yuv_stack does not cover; a tile (LDS window) kernel; a strength per pixel (a matte). */
+ * Not covered: what lutr_apply_yuv_stack does not cover; a tile (LDS window) kernel. */
 int lutr_apply_yuv_stack_mix(lutr_ctx *ctx, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
                              float strength, const float *frame_strength, int w, int h, int nframes, const lutr_planes *src,
                              const lutr_planes *dst, int row0, int rows);
+
+/* ---- a matte plane: a strength per pixel -- the key that holds a look off the skin tones, a power window, a
+ *      title-safe area left alone, a wipe between graded and ungraded. ----
+ * lutr_apply_yuv_stack_mix's pass with the strength of a pixel scaled by a matte sample.  The matte is one plane at luma
+ * resolution of unsigned codes of `depth` bits (8..16), Mm = 2^depth - 1: bytes when depth == 8, little-endian 16-bit words
+ * otherwise.  With a the code at the pixel's luma position and s' the clamped strength of the pixel's frame, in fp32 with every
+ * operation rounded on its own:
+ *   a'  = min(a, Mm)                          a 16-bit container may hold more than `depth` bits
+ *   a'' = invert ? Mm - a' : a'
+ *   t   = (float)a'' * rcp                    rcp = 1.0f / (float)Mm, formed once on the host
+ *   w   = s' * t
+ *   q_c = (int)((q0_c + w * (q1_c - q0_c)) + 0.5f)
+ * and q_c feeds the RGB -> YUV stage: luma per pixel, chroma from the block sums of the mixed codes, so a matte edge inside a
+ * chroma block is handled in RGB ahead of the mean.  t is increasing in a, never above 1 and exactly 1 at Mm: a matte of Mm
+ * everywhere (0 everywhere with invert) gives lutr_apply_yuv_stack_mix's output bit for bit, a matte of 0 everywhere that of
+ * strength 0.
+ * The matte has no chroma plane.  `data` is row 0 of the first frame, as the planes' pointers are; the sample of a pixel is at its
+ * absolute luma row and column, so row shards give the bits of the whole call.  frame_stride 0 with nframes > 1 is a still matte:
+ * every frame reads the same plane.
+ * Every refusal of lutr_apply_yuv_stack_mix, and LUTR_EINVAL before anything touches the device for: a null matte or data, a
+ * depth outside 8..16, invert outside 0 | 1, a stride shorter than a row of the matte, an odd base, stride or frame stride on a
+ * 16-bit container, a negative frame stride, a matte that overlaps a destination plane.
+ * Kernels: always the matte forms, with a constant matte as well --
+ * "k_yuv_stack_matte_vec<win,wout,wm,icsx,icsy,ocsx,ocsy,tri,lds>[stages]" (wm: the matte's container; built for wm == win and
+ * for bytes beside a 16-bit source; base, stride and frame stride aligned to the thread's 4..16 bytes),
+ * "k_yuv_stack_matte_generic[stages]" for everything else, "<vector kernel>+k_yuv_stack_matte_generic[stages]" for a ragged width.
+ * Not covered: what lutr_apply_yuv_stack_mix does not cover; a matte at chroma resolution or in floats; feathering or any
+ * other processing of the matte. */
+typedef struct lutr_matte {
+    const void *data;         /* device */
+    ptrdiff_t   stride;       /* bytes between rows */
+    int64_t     frame_stride; /* bytes between frames; 0 = one matte for every frame */
+    int32_t     depth;        /* 8..16 */
+    int32_t     invert;       /* 0 | 1 */
+} lutr_matte;
+int lutr_apply_yuv_stack_matte(lutr_ctx *ctx, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                               float strength, const float *frame_strength, const lutr_matte *matte, int w, int h, int nframes,
+                               const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
 
 /* ---- the alpha plane of yuva* / gbrap* frames: ProRes 4444 (yuva444p10le / 12le), VP8 / VP9 with alpha
  *      (yuva420p), PNG / TIFF / EXR sequences with alpha (rgba, rgba64le, gbrap*, gbrapf32le).  In the reference's chain lut3d

@@ -48,7 +48,7 @@ SYMBOLS = (
     "lutr_apply_yuv_dual", "lutr_apply_yuv_v210", "lutr_alpha_plane", "lutr_ctx_set_lut2", "lutr_apply_yuv_chain",
     "lutr_apply_yuv_premul", "lutr_apply_planar_rgb_f32_premul", "lutr_cdl_table", "lutr_apply_yuv_cdl",
     "lutr_lut1d_parse", "lutr_lut1d_table", "lutr_ctx_set_lut1d", "lutr_apply_yuv_lut1d", "lutr_apply_planar_rgb_lut1d",
-    "lutr_apply_yuv_stack", "lutr_apply_yuv_stack_mix",
+    "lutr_apply_yuv_stack", "lutr_apply_yuv_stack_mix", "lutr_apply_yuv_stack_matte",
     "lutr_resize_filter", "lutr_resize_planes", "lutr_dither_mask",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
     "lutr_max_waves_knob",
@@ -100,6 +100,12 @@ class CdlStruct(C.Structure):
 class StageStruct(C.Structure):
     """struct lutr_stage: one stage of a stack"""
     _fields_ = [("kind", C.c_int32), ("interp", C.c_int32)]
+
+
+class MatteStruct(C.Structure):
+    """struct lutr_matte: the matte plane of lutr_apply_yuv_stack_matte"""
+    _fields_ = [("data", C.c_void_p), ("stride", C.c_ssize_t), ("frame_stride", C.c_int64), ("depth", C.c_int32),
+                ("invert", C.c_int32)]
 
 
 def stage_array(stages):
@@ -256,6 +262,8 @@ def load() -> C.CDLL:
                                          C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_apply_yuv_stack_mix.argtypes = [vp, C.POINTER(YuvParams), C.POINTER(StageStruct), ci, C.POINTER(CdlStruct), C.c_float,
                                              vp, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
+    lib.lutr_apply_yuv_stack_matte.argtypes = [vp, C.POINTER(YuvParams), C.POINTER(StageStruct), ci, C.POINTER(CdlStruct), C.c_float,
+                                               vp, C.POINTER(MatteStruct), ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_dither_mask.argtypes = [C.POINTER(C.c_uint16)]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]

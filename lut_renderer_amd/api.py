@@ -210,10 +210,11 @@ def resolve_engine_dither(engine_dither: str, dither: str = "none") -> str:
 
 
 def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, engine, devices, precision,
-                 chroma_loc, out_size, alpha_mode, second_pix_fmt, strength=None):
+                 chroma_loc, out_size, alpha_mode, second_pix_fmt, strength=None, matte=None):
     """`apply_lut(stages=...)`: load what the list names, with the caches the single-feature routes use, and
     route to `apply_yuv_stack`.  `kw` is what `engine_call_for` returned, with `dither` filled in.  `strength`
-    travels to the engine; `stages` None is then the list the other options imply."""
+    travels to the engine; `stages` None is then the list the other options imply.  `matte`: None, or the dict of
+    the engine's `matte`, `matte_depth` and `matte_invert` arguments, which travels likewise."""
     from .plan import INTERP_WHITELIST
     from . import _native
     mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
@@ -243,7 +244,7 @@ def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d,
     check_stack_options(kw["pix_fmt"], kw["out_pix_fmt"], stages=st, cdl=cdl is not None, lut=lut is not None or held("n"),
                         lut2=lut2 is not None or held("n2"), lut1d=lut1d is not None or held("n1d"), prelut=prelut,
                         dither=kw.get("dither", "none"), chroma_loc=chroma_loc, out_size=out_size, alpha_mode=alpha_mode,
-                        out2_pix_fmt=second_pix_fmt, strength=strength, precision=precision)
+                        out2_pix_fmt=second_pix_fmt, strength=strength, precision=precision, matte=matte is not None)
     own = engine is None
     eng = engine if engine is not None else _cached_engine(devices)
     call = {k: v for k, v in kw.items() if k not in ("dither", "interp", "alpha_mode")}
@@ -263,6 +264,8 @@ def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d,
             eng.set_precision(precision)
         if strength is not None:
             call["strength"] = strength
+        if matte is not None:
+            call.update(matte)
         result = eng.apply_yuv_stack(planes, out, stages=st, cdl=cdl, **call)
         if own:
             eng.sync()
@@ -276,7 +279,8 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               devices: Sequence[int] = (0,), precision: str = "strict", chroma_loc: Optional[str] = None,
               resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
               cube2=None, interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None, cdl_id: Optional[str] = None,
-              lut1d=None, interp1d: str = "linear", stages=None, strength=None):
+              lut1d=None, interp1d: str = "linear", stages=None, strength=None, matte=None, matte_depth: Optional[int] = None,
+              matte_invert: bool = False):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -371,7 +375,13 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     order, so `cube` is ("lut3d",), `cdl` + `cube` ("cdl", "lut3d"), `lut1d` + `cube` ("lut1d", "lut3d"), `lut1d` alone ("lut1d",),
     `cube` + `cube2` ("lut3d", "lut3d2") -- on the stack's terms: whatever the stack refuses is refused with `strength`, in a
     message that names both, and so is a `precision` other than strict.  A plain `cube` with a strength therefore runs the
-    stack's gather kernel, not the LDS-window tile kernel.  None (default) leaves every route as it is."""
+    stack's gather kernel, not the LDS-window tile kernel.  None (default) leaves every route as it is.
+
+    `matte` (a key, a power window, a wipe) is a strength per pixel: a tensor on the engine's device at the luma
+    size of the frame, [H,W] or [1,H,W] (a still for every frame) or [F,H,W], uint8 or int16 / uint16 with `matte_depth` (9..16);
+    `matte_invert` takes Mm - a.  The strength of a pixel is `strength` (1 when not given) times its matte sample over Mm, applied
+    in RGB ahead of the chroma mean.  It routes to the stack as a strength does, on the same terms, in messages that name the
+    matte.  None (default) leaves every route as it is; `matte_depth` / `matte_invert` without a matte are a ValueError."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -419,9 +429,12 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         check_premul_options(kw["pix_fmt"], kw["out_pix_fmt"], dither=kw["dither"], chroma_loc=chroma_loc, out_size=out_size,
                              range_src=kw.get("range_src", "tv"), range_in=kw.get("range_in"), lut_depth=kw.get("lut_depth"),
                              out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None)
-    if stages is not None or strength is not None:
+    if matte is None and (matte_depth is not None or matte_invert is not False):
+        raise ValueError("matte_depth / matte_invert describe a matte: they need matte")
+    if stages is not None or strength is not None or matte is not None:
         result = _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, engine, devices, precision,
-                              chroma_loc, out_size, alpha_mode, second_pix_fmt, strength)
+                              chroma_loc, out_size, alpha_mode, second_pix_fmt, strength,
+                              None if matte is None else dict(matte=matte, matte_depth=matte_depth, matte_invert=matte_invert))
         return result, output_color_tags(plan.output_policy)
     if lut1d is not None:
         check_lut1d_options(kw["pix_fmt"], kw["out_pix_fmt"], interp1d=interp1d, dither=kw["dither"], chroma_loc=chroma_loc,

@@ -117,6 +117,15 @@ def build_parser() -> argparse.ArgumentParser:
                      help="engine setting: LUT strength by key frames -- frame F of the stream (counted from 0 across batches) "
                           "takes strength S, linear between the keys, held before the first and behind the last; e.g. 0:0,24:1 "
                           "ramps the look in over the first second.  Not together with --strength")
+    ap.add_argument("--matte", default=None, metavar="PATH",
+                    help="engine setting: a matte plane (DESIGN.md 3.23; a key, a power window, a wipe) -- raw gray frames of "
+                         "--size, read in lockstep with the input; the strength of a pixel is --strength (1 when not given) times "
+                         "its matte sample over the largest code, applied in RGB in the same pass.  A regular file of exactly one "
+                         "frame is a still for the whole stream; a matte that ends before the input is an error.  A file or FIFO, "
+                         "not '-'.  Runs the stage stack, as --strength does")
+    ap.add_argument("--matte-pix-fmt", default=None, metavar="FMT",
+                    help="pixel format of --matte: gray | gray10le | gray12le | gray14le | gray16le (default gray)")
+    ap.add_argument("--matte-invert", action="store_true", help="use the largest code minus the matte sample (an outside window)")
     ap.add_argument("-y", action="store_true", help="overwrite the output (ffmpeg's -y)")
     ap.add_argument("--duration", type=float, default=None,
                     help="seconds of video, for the Duration: line when the input is a pipe (-i -) and cannot be measured")
@@ -142,12 +151,14 @@ def stack_call_from_args(args, kw: dict, cdl) -> dict:
     """The keyword arguments of `apply_yuv_stack` for --stages from those `engine_call_for` returned: the stage
     list parsed with --interp / --interp2 as the lut3d stages' defaults, every refusal of `check_stack_options`, and a file for
     every stage and a stage for every file.  With --strength / --strength-keys and no --stages the list is the
-    one the other options imply (`formats.implied_stages`); `strength` or `strength_keys` (the parsed callable) go into the call."""
+    one the other options imply (`formats.implied_stages`); `strength` or `strength_keys` (the parsed callable) go into the call.
+    With --matte likewise; `matte` (the path), `matte_pix_fmt` and `matte_invert` go into the call."""
     from .plan import INTERP_WHITELIST
     interp2 = getattr(args, "interp2", None)
     mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
     cube2, lut1d = getattr(args, "cube2", None), getattr(args, "lut1d", None)
     strength, keys = strength_from_args(args)
+    matte = matte_from_args(args)
     listed = getattr(args, "stages", None)
     if listed is None:
         listed = implied_stages(args.cube is not None, cube2 is not None, lut1d is not None, cdl is not None)
@@ -177,7 +188,8 @@ def stack_call_from_args(args, kw: dict, cdl) -> dict:
                         chroma_loc=getattr(args, "chroma_loc", None), out_size=getattr(args, "out_size", None),
                         alpha_mode=getattr(args, "alpha_mode", None) or "straight",
                         out2_pix_fmt=second_fmt if second_fmt is not None else second_out,
-                        strength=strength if keys is None else 1.0, precision=getattr(args, "precision", None))
+                        strength=strength if keys is None else 1.0, precision=getattr(args, "precision", None),
+                        matte=matte is not None)
     call = {k: v for k, v in kw.items() if k not in ("interp", "alpha_mode", "dither")}
     call["stages"] = st
     if cdl is not None:
@@ -186,7 +198,26 @@ def stack_call_from_args(args, kw: dict, cdl) -> dict:
         call["strength"] = strength
     if keys is not None:
         call["strength_keys"] = keys
+    if matte is not None:
+        call.update(matte)
     return call
+
+
+def matte_from_args(args):
+    """None without --matte, else dict(matte=the path, matte_pix_fmt=, matte_invert=); --matte-pix-fmt / --matte-invert without
+    --matte, '-' and an unknown format are errors."""
+    from .formats import MATTE_PIX_FMTS
+    path, fmt, invert = getattr(args, "matte", None), getattr(args, "matte_pix_fmt", None), bool(getattr(args, "matte_invert", False))
+    if path is None:
+        if fmt is not None or invert:
+            raise ValueError("--matte-pix-fmt / --matte-invert describe a matte: they need --matte")
+        return None
+    if str(path) == "-":
+        raise ValueError("--matte is a file or FIFO, not '-': stdin carries the input")
+    fmt = fmt or "gray"
+    if fmt not in MATTE_PIX_FMTS:
+        raise ValueError(f"unknown --matte-pix-fmt '{fmt}' ({' | '.join(MATTE_PIX_FMTS)})")
+    return dict(matte=str(path), matte_pix_fmt=fmt, matte_invert=invert)
 
 
 def strength_from_args(args):
@@ -228,6 +259,7 @@ def plan_from_args(args):
                              out2_pix_fmt=getattr(args, "second_pix_fmt", None), lut2=getattr(args, "cube2", None) is not None)
     cdl = cdl_from_args(args)
     mixed = getattr(args, "strength", None) is not None or getattr(args, "strength_keys", None) is not None
+    mixed = mixed or matte_from_args(args) is not None
     if stages is not None or mixed:
         return plan, stack_call_from_args(args, kw, cdl), w, h
     if lut1d is not None:
@@ -318,7 +350,7 @@ def main(argv=None) -> int:
             raise FileExistsError(f"{second} exists (pass -y to overwrite)")
         from .cube import read_lut, read_lut1d
         from .engine import LutEngine
-        from .stream import HostPipeline
+        from .stream import HostPipeline, MatteReader
 
         lut2 = None if args.cube2 is None else read_lut(args.cube2)
         check_lut2(lut2)
@@ -332,6 +364,8 @@ def main(argv=None) -> int:
             eng.set_lut1d(read_lut1d(args.lut1d), args.interp1d)
         pix_fmt, out_fmt = kw.pop("pix_fmt"), kw.pop("out_pix_fmt")
         second_fmt = kw.pop("out2_pix_fmt", None)
+        if "matte" in kw:
+            kw["matte"] = MatteReader(kw.pop("matte"), kw.pop("matte_pix_fmt"), w, h)
         pipe = HostPipeline(eng, pix_fmt, w, h, batch=args.batch, out_pix_fmt=out_fmt, out_size=args.out_size,
                             second_pix_fmt=second_fmt, chain=lut2 is not None and "stages" not in kw,
                             lut1d=args.lut1d is not None and "stages" not in kw, **kw)

@@ -258,7 +258,8 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                    cube2: Optional[Path] = None, interp2: Optional[str] = None, alpha_mode: str = "straight",
                    cdl=None, cdl_id: Optional[str] = None, lut1d: Optional[Path] = None,
                    interp1d: Optional[str] = None, stages=None, strength: Optional[float] = None,
-                   strength_keys: Optional[str] = None) -> List[str]:
+                   strength_keys: Optional[str] = None, matte: Optional[Path] = None, matte_pix_fmt: Optional[str] = None,
+                   matte_invert: bool = False) -> List[str]:
     """`build_command`'s twin for the LUT stage alone: the argv of the ENGINE CLI (`python -m lut_renderer_amd.cli`)
     that applies exactly the chain `build_command` would put into `-vf` -- the same `LutPlan`, rendered as CLI options
     instead of as a filter string (ffmpeg.py:195-247, :287-310).  `source` / `output` are rawvideo files (or `-`) in
@@ -295,7 +296,12 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     `strength` (a number in [0, 1]) or `strength_keys` ("F:S,F:S,...", `params.strength_keys`) are engine settings
     beside `engine_dither` -- the reference's `ProcessingParams` has no such field: the graded frame mixed with the source in the
     same pass (`--strength` / `--strength-keys`, rendered only when given, never both).  They run the stage stack, with `stages`
-    or with the list the other options imply, and on its terms: the refusals are `check_stack_options`'s and name the strength."""
+    or with the list the other options imply, and on its terms: the refusals are `check_stack_options`'s and name the strength.
+    `matte` (the path of raw gray frames of the source's size, one for the whole stream or one per frame),
+    `matte_pix_fmt` (gray | gray10le | gray12le | gray14le | gray16le, default gray) and `matte_invert` are engine settings
+    likewise: a strength per pixel in the same pass (`--matte`, `--matte-pix-fmt`, `--matte-invert`, rendered only when given).
+    They run the stage stack as a strength does, in refusals that name the matte; `-` is refused, and so are `matte_pix_fmt` /
+    `matte_invert` without `matte`."""
     import sys as _sys
     premul = check_alpha_mode(alpha_mode)
     if precision not in ("strict", "fast", "fma32"):
@@ -379,7 +385,15 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     if strength is not None and strength_keys is not None:
         raise ValueError("strength and strength_keys are mutually exclusive: give one or neither")
     mixed = strength is not None or strength_keys is not None
-    stack = stages is not None or mixed      # the pairwise refusals below give way to check_stack_options at the end
+    if matte is None and (matte_pix_fmt is not None or matte_invert):
+        raise ValueError("matte_pix_fmt / matte_invert describe a matte: they need matte")
+    if matte is not None:
+        from .formats import MATTE_PIX_FMTS
+        if str(matte) == "-":
+            raise ValueError("matte is a file or FIFO, not '-': stdin carries the input")
+        if (matte_pix_fmt or "gray") not in MATTE_PIX_FMTS:
+            raise ValueError(f"unknown matte_pix_fmt '{matte_pix_fmt}' ({' | '.join(MATTE_PIX_FMTS)})")
+    stack = stages is not None or mixed or matte is not None      # the pairwise refusals below give way to check_stack_options at the end
     if cube2 is not None:
         from .plan import INTERP_WHITELIST
         if not stack:
@@ -445,7 +459,7 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                             lut=True, lut2=cube2 is not None, lut1d=lut1d is not None, dither=dither, chroma_loc=chroma_loc,
                             out_size=params.resolution if "--out-size" in cmd else None, alpha_mode=alpha_mode,
                             out2_pix_fmt=second_pix_fmt, strength=(strength if strength_keys is None else 1.0) if mixed else None,
-                            precision=precision)
+                            precision=precision, matte=matte is not None)
         if stages is not None:
             cmd += ["--stages", stages_string(st)]
         if strength is not None:
@@ -454,6 +468,12 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
             from .params import strength_keys as parse_keys
             parse_keys(strength_keys)
             cmd += ["--strength-keys", str(strength_keys)]
+        if matte is not None:
+            cmd += ["--matte", str(matte)]
+            if matte_pix_fmt is not None:
+                cmd += ["--matte-pix-fmt", matte_pix_fmt]
+            if matte_invert:
+                cmd += ["--matte-invert"]
     return cmd
 
 

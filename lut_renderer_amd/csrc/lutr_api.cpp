@@ -1612,9 +1612,10 @@ int lutr_apply_yuv_lut1d(lutr_ctx *c, const lutr_yuv_params *p, int interp, int 
 // lutr_apply_yuv_cdl's pass with the stage list compiled into steps: the pixel's state (codes or unit) is followed here, so the
 // kernels are told which form of a lattice stage to run and where the rounding goes.
 // `mix`: nullptr for lutr_apply_yuv_stack, the strength for lutr_apply_yuv_stack_mix.
+// `matte` (with `mix`): the matte of lutr_apply_yuv_stack_matte, its pointer, depth and invert already checked.
 static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
-                           const MixConsts *mix, int w, int h, int nframes, const lutr_planes *src, const lutr_planes *dst, int row0,
-                           int rows)
+                           const MixConsts *mix, const lutr_matte *matte, int w, int h, int nframes, const lutr_planes *src,
+                           const lutr_planes *dst, int row0, int rows)
 {
     if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
     if (nstages < 1 || nstages > 4) { set_error("stack: %d stages; a stack has 1 to 4", nstages); return LUTR_EINVAL; }
@@ -1708,6 +1709,27 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
     planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
     planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
     if (const int rc = check_disjoint("the stack pass", true, ss, 3, ds, 3)) return rc;
+    MatteConsts A{};
+    if (matte) {
+        const int mb = matte->depth > 8 ? 2 : 1;
+        if ((long long)matte->stride < (long long)w * mb) {
+            set_error("stack: matte stride %lld is shorter than a row of %d samples of %d byte(s)", (long long)matte->stride, w, mb);
+            return LUTR_EINVAL;
+        }
+        if (mb == 2 && (((uintptr_t)matte->data | (uintptr_t)matte->stride | (uintptr_t)matte->frame_stride) & 1)) {
+            set_error("stack: a matte of %d bits is held in 16-bit words: base, stride and frame stride must be even", matte->depth);
+            return LUTR_EINVAL;
+        }
+        const Span ms = plane_span(matte->data, matte->stride, matte->frame_stride, h, (long long)w * mb, nframes);
+        for (int j = 0; j < 3; j++)
+            if (ms.lo < ds[j].hi && ds[j].lo < ms.hi) {
+                set_error("stack: the byte range of the matte overlaps that of destination plane %d", j);
+                return LUTR_EINVAL;
+            }
+        const float maxm = (float)((1 << matte->depth) - 1);
+        A = MatteConsts{(const uint8_t *)matte->data, (long long)matte->stride, nframes > 1 ? (long long)matte->frame_stride : 0, maxm,
+                        1.0f / maxm, matte->invert, mb == 2};
+    }
     HIP_TRY(hipSetDevice(c->device));
     // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
     LutConsts L{}, L2{}; StackConsts S{}; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
@@ -1740,7 +1762,8 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
         S.lds_l1d_words = 3 * (S.stride >> 1);
     }
     fill_planes(&P, src, dst);
-    const char *name = launch_yuv_stack(c->stream, c->variant, L, L2, S, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, mix);
+    const char *name = launch_yuv_stack(c->stream, c->variant, L, L2, S, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, mix,
+                                        matte ? &A : nullptr);
     if (!name) return finish_launch(c, nullptr);
     const std::string full = std::string(name) + "[" + list + "]";
     return finish_launch(c, full.c_str());
@@ -1749,7 +1772,7 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
 int lutr_apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl, int w,
                          int h, int nframes, const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
 {
-    return apply_yuv_stack(c, p, stages, nstages, cdl, nullptr, w, h, nframes, src, dst, row0, rows);
+    return apply_yuv_stack(c, p, stages, nstages, cdl, nullptr, nullptr, w, h, nframes, src, dst, row0, rows);
 }
 
 // ---- the stack with a strength behind it: the same pass, the mix kernels whatever the strength
@@ -1765,7 +1788,29 @@ int lutr_apply_yuv_stack_mix(lutr_ctx *c, const lutr_yuv_params *p, const lutr_s
         return LUTR_EINVAL;
     }
     const MixConsts M{frame_strength, frame_strength ? 1.0f : strength};
-    return apply_yuv_stack(c, p, stages, nstages, cdl, &M, w, h, nframes, src, dst, row0, rows);
+    return apply_yuv_stack(c, p, stages, nstages, cdl, &M, nullptr, w, h, nframes, src, dst, row0, rows);
+}
+
+// ---- the stack with a matte scaling the strength per pixel: the same pass, the matte kernels whatever the matte
+int lutr_apply_yuv_stack_matte(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                               float strength, const float *frame_strength, const lutr_matte *matte, int w, int h, int nframes,
+                               const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+{
+    uint32_t bits;
+    memcpy(&bits, &strength, sizeof bits);
+    if (!frame_strength && ((bits & 0x7fffffffu) > 0x7f800000u || strength < 0.0f || strength > 1.0f)) {
+        set_error("stack: strength %g outside [0, 1]", (double)strength);
+        return LUTR_EINVAL;
+    }
+    if (!matte || !matte->data) { set_error("stack: null matte"); return LUTR_EINVAL; }
+    if (matte->depth < 8 || matte->depth > 16) { set_error("stack: matte depth %d outside 8..16", matte->depth); return LUTR_EINVAL; }
+    if (matte->invert != 0 && matte->invert != 1) { set_error("stack: matte invert %d is neither 0 nor 1", matte->invert); return LUTR_EINVAL; }
+    if (matte->frame_stride < 0) {
+        set_error("stack: matte frame stride %lld is negative", (long long)matte->frame_stride);
+        return LUTR_EINVAL;
+    }
+    const MixConsts M{frame_strength, frame_strength ? 1.0f : strength};
+    return apply_yuv_stack(c, p, stages, nstages, cdl, &M, matte, w, h, nframes, src, dst, row0, rows);
 }
 
 int lutr_apply_planar_rgb_lut1d(lutr_ctx *c, int depth, int w, int h, int nframes, const lutr_planes *src, const lutr_planes *dst,

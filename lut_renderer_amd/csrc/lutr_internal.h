@@ -216,10 +216,32 @@ struct MixConsts {
     const float *frame;
     float s;
 };
-// M = nullptr: the kernels of 3.21; else their mix forms (k_yuv_stack_mix_vec / k_yuv_stack_mix_generic), whatever the strength
+// The matte behind the list: one plane of unsigned codes at luma resolution, bytes or 16-bit words; `data` is row
+// 0 of the first frame, fstride 0 = one matte for every frame.  The strength of a pixel is its frame's times
+// (invert ? maxf - min(a, maxf) : min(a, maxf)) * rcp.
+struct MatteConsts {
+    const uint8_t *data;
+    long long stride, fstride;   // bytes
+    float maxf;                  // (float)(2^depth - 1)
+    float rcp;                   // 1.0f / maxf, formed on the host
+    int   invert;
+    int   wide;                  // 16-bit words
+};
+// M = nullptr: the kernels of 3.21; else their mix forms (k_yuv_stack_mix_vec / k_yuv_stack_mix_generic), whatever the strength;
+// A (with M): their matte forms (k_yuv_stack_matte_vec / k_yuv_stack_matte_generic), whatever the matte
 const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
                              const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int din, int dout, int icsx, int icsy,
-                             int ocsx, int ocsy, const MixConsts *M);
+                             int ocsx, int ocsy, const MixConsts *M, const MatteConsts *A);
+const char *launch_yuv_stack_matte_generic(hipStream_t st, unsigned grid, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
+                                           const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const MixConsts &M,
+                                           const MatteConsts &A, int win, int wout, int icsx, int icsy, int ocsx, int ocsy);
+// the matte vector kernels, one translation unit per (w<in wide><out wide><matte wide>)
+#define LUTR_SKA_DECL(tag) \
+    const char *launch_yuv_stack_matte_vec_##tag(hipStream_t st, const LutConsts &L, const LutConsts &L2, const StackConsts &S, \
+                                                 const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int icsx, int icsy, \
+                                                 int ocsx, int ocsy, bool tri, bool lds, MixConsts M, MatteConsts A);
+LUTR_SKA_DECL(w000) LUTR_SKA_DECL(w110) LUTR_SKA_DECL(w111) LUTR_SKA_DECL(w100) LUTR_SKA_DECL(w101)
+#undef LUTR_SKA_DECL
 // its vector kernels, one translation unit per container mix (w<in wide><out wide>) and form; tri: some lattice step is
 // trilinear; lds: stage the tables per workgroup
 const char *launch_yuv_stack_mix_generic(hipStream_t st, unsigned grid, const LutConsts &L, const LutConsts &L2, const StackConsts &S,

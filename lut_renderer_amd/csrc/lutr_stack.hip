@@ -21,17 +21,43 @@
 //                        trilinear) x 2 placements
 //   LUTR_SKM_WI / _WO    the same set in its MIX form: k_yuv_stack_mix_vec
 //   LUTR_SKM_GENERIC     the generic kernel in its MIX form: k_yuv_stack_mix_generic
+//   LUTR_SKA_WI / _WO / _WM   the vector kernels in their MATTE form, for one container mix and one matte container:
+//                        k_yuv_stack_matte_vec
+//   LUTR_SKA_GENERIC     the generic kernel in its MATTE form: k_yuv_stack_matte_generic
 //
 // MIX is a compile-time parameter of the translation unit, LUTR_SK_MIX: the same kernel text, with the pixel's
 // codes behind the YUV -> RGB stage (q0) kept across the step walk, or evaluated again behind it, and
 // q = (int)((q0 + s * (q1 - q0)) + 0.5f) sent to the RGB -> YUV stage; s is the strength of the pixel's frame, clamped to [0, 1].
 // A translation unit without it holds nothing of the mix: the kernels of 3.21 keep their code, registers and names.
+//
+// MATTE is a third form, LUTR_SK_MATTE, which implies LUTR_SK_MIX: the mix form's text with one more argument, a
+// plane of unsigned codes at luma resolution.  The strength of a pixel is the frame's times its matte sample: a' = min(a, Mm),
+// a'' = invert ? Mm - a' : a', w = s * (a'' * rcp), and w takes the place of s in the mix.  The vector kernels are built per
+// matte container (WM) beside the source's; where the matte's words are loaded is LUTR_SK_MATTE_LATE (3.23 point 5).  A
+// translation unit without LUTR_SK_MATTE holds nothing of it.
 #include <string>
 #if defined(LUTR_SKM_WI)
 #define LUTR_SK_WI LUTR_SKM_WI
 #define LUTR_SK_WO LUTR_SKM_WO
 #endif
-#if defined(LUTR_SKM_WI) || defined(LUTR_SKM_GENERIC)
+#if defined(LUTR_SKA_WI)
+#define LUTR_SK_WI LUTR_SKA_WI
+#define LUTR_SK_WO LUTR_SKA_WO
+#define LUTR_SK_WM LUTR_SKA_WM
+#endif
+#if defined(LUTR_SKA_WI) || defined(LUTR_SKA_GENERIC)
+#define LUTR_SK_MATTE 1
+#define LUTR_SK_MIX 1
+#define SK_MIX_PARAM , MixConsts M, MatteConsts A
+#define SK_MIX_ARG , M, A
+#define SK_WM_TPARAM int WM,
+#define SK_WM_TARG LUTR_SK_WM,
+#define SK_WM_NAME LUTR_STR(LUTR_SK_WM) ","
+#define SK_VEC k_yuv_stack_matte_vec
+#define SK_VEC_NAME "k_yuv_stack_matte_vec<"
+#define SK_VEC_LAUNCH_FN LUTR_CAT(LUTR_CAT(LUTR_CAT(launch_yuv_stack_matte_vec_w, LUTR_SK_WI), LUTR_SK_WO), LUTR_SK_WM)
+#define SK_GENERIC k_yuv_stack_matte_generic
+#elif defined(LUTR_SKM_WI) || defined(LUTR_SKM_GENERIC)
 #define LUTR_SK_MIX 1
 #define SK_MIX_PARAM , MixConsts M
 #define SK_MIX_ARG , M
@@ -46,6 +72,12 @@
 #define SK_VEC_NAME "k_yuv_stack_vec<"
 #define SK_VEC_LAUNCH launch_yuv_stack_vec_w
 #define SK_GENERIC k_yuv_stack_generic
+#endif
+#ifndef LUTR_SK_MATTE
+#define SK_WM_TPARAM
+#define SK_WM_TARG
+#define SK_WM_NAME
+#define SK_VEC_LAUNCH_FN LUTR_CAT(LUTR_CAT(SK_VEC_LAUNCH, LUTR_SK_WI), LUTR_SK_WO)
 #endif
 
 #include "lutr_device.h"
@@ -91,6 +123,18 @@ __device__ __forceinline__ Rgb mix_px(float s, const Rgb &q0, const Rgb &q1)
     q.g = (float)(int)((q0.g + s * (q1.g - q0.g)) + 0.5f);
     q.b = (float)(int)((q0.b + s * (q1.b - q0.b)) + 0.5f);
     return q;
+}
+#endif
+
+#ifdef LUTR_SK_MATTE
+// The strength of one pixel: the frame's strength s times the matte sample a (a code held as a float).  The clamp and the
+// inversion are on integers below 2^16, exact in fp32; then one rounded product each for the normalisation and the scaling.
+__device__ __forceinline__ float matte_weight(const MatteConsts &A, float s, float a)
+{
+    const float c = fminf(a, A.maxf);
+    const float v = A.invert ? A.maxf - c : c;
+    const float t = v * A.rcp;
+    return s * t;
 }
 #endif
 
@@ -154,7 +198,7 @@ __device__ __forceinline__ void stack_block(const StackConsts &S, const CdlConst
 
 // k_yuv_l1d_vec's structure (lutr_l1d.hip) with the step walk as the per-block middle.  TRI: some stage is trilinear (a stack of
 // nearest / tetrahedral stages does not carry trilinear's registers).  No thread leaves before the barrier behind the staging.
-template <int WIN, int WOUT, int ICSX, int ICSY, int OCSX, int OCSY, bool TRI, bool LDS>
+template <int WIN, int WOUT, SK_WM_TPARAM int ICSX, int ICSY, int OCSX, int OCSY, bool TRI, bool LDS>
 __global__ __launch_bounds__(256) void SK_VEC(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P, FrameGeom G SK_MIX_PARAM)
 {
     constexpr int VB = vec_bytes<WIN, WOUT>();
@@ -185,6 +229,17 @@ __global__ __launch_bounds__(256) void SK_VEC(LutConsts L, LutConsts L2, StackCo
                         cxo = (long long)xu * (CWO * 4);
 #ifdef LUTR_SK_MIX
         const float strength = mix_strength(M, fr);
+#endif
+#ifdef LUTR_SK_MATTE
+        // the matte samples of the thread's BH rows x PXT luma samples: whole dwords in every container mix this is built for
+        constexpr int MWI = PXT * (WM ? 2 : 1) / 4;
+        static_assert(MWI >= 1, "a thread must own whole matte words");
+        const uint8_t *mrow = A.data + fr * A.fstride + (long long)y0 * A.stride + (long long)xu * (MWI * 4);
+#ifndef LUTR_SK_MATTE_LATE
+        uint32_t mw[BH][MWI];
+#pragma unroll
+        for (int dy = 0; dy < BH; dy++) ld_words<MWI>(mw[dy], mrow + dy * A.stride);
+#endif
 #endif
 
         uint32_t yw[BH][YWI], cbw[IRH][CWI], crw[IRH][CWI];
@@ -234,6 +289,25 @@ __global__ __launch_bounds__(256) void SK_VEC(LutConsts L, LutConsts L2, StackCo
             }
 #endif
             stack_block<TRI>(S, C, l1d, L, L2, px);
+#ifdef LUTR_SK_MATTE
+            // the block's weights, in the mix's order.  LATE: the block's samples are read here, behind the walk -- nothing of the
+            // matte is live across the gathers, and the loads are exposed
+            float wgt[BH * BW];
+#pragma unroll
+            for (int dy = 0; dy < BH; dy++)
+#pragma unroll
+                for (int dx = 0; dx < BW; dx++) {
+#ifdef LUTR_SK_MATTE_LATE
+                    const float a = ld_sample(mrow + dy * A.stride, j * BW + dx, WM);   // hipcc merges the BW loads of a row
+#else
+                    const float a = word_sample<WM>(mw[dy], j * BW + dx);
+#endif
+                    wgt[dy * BW + dx] = matte_weight(A, strength, a);
+                }
+#define SK_STRENGTH(i) wgt[i]
+#else
+#define SK_STRENGTH(i) strength
+#endif
 #ifdef LUTR_SK_MIX
             if constexpr (AGAIN) {
 #pragma unroll
@@ -243,14 +317,15 @@ __global__ __launch_bounds__(256) void SK_VEC(LutConsts L, LutConsts L2, StackCo
 #pragma unroll
                     for (int dx = 0; dx < BW; dx++) {
                         const Rgb q0 = yuv_to_rgb(K, word_sample<WIN>(yw[dy], j * BW + dx), c[dy >> ICSY][dx >> ICSX]);
-                        px[dy * BW + dx] = mix_px(strength, q0, px[dy * BW + dx]);
+                        px[dy * BW + dx] = mix_px(SK_STRENGTH(dy * BW + dx), q0, px[dy * BW + dx]);
                     }
                 }
             } else {
 #pragma unroll
-                for (int i = 0; i < BH * BW; i++) px[i] = mix_px(strength, px0[i], px[i]);
+                for (int i = 0; i < BH * BW; i++) px[i] = mix_px(SK_STRENGTH(i), px0[i], px[i]);
             }
 #endif
+#undef SK_STRENGTH
             float rs[ORH][OBX], gs[ORH][OBX], bs[ORH][OBX];
 #pragma unroll
             for (int oy = 0; oy < ORH; oy++)
@@ -281,6 +356,10 @@ __global__ __launch_bounds__(256) void SK_VEC(LutConsts L, LutConsts L2, StackCo
                 for (int k = 0; k < YWI; k++) asm volatile("" : "+v"(yw[dy][k]));
 #pragma unroll
                 for (int k = 0; k < YWO; k++) asm volatile("" : "+v"(yo[dy][k]));
+#if defined(LUTR_SK_MATTE) && !defined(LUTR_SK_MATTE_LATE)
+#pragma unroll
+                for (int k = 0; k < MWI; k++) asm volatile("" : "+v"(mw[dy][k]));
+#endif
             }
 #pragma unroll
             for (int iy = 0; iy < IRH; iy++)
@@ -305,10 +384,9 @@ __global__ __launch_bounds__(256) void SK_VEC(LutConsts L, LutConsts L2, StackCo
 
 // The vector kernels of this translation unit's container mix; the layout checks are the caller's (launch_yuv_stack).  The grid:
 // with tables in LDS, eight workgroups a CU, each staging once and walking its share of the units; without, the usual cap.
-const char *LUTR_CAT(LUTR_CAT(SK_VEC_LAUNCH, LUTR_SK_WI), LUTR_SK_WO)(hipStream_t st, const LutConsts &L, const LutConsts &L2,
-                                                                      const StackConsts &S, const YuvConsts &K, const PlaneSet &P,
-                                                                      const FrameGeom &G, int icsx, int icsy, int ocsx, int ocsy,
-                                                                      bool tri, bool lds SK_MIX_PARAM)
+const char *SK_VEC_LAUNCH_FN(hipStream_t st, const LutConsts &L, const LutConsts &L2, const StackConsts &S, const YuvConsts &K,
+                             const PlaneSet &P, const FrameGeom &G, int icsx, int icsy, int ocsx, int ocsy, bool tri,
+                             bool lds SK_MIX_PARAM)
 {
     constexpr int WI = LUTR_SK_WI, WO = LUTR_SK_WO;
     constexpr int PXT = vec_bytes<WI, WO>() / (WI ? 2 : 1);
@@ -318,10 +396,10 @@ const char *LUTR_CAT(LUTR_CAT(SK_VEC_LAUNCH, LUTR_SK_WI), LUTR_SK_WO)(hipStream_
     const size_t lds_bytes = lds ? (size_t)(S.lds_cdl_words + S.lds_l1d_words) * sizeof(uint32_t) : 0;
 #define SK_CASE(IX, IY, OX, OY, T) \
     if (icsx == IX && icsy == IY && ocsx == OX && ocsy == OY && tri == (T != 0)) { \
-        if (lds) hipLaunchKernelGGL((SK_VEC<WI, WO, IX, IY, OX, OY, T != 0, true>), grid, block, lds_bytes, st, L, L2, S, K, P, G SK_MIX_ARG); \
-        else hipLaunchKernelGGL((SK_VEC<WI, WO, IX, IY, OX, OY, T != 0, false>), grid, block, 0, st, L, L2, S, K, P, G SK_MIX_ARG); \
-        return lds ? SK_VEC_NAME LUTR_STR(LUTR_SK_WI) "," LUTR_STR(LUTR_SK_WO) "," #IX "," #IY "," #OX "," #OY "," #T ",1>" \
-                   : SK_VEC_NAME LUTR_STR(LUTR_SK_WI) "," LUTR_STR(LUTR_SK_WO) "," #IX "," #IY "," #OX "," #OY "," #T ",0>"; \
+        if (lds) hipLaunchKernelGGL((SK_VEC<WI, WO, SK_WM_TARG IX, IY, OX, OY, T != 0, true>), grid, block, lds_bytes, st, L, L2, S, K, P, G SK_MIX_ARG); \
+        else hipLaunchKernelGGL((SK_VEC<WI, WO, SK_WM_TARG IX, IY, OX, OY, T != 0, false>), grid, block, 0, st, L, L2, S, K, P, G SK_MIX_ARG); \
+        return lds ? SK_VEC_NAME LUTR_STR(LUTR_SK_WI) "," LUTR_STR(LUTR_SK_WO) "," SK_WM_NAME #IX "," #IY "," #OX "," #OY "," #T ",1>" \
+                   : SK_VEC_NAME LUTR_STR(LUTR_SK_WI) "," LUTR_STR(LUTR_SK_WO) "," SK_WM_NAME #IX "," #IY "," #OX "," #OY "," #T ",0>"; \
     }
 #define SK_PAIR(IX, IY, OX, OY) SK_CASE(IX, IY, OX, OY, 0) SK_CASE(IX, IY, OX, OY, 1)
     SK_PAIR(1, 1, 1, 1) SK_PAIR(1, 1, 1, 0) SK_PAIR(1, 1, 0, 0)
@@ -367,6 +445,12 @@ __global__ __launch_bounds__(256) void SK_GENERIC(LutConsts L, LutConsts L2, Sta
 #ifdef LUTR_SK_MIX
                         const Rgb o0 = o;
 #endif
+#ifdef LUTR_SK_MATTE
+                        const float wgt = matte_weight(A, strength, ld_sample(A.data + fr * A.fstride + (long long)y * A.stride, x, A.wide));
+#define SK_STRENGTH wgt
+#else
+#define SK_STRENGTH strength
+#endif
 #pragma nounroll
                         for (unsigned long long ops = S.ops; ops & 0xffull; ops >>= 8) {
                             const int op = (int)(ops & 15u), mode = (int)((ops >> 4) & 15u);
@@ -381,8 +465,9 @@ __global__ __launch_bounds__(256) void SK_GENERIC(LutConsts L, LutConsts L2, Sta
                             }
                         }
 #ifdef LUTR_SK_MIX
-                        o = mix_px(strength, o0, o);
+                        o = mix_px(SK_STRENGTH, o0, o);
 #endif
+#undef SK_STRENGTH
                         rs += o.r; gs += o.g; bs += o.b;
                         if (yy < G.h && xx < G.w) sink.luma(fr, x, y, o);
                     }
@@ -394,7 +479,17 @@ __global__ __launch_bounds__(256) void SK_GENERIC(LutConsts L, LutConsts L2, Sta
     });
 }
 
-#ifdef LUTR_SK_MIX
+#if defined(LUTR_SK_MATTE)
+// the MATTE form's launch, for the launcher in the translation unit without LUTR_SK_MIX
+const char *launch_yuv_stack_matte_generic(hipStream_t st, unsigned grid, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
+                                           const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const MixConsts &M,
+                                           const MatteConsts &A, int win, int wout, int icsx, int icsy, int ocsx, int ocsy)
+{
+    hipLaunchKernelGGL(k_yuv_stack_matte_generic, dim3(grid), dim3(256), 0, st, L, L2, S, K, P, G, M, A, win, wout, icsx, icsy, ocsx,
+                       ocsy);
+    return "k_yuv_stack_matte_generic";
+}
+#elif defined(LUTR_SK_MIX)
 // the MIX form's launch, for the launcher in the translation unit without LUTR_SK_MIX
 const char *launch_yuv_stack_mix_generic(hipStream_t st, unsigned grid, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
                                          const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const MixConsts &M, int win,
@@ -423,7 +518,7 @@ static bool stack_in_lds(const StackConsts &S)
 
 const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
                              const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int din, int dout, int icsx, int icsy,
-                             int ocsx, int ocsy, const MixConsts *M)
+                             int ocsx, int ocsy, const MixConsts *M, const MatteConsts *A)
 {
     const int win = din > 8, wout = dout > 8;
     const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy), bh = 1 << csy;
@@ -452,10 +547,22 @@ const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, co
             if (!plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], (pxt >> icsx) * bsi, batch, kStrideAny, false) ||
                 !plane_ok(Q.d[c], Q.ds[c], Q.dfs[c], (pxt >> ocsx) * bso, batch, kStrideAny, false))
                 return false;
+        // the matte kernels: built for the source's container and for bytes beside a 16-bit source; whole aligned dwords a thread
+        if (A && (A->wide > win || !plane_ok(A->data, A->stride, A->fstride, pxt * (A->wide ? 2 : 1), batch, kStrideAny, false)))
+            return false;
         return true;
     };
     auto vec = [&](const PlaneSet &Q, const FrameGeom &H) -> const char * {
         ran |= 1;
+        if (A) {
+            if (win && wout)
+                return A->wide ? launch_yuv_stack_matte_vec_w111(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M, *A)
+                               : launch_yuv_stack_matte_vec_w110(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M, *A);
+            if (win)
+                return A->wide ? launch_yuv_stack_matte_vec_w101(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M, *A)
+                               : launch_yuv_stack_matte_vec_w100(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M, *A);
+            return launch_yuv_stack_matte_vec_w000(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M, *A);
+        }
         if (M) {
             if (win && wout) return launch_yuv_stack_mix_vec_w11(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M);
             if (win) return launch_yuv_stack_mix_vec_w10(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M);
@@ -467,6 +574,13 @@ const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, co
     };
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
         ran |= 2;
+        if (A) {
+            // the tail of a column split: the matte moves right with the source's luma plane
+            MatteConsts B = *A;
+            B.data += (Q.s[0] - P.s[0]) / bsi * (A->wide ? 2 : 1);
+            return launch_yuv_stack_matte_generic(st, block_grid(H.w, H.rows, H.nframes, csx, csy), L, L2, S, K, Q, H, *M, B, win, wout,
+                                                  icsx, icsy, ocsx, ocsy);
+        }
         if (M)
             return launch_yuv_stack_mix_generic(st, block_grid(H.w, H.rows, H.nframes, csx, csy), L, L2, S, K, Q, H, *M, win, wout, icsx,
                                                 icsy, ocsx, ocsy);
@@ -480,7 +594,7 @@ const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, co
     if (!name || ran != 3) return name;
     // a ragged width split between the two kernels: both are named
     static thread_local std::string both;
-    both = std::string(name) + (M ? "+k_yuv_stack_mix_generic" : "+k_yuv_stack_generic");
+    both = std::string(name) + (A ? "+k_yuv_stack_matte_generic" : M ? "+k_yuv_stack_mix_generic" : "+k_yuv_stack_generic");
     return both.c_str();
 }
 #endif  // LUTR_SK_MIX

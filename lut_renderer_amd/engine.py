@@ -24,7 +24,7 @@ from .cube import CubeLut, Lut1D, read_cube, read_lut, read_lut1d
 # (the formats and the checks of names and options live in formats.py; the names callers have always imported from here stay)
 from .formats import (_ALPHA_RESIZE, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, V210Fmt, chain_interp, chain_side,  # noqa: F401
                       changes_subsampling, check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc,
-                      check_lut1d_options, check_stack_options, check_strength,
+                      check_lut1d_options, check_matte, check_stack_options, check_strength,
                       check_container_options,
                       check_dual_options, check_lut2, check_packed_options, check_premul_options, check_semi_options,
                       chroma_loc_code, dual_side, has_prologue, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt,
@@ -914,7 +914,8 @@ class LutEngine:
                         out_pix_fmt: Optional[str] = None, stages, cdl: Optional[Cdl] = None, matrix_in: str = "bt709",
                         matrix_out: Optional[str] = None, range_src: str = "tv", range_in: Optional[str] = None,
                         range_out: str = "tv", lut_depth: Optional[int] = None, row0: int = 0, rows: Optional[int] = None,
-                        strength=None, **other):
+                        strength=None, matte: Optional[torch.Tensor] = None, matte_depth: Optional[int] = None,
+                        matte_invert: bool = False, **other):
         """`apply_yuv` with an ordered stack of 1..4 stages between its YUV -> RGB and RGB -> YUV stages, in one pass
         (lutr_apply_yuv_stack).  `stages` is a sequence of "lut3d" (`set_lut`), "lut3d2" (`set_lut2`), "lut1d"
         (`set_lut1d`), "cdl" (the `cdl` argument), each at most once; a lut3d stage may be a pair ("lut3d", "trilinear") -- the
@@ -929,7 +930,14 @@ class LutEngine:
         gives the bits of the call without it, 0 those of the two conversion stages alone.  A sequence, NumPy array or CPU tensor
         of one number per frame gives every frame of the call its own strength (frame 0 = the first frame of `src`, whatever
         row0 / rows are): it is checked on the host (length, finite, in [0, 1]; a ValueError names the index and the value),
-        uploaded on the engine's stream and held by the engine until the next such call replaces it."""
+        uploaded on the engine's stream and held by the engine until the next such call replaces it.
+        `matte`: None runs the passes above unchanged.  A tensor on the engine's device, [H,W] or [1,H,W] (a still:
+        one matte for every frame) or [F,H,W], at the luma size of the frame, uint8 (`matte_depth` 8, the default) or int16 /
+        uint16 (`matte_depth` 9..16, required; a code above 2^matte_depth - 1 acts as that), scales the strength per pixel in the
+        same pass (lutr_apply_yuv_stack_matte): w = s * (a / Mm), or s * ((Mm - a) / Mm) with `matte_invert`, takes the place of s
+        in the mix above, ahead of the chroma mean.  `strength` defaults to 1 with a matte.  A matte of Mm everywhere gives the
+        bits of the call with the strength alone, 0 everywhere those of strength 0.  The matte is not processed in any way; the
+        alpha plane of a yuva* source goes past it unchanged -- to key on it, pass it as `matte` (`formats.check_matte`)."""
         for k in other:
             if k not in ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt"):
                 raise TypeError(f"apply_yuv_stack() got an unexpected keyword argument '{k}'")
@@ -939,7 +947,8 @@ class LutEngine:
             pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(self, "n", 0)),
             lut2=bool(getattr(self, "n2", 0)), lut1d=bool(getattr(self, "n1d", 0)), prelut=bool(getattr(self, "_has_prelut", False)),
             dither=other.get("dither", "none"), chroma_loc=other.get("chroma_loc"), out_size=other.get("out_size"),
-            alpha_mode=other.get("alpha_mode", "straight"), out2_pix_fmt=other.get("out2_pix_fmt"), strength=strength)
+            alpha_mode=other.get("alpha_mode", "straight"), out2_pix_fmt=other.get("out2_pix_fmt"), strength=strength,
+            matte=matte is not None)
         if fin.alpha or fout.alpha:
             # yuva*: the colour planes through this very call under their three-plane names, then the alpha plane on the same
             # stream, exactly as the CDL call does; straight alpha goes past the mix unchanged
@@ -956,7 +965,8 @@ class LutEngine:
             self._alpha_tail(lambda: self.apply_yuv_stack(
                 src[:3], dst[:3], pix_fmt=fin.colour.name, out_pix_fmt=fout.colour.name, stages=st, cdl=cdl, matrix_in=matrix_in,
                 matrix_out=matrix_out, range_src=range_src, range_in=range_in, range_out=range_out, lut_depth=lut_depth, row0=row0,
-                rows=rows, strength=strength), [(fout, dst)], a_src, fin.depth, w, h, row0, rows)
+                rows=rows, strength=strength, matte=matte, matte_depth=matte_depth, matte_invert=matte_invert),
+                [(fout, dst)], a_src, fin.depth, w, h, row0, rows)
             return dst
         p = _yuv_call_params(fin, fout, lut_depth, matrix_in, matrix_out, range_src, range_in, range_out)
         h, w = src[0].shape[-2], src[0].shape[-1]
@@ -970,9 +980,28 @@ class LutEngine:
         arr = _native.stage_array(st)
         k = None if cdl is None else C.byref(_native.cdl_struct(cdl))
         strength = check_strength(strength, nf)
+        if matte is not None:
+            matte, mdepth, minvert, still = check_matte(matte, matte_depth, matte_invert, w=w, h=h, nframes=nf, device=self.device)
+            m = _native.MatteStruct()
+            m.data = matte.data_ptr()
+            m.stride = matte.stride(-2) * matte.element_size()
+            m.frame_stride = 0 if still else matte.stride(0) * matte.element_size()
+            m.depth, m.invert = mdepth, minvert
+            if strength is None:
+                strength = 1.0
         with self._lock:
             self._bind_stream()
-            if strength is None:
+            if matte is not None:
+                frame = None
+                if not isinstance(strength, float):              # one float per frame: uploaded and kept as below
+                    if not self.use_torch_stream and self._frame_strength is not None:
+                        self.sync()
+                    self._frame_strength = torch.from_numpy(strength).to(self.device)
+                    frame = C.c_void_p(self._frame_strength.data_ptr())
+                _native.check(self._lib.lutr_apply_yuv_stack_matte(
+                    self._ctx, C.byref(p), arr, len(st), k, strength if frame is None else 1.0, frame, C.byref(m), w, h, nf,
+                    C.byref(s), C.byref(d), row0, rows))
+            elif strength is None:
                 _native.check(self._lib.lutr_apply_yuv_stack(
                     self._ctx, C.byref(p), arr, len(st), k, w, h, nf, C.byref(s), C.byref(d), row0, rows))
             elif isinstance(strength, float):

@@ -645,6 +645,52 @@ def check_strength(strength, nframes: Optional[int] = None):
     return arr.astype(np.float32)
 
 
+#: what `--matte-pix-fmt` takes -> the matte's depth: one plane of unsigned codes, bytes at 8 bit, else
+#: little-endian 16-bit words
+MATTE_PIX_FMTS = {"gray": 8, "gray10le": 10, "gray12le": 12, "gray14le": 14, "gray16le": 16}
+
+
+def check_matte(matte, matte_depth=None, matte_invert=False, *, w: int, h: int, nframes: int, device=None):
+    """The `matte`, `matte_depth` and `matte_invert` arguments of a stage stack, the one copy of their checks.
+    `matte` is a torch tensor [H, W], [1, H, W] (both a still: one matte for every frame) or [F, H, W] with the call's `nframes`
+    frames, at the luma size `w` x `h` of the call, of dtype uint8 (depth 8, the default) or int16 / uint16 (`matte_depth` 9..16,
+    required), dense along the row, on `device` (the engine's; None: not checked).  Returns (matte, depth, invert as 0 | 1,
+    still).  ValueError otherwise, naming the argument and the fault."""
+    if not (hasattr(matte, "dim") and hasattr(matte, "data_ptr") and hasattr(matte, "element_size")):
+        raise ValueError(f"matte is a torch tensor [H,W], [1,H,W] or [F,H,W] on the engine's device, not {type(matte).__name__}")
+    if device is not None and matte.device != device:
+        raise ValueError(f"matte is on {matte.device}, the engine is on {device}: the matte must be on the engine's device")
+    name = str(matte.dtype).replace("torch.", "")
+    if name not in ("uint8", "int16", "uint16"):
+        raise ValueError(f"matte has dtype {name}: a matte is uint8, or int16 / uint16 with matte_depth")
+    wide = name != "uint8"
+    if isinstance(matte_depth, bool) or (matte_depth is not None and not isinstance(matte_depth, (int, np.integer))):
+        raise ValueError(f"matte_depth is an integer in 8..16, not {matte_depth!r}")
+    if matte_depth is None:
+        if wide:
+            raise ValueError(f"matte_depth is required for a {name} matte (9..16: the bits of its codes)")
+        matte_depth = 8
+    depth = int(matte_depth)
+    if not 8 <= depth <= 16:
+        raise ValueError(f"matte_depth {depth} is outside 8..16")
+    if wide and depth == 8:
+        raise ValueError(f"matte_depth 8 is held in bytes: a {name} matte has matte_depth 9..16")
+    if not wide and depth != 8:
+        raise ValueError(f"matte_depth {depth} is held in 16-bit words: a uint8 matte has matte_depth 8")
+    if not isinstance(matte_invert, (bool, np.bool_)):
+        raise ValueError(f"matte_invert is True or False, not {matte_invert!r}")
+    if matte.dim() not in (2, 3):
+        raise ValueError(f"matte has shape {tuple(matte.shape)}: a matte is [H,W], [1,H,W] or [F,H,W]")
+    if tuple(matte.shape[-2:]) != (h, w):
+        raise ValueError(f"matte is {matte.shape[-1]}x{matte.shape[-2]}, the frame is {w}x{h}: a matte has the luma size of the frame")
+    still = matte.dim() == 2 or matte.shape[0] == 1
+    if not still and matte.shape[0] != nframes:
+        raise ValueError(f"matte has {matte.shape[0]} frames for {nframes} frames: a matte has one frame (a still) or one per frame")
+    if w > 1 and matte.stride(-1) != 1:
+        raise ValueError("matte must be dense along the row")
+    return matte, depth, int(bool(matte_invert)), still
+
+
 def implied_stages(cube: bool, cube2: bool = False, lut1d: bool = False, cdl: bool = False) -> Tuple[str, ...]:
     """The stage list the options of a call without `stages` imply when a strength sends it to the stack: the
     order of the dedicated routes -- lut1d, cdl, lut3d, lut3d2.  A 1D LUT without `cube` is lut1d alone, as in `apply_lut`;
@@ -665,17 +711,23 @@ def check_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = Non
                         lut: bool = True, lut2: bool = True, lut1d: bool = True, prelut: bool = False, dither: str = "none",
                         chroma_loc: Optional[str] = None, out_size=None, alpha_mode: str = "straight",
                         out2_pix_fmt: Optional[str] = None, variant: Optional[str] = None, strength=None,
-                        precision: Optional[str] = None):
+                        precision: Optional[str] = None, matte: bool = False):
     """The checks every layer makes of a stage stack before any GPU work, the one copy of its refusals: a stage
     list `parse_stages` takes; every listed stage's resource there (`lut`, `lut2`, `lut1d`: a first / second lattice, a 1D LUT is
     loaded; `cdl`: a CDL is given) and no CDL without a cdl stage; no lut3d directly behind cdl when the first LUT carries a .csp
     prelut (`prelut`); planar YUV on both sides (yuva* with straight alpha included); no dither, chroma_loc, out_size, second
     output or premultiplied alpha; not the vec_lds variant.  With a `strength` (anything but None) every message
     names it beside the option, the strength itself is checked (`check_strength`) and a `precision` other than strict is refused.
+    With `matte` (True: the call has a matte plane, which `check_matte` checks) every message names the matte as
+    well, and `precision` is refused likewise.
     Returns (parsed stages, source format, output format)."""
     mixed = strength is not None
+    matte = matte is not None and matte is not False
     tail = "a stage stack with strength" if mixed else "a stage stack"
     noun = "stack (strength)" if mixed else "stack"
+    if matte:
+        tail = "a stage stack with strength and a matte" if mixed else "a stage stack with a matte"
+        noun = "stack (strength, matte)" if mixed else "stack (matte)"
     st = parse_stages(stages)
     kinds = [k for k, _m in st]
     if "lut3d" in kinds and not lut:
@@ -705,9 +757,10 @@ def check_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = Non
         raise ValueError(f"alpha_mode='{alpha_mode}' is not supported with {tail}")
     if variant == "vec_lds":
         raise ValueError(f"variant vec_lds is not supported with {tail}: there is no LDS-window kernel for the stack pass")
+    if (mixed or matte) and precision not in (None, "strict"):
+        what = "strength and a matte" if mixed and matte else "a matte" if matte else "strength"
+        raise ValueError(f"precision='{precision}' is not supported with {what}: the mix is defined on the strict path only")
     if mixed:
-        if precision not in (None, "strict"):
-            raise ValueError(f"precision='{precision}' is not supported with strength: the mix is defined on the strict path only")
         check_strength(strength)
     return st, fin, fout
 

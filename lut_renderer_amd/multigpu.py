@@ -29,7 +29,7 @@ import torch
 from . import _native
 from .cube import CubeLut, read_lut, read_lut1d
 from .engine import LutEngine, _fresh_planes, _new_planes, _yuv_out_dtype, chain_args, dual_args
-from .formats import (check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2, check_stack_options, check_strength,
+from .formats import (check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2, check_matte, check_stack_options, check_strength,
                       check_premul_options,
                       packed_frame_width, parse_pix_fmt, parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords,
                       v210_frame_width, yuv_side)
@@ -356,7 +356,9 @@ class LutEngineGroup:
         """`LutEngine.apply_yuv_stack` with the rows of every frame split over the group's devices: the lattices
         and the 1D LUT are on every engine through the group's setters, the CDL travels with the call; shards on multiples of the
         union block height of the two layouts, alpha rows go with the luma rows, no halo.  `strength` as the
-        engine takes it: a per-frame array goes to every device once, and the shards give the bits of the whole call."""
+        engine takes it: a per-frame array goes to every device once, and the shards give the bits of the whole call.  `matte`
+         as the engine takes it, on the source's device: its rows travel with the source's luma rows, a still's
+        once per device, and a pixel reads the sample of its own row and column on every shard."""
         with self._lock:
             if "row0" in kw or "rows" in kw:
                 raise ValueError("the group owns the row partition")
@@ -365,7 +367,11 @@ class LutEngineGroup:
                 pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(e0, "n", 0)),
                 lut2=bool(getattr(e0, "n2", 0)), lut1d=bool(self.n1d), prelut=bool(getattr(e0, "_has_prelut", False)),
                 dither=kw.get("dither", "none"), chroma_loc=kw.get("chroma_loc"), out_size=kw.get("out_size"),
-                alpha_mode=kw.get("alpha_mode", "straight"), out2_pix_fmt=kw.get("out2_pix_fmt"), strength=kw.get("strength"))
+                alpha_mode=kw.get("alpha_mode", "straight"), out2_pix_fmt=kw.get("out2_pix_fmt"), strength=kw.get("strength"),
+                matte=kw.get("matte") is not None)
+            if kw.get("matte") is not None:
+                check_matte(kw["matte"], kw.get("matte_depth"), kw.get("matte_invert", False), w=src[0].shape[-1], h=src[0].shape[-2],
+                            nframes=src[0].shape[0] if len(src[0].shape) == 3 else 1, device=src[0].device)
             if kw.get("strength") is not None:
                 # checked once for the whole call; every engine uploads its own copy of a per-frame array, and a shard's frame
                 # 0 is the call's frame 0 (rows are split, frames are not)
@@ -380,7 +386,8 @@ class LutEngineGroup:
                 eng.apply_yuv_stack(src, dst, row0=r0, rows=r1 - r0, **names, **kw)
 
             def remote(eng, r0, r1):
-                out = eng.apply_yuv_stack(_travel(src, _row_ranges(fin, r0, r1), eng.device), None, **names, **kw)
+                there = kw if kw.get("matte") is None else dict(kw, matte=_travel([kw["matte"]], [(r0, r1)], eng.device)[0])
+                out = eng.apply_yuv_stack(_travel(src, _row_ranges(fin, r0, r1), eng.device), None, **names, **there)
                 return [(dst, out, _row_ranges(fout, r0, r1))]
 
             self._shard(h, 1 << max(fin.csy, fout.csy), home, local, remote)

@@ -51,7 +51,8 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
                           interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None,
                           cdl_id: Optional[str] = None, lut1d: Optional[Path] = None,
                           interp1d: Optional[str] = None, stages=None, strength: Optional[float] = None,
-                          strength_keys: Optional[str] = None) -> StageCommands:
+                          strength_keys: Optional[str] = None, matte: Optional[Path] = None,
+                          matte_pix_fmt: Optional[str] = None, matte_invert: bool = False) -> StageCommands:
     """The three argv lists of one LUT stage.  Raises what `build_command` / `engine_command` raise (copy guard, missing
     geometry).  `chroma_loc` goes to the engine (`--chroma-loc`) and, as `-chroma_sample_location`, to the encoder, so the
     output stream declares the siting the engine assumed.  `gpu_resize` with `params.resolution` set resizes in the engine
@@ -62,14 +63,18 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
     LUT, DESIGN.md 3.19: `--cdl` / `--cdl-id`, or `--cdl-sop` / `--cdl-sat` for a `cdl.Cdl`) and for `lut1d` / `interp1d` (a 1D LUT
     file ahead of the LUT, DESIGN.md 3.20: `--lut1d` / `--interp1d`), and for `stages` (these operators as an ordered stack in one
     pass, DESIGN.md 3.21: `--stages`, rendered only when given), and for `strength` / `strength_keys` (the LUT's strength, DESIGN.md
-    3.22: `--strength` / `--strength-keys`, rendered only when given; the key frames count the frames of the stream)."""
+    3.22: `--strength` / `--strength-keys`, rendered only when given; the key frames count the frames of the stream), and for `matte` /
+    `matte_pix_fmt` / `matte_invert` (a matte plane, DESIGN.md 3.23: `--matte` / `--matte-pix-fmt` / `--matte-invert`, rendered only
+    when given; the matte file is raw gray frames at the size of the decoded source)."""
     notes: List[str] = []
     engine = engine_command(Path("-"), Path("-"), params, lut_path, source_info, python_bin=python_bin, device=device, notes=notes,
                             precision=precision, chroma_loc=chroma_loc, gpu_resize=gpu_resize, engine_dither=engine_dither,
                             cube2=cube2, interp2=interp2, alpha_mode=alpha_mode, cdl=cdl, cdl_id=cdl_id, lut1d=lut1d,
                             interp1d=interp1d, **({} if stages is None else {"stages": stages}),
                             **({} if strength is None else {"strength": strength}),
-                            **({} if strength_keys is None else {"strength_keys": strength_keys}))
+                            **({} if strength_keys is None else {"strength_keys": strength_keys}),
+                            **({} if matte is None and matte_pix_fmt is None and not matte_invert else
+                               {"matte": matte, "matte_pix_fmt": matte_pix_fmt, "matte_invert": matte_invert}))
     resized = gpu_resize and bool(params.resolution)
     if source_info.duration:
         engine += ["--duration", f"{float(source_info.duration):.3f}"]
@@ -170,6 +175,9 @@ def main(argv=None) -> int:
     mix = ap.add_mutually_exclusive_group()
     mix.add_argument("--strength", default=None, type=float, help="engine setting: LUT strength in [0, 1], see lut_renderer_amd.cli")
     mix.add_argument("--strength-keys", default=None, help="engine setting: LUT strength by key frames F:S,F:S,..., see lut_renderer_amd.cli")
+    ap.add_argument("--matte", default=None, help="engine setting: a matte plane (raw gray frames), see lut_renderer_amd.cli")
+    ap.add_argument("--matte-pix-fmt", default=None, help="pixel format of --matte, see lut_renderer_amd.cli")
+    ap.add_argument("--matte-invert", action="store_true", help="invert --matte, see lut_renderer_amd.cli")
     ap.add_argument("--gpu-resize", action="store_true", help="resize to the params' resolution in the engine (--out-size) instead of the encoder")
     a = ap.parse_args(argv)
     try:
@@ -186,7 +194,9 @@ def main(argv=None) -> int:
                                      engine_dither=a.engine_dither, cube2=None if a.cube2 is None else Path(a.cube2),
                                      interp2=a.interp2, alpha_mode=a.alpha_mode, cdl=cdl, cdl_id=a.cdl_id,
                                      lut1d=None if a.lut1d is None else Path(a.lut1d), interp1d=a.interp1d,
-                                     stages=a.stages, strength=a.strength, strength_keys=a.strength_keys)
+                                     stages=a.stages, strength=a.strength, strength_keys=a.strength_keys,
+                                     matte=None if a.matte is None else Path(a.matte), matte_pix_fmt=a.matte_pix_fmt,
+                                     matte_invert=a.matte_invert)
     except Exception as exc:
         print(f"Error: {exc}", flush=True)
         return 1

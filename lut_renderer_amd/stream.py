@@ -12,6 +12,8 @@ Frames are rawvideo-style: planes back to back (Y, Cb, Cr), frames back to back 
 """
 from __future__ import annotations
 
+import os
+import stat
 from dataclasses import dataclass
 from typing import Callable, Iterable, Iterator, List, Optional
 
@@ -20,7 +22,7 @@ import torch
 
 from .engine import LutEngine
 from .params import strength_keys
-from .formats import (RgbSource, check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options,
+from .formats import (MATTE_PIX_FMTS, RgbSource, check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options,
                       check_lut1d_options, check_stack_options,
                       check_premul_options, parse_rgb_source, parse_size, premul_to_yuv, refuse_alpha_resize, yuv_side)
 
@@ -135,6 +137,51 @@ def dual_layout(pix_fmt: str, out_pix_fmt: Optional[str], second_pix_fmt: Option
     return FrameLayout(f2, width, height)
 
 
+class MatteReader:
+    """The matte of a stream: raw frames of `width` x `height` gray samples (`pix_fmt`: gray, or gray10le ..
+    gray16le in little-endian 16-bit words), read in lockstep with the input batches.  A regular file that holds exactly one frame
+    is a still: it is read once (`still`, [H, W]) and serves the whole stream.  Anything else is a stream of one matte per
+    frame; `read(n)` gives the next n as [n, H, W] and raises a ValueError naming the frame number when the stream ends before
+    the input does.  No device work: `HostPipeline` uploads what this reads."""
+
+    def __init__(self, path, pix_fmt: str, width: int, height: int):
+        if pix_fmt not in MATTE_PIX_FMTS:
+            raise ValueError(f"unknown matte pixel format '{pix_fmt}' ({' | '.join(MATTE_PIX_FMTS)})")
+        if str(path) == "-":
+            raise ValueError("the matte is a file or FIFO, not '-': stdin carries the input")
+        self.path, self.pix_fmt, self.depth = str(path), pix_fmt, MATTE_PIX_FMTS[pix_fmt]
+        self.width, self.height = int(width), int(height)
+        self.dtype = np.dtype(np.uint8) if self.depth == 8 else np.dtype("<u2")
+        self.frame_bytes = self.width * self.height * self.dtype.itemsize
+        self.frames_read = 0
+        self.still = None
+        st = os.stat(self.path)
+        self._f = open(self.path, "rb")
+        if stat.S_ISREG(st.st_mode) and st.st_size == self.frame_bytes:
+            self.still = self.read(1)[0]
+            self.close()
+
+    def read(self, n: int) -> np.ndarray:
+        """The mattes of the next `n` frames of the stream, [n, H, W]."""
+        buf = bytearray(n * self.frame_bytes)
+        view, got = memoryview(buf), 0
+        while got < len(view):                               # a FIFO returns short reads: collect the whole batch (or EOF)
+            k = self._f.readinto(view[got:])
+            if not k:
+                break
+            got += k
+        if got < len(view):
+            raise ValueError(f"matte '{self.path}' ended at frame {self.frames_read + got // self.frame_bytes}: the input goes on "
+                             f"(a matte has one frame for the whole stream or one for every frame)")
+        self.frames_read += n
+        return np.frombuffer(buf, dtype=self.dtype).reshape(n, self.height, self.width)
+
+    def close(self) -> None:
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+
+
 class HostPipeline:
     """Apply the LUT to batches of host frames with copies overlapped against compute."""
 
@@ -150,8 +197,17 @@ class HostPipeline:
         # `apply_kw["strength"]` (a number) or `apply_kw["strength_keys"]` ("F:S,..." or `params.strength_keys`' callable) mix the
         # graded frame with the source: the keys are read at the frame's number in the stream, counted here
         # across the batches
+        # `apply_kw["matte"]` (a `MatteReader`) scales the strength per pixel: a still is uploaded once, a matte
+        # per frame is read and uploaded with every input batch; `apply_kw["matte_invert"]` travels to the engine
         stages = apply_kw.get("stages")
         self.stack = stages is not None
+        self.matte = apply_kw.pop("matte", None)
+        if self.matte is None:
+            apply_kw.pop("matte_invert", None)
+        elif not self.stack:
+            raise ValueError("a matte runs in the stage stack: it needs stages")
+        elif (self.matte.width, self.matte.height) != (width, height):
+            raise ValueError(f"the matte is {self.matte.width}x{self.matte.height}, the frames are {width}x{height}")
         keys = apply_kw.pop("strength_keys", None)
         if keys is not None and apply_kw.get("strength") is not None:
             raise ValueError("strength and strength_keys are mutually exclusive")
@@ -170,7 +226,7 @@ class HostPipeline:
                                 lut1d=bool(getattr(engine, "n1d", 0)), prelut=bool(getattr(engine, "_has_prelut", False)),
                                 dither=apply_kw.get("dither", "none"), chroma_loc=apply_kw.get("chroma_loc"), out_size=out_size,
                                 alpha_mode=apply_kw.get("alpha_mode", "straight"), out2_pix_fmt=second_pix_fmt,
-                                strength=apply_kw.get("strength", 1.0 if mixed else None))
+                                strength=apply_kw.get("strength", 1.0 if mixed else None), matte=self.matte is not None)
             apply_kw = {k: v for k, v in apply_kw.items() if k not in ("dither", "alpha_mode", "interp") and
                         not (k == "cdl" and v is None)}
         self.chain = bool(chain)
@@ -239,6 +295,14 @@ class HostPipeline:
             self.kw["out2_pix_fmt"] = self.fout2.fmt.name
             self.h_out2 = [torch.empty(self.batch * self.fout2.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]
             self.d_out2 = [torch.empty(self.batch * self.fout2.frame_bytes, dtype=torch.uint8, device=dev) for _ in range(slots)]
+        if self.matte is not None:
+            self.kw["matte_depth"] = self.matte.depth
+            if self.matte.still is not None:
+                self.d_matte = self._matte_tensor(self.matte.still).to(dev)
+            else:
+                nb = self.batch * self.matte.frame_bytes
+                self.h_matte = [torch.empty(nb, dtype=torch.uint8).pin_memory() for _ in range(slots)]
+                self.d_matte = [torch.empty(nb, dtype=torch.uint8, device=dev) for _ in range(slots)]
         self.s_h2d, self.s_run, self.s_d2h = (torch.cuda.Stream(dev) for _ in range(3))
         self.e_in = [torch.cuda.Event() for _ in range(slots)]
         self.e_run = [torch.cuda.Event() for _ in range(slots)]
@@ -253,10 +317,31 @@ class HostPipeline:
     def host_out2(self, slot: int) -> np.ndarray:
         return self.h_out2[slot].numpy()
 
-    def _run_stack(self, src, dst, nframes: int) -> None:
+    @staticmethod
+    def _matte_tensor(a: np.ndarray) -> torch.Tensor:
+        """A host matte as the tensor the engine takes: uint8, or the 16-bit words as int16."""
+        return torch.from_numpy(np.ascontiguousarray(a) if a.dtype == np.uint8 else np.ascontiguousarray(a).view(np.int16))
+
+    def _load_matte(self, slot: int, nframes: int):
+        """The matte of the batch in `slot`: the still, or the next `nframes` frames of the matte stream read into the slot's pinned
+        buffer and copied on the input's stream (the caller waits for `e_in`).  None without a matte."""
+        if self.matte is None:
+            return None
+        if self.matte.still is not None:
+            return self.d_matte
+        nb = nframes * self.matte.frame_bytes
+        self.h_matte[slot].numpy()[:nb] = self.matte.read(nframes).reshape(-1).view(np.uint8)
+        with torch.cuda.stream(self.s_h2d):
+            self.d_matte[slot][:nb].copy_(self.h_matte[slot][:nb], non_blocking=True)
+        typed = self.d_matte[slot][:nb] if self.matte.depth == 8 else self.d_matte[slot][:nb].view(torch.int16)
+        return typed.view(nframes, self.matte.height, self.matte.width)
+
+    def _run_stack(self, src, dst, nframes: int, matte=None) -> None:
         """One batch through the stage stack; with key frames every frame takes the strength of its number in the
-        stream, counted here across the batches."""
+        stream, counted here across the batches.  `matte`: the batch's matte on the device, or None."""
         kw = self.kw
+        if matte is not None:
+            kw = dict(kw, matte=matte)
         if self.strength_keys is not None:
             kw = dict(kw, strength=self.strength_keys(self.frames_submitted, nframes))
         self.frames_submitted += nframes
@@ -264,6 +349,7 @@ class HostPipeline:
 
     def _submit(self, slot: int, nframes: int) -> None:
         nb_in, nb_out = nframes * self.fin.frame_bytes, nframes * self.fout.frame_bytes
+        matte = self._load_matte(slot, nframes)
         with torch.cuda.stream(self.s_h2d):
             self.d_in[slot][:nb_in].copy_(self.h_in[slot][:nb_in], non_blocking=True)
             self.e_in[slot].record()
@@ -271,7 +357,7 @@ class HostPipeline:
             self.s_run.wait_event(self.e_in[slot])
             dst = self.fout.plane_views(self.d_out[slot], nframes)
             if self.stack:
-                self._run_stack(self.fin.plane_views(self.d_in[slot], nframes), dst, nframes)
+                self._run_stack(self.fin.plane_views(self.d_in[slot], nframes), dst, nframes, matte)
             elif self.lut1d:
                 self.eng.apply_yuv_lut1d(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
             elif self.chain:

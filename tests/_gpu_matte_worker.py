@@ -1,0 +1,51 @@
+"""Worker of tests/test_gpu_matte.py::test_lds_and_global_tables_give_the_same_bytes -- TEST INFRASTRUCTURE ONLY.
+
+Where the matte forms of the stack kernels read the CDL and 1D tables (LDS or global memory) is read from
+LUTR_STACK_LDS when the kernel is launched; the parent starts this file once per setting and compares what it writes to stdout byte
+for byte: the output planes of a few `apply_yuv_stack(matte=...)` calls at depths whose tables fit LDS and one that does not.  The
+placement that ran goes to stderr, one digit per call.
+
+    python tests/_gpu_matte_worker.py LUT3D.cube LUT1D.cube CDL.cc
+"""
+import sys
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+if str(ROOT) not in sys.path:
+    sys.path.insert(0, str(ROOT))
+
+
+def main(lut3d, lut1d, cc):
+    import torch
+    from lut_renderer_amd import frames
+    from lut_renderer_amd.cdl import read_cdl
+    from lut_renderer_amd.engine import LutEngine
+    out = []
+    grade = read_cdl(cc)
+    rng = np.random.default_rng(23)
+    with LutEngine(0) as eng:
+        eng.load_cube(lut3d)
+        eng.load_lut1d(lut1d, "cubic")
+        for depth, a, b, stages, strength, dm in ((8, (1, 1), "yuv420p", "lut1d,cdl,lut3d", 0.6, 8),
+                                                  (10, (1, 1), "yuv422p10le", "lut1d,cdl,lut3d", [0.25, 0.9], 10),
+                                                  (10, (1, 0), "yuv420p10le", "lut3d:trilinear,cdl", 0.37, 8),
+                                                  (16, (1, 1), "yuv420p16le", "lut1d,cdl", 0.6, 16)):
+            fs = [frames.make_yuv("natural", 136, 36, depth, *a, k=3 + i) for i in range(2)]
+            src = [np.stack([f[i] for f in fs]) for i in range(3)]
+            dev = [torch.from_numpy(p.view(np.int16) if p.dtype == np.uint16 else p).to(eng.device) for p in src]
+            m = rng.integers(0, 1 << dm, size=(2, 36, 136)).astype(np.uint8 if dm == 8 else np.uint16)
+            matte = torch.from_numpy(m if dm == 8 else m.view(np.int16)).to(eng.device)
+            name = {(1, 1): "420", (1, 0): "422", (0, 0): "444"}[a]
+            got = eng.apply_yuv_stack(dev, pix_fmt=f"yuv{name}p" + ("" if depth == 8 else f"{depth}le"), out_pix_fmt=b, stages=stages,
+                                      cdl=grade if "cdl" in stages else None, strength=strength, matte=matte, matte_depth=dm)
+            assert eng.last_kernel.startswith("k_yuv_stack_matte_vec<"), eng.last_kernel
+            out += [t.cpu().numpy().tobytes() for t in got]
+            sys.stderr.write(eng.last_kernel.split(">")[0][-1])         # the placement that ran: the parent checks the digits
+    sys.stdout.buffer.write(b"".join(out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(*sys.argv[1:4]))
