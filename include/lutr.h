@@ -971,6 +971,10 @@ int lutr_yuv_constants(const lutr_yuv_params *p, float out[32]);
  * launchers call the same function: `text` counts only as a plain positive decimal multiple of waves_per_block that is
  * not above `uncapped`; anything else returns `uncapped`. */
 int lutr_max_waves_knob(const char *text, int waves_per_block, int uncapped);
+/* Host only, for tests: the most workgroups a grid-stride launch whose own cap is `cap` gets when the environment variable
+ * LUTR_MAX_BLOCKS holds `text` (NULL = unset).  The launchers call the same function: `text` counts only as a plain positive
+ * decimal that fits 31 bits, and then gives min(cap, value); anything else returns `cap`. */
+int lutr_max_blocks_knob(const char *text, int cap);
 
 #ifdef __cplusplus
 }

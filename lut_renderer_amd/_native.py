@@ -51,7 +51,7 @@ SYMBOLS = (
     "lutr_apply_yuv_stack", "lutr_apply_yuv_stack_mix", "lutr_apply_yuv_stack_matte",
     "lutr_resize_filter", "lutr_resize_planes", "lutr_dither_mask",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
-    "lutr_max_waves_knob",
+    "lutr_max_waves_knob", "lutr_max_blocks_knob",
 )
 
 
@@ -274,6 +274,7 @@ def load() -> C.CDLL:
     lib.lutr_ctx_tile_stats.argtypes = [vp, ci, C.POINTER(C.c_uint64)]
     lib.lutr_yuv_constants.argtypes = [C.POINTER(YuvParams), C.POINTER(C.c_float)]
     lib.lutr_max_waves_knob.argtypes = [cp, ci, ci]
+    lib.lutr_max_blocks_knob.argtypes = [cp, ci]
     _lib = lib
     return lib
 
@@ -321,6 +322,12 @@ def lut1d_table(lut1d, interp1d: str, depth: int):
 def max_waves_knob(text, waves_per_block: int, uncapped: int) -> int:
     """lutr_max_waves_knob (host only): what the tile launchers make of LUTR_MAX_WAVES = `text` (None = unset)."""
     return load().lutr_max_waves_knob(None if text is None else str(text).encode(), waves_per_block, uncapped)
+
+
+def max_blocks_knob(text, cap: int) -> int:
+    """lutr_max_blocks_knob (host only): the blocks a grid-stride launch capped at `cap` may get under LUTR_MAX_BLOCKS = `text`
+    (None = unset)."""
+    return load().lutr_max_blocks_knob(None if text is None else str(text).encode(), cap)
 
 
 def resize_filter(src: int, dst: int, cs: int = 0, cosited: bool = False):

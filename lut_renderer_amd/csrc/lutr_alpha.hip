@@ -173,7 +173,8 @@ const char *launch_alpha(hipStream_t st, int variant, const AlphaArgs &A, const 
         return plane_ok(S.d, S.ds, S.dfs, da, batch, kStrideAny, false);
     };
     auto vec = [&](const AlphaArgs &S, const FrameGeom &H) -> const char * {
-        const dim3 grid(grid_for((long long)(H.w / pxt) * H.rows * H.nframes, kAlphaGridCap)), block(256);
+        const dim3 grid(stride_grid(S.kind == 0 ? "k_alpha_fill" : "k_alpha_vec", (long long)(H.w / pxt) * H.rows * H.nframes, kAlphaGridCap)),
+                        block(256);
         if (S.kind == 0) { hipLaunchKernelGGL(k_alpha_fill<true>, grid, block, 0, st, S, H); return "k_alpha_fill"; }
         switch (src * 2 + S.wout) {
         case 0:  hipLaunchKernelGGL((k_alpha_vec<0, 0>), grid, block, 0, st, S, H); return "k_alpha_vec<0,0>";
@@ -185,7 +186,8 @@ const char *launch_alpha(hipStream_t st, int variant, const AlphaArgs &A, const 
         }
     };
     auto generic = [&](const AlphaArgs &S, const FrameGeom &H) {
-        const dim3 grid(grid_for((long long)H.w * H.rows * H.nframes, kAlphaGridCap)), block(256);
+        const dim3 grid(stride_grid(S.kind == 0 ? "k_alpha_fill" : "k_alpha_generic", (long long)H.w * H.rows * H.nframes, kAlphaGridCap)),
+                        block(256);
         if (S.kind == 0) { hipLaunchKernelGGL(k_alpha_fill<false>, grid, block, 0, st, S, H); return "k_alpha_fill"; }
         hipLaunchKernelGGL(k_alpha_generic, grid, block, 0, st, S, H);
         return "k_alpha_generic";

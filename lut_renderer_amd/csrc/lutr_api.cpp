@@ -429,6 +429,11 @@ int lutr_max_waves_knob(const char *text, int waves_per_block, int uncapped)
     return capped_waves(text, waves_per_block, uncapped);
 }
 
+int lutr_max_blocks_knob(const char *text, int cap)
+{
+    return cap < 1 ? cap : (int)capped_blocks(text, (unsigned)cap);
+}
+
 int lutr_yuv_constants(const lutr_yuv_params *p, float out[32])
 {
     return export_consts("lutr_yuv_constants", p, out, [&](YuvConsts *k) { return make_yuv_consts(*p, k); });

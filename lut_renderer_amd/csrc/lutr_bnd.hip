@@ -93,7 +93,8 @@ const char *launch_yuv_bn(hipStream_t st, int variant, const LutConsts &L, const
     // runs just ahead of the generic launch it feeds; every other launch starts at column 0)
     int x0 = 0;
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
-        hipLaunchKernelGGL(k_yuv_bn_generic, dim3(block_grid(H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, K, Q, H, bn, x0,
+        hipLaunchKernelGGL(k_yuv_bn_generic, dim3(block_grid("k_yuv_bn_generic", H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, K, Q, H,
+                           bn, x0,
                            win, wout, icsx, icsy, ocsx, ocsy, mode);
         return "k_yuv_bn_generic";
     };

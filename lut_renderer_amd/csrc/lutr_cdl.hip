@@ -228,7 +228,8 @@ const char *launch_yuv_cdl(hipStream_t st, int variant, const LutConsts &L, cons
     };
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
         ran |= 2;
-        hipLaunchKernelGGL(k_yuv_cdl_generic, dim3(block_grid(H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, C, K, Q, H, win,
+        hipLaunchKernelGGL(k_yuv_cdl_generic, dim3(block_grid("k_yuv_cdl_generic", H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, C, K, Q,
+                           H, win,
                            wout, icsx, icsy, ocsx, ocsy, mode);
         return "k_yuv_cdl_generic";
     };

@@ -228,7 +228,8 @@ const char *launch_yuv_chain(hipStream_t st, int variant, const LutConsts &L, co
     };
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
         ran |= 2;
-        hipLaunchKernelGGL(k_yuv_chain_generic, dim3(block_grid(H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, L2, K, Q, H,
+        hipLaunchKernelGGL(k_yuv_chain_generic, dim3(block_grid("k_yuv_chain_generic", H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, L2,
+                           K, Q, H,
                            win, wout, icsx, icsy, ocsx, ocsy, mode, mode2);
         return "k_yuv_chain_generic";
     };

@@ -196,7 +196,8 @@ const char *launch_yuv_dither(hipStream_t st, const LutConsts &L, const YuvConst
         // a subsampling change: pass 1 by union blocks (lutr_xsub.hip); pass 2 below sizes its planes from the output
         launch_yuv_float_xsub(st, L, K, P, G, F, win, csx, csy, ocsx, ocsy, mode);
     } else {
-        hipLaunchKernelGGL(k_yuv_float, dim3(block_grid(G.w, G.h, G.nframes, csx, csy)), dim3(256), 0, st, L, K, P, G, F, win, csx, csy, mode);
+        hipLaunchKernelGGL(k_yuv_float, dim3(block_grid("k_yuv_float", G.w, G.h, G.nframes, csx, csy)), dim3(256), 0, st, L, K, P, G, F, win, csx,
+                           csy, mode);
     }
     return launch_dither_ed(st, K, P, G, F, wout, ocsx, ocsy) ? "k_yuv_float+k_dither_ed" : nullptr;
 }

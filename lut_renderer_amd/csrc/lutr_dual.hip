@@ -309,7 +309,8 @@ const char *launch_yuv_dual(hipStream_t st, int variant, const LutConsts &L, con
         return launch_yuv_dual_vec_w000(st, L, KA, KB, A, Bd, H, icsx, icsy, bcsx, bcsy, mode);
     };
     auto generic = [&](const Both &Q, const FrameGeom &H) {
-        hipLaunchKernelGGL(k_yuv_dual_generic, dim3(block_grid(H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, K1, K2, Q.P,
+        hipLaunchKernelGGL(k_yuv_dual_generic, dim3(block_grid("k_yuv_dual_generic", H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, K1,
+                           K2, Q.P,
                            Q.B, H, win, icsx, icsy, w1, csx1, csy1, w2, csx2, csy2, mode);
         return "k_yuv_dual_generic";
     };

@@ -210,14 +210,14 @@ const char *launch_rgb(hipStream_t st, int variant, const LutConsts &L, const Pl
         const long long eb = (long long)wv * (wide ? 2 : 1);
         const PlaneSet Pe = advance_planes(P, eb, eb, eb, eb);
         const char *name = launch_rgb_tile(st, L, P, Gv, depth, mode, stats, queue);
-        hipLaunchKernelGGL(k_rgb_generic, dim3(grid_for((long long)Ge.w * G.rows * G.nframes, kGridStrideCap)), dim3(256), 0, st,
+        hipLaunchKernelGGL(k_rgb_generic, dim3(stride_grid("k_rgb_generic", (long long)Ge.w * G.rows * G.nframes, kGridStrideCap)), dim3(256), 0, st,
                            L, Pe, Ge, wide, mode);
         return name;
     }
     if (!vec_ok) {
         if (variant == VAR_VEC_GLOBAL || variant == VAR_VEC_LDS) return nullptr;
         // grid-stride; enough blocks to fill 256 CUs x 8
-        hipLaunchKernelGGL(k_rgb_generic, dim3(grid_for(px, kGridStrideCap)), dim3(256), 0, st, L, P, G, wide, mode);
+        hipLaunchKernelGGL(k_rgb_generic, dim3(stride_grid("k_rgb_generic", px, kGridStrideCap)), dim3(256), 0, st, L, P, G, wide, mode);
         return "k_rgb_generic";
     }
     const dim3 grid(grid_for(px / (kVecBytes / (wide ? 2 : 1)))), block(256);
@@ -298,7 +298,7 @@ const char *launch_yuv(hipStream_t st, int variant, const LutConsts &L, const Yu
         if (const char *name = try_tile2(st, L, K, P, Gv, din, dout, lut_depth, csx, csy, mode, fast, stats, queue)) {
             const long long bsi = win ? 2 : 1, bso = wout ? 2 : 1;
             const PlaneSet Pe = advance_planes(P, wv * bsi, (wv >> csx) * bsi, wv * bso, (wv >> csx) * bso);
-            hipLaunchKernelGGL(k_yuv_generic, dim3(block_grid(Ge.w, G.rows, G.nframes, csx, csy)), dim3(256), 0, st, L, K, Pe, Ge,
+            hipLaunchKernelGGL(k_yuv_generic, dim3(block_grid("k_yuv_generic", Ge.w, G.rows, G.nframes, csx, csy)), dim3(256), 0, st, L, K, Pe, Ge,
                                win, wout, csx, csy, mode);
             return name;
         }
@@ -327,7 +327,7 @@ const char *launch_yuv(hipStream_t st, int variant, const LutConsts &L, const Yu
     }
     if (!vec_ok) {
         if (variant == VAR_VEC_GLOBAL || variant == VAR_VEC_LDS) return nullptr;
-        hipLaunchKernelGGL(k_yuv_generic, dim3(block_grid(G.w, G.rows, G.nframes, csx, csy)), dim3(256), 0, st, L, K, P, G, win,
+        hipLaunchKernelGGL(k_yuv_generic, dim3(block_grid("k_yuv_generic", G.w, G.rows, G.nframes, csx, csy)), dim3(256), 0, st, L, K, P, G, win,
                            wout, csx, csy, mode);
         return "k_yuv_generic";
     }

@@ -171,7 +171,7 @@ const char *LUTR_CAT(LUTR_CAT(launch_yuv_l1d_vec_w, LUTR_L1_WI), LUTR_L1_WO)(hip
     constexpr int PXT = vec_bytes<WI, WO>() / (WI ? 2 : 1);
     const int bh = 1 << cmax(icsy, ocsy);
     const long long units = (long long)(G.w / PXT) * (G.rows / bh) * G.nframes;
-    const dim3 grid(grid_for(units, lds ? (unsigned)device_cus() * 8u : kGridStrideCap)), block(256);
+    const dim3 grid(stride_grid("k_yuv_l1d_vec", units, lds ? (unsigned)device_cus() * 8u : kGridStrideCap)), block(256);
     const size_t lds_bytes = lds ? (size_t)3 * C.stride * sizeof(uint16_t) : 0;
 #define L1_CASE(IX, IY, OX, OY, I) \
     if (icsx == IX && icsy == IY && ocsx == OX && ocsy == OY && mode == (I)) { \
@@ -278,7 +278,8 @@ const char *launch_yuv_l1d(hipStream_t st, int variant, const LutConsts &L, cons
     };
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
         ran |= 2;
-        hipLaunchKernelGGL(k_yuv_l1d_generic, dim3(block_grid(H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, C, K, Q, H, win,
+        hipLaunchKernelGGL(k_yuv_l1d_generic, dim3(block_grid("k_yuv_l1d_generic", H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, C, K, Q,
+                           H, win,
                            wout, icsx, icsy, ocsx, ocsy, mode);
         return "k_yuv_l1d_generic";
     };
@@ -356,7 +357,7 @@ const char *launch_rgb_l1d(hipStream_t st, int variant, const L1dConsts &C, cons
     if (variant == VAR_VEC_GLOBAL && wv != G.w) return nullptr;
     if (ww > 0) {
         const bool lds = l1d_in_lds(C);
-        const unsigned grid = grid_for((long long)ww * G.rows * G.nframes, lds ? (unsigned)device_cus() * 8u : kGridStrideCap);
+        const unsigned grid = stride_grid("k_rgb_l1d", (long long)ww * G.rows * G.nframes, lds ? (unsigned)device_cus() * 8u : kGridStrideCap);
         const size_t lds_bytes = lds ? (size_t)3 * C.stride * sizeof(uint16_t) : 0;
         if (wide && lds) hipLaunchKernelGGL((k_rgb_l1d<1, true>), dim3(grid), dim3(256), lds_bytes, st, C, P, G, maxi, ww);
         else if (wide) hipLaunchKernelGGL((k_rgb_l1d<1, false>), dim3(grid), dim3(256), 0, st, C, P, G, maxi, ww);
@@ -364,7 +365,7 @@ const char *launch_rgb_l1d(hipStream_t st, int variant, const L1dConsts &C, cons
         else hipLaunchKernelGGL((k_rgb_l1d<0, false>), dim3(grid), dim3(256), 0, st, C, P, G, maxi, ww);
     }
     if (wv < G.w) {
-        const unsigned grid = grid_for((long long)(G.w - wv) * G.rows * G.nframes, kGridStrideCap);
+        const unsigned grid = stride_grid("k_rgb_l1d_generic", (long long)(G.w - wv) * G.rows * G.nframes, kGridStrideCap);
         hipLaunchKernelGGL(k_rgb_l1d_generic, dim3(grid), dim3(256), 0, st, C, P, G, maxi, wide, wv);
     }
     if (wv == G.w) return wide ? "k_rgb_l1d<1>" : "k_rgb_l1d<0>";

@@ -3,7 +3,9 @@
 #pragma once
 
 #include <climits>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <set>
 #include <utility>
@@ -78,8 +80,8 @@ inline bool vec_mode(int mode)
 }
 
 // ---------------------------------------------------------------- launch sizing
-// Blocks of 256 threads for `units` work items, at least one.  Grid-stride kernels pass kGridStrideCap: enough blocks to fill
-// 256 CUs x 8.
+// Blocks of 256 threads for `units` work items, at least one.  Grid-stride kernels go through stride_grid (below), most with
+// kGridStrideCap: enough blocks to fill 256 CUs x 8.
 constexpr unsigned kGridStrideCap = 256 * 64;
 inline unsigned grid_for(long long units, unsigned cap = 0x7fffffffu)
 {
@@ -92,11 +94,46 @@ inline unsigned grid_for(long long units, unsigned cap = 0x7fffffffu)
 // the one-thread-per-unit kernels index their units with 32 bits
 inline bool units_fit(long long units) { return units < 0x7fffffffll; }
 
-// blocks of 2^cs samples that cover n samples, and the grid of a by-block generic kernel (one thread per 2^csx x 2^csy block)
-inline long long blocks(int n, int cs) { return (n + (1 << cs) - 1) >> cs; }
-inline unsigned block_grid(int w, int rows, int nframes, int csx, int csy)
+// LUTR_MAX_BLOCKS (tests and tools only): a cap on the workgroups of every grid-stride launch, so that a frame of a few thousand
+// units runs each thread of a grid-stride kernel for several trips, the last of them partial, as a UHD frame does under the
+// launchers' own caps.  `text` is the variable's value (or null), `cap` the launch site's own cap.  Accepted only as a plain
+// positive decimal that fits a grid; the launch then gets min(cap, value) blocks.  Anything else leaves `cap`.
+inline unsigned capped_blocks(const char *text, unsigned cap)
 {
-    return grid_for(blocks(w, csx) * blocks(rows, csy) * nframes, kGridStrideCap);
+    if (!text || !*text) return cap;
+    long long v = 0;
+    for (const char *c = text; *c; c++) {
+        if (*c < '0' || *c > '9') return cap;
+        v = v * 10 + (*c - '0');
+        if (v > 0x7fffffffll) return cap;
+    }
+    return v > 0 && v < (long long)cap ? (unsigned)v : cap;
+}
+
+// The grid of a grid-stride launch (a kernel that walks `for (u = blockIdx.x * 256 + threadIdx.x; u < units; u += gridDim.x *
+// 256)`): grid_for under the site's cap and LUTR_MAX_BLOCKS.  Both variables are read once per process.  LUTR_DEBUG: one line
+// per launch, `family` names the kernel.  Never for a one-thread-per-unit kernel: a cap would drop its work.
+inline unsigned stride_grid(const char *family, long long units, unsigned cap)
+{
+    struct Env { const char *max_blocks; bool debug; };
+    static const Env env = [] {
+        static char text[32];
+        const char *e = getenv("LUTR_MAX_BLOCKS");
+        // a copy (a later setenv may move the value); a value too long for it is no valid grid either
+        if (e) snprintf(text, sizeof text, "%s", strlen(e) < sizeof text ? e : "x");
+        return Env{e ? text : nullptr, getenv("LUTR_DEBUG") != nullptr};
+    }();
+    const unsigned b = grid_for(units, capped_blocks(env.max_blocks, cap));
+    if (env.debug) fprintf(stderr, "[lutr gs] %s units %lld blocks %u\n", family, units, b);
+    return b;
+}
+
+// blocks of 2^cs samples that cover n samples, and the grid of a by-block generic kernel (one thread per 2^csx x 2^csy block,
+// for_each_block's walk)
+inline long long blocks(int n, int cs) { return (n + (1 << cs) - 1) >> cs; }
+inline unsigned block_grid(const char *family, int w, int rows, int nframes, int csx, int csy)
+{
+    return stride_grid(family, blocks(w, csx) * blocks(rows, csy) * nframes, kGridStrideCap);
 }
 
 // The launch sequence of a path that has global-gather vector kernels and a generic kernel, no LDS kernel.  vec_fits(P, G): the

@@ -139,7 +139,7 @@ const char *launch_packed(hipStream_t st, int variant, const LutConsts &L, const
     if (variant == VAR_GENERIC) vec_ok = false;
     if (!vec_ok) {
         if (variant == VAR_VEC_GLOBAL || variant == VAR_VEC_LDS) return nullptr;
-        hipLaunchKernelGGL(k_packed_generic, dim3(grid_for(px, kGridStrideCap)), dim3(256), 0, st, L, P, G, wide, nc, mode);
+        hipLaunchKernelGGL(k_packed_generic, dim3(stride_grid("k_packed_generic", px, kGridStrideCap)), dim3(256), 0, st, L, P, G, wide, nc, mode);
         return "k_packed_generic";
     }
     const dim3 grid((unsigned)((px / 4 + 255) / 256)), block(256);

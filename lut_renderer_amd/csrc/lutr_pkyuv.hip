@@ -317,7 +317,8 @@ const char *launch_yuv_packed(hipStream_t st, int variant, const LutConsts &L, c
         return launch_yuv_pk_vec_w00(st, L, K, Q, H, A, ocsy, mode);
     };
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
-        hipLaunchKernelGGL(k_yuv_pk_generic, dim3(block_grid(H.w, H.rows, H.nframes, 1, ocsy)), dim3(256), 0, st, L, K, Q, H, A, win,
+        hipLaunchKernelGGL(k_yuv_pk_generic, dim3(block_grid("k_yuv_pk_generic", H.w, H.rows, H.nframes, 1, ocsy)), dim3(256), 0, st, L, K, Q, H, A,
+                           win,
                            wout, ocsx, ocsy, mode);
         return "k_yuv_pk_generic";
     };

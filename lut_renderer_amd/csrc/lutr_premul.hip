@@ -273,7 +273,8 @@ const char *launch_yuva_premul(hipStream_t st, int variant, const LutConsts &L, 
     };
     auto generic = [&](const PremulPlanes &R, const FrameGeom &H) {
         ran |= 2;
-        hipLaunchKernelGGL(k_yuva_premul_generic, dim3(block_grid(H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, K, M, R, H,
+        hipLaunchKernelGGL(k_yuva_premul_generic, dim3(block_grid("k_yuva_premul_generic", H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L,
+                           K, M, R, H,
                            win, wout, icsx, icsy, ocsx, ocsy, mode);
         return "k_yuva_premul_generic";
     };
@@ -437,7 +438,8 @@ const char *launch_rgbaf_premul(hipStream_t st, int variant, const LutConsts &L,
     };
     auto generic = [&](const PremulPlanes &R, const FrameGeom &H) {
         ran |= 2;
-        hipLaunchKernelGGL(k_rgbaf_premul_generic, dim3(grid_for((long long)H.w * H.rows * H.nframes, kGridStrideCap)), dim3(256), 0, st,
+        hipLaunchKernelGGL(k_rgbaf_premul_generic, dim3(stride_grid("k_rgbaf_premul_generic", (long long)H.w * H.rows * H.nframes, kGridStrideCap)),
+                           dim3(256), 0, st,
                            L, Q, R, H, mode);
         return "k_rgbaf_premul_generic";
     };

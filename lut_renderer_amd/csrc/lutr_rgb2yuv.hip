@@ -201,7 +201,8 @@ __global__ __launch_bounds__(256) void k_rgb2yuv_float(LutConsts L, YuvConsts K,
 const char *launch_rgb2yuv_dither(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const RgbLayout &Y,
                                   const FrameGeom &G, const FloatPlanes &F, int dout, int ocsx, int ocsy, int mode)
 {
-    hipLaunchKernelGGL(k_rgb2yuv_float, dim3(block_grid(G.w, G.h, G.nframes, ocsx, ocsy)), dim3(256), 0, st, L, K, P, G, Y, F, ocsx, ocsy, mode);
+    hipLaunchKernelGGL(k_rgb2yuv_float, dim3(block_grid("k_rgb2yuv_float", G.w, G.h, G.nframes, ocsx, ocsy)), dim3(256), 0, st, L, K, P, G, Y, F,
+                       ocsx, ocsy, mode);
     return launch_dither_ed(st, K, P, G, F, dout > 8, ocsx, ocsy) ? "k_rgb2yuv_float+k_dither_ed" : nullptr;
 }
 
@@ -218,7 +219,8 @@ const char *launch_rgb2yuv_bn(hipStream_t st, int variant, const LutConsts &L, c
                               const RgbLayout &Y, const FrameGeom &G, const float *bn, int dout, int ocsx, int ocsy, int mode)
 {
     if (variant == VAR_VEC_GLOBAL || variant == VAR_VEC_LDS) return nullptr;
-    hipLaunchKernelGGL(k_rgb2yuv_bn_generic, dim3(block_grid(G.w, G.rows, G.nframes, ocsx, ocsy)), dim3(256), 0, st, L, K, P, G, Y, bn,
+    hipLaunchKernelGGL(k_rgb2yuv_bn_generic, dim3(block_grid("k_rgb2yuv_bn_generic", G.w, G.rows, G.nframes, ocsx, ocsy)), dim3(256), 0, st, L, K,
+                       P, G, Y, bn,
                        dout > 8, ocsx, ocsy, mode);
     return "k_rgb2yuv_bn_generic";
 }
@@ -256,7 +258,8 @@ const char *launch_rgb2yuv(hipStream_t st, int variant, const LutConsts &L, cons
         return launch_rgb2yuv_vec_w00(st, L, K, Q, Y, H, ocsx, ocsy, mode);
     };
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
-        hipLaunchKernelGGL(k_rgb2yuv_generic, dim3(block_grid(H.w, H.rows, H.nframes, ocsx, ocsy)), dim3(256), 0, st, L, K, Q, H, Y, wout, ocsx, ocsy, mode);
+        hipLaunchKernelGGL(k_rgb2yuv_generic, dim3(block_grid("k_rgb2yuv_generic", H.w, H.rows, H.nframes, ocsx, ocsy)), dim3(256), 0, st, L, K, Q,
+                           H, Y, wout, ocsx, ocsy, mode);
         return "k_rgb2yuv_generic";
     };
     // (no LDS kernel for this path; the unit is 8 luma samples wide, whole chroma blocks)

@@ -307,7 +307,8 @@ const char *launch_rgbf(hipStream_t st, int variant, const LutConsts &L, const F
         }
     };
     auto generic = [&](const PlaneSet &S, const FrameGeom &H) {
-        hipLaunchKernelGGL(k_rgbf_generic, dim3(grid_for((long long)H.w * H.rows * H.nframes, kGridStrideCap)), dim3(256), 0, st, L, Q,
+        hipLaunchKernelGGL(k_rgbf_generic, dim3(stride_grid("k_rgbf_generic", (long long)H.w * H.rows * H.nframes, kGridStrideCap)), dim3(256), 0,
+                           st, L, Q,
                            S, H, mode);
         return "k_rgbf_generic";
     };
@@ -320,7 +321,8 @@ const char *launch_rgbf(hipStream_t st, int variant, const LutConsts &L, const F
 const char *launch_rgbf2yuv_dither(hipStream_t st, const LutConsts &L, const FloatPre &Q, const YuvConsts &K, const PlaneSet &P,
                                    const FrameGeom &G, const FloatPlanes &F, int dout, int ocsx, int ocsy, int mode)
 {
-    hipLaunchKernelGGL(k_rgbf2yuv_float, dim3(block_grid(G.w, G.h, G.nframes, ocsx, ocsy)), dim3(256), 0, st, L, Q, K, P, G, F, ocsx, ocsy, mode);
+    hipLaunchKernelGGL(k_rgbf2yuv_float, dim3(block_grid("k_rgbf2yuv_float", G.w, G.h, G.nframes, ocsx, ocsy)), dim3(256), 0, st, L, Q, K, P, G, F,
+                       ocsx, ocsy, mode);
     return launch_dither_ed(st, K, P, G, F, dout > 8, ocsx, ocsy) ? "k_rgbf2yuv_float+k_dither_ed" : nullptr;
 }
 
@@ -328,7 +330,8 @@ const char *launch_rgbf2yuv_bn(hipStream_t st, int variant, const LutConsts &L, 
                                const PlaneSet &P, const FrameGeom &G, const float *bn, int dout, int ocsx, int ocsy, int mode)
 {
     if (variant == VAR_VEC_GLOBAL || variant == VAR_VEC_LDS) return nullptr;
-    hipLaunchKernelGGL(k_rgbf2yuv_bn_generic, dim3(block_grid(G.w, G.rows, G.nframes, ocsx, ocsy)), dim3(256), 0, st, L, Q, K, P, G, bn,
+    hipLaunchKernelGGL(k_rgbf2yuv_bn_generic, dim3(block_grid("k_rgbf2yuv_bn_generic", G.w, G.rows, G.nframes, ocsx, ocsy)), dim3(256), 0, st, L, Q,
+                       K, P, G, bn,
                        dout > 8, ocsx, ocsy, mode);
     return "k_rgbf2yuv_bn_generic";
 }
@@ -355,7 +358,8 @@ const char *launch_rgbf2yuv(hipStream_t st, int variant, const LutConsts &L, con
         return wout ? launch_rgbf2yuv_vec_w1(st, L, Q, K, S, H, ocsx, ocsy, mode) : launch_rgbf2yuv_vec_w0(st, L, Q, K, S, H, ocsx, ocsy, mode);
     };
     auto generic = [&](const PlaneSet &S, const FrameGeom &H) {
-        hipLaunchKernelGGL(k_rgbf2yuv_generic, dim3(block_grid(H.w, H.rows, H.nframes, ocsx, ocsy)), dim3(256), 0, st, L, Q, K, S, H, wout, ocsx, ocsy, mode);
+        hipLaunchKernelGGL(k_rgbf2yuv_generic, dim3(block_grid("k_rgbf2yuv_generic", H.w, H.rows, H.nframes, ocsx, ocsy)), dim3(256), 0, st, L, Q,
+                           K, S, H, wout, ocsx, ocsy, mode);
         return "k_rgbf2yuv_generic";
     };
     // (no LDS kernel for this path; the unit is 8 luma samples wide, whole chroma blocks)

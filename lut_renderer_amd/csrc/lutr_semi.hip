@@ -260,7 +260,8 @@ const char *launch_yuv_semi(hipStream_t st, int variant, const LutConsts &L, con
         return launch_yuv_semi_vec_w00(st, L, K, Q, H, A, csy, mode);
     };
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
-        hipLaunchKernelGGL(k_yuv_semi_generic, dim3(block_grid(H.w, H.rows, H.nframes, 1, csy)), dim3(256), 0, st, L, K, Q, H, A, win, wout, csy, mode);
+        hipLaunchKernelGGL(k_yuv_semi_generic, dim3(block_grid("k_yuv_semi_generic", H.w, H.rows, H.nframes, 1, csy)), dim3(256), 0, st, L, K, Q, H,
+                           A, win, wout, csy, mode);
         return "k_yuv_semi_generic";
     };
     // (no LDS-window kernel for semi-planar frames; the unit is 4 or 8 luma samples wide, whole chroma blocks)

@@ -392,7 +392,7 @@ const char *SK_VEC_LAUNCH_FN(hipStream_t st, const LutConsts &L, const LutConsts
     constexpr int PXT = vec_bytes<WI, WO>() / (WI ? 2 : 1);
     const int bh = 1 << cmax(icsy, ocsy);
     const long long units = (long long)(G.w / PXT) * (G.rows / bh) * G.nframes;
-    const dim3 grid(grid_for(units, lds ? (unsigned)device_cus() * 8u : kGridStrideCap)), block(256);
+    const dim3 grid(stride_grid(LUTR_STR(SK_VEC), units, lds ? (unsigned)device_cus() * 8u : kGridStrideCap)), block(256);
     const size_t lds_bytes = lds ? (size_t)(S.lds_cdl_words + S.lds_l1d_words) * sizeof(uint32_t) : 0;
 #define SK_CASE(IX, IY, OX, OY, T) \
     if (icsx == IX && icsy == IY && ocsx == OX && ocsy == OY && tri == (T != 0)) { \
@@ -578,13 +578,16 @@ const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, co
             // the tail of a column split: the matte moves right with the source's luma plane
             MatteConsts B = *A;
             B.data += (Q.s[0] - P.s[0]) / bsi * (A->wide ? 2 : 1);
-            return launch_yuv_stack_matte_generic(st, block_grid(H.w, H.rows, H.nframes, csx, csy), L, L2, S, K, Q, H, *M, B, win, wout,
+            return launch_yuv_stack_matte_generic(st, block_grid("k_yuv_stack_matte_generic", H.w, H.rows, H.nframes, csx, csy), L, L2, S, K, Q, H,
+                                                  *M, B, win, wout,
                                                   icsx, icsy, ocsx, ocsy);
         }
         if (M)
-            return launch_yuv_stack_mix_generic(st, block_grid(H.w, H.rows, H.nframes, csx, csy), L, L2, S, K, Q, H, *M, win, wout, icsx,
+            return launch_yuv_stack_mix_generic(st, block_grid("k_yuv_stack_mix_generic", H.w, H.rows, H.nframes, csx, csy), L, L2, S, K, Q, H, *M,
+                                                win, wout, icsx,
                                                 icsy, ocsx, ocsy);
-        hipLaunchKernelGGL(k_yuv_stack_generic, dim3(block_grid(H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, L2, S, K, Q, H,
+        hipLaunchKernelGGL(k_yuv_stack_generic, dim3(block_grid("k_yuv_stack_generic", H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, L2,
+                           S, K, Q, H,
                            win, wout, icsx, icsy, ocsx, ocsy);
         return "k_yuv_stack_generic";
     };

@@ -328,7 +328,8 @@ const char *launch_yuv_v210(hipStream_t st, int variant, const LutConsts &L, con
     };
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
         const long long units = ((long long)H.w + 5) / 6 * blocks(H.rows, ocsy) * H.nframes;
-        hipLaunchKernelGGL(k_yuv_v210_generic, dim3(grid_for(units, kGridStrideCap)), dim3(256), 0, st, L, K, Q, H, A, wp_in, wp_out,
+        hipLaunchKernelGGL(k_yuv_v210_generic, dim3(stride_grid("k_yuv_v210_generic", units, kGridStrideCap)), dim3(256), 0, st, L, K, Q, H, A,
+                           wp_in, wp_out,
                            ocsx, ocsy, mode);
         return "k_yuv_v210_generic";
     };

@@ -78,7 +78,8 @@ __global__ __launch_bounds__(256) void k_yuv_float_xsub(LutConsts L, YuvConsts K
 void launch_yuv_float_xsub(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
                            const FloatPlanes &F, int win, int icsx, int icsy, int ocsx, int ocsy, int mode)
 {
-    hipLaunchKernelGGL(k_yuv_float_xsub, dim3(block_grid(G.w, G.h, G.nframes, cmax(icsx, ocsx), cmax(icsy, ocsy))), dim3(256), 0, st,
+    hipLaunchKernelGGL(k_yuv_float_xsub, dim3(block_grid("k_yuv_float_xsub", G.w, G.h, G.nframes, cmax(icsx, ocsx), cmax(icsy, ocsy))), dim3(256),
+                       0, st,
                        L, K, P, G, F, win, icsx, icsy, ocsx, ocsy, mode);
 }
 
@@ -111,7 +112,8 @@ const char *launch_yuv_xsub(hipStream_t st, int variant, const LutConsts &L, con
         return launch_yuv_xsub_vec_w00(st, L, K, Q, H, icsx, icsy, ocsx, ocsy, mode);
     };
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
-        hipLaunchKernelGGL(k_yuv_xsub_generic, dim3(block_grid(H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, K, Q, H, win,
+        hipLaunchKernelGGL(k_yuv_xsub_generic, dim3(block_grid("k_yuv_xsub_generic", H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, K, Q,
+                           H, win,
                            wout, icsx, icsy, ocsx, ocsy, mode);
         return "k_yuv_xsub_generic";
     };
