@@ -16,11 +16,21 @@ namespace lutr {
 
 #ifdef LUTR_BN_WI
 // ================================================================= vector kernel, global gather
-// k_yuv_xsub_vec's body with the offsets (yuv_xsub_vec_body, lutr_device.h)
+// k_yuv_xsub_vec with the offsets in the output stage (union_vec_unit's BN, lutr_device.h).  bn_vec takes the constants by value:
+// handed on from the kernel's own arguments, hipcc schedules a dozen instances across a wave boundary.
+template <class U, int INTERP>
+__device__ __forceinline__ void bn_vec(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, const float *__restrict__ bn)
+{
+    const GFetch f(L);
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= U::count(G)) return;
+    auto px = [&](const Rgb &q) __attribute__((always_inline)) { return lut3d_px<INTERP>(L, f, q.r, q.g, q.b); };
+    union_vec_unit<U, true>(u, K, P, G, px, bn);
+}
 template <int WIN, int WOUT, int ICSX, int ICSY, int OCSX, int OCSY, int INTERP>
 __global__ __launch_bounds__(256) void k_yuv_bn_vec(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, const float *__restrict__ bn)
 {
-    yuv_xsub_vec_body<WIN, WOUT, ICSX, ICSY, OCSX, OCSY, INTERP, true>(L, K, P, G, bn);
+    bn_vec<UnionUnit<WIN, WOUT, ICSX, ICSY, OCSX, OCSY>, INTERP>(L, K, P, G, bn);
 }
 
 // The vector kernels of this translation unit's container mix; the layout checks are the caller's (launch_yuv_bn).
@@ -29,19 +39,14 @@ const char *LUTR_CAT(LUTR_CAT(launch_yuv_bn_vec_w, LUTR_BN_WI), LUTR_BN_WO)(hipS
                                                                              int icsx, int icsy, int ocsx, int ocsy, int mode)
 {
     constexpr int WI = LUTR_BN_WI, WO = LUTR_BN_WO;
-    constexpr int PXT = vec_bytes<WI, WO>() / (WI ? 2 : 1);
-    const int bh = 1 << cmax(icsy, ocsy);
-    const long long units = (long long)(G.w / PXT) * (G.rows / bh) * G.nframes;
-    const dim3 grid((unsigned)((units + 255) / 256)), block(256);
+    const dim3 grid((unsigned)((union_units<WI, WO>(G, icsy, ocsy) + 255) / 256)), block(256);
 #define BN_CASE(IX, IY, OX, OY, I) \
     if (icsx == IX && icsy == IY && ocsx == OX && ocsy == OY && mode == I) { \
         hipLaunchKernelGGL((k_yuv_bn_vec<WI, WO, IX, IY, OX, OY, I>), grid, block, 0, st, L, K, P, G, bn); \
         return "k_yuv_bn_vec<" LUTR_STR(LUTR_BN_WI) "," LUTR_STR(LUTR_BN_WO) "," #IX "," #IY "," #OX "," #OY "," #I ">"; \
     }
 #define BN_PAIR(IX, IY, OX, OY) BN_CASE(IX, IY, OX, OY, 0) BN_CASE(IX, IY, OX, OY, 1) BN_CASE(IX, IY, OX, OY, 2)
-#define BN_FROM(IX, IY) BN_PAIR(IX, IY, 1, 1) BN_PAIR(IX, IY, 1, 0) BN_PAIR(IX, IY, 0, 0)
-    BN_FROM(1, 1) BN_FROM(1, 0) BN_FROM(0, 0)
-#undef BN_FROM
+    LUTR_UNION_PAIRS(BN_PAIR)
 #undef BN_PAIR
 #undef BN_CASE
     return nullptr;
@@ -57,7 +62,9 @@ __global__ __launch_bounds__(256) void k_yuv_bn_generic(LutConsts L, YuvConsts K
     const GFetch f(L);
     DitherSink sink{K, P, wout, bn, x0, x0 >> ocsx};
     for_each_block(G, cmax(icsx, ocsx), cmax(icsy, ocsy), false, [&](long long fr, int ux, int uy) {
-        xsub_union_block(L, f, K, P, G, fr, ux, uy, win, icsx, icsy, ocsx, ocsy, mode, sink);
+        xsub_union_block(K, P, G, fr, ux, uy, win, icsx, icsy, ocsx, ocsy, sink, [&](long long, int, int, const Rgb &q) {
+            return lut3d_px_rt(mode, L, f, q.r, q.g, q.b);
+        });
     });
 }
 
@@ -65,43 +72,20 @@ __global__ __launch_bounds__(256) void k_yuv_bn_generic(LutConsts L, YuvConsts K
 const char *launch_yuv_bn(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G,
                           const float *bn, int din, int dout, int icsx, int icsy, int ocsx, int ocsy, int mode)
 {
-    const int win = din > 8, wout = dout > 8;
-    const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy), bh = 1 << csy;
-    // k_yuv_xsub_vec's unit and conditions: 8 bytes of luma per row (16 for a 16-bit source written as 8 bit); 8 -> 16 bit has none
-    const bool mix_ok = win == wout || (win && !wout);
-    const int pxt = (win && !wout) ? 8 : (win ? 4 : 8);
-    const long long bsi = win ? 2 : 1, bso = wout ? 2 : 1;
-    const bool batch = G.nframes > 1;
-    auto vec_fits = [&](const PlaneSet &Q, const FrameGeom &H) {
-        if (!mix_ok || !vec_mode(mode)) return false;
-        if (H.w % pxt || H.row0 % bh || H.rows % bh) return false;
-        if (!units_fit((long long)(H.w / pxt) * (H.rows / bh) * H.nframes)) return false;
-        if (!plane_ok(Q.s[0], Q.ss[0], Q.sfs[0], pxt * bsi, batch, kStrideAny, false) || !plane_ok(Q.d[0], Q.ds[0], Q.dfs[0], pxt * bso, batch, kStrideAny, false))
-            return false;
-        for (int c = 1; c < 3; c++)
-            if (!plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], (pxt >> icsx) * bsi, batch, kStrideAny, false) ||
-                !plane_ok(Q.d[c], Q.ds[c], Q.dfs[c], (pxt >> ocsx) * bso, batch, kStrideAny, false))
-                return false;
-        return true;
-    };
+    const UnionLaunch U(G, din, dout, icsx, icsy, ocsx, ocsy);
     auto vec = [&](const PlaneSet &Q, const FrameGeom &H) -> const char * {
-        if (win && wout) return launch_yuv_bn_vec_w11(st, L, K, Q, H, bn, icsx, icsy, ocsx, ocsy, mode);
-        if (win) return launch_yuv_bn_vec_w10(st, L, K, Q, H, bn, icsx, icsy, ocsx, ocsy, mode);
+        if (U.win && U.wout) return launch_yuv_bn_vec_w11(st, L, K, Q, H, bn, icsx, icsy, ocsx, ocsy, mode);
+        if (U.win) return launch_yuv_bn_vec_w10(st, L, K, Q, H, bn, icsx, icsy, ocsx, ocsy, mode);
         return launch_yuv_bn_vec_w00(st, L, K, Q, H, bn, icsx, icsy, ocsx, ocsy, mode);
     };
-    // the pattern is anchored to the frame: the tail of a column split tells the generic kernel where its planes begin (tail(wv)
-    // runs just ahead of the generic launch it feeds; every other launch starts at column 0)
-    int x0 = 0;
-    auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
-        hipLaunchKernelGGL(k_yuv_bn_generic, dim3(block_grid("k_yuv_bn_generic", H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, K, Q, H,
-                           bn, x0,
-                           win, wout, icsx, icsy, ocsx, ocsy, mode);
+    // the pattern is anchored to the frame: the generic kernel is told where its planes begin
+    auto generic = [&](const PlaneSet &Q, const FrameGeom &H, int x0) {
+        hipLaunchKernelGGL(k_yuv_bn_generic, dim3(U.generic_grid("k_yuv_bn_generic", H)), dim3(256), 0, st, L, K, Q, H, bn, x0, U.win,
+                           U.wout, icsx, icsy, ocsx, ocsy, mode);
         return "k_yuv_bn_generic";
     };
-    return launch_vec_or_generic(variant, P, G, pxt, vec_fits, vec, generic, [&](int wv) {
-        x0 = wv;
-        return advance_planes(P, wv * bsi, (wv >> icsx) * bsi, wv * bso, (wv >> ocsx) * bso);
-    });
+    // k_yuv_xsub_vec's unit and conditions
+    return launch_union(variant, P, G, U, vec_mode(mode), vec, generic);
 }
 #endif  // LUTR_BN_WI
 

@@ -1,7 +1,8 @@
 // lutr_device.h -- device-side pieces shared by the gfx950 gather kernels (lutr_kernels.hip, lutr_packed.hip, lutr_sited.hip,
 // lutr_dither.hip, lutr_xsub.hip, lutr_bnd.hip, lutr_rgb2yuv.hip, lutr_rgbf.hip, lutr_semi.hip): the lut3d per-pixel restatement (SURVEY.md
 // Appendix A.3-A.5), the YUV contract (DESIGN.md "YUV contract"), little sample/word accessors, the block walk, block
-// body and output sinks of the by-block generic kernels, and the vector kernels' unit size.
+// body and output sinks of the by-block generic kernels, the vector kernels' unit size, and the unit, vector body and
+// generic walk of the paths that work by union blocks (UnionUnit, union_vec_unit, xsub_union_block).
 //
 // Everything here rounds exactly like FFmpeg's scalar C (-ffp-contract=off; fused
 // multiply-adds only where written as __builtin_fmaf).
@@ -493,15 +494,15 @@ __device__ __forceinline__ void yuv_block(const LutConsts &L, const GFetch &f, c
     sink.chroma(fr, cx, cy, rs, gs, bs);
 }
 
-// One union block of a pass that changes the chroma subsampling (k_yuv_xsub_generic, k_yuv_float_xsub,
-// k_yuv_bn_generic).  The block is walked one OUTPUT
+// One union block of a pass that works by union blocks (the generic kernels of lutr_xsub.hip, lutr_bnd.hip,
+// lutr_chain.hip, lutr_cdl.hip, lutr_l1d.hip and lutr_stack.hip).  The block is walked one OUTPUT
 // chroma block at a time (its sum is then one set of three accumulators); every pixel reads the input chroma sample of its
-// own input block.  A pixel outside the frame is the edge pixel again (its luma and its chroma), so a partial output block
+// own input block and goes through px(fr, x, y, q) -> o, the family's stages on the codes q behind the YUV -> RGB stage.  A
+// pixel outside the frame is the edge pixel again (its luma, its chroma and the (x, y) px sees), so a partial output block
 // sums the edge column / row twice, like np.pad(mode="edge"); only pixels and chroma samples inside the planes are written.
-template <class Sink>
-__device__ __forceinline__ void xsub_union_block(const LutConsts &L, const GFetch &f, const YuvConsts &K, const PlaneSet &P,
-                                                 const FrameGeom &G, long long fr, int ux, int uy, int win, int icsx, int icsy,
-                                                 int ocsx, int ocsy, int mode, Sink &sink)
+template <class Sink, class Px>
+__device__ __forceinline__ void xsub_union_block(const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, long long fr, int ux,
+                                                 int uy, int win, int icsx, int icsy, int ocsx, int ocsy, Sink &sink, Px px)
 {
     const int bw = 1 << cmax(icsx, ocsx), bh = 1 << cmax(icsy, ocsy), obw = 1 << ocsx, obh = 1 << ocsy;
     const int cwo = (G.w + obw - 1) >> ocsx, cho = (G.h + obh - 1) >> ocsy;
@@ -517,8 +518,7 @@ __device__ __forceinline__ void xsub_union_block(const LutConsts &L, const GFetc
                     const float cbv = ld_sample(src_row(P, 1, fr, y >> icsy), x >> icsx, win);
                     const float crv = ld_sample(src_row(P, 2, fr, y >> icsy), x >> icsx, win);
                     const float yv = ld_sample(src_row(P, 0, fr, y), x, win);
-                    const Rgb q = yuv_to_rgb(K, yv, chroma_terms(K, cbv, crv));
-                    const Rgb o = lut3d_px_rt(mode, L, f, q.r, q.g, q.b);
+                    const Rgb o = px(fr, x, y, yuv_to_rgb(K, yv, chroma_terms(K, cbv, crv)));
                     rs += o.r; gs += o.g; bs += o.b;
                     if (yy < G.h && xx < G.w) sink.luma(fr, x, y, o);
                 }
@@ -552,7 +552,7 @@ constexpr int kVecBytes = 8;
 template <int WIN, int WOUT> constexpr int vec_bytes() { return (WIN && !WOUT) ? 16 : kVecBytes; }
 
 
-// ---------------------------------------------------------------- the vector body of a subsampling change (3.8) and of blue-noise dither (3.15)
+// ---------------------------------------------------------------- the vector body of every pass that works by union blocks (3.8)
 // N offsets of one table row for the samples x .. x + N - 1 of a plane (x a multiple of min(N, 4); ox a multiple of 8): aligned
 // 16-byte (8-byte for N = 2) loads, each inside one row of the table.
 template <int N>
@@ -571,37 +571,63 @@ __device__ __forceinline__ void ld_bn(float *d, const float *__restrict__ row, i
     }
 }
 
-// k_yuv_vec's structure (lutr_kernels.hip): whole-word loads and stores, VB bytes of luma per thread and row, BH luma rows per
-// thread, lattice taps gathered from L1/L2.  The thread's input chroma rows (BH >> ICSY) and output chroma rows (BH >> OCSY)
-// are separate arrays; the thread walks its union blocks one after the other.  (Frame written out: see k_yuv_vec.)  The body of
-// k_yuv_xsub_vec (lutr_xsub.hip, BN = false: bn is not read) and of k_yuv_bn_vec (lutr_bnd.hip, BN = true: the offsets of the
-// thread's output samples are loaded beside its source words, PXT floats per luma row, PXT >> OCSX per output chroma row and
-// plane; the table, 16 KB, stays in L1 / L2).
-template <int WIN, int WOUT, int ICSX, int ICSY, int OCSX, int OCSY, int INTERP, bool BN>
-__device__ __forceinline__ void yuv_xsub_vec_body(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G,
-                                                   const float *__restrict__ bn)
-{
-    constexpr int VB = vec_bytes<WIN, WOUT>();
-    constexpr int PXT = VB / (WIN ? 2 : 1);                       // luma samples per thread per row
-    constexpr int YWI = VB / 4, YWO = PXT * (WOUT ? 2 : 1) / 4;   // luma words per thread per row, in / out
-    constexpr int CSX = cmax(ICSX, OCSX), CSY = cmax(ICSY, OCSY);
-    constexpr int BW = 1 << CSX, BH = 1 << CSY;                   // the union block
-    constexpr int NB = PXT / BW;                                  // union blocks per thread
-    constexpr int IRH = BH >> ICSY, ORH = BH >> OCSY;             // chroma rows per thread, in / out
-    constexpr int IBX = BW >> ICSX, OBX = BW >> OCSX;             // chroma samples per union block and row, in / out
-    constexpr int CWI = (PXT >> ICSX) * (WIN ? 2 : 1) / 4, CWO = (PXT >> OCSX) * (WOUT ? 2 : 1) / 4;
-    constexpr int CPX = PXT >> OCSX;                              // output chroma samples per thread per row
+// One unit of a vector kernel that works by union blocks: the thread's share of a frame, VB bytes of luma per row
+// (PXT samples), BH luma rows, NB union blocks side by side.  The input chroma rows (IRH) and output chroma rows (ORH) of the
+// unit are separate word arrays.
+template <int WIN, int WOUT, int ICSX, int ICSY, int OCSX, int OCSY>
+struct UnionUnit {
+    static constexpr int kWin = WIN, kWout = WOUT, kIcsx = ICSX, kIcsy = ICSY, kOcsx = OCSX, kOcsy = OCSY;
+    static constexpr int VB = vec_bytes<WIN, WOUT>();
+    static constexpr int PXT = VB / (WIN ? 2 : 1);                       // luma samples per thread per row
+    static constexpr int YWI = VB / 4, YWO = PXT * (WOUT ? 2 : 1) / 4;   // luma words per thread per row, in / out
+    static constexpr int CSX = cmax(ICSX, OCSX), CSY = cmax(ICSY, OCSY);
+    static constexpr int BW = 1 << CSX, BH = 1 << CSY;                   // the union block
+    static constexpr int NB = PXT / BW;                                  // union blocks per thread
+    static constexpr int IRH = BH >> ICSY, ORH = BH >> OCSY;             // chroma rows per thread, in / out
+    static constexpr int IBX = BW >> ICSX, OBX = BW >> OCSX;             // chroma samples per union block and row, in / out
+    static constexpr int CWI = (PXT >> ICSX) * (WIN ? 2 : 1) / 4, CWO = (PXT >> OCSX) * (WOUT ? 2 : 1) / 4;
+    static constexpr int CPX = PXT >> OCSX;                              // output chroma samples per thread per row
     static_assert(NB >= 1 && CWI >= 1 && CWO >= 1 && YWO >= 1, "a thread must own whole words");
-    const GFetch f(L);
+    // the units of a launch: what a one-shot kernel compares its thread against and a grid-stride kernel walks up to
+    static __device__ __forceinline__ unsigned count(const FrameGeom &G)
+    {
+        return ((unsigned)G.w / PXT) * ((unsigned)G.rows >> CSY) * (unsigned)G.nframes;
+    }
+};
+
+// the same count on the host, for the launchers of one container mix (the layout checks are their callers')
+template <int WI, int WO>
+inline long long union_units(const FrameGeom &G, int icsy, int ocsy)
+{
+    constexpr int PXT = vec_bytes<WI, WO>() / (WI ? 2 : 1);
+    return (long long)(G.w / PXT) * (G.rows >> cmax(icsy, ocsy)) * G.nframes;
+}
+
+// the nine pairs of chroma layouts (ICSX, ICSY, OCSX, OCSY) these kernels are instantiated for
+#define LUTR_UNION_PAIRS(X) \
+    X(1, 1, 1, 1) X(1, 1, 1, 0) X(1, 1, 0, 0) \
+    X(1, 0, 1, 1) X(1, 0, 1, 0) X(1, 0, 0, 0) \
+    X(0, 0, 1, 1) X(0, 0, 1, 0) X(0, 0, 0, 0)
+
+// Unit u of a launch, whole: k_yuv_vec's structure (lutr_kernels.hip) -- whole-word loads and stores, lattice taps gathered from
+// L1/L2 -- for every pair of layouts; the thread walks its union blocks one after the other.  px(q) -> o: the family's stages on
+// the codes q of one pixel behind the YUV -> RGB stage.  The body of k_yuv_xsub_vec, k_yuv_bn_vec, k_yuv_chain_vec and
+// k_yuv_cdl_vec; the kernel keeps how units are walked.  (k_yuv_l1d_vec and k_yuv_stack*_vec hold copies of it: DESIGN.md 3.8.)  BN
+// (3.15): the offsets of the thread's output samples are loaded beside its source words, PXT floats per luma row, PXT >> OCSX
+// per output chroma row and plane (the table, 16 KB, stays in L1 / L2); otherwise bn is not read.
+template <class U, bool BN = false, class Px>
+__device__ __forceinline__ void union_vec_unit(unsigned u, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, Px px,
+                                               const float *__restrict__ bn = nullptr)
+{
+    constexpr int WIN = U::kWin, WOUT = U::kWout, ICSX = U::kIcsx, ICSY = U::kIcsy, OCSX = U::kOcsx, OCSY = U::kOcsy;
+    constexpr int PXT = U::PXT, YWI = U::YWI, YWO = U::YWO, BW = U::BW, BH = U::BH, IRH = U::IRH, ORH = U::ORH, IBX = U::IBX,
+                  OBX = U::OBX, CWI = U::CWI, CWO = U::CWO, CPX = U::CPX;
     const unsigned uw = (unsigned)G.w / PXT;
-    const unsigned ub = (unsigned)G.rows >> CSY;
-    const unsigned total = uw * ub * (unsigned)G.nframes;
-    const unsigned u = blockIdx.x * 256u + threadIdx.x;
-    if (u >= total) return;
+    const unsigned ub = (unsigned)G.rows >> U::CSY;
     const unsigned xu = u % uw, t = u / uw;
-    const int y0 = ((G.row0 >> CSY) + (int)(t % ub)) * BH;        // first luma row of the thread
+    const int y0 = ((G.row0 >> U::CSY) + (int)(t % ub)) * BH;     // first luma row of the thread
     const long long fr = t / ub;
-    const long long xi = (long long)xu * VB, xo = (long long)xu * (YWO * 4), cxi = (long long)xu * (CWI * 4),
+    const long long xi = (long long)xu * U::VB, xo = (long long)xu * (YWO * 4), cxi = (long long)xu * (CWI * 4),
                     cxo = (long long)xu * (CWO * 4);
 
     uint32_t yw[BH][YWI], cbw[IRH][CWI], crw[IRH][CWI];
@@ -632,7 +658,7 @@ __device__ __forceinline__ void yuv_xsub_vec_body(LutConsts L, YuvConsts K, Plan
     }
 
 #pragma unroll
-    for (int j = 0; j < NB; j++) {
+    for (int j = 0; j < U::NB; j++) {
         Chroma c[IRH][IBX];
 #pragma unroll
         for (int iy = 0; iy < IRH; iy++)
@@ -649,8 +675,7 @@ __device__ __forceinline__ void yuv_xsub_vec_body(LutConsts L, YuvConsts K, Plan
 #pragma unroll
             for (int dx = 0; dx < BW; dx++) {
                 const int i = j * BW + dx;
-                const Rgb q = yuv_to_rgb(K, word_sample<WIN>(yw[dy], i), c[dy >> ICSY][dx >> ICSX]);
-                const Rgb o = lut3d_px<INTERP>(L, f, q.r, q.g, q.b);
+                const Rgb o = px(yuv_to_rgb(K, word_sample<WIN>(yw[dy], i), c[dy >> ICSY][dx >> ICSX]));
                 rs[dy >> OCSY][dx >> OCSX] += o.r; gs[dy >> OCSY][dx >> OCSX] += o.g; bs[dy >> OCSY][dx >> OCSX] += o.b;
                 if constexpr (BN) word_put<WOUT>(yo[dy], i, rgb_to_y(K, o, dy_[dy][i]));
                 else word_put<WOUT>(yo[dy], i, rgb_to_y(K, o));

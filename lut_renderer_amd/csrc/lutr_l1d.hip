@@ -13,8 +13,6 @@
 // One source, two kinds of translation unit (Makefile MIX_RULE):
 //   without LUTR_L1_WI   the generic kernel, the planar RGB kernels and the launchers
 //   LUTR_L1_WI / _WO     the vector kernels of one container mix (8 -> 8, 16 -> 16, 16 -> 8): 9 layout pairs x 4 modes x 2 placements
-#include <string>
-
 #include "lutr_device.h"
 #include "lutr_launch.h"
 
@@ -49,7 +47,8 @@ __device__ __forceinline__ Rgb l1d_px(const L1dConsts &C, const Rgb &q)
     return t;
 }
 
-// k_yuv_cdl_vec's structure (lutr_cdl.hip) with the uint16 lookup in place of the float table and the saturation mix, inside a
+// union_vec_unit's structure (lutr_device.h), kept as this family's own copy: through the shared body a dozen instances lose a wave
+// (DESIGN.md 3.8).  The uint16 lookup sits in front of the lattice, inside a
 // grid-stride walk over the units: no thread leaves before the barrier behind the staging.
 template <int WIN, int WOUT, int ICSX, int ICSY, int OCSX, int OCSY, int INTERP, bool LDS>
 __global__ __launch_bounds__(256) void k_yuv_l1d_vec(LutConsts L, L1dConsts C, YuvConsts K, PlaneSet P, FrameGeom G)
@@ -168,10 +167,7 @@ const char *LUTR_CAT(LUTR_CAT(launch_yuv_l1d_vec_w, LUTR_L1_WI), LUTR_L1_WO)(hip
                                                                               int ocsy, int mode, bool lds)
 {
     constexpr int WI = LUTR_L1_WI, WO = LUTR_L1_WO;
-    constexpr int PXT = vec_bytes<WI, WO>() / (WI ? 2 : 1);
-    const int bh = 1 << cmax(icsy, ocsy);
-    const long long units = (long long)(G.w / PXT) * (G.rows / bh) * G.nframes;
-    const dim3 grid(stride_grid("k_yuv_l1d_vec", units, lds ? (unsigned)device_cus() * 8u : kGridStrideCap)), block(256);
+    const dim3 grid(stride_grid("k_yuv_l1d_vec", union_units<WI, WO>(G, icsy, ocsy), lds ? (unsigned)device_cus() * 8u : kGridStrideCap)), block(256);
     const size_t lds_bytes = lds ? (size_t)3 * C.stride * sizeof(uint16_t) : 0;
 #define L1_CASE(IX, IY, OX, OY, I) \
     if (icsx == IX && icsy == IY && ocsx == OX && ocsy == OY && mode == (I)) { \
@@ -180,9 +176,7 @@ const char *LUTR_CAT(LUTR_CAT(launch_yuv_l1d_vec_w, LUTR_L1_WI), LUTR_L1_WO)(hip
         return "k_yuv_l1d_vec<" LUTR_STR(LUTR_L1_WI) "," LUTR_STR(LUTR_L1_WO) "," #IX "," #IY "," #OX "," #OY "," #I ">"; \
     }
 #define L1_PAIR(IX, IY, OX, OY) L1_CASE(IX, IY, OX, OY, -1) L1_CASE(IX, IY, OX, OY, 0) L1_CASE(IX, IY, OX, OY, 1) L1_CASE(IX, IY, OX, OY, 2)
-    L1_PAIR(1, 1, 1, 1) L1_PAIR(1, 1, 1, 0) L1_PAIR(1, 1, 0, 0)
-    L1_PAIR(1, 0, 1, 1) L1_PAIR(1, 0, 1, 0) L1_PAIR(1, 0, 0, 0)
-    L1_PAIR(0, 0, 1, 1) L1_PAIR(0, 0, 1, 0) L1_PAIR(0, 0, 0, 0)
+    LUTR_UNION_PAIRS(L1_PAIR)
 #undef L1_PAIR
 #undef L1_CASE
     return nullptr;
@@ -190,44 +184,22 @@ const char *LUTR_CAT(LUTR_CAT(launch_yuv_l1d_vec_w, LUTR_L1_WI), LUTR_L1_WO)(hip
 
 #else  // !LUTR_L1_WI
 // ================================================================= generic kernel
-// One thread per union block; any depth, stride or alignment, odd sizes, all five modes and none.  k_yuv_cdl_generic's walk with
-// the table lookup in front of the lattice (read from global memory): a pixel outside the frame is the edge pixel again, only
-// pixels and chroma samples inside the planes are written.
+// One thread per union block; any depth, stride or alignment, odd sizes, all five modes and none.  xsub_union_block's walk
+// (lutr_device.h) with the table lookup in front of the lattice (read from global memory).
 __global__ __launch_bounds__(256) void k_yuv_l1d_generic(LutConsts L, L1dConsts C, YuvConsts K, PlaneSet P, FrameGeom G, int win,
                                                          int wout, int icsx, int icsy, int ocsx, int ocsy, int mode)
 {
     const GFetch f(L);
     PlaneSink sink{K, P, wout};
-    const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy);
-    const int bw = 1 << csx, bh = 1 << csy, obw = 1 << ocsx, obh = 1 << ocsy;
-    const int cwo = (G.w + obw - 1) >> ocsx, cho = (G.h + obh - 1) >> ocsy;
-    for_each_block(G, csx, csy, false, [&](long long fr, int ux, int uy) {
-        for (int oy = 0; oy < bh; oy += obh) {
-            for (int ox = 0; ox < bw; ox += obw) {
-                float rs = 0.f, gs = 0.f, bs = 0.f;
-                for (int dy = 0; dy < obh; dy++) {
-                    const int yy = uy * bh + oy + dy;
-                    const int y = yy < G.h ? yy : G.h - 1;
-                    for (int dx = 0; dx < obw; dx++) {
-                        const int xx = ux * bw + ox + dx;
-                        const int x = xx < G.w ? xx : G.w - 1;
-                        const float cbv = ld_sample(src_row(P, 1, fr, y >> icsy), x >> icsx, win);
-                        const float crv = ld_sample(src_row(P, 2, fr, y >> icsy), x >> icsx, win);
-                        const float yv = ld_sample(src_row(P, 0, fr, y), x, win);
-                        const Rgb q = yuv_to_rgb(K, yv, chroma_terms(K, cbv, crv));
-                        Rgb o;
-                        o.r = (float)C.tab[(int)q.r];
-                        o.g = (float)C.tab[C.stride + (int)q.g];
-                        o.b = (float)C.tab[2 * C.stride + (int)q.b];
-                        if (mode != LUTR_INTERP_NONE) o = lut3d_px_rt(mode, L, f, o.r, o.g, o.b);
-                        rs += o.r; gs += o.g; bs += o.b;
-                        if (yy < G.h && xx < G.w) sink.luma(fr, x, y, o);
-                    }
-                }
-                const int ocx = (ux * bw + ox) >> ocsx, ocy = (uy * bh + oy) >> ocsy;
-                if (ocx < cwo && ocy < cho) sink.chroma(fr, ocx, ocy, rs, gs, bs);
-            }
-        }
+    for_each_block(G, cmax(icsx, ocsx), cmax(icsy, ocsy), false, [&](long long fr, int ux, int uy) {
+        xsub_union_block(K, P, G, fr, ux, uy, win, icsx, icsy, ocsx, ocsy, sink, [&](long long, int, int, const Rgb &q) {
+            Rgb o;
+            o.r = (float)C.tab[(int)q.r];
+            o.g = (float)C.tab[C.stride + (int)q.g];
+            o.b = (float)C.tab[2 * C.stride + (int)q.b];
+            if (mode != LUTR_INTERP_NONE) o = lut3d_px_rt(mode, L, f, o.r, o.g, o.b);
+            return o;
+        });
     });
 }
 
@@ -249,48 +221,19 @@ static bool l1d_in_lds(const L1dConsts &C)
 const char *launch_yuv_l1d(hipStream_t st, int variant, const LutConsts &L, const L1dConsts &C, const YuvConsts &K, const PlaneSet &P,
                            const FrameGeom &G, int din, int dout, int icsx, int icsy, int ocsx, int ocsy, int mode)
 {
-    const int win = din > 8, wout = dout > 8;
-    const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy), bh = 1 << csy;
-    // the vector kernels' unit: 8 bytes of luma per row (16 for a 16-bit source written as 8 bit); 8 -> 16 bit has none
-    const bool mix_ok = win == wout || (win && !wout);
-    const int pxt = (win && !wout) ? 8 : (win ? 4 : 8);
-    const long long bsi = win ? 2 : 1, bso = wout ? 2 : 1;
-    const bool batch = G.nframes > 1;
+    const UnionLaunch U(G, din, dout, icsx, icsy, ocsx, ocsy);
     const bool lds = l1d_in_lds(C);
-    int ran = 0;                                 // bit 0: a vector kernel was launched, bit 1: the generic one
-    auto vec_fits = [&](const PlaneSet &Q, const FrameGeom &H) {
-        if (!mix_ok || !(mode == LUTR_INTERP_NONE || vec_mode(mode))) return false;
-        if (H.w % pxt || H.row0 % bh || H.rows % bh) return false;
-        if (!units_fit((long long)(H.w / pxt) * (H.rows / bh) * H.nframes)) return false;
-        if (!plane_ok(Q.s[0], Q.ss[0], Q.sfs[0], pxt * bsi, batch, kStrideAny, false) || !plane_ok(Q.d[0], Q.ds[0], Q.dfs[0], pxt * bso, batch, kStrideAny, false))
-            return false;
-        for (int c = 1; c < 3; c++)
-            if (!plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], (pxt >> icsx) * bsi, batch, kStrideAny, false) ||
-                !plane_ok(Q.d[c], Q.ds[c], Q.dfs[c], (pxt >> ocsx) * bso, batch, kStrideAny, false))
-                return false;
-        return true;
-    };
     auto vec = [&](const PlaneSet &Q, const FrameGeom &H) -> const char * {
-        ran |= 1;
-        if (win && wout) return launch_yuv_l1d_vec_w11(st, L, C, K, Q, H, icsx, icsy, ocsx, ocsy, mode, lds);
-        if (win) return launch_yuv_l1d_vec_w10(st, L, C, K, Q, H, icsx, icsy, ocsx, ocsy, mode, lds);
+        if (U.win && U.wout) return launch_yuv_l1d_vec_w11(st, L, C, K, Q, H, icsx, icsy, ocsx, ocsy, mode, lds);
+        if (U.win) return launch_yuv_l1d_vec_w10(st, L, C, K, Q, H, icsx, icsy, ocsx, ocsy, mode, lds);
         return launch_yuv_l1d_vec_w00(st, L, C, K, Q, H, icsx, icsy, ocsx, ocsy, mode, lds);
     };
-    auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
-        ran |= 2;
-        hipLaunchKernelGGL(k_yuv_l1d_generic, dim3(block_grid("k_yuv_l1d_generic", H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, C, K, Q,
-                           H, win,
-                           wout, icsx, icsy, ocsx, ocsy, mode);
+    auto generic = [&](const PlaneSet &Q, const FrameGeom &H, int) {
+        hipLaunchKernelGGL(k_yuv_l1d_generic, dim3(U.generic_grid("k_yuv_l1d_generic", H)), dim3(256), 0, st, L, C, K, Q, H, U.win, U.wout,
+                           icsx, icsy, ocsx, ocsy, mode);
         return "k_yuv_l1d_generic";
     };
-    const char *name = launch_vec_or_generic(variant, P, G, pxt, vec_fits, vec, generic, [&](int wv) {
-        return advance_planes(P, wv * bsi, (wv >> icsx) * bsi, wv * bso, (wv >> ocsx) * bso);
-    });
-    if (!name || ran != 3) return name;
-    // a ragged width split between the two kernels: both are named
-    static thread_local std::string both;
-    both = std::string(name) + "+k_yuv_l1d_generic";
-    return both.c_str();
+    return launch_union(variant, P, G, U, mode == LUTR_INTERP_NONE || vec_mode(mode), vec, generic, "k_yuv_l1d_generic");
 }
 
 // ================================================================= lut1d alone on planar RGB

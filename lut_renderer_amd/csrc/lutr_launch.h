@@ -8,6 +8,7 @@
 #include <cstring>
 #include <mutex>
 #include <set>
+#include <string>
 #include <utility>
 
 #include "lutr_internal.h"
@@ -161,6 +162,66 @@ const char *launch_vec_or_generic(int variant, const Planes &P, const FrameGeom 
         }
     }
     return generic(P, G);
+}
+
+// ---------------------------------------------------------------- the paths that work by union blocks
+// What the launchers of lutr_xsub.hip, lutr_bnd.hip, lutr_chain.hip, lutr_cdl.hip, lutr_l1d.hip and lutr_stack.hip share: the
+// widths and the vector kernels' unit of a call, the plane checks of those kernels and the planes of a column split's tail.
+struct UnionLaunch {
+    int win, wout;             // 16-bit containers in / out
+    int icsx, ocsx, csx, csy;  // the chroma shifts the checks need, and the union block's
+    int bh, pxt;               // the unit: bh luma rows of pxt samples, 8 bytes of luma per row (16 for a 16-bit source written as 8 bit)
+    long long bsi, bso;        // bytes per sample in / out
+    bool mix_ok, batch;        // the container mix has vector kernels (8 -> 16 bit has none); more than one frame
+
+    UnionLaunch(const FrameGeom &G, int din, int dout, int icsx_, int icsy, int ocsx_, int ocsy)
+        : win(din > 8), wout(dout > 8), icsx(icsx_), ocsx(ocsx_), csx(icsx_ > ocsx_ ? icsx_ : ocsx_), csy(icsy > ocsy ? icsy : ocsy),
+          bh(1 << csy), pxt((win && !wout) ? 8 : (win ? 4 : 8)), bsi(win ? 2 : 1), bso(wout ? 2 : 1),
+          mix_ok(win == wout || (win && !wout)), batch(G.nframes > 1) {}
+
+    // whole units, 32-bit unit indices, and whole aligned words of every plane per thread
+    bool fits(const PlaneSet &Q, const FrameGeom &H) const
+    {
+        if (!mix_ok) return false;
+        if (H.w % pxt || H.row0 % bh || H.rows % bh) return false;
+        if (!units_fit((long long)(H.w / pxt) * (H.rows / bh) * H.nframes)) return false;
+        if (!plane_ok(Q.s[0], Q.ss[0], Q.sfs[0], pxt * bsi, batch, kStrideAny, false) || !plane_ok(Q.d[0], Q.ds[0], Q.dfs[0], pxt * bso, batch, kStrideAny, false))
+            return false;
+        for (int c = 1; c < 3; c++)
+            if (!plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], (pxt >> icsx) * bsi, batch, kStrideAny, false) ||
+                !plane_ok(Q.d[c], Q.ds[c], Q.dfs[c], (pxt >> ocsx) * bso, batch, kStrideAny, false))
+                return false;
+        return true;
+    }
+    // a plane at luma resolution beside the source (the stack's matte): whole aligned words per thread
+    bool luma_plane_fits(const void *p, long long stride, long long fstride, int wide) const
+    {
+        return plane_ok(p, stride, fstride, pxt * (wide ? 2 : 1), batch, kStrideAny, false);
+    }
+    unsigned generic_grid(const char *family, const FrameGeom &H) const { return block_grid(family, H.w, H.rows, H.nframes, csx, csy); }
+};
+
+// launch_vec_or_generic for such a path.  extra_ok: what the family's vector kernels ask beyond UnionLaunch::fits (their modes, a
+// plane of their own).  vec(Q, H) and generic(Q, H, x0) launch and return the kernel's name; x0 is the frame column of the planes'
+// column 0, wv for the tail of a column split and 0 otherwise.  tail_name: the generic kernel's name, for a family that reports
+// "<vector kernel>+<tail_name>" on a ragged split; null: the vector kernel's name alone.
+template <class Vec, class Generic>
+const char *launch_union(int variant, const PlaneSet &P, const FrameGeom &G, const UnionLaunch &U, bool extra_ok, Vec vec,
+                         Generic generic, const char *tail_name = nullptr)
+{
+    int ran = 0, x0 = 0;                         // ran bit 0: a vector kernel was launched, bit 1: the generic one
+    const char *name = launch_vec_or_generic(
+        variant, P, G, U.pxt, [&](const PlaneSet &Q, const FrameGeom &H) { return extra_ok && U.fits(Q, H); },
+        [&](const PlaneSet &Q, const FrameGeom &H) { ran |= 1; return vec(Q, H); },
+        [&](const PlaneSet &Q, const FrameGeom &H) { ran |= 2; return generic(Q, H, x0); },
+        [&](int wv) {
+            x0 = wv;
+            return advance_planes(P, wv * U.bsi, (wv >> U.icsx) * U.bsi, wv * U.bso, (wv >> U.ocsx) * U.bso);
+        });
+    if (!name || ran != 3 || !tail_name) return name;
+    static thread_local std::string both;
+    both = std::string(name) + "+" + tail_name;
+    return both.c_str();
 }
 
 // The persistent tile kernels pay a fixed start-up (coordinate table, tube staging, a wave's first tile at a quarter of the issue

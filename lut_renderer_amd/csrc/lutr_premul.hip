@@ -57,7 +57,7 @@ __device__ __forceinline__ uint32_t word_code(const uint32_t *w, int i)
     else return (w[i >> 2] >> ((i & 3) * 8)) & 0xffu;
 }
 
-// yuv_xsub_vec_body's structure (lutr_device.h) without the dither offsets: whole-word loads and stores, the union block walk,
+// union_vec_unit's structure (lutr_device.h) without the dither offsets: whole-word loads and stores, the union block walk,
 // taps gathered from L1 / L2.  The thread's alpha words are loaded beside its luma words (BH rows, the same word count); the two
 // integer steps sit around lut3d_px.
 template <int WIN, int WOUT, int ICSX, int ICSY, int OCSX, int OCSY, int INTERP>

@@ -25,17 +25,21 @@
 //                        k_yuv_stack_matte_vec
 //   LUTR_SKA_GENERIC     the generic kernel in its MATTE form: k_yuv_stack_matte_generic
 //
-// MIX is a compile-time parameter of the translation unit, LUTR_SK_MIX: the same kernel text, with the pixel's
-// codes behind the YUV -> RGB stage (q0) kept across the step walk, or evaluated again behind it, and
-// q = (int)((q0 + s * (q1 - q0)) + 0.5f) sent to the RGB -> YUV stage; s is the strength of the pixel's frame, clamped to [0, 1].
-// A translation unit without it holds nothing of the mix: the kernels of 3.21 keep their code, registers and names.
+// MIX is a form of the same kernel text, with the pixel's codes behind the YUV -> RGB stage (q0) kept across the
+// step walk, or evaluated again behind it, and q = (int)((q0 + s * (q1 - q0)) + 0.5f) sent to the RGB -> YUV stage; s is the
+// strength of the pixel's frame, clamped to [0, 1].
 //
-// MATTE is a third form, LUTR_SK_MATTE, which implies LUTR_SK_MIX: the mix form's text with one more argument, a
-// plane of unsigned codes at luma resolution.  The strength of a pixel is the frame's times its matte sample: a' = min(a, Mm),
+// MATTE is a third form, which implies MIX: the mix form's text with one more argument, a plane of unsigned
+// codes at luma resolution.  The strength of a pixel is the frame's times its matte sample: a' = min(a, Mm),
 // a'' = invert ? Mm - a' : a', w = s * (a'' * rcp), and w takes the place of s in the mix.  The vector kernels are built per
-// matte container (WM) beside the source's; where the matte's words are loaded is LUTR_SK_MATTE_LATE (3.23 point 5).  A
-// translation unit without LUTR_SK_MATTE holds nothing of it.
-#include <string>
+// matte container (WM) beside the source's and load the thread's matte words at the top of a unit, beside the source words (3.23
+// point 5).
+//
+// How the forms are told apart: the generic kernel's body takes the form as a template parameter (StackForm), and the switches
+// of its translation units only choose the instantiation.  The vector kernel keeps its own copy of union_vec_unit's structure
+// (lutr_device.h) and the preprocessor forms it had, LUTR_SK_MIX and LUTR_SK_MATTE with the SK_* macros below: through the shared
+// body mix instances lose a wave and the matte forms run slower.  Either way a translation unit without the MIX
+// or MATTE switches holds nothing of them: the kernels of 3.21 keep their code, registers and names.
 #if defined(LUTR_SKM_WI)
 #define LUTR_SK_WI LUTR_SKM_WI
 #define LUTR_SK_WO LUTR_SKM_WO
@@ -45,7 +49,8 @@
 #define LUTR_SK_WO LUTR_SKA_WO
 #define LUTR_SK_WM LUTR_SKA_WM
 #endif
-#if defined(LUTR_SKA_WI) || defined(LUTR_SKA_GENERIC)
+#ifdef LUTR_SK_WI                    // the vector kernel's forms
+#if defined(LUTR_SKA_WI)
 #define LUTR_SK_MATTE 1
 #define LUTR_SK_MIX 1
 #define SK_MIX_PARAM , MixConsts M, MatteConsts A
@@ -56,22 +61,19 @@
 #define SK_VEC k_yuv_stack_matte_vec
 #define SK_VEC_NAME "k_yuv_stack_matte_vec<"
 #define SK_VEC_LAUNCH_FN LUTR_CAT(LUTR_CAT(LUTR_CAT(launch_yuv_stack_matte_vec_w, LUTR_SK_WI), LUTR_SK_WO), LUTR_SK_WM)
-#define SK_GENERIC k_yuv_stack_matte_generic
-#elif defined(LUTR_SKM_WI) || defined(LUTR_SKM_GENERIC)
+#elif defined(LUTR_SKM_WI)
 #define LUTR_SK_MIX 1
 #define SK_MIX_PARAM , MixConsts M
 #define SK_MIX_ARG , M
 #define SK_VEC k_yuv_stack_mix_vec
 #define SK_VEC_NAME "k_yuv_stack_mix_vec<"
 #define SK_VEC_LAUNCH launch_yuv_stack_mix_vec_w
-#define SK_GENERIC k_yuv_stack_mix_generic
 #else
 #define SK_MIX_PARAM
 #define SK_MIX_ARG
 #define SK_VEC k_yuv_stack_vec
 #define SK_VEC_NAME "k_yuv_stack_vec<"
 #define SK_VEC_LAUNCH launch_yuv_stack_vec_w
-#define SK_GENERIC k_yuv_stack_generic
 #endif
 #ifndef LUTR_SK_MATTE
 #define SK_WM_TPARAM
@@ -79,6 +81,7 @@
 #define SK_WM_NAME
 #define SK_VEC_LAUNCH_FN LUTR_CAT(LUTR_CAT(SK_VEC_LAUNCH, LUTR_SK_WI), LUTR_SK_WO)
 #endif
+#endif  // LUTR_SK_WI
 
 #include "lutr_device.h"
 #include "lutr_launch.h"
@@ -105,7 +108,8 @@ __device__ __forceinline__ Rgb stack_round_px(float maxf, const Rgb &o)
     return q;
 }
 
-#ifdef LUTR_SK_MIX
+enum StackForm { SK_PLAIN, SK_MIX, SK_MATTE };
+
 // The strength of frame fr: one dword of the per-frame array, or the call's scalar.  A NaN is 0, found by its bits (the build does
 // not honour NaNs in float compares); then the clamp.
 __device__ __forceinline__ float mix_strength(const MixConsts &M, long long fr)
@@ -124,9 +128,7 @@ __device__ __forceinline__ Rgb mix_px(float s, const Rgb &q0, const Rgb &q1)
     q.b = (float)(int)((q0.b + s * (q1.b - q0.b)) + 0.5f);
     return q;
 }
-#endif
 
-#ifdef LUTR_SK_MATTE
 // The strength of one pixel: the frame's strength s times the matte sample a (a code held as a float).  The clamp and the
 // inversion are on integers below 2^16, exact in fp32; then one rounded product each for the normalisation and the scaling.
 __device__ __forceinline__ float matte_weight(const MatteConsts &A, float s, float a)
@@ -136,7 +138,6 @@ __device__ __forceinline__ float matte_weight(const MatteConsts &A, float s, flo
     const float t = v * A.rcp;
     return s * t;
 }
-#endif
 
 #ifdef LUTR_SK_WI
 // ================================================================= vector kernel
@@ -196,8 +197,8 @@ __device__ __forceinline__ void stack_block(const StackConsts &S, const CdlConst
     }
 }
 
-// k_yuv_l1d_vec's structure (lutr_l1d.hip) with the step walk as the per-block middle.  TRI: some stage is trilinear (a stack of
-// nearest / tetrahedral stages does not carry trilinear's registers).  No thread leaves before the barrier behind the staging.
+// union_vec_unit's structure (lutr_device.h), as this family's own copy, with the step walk as the per-block middle.  TRI: some
+// stage is trilinear (a stack of nearest / tetrahedral stages does not carry trilinear's registers).  No thread leaves before the barrier behind the staging.
 template <int WIN, int WOUT, SK_WM_TPARAM int ICSX, int ICSY, int OCSX, int OCSY, bool TRI, bool LDS>
 __global__ __launch_bounds__(256) void SK_VEC(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P, FrameGeom G SK_MIX_PARAM)
 {
@@ -235,11 +236,9 @@ __global__ __launch_bounds__(256) void SK_VEC(LutConsts L, LutConsts L2, StackCo
         constexpr int MWI = PXT * (WM ? 2 : 1) / 4;
         static_assert(MWI >= 1, "a thread must own whole matte words");
         const uint8_t *mrow = A.data + fr * A.fstride + (long long)y0 * A.stride + (long long)xu * (MWI * 4);
-#ifndef LUTR_SK_MATTE_LATE
         uint32_t mw[BH][MWI];
 #pragma unroll
         for (int dy = 0; dy < BH; dy++) ld_words<MWI>(mw[dy], mrow + dy * A.stride);
-#endif
 #endif
 
         uint32_t yw[BH][YWI], cbw[IRH][CWI], crw[IRH][CWI];
@@ -290,19 +289,13 @@ __global__ __launch_bounds__(256) void SK_VEC(LutConsts L, LutConsts L2, StackCo
 #endif
             stack_block<TRI>(S, C, l1d, L, L2, px);
 #ifdef LUTR_SK_MATTE
-            // the block's weights, in the mix's order.  LATE: the block's samples are read here, behind the walk -- nothing of the
-            // matte is live across the gathers, and the loads are exposed
+            // the block's weights, in the mix's order
             float wgt[BH * BW];
 #pragma unroll
             for (int dy = 0; dy < BH; dy++)
 #pragma unroll
                 for (int dx = 0; dx < BW; dx++) {
-#ifdef LUTR_SK_MATTE_LATE
-                    const float a = ld_sample(mrow + dy * A.stride, j * BW + dx, WM);   // hipcc merges the BW loads of a row
-#else
-                    const float a = word_sample<WM>(mw[dy], j * BW + dx);
-#endif
-                    wgt[dy * BW + dx] = matte_weight(A, strength, a);
+                    wgt[dy * BW + dx] = matte_weight(A, strength, word_sample<WM>(mw[dy], j * BW + dx));
                 }
 #define SK_STRENGTH(i) wgt[i]
 #else
@@ -356,7 +349,7 @@ __global__ __launch_bounds__(256) void SK_VEC(LutConsts L, LutConsts L2, StackCo
                 for (int k = 0; k < YWI; k++) asm volatile("" : "+v"(yw[dy][k]));
 #pragma unroll
                 for (int k = 0; k < YWO; k++) asm volatile("" : "+v"(yo[dy][k]));
-#if defined(LUTR_SK_MATTE) && !defined(LUTR_SK_MATTE_LATE)
+#ifdef LUTR_SK_MATTE
 #pragma unroll
                 for (int k = 0; k < MWI; k++) asm volatile("" : "+v"(mw[dy][k]));
 #endif
@@ -389,10 +382,7 @@ const char *SK_VEC_LAUNCH_FN(hipStream_t st, const LutConsts &L, const LutConsts
                              bool lds SK_MIX_PARAM)
 {
     constexpr int WI = LUTR_SK_WI, WO = LUTR_SK_WO;
-    constexpr int PXT = vec_bytes<WI, WO>() / (WI ? 2 : 1);
-    const int bh = 1 << cmax(icsy, ocsy);
-    const long long units = (long long)(G.w / PXT) * (G.rows / bh) * G.nframes;
-    const dim3 grid(stride_grid(LUTR_STR(SK_VEC), units, lds ? (unsigned)device_cus() * 8u : kGridStrideCap)), block(256);
+    const dim3 grid(stride_grid(LUTR_STR(SK_VEC), union_units<WI, WO>(G, icsy, ocsy), lds ? (unsigned)device_cus() * 8u : kGridStrideCap)), block(256);
     const size_t lds_bytes = lds ? (size_t)(S.lds_cdl_words + S.lds_l1d_words) * sizeof(uint32_t) : 0;
 #define SK_CASE(IX, IY, OX, OY, T) \
     if (icsx == IX && icsy == IY && ocsx == OX && ocsy == OY && tri == (T != 0)) { \
@@ -402,9 +392,7 @@ const char *SK_VEC_LAUNCH_FN(hipStream_t st, const LutConsts &L, const LutConsts
                    : SK_VEC_NAME LUTR_STR(LUTR_SK_WI) "," LUTR_STR(LUTR_SK_WO) "," SK_WM_NAME #IX "," #IY "," #OX "," #OY "," #T ",0>"; \
     }
 #define SK_PAIR(IX, IY, OX, OY) SK_CASE(IX, IY, OX, OY, 0) SK_CASE(IX, IY, OX, OY, 1)
-    SK_PAIR(1, 1, 1, 1) SK_PAIR(1, 1, 1, 0) SK_PAIR(1, 1, 0, 0)
-    SK_PAIR(1, 0, 1, 1) SK_PAIR(1, 0, 1, 0) SK_PAIR(1, 0, 0, 0)
-    SK_PAIR(0, 0, 1, 1) SK_PAIR(0, 0, 1, 0) SK_PAIR(0, 0, 0, 0)
+    LUTR_UNION_PAIRS(SK_PAIR)
 #undef SK_PAIR
 #undef SK_CASE
     return nullptr;
@@ -412,75 +400,55 @@ const char *SK_VEC_LAUNCH_FN(hipStream_t st, const LutConsts &L, const LutConsts
 
 #else  // !LUTR_SK_WI
 // ================================================================= generic kernel
-// One thread per union block; any depth, stride or alignment, odd sizes, all five modes on either lattice.  k_yuv_cdl_generic's
-// walk with the step list per pixel (the tables read from global memory): a pixel outside the frame is the edge pixel again, only
-// pixels and chroma samples inside the planes are written.
-__global__ __launch_bounds__(256) void SK_GENERIC(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P, FrameGeom G SK_MIX_PARAM,
-                                                  int win, int wout, int icsx, int icsy, int ocsx, int ocsy)
+// One thread per union block; any depth, stride or alignment, odd sizes, all five modes on either lattice.  xsub_union_block's
+// walk (lutr_device.h) with the step list per pixel (the tables read from global memory), then (MIX, MATTE) the mix with the
+// pixel's own q; the matte form reads its sample at the pixel's clamped (x, y).  M and A are null in the forms without them.
+template <int FORM>
+__device__ __forceinline__ void stack_generic(const LutConsts &L, const LutConsts &L2, const StackConsts &S, const YuvConsts &K,
+                                              const PlaneSet &P, const FrameGeom &G, const MixConsts *M, const MatteConsts *A, int win,
+                                              int wout, int icsx, int icsy, int ocsx, int ocsy)
 {
     const GFetch f(L), f2(L2);
     PlaneSink sink{K, P, wout};
     const CdlConsts C{S.cdl_tab, S.stride, S.sat};
     const bool mix = S.sat != 1.0f;
-    const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy);
-    const int bw = 1 << csx, bh = 1 << csy, obw = 1 << ocsx, obh = 1 << ocsy;
-    const int cwo = (G.w + obw - 1) >> ocsx, cho = (G.h + obh - 1) >> ocsy;
-    for_each_block(G, csx, csy, false, [&](long long fr, int ux, int uy) {
-#ifdef LUTR_SK_MIX
-        const float strength = mix_strength(M, fr);
-#endif
-        for (int oy = 0; oy < bh; oy += obh) {
-            for (int ox = 0; ox < bw; ox += obw) {
-                float rs = 0.f, gs = 0.f, bs = 0.f;
-                for (int dy = 0; dy < obh; dy++) {
-                    const int yy = uy * bh + oy + dy;
-                    const int y = yy < G.h ? yy : G.h - 1;
-                    for (int dx = 0; dx < obw; dx++) {
-                        const int xx = ux * bw + ox + dx;
-                        const int x = xx < G.w ? xx : G.w - 1;
-                        const float cbv = ld_sample(src_row(P, 1, fr, y >> icsy), x >> icsx, win);
-                        const float crv = ld_sample(src_row(P, 2, fr, y >> icsy), x >> icsx, win);
-                        const float yv = ld_sample(src_row(P, 0, fr, y), x, win);
-                        Rgb o = yuv_to_rgb(K, yv, chroma_terms(K, cbv, crv));
-#ifdef LUTR_SK_MIX
-                        const Rgb o0 = o;
-#endif
-#ifdef LUTR_SK_MATTE
-                        const float wgt = matte_weight(A, strength, ld_sample(A.data + fr * A.fstride + (long long)y * A.stride, x, A.wide));
-#define SK_STRENGTH wgt
-#else
-#define SK_STRENGTH strength
-#endif
+    for_each_block(G, cmax(icsx, ocsx), cmax(icsy, ocsy), false, [&](long long fr, int ux, int uy) {
+        float strength = 0.0f;
+        if constexpr (FORM != SK_PLAIN) strength = mix_strength(*M, fr);
+        xsub_union_block(K, P, G, fr, ux, uy, win, icsx, icsy, ocsx, ocsy, sink, [&](long long fr, int x, int y, const Rgb &q) {
+            Rgb o = q;
+            float wgt = strength;
+            if constexpr (FORM == SK_MATTE)
+                wgt = matte_weight(*A, strength, ld_sample(A->data + fr * A->fstride + (long long)y * A->stride, x, A->wide));
 #pragma nounroll
-                        for (unsigned long long ops = S.ops; ops & 0xffull; ops >>= 8) {
-                            const int op = (int)(ops & 15u), mode = (int)((ops >> 4) & 15u);
-                            switch (op) {
-                            case STACK_OP_L1D:        o = stack_l1d_px(S.l1d_tab, S.stride, o); break;
-                            case STACK_OP_CDL:        o = cdl_px(C, mix, o); break;
-                            case STACK_OP_ROUND:      o = stack_round_px(S.maxf, o); break;
-                            case STACK_OP_LAT_CODES:  o = lut3d_px_rt(mode, L, f, o.r, o.g, o.b); break;
-                            case STACK_OP_LAT_UNIT:   o = lut3d_unit_rt(mode, L, f, o); break;
-                            case STACK_OP_LAT2_CODES: o = lut3d_px_rt(mode, L2, f2, o.r, o.g, o.b); break;
-                            default:                  o = lut3d_unit_rt(mode, L2, f2, o); break;
-                            }
-                        }
-#ifdef LUTR_SK_MIX
-                        o = mix_px(SK_STRENGTH, o0, o);
-#endif
-#undef SK_STRENGTH
-                        rs += o.r; gs += o.g; bs += o.b;
-                        if (yy < G.h && xx < G.w) sink.luma(fr, x, y, o);
-                    }
+            for (unsigned long long ops = S.ops; ops & 0xffull; ops >>= 8) {
+                const int op = (int)(ops & 15u), mode = (int)((ops >> 4) & 15u);
+                switch (op) {
+                case STACK_OP_L1D:        o = stack_l1d_px(S.l1d_tab, S.stride, o); break;
+                case STACK_OP_CDL:        o = cdl_px(C, mix, o); break;
+                case STACK_OP_ROUND:      o = stack_round_px(S.maxf, o); break;
+                case STACK_OP_LAT_CODES:  o = lut3d_px_rt(mode, L, f, o.r, o.g, o.b); break;
+                case STACK_OP_LAT_UNIT:   o = lut3d_unit_rt(mode, L, f, o); break;
+                case STACK_OP_LAT2_CODES: o = lut3d_px_rt(mode, L2, f2, o.r, o.g, o.b); break;
+                default:                  o = lut3d_unit_rt(mode, L2, f2, o); break;
                 }
-                const int ocx = (ux * bw + ox) >> ocsx, ocy = (uy * bh + oy) >> ocsy;
-                if (ocx < cwo && ocy < cho) sink.chroma(fr, ocx, ocy, rs, gs, bs);
             }
-        }
+            if constexpr (FORM != SK_PLAIN) o = mix_px(wgt, q, o);
+            return o;
+        });
     });
 }
 
-#if defined(LUTR_SK_MATTE)
-// the MATTE form's launch, for the launcher in the translation unit without LUTR_SK_MIX
+// this translation unit's kernel and its launch: the one place that says which form it holds
+#if defined(LUTR_SKA_GENERIC)
+__global__ __launch_bounds__(256) void k_yuv_stack_matte_generic(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P,
+                                                                 FrameGeom G, MixConsts M, MatteConsts A, int win, int wout, int icsx,
+                                                                 int icsy, int ocsx, int ocsy)
+{
+    stack_generic<SK_MATTE>(L, L2, S, K, P, G, &M, &A, win, wout, icsx, icsy, ocsx, ocsy);
+}
+
+// its launch, for the launcher in the plain translation unit
 const char *launch_yuv_stack_matte_generic(hipStream_t st, unsigned grid, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
                                            const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const MixConsts &M,
                                            const MatteConsts &A, int win, int wout, int icsx, int icsy, int ocsx, int ocsy)
@@ -489,8 +457,15 @@ const char *launch_yuv_stack_matte_generic(hipStream_t st, unsigned grid, const 
                        ocsy);
     return "k_yuv_stack_matte_generic";
 }
-#elif defined(LUTR_SK_MIX)
-// the MIX form's launch, for the launcher in the translation unit without LUTR_SK_MIX
+#elif defined(LUTR_SKM_GENERIC)
+__global__ __launch_bounds__(256) void k_yuv_stack_mix_generic(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P,
+                                                               FrameGeom G, MixConsts M, int win, int wout, int icsx, int icsy,
+                                                               int ocsx, int ocsy)
+{
+    stack_generic<SK_MIX>(L, L2, S, K, P, G, &M, nullptr, win, wout, icsx, icsy, ocsx, ocsy);
+}
+
+// its launch, for the launcher in the plain translation unit
 const char *launch_yuv_stack_mix_generic(hipStream_t st, unsigned grid, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
                                          const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const MixConsts &M, int win,
                                          int wout, int icsx, int icsy, int ocsx, int ocsy)
@@ -499,6 +474,12 @@ const char *launch_yuv_stack_mix_generic(hipStream_t st, unsigned grid, const Lu
     return "k_yuv_stack_mix_generic";
 }
 #else
+__global__ __launch_bounds__(256) void k_yuv_stack_generic(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P, FrameGeom G,
+                                                           int win, int wout, int icsx, int icsy, int ocsx, int ocsy)
+{
+    stack_generic<SK_PLAIN>(L, L2, S, K, P, G, nullptr, nullptr, win, wout, icsx, icsy, ocsx, ocsy);
+}
+
 // ================================================================= launcher
 // LUTR_STACK_LDS=0 / 1: where the vector kernels read the CDL and 1D tables (tests and tools; unset: the default below).  The
 // tables the stack uses go to LDS together or not at all: above 24 KB in sum they are read from global memory.  The default follows
@@ -520,13 +501,7 @@ const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, co
                              const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int din, int dout, int icsx, int icsy,
                              int ocsx, int ocsy, const MixConsts *M, const MatteConsts *A)
 {
-    const int win = din > 8, wout = dout > 8;
-    const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy), bh = 1 << csy;
-    // the vector kernels' unit: 8 bytes of luma per row (16 for a 16-bit source written as 8 bit); 8 -> 16 bit has none
-    const bool mix_ok = win == wout || (win && !wout);
-    const int pxt = (win && !wout) ? 8 : (win ? 4 : 8);
-    const long long bsi = win ? 2 : 1, bso = wout ? 2 : 1;
-    const bool batch = G.nframes > 1;
+    const UnionLaunch U(G, din, dout, icsx, icsy, ocsx, ocsy);
     const bool lds = stack_in_lds(S);
     // the lattice steps' modes: the vector kernels have nearest / trilinear / tetrahedral
     bool modes_ok = true, tri = false;
@@ -536,71 +511,44 @@ const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, co
         modes_ok = modes_ok && vec_mode(mode);
         tri = tri || mode == LUTR_INTERP_TRILINEAR;
     }
-    int ran = 0;                                 // bit 0: a vector kernel was launched, bit 1: the generic one
-    auto vec_fits = [&](const PlaneSet &Q, const FrameGeom &H) {
-        if (!mix_ok || !modes_ok) return false;
-        if (H.w % pxt || H.row0 % bh || H.rows % bh) return false;
-        if (!units_fit((long long)(H.w / pxt) * (H.rows / bh) * H.nframes)) return false;
-        if (!plane_ok(Q.s[0], Q.ss[0], Q.sfs[0], pxt * bsi, batch, kStrideAny, false) || !plane_ok(Q.d[0], Q.ds[0], Q.dfs[0], pxt * bso, batch, kStrideAny, false))
-            return false;
-        for (int c = 1; c < 3; c++)
-            if (!plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], (pxt >> icsx) * bsi, batch, kStrideAny, false) ||
-                !plane_ok(Q.d[c], Q.ds[c], Q.dfs[c], (pxt >> ocsx) * bso, batch, kStrideAny, false))
-                return false;
-        // the matte kernels: built for the source's container and for bytes beside a 16-bit source; whole aligned dwords a thread
-        if (A && (A->wide > win || !plane_ok(A->data, A->stride, A->fstride, pxt * (A->wide ? 2 : 1), batch, kStrideAny, false)))
-            return false;
-        return true;
-    };
+    // the matte kernels: built for the source's container and for bytes beside a 16-bit source; whole aligned dwords a thread
+    const bool matte_ok = !A || (A->wide <= U.win && U.luma_plane_fits(A->data, A->stride, A->fstride, A->wide));
     auto vec = [&](const PlaneSet &Q, const FrameGeom &H) -> const char * {
-        ran |= 1;
         if (A) {
-            if (win && wout)
+            if (U.win && U.wout)
                 return A->wide ? launch_yuv_stack_matte_vec_w111(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M, *A)
                                : launch_yuv_stack_matte_vec_w110(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M, *A);
-            if (win)
+            if (U.win)
                 return A->wide ? launch_yuv_stack_matte_vec_w101(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M, *A)
                                : launch_yuv_stack_matte_vec_w100(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M, *A);
             return launch_yuv_stack_matte_vec_w000(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M, *A);
         }
         if (M) {
-            if (win && wout) return launch_yuv_stack_mix_vec_w11(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M);
-            if (win) return launch_yuv_stack_mix_vec_w10(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M);
+            if (U.win && U.wout) return launch_yuv_stack_mix_vec_w11(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M);
+            if (U.win) return launch_yuv_stack_mix_vec_w10(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M);
             return launch_yuv_stack_mix_vec_w00(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M);
         }
-        if (win && wout) return launch_yuv_stack_vec_w11(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds);
-        if (win) return launch_yuv_stack_vec_w10(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds);
+        if (U.win && U.wout) return launch_yuv_stack_vec_w11(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds);
+        if (U.win) return launch_yuv_stack_vec_w10(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds);
         return launch_yuv_stack_vec_w00(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds);
     };
-    auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
-        ran |= 2;
+    const char *const generic_name = A ? "k_yuv_stack_matte_generic" : M ? "k_yuv_stack_mix_generic" : "k_yuv_stack_generic";
+    auto generic = [&](const PlaneSet &Q, const FrameGeom &H, int x0) {
+        const unsigned grid = U.generic_grid(generic_name, H);
         if (A) {
             // the tail of a column split: the matte moves right with the source's luma plane
             MatteConsts B = *A;
-            B.data += (Q.s[0] - P.s[0]) / bsi * (A->wide ? 2 : 1);
-            return launch_yuv_stack_matte_generic(st, block_grid("k_yuv_stack_matte_generic", H.w, H.rows, H.nframes, csx, csy), L, L2, S, K, Q, H,
-                                                  *M, B, win, wout,
-                                                  icsx, icsy, ocsx, ocsy);
+            B.data += (long long)x0 * (A->wide ? 2 : 1);
+            return launch_yuv_stack_matte_generic(st, grid, L, L2, S, K, Q, H, *M, B, U.win, U.wout, icsx, icsy, ocsx, ocsy);
         }
-        if (M)
-            return launch_yuv_stack_mix_generic(st, block_grid("k_yuv_stack_mix_generic", H.w, H.rows, H.nframes, csx, csy), L, L2, S, K, Q, H, *M,
-                                                win, wout, icsx,
-                                                icsy, ocsx, ocsy);
-        hipLaunchKernelGGL(k_yuv_stack_generic, dim3(block_grid("k_yuv_stack_generic", H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, L2,
-                           S, K, Q, H,
-                           win, wout, icsx, icsy, ocsx, ocsy);
-        return "k_yuv_stack_generic";
+        if (M) return launch_yuv_stack_mix_generic(st, grid, L, L2, S, K, Q, H, *M, U.win, U.wout, icsx, icsy, ocsx, ocsy);
+        hipLaunchKernelGGL(k_yuv_stack_generic, dim3(grid), dim3(256), 0, st, L, L2, S, K, Q, H, U.win, U.wout, icsx, icsy, ocsx, ocsy);
+        return generic_name;
     };
-    const char *name = launch_vec_or_generic(variant, P, G, pxt, vec_fits, vec, generic, [&](int wv) {
-        return advance_planes(P, wv * bsi, (wv >> icsx) * bsi, wv * bso, (wv >> ocsx) * bso);
-    });
-    if (!name || ran != 3) return name;
-    // a ragged width split between the two kernels: both are named
-    static thread_local std::string both;
-    both = std::string(name) + (A ? "+k_yuv_stack_matte_generic" : M ? "+k_yuv_stack_mix_generic" : "+k_yuv_stack_generic");
-    return both.c_str();
+    return launch_union(variant, P, G, U, modes_ok && matte_ok, vec, generic, generic_name);
 }
-#endif  // LUTR_SK_MIX
+#endif  // the generic forms
+
 #endif  // LUTR_SK_WI
 
 }  // namespace lutr

@@ -19,11 +19,16 @@ namespace lutr {
 
 #ifdef LUTR_XS_WI
 // ================================================================= vector kernel, global gather
-// (the body, shared with the blue-noise kernels of lutr_bnd.hip: yuv_xsub_vec_body, lutr_device.h)
+// union_vec_unit (lutr_device.h) with the lattice as its per-pixel stage, one unit per thread
 template <int WIN, int WOUT, int ICSX, int ICSY, int OCSX, int OCSY, int INTERP>
 __global__ __launch_bounds__(256) void k_yuv_xsub_vec(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G)
 {
-    yuv_xsub_vec_body<WIN, WOUT, ICSX, ICSY, OCSX, OCSY, INTERP, false>(L, K, P, G, nullptr);
+    using U = UnionUnit<WIN, WOUT, ICSX, ICSY, OCSX, OCSY>;
+    const GFetch f(L);
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    if (u >= U::count(G)) return;
+    auto px = [=](const Rgb &q) __attribute__((always_inline)) { return lut3d_px<INTERP>(L, f, q.r, q.g, q.b); };
+    union_vec_unit<U>(u, K, P, G, px);
 }
 
 // The vector kernels of this translation unit's container mix; the layout checks are the caller's (launch_yuv_xsub).
@@ -32,16 +37,14 @@ const char *LUTR_CAT(LUTR_CAT(launch_yuv_xsub_vec_w, LUTR_XS_WI), LUTR_XS_WO)(hi
                                                                                int icsy, int ocsx, int ocsy, int mode)
 {
     constexpr int WI = LUTR_XS_WI, WO = LUTR_XS_WO;
-    constexpr int PXT = vec_bytes<WI, WO>() / (WI ? 2 : 1);
-    const int bh = 1 << cmax(icsy, ocsy);
-    const long long units = (long long)(G.w / PXT) * (G.rows / bh) * G.nframes;
-    const dim3 grid((unsigned)((units + 255) / 256)), block(256);
+    const dim3 grid((unsigned)((union_units<WI, WO>(G, icsy, ocsy) + 255) / 256)), block(256);
 #define XS_CASE(IX, IY, OX, OY, I) \
     if (icsx == IX && icsy == IY && ocsx == OX && ocsy == OY && mode == I) { \
         hipLaunchKernelGGL((k_yuv_xsub_vec<WI, WO, IX, IY, OX, OY, I>), grid, block, 0, st, L, K, P, G); \
         return "k_yuv_xsub_vec<" LUTR_STR(LUTR_XS_WI) "," LUTR_STR(LUTR_XS_WO) "," #IX "," #IY "," #OX "," #OY "," #I ">"; \
     }
 #define XS_PAIR(IX, IY, OX, OY) XS_CASE(IX, IY, OX, OY, 0) XS_CASE(IX, IY, OX, OY, 1) XS_CASE(IX, IY, OX, OY, 2)
+    // a subsampling change: the six unequal pairs of LUTR_UNION_PAIRS
     XS_PAIR(1, 1, 1, 0) XS_PAIR(1, 1, 0, 0)
     XS_PAIR(1, 0, 1, 1) XS_PAIR(1, 0, 0, 0)
     XS_PAIR(0, 0, 1, 1) XS_PAIR(0, 0, 1, 0)
@@ -60,7 +63,9 @@ __global__ __launch_bounds__(256) void k_yuv_xsub_generic(LutConsts L, YuvConsts
     const GFetch f(L);
     PlaneSink sink{K, P, wout};
     for_each_block(G, cmax(icsx, ocsx), cmax(icsy, ocsy), false, [&](long long fr, int ux, int uy) {
-        xsub_union_block(L, f, K, P, G, fr, ux, uy, win, icsx, icsy, ocsx, ocsy, mode, sink);
+        xsub_union_block(K, P, G, fr, ux, uy, win, icsx, icsy, ocsx, ocsy, sink, [&](long long, int, int, const Rgb &q) {
+            return lut3d_px_rt(mode, L, f, q.r, q.g, q.b);
+        });
     });
 }
 
@@ -71,7 +76,9 @@ __global__ __launch_bounds__(256) void k_yuv_float_xsub(LutConsts L, YuvConsts K
     const GFetch f(L);
     FloatSink sink(K, F, G, ocsx, ocsy);
     for_each_block(G, cmax(icsx, ocsx), cmax(icsy, ocsy), true, [&](long long fr, int ux, int uy) {
-        xsub_union_block(L, f, K, P, G, fr, ux, uy, win, icsx, icsy, ocsx, ocsy, mode, sink);
+        xsub_union_block(K, P, G, fr, ux, uy, win, icsx, icsy, ocsx, ocsy, sink, [&](long long, int, int, const Rgb &q) {
+            return lut3d_px_rt(mode, L, f, q.r, q.g, q.b);
+        });
     });
 }
 
@@ -87,40 +94,19 @@ void launch_yuv_float_xsub(hipStream_t st, const LutConsts &L, const YuvConsts &
 const char *launch_yuv_xsub(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
                             const FrameGeom &G, int din, int dout, int icsx, int icsy, int ocsx, int ocsy, int mode)
 {
-    const int win = din > 8, wout = dout > 8;
-    const int csx = cmax(icsx, ocsx), csy = cmax(icsy, ocsy), bh = 1 << csy;
-    // the vector kernels' unit: 8 bytes of luma per row (16 for a 16-bit source written as 8 bit); 8 -> 16 bit has none
-    const bool mix_ok = win == wout || (win && !wout);
-    const int pxt = (win && !wout) ? 8 : (win ? 4 : 8);
-    const long long bsi = win ? 2 : 1, bso = wout ? 2 : 1;
-    const bool batch = G.nframes > 1;
-    auto vec_fits = [&](const PlaneSet &Q, const FrameGeom &H) {
-        if (!mix_ok || !vec_mode(mode)) return false;
-        if (H.w % pxt || H.row0 % bh || H.rows % bh) return false;
-        if (!units_fit((long long)(H.w / pxt) * (H.rows / bh) * H.nframes)) return false;
-        if (!plane_ok(Q.s[0], Q.ss[0], Q.sfs[0], pxt * bsi, batch, kStrideAny, false) || !plane_ok(Q.d[0], Q.ds[0], Q.dfs[0], pxt * bso, batch, kStrideAny, false))
-            return false;
-        for (int c = 1; c < 3; c++)
-            if (!plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], (pxt >> icsx) * bsi, batch, kStrideAny, false) ||
-                !plane_ok(Q.d[c], Q.ds[c], Q.dfs[c], (pxt >> ocsx) * bso, batch, kStrideAny, false))
-                return false;
-        return true;
-    };
+    const UnionLaunch U(G, din, dout, icsx, icsy, ocsx, ocsy);
     auto vec = [&](const PlaneSet &Q, const FrameGeom &H) -> const char * {
-        if (win && wout) return launch_yuv_xsub_vec_w11(st, L, K, Q, H, icsx, icsy, ocsx, ocsy, mode);
-        if (win) return launch_yuv_xsub_vec_w10(st, L, K, Q, H, icsx, icsy, ocsx, ocsy, mode);
+        if (U.win && U.wout) return launch_yuv_xsub_vec_w11(st, L, K, Q, H, icsx, icsy, ocsx, ocsy, mode);
+        if (U.win) return launch_yuv_xsub_vec_w10(st, L, K, Q, H, icsx, icsy, ocsx, ocsy, mode);
         return launch_yuv_xsub_vec_w00(st, L, K, Q, H, icsx, icsy, ocsx, ocsy, mode);
     };
-    auto generic = [&](const PlaneSet &Q, const FrameGeom &H) {
-        hipLaunchKernelGGL(k_yuv_xsub_generic, dim3(block_grid("k_yuv_xsub_generic", H.w, H.rows, H.nframes, csx, csy)), dim3(256), 0, st, L, K, Q,
-                           H, win,
-                           wout, icsx, icsy, ocsx, ocsy, mode);
+    auto generic = [&](const PlaneSet &Q, const FrameGeom &H, int) {
+        hipLaunchKernelGGL(k_yuv_xsub_generic, dim3(U.generic_grid("k_yuv_xsub_generic", H)), dim3(256), 0, st, L, K, Q, H, U.win, U.wout,
+                           icsx, icsy, ocsx, ocsy, mode);
         return "k_yuv_xsub_generic";
     };
     // (no LDS-window kernel for a subsampling change; the unit is 4, 8 or 16 luma samples wide, whole union blocks)
-    return launch_vec_or_generic(variant, P, G, pxt, vec_fits, vec, generic, [&](int wv) {
-        return advance_planes(P, wv * bsi, (wv >> icsx) * bsi, wv * bso, (wv >> ocsx) * bso);
-    });
+    return launch_union(variant, P, G, U, vec_mode(mode), vec, generic);
 }
 #endif  // LUTR_XS_WI
 

@@ -17,9 +17,7 @@ Paths are timed in alternating rounds with HIP events around `--steps` launches,
 the median round.  Prints one JSON line (and writes it to `--out` when given): Gpx/s and ms per path and the time ratios
 <path>_time_vs_mix.
 
-Where the vector kernels load the matte words is a build switch (csrc/Makefile SKAFLAGS=-DLUTR_SK_MATTE_LATE: behind the step
-walk instead of at the top with the other planes).  `--alt-library PATH` names a liblutr.so built the other way (in a second
-checkout); the tool then measures both, each in a child process of its own with LUTR_LIBRARY set, and writes both under
+`--alt-library PATH` names a second liblutr.so (built in another checkout); the tool then measures both, each in a child process of its own with LUTR_LIBRARY set, and writes both under
 "placements" (`--name` / `--alt-name` label them; "chosen" is `--name`, the tree's).  `--resources FILE` carries a JSON object of
 compile-time figures along under "resources": VGPRs / waves per SIMD / scratch of the instances, from
 `hipcc -Rpass-analysis=kernel-resource-usage`, which needs no GPU.
