@@ -362,13 +362,52 @@ int lutr_yuv_constants_xsub(const lutr_yuv_params *p, float out[32]);
  * else; a ragged width on aligned rows is split between the two; dithering runs "k_rgb2yuv_float+k_dither_ed".  Variants: auto
  * and generic as for lutr_apply_yuv; vec_global fails with LUTR_EINVAL where the vector kernel cannot take the layout; vec_lds
  * always fails with LUTR_EINVAL (there is no LDS kernel for this path).
- * Not covered: YUV in with RGB out, chroma siting, a tile (LDS) kernel. */
+ * Not covered: chroma siting, a tile (LDS) kernel.  (YUV in with RGB out is lutr_apply_yuv_to_rgb.) */
 int lutr_apply_rgb_to_yuv(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int dither, int src_kind, int w, int h, int nframes,
                           const lutr_planes *src_planar, const lutr_packed *src_packed, const lutr_planes *dst, int row0, int rows);
 /* The constant block lutr_apply_rgb_to_yuv uses.  Its output-stage entries (cyr..crb, yob, cob, max_o) equal, bit for bit, those
  * of lutr_yuv_constants_xsub for a 4:4:4 source at depth lut_depth with the same output side; the input-stage entries are not
  * read by the kernels (they are filled from matrix_out / range_out).  Host only. */
 int lutr_yuv_constants_rgb2yuv(const lutr_yuv_params *p, float out[32]);
+
+/* ---- YUV sources with an RGB output (ffmpeg's lut3d=...,format=<rgb fmt> on a camera file: a DPX / TIFF / PNG
+ *      sequence, a review still, a GUI preview) ---- */
+/* Planar YUV p->fmt_in (4:2:0 / 4:2:2 / 4:4:4 at any depth din in 8..16; 4:4:0 is LUTR_EINVAL) -> each chroma sample replicated
+ * over its INPUT block (x >> icsx, y >> icsy), as lutr_apply_yuv_xsub -> integer RGB at p->lut_depth through matrix_in (the
+ * input stage of lutr_apply_yuv) -> lut3d at that depth (every interpolation mode, a .csp prelut taken; LUTR_INTERP_NONE leaves
+ * it out) -> stored as it is.  The LUT runs at the DESTINATION's depth, where ffmpeg's format negotiation puts lut3d when
+ * format=<rgb fmt> follows it; there is no depth change behind the LUT.  Of *p only fmt_in, lut_depth, matrix_in, range_src and
+ * range_in are read.
+ * dst_kind == 0: planar gbrp in dst_planar (plane 0 = G, 1 = B, 2 = R; uint8 for lut_depth 8, else uint16 LE), dst_packed unused.
+ * dst_kind == LUTR_PK_* / LUTR_PACKED(...): one packed image in dst_packed, dst_planar unused; lut_depth must be the format's
+ *   bits (8 | 16), else LUTR_EINVAL; the fourth component of a 4-component format is written 2^lut_depth - 1 (opaque).  16-bit
+ *   formats need 2-byte aligned rows.
+ * Depth: with range_src == range_in a source depth other than lut_depth is NOT a prologue here (so a tv source may change depth):
+ *   the change is folded into the input-stage constants (lutr_yuv_constants_yuv2rgb).  With range_src != range_in the prologue of
+ *   lutr_apply_yuv runs, on its terms (a pc source only), and lands at (lut_depth, range_in).
+ * row0 and rows must be multiples of the input chroma block height 2^icsy unless row0 + rows == h.
+ * Always strict precision (fast / fma32 run strict here, no suffix on the last kernel).
+ * Not in place: the bounding byte range of every source plane (all rows and frames) must be disjoint from that of every
+ * destination plane / the destination image (the rule of lutr_apply_yuv_sited), else LUTR_EINVAL before anything touches the device.
+ * Kernels: "k_yuv2rgb_vec<win,icsx,icsy,nc,wout,interp|nolut>" (nc = 1 planar, 3 | 4 packed components; nearest / trilinear /
+ * tetrahedral / no LUT; 8 -> 8, 16 -> 16 and 16 -> 8 bit containers; width a multiple of 8; positive strides; source planes
+ * aligned to the 8 (chroma: 8 >> icsx) samples a thread loads, planar destination planes to 8 samples, a packed image to 4 bytes;
+ * 3-component destinations in R G B or B G R order; row0 / rows multiples of 2^icsy), "k_yuv2rgb_generic" for everything else; a
+ * ragged width on aligned rows is split between the two.  Variants: auto and generic as for lutr_apply_yuv; vec_global fails with
+ * LUTR_EINVAL where the vector kernel cannot take the layout; vec_lds always fails with LUTR_EINVAL (there is no LDS kernel for
+ * this path).
+ * Not covered: chroma siting, dither, a resize, a float destination, alpha carried into a packed destination, a tile (LDS) kernel. */
+int lutr_apply_yuv_to_rgb(lutr_ctx *ctx, const lutr_yuv_params *p, int interp, int dst_kind, int w, int h, int nframes,
+                          const lutr_planes *src, const lutr_planes *dst_planar, const lutr_packed *dst_packed, int row0, int rows);
+/* The constant block lutr_apply_yuv_to_rgb uses.  With range_src == range_in, for s = 2^(din - 8), Mi = 2^din - 1,
+ * Ml = 2^lut_depth - 1 (formed in double, each entry rounded once):
+ *   tv: ky = Ml / (219 s), yoff = 16 s, kc = Ml / (224 s)      pc: ky = Ml / Mi, yoff = 0, kc = Ml / Mi
+ *   yb = -ky yoff + 0.5, coff = 128 s, krv = 2 (1 - kr) kc, kbu = 2 (1 - kb) kc, kgu = -2 kb (1 - kb) / kg kc,
+ *   kgv = -2 kr (1 - kr) / kg kc, max_l = Ml, pre = 0
+ * -- for din == lut_depth the input-stage entries of lutr_yuv_constants bit for bit; legal black gives code 0 and legal white Ml
+ * for every depth pair.  With range_src != range_in it is the block of lutr_yuv_constants for an output at (lut_depth, 4:4:4,
+ * matrix_in, range_in).  The output-stage entries are not read by the kernels.  Host only. */
+int lutr_yuv_constants_yuv2rgb(const lutr_yuv_params *p, float out[32]);
 
 /* ---- planar float RGB sources, gbrpf32le (what ffmpeg decodes an OpenEXR sequence to: lut3d's planar-float
  *      path on the frame itself, then format=<pix_fmt>, ffmpeg.py:246 and :304-310) ---- */

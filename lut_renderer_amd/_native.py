@@ -43,7 +43,7 @@ SYMBOLS = (
     "lutr_lattice_bytes", "lutr_lut_broadcast", "lutr_lut_broadcast_ex",
     "lutr_apply_planar_rgb", "lutr_apply_packed_rgb", "lutr_apply_yuv", "lutr_apply_yuv_dither",
     "lutr_apply_yuv_sited", "lutr_yuv_constants_sited", "lutr_apply_yuv_xsub", "lutr_yuv_constants_xsub",
-    "lutr_apply_rgb_to_yuv", "lutr_yuv_constants_rgb2yuv",
+    "lutr_apply_rgb_to_yuv", "lutr_yuv_constants_rgb2yuv", "lutr_apply_yuv_to_rgb", "lutr_yuv_constants_yuv2rgb",
     "lutr_apply_planar_rgb_f32", "lutr_apply_rgbf_to_yuv", "lutr_apply_yuv_semi", "lutr_apply_yuv_packed",
     "lutr_apply_yuv_dual", "lutr_apply_yuv_v210", "lutr_alpha_plane", "lutr_ctx_set_lut2", "lutr_apply_yuv_chain",
     "lutr_apply_yuv_premul", "lutr_apply_planar_rgb_f32_premul", "lutr_cdl_table", "lutr_apply_yuv_cdl",
@@ -233,6 +233,9 @@ def load() -> C.CDLL:
     lib.lutr_apply_rgb_to_yuv.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Packed),
                                           C.POINTER(Planes), ci, ci]
     lib.lutr_yuv_constants_rgb2yuv.argtypes = [C.POINTER(YuvParams), C.POINTER(C.c_float)]
+    lib.lutr_apply_yuv_to_rgb.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes),
+                                          C.POINTER(Packed), ci, ci]
+    lib.lutr_yuv_constants_yuv2rgb.argtypes = [C.POINTER(YuvParams), C.POINTER(C.c_float)]
     lib.lutr_apply_planar_rgb_f32.argtypes = [vp, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_apply_rgbf_to_yuv.argtypes = [vp, C.POINTER(YuvParams), ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes),
                                            ci, ci]

@@ -24,7 +24,8 @@ from typing import Dict, Optional, Sequence, Tuple
 from .cdl import as_cdl
 from .cube import CubeLut, as_lut1d, read_cube, read_lut, read_lut1d
 from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc, check_container_options,
-                      check_dual_options, check_lut1d_options, check_lut2, check_premul_options, check_stack_options, implied_stages, packed_frame_width, parse_packed_yuv_fmt,
+                      check_dual_options, check_lut1d_options, check_lut2, check_premul_options, check_stack_options,
+                      check_yuv2rgb_options, implied_stages, packed_frame_width, parse_packed_yuv_fmt,
                       parse_pix_fmt, parse_rgb_source, parse_semi_fmt, parse_size, parse_stages, parse_v210_fmt, premul_to_yuv,
                       refuse_alpha_resize, source_bit_depth, v210_frame_width, yuv_side)
 from .params import ProcessingParams, VideoInfo
@@ -84,7 +85,8 @@ def _cached_cube(path: Path, reader=read_lut) -> CubeLut:
     return lut
 
 
-def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = None, alpha_mode: str = "straight") -> dict:
+def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = None, alpha_mode: str = "straight",
+                    rgb_out: Optional[str] = None) -> dict:
     """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv (`pix_fmt` / `out_pix_fmt` planar YUV -- yuva* too, DESIGN.md
     3.16: without `out_pix_fmt` the source's format, alpha included, is kept; a named output without alpha drops it, one with alpha
     on a source without is filled opaque; the full-range prologue's default output stays the 8-bit yuv4xxp -- , semi-planar names
@@ -94,10 +96,28 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
     `pix_fmt` (gbrpf32le / gbrapf32le) without `out_pix_fmt`, or with a float one, stays float:
     `is_float_out_call(kw)`, and LutEngine.apply_rgb_float takes `kw["interp"]`.
     alpha_mode="premultiplied"  adds `alpha_mode` to the arguments of a yuva* -> planar YUV call or of a gbrapf32le
-    float call and is a ValueError for every other call; "straight" (the default) returns what it always returned."""
+    float call and is a ValueError for every other call; "straight" (the default) returns what it always returned.
+    `rgb_out` (gbrp .. gbrp16le, gbrap*, or a packed name) asks for an RGB output from a planar YUV `pix_fmt`: the
+    arguments are then those of LutEngine.apply_yuv_to_rgb (`is_rgb_out_call(kw)`), the LUT runs at that format's depth, and a plan
+    with the full-range prologue (which lands at 8 bit) takes an 8-bit `rgb_out` only.  Not together with `out_pix_fmt`."""
     if plan.interp not in _ENGINE_INTERP:
         raise ValueError(f"lut3d has no interpolation mode '{plan.interp}'")
     premul = check_alpha_mode(alpha_mode)
+    if rgb_out is not None:
+        if out_pix_fmt:
+            raise ValueError(f"rgb_out ('{rgb_out}') and out_pix_fmt ('{out_pix_fmt}') are mutually exclusive: a call has one output")
+        _fin, fout = check_yuv2rgb_options(pix_fmt, rgb_out, alpha_mode=alpha_mode)
+        kw = dict(pix_fmt=pix_fmt.replace("yuvj", "yuv"), out_pix_fmt=rgb_out, interp=plan.interp,
+                  matrix_in=plan.matrix or "smpte170m")
+        if plan.prologue:
+            # scale=in_range=pc:out_range=R, format=yuv4xxp (8 bit) ahead of lut3d: the LUT, and so the output, is at 8 bit
+            if fout.depth != 8:
+                raise ValueError(f"a source flagged full range is converted to 8 bit ahead of lut3d: it takes an 8-bit rgb_out "
+                                 f"(gbrp, rgb24, rgba, ..), not '{rgb_out}'")
+            kw.update(range_src="pc", range_in=plan.prologue_out_range)
+        else:
+            kw.update(range_src="tv", range_in="tv")
+        return kw
     rgb = parse_rgb_source(pix_fmt)
     if premul and rgb is not None:
         check_premul_options(pix_fmt, out_pix_fmt, to_yuv=premul_to_yuv(pix_fmt, out_pix_fmt))
@@ -193,6 +213,11 @@ def is_rgb_call(kw: dict) -> bool:
     return parse_rgb_source(kw.get("pix_fmt")) is not None
 
 
+def is_rgb_out_call(kw: dict) -> bool:
+    """True when `engine_call_for` returned arguments of `apply_yuv_to_rgb` (a YUV source with `rgb_out`)."""
+    return parse_rgb_source(kw.get("pix_fmt")) is None and parse_rgb_source(kw.get("out_pix_fmt")) is not None
+
+
 def is_float_out_call(kw: dict) -> bool:
     """True when `engine_call_for` returned a float source with a float output (LutEngine.apply_rgb_float)."""
     out = parse_rgb_source(kw.get("out_pix_fmt"))
@@ -280,7 +305,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
               cube2=None, interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None, cdl_id: Optional[str] = None,
               lut1d=None, interp1d: str = "linear", stages=None, strength=None, matte=None, matte_depth: Optional[int] = None,
-              matte_invert: bool = False):
+              matte_invert: bool = False, rgb_out: Optional[str] = None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -381,7 +406,16 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     size of the frame, [H,W] or [1,H,W] (a still for every frame) or [F,H,W], uint8 or int16 / uint16 with `matte_depth` (9..16);
     `matte_invert` takes Mm - a.  The strength of a pixel is `strength` (1 when not given) times its matte sample over Mm, applied
     in RGB ahead of the chroma mean.  It routes to the stack as a strength does, on the same terms, in messages that name the
-    matte.  None (default) leaves every route as it is; `matte_depth` / `matte_invert` without a matte are a ValueError."""
+    matte.  None (default) leaves every route as it is; `matte_depth` / `matte_invert` without a matte are a ValueError.
+
+    `rgb_out` (a DPX / TIFF / PNG pull, a review still, a preview) writes RGB from planar YUV frames in the same
+    pass: gbrp .. gbrp16le (three planes G, B, R come back), gbrap* (four, alpha from a yuva* source or opaque) or a packed name
+    such as rgb24, rgba, bgra, rgb48le, rgba64le (one [F,]H,W,C tensor, a fourth component opaque); `out` is then such planes or
+    such a tensor.  The LUT runs at that format's depth, as ffmpeg's `lut3d=...,format=<rgb fmt>` does; a source flagged full
+    range takes an 8-bit `rgb_out` only.  A LutEngineGroup row-shards it; always strict arithmetic.  Not together with
+    `out_pix_fmt`, and no dither, chroma_loc, resolution, premultiplied alpha, second output, second LUT, CDL, 1D LUT, stages,
+    strength or matte, nor a semi-planar / packed 4:2:2 / v210 source: each is a ValueError naming it.  None (default) leaves
+    every route as it is."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -415,6 +449,28 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     # (the plan only carries the path into the filter string / notes; a parsed CubeLut or an engine that already holds the
     # lattice has none)
     plan = resolve_lut_plan(params, cube if isinstance(cube, (str, Path)) else "engine.cube", info)
+    if rgb_out is not None:
+        # YUV in, RGB out: a route of its own, with none of the options below
+        kw = engine_call_for(plan, pix_fmt, out_pix_fmt, alpha_mode, rgb_out=rgb_out)
+        check_yuv2rgb_options(pix_fmt, rgb_out, chroma_loc=chroma_loc, engine_dither=engine_dither, out_size=out_size,
+                              dither="error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none",
+                              cdl=cdl, lut1d=lut1d, stages=stages, strength=strength, matte=matte, out2_pix_fmt=second_pix_fmt,
+                              cube2=cube2, interp2=interp2)
+        if precision not in ("strict", "fast", "fma32"):
+            raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
+        own = engine is None
+        eng = engine if engine is not None else _cached_engine(devices)
+        lut = None if cube is None else cube if isinstance(cube, CubeLut) else _cached_cube(Path(cube))
+        with eng._lock:             # upload, precision and launch of ONE task, as below
+            if lut is not None and eng._applied_lut is not lut:
+                eng.set_lut(lut)
+                eng._applied_lut = lut
+            if eng.precision != precision:
+                eng.set_precision(precision)
+            result = eng.apply_yuv_to_rgb(planes, out, **kw)
+            if own:
+                eng.sync()
+        return result, output_color_tags(plan.output_policy)
     kw = engine_call_for(plan, pix_fmt, out_pix_fmt, alpha_mode)
     refuse_alpha_resize(kw.get("out_pix_fmt"), out_size)        # (the resize takes three planes)
     # ffmpeg.py:305-307: any value other than "error_diffusion" leaves the chain without a dither filter

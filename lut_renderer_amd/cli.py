@@ -49,6 +49,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help="planar YUV (yuva* too: four planes, alpha last, kept unless --out-pix-fmt has none), semi-planar YUV (nv12, nv21, nv16, p010le .. p216le), packed 4:2:2 YUV (yuyv422, uyvy422, yvyu422, y210le, y212le, y216le), v210 (10-bit 4:2:2 in 32-bit words, rows of 128 * ceil(w / 48) bytes; in FFmpeg a codec / FourCC name, not a pix_fmt: its bytes are what `-c:v v210 -f rawvideo` writes), or an RGB source (gbrp* / gbrap* / rgb24, bgr24, rgba .., rgb48le, rgba64le) with a YUV --out-pix-fmt, "
                          "or float RGB (gbrpf32le / gbrapf32le): float out without --out-pix-fmt, else a YUV one")
     ap.add_argument("--out-pix-fmt", default=None)
+    ap.add_argument("--rgb-out", default=None, metavar="FMT",
+                    help="engine setting: write RGB from a planar YUV --pix-fmt in the same pass (DESIGN.md 3.24; ffmpeg's "
+                         "lut3d=...,format=FMT): gbrp .. gbrp16le or gbrap* (planes G, B, R[, A] back to back) or a packed name "
+                         "(rgb24, bgr24, rgba, bgra, argb, abgr, rgb48le, rgba64le, ..; a fourth component is opaque).  The LUT runs at "
+                         "FMT's depth; a full-range source takes an 8-bit FMT.  Not with --out-pix-fmt, dither, --chroma-loc, "
+                         "--out-size, --second-output, --cube2, --cdl, --lut1d, --stages, --strength, --matte or "
+                         "--alpha-mode premultiplied")
     ap.add_argument("--cube", default=None, help="the 3D LUT; required unless --lut1d is given (lut1d alone)")
     ap.add_argument("--interp", default="tetrahedral")
     ap.add_argument("--input-matrix", default="auto")
@@ -248,6 +255,20 @@ def plan_from_args(args):
         raise ValueError("--cube is required unless --lut1d is given")
     plan = resolve_lut_plan(params, args.cube if args.cube is not None else "engine.cube", info)
     alpha_mode = getattr(args, "alpha_mode", None) or "straight"
+    rgb_out = getattr(args, "rgb_out", None)
+    if rgb_out is not None:
+        # YUV in, RGB out: a route of its own, with none of the options below
+        from .formats import check_yuv2rgb_options
+        kw = engine_call_for(plan, args.pix_fmt, args.out_pix_fmt, alpha_mode, rgb_out=rgb_out)
+        second = getattr(args, "second_pix_fmt", None)
+        check_yuv2rgb_options(args.pix_fmt, rgb_out, chroma_loc=getattr(args, "chroma_loc", None),
+                              dither="error_diffusion" if args.zscale_dither == "error_diffusion" else "none",
+                              engine_dither=getattr(args, "engine_dither", None), out_size=getattr(args, "out_size", None),
+                              cdl=cdl_from_args(args), lut1d=lut1d, stages=stages, strength=getattr(args, "strength", None),
+                              strength_keys=getattr(args, "strength_keys", None), matte=getattr(args, "matte", None),
+                              out2_pix_fmt=second if second is not None else getattr(args, "second_output", None),
+                              cube2=getattr(args, "cube2", None), interp2=getattr(args, "interp2", None))
+        return plan, kw, w, h
     kw = engine_call_for(plan, args.pix_fmt, args.out_pix_fmt, alpha_mode)
     from .api import is_float_out_call
     engine_dither = getattr(args, "engine_dither", None)
@@ -362,13 +383,17 @@ def main(argv=None) -> int:
             eng.set_lut2(lut2)
         if args.lut1d is not None:
             eng.set_lut1d(read_lut1d(args.lut1d), args.interp1d)
+        from .api import is_rgb_out_call
+        rgb_out = kw["out_pix_fmt"] if is_rgb_out_call(kw) else None
         pix_fmt, out_fmt = kw.pop("pix_fmt"), kw.pop("out_pix_fmt")
+        if rgb_out is not None:
+            out_fmt = None
         second_fmt = kw.pop("out2_pix_fmt", None)
         if "matte" in kw:
             kw["matte"] = MatteReader(kw.pop("matte"), kw.pop("matte_pix_fmt"), w, h)
         pipe = HostPipeline(eng, pix_fmt, w, h, batch=args.batch, out_pix_fmt=out_fmt, out_size=args.out_size,
                             second_pix_fmt=second_fmt, chain=lut2 is not None and "stages" not in kw,
-                            lut1d=args.lut1d is not None and "stages" not in kw, **kw)
+                            lut1d=args.lut1d is not None and "stages" not in kw, rgb_out=rgb_out, **kw)
         fb = pipe.fin.frame_bytes
         if piped_in:
             total = None if args.duration is None else max(1, int(round(args.duration * args.fps)))

@@ -205,6 +205,45 @@ int make_yuv_consts_rgb2yuv(const lutr_yuv_params &p, YuvConsts *o)
     return yuv_consts_n(q, 1 << (LUTR_FMT_CSX(p.fmt_out) + LUTR_FMT_CSY(p.fmt_out)), o);
 }
 
+// a YUV source converted to integer RGB at lut_depth, the depth of the RGB destination.  Only the input side
+// enters the kernels; fmt_out, matrix_out and range_out are ignored (the block's output-stage entries are those of a 4:4:4 output
+// at lut_depth with the input side's matrix and range, so that the call cannot fail on them).  With range_src != range_in the
+// block is yuv_consts_n's: the prologue of a full-range source lands at (lut_depth, range_in).  Otherwise a depth change is no
+// prologue here (yuv_consts_n refuses one for a tv source): it is folded into the input-stage entries, each formed in double and
+// rounded once.  For din == lut_depth these are yuv_consts_n's entries bit for bit (pc: Ml / Mi is exactly 1).
+int make_yuv_consts_yuv2rgb(const lutr_yuv_params &p, YuvConsts *o)
+{
+    const int din = LUTR_FMT_DEPTH(p.fmt_in), dl = p.lut_depth;
+    lutr_yuv_params q = p;
+    q.fmt_out = LUTR_FMT(dl & 0xff, 0, 0);
+    q.matrix_out = p.matrix_in;
+    q.range_out = p.range_in;
+    if (p.range_src != p.range_in) return yuv_consts_n(q, 1, o);
+    if (din < 8 || din > 16) {
+        set_error("unsupported bit depth (in %d, lut %d)", din, dl);
+        return LUTR_EINVAL;
+    }
+    q.fmt_in = LUTR_FMT(dl & 0xff, LUTR_FMT_CSX(p.fmt_in), LUTR_FMT_CSY(p.fmt_in));
+    if (const int rc = yuv_consts_n(q, 1, o)) return rc;
+    double kr, kb;
+    matrix_k(p.matrix_in, &kr, &kb);                      // (checked by yuv_consts_n)
+    const double kg = 1.0 - kr - kb;
+    const double s = (double)(1 << (din - 8));
+    const double mi = (double)((1 << din) - 1), ml = (double)((1 << dl) - 1);
+    double ky, yoff, kc;
+    if (p.range_in == LUTR_RANGE_TV) { ky = ml / (219.0 * s); yoff = 16.0 * s; kc = ml / (224.0 * s); }
+    else { ky = ml / mi; yoff = 0.0; kc = ml / mi; }
+    o->ky = (float)ky;
+    o->yb = (float)(-ky * yoff + 0.5);
+    o->coff = (float)(128.0 * s);
+    o->krv = (float)(2.0 * (1.0 - kr) * kc);
+    o->kbu = (float)(2.0 * (1.0 - kb) * kc);
+    o->kgu = (float)(-2.0 * kb * (1.0 - kb) / kg * kc);
+    o->kgv = (float)(-2.0 * kr * (1.0 - kr) / kg * kc);
+    o->max_l = (float)ml;
+    return LUTR_OK;
+}
+
 
 // ---------------------------------------------------------------- output resize tables
 // The bicubic of libswscale's SWS_BICUBIC defaults (B = 0, C = 0.6).  Evaluated in this exact order: tests/_resize_twin.py
@@ -452,6 +491,11 @@ int lutr_yuv_constants_xsub(const lutr_yuv_params *p, float out[32])
 int lutr_yuv_constants_rgb2yuv(const lutr_yuv_params *p, float out[32])
 {
     return export_consts("lutr_yuv_constants_rgb2yuv", p, out, [&](YuvConsts *k) { return make_yuv_consts_rgb2yuv(*p, k); });
+}
+
+int lutr_yuv_constants_yuv2rgb(const lutr_yuv_params *p, float out[32])
+{
+    return export_consts("lutr_yuv_constants_yuv2rgb", p, out, [&](YuvConsts *k) { return make_yuv_consts_yuv2rgb(*p, k); });
 }
 
 int lutr_ctx_create(int device, lutr_ctx **out)
@@ -2136,6 +2180,62 @@ int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
     FloatPlanes F;
     if (const int rc = dither_scratch(c, G, ocsx, ocsy, &F)) return rc;
     return finish_launch(c, launch_rgb2yuv_dither(c->stream, L, K, P, Y, G, F, dout, ocsx, ocsy, interp));
+}
+
+int lutr_apply_yuv_to_rgb(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dst_kind, int w, int h, int nframes,
+                          const lutr_planes *src, const lutr_planes *dst_planar, const lutr_packed *dst_packed, int row0, int rows)
+{
+    const bool packed = dst_kind != 0;
+    const void *dst = packed ? (const void *)dst_packed : (const void *)dst_planar;
+    int rc = check_common(c, interp, LUTR_INTERP_NONE, w, h, nframes, src, dst, row0, rows);
+    if (rc) return rc;
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    YuvConsts K;
+    rc = make_yuv_consts_yuv2rgb(*p, &K);
+    if (rc) return rc;
+    const int din = LUTR_FMT_DEPTH(p->fmt_in), dl = p->lut_depth;
+    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
+    RgbLayout Y{1, dl > 8, 0, 0, 0};
+    if (packed) {
+        PackedFmt f;
+        if (const int rc = decode_packed(dst_kind, &f)) return rc;
+        if (dl != f.bits) { set_error("lut_depth %d must be the packed destination's depth %d", dl, f.bits); return LUTR_EINVAL; }
+        Y = RgbLayout{f.nc, f.bits == 16, f.ro, f.go, f.bo};
+    }
+    const int bh = 1 << icsy;
+    if (const int rc = check_row_blocks(row0, rows, h, bh, "chroma block height")) return rc;
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    if (const int rc = check_planes_set(src, nullptr)) return rc;
+    // destination streams in R, G, B order: gbrp planes are G, B, R
+    PlaneSet P{};
+    const long long bso = Y.wide ? 2 : 1;
+    for (int i = 0; i < 3; i++) { P.s[i] = (const uint8_t *)src->data[i]; P.ss[i] = src->stride[i]; P.sfs[i] = src->frame_stride[i]; }
+    if (packed) {
+        if (!dst_packed->data) { set_error("null image"); return LUTR_EINVAL; }
+        if (Y.wide && !check_aligned(dst_packed->data, dst_packed->stride, dst_packed->frame_stride, nframes, 1)) {
+            set_error("16-bit packed formats need 2-byte aligned rows");
+            return LUTR_EINVAL;
+        }
+        for (int k = 0; k < 3; k++) { P.d[k] = (uint8_t *)dst_packed->data; P.ds[k] = dst_packed->stride; P.dfs[k] = dst_packed->frame_stride; }
+    } else {
+        for (int k = 0; k < 3; k++) {
+            const int f = kGbrpToRgb[k];
+            P.d[k] = (uint8_t *)dst_planar->data[f]; P.ds[k] = dst_planar->stride[f]; P.dfs[k] = dst_planar->frame_stride[f];
+            if (!P.d[k]) { set_error("null plane %d", f); return LUTR_EINVAL; }
+        }
+    }
+    // the two sides differ in size and layout: a thread's stores would land on samples another thread has yet to read
+    Span ss[3], ds[3];
+    planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
+    for (int i = 0; i < 3; i++) ds[i] = plane_span(P.d[i], P.ds[i], P.dfs[i], h, (long long)w * Y.step * bso, nframes);
+    if (const int rc = check_disjoint("YUV -> RGB", true, ss, 3, ds, packed ? 1 : 3)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
+    LutConsts L{};
+    FrameGeom G{w, h, row0, rows, nframes};
+    if (interp != LUTR_INTERP_NONE)
+        if (const int rc = fill_lut(&L, c, dl)) return rc;
+    return finish_launch(c, launch_yuv2rgb(c->stream, c->variant, L, K, P, Y, G, din, icsx, icsy, interp));
 }
 
 // gbrpf32 planes hold 4-byte samples: base pointers, row strides and (batches) frame strides must be multiples of 4

@@ -369,6 +369,20 @@ const char *launch_rgb2yuv_dither(hipStream_t st, const LutConsts &L, const YuvC
 const char *launch_rgb2yuv_bn(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
                               const RgbLayout &Y, const FrameGeom &G, const float *bn, int dout, int ocsx, int ocsy, int mode);
 
+// YUV source -> RGB output (lutr_yuv2rgb.hip).  PlaneSet::s is Y, Cb, Cr at depth din in the layout icsx, icsy; the
+// destination travels in PlaneSet::d as three component streams in R, G, B order, described by Y as the source of launch_rgb2yuv
+// is (planar = the three planes; packed = the image's base three times; the fourth component of a 4-component image is written
+// K.max_l).  mode: LUTR_INTERP_*, or -1 = no lut3d.  nullptr = the variant cannot take the call (vec_lds always; vec_global on
+// layouts the vector kernel cannot take)
+const char *launch_yuv2rgb(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,
+                           const RgbLayout &Y, const FrameGeom &G, int din, int icsx, int icsy, int mode);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>): nullptr = not a layout / mode it has
+#define LUTR_Y2R_DECL(tag) \
+    const char *launch_yuv2rgb_vec_##tag(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, \
+                                         const RgbLayout &Y, const FrameGeom &G, int icsx, int icsy, int mode);
+LUTR_Y2R_DECL(w00) LUTR_Y2R_DECL(w11) LUTR_Y2R_DECL(w10)
+#undef LUTR_Y2R_DECL
+
 // planar float RGB sources (lutr_rgbf.hip): gbrpf32 planes in PlaneSet::s in R, G, B order.  No per-code
 // coordinate table exists for a float input, so lut3d's prelut travels as the raw table lutr_ctx_set_prelut was given and is
 // applied per pixel (FFmpeg's prelut_interp_1d_linear); LutConsts::pre is not read by these kernels.
@@ -500,6 +514,7 @@ int make_yuv_consts(const lutr_yuv_params &p, YuvConsts *out);
 int make_yuv_consts_xsub(const lutr_yuv_params &p, YuvConsts *out);
 int make_yuv_consts_sited(const lutr_yuv_params &p, int chroma_loc, YuvConsts *out);
 int make_yuv_consts_rgb2yuv(const lutr_yuv_params &p, YuvConsts *out);
+int make_yuv_consts_yuv2rgb(const lutr_yuv_params &p, YuvConsts *out);
 void set_error(const char *fmt, ...);
 
 }  // namespace lutr

@@ -24,7 +24,7 @@ from .cube import CubeLut, Lut1D, read_cube, read_lut, read_lut1d
 # (the formats and the checks of names and options live in formats.py; the names callers have always imported from here stay)
 from .formats import (_ALPHA_RESIZE, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, V210Fmt, chain_interp, chain_side,  # noqa: F401
                       changes_subsampling, check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc,
-                      check_lut1d_options, check_matte, check_stack_options, check_strength,
+                      check_lut1d_options, check_matte, check_stack_options, check_strength, check_yuv2rgb_options,
                       check_container_options,
                       check_dual_options, check_lut2, check_packed_options, check_premul_options, check_semi_options,
                       chroma_loc_code, dual_side, has_prologue, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt,
@@ -130,6 +130,7 @@ _STACK_IN_PLACE = "the stack pass cannot run in place: destination planes must n
 _LUT1D_IN_PLACE = "the lut1d pass cannot run in place: destination planes must not overlap the source planes"
 _RESIZE_IN_PLACE = "a resize cannot run in place: destination planes must not overlap the source planes"
 _RGB2YUV_IN_PLACE = "RGB -> YUV cannot run in place: destination planes must not overlap the source"
+_YUV2RGB_IN_PLACE = "YUV -> RGB cannot run in place: the destination must not overlap the source planes"
 
 
 def _check_not_in_place(src: Sequence[torch.Tensor], dst: Sequence[torch.Tensor], message: str) -> None:
@@ -1275,6 +1276,69 @@ class LutEngine:
                 row0, rows))
         return dst
 
+    # -- YUV source, RGB output --------------------------------
+    def apply_yuv_to_rgb(self, src: Sequence[torch.Tensor], dst=None, *, pix_fmt: str, out_pix_fmt: str,
+                         interp: str = "tetrahedral", matrix_in: str = "bt709", range_src: str = "tv",
+                         range_in: Optional[str] = None, row0: int = 0, rows: Optional[int] = None, lut: bool = True, **refused):
+        """Planar YUV frames (Y, Cb, Cr; `pix_fmt` 4:2:0 / 4:2:2 / 4:4:4 at 8..16 bit) -> integer RGB -> lut3d -> stored as RGB, in
+        one pass (ffmpeg's `lut3d=...,format=<rgb fmt>`).  `out_pix_fmt` is gbrp .. gbrp16le (three planes G, B, R
+        come back), gbrap* (four: alpha last) or a name of `_native.PACKED_FORMATS` (one [F,]H,W,C tensor; a fourth component is
+        written opaque).  The LUT runs at the OUTPUT's depth; a source of another depth is converted inside the matrix constants
+        (range_src == range_in), or by the full-range prologue (range_src="pc" with another range_in).  Source chroma is
+        replicated over its block; always strict arithmetic; not in place.  `dst` is allocated when none is given: uint8 up to 8
+        bit, int16 above.  A yuva* source carries its alpha into gbrap* (converted to the output depth; filled opaque for a
+        yuv* source or a prologue call), drops it for a 3-component output, and is a ValueError for a 4-component packed one.
+        lut=False leaves lut3d out.  chroma_loc, dither, out_size, alpha_mode="premultiplied", cdl, lut1d, stages, strength,
+        matte, a second output, a second LUT and semi-planar / packed 4:2:2 / v210 sources are each a ValueError naming it."""
+        fin, fout = check_yuv2rgb_options(pix_fmt, out_pix_fmt, **refused)
+        if interp not in _native.INTERP:
+            raise ValueError(f"lut3d has no interpolation mode '{interp}'")
+        if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
+            raise ValueError(_PLANE_COUNT[fin.nplanes].format(fin.name))
+        if not isinstance(src[0], torch.Tensor):
+            raise TypeError(_NOT_TENSORS)
+        h, w = src[0].shape[-2], src[0].shape[-1]
+        _check_planes(src, fin, w, h, "source")
+        lead = tuple(src[0].shape[:-2])
+        odt = torch.uint8 if fout.depth <= 8 else torch.int16
+        packed = isinstance(fout, RgbSource)
+        s, nf = _planes_struct(src[:3], self.device)
+        if packed:
+            if dst is None:
+                dst = torch.empty(lead + (h, w, fout.ncomp), dtype=odt, device=self.device)
+            d = _packed_struct(dst, fout.name, fout.ncomp, fout.depth, self.device, True)
+            if tuple(dst.shape[-3:-1]) != (h, w):
+                raise ValueError(f"the destination image is {tuple(dst.shape[-3:-1])}, the frame is {(h, w)}")
+            nfd = dst.shape[0] if dst.dim() == 4 else 1
+        else:
+            if dst is None:
+                dst = _new_planes(fout, w, h, lead, odt, self.device)
+            _check_planes(dst, fout, w, h, "destination")
+            d, nfd = _planes_struct(dst[:3], self.device)
+        if nf != nfd:
+            raise ValueError("src and dst disagree on the number of frames")
+        _check_not_in_place(src[:3], [dst] if packed else dst[:3], _YUV2RGB_IN_PLACE)
+        rin = range_in or range_src
+        p = _yuv_params(fin.colour.code, _native.fmt_code(fout.depth, 0, 0), fout.depth, matrix_in, matrix_in, range_src, rin, rin)
+        mode = _native.INTERP[interp] if lut else _native.INTERP_NONE
+        nrows = h - row0 if rows is None else rows
+
+        def colour():
+            self._bind_stream()
+            _native.check(self._lib.lutr_apply_yuv_to_rgb(
+                self._ctx, C.byref(p), mode, fout.code if packed else 0, w, h, nf, C.byref(s), None if packed else C.byref(d),
+                C.byref(d) if packed else None, row0, nrows))
+
+        if not packed and fout.alpha:
+            # gbrap*: the colour planes, then the alpha plane on the same stream (DESIGN.md 3.16); a prologue call fills
+            a_src = src[3] if fin.alpha and rin == range_src else None
+            _check_alpha_overlap(a_src, fin.depth, dst, fout.depth)
+            self._alpha_tail(colour, [(fout, dst)], a_src, fin.depth, w, h, row0, rows)
+        else:
+            with self._lock:
+                colour()
+        return dst
+
     def apply_rgb_full_range(self, src, dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: str,
                              intermediate_pix_fmt: str, prologue_out_range: Optional[str], matrix: Optional[str],
                              interp: str = "tetrahedral", range_out: str = "tv", row0: int = 0, rows: Optional[int] = None,
@@ -1329,6 +1393,12 @@ def yuv_constants_xsub(**kw) -> np.ndarray:
 def yuv_constants_rgb2yuv(**kw) -> np.ndarray:
     """The constant block of `apply_rgb_to_yuv` (lutr_yuv_constants_rgb2yuv): fmt_out, lut_depth, matrix_out and range_out count."""
     return _yuv_constants("lutr_yuv_constants_rgb2yuv", **kw)
+
+
+def yuv_constants_yuv2rgb(**kw) -> np.ndarray:
+    """The constant block of `apply_yuv_to_rgb` (lutr_yuv_constants_yuv2rgb): fmt_in, lut_depth, matrix_in, range_src and range_in
+    count."""
+    return _yuv_constants("lutr_yuv_constants_yuv2rgb", **kw)
 
 
 def yuv_constants_sited(chroma_loc: Optional[str], **kw) -> np.ndarray:

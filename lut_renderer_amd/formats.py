@@ -873,3 +873,62 @@ def refuse_alpha_resize(out_pix_fmt: Optional[str], out_size) -> None:
         return
     if fmt.alpha:
         raise ValueError(_ALPHA_RESIZE.format(out_pix_fmt))
+
+
+# ---------------------------------------------------------------- YUV in, RGB out
+def parse_rgb_out(name: Optional[str]):
+    """The RGB destination `name` of `LutEngine.apply_yuv_to_rgb`: a `PixFmt` of the gbr family (gbrp .. gbrp16le, gbrap*: three
+    or four planes) or a packed `RgbSource` (a name of `_native.PACKED_FORMATS`: one [F,]H,W,C image).  ValueError for every
+    other name, a float one included."""
+    rgb = parse_rgb_source(name)
+    if rgb is None:
+        raise ValueError(f"'{name}' is not an RGB output format (gbrp .. gbrp16le, gbrap*, or a packed name such as rgb24, "
+                         f"rgba, rgb48le)")
+    if rgb.floating:
+        raise ValueError(f"a float output ('{name}') from a YUV source is not supported: the LUT runs on integer codes at the "
+                         f"output's depth")
+    return rgb if rgb.packed else parse_pix_fmt(name)
+
+
+#: what `apply_yuv_to_rgb` does not take, by keyword -> (its neutral value, what the refusal calls it)
+_YUV2RGB_NOT_TAKEN = {
+    "chroma_loc": (None, "sited chroma resampling (chroma_loc)"), "dither": ("none", "dither"),
+    "engine_dither": (None, "dither (engine_dither)"), "out_size": (None, "a resize (out_size / resolution)"),
+    "resize_chunk": (None, "a resize (out_size / resolution)"),
+    "alpha_mode": ("straight", "alpha_mode='premultiplied'"), "cdl": (None, "an ASC CDL (cdl)"), "lut1d": (None, "a 1D LUT (lut1d)"),
+    "stages": (None, "a stage stack (stages)"), "strength": (None, "a LUT strength (strength)"),
+    "strength_keys": (None, "a LUT strength (strength_keys)"), "matte": (None, "a matte (matte)"),
+    "out2_pix_fmt": (None, "a second output (out2_pix_fmt / second_pix_fmt)"), "cube2": (None, "a second LUT (cube2)"),
+    "lut2": (False, "a second LUT (cube2)"), "interp2": (None, "a second LUT (interp2)"),
+}
+
+
+def check_yuv2rgb_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str], **options):
+    """The checks every layer makes of a YUV -> RGB call before any GPU work: a planar YUV source (yuva* too)
+    and an RGB destination; ValueError, naming it, for every option the pass does not take (`_YUV2RGB_NOT_TAKEN`: a keyword at its
+    neutral value passes), for a semi-planar, packed 4:2:2 or v210 source, and for alpha into a 4-component packed destination;
+    TypeError for a keyword nothing knows.  Returns (source `PixFmt`, destination `PixFmt` | packed `RgbSource`)."""
+    head = "YUV in with RGB out (apply_yuv_to_rgb)"
+    for k, v in options.items():
+        if k not in _YUV2RGB_NOT_TAKEN:
+            raise TypeError(f"apply_yuv_to_rgb() got an unexpected keyword argument '{k}'")
+        neutral, what = _YUV2RGB_NOT_TAKEN[k]
+        if (v is not None) if neutral is None else (v != neutral):
+            raise ValueError(f"{what} is not supported with {head}")
+    if not pix_fmt:
+        raise ValueError(f"{head} needs pix_fmt")
+    name = pix_fmt.replace("yuvj", "yuv")
+    if parse_semi_fmt(name) is not None:
+        raise ValueError(f"{head} takes planar YUV sources: '{pix_fmt}' is a semi-planar container")
+    if parse_packed_yuv_fmt(name) is not None or name in _PACKED_YUV_UNSUPPORTED:
+        raise ValueError(f"{head} takes planar YUV sources: '{pix_fmt}' is a packed 4:2:2 container")
+    if parse_v210_fmt(name) is not None:
+        raise ValueError(f"{head} takes planar YUV sources: '{pix_fmt}' is a v210 container")
+    if parse_rgb_source(name) is not None:
+        raise ValueError(f"{head} takes planar YUV sources: '{pix_fmt}' is an RGB format (use apply_rgb / apply_packed)")
+    fin = parse_pix_fmt(name)
+    fout = parse_rgb_out(out_pix_fmt)
+    if fin.alpha and isinstance(fout, RgbSource) and fout.ncomp == 4:
+        raise ValueError(f"alpha from '{pix_fmt}' into the packed destination '{out_pix_fmt}' is not supported yet (a follow-up): "
+                         f"use gbrap* to carry alpha, or a yuv* name / a 3-component destination to drop it")
+    return fin, fout

@@ -29,7 +29,7 @@ import torch
 from . import _native
 from .cube import CubeLut, read_lut, read_lut1d
 from .engine import LutEngine, _fresh_planes, _new_planes, _yuv_out_dtype, chain_args, dual_args
-from .formats import (check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2, check_matte, check_stack_options, check_strength,
+from .formats import (RgbSource, check_yuv2rgb_options, check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2, check_matte, check_stack_options, check_strength,
                       check_premul_options,
                       packed_frame_width, parse_pix_fmt, parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords,
                       v210_frame_width, yuv_side)
@@ -459,4 +459,37 @@ class LutEngineGroup:
                 return [(dst, *_crop(full, fout, s0, r0, r1))]
 
             self._shard(h, 1 << csy, home, local, remote)
+            return dst
+
+    def apply_yuv_to_rgb(self, src: Sequence[torch.Tensor], dst=None, *, pix_fmt: str, out_pix_fmt: str, **kw):
+        """`LutEngine.apply_yuv_to_rgb` with the rows of every frame split over the group's devices: shards on
+        multiples of the source's chroma block height, the source's chroma rows counted in its own layout, every destination
+        plane (or the packed image) in luma rows, alpha rows with the luma rows; no halo."""
+        with self._lock:
+            if "row0" in kw or "rows" in kw:
+                raise ValueError("the group owns the row partition")
+            fin, fout = check_yuv2rgb_options(pix_fmt, out_pix_fmt, **{k: v for k, v in kw.items() if k not in (
+                "interp", "matrix_in", "range_src", "range_in", "lut")})
+            if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
+                raise ValueError(f"'{fin.name}' takes {fin.nplanes} planes")
+            h, w = src[0].shape[-2], src[0].shape[-1]
+            home = src[0].device
+            lead = tuple(src[0].shape[:-2])
+            packed = isinstance(fout, RgbSource)
+            odt = torch.uint8 if fout.depth <= 8 else torch.int16
+            if dst is None:
+                dst = torch.empty(lead + (h, w, fout.ncomp), dtype=odt, device=home) if packed else \
+                    _new_planes(fout, w, h, lead, odt, home)
+            names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt)
+
+            def local(eng, r0, r1):
+                eng.apply_yuv_to_rgb(src, dst, row0=r0, rows=r1 - r0, **names, **kw)
+
+            def remote(eng, r0, r1):
+                out = eng.apply_yuv_to_rgb(_travel(src, _row_ranges(fin, r0, r1), eng.device), None, **names, **kw)
+                if packed:                                         # (rows of w * C components: a plane to the copy back)
+                    return [([dst.flatten(-2)], [out.flatten(-2)], [(r0, r1)])]
+                return [(dst, out, _row_ranges(fout, r0, r1))]
+
+            self._shard(h, 1 << fin.csy, home, local, remote)
             return dst

@@ -24,7 +24,8 @@ from .engine import LutEngine
 from .params import strength_keys
 from .formats import (MATTE_PIX_FMTS, RgbSource, check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options,
                       check_lut1d_options, check_stack_options,
-                      check_premul_options, parse_rgb_source, parse_size, premul_to_yuv, refuse_alpha_resize, yuv_side)
+                      check_premul_options, check_yuv2rgb_options, parse_rgb_out, parse_rgb_source, parse_size, premul_to_yuv,
+                      refuse_alpha_resize, yuv_side, _YUV2RGB_NOT_TAKEN)
 
 
 @dataclass
@@ -71,7 +72,8 @@ def yuv_layout(pix_fmt: str, width: int, height: int) -> FrameLayout:
 
 @dataclass
 class PackedFrameLayout:
-    """Byte layout of one packed RGB frame in a rawvideo stream: h x w pixels of `ncomp` components (input side only)."""
+    """Byte layout of one packed RGB frame in a rawvideo stream: h x w pixels of `ncomp` components.  The input side of an RGB
+    source, and the output side of a YUV source with an RGB output."""
     fmt: RgbSource
     width: int
     height: int
@@ -124,6 +126,13 @@ def input_layout(pix_fmt: str, width: int, height: int):
     if rgb is not None and rgb.floating:
         return FloatFrameLayout(rgb, width, height)
     return yuv_layout(pix_fmt, width, height)
+
+
+def output_layout(pix_fmt: str, width: int, height: int):
+    """The layout of a rawvideo RGB output: `PackedFrameLayout` for a packed name, `FrameLayout` for gbrp* /
+    gbrap* (planes G, B, R[, A] back to back: ffmpeg's rawvideo order)."""
+    fmt = parse_rgb_out(pix_fmt)
+    return PackedFrameLayout(fmt, width, height) if isinstance(fmt, RgbSource) else FrameLayout(fmt, width, height)
 
 
 def dual_layout(pix_fmt: str, out_pix_fmt: Optional[str], second_pix_fmt: Optional[str], width: int, height: int, out_size=None,
@@ -186,7 +195,8 @@ class HostPipeline:
     """Apply the LUT to batches of host frames with copies overlapped against compute."""
 
     def __init__(self, engine: LutEngine, pix_fmt: str, width: int, height: int, batch: int = 8, slots: int = 3,
-                 out_pix_fmt: Optional[str] = None, out_size=None, second_pix_fmt: Optional[str] = None, chain: bool = False, lut1d: bool = False, **apply_kw):
+                 out_pix_fmt: Optional[str] = None, out_size=None, second_pix_fmt: Optional[str] = None, chain: bool = False, lut1d: bool = False,
+                 rgb_out: Optional[str] = None, **apply_kw):
         """`out_size` = (w, h) or "WxH": the engine resizes every frame to it and the output layout has that size.
         `second_pix_fmt`: a second planar YUV output from the same pass with a pinned output ring of its own
         (`fout2`); `run` then takes a second drain.
@@ -199,6 +209,16 @@ class HostPipeline:
         # across the batches
         # `apply_kw["matte"]` (a `MatteReader`) scales the strength per pixel: a still is uploaded once, a matte
         # per frame is read and uploaded with every input batch; `apply_kw["matte_invert"]` travels to the engine
+        # `rgb_out`: a planar YUV source written as RGB -- gbrp* / gbrap* planes or a packed image -- through
+        # `apply_yuv_to_rgb`; the output ring has that layout (`output_layout`).  Not with `out_pix_fmt` or anything the pass refuses
+        self.rgb_out = rgb_out is not None
+        if self.rgb_out:
+            if out_pix_fmt:
+                raise ValueError(f"rgb_out ('{rgb_out}') and out_pix_fmt ('{out_pix_fmt}') are mutually exclusive")
+            check_yuv2rgb_options(pix_fmt, rgb_out, out_size=out_size, out2_pix_fmt=second_pix_fmt, lut2=bool(chain),
+                                  lut1d=True if lut1d else None,
+                                  **{k: v for k, v in apply_kw.items() if k in _YUV2RGB_NOT_TAKEN and k not in ("out_size", "lut1d")})
+            apply_kw = {k: v for k, v in apply_kw.items() if k not in _YUV2RGB_NOT_TAKEN}
         stages = apply_kw.get("stages")
         self.stack = stages is not None
         self.matte = apply_kw.pop("matte", None)
@@ -276,6 +296,8 @@ class HostPipeline:
             if out_size is not None or out_rgb.nplanes > src_rgb.nplanes:
                 raise ValueError("a float output takes no out_size and cannot add an alpha plane")
             self.fout = FloatFrameLayout(out_rgb, ow, oh)
+        elif self.rgb_out:
+            self.fout = output_layout(rgb_out, ow, oh)
         else:
             self.fout = yuv_layout(out_pix_fmt or pix_fmt, ow, oh)
         self.batch, self.slots = int(batch), int(slots)
@@ -355,8 +377,11 @@ class HostPipeline:
             self.e_in[slot].record()
         with torch.cuda.stream(self.s_run):
             self.s_run.wait_event(self.e_in[slot])
-            dst = self.fout.plane_views(self.d_out[slot], nframes)
-            if self.stack:
+            dst = self.fout.image_view(self.d_out[slot], nframes) if isinstance(self.fout, PackedFrameLayout) \
+                else self.fout.plane_views(self.d_out[slot], nframes)
+            if self.rgb_out:
+                self.eng.apply_yuv_to_rgb(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
+            elif self.stack:
                 self._run_stack(self.fin.plane_views(self.d_in[slot], nframes), dst, nframes, matte)
             elif self.lut1d:
                 self.eng.apply_yuv_lut1d(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
