@@ -913,6 +913,15 @@ int lutr_ctx_lut_device(lutr_ctx *c, void **dptr, size_t *bytes)
     return LUTR_OK;
 }
 
+static int check_geometry(int w, int h, int nframes, int row0, int rows)
+{
+    if (w < 0 || h < 0 || nframes < 0 || row0 < 0 || rows < 0 || row0 + rows > h) {
+        set_error("bad geometry w=%d h=%d nframes=%d row0=%d rows=%d", w, h, nframes, row0, rows);
+        return LUTR_EINVAL;
+    }
+    return LUTR_OK;
+}
+
 // min_interp: the lowest legal mode -- LUTR_INTERP_NEAREST, or LUTR_INTERP_NONE where the entry point can leave lut3d out
 // (no lattice is needed for that mode then)
 static int check_common(lutr_ctx *c, int interp, int min_interp, int w, int h, int nframes, const void *src, const void *dst,
@@ -927,11 +936,7 @@ static int check_common(lutr_ctx *c, int interp, int min_interp, int w, int h, i
         set_error("unknown interpolation mode %d", interp);
         return LUTR_EINVAL;
     }
-    if (w < 0 || h < 0 || nframes < 0 || row0 < 0 || rows < 0 || row0 + rows > h) {
-        set_error("bad geometry w=%d h=%d nframes=%d row0=%d rows=%d", w, h, nframes, row0, rows);
-        return LUTR_EINVAL;
-    }
-    return LUTR_OK;
+    return check_geometry(w, h, nframes, row0, rows);
 }
 
 // every plane of a (and of b, when given) has a base pointer
@@ -1030,7 +1035,8 @@ static const float4 *fma32_lattice(lutr_ctx *c, int depth)
     return derived_lattice(c, &c->latm[depth - 8], depth, launch_make_latm);
 }
 
-// the lattice side of LutConsts (everything but the prelut's per-code table)
+// the lattice side of LutConsts (everything but the prelut's per-code table).  Every entry but lutr_apply_yuv is always strict:
+// the fast / fma32 lattices are left unset here and in fill_lut, and no kernel of the other paths reads them
 static void fill_lattice(LutConsts *L, lutr_ctx *c, int depth)
 {
     const int maxi = (1 << depth) - 1;
@@ -1057,6 +1063,20 @@ static int fill_lut(LutConsts *L, lutr_ctx *c, int depth)
     L->pre_gen = t->gen;
     fill_lattice(L, c, depth);
     return LUTR_OK;
+}
+
+// The second lattice (lutr_ctx_set_lut2) at `depth`: its own size and scale, no prelut (pre stays null), never the clip-free path
+static LutConsts second_lattice(const lutr_ctx *c, int depth)
+{
+    LutConsts L{};
+    const int maxi = (1 << depth) - 1;
+    L.lat = c->lat2;
+    L.n1 = c->n2 + 1;
+    L.maxf = (float)maxi;
+    L.scale_f = 1.0f / (float)maxi;
+    L.lut_max = (float)(c->n2 - 1);
+    for (int i = 0; i < 3; i++) L.sc[i] = c->scale2[i] * L.lut_max;
+    return L;
 }
 
 // The float path's constants: the lattice (at depth 16, which only sets fields these kernels do not read) and the prelut as the
@@ -1195,6 +1215,106 @@ static int check_disjoint(const char *what, bool name_src, const Span *s, int ns
     return LUTR_OK;
 }
 
+// One side of a call: the name the messages give it, its planes, and the depth and chroma layout of its format code (depth 32:
+// the float samples of gbrpf32).
+// packed: the side is one plane (a packed 4:2:2 or v210 container) of packed_row bytes a row, not three planes.
+struct Side { const char *name; const lutr_planes *pl; int depth, csx, csy; bool packed; long long packed_row; };
+
+static Side planar_side(const char *name, const lutr_planes *pl, int fmt)
+{
+    return Side{name, pl, LUTR_FMT_DEPTH(fmt), LUTR_FMT_CSX(fmt), LUTR_FMT_CSY(fmt), false, 0};
+}
+
+// Samples above 8 bit are 16-bit words: the base pointer, row stride and frame stride of plane i are even.  `held` is what holds
+// them in the entry's message ("planes" | "containers"); this is the only place that message is formatted.
+static int check_plane_aligned(const Side &s, int i, int nframes, const char *held)
+{
+    if (s.depth > 8 && !check_aligned(s.pl->data[i], s.pl->stride[i], s.pl->frame_stride[i], nframes, 1)) {
+        set_error("%s plane %d: 16-bit %s need 2-byte aligned rows", s.name, i, held);
+        return LUTR_EINVAL;
+    }
+    return LUTR_OK;
+}
+
+// ... for the three planes of each of n sides, in the order given
+static int check_sides_aligned(const Side *sides, int n, int nframes)
+{
+    for (int k = 0; k < n; k++)
+        for (int i = 0; i < 3; i++)
+            if (const int rc = check_plane_aligned(sides[k], i, nframes, "planes")) return rc;
+    return LUTR_OK;
+}
+
+// the byte ranges of a side's planes over all rows and frames, and their number
+static int side_spans(const Side &s, const FrameGeom &G, Span out[3])
+{
+    if (s.packed) {
+        out[0] = plane_span(s.pl->data[0], s.pl->stride[0], s.pl->frame_stride[0], G.h, s.packed_row, G.nframes);
+        return 1;
+    }
+    planar_spans(s.pl, s.csx, s.csy, G.w, G.h, s.depth > 16 ? 4 : s.depth > 8 ? 2 : 1, G.nframes, out);
+    return 3;
+}
+
+// check_disjoint between the planes of two sides
+static int check_sides_disjoint(const char *what, bool name_src, const Side &a, const Side &b, const FrameGeom &G)
+{
+    Span as[3], bs[3];
+    const int na = side_spans(a, G, as), nb = side_spans(b, G, bs);
+    return check_disjoint(what, name_src, as, na, bs, nb);
+}
+
+// In place means the same container on both sides (`same`: the entry's word on that) and the same bytes; anything else must not
+// overlap at all.
+static int check_in_place(const char *what, bool same, const Side &s, const Side &d, const FrameGeom &G)
+{
+    if (same && s.pl->data[0] == d.pl->data[0] && s.pl->stride[0] == d.pl->stride[0] &&
+        (G.nframes <= 1 || s.pl->frame_stride[0] == d.pl->frame_stride[0])) return LUTR_OK;
+    return check_sides_disjoint(what, true, s, d, G);
+}
+
+// ---- what the host entries of the union-block kernels share (lutr_apply_yuv_xsub's pass with something added to it: DESIGN.md
+// 3.13, 3.17 - 3.23).  An entry runs its own refusals, then union_open, then whatever its family refuses on the formats, then
+// union_rules, the empty call, union_planes_ready and the overlap check under its own noun.
+struct UnionCall {
+    YuvConsts K;           // make_yuv_consts_xsub's block for side[1]
+    Side side[3];          // source, destination, and lutr_apply_yuv_dual's second destination
+    int nsides;
+    int lut_depth;
+};
+
+// First half: the constants, then the layouts and depths of the two sides.
+static int union_open(const lutr_yuv_params &p, const lutr_planes *src, const lutr_planes *dst, UnionCall *u)
+{
+    if (const int rc = make_yuv_consts_xsub(p, &u->K)) return rc;
+    u->side[0] = planar_side("source", src, p.fmt_in);
+    u->side[1] = planar_side("destination", dst, p.fmt_out);
+    u->nsides = 2;
+    u->lut_depth = p.lut_depth;
+    return LUTR_OK;
+}
+
+// Second half, ahead of the empty call: lut_depth in range under the family's `tag` (nullptr: the family has no such check, the
+// constants have refused a depth outside 8..16), whole union blocks of every side, and no LDS-window kernel (`lds_noun`: for what).
+static int union_rules(const lutr_ctx *c, const UnionCall &u, const FrameGeom &G, const char *tag, const char *lds_noun)
+{
+    if (tag && (u.lut_depth < 8 || u.lut_depth > 16)) { set_error("%s: LUT depth %d outside 8..16", tag, u.lut_depth); return LUTR_EINVAL; }
+    int csy = 0;
+    for (int k = 0; k < u.nsides; k++) csy = std::max(csy, u.side[k].csy);
+    if (const int rc = check_row_blocks(G.row0, G.rows, G.h, 1 << csy, "union chroma block height")) return rc;
+    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for %s", lds_noun); return LUTR_EINVAL; }
+    return LUTR_OK;
+}
+
+// ... and behind it: every plane has a base pointer, and the 16-bit planes are aligned.
+static int union_planes_ready(const UnionCall &u, const FrameGeom &G)
+{
+    if (const int rc = check_planes_set(u.side[0].pl, u.side[1].pl)) return rc;
+    if (u.nsides > 2)
+        if (const int rc = check_planes_set(u.side[2].pl, nullptr)) return rc;
+    return check_sides_aligned(u.side, u.nsides, G.nframes);
+}
+
 // The dither path's float planes for the whole frames of G with output chroma subsampled by 2^csx x 2^csy, out of the context's
 // scratch (grown when too small).
 static int dither_scratch(lutr_ctx *c, const FrameGeom &G, int csx, int csy, FloatPlanes *F)
@@ -1254,12 +1374,11 @@ int lutr_apply_yuv_sited(lutr_ctx *c, const lutr_yuv_params *p, int interp, int 
     if (const int rc = check_planes_set(src, dst)) return rc;
     // the resampling reads around every output sample: a destination that overlaps a source would be read after being written
     const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
-    Span ss[3], ds[3];
-    planar_spans(src, csx, csy, w, h, din > 8 ? 2 : 1, nframes, ss);
-    planar_spans(dst, csx, csy, w, h, dout > 8 ? 2 : 1, nframes, ds);
-    if (const int rc = check_disjoint("sited chroma resampling", true, ss, 3, ds, 3)) return rc;
+    const FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = check_sides_disjoint("sited chroma resampling", true, planar_side("source", src, p->fmt_in),
+                                            planar_side("destination", dst, p->fmt_out), G)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    LutConsts L; PlaneSet P;
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
     fill_planes(&P, src, dst);
     const char *name = launch_yuv_sited(c->stream, L, K, P, G, din, dout, csy, chroma_loc, interp);
@@ -1313,7 +1432,6 @@ int lutr_apply_yuv_xsub(lutr_ctx *c, const lutr_yuv_params *p, int interp, int d
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
     if (const int rc = check_planes_set(src, dst)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
     LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
     fill_planes(&P, src, dst);
@@ -1339,60 +1457,41 @@ int lutr_apply_yuv_dual(lutr_ctx *c, const lutr_yuv_params *p, int fmt_out2, int
     if (rc) return rc;
     if (!dst2) { set_error("null argument"); return LUTR_EINVAL; }
     if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
-    YuvConsts K1, K2;
-    rc = make_yuv_consts_xsub(*p, &K1);
-    if (rc) return rc;
+    UnionCall U; YuvConsts K2; const FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = union_open(*p, src, dst, &U)) return rc;
     lutr_yuv_params p2 = *p;
     p2.fmt_out = fmt_out2;
     if ((fmt_out2 >> 10) || make_yuv_consts_xsub(p2, &K2)) {
         set_error("bad fmt_out2 0x%x: the second output is planar 4:2:0 / 4:2:2 / 4:4:4 at a depth of 8 to 16 bit", fmt_out2);
         return LUTR_EINVAL;
     }
-    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
-    const int csx1 = LUTR_FMT_CSX(p->fmt_out), csy1 = LUTR_FMT_CSY(p->fmt_out);
-    const int csx2 = LUTR_FMT_CSX(fmt_out2), csy2 = LUTR_FMT_CSY(fmt_out2);
-    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout1 = LUTR_FMT_DEPTH(p->fmt_out), dout2 = LUTR_FMT_DEPTH(fmt_out2);
-    const int bh = 1 << std::max(icsy, std::max(csy1, csy2));
-    if (const int rc = check_row_blocks(row0, rows, h, bh, "union chroma block height")) return rc;
-    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for two outputs"); return LUTR_EINVAL; }
+    U.side[U.nsides++] = planar_side("second destination", dst2, fmt_out2);
+    const Side &S = U.side[0], &D1 = U.side[1], &D2 = U.side[2];
+    if (const int rc = union_rules(c, U, G, nullptr, "two outputs")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    if (const int rc = check_planes_set(src, dst)) return rc;
-    if (const int rc = check_planes_set(dst2, nullptr)) return rc;
-    const struct { const char *side; const lutr_planes *pl; int depth; } sides[3] = {
-        {"source", src, din}, {"destination", dst, dout1}, {"second destination", dst2, dout2}};
-    for (const auto &s : sides)
-        for (int i = 0; i < 3; i++)
-            if (s.depth > 8 && !check_aligned(s.pl->data[i], s.pl->stride[i], s.pl->frame_stride[i], nframes, 1)) {
-                set_error("%s plane %d: 16-bit planes need 2-byte aligned rows", s.side, i);
-                return LUTR_EINVAL;
-            }
+    if (const int rc = union_planes_ready(U, G)) return rc;
     // one pass writes both outputs while it still reads the source: nothing may overlap anything
-    Span ss[3], d1[3], d2[3];
-    planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
-    planar_spans(dst, csx1, csy1, w, h, dout1 > 8 ? 2 : 1, nframes, d1);
-    planar_spans(dst2, csx2, csy2, w, h, dout2 > 8 ? 2 : 1, nframes, d2);
-    if (const int rc = check_disjoint("the two-output pass", true, ss, 3, d1, 3)) return rc;
-    if (check_disjoint("the two-output pass", true, ss, 3, d2, 3)) {
+    if (const int rc = check_sides_disjoint("the two-output pass", true, S, D1, G)) return rc;
+    if (check_sides_disjoint("the two-output pass", true, S, D2, G)) {
         const std::string m = g_last_error;
         set_error("%s (the second destination)", m.c_str());
         return LUTR_EINVAL;
     }
-    if (check_disjoint("", false, d1, 3, d2, 3)) {
+    if (check_sides_disjoint("", false, D1, D2, G)) {
         set_error("the two destinations overlap: their byte ranges over all rows and frames must be disjoint");
         return LUTR_EINVAL;
     }
     HIP_TRY(hipSetDevice(c->device));
-    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
-    LutConsts L; PlaneSet P; DstPlanes D2; FrameGeom G{w, h, row0, rows, nframes};
+    LutConsts L; PlaneSet P; DstPlanes P2;
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
     fill_planes(&P, src, dst);
     for (int i = 0; i < 3; i++) {
-        D2.d[i] = (uint8_t *)dst2->data[i];
-        D2.ds[i] = dst2->stride[i];
-        D2.dfs[i] = dst2->frame_stride[i];
+        P2.d[i] = (uint8_t *)dst2->data[i];
+        P2.ds[i] = dst2->stride[i];
+        P2.dfs[i] = dst2->frame_stride[i];
     }
-    return finish_launch(c, launch_yuv_dual(c->stream, c->variant, L, K1, K2, P, D2, G, din, dout1, csx1, csy1, dout2, csx2, csy2,
-                                            icsx, icsy, interp));
+    return finish_launch(c, launch_yuv_dual(c->stream, c->variant, L, U.K, K2, P, P2, G, S.depth, D1.depth, D1.csx, D1.csy, D2.depth,
+                                            D2.csx, D2.csy, S.csx, S.csy, interp));
 }
 
 // lutr_apply_yuv_xsub's pass for any pair of layouts with the second lattice behind the first.
@@ -1407,41 +1506,19 @@ int lutr_apply_yuv_chain(lutr_ctx *c, const lutr_yuv_params *p, int interp, int 
         return LUTR_EINVAL;
     }
     if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
-    YuvConsts K;
-    rc = make_yuv_consts_xsub(*p, &K);
-    if (rc) return rc;
-    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
-    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
-    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
-    if (const int rc = check_row_blocks(row0, rows, h, 1 << std::max(icsy, ocsy), "union chroma block height")) return rc;
-    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for two LUTs in one pass"); return LUTR_EINVAL; }
+    UnionCall U; const FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = union_open(*p, src, dst, &U)) return rc;
+    const Side &S = U.side[0], &D = U.side[1];
+    if (const int rc = union_rules(c, U, G, nullptr, "two LUTs in one pass")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    if (const int rc = check_planes_set(src, dst)) return rc;
-    const struct { const char *side; const lutr_planes *pl; int depth; } sides[2] = {{"source", src, din}, {"destination", dst, dout}};
-    for (const auto &s : sides)
-        for (int i = 0; i < 3; i++)
-            if (s.depth > 8 && !check_aligned(s.pl->data[i], s.pl->stride[i], s.pl->frame_stride[i], nframes, 1)) {
-                set_error("%s plane %d: 16-bit planes need 2-byte aligned rows", s.side, i);
-                return LUTR_EINVAL;
-            }
-    Span ss[3], ds[3];
-    planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
-    planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
-    if (const int rc = check_disjoint("the two-LUT pass", true, ss, 3, ds, 3)) return rc;
+    if (const int rc = union_planes_ready(U, G)) return rc;
+    if (const int rc = check_sides_disjoint("the two-LUT pass", true, S, D, G)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
-    LutConsts L, L2{}; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    LutConsts L; PlaneSet P;
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
-    // the second lattice at the same depth: its own size and scale, no prelut (L2.pre stays null), never the clip-free path
-    const int maxi = (1 << p->lut_depth) - 1;
-    L2.lat = c->lat2;
-    L2.n1 = c->n2 + 1;
-    L2.maxf = (float)maxi;
-    L2.scale_f = 1.0f / (float)maxi;
-    L2.lut_max = (float)(c->n2 - 1);
-    for (int i = 0; i < 3; i++) L2.sc[i] = c->scale2[i] * L2.lut_max;
     fill_planes(&P, src, dst);
-    return finish_launch(c, launch_yuv_chain(c->stream, c->variant, L, L2, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, interp, interp2));
+    return finish_launch(c, launch_yuv_chain(c->stream, c->variant, L, second_lattice(c, p->lut_depth), U.K, P, G, S.depth, D.depth,
+                                             S.csx, S.csy, D.csx, D.csy, interp, interp2));
 }
 
 // ---- ASC CDL in front of lut3d
@@ -1534,35 +1611,19 @@ int lutr_apply_yuv_cdl(lutr_ctx *c, const lutr_yuv_params *p, int interp, const 
         return LUTR_EINVAL;
     }
     if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
-    YuvConsts K;
-    rc = make_yuv_consts_xsub(*p, &K);
-    if (rc) return rc;
-    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
-    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
-    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
-    if (p->lut_depth < 8 || p->lut_depth > 16) { set_error("CDL: LUT depth %d outside 8..16", p->lut_depth); return LUTR_EINVAL; }
-    if (const int rc = check_row_blocks(row0, rows, h, 1 << std::max(icsy, ocsy), "union chroma block height")) return rc;
-    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for the CDL pass"); return LUTR_EINVAL; }
+    UnionCall U; const FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = union_open(*p, src, dst, &U)) return rc;
+    const Side &S = U.side[0], &D = U.side[1];
+    if (const int rc = union_rules(c, U, G, "CDL", "the CDL pass")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    if (const int rc = check_planes_set(src, dst)) return rc;
-    const struct { const char *side; const lutr_planes *pl; int depth; } sides[2] = {{"source", src, din}, {"destination", dst, dout}};
-    for (const auto &s : sides)
-        for (int i = 0; i < 3; i++)
-            if (s.depth > 8 && !check_aligned(s.pl->data[i], s.pl->stride[i], s.pl->frame_stride[i], nframes, 1)) {
-                set_error("%s plane %d: 16-bit planes need 2-byte aligned rows", s.side, i);
-                return LUTR_EINVAL;
-            }
-    Span ss[3], ds[3];
-    planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
-    planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
-    if (const int rc = check_disjoint("the CDL pass", true, ss, 3, ds, 3)) return rc;
+    if (const int rc = union_planes_ready(U, G)) return rc;
+    if (const int rc = check_sides_disjoint("the CDL pass", true, S, D, G)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
-    LutConsts L; CdlConsts C; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    LutConsts L; CdlConsts C; PlaneSet P;
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
     if (const int rc = cdl_device_table(c, *cdl, p->lut_depth, &C)) return rc;
     fill_planes(&P, src, dst);
-    return finish_launch(c, launch_yuv_cdl(c->stream, c->variant, L, C, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, interp));
+    return finish_launch(c, launch_yuv_cdl(c->stream, c->variant, L, C, U.K, P, G, S.depth, D.depth, S.csx, S.csy, D.csx, D.csy, interp));
 }
 
 // ---- 1D LUT alone or in front of lut3d
@@ -1625,36 +1686,20 @@ int lutr_apply_yuv_lut1d(lutr_ctx *c, const lutr_yuv_params *p, int interp, int 
     if (rc) return rc;
     if (!c->l1d_size) { set_error("no 1D LUT set on this context (call lutr_ctx_set_lut1d first)"); return LUTR_EINVAL; }
     if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
-    YuvConsts K;
-    rc = make_yuv_consts_xsub(*p, &K);
-    if (rc) return rc;
-    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
-    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
-    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
-    if (p->lut_depth < 8 || p->lut_depth > 16) { set_error("lut1d: LUT depth %d outside 8..16", p->lut_depth); return LUTR_EINVAL; }
-    if (const int rc = check_row_blocks(row0, rows, h, 1 << std::max(icsy, ocsy), "union chroma block height")) return rc;
-    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for the lut1d pass"); return LUTR_EINVAL; }
+    UnionCall U; const FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = union_open(*p, src, dst, &U)) return rc;
+    const Side &S = U.side[0], &D = U.side[1];
+    if (const int rc = union_rules(c, U, G, "lut1d", "the lut1d pass")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    if (const int rc = check_planes_set(src, dst)) return rc;
-    const struct { const char *side; const lutr_planes *pl; int depth; } sides[2] = {{"source", src, din}, {"destination", dst, dout}};
-    for (const auto &s : sides)
-        for (int i = 0; i < 3; i++)
-            if (s.depth > 8 && !check_aligned(s.pl->data[i], s.pl->stride[i], s.pl->frame_stride[i], nframes, 1)) {
-                set_error("%s plane %d: 16-bit planes need 2-byte aligned rows", s.side, i);
-                return LUTR_EINVAL;
-            }
-    Span ss[3], ds[3];
-    planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
-    planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
-    if (const int rc = check_disjoint("the lut1d pass", true, ss, 3, ds, 3)) return rc;
+    if (const int rc = union_planes_ready(U, G)) return rc;
+    if (const int rc = check_sides_disjoint("the lut1d pass", true, S, D, G)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
-    LutConsts L{}; L1dConsts C; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    LutConsts L{}; L1dConsts C; PlaneSet P;
     if (interp != LUTR_INTERP_NONE)
         if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
     if (const int rc = l1d_device_table(c, p->lut_depth, &C)) return rc;
     fill_planes(&P, src, dst);
-    return finish_launch(c, launch_yuv_l1d(c->stream, c->variant, L, C, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, interp));
+    return finish_launch(c, launch_yuv_l1d(c->stream, c->variant, L, C, U.K, P, G, S.depth, D.depth, S.csx, S.csy, D.csx, D.csy, interp));
 }
 
 // ---- an ordered stack of lut1d / CDL / lut3d stages
@@ -1700,10 +1745,7 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
     if (!seen[LUTR_STAGE_CDL] && cdl) { set_error("stack: a CDL is given and no cdl stage is listed"); return LUTR_EINVAL; }
     if (cdl)
         if (const int rc = check_cdl(cdl)) return rc;
-    if (w < 0 || h < 0 || nframes < 0 || row0 < 0 || rows < 0 || row0 + rows > h) {
-        set_error("bad geometry w=%d h=%d nframes=%d row0=%d rows=%d", w, h, nframes, row0, rows);
-        return LUTR_EINVAL;
-    }
+    if (const int rc = check_geometry(w, h, nframes, row0, rows)) return rc;
     // the steps: a unit pixel is rounded to codes ahead of lut1d and at the end of the list
     unsigned long long ops = 0;
     int nops = 0;
@@ -1737,29 +1779,17 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
     }
     if (unit) push(STACK_OP_ROUND, 0);
     if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
-    YuvConsts K;
-    if (const int rc = make_yuv_consts_xsub(*p, &K)) return rc;
-    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
-    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
-    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
-    if (p->lut_depth < 8 || p->lut_depth > 16) { set_error("stack: LUT depth %d outside 8..16", p->lut_depth); return LUTR_EINVAL; }
-    if (const int rc = check_row_blocks(row0, rows, h, 1 << std::max(icsy, ocsy), "union chroma block height")) return rc;
-    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for the stack pass"); return LUTR_EINVAL; }
+    UnionCall U; const FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = union_open(*p, src, dst, &U)) return rc;
+    const Side &Si = U.side[0], &Di = U.side[1];
+    if (const int rc = union_rules(c, U, G, "stack", "the stack pass")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    if (const int rc = check_planes_set(src, dst)) return rc;
-    const struct { const char *side; const lutr_planes *pl; int depth; } sides[2] = {{"source", src, din}, {"destination", dst, dout}};
-    for (const auto &s : sides)
-        for (int i = 0; i < 3; i++)
-            if (s.depth > 8 && !check_aligned(s.pl->data[i], s.pl->stride[i], s.pl->frame_stride[i], nframes, 1)) {
-                set_error("%s plane %d: 16-bit planes need 2-byte aligned rows", s.side, i);
-                return LUTR_EINVAL;
-            }
-    Span ss[3], ds[3];
-    planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
-    planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
-    if (const int rc = check_disjoint("the stack pass", true, ss, 3, ds, 3)) return rc;
+    if (const int rc = union_planes_ready(U, G)) return rc;
+    if (const int rc = check_sides_disjoint("the stack pass", true, Si, Di, G)) return rc;
     MatteConsts A{};
     if (matte) {
+        Span ds[3];
+        side_spans(Di, G, ds);
         const int mb = matte->depth > 8 ? 2 : 1;
         if ((long long)matte->stride < (long long)w * mb) {
             set_error("stack: matte stride %lld is shorter than a row of %d samples of %d byte(s)", (long long)matte->stride, w, mb);
@@ -1780,23 +1810,14 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
                         1.0f / maxm, matte->invert, mb == 2};
     }
     HIP_TRY(hipSetDevice(c->device));
-    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
-    LutConsts L{}, L2{}; StackConsts S{}; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
-    const int maxi = (1 << p->lut_depth) - 1;
+    LutConsts L{}; StackConsts S{}; PlaneSet P;
     if (seen[LUTR_STAGE_LUT3D])
         if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
-    if (seen[LUTR_STAGE_LUT3D_2]) {      // lutr_apply_yuv_chain's second lattice: its own size and scale, no prelut
-        L2.lat = c->lat2;
-        L2.n1 = c->n2 + 1;
-        L2.maxf = (float)maxi;
-        L2.scale_f = 1.0f / (float)maxi;
-        L2.lut_max = (float)(c->n2 - 1);
-        for (int i = 0; i < 3; i++) L2.sc[i] = c->scale2[i] * L2.lut_max;
-    }
+    const LutConsts L2 = seen[LUTR_STAGE_LUT3D_2] ? second_lattice(c, p->lut_depth) : LutConsts{};
     S.ops = ops;
     S.stride = 1 << p->lut_depth;
     S.sat = 1.0f;
-    S.maxf = (float)maxi;
+    S.maxf = (float)((1 << p->lut_depth) - 1);
     if (cdl) {
         CdlConsts C;
         if (const int rc = cdl_device_table(c, *cdl, p->lut_depth, &C)) return rc;
@@ -1811,7 +1832,7 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
         S.lds_l1d_words = 3 * (S.stride >> 1);
     }
     fill_planes(&P, src, dst);
-    const char *name = launch_yuv_stack(c->stream, c->variant, L, L2, S, K, P, G, din, dout, icsx, icsy, ocsx, ocsy, mix,
+    const char *name = launch_yuv_stack(c->stream, c->variant, L, L2, S, U.K, P, G, Si.depth, Di.depth, Si.csx, Si.csy, Di.csx, Di.csy, mix,
                                         matte ? &A : nullptr);
     if (!name) return finish_launch(c, nullptr);
     const std::string full = std::string(name) + "[" + list + "]";
@@ -1824,18 +1845,25 @@ int lutr_apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage
     return apply_yuv_stack(c, p, stages, nstages, cdl, nullptr, nullptr, w, h, nframes, src, dst, row0, rows);
 }
 
-// ---- the stack with a strength behind it (DESIGN.md 3.22): the same pass, the mix kernels whatever the strength
-int lutr_apply_yuv_stack_mix(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
-                             float strength, const float *frame_strength, int w, int h, int nframes, const lutr_planes *src,
-                             const lutr_planes *dst, int row0, int rows)
+// The strength of the mix and matte entries: the scalar is read only without the array; a NaN is found by its bits (this file is
+// built without honouring NaNs)
+static int check_strength(float strength, const float *frame_strength)
 {
-    // the scalar is read only without the array; a NaN is found by its bits (this file is built without honouring NaNs)
     uint32_t bits;
     memcpy(&bits, &strength, sizeof bits);
     if (!frame_strength && ((bits & 0x7fffffffu) > 0x7f800000u || strength < 0.0f || strength > 1.0f)) {
         set_error("stack: strength %g outside [0, 1]", (double)strength);
         return LUTR_EINVAL;
     }
+    return LUTR_OK;
+}
+
+// ---- the stack with a strength behind it (DESIGN.md 3.22): the same pass, the mix kernels whatever the strength
+int lutr_apply_yuv_stack_mix(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                             float strength, const float *frame_strength, int w, int h, int nframes, const lutr_planes *src,
+                             const lutr_planes *dst, int row0, int rows)
+{
+    if (const int rc = check_strength(strength, frame_strength)) return rc;
     const MixConsts M{frame_strength, frame_strength ? 1.0f : strength};
     return apply_yuv_stack(c, p, stages, nstages, cdl, &M, nullptr, w, h, nframes, src, dst, row0, rows);
 }
@@ -1845,12 +1873,7 @@ int lutr_apply_yuv_stack_matte(lutr_ctx *c, const lutr_yuv_params *p, const lutr
                                float strength, const float *frame_strength, const lutr_matte *matte, int w, int h, int nframes,
                                const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
 {
-    uint32_t bits;
-    memcpy(&bits, &strength, sizeof bits);
-    if (!frame_strength && ((bits & 0x7fffffffu) > 0x7f800000u || strength < 0.0f || strength > 1.0f)) {
-        set_error("stack: strength %g outside [0, 1]", (double)strength);
-        return LUTR_EINVAL;
-    }
+    if (const int rc = check_strength(strength, frame_strength)) return rc;
     if (!matte || !matte->data) { set_error("stack: null matte"); return LUTR_EINVAL; }
     if (matte->depth < 8 || matte->depth > 16) { set_error("stack: matte depth %d outside 8..16", matte->depth); return LUTR_EINVAL; }
     if (matte->invert != 0 && matte->invert != 1) { set_error("stack: matte invert %d is neither 0 nor 1", matte->invert); return LUTR_EINVAL; }
@@ -1886,38 +1909,40 @@ int lutr_apply_planar_rgb_lut1d(lutr_ctx *c, int depth, int w, int h, int nframe
     return finish_launch(c, launch_rgb_l1d(c->stream, c->variant, C, P, G, depth));
 }
 
-// What a semi-planar and a packed side share: `noun` ("layout" | "packing") names the struct in the messages; the shift against
-// the format's depth, then `bad_shape` (the side's own refusal of the format's subsampling, or nullptr -- it has always come
-// between the two), then the `nplanes` planes the side has and their alignment.
-static int check_container_side(const char *side, const char *noun, int shift, int depth, int nplanes, const lutr_planes *pl,
-                                int nframes, const char *bad_shape)
+// the first `nplanes` planes of a container's side, plane by plane: a base pointer, then the 16-bit alignment
+static int check_container_planes(const Side &s, int nplanes, int nframes)
 {
-    if (depth <= 8 ? shift != 0 : (shift != 0 && shift != 16 - depth)) {
-        if (depth <= 8) set_error("%s %s: an 8-bit container takes shift 0, not %d", side, noun, shift);
-        else set_error("%s %s: shift is %d (16 - depth) or 0 at %d bit, not %d", side, noun, 16 - depth, depth, shift);
-        return LUTR_EINVAL;
-    }
-    if (bad_shape) { set_error("%s %s: %s", side, noun, bad_shape); return LUTR_EINVAL; }
     for (int i = 0; i < nplanes; i++) {
-        if (!pl->data[i]) { set_error("null %s plane %d", side, i); return LUTR_EINVAL; }
-        if (depth > 8 && !check_aligned(pl->data[i], pl->stride[i], pl->frame_stride[i], nframes, 1)) {
-            set_error("%s plane %d: 16-bit containers need 2-byte aligned rows", side, i);
-            return LUTR_EINVAL;
-        }
+        if (!s.pl->data[i]) { set_error("null %s plane %d", s.name, i); return LUTR_EINVAL; }
+        if (const int rc = check_plane_aligned(s, i, nframes, "containers")) return rc;
     }
     return LUTR_OK;
 }
 
-// one side of lutr_apply_yuv_semi: the layout against the format, the planes it needs and their alignment
-static int check_semi_side(const char *side, const lutr_yuv_layout *y, int fmt, const lutr_planes *pl, int nframes)
+// What a semi-planar and a packed side share: `noun` ("layout" | "packing") names the struct in the messages; the shift against
+// the format's depth, then `bad_shape` (the side's own refusal of the format's subsampling, or nullptr -- it has always come
+// between the two), then the `nplanes` planes the side has and their alignment.
+static int check_container_side(const Side &s, const char *noun, int shift, int nplanes, int nframes, const char *bad_shape)
 {
-    if ((y->semi != 0 && y->semi != 1) || (y->swap != 0 && y->swap != 1)) {
-        set_error("%s layout: semi and swap are 0 or 1 (got %d, %d)", side, y->semi, y->swap);
+    if (s.depth <= 8 ? shift != 0 : (shift != 0 && shift != 16 - s.depth)) {
+        if (s.depth <= 8) set_error("%s %s: an 8-bit container takes shift 0, not %d", s.name, noun, shift);
+        else set_error("%s %s: shift is %d (16 - depth) or 0 at %d bit, not %d", s.name, noun, 16 - s.depth, s.depth, shift);
         return LUTR_EINVAL;
     }
-    if (y->swap && !y->semi) { set_error("%s layout: swap needs a semi-planar side", side); return LUTR_EINVAL; }
-    return check_container_side(side, "layout", y->shift, LUTR_FMT_DEPTH(fmt), y->semi ? 2 : 3, pl, nframes,
-                                y->semi && LUTR_FMT_CSX(fmt) != 1 ? "semi-planar frames are 4:2:0 or 4:2:2" : nullptr);
+    if (bad_shape) { set_error("%s %s: %s", s.name, noun, bad_shape); return LUTR_EINVAL; }
+    return check_container_planes(s, nplanes, nframes);
+}
+
+// one side of lutr_apply_yuv_semi: the layout against the format, the planes it needs and their alignment
+static int check_semi_side(const Side &s, const lutr_yuv_layout *y, int nframes)
+{
+    if ((y->semi != 0 && y->semi != 1) || (y->swap != 0 && y->swap != 1)) {
+        set_error("%s layout: semi and swap are 0 or 1 (got %d, %d)", s.name, y->semi, y->swap);
+        return LUTR_EINVAL;
+    }
+    if (y->swap && !y->semi) { set_error("%s layout: swap needs a semi-planar side", s.name); return LUTR_EINVAL; }
+    return check_container_side(s, "layout", y->shift, y->semi ? 2 : 3, nframes,
+                                y->semi && s.csx != 1 ? "semi-planar frames are 4:2:0 or 4:2:2" : nullptr);
 }
 
 int lutr_apply_yuv_semi(lutr_ctx *c, const lutr_yuv_params *p, int interp, const lutr_yuv_layout *in_layout,
@@ -1932,14 +1957,13 @@ int lutr_apply_yuv_semi(lutr_ctx *c, const lutr_yuv_params *p, int interp, const
     YuvConsts K;
     rc = make_yuv_consts(*p, &K);
     if (rc) return rc;
-    if (const int rc = check_semi_side("source", in_layout, p->fmt_in, src, nframes)) return rc;
-    if (const int rc = check_semi_side("destination", out_layout, p->fmt_out, dst, nframes)) return rc;
+    if (const int rc = check_semi_side(planar_side("source", src, p->fmt_in), in_layout, nframes)) return rc;
+    if (const int rc = check_semi_side(planar_side("destination", dst, p->fmt_out), out_layout, nframes)) return rc;
     const int csx = LUTR_FMT_CSX(p->fmt_in), csy = LUTR_FMT_CSY(p->fmt_in);
     if (csx != 1) { set_error("a shifted planar container is taken at 4:2:0 / 4:2:2 only"); return LUTR_EINVAL; }
     if (const int rc = check_row_blocks(row0, rows, h, 1 << csy, "chroma block height")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
     HIP_TRY(hipSetDevice(c->device));
-    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
     LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
     fill_planes(&P, src, dst);
@@ -1952,28 +1976,25 @@ int lutr_apply_yuv_semi(lutr_ctx *c, const lutr_yuv_params *p, int interp, const
 
 
 // one side of lutr_apply_yuv_packed: the packing against the format, the planes it needs and their alignment
-static int check_packed_side(const char *side, const lutr_yuv_packing *y, int fmt, const lutr_planes *pl, int nframes)
+static int check_packed_side(const Side &s, const lutr_yuv_packing *y, int nframes)
 {
-    if (y->packed != 0 && y->packed != 1) { set_error("%s packing: packed is 0 or 1 (got %d)", side, y->packed); return LUTR_EINVAL; }
+    if (y->packed != 0 && y->packed != 1) { set_error("%s packing: packed is 0 or 1 (got %d)", s.name, y->packed); return LUTR_EINVAL; }
     if (y->order < LUTR_PK_YUYV || y->order > LUTR_PK_YVYU) {
-        set_error("%s packing: order is 0 (yuyv), 1 (uyvy) or 2 (yvyu), not %d", side, y->order);
+        set_error("%s packing: order is 0 (yuyv), 1 (uyvy) or 2 (yvyu), not %d", s.name, y->order);
         return LUTR_EINVAL;
     }
-    if (!y->packed && (y->order || y->shift)) { set_error("%s packing: a planar side takes order 0 and shift 0", side); return LUTR_EINVAL; }
-    return check_container_side(side, "packing", y->shift, LUTR_FMT_DEPTH(fmt), y->packed ? 1 : 3, pl, nframes,
-                                y->packed && !(LUTR_FMT_CSX(fmt) == 1 && LUTR_FMT_CSY(fmt) == 0) ? "packed frames are 4:2:2" : nullptr);
+    if (!y->packed && (y->order || y->shift)) { set_error("%s packing: a planar side takes order 0 and shift 0", s.name); return LUTR_EINVAL; }
+    return check_container_side(s, "packing", y->shift, y->packed ? 1 : 3, nframes,
+                                y->packed && !(s.csx == 1 && s.csy == 0) ? "packed frames are 4:2:2" : nullptr);
 }
 
-// the byte ranges of one side of lutr_apply_yuv_packed over all rows and frames; returns their number
-static int packed_side_spans(const lutr_yuv_packing *y, int fmt, const lutr_planes *pl, int w, int h, int nframes, Span *out)
+// one side of lutr_apply_yuv_packed as a value: a packed side is one plane of whole groups of two pixels, four samples each
+static Side packed_side(const char *name, const lutr_planes *pl, int fmt, const lutr_yuv_packing *y, int w)
 {
-    const long long bs = LUTR_FMT_DEPTH(fmt) > 8 ? 2 : 1;
-    if (y->packed) {
-        out[0] = plane_span(pl->data[0], pl->stride[0], pl->frame_stride[0], h, 4ll * ((w + 1) >> 1) * bs, nframes);
-        return 1;
-    }
-    planar_spans(pl, LUTR_FMT_CSX(fmt), LUTR_FMT_CSY(fmt), w, h, (int)bs, nframes, out);
-    return 3;
+    Side s = planar_side(name, pl, fmt);
+    s.packed = y->packed != 0;
+    s.packed_row = 4ll * ((w + 1) >> 1) * (s.depth > 8 ? 2 : 1);
+    return s;
 }
 
 int lutr_apply_yuv_packed(lutr_ctx *c, const lutr_yuv_params *p, int interp, const lutr_yuv_packing *in,
@@ -1995,23 +2016,16 @@ int lutr_apply_yuv_packed(lutr_ctx *c, const lutr_yuv_params *p, int interp, con
         return LUTR_EINVAL;
     }
     if (!((ocsx == 1 && ocsy <= 1) || (ocsx == 0 && ocsy == 0))) { set_error("the destination is 4:2:2, 4:2:0 or 4:4:4"); return LUTR_EINVAL; }
-    if (const int rc = check_packed_side("source", in, p->fmt_in, src, nframes)) return rc;
-    if (const int rc = check_packed_side("destination", out, p->fmt_out, dst, nframes)) return rc;
+    const Side S = packed_side("source", src, p->fmt_in, in, w), D = packed_side("destination", dst, p->fmt_out, out, w);
+    const FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = check_packed_side(S, in, nframes)) return rc;
+    if (const int rc = check_packed_side(D, out, nframes)) return rc;
     if (const int rc = check_row_blocks(row0, rows, h, 1 << ocsy, "chroma block height")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    // in place: the same packed container, the same bytes.  Anything else must not overlap at all
-    const bool in_place = in->packed && out->packed && in->order == out->order && in->shift == out->shift &&
-                          LUTR_FMT_DEPTH(p->fmt_in) == LUTR_FMT_DEPTH(p->fmt_out) && src->data[0] == dst->data[0] &&
-                          src->stride[0] == dst->stride[0] && (nframes <= 1 || src->frame_stride[0] == dst->frame_stride[0]);
-    if (!in_place) {
-        Span ss[3], ds[3];
-        const int ns = packed_side_spans(in, p->fmt_in, src, w, h, nframes, ss);
-        const int nd = packed_side_spans(out, p->fmt_out, dst, w, h, nframes, ds);
-        if (const int rc = check_disjoint("a packed 4:2:2 call between different buffers or containers", true, ss, ns, ds, nd)) return rc;
-    }
+    const bool same = in->packed && out->packed && in->order == out->order && in->shift == out->shift && S.depth == D.depth;
+    if (const int rc = check_in_place("a packed 4:2:2 call between different buffers or containers", same, S, D, G)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
-    LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    LutConsts L; PlaneSet P;
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
     fill_planes(&P, src, dst);
     if (in->packed) clear_planes(&P, true, 1);
@@ -2026,41 +2040,32 @@ int lutr_apply_yuv_packed(lutr_ctx *c, const lutr_yuv_params *p, int interp, con
 static long long v210_row_bytes(int w) { return 16ll * ((w + 5) / 6); }
 
 // one side of lutr_apply_yuv_v210: a v210 side's format, plane, alignment and stride; a planar side's three planes
-static int check_v210_side(const char *side, int v210, int fmt, const lutr_planes *pl, int w, int nframes)
+// (`fmt`: the side's whole format code, as the message prints it)
+static int check_v210_side(const Side &s, int fmt, int w, int nframes)
 {
-    if (!v210) {
-        for (int i = 0; i < 3; i++) {
-            if (!pl->data[i]) { set_error("null %s plane %d", side, i); return LUTR_EINVAL; }
-            if (LUTR_FMT_DEPTH(fmt) > 8 && !check_aligned(pl->data[i], pl->stride[i], pl->frame_stride[i], nframes, 1)) {
-                set_error("%s plane %d: 16-bit containers need 2-byte aligned rows", side, i);
-                return LUTR_EINVAL;
-            }
-        }
-        return LUTR_OK;
-    }
-    if (fmt != LUTR_FMT(10, 1, 0)) { set_error("%s: a v210 frame is 10-bit 4:2:2 (format 0x%x)", side, fmt); return LUTR_EINVAL; }
-    if (!pl->data[0]) { set_error("null %s plane 0", side); return LUTR_EINVAL; }
+    if (!s.packed) return check_container_planes(s, 3, nframes);
+    const lutr_planes *pl = s.pl;
+    if (fmt != LUTR_FMT(10, 1, 0)) { set_error("%s: a v210 frame is 10-bit 4:2:2 (format 0x%x)", s.name, fmt); return LUTR_EINVAL; }
+    if (!pl->data[0]) { set_error("null %s plane 0", s.name); return LUTR_EINVAL; }
     if (!check_aligned(pl->data[0], pl->stride[0], pl->frame_stride[0], nframes, 3)) {
-        set_error("%s: v210 rows are 32-bit words: base, stride and frame stride must be 4-byte aligned", side);
+        set_error("%s: v210 rows are 32-bit words: base, stride and frame stride must be 4-byte aligned", s.name);
         return LUTR_EINVAL;
     }
     const long long st = pl->stride[0] < 0 ? -(long long)pl->stride[0] : (long long)pl->stride[0];
-    if (st < v210_row_bytes(w)) {
-        set_error("%s: a v210 row of %d samples takes %lld bytes, the stride is %lld", side, w, v210_row_bytes(w), (long long)pl->stride[0]);
+    if (st < s.packed_row) {
+        set_error("%s: a v210 row of %d samples takes %lld bytes, the stride is %lld", s.name, w, s.packed_row, (long long)pl->stride[0]);
         return LUTR_EINVAL;
     }
     return LUTR_OK;
 }
 
-// the byte ranges of one side of lutr_apply_yuv_v210 over all rows and frames; returns their number
-static int v210_side_spans(int v210, int fmt, const lutr_planes *pl, int w, int h, int nframes, Span *out)
+// one side of lutr_apply_yuv_v210 as a value
+static Side v210_side(const char *name, const lutr_planes *pl, int fmt, int v210, int w)
 {
-    if (v210) {
-        out[0] = plane_span(pl->data[0], pl->stride[0], pl->frame_stride[0], h, v210_row_bytes(w), nframes);
-        return 1;
-    }
-    planar_spans(pl, LUTR_FMT_CSX(fmt), LUTR_FMT_CSY(fmt), w, h, LUTR_FMT_DEPTH(fmt) > 8 ? 2 : 1, nframes, out);
-    return 3;
+    Side s = planar_side(name, pl, fmt);
+    s.packed = v210 != 0;
+    s.packed_row = v210_row_bytes(w);
+    return s;
 }
 
 int lutr_apply_yuv_v210(lutr_ctx *c, const lutr_yuv_params *p, int interp, int in_v210, int out_v210, int w, int h, int nframes,
@@ -2078,12 +2083,14 @@ int lutr_apply_yuv_v210(lutr_ctx *c, const lutr_yuv_params *p, int interp, int i
         return LUTR_EINVAL;
     }
     // (the container's own refusals first: they name the side; then the constants, which check depths, matrices and ranges)
-    if (const int rc = check_v210_side("source", in_v210, p->fmt_in, src, w, nframes)) return rc;
-    if (!(LUTR_FMT_CSX(p->fmt_in) == 1 && LUTR_FMT_CSY(p->fmt_in) == 0)) {
+    const Side S = v210_side("source", src, p->fmt_in, in_v210, w), D = v210_side("destination", dst, p->fmt_out, out_v210, w);
+    const FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = check_v210_side(S, p->fmt_in, w, nframes)) return rc;
+    if (!(S.csx == 1 && S.csy == 0)) {
         set_error("a v210 destination takes a 4:2:2 source (no subsampling change into a v210 frame)");
         return LUTR_EINVAL;
     }
-    if (const int rc = check_v210_side("destination", out_v210, p->fmt_out, dst, w, nframes)) return rc;
+    if (const int rc = check_v210_side(D, p->fmt_out, w, nframes)) return rc;
     YuvConsts K;
     rc = make_yuv_consts_xsub(*p, &K);           // (one layout on both sides: lutr_apply_yuv's own constants)
     if (rc) return rc;
@@ -2091,18 +2098,9 @@ int lutr_apply_yuv_v210(lutr_ctx *c, const lutr_yuv_params *p, int interp, int i
     if (!((ocsx == 1 && ocsy <= 1) || (ocsx == 0 && ocsy == 0))) { set_error("the destination is 4:2:2, 4:2:0 or 4:4:4"); return LUTR_EINVAL; }
     if (const int rc = check_row_blocks(row0, rows, h, 1 << ocsy, "chroma block height")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    // in place: v210 on both sides, the same bytes.  Anything else must not overlap at all
-    const bool in_place = in_v210 && out_v210 && src->data[0] == dst->data[0] && src->stride[0] == dst->stride[0] &&
-                          (nframes <= 1 || src->frame_stride[0] == dst->frame_stride[0]);
-    if (!in_place) {
-        Span ss[3], ds[3];
-        const int ns = v210_side_spans(in_v210, p->fmt_in, src, w, h, nframes, ss);
-        const int nd = v210_side_spans(out_v210, p->fmt_out, dst, w, h, nframes, ds);
-        if (const int rc = check_disjoint("a v210 call between different buffers or containers", true, ss, ns, ds, nd)) return rc;
-    }
+    if (const int rc = check_in_place("a v210 call between different buffers or containers", in_v210 && out_v210, S, D, G)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
-    LutConsts L; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
+    LutConsts L; PlaneSet P;
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
     fill_planes(&P, src, dst);
     if (in_v210) clear_planes(&P, true, 1);
@@ -2112,130 +2110,116 @@ int lutr_apply_yuv_v210(lutr_ctx *c, const lutr_yuv_params *p, int interp, int i
                                             LUTR_FMT_DEPTH(p->fmt_out), ocsx, ocsy, interp));
 }
 
+// ---- the RGB side of lutr_apply_rgb_to_yuv / lutr_apply_yuv_to_rgb (`side`: "source" | "destination"): gbrp planes at lut_depth
+// (kind 0), or the packed format `kind`, whose depth lut_depth must be
+static int rgb_side_layout(int kind, int lut_depth, const char *side, RgbLayout *Y)
+{
+    *Y = RgbLayout{1, lut_depth > 8, 0, 0, 0};
+    if (!kind) return LUTR_OK;
+    PackedFmt f;
+    if (const int rc = decode_packed(kind, &f)) return rc;
+    if (lut_depth != f.bits) { set_error("lut_depth %d must be the packed %s's depth %d", lut_depth, side, f.bits); return LUTR_EINVAL; }
+    *Y = RgbLayout{f.nc, f.bits == 16, f.ro, f.go, f.bo};
+    return LUTR_OK;
+}
+
+// ... and behind the empty call: the image, or the three planes, must be there (a packed image aligned to its samples).  Its streams
+// go into the source (src = true) or destination half of P in R, G, B order -- gbrp planes are G, B, R, and a null one is reported
+// under its own number -- and their byte ranges into sp; returns how many ranges differ (1 for an image) through *n.
+static int rgb_side_streams(const RgbLayout &Y, const lutr_planes *planar, const lutr_packed *packed, const FrameGeom &G, bool src,
+                            PlaneSet *P, Span sp[3], int *n)
+{
+    const bool image = Y.step > 1;
+    if (image) {
+        if (!packed->data) { set_error("null image"); return LUTR_EINVAL; }
+        if (Y.wide && !check_aligned(packed->data, packed->stride, packed->frame_stride, G.nframes, 1)) {
+            set_error("16-bit packed formats need 2-byte aligned rows");
+            return LUTR_EINVAL;
+        }
+    }
+    for (int k = 0; k < 3; k++) {
+        const int f = kGbrpToRgb[k];
+        const void *data = image ? packed->data : planar->data[f];
+        const long long stride = image ? packed->stride : planar->stride[f];
+        const long long fstride = image ? packed->frame_stride : planar->frame_stride[f];
+        if (!data) { set_error("null plane %d", f); return LUTR_EINVAL; }
+        if (src) { P->s[k] = (const uint8_t *)data; P->ss[k] = stride; P->sfs[k] = fstride; }
+        else { P->d[k] = (uint8_t *)data; P->ds[k] = stride; P->dfs[k] = fstride; }
+        sp[k] = plane_span(data, stride, fstride, G.h, (long long)G.w * Y.step * (Y.wide ? 2 : 1), G.nframes);
+    }
+    *n = image ? 1 : 3;
+    return LUTR_OK;
+}
+
 int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dither, int src_kind, int w, int h, int nframes,
                           const lutr_planes *src_planar, const lutr_packed *src_packed, const lutr_planes *dst, int row0, int rows)
 {
     if (const int rc = check_dither(dither)) return rc;
-    const bool packed = src_kind != 0;
-    const void *src = packed ? (const void *)src_packed : (const void *)src_planar;
+    const void *src = src_kind ? (const void *)src_packed : (const void *)src_planar;
     int rc = check_common(c, interp, LUTR_INTERP_NONE, w, h, nframes, src, dst, row0, rows);
     if (rc) return rc;
     if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
     YuvConsts K;
     rc = make_yuv_consts_rgb2yuv(*p, &K);
     if (rc) return rc;
-    const int dl = p->lut_depth, dout = LUTR_FMT_DEPTH(p->fmt_out);
-    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
-    RgbLayout Y{1, dl > 8, 0, 0, 0};
-    if (packed) {
-        PackedFmt f;
-        if (const int rc = decode_packed(src_kind, &f)) return rc;
-        if (dl != f.bits) { set_error("lut_depth %d must be the packed source's depth %d", dl, f.bits); return LUTR_EINVAL; }
-        Y = RgbLayout{f.nc, f.bits == 16, f.ro, f.go, f.bo};
-    }
+    const int dl = p->lut_depth;
+    const Side D = planar_side("destination", dst, p->fmt_out);
+    RgbLayout Y;
+    if (const int rc = rgb_side_layout(src_kind, dl, "source", &Y)) return rc;
     if (const int rc = check_dither_rows(dither, row0, rows, h)) return rc;
-    const int bh = 1 << ocsy;
-    if (const int rc = check_row_blocks(row0, rows, h, bh, "output chroma block height")) return rc;
+    if (const int rc = check_row_blocks(row0, rows, h, 1 << D.csy, "output chroma block height")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    // source streams in R, G, B order: gbrp planes are G, B, R
-    PlaneSet P{};
-    const long long bsi = Y.wide ? 2 : 1;
-    if (packed) {
-        if (!src_packed->data) { set_error("null image"); return LUTR_EINVAL; }
-        if (Y.wide && !check_aligned(src_packed->data, src_packed->stride, src_packed->frame_stride, nframes, 1)) {
-            set_error("16-bit packed formats need 2-byte aligned rows");
-            return LUTR_EINVAL;
-        }
-        for (int k = 0; k < 3; k++) {
-            P.s[k] = (const uint8_t *)src_packed->data; P.ss[k] = src_packed->stride; P.sfs[k] = src_packed->frame_stride;
-        }
-    } else {
-        for (int i = 0; i < 3; i++) {
-            P.s[i] = (const uint8_t *)src_planar->data[i]; P.ss[i] = src_planar->stride[i]; P.sfs[i] = src_planar->frame_stride[i];
-        }
-        P = gbrp_to_rgb(P);
-        for (int k = 0; k < 3; k++)
-            if (!P.s[k]) { set_error("null plane %d", kGbrpToRgb[k]); return LUTR_EINVAL; }
-    }
+    PlaneSet P{}; Span ss[3], ds[3]; int ns; const FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = rgb_side_streams(Y, src_planar, src_packed, G, true, &P, ss, &ns)) return rc;
     if (const int rc = check_planes_set(dst, nullptr)) return rc;
     for (int i = 0; i < 3; i++) { P.d[i] = (uint8_t *)dst->data[i]; P.ds[i] = dst->stride[i]; P.dfs[i] = dst->frame_stride[i]; }
     // a chroma sample is written by one thread while another may still read the pixels of its block: no in-place operation
-    Span ss[3], ds[3];
-    for (int i = 0; i < 3; i++) ss[i] = plane_span(P.s[i], P.ss[i], P.sfs[i], h, (long long)w * Y.step * bsi, nframes);
-    planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
-    if (const int rc = check_disjoint("RGB -> YUV", false, ss, packed ? 1 : 3, ds, 3)) return rc;
+    side_spans(D, G, ds);
+    if (const int rc = check_disjoint("RGB -> YUV", false, ss, ns, ds, 3)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
     LutConsts L{};
-    FrameGeom G{w, h, row0, rows, nframes};
     if (interp != LUTR_INTERP_NONE)
         if (const int rc = fill_lut(&L, c, dl)) return rc;
     if (dither == LUTR_DITHER_NONE)
-        return finish_launch(c, launch_rgb2yuv(c->stream, c->variant, L, K, P, Y, G, dout, ocsx, ocsy, interp));
+        return finish_launch(c, launch_rgb2yuv(c->stream, c->variant, L, K, P, Y, G, D.depth, D.csx, D.csy, interp));
     if (dither == LUTR_DITHER_BLUE_NOISE) {
         const float *bn;
         if (const int rc = bn_table(c, &bn)) return rc;
-        return finish_launch(c, launch_rgb2yuv_bn(c->stream, c->variant, L, K, P, Y, G, bn, dout, ocsx, ocsy, interp));
+        return finish_launch(c, launch_rgb2yuv_bn(c->stream, c->variant, L, K, P, Y, G, bn, D.depth, D.csx, D.csy, interp));
     }
     FloatPlanes F;
-    if (const int rc = dither_scratch(c, G, ocsx, ocsy, &F)) return rc;
-    return finish_launch(c, launch_rgb2yuv_dither(c->stream, L, K, P, Y, G, F, dout, ocsx, ocsy, interp));
+    if (const int rc = dither_scratch(c, G, D.csx, D.csy, &F)) return rc;
+    return finish_launch(c, launch_rgb2yuv_dither(c->stream, L, K, P, Y, G, F, D.depth, D.csx, D.csy, interp));
 }
 
 int lutr_apply_yuv_to_rgb(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dst_kind, int w, int h, int nframes,
                           const lutr_planes *src, const lutr_planes *dst_planar, const lutr_packed *dst_packed, int row0, int rows)
 {
-    const bool packed = dst_kind != 0;
-    const void *dst = packed ? (const void *)dst_packed : (const void *)dst_planar;
+    const void *dst = dst_kind ? (const void *)dst_packed : (const void *)dst_planar;
     int rc = check_common(c, interp, LUTR_INTERP_NONE, w, h, nframes, src, dst, row0, rows);
     if (rc) return rc;
     if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
     YuvConsts K;
     rc = make_yuv_consts_yuv2rgb(*p, &K);
     if (rc) return rc;
-    const int din = LUTR_FMT_DEPTH(p->fmt_in), dl = p->lut_depth;
-    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
-    RgbLayout Y{1, dl > 8, 0, 0, 0};
-    if (packed) {
-        PackedFmt f;
-        if (const int rc = decode_packed(dst_kind, &f)) return rc;
-        if (dl != f.bits) { set_error("lut_depth %d must be the packed destination's depth %d", dl, f.bits); return LUTR_EINVAL; }
-        Y = RgbLayout{f.nc, f.bits == 16, f.ro, f.go, f.bo};
-    }
-    const int bh = 1 << icsy;
-    if (const int rc = check_row_blocks(row0, rows, h, bh, "chroma block height")) return rc;
+    const int dl = p->lut_depth;
+    const Side S = planar_side("source", src, p->fmt_in);
+    RgbLayout Y;
+    if (const int rc = rgb_side_layout(dst_kind, dl, "destination", &Y)) return rc;
+    if (const int rc = check_row_blocks(row0, rows, h, 1 << S.csy, "chroma block height")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
     if (const int rc = check_planes_set(src, nullptr)) return rc;
-    // destination streams in R, G, B order: gbrp planes are G, B, R
-    PlaneSet P{};
-    const long long bso = Y.wide ? 2 : 1;
+    PlaneSet P{}; Span ss[3], ds[3]; int nd; const FrameGeom G{w, h, row0, rows, nframes};
     for (int i = 0; i < 3; i++) { P.s[i] = (const uint8_t *)src->data[i]; P.ss[i] = src->stride[i]; P.sfs[i] = src->frame_stride[i]; }
-    if (packed) {
-        if (!dst_packed->data) { set_error("null image"); return LUTR_EINVAL; }
-        if (Y.wide && !check_aligned(dst_packed->data, dst_packed->stride, dst_packed->frame_stride, nframes, 1)) {
-            set_error("16-bit packed formats need 2-byte aligned rows");
-            return LUTR_EINVAL;
-        }
-        for (int k = 0; k < 3; k++) { P.d[k] = (uint8_t *)dst_packed->data; P.ds[k] = dst_packed->stride; P.dfs[k] = dst_packed->frame_stride; }
-    } else {
-        for (int k = 0; k < 3; k++) {
-            const int f = kGbrpToRgb[k];
-            P.d[k] = (uint8_t *)dst_planar->data[f]; P.ds[k] = dst_planar->stride[f]; P.dfs[k] = dst_planar->frame_stride[f];
-            if (!P.d[k]) { set_error("null plane %d", f); return LUTR_EINVAL; }
-        }
-    }
+    if (const int rc = rgb_side_streams(Y, dst_planar, dst_packed, G, false, &P, ds, &nd)) return rc;
     // the two sides differ in size and layout: a thread's stores would land on samples another thread has yet to read
-    Span ss[3], ds[3];
-    planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
-    for (int i = 0; i < 3; i++) ds[i] = plane_span(P.d[i], P.ds[i], P.dfs[i], h, (long long)w * Y.step * bso, nframes);
-    if (const int rc = check_disjoint("YUV -> RGB", true, ss, 3, ds, packed ? 1 : 3)) return rc;
+    side_spans(S, G, ss);
+    if (const int rc = check_disjoint("YUV -> RGB", true, ss, 3, ds, nd)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
     LutConsts L{};
-    FrameGeom G{w, h, row0, rows, nframes};
     if (interp != LUTR_INTERP_NONE)
         if (const int rc = fill_lut(&L, c, dl)) return rc;
-    return finish_launch(c, launch_yuv2rgb(c->stream, c->variant, L, K, P, Y, G, din, icsx, icsy, interp));
+    return finish_launch(c, launch_yuv2rgb(c->stream, c->variant, L, K, P, Y, G, S.depth, S.csx, S.csy, interp));
 }
 
 // gbrpf32 planes hold 4-byte samples: base pointers, row strides and (batches) frame strides must be multiples of 4
@@ -2259,7 +2243,6 @@ int lutr_apply_planar_rgb_f32(lutr_ctx *c, int interp, int w, int h, int nframes
     if (const int rc = check_float_planes(src, nframes, "source")) return rc;
     if (const int rc = check_float_planes(dst, nframes, "destination")) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    // always strict: no kernel of this path reads the fast / fma32 lattices
     LutConsts L; FloatPre Q; PlaneSet P; FrameGeom G{w, h, row0, rows, nframes};
     if (const int rc = fill_lut_float(&L, &Q, c, true)) return rc;
     fill_planes(&P, src, dst);
@@ -2287,15 +2270,14 @@ int lutr_apply_rgbf_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, in
     PlaneSet P;
     fill_planes(&P, src, dst);
     // a chroma sample is written by one thread while another may still read the pixels of its block: no in-place operation
-    Span ss[3], ds[3];
-    planar_spans(src, 0, 0, w, h, 4, nframes, ss);
-    planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
-    if (const int rc = check_disjoint("float RGB -> YUV", true, ss, 3, ds, 3)) return rc;
+    const FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = check_sides_disjoint("float RGB -> YUV", true, planar_side("source", src, LUTR_FMT(32, 0, 0)),
+                                            planar_side("destination", dst, p->fmt_out), G)) return rc;
     // source planes in R, G, B order (gbrp planes are G, B, R); the destination stays Y, Cb, Cr
     const PlaneSet S = gbrp_to_rgb(P);
     for (int k = 0; k < 3; k++) { P.s[k] = S.s[k]; P.ss[k] = S.ss[k]; P.sfs[k] = S.sfs[k]; }
     HIP_TRY(hipSetDevice(c->device));
-    LutConsts L; FloatPre Q; FrameGeom G{w, h, row0, rows, nframes};
+    LutConsts L; FloatPre Q;
     if (const int rc = fill_lut_float(&L, &Q, c, interp != LUTR_INTERP_NONE)) return rc;
     if (dither == LUTR_DITHER_NONE)
         return finish_launch(c, launch_rgbf2yuv(c->stream, c->variant, L, Q, K, P, G, dout, ocsx, ocsy, interp));
@@ -2323,10 +2305,7 @@ int lutr_alpha_plane(lutr_ctx *c, const lutr_alpha_src *src, int dout, void *dst
         set_error("unsupported alpha depth %d on the source", (int)src->depth);
         return LUTR_EINVAL;
     }
-    if (w < 0 || h < 0 || nframes < 0 || row0 < 0 || rows < 0 || row0 + rows > h) {
-        set_error("bad geometry w=%d h=%d nframes=%d row0=%d rows=%d", w, h, nframes, row0, rows);
-        return LUTR_EINVAL;
-    }
+    if (const int rc = check_geometry(w, h, nframes, row0, rows)) return rc;
     const int din = kind == LUTR_ALPHA_INT ? src->depth : 0;
     const long long sb = kind == LUTR_ALPHA_FLOAT ? 4 : din > 8 ? 2 : 1, db = dout > 8 ? 2 : 1;
     if (kind != LUTR_ALPHA_NONE) {
@@ -2405,42 +2384,31 @@ int lutr_apply_yuv_premul(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
     if (rc) return rc;
     if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
     if (!alpha) { set_error("null alpha source"); return LUTR_EINVAL; }
-    YuvConsts K;
-    rc = make_yuv_consts_xsub(*p, &K);
-    if (rc) return rc;
-    const int icsx = LUTR_FMT_CSX(p->fmt_in), icsy = LUTR_FMT_CSY(p->fmt_in);
-    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
-    const int din = LUTR_FMT_DEPTH(p->fmt_in), dout = LUTR_FMT_DEPTH(p->fmt_out);
-    if (p->range_src != p->range_in || p->lut_depth != din) {
+    UnionCall U; const FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = union_open(*p, src, dst, &U)) return rc;
+    const Side &S = U.side[0], &D = U.side[1];
+    if (p->range_src != p->range_in || p->lut_depth != S.depth) {
         set_error("premultiplied alpha: a call with a prologue (range_src != range_in, or lut_depth %d other than the source's depth "
-                  "%d) has no alpha to carry", p->lut_depth, din);
+                  "%d) has no alpha to carry", p->lut_depth, S.depth);
         return LUTR_EINVAL;
     }
-    if (const int rc = check_premul_alpha("premultiplied alpha", alpha, LUTR_ALPHA_INT, din, nframes)) return rc;
-    if (const int rc = check_row_blocks(row0, rows, h, 1 << std::max(icsy, ocsy), "union chroma block height")) return rc;
-    if (c->variant == VAR_VEC_LDS) { set_error("variant vec_lds: there is no LDS-window kernel for premultiplied alpha"); return LUTR_EINVAL; }
+    if (const int rc = check_premul_alpha("premultiplied alpha", alpha, LUTR_ALPHA_INT, S.depth, nframes)) return rc;
+    if (const int rc = union_rules(c, U, G, nullptr, "premultiplied alpha")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    if (const int rc = check_planes_set(src, dst)) return rc;
-    const struct { const char *side; const lutr_planes *pl; int depth; } sides[2] = {{"source", src, din}, {"destination", dst, dout}};
-    for (const auto &s : sides)
-        for (int i = 0; i < 3; i++)
-            if (s.depth > 8 && !check_aligned(s.pl->data[i], s.pl->stride[i], s.pl->frame_stride[i], nframes, 1)) {
-                set_error("%s plane %d: 16-bit planes need 2-byte aligned rows", s.side, i);
-                return LUTR_EINVAL;
-            }
+    if (const int rc = union_planes_ready(U, G)) return rc;
     // not in place: the three colour planes and the alpha plane (source plane 3 in the message) against every colour destination
     Span ss[4], ds[3];
-    planar_spans(src, icsx, icsy, w, h, din > 8 ? 2 : 1, nframes, ss);
-    ss[3] = plane_span(alpha->data, alpha->stride, alpha->frame_stride, h, (long long)w * (din > 8 ? 2 : 1), nframes);
-    planar_spans(dst, ocsx, ocsy, w, h, dout > 8 ? 2 : 1, nframes, ds);
+    side_spans(S, G, ss);
+    ss[3] = plane_span(alpha->data, alpha->stride, alpha->frame_stride, h, (long long)w * (S.depth > 8 ? 2 : 1), nframes);
+    side_spans(D, G, ds);
     if (const int rc = check_disjoint("the premultiplied-alpha pass", true, ss, 4, ds, 3)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    // always strict: fill_lut leaves the fast / fma32 lattices unset, and no kernel of this path reads them
-    LutConsts L; PremulPlanes P; FrameGeom G{w, h, row0, rows, nframes};
+    LutConsts L; PremulPlanes P;
     if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
     fill_planes(&P.p, src, dst);
     P.a = AlphaIn{(const uint8_t *)alpha->data, (long long)alpha->stride, (long long)alpha->frame_stride};
-    return finish_launch(c, launch_yuva_premul(c->stream, c->variant, L, K, P, G, din, dout, p->lut_depth, icsx, icsy, ocsx, ocsy, interp));
+    return finish_launch(c, launch_yuva_premul(c->stream, c->variant, L, U.K, P, G, S.depth, D.depth, p->lut_depth, S.csx, S.csy, D.csx,
+                                               D.csy, interp));
 }
 
 // lutr_apply_planar_rgb_f32's pass with the division by alpha in front of lut3d and the multiplication behind it.
@@ -2466,7 +2434,6 @@ int lutr_apply_planar_rgb_f32_premul(lutr_ctx *c, int interp, int w, int h, int 
             return LUTR_EINVAL;
         }
     HIP_TRY(hipSetDevice(c->device));
-    // always strict: no kernel of this path reads the fast / fma32 lattices
     LutConsts L; FloatPre Q; PremulPlanes P; FrameGeom G{w, h, row0, rows, nframes};
     if (const int rc = fill_lut_float(&L, &Q, c, true)) return rc;
     fill_planes(&P.p, src, dst);
@@ -2555,8 +2522,8 @@ int lutr_resize_planes(lutr_ctx *c, int family, int depth, int csx, int csy, int
     }
     // every destination sample reads a neighbourhood of source samples: no destination may overlap a source
     Span ss[3], ds[3];
-    planar_spans(src, csx, csy, sw, sh, es, nframes, ss);
-    planar_spans(dst, csx, csy, dw, dh, es, nframes, ds);
+    side_spans(planar_side("source", src, LUTR_FMT(depth, csx, csy)), FrameGeom{sw, sh, 0, sh, nframes}, ss);
+    side_spans(planar_side("destination", dst, LUTR_FMT(depth, csx, csy)), FrameGeom{dw, dh, 0, dh, nframes}, ds);
     if (const int rc = check_disjoint("resize", true, ss, 3, ds, 3)) return rc;
     if (es == 2)
         for (int i = 0; i < 3; i++)
