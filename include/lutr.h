@@ -759,7 +759,8 @@ enum lutr_stage_kind {
     LUTR_STAGE_LUT3D   = 1,   /* the context's first lattice (lutr_ctx_set_lut), its .csp prelut taken where the pixel is a code */
     LUTR_STAGE_LUT3D_2 = 2,   /* the second lattice (lutr_ctx_set_lut2); never a prelut */
     LUTR_STAGE_LUT1D   = 3,   /* the context's 1D LUT (lutr_ctx_set_lut1d) */
-    LUTR_STAGE_CDL     = 4    /* the `cdl` argument of the call */
+    LUTR_STAGE_CDL     = 4,   /* the `cdl` argument of the call */
+    LUTR_STAGE_MATRIX  = 5    /* the `mtx` argument of lutr_apply_yuv_stack_matrix; the other stack entries refuse it by name */
 };
 typedef struct lutr_stage {
     int32_t kind;             /* enum lutr_stage_kind */
@@ -866,6 +867,42 @@ typedef struct lutr_matte {
 int lutr_apply_yuv_stack_matte(lutr_ctx *ctx, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
                                float strength, const float *frame_strength, const lutr_matte *matte, int w, int h, int nframes,
                                const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
+
+/* ---- an RGB matrix stage in the stack: the 3x3 matrix with offset of a colour pipeline -- a gamut conversion
+ *      between a camera curve and a working space (lut1d, matrix, lut3d), a white-balance or channel-mixer trim ahead of the
+ *      show LUT, a channel swap. ----
+ * lutr_apply_yuv_stack's pass with one more stage kind, LUTR_STAGE_MATRIX, at most once in the list of 1..4 stages, in any
+ * position; its resource is the `mtx` argument of the call, as the CDL is `cdl`.  m is row-major: row 0 gives R', row 1 G', row 2
+ * B', from (R, G, B).  The stage takes a pixel in either state and produces UNIT floats.  With M = 2^lut_depth - 1, in fp32 with
+ * every operation rounded on its own (no contraction):
+ *   u_c = q_c * rcp                           from codes; rcp = 1.0f / (float)M, formed once on the host: the float the identity
+ *                                             CDL's table holds for code q_c
+ *   u_c = o_c                                 from unit
+ *   t_r = ((m[0] * u_r + m[1] * u_g) + m[2] * u_b) + offset[0]        likewise t_g (row 1), t_b (row 2)
+ *   o_c = min(max(t_c, 0), 1)
+ * Behind it: a lut3d / lut3d2 stage runs in its unit form, as behind the CDL (LUTR_STAGE_LUT3D with a .csp prelut is refused
+ * there, as behind the CDL); LUTR_STAGE_LUT1D and the end of the list take the unit -> codes rounding of lutr_apply_yuv_stack; and
+ * so does LUTR_STAGE_CDL, whose table is per code: {MATRIX, CDL} quantises to lut_depth bits in between.
+ * Bit for bit: {MATRIX} with the identity is {CDL} with the identity CDL, {MATRIX(I), LUT3D} is {CDL(identity), LUT3D},
+ * {LUT3D, MATRIX(I)} is {LUT3D} and {MATRIX(I), LUT1D} is {LUT1D}.
+ * Everything else -- stages 1 and 3, the prologue, layouts, depths, row rules, the overlap rule, the resources, strict
+ * arithmetic -- is lutr_apply_yuv_stack's.
+ * LUTR_EINVAL with a message, before anything touches the device: everything lutr_apply_yuv_stack refuses; a matrix stage with
+ * mtx == NULL, or mtx without a matrix stage; an entry of m or offset that is not finite or above 65536 in magnitude (which
+ * keeps every sum finite: no NaN reaches the clamp).  lutr_apply_yuv_stack, _mix and _matte refuse LUTR_STAGE_MATRIX by name.
+ * Kernels: always the matrix forms, whose twelve numbers are kernel arguments --
+ * "k_yuv_stack_mtx_vec<win,wout,icsx,icsy,ocsx,ocsy,tri,lds>[stages]", "k_yuv_stack_mtx_generic[stages]",
+ * "<vector kernel>+k_yuv_stack_mtx_generic[stages]" for a ragged width, chosen by the rules of lutr_apply_yuv_stack; the stage is
+ * "matrix" in [stages].
+ * Not covered: what lutr_apply_yuv_stack does not cover; a strength or a matte together with a matrix; a second matrix; a tile
+ * (LDS window) kernel; named gamut presets. */
+typedef struct lutr_rgb_matrix {
+    float m[9];               /* row-major */
+    float offset[3];          /* in unit floats */
+} lutr_rgb_matrix;
+int lutr_apply_yuv_stack_matrix(lutr_ctx *ctx, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                                const lutr_rgb_matrix *mtx, int w, int h, int nframes, const lutr_planes *src,
+                                const lutr_planes *dst, int row0, int rows);
 
 /* ---- the alpha plane of yuva* / gbrap* frames: ProRes 4444 (yuva444p10le / 12le), VP8 / VP9 with alpha
  *      (yuva420p), PNG / TIFF / EXR sequences with alpha (rgba, rgba64le, gbrap*, gbrapf32le).  In the reference's chain lut3d

@@ -20,6 +20,8 @@ INTERP = {"nearest": 0, "trilinear": 1, "tetrahedral": 2, "pyramid": 3, "prism":
 INTERP1D = {"nearest": 0, "linear": 1, "cosine": 2, "cubic": 3, "spline": 4}
 #: enum lutr_stage_kind: the stage kinds of a stack
 STAGE_KINDS = {"lut3d": 1, "lut3d2": 2, "lut1d": 3, "cdl": 4}
+#: the stage kinds of lutr_apply_yuv_stack_matrix alone: LUTR_STAGE_MATRIX
+MATRIX_STAGE_KINDS = {"matrix": 5}
 MATRIX = {"bt709": 0, "smpte170m": 1, "bt470bg": 1, "bt601": 1, "bt2020nc": 2, "bt2020c": 2}
 RANGE = {"tv": 0, "pc": 1}
 DITHER = {"none": 0, "error_diffusion": 1, "blue_noise": 2}
@@ -49,6 +51,7 @@ SYMBOLS = (
     "lutr_apply_yuv_premul", "lutr_apply_planar_rgb_f32_premul", "lutr_cdl_table", "lutr_apply_yuv_cdl",
     "lutr_lut1d_parse", "lutr_lut1d_table", "lutr_ctx_set_lut1d", "lutr_apply_yuv_lut1d", "lutr_apply_planar_rgb_lut1d",
     "lutr_apply_yuv_stack", "lutr_apply_yuv_stack_mix", "lutr_apply_yuv_stack_matte",
+    "lutr_apply_yuv_stack_matrix",
     "lutr_resize_filter", "lutr_resize_planes", "lutr_dither_mask",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
     "lutr_max_waves_knob", "lutr_max_blocks_knob",
@@ -108,11 +111,26 @@ class MatteStruct(C.Structure):
                 ("invert", C.c_int32)]
 
 
+class RgbMatrixStruct(C.Structure):
+    """struct lutr_rgb_matrix: the matrix of lutr_apply_yuv_stack_matrix"""
+    _fields_ = [("m", C.c_float * 9), ("offset", C.c_float * 3)]
+
+
+def rgb_matrix_struct(mtx) -> RgbMatrixStruct:
+    """struct lutr_rgb_matrix from an `rgbmatrix.RgbMatrix` (its numbers rounded to float32, as the C-ABI carries them)."""
+    st = RgbMatrixStruct()
+    for i in range(9):
+        st.m[i] = mtx.m[i]
+    for i in range(3):
+        st.offset[i] = mtx.offset[i]
+    return st
+
+
 def stage_array(stages):
     """lutr_stage[] from parsed stages ((kind name, lut3d mode name or None), ...; `formats.parse_stages`)."""
     arr = (StageStruct * len(stages))()
     for i, (kind, mode) in enumerate(stages):
-        arr[i].kind = STAGE_KINDS[kind]
+        arr[i].kind = MATRIX_STAGE_KINDS[kind] if kind in MATRIX_STAGE_KINDS else STAGE_KINDS[kind]
         arr[i].interp = 0 if mode is None else INTERP[mode]
     return arr
 
@@ -267,6 +285,8 @@ def load() -> C.CDLL:
                                              vp, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_apply_yuv_stack_matte.argtypes = [vp, C.POINTER(YuvParams), C.POINTER(StageStruct), ci, C.POINTER(CdlStruct), C.c_float,
                                                vp, C.POINTER(MatteStruct), ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
+    lib.lutr_apply_yuv_stack_matrix.argtypes = [vp, C.POINTER(YuvParams), C.POINTER(StageStruct), ci, C.POINTER(CdlStruct),
+                                                C.POINTER(RgbMatrixStruct), ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_dither_mask.argtypes = [C.POINTER(C.c_uint16)]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]

@@ -22,6 +22,7 @@ from pathlib import Path
 from typing import Dict, Optional, Sequence, Tuple
 
 from .cdl import as_cdl
+from .rgbmatrix import as_rgb_matrix
 from .cube import CubeLut, as_lut1d, read_cube, read_lut, read_lut1d
 from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc, check_container_options,
                       check_dual_options, check_lut1d_options, check_lut2, check_premul_options, check_stack_options,
@@ -235,11 +236,12 @@ def resolve_engine_dither(engine_dither: str, dither: str = "none") -> str:
 
 
 def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, engine, devices, precision,
-                 chroma_loc, out_size, alpha_mode, second_pix_fmt, strength=None, matte=None):
+                 chroma_loc, out_size, alpha_mode, second_pix_fmt, strength=None, matte=None, rgb_matrix=None):
     """`apply_lut(stages=...)`: load what the list names, with the caches the single-feature routes use, and
     route to `apply_yuv_stack`.  `kw` is what `engine_call_for` returned, with `dither` filled in.  `strength`
     travels to the engine; `stages` None is then the list the other options imply.  `matte`: None, or the dict of
-    the engine's `matte`, `matte_depth` and `matte_invert` arguments, which travels likewise."""
+    the engine's `matte`, `matte_depth` and `matte_invert` arguments, which travels likewise.  `rgb_matrix`: None,
+    an RgbMatrix or the path of a .spimtx file, the resource of a matrix stage."""
     from .plan import INTERP_WHITELIST
     from . import _native
     mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
@@ -263,13 +265,15 @@ def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d,
         lut1d = _cached_cube(Path(lut1d), read_lut1d) if isinstance(lut1d, (str, Path)) and Path(lut1d).is_file() else as_lut1d(lut1d)
     if cdl is not None:
         cdl = as_cdl(cdl, cdl_id)
+    rgb_matrix = as_rgb_matrix(rgb_matrix)
     first = engine.engines[0] if engine is not None and hasattr(engine, "engines") else engine
     held = lambda name: bool(getattr(first, name, 0))                                  # noqa: E731
     prelut = getattr(lut, "prelut", None) is not None if lut is not None else held("_has_prelut")
     check_stack_options(kw["pix_fmt"], kw["out_pix_fmt"], stages=st, cdl=cdl is not None, lut=lut is not None or held("n"),
                         lut2=lut2 is not None or held("n2"), lut1d=lut1d is not None or held("n1d"), prelut=prelut,
                         dither=kw.get("dither", "none"), chroma_loc=chroma_loc, out_size=out_size, alpha_mode=alpha_mode,
-                        out2_pix_fmt=second_pix_fmt, strength=strength, precision=precision, matte=matte is not None)
+                        out2_pix_fmt=second_pix_fmt, strength=strength, precision=precision, matte=matte is not None,
+                        rgb_matrix=rgb_matrix is not None)
     own = engine is None
     eng = engine if engine is not None else _cached_engine(devices)
     call = {k: v for k, v in kw.items() if k not in ("dither", "interp", "alpha_mode")}
@@ -291,6 +295,8 @@ def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d,
             call["strength"] = strength
         if matte is not None:
             call.update(matte)
+        if rgb_matrix is not None:
+            call["rgb_matrix"] = rgb_matrix
         result = eng.apply_yuv_stack(planes, out, stages=st, cdl=cdl, **call)
         if own:
             eng.sync()
@@ -305,7 +311,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
               cube2=None, interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None, cdl_id: Optional[str] = None,
               lut1d=None, interp1d: str = "linear", stages=None, strength=None, matte=None, matte_depth: Optional[int] = None,
-              matte_invert: bool = False, rgb_out: Optional[str] = None):
+              matte_invert: bool = False, rgb_out: Optional[str] = None, rgb_matrix=None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -415,7 +421,13 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     range takes an 8-bit `rgb_out` only.  A LutEngineGroup row-shards it; always strict arithmetic.  Not together with
     `out_pix_fmt`, and no dither, chroma_loc, resolution, premultiplied alpha, second output, second LUT, CDL, 1D LUT, stages,
     strength or matte, nor a semi-planar / packed 4:2:2 / v210 source: each is a ValueError naming it.  None (default) leaves
-    every route as it is."""
+    every route as it is.
+
+    `rgb_matrix` (a gamut conversion, a white-balance or channel-mixer trim, a channel swap) is the resource of a
+    "matrix" stage of `stages`: an `rgbmatrix.RgbMatrix` (nine numbers row-major and an offset in unit floats) or the path of a
+    .spimtx file.  The stage computes clamp(M * rgb + offset, 0, 1) on unit RGB where the list places it, e.g.
+    stages="lut1d,matrix,lut3d".  It has no implied position: `rgb_matrix` without `stages`, without a matrix stage in it, or a
+    matrix stage without `rgb_matrix` is a ValueError, and so is a strength or matte together with it."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -427,6 +439,8 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         from .multigpu import LutEngineGroup
         if isinstance(engine, LutEngineGroup) or (engine is None and len(devices) > 1):
             raise ValueError("resolution needs a single device")
+    if rgb_matrix is not None and stages is None:
+        raise ValueError("rgb_matrix needs stages: a matrix stage has no implied position (e.g. stages='lut1d,matrix,lut3d')")
     rgb_src = parse_rgb_source(pix_fmt)
     if rgb_src is not None and rgb_src.packed:
         got_w, got_h = planes.shape[-2], planes.shape[-3]
@@ -490,7 +504,8 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     if stages is not None or strength is not None or matte is not None:
         result = _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, engine, devices, precision,
                               chroma_loc, out_size, alpha_mode, second_pix_fmt, strength,
-                              None if matte is None else dict(matte=matte, matte_depth=matte_depth, matte_invert=matte_invert))
+                              None if matte is None else dict(matte=matte, matte_depth=matte_depth, matte_invert=matte_invert),
+                              rgb_matrix)
         return result, output_color_tags(plan.output_policy)
     if lut1d is not None:
         check_lut1d_options(kw["pix_fmt"], kw["out_pix_fmt"], interp1d=interp1d, dither=kw["dither"], chroma_loc=chroma_loc,

@@ -114,6 +114,16 @@ def build_parser() -> argparse.ArgumentParser:
                          "stages, a lut3d stage without a mode takes --interp / --interp2; every stage needs its file and every "
                          "file its stage; planar YUV on both sides, no dither, --chroma-loc, --out-size, --second-output or "
                          "--alpha-mode premultiplied")
+    ap.add_argument("--rgb-matrix", default=None, metavar="\"M00 M01 M02 M10 .. M22\"",
+                    help="engine setting: the nine numbers, row-major, of the RGB matrix a 'matrix' stage of --stages applies "
+                         "(DESIGN.md 3.25; a gamut conversion, a white-balance or channel-mixer trim, a channel swap): "
+                         "clamp(M * rgb + offset, 0, 1) on unit RGB, e.g. --stages lut1d,matrix,lut3d.  Needs --stages with a "
+                         "matrix stage; not together with --strength or --matte")
+    ap.add_argument("--rgb-matrix-offset", default=None, metavar="\"O O O\"",
+                    help="the offset of --rgb-matrix in unit floats (default 0 0 0)")
+    ap.add_argument("--rgb-matrix-file", default=None, metavar="PATH",
+                    help="the matrix of a 'matrix' stage from a .spimtx file (twelve numbers, row-major 3 x 4, the offset column in "
+                         "16-bit codes) instead of --rgb-matrix / --rgb-matrix-offset")
     mix = ap.add_mutually_exclusive_group()
     mix.add_argument("--strength", default=None, type=float, metavar="X",
                      help="engine setting: LUT strength in [0, 1] (DESIGN.md 3.22; the intensity / opacity control of a grade) -- "
@@ -154,25 +164,45 @@ def cdl_from_args(args):
     return read_cdl(path, cc_id) if path is not None else Cdl.from_sop_text(sop, sat)
 
 
+def rgb_matrix_from_args(args):
+    """The `rgbmatrix.RgbMatrix` the options name, or None: --rgb-matrix-file PATH, or --rgb-matrix [--rgb-matrix-offset]; a file
+    and literal values together, and an offset without its matrix, are errors."""
+    path, m, off = getattr(args, "rgb_matrix_file", None), getattr(args, "rgb_matrix", None), getattr(args, "rgb_matrix_offset", None)
+    if path is not None and (m is not None or off is not None):
+        raise ValueError("--rgb-matrix-file names a file and --rgb-matrix / --rgb-matrix-offset give literal values: use one or "
+                         "the other")
+    if off is not None and m is None:
+        raise ValueError("--rgb-matrix-offset is the offset of a matrix: it needs --rgb-matrix")
+    if path is None and m is None:
+        return None
+    from .rgbmatrix import RgbMatrix, read_rgb_matrix
+    return read_rgb_matrix(path) if path is not None else RgbMatrix.from_text(m, off)
+
+
 def stack_call_from_args(args, kw: dict, cdl) -> dict:
     """The keyword arguments of `apply_yuv_stack` for --stages from those `engine_call_for` returned: the stage
     list parsed with --interp / --interp2 as the lut3d stages' defaults, every refusal of `check_stack_options`, and a file for
     every stage and a stage for every file.  With --strength / --strength-keys and no --stages the list is the
     one the other options imply (`formats.implied_stages`); `strength` or `strength_keys` (the parsed callable) go into the call.
-    With --matte likewise; `matte` (the path), `matte_pix_fmt` and `matte_invert` go into the call."""
+    With --matte likewise; `matte` (the path), `matte_pix_fmt` and `matte_invert` go into the call.  With
+    --rgb-matrix / --rgb-matrix-file `rgb_matrix` goes into the call; it needs --stages with a matrix stage."""
     from .plan import INTERP_WHITELIST
     interp2 = getattr(args, "interp2", None)
     mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
     cube2, lut1d = getattr(args, "cube2", None), getattr(args, "lut1d", None)
     strength, keys = strength_from_args(args)
     matte = matte_from_args(args)
+    mtx = rgb_matrix_from_args(args)
     listed = getattr(args, "stages", None)
+    if mtx is not None and listed is None:
+        raise ValueError("--rgb-matrix / --rgb-matrix-file need --stages: a matrix stage has no implied position "
+                         "(e.g. --stages lut1d,matrix,lut3d)")
     if listed is None:
         listed = implied_stages(args.cube is not None, cube2 is not None, lut1d is not None, cdl is not None)
     st = parse_stages(listed, interp=kw.get("interp"), interp2=mode2)
     kinds = [k for k, _m in st]
     for flag, given, kind in (("--cube", args.cube, "lut3d"), ("--cube2", cube2, "lut3d2"), ("--lut1d", lut1d, "lut1d"),
-                              ("--cdl / --cdl-sop / --cdl-sat", cdl, "cdl")):
+                              ("--cdl / --cdl-sop / --cdl-sat", cdl, "cdl"), ("--rgb-matrix / --rgb-matrix-file", mtx, "matrix")):
         if given is not None and kind not in kinds:
             raise ValueError(f"{flag} is given and --stages has no '{kind}' stage")
     if interp2 is not None and "lut3d2" not in kinds:
@@ -182,7 +212,7 @@ def stack_call_from_args(args, kw: dict, cdl) -> dict:
     if interp1d not in _native.INTERP1D:
         raise ValueError(f"lut1d has no interpolation mode '{interp1d}' ({' | '.join(_native.INTERP1D)})")
     prelut = False
-    if "cdl" in kinds and args.cube is not None and os.path.isfile(args.cube):
+    if ("cdl" in kinds or "matrix" in kinds) and args.cube is not None and os.path.isfile(args.cube):
         from pathlib import Path
         from . import engine  # noqa: F401  (torch first, as in plan_from_args)
         from .api import _cached_cube
@@ -196,11 +226,13 @@ def stack_call_from_args(args, kw: dict, cdl) -> dict:
                         alpha_mode=getattr(args, "alpha_mode", None) or "straight",
                         out2_pix_fmt=second_fmt if second_fmt is not None else second_out,
                         strength=strength if keys is None else 1.0, precision=getattr(args, "precision", None),
-                        matte=matte is not None)
+                        matte=matte is not None, rgb_matrix=mtx is not None)
     call = {k: v for k, v in kw.items() if k not in ("interp", "alpha_mode", "dither")}
     call["stages"] = st
     if cdl is not None:
         call["cdl"] = cdl
+    if mtx is not None:
+        call["rgb_matrix"] = mtx
     if strength is not None:
         call["strength"] = strength
     if keys is not None:
@@ -269,6 +301,9 @@ def plan_from_args(args):
                               out2_pix_fmt=second if second is not None else getattr(args, "second_output", None),
                               cube2=getattr(args, "cube2", None), interp2=getattr(args, "interp2", None))
         return plan, kw, w, h
+    if stages is None and rgb_matrix_from_args(args) is not None:
+        raise ValueError("--rgb-matrix / --rgb-matrix-file need --stages: a matrix stage has no implied position "
+                         "(e.g. --stages lut1d,matrix,lut3d)")
     kw = engine_call_for(plan, args.pix_fmt, args.out_pix_fmt, alpha_mode)
     from .api import is_float_out_call
     engine_dither = getattr(args, "engine_dither", None)

@@ -259,7 +259,7 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                    cdl=None, cdl_id: Optional[str] = None, lut1d: Optional[Path] = None,
                    interp1d: Optional[str] = None, stages=None, strength: Optional[float] = None,
                    strength_keys: Optional[str] = None, matte: Optional[Path] = None, matte_pix_fmt: Optional[str] = None,
-                   matte_invert: bool = False) -> List[str]:
+                   matte_invert: bool = False, rgb_matrix=None) -> List[str]:
     """`build_command`'s twin for the LUT stage alone: the argv of the ENGINE CLI (`python -m lut_renderer_amd.cli`)
     that applies exactly the chain `build_command` would put into `-vf` -- the same `LutPlan`, rendered as CLI options
     instead of as a filter string (ffmpeg.py:195-247, :287-310).  `source` / `output` are rawvideo files (or `-`) in
@@ -301,7 +301,10 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     `matte_pix_fmt` (gray | gray10le | gray12le | gray14le | gray16le, default gray) and `matte_invert` are engine settings
     likewise: a strength per pixel in the same pass (`--matte`, `--matte-pix-fmt`, `--matte-invert`, rendered only when given).
     They run the stage stack as a strength does, in refusals that name the matte; `-` is refused, and so are `matte_pix_fmt` /
-    `matte_invert` without `matte`."""
+    `matte_invert` without `matte`.
+    `rgb_matrix` is the resource of a `matrix` stage of `stages`, an engine setting as well: an
+    `rgbmatrix.RgbMatrix` (`--rgb-matrix`, and `--rgb-matrix-offset` unless it is zero) or the path of a .spimtx file
+    (`--rgb-matrix-file`); rendered only when given.  It needs `stages` with a matrix stage, and the stage needs it."""
     import sys as _sys
     premul = check_alpha_mode(alpha_mode)
     if precision not in ("strict", "fast", "fma32"):
@@ -393,6 +396,8 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
             raise ValueError("matte is a file or FIFO, not '-': stdin carries the input")
         if (matte_pix_fmt or "gray") not in MATTE_PIX_FMTS:
             raise ValueError(f"unknown matte_pix_fmt '{matte_pix_fmt}' ({' | '.join(MATTE_PIX_FMTS)})")
+    if rgb_matrix is not None and stages is None:
+        raise ValueError("rgb_matrix needs stages: a matrix stage has no implied position (e.g. stages='lut1d,matrix,lut3d')")
     stack = stages is not None or mixed or matte is not None      # the pairwise refusals below give way to check_stack_options at the end
     if cube2 is not None:
         from .plan import INTERP_WHITELIST
@@ -452,14 +457,24 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
         if (interp1d or "linear") not in _native.INTERP1D:
             raise ValueError(f"lut1d has no interpolation mode '{interp1d}' ({' | '.join(_native.INTERP1D)})")
         for name, given, kind in (("the LUT", lut_path, "lut3d"), ("cube2", cube2, "lut3d2"), ("lut1d", lut1d, "lut1d"),
-                                  ("cdl", cdl, "cdl")):
+                                  ("cdl", cdl, "cdl"), ("rgb_matrix", rgb_matrix, "matrix")):
             if given is not None and kind not in kinds:
                 raise ValueError(f"{name} is given and the stage list has no '{kind}' stage")
         check_stack_options(str(source_info.pix_fmt).replace("yuvj", "yuv"), pix_fmt or None, stages=st, cdl=cdl is not None,
                             lut=True, lut2=cube2 is not None, lut1d=lut1d is not None, dither=dither, chroma_loc=chroma_loc,
                             out_size=params.resolution if "--out-size" in cmd else None, alpha_mode=alpha_mode,
                             out2_pix_fmt=second_pix_fmt, strength=(strength if strength_keys is None else 1.0) if mixed else None,
-                            precision=precision, matte=matte is not None)
+                            precision=precision, matte=matte is not None, rgb_matrix=rgb_matrix is not None)
+        if rgb_matrix is not None:
+            from .rgbmatrix import RgbMatrix
+            if isinstance(rgb_matrix, RgbMatrix):
+                cmd += ["--rgb-matrix", rgb_matrix.m_text()]
+                if rgb_matrix.offset != (0.0, 0.0, 0.0):
+                    cmd += ["--rgb-matrix-offset", rgb_matrix.offset_text()]
+            elif isinstance(rgb_matrix, (str, Path)):
+                cmd += ["--rgb-matrix-file", str(rgb_matrix)]
+            else:
+                raise TypeError(f"rgb_matrix must be an RgbMatrix or the path of a .spimtx file, not {type(rgb_matrix).__name__}")
         if stages is not None:
             cmd += ["--stages", stages_string(st)]
         if strength is not None:

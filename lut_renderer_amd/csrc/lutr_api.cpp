@@ -1702,24 +1702,48 @@ int lutr_apply_yuv_lut1d(lutr_ctx *c, const lutr_yuv_params *p, int interp, int 
     return finish_launch(c, launch_yuv_l1d(c->stream, c->variant, L, C, U.K, P, G, S.depth, D.depth, S.csx, S.csy, D.csx, D.csy, interp));
 }
 
+// The matrix of lutr_apply_yuv_stack_matrix: every entry finite and at most 65536 in magnitude, so that every sum of the stage is
+// finite.  The test is on the bits (this file is built without honouring NaNs): 65536.0f is 0x47800000.
+static int check_rgb_matrix(const lutr_rgb_matrix *mtx)
+{
+    for (int i = 0; i < 12; i++) {
+        const float v = i < 9 ? mtx->m[i] : mtx->offset[i - 9];
+        uint32_t bits;
+        memcpy(&bits, &v, sizeof bits);
+        if ((bits & 0x7fffffffu) > 0x47800000u) {
+            if (i < 9) set_error("stack: matrix entry m[%d] = %g is not finite or above 65536 in magnitude", i, (double)v);
+            else set_error("stack: matrix entry offset[%d] = %g is not finite or above 65536 in magnitude", i - 9, (double)v);
+            return LUTR_EINVAL;
+        }
+    }
+    return LUTR_OK;
+}
+
 // ---- an ordered stack of lut1d / CDL / lut3d stages
 // lutr_apply_yuv_cdl's pass with the stage list compiled into steps: the pixel's state (codes or unit) is followed here, so the
 // kernels are told which form of a lattice stage to run and where the rounding goes.
 // `mix`: nullptr for lutr_apply_yuv_stack, the strength for lutr_apply_yuv_stack_mix.
 // `matte` (with `mix`): the matte of lutr_apply_yuv_stack_matte, its pointer, depth and invert already checked.
+// `with_mtx` (without `mix`): the call is lutr_apply_yuv_stack_matrix's, the one entry that takes a matrix stage;
+// `mtx` is its matrix, or nullptr.
 static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
-                           const MixConsts *mix, const lutr_matte *matte, int w, int h, int nframes, const lutr_planes *src,
-                           const lutr_planes *dst, int row0, int rows)
+                           const MixConsts *mix, const lutr_matte *matte, bool with_mtx, const lutr_rgb_matrix *mtx, int w, int h,
+                           int nframes, const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
 {
     if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
     if (nstages < 1 || nstages > 4) { set_error("stack: %d stages; a stack has 1 to 4", nstages); return LUTR_EINVAL; }
     if (!stages) { set_error("stack: null stage list"); return LUTR_EINVAL; }
-    static const char *const kind_name[5] = {"", "lut3d", "lut3d2", "lut1d", "cdl"};
-    bool seen[5] = {false, false, false, false, false};
+    static const char *const kind_name[6] = {"", "lut3d", "lut3d2", "lut1d", "cdl", "matrix"};
+    bool seen[6] = {false, false, false, false, false, false};
     std::string list;
     for (int i = 0; i < nstages; i++) {
         const int k = stages[i].kind;
-        if (k < LUTR_STAGE_LUT3D || k > LUTR_STAGE_CDL) { set_error("stack: stage %d has unknown kind %d", i, k); return LUTR_EINVAL; }
+        if (k < LUTR_STAGE_LUT3D || k > LUTR_STAGE_MATRIX) { set_error("stack: stage %d has unknown kind %d", i, k); return LUTR_EINVAL; }
+        if (k == LUTR_STAGE_MATRIX && !with_mtx) {
+            set_error("stack: stage %d is a matrix stage; a matrix is lutr_apply_yuv_stack_matrix's, and a strength or a matte "
+                      "together with a matrix is not supported", i);
+            return LUTR_EINVAL;
+        }
         if (seen[k]) { set_error("stack: stage kind %s is listed twice; each kind may appear once", kind_name[k]); return LUTR_EINVAL; }
         seen[k] = true;
         if (i) list += ",";
@@ -1745,8 +1769,12 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
     if (!seen[LUTR_STAGE_CDL] && cdl) { set_error("stack: a CDL is given and no cdl stage is listed"); return LUTR_EINVAL; }
     if (cdl)
         if (const int rc = check_cdl(cdl)) return rc;
+    if (seen[LUTR_STAGE_MATRIX] && !mtx) { set_error("stack: a matrix stage is listed and the matrix is null"); return LUTR_EINVAL; }
+    if (!seen[LUTR_STAGE_MATRIX] && mtx) { set_error("stack: a matrix is given and no matrix stage is listed"); return LUTR_EINVAL; }
+    if (mtx)
+        if (const int rc = check_rgb_matrix(mtx)) return rc;
     if (const int rc = check_geometry(w, h, nframes, row0, rows)) return rc;
-    // the steps: a unit pixel is rounded to codes ahead of lut1d and at the end of the list
+    // the steps: a unit pixel is rounded to codes ahead of lut1d, ahead of the CDL (behind a matrix) and at the end of the list
     unsigned long long ops = 0;
     int nops = 0;
     bool unit = false;
@@ -1759,13 +1787,22 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
             unit = false;
             break;
         case LUTR_STAGE_CDL:
-            push(STACK_OP_CDL, 0);       // each kind once: the pixel is a code here
+            if (unit) push(STACK_OP_ROUND, 0);   // behind a matrix only: the CDL's table is per code
+            push(STACK_OP_CDL, 0);
+            unit = true;
+            break;
+        case LUTR_STAGE_MATRIX:
+            push(unit ? STACK_OP_MTX_UNIT : STACK_OP_MTX_CODES, 0);
             unit = true;
             break;
         case LUTR_STAGE_LUT3D:
             if (unit && c->pre_size) {
-                set_error("stack: lut3d directly behind cdl, and the LUT has a .csp prelut; its table is indexed by integer codes, and "
-                          "the CDL's output is not a code");
+                if (stages[i - 1].kind == LUTR_STAGE_MATRIX)
+                    set_error("stack: lut3d directly behind matrix, and the LUT has a .csp prelut; its table is indexed by integer "
+                              "codes, and the matrix's output is not a code");
+                else
+                    set_error("stack: lut3d directly behind cdl, and the LUT has a .csp prelut; its table is indexed by integer codes, and "
+                              "the CDL's output is not a code");
                 return LUTR_EINVAL;
             }
             push(unit ? STACK_OP_LAT_UNIT : STACK_OP_LAT_CODES, stages[i].interp);
@@ -1831,9 +1868,15 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
         S.l1d_tab = C1.tab;
         S.lds_l1d_words = 3 * (S.stride >> 1);
     }
+    MtxConsts X{};
+    if (mtx) {
+        for (int i = 0; i < 9; i++) X.m[i] = mtx->m[i];
+        for (int i = 0; i < 3; i++) X.off[i] = mtx->offset[i];
+        X.rcp = 1.0f / S.maxf;
+    }
     fill_planes(&P, src, dst);
     const char *name = launch_yuv_stack(c->stream, c->variant, L, L2, S, U.K, P, G, Si.depth, Di.depth, Si.csx, Si.csy, Di.csx, Di.csy, mix,
-                                        matte ? &A : nullptr);
+                                        matte ? &A : nullptr, with_mtx ? &X : nullptr);
     if (!name) return finish_launch(c, nullptr);
     const std::string full = std::string(name) + "[" + list + "]";
     return finish_launch(c, full.c_str());
@@ -1842,7 +1885,15 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
 int lutr_apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl, int w,
                          int h, int nframes, const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
 {
-    return apply_yuv_stack(c, p, stages, nstages, cdl, nullptr, nullptr, w, h, nframes, src, dst, row0, rows);
+    return apply_yuv_stack(c, p, stages, nstages, cdl, nullptr, nullptr, false, nullptr, w, h, nframes, src, dst, row0, rows);
+}
+
+// ---- the stack with an RGB matrix stage: the same pass, the matrix kernels whatever the list
+int lutr_apply_yuv_stack_matrix(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                                const lutr_rgb_matrix *mtx, int w, int h, int nframes, const lutr_planes *src,
+                                const lutr_planes *dst, int row0, int rows)
+{
+    return apply_yuv_stack(c, p, stages, nstages, cdl, nullptr, nullptr, true, mtx, w, h, nframes, src, dst, row0, rows);
 }
 
 // The strength of the mix and matte entries: the scalar is read only without the array; a NaN is found by its bits (this file is
@@ -1865,7 +1916,7 @@ int lutr_apply_yuv_stack_mix(lutr_ctx *c, const lutr_yuv_params *p, const lutr_s
 {
     if (const int rc = check_strength(strength, frame_strength)) return rc;
     const MixConsts M{frame_strength, frame_strength ? 1.0f : strength};
-    return apply_yuv_stack(c, p, stages, nstages, cdl, &M, nullptr, w, h, nframes, src, dst, row0, rows);
+    return apply_yuv_stack(c, p, stages, nstages, cdl, &M, nullptr, false, nullptr, w, h, nframes, src, dst, row0, rows);
 }
 
 // ---- the stack with a matte scaling the strength per pixel: the same pass, the matte kernels whatever the matte
@@ -1882,7 +1933,7 @@ int lutr_apply_yuv_stack_matte(lutr_ctx *c, const lutr_yuv_params *p, const lutr
         return LUTR_EINVAL;
     }
     const MixConsts M{frame_strength, frame_strength ? 1.0f : strength};
-    return apply_yuv_stack(c, p, stages, nstages, cdl, &M, matte, w, h, nframes, src, dst, row0, rows);
+    return apply_yuv_stack(c, p, stages, nstages, cdl, &M, matte, false, nullptr, w, h, nframes, src, dst, row0, rows);
 }
 
 int lutr_apply_planar_rgb_lut1d(lutr_ctx *c, int depth, int w, int h, int nframes, const lutr_planes *src, const lutr_planes *dst,

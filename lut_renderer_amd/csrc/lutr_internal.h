@@ -196,10 +196,12 @@ enum StackOp {
     STACK_OP_LAT2_UNIT  = 4,
     STACK_OP_L1D        = 5,     // codes -> codes through the 1D table
     STACK_OP_CDL        = 6,     // codes -> unit: cdl_px
-    STACK_OP_ROUND      = 7      // unit -> codes: (int)(o * maxf + 0.5f)
+    STACK_OP_ROUND      = 7,     // unit -> codes: (int)(o * maxf + 0.5f)
+    STACK_OP_MTX_CODES  = 8,     // the RGB matrix on codes (codes -> unit) and on unit floats (unit -> unit): the matrix forms of
+    STACK_OP_MTX_UNIT   = 9      // the kernels only
 };
 struct StackConsts {
-    unsigned long long ops;      // at most 5 steps: four stages and one rounding
+    unsigned long long ops;      // at most 6 steps: four stages and two roundings (matrix, cdl, lut1d, lut3d)
     const float    *cdl_tab;     // CdlConsts::tab, or nullptr when no step reads it
     const uint16_t *l1d_tab;     // L1dConsts::tab, likewise
     int   stride;                // 2^lut_depth
@@ -227,11 +229,29 @@ struct MatteConsts {
     int   invert;
     int   wide;                  // 16-bit words
 };
+// The RGB matrix of a matrix step: twelve numbers and the host's 1.0f / maxf, passed by value -- wave-uniform, no
+// table.  t_r = ((m[0] * u_r + m[1] * u_g) + m[2] * u_b) + off[0], rows 1 and 2 likewise; u = q * rcp on codes.
+struct MtxConsts {
+    float m[9];
+    float off[3];
+    float rcp;
+};
 // M = nullptr: the kernels of 3.21; else their mix forms (k_yuv_stack_mix_vec / k_yuv_stack_mix_generic), whatever the strength;
-// A (with M): their matte forms (k_yuv_stack_matte_vec / k_yuv_stack_matte_generic), whatever the matte
+// A (with M): their matte forms (k_yuv_stack_matte_vec / k_yuv_stack_matte_generic), whatever the matte;
+// X (without M and A): the matrix forms (k_yuv_stack_mtx_vec / k_yuv_stack_mtx_generic), the only ones with the matrix steps
 const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
                              const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int din, int dout, int icsx, int icsy,
-                             int ocsx, int ocsy, const MixConsts *M, const MatteConsts *A);
+                             int ocsx, int ocsy, const MixConsts *M, const MatteConsts *A, const MtxConsts *X = nullptr);
+const char *launch_yuv_stack_mtx_generic(hipStream_t st, unsigned grid, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
+                                         const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const MtxConsts &X, int win,
+                                         int wout, int icsx, int icsy, int ocsx, int ocsy);
+// the matrix vector kernels, one translation unit per container mix (w<in wide><out wide>)
+#define LUTR_SKX_DECL(tag) \
+    const char *launch_yuv_stack_mtx_vec_##tag(hipStream_t st, const LutConsts &L, const LutConsts &L2, const StackConsts &S, \
+                                               const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int icsx, int icsy, \
+                                               int ocsx, int ocsy, bool tri, bool lds, MtxConsts X);
+LUTR_SKX_DECL(w00) LUTR_SKX_DECL(w11) LUTR_SKX_DECL(w10)
+#undef LUTR_SKX_DECL
 const char *launch_yuv_stack_matte_generic(hipStream_t st, unsigned grid, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
                                            const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const MixConsts &M,
                                            const MatteConsts &A, int win, int wout, int icsx, int icsy, int ocsx, int ocsy);

@@ -24,6 +24,8 @@
 //   LUTR_SKA_WI / _WO / _WM   the vector kernels in their MATTE form, for one container mix and one matte container:
 //                        k_yuv_stack_matte_vec
 //   LUTR_SKA_GENERIC     the generic kernel in its MATTE form: k_yuv_stack_matte_generic
+//   LUTR_SKX_WI / _WO    the vector kernels in their MATRIX form: k_yuv_stack_mtx_vec
+//   LUTR_SKX_GENERIC     the generic kernel in its MATRIX form: k_yuv_stack_mtx_generic
 //
 // MIX is a form of the same kernel text, with the pixel's codes behind the YUV -> RGB stage (q0) kept across the
 // step walk, or evaluated again behind it, and q = (int)((q0 + s * (q1 - q0)) + 0.5f) sent to the RGB -> YUV stage; s is the
@@ -34,6 +36,10 @@
 // a'' = invert ? Mm - a' : a', w = s * (a'' * rcp), and w takes the place of s in the mix.  The vector kernels are built per
 // matte container (WM) beside the source's and load the thread's matte words at the top of a unit, beside the source words (3.23
 // point 5).
+//
+// MATRIX is a fourth form, without MIX: the plain form's text with one more argument, the twelve numbers of an
+// RGB matrix with offset (MtxConsts, wave-uniform: no table, no LDS), and two more steps in the walk, the matrix on codes and on
+// unit floats.  Only this form's translation units hold those steps.
 //
 // How the forms are told apart: the generic kernel's body takes the form as a template parameter (StackForm), and the switches
 // of its translation units only choose the instantiation.  The vector kernel keeps its own copy of union_vec_unit's structure
@@ -48,6 +54,18 @@
 #define LUTR_SK_WI LUTR_SKA_WI
 #define LUTR_SK_WO LUTR_SKA_WO
 #define LUTR_SK_WM LUTR_SKA_WM
+#endif
+#if defined(LUTR_SKX_WI)
+#define LUTR_SK_WI LUTR_SKX_WI
+#define LUTR_SK_WO LUTR_SKX_WO
+#endif
+#if defined(LUTR_SKX_WI) || defined(LUTR_SKX_GENERIC)
+#define LUTR_SK_MTX 1
+#define SK_MTX_PARAM , const MtxConsts &X
+#define SK_MTX_ARG , X
+#else
+#define SK_MTX_PARAM
+#define SK_MTX_ARG
 #endif
 #ifdef LUTR_SK_WI                    // the vector kernel's forms
 #if defined(LUTR_SKA_WI)
@@ -68,6 +86,12 @@
 #define SK_VEC k_yuv_stack_mix_vec
 #define SK_VEC_NAME "k_yuv_stack_mix_vec<"
 #define SK_VEC_LAUNCH launch_yuv_stack_mix_vec_w
+#elif defined(LUTR_SKX_WI)                 // the matrix form: no mix; its one more argument travels where the mix forms' do
+#define SK_MIX_PARAM , MtxConsts X
+#define SK_MIX_ARG , X
+#define SK_VEC k_yuv_stack_mtx_vec
+#define SK_VEC_NAME "k_yuv_stack_mtx_vec<"
+#define SK_VEC_LAUNCH launch_yuv_stack_mtx_vec_w
 #else
 #define SK_MIX_PARAM
 #define SK_MIX_ARG
@@ -106,6 +130,19 @@ __device__ __forceinline__ Rgb stack_round_px(float maxf, const Rgb &o)
     q.g = (float)(int)(o.g * maxf + 0.5f);
     q.b = (float)(int)(o.b * maxf + 0.5f);
     return q;
+}
+
+// The RGB matrix of 3.25 on one pixel: u = p * k (k = 1 / M on codes; 1 on unit floats, where the product is u itself), then per
+// row two products summed, the third product added, the offset added -- each rounded on its own -- and the clamp to [0, 1].  The
+// host keeps the entries finite and small enough for every sum to be finite.
+__device__ __forceinline__ Rgb mtx_px(const MtxConsts &X, float k, const Rgb &p)
+{
+    const float r = p.r * k, g = p.g * k, b = p.b * k;
+    Rgb o;
+    o.r = med3(((X.m[0] * r + X.m[1] * g) + X.m[2] * b) + X.off[0], 0.0f, 1.0f);
+    o.g = med3(((X.m[3] * r + X.m[4] * g) + X.m[5] * b) + X.off[1], 0.0f, 1.0f);
+    o.b = med3(((X.m[6] * r + X.m[7] * g) + X.m[8] * b) + X.off[2], 0.0f, 1.0f);
+    return o;
 }
 
 enum StackForm { SK_PLAIN, SK_MIX, SK_MATTE };
@@ -170,7 +207,7 @@ __device__ __forceinline__ void stack_lattice(bool unit, const LutConsts &X, con
 // The pixels of one union block through the step list.  Every branch depends on kernel arguments only.
 template <bool TRI, int N>
 __device__ __forceinline__ void stack_block(const StackConsts &S, const CdlConsts &C, const uint16_t *l1d, const LutConsts &L,
-                                            const LutConsts &L2, Rgb (&px)[N])
+                                            const LutConsts &L2, Rgb (&px)[N] SK_MTX_PARAM)
 {
     const bool mix = S.sat != 1.0f;
 #pragma nounroll
@@ -185,6 +222,12 @@ __device__ __forceinline__ void stack_block(const StackConsts &S, const CdlConst
         } else if (op == STACK_OP_ROUND) {
 #pragma unroll
             for (int i = 0; i < N; i++) px[i] = stack_round_px(S.maxf, px[i]);
+#ifdef LUTR_SK_MTX
+        } else if (op == STACK_OP_MTX_CODES || op == STACK_OP_MTX_UNIT) {
+            const float k = op == STACK_OP_MTX_CODES ? X.rcp : 1.0f;
+#pragma unroll
+            for (int i = 0; i < N; i++) px[i] = mtx_px(X, k, px[i]);
+#endif
         } else {
             const bool second = op == STACK_OP_LAT2_CODES || op == STACK_OP_LAT2_UNIT;
             const bool unit = op == STACK_OP_LAT_UNIT || op == STACK_OP_LAT2_UNIT;
@@ -287,7 +330,7 @@ __global__ __launch_bounds__(256) void SK_VEC(LutConsts L, LutConsts L2, StackCo
                 for (int i = 0; i < BH * BW; i++) px0[i] = px[i];
             }
 #endif
-            stack_block<TRI>(S, C, l1d, L, L2, px);
+            stack_block<TRI>(S, C, l1d, L, L2, px SK_MTX_ARG);
 #ifdef LUTR_SK_MATTE
             // the block's weights, in the mix's order
             float wgt[BH * BW];
@@ -402,11 +445,12 @@ const char *SK_VEC_LAUNCH_FN(hipStream_t st, const LutConsts &L, const LutConsts
 // ================================================================= generic kernel
 // One thread per union block; any depth, stride or alignment, odd sizes, all five modes on either lattice.  xsub_union_block's
 // walk (lutr_device.h) with the step list per pixel (the tables read from global memory), then (MIX, MATTE) the mix with the
-// pixel's own q; the matte form reads its sample at the pixel's clamped (x, y).  M and A are null in the forms without them.
+// pixel's own q; the matte form reads its sample at the pixel's clamped (x, y).  M and A are null in the forms without them, and
+// so is X: the matrix form is the plain one with X set, and its steps are in its translation unit only.
 template <int FORM>
 __device__ __forceinline__ void stack_generic(const LutConsts &L, const LutConsts &L2, const StackConsts &S, const YuvConsts &K,
-                                              const PlaneSet &P, const FrameGeom &G, const MixConsts *M, const MatteConsts *A, int win,
-                                              int wout, int icsx, int icsy, int ocsx, int ocsy)
+                                              const PlaneSet &P, const FrameGeom &G, const MixConsts *M, const MatteConsts *A,
+                                              const MtxConsts *X, int win, int wout, int icsx, int icsy, int ocsx, int ocsy)
 {
     const GFetch f(L), f2(L2);
     PlaneSink sink{K, P, wout};
@@ -430,6 +474,10 @@ __device__ __forceinline__ void stack_generic(const LutConsts &L, const LutConst
                 case STACK_OP_LAT_CODES:  o = lut3d_px_rt(mode, L, f, o.r, o.g, o.b); break;
                 case STACK_OP_LAT_UNIT:   o = lut3d_unit_rt(mode, L, f, o); break;
                 case STACK_OP_LAT2_CODES: o = lut3d_px_rt(mode, L2, f2, o.r, o.g, o.b); break;
+#ifdef LUTR_SK_MTX
+                case STACK_OP_MTX_CODES:  o = mtx_px(*X, X->rcp, o); break;
+                case STACK_OP_MTX_UNIT:   o = mtx_px(*X, 1.0f, o); break;
+#endif
                 default:                  o = lut3d_unit_rt(mode, L2, f2, o); break;
                 }
             }
@@ -445,7 +493,7 @@ __global__ __launch_bounds__(256) void k_yuv_stack_matte_generic(LutConsts L, Lu
                                                                  FrameGeom G, MixConsts M, MatteConsts A, int win, int wout, int icsx,
                                                                  int icsy, int ocsx, int ocsy)
 {
-    stack_generic<SK_MATTE>(L, L2, S, K, P, G, &M, &A, win, wout, icsx, icsy, ocsx, ocsy);
+    stack_generic<SK_MATTE>(L, L2, S, K, P, G, &M, &A, nullptr, win, wout, icsx, icsy, ocsx, ocsy);
 }
 
 // its launch, for the launcher in the plain translation unit
@@ -457,12 +505,28 @@ const char *launch_yuv_stack_matte_generic(hipStream_t st, unsigned grid, const 
                        ocsy);
     return "k_yuv_stack_matte_generic";
 }
+#elif defined(LUTR_SKX_GENERIC)
+__global__ __launch_bounds__(256) void k_yuv_stack_mtx_generic(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P,
+                                                               FrameGeom G, MtxConsts X, int win, int wout, int icsx, int icsy,
+                                                               int ocsx, int ocsy)
+{
+    stack_generic<SK_PLAIN>(L, L2, S, K, P, G, nullptr, nullptr, &X, win, wout, icsx, icsy, ocsx, ocsy);
+}
+
+// its launch, for the launcher in the plain translation unit
+const char *launch_yuv_stack_mtx_generic(hipStream_t st, unsigned grid, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
+                                         const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const MtxConsts &X, int win,
+                                         int wout, int icsx, int icsy, int ocsx, int ocsy)
+{
+    hipLaunchKernelGGL(k_yuv_stack_mtx_generic, dim3(grid), dim3(256), 0, st, L, L2, S, K, P, G, X, win, wout, icsx, icsy, ocsx, ocsy);
+    return "k_yuv_stack_mtx_generic";
+}
 #elif defined(LUTR_SKM_GENERIC)
 __global__ __launch_bounds__(256) void k_yuv_stack_mix_generic(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P,
                                                                FrameGeom G, MixConsts M, int win, int wout, int icsx, int icsy,
                                                                int ocsx, int ocsy)
 {
-    stack_generic<SK_MIX>(L, L2, S, K, P, G, &M, nullptr, win, wout, icsx, icsy, ocsx, ocsy);
+    stack_generic<SK_MIX>(L, L2, S, K, P, G, &M, nullptr, nullptr, win, wout, icsx, icsy, ocsx, ocsy);
 }
 
 // its launch, for the launcher in the plain translation unit
@@ -477,7 +541,7 @@ const char *launch_yuv_stack_mix_generic(hipStream_t st, unsigned grid, const Lu
 __global__ __launch_bounds__(256) void k_yuv_stack_generic(LutConsts L, LutConsts L2, StackConsts S, YuvConsts K, PlaneSet P, FrameGeom G,
                                                            int win, int wout, int icsx, int icsy, int ocsx, int ocsy)
 {
-    stack_generic<SK_PLAIN>(L, L2, S, K, P, G, nullptr, nullptr, win, wout, icsx, icsy, ocsx, ocsy);
+    stack_generic<SK_PLAIN>(L, L2, S, K, P, G, nullptr, nullptr, nullptr, win, wout, icsx, icsy, ocsx, ocsy);
 }
 
 // ================================================================= launcher
@@ -499,7 +563,7 @@ static bool stack_in_lds(const StackConsts &S)
 
 const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
                              const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int din, int dout, int icsx, int icsy,
-                             int ocsx, int ocsy, const MixConsts *M, const MatteConsts *A)
+                             int ocsx, int ocsy, const MixConsts *M, const MatteConsts *A, const MtxConsts *X)
 {
     const UnionLaunch U(G, din, dout, icsx, icsy, ocsx, ocsy);
     const bool lds = stack_in_lds(S);
@@ -507,7 +571,7 @@ const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, co
     bool modes_ok = true, tri = false;
     for (unsigned long long ops = S.ops; ops & 0xffull; ops >>= 8) {
         const int op = (int)(ops & 15u), mode = (int)((ops >> 4) & 15u);
-        if (op == STACK_OP_L1D || op == STACK_OP_CDL || op == STACK_OP_ROUND) continue;
+        if (op == STACK_OP_L1D || op == STACK_OP_CDL || op == STACK_OP_ROUND || op == STACK_OP_MTX_CODES || op == STACK_OP_MTX_UNIT) continue;
         modes_ok = modes_ok && vec_mode(mode);
         tri = tri || mode == LUTR_INTERP_TRILINEAR;
     }
@@ -528,11 +592,16 @@ const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, co
             if (U.win) return launch_yuv_stack_mix_vec_w10(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M);
             return launch_yuv_stack_mix_vec_w00(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *M);
         }
+        if (X) {
+            if (U.win && U.wout) return launch_yuv_stack_mtx_vec_w11(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *X);
+            if (U.win) return launch_yuv_stack_mtx_vec_w10(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *X);
+            return launch_yuv_stack_mtx_vec_w00(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds, *X);
+        }
         if (U.win && U.wout) return launch_yuv_stack_vec_w11(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds);
         if (U.win) return launch_yuv_stack_vec_w10(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds);
         return launch_yuv_stack_vec_w00(st, L, L2, S, K, Q, H, icsx, icsy, ocsx, ocsy, tri, lds);
     };
-    const char *const generic_name = A ? "k_yuv_stack_matte_generic" : M ? "k_yuv_stack_mix_generic" : "k_yuv_stack_generic";
+    const char *const generic_name = A ? "k_yuv_stack_matte_generic" : M ? "k_yuv_stack_mix_generic" : X ? "k_yuv_stack_mtx_generic" : "k_yuv_stack_generic";
     auto generic = [&](const PlaneSet &Q, const FrameGeom &H, int x0) {
         const unsigned grid = U.generic_grid(generic_name, H);
         if (A) {
@@ -542,6 +611,7 @@ const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, co
             return launch_yuv_stack_matte_generic(st, grid, L, L2, S, K, Q, H, *M, B, U.win, U.wout, icsx, icsy, ocsx, ocsy);
         }
         if (M) return launch_yuv_stack_mix_generic(st, grid, L, L2, S, K, Q, H, *M, U.win, U.wout, icsx, icsy, ocsx, ocsy);
+        if (X) return launch_yuv_stack_mtx_generic(st, grid, L, L2, S, K, Q, H, *X, U.win, U.wout, icsx, icsy, ocsx, ocsy);
         hipLaunchKernelGGL(k_yuv_stack_generic, dim3(grid), dim3(256), 0, st, L, L2, S, K, Q, H, U.win, U.wout, icsx, icsy, ocsx, ocsy);
         return generic_name;
     };

@@ -21,6 +21,7 @@ import torch
 from . import _native
 from .cdl import Cdl
 from .cube import CubeLut, Lut1D, read_cube, read_lut, read_lut1d
+from .rgbmatrix import RgbMatrix
 # (the formats and the checks of names and options live in formats.py; the names callers have always imported from here stay)
 from .formats import (_ALPHA_RESIZE, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, V210Fmt, chain_interp, chain_side,  # noqa: F401
                       changes_subsampling, check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc,
@@ -916,7 +917,7 @@ class LutEngine:
                         matrix_out: Optional[str] = None, range_src: str = "tv", range_in: Optional[str] = None,
                         range_out: str = "tv", lut_depth: Optional[int] = None, row0: int = 0, rows: Optional[int] = None,
                         strength=None, matte: Optional[torch.Tensor] = None, matte_depth: Optional[int] = None,
-                        matte_invert: bool = False, **other):
+                        matte_invert: bool = False, rgb_matrix: Optional[RgbMatrix] = None, **other):
         """`apply_yuv` with an ordered stack of 1..4 stages between its YUV -> RGB and RGB -> YUV stages, in one pass
         (lutr_apply_yuv_stack).  `stages` is a sequence of "lut3d" (`set_lut`), "lut3d2" (`set_lut2`), "lut1d"
         (`set_lut1d`), "cdl" (the `cdl` argument), each at most once; a lut3d stage may be a pair ("lut3d", "trilinear") -- the
@@ -938,18 +939,25 @@ class LutEngine:
         same pass (lutr_apply_yuv_stack_matte): w = s * (a / Mm), or s * ((Mm - a) / Mm) with `matte_invert`, takes the place of s
         in the mix above, ahead of the chroma mean.  `strength` defaults to 1 with a matte.  A matte of Mm everywhere gives the
         bits of the call with the strength alone, 0 everywhere those of strength 0.  The matte is not processed in any way; the
-        alpha plane of a yuva* source goes past it unchanged -- to key on it, pass it as `matte` (`formats.check_matte`)."""
+        alpha plane of a yuva* source goes past it unchanged -- to key on it, pass it as `matte` (`formats.check_matte`).
+        `rgb_matrix`: the `rgbmatrix.RgbMatrix` of a "matrix" stage, which may stand once anywhere in the list:
+        o = clamp(M * u + offset, 0, 1) on unit RGB, u = q / (2^lut_depth - 1) where the pixel is a code.  A lattice behind it is
+        fed unit floats as behind the CDL; lut1d, cdl and the end of the list round to codes first.  The call goes to
+        lutr_apply_yuv_stack_matrix when a matrix stage is listed and only then; a matrix without its stage, a stage without its
+        matrix and a strength or matte together with the stage are ValueErrors."""
         for k in other:
             if k not in ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt"):
                 raise TypeError(f"apply_yuv_stack() got an unexpected keyword argument '{k}'")
         if cdl is not None and not isinstance(cdl, Cdl):
             raise TypeError(f"cdl must be a lut_renderer_amd.cdl.Cdl, not {type(cdl).__name__}")
+        if rgb_matrix is not None and not isinstance(rgb_matrix, RgbMatrix):
+            raise TypeError(f"rgb_matrix must be a lut_renderer_amd.rgbmatrix.RgbMatrix, not {type(rgb_matrix).__name__}")
         st, fin, fout = check_stack_options(
             pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(self, "n", 0)),
             lut2=bool(getattr(self, "n2", 0)), lut1d=bool(getattr(self, "n1d", 0)), prelut=bool(getattr(self, "_has_prelut", False)),
             dither=other.get("dither", "none"), chroma_loc=other.get("chroma_loc"), out_size=other.get("out_size"),
             alpha_mode=other.get("alpha_mode", "straight"), out2_pix_fmt=other.get("out2_pix_fmt"), strength=strength,
-            matte=matte is not None)
+            matte=matte is not None, rgb_matrix=rgb_matrix is not None)
         if fin.alpha or fout.alpha:
             # yuva*: the colour planes through this very call under their three-plane names, then the alpha plane on the same
             # stream, exactly as the CDL call does (DESIGN.md 3.16); straight alpha goes past the mix unchanged
@@ -966,7 +974,8 @@ class LutEngine:
             self._alpha_tail(lambda: self.apply_yuv_stack(
                 src[:3], dst[:3], pix_fmt=fin.colour.name, out_pix_fmt=fout.colour.name, stages=st, cdl=cdl, matrix_in=matrix_in,
                 matrix_out=matrix_out, range_src=range_src, range_in=range_in, range_out=range_out, lut_depth=lut_depth, row0=row0,
-                rows=rows, strength=strength, matte=matte, matte_depth=matte_depth, matte_invert=matte_invert),
+                rows=rows, strength=strength, matte=matte, matte_depth=matte_depth, matte_invert=matte_invert,
+                rgb_matrix=rgb_matrix),
                 [(fout, dst)], a_src, fin.depth, w, h, row0, rows)
             return dst
         p = _yuv_call_params(fin, fout, lut_depth, matrix_in, matrix_out, range_src, range_in, range_out)
@@ -992,7 +1001,11 @@ class LutEngine:
                 strength = 1.0
         with self._lock:
             self._bind_stream()
-            if matte is not None:
+            if rgb_matrix is not None:                            # a matrix stage is listed (check_stack_options)
+                _native.check(self._lib.lutr_apply_yuv_stack_matrix(
+                    self._ctx, C.byref(p), arr, len(st), k, C.byref(_native.rgb_matrix_struct(rgb_matrix)), w, h, nf, C.byref(s),
+                    C.byref(d), row0, rows))
+            elif matte is not None:
                 frame = None
                 if not isinstance(strength, float):              # one float per frame: uploaded and kept as below
                     if not self.use_torch_stream and self._frame_strength is not None:

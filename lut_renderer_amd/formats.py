@@ -567,14 +567,17 @@ def check_lut1d_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = Non
 
 #: the stage kinds of a stack and enum lutr_stage_kind
 STAGE_KINDS = _native.STAGE_KINDS
+#: with the kind of 3.25, which only the matrix entry takes: what a stage list may name
+ALL_STAGE_KINDS = {**_native.STAGE_KINDS, **_native.MATRIX_STAGE_KINDS}
 MAX_STAGES = 4
 
 
 def parse_stages(stages, interp: Optional[str] = None, interp2: Optional[str] = None) -> Tuple[Tuple[str, Optional[str]], ...]:
     """The one parser of a stage list.  `stages` is a comma string ("lut1d,cdl,lut3d:trilinear") or a sequence
     of names and (name, mode) pairs.  Returns ((kind, mode), ...): mode is a lut3d mode name for the two lut3d kinds -- the
-    stage's own, else `interp` (lut3d) / `interp2` (lut3d2; None = `interp`), else tetrahedral -- and None for lut1d and cdl.
-    ValueError: an empty list, more than four stages, an unknown kind, a kind twice, a mode on lut1d / cdl, an unknown mode."""
+    stage's own, else `interp` (lut3d) / `interp2` (lut3d2; None = `interp`), else tetrahedral -- and None for lut1d, cdl and
+    matrix.  ValueError: an empty list, more than four stages, an unknown kind, a kind twice, a mode on lut1d / cdl / matrix, an
+    unknown mode."""
     if isinstance(stages, str):
         items = [s.strip() for s in stages.split(",")] if stages.strip() else []
     elif stages is None:
@@ -582,7 +585,7 @@ def parse_stages(stages, interp: Optional[str] = None, interp2: Optional[str] = 
     else:
         items = list(stages)
     if not items:
-        raise ValueError("the stage list is empty: a stack has 1 to 4 stages (lut3d | lut3d2 | lut1d | cdl)")
+        raise ValueError("the stage list is empty: a stack has 1 to 4 stages (lut3d | lut3d2 | lut1d | cdl | matrix)")
     if len(items) > MAX_STAGES:
         raise ValueError(f"the stage list has {len(items)} stages: a stack has 1 to {MAX_STAGES}")
     out = []
@@ -597,8 +600,8 @@ def parse_stages(stages, interp: Optional[str] = None, interp2: Optional[str] = 
                 kind, mode = item
             except (TypeError, ValueError):
                 raise ValueError(f"a stage is a name or a (name, mode) pair, not {item!r}") from None
-        if kind not in STAGE_KINDS:
-            raise ValueError(f"unknown stage kind '{kind}' ({' | '.join(STAGE_KINDS)})")
+        if kind not in ALL_STAGE_KINDS:
+            raise ValueError(f"unknown stage kind '{kind}' ({' | '.join(ALL_STAGE_KINDS)})")
         if any(kind == k for k, _m in out):
             raise ValueError(f"stage kind '{kind}' is listed twice: each kind may appear once")
         if kind in ("lut3d", "lut3d2"):
@@ -711,7 +714,7 @@ def check_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = Non
                         lut: bool = True, lut2: bool = True, lut1d: bool = True, prelut: bool = False, dither: str = "none",
                         chroma_loc: Optional[str] = None, out_size=None, alpha_mode: str = "straight",
                         out2_pix_fmt: Optional[str] = None, variant: Optional[str] = None, strength=None,
-                        precision: Optional[str] = None, matte: bool = False):
+                        precision: Optional[str] = None, matte: bool = False, rgb_matrix: bool = False):
     """The checks every layer makes of a stage stack before any GPU work, the one copy of its refusals: a stage
     list `parse_stages` takes; every listed stage's resource there (`lut`, `lut2`, `lut1d`: a first / second lattice, a 1D LUT is
     loaded; `cdl`: a CDL is given) and no CDL without a cdl stage; no lut3d directly behind cdl when the first LUT carries a .csp
@@ -719,7 +722,9 @@ def check_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = Non
     output or premultiplied alpha; not the vec_lds variant.  With a `strength` (anything but None) every message
     names it beside the option, the strength itself is checked (`check_strength`) and a `precision` other than strict is refused.
     With `matte` (True: the call has a matte plane, which `check_matte` checks) every message names the matte as
-    well, and `precision` is refused likewise.
+    well, and `precision` is refused likewise.  `rgb_matrix` (True: an RGB matrix is given): a matrix stage and
+    its matrix come together, lut3d directly behind matrix is refused with a prelut as behind cdl, and a strength or a matte
+    together with a matrix stage is refused.
     Returns (parsed stages, source format, output format)."""
     mixed = strength is not None
     matte = matte is not None and matte is not False
@@ -743,6 +748,16 @@ def check_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = Non
     if prelut and "cdl" in kinds and kinds.index("cdl") + 1 < len(kinds) and kinds[kinds.index("cdl") + 1] == "lut3d":
         raise ValueError("stage 'lut3d' directly behind 'cdl' is not supported with a LUT that carries a .csp prelut: the prelut's "
                          "table is indexed by integer codes, and the CDL's output is not a code")
+    if "matrix" in kinds and not rgb_matrix:
+        raise ValueError("stage 'matrix' is listed and no RGB matrix is given: pass rgb_matrix")
+    if rgb_matrix and "matrix" not in kinds:
+        raise ValueError("an RGB matrix is given and the stage list has no 'matrix' stage")
+    if prelut and "matrix" in kinds and kinds.index("matrix") + 1 < len(kinds) and kinds[kinds.index("matrix") + 1] == "lut3d":
+        raise ValueError("stage 'lut3d' directly behind 'matrix' is not supported with a LUT that carries a .csp prelut: the prelut's "
+                         "table is indexed by integer codes, and the matrix's output is not a code")
+    if "matrix" in kinds and (mixed or matte):
+        what = "strength and a matte" if mixed and matte else "a matte" if matte else "strength"
+        raise ValueError(f"stage 'matrix' is not supported with {what}: the matrix stage has no mix form")
     fin = _pass_side(pix_fmt, "pix_fmt", noun, "both sides", True, alpha_ok=True)
     fout = _pass_side(out_pix_fmt or pix_fmt, "out_pix_fmt", noun, "both sides", True, alpha_ok=True)
     if dither != "none":

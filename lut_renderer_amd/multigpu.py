@@ -358,7 +358,8 @@ class LutEngineGroup:
         union block height of the two layouts, alpha rows go with the luma rows, no halo.  `strength` as the
         engine takes it: a per-frame array goes to every device once, and the shards give the bits of the whole call.  `matte`
          as the engine takes it, on the source's device: its rows travel with the source's luma rows, a still's
-        once per device, and a pixel reads the sample of its own row and column on every shard."""
+        once per device, and a pixel reads the sample of its own row and column on every shard.  `rgb_matrix`
+        travels with the call like the CDL."""
         with self._lock:
             if "row0" in kw or "rows" in kw:
                 raise ValueError("the group owns the row partition")
@@ -368,7 +369,7 @@ class LutEngineGroup:
                 lut2=bool(getattr(e0, "n2", 0)), lut1d=bool(self.n1d), prelut=bool(getattr(e0, "_has_prelut", False)),
                 dither=kw.get("dither", "none"), chroma_loc=kw.get("chroma_loc"), out_size=kw.get("out_size"),
                 alpha_mode=kw.get("alpha_mode", "straight"), out2_pix_fmt=kw.get("out2_pix_fmt"), strength=kw.get("strength"),
-                matte=kw.get("matte") is not None)
+                matte=kw.get("matte") is not None, rgb_matrix=kw.get("rgb_matrix") is not None)
             if kw.get("matte") is not None:
                 check_matte(kw["matte"], kw.get("matte_depth"), kw.get("matte_invert", False), w=src[0].shape[-1], h=src[0].shape[-2],
                             nframes=src[0].shape[0] if len(src[0].shape) == 3 else 1, device=src[0].device)

@@ -52,7 +52,7 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
                           cdl_id: Optional[str] = None, lut1d: Optional[Path] = None,
                           interp1d: Optional[str] = None, stages=None, strength: Optional[float] = None,
                           strength_keys: Optional[str] = None, matte: Optional[Path] = None,
-                          matte_pix_fmt: Optional[str] = None, matte_invert: bool = False) -> StageCommands:
+                          matte_pix_fmt: Optional[str] = None, matte_invert: bool = False, rgb_matrix=None) -> StageCommands:
     """The three argv lists of one LUT stage.  Raises what `build_command` / `engine_command` raise (copy guard, missing
     geometry).  `chroma_loc` goes to the engine (`--chroma-loc`) and, as `-chroma_sample_location`, to the encoder, so the
     output stream declares the siting the engine assumed.  `gpu_resize` with `params.resolution` set resizes in the engine
@@ -65,7 +65,9 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
     pass, DESIGN.md 3.21: `--stages`, rendered only when given), and for `strength` / `strength_keys` (the LUT's strength, DESIGN.md
     3.22: `--strength` / `--strength-keys`, rendered only when given; the key frames count the frames of the stream), and for `matte` /
     `matte_pix_fmt` / `matte_invert` (a matte plane, DESIGN.md 3.23: `--matte` / `--matte-pix-fmt` / `--matte-invert`, rendered only
-    when given; the matte file is raw gray frames at the size of the decoded source)."""
+    when given; the matte file is raw gray frames at the size of the decoded source), and for `rgb_matrix` (the matrix of a
+    `matrix` stage of `stages`, DESIGN.md 3.25: `--rgb-matrix` / `--rgb-matrix-offset` for an `rgbmatrix.RgbMatrix`,
+    `--rgb-matrix-file` for a path, rendered only when given)."""
     notes: List[str] = []
     engine = engine_command(Path("-"), Path("-"), params, lut_path, source_info, python_bin=python_bin, device=device, notes=notes,
                             precision=precision, chroma_loc=chroma_loc, gpu_resize=gpu_resize, engine_dither=engine_dither,
@@ -74,7 +76,8 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
                             **({} if strength is None else {"strength": strength}),
                             **({} if strength_keys is None else {"strength_keys": strength_keys}),
                             **({} if matte is None and matte_pix_fmt is None and not matte_invert else
-                               {"matte": matte, "matte_pix_fmt": matte_pix_fmt, "matte_invert": matte_invert}))
+                               {"matte": matte, "matte_pix_fmt": matte_pix_fmt, "matte_invert": matte_invert}),
+                            **({} if rgb_matrix is None else {"rgb_matrix": rgb_matrix}))
     resized = gpu_resize and bool(params.resolution)
     if source_info.duration:
         engine += ["--duration", f"{float(source_info.duration):.3f}"]
@@ -178,6 +181,9 @@ def main(argv=None) -> int:
     ap.add_argument("--matte", default=None, help="engine setting: a matte plane (raw gray frames), see lut_renderer_amd.cli")
     ap.add_argument("--matte-pix-fmt", default=None, help="pixel format of --matte, see lut_renderer_amd.cli")
     ap.add_argument("--matte-invert", action="store_true", help="invert --matte, see lut_renderer_amd.cli")
+    ap.add_argument("--rgb-matrix", default=None, help="engine setting: the matrix of a 'matrix' stage as nine literal values, see lut_renderer_amd.cli")
+    ap.add_argument("--rgb-matrix-offset", default=None, help="the offset of --rgb-matrix as three literal values")
+    ap.add_argument("--rgb-matrix-file", default=None, help="the matrix of a 'matrix' stage from a .spimtx file, see lut_renderer_amd.cli")
     ap.add_argument("--gpu-resize", action="store_true", help="resize to the params' resolution in the engine (--out-size) instead of the encoder")
     a = ap.parse_args(argv)
     try:
@@ -189,6 +195,10 @@ def main(argv=None) -> int:
         if a.cdl_sop is not None or a.cdl_sat is not None:
             from .cdl import Cdl
             cdl = Cdl.from_sop_text(a.cdl_sop, a.cdl_sat)
+        from .cli import rgb_matrix_from_args
+        mtx = rgb_matrix_from_args(a)                           # (the checks; a file travels to the engine as its path)
+        if a.rgb_matrix_file is not None:
+            mtx = Path(a.rgb_matrix_file)
         cmds = engine_stage_commands(Path(a.input), Path(a.output), params, Path(a.cube), info, ffmpeg_bin=a.ffmpeg, device=a.device,
                                      precision=a.precision, chroma_loc=a.chroma_loc, gpu_resize=a.gpu_resize,
                                      engine_dither=a.engine_dither, cube2=None if a.cube2 is None else Path(a.cube2),
@@ -196,7 +206,7 @@ def main(argv=None) -> int:
                                      lut1d=None if a.lut1d is None else Path(a.lut1d), interp1d=a.interp1d,
                                      stages=a.stages, strength=a.strength, strength_keys=a.strength_keys,
                                      matte=None if a.matte is None else Path(a.matte), matte_pix_fmt=a.matte_pix_fmt,
-                                     matte_invert=a.matte_invert)
+                                     matte_invert=a.matte_invert, rgb_matrix=mtx)
     except Exception as exc:
         print(f"Error: {exc}", flush=True)
         return 1

@@ -219,8 +219,14 @@ class HostPipeline:
                                   lut1d=True if lut1d else None,
                                   **{k: v for k, v in apply_kw.items() if k in _YUV2RGB_NOT_TAKEN and k not in ("out_size", "lut1d")})
             apply_kw = {k: v for k, v in apply_kw.items() if k not in _YUV2RGB_NOT_TAKEN}
+        # `apply_kw["rgb_matrix"]` (an `rgbmatrix.RgbMatrix`): the resource of a matrix stage of `stages`, which
+        # travels to the engine with every batch like the CDL; None is not passed on
         stages = apply_kw.get("stages")
         self.stack = stages is not None
+        if apply_kw.get("rgb_matrix") is None:
+            apply_kw.pop("rgb_matrix", None)
+        elif not self.stack:
+            raise ValueError("an RGB matrix is a stage of the stage stack: it needs stages")
         self.matte = apply_kw.pop("matte", None)
         if self.matte is None:
             apply_kw.pop("matte_invert", None)
@@ -246,7 +252,8 @@ class HostPipeline:
                                 lut1d=bool(getattr(engine, "n1d", 0)), prelut=bool(getattr(engine, "_has_prelut", False)),
                                 dither=apply_kw.get("dither", "none"), chroma_loc=apply_kw.get("chroma_loc"), out_size=out_size,
                                 alpha_mode=apply_kw.get("alpha_mode", "straight"), out2_pix_fmt=second_pix_fmt,
-                                strength=apply_kw.get("strength", 1.0 if mixed else None), matte=self.matte is not None)
+                                strength=apply_kw.get("strength", 1.0 if mixed else None), matte=self.matte is not None,
+                                rgb_matrix="rgb_matrix" in apply_kw)
             apply_kw = {k: v for k, v in apply_kw.items() if k not in ("dither", "alpha_mode", "interp") and
                         not (k == "cdl" and v is None)}
         self.chain = bool(chain)
