@@ -904,6 +904,42 @@ int lutr_apply_yuv_stack_matrix(lutr_ctx *ctx, const lutr_yuv_params *p, const l
                                 const lutr_rgb_matrix *mtx, int w, int h, int nframes, const lutr_planes *src,
                                 const lutr_planes *dst, int row0, int rows);
 
+/* ---- the stage stack on RGB sources: a DPX / TIFF / PNG sequence through an input transform, a per-shot CDL, a
+ *      gamut matrix and the show LUT in one pass, into a YUV master or back into planar RGB ----
+ * The source is lutr_apply_rgb_to_yuv's: src_kind == 0 takes gbrp planes in src_planar (plane 0 = G, 1 = B, 2 = R; uint8 at depth 8,
+ * else uint16 LE), src_kind == LUTR_PK_* / LUTR_PACKED(...) one packed image in src_packed (a fourth component is read past).  Its
+ * integer codes at the depth dl of the list enter the list as codes held as floats -- the state stage 1 of lutr_apply_yuv_stack
+ * produces -- and a 16-bit word above M = 2^dl - 1 acts as M.  The list is lutr_apply_yuv_stack_matrix's, unchanged: 1..4 stages out
+ * of LUT3D, LUT3D_2, LUT1D, CDL, MATRIX, each at most once, in any order, every lattice stage with its own mode (all five), the
+ * first lattice's .csp prelut taken where it is fed codes, the same compiled steps, the same unit -> codes rounding and per-stage
+ * arithmetic in strict fp32 without contraction.
+ * dst_kind == LUTR_RGB_STACK_YUV: dl = p->lut_depth (a packed source's bits); the list's final codes go through the output stage
+ *   of lutr_apply_rgb_to_yuv into planar YUV p->fmt_out (4:2:0 / 4:2:2 / 4:4:4 at 8..16 bit; constants
+ *   lutr_yuv_constants_rgb2yuv; each chroma sample from the sum of the final codes over its output block; a partial block takes
+ *   the edge column / row again).  Of *p only fmt_out, lut_depth, matrix_out and range_out are read.  Not in place: the byte-range
+ *   rule of lutr_apply_rgb_to_yuv.
+ * dst_kind == 8..16: dl = dst_kind, which a packed source's bits must equal; the final codes are stored as they are into three
+ *   gbrp planes of dl bits in dst (G, B, R).  p is not read and may be NULL.  dst may be a planar source's own planes (the same
+ *   base, stride and frame stride plane by plane: a sample is read and written by the same lane); any other overlap is refused.
+ * row0 and rows must be multiples of the output chroma block height (1 for a gbrp destination) unless row0 + rows == h.
+ * Bit for bit: {LUT3D} into YUV is lutr_apply_rgb_to_yuv; {LUT3D} into gbrp is lutr_apply_planar_rgb; {LUT1D} into gbrp is
+ * lutr_apply_planar_rgb_lut1d; {CDL} with the identity CDL and {MATRIX} with the identity matrix into gbrp give the source
+ * (codes <= M).
+ * LUTR_EINVAL with a message, before anything touches the device: everything lutr_apply_yuv_stack_matrix refuses about the list
+ * and its resources; a dst_kind that is neither; a packed source whose bits differ from dl; the format errors of
+ * lutr_apply_rgb_to_yuv; variant vec_lds; an overlap as above.
+ * Kernels: "k_rgb_stack_vec<win,nc,wout,sink,ocsx,ocsy,tri,lds>[stages]" (nc = 1 planar, 3 | 4 packed; sink 0 = YUV, 1 = gbrp;
+ * nearest / trilinear / tetrahedral stages; 8 -> 8, 16 -> 16 and, into YUV, 16 -> 8 bit containers; the layout rules of
+ * "k_rgb2yuv_vec"; the tables in LDS when they fit 24 KB, LUTR_STACK_LDS=0 | 1 as for lutr_apply_yuv_stack),
+ * "k_rgb_stack_generic[stages]" for everything else, "<vector kernel>+k_rgb_stack_generic[stages]" for a ragged width on aligned
+ * rows; [stages] as lutr_apply_yuv_stack writes it.  vec_global fails with LUTR_EINVAL where the vector kernel cannot take the call.
+ * Not covered: packed RGB destinations, float sources, a strength or a matte, dither, a resize, semi-planar / packed YUV
+ * destinations, a tile (LDS window) kernel. */
+#define LUTR_RGB_STACK_YUV 0
+int lutr_apply_rgb_stack(lutr_ctx *ctx, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                         const lutr_rgb_matrix *mtx, int src_kind, int w, int h, int nframes, const lutr_planes *src_planar,
+                         const lutr_packed *src_packed, int dst_kind, const lutr_planes *dst, int row0, int rows);
+
 /* ---- the alpha plane of yuva* / gbrap* frames: ProRes 4444 (yuva444p10le / 12le), VP8 / VP9 with alpha
  *      (yuva420p), PNG / TIFF / EXR sequences with alpha (rgba, rgba64le, gbrap*, gbrapf32le).  In the reference's chain lut3d
  *      copies the alpha plane through and format=<pix_fmt> keeps, converts, drops or makes it (ffmpeg.py:246, :304-310) ---- */

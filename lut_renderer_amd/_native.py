@@ -25,6 +25,8 @@ MATRIX_STAGE_KINDS = {"matrix": 5}
 MATRIX = {"bt709": 0, "smpte170m": 1, "bt470bg": 1, "bt601": 1, "bt2020nc": 2, "bt2020c": 2}
 RANGE = {"tv": 0, "pc": 1}
 DITHER = {"none": 0, "error_diffusion": 1, "blue_noise": 2}
+#: LUTR_RGB_STACK_YUV: the dst_kind of lutr_apply_rgb_stack for a YUV destination (a gbrp destination's is its depth)
+RGB_STACK_YUV = 0
 #: LUTR_INTERP_NONE: lutr_apply_rgb_to_yuv without lut3d
 INTERP_NONE = -1
 VARIANT = {"auto": 0, "generic": 1, "vec_global": 2, "vec_lds": 3}
@@ -51,7 +53,7 @@ SYMBOLS = (
     "lutr_apply_yuv_premul", "lutr_apply_planar_rgb_f32_premul", "lutr_cdl_table", "lutr_apply_yuv_cdl",
     "lutr_lut1d_parse", "lutr_lut1d_table", "lutr_ctx_set_lut1d", "lutr_apply_yuv_lut1d", "lutr_apply_planar_rgb_lut1d",
     "lutr_apply_yuv_stack", "lutr_apply_yuv_stack_mix", "lutr_apply_yuv_stack_matte",
-    "lutr_apply_yuv_stack_matrix",
+    "lutr_apply_yuv_stack_matrix", "lutr_apply_rgb_stack",
     "lutr_resize_filter", "lutr_resize_planes", "lutr_dither_mask",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
     "lutr_max_waves_knob", "lutr_max_blocks_knob",
@@ -287,6 +289,9 @@ def load() -> C.CDLL:
                                                vp, C.POINTER(MatteStruct), ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_apply_yuv_stack_matrix.argtypes = [vp, C.POINTER(YuvParams), C.POINTER(StageStruct), ci, C.POINTER(CdlStruct),
                                                 C.POINTER(RgbMatrixStruct), ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
+    lib.lutr_apply_rgb_stack.argtypes = [vp, C.POINTER(YuvParams), C.POINTER(StageStruct), ci, C.POINTER(CdlStruct),
+                                         C.POINTER(RgbMatrixStruct), ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Packed), ci,
+                                         C.POINTER(Planes), ci, ci]
     lib.lutr_dither_mask.argtypes = [C.POINTER(C.c_uint16)]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]

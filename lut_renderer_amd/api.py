@@ -26,7 +26,7 @@ from .rgbmatrix import as_rgb_matrix
 from .cube import CubeLut, as_lut1d, read_cube, read_lut, read_lut1d
 from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc, check_container_options,
                       check_dual_options, check_lut1d_options, check_lut2, check_premul_options, check_stack_options,
-                      check_yuv2rgb_options, implied_stages, packed_frame_width, parse_packed_yuv_fmt,
+                      check_rgb_stack_options, check_yuv2rgb_options, implied_stages, packed_frame_width, parse_packed_yuv_fmt,
                       parse_pix_fmt, parse_rgb_source, parse_semi_fmt, parse_size, parse_stages, parse_v210_fmt, premul_to_yuv,
                       refuse_alpha_resize, source_bit_depth, v210_frame_width, yuv_side)
 from .params import ProcessingParams, VideoInfo
@@ -235,19 +235,11 @@ def resolve_engine_dither(engine_dither: str, dither: str = "none") -> str:
     return "blue_noise"
 
 
-def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, engine, devices, precision,
-                 chroma_loc, out_size, alpha_mode, second_pix_fmt, strength=None, matte=None, rgb_matrix=None):
-    """`apply_lut(stages=...)` (DESIGN.md 3.21): load what the list names, with the caches the single-feature routes use, and
-    route to `apply_yuv_stack`.  `kw` is what `engine_call_for` returned, with `dither` filled in.  `strength` (DESIGN.md 3.22)
-    travels to the engine; `stages` None is then the list the other options imply.  `matte` (DESIGN.md 3.23): None, or the dict of
-    the engine's `matte`, `matte_depth` and `matte_invert` arguments, which travels likewise.  `rgb_matrix` (DESIGN.md 3.25): None,
-    an RgbMatrix or the path of a .spimtx file, the resource of a matrix stage."""
-    from .plan import INTERP_WHITELIST
+def _stack_resources(st, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, rgb_matrix, engine):
+    """What `apply_lut(stages=)` and `apply_lut(rgb_stages=)` load for the parsed list `st`, with the caches the single-feature
+    routes use: a stage for every file given, then (lattice | None, second lattice | None, 1D LUT | None, Cdl | None, RgbMatrix |
+    None, `held(name)` -- what the engine of the call already holds -- , whether the first lattice carries a prelut)."""
     from . import _native
-    mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
-    if stages is None:
-        stages = implied_stages(cube is not None, cube2 is not None, lut1d is not None, cdl is not None)
-    st = parse_stages(stages, interp=kw.get("interp"), interp2=mode2)
     kinds = [k for k, _m in st]
     if interp1d not in _native.INTERP1D:
         raise ValueError(f"lut1d has no interpolation mode '{interp1d}' ({' | '.join(_native.INTERP1D)})")
@@ -269,6 +261,41 @@ def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d,
     first = engine.engines[0] if engine is not None and hasattr(engine, "engines") else engine
     held = lambda name: bool(getattr(first, name, 0))                                  # noqa: E731
     prelut = getattr(lut, "prelut", None) is not None if lut is not None else held("_has_prelut")
+    return lut, lut2, lut1d, cdl, rgb_matrix, held, prelut
+
+
+def _stack_upload(eng, lut, lut2, lut1d, interp1d, precision) -> None:
+    """The uploads and the precision of one stack task, under the engine's lock: a resource the engine took from the same parsed
+    object last time stands."""
+    if lut is not None and eng._applied_lut is not lut:
+        eng.set_lut(lut)
+        eng._applied_lut = lut
+    if lut2 is not None and eng._applied_lut2 is not lut2:
+        eng.set_lut2(lut2)
+        eng._applied_lut2 = lut2
+    if lut1d is not None:
+        had = eng._applied_lut1d
+        if not (had is not None and had[0] is lut1d and had[1] == interp1d):
+            eng.set_lut1d(lut1d, interp1d)
+            eng._applied_lut1d = (lut1d, interp1d)
+    if eng.precision != precision:
+        eng.set_precision(precision)
+
+
+def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, engine, devices, precision,
+                 chroma_loc, out_size, alpha_mode, second_pix_fmt, strength=None, matte=None, rgb_matrix=None):
+    """`apply_lut(stages=...)` (DESIGN.md 3.21): load what the list names, with the caches the single-feature routes use, and
+    route to `apply_yuv_stack`.  `kw` is what `engine_call_for` returned, with `dither` filled in.  `strength` (DESIGN.md 3.22)
+    travels to the engine; `stages` None is then the list the other options imply.  `matte` (DESIGN.md 3.23): None, or the dict of
+    the engine's `matte`, `matte_depth` and `matte_invert` arguments, which travels likewise.  `rgb_matrix` (DESIGN.md 3.25): None,
+    an RgbMatrix or the path of a .spimtx file, the resource of a matrix stage."""
+    from .plan import INTERP_WHITELIST
+    mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
+    if stages is None:
+        stages = implied_stages(cube is not None, cube2 is not None, lut1d is not None, cdl is not None)
+    st = parse_stages(stages, interp=kw.get("interp"), interp2=mode2)
+    lut, lut2, lut1d, cdl, rgb_matrix, held, prelut = _stack_resources(st, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id,
+                                                                      rgb_matrix, engine)
     check_stack_options(kw["pix_fmt"], kw["out_pix_fmt"], stages=st, cdl=cdl is not None, lut=lut is not None or held("n"),
                         lut2=lut2 is not None or held("n2"), lut1d=lut1d is not None or held("n1d"), prelut=prelut,
                         dither=kw.get("dither", "none"), chroma_loc=chroma_loc, out_size=out_size, alpha_mode=alpha_mode,
@@ -278,19 +305,7 @@ def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d,
     eng = engine if engine is not None else _cached_engine(devices)
     call = {k: v for k, v in kw.items() if k not in ("dither", "interp", "alpha_mode")}
     with eng._lock:                 # uploads, precision and launch of ONE task, as in apply_lut
-        if lut is not None and eng._applied_lut is not lut:
-            eng.set_lut(lut)
-            eng._applied_lut = lut
-        if lut2 is not None and eng._applied_lut2 is not lut2:
-            eng.set_lut2(lut2)
-            eng._applied_lut2 = lut2
-        if lut1d is not None:
-            had = eng._applied_lut1d
-            if not (had is not None and had[0] is lut1d and had[1] == interp1d):
-                eng.set_lut1d(lut1d, interp1d)
-                eng._applied_lut1d = (lut1d, interp1d)
-        if eng.precision != precision:
-            eng.set_precision(precision)
+        _stack_upload(eng, lut, lut2, lut1d, interp1d, precision)
         if strength is not None:
             call["strength"] = strength
         if matte is not None:
@@ -298,6 +313,32 @@ def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d,
         if rgb_matrix is not None:
             call["rgb_matrix"] = rgb_matrix
         result = eng.apply_yuv_stack(planes, out, stages=st, cdl=cdl, **call)
+        if own:
+            eng.sync()
+    return result
+
+
+def _apply_rgb_stack(planes, out, plan, pix_fmt, out_pix_fmt, rgb_stages, interp, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id,
+                     rgb_matrix, engine, devices, precision, refusable):
+    """`apply_lut(rgb_stages=...)`: load what the list names, with the caches the other routes use, and route to
+    `apply_rgb_stack`.  `refusable`: the options of the call the pass does not take, by `check_rgb_stack_options`' keyword."""
+    from .plan import INTERP_WHITELIST
+    mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
+    st = parse_stages(rgb_stages, interp=interp, interp2=mode2)
+    lut, lut2, lut1d, cdl, rgb_matrix, held, prelut = _stack_resources(st, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id,
+                                                                      rgb_matrix, engine)
+    if precision not in ("strict", "fast", "fma32"):
+        raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
+    check_rgb_stack_options(pix_fmt, out_pix_fmt, stages=st, cdl=cdl is not None, lut=lut is not None or held("n"),
+                            lut2=lut2 is not None or held("n2"), lut1d=lut1d is not None or held("n1d"), prelut=prelut,
+                            rgb_matrix=rgb_matrix is not None,
+                            intermediate_pix_fmt=plan.intermediate_pix_fmt if plan.prologue else None, **refusable)
+    own = engine is None
+    eng = engine if engine is not None else _cached_engine(devices)
+    with eng._lock:                 # uploads, precision and launch of ONE task, as in apply_lut
+        _stack_upload(eng, lut, lut2, lut1d, interp1d, precision)
+        result = eng.apply_rgb_stack(planes, out, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, stages=st, cdl=cdl, rgb_matrix=rgb_matrix,
+                                     matrix_out=plan.matrix or "smpte170m", range_out="tv")
         if own:
             eng.sync()
     return result
@@ -311,7 +352,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
               cube2=None, interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None, cdl_id: Optional[str] = None,
               lut1d=None, interp1d: str = "linear", stages=None, strength=None, matte=None, matte_depth: Optional[int] = None,
-              matte_invert: bool = False, rgb_out: Optional[str] = None, rgb_matrix=None):
+              matte_invert: bool = False, rgb_out: Optional[str] = None, rgb_matrix=None, rgb_stages=None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -427,7 +468,14 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     "matrix" stage of `stages`: an `rgbmatrix.RgbMatrix` (nine numbers row-major and an offset in unit floats) or the path of a
     .spimtx file.  The stage computes clamp(M * rgb + offset, 0, 1) on unit RGB where the list places it, e.g.
     stages="lut1d,matrix,lut3d".  It has no implied position: `rgb_matrix` without `stages`, without a matrix stage in it, or a
-    matrix stage without `rgb_matrix` is a ValueError, and so is a strength or matte together with it."""
+    matrix stage without `rgb_matrix` is a ValueError, and so is a strength or matte together with it.
+
+    `rgb_stages` is `stages` for an RGB `pix_fmt` -- gbrp*, gbrap* or a packed name: the same lists, the same
+    resources (`cube`, `cube2`, `lut1d`, `cdl`, `rgb_matrix`), run on the source's own codes in ONE pass
+    (LutEngine.apply_rgb_stack) into a planar YUV `out_pix_fmt`, or into gbrp* / gbrap* at the source's depth -- the default for
+    a planar source.  It is valid only with an RGB `pix_fmt`; `stages` together with it, a float source, a packed RGB output, a
+    gbrp output of another depth, a source flagged full range, dither, resolution, chroma_loc, strength, matte, premultiplied
+    alpha and a second output are ValueErrors naming them."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -439,9 +487,15 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         from .multigpu import LutEngineGroup
         if isinstance(engine, LutEngineGroup) or (engine is None and len(devices) > 1):
             raise ValueError("resolution needs a single device")
-    if rgb_matrix is not None and stages is None:
+    if rgb_stages is not None and stages is not None:
+        raise ValueError("stages and rgb_stages are mutually exclusive: stages is the list of a YUV source, rgb_stages that of an "
+                         "RGB source")
+    if rgb_matrix is not None and stages is None and rgb_stages is None:
         raise ValueError("rgb_matrix needs stages: a matrix stage has no implied position (e.g. stages='lut1d,matrix,lut3d')")
     rgb_src = parse_rgb_source(pix_fmt)
+    if rgb_stages is not None and rgb_src is None:
+        raise ValueError(f"rgb_stages is the stage list of an RGB source (gbrp*, gbrap*, a packed name): '{pix_fmt}' is not one; "
+                         f"a YUV source takes stages")
     if rgb_src is not None and rgb_src.packed:
         got_w, got_h = planes.shape[-2], planes.shape[-3]
     else:
@@ -463,6 +517,18 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     # (the plan only carries the path into the filter string / notes; a parsed CubeLut or an engine that already holds the
     # lattice has none)
     plan = resolve_lut_plan(params, cube if isinstance(cube, (str, Path)) else "engine.cube", info)
+    if rgb_stages is not None:
+        # the stage stack on an RGB source: a route of its own
+        dither = "error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none"
+        if engine_dither is not None:
+            dither = resolve_engine_dither(engine_dither, dither)
+        if rgb_out is not None:
+            raise ValueError(f"rgb_out ('{rgb_out}') names the RGB output of a YUV source: with rgb_stages the output is out_pix_fmt")
+        result = _apply_rgb_stack(planes, out, plan, pix_fmt, out_pix_fmt, rgb_stages, interp, cube, cube2, interp2, lut1d, interp1d,
+                                  cdl, cdl_id, rgb_matrix, engine, devices, precision,
+                                  dict(dither=dither, chroma_loc=chroma_loc, out_size=out_size, alpha_mode=alpha_mode,
+                                       out2_pix_fmt=second_pix_fmt, strength=strength, matte=matte))
+        return result, output_color_tags(plan.output_policy)
     if rgb_out is not None:
         # YUV in, RGB out: a route of its own, with none of the options below
         kw = engine_call_for(plan, pix_fmt, out_pix_fmt, alpha_mode, rgb_out=rgb_out)

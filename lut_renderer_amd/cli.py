@@ -20,7 +20,7 @@ import signal
 import sys
 import time
 
-from .formats import (check_cdl_options, check_chroma_loc, check_container_options, check_lut1d_options, check_lut2, check_stack_options, implied_stages, parse_stages,
+from .formats import (check_cdl_options, check_chroma_loc, check_container_options, check_lut1d_options, check_lut2, check_rgb_stack_options, check_stack_options, implied_stages, parse_stages,
                       check_premul_options, parse_size, refuse_alpha_resize, source_bit_depth)
 
 
@@ -114,6 +114,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "stages, a lut3d stage without a mode takes --interp / --interp2; every stage needs its file and every "
                          "file its stage; planar YUV on both sides, no dither, --chroma-loc, --out-size, --second-output or "
                          "--alpha-mode premultiplied")
+    ap.add_argument("--rgb-stages", default=None, metavar="LIST",
+                    help="engine setting: --stages for an RGB --pix-fmt (gbrp*, gbrap*, rgb24 .. rgba64le; DESIGN.md 3.26): the same "
+                         "lists and files, run on the source's own codes in ONE pass into a planar YUV --out-pix-fmt, or into gbrp* "
+                         "at the source's depth (the default for a planar source); no dither, --chroma-loc, --out-size, --strength, "
+                         "--matte, --second-output or --alpha-mode premultiplied; not together with --stages")
     ap.add_argument("--rgb-matrix", default=None, metavar="\"M00 M01 M02 M10 .. M22\"",
                     help="engine setting: the nine numbers, row-major, of the RGB matrix a 'matrix' stage of --stages applies "
                          "(DESIGN.md 3.25; a gamut conversion, a white-balance or channel-mixer trim, a channel swap): "
@@ -242,6 +247,59 @@ def stack_call_from_args(args, kw: dict, cdl) -> dict:
     return call
 
 
+def rgb_stack_call_from_args(args, plan) -> dict:
+    """The keyword arguments of `apply_rgb_stack` for --rgb-stages, with `pix_fmt` / `out_pix_fmt` as every
+    call of `plan_from_args` carries them and the parsed list under `rgb_stages`: the list parsed with --interp / --interp2 as
+    the lut3d stages' defaults, every refusal of `check_rgb_stack_options`, and a file for every stage and a stage for every
+    file."""
+    from .plan import INTERP_WHITELIST
+    if getattr(args, "stages", None) is not None:
+        raise ValueError("--stages and --rgb-stages are mutually exclusive: --stages is the list of a YUV source, --rgb-stages "
+                         "that of an RGB source")
+    if getattr(args, "rgb_out", None) is not None:
+        raise ValueError("--rgb-out names the RGB output of a YUV source: with --rgb-stages the output is --out-pix-fmt")
+    interp2 = getattr(args, "interp2", None)
+    mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
+    cube2, lut1d = getattr(args, "cube2", None), getattr(args, "lut1d", None)
+    cdl, mtx = cdl_from_args(args), rgb_matrix_from_args(args)
+    strength, keys = strength_from_args(args)
+    matte = matte_from_args(args)
+    st = parse_stages(args.rgb_stages, interp=plan.interp, interp2=mode2)
+    kinds = [k for k, _m in st]
+    for flag, given, kind in (("--cube", args.cube, "lut3d"), ("--cube2", cube2, "lut3d2"), ("--lut1d", lut1d, "lut1d"),
+                              ("--cdl / --cdl-sop / --cdl-sat", cdl, "cdl"), ("--rgb-matrix / --rgb-matrix-file", mtx, "matrix")):
+        if given is not None and kind not in kinds:
+            raise ValueError(f"{flag} is given and --rgb-stages has no '{kind}' stage")
+    if interp2 is not None and "lut3d2" not in kinds:
+        raise ValueError("--interp2 is the mode of the second LUT: --rgb-stages has no 'lut3d2' stage")
+    interp1d = getattr(args, "interp1d", None) or "linear"
+    from . import _native
+    if interp1d not in _native.INTERP1D:
+        raise ValueError(f"lut1d has no interpolation mode '{interp1d}' ({' | '.join(_native.INTERP1D)})")
+    prelut = False
+    if ("cdl" in kinds or "matrix" in kinds) and args.cube is not None and os.path.isfile(args.cube):
+        from pathlib import Path
+        from . import engine  # noqa: F401  (torch first, as in plan_from_args)
+        from .api import _cached_cube
+        prelut = getattr(_cached_cube(Path(args.cube)), "prelut", None) is not None
+    second_out, second_fmt = getattr(args, "second_output", None), getattr(args, "second_pix_fmt", None)
+    _st, _fin, fout = check_rgb_stack_options(
+        args.pix_fmt, args.out_pix_fmt, stages=st, cdl=cdl is not None, lut=args.cube is not None, lut2=cube2 is not None,
+        lut1d=lut1d is not None, prelut=prelut, rgb_matrix=mtx is not None,
+        dither="error_diffusion" if args.zscale_dither == "error_diffusion" else getattr(args, "engine_dither", None) or "none",
+        chroma_loc=getattr(args, "chroma_loc", None), out_size=getattr(args, "out_size", None),
+        alpha_mode=getattr(args, "alpha_mode", None) or "straight",
+        out2_pix_fmt=second_fmt if second_fmt is not None else second_out,
+        strength=strength if keys is None else 1.0, matte=matte is not None,
+        intermediate_pix_fmt=plan.intermediate_pix_fmt if plan.prologue else None)
+    call = dict(pix_fmt=args.pix_fmt, out_pix_fmt=fout.name, rgb_stages=st, matrix_out=plan.matrix or "smpte170m", range_out="tv")
+    if cdl is not None:
+        call["cdl"] = cdl
+    if mtx is not None:
+        call["rgb_matrix"] = mtx
+    return call
+
+
 def matte_from_args(args):
     """None without --matte, else dict(matte=the path, matte_pix_fmt=, matte_invert=); --matte-pix-fmt / --matte-invert without
     --matte, '-' and an unknown format are errors."""
@@ -283,11 +341,15 @@ def plan_from_args(args):
                      colorspace=args.colorspace, color_range=args.color_range)
     lut1d = getattr(args, "lut1d", None)
     stages = getattr(args, "stages", None)
-    if args.cube is None and lut1d is None and stages is None:
+    rgb_stages = getattr(args, "rgb_stages", None)
+    if args.cube is None and lut1d is None and stages is None and rgb_stages is None:
         raise ValueError("--cube is required unless --lut1d is given")
     plan = resolve_lut_plan(params, args.cube if args.cube is not None else "engine.cube", info)
     alpha_mode = getattr(args, "alpha_mode", None) or "straight"
     rgb_out = getattr(args, "rgb_out", None)
+    if rgb_stages is not None:
+        # the stage stack on an RGB source: a route of its own
+        return plan, rgb_stack_call_from_args(args, plan), w, h
     if rgb_out is not None:
         # YUV in, RGB out: a route of its own, with none of the options below
         from .formats import check_yuv2rgb_options
@@ -385,7 +447,7 @@ def plan_from_args(args):
 def main(argv=None) -> int:
     ap = build_parser()
     args = ap.parse_args(argv)
-    if args.cube is None and args.lut1d is None and args.stages is None:
+    if args.cube is None and args.lut1d is None and args.stages is None and args.rgb_stages is None:
         ap.error("the following arguments are required: --cube (or --lut1d for a 1D LUT alone)")
 
     stop = {"flag": False}
@@ -427,8 +489,8 @@ def main(argv=None) -> int:
         if "matte" in kw:
             kw["matte"] = MatteReader(kw.pop("matte"), kw.pop("matte_pix_fmt"), w, h)
         pipe = HostPipeline(eng, pix_fmt, w, h, batch=args.batch, out_pix_fmt=out_fmt, out_size=args.out_size,
-                            second_pix_fmt=second_fmt, chain=lut2 is not None and "stages" not in kw,
-                            lut1d=args.lut1d is not None and "stages" not in kw, rgb_out=rgb_out, **kw)
+                            second_pix_fmt=second_fmt, chain=lut2 is not None and "stages" not in kw and "rgb_stages" not in kw,
+                            lut1d=args.lut1d is not None and "stages" not in kw and "rgb_stages" not in kw, rgb_out=rgb_out, **kw)
         fb = pipe.fin.frame_bytes
         if piped_in:
             total = None if args.duration is None else max(1, int(round(args.duration * args.fps)))

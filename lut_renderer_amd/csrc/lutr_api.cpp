@@ -1719,23 +1719,21 @@ static int check_rgb_matrix(const lutr_rgb_matrix *mtx)
     return LUTR_OK;
 }
 
-// ---- an ordered stack of lut1d / CDL / lut3d stages (DESIGN.md 3.21)
-// lutr_apply_yuv_cdl's pass with the stage list compiled into steps: the pixel's state (codes or unit) is followed here, so the
-// kernels are told which form of a lattice stage to run and where the rounding goes.
-// `mix` (DESIGN.md 3.22): nullptr for lutr_apply_yuv_stack, the strength for lutr_apply_yuv_stack_mix.
-// `matte` (DESIGN.md 3.23; with `mix`): the matte of lutr_apply_yuv_stack_matte, its pointer, depth and invert already checked.
-// `with_mtx` (DESIGN.md 3.25; without `mix`): the call is lutr_apply_yuv_stack_matrix's, the one entry that takes a matrix stage;
-// `mtx` is its matrix, or nullptr.
-static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
-                           const MixConsts *mix, const lutr_matte *matte, bool with_mtx, const lutr_rgb_matrix *mtx, int w, int h,
-                           int nframes, const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+// ---- the stage list of the stack entries, the one copy of its checks, its compilation into steps
+// and its device resources.  What a list gives: which kinds it names, its text for lutr_ctx_last_kernel, its step word.
+struct StackList {
+    bool seen[6] = {false, false, false, false, false, false};
+    std::string list;
+    unsigned long long ops = 0;
+};
+
+// `with_mtx`: the entry takes a matrix stage (lutr_apply_yuv_stack_matrix, lutr_apply_rgb_stack); `mtx` is its matrix, or nullptr
+static int stack_check_list(const lutr_ctx *c, const lutr_stage *stages, int nstages, const lutr_cdl *cdl, bool with_mtx,
+                            const lutr_rgb_matrix *mtx, StackList *T)
 {
-    if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
     if (nstages < 1 || nstages > 4) { set_error("stack: %d stages; a stack has 1 to 4", nstages); return LUTR_EINVAL; }
     if (!stages) { set_error("stack: null stage list"); return LUTR_EINVAL; }
     static const char *const kind_name[6] = {"", "lut3d", "lut3d2", "lut1d", "cdl", "matrix"};
-    bool seen[6] = {false, false, false, false, false, false};
-    std::string list;
     for (int i = 0; i < nstages; i++) {
         const int k = stages[i].kind;
         if (k < LUTR_STAGE_LUT3D || k > LUTR_STAGE_MATRIX) { set_error("stack: stage %d has unknown kind %d", i, k); return LUTR_EINVAL; }
@@ -1744,36 +1742,42 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
                       "together with a matrix is not supported", i);
             return LUTR_EINVAL;
         }
-        if (seen[k]) { set_error("stack: stage kind %s is listed twice; each kind may appear once", kind_name[k]); return LUTR_EINVAL; }
-        seen[k] = true;
-        if (i) list += ",";
-        list += kind_name[k];
+        if (T->seen[k]) { set_error("stack: stage kind %s is listed twice; each kind may appear once", kind_name[k]); return LUTR_EINVAL; }
+        T->seen[k] = true;
+        if (i) T->list += ",";
+        T->list += kind_name[k];
         if (k == LUTR_STAGE_LUT3D || k == LUTR_STAGE_LUT3D_2) {
             if (stages[i].interp < LUTR_INTERP_NEAREST || stages[i].interp > LUTR_INTERP_PRISM) {
                 set_error("stack: unknown interpolation mode %d on stage %d (%s)", stages[i].interp, i, kind_name[k]);
                 return LUTR_EINVAL;
             }
-            list += ":" + std::to_string(stages[i].interp);
+            T->list += ":" + std::to_string(stages[i].interp);
         }
     }
-    if (seen[LUTR_STAGE_LUT3D] && !c->lat) { set_error("stack: no lattice set on this context (call lutr_ctx_set_lut first)"); return LUTR_EINVAL; }
-    if (seen[LUTR_STAGE_LUT3D_2] && !c->lat2) {
+    if (T->seen[LUTR_STAGE_LUT3D] && !c->lat) { set_error("stack: no lattice set on this context (call lutr_ctx_set_lut first)"); return LUTR_EINVAL; }
+    if (T->seen[LUTR_STAGE_LUT3D_2] && !c->lat2) {
         set_error("stack: no second lattice set on this context (call lutr_ctx_set_lut2 first)");
         return LUTR_EINVAL;
     }
-    if (seen[LUTR_STAGE_LUT1D] && !c->l1d_size) {
+    if (T->seen[LUTR_STAGE_LUT1D] && !c->l1d_size) {
         set_error("stack: no 1D LUT set on this context (call lutr_ctx_set_lut1d first)");
         return LUTR_EINVAL;
     }
-    if (seen[LUTR_STAGE_CDL] && !cdl) { set_error("stack: a cdl stage is listed and the CDL is null"); return LUTR_EINVAL; }
-    if (!seen[LUTR_STAGE_CDL] && cdl) { set_error("stack: a CDL is given and no cdl stage is listed"); return LUTR_EINVAL; }
+    if (T->seen[LUTR_STAGE_CDL] && !cdl) { set_error("stack: a cdl stage is listed and the CDL is null"); return LUTR_EINVAL; }
+    if (!T->seen[LUTR_STAGE_CDL] && cdl) { set_error("stack: a CDL is given and no cdl stage is listed"); return LUTR_EINVAL; }
     if (cdl)
         if (const int rc = check_cdl(cdl)) return rc;
-    if (seen[LUTR_STAGE_MATRIX] && !mtx) { set_error("stack: a matrix stage is listed and the matrix is null"); return LUTR_EINVAL; }
-    if (!seen[LUTR_STAGE_MATRIX] && mtx) { set_error("stack: a matrix is given and no matrix stage is listed"); return LUTR_EINVAL; }
+    if (T->seen[LUTR_STAGE_MATRIX] && !mtx) { set_error("stack: a matrix stage is listed and the matrix is null"); return LUTR_EINVAL; }
+    if (!T->seen[LUTR_STAGE_MATRIX] && mtx) { set_error("stack: a matrix is given and no matrix stage is listed"); return LUTR_EINVAL; }
     if (mtx)
         if (const int rc = check_rgb_matrix(mtx)) return rc;
-    if (const int rc = check_geometry(w, h, nframes, row0, rows)) return rc;
+    return LUTR_OK;
+}
+
+// The pixel's state (codes or unit) is followed here, so the kernels are told which form of a lattice stage to run and where the
+// rounding goes.
+static int stack_compile_steps(const lutr_ctx *c, const lutr_stage *stages, int nstages, StackList *T)
+{
     // the steps: a unit pixel is rounded to codes ahead of lut1d, ahead of the CDL (behind a matrix) and at the end of the list
     unsigned long long ops = 0;
     int nops = 0;
@@ -1815,6 +1819,57 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
         }
     }
     if (unit) push(STACK_OP_ROUND, 0);
+    T->ops = ops;
+    return LUTR_OK;
+}
+
+// the lattices, the step word and the tables of the listed stages at `depth`, behind hipSetDevice
+static int stack_device_consts(lutr_ctx *c, const StackList &T, const lutr_cdl *cdl, const lutr_rgb_matrix *mtx, int depth, LutConsts *L,
+                               LutConsts *L2, StackConsts *S, MtxConsts *X)
+{
+    if (T.seen[LUTR_STAGE_LUT3D])
+        if (const int rc = fill_lut(L, c, depth)) return rc;
+    if (T.seen[LUTR_STAGE_LUT3D_2]) *L2 = second_lattice(c, depth);
+    S->ops = T.ops;
+    S->stride = 1 << depth;
+    S->sat = 1.0f;
+    S->maxf = (float)((1 << depth) - 1);
+    if (cdl) {
+        CdlConsts C;
+        if (const int rc = cdl_device_table(c, *cdl, depth, &C)) return rc;
+        S->cdl_tab = C.tab;
+        S->sat = C.sat;
+        S->lds_cdl_words = 3 * S->stride;
+    }
+    if (T.seen[LUTR_STAGE_LUT1D]) {
+        L1dConsts C1;
+        if (const int rc = l1d_device_table(c, depth, &C1)) return rc;
+        S->l1d_tab = C1.tab;
+        S->lds_l1d_words = 3 * (S->stride >> 1);
+    }
+    if (mtx) {
+        for (int i = 0; i < 9; i++) X->m[i] = mtx->m[i];
+        for (int i = 0; i < 3; i++) X->off[i] = mtx->offset[i];
+        X->rcp = 1.0f / S->maxf;
+    }
+    return LUTR_OK;
+}
+
+// ---- an ordered stack of lut1d / CDL / lut3d stages (DESIGN.md 3.21)
+// lutr_apply_yuv_cdl's pass with the stage list compiled into steps (stack_compile_steps).
+// `mix` (DESIGN.md 3.22): nullptr for lutr_apply_yuv_stack, the strength for lutr_apply_yuv_stack_mix.
+// `matte` (DESIGN.md 3.23; with `mix`): the matte of lutr_apply_yuv_stack_matte, its pointer, depth and invert already checked.
+// `with_mtx` (DESIGN.md 3.25; without `mix`): the call is lutr_apply_yuv_stack_matrix's, the one entry that takes a matrix stage;
+// `mtx` is its matrix, or nullptr.
+static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                           const MixConsts *mix, const lutr_matte *matte, bool with_mtx, const lutr_rgb_matrix *mtx, int w, int h,
+                           int nframes, const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+{
+    if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
+    StackList T;
+    if (const int rc = stack_check_list(c, stages, nstages, cdl, with_mtx, mtx, &T)) return rc;
+    if (const int rc = check_geometry(w, h, nframes, row0, rows)) return rc;
+    if (const int rc = stack_compile_steps(c, stages, nstages, &T)) return rc;
     if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
     UnionCall U; const FrameGeom G{w, h, row0, rows, nframes};
     if (const int rc = union_open(*p, src, dst, &U)) return rc;
@@ -1847,38 +1902,13 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
                         1.0f / maxm, matte->invert, mb == 2};
     }
     HIP_TRY(hipSetDevice(c->device));
-    LutConsts L{}; StackConsts S{}; PlaneSet P;
-    if (seen[LUTR_STAGE_LUT3D])
-        if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
-    const LutConsts L2 = seen[LUTR_STAGE_LUT3D_2] ? second_lattice(c, p->lut_depth) : LutConsts{};
-    S.ops = ops;
-    S.stride = 1 << p->lut_depth;
-    S.sat = 1.0f;
-    S.maxf = (float)((1 << p->lut_depth) - 1);
-    if (cdl) {
-        CdlConsts C;
-        if (const int rc = cdl_device_table(c, *cdl, p->lut_depth, &C)) return rc;
-        S.cdl_tab = C.tab;
-        S.sat = C.sat;
-        S.lds_cdl_words = 3 * S.stride;
-    }
-    if (seen[LUTR_STAGE_LUT1D]) {
-        L1dConsts C1;
-        if (const int rc = l1d_device_table(c, p->lut_depth, &C1)) return rc;
-        S.l1d_tab = C1.tab;
-        S.lds_l1d_words = 3 * (S.stride >> 1);
-    }
-    MtxConsts X{};
-    if (mtx) {
-        for (int i = 0; i < 9; i++) X.m[i] = mtx->m[i];
-        for (int i = 0; i < 3; i++) X.off[i] = mtx->offset[i];
-        X.rcp = 1.0f / S.maxf;
-    }
+    LutConsts L{}, L2{}; StackConsts S{}; MtxConsts X{}; PlaneSet P;
+    if (const int rc = stack_device_consts(c, T, cdl, mtx, p->lut_depth, &L, &L2, &S, &X)) return rc;
     fill_planes(&P, src, dst);
     const char *name = launch_yuv_stack(c->stream, c->variant, L, L2, S, U.K, P, G, Si.depth, Di.depth, Si.csx, Si.csy, Di.csx, Di.csy, mix,
                                         matte ? &A : nullptr, with_mtx ? &X : nullptr);
     if (!name) return finish_launch(c, nullptr);
-    const std::string full = std::string(name) + "[" + list + "]";
+    const std::string full = std::string(name) + "[" + T.list + "]";
     return finish_launch(c, full.c_str());
 }
 
@@ -2241,6 +2271,89 @@ int lutr_apply_rgb_to_yuv(lutr_ctx *c, const lutr_yuv_params *p, int interp, int
     FloatPlanes F;
     if (const int rc = dither_scratch(c, G, D.csx, D.csy, &F)) return rc;
     return finish_launch(c, launch_rgb2yuv_dither(c->stream, L, K, P, Y, G, F, D.depth, D.csx, D.csy, interp));
+}
+
+// ---- the stage stack on an RGB source: lutr_apply_rgb_to_yuv's source through the list of
+// lutr_apply_yuv_stack_matrix into planar YUV (dst_kind 0) or three gbrp planes at the source's depth (dst_kind = that depth)
+int lutr_apply_rgb_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                         const lutr_rgb_matrix *mtx, int src_kind, int w, int h, int nframes, const lutr_planes *src_planar,
+                         const lutr_packed *src_packed, int dst_kind, const lutr_planes *dst, int row0, int rows)
+{
+    const void *src = src_kind ? (const void *)src_packed : (const void *)src_planar;
+    if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
+    StackList T;
+    if (const int rc = stack_check_list(c, stages, nstages, cdl, true, mtx, &T)) return rc;
+    if (const int rc = check_geometry(w, h, nframes, row0, rows)) return rc;
+    if (const int rc = stack_compile_steps(c, stages, nstages, &T)) return rc;
+    const bool yuv = dst_kind == LUTR_RGB_STACK_YUV;
+    if (!yuv && (dst_kind < 8 || dst_kind > 16)) {
+        set_error("rgb stack: destination kind %d is neither LUTR_RGB_STACK_YUV nor a gbrp depth in 8..16", dst_kind);
+        return LUTR_EINVAL;
+    }
+    if (yuv && !p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    YuvConsts K{};
+    if (yuv)
+        if (const int rc = make_yuv_consts_rgb2yuv(*p, &K)) return rc;
+    // the depth of the list: the YUV call's lut_depth, which a packed source must have; else the gbrp destination's, likewise
+    const int dl = yuv ? p->lut_depth : dst_kind;
+    RgbLayout Y;
+    if (!yuv && src_kind) {
+        PackedFmt f;
+        if (const int rc = decode_packed(src_kind, &f)) return rc;
+        if (f.bits != dl) {
+            set_error("rgb stack: a gbrp destination of %d bits from a source of %d bits: the planar RGB destination has the source's depth",
+                      dl, f.bits);
+            return LUTR_EINVAL;
+        }
+    }
+    if (const int rc = rgb_side_layout(src_kind, dl, "source", &Y)) return rc;
+    const Side D = yuv ? planar_side("destination", dst, p->fmt_out) : Side{};
+    const int ocsx = yuv ? D.csx : 0, ocsy = yuv ? D.csy : 0;
+    if (c->variant == VAR_VEC_LDS) {
+        set_error("variant vec_lds: there is no LDS-window kernel for the RGB stack pass");
+        return LUTR_EINVAL;
+    }
+    if (const int rc = check_row_blocks(row0, rows, h, 1 << ocsy, "output chroma block height")) return rc;
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    PlaneSet P{}; Span ss[3], ds[3]; int ns; const FrameGeom G{w, h, row0, rows, nframes};
+    if (const int rc = rgb_side_streams(Y, src_planar, src_packed, G, true, &P, ss, &ns)) return rc;
+    if (const int rc = check_planes_set(dst, nullptr)) return rc;
+    if (yuv) {
+        for (int i = 0; i < 3; i++) { P.d[i] = (uint8_t *)dst->data[i]; P.ds[i] = dst->stride[i]; P.dfs[i] = dst->frame_stride[i]; }
+        // a chroma sample is written by one thread while another may still read the pixels of its block: no in-place operation
+        side_spans(D, G, ds);
+        if (const int rc = check_disjoint("the RGB stack pass", false, ss, ns, ds, 3)) return rc;
+    } else {
+        const RgbLayout Yd{1, dl > 8, 0, 0, 0};
+        int nd;
+        if (const int rc = rgb_side_streams(Yd, dst, nullptr, G, false, &P, ds, &nd)) return rc;
+        if (Yd.wide)
+            for (int i = 0; i < 3; i++)
+                if (!check_aligned(dst->data[i], dst->stride[i], dst->frame_stride[i], nframes, 1)) {
+                    set_error("plane %d: 16-bit planes need 2-byte aligned rows", i);
+                    return LUTR_EINVAL;
+                }
+        // A sample is read and written by the same lane: plane k of the destination may be plane k of a planar source, row for
+        // row.  Any other overlap would let a thread's stores land on samples another thread has yet to read.
+        bool same = !src_kind;
+        for (int k = 0; k < 3 && same; k++) same = P.s[k] == P.d[k] && P.ss[k] == P.ds[k] && (nframes == 1 || P.sfs[k] == P.dfs[k]);
+        if (!same)
+            if (const int rc = check_disjoint("an RGB stack call between different buffers", false, ss, ns, ds, 3)) return rc;
+    }
+    if (Y.step == 1 && Y.wide)
+        for (int i = 0; i < 3; i++)
+            if (!check_aligned(src_planar->data[i], src_planar->stride[i], src_planar->frame_stride[i], nframes, 1)) {
+                set_error("plane %d: 16-bit planes need 2-byte aligned rows", i);
+                return LUTR_EINVAL;
+            }
+    HIP_TRY(hipSetDevice(c->device));
+    LutConsts L{}, L2{}; StackConsts S{}; MtxConsts X{};
+    if (const int rc = stack_device_consts(c, T, cdl, mtx, dl, &L, &L2, &S, &X)) return rc;
+    const char *name = launch_rgb_stack(c->stream, c->variant, L, L2, S, X, K, P, Y, G, yuv ? SINK_YUV : SINK_RGB, yuv ? D.depth : dl,
+                                        ocsx, ocsy);
+    if (!name) return finish_launch(c, nullptr);
+    const std::string full = std::string(name) + "[" + T.list + "]";
+    return finish_launch(c, full.c_str());
 }
 
 int lutr_apply_yuv_to_rgb(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dst_kind, int w, int h, int nframes,

@@ -357,6 +357,37 @@ __device__ __forceinline__ void st_words(uint8_t *p, const uint32_t *w)
     }
 }
 
+// ---------------------------------------------------------------- RGB sources of the vector kernels (lutr_rgb2yuv.hip, lutr_rgbstack.hip)
+// `in` holds the 8 pixels of a thread and row: planar (NC = 1) the 8 samples of R, of G and of B one after the other; packed
+// (NC = 3 | 4) the 8 pixels as they lie in memory.
+
+// component `off` (runtime, wave-uniform) of pixel i of a 4-component run
+template <int WIDE>
+__device__ __forceinline__ float r2y_comp4(const uint32_t *w, int i, int off)
+{
+    if constexpr (WIDE) {
+        const unsigned long long pv = ((unsigned long long)w[2 * i + 1] << 32) | w[2 * i];
+        return (float)(unsigned)((pv >> (off * 16)) & 0xffffull);
+    } else {
+        return (float)((w[i] >> (off * 8)) & 0xffu);
+    }
+}
+
+template <int WIN, int NC>
+__device__ __forceinline__ Rgb r2y_pixel(const uint32_t *in, int i, const RgbLayout &Y)
+{
+    constexpr int SW = 8 * (WIN ? 2 : 1) / 4;             // dwords of 8 samples of one plane
+    if constexpr (NC == 1) {
+        return Rgb{word_sample<WIN>(in, i), word_sample<WIN>(in + SW, i), word_sample<WIN>(in + 2 * SW, i)};
+    } else if constexpr (NC == 3) {
+        const float c0 = word_sample<WIN>(in, i * 3), c1 = word_sample<WIN>(in, i * 3 + 1), c2 = word_sample<WIN>(in, i * 3 + 2);
+        const bool swap = Y.ro != 0;                      // bgr order
+        return Rgb{swap ? c2 : c0, c1, swap ? c0 : c2};
+    } else {
+        return Rgb{r2y_comp4<WIN>(in, i, Y.ro), r2y_comp4<WIN>(in, i, Y.go), r2y_comp4<WIN>(in, i, Y.bo)};
+    }
+}
+
 // ---------------------------------------------------------------- plane rows
 template <class Y>
 __device__ __forceinline__ const uint8_t *src_row(const PlaneSet &P, int c, long long fr, Y y)

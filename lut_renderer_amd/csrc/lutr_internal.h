@@ -384,6 +384,24 @@ LUTR_R2Y_DECL(w00) LUTR_R2Y_DECL(w11) LUTR_R2Y_DECL(w10)
 const char *launch_rgb2yuv_dither(hipStream_t st, const LutConsts &L, const YuvConsts &K, const PlaneSet &P, const RgbLayout &Y,
                                   const FrameGeom &G, const FloatPlanes &F, int dout, int ocsx, int ocsy, int mode);
 
+// the stage stack on an RGB source (lutr_rgbstack.hip): launch_rgb2yuv's source (P.s, Y) through the step list S
+// (StackConsts, as launch_yuv_stack takes it; X is read by the matrix steps only) into one of two sinks: SINK_YUV = P.d is Y, Cb,
+// Cr at depth dout in the layout ocsx, ocsy, through K; SINK_RGB = P.d is three planes in R, G, B order at the source's depth
+// (dout is that depth, ocsx = ocsy = 0, K is not read; P.d may be P.s).  nullptr = the variant cannot take the call (vec_lds
+// always; vec_global on layouts the vector kernel cannot take and on pyramid / prism stages)
+enum RgbStackSink { SINK_YUV = 0, SINK_RGB = 1 };
+const char *launch_rgb_stack(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
+                             const MtxConsts &X, const YuvConsts &K, const PlaneSet &P, const RgbLayout &Y, const FrameGeom &G,
+                             int sink, int dout, int ocsx, int ocsy);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>); tri: some lattice step is trilinear; lds:
+// stage the tables per workgroup.  nullptr = not a source kind / sink / layout it has
+#define LUTR_RSK_DECL(tag) \
+    const char *launch_rgb_stack_vec_##tag(hipStream_t st, const LutConsts &L, const LutConsts &L2, const StackConsts &S, \
+                                           const MtxConsts &X, const YuvConsts &K, const PlaneSet &P, const RgbLayout &Y, \
+                                           const FrameGeom &G, int sink, int ocsx, int ocsy, bool tri, bool lds);
+LUTR_RSK_DECL(w00) LUTR_RSK_DECL(w11) LUTR_RSK_DECL(w10)
+#undef LUTR_RSK_DECL
+
 // the blue-noise path: the generic kernel with a DitherSink, row shards allowed; nullptr = a vector variant was
 // asked for (this path has no vector kernel yet)
 const char *launch_rgb2yuv_bn(hipStream_t st, int variant, const LutConsts &L, const YuvConsts &K, const PlaneSet &P,

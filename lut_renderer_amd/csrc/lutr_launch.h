@@ -224,6 +224,21 @@ const char *launch_union(int variant, const PlaneSet &P, const FrameGeom &G, con
     return both.c_str();
 }
 
+// Where the vector kernels of a stage stack (lutr_stack.hip, lutr_rgbstack.hip) read the CDL and 1D tables.  The tables the stack
+// uses go to LDS together or not at all: above 24 KB in sum they are read from global memory.  LUTR_STACK_LDS=0 / 1 (tests and
+// tools) says which; unset: the family's own default.
+constexpr size_t kStackLdsBytes = 24 * 1024;
+inline bool stack_in_lds(const StackConsts &S, bool family_default)
+{
+    const size_t bytes = (size_t)(S.lds_cdl_words + S.lds_l1d_words) * sizeof(uint32_t);
+    if (bytes == 0 || bytes > kStackLdsBytes) return false;
+    if (const char *e = getenv("LUTR_STACK_LDS")) {
+        if (e[0] == '0' && !e[1]) return false;
+        if (e[0] == '1' && !e[1]) return true;
+    }
+    return family_default;
+}
+
 // The persistent tile kernels pay a fixed start-up (coordinate table, tube staging, a wave's first tile at a quarter of the issue
 // rate) and end with a tail of partly idle CUs, so they only win on big launches.  Round 3, Gpx/s tile / plain vector kernels (taps
 // gathered from L1/L2, 5-8 waves per SIMD; profiles/r03_exp19_small_launches.txt), fused yuv420p10le strict: UHD 1 frame 181 / 272,

@@ -22,34 +22,8 @@ namespace lutr {
 // ================================================================= vector kernel, global gather
 // k_yuv_xsub_vec's structure with the input side replaced: whole-dword loads and stores, 8 luma samples per thread and row,
 // 2^OCSY rows per thread, lattice taps gathered from L1/L2 (frame written out: see k_yuv_vec).  NC = 1: three planes; 3 | 4: one packed image (8 pixels = 6, 8, 12 or
-// 16 dwords per row, unpacked as k_packed_vec does).  The component order of a packed source is a wave-uniform argument.
-
-// component `off` (runtime, wave-uniform) of pixel i of a 4-component run
-template <int WIDE>
-__device__ __forceinline__ float r2y_comp4(const uint32_t *w, int i, int off)
-{
-    if constexpr (WIDE) {
-        const unsigned long long pv = ((unsigned long long)w[2 * i + 1] << 32) | w[2 * i];
-        return (float)(unsigned)((pv >> (off * 16)) & 0xffffull);
-    } else {
-        return (float)((w[i] >> (off * 8)) & 0xffu);
-    }
-}
-
-template <int WIN, int NC>
-__device__ __forceinline__ Rgb r2y_pixel(const uint32_t *in, int i, const RgbLayout &Y)
-{
-    constexpr int SW = 8 * (WIN ? 2 : 1) / 4;             // dwords of 8 samples of one plane
-    if constexpr (NC == 1) {
-        return Rgb{word_sample<WIN>(in, i), word_sample<WIN>(in + SW, i), word_sample<WIN>(in + 2 * SW, i)};
-    } else if constexpr (NC == 3) {
-        const float c0 = word_sample<WIN>(in, i * 3), c1 = word_sample<WIN>(in, i * 3 + 1), c2 = word_sample<WIN>(in, i * 3 + 2);
-        const bool swap = Y.ro != 0;                      // bgr order
-        return Rgb{swap ? c2 : c0, c1, swap ? c0 : c2};
-    } else {
-        return Rgb{r2y_comp4<WIN>(in, i, Y.ro), r2y_comp4<WIN>(in, i, Y.go), r2y_comp4<WIN>(in, i, Y.bo)};
-    }
-}
+// 16 dwords per row, unpacked as k_packed_vec does: r2y_pixel, lutr_device.h).  The component order of a packed source is a
+// wave-uniform argument.
 
 template <int WIN, int NC, int WOUT, int OCSX, int OCSY, int INTERP>
 __global__ __launch_bounds__(256) void k_rgb2yuv_vec(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, RgbLayout Y)

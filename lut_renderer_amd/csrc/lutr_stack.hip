@@ -109,41 +109,9 @@
 
 #include "lutr_device.h"
 #include "lutr_launch.h"
+#include "lutr_stack_steps.h"   // stack_l1d_px, stack_round_px, mtx_px, stack_lattice, stack_block
 
 namespace lutr {
-
-// the 1D lookup of 3.20 on one pixel of codes
-__device__ __forceinline__ Rgb stack_l1d_px(const uint16_t *tab, int stride, const Rgb &q)
-{
-    Rgb t;
-    t.r = (float)tab[(int)q.r];
-    t.g = (float)tab[stride + (int)q.g];
-    t.b = (float)tab[2 * stride + (int)q.b];
-    return t;
-}
-
-// unit -> codes: the product and the sum each rounded on their own (no contraction); o in [0, 1] gives [0, M] without a clip
-__device__ __forceinline__ Rgb stack_round_px(float maxf, const Rgb &o)
-{
-    Rgb q;
-    q.r = (float)(int)(o.r * maxf + 0.5f);
-    q.g = (float)(int)(o.g * maxf + 0.5f);
-    q.b = (float)(int)(o.b * maxf + 0.5f);
-    return q;
-}
-
-// The RGB matrix of 3.25 on one pixel: u = p * k (k = 1 / M on codes; 1 on unit floats, where the product is u itself), then per
-// row two products summed, the third product added, the offset added -- each rounded on its own -- and the clamp to [0, 1].  The
-// host keeps the entries finite and small enough for every sum to be finite.
-__device__ __forceinline__ Rgb mtx_px(const MtxConsts &X, float k, const Rgb &p)
-{
-    const float r = p.r * k, g = p.g * k, b = p.b * k;
-    Rgb o;
-    o.r = med3(((X.m[0] * r + X.m[1] * g) + X.m[2] * b) + X.off[0], 0.0f, 1.0f);
-    o.g = med3(((X.m[3] * r + X.m[4] * g) + X.m[5] * b) + X.off[1], 0.0f, 1.0f);
-    o.b = med3(((X.m[6] * r + X.m[7] * g) + X.m[8] * b) + X.off[2], 0.0f, 1.0f);
-    return o;
-}
 
 enum StackForm { SK_PLAIN, SK_MIX, SK_MATTE };
 
@@ -190,54 +158,6 @@ __device__ __forceinline__ void stack_stage_tables(const StackConsts &S)
     for (int i = threadIdx.x; i < S.lds_cdl_words; i += 256) stack_lds[i] = a[i];
     for (int i = threadIdx.x; i < S.lds_l1d_words; i += 256) stack_lds[S.lds_cdl_words + i] = b[i];
     __syncthreads();
-}
-
-template <int INTERP, int N>
-__device__ __forceinline__ void stack_lattice(bool unit, const LutConsts &X, const GFetch &fx, Rgb (&px)[N])
-{
-    if (unit) {
-#pragma unroll
-        for (int i = 0; i < N; i++) px[i] = lut3d_unit<INTERP>(X, fx, px[i]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; i++) px[i] = lut3d_px<INTERP>(X, fx, px[i].r, px[i].g, px[i].b);
-    }
-}
-
-// The pixels of one union block through the step list.  Every branch depends on kernel arguments only.
-template <bool TRI, int N>
-__device__ __forceinline__ void stack_block(const StackConsts &S, const CdlConsts &C, const uint16_t *l1d, const LutConsts &L,
-                                            const LutConsts &L2, Rgb (&px)[N] SK_MTX_PARAM)
-{
-    const bool mix = S.sat != 1.0f;
-#pragma nounroll
-    for (unsigned long long ops = S.ops; ops & 0xffull; ops >>= 8) {
-        const int op = (int)(ops & 15u), mode = (int)((ops >> 4) & 15u);
-        if (op == STACK_OP_L1D) {
-#pragma unroll
-            for (int i = 0; i < N; i++) px[i] = stack_l1d_px(l1d, S.stride, px[i]);
-        } else if (op == STACK_OP_CDL) {
-#pragma unroll
-            for (int i = 0; i < N; i++) px[i] = cdl_px(C, mix, px[i]);
-        } else if (op == STACK_OP_ROUND) {
-#pragma unroll
-            for (int i = 0; i < N; i++) px[i] = stack_round_px(S.maxf, px[i]);
-#ifdef LUTR_SK_MTX
-        } else if (op == STACK_OP_MTX_CODES || op == STACK_OP_MTX_UNIT) {
-            const float k = op == STACK_OP_MTX_CODES ? X.rcp : 1.0f;
-#pragma unroll
-            for (int i = 0; i < N; i++) px[i] = mtx_px(X, k, px[i]);
-#endif
-        } else {
-            const bool second = op == STACK_OP_LAT2_CODES || op == STACK_OP_LAT2_UNIT;
-            const bool unit = op == STACK_OP_LAT_UNIT || op == STACK_OP_LAT2_UNIT;
-            const LutConsts X = second ? L2 : L;
-            const GFetch fx(X);                                   // each lattice its own fetch; a pixel holds one set of taps
-            if (mode == LUTR_INTERP_TETRAHEDRAL) stack_lattice<LUTR_INTERP_TETRAHEDRAL>(unit, X, fx, px);
-            else if (TRI && mode == LUTR_INTERP_TRILINEAR) stack_lattice<LUTR_INTERP_TRILINEAR>(unit, X, fx, px);
-            else stack_lattice<LUTR_INTERP_NEAREST>(unit, X, fx, px);
-        }
-    }
 }
 
 // union_vec_unit's structure (lutr_device.h), as this family's own copy, with the step walk as the per-block middle.  TRI: some
@@ -545,28 +465,16 @@ __global__ __launch_bounds__(256) void k_yuv_stack_generic(LutConsts L, LutConst
 }
 
 // ================================================================= launcher
-// LUTR_STACK_LDS=0 / 1: where the vector kernels read the CDL and 1D tables (tests and tools; unset: the default below).  The
-// tables the stack uses go to LDS together or not at all: above 24 KB in sum they are read from global memory.  The default follows
-// 3.20's measurement of the 1D table.
-constexpr size_t kStackLdsBytes = 24 * 1024;
+// (where the vector kernels read the CDL and 1D tables: stack_in_lds, lutr_launch.h; the default follows 3.20's measurement of
+// the 1D table)
 constexpr bool kStackLdsDefault = true;
-static bool stack_in_lds(const StackConsts &S)
-{
-    const size_t bytes = (size_t)(S.lds_cdl_words + S.lds_l1d_words) * sizeof(uint32_t);
-    if (bytes == 0 || bytes > kStackLdsBytes) return false;
-    if (const char *e = getenv("LUTR_STACK_LDS")) {
-        if (e[0] == '0' && !e[1]) return false;
-        if (e[0] == '1' && !e[1]) return true;
-    }
-    return kStackLdsDefault;
-}
 
 const char *launch_yuv_stack(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
                              const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int din, int dout, int icsx, int icsy,
                              int ocsx, int ocsy, const MixConsts *M, const MatteConsts *A, const MtxConsts *X)
 {
     const UnionLaunch U(G, din, dout, icsx, icsy, ocsx, ocsy);
-    const bool lds = stack_in_lds(S);
+    const bool lds = stack_in_lds(S, kStackLdsDefault);
     // the lattice steps' modes: the vector kernels have nearest / trilinear / tetrahedral
     bool modes_ok = true, tri = false;
     for (unsigned long long ops = S.ops; ops & 0xffull; ops >>= 8) {

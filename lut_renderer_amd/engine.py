@@ -25,7 +25,7 @@ from .rgbmatrix import RgbMatrix
 # (the formats and the checks of names and options live in formats.py; the names callers have always imported from here stay)
 from .formats import (_ALPHA_RESIZE, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, V210Fmt, chain_interp, chain_side,  # noqa: F401
                       changes_subsampling, check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc,
-                      check_lut1d_options, check_matte, check_stack_options, check_strength, check_yuv2rgb_options,
+                      check_lut1d_options, check_matte, check_rgb_stack_options, check_stack_options, check_strength, check_yuv2rgb_options,
                       check_container_options,
                       check_dual_options, check_lut2, check_packed_options, check_premul_options, check_semi_options,
                       chroma_loc_code, dual_side, has_prologue, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt,
@@ -132,6 +132,9 @@ _LUT1D_IN_PLACE = "the lut1d pass cannot run in place: destination planes must n
 _RESIZE_IN_PLACE = "a resize cannot run in place: destination planes must not overlap the source planes"
 _RGB2YUV_IN_PLACE = "RGB -> YUV cannot run in place: destination planes must not overlap the source"
 _YUV2RGB_IN_PLACE = "YUV -> RGB cannot run in place: the destination must not overlap the source planes"
+_RGBSTACK_YUV_IN_PLACE = "the RGB stack pass cannot run in place into YUV: destination planes must not overlap the source"
+_RGBSTACK_IN_PLACE = ("the RGB stack pass runs in place only on a planar source's own planes: any other destination must not "
+                      "overlap the source")
 
 
 def _check_not_in_place(src: Sequence[torch.Tensor], dst: Sequence[torch.Tensor], message: str) -> None:
@@ -486,6 +489,7 @@ class LutEngine:
     # -- control ----------------------------------------------------------
     def set_variant(self, name: str) -> None:
         _native.check(self._lib.lutr_ctx_set_variant(self._ctx, _native.VARIANT[name]))
+        self._variant_name = name
 
     def set_precision(self, name: str) -> None:
         """"strict" (default): bit-exact with FFmpeg's scalar C.  "fast": allow the tolerance-bounded tile kernels
@@ -1286,6 +1290,82 @@ class LutEngine:
             _native.check(self._lib.lutr_apply_rgb_to_yuv(
                 self._ctx, C.byref(p), mode, _native.DITHER[dither], fin.code, w, h, nf,
                 C.byref(planar) if planar is not None else None, C.byref(packed) if packed is not None else None, C.byref(d),
+                row0, rows))
+        return dst
+
+    # -- the stage stack on an RGB source -----------------------
+    def apply_rgb_stack(self, src, dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str,
+                        out_pix_fmt: Optional[str] = None, stages, cdl: Optional[Cdl] = None,
+                        rgb_matrix: Optional[RgbMatrix] = None, matrix_out: str = "smpte170m", range_out: str = "tv",
+                        row0: int = 0, rows: Optional[int] = None, **other):
+        """The ordered stack of `apply_yuv_stack` -- 1..4 stages out of "lut3d", "lut3d2", "lut1d", "cdl", "matrix", each at most
+        once, in any order, every lut3d stage with its own mode -- on an RGB source, in one pass (lutr_apply_rgb_stack; DESIGN.md
+        3.26).  `src` is `apply_rgb_to_yuv`'s: three gbrp-ordered planes (G, B, R; `pix_fmt` = gbrp, gbrp9le .. gbrp16le; gbrap*
+        with its alpha plane) or one [F,]H,W,C packed tensor (a name of `_native.PACKED_FORMATS`).  Its codes enter the list as
+        they are (a 16-bit word above 2^depth - 1 acts as that); the list runs at the source's depth.  `out_pix_fmt` is planar
+        YUV (4:2:0 / 4:2:2 / 4:4:4 at 8..16 bit, through `apply_rgb_to_yuv`'s output stage with `matrix_out` / `range_out`; not in
+        place), or gbrp* / gbrap* at the source's depth -- the default for a planar source -- where the final codes are stored as
+        they are and `dst` may be `src`.  Alpha (gbrap*, a packed name's real A) goes past the list as in `apply_rgb_to_yuv`.
+        ("lut3d",) gives the bits of `apply_rgb_to_yuv` / `apply_rgb`, ("lut1d",) into gbrp* those of `apply_rgb_lut1d`.  A float
+        source, a packed destination, a gbrp destination of another depth, dither, out_size, chroma_loc, strength, matte,
+        premultiplied alpha, a second output and the full-range composition are ValueErrors naming them
+        (`formats.check_rgb_stack_options`)."""
+        for k in other:
+            if k not in ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength", "matte",
+                         "intermediate_pix_fmt"):
+                raise TypeError(f"apply_rgb_stack() got an unexpected keyword argument '{k}'")
+        if cdl is not None and not isinstance(cdl, Cdl):
+            raise TypeError(f"cdl must be a lut_renderer_amd.cdl.Cdl, not {type(cdl).__name__}")
+        if rgb_matrix is not None and not isinstance(rgb_matrix, RgbMatrix):
+            raise TypeError(f"rgb_matrix must be a lut_renderer_amd.rgbmatrix.RgbMatrix, not {type(rgb_matrix).__name__}")
+        st, fin, fout = check_rgb_stack_options(
+            pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(self, "n", 0)),
+            lut2=bool(getattr(self, "n2", 0)), lut1d=bool(getattr(self, "n1d", 0)), prelut=bool(getattr(self, "_has_prelut", False)),
+            rgb_matrix=rgb_matrix is not None, dither=other.get("dither", "none"), chroma_loc=other.get("chroma_loc"),
+            out_size=other.get("out_size"), alpha_mode=other.get("alpha_mode", "straight"),
+            out2_pix_fmt=other.get("out2_pix_fmt"), variant=getattr(self, "_variant_name", None), strength=other.get("strength"),
+            matte=other.get("matte"), intermediate_pix_fmt=other.get("intermediate_pix_fmt"))
+        to_rgb = fout.family == "gbr"
+        planar, packed, w, h, nf, lead = self._rgb_source(src, fin)
+        if dst is None:
+            dtype = (torch.uint8 if fout.depth <= 8 else torch.int16) if fin.packed or not to_rgb else src[0].dtype
+            dst = _new_planes(fout, w, h, lead, dtype if to_rgb else _yuv_out_dtype(fout.depth, None), self.device)
+        _check_planes(dst, fout, w, h, "destination")
+        if fout.alpha:
+            # the colour planes through this very call under the three-plane name, then alpha from gbrap*'s fourth plane or a
+            # packed name's real A on the same stream -- any other source fills it (DESIGN.md 3.16)
+            a_src, slot = None, None
+            if fin.packed and fin.alpha_slot is not None:
+                a_src, slot = src, fin.alpha_slot
+            elif not fin.packed and fin.nplanes == 4:
+                a_src = src[3]
+            _check_alpha_overlap(a_src, fin.depth, dst, fout.depth)
+            self._alpha_tail(lambda: self.apply_rgb_stack(
+                src, dst[:3], pix_fmt=pix_fmt, out_pix_fmt=fout.colour.name, stages=st, cdl=cdl, rgb_matrix=rgb_matrix,
+                matrix_out=matrix_out, range_out=range_out, row0=row0, rows=rows),
+                [(fout, dst)], a_src, fin.depth, w, h, row0, rows, slot)
+            return dst
+        d, nfd = _planes_struct(dst, self.device)
+        if nf != nfd:
+            raise ValueError("src and dst disagree on the number of frames")
+        rows = h - row0 if rows is None else rows
+        colour_src = [src] if fin.packed else list(src[:3])
+        in_place = (to_rgb and not fin.packed and all(
+            a.data_ptr() == b.data_ptr() and a.stride() == b.stride() and a.shape == b.shape for a, b in zip(colour_src, dst)))
+        if not in_place:
+            _check_not_in_place(colour_src, dst, _RGBSTACK_IN_PLACE if to_rgb else _RGBSTACK_YUV_IN_PLACE)
+        p = None
+        if not to_rgb:
+            p = C.byref(_yuv_params(_native.fmt_code(fin.depth, 0, 0), fout.code, fin.depth, matrix_out, matrix_out, range_out,
+                                    range_out, range_out))
+        arr = _native.stage_array(st)
+        k = None if cdl is None else C.byref(_native.cdl_struct(cdl))
+        m = None if rgb_matrix is None else C.byref(_native.rgb_matrix_struct(rgb_matrix))
+        with self._lock:
+            self._bind_stream()
+            _native.check(self._lib.lutr_apply_rgb_stack(
+                self._ctx, p, arr, len(st), k, m, fin.code, w, h, nf, C.byref(planar) if planar is not None else None,
+                C.byref(packed) if packed is not None else None, fin.depth if to_rgb else _native.RGB_STACK_YUV, C.byref(d),
                 row0, rows))
         return dst
 

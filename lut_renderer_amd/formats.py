@@ -710,6 +710,36 @@ def implied_stages(cube: bool, cube2: bool = False, lut1d: bool = False, cdl: bo
     return tuple(st)
 
 
+def check_stage_list(stages, *, cdl: bool = False, lut: bool = True, lut2: bool = True, lut1d: bool = True, prelut: bool = False,
+                     rgb_matrix: bool = False):
+    """What every stack refuses about the list and its resources, whatever its sides: a list
+    `parse_stages` takes; every listed stage's resource there and no CDL or matrix without its stage; no lut3d directly behind cdl
+    or matrix when the first LUT carries a .csp prelut.  Returns the parsed stages."""
+    st = parse_stages(stages)
+    kinds = [k for k, _m in st]
+    if "lut3d" in kinds and not lut:
+        raise ValueError("stage 'lut3d' is listed and no 3D LUT is loaded: call set_lut / load_cube first, or pass cube")
+    if "lut3d2" in kinds and not lut2:
+        raise ValueError("stage 'lut3d2' is listed and no second LUT is loaded: call set_lut2 / load_cube2 first, or pass cube2")
+    if "lut1d" in kinds and not lut1d:
+        raise ValueError("stage 'lut1d' is listed and no 1D LUT is loaded: call set_lut1d / load_lut1d first, or pass lut1d")
+    if "cdl" in kinds and not cdl:
+        raise ValueError("stage 'cdl' is listed and no CDL is given: pass cdl")
+    if cdl and "cdl" not in kinds:
+        raise ValueError("a CDL is given and the stage list has no 'cdl' stage")
+    if prelut and "cdl" in kinds and kinds.index("cdl") + 1 < len(kinds) and kinds[kinds.index("cdl") + 1] == "lut3d":
+        raise ValueError("stage 'lut3d' directly behind 'cdl' is not supported with a LUT that carries a .csp prelut: the prelut's "
+                         "table is indexed by integer codes, and the CDL's output is not a code")
+    if "matrix" in kinds and not rgb_matrix:
+        raise ValueError("stage 'matrix' is listed and no RGB matrix is given: pass rgb_matrix")
+    if rgb_matrix and "matrix" not in kinds:
+        raise ValueError("an RGB matrix is given and the stage list has no 'matrix' stage")
+    if prelut and "matrix" in kinds and kinds.index("matrix") + 1 < len(kinds) and kinds[kinds.index("matrix") + 1] == "lut3d":
+        raise ValueError("stage 'lut3d' directly behind 'matrix' is not supported with a LUT that carries a .csp prelut: the prelut's "
+                         "table is indexed by integer codes, and the matrix's output is not a code")
+    return st
+
+
 def check_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = None, *, stages, cdl: bool = False,
                         lut: bool = True, lut2: bool = True, lut1d: bool = True, prelut: bool = False, dither: str = "none",
                         chroma_loc: Optional[str] = None, out_size=None, alpha_mode: str = "straight",
@@ -733,28 +763,8 @@ def check_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = Non
     if matte:
         tail = "a stage stack with strength and a matte" if mixed else "a stage stack with a matte"
         noun = "stack (strength, matte)" if mixed else "stack (matte)"
-    st = parse_stages(stages)
+    st = check_stage_list(stages, cdl=cdl, lut=lut, lut2=lut2, lut1d=lut1d, prelut=prelut, rgb_matrix=rgb_matrix)
     kinds = [k for k, _m in st]
-    if "lut3d" in kinds and not lut:
-        raise ValueError("stage 'lut3d' is listed and no 3D LUT is loaded: call set_lut / load_cube first, or pass cube")
-    if "lut3d2" in kinds and not lut2:
-        raise ValueError("stage 'lut3d2' is listed and no second LUT is loaded: call set_lut2 / load_cube2 first, or pass cube2")
-    if "lut1d" in kinds and not lut1d:
-        raise ValueError("stage 'lut1d' is listed and no 1D LUT is loaded: call set_lut1d / load_lut1d first, or pass lut1d")
-    if "cdl" in kinds and not cdl:
-        raise ValueError("stage 'cdl' is listed and no CDL is given: pass cdl")
-    if cdl and "cdl" not in kinds:
-        raise ValueError("a CDL is given and the stage list has no 'cdl' stage")
-    if prelut and "cdl" in kinds and kinds.index("cdl") + 1 < len(kinds) and kinds[kinds.index("cdl") + 1] == "lut3d":
-        raise ValueError("stage 'lut3d' directly behind 'cdl' is not supported with a LUT that carries a .csp prelut: the prelut's "
-                         "table is indexed by integer codes, and the CDL's output is not a code")
-    if "matrix" in kinds and not rgb_matrix:
-        raise ValueError("stage 'matrix' is listed and no RGB matrix is given: pass rgb_matrix")
-    if rgb_matrix and "matrix" not in kinds:
-        raise ValueError("an RGB matrix is given and the stage list has no 'matrix' stage")
-    if prelut and "matrix" in kinds and kinds.index("matrix") + 1 < len(kinds) and kinds[kinds.index("matrix") + 1] == "lut3d":
-        raise ValueError("stage 'lut3d' directly behind 'matrix' is not supported with a LUT that carries a .csp prelut: the prelut's "
-                         "table is indexed by integer codes, and the matrix's output is not a code")
     if "matrix" in kinds and (mixed or matte):
         what = "strength and a matte" if mixed and matte else "a matte" if matte else "strength"
         raise ValueError(f"stage 'matrix' is not supported with {what}: the matrix stage has no mix form")
@@ -947,3 +957,78 @@ def check_yuv2rgb_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str], **
         raise ValueError(f"alpha from '{pix_fmt}' into the packed destination '{out_pix_fmt}' is not supported yet (a follow-up): "
                          f"use gbrap* to carry alpha, or a yuv* name / a 3-component destination to drop it")
     return fin, fout
+
+
+# ---------------------------------------------------------------- the stage stack on RGB sources
+def check_rgb_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = None, *, stages, cdl: bool = False,
+                            lut: bool = True, lut2: bool = True, lut1d: bool = True, prelut: bool = False,
+                            rgb_matrix: bool = False, dither: str = "none", chroma_loc: Optional[str] = None, out_size=None,
+                            alpha_mode: str = "straight", out2_pix_fmt: Optional[str] = None, variant: Optional[str] = None,
+                            strength=None, matte=None, intermediate_pix_fmt: Optional[str] = None):
+    """The checks every layer makes of a stage stack on an RGB source before any GPU work, the one copy of its
+    refusals: everything `check_stage_list` refuses; a source that is not integer RGB (`gbrp*`, `gbrap*`, a packed name) -- a float
+    one by name; a destination that is neither planar YUV (4:2:0 / 4:2:2 / 4:4:4, yuva* included) nor `gbrp*` / `gbrap*` at the
+    source's depth -- a packed one, and a gbrp one of another depth, by name; a packed source without `out_pix_fmt`; the
+    full-range two-stage composition (`intermediate_pix_fmt`); dither, out_size, chroma_loc; strength / matte; premultiplied
+    alpha; a second output; the vec_lds variant, and vec_global where the names of the call already say that the vector kernel
+    cannot take it (a pyramid / prism stage, an 8-bit source written as 16-bit words).  `out_pix_fmt` None means `gbrp*` at the
+    source's depth.
+    Returns (parsed stages, source `RgbSource`, destination `PixFmt`)."""
+    tail = "a stage stack on an RGB source (rgb_stages)"
+    st = check_stage_list(stages, cdl=cdl, lut=lut, lut2=lut2, lut1d=lut1d, prelut=prelut, rgb_matrix=rgb_matrix)
+    fin = parse_rgb_source(pix_fmt)
+    if fin is None:
+        raise ValueError(f"{tail} takes gbrp*, gbrap* or packed RGB sources: '{pix_fmt}' is not an RGB format (planar YUV goes "
+                         f"through stages / apply_yuv_stack)")
+    if fin.floating:
+        raise ValueError(f"a float source ('{pix_fmt}') is not supported with {tail}: the list runs on integer codes at the "
+                         f"source's depth")
+    if out_pix_fmt is None:
+        if fin.packed:
+            raise ValueError(f"a packed source ('{pix_fmt}') with {tail} needs out_pix_fmt: a planar YUV name, or gbrp* at the "
+                             f"source's depth ({fin.depth} bit)")
+        fout = PixFmt(fin.name, "gbr", fin.depth, 0, 0, True, fin.nplanes == 4)
+    else:
+        out = parse_rgb_source(out_pix_fmt)
+        if out is not None and out.packed:
+            raise ValueError(f"a packed RGB destination ('{out_pix_fmt}') is not supported with {tail}: the destination is planar "
+                             f"YUV or gbrp* at the source's depth")
+        if out is not None and out.floating:
+            raise ValueError(f"a float destination ('{out_pix_fmt}') is not supported with {tail}")
+        try:
+            fout = parse_pix_fmt(out_pix_fmt.replace("yuvj", "yuv"))
+        except ValueError:
+            raise ValueError(f"'{out_pix_fmt}' is not a destination of {tail}: planar YUV (yuv420p .. yuv444p16le, yuva*) or "
+                             f"gbrp* / gbrap* at the source's depth") from None
+        if fout.family == "gbr" and fout.depth != fin.depth:
+            raise ValueError(f"a gbrp destination of another depth ('{out_pix_fmt}', {fout.depth} bit, from '{pix_fmt}', "
+                             f"{fin.depth} bit) is not supported with {tail}: the final codes are stored at the source's depth")
+    if intermediate_pix_fmt is not None:
+        raise ValueError(f"the full-range two-stage composition (intermediate_pix_fmt) is not supported with {tail}")
+    if dither != "none":
+        raise ValueError(f"dither ('{dither}') is not supported with {tail}")
+    if out_size is not None:
+        raise ValueError(f"a resize (out_size / resolution) is not supported with {tail}")
+    if chroma_loc is not None:
+        raise ValueError(f"sited chroma resampling (chroma_loc) is not supported with {tail}")
+    if strength is not None:
+        raise ValueError(f"a LUT strength (strength) is not supported with {tail}")
+    if matte is not None and matte is not False:
+        raise ValueError(f"a matte (matte) is not supported with {tail}")
+    if alpha_mode != "straight":
+        raise ValueError(f"alpha_mode='{alpha_mode}' is not supported with {tail}")
+    if out2_pix_fmt is not None:
+        raise ValueError(f"the two-output pass (out2_pix_fmt) is not supported with {tail}")
+    if variant == "vec_lds":
+        raise ValueError(f"variant vec_lds is not supported with {tail}: there is no LDS-window kernel for the RGB stack pass")
+    if variant == "vec_global":
+        # what the names of the call say already; sizes, strides and alignment the vector kernel cannot take are the C layer's
+        # (LUTR_EINVAL: it sees the planes)
+        slow = [f"{k}:{m}" for k, m in st if m in ("pyramid", "prism")]
+        if slow:
+            raise ValueError(f"variant vec_global cannot take stage '{slow[0]}' of {tail}: the vector kernel has nearest, trilinear "
+                             f"and tetrahedral")
+        if fin.depth <= 8 and fout.depth > 8:
+            raise ValueError(f"variant vec_global cannot take an 8-bit source ('{pix_fmt}') written as 16-bit words "
+                             f"('{fout.name}') with {tail}: that container mix has no vector kernel")
+    return st, fin, fout

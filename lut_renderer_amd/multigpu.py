@@ -29,7 +29,7 @@ import torch
 from . import _native
 from .cube import CubeLut, read_lut, read_lut1d
 from .engine import LutEngine, _fresh_planes, _new_planes, _yuv_out_dtype, chain_args, dual_args
-from .formats import (RgbSource, check_yuv2rgb_options, check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2, check_matte, check_stack_options, check_strength,
+from .formats import (RgbSource, check_yuv2rgb_options, check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2, check_matte, check_rgb_stack_options, check_stack_options, check_strength,
                       check_premul_options,
                       packed_frame_width, parse_pix_fmt, parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords,
                       v210_frame_width, yuv_side)
@@ -460,6 +460,45 @@ class LutEngineGroup:
                 return [(dst, *_crop(full, fout, s0, r0, r1))]
 
             self._shard(h, 1 << csy, home, local, remote)
+            return dst
+
+    def apply_rgb_stack(self, src, dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: Optional[str] = None,
+                        stages, cdl=None, rgb_matrix=None, **kw):
+        """`LutEngine.apply_rgb_stack` with the rows of every frame split over the group's devices: the lattices
+        and the 1D LUT are on every engine through the group's setters, the CDL and the matrix travel with the call; shards on
+        multiples of the output chroma block height (any row for a gbrp destination), every source plane (or the packed image)
+        and alpha counted in luma rows, no halo."""
+        with self._lock:
+            if "row0" in kw or "rows" in kw:
+                raise ValueError("the group owns the row partition")
+            e0 = self.engines[0]
+            refusable = ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength", "matte", "intermediate_pix_fmt")
+            st, fin, fout = check_rgb_stack_options(
+                pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(e0, "n", 0)),
+                lut2=bool(getattr(e0, "n2", 0)), lut1d=bool(self.n1d), prelut=bool(getattr(e0, "_has_prelut", False)),
+                rgb_matrix=rgb_matrix is not None, variant=getattr(e0, "_variant_name", None),
+                **{k: kw[k] for k in refusable if k in kw})
+            first = src if fin.packed else src[0]
+            h, w = (first.shape[-3], first.shape[-2]) if fin.packed else (first.shape[-2], first.shape[-1])
+            lead = tuple(first.shape[:-3]) if fin.packed else tuple(first.shape[:-2])
+            home = first.device
+            if dst is None:
+                dtype = first.dtype if fout.family == "gbr" and not fin.packed else _yuv_out_dtype(fout.depth, None)
+                dst = _new_planes(fout, w, h, lead, dtype, home)
+            names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, stages=st, cdl=cdl, rgb_matrix=rgb_matrix)
+
+            def local(eng, r0, r1):
+                eng.apply_rgb_stack(src, dst, row0=r0, rows=r1 - r0, **names, **kw)
+
+            def remote(eng, r0, r1):
+                if fin.packed:
+                    part = src[..., r0:r1, :, :].to(eng.device, non_blocking=True, copy=True).contiguous()
+                else:
+                    part = _travel(src, [(r0, r1)] * len(src), eng.device)
+                out = eng.apply_rgb_stack(part, None, **names, **kw)
+                return [(dst, out, _row_ranges(fout, r0, r1))]
+
+            self._shard(h, 1 << fout.csy, home, local, remote)
             return dst
 
     def apply_yuv_to_rgb(self, src: Sequence[torch.Tensor], dst=None, *, pix_fmt: str, out_pix_fmt: str, **kw):

@@ -24,7 +24,7 @@ from .engine import LutEngine
 from .params import strength_keys
 from .formats import (MATTE_PIX_FMTS, RgbSource, check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options,
                       check_lut1d_options, check_stack_options,
-                      check_premul_options, check_yuv2rgb_options, parse_rgb_out, parse_rgb_source, parse_size, premul_to_yuv,
+                      check_premul_options, check_rgb_stack_options, check_yuv2rgb_options, parse_rgb_out, parse_rgb_source, parse_size, premul_to_yuv,
                       refuse_alpha_resize, yuv_side, _YUV2RGB_NOT_TAKEN)
 
 
@@ -211,6 +211,37 @@ class HostPipeline:
         # per frame is read and uploaded with every input batch; `apply_kw["matte_invert"]` travels to the engine
         # `rgb_out`: a planar YUV source written as RGB -- gbrp* / gbrap* planes or a packed image -- through
         # `apply_yuv_to_rgb`; the output ring has that layout (`output_layout`).  Not with `out_pix_fmt` or anything the pass refuses
+        # `apply_kw["rgb_stages"]`: an RGB source through the stage stack -- every batch goes through
+        # `apply_rgb_stack` with the lattices and the 1D LUT the engine holds, `apply_kw["cdl"]` and `apply_kw["rgb_matrix"]`, into
+        # planar YUV or gbrp* / gbrap* at the source's depth (`out_pix_fmt` None: the latter, for a planar source)
+        self.rgb_stack = apply_kw.get("rgb_stages") is not None
+        if self.rgb_stack:
+            if apply_kw.get("stages") is not None:
+                raise ValueError("stages and rgb_stages are mutually exclusive")
+            if rgb_out is not None:
+                raise ValueError(f"rgb_out ('{rgb_out}') names the RGB output of a YUV source: with rgb_stages the output is out_pix_fmt")
+            if chain or lut1d:
+                raise ValueError("a stage stack names its lut3d2 / lut1d stages itself: chain / lut1d are not set with rgb_stages")
+            refusable = ("dither", "chroma_loc", "alpha_mode", "strength", "matte", "intermediate_pix_fmt")
+            st, _fin, fout = check_rgb_stack_options(
+                pix_fmt, out_pix_fmt, stages=apply_kw["rgb_stages"], cdl=apply_kw.get("cdl") is not None,
+                lut=bool(getattr(engine, "n", 0)), lut2=bool(getattr(engine, "n2", 0)), lut1d=bool(getattr(engine, "n1d", 0)),
+                prelut=bool(getattr(engine, "_has_prelut", False)), rgb_matrix=apply_kw.get("rgb_matrix") is not None,
+                out_size=out_size, out2_pix_fmt=second_pix_fmt, **{k: apply_kw[k] for k in refusable if k in apply_kw})
+            if apply_kw.get("strength_keys") is not None:
+                raise ValueError("a LUT strength (strength_keys) is not supported with a stage stack on an RGB source (rgb_stages)")
+            self.rgb_out = self.stack = self.chain = self.lut1d = self.float_out = False
+            self.rgb = True
+            self.matte = self.strength_keys = self.fout2 = None
+            self.frames_submitted = 0
+            self.eng = engine
+            self.fin = input_layout(pix_fmt, width, height)
+            self.fout = yuv_layout(fout.name, width, height)
+            self.batch, self.slots = int(batch), int(slots)
+            self.kw = dict({k: apply_kw[k] for k in ("cdl", "rgb_matrix", "matrix_out", "range_out") if apply_kw.get(k) is not None},
+                           stages=st, pix_fmt=pix_fmt, out_pix_fmt=fout.name)
+            self._allocate(engine, slots)
+            return
         self.rgb_out = rgb_out is not None
         if self.rgb_out:
             if out_pix_fmt:
@@ -313,6 +344,10 @@ class HostPipeline:
             self.kw["out_size"] = (ow, oh)
         if self.fin.fmt.nplanes == 1 or self.fout.fmt.nplanes == 1:
             self.kw["width"] = width                           # (a packed row cannot tell an odd width)
+        self._allocate(engine, slots)
+
+    def _allocate(self, engine: LutEngine, slots: int) -> None:
+        """The pinned host rings, the device rings and the streams of the layouts `__init__` settled."""
         dev = engine.device
         self.h_in = [torch.empty(self.batch * self.fin.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]
         self.h_out = [torch.empty(self.batch * self.fout.frame_bytes, dtype=torch.uint8).pin_memory() for _ in range(slots)]
@@ -386,7 +421,11 @@ class HostPipeline:
             self.s_run.wait_event(self.e_in[slot])
             dst = self.fout.image_view(self.d_out[slot], nframes) if isinstance(self.fout, PackedFrameLayout) \
                 else self.fout.plane_views(self.d_out[slot], nframes)
-            if self.rgb_out:
+            if self.rgb_stack:
+                src = self.fin.image_view(self.d_in[slot], nframes) if isinstance(self.fin, PackedFrameLayout) \
+                    else self.fin.plane_views(self.d_in[slot], nframes)
+                self.eng.apply_rgb_stack(src, dst, **self.kw)
+            elif self.rgb_out:
                 self.eng.apply_yuv_to_rgb(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
             elif self.stack:
                 self._run_stack(self.fin.plane_views(self.d_in[slot], nframes), dst, nframes, matte)
