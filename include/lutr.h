@@ -940,6 +940,36 @@ int lutr_apply_rgb_stack(lutr_ctx *ctx, const lutr_yuv_params *p, const lutr_sta
                          const lutr_rgb_matrix *mtx, int src_kind, int w, int h, int nframes, const lutr_planes *src_planar,
                          const lutr_packed *src_packed, int dst_kind, const lutr_planes *dst, int row0, int rows);
 
+/* ---- the stage stack from YUV sources into RGB frames: a camera file (ProRes / HEVC) graded with the per-shot
+ *      CDL and the show LUT into a DPX / TIFF / PNG sequence, or with lut1d,matrix,lut3d into rgba / bgra for a viewer ----
+ * The source and the destination are lutr_apply_yuv_to_rgb's, and so are dst_kind and the fields of *p that are read (fmt_in,
+ * lut_depth, matrix_in, range_src, range_in): planar YUV p->fmt_in (4:2:0 / 4:2:2 / 4:4:4 at any depth din in 8..16; 4:4:0 is
+ * LUTR_EINVAL) -> [the prologue only if range_src != range_in, on lutr_apply_yuv_to_rgb's terms] -> each chroma sample replicated
+ * over its INPUT block -> integer RGB codes at dl = p->lut_depth, the destination's depth (constants lutr_yuv_constants_yuv2rgb,
+ * unchanged) -> the list of lutr_apply_rgb_stack / lutr_apply_yuv_stack_matrix, unchanged: 1..4 stages out of LUT3D, LUT3D_2,
+ * LUT1D, CDL, MATRIX, each at most once, in any order, every lattice stage with its own mode (all five), the first lattice's .csp
+ * prelut taken where it is fed codes, the same compiled steps, the same unit -> codes rounding and per-stage arithmetic in strict
+ * fp32 without contraction -> the final codes stored as they are: gbrp planes at dl in dst_planar (dst_kind == 0; G, B, R), or one
+ * packed image in dst_packed (dst_kind == LUTR_PK_* / LUTR_PACKED(...), whose bits dl must be; a fourth component is written
+ * 2^dl - 1, opaque; 16-bit formats need 2-byte aligned rows).
+ * row0 and rows must be multiples of the input chroma block height 2^icsy unless row0 + rows == h.  Not in place: the byte-range
+ * rule of lutr_apply_yuv_to_rgb.
+ * Bit for bit: {LUT3D} is lutr_apply_yuv_to_rgb with that mode; {CDL} with the identity CDL and {MATRIX} with the identity matrix
+ * are lutr_apply_yuv_to_rgb with LUTR_INTERP_NONE; any list is lutr_apply_rgb_stack from gbrp into gbrp on the planes
+ * lutr_apply_yuv_to_rgb with LUTR_INTERP_NONE writes at dl (the conversion clips to [0, 2^dl - 1]), arranged as the destination.
+ * LUTR_EINVAL with a message, before anything touches the device: everything lutr_apply_yuv_stack_matrix refuses about the list
+ * and its resources; the format errors of lutr_apply_yuv_to_rgb; variant vec_lds; an overlap as above.
+ * Kernels: "k_yuv2rgb_stack_vec<win,icsx,icsy,nc,wout,tri,lds>[stages]" (nc = 1 planar, 3 | 4 packed; nearest / trilinear /
+ * tetrahedral stages; the layout rules of "k_yuv2rgb_vec"; the tables in LDS when they fit 24 KB, LUTR_STACK_LDS=0 | 1 as for
+ * lutr_apply_yuv_stack), "k_yuv2rgb_stack_generic[stages]" for everything else, "<vector kernel>+k_yuv2rgb_stack_generic[stages]"
+ * for a ragged width on aligned rows; [stages] as lutr_apply_yuv_stack writes it.  vec_global fails with LUTR_EINVAL where the
+ * vector kernel cannot take the call.
+ * Not covered: a strength or a matte, dither, a resize, chroma siting, a float destination, semi-planar / packed 4:2:2 / v210
+ * sources, alpha carried into a packed destination, a tile (LDS window) kernel. */
+int lutr_apply_yuv_stack_to_rgb(lutr_ctx *ctx, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                                const lutr_rgb_matrix *mtx, int dst_kind, int w, int h, int nframes, const lutr_planes *src,
+                                const lutr_planes *dst_planar, const lutr_packed *dst_packed, int row0, int rows);
+
 /* ---- the alpha plane of yuva* / gbrap* frames: ProRes 4444 (yuva444p10le / 12le), VP8 / VP9 with alpha
  *      (yuva420p), PNG / TIFF / EXR sequences with alpha (rgba, rgba64le, gbrap*, gbrapf32le).  In the reference's chain lut3d
  *      copies the alpha plane through and format=<pix_fmt> keeps, converts, drops or makes it (ffmpeg.py:246, :304-310) ---- */

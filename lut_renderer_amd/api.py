@@ -26,7 +26,7 @@ from .rgbmatrix import as_rgb_matrix
 from .cube import CubeLut, as_lut1d, read_cube, read_lut, read_lut1d
 from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc, check_container_options,
                       check_dual_options, check_lut1d_options, check_lut2, check_premul_options, check_stack_options,
-                      check_rgb_stack_options, check_yuv2rgb_options, implied_stages, packed_frame_width, parse_packed_yuv_fmt,
+                      check_rgb_stack_options, check_yuv2rgb_options, check_yuv2rgb_stack_options, implied_stages, packed_frame_width, parse_packed_yuv_fmt,
                       parse_pix_fmt, parse_rgb_source, parse_semi_fmt, parse_size, parse_stages, parse_v210_fmt, premul_to_yuv,
                       refuse_alpha_resize, source_bit_depth, v210_frame_width, yuv_side)
 from .params import ProcessingParams, VideoInfo
@@ -344,6 +344,32 @@ def _apply_rgb_stack(planes, out, plan, pix_fmt, out_pix_fmt, rgb_stages, interp
     return result
 
 
+def _apply_yuv_stack_to_rgb(planes, out, plan, pix_fmt, rgb_out, rgb_out_stages, interp, cube, cube2, interp2, lut1d, interp1d, cdl,
+                            cdl_id, rgb_matrix, engine, devices, precision, refusable):
+    """`apply_lut(rgb_out=, rgb_out_stages=...)`: load what the list names, with the caches the other routes use,
+    and route to `apply_yuv_stack_to_rgb` with the matrix and ranges `engine_call_for(rgb_out=)` gives the plan.  `refusable`: the
+    options of the call the pass does not take, by `check_yuv2rgb_stack_options`' keyword."""
+    from .plan import INTERP_WHITELIST
+    mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
+    st = parse_stages(rgb_out_stages, interp=interp, interp2=mode2)
+    lut, lut2, lut1d, cdl, rgb_matrix, held, prelut = _stack_resources(st, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id,
+                                                                      rgb_matrix, engine)
+    if precision not in ("strict", "fast", "fma32"):
+        raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
+    check_yuv2rgb_stack_options(pix_fmt, rgb_out, stages=st, cdl=cdl is not None, lut=lut is not None or held("n"),
+                                lut2=lut2 is not None or held("n2"), lut1d=lut1d is not None or held("n1d"), prelut=prelut,
+                                rgb_matrix=rgb_matrix is not None, **refusable)
+    call = {k: v for k, v in engine_call_for(plan, pix_fmt, None, "straight", rgb_out=rgb_out).items() if k != "interp"}
+    own = engine is None
+    eng = engine if engine is not None else _cached_engine(devices)
+    with eng._lock:                 # uploads, precision and launch of ONE task, as in apply_lut
+        _stack_upload(eng, lut, lut2, lut1d, interp1d, precision)
+        result = eng.apply_yuv_stack_to_rgb(planes, out, stages=st, cdl=cdl, rgb_matrix=rgb_matrix, **call)
+        if own:
+            eng.sync()
+    return result
+
+
 def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: str, width: Optional[int] = None,
               height: Optional[int] = None, input_matrix: str = "auto", colorspace: Optional[str] = None,
               color_range: Optional[str] = None, output_tags: str = "bt709", out_pix_fmt: Optional[str] = None,
@@ -352,7 +378,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
               cube2=None, interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None, cdl_id: Optional[str] = None,
               lut1d=None, interp1d: str = "linear", stages=None, strength=None, matte=None, matte_depth: Optional[int] = None,
-              matte_invert: bool = False, rgb_out: Optional[str] = None, rgb_matrix=None, rgb_stages=None):
+              matte_invert: bool = False, rgb_out: Optional[str] = None, rgb_matrix=None, rgb_stages=None, rgb_out_stages=None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -475,7 +501,14 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     (LutEngine.apply_rgb_stack) into a planar YUV `out_pix_fmt`, or into gbrp* / gbrap* at the source's depth -- the default for
     a planar source.  It is valid only with an RGB `pix_fmt`; `stages` together with it, a float source, a packed RGB output, a
     gbrp output of another depth, a source flagged full range, dither, resolution, chroma_loc, strength, matte, premultiplied
-    alpha and a second output are ValueErrors naming them."""
+    alpha and a second output are ValueErrors naming them.
+
+    `rgb_out_stages` is `stages` for a planar YUV `pix_fmt` with `rgb_out`: the same lists, the same resources
+    (`cube`, `cube2`, `lut1d`, `cdl`, `rgb_matrix`), run at the depth of `rgb_out` in ONE pass (LutEngine.apply_yuv_stack_to_rgb)
+    between the conversion to integer RGB and the stores, e.g. rgb_out="rgb48le", rgb_out_stages="lut1d,cdl,lut3d".  It needs
+    `rgb_out`; `stages` or `rgb_stages` together with it, dither, resolution, chroma_loc, strength, matte, premultiplied alpha
+    and a second output are ValueErrors naming them, and the format rules are those of `rgb_out`.  None (default) leaves every
+    route as it is."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -490,7 +523,13 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     if rgb_stages is not None and stages is not None:
         raise ValueError("stages and rgb_stages are mutually exclusive: stages is the list of a YUV source, rgb_stages that of an "
                          "RGB source")
-    if rgb_matrix is not None and stages is None and rgb_stages is None:
+    if rgb_out_stages is not None:
+        if rgb_out is None:
+            raise ValueError("rgb_out_stages is the stage list of a YUV source written as RGB: it needs rgb_out")
+        if stages is not None or rgb_stages is not None:
+            raise ValueError("rgb_out_stages and stages / rgb_stages are mutually exclusive: stages is the list of a YUV source with "
+                             "a YUV output, rgb_stages that of an RGB source, rgb_out_stages that of a YUV source with rgb_out")
+    if rgb_matrix is not None and stages is None and rgb_stages is None and rgb_out_stages is None:
         raise ValueError("rgb_matrix needs stages: a matrix stage has no implied position (e.g. stages='lut1d,matrix,lut3d')")
     rgb_src = parse_rgb_source(pix_fmt)
     if rgb_stages is not None and rgb_src is None:
@@ -531,6 +570,17 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         return result, output_color_tags(plan.output_policy)
     if rgb_out is not None:
         # YUV in, RGB out: a route of its own, with none of the options below
+        if rgb_out_stages is not None:
+            # ... with the stage stack between the conversion and the stores
+            if out_pix_fmt:
+                raise ValueError(f"rgb_out ('{rgb_out}') and out_pix_fmt ('{out_pix_fmt}') are mutually exclusive: a call has one "
+                                 f"output")
+            dither = "error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none"
+            refusable = dict(dither=dither, engine_dither=engine_dither, chroma_loc=chroma_loc, out_size=out_size,
+                             alpha_mode=alpha_mode, out2_pix_fmt=second_pix_fmt, strength=strength, matte=matte)
+            result = _apply_yuv_stack_to_rgb(planes, out, plan, pix_fmt, rgb_out, rgb_out_stages, interp, cube, cube2, interp2, lut1d,
+                                             interp1d, cdl, cdl_id, rgb_matrix, engine, devices, precision, refusable)
+            return result, output_color_tags(plan.output_policy)
         kw = engine_call_for(plan, pix_fmt, out_pix_fmt, alpha_mode, rgb_out=rgb_out)
         check_yuv2rgb_options(pix_fmt, rgb_out, chroma_loc=chroma_loc, engine_dither=engine_dither, out_size=out_size,
                               dither="error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none",

@@ -20,7 +20,7 @@ import signal
 import sys
 import time
 
-from .formats import (check_cdl_options, check_chroma_loc, check_container_options, check_lut1d_options, check_lut2, check_rgb_stack_options, check_stack_options, implied_stages, parse_stages,
+from .formats import (check_cdl_options, check_chroma_loc, check_container_options, check_lut1d_options, check_lut2, check_rgb_stack_options, check_stack_options, check_yuv2rgb_stack_options, implied_stages, parse_stages,
                       check_premul_options, parse_size, refuse_alpha_resize, source_bit_depth)
 
 
@@ -119,6 +119,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "lists and files, run on the source's own codes in ONE pass into a planar YUV --out-pix-fmt, or into gbrp* "
                          "at the source's depth (the default for a planar source); no dither, --chroma-loc, --out-size, --strength, "
                          "--matte, --second-output or --alpha-mode premultiplied; not together with --stages")
+    ap.add_argument("--rgb-out-stages", default=None, metavar="LIST",
+                    help="engine setting: --stages for a planar YUV --pix-fmt with --rgb-out (DESIGN.md 3.27): the same lists and "
+                         "files, run at the depth of --rgb-out in ONE pass between the conversion to RGB and the stores, e.g. "
+                         "--rgb-out rgb48le --rgb-out-stages lut1d,cdl,lut3d; needs --rgb-out; no dither, --chroma-loc, --out-size, "
+                         "--strength, --matte, --second-output or --alpha-mode premultiplied; not together with --stages or "
+                         "--rgb-stages")
     ap.add_argument("--rgb-matrix", default=None, metavar="\"M00 M01 M02 M10 .. M22\"",
                     help="engine setting: the nine numbers, row-major, of the RGB matrix a 'matrix' stage of --stages applies "
                          "(DESIGN.md 3.25; a gamut conversion, a white-balance or channel-mixer trim, a channel swap): "
@@ -247,31 +253,25 @@ def stack_call_from_args(args, kw: dict, cdl) -> dict:
     return call
 
 
-def rgb_stack_call_from_args(args, plan) -> dict:
-    """The keyword arguments of `apply_rgb_stack` for --rgb-stages (DESIGN.md 3.26), with `pix_fmt` / `out_pix_fmt` as every
-    call of `plan_from_args` carries them and the parsed list under `rgb_stages`: the list parsed with --interp / --interp2 as
-    the lut3d stages' defaults, every refusal of `check_rgb_stack_options`, and a file for every stage and a stage for every
-    file."""
+def _stage_list_from_args(args, plan, flag: str, text) -> dict:
+    """What --rgb-stages and --rgb-out-stages (`flag`, its value `text`) share: the list parsed with --interp / --interp2 as the
+    lut3d stages' defaults, a file for every stage and a stage for every file, and what `check_stage_list` and the option checks
+    are told -- dict(stages, cdl, rgb_matrix, list=the keywords of `check_stage_list`, options=those of the refusals by name)."""
     from .plan import INTERP_WHITELIST
-    if getattr(args, "stages", None) is not None:
-        raise ValueError("--stages and --rgb-stages are mutually exclusive: --stages is the list of a YUV source, --rgb-stages "
-                         "that of an RGB source")
-    if getattr(args, "rgb_out", None) is not None:
-        raise ValueError("--rgb-out names the RGB output of a YUV source: with --rgb-stages the output is --out-pix-fmt")
     interp2 = getattr(args, "interp2", None)
     mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
     cube2, lut1d = getattr(args, "cube2", None), getattr(args, "lut1d", None)
     cdl, mtx = cdl_from_args(args), rgb_matrix_from_args(args)
     strength, keys = strength_from_args(args)
     matte = matte_from_args(args)
-    st = parse_stages(args.rgb_stages, interp=plan.interp, interp2=mode2)
+    st = parse_stages(text, interp=plan.interp, interp2=mode2)
     kinds = [k for k, _m in st]
-    for flag, given, kind in (("--cube", args.cube, "lut3d"), ("--cube2", cube2, "lut3d2"), ("--lut1d", lut1d, "lut1d"),
-                              ("--cdl / --cdl-sop / --cdl-sat", cdl, "cdl"), ("--rgb-matrix / --rgb-matrix-file", mtx, "matrix")):
+    for opt, given, kind in (("--cube", args.cube, "lut3d"), ("--cube2", cube2, "lut3d2"), ("--lut1d", lut1d, "lut1d"),
+                             ("--cdl / --cdl-sop / --cdl-sat", cdl, "cdl"), ("--rgb-matrix / --rgb-matrix-file", mtx, "matrix")):
         if given is not None and kind not in kinds:
-            raise ValueError(f"{flag} is given and --rgb-stages has no '{kind}' stage")
+            raise ValueError(f"{opt} is given and {flag} has no '{kind}' stage")
     if interp2 is not None and "lut3d2" not in kinds:
-        raise ValueError("--interp2 is the mode of the second LUT: --rgb-stages has no 'lut3d2' stage")
+        raise ValueError(f"--interp2 is the mode of the second LUT: {flag} has no 'lut3d2' stage")
     interp1d = getattr(args, "interp1d", None) or "linear"
     from . import _native
     if interp1d not in _native.INTERP1D:
@@ -283,20 +283,63 @@ def rgb_stack_call_from_args(args, plan) -> dict:
         from .api import _cached_cube
         prelut = getattr(_cached_cube(Path(args.cube)), "prelut", None) is not None
     second_out, second_fmt = getattr(args, "second_output", None), getattr(args, "second_pix_fmt", None)
+    return dict(
+        stages=st, cdl=cdl, rgb_matrix=mtx,
+        list=dict(cdl=cdl is not None, lut=args.cube is not None, lut2=cube2 is not None, lut1d=lut1d is not None, prelut=prelut,
+                  rgb_matrix=mtx is not None),
+        options=dict(chroma_loc=getattr(args, "chroma_loc", None), out_size=getattr(args, "out_size", None),
+                     alpha_mode=getattr(args, "alpha_mode", None) or "straight",
+                     out2_pix_fmt=second_fmt if second_fmt is not None else second_out,
+                     strength=strength if keys is None else 1.0, matte=matte is not None))
+
+
+def rgb_stack_call_from_args(args, plan) -> dict:
+    """The keyword arguments of `apply_rgb_stack` for --rgb-stages (DESIGN.md 3.26), with `pix_fmt` / `out_pix_fmt` as every
+    call of `plan_from_args` carries them and the parsed list under `rgb_stages`: the list parsed with --interp / --interp2 as
+    the lut3d stages' defaults, every refusal of `check_rgb_stack_options`, and a file for every stage and a stage for every
+    file."""
+    if getattr(args, "stages", None) is not None:
+        raise ValueError("--stages and --rgb-stages are mutually exclusive: --stages is the list of a YUV source, --rgb-stages "
+                         "that of an RGB source")
+    if getattr(args, "rgb_out", None) is not None:
+        raise ValueError("--rgb-out names the RGB output of a YUV source: with --rgb-stages the output is --out-pix-fmt")
+    r = _stage_list_from_args(args, plan, "--rgb-stages", args.rgb_stages)
+    st, cdl, mtx = r["stages"], r["cdl"], r["rgb_matrix"]
     _st, _fin, fout = check_rgb_stack_options(
-        args.pix_fmt, args.out_pix_fmt, stages=st, cdl=cdl is not None, lut=args.cube is not None, lut2=cube2 is not None,
-        lut1d=lut1d is not None, prelut=prelut, rgb_matrix=mtx is not None,
+        args.pix_fmt, args.out_pix_fmt, stages=st, **r["list"],
         dither="error_diffusion" if args.zscale_dither == "error_diffusion" else getattr(args, "engine_dither", None) or "none",
-        chroma_loc=getattr(args, "chroma_loc", None), out_size=getattr(args, "out_size", None),
-        alpha_mode=getattr(args, "alpha_mode", None) or "straight",
-        out2_pix_fmt=second_fmt if second_fmt is not None else second_out,
-        strength=strength if keys is None else 1.0, matte=matte is not None,
-        intermediate_pix_fmt=plan.intermediate_pix_fmt if plan.prologue else None)
+        intermediate_pix_fmt=plan.intermediate_pix_fmt if plan.prologue else None, **r["options"])
     call = dict(pix_fmt=args.pix_fmt, out_pix_fmt=fout.name, rgb_stages=st, matrix_out=plan.matrix or "smpte170m", range_out="tv")
     if cdl is not None:
         call["cdl"] = cdl
     if mtx is not None:
         call["rgb_matrix"] = mtx
+    return call
+
+
+def rgb_out_stack_call_from_args(args, plan) -> dict:
+    """The keyword arguments of `apply_yuv_stack_to_rgb` for --rgb-out FMT --rgb-out-stages LIST, with
+    `pix_fmt` / `out_pix_fmt` (= FMT) as every call of `plan_from_args` carries them and the parsed list under `rgb_out_stages`:
+    the list as --rgb-stages parses it, every refusal of `check_yuv2rgb_stack_options`, the matrix and ranges of --rgb-out."""
+    from .api import engine_call_for
+    if getattr(args, "stages", None) is not None or getattr(args, "rgb_stages", None) is not None:
+        raise ValueError("--rgb-out-stages and --stages / --rgb-stages are mutually exclusive: --stages is the list of a YUV source "
+                         "with a YUV output, --rgb-stages that of an RGB source, --rgb-out-stages that of a YUV source with --rgb-out")
+    if getattr(args, "rgb_out", None) is None:
+        raise ValueError("--rgb-out-stages is the stage list of a YUV source written as RGB: it needs --rgb-out")
+    if args.out_pix_fmt:
+        raise ValueError(f"rgb_out ('{args.rgb_out}') and out_pix_fmt ('{args.out_pix_fmt}') are mutually exclusive: a call has one "
+                         f"output")
+    r = _stage_list_from_args(args, plan, "--rgb-out-stages", args.rgb_out_stages)
+    check_yuv2rgb_stack_options(args.pix_fmt, args.rgb_out, stages=r["stages"], **r["list"],
+                                dither="error_diffusion" if args.zscale_dither == "error_diffusion" else "none",
+                                engine_dither=getattr(args, "engine_dither", None), **r["options"])
+    call = {k: v for k, v in engine_call_for(plan, args.pix_fmt, None, "straight", rgb_out=args.rgb_out).items() if k != "interp"}
+    call["rgb_out_stages"] = r["stages"]
+    if r["cdl"] is not None:
+        call["cdl"] = r["cdl"]
+    if r["rgb_matrix"] is not None:
+        call["rgb_matrix"] = r["rgb_matrix"]
     return call
 
 
@@ -342,11 +385,15 @@ def plan_from_args(args):
     lut1d = getattr(args, "lut1d", None)
     stages = getattr(args, "stages", None)
     rgb_stages = getattr(args, "rgb_stages", None)
-    if args.cube is None and lut1d is None and stages is None and rgb_stages is None:
+    rgb_out_stages = getattr(args, "rgb_out_stages", None)
+    if args.cube is None and lut1d is None and stages is None and rgb_stages is None and rgb_out_stages is None:
         raise ValueError("--cube is required unless --lut1d is given")
     plan = resolve_lut_plan(params, args.cube if args.cube is not None else "engine.cube", info)
     alpha_mode = getattr(args, "alpha_mode", None) or "straight"
     rgb_out = getattr(args, "rgb_out", None)
+    if rgb_out_stages is not None:
+        # the stage stack from a YUV source into an RGB frame: a route of its own
+        return plan, rgb_out_stack_call_from_args(args, plan), w, h
     if rgb_stages is not None:
         # the stage stack on an RGB source: a route of its own
         return plan, rgb_stack_call_from_args(args, plan), w, h
@@ -447,7 +494,7 @@ def plan_from_args(args):
 def main(argv=None) -> int:
     ap = build_parser()
     args = ap.parse_args(argv)
-    if args.cube is None and args.lut1d is None and args.stages is None and args.rgb_stages is None:
+    if args.cube is None and args.lut1d is None and args.stages is None and args.rgb_stages is None and args.rgb_out_stages is None:
         ap.error("the following arguments are required: --cube (or --lut1d for a 1D LUT alone)")
 
     stop = {"flag": False}
@@ -488,9 +535,10 @@ def main(argv=None) -> int:
         second_fmt = kw.pop("out2_pix_fmt", None)
         if "matte" in kw:
             kw["matte"] = MatteReader(kw.pop("matte"), kw.pop("matte_pix_fmt"), w, h)
+        stacked = any(k in kw for k in ("stages", "rgb_stages", "rgb_out_stages"))   # (the list names its lut3d2 / lut1d stages)
         pipe = HostPipeline(eng, pix_fmt, w, h, batch=args.batch, out_pix_fmt=out_fmt, out_size=args.out_size,
-                            second_pix_fmt=second_fmt, chain=lut2 is not None and "stages" not in kw and "rgb_stages" not in kw,
-                            lut1d=args.lut1d is not None and "stages" not in kw and "rgb_stages" not in kw, rgb_out=rgb_out, **kw)
+                            second_pix_fmt=second_fmt, chain=lut2 is not None and not stacked,
+                            lut1d=args.lut1d is not None and not stacked, rgb_out=rgb_out, **kw)
         fb = pipe.fin.frame_bytes
         if piped_in:
             total = None if args.duration is None else max(1, int(round(args.duration * args.fps)))

@@ -20,7 +20,7 @@ from pathlib import Path
 from typing import List, Optional, Tuple
 
 from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options, check_lut1d_options,
-                      check_premul_options, check_rgb_stack_options, check_stack_options, implied_stages, parse_stages, stages_string, parse_rgb_source, premul_to_yuv)
+                      check_premul_options, check_rgb_stack_options, check_stack_options, check_yuv2rgb_stack_options, implied_stages, parse_stages, stages_string, parse_rgb_source, premul_to_yuv)
 from .params import ProcessingParams, Task, VideoInfo
 from .plan import LutPlan, output_color_tags, resolve_lut_plan, resolve_pix_fmt
 
@@ -259,7 +259,8 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                    cdl=None, cdl_id: Optional[str] = None, lut1d: Optional[Path] = None,
                    interp1d: Optional[str] = None, stages=None, strength: Optional[float] = None,
                    strength_keys: Optional[str] = None, matte: Optional[Path] = None, matte_pix_fmt: Optional[str] = None,
-                   matte_invert: bool = False, rgb_matrix=None, rgb_stages=None) -> List[str]:
+                   matte_invert: bool = False, rgb_matrix=None, rgb_stages=None, rgb_out: Optional[str] = None,
+                   rgb_out_stages=None) -> List[str]:
     """`build_command`'s twin for the LUT stage alone: the argv of the ENGINE CLI (`python -m lut_renderer_amd.cli`)
     that applies exactly the chain `build_command` would put into `-vf` -- the same `LutPlan`, rendered as CLI options
     instead of as a filter string (ffmpeg.py:195-247, :287-310).  `source` / `output` are rawvideo files (or `-`) in
@@ -307,7 +308,12 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     (`--rgb-matrix-file`); rendered only when given.  It needs `stages` with a matrix stage, and the stage needs it.
     `rgb_stages` is `stages` for an RGB source (`--rgb-stages`, rendered only when given: without it the argv
     is what it was): the same lists and files on gbrp* / gbrap* / packed RGB frames, into the resolved output format -- planar
-    YUV, or gbrp* at the source's depth; the refusals are `formats.check_rgb_stack_options`'s.  Not together with `stages`."""
+    YUV, or gbrp* at the source's depth; the refusals are `formats.check_rgb_stack_options`'s.  Not together with `stages`.
+    `rgb_out` with `rgb_out_stages` is `stages` for a planar YUV source written as RGB (`--rgb-out FMT
+    --rgb-out-stages LIST`, rendered only when given: without them the argv is what it was): the same lists and files at the
+    depth of `rgb_out` (gbrp*, gbrap* or a packed name), which takes the place of the resolved output format -- `params` must
+    then resolve none, or that very name; the refusals are `formats.check_yuv2rgb_stack_options`'s.  Each needs the other; not together with
+    `stages` / `rgb_stages`."""
     import sys as _sys
     premul = check_alpha_mode(alpha_mode)
     if precision not in ("strict", "fast", "fma32"):
@@ -329,6 +335,17 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     cmd += ["-i", str(source), "-o", str(output), "--size", f"{source_info.width}x{source_info.height}",
             "--pix-fmt", source_info.pix_fmt]
     pix_fmt = resolve_pix_fmt(params, source_info, notes) if params.video_codec else ""
+    if rgb_out_stages is not None:
+        if rgb_out is None:
+            raise ValueError("rgb_out_stages is the stage list of a YUV source written as RGB: it needs rgb_out")
+        if stages is not None or rgb_stages is not None:
+            raise ValueError("rgb_out_stages and stages / rgb_stages are mutually exclusive: stages is the list of a YUV source with "
+                             "a YUV output, rgb_stages that of an RGB source, rgb_out_stages that of a YUV source with rgb_out")
+        if pix_fmt and pix_fmt != rgb_out:
+            raise ValueError(f"rgb_out ('{rgb_out}') and out_pix_fmt ('{pix_fmt}') are mutually exclusive: a call has one output")
+        pix_fmt = ""                                           # (--rgb-out names the output)
+    elif rgb_out is not None:
+        raise ValueError("engine_command renders rgb_out together with rgb_out_stages only")
     src_rgb = parse_rgb_source(str(source_info.pix_fmt))
     float_src = src_rgb is not None and src_rgb.floating
     if float_src:
@@ -346,7 +363,7 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
         cmd += ["--out-pix-fmt", pix_fmt]
     cmd += ["--cube", str(plan.lut_path), "--interp", plan.interp, "--input-matrix", plan.matrix_policy,
             "--output-tags", plan.output_policy]
-    if getattr(params, "zscale_dither", "none") == "error_diffusion" and pix_fmt:
+    if getattr(params, "zscale_dither", "none") == "error_diffusion" and (pix_fmt or rgb_out is not None):
         cmd += ["--zscale-dither", "error_diffusion"]
         notes.append("抖动: zscale=dither=error_diffusion")
     if source_info.colorspace:
@@ -402,10 +419,10 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     if rgb_stages is not None and stages is not None:
         raise ValueError("stages and rgb_stages are mutually exclusive: stages is the list of a YUV source, rgb_stages that of an "
                          "RGB source")
-    if rgb_matrix is not None and stages is None and rgb_stages is None:
+    if rgb_matrix is not None and stages is None and rgb_stages is None and rgb_out_stages is None:
         raise ValueError("rgb_matrix needs stages: a matrix stage has no implied position (e.g. stages='lut1d,matrix,lut3d')")
-    # the pairwise refusals below give way to check_stack_options / check_rgb_stack_options at the end
-    stack = stages is not None or mixed or matte is not None or rgb_stages is not None
+    # the pairwise refusals below give way to check_stack_options / check_rgb_stack_options / check_yuv2rgb_stack_options at the end
+    stack = stages is not None or mixed or matte is not None or rgb_stages is not None or rgb_out_stages is not None
     if cube2 is not None:
         from .plan import INTERP_WHITELIST
         if not stack:
@@ -458,7 +475,7 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
         from . import _native
         from .plan import INTERP_WHITELIST
         mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
-        listed = rgb_stages if rgb_stages is not None else stages if stages is not None else \
+        listed = rgb_out_stages if rgb_out_stages is not None else rgb_stages if rgb_stages is not None else stages if stages is not None else \
             implied_stages(True, cube2 is not None, lut1d is not None, cdl is not None)
         st = parse_stages(listed, interp=plan.interp, interp2=mode2)
         kinds = [k for k, _m in st]
@@ -468,7 +485,18 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                                   ("cdl", cdl, "cdl"), ("rgb_matrix", rgb_matrix, "matrix")):
             if given is not None and kind not in kinds:
                 raise ValueError(f"{name} is given and the stage list has no '{kind}' stage")
-        if rgb_stages is not None:
+        if rgb_out_stages is not None:
+            from .api import engine_call_for
+            check_yuv2rgb_stack_options(str(source_info.pix_fmt), rgb_out, stages=st, cdl=cdl is not None, lut=True,
+                                        lut2=cube2 is not None, lut1d=lut1d is not None, rgb_matrix=rgb_matrix is not None,
+                                        dither="error_diffusion" if dither == "error_diffusion" else "none",
+                                        engine_dither=engine_dither, chroma_loc=chroma_loc,
+                                        out_size=params.resolution if "--out-size" in cmd else None, alpha_mode=alpha_mode,
+                                        out2_pix_fmt=second_pix_fmt,
+                                        strength=(strength if strength_keys is None else 1.0) if mixed else None,
+                                        matte=matte is not None)
+            engine_call_for(plan, str(source_info.pix_fmt), None, "straight", rgb_out=rgb_out)   # (a full-range source: 8 bit only)
+        elif rgb_stages is not None:
             check_rgb_stack_options(str(source_info.pix_fmt), pix_fmt or None, stages=st, cdl=cdl is not None, lut=True,
                                     lut2=cube2 is not None, lut1d=lut1d is not None, rgb_matrix=rgb_matrix is not None, dither=dither,
                                     chroma_loc=chroma_loc, out_size=params.resolution if "--out-size" in cmd else None,
@@ -491,7 +519,9 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                 cmd += ["--rgb-matrix-file", str(rgb_matrix)]
             else:
                 raise TypeError(f"rgb_matrix must be an RgbMatrix or the path of a .spimtx file, not {type(rgb_matrix).__name__}")
-        if rgb_stages is not None:
+        if rgb_out_stages is not None:
+            cmd += ["--rgb-out", rgb_out, "--rgb-out-stages", stages_string(st)]
+        elif rgb_stages is not None:
             cmd += ["--rgb-stages", stages_string(st)]
         elif stages is not None:
             cmd += ["--stages", stages_string(st)]

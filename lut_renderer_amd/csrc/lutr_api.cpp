@@ -2356,34 +2356,74 @@ int lutr_apply_rgb_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage
     return finish_launch(c, full.c_str());
 }
 
+// lutr_apply_yuv_to_rgb and lutr_apply_yuv_stack_to_rgb behind their own first checks: the constants, the
+// two sides, the row rule, the plane and overlap checks.  `what`: the pass as the overlap message names it.  *empty: nothing to do.
+struct Yuv2RgbCall { YuvConsts K; Side S; RgbLayout Y; PlaneSet P; FrameGeom G; bool empty; };
+
+static int yuv2rgb_open(const lutr_yuv_params *p, int dst_kind, int w, int h, int nframes, const lutr_planes *src,
+                        const lutr_planes *dst_planar, const lutr_packed *dst_packed, int row0, int rows, const char *what,
+                        Yuv2RgbCall *u)
+{
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    if (const int rc = make_yuv_consts_yuv2rgb(*p, &u->K)) return rc;
+    u->S = planar_side("source", src, p->fmt_in);
+    if (const int rc = rgb_side_layout(dst_kind, p->lut_depth, "destination", &u->Y)) return rc;
+    if (const int rc = check_row_blocks(row0, rows, h, 1 << u->S.csy, "chroma block height")) return rc;
+    u->G = FrameGeom{w, h, row0, rows, nframes};
+    u->P = PlaneSet{};
+    u->empty = w == 0 || rows == 0 || nframes == 0;
+    if (u->empty) return LUTR_OK;
+    if (const int rc = check_planes_set(src, nullptr)) return rc;
+    Span ss[3], ds[3]; int nd;
+    for (int i = 0; i < 3; i++) { u->P.s[i] = (const uint8_t *)src->data[i]; u->P.ss[i] = src->stride[i]; u->P.sfs[i] = src->frame_stride[i]; }
+    if (const int rc = rgb_side_streams(u->Y, dst_planar, dst_packed, u->G, false, &u->P, ds, &nd)) return rc;
+    // the two sides differ in size and layout: a thread's stores would land on samples another thread has yet to read
+    side_spans(u->S, u->G, ss);
+    return check_disjoint(what, true, ss, 3, ds, nd);
+}
+
 int lutr_apply_yuv_to_rgb(lutr_ctx *c, const lutr_yuv_params *p, int interp, int dst_kind, int w, int h, int nframes,
                           const lutr_planes *src, const lutr_planes *dst_planar, const lutr_packed *dst_packed, int row0, int rows)
 {
     const void *dst = dst_kind ? (const void *)dst_packed : (const void *)dst_planar;
-    int rc = check_common(c, interp, LUTR_INTERP_NONE, w, h, nframes, src, dst, row0, rows);
-    if (rc) return rc;
-    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
-    YuvConsts K;
-    rc = make_yuv_consts_yuv2rgb(*p, &K);
-    if (rc) return rc;
-    const int dl = p->lut_depth;
-    const Side S = planar_side("source", src, p->fmt_in);
-    RgbLayout Y;
-    if (const int rc = rgb_side_layout(dst_kind, dl, "destination", &Y)) return rc;
-    if (const int rc = check_row_blocks(row0, rows, h, 1 << S.csy, "chroma block height")) return rc;
-    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    if (const int rc = check_planes_set(src, nullptr)) return rc;
-    PlaneSet P{}; Span ss[3], ds[3]; int nd; const FrameGeom G{w, h, row0, rows, nframes};
-    for (int i = 0; i < 3; i++) { P.s[i] = (const uint8_t *)src->data[i]; P.ss[i] = src->stride[i]; P.sfs[i] = src->frame_stride[i]; }
-    if (const int rc = rgb_side_streams(Y, dst_planar, dst_packed, G, false, &P, ds, &nd)) return rc;
-    // the two sides differ in size and layout: a thread's stores would land on samples another thread has yet to read
-    side_spans(S, G, ss);
-    if (const int rc = check_disjoint("YUV -> RGB", true, ss, 3, ds, nd)) return rc;
+    if (const int rc = check_common(c, interp, LUTR_INTERP_NONE, w, h, nframes, src, dst, row0, rows)) return rc;
+    Yuv2RgbCall U;
+    if (const int rc = yuv2rgb_open(p, dst_kind, w, h, nframes, src, dst_planar, dst_packed, row0, rows, "YUV -> RGB", &U)) return rc;
+    if (U.empty) return LUTR_OK;
     HIP_TRY(hipSetDevice(c->device));
     LutConsts L{};
     if (interp != LUTR_INTERP_NONE)
-        if (const int rc = fill_lut(&L, c, dl)) return rc;
-    return finish_launch(c, launch_yuv2rgb(c->stream, c->variant, L, K, P, Y, G, S.depth, S.csx, S.csy, interp));
+        if (const int rc = fill_lut(&L, c, p->lut_depth)) return rc;
+    return finish_launch(c, launch_yuv2rgb(c->stream, c->variant, L, U.K, U.P, U.Y, U.G, U.S.depth, U.S.csx, U.S.csy, interp));
+}
+
+// ---- the stage stack from a YUV source into an RGB frame: lutr_apply_yuv_to_rgb's two sides with the list of
+// lutr_apply_rgb_stack between the conversion and the stores
+int lutr_apply_yuv_stack_to_rgb(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                                const lutr_rgb_matrix *mtx, int dst_kind, int w, int h, int nframes, const lutr_planes *src,
+                                const lutr_planes *dst_planar, const lutr_packed *dst_packed, int row0, int rows)
+{
+    const void *dst = dst_kind ? (const void *)dst_packed : (const void *)dst_planar;
+    if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
+    StackList T;
+    if (const int rc = stack_check_list(c, stages, nstages, cdl, true, mtx, &T)) return rc;
+    if (const int rc = check_geometry(w, h, nframes, row0, rows)) return rc;
+    if (const int rc = stack_compile_steps(c, stages, nstages, &T)) return rc;
+    if (c->variant == VAR_VEC_LDS) {
+        set_error("variant vec_lds: there is no LDS-window kernel for the YUV -> RGB stack pass");
+        return LUTR_EINVAL;
+    }
+    Yuv2RgbCall U;
+    if (const int rc = yuv2rgb_open(p, dst_kind, w, h, nframes, src, dst_planar, dst_packed, row0, rows, "the YUV -> RGB stack pass", &U))
+        return rc;
+    if (U.empty) return LUTR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    LutConsts L{}, L2{}; StackConsts S{}; MtxConsts X{};
+    if (const int rc = stack_device_consts(c, T, cdl, mtx, p->lut_depth, &L, &L2, &S, &X)) return rc;
+    const char *name = launch_yuv2rgb_stack(c->stream, c->variant, L, L2, S, X, U.K, U.P, U.Y, U.G, U.S.depth, U.S.csx, U.S.csy);
+    if (!name) return finish_launch(c, nullptr);
+    const std::string full = std::string(name) + "[" + T.list + "]";
+    return finish_launch(c, full.c_str());
 }
 
 // gbrpf32 planes hold 4-byte samples: base pointers, row strides and (batches) frame strides must be multiples of 4

@@ -388,6 +388,39 @@ __device__ __forceinline__ Rgb r2y_pixel(const uint32_t *in, int i, const RgbLay
     }
 }
 
+// ---------------------------------------------------------------- RGB destinations of the vector kernels (lutr_yuv2rgb.hip, lutr_y2rstack.hip)
+// `out` holds the 8 pixels of a thread and row as `in` above does: planar the 8 samples of R, of G and of B; packed as in memory.
+
+// pixel i of the thread's 8 into the output words of one row
+template <int WOUT, int NC>
+__device__ __forceinline__ void y2r_put(uint32_t *out, int i, const Rgb &o, const RgbLayout &Y, uint32_t amax)
+{
+    constexpr int SW = 8 * (WOUT ? 2 : 1) / 4;            // dwords of 8 samples of one plane
+    if constexpr (NC == 1) {
+        word_put<WOUT>(out, i, o.r);
+        word_put<WOUT>(out + SW, i, o.g);
+        word_put<WOUT>(out + 2 * SW, i, o.b);
+    } else if constexpr (NC == 3) {
+        const bool swap = Y.ro != 0;                      // bgr order
+        word_put<WOUT>(out, i * 3 + 0, swap ? o.b : o.r);
+        word_put<WOUT>(out, i * 3 + 1, o.g);
+        word_put<WOUT>(out, i * 3 + 2, swap ? o.r : o.b);
+    } else {
+        const int ao = 6 - Y.ro - Y.go - Y.bo;
+        if constexpr (WOUT) {
+            const unsigned long long q = ((unsigned long long)amax << (ao * 16)) |
+                                         ((unsigned long long)(unsigned)o.r << (Y.ro * 16)) |
+                                         ((unsigned long long)(unsigned)o.g << (Y.go * 16)) |
+                                         ((unsigned long long)(unsigned)o.b << (Y.bo * 16));
+            out[2 * i] = (uint32_t)q;
+            out[2 * i + 1] = (uint32_t)(q >> 32);
+        } else {
+            out[i] = (amax << (ao * 8)) | ((unsigned)o.r << (Y.ro * 8)) | ((unsigned)o.g << (Y.go * 8)) |
+                     ((unsigned)o.b << (Y.bo * 8));
+        }
+    }
+}
+
 // ---------------------------------------------------------------- plane rows
 template <class Y>
 __device__ __forceinline__ const uint8_t *src_row(const PlaneSet &P, int c, long long fr, Y y)
@@ -400,6 +433,22 @@ __device__ __forceinline__ uint8_t *dst_row(const PlaneSet &P, int c, long long 
 {
     return P.d[c] + fr * P.dfs[c] + y * P.ds[c];
 }
+
+// the RGB destination of the by-block generic kernels (lutr_yuv2rgb.hip, lutr_y2rstack.hip): a sink that stores the pixel
+struct RgbSink {
+    const PlaneSet &P;
+    const RgbLayout &Y;
+    float amax;
+    __device__ __forceinline__ void luma(long long fr, int x, int y, const Rgb &o)
+    {
+        const int e = x * Y.step;
+        st_sample(dst_row(P, 0, fr, y), e + Y.ro, Y.wide, o.r);
+        st_sample(dst_row(P, 1, fr, y), e + Y.go, Y.wide, o.g);
+        st_sample(dst_row(P, 2, fr, y), e + Y.bo, Y.wide, o.b);
+        if (Y.step == 4) st_sample(dst_row(P, 0, fr, y), e + 6 - Y.ro - Y.go - Y.bo, Y.wide, amax);
+    }
+    __device__ __forceinline__ void chroma(long long, int, int, float, float, float) {}
+};
 
 // ---------------------------------------------------------------- by-block generic kernels: the walk and the output sinks
 // Grid-stride walk of blocks of 2^csx x 2^csy luma samples, one thread per block: body(fr, cx, cy) for every block that touches

@@ -421,6 +421,22 @@ const char *launch_yuv2rgb(hipStream_t st, int variant, const LutConsts &L, cons
 LUTR_Y2R_DECL(w00) LUTR_Y2R_DECL(w11) LUTR_Y2R_DECL(w10)
 #undef LUTR_Y2R_DECL
 
+// the stage stack from a YUV source into an RGB frame (lutr_y2rstack.hip): launch_yuv2rgb's source and destination
+// (P, Y, din, icsx, icsy) with the step list S of launch_rgb_stack (L2, X likewise) between yuv_to_rgb and the stores.  nullptr =
+// the variant cannot take the call (vec_lds always; vec_global on layouts the vector kernel cannot take and on pyramid / prism
+// stages)
+const char *launch_yuv2rgb_stack(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
+                                 const MtxConsts &X, const YuvConsts &K, const PlaneSet &P, const RgbLayout &Y, const FrameGeom &G,
+                                 int din, int icsx, int icsy);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>); tri: some lattice step is trilinear; lds:
+// stage the tables per workgroup.  nullptr = not a layout / destination kind it has
+#define LUTR_YRS_DECL(tag) \
+    const char *launch_yuv2rgb_stack_vec_##tag(hipStream_t st, const LutConsts &L, const LutConsts &L2, const StackConsts &S, \
+                                               const MtxConsts &X, const YuvConsts &K, const PlaneSet &P, const RgbLayout &Y, \
+                                               const FrameGeom &G, int icsx, int icsy, bool tri, bool lds);
+LUTR_YRS_DECL(w00) LUTR_YRS_DECL(w11) LUTR_YRS_DECL(w10)
+#undef LUTR_YRS_DECL
+
 // planar float RGB sources (lutr_rgbf.hip): gbrpf32 planes in PlaneSet::s in R, G, B order.  No per-code
 // coordinate table exists for a float input, so lut3d's prelut travels as the raw table lutr_ctx_set_prelut was given and is
 // applied per pixel (FFmpeg's prelut_interp_1d_linear); LutConsts::pre is not read by these kernels.

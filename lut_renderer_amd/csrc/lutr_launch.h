@@ -224,9 +224,9 @@ const char *launch_union(int variant, const PlaneSet &P, const FrameGeom &G, con
     return both.c_str();
 }
 
-// Where the vector kernels of a stage stack (lutr_stack.hip, lutr_rgbstack.hip) read the CDL and 1D tables.  The tables the stack
-// uses go to LDS together or not at all: above 24 KB in sum they are read from global memory.  LUTR_STACK_LDS=0 / 1 (tests and
-// tools) says which; unset: the family's own default.
+// Where the vector kernels of a stage stack (lutr_stack.hip, lutr_rgbstack.hip, lutr_y2rstack.hip) read the CDL and 1D tables.
+// The tables the stack uses go to LDS together or not at all: above 24 KB in sum they are read from global memory.
+// LUTR_STACK_LDS=0 / 1 (tests and tools) says which; unset: the family's own default.
 constexpr size_t kStackLdsBytes = 24 * 1024;
 inline bool stack_in_lds(const StackConsts &S, bool family_default)
 {

@@ -38,11 +38,7 @@ extern __shared__ uint32_t rsk_lds[];                             // the staged 
 // stack_stage_tables of lutr_stack.hip on this family's LDS: every thread of the workgroup must arrive here
 __device__ __forceinline__ void rsk_stage_tables(const StackConsts &S)
 {
-    const uint32_t *__restrict__ a = (const uint32_t *)S.cdl_tab;
-    const uint32_t *__restrict__ b = (const uint32_t *)S.l1d_tab;
-    for (int i = threadIdx.x; i < S.lds_cdl_words; i += 256) rsk_lds[i] = a[i];
-    for (int i = threadIdx.x; i < S.lds_l1d_words; i += 256) rsk_lds[S.lds_cdl_words + i] = b[i];
-    __syncthreads();
+    stack_stage_to(rsk_lds, S);
 }
 
 // k_rgb2yuv_vec's input side (8 samples per thread and row, 2^OCSY rows, NC = 1 planar | 3 | 4 packed), k_yuv_stack_vec's walk
@@ -179,28 +175,6 @@ const char *LUTR_CAT(LUTR_CAT(launch_rgb_stack_vec_w, LUTR_RSK_WI), LUTR_RSK_WO)
 
 #else  // !LUTR_RSK_WI
 // ================================================================= generic kernel
-// stack_generic's per-pixel step loop (lutr_stack.hip) on one pixel of codes: the tables read from global memory, all five modes
-__device__ __forceinline__ Rgb rsk_steps_px(const LutConsts &L, const LutConsts &L2, const GFetch &f, const GFetch &f2,
-                                            const StackConsts &S, const CdlConsts &C, const MtxConsts &X, bool mix, Rgb o)
-{
-#pragma nounroll
-    for (unsigned long long ops = S.ops; ops & 0xffull; ops >>= 8) {
-        const int op = (int)(ops & 15u), mode = (int)((ops >> 4) & 15u);
-        switch (op) {
-        case STACK_OP_L1D:        o = stack_l1d_px(S.l1d_tab, S.stride, o); break;
-        case STACK_OP_CDL:        o = cdl_px(C, mix, o); break;
-        case STACK_OP_ROUND:      o = stack_round_px(S.maxf, o); break;
-        case STACK_OP_LAT_CODES:  o = lut3d_px_rt(mode, L, f, o.r, o.g, o.b); break;
-        case STACK_OP_LAT_UNIT:   o = lut3d_unit_rt(mode, L, f, o); break;
-        case STACK_OP_LAT2_CODES: o = lut3d_px_rt(mode, L2, f2, o.r, o.g, o.b); break;
-        case STACK_OP_MTX_CODES:  o = mtx_px(X, X.rcp, o); break;
-        case STACK_OP_MTX_UNIT:   o = mtx_px(X, 1.0f, o); break;
-        default:                  o = lut3d_unit_rt(mode, L2, f2, o); break;
-        }
-    }
-    return o;
-}
-
 // One thread per output block (r2y_block's walk): any depth mix, stride or alignment, odd sizes, both sinks.  A pixel outside the
 // frame is the edge pixel again; only pixels inside the planes are written.  The RGB sink's block is one pixel.
 __global__ __launch_bounds__(256) void k_rgb_stack_generic(LutConsts L, LutConsts L2, StackConsts S, MtxConsts X, YuvConsts K, PlaneSet P,

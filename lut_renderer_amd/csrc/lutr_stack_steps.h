@@ -1,6 +1,6 @@
 // lutr_stack_steps.h -- the per-pixel step functions of a stage stack and the walk of one block of pixels
-// through the compiled step list, shared by the YUV stack kernels (lutr_stack.hip) and the RGB-source ones (lutr_rgbstack.hip,
-// DESIGN.md 3.26).  Device code only; include it behind lutr_device.h.
+// through the compiled step list, shared by the YUV stack kernels (lutr_stack.hip), the RGB-source ones (lutr_rgbstack.hip,
+// DESIGN.md 3.26) and the YUV -> RGB ones (lutr_y2rstack.hip).  Device code only; include it behind lutr_device.h.
 //
 // The includer says whether its translation unit holds the matrix steps: with LUTR_SK_MTX defined, SK_MTX_PARAM is
 // `, const MtxConsts &X` and stack_block takes the matrix as its last argument; without, SK_MTX_PARAM is empty and the steps are
@@ -60,6 +60,17 @@ __device__ __forceinline__ void stack_lattice(bool unit, const LutConsts &X, con
     }
 }
 
+// The CDL's and the 1D table's words of S into a workgroup's LDS, the CDL's first (stack_in_lds, lutr_launch.h); every thread of the
+// workgroup must arrive here
+__device__ __forceinline__ void stack_stage_to(uint32_t *lds, const StackConsts &S)
+{
+    const uint32_t *__restrict__ a = (const uint32_t *)S.cdl_tab;
+    const uint32_t *__restrict__ b = (const uint32_t *)S.l1d_tab;
+    for (int i = threadIdx.x; i < S.lds_cdl_words; i += 256) lds[i] = a[i];
+    for (int i = threadIdx.x; i < S.lds_l1d_words; i += 256) lds[S.lds_cdl_words + i] = b[i];
+    __syncthreads();
+}
+
 // The pixels of one block through the step list.  Every branch depends on kernel arguments only.
 template <bool TRI, int N>
 __device__ __forceinline__ void stack_block(const StackConsts &S, const CdlConsts &C, const uint16_t *l1d, const LutConsts &L,
@@ -95,5 +106,29 @@ __device__ __forceinline__ void stack_block(const StackConsts &S, const CdlConst
         }
     }
 }
+
+#ifdef LUTR_SK_MTX
+// stack_generic's per-pixel step loop (lutr_stack.hip) on one pixel of codes: the tables read from global memory, all five modes
+__device__ __forceinline__ Rgb rsk_steps_px(const LutConsts &L, const LutConsts &L2, const GFetch &f, const GFetch &f2,
+                                            const StackConsts &S, const CdlConsts &C, const MtxConsts &X, bool mix, Rgb o)
+{
+#pragma nounroll
+    for (unsigned long long ops = S.ops; ops & 0xffull; ops >>= 8) {
+        const int op = (int)(ops & 15u), mode = (int)((ops >> 4) & 15u);
+        switch (op) {
+        case STACK_OP_L1D:        o = stack_l1d_px(S.l1d_tab, S.stride, o); break;
+        case STACK_OP_CDL:        o = cdl_px(C, mix, o); break;
+        case STACK_OP_ROUND:      o = stack_round_px(S.maxf, o); break;
+        case STACK_OP_LAT_CODES:  o = lut3d_px_rt(mode, L, f, o.r, o.g, o.b); break;
+        case STACK_OP_LAT_UNIT:   o = lut3d_unit_rt(mode, L, f, o); break;
+        case STACK_OP_LAT2_CODES: o = lut3d_px_rt(mode, L2, f2, o.r, o.g, o.b); break;
+        case STACK_OP_MTX_CODES:  o = mtx_px(X, X.rcp, o); break;
+        case STACK_OP_MTX_UNIT:   o = mtx_px(X, 1.0f, o); break;
+        default:                  o = lut3d_unit_rt(mode, L2, f2, o); break;
+        }
+    }
+    return o;
+}
+#endif
 
 }  // namespace lutr

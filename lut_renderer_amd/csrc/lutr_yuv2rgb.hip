@@ -26,36 +26,6 @@ namespace lutr {
 // per input chroma sample, lattice taps gathered from L1/L2) with k_packed_vec's output side.  NC = 1: three planes; 3 | 4: one
 // packed image (8 pixels = 6, 8, 12 or 16 dwords per row).  The component order of a packed destination is a wave-uniform argument.
 
-// pixel i of the thread's 8 into the output words of one row
-template <int WOUT, int NC>
-__device__ __forceinline__ void y2r_put(uint32_t *out, int i, const Rgb &o, const RgbLayout &Y, uint32_t amax)
-{
-    constexpr int SW = 8 * (WOUT ? 2 : 1) / 4;            // dwords of 8 samples of one plane
-    if constexpr (NC == 1) {
-        word_put<WOUT>(out, i, o.r);
-        word_put<WOUT>(out + SW, i, o.g);
-        word_put<WOUT>(out + 2 * SW, i, o.b);
-    } else if constexpr (NC == 3) {
-        const bool swap = Y.ro != 0;                      // bgr order
-        word_put<WOUT>(out, i * 3 + 0, swap ? o.b : o.r);
-        word_put<WOUT>(out, i * 3 + 1, o.g);
-        word_put<WOUT>(out, i * 3 + 2, swap ? o.r : o.b);
-    } else {
-        const int ao = 6 - Y.ro - Y.go - Y.bo;
-        if constexpr (WOUT) {
-            const unsigned long long q = ((unsigned long long)amax << (ao * 16)) |
-                                         ((unsigned long long)(unsigned)o.r << (Y.ro * 16)) |
-                                         ((unsigned long long)(unsigned)o.g << (Y.go * 16)) |
-                                         ((unsigned long long)(unsigned)o.b << (Y.bo * 16));
-            out[2 * i] = (uint32_t)q;
-            out[2 * i + 1] = (uint32_t)(q >> 32);
-        } else {
-            out[i] = (amax << (ao * 8)) | ((unsigned)o.r << (Y.ro * 8)) | ((unsigned)o.g << (Y.go * 8)) |
-                     ((unsigned)o.b << (Y.bo * 8));
-        }
-    }
-}
-
 template <int WIN, int ICSX, int ICSY, int NC, int WOUT, int INTERP>
 __global__ __launch_bounds__(256) void k_yuv2rgb_vec(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, RgbLayout Y)
 {
@@ -160,21 +130,6 @@ const char *LUTR_CAT(LUTR_CAT(launch_yuv2rgb_vec_w, LUTR_Y2R_WI), LUTR_Y2R_WO)(h
 // One thread per input chroma block: xsub_union_block (lutr_device.h) with a 4:4:4 "output layout", so that every pixel is a
 // block of its own, and a sink that stores the pixel; any depth pair, stride or alignment, odd sizes, all five modes and the
 // LUT-free form.  Only pixels inside the frame are written.
-struct RgbSink {
-    const PlaneSet &P;
-    const RgbLayout &Y;
-    float amax;
-    __device__ __forceinline__ void luma(long long fr, int x, int y, const Rgb &o)
-    {
-        const int e = x * Y.step;
-        st_sample(dst_row(P, 0, fr, y), e + Y.ro, Y.wide, o.r);
-        st_sample(dst_row(P, 1, fr, y), e + Y.go, Y.wide, o.g);
-        st_sample(dst_row(P, 2, fr, y), e + Y.bo, Y.wide, o.b);
-        if (Y.step == 4) st_sample(dst_row(P, 0, fr, y), e + 6 - Y.ro - Y.go - Y.bo, Y.wide, amax);
-    }
-    __device__ __forceinline__ void chroma(long long, int, int, float, float, float) {}
-};
-
 __global__ __launch_bounds__(256) void k_yuv2rgb_generic(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, RgbLayout Y, int win,
                                                          int icsx, int icsy, int mode)
 {

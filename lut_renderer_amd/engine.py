@@ -25,7 +25,7 @@ from .rgbmatrix import RgbMatrix
 # (the formats and the checks of names and options live in formats.py; the names callers have always imported from here stay)
 from .formats import (_ALPHA_RESIZE, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, V210Fmt, chain_interp, chain_side,  # noqa: F401
                       changes_subsampling, check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc,
-                      check_lut1d_options, check_matte, check_rgb_stack_options, check_stack_options, check_strength, check_yuv2rgb_options,
+                      check_lut1d_options, check_matte, check_rgb_stack_options, check_stack_options, check_strength, check_yuv2rgb_options, check_yuv2rgb_stack_options,
                       check_container_options,
                       check_dual_options, check_lut2, check_packed_options, check_premul_options, check_semi_options,
                       chroma_loc_code, dual_side, has_prologue, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt,
@@ -1386,6 +1386,18 @@ class LutEngine:
         fin, fout = check_yuv2rgb_options(pix_fmt, out_pix_fmt, **refused)
         if interp not in _native.INTERP:
             raise ValueError(f"lut3d has no interpolation mode '{interp}'")
+        mode = _native.INTERP[interp] if lut else _native.INTERP_NONE
+
+        def call(p, kind, w, h, nf, s, d_planar, d_packed, row0, nrows):
+            return self._lib.lutr_apply_yuv_to_rgb(self._ctx, p, mode, kind, w, h, nf, s, d_planar, d_packed, row0, nrows)
+
+        return self._yuv2rgb_run(call, src, dst, fin, fout, matrix_in, range_src, range_in, row0, rows)
+
+    def _yuv2rgb_run(self, call, src, dst, fin, fout, matrix_in: str, range_src: str, range_in: Optional[str], row0: int,
+                     rows: Optional[int]):
+        """The host side `apply_yuv_to_rgb` and `apply_yuv_stack_to_rgb` share behind their option checks: the planes, the
+        destination (allocated when none is given), the parameter block, `call(p, dst_kind, w, h, nframes, src, dst_planar,
+        dst_packed, row0, rows)` -- the C entry -- and gbrap*'s alpha plane."""
         if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
             raise ValueError(_PLANE_COUNT[fin.nplanes].format(fin.name))
         if not isinstance(src[0], torch.Tensor):
@@ -1413,14 +1425,12 @@ class LutEngine:
         _check_not_in_place(src[:3], [dst] if packed else dst[:3], _YUV2RGB_IN_PLACE)
         rin = range_in or range_src
         p = _yuv_params(fin.colour.code, _native.fmt_code(fout.depth, 0, 0), fout.depth, matrix_in, matrix_in, range_src, rin, rin)
-        mode = _native.INTERP[interp] if lut else _native.INTERP_NONE
         nrows = h - row0 if rows is None else rows
 
         def colour():
             self._bind_stream()
-            _native.check(self._lib.lutr_apply_yuv_to_rgb(
-                self._ctx, C.byref(p), mode, fout.code if packed else 0, w, h, nf, C.byref(s), None if packed else C.byref(d),
-                C.byref(d) if packed else None, row0, nrows))
+            _native.check(call(C.byref(p), fout.code if packed else 0, w, h, nf, C.byref(s), None if packed else C.byref(d),
+                               C.byref(d) if packed else None, row0, nrows))
 
         if not packed and fout.alpha:
             # gbrap*: the colour planes, then the alpha plane on the same stream; a prologue call fills
@@ -1431,6 +1441,45 @@ class LutEngine:
             with self._lock:
                 colour()
         return dst
+
+    # -- the stage stack from a YUV source into an RGB frame -----
+    def apply_yuv_stack_to_rgb(self, src: Sequence[torch.Tensor], dst=None, *, pix_fmt: str, out_pix_fmt: str, stages,
+                               cdl: Optional[Cdl] = None, rgb_matrix: Optional[RgbMatrix] = None, matrix_in: str = "bt709",
+                               range_src: str = "tv", range_in: Optional[str] = None, row0: int = 0, rows: Optional[int] = None,
+                               **other):
+        """`apply_yuv_to_rgb` with the ordered stack of `apply_rgb_stack` in place of lut3d -- 1..4 stages out of "lut3d",
+        "lut3d2", "lut1d", "cdl", "matrix", each at most once, in any order, every lut3d stage with its own mode -- in one pass
+        (lutr_apply_yuv_stack_to_rgb).  `src`, `dst`, `pix_fmt`, `out_pix_fmt`, `matrix_in`, `range_src`,
+        `range_in`, `row0` / `rows` and the alpha rules are `apply_yuv_to_rgb`'s: planar YUV (4:2:0 / 4:2:2 / 4:4:4 at 8..16 bit,
+        yuva* too) converted to integer RGB codes at the OUTPUT's depth, where the list runs; its final codes are stored as they
+        are into gbrp* / gbrap* planes or one packed image (a fourth component opaque).  Not in place.  ("lut3d",) gives the bits
+        of `apply_yuv_to_rgb`; any list gives those of `apply_rgb_stack` from gbrp* into gbrp* on the output of
+        `apply_yuv_to_rgb(lut=False)`.  Dither, out_size, chroma_loc, strength, matte, premultiplied alpha, a second output, a
+        float destination, semi-planar / packed 4:2:2 / v210 sources and alpha into a 4-component packed destination are
+        ValueErrors naming them (`formats.check_yuv2rgb_stack_options`)."""
+        for k in other:
+            if k not in ("dither", "engine_dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength", "matte"):
+                raise TypeError(f"apply_yuv_stack_to_rgb() got an unexpected keyword argument '{k}'")
+        if cdl is not None and not isinstance(cdl, Cdl):
+            raise TypeError(f"cdl must be a lut_renderer_amd.cdl.Cdl, not {type(cdl).__name__}")
+        if rgb_matrix is not None and not isinstance(rgb_matrix, RgbMatrix):
+            raise TypeError(f"rgb_matrix must be a lut_renderer_amd.rgbmatrix.RgbMatrix, not {type(rgb_matrix).__name__}")
+        st, fin, fout = check_yuv2rgb_stack_options(
+            pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(self, "n", 0)),
+            lut2=bool(getattr(self, "n2", 0)), lut1d=bool(getattr(self, "n1d", 0)), prelut=bool(getattr(self, "_has_prelut", False)),
+            rgb_matrix=rgb_matrix is not None, dither=other.get("dither", "none"), engine_dither=other.get("engine_dither"),
+            chroma_loc=other.get("chroma_loc"), out_size=other.get("out_size"), alpha_mode=other.get("alpha_mode", "straight"),
+            out2_pix_fmt=other.get("out2_pix_fmt"), variant=getattr(self, "_variant_name", None), strength=other.get("strength"),
+            matte=other.get("matte"))
+        arr = _native.stage_array(st)
+        k = None if cdl is None else C.byref(_native.cdl_struct(cdl))
+        m = None if rgb_matrix is None else C.byref(_native.rgb_matrix_struct(rgb_matrix))
+
+        def call(p, kind, w, h, nf, s, d_planar, d_packed, row0, nrows):
+            return self._lib.lutr_apply_yuv_stack_to_rgb(self._ctx, p, arr, len(st), k, m, kind, w, h, nf, s, d_planar, d_packed,
+                                                         row0, nrows)
+
+        return self._yuv2rgb_run(call, src, dst, fin, fout, matrix_in, range_src, range_in, row0, rows)
 
     def apply_rgb_full_range(self, src, dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str, out_pix_fmt: str,
                              intermediate_pix_fmt: str, prologue_out_range: Optional[str], matrix: Optional[str],

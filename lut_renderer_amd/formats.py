@@ -915,6 +915,28 @@ def parse_rgb_out(name: Optional[str]):
     return rgb if rgb.packed else parse_pix_fmt(name)
 
 
+def _yuv2rgb_sides(pix_fmt: Optional[str], out_pix_fmt: Optional[str], head: str):
+    """The format checks of a YUV -> RGB pass called `head`: a planar YUV source (yuva* too), an RGB
+    destination, no alpha into a 4-component packed one.  Returns (source `PixFmt`, destination `PixFmt` | packed `RgbSource`)."""
+    if not pix_fmt:
+        raise ValueError(f"{head} needs pix_fmt")
+    name = pix_fmt.replace("yuvj", "yuv")
+    if parse_semi_fmt(name) is not None:
+        raise ValueError(f"{head} takes planar YUV sources: '{pix_fmt}' is a semi-planar container")
+    if parse_packed_yuv_fmt(name) is not None or name in _PACKED_YUV_UNSUPPORTED:
+        raise ValueError(f"{head} takes planar YUV sources: '{pix_fmt}' is a packed 4:2:2 container")
+    if parse_v210_fmt(name) is not None:
+        raise ValueError(f"{head} takes planar YUV sources: '{pix_fmt}' is a v210 container")
+    if parse_rgb_source(name) is not None:
+        raise ValueError(f"{head} takes planar YUV sources: '{pix_fmt}' is an RGB format (use apply_rgb / apply_packed)")
+    fin = parse_pix_fmt(name)
+    fout = parse_rgb_out(out_pix_fmt)
+    if fin.alpha and isinstance(fout, RgbSource) and fout.ncomp == 4:
+        raise ValueError(f"alpha from '{pix_fmt}' into the packed destination '{out_pix_fmt}' is not supported yet (a follow-up): "
+                         f"use gbrap* to carry alpha, or a yuv* name / a 3-component destination to drop it")
+    return fin, fout
+
+
 #: what `apply_yuv_to_rgb` does not take, by keyword -> (its neutral value, what the refusal calls it)
 _YUV2RGB_NOT_TAKEN = {
     "chroma_loc": (None, "sited chroma resampling (chroma_loc)"), "dither": ("none", "dither"),
@@ -940,23 +962,7 @@ def check_yuv2rgb_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str], **
         neutral, what = _YUV2RGB_NOT_TAKEN[k]
         if (v is not None) if neutral is None else (v != neutral):
             raise ValueError(f"{what} is not supported with {head}")
-    if not pix_fmt:
-        raise ValueError(f"{head} needs pix_fmt")
-    name = pix_fmt.replace("yuvj", "yuv")
-    if parse_semi_fmt(name) is not None:
-        raise ValueError(f"{head} takes planar YUV sources: '{pix_fmt}' is a semi-planar container")
-    if parse_packed_yuv_fmt(name) is not None or name in _PACKED_YUV_UNSUPPORTED:
-        raise ValueError(f"{head} takes planar YUV sources: '{pix_fmt}' is a packed 4:2:2 container")
-    if parse_v210_fmt(name) is not None:
-        raise ValueError(f"{head} takes planar YUV sources: '{pix_fmt}' is a v210 container")
-    if parse_rgb_source(name) is not None:
-        raise ValueError(f"{head} takes planar YUV sources: '{pix_fmt}' is an RGB format (use apply_rgb / apply_packed)")
-    fin = parse_pix_fmt(name)
-    fout = parse_rgb_out(out_pix_fmt)
-    if fin.alpha and isinstance(fout, RgbSource) and fout.ncomp == 4:
-        raise ValueError(f"alpha from '{pix_fmt}' into the packed destination '{out_pix_fmt}' is not supported yet (a follow-up): "
-                         f"use gbrap* to carry alpha, or a yuv* name / a 3-component destination to drop it")
-    return fin, fout
+    return _yuv2rgb_sides(pix_fmt, out_pix_fmt, head)
 
 
 # ---------------------------------------------------------------- the stage stack on RGB sources
@@ -1021,6 +1027,53 @@ def check_rgb_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] =
         raise ValueError(f"the two-output pass (out2_pix_fmt) is not supported with {tail}")
     if variant == "vec_lds":
         raise ValueError(f"variant vec_lds is not supported with {tail}: there is no LDS-window kernel for the RGB stack pass")
+    if variant == "vec_global":
+        # what the names of the call say already; sizes, strides and alignment the vector kernel cannot take are the C layer's
+        # (LUTR_EINVAL: it sees the planes)
+        slow = [f"{k}:{m}" for k, m in st if m in ("pyramid", "prism")]
+        if slow:
+            raise ValueError(f"variant vec_global cannot take stage '{slow[0]}' of {tail}: the vector kernel has nearest, trilinear "
+                             f"and tetrahedral")
+        if fin.depth <= 8 and fout.depth > 8:
+            raise ValueError(f"variant vec_global cannot take an 8-bit source ('{pix_fmt}') written as 16-bit words "
+                             f"('{fout.name}') with {tail}: that container mix has no vector kernel")
+    return st, fin, fout
+
+
+# ---------------------------------------------------------------- the stage stack from YUV sources into RGB frames
+def check_yuv2rgb_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str], *, stages, cdl: bool = False,
+                                lut: bool = True, lut2: bool = True, lut1d: bool = True, prelut: bool = False,
+                                rgb_matrix: bool = False, dither: str = "none", engine_dither: Optional[str] = None,
+                                chroma_loc: Optional[str] = None, out_size=None, alpha_mode: str = "straight",
+                                out2_pix_fmt: Optional[str] = None, variant: Optional[str] = None, strength=None, matte=None):
+    """The checks every layer makes of a stage stack from a YUV source into an RGB frame before any GPU work,
+    the one copy of its refusals: everything `check_stage_list` refuses; the format checks of `check_yuv2rgb_options` (a planar
+    YUV source, yuva* too -- a semi-planar, packed 4:2:2 or v210 one by name; an integer RGB destination -- a float one by name;
+    no alpha into a 4-component packed destination); chroma_loc, both dithers, out_size; strength / matte; premultiplied alpha;
+    a second output; the vec_lds variant, and vec_global where the names of the call already say that the vector kernel cannot
+    take it (a pyramid / prism stage, an 8-bit source written as 16-bit words).
+    Returns (parsed stages, source `PixFmt`, destination `PixFmt` | packed `RgbSource`)."""
+    tail = "a stage stack from a YUV source into an RGB frame (rgb_out_stages)"
+    st = check_stage_list(stages, cdl=cdl, lut=lut, lut2=lut2, lut1d=lut1d, prelut=prelut, rgb_matrix=rgb_matrix)
+    fin, fout = _yuv2rgb_sides(pix_fmt, out_pix_fmt, "the stage stack from YUV into RGB (apply_yuv_stack_to_rgb)")
+    if chroma_loc is not None:
+        raise ValueError(f"sited chroma resampling (chroma_loc) is not supported with {tail}")
+    if dither != "none":
+        raise ValueError(f"dither ('{dither}') is not supported with {tail}")
+    if engine_dither is not None:
+        raise ValueError(f"dither (engine_dither='{engine_dither}') is not supported with {tail}")
+    if out_size is not None:
+        raise ValueError(f"a resize (out_size / resolution) is not supported with {tail}")
+    if strength is not None:
+        raise ValueError(f"a LUT strength (strength) is not supported with {tail}")
+    if matte is not None and matte is not False:
+        raise ValueError(f"a matte (matte) is not supported with {tail}")
+    if alpha_mode != "straight":
+        raise ValueError(f"alpha_mode='{alpha_mode}' is not supported with {tail}")
+    if out2_pix_fmt is not None:
+        raise ValueError(f"the two-output pass (out2_pix_fmt) is not supported with {tail}")
+    if variant == "vec_lds":
+        raise ValueError(f"variant vec_lds is not supported with {tail}: there is no LDS-window kernel for the YUV -> RGB stack pass")
     if variant == "vec_global":
         # what the names of the call say already; sizes, strides and alignment the vector kernel cannot take are the C layer's
         # (LUTR_EINVAL: it sees the planes)

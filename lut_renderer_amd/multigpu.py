@@ -29,7 +29,7 @@ import torch
 from . import _native
 from .cube import CubeLut, read_lut, read_lut1d
 from .engine import LutEngine, _fresh_planes, _new_planes, _yuv_out_dtype, chain_args, dual_args
-from .formats import (RgbSource, check_yuv2rgb_options, check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2, check_matte, check_rgb_stack_options, check_stack_options, check_strength,
+from .formats import (RgbSource, check_yuv2rgb_options, check_yuv2rgb_stack_options, check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2, check_matte, check_rgb_stack_options, check_stack_options, check_strength,
                       check_premul_options,
                       packed_frame_width, parse_pix_fmt, parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords,
                       v210_frame_width, yuv_side)
@@ -510,26 +510,47 @@ class LutEngineGroup:
                 raise ValueError("the group owns the row partition")
             fin, fout = check_yuv2rgb_options(pix_fmt, out_pix_fmt, **{k: v for k, v in kw.items() if k not in (
                 "interp", "matrix_in", "range_src", "range_in", "lut")})
-            if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
-                raise ValueError(f"'{fin.name}' takes {fin.nplanes} planes")
-            h, w = src[0].shape[-2], src[0].shape[-1]
-            home = src[0].device
-            lead = tuple(src[0].shape[:-2])
-            packed = isinstance(fout, RgbSource)
-            odt = torch.uint8 if fout.depth <= 8 else torch.int16
-            if dst is None:
-                dst = torch.empty(lead + (h, w, fout.ncomp), dtype=odt, device=home) if packed else \
-                    _new_planes(fout, w, h, lead, odt, home)
-            names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt)
+            return self._yuv2rgb_shards("apply_yuv_to_rgb", src, dst, fin, fout, dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt), kw)
 
-            def local(eng, r0, r1):
-                eng.apply_yuv_to_rgb(src, dst, row0=r0, rows=r1 - r0, **names, **kw)
+    def _yuv2rgb_shards(self, method: str, src, dst, fin, fout, names: dict, kw: dict):
+        """The row shards of `apply_yuv_to_rgb` / `apply_yuv_stack_to_rgb` (`method`) behind their option checks."""
+        if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
+            raise ValueError(f"'{fin.name}' takes {fin.nplanes} planes")
+        h, w = src[0].shape[-2], src[0].shape[-1]
+        home = src[0].device
+        lead = tuple(src[0].shape[:-2])
+        packed = isinstance(fout, RgbSource)
+        odt = torch.uint8 if fout.depth <= 8 else torch.int16
+        if dst is None:
+            dst = torch.empty(lead + (h, w, fout.ncomp), dtype=odt, device=home) if packed else \
+                _new_planes(fout, w, h, lead, odt, home)
 
-            def remote(eng, r0, r1):
-                out = eng.apply_yuv_to_rgb(_travel(src, _row_ranges(fin, r0, r1), eng.device), None, **names, **kw)
-                if packed:                                         # (rows of w * C components: a plane to the copy back)
-                    return [([dst.flatten(-2)], [out.flatten(-2)], [(r0, r1)])]
-                return [(dst, out, _row_ranges(fout, r0, r1))]
+        def local(eng, r0, r1):
+            getattr(eng, method)(src, dst, row0=r0, rows=r1 - r0, **names, **kw)
 
-            self._shard(h, 1 << fin.csy, home, local, remote)
-            return dst
+        def remote(eng, r0, r1):
+            out = getattr(eng, method)(_travel(src, _row_ranges(fin, r0, r1), eng.device), None, **names, **kw)
+            if packed:                                         # (rows of w * C components: a plane to the copy back)
+                return [([dst.flatten(-2)], [out.flatten(-2)], [(r0, r1)])]
+            return [(dst, out, _row_ranges(fout, r0, r1))]
+
+        self._shard(h, 1 << fin.csy, home, local, remote)
+        return dst
+
+    def apply_yuv_stack_to_rgb(self, src: Sequence[torch.Tensor], dst=None, *, pix_fmt: str, out_pix_fmt: str, stages, cdl=None,
+                               rgb_matrix=None, **kw):
+        """`LutEngine.apply_yuv_stack_to_rgb` with the rows of every frame split over the group's devices, as
+        `apply_yuv_to_rgb` splits them (shards on multiples of the source's chroma block height 2^icsy, no halo): the lattices
+        and the 1D LUT are on every engine through the group's setters, the CDL and the matrix travel with the call."""
+        with self._lock:
+            if "row0" in kw or "rows" in kw:
+                raise ValueError("the group owns the row partition")
+            e0 = self.engines[0]
+            refusable = ("dither", "engine_dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength", "matte")
+            st, fin, fout = check_yuv2rgb_stack_options(
+                pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(e0, "n", 0)),
+                lut2=bool(getattr(e0, "n2", 0)), lut1d=bool(self.n1d), prelut=bool(getattr(e0, "_has_prelut", False)),
+                rgb_matrix=rgb_matrix is not None, variant=getattr(e0, "_variant_name", None),
+                **{k: kw[k] for k in refusable if k in kw})
+            names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, stages=st, cdl=cdl, rgb_matrix=rgb_matrix)
+            return self._yuv2rgb_shards("apply_yuv_stack_to_rgb", src, dst, fin, fout, names, kw)

@@ -24,7 +24,7 @@ from .engine import LutEngine
 from .params import strength_keys
 from .formats import (MATTE_PIX_FMTS, RgbSource, check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options,
                       check_lut1d_options, check_stack_options,
-                      check_premul_options, check_rgb_stack_options, check_yuv2rgb_options, parse_rgb_out, parse_rgb_source, parse_size, premul_to_yuv,
+                      check_premul_options, check_rgb_stack_options, check_yuv2rgb_options, check_yuv2rgb_stack_options, parse_rgb_out, parse_rgb_source, parse_size, premul_to_yuv,
                       refuse_alpha_resize, yuv_side, _YUV2RGB_NOT_TAKEN)
 
 
@@ -196,7 +196,7 @@ class HostPipeline:
 
     def __init__(self, engine: LutEngine, pix_fmt: str, width: int, height: int, batch: int = 8, slots: int = 3,
                  out_pix_fmt: Optional[str] = None, out_size=None, second_pix_fmt: Optional[str] = None, chain: bool = False, lut1d: bool = False,
-                 rgb_out: Optional[str] = None, **apply_kw):
+                 rgb_out: Optional[str] = None, rgb_out_stages=None, **apply_kw):
         """`out_size` = (w, h) or "WxH": the engine resizes every frame to it and the output layout has that size.
         `second_pix_fmt`: a second planar YUV output from the same pass with a pinned output ring of its own
         (`fout2`); `run` then takes a second drain.
@@ -214,6 +214,39 @@ class HostPipeline:
         # `apply_kw["rgb_stages"]`: an RGB source through the stage stack -- every batch goes through
         # `apply_rgb_stack` with the lattices and the 1D LUT the engine holds, `apply_kw["cdl"]` and `apply_kw["rgb_matrix"]`, into
         # planar YUV or gbrp* / gbrap* at the source's depth (`out_pix_fmt` None: the latter, for a planar source)
+        # `rgb_out_stages`: with `rgb_out`, every batch goes through `apply_yuv_stack_to_rgb` with the lattices and
+        # the 1D LUT the engine holds, `apply_kw["cdl"]` and `apply_kw["rgb_matrix"]`; the output ring is that of `rgb_out`
+        self.rgb_out_stack = rgb_out_stages is not None
+        if self.rgb_out_stack:
+            if rgb_out is None:
+                raise ValueError("rgb_out_stages is the stage list of a YUV source written as RGB: it needs rgb_out")
+            if apply_kw.get("stages") is not None or apply_kw.get("rgb_stages") is not None:
+                raise ValueError("rgb_out_stages and stages / rgb_stages are mutually exclusive")
+            if out_pix_fmt:
+                raise ValueError(f"rgb_out ('{rgb_out}') and out_pix_fmt ('{out_pix_fmt}') are mutually exclusive")
+            if chain or lut1d:
+                raise ValueError("a stage stack names its lut3d2 / lut1d stages itself: chain / lut1d are not set with rgb_out_stages")
+            refusable = ("dither", "engine_dither", "chroma_loc", "alpha_mode", "strength", "matte")
+            st, _fin, _fout = check_yuv2rgb_stack_options(
+                pix_fmt, rgb_out, stages=rgb_out_stages, cdl=apply_kw.get("cdl") is not None,
+                lut=bool(getattr(engine, "n", 0)), lut2=bool(getattr(engine, "n2", 0)), lut1d=bool(getattr(engine, "n1d", 0)),
+                prelut=bool(getattr(engine, "_has_prelut", False)), rgb_matrix=apply_kw.get("rgb_matrix") is not None,
+                out_size=out_size, out2_pix_fmt=second_pix_fmt, **{k: apply_kw[k] for k in refusable if k in apply_kw})
+            if apply_kw.get("strength_keys") is not None:
+                raise ValueError("a LUT strength (strength_keys) is not supported with a stage stack from a YUV source into an RGB "
+                                 "frame (rgb_out_stages)")
+            self.rgb_stack = self.stack = self.chain = self.lut1d = self.float_out = self.rgb = False
+            self.rgb_out = True
+            self.matte = self.strength_keys = self.fout2 = None
+            self.frames_submitted = 0
+            self.eng = engine
+            self.fin = input_layout(pix_fmt, width, height)
+            self.fout = output_layout(rgb_out, width, height)
+            self.batch, self.slots = int(batch), int(slots)
+            self.kw = dict({k: apply_kw[k] for k in ("cdl", "rgb_matrix", "matrix_in", "range_src", "range_in")
+                            if apply_kw.get(k) is not None}, stages=st, pix_fmt=self.fin.fmt.name, out_pix_fmt=self.fout.fmt.name)
+            self._allocate(engine, slots)
+            return
         self.rgb_stack = apply_kw.get("rgb_stages") is not None
         if self.rgb_stack:
             if apply_kw.get("stages") is not None:
@@ -425,6 +458,8 @@ class HostPipeline:
                 src = self.fin.image_view(self.d_in[slot], nframes) if isinstance(self.fin, PackedFrameLayout) \
                     else self.fin.plane_views(self.d_in[slot], nframes)
                 self.eng.apply_rgb_stack(src, dst, **self.kw)
+            elif self.rgb_out_stack:
+                self.eng.apply_yuv_stack_to_rgb(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
             elif self.rgb_out:
                 self.eng.apply_yuv_to_rgb(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
             elif self.stack:
