@@ -86,6 +86,12 @@ def _cached_cube(path: Path, reader=read_lut) -> CubeLut:
     return lut
 
 
+def _parsed_lut(cube) -> Optional[CubeLut]:
+    """None, the parsed LUT that was given, or the file's -- parsed once and kept, so that the same object comes back the next
+    time and the engine's device copy stands."""
+    return None if cube is None else cube if isinstance(cube, CubeLut) else _cached_cube(Path(cube))
+
+
 def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = None, alpha_mode: str = "straight",
                     rgb_out: Optional[str] = None) -> dict:
     """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv (`pix_fmt` / `out_pix_fmt` planar YUV -- yuva* too, DESIGN.md
@@ -250,8 +256,7 @@ def _stack_resources(st, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, rgb
         raise ValueError("interp2 is the mode of the second LUT: the stage list has no 'lut3d2' stage")
     if cdl is None and cdl_id is not None:
         raise ValueError("cdl_id names a correction inside a CDL file: it needs cdl")
-    lut = None if cube is None else cube if isinstance(cube, CubeLut) else _cached_cube(Path(cube))
-    lut2 = None if cube2 is None else cube2 if isinstance(cube2, CubeLut) else _cached_cube(Path(cube2))
+    lut, lut2 = _parsed_lut(cube), _parsed_lut(cube2)
     check_lut2(lut2)
     if lut1d is not None:
         lut1d = _cached_cube(Path(lut1d), read_lut1d) if isinstance(lut1d, (str, Path)) and Path(lut1d).is_file() else as_lut1d(lut1d)
@@ -265,8 +270,9 @@ def _stack_resources(st, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, rgb
 
 
 def _stack_upload(eng, lut, lut2, lut1d, interp1d, precision) -> None:
-    """The uploads and the precision of one stack task, under the engine's lock: a resource the engine took from the same parsed
-    object last time stands."""
+    """The uploads and the precision of one task of `apply_lut`, under the engine's lock, and the one place that reads the
+    engine's `_applied_*` markers: a resource the engine took from the same parsed object last time (the 1D LUT: and in the same
+    mode) stands, its device copy with it; the engine's own setters clear the markers.  None uploads nothing."""
     if lut is not None and eng._applied_lut is not lut:
         eng.set_lut(lut)
         eng._applied_lut = lut
@@ -282,89 +288,32 @@ def _stack_upload(eng, lut, lut2, lut1d, interp1d, precision) -> None:
         eng.set_precision(precision)
 
 
-def _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, engine, devices, precision,
-                 chroma_loc, out_size, alpha_mode, second_pix_fmt, strength=None, matte=None, rgb_matrix=None):
-    """`apply_lut(stages=...)`: load what the list names, with the caches the single-feature routes use, and
-    route to `apply_yuv_stack`.  `kw` is what `engine_call_for` returned, with `dither` filled in.  `strength`
-    travels to the engine; `stages` None is then the list the other options imply.  `matte`: None, or the dict of
-    the engine's `matte`, `matte_depth` and `matte_invert` arguments, which travels likewise.  `rgb_matrix`: None,
-    an RgbMatrix or the path of a .spimtx file, the resource of a matrix stage."""
+def _stack_route(planes, out, check, entry: str, names, listed, interp, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, rgb_matrix,
+                 engine, devices, precision, refusable: dict, call):
+    """The one route behind `apply_lut`'s three stage lists -- `stages` (DESIGN.md 3.21 .. 3.23, 3.25), `rgb_stages` (3.26) and
+    `rgb_out_stages` (3.27): parse `listed` with `interp` / `interp2` as the modes of the lut3d stages that spell none, load what
+    it names with the caches the single-feature routes use (`_stack_resources`), make the family's `check` of the two format
+    `names` with `refusable` -- the options of the call the pass does not take, or words its messages for, by the check's
+    keyword -- and then, under the engine's lock, upload, set the precision and call the engine's `entry` with the parsed list,
+    the CDL and `call()`: the family's other keywords, made behind the check.  The matrix travels when there is one, or where
+    `call()` names `rgb_matrix` already."""
     from .plan import INTERP_WHITELIST
     mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
-    if stages is None:
-        stages = implied_stages(cube is not None, cube2 is not None, lut1d is not None, cdl is not None)
-    st = parse_stages(stages, interp=kw.get("interp"), interp2=mode2)
-    lut, lut2, lut1d, cdl, rgb_matrix, held, prelut = _stack_resources(st, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id,
-                                                                      rgb_matrix, engine)
-    check_stack_options(kw["pix_fmt"], kw["out_pix_fmt"], stages=st, cdl=cdl is not None, lut=lut is not None or held("n"),
-                        lut2=lut2 is not None or held("n2"), lut1d=lut1d is not None or held("n1d"), prelut=prelut,
-                        dither=kw.get("dither", "none"), chroma_loc=chroma_loc, out_size=out_size, alpha_mode=alpha_mode,
-                        out2_pix_fmt=second_pix_fmt, strength=strength, precision=precision, matte=matte is not None,
-                        rgb_matrix=rgb_matrix is not None)
-    own = engine is None
-    eng = engine if engine is not None else _cached_engine(devices)
-    call = {k: v for k, v in kw.items() if k not in ("dither", "interp", "alpha_mode")}
-    with eng._lock:                 # uploads, precision and launch of ONE task, as in apply_lut
-        _stack_upload(eng, lut, lut2, lut1d, interp1d, precision)
-        if strength is not None:
-            call["strength"] = strength
-        if matte is not None:
-            call.update(matte)
-        if rgb_matrix is not None:
-            call["rgb_matrix"] = rgb_matrix
-        result = eng.apply_yuv_stack(planes, out, stages=st, cdl=cdl, **call)
-        if own:
-            eng.sync()
-    return result
-
-
-def _apply_rgb_stack(planes, out, plan, pix_fmt, out_pix_fmt, rgb_stages, interp, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id,
-                     rgb_matrix, engine, devices, precision, refusable):
-    """`apply_lut(rgb_stages=...)`: load what the list names, with the caches the other routes use, and route to
-    `apply_rgb_stack`.  `refusable`: the options of the call the pass does not take, by `check_rgb_stack_options`' keyword."""
-    from .plan import INTERP_WHITELIST
-    mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
-    st = parse_stages(rgb_stages, interp=interp, interp2=mode2)
+    st = parse_stages(listed, interp=interp, interp2=mode2)
     lut, lut2, lut1d, cdl, rgb_matrix, held, prelut = _stack_resources(st, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id,
                                                                       rgb_matrix, engine)
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
-    check_rgb_stack_options(pix_fmt, out_pix_fmt, stages=st, cdl=cdl is not None, lut=lut is not None or held("n"),
-                            lut2=lut2 is not None or held("n2"), lut1d=lut1d is not None or held("n1d"), prelut=prelut,
-                            rgb_matrix=rgb_matrix is not None,
-                            intermediate_pix_fmt=plan.intermediate_pix_fmt if plan.prologue else None, **refusable)
+    check(*names, stages=st, cdl=cdl is not None, lut=lut is not None or held("n"), lut2=lut2 is not None or held("n2"),
+          lut1d=lut1d is not None or held("n1d"), prelut=prelut, rgb_matrix=rgb_matrix is not None, **refusable)
+    kw = dict(call(), stages=st, cdl=cdl)
+    if rgb_matrix is not None or "rgb_matrix" in kw:
+        kw["rgb_matrix"] = rgb_matrix
     own = engine is None
     eng = engine if engine is not None else _cached_engine(devices)
     with eng._lock:                 # uploads, precision and launch of ONE task, as in apply_lut
         _stack_upload(eng, lut, lut2, lut1d, interp1d, precision)
-        result = eng.apply_rgb_stack(planes, out, pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, stages=st, cdl=cdl, rgb_matrix=rgb_matrix,
-                                     matrix_out=plan.matrix or "smpte170m", range_out="tv")
-        if own:
-            eng.sync()
-    return result
-
-
-def _apply_yuv_stack_to_rgb(planes, out, plan, pix_fmt, rgb_out, rgb_out_stages, interp, cube, cube2, interp2, lut1d, interp1d, cdl,
-                            cdl_id, rgb_matrix, engine, devices, precision, refusable):
-    """`apply_lut(rgb_out=, rgb_out_stages=...)`: load what the list names, with the caches the other routes use,
-    and route to `apply_yuv_stack_to_rgb` with the matrix and ranges `engine_call_for(rgb_out=)` gives the plan.  `refusable`: the
-    options of the call the pass does not take, by `check_yuv2rgb_stack_options`' keyword."""
-    from .plan import INTERP_WHITELIST
-    mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
-    st = parse_stages(rgb_out_stages, interp=interp, interp2=mode2)
-    lut, lut2, lut1d, cdl, rgb_matrix, held, prelut = _stack_resources(st, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id,
-                                                                      rgb_matrix, engine)
-    if precision not in ("strict", "fast", "fma32"):
-        raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
-    check_yuv2rgb_stack_options(pix_fmt, rgb_out, stages=st, cdl=cdl is not None, lut=lut is not None or held("n"),
-                                lut2=lut2 is not None or held("n2"), lut1d=lut1d is not None or held("n1d"), prelut=prelut,
-                                rgb_matrix=rgb_matrix is not None, **refusable)
-    call = {k: v for k, v in engine_call_for(plan, pix_fmt, None, "straight", rgb_out=rgb_out).items() if k != "interp"}
-    own = engine is None
-    eng = engine if engine is not None else _cached_engine(devices)
-    with eng._lock:                 # uploads, precision and launch of ONE task, as in apply_lut
-        _stack_upload(eng, lut, lut2, lut1d, interp1d, precision)
-        result = eng.apply_yuv_stack_to_rgb(planes, out, stages=st, cdl=cdl, rgb_matrix=rgb_matrix, **call)
+        result = getattr(eng, entry)(planes, out, **kw)
         if own:
             eng.sync()
     return result
@@ -556,17 +505,21 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     # (the plan only carries the path into the filter string / notes; a parsed CubeLut or an engine that already holds the
     # lattice has none)
     plan = resolve_lut_plan(params, cube if isinstance(cube, (str, Path)) else "engine.cube", info)
+    # (what every stage-stack route loads from, and where it runs: `_stack_route`'s arguments behind the list and its modes)
+    loaded = (cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, rgb_matrix, engine, devices, precision)
+    # ffmpeg.py:305-307: any value other than "error_diffusion" leaves the chain without a dither filter
+    zdither = "error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none"
     if rgb_stages is not None:
         # the stage stack on an RGB source: a route of its own
-        dither = "error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none"
-        if engine_dither is not None:
-            dither = resolve_engine_dither(engine_dither, dither)
+        dither = zdither if engine_dither is None else resolve_engine_dither(engine_dither, zdither)
         if rgb_out is not None:
             raise ValueError(f"rgb_out ('{rgb_out}') names the RGB output of a YUV source: with rgb_stages the output is out_pix_fmt")
-        result = _apply_rgb_stack(planes, out, plan, pix_fmt, out_pix_fmt, rgb_stages, interp, cube, cube2, interp2, lut1d, interp1d,
-                                  cdl, cdl_id, rgb_matrix, engine, devices, precision,
-                                  dict(dither=dither, chroma_loc=chroma_loc, out_size=out_size, alpha_mode=alpha_mode,
-                                       out2_pix_fmt=second_pix_fmt, strength=strength, matte=matte))
+        result = _stack_route(
+            planes, out, check_rgb_stack_options, "apply_rgb_stack", (pix_fmt, out_pix_fmt), rgb_stages, interp, *loaded,
+            dict(dither=dither, chroma_loc=chroma_loc, out_size=out_size, alpha_mode=alpha_mode, out2_pix_fmt=second_pix_fmt,
+                 strength=strength, matte=matte, intermediate_pix_fmt=plan.intermediate_pix_fmt if plan.prologue else None),
+            lambda: dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, rgb_matrix=None, matrix_out=plan.matrix or "smpte170m",
+                         range_out="tv"))
         return result, output_color_tags(plan.output_policy)
     if rgb_out is not None:
         # YUV in, RGB out: a route of its own, with none of the options below
@@ -575,38 +528,33 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
             if out_pix_fmt:
                 raise ValueError(f"rgb_out ('{rgb_out}') and out_pix_fmt ('{out_pix_fmt}') are mutually exclusive: a call has one "
                                  f"output")
-            dither = "error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none"
-            refusable = dict(dither=dither, engine_dither=engine_dither, chroma_loc=chroma_loc, out_size=out_size,
+            refusable = dict(dither=zdither, engine_dither=engine_dither, chroma_loc=chroma_loc, out_size=out_size,
                              alpha_mode=alpha_mode, out2_pix_fmt=second_pix_fmt, strength=strength, matte=matte)
-            result = _apply_yuv_stack_to_rgb(planes, out, plan, pix_fmt, rgb_out, rgb_out_stages, interp, cube, cube2, interp2, lut1d,
-                                             interp1d, cdl, cdl_id, rgb_matrix, engine, devices, precision, refusable)
+            # (the matrix and the ranges are those `engine_call_for(rgb_out=)` gives the plan)
+            result = _stack_route(
+                planes, out, check_yuv2rgb_stack_options, "apply_yuv_stack_to_rgb", (pix_fmt, rgb_out), rgb_out_stages, interp,
+                *loaded, refusable, lambda: dict({k: v for k, v in engine_call_for(plan, pix_fmt, None, "straight",
+                                                                                  rgb_out=rgb_out).items() if k != "interp"},
+                                                 rgb_matrix=None))
             return result, output_color_tags(plan.output_policy)
         kw = engine_call_for(plan, pix_fmt, out_pix_fmt, alpha_mode, rgb_out=rgb_out)
         check_yuv2rgb_options(pix_fmt, rgb_out, chroma_loc=chroma_loc, engine_dither=engine_dither, out_size=out_size,
-                              dither="error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none",
-                              cdl=cdl, lut1d=lut1d, stages=stages, strength=strength, matte=matte, out2_pix_fmt=second_pix_fmt,
+                              dither=zdither, cdl=cdl, lut1d=lut1d, stages=stages, strength=strength, matte=matte, out2_pix_fmt=second_pix_fmt,
                               cube2=cube2, interp2=interp2)
         if precision not in ("strict", "fast", "fma32"):
             raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
         own = engine is None
         eng = engine if engine is not None else _cached_engine(devices)
-        lut = None if cube is None else cube if isinstance(cube, CubeLut) else _cached_cube(Path(cube))
+        lut = _parsed_lut(cube)
         with eng._lock:             # upload, precision and launch of ONE task, as below
-            if lut is not None and eng._applied_lut is not lut:
-                eng.set_lut(lut)
-                eng._applied_lut = lut
-            if eng.precision != precision:
-                eng.set_precision(precision)
+            _stack_upload(eng, lut, None, None, interp1d, precision)
             result = eng.apply_yuv_to_rgb(planes, out, **kw)
             if own:
                 eng.sync()
         return result, output_color_tags(plan.output_policy)
     kw = engine_call_for(plan, pix_fmt, out_pix_fmt, alpha_mode)
     refuse_alpha_resize(kw.get("out_pix_fmt"), out_size)        # (the resize takes three planes)
-    # ffmpeg.py:305-307: any value other than "error_diffusion" leaves the chain without a dither filter
-    kw["dither"] = "error_diffusion" if getattr(params, "zscale_dither", "none") == "error_diffusion" else "none"
-    if engine_dither is not None:
-        kw["dither"] = resolve_engine_dither(engine_dither, kw["dither"])
+    kw["dither"] = zdither if engine_dither is None else resolve_engine_dither(engine_dither, zdither)
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
     if cube2 is None and interp2 is not None:
@@ -618,10 +566,20 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     if matte is None and (matte_depth is not None or matte_invert is not False):
         raise ValueError("matte_depth / matte_invert describe a matte: they need matte")
     if stages is not None or strength is not None or matte is not None:
-        result = _apply_stack(planes, out, kw, stages, cube, cube2, interp2, lut1d, interp1d, cdl, cdl_id, engine, devices, precision,
-                              chroma_loc, out_size, alpha_mode, second_pix_fmt, strength,
-                              None if matte is None else dict(matte=matte, matte_depth=matte_depth, matte_invert=matte_invert),
-                              rgb_matrix)
+        # the stage stack: with a strength (3.22) or a matte (3.23) and no `stages`, the list the other options
+        # imply; both travel to the engine with what `engine_call_for` returned
+        if stages is None:
+            stages = implied_stages(cube is not None, cube2 is not None, lut1d is not None, cdl is not None)
+        call = {k: v for k, v in kw.items() if k not in ("dither", "interp", "alpha_mode")}
+        if strength is not None:
+            call["strength"] = strength
+        if matte is not None:
+            call.update(matte=matte, matte_depth=matte_depth, matte_invert=matte_invert)
+        result = _stack_route(
+            planes, out, check_stack_options, "apply_yuv_stack", (kw["pix_fmt"], kw["out_pix_fmt"]), stages, kw.get("interp"),
+            *loaded, dict(dither=kw["dither"], chroma_loc=chroma_loc, out_size=out_size, alpha_mode=alpha_mode,
+                          out2_pix_fmt=second_pix_fmt, strength=strength, precision=precision, matte=matte is not None),
+            lambda: call)
         return result, output_color_tags(plan.output_policy)
     if lut1d is not None:
         check_lut1d_options(kw["pix_fmt"], kw["out_pix_fmt"], interp1d=interp1d, dither=kw["dither"], chroma_loc=chroma_loc,
@@ -634,7 +592,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     if cdl is not None:
         cdl = as_cdl(cdl, cdl_id)
         # (a parsed LUT tells whether it carries a prelut; an engine that already holds the lattice knows it of its own)
-        held = cube if isinstance(cube, CubeLut) else _cached_cube(Path(cube)) if cube is not None else None
+        held = _parsed_lut(cube)
         prelut = getattr(held, "prelut", None) is not None if held is not None else bool(getattr(engine, "_has_prelut", False))
         check_cdl_options(kw["pix_fmt"], kw["out_pix_fmt"], dither=kw["dither"], chroma_loc=chroma_loc, out_size=out_size,
                           alpha_mode=alpha_mode, out2_pix_fmt=second_pix_fmt, lut2=cube2 is not None, prelut=prelut)
@@ -667,26 +625,11 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
             raise ValueError("a float output needs a single device")
     own = engine is None
     eng = engine if engine is not None else _cached_engine(devices)
-    lut = lut2 = None
-    if cube is not None:
-        lut = cube if isinstance(cube, CubeLut) else _cached_cube(Path(cube))
-    if cube2 is not None:
-        lut2 = cube2 if isinstance(cube2, CubeLut) else _cached_cube(Path(cube2))
-        check_lut2(lut2)
+    lut, lut2 = _parsed_lut(cube), _parsed_lut(cube2)
+    check_lut2(lut2)
     with eng._lock:                 # upload, precision and launch of ONE task: no other thread's call gets in between
-        if lut is not None and eng._applied_lut is not lut:      # same parsed LUT as last time: the device copy stands
-            eng.set_lut(lut)                                     # (set_lut itself clears the marker)
-            eng._applied_lut = lut
-        if lut2 is not None and eng._applied_lut2 is not lut2:   # the same shortcut for the second LUT, on its own marker
-            eng.set_lut2(lut2)
-            eng._applied_lut2 = lut2
-        if eng.precision != precision:
-            eng.set_precision(precision)
+        _stack_upload(eng, lut, lut2, lut1d, interp1d, precision)
         if lut1d is not None:
-            held = eng._applied_lut1d                            # the same parsed 1D LUT and mode as last time: the table stands
-            if not (held is not None and held[0] is lut1d and held[1] == interp1d):
-                eng.set_lut1d(lut1d, interp1d)                   # (set_lut1d itself clears the marker)
-                eng._applied_lut1d = (lut1d, interp1d)
             # (cube=None with a 1D LUT is lut1d alone, whatever lattice the engine holds)
             kw1 = {k: v for k, v in kw.items() if k != "dither"}
             result = eng.apply_yuv_lut1d(planes, out, **dict(kw1, interp=kw1["interp"] if cube is not None else None))

@@ -190,73 +190,11 @@ def rgb_matrix_from_args(args):
     return read_rgb_matrix(path) if path is not None else RgbMatrix.from_text(m, off)
 
 
-def stack_call_from_args(args, kw: dict, cdl) -> dict:
-    """The keyword arguments of `apply_yuv_stack` for --stages (DESIGN.md 3.21) from those `engine_call_for` returned: the stage
-    list parsed with --interp / --interp2 as the lut3d stages' defaults, every refusal of `check_stack_options`, and a file for
-    every stage and a stage for every file.  With --strength / --strength-keys (DESIGN.md 3.22) and no --stages the list is the
-    one the other options imply (`formats.implied_stages`); `strength` or `strength_keys` (the parsed callable) go into the call.
-    With --matte (DESIGN.md 3.23) likewise; `matte` (the path), `matte_pix_fmt` and `matte_invert` go into the call.  With
-    --rgb-matrix / --rgb-matrix-file (DESIGN.md 3.25) `rgb_matrix` goes into the call; it needs --stages with a matrix stage."""
-    from .plan import INTERP_WHITELIST
-    interp2 = getattr(args, "interp2", None)
-    mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
-    cube2, lut1d = getattr(args, "cube2", None), getattr(args, "lut1d", None)
-    strength, keys = strength_from_args(args)
-    matte = matte_from_args(args)
-    mtx = rgb_matrix_from_args(args)
-    listed = getattr(args, "stages", None)
-    if mtx is not None and listed is None:
-        raise ValueError("--rgb-matrix / --rgb-matrix-file need --stages: a matrix stage has no implied position "
-                         "(e.g. --stages lut1d,matrix,lut3d)")
-    if listed is None:
-        listed = implied_stages(args.cube is not None, cube2 is not None, lut1d is not None, cdl is not None)
-    st = parse_stages(listed, interp=kw.get("interp"), interp2=mode2)
-    kinds = [k for k, _m in st]
-    for flag, given, kind in (("--cube", args.cube, "lut3d"), ("--cube2", cube2, "lut3d2"), ("--lut1d", lut1d, "lut1d"),
-                              ("--cdl / --cdl-sop / --cdl-sat", cdl, "cdl"), ("--rgb-matrix / --rgb-matrix-file", mtx, "matrix")):
-        if given is not None and kind not in kinds:
-            raise ValueError(f"{flag} is given and --stages has no '{kind}' stage")
-    if interp2 is not None and "lut3d2" not in kinds:
-        raise ValueError("--interp2 is the mode of the second LUT: --stages has no 'lut3d2' stage")
-    interp1d = getattr(args, "interp1d", None) or "linear"
-    from . import _native
-    if interp1d not in _native.INTERP1D:
-        raise ValueError(f"lut1d has no interpolation mode '{interp1d}' ({' | '.join(_native.INTERP1D)})")
-    prelut = False
-    if ("cdl" in kinds or "matrix" in kinds) and args.cube is not None and os.path.isfile(args.cube):
-        from pathlib import Path
-        from . import engine  # noqa: F401  (torch first, as in plan_from_args)
-        from .api import _cached_cube
-        prelut = getattr(_cached_cube(Path(args.cube)), "prelut", None) is not None
-    second_out, second_fmt = getattr(args, "second_output", None), getattr(args, "second_pix_fmt", None)
-    engine_dither = getattr(args, "engine_dither", None)
-    check_stack_options(kw["pix_fmt"], kw["out_pix_fmt"], stages=st, cdl=cdl is not None, lut=args.cube is not None,
-                        lut2=cube2 is not None, lut1d=lut1d is not None, prelut=prelut,
-                        dither="error_diffusion" if args.zscale_dither == "error_diffusion" else engine_dither or "none",
-                        chroma_loc=getattr(args, "chroma_loc", None), out_size=getattr(args, "out_size", None),
-                        alpha_mode=getattr(args, "alpha_mode", None) or "straight",
-                        out2_pix_fmt=second_fmt if second_fmt is not None else second_out,
-                        strength=strength if keys is None else 1.0, precision=getattr(args, "precision", None),
-                        matte=matte is not None, rgb_matrix=mtx is not None)
-    call = {k: v for k, v in kw.items() if k not in ("interp", "alpha_mode", "dither")}
-    call["stages"] = st
-    if cdl is not None:
-        call["cdl"] = cdl
-    if mtx is not None:
-        call["rgb_matrix"] = mtx
-    if strength is not None:
-        call["strength"] = strength
-    if keys is not None:
-        call["strength_keys"] = keys
-    if matte is not None:
-        call.update(matte)
-    return call
-
-
-def _stage_list_from_args(args, plan, flag: str, text) -> dict:
-    """What --rgb-stages and --rgb-out-stages (`flag`, its value `text`) share: the list parsed with --interp / --interp2 as the
-    lut3d stages' defaults, a file for every stage and a stage for every file, and what `check_stage_list` and the option checks
-    are told -- dict(stages, cdl, rgb_matrix, list=the keywords of `check_stage_list`, options=those of the refusals by name)."""
+def _stage_list_from_args(args, interp, flag: str, text) -> dict:
+    """What --stages, --rgb-stages and --rgb-out-stages (`flag`, its value `text`) share: the list parsed with `interp` (--interp
+    as the plan resolved it) / --interp2 as the lut3d stages' defaults, a file for every stage and a stage for every file, and
+    what `check_stage_list` and the option checks are told -- dict(stages, cdl, rgb_matrix, mix=the strength, key frames and
+    matte that travel with a --stages call, list=the keywords of `check_stage_list`, options=those of the refusals by name)."""
     from .plan import INTERP_WHITELIST
     interp2 = getattr(args, "interp2", None)
     mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
@@ -264,7 +202,7 @@ def _stage_list_from_args(args, plan, flag: str, text) -> dict:
     cdl, mtx = cdl_from_args(args), rgb_matrix_from_args(args)
     strength, keys = strength_from_args(args)
     matte = matte_from_args(args)
-    st = parse_stages(text, interp=plan.interp, interp2=mode2)
+    st = parse_stages(text, interp=interp, interp2=mode2)
     kinds = [k for k, _m in st]
     for opt, given, kind in (("--cube", args.cube, "lut3d"), ("--cube2", cube2, "lut3d2"), ("--lut1d", lut1d, "lut1d"),
                              ("--cdl / --cdl-sop / --cdl-sat", cdl, "cdl"), ("--rgb-matrix / --rgb-matrix-file", mtx, "matrix")):
@@ -283,14 +221,47 @@ def _stage_list_from_args(args, plan, flag: str, text) -> dict:
         from .api import _cached_cube
         prelut = getattr(_cached_cube(Path(args.cube)), "prelut", None) is not None
     second_out, second_fmt = getattr(args, "second_output", None), getattr(args, "second_pix_fmt", None)
+    mix = dict(matte or {})
+    mix.update({k: v for k, v in (("strength", strength), ("strength_keys", keys)) if v is not None})
     return dict(
-        stages=st, cdl=cdl, rgb_matrix=mtx,
+        stages=st, cdl=cdl, rgb_matrix=mtx, mix=mix,
         list=dict(cdl=cdl is not None, lut=args.cube is not None, lut2=cube2 is not None, lut1d=lut1d is not None, prelut=prelut,
                   rgb_matrix=mtx is not None),
         options=dict(chroma_loc=getattr(args, "chroma_loc", None), out_size=getattr(args, "out_size", None),
                      alpha_mode=getattr(args, "alpha_mode", None) or "straight",
                      out2_pix_fmt=second_fmt if second_fmt is not None else second_out,
                      strength=strength if keys is None else 1.0, matte=matte is not None))
+
+
+def _stack_call(call: dict, r: dict, list_kw: str) -> dict:
+    """`call` with what `_stage_list_from_args` resolved (`r`): the parsed list under `list_kw`, the CDL and the matrix where
+    there is one."""
+    call[list_kw] = r["stages"]
+    call.update({k: r[k] for k in ("cdl", "rgb_matrix") if r[k] is not None})
+    return call
+
+
+def stack_call_from_args(args, kw: dict, cdl) -> dict:
+    """The keyword arguments of `apply_yuv_stack` for --stages (DESIGN.md 3.21) from those `engine_call_for` returned: the stage
+    list parsed with --interp / --interp2 as the lut3d stages' defaults, every refusal of `check_stack_options`, and a file for
+    every stage and a stage for every file.  With --strength / --strength-keys (DESIGN.md 3.22) and no --stages the list is the
+    one the other options imply (`formats.implied_stages`); `strength` or `strength_keys` (the parsed callable) go into the call.
+    With --matte (DESIGN.md 3.23) likewise; `matte` (the path), `matte_pix_fmt` and `matte_invert` go into the call.  With
+    --rgb-matrix / --rgb-matrix-file (DESIGN.md 3.25) `rgb_matrix` goes into the call; it needs --stages with a matrix stage."""
+    listed = getattr(args, "stages", None)
+    if listed is None:
+        if rgb_matrix_from_args(args) is not None:
+            raise ValueError("--rgb-matrix / --rgb-matrix-file need --stages: a matrix stage has no implied position "
+                             "(e.g. --stages lut1d,matrix,lut3d)")
+        listed = implied_stages(args.cube is not None, getattr(args, "cube2", None) is not None,
+                                getattr(args, "lut1d", None) is not None, cdl is not None)
+    r = _stage_list_from_args(args, kw.get("interp"), "--stages", listed)
+    check_stack_options(kw["pix_fmt"], kw["out_pix_fmt"], stages=r["stages"], **r["list"],
+                        dither="error_diffusion" if args.zscale_dither == "error_diffusion"
+                        else getattr(args, "engine_dither", None) or "none",
+                        precision=getattr(args, "precision", None), **r["options"])
+    call = {k: v for k, v in kw.items() if k not in ("interp", "alpha_mode", "dither")}
+    return dict(_stack_call(call, r, "stages"), **r["mix"])
 
 
 def rgb_stack_call_from_args(args, plan) -> dict:
@@ -303,18 +274,13 @@ def rgb_stack_call_from_args(args, plan) -> dict:
                          "that of an RGB source")
     if getattr(args, "rgb_out", None) is not None:
         raise ValueError("--rgb-out names the RGB output of a YUV source: with --rgb-stages the output is --out-pix-fmt")
-    r = _stage_list_from_args(args, plan, "--rgb-stages", args.rgb_stages)
-    st, cdl, mtx = r["stages"], r["cdl"], r["rgb_matrix"]
+    r = _stage_list_from_args(args, plan.interp, "--rgb-stages", args.rgb_stages)
     _st, _fin, fout = check_rgb_stack_options(
-        args.pix_fmt, args.out_pix_fmt, stages=st, **r["list"],
+        args.pix_fmt, args.out_pix_fmt, stages=r["stages"], **r["list"],
         dither="error_diffusion" if args.zscale_dither == "error_diffusion" else getattr(args, "engine_dither", None) or "none",
         intermediate_pix_fmt=plan.intermediate_pix_fmt if plan.prologue else None, **r["options"])
-    call = dict(pix_fmt=args.pix_fmt, out_pix_fmt=fout.name, rgb_stages=st, matrix_out=plan.matrix or "smpte170m", range_out="tv")
-    if cdl is not None:
-        call["cdl"] = cdl
-    if mtx is not None:
-        call["rgb_matrix"] = mtx
-    return call
+    return _stack_call(dict(pix_fmt=args.pix_fmt, out_pix_fmt=fout.name, matrix_out=plan.matrix or "smpte170m", range_out="tv"),
+                       r, "rgb_stages")
 
 
 def rgb_out_stack_call_from_args(args, plan) -> dict:
@@ -330,17 +296,12 @@ def rgb_out_stack_call_from_args(args, plan) -> dict:
     if args.out_pix_fmt:
         raise ValueError(f"rgb_out ('{args.rgb_out}') and out_pix_fmt ('{args.out_pix_fmt}') are mutually exclusive: a call has one "
                          f"output")
-    r = _stage_list_from_args(args, plan, "--rgb-out-stages", args.rgb_out_stages)
+    r = _stage_list_from_args(args, plan.interp, "--rgb-out-stages", args.rgb_out_stages)
     check_yuv2rgb_stack_options(args.pix_fmt, args.rgb_out, stages=r["stages"], **r["list"],
                                 dither="error_diffusion" if args.zscale_dither == "error_diffusion" else "none",
                                 engine_dither=getattr(args, "engine_dither", None), **r["options"])
     call = {k: v for k, v in engine_call_for(plan, args.pix_fmt, None, "straight", rgb_out=args.rgb_out).items() if k != "interp"}
-    call["rgb_out_stages"] = r["stages"]
-    if r["cdl"] is not None:
-        call["cdl"] = r["cdl"]
-    if r["rgb_matrix"] is not None:
-        call["rgb_matrix"] = r["rgb_matrix"]
-    return call
+    return _stack_call(call, r, "rgb_out_stages")
 
 
 def matte_from_args(args):

@@ -485,30 +485,22 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                                   ("cdl", cdl, "cdl"), ("rgb_matrix", rgb_matrix, "matrix")):
             if given is not None and kind not in kinds:
                 raise ValueError(f"{name} is given and the stage list has no '{kind}' stage")
+        # what the three families' checks are told alike; each adds its own dither, and what only it takes
+        told = dict(stages=st, cdl=cdl is not None, lut=True, lut2=cube2 is not None, lut1d=lut1d is not None,
+                    rgb_matrix=rgb_matrix is not None, chroma_loc=chroma_loc, out_size=params.resolution if "--out-size" in cmd else None,
+                    alpha_mode=alpha_mode, out2_pix_fmt=second_pix_fmt,
+                    strength=(strength if strength_keys is None else 1.0) if mixed else None, matte=matte is not None)
+        src_fmt = str(source_info.pix_fmt)
         if rgb_out_stages is not None:
             from .api import engine_call_for
-            check_yuv2rgb_stack_options(str(source_info.pix_fmt), rgb_out, stages=st, cdl=cdl is not None, lut=True,
-                                        lut2=cube2 is not None, lut1d=lut1d is not None, rgb_matrix=rgb_matrix is not None,
-                                        dither="error_diffusion" if dither == "error_diffusion" else "none",
-                                        engine_dither=engine_dither, chroma_loc=chroma_loc,
-                                        out_size=params.resolution if "--out-size" in cmd else None, alpha_mode=alpha_mode,
-                                        out2_pix_fmt=second_pix_fmt,
-                                        strength=(strength if strength_keys is None else 1.0) if mixed else None,
-                                        matte=matte is not None)
-            engine_call_for(plan, str(source_info.pix_fmt), None, "straight", rgb_out=rgb_out)   # (a full-range source: 8 bit only)
+            check_yuv2rgb_stack_options(src_fmt, rgb_out, dither="error_diffusion" if dither == "error_diffusion" else "none",
+                                        engine_dither=engine_dither, **told)
+            engine_call_for(plan, src_fmt, None, "straight", rgb_out=rgb_out)               # (a full-range source: 8 bit only)
         elif rgb_stages is not None:
-            check_rgb_stack_options(str(source_info.pix_fmt), pix_fmt or None, stages=st, cdl=cdl is not None, lut=True,
-                                    lut2=cube2 is not None, lut1d=lut1d is not None, rgb_matrix=rgb_matrix is not None, dither=dither,
-                                    chroma_loc=chroma_loc, out_size=params.resolution if "--out-size" in cmd else None,
-                                    alpha_mode=alpha_mode, out2_pix_fmt=second_pix_fmt,
-                                    strength=(strength if strength_keys is None else 1.0) if mixed else None,
-                                    matte=matte is not None, intermediate_pix_fmt=plan.intermediate_pix_fmt if plan.prologue else None)
+            check_rgb_stack_options(src_fmt, pix_fmt or None, dither=dither,
+                                    intermediate_pix_fmt=plan.intermediate_pix_fmt if plan.prologue else None, **told)
         else:
-            check_stack_options(str(source_info.pix_fmt).replace("yuvj", "yuv"), pix_fmt or None, stages=st, cdl=cdl is not None,
-                                lut=True, lut2=cube2 is not None, lut1d=lut1d is not None, dither=dither, chroma_loc=chroma_loc,
-                                out_size=params.resolution if "--out-size" in cmd else None, alpha_mode=alpha_mode,
-                                out2_pix_fmt=second_pix_fmt, strength=(strength if strength_keys is None else 1.0) if mixed else None,
-                                precision=precision, matte=matte is not None, rgb_matrix=rgb_matrix is not None)
+            check_stack_options(src_fmt.replace("yuvj", "yuv"), pix_fmt or None, dither=dither, precision=precision, **told)
         if rgb_matrix is not None:
             from .rgbmatrix import RgbMatrix
             if isinstance(rgb_matrix, RgbMatrix):

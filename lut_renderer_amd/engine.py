@@ -28,13 +28,34 @@ from .formats import (_ALPHA_RESIZE, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, V
                       check_lut1d_options, check_matte, check_rgb_stack_options, check_stack_options, check_strength, check_yuv2rgb_options, check_yuv2rgb_stack_options,
                       check_container_options,
                       check_dual_options, check_lut2, check_packed_options, check_premul_options, check_semi_options,
-                      chroma_loc_code, dual_side, has_prologue, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt,
+                      chroma_loc_code, dual_side, has_prologue, held_resources, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt,
                       parse_rgb_source, parse_semi_fmt, parse_size, parse_v210_fmt, refuse_alpha_resize, refuse_chain_keywords,
                       refuse_dual_keywords, source_bit_depth, v210_frame_width, yuv_side)
 
 _NOT_TENSORS = "planes must be torch tensors resident on the engine's GPU"
 #: what a planar side with the wrong number of planes is told
 _PLANE_COUNT = {3: "expected three planes", 4: "'{}' takes four planes: the three colour planes and alpha"}
+
+
+def _stack_front(eng, entry: str, check, allowed: Tuple[str, ...], pix_fmt, out_pix_fmt, stages, cdl, rgb_matrix, other: dict,
+                 variant: bool = True, **told):
+    """What the three stack entries (`entry`: the name of the one calling) do before they look at a plane: TypeError for a
+    keyword of `other` that is not one of `allowed` -- the options the family's `check` refuses by name -- and for a `cdl` /
+    `rgb_matrix` of the wrong type; then `check` with what `eng` holds (`held_resources`; its variant too unless `variant` is
+    False), `other` and `told`.  Returns (parsed stages, source format, destination format, (the stage array, its length, the
+    CDL's pointer | None, the matrix's pointer | None) as the C entries take them)."""
+    for k in other:
+        if k not in allowed:
+            raise TypeError(f"{entry}() got an unexpected keyword argument '{k}'")
+    if cdl is not None and not isinstance(cdl, Cdl):
+        raise TypeError(f"cdl must be a lut_renderer_amd.cdl.Cdl, not {type(cdl).__name__}")
+    if rgb_matrix is not None and not isinstance(rgb_matrix, RgbMatrix):
+        raise TypeError(f"rgb_matrix must be a lut_renderer_amd.rgbmatrix.RgbMatrix, not {type(rgb_matrix).__name__}")
+    st, fin, fout = check(pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, rgb_matrix=rgb_matrix is not None,
+                          **held_resources(eng, variant), **other, **told)
+    k = None if cdl is None else C.byref(_native.cdl_struct(cdl))
+    m = None if rgb_matrix is None else C.byref(_native.rgb_matrix_struct(rgb_matrix))
+    return st, fin, fout, (_native.stage_array(st), len(st), k, m)
 
 
 def _source_frame(src, fin: PixFmt) -> Tuple[int, int]:
@@ -540,6 +561,35 @@ class LutEngine:
                     self._alpha_plane(a_src, planes[3], din, fmt.depth, w, h, row0, rows, slot, after=self.last_kernel)
         return out
 
+    def _yuva_call(self, colour, src, dst, fin: PixFmt, fout: PixFmt, prologue: bool, row0: int, rows: Optional[int]):
+        """The yuva* path of an entry that takes planar YUV on both sides: the planes checked, the destination
+        allocated when none is given, then `colour(src[:3], dst[:3], source name, output name)` -- the entry itself on the colour
+        planes under their three-plane names -- and the alpha plane on the same stream (`_alpha_tail`).  Straight alpha goes past
+        everything the colour call does; with `prologue` (the call has one) the output's alpha is filled.  Returns `dst`."""
+        if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
+            raise ValueError(_PLANE_COUNT[fin.nplanes].format(fin.name))
+        h, w = src[0].shape[-2], src[0].shape[-1]
+        _check_planes(src, fin, w, h, "source")
+        if dst is None:
+            dst = _fresh_planes(fout, w, h, src[0], self.device)
+        _check_planes(dst, fout, w, h, "destination")
+        a_src = src[3] if fin.alpha and not prologue else None
+        if fout.alpha:
+            _check_alpha_overlap(a_src, fin.depth, dst, fout.depth)
+        self._alpha_tail(lambda: colour(src[:3], dst[:3], fin.colour.name, fout.colour.name), [(fout, dst)], a_src, fin.depth, w, h,
+                         row0, rows)
+        return dst
+
+    def _upload_frame_strength(self, strength: np.ndarray) -> C.c_void_p:
+        """One float per frame on the device, on the stream the kernel reads it from; the engine keeps it until the next one
+        replaces it (torch's allocator hands the old one's memory out again in stream order; a context on a stream of its own is
+        waited for first, so that the previous array is not recycled under a running kernel).  Called under the lock, after
+        `_bind_stream`."""
+        if not self.use_torch_stream and self._frame_strength is not None:
+            self.sync()
+        self._frame_strength = torch.from_numpy(strength).to(self.device)
+        return C.c_void_p(self._frame_strength.data_ptr())
+
     def tile_stats(self, enable: bool = True) -> dict:
         """Counters of the LDS-window kernels since the previous call; (re)arms collection."""
         out = (C.c_uint64 * 8)()
@@ -886,21 +936,10 @@ class LutEngine:
         if fin.alpha or fout.alpha:
             # yuva*: the colour planes through this very call under their three-plane names, then the alpha plane on the same
             # stream, exactly as the CDL call does
-            if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
-                raise ValueError(_PLANE_COUNT[fin.nplanes].format(fin.name))
-            h, w = src[0].shape[-2], src[0].shape[-1]
-            _check_planes(src, fin, w, h, "source")
-            if dst is None:
-                dst = _fresh_planes(fout, w, h, src[0], self.device)
-            _check_planes(dst, fout, w, h, "destination")
-            a_src = src[3] if fin.alpha and not has_prologue(fin.depth, range_src, range_in, lut_depth) else None
-            if fout.alpha:
-                _check_alpha_overlap(a_src, fin.depth, dst, fout.depth)
-            self._alpha_tail(lambda: self.apply_yuv_lut1d(
-                src[:3], dst[:3], pix_fmt=fin.colour.name, out_pix_fmt=fout.colour.name, interp=interp, matrix_in=matrix_in,
-                matrix_out=matrix_out, range_src=range_src, range_in=range_in, range_out=range_out, lut_depth=lut_depth, row0=row0,
-                rows=rows), [(fout, dst)], a_src, fin.depth, w, h, row0, rows)
-            return dst
+            return self._yuva_call(lambda s3, d3, name, out_name: self.apply_yuv_lut1d(
+                s3, d3, pix_fmt=name, out_pix_fmt=out_name, interp=interp, matrix_in=matrix_in, matrix_out=matrix_out,
+                range_src=range_src, range_in=range_in, range_out=range_out, lut_depth=lut_depth, row0=row0, rows=rows),
+                src, dst, fin, fout, has_prologue(fin.depth, range_src, range_in, lut_depth), row0, rows)
         p = _yuv_call_params(fin, fout, lut_depth, matrix_in, matrix_out, range_src, range_in, range_out)
         h, w = src[0].shape[-2], src[0].shape[-1]
         if dst is None:
@@ -949,39 +988,17 @@ class LutEngine:
         fed unit floats as behind the CDL; lut1d, cdl and the end of the list round to codes first.  The call goes to
         lutr_apply_yuv_stack_matrix when a matrix stage is listed and only then; a matrix without its stage, a stage without its
         matrix and a strength or matte together with the stage are ValueErrors."""
-        for k in other:
-            if k not in ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt"):
-                raise TypeError(f"apply_yuv_stack() got an unexpected keyword argument '{k}'")
-        if cdl is not None and not isinstance(cdl, Cdl):
-            raise TypeError(f"cdl must be a lut_renderer_amd.cdl.Cdl, not {type(cdl).__name__}")
-        if rgb_matrix is not None and not isinstance(rgb_matrix, RgbMatrix):
-            raise TypeError(f"rgb_matrix must be a lut_renderer_amd.rgbmatrix.RgbMatrix, not {type(rgb_matrix).__name__}")
-        st, fin, fout = check_stack_options(
-            pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(self, "n", 0)),
-            lut2=bool(getattr(self, "n2", 0)), lut1d=bool(getattr(self, "n1d", 0)), prelut=bool(getattr(self, "_has_prelut", False)),
-            dither=other.get("dither", "none"), chroma_loc=other.get("chroma_loc"), out_size=other.get("out_size"),
-            alpha_mode=other.get("alpha_mode", "straight"), out2_pix_fmt=other.get("out2_pix_fmt"), strength=strength,
-            matte=matte is not None, rgb_matrix=rgb_matrix is not None)
+        st, fin, fout, (arr, n, k, mtx) = _stack_front(
+            self, "apply_yuv_stack", check_stack_options, ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt"),
+            pix_fmt, out_pix_fmt, stages, cdl, rgb_matrix, other, variant=False, strength=strength, matte=matte is not None)
         if fin.alpha or fout.alpha:
             # yuva*: the colour planes through this very call under their three-plane names, then the alpha plane on the same
             # stream, exactly as the CDL call does (DESIGN.md 3.16); straight alpha goes past the mix unchanged
-            if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
-                raise ValueError(_PLANE_COUNT[fin.nplanes].format(fin.name))
-            h, w = src[0].shape[-2], src[0].shape[-1]
-            _check_planes(src, fin, w, h, "source")
-            if dst is None:
-                dst = _fresh_planes(fout, w, h, src[0], self.device)
-            _check_planes(dst, fout, w, h, "destination")
-            a_src = src[3] if fin.alpha and not has_prologue(fin.depth, range_src, range_in, lut_depth) else None
-            if fout.alpha:
-                _check_alpha_overlap(a_src, fin.depth, dst, fout.depth)
-            self._alpha_tail(lambda: self.apply_yuv_stack(
-                src[:3], dst[:3], pix_fmt=fin.colour.name, out_pix_fmt=fout.colour.name, stages=st, cdl=cdl, matrix_in=matrix_in,
-                matrix_out=matrix_out, range_src=range_src, range_in=range_in, range_out=range_out, lut_depth=lut_depth, row0=row0,
-                rows=rows, strength=strength, matte=matte, matte_depth=matte_depth, matte_invert=matte_invert,
-                rgb_matrix=rgb_matrix),
-                [(fout, dst)], a_src, fin.depth, w, h, row0, rows)
-            return dst
+            return self._yuva_call(lambda s3, d3, name, out_name: self.apply_yuv_stack(
+                s3, d3, pix_fmt=name, out_pix_fmt=out_name, stages=st, cdl=cdl, matrix_in=matrix_in, matrix_out=matrix_out,
+                range_src=range_src, range_in=range_in, range_out=range_out, lut_depth=lut_depth, row0=row0, rows=rows,
+                strength=strength, matte=matte, matte_depth=matte_depth, matte_invert=matte_invert, rgb_matrix=rgb_matrix),
+                src, dst, fin, fout, has_prologue(fin.depth, range_src, range_in, lut_depth), row0, rows)
         p = _yuv_call_params(fin, fout, lut_depth, matrix_in, matrix_out, range_src, range_in, range_out)
         h, w = src[0].shape[-2], src[0].shape[-1]
         if dst is None:
@@ -991,8 +1008,6 @@ class LutEngine:
         _check_not_in_place(src, dst, _STACK_IN_PLACE)
         s, d, nf = _plane_pair(src, dst, self.device)
         rows = h - row0 if rows is None else rows
-        arr = _native.stage_array(st)
-        k = None if cdl is None else C.byref(_native.cdl_struct(cdl))
         strength = check_strength(strength, nf)
         if matte is not None:
             matte, mdepth, minvert, still = check_matte(matte, matte_depth, matte_invert, w=w, h=h, nframes=nf, device=self.device)
@@ -1007,34 +1022,20 @@ class LutEngine:
             self._bind_stream()
             if rgb_matrix is not None:                            # a matrix stage is listed (check_stack_options)
                 _native.check(self._lib.lutr_apply_yuv_stack_matrix(
-                    self._ctx, C.byref(p), arr, len(st), k, C.byref(_native.rgb_matrix_struct(rgb_matrix)), w, h, nf, C.byref(s),
-                    C.byref(d), row0, rows))
-            elif matte is not None:
-                frame = None
-                if not isinstance(strength, float):              # one float per frame: uploaded and kept as below
-                    if not self.use_torch_stream and self._frame_strength is not None:
-                        self.sync()
-                    self._frame_strength = torch.from_numpy(strength).to(self.device)
-                    frame = C.c_void_p(self._frame_strength.data_ptr())
-                _native.check(self._lib.lutr_apply_yuv_stack_matte(
-                    self._ctx, C.byref(p), arr, len(st), k, strength if frame is None else 1.0, frame, C.byref(m), w, h, nf,
-                    C.byref(s), C.byref(d), row0, rows))
-            elif strength is None:
+                    self._ctx, C.byref(p), arr, n, k, mtx, w, h, nf, C.byref(s), C.byref(d), row0, rows))
+            elif strength is None:                                # (a matte brings a strength of 1)
                 _native.check(self._lib.lutr_apply_yuv_stack(
-                    self._ctx, C.byref(p), arr, len(st), k, w, h, nf, C.byref(s), C.byref(d), row0, rows))
-            elif isinstance(strength, float):
-                _native.check(self._lib.lutr_apply_yuv_stack_mix(
-                    self._ctx, C.byref(p), arr, len(st), k, strength, None, w, h, nf, C.byref(s), C.byref(d), row0, rows))
+                    self._ctx, C.byref(p), arr, n, k, w, h, nf, C.byref(s), C.byref(d), row0, rows))
             else:
-                # one float per frame, on the stream the kernel reads it from; the engine keeps it until the next one replaces it
-                # (torch's allocator hands the old one's memory out again in stream order; a context on a stream of its own is
-                # waited for first)
-                if not self.use_torch_stream and self._frame_strength is not None:
-                    self.sync()
-                self._frame_strength = torch.from_numpy(strength).to(self.device)
-                _native.check(self._lib.lutr_apply_yuv_stack_mix(
-                    self._ctx, C.byref(p), arr, len(st), k, 1.0, C.c_void_p(self._frame_strength.data_ptr()), w, h, nf,
-                    C.byref(s), C.byref(d), row0, rows))
+                # one number for the call, or 1.0 beside one float per frame
+                frame = None if isinstance(strength, float) else self._upload_frame_strength(strength)
+                mix = (strength if frame is None else 1.0, frame)
+                if matte is not None:
+                    _native.check(self._lib.lutr_apply_yuv_stack_matte(
+                        self._ctx, C.byref(p), arr, n, k, *mix, C.byref(m), w, h, nf, C.byref(s), C.byref(d), row0, rows))
+                else:
+                    _native.check(self._lib.lutr_apply_yuv_stack_mix(
+                        self._ctx, C.byref(p), arr, n, k, *mix, w, h, nf, C.byref(s), C.byref(d), row0, rows))
         return dst
 
     def apply_rgb_lut1d(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, depth: int,
@@ -1310,21 +1311,10 @@ class LutEngine:
         source, a packed destination, a gbrp destination of another depth, dither, out_size, chroma_loc, strength, matte,
         premultiplied alpha, a second output and the full-range composition are ValueErrors naming them
         (`formats.check_rgb_stack_options`)."""
-        for k in other:
-            if k not in ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength", "matte",
-                         "intermediate_pix_fmt"):
-                raise TypeError(f"apply_rgb_stack() got an unexpected keyword argument '{k}'")
-        if cdl is not None and not isinstance(cdl, Cdl):
-            raise TypeError(f"cdl must be a lut_renderer_amd.cdl.Cdl, not {type(cdl).__name__}")
-        if rgb_matrix is not None and not isinstance(rgb_matrix, RgbMatrix):
-            raise TypeError(f"rgb_matrix must be a lut_renderer_amd.rgbmatrix.RgbMatrix, not {type(rgb_matrix).__name__}")
-        st, fin, fout = check_rgb_stack_options(
-            pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(self, "n", 0)),
-            lut2=bool(getattr(self, "n2", 0)), lut1d=bool(getattr(self, "n1d", 0)), prelut=bool(getattr(self, "_has_prelut", False)),
-            rgb_matrix=rgb_matrix is not None, dither=other.get("dither", "none"), chroma_loc=other.get("chroma_loc"),
-            out_size=other.get("out_size"), alpha_mode=other.get("alpha_mode", "straight"),
-            out2_pix_fmt=other.get("out2_pix_fmt"), variant=getattr(self, "_variant_name", None), strength=other.get("strength"),
-            matte=other.get("matte"), intermediate_pix_fmt=other.get("intermediate_pix_fmt"))
+        st, fin, fout, (arr, n, k, m) = _stack_front(
+            self, "apply_rgb_stack", check_rgb_stack_options,
+            ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength", "matte", "intermediate_pix_fmt"),
+            pix_fmt, out_pix_fmt, stages, cdl, rgb_matrix, other)
         to_rgb = fout.family == "gbr"
         planar, packed, w, h, nf, lead = self._rgb_source(src, fin)
         if dst is None:
@@ -1358,13 +1348,10 @@ class LutEngine:
         if not to_rgb:
             p = C.byref(_yuv_params(_native.fmt_code(fin.depth, 0, 0), fout.code, fin.depth, matrix_out, matrix_out, range_out,
                                     range_out, range_out))
-        arr = _native.stage_array(st)
-        k = None if cdl is None else C.byref(_native.cdl_struct(cdl))
-        m = None if rgb_matrix is None else C.byref(_native.rgb_matrix_struct(rgb_matrix))
         with self._lock:
             self._bind_stream()
             _native.check(self._lib.lutr_apply_rgb_stack(
-                self._ctx, p, arr, len(st), k, m, fin.code, w, h, nf, C.byref(planar) if planar is not None else None,
+                self._ctx, p, arr, n, k, m, fin.code, w, h, nf, C.byref(planar) if planar is not None else None,
                 C.byref(packed) if packed is not None else None, fin.depth if to_rgb else _native.RGB_STACK_YUV, C.byref(d),
                 row0, rows))
         return dst
@@ -1457,27 +1444,13 @@ class LutEngine:
         `apply_yuv_to_rgb(lut=False)`.  Dither, out_size, chroma_loc, strength, matte, premultiplied alpha, a second output, a
         float destination, semi-planar / packed 4:2:2 / v210 sources and alpha into a 4-component packed destination are
         ValueErrors naming them (`formats.check_yuv2rgb_stack_options`)."""
-        for k in other:
-            if k not in ("dither", "engine_dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength", "matte"):
-                raise TypeError(f"apply_yuv_stack_to_rgb() got an unexpected keyword argument '{k}'")
-        if cdl is not None and not isinstance(cdl, Cdl):
-            raise TypeError(f"cdl must be a lut_renderer_amd.cdl.Cdl, not {type(cdl).__name__}")
-        if rgb_matrix is not None and not isinstance(rgb_matrix, RgbMatrix):
-            raise TypeError(f"rgb_matrix must be a lut_renderer_amd.rgbmatrix.RgbMatrix, not {type(rgb_matrix).__name__}")
-        st, fin, fout = check_yuv2rgb_stack_options(
-            pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(self, "n", 0)),
-            lut2=bool(getattr(self, "n2", 0)), lut1d=bool(getattr(self, "n1d", 0)), prelut=bool(getattr(self, "_has_prelut", False)),
-            rgb_matrix=rgb_matrix is not None, dither=other.get("dither", "none"), engine_dither=other.get("engine_dither"),
-            chroma_loc=other.get("chroma_loc"), out_size=other.get("out_size"), alpha_mode=other.get("alpha_mode", "straight"),
-            out2_pix_fmt=other.get("out2_pix_fmt"), variant=getattr(self, "_variant_name", None), strength=other.get("strength"),
-            matte=other.get("matte"))
-        arr = _native.stage_array(st)
-        k = None if cdl is None else C.byref(_native.cdl_struct(cdl))
-        m = None if rgb_matrix is None else C.byref(_native.rgb_matrix_struct(rgb_matrix))
+        _st, fin, fout, stack = _stack_front(
+            self, "apply_yuv_stack_to_rgb", check_yuv2rgb_stack_options,
+            ("dither", "engine_dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength", "matte"),
+            pix_fmt, out_pix_fmt, stages, cdl, rgb_matrix, other)
 
         def call(p, kind, w, h, nf, s, d_planar, d_packed, row0, nrows):
-            return self._lib.lutr_apply_yuv_stack_to_rgb(self._ctx, p, arr, len(st), k, m, kind, w, h, nf, s, d_planar, d_packed,
-                                                         row0, nrows)
+            return self._lib.lutr_apply_yuv_stack_to_rgb(self._ctx, p, *stack, kind, w, h, nf, s, d_planar, d_packed, row0, nrows)
 
         return self._yuv2rgb_run(call, src, dst, fin, fout, matrix_in, range_src, range_in, row0, rows)
 

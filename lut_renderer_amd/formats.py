@@ -490,6 +490,57 @@ def chain_interp(interp: str, interp2: Optional[str]) -> Tuple[int, int]:
 
 
 
+#: what a stage-stack pass does not take, by keyword of its check -> (the keyword's neutral value,
+#: what the refusal calls it, `{v}` being the value given).  The CDL and lut1d passes, the stack's one-stage forerunners, word
+#: theirs the same way.
+_STACK_NOT_TAKEN = {
+    "dither": ("none", "dither ('{v}')"), "engine_dither": (None, "dither (engine_dither='{v}')"),
+    "chroma_loc": (None, "sited chroma resampling (chroma_loc)"), "out_size": (None, "a resize (out_size / resolution)"),
+    "out2_pix_fmt": (None, "the two-output pass (out2_pix_fmt)"), "lut2": (False, "the two-LUT chain (a second LUT)"),
+    "cdl": (False, "a CDL"), "alpha_mode": ("straight", "alpha_mode='{v}'"), "strength": (None, "a LUT strength (strength)"),
+    "matte": (None, "a matte (matte)"),
+    "intermediate_pix_fmt": (None, "the full-range two-stage composition (intermediate_pix_fmt)"),
+}
+
+#: what the refusals of the two newer stack passes call them
+RGB_STACK_TAIL = "a stage stack on an RGB source (rgb_stages)"
+YUV2RGB_STACK_TAIL = "a stage stack from a YUV source into an RGB frame (rgb_out_stages)"
+
+
+def held_resources(eng, variant: bool = False, lut1d_of=None) -> dict:
+    """What an engine holds, as the `lut` / `lut2` / `lut1d` / `prelut` keywords of `check_stage_list` and the stack checks (with
+    `variant`, `variant` too).  `eng` is a `LutEngine`, a group's first engine -- the group itself, `lut1d_of`, then tells of the 1D
+    LUT -- or any object with some of their attributes: one it has not counts as nothing held."""
+    kw = dict(lut=bool(getattr(eng, "n", 0)), lut2=bool(getattr(eng, "n2", 0)),
+              lut1d=bool(getattr(eng if lut1d_of is None else lut1d_of, "n1d", 0)), prelut=bool(getattr(eng, "_has_prelut", False)))
+    if variant:
+        kw["variant"] = getattr(eng, "_variant_name", None)
+    return kw
+
+
+def _refuse_stack_options(tail: str, kernel: str, variant: Optional[str], options: dict, vector=None) -> None:
+    """ValueError, in the words of `_STACK_NOT_TAKEN`, for the first of `options` -- keyword -> value, in the order the pass
+    called `tail` answers them -- that is not at its neutral value; then for the vec_lds variant (`kernel` names the pass there);
+    then, with `vector` = (parsed stages, source depth, destination depth, source name, destination name), for vec_global where
+    the names of the call already say that the vector kernel cannot take it.  Sizes, strides and alignment the vector kernel
+    cannot take are the C layer's (LUTR_EINVAL: it sees the planes)."""
+    for k, v in options.items():
+        neutral, what = _STACK_NOT_TAKEN[k]
+        if (v is not None) if neutral is None else (v != neutral):
+            raise ValueError(f"{what.format(v=v)} is not supported with {tail}")
+    if variant == "vec_lds":
+        raise ValueError(f"variant vec_lds is not supported with {tail}: there is no LDS-window kernel for the {kernel} pass")
+    if variant == "vec_global" and vector is not None:
+        st, din, dout, src_name, dst_name = vector
+        slow = [f"{k}:{m}" for k, m in st if m in ("pyramid", "prism")]
+        if slow:
+            raise ValueError(f"variant vec_global cannot take stage '{slow[0]}' of {tail}: the vector kernel has nearest, trilinear "
+                             f"and tetrahedral")
+        if din <= 8 and dout > 8:
+            raise ValueError(f"variant vec_global cannot take an 8-bit source ('{src_name}') written as 16-bit words "
+                             f"('{dst_name}') with {tail}: that container mix has no vector kernel")
+
+
 def check_cdl_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = None, *, dither: str = "none",
                       chroma_loc: Optional[str] = None, out_size=None, alpha_mode: str = "straight",
                       out2_pix_fmt: Optional[str] = None, lut2: bool = False, prelut: bool = False,
@@ -507,20 +558,8 @@ def check_cdl_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = None,
     if prelut:
         raise ValueError(f"a LUT with a .csp prelut is not supported with {tail}: the prelut's table is indexed by integer codes, "
                          f"and the CDL's output is not a code")
-    if dither != "none":
-        raise ValueError(f"dither ('{dither}') is not supported with {tail}")
-    if chroma_loc is not None:
-        raise ValueError(f"sited chroma resampling (chroma_loc) is not supported with {tail}")
-    if out_size is not None:
-        raise ValueError(f"a resize (out_size / resolution) is not supported with {tail}")
-    if out2_pix_fmt is not None:
-        raise ValueError(f"the two-output pass (out2_pix_fmt) is not supported with {tail}")
-    if lut2:
-        raise ValueError(f"the two-LUT chain (a second LUT) is not supported with {tail}")
-    if alpha_mode != "straight":
-        raise ValueError(f"alpha_mode='{alpha_mode}' is not supported with {tail}")
-    if variant == "vec_lds":
-        raise ValueError(f"variant vec_lds is not supported with {tail}: there is no LDS-window kernel for the CDL pass")
+    _refuse_stack_options(tail, "CDL", variant, dict(dither=dither, chroma_loc=chroma_loc, out_size=out_size,
+                                                     out2_pix_fmt=out2_pix_fmt, lut2=bool(lut2), alpha_mode=alpha_mode))
     return fin, fout
 
 
@@ -544,22 +583,8 @@ def check_lut1d_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = Non
     if fin.family != "yuv" or fout.family != "yuv":
         bad, what = (pix_fmt, "pix_fmt") if fin.family != "yuv" else (out_pix_fmt, "out_pix_fmt")
         raise ValueError(f"the lut1d pass takes planar YUV on both sides: {what} '{bad}' is an RGB format")
-    if dither != "none":
-        raise ValueError(f"dither ('{dither}') is not supported with {tail}")
-    if chroma_loc is not None:
-        raise ValueError(f"sited chroma resampling (chroma_loc) is not supported with {tail}")
-    if out_size is not None:
-        raise ValueError(f"a resize (out_size / resolution) is not supported with {tail}")
-    if cdl:
-        raise ValueError(f"a CDL is not supported with {tail}")
-    if lut2:
-        raise ValueError(f"the two-LUT chain (a second LUT) is not supported with {tail}")
-    if out2_pix_fmt is not None:
-        raise ValueError(f"the two-output pass (out2_pix_fmt) is not supported with {tail}")
-    if alpha_mode != "straight":
-        raise ValueError(f"alpha_mode='{alpha_mode}' is not supported with {tail}")
-    if variant == "vec_lds":
-        raise ValueError(f"variant vec_lds is not supported with {tail}: there is no LDS-window kernel for the lut1d pass")
+    _refuse_stack_options(tail, "lut1d", variant, dict(dither=dither, chroma_loc=chroma_loc, out_size=out_size, cdl=bool(cdl),
+                                                       lut2=bool(lut2), out2_pix_fmt=out2_pix_fmt, alpha_mode=alpha_mode))
     if not loaded:
         raise ValueError("no 1D LUT is loaded: call set_lut1d / load_lut1d first, or pass lut1d")
     return fin, fout
@@ -723,20 +748,15 @@ def check_stage_list(stages, *, cdl: bool = False, lut: bool = True, lut2: bool 
         raise ValueError("stage 'lut3d2' is listed and no second LUT is loaded: call set_lut2 / load_cube2 first, or pass cube2")
     if "lut1d" in kinds and not lut1d:
         raise ValueError("stage 'lut1d' is listed and no 1D LUT is loaded: call set_lut1d / load_lut1d first, or pass lut1d")
-    if "cdl" in kinds and not cdl:
-        raise ValueError("stage 'cdl' is listed and no CDL is given: pass cdl")
-    if cdl and "cdl" not in kinds:
-        raise ValueError("a CDL is given and the stage list has no 'cdl' stage")
-    if prelut and "cdl" in kinds and kinds.index("cdl") + 1 < len(kinds) and kinds[kinds.index("cdl") + 1] == "lut3d":
-        raise ValueError("stage 'lut3d' directly behind 'cdl' is not supported with a LUT that carries a .csp prelut: the prelut's "
-                         "table is indexed by integer codes, and the CDL's output is not a code")
-    if "matrix" in kinds and not rgb_matrix:
-        raise ValueError("stage 'matrix' is listed and no RGB matrix is given: pass rgb_matrix")
-    if rgb_matrix and "matrix" not in kinds:
-        raise ValueError("an RGB matrix is given and the stage list has no 'matrix' stage")
-    if prelut and "matrix" in kinds and kinds.index("matrix") + 1 < len(kinds) and kinds[kinds.index("matrix") + 1] == "lut3d":
-        raise ValueError("stage 'lut3d' directly behind 'matrix' is not supported with a LUT that carries a .csp prelut: the prelut's "
-                         "table is indexed by integer codes, and the matrix's output is not a code")
+    for kind, given, arg, name, its in (("cdl", cdl, "cdl", "a CDL", "the CDL's"),
+                                        ("matrix", rgb_matrix, "rgb_matrix", "an RGB matrix", "the matrix's")):
+        if kind in kinds and not given:
+            raise ValueError(f"stage '{kind}' is listed and no {name.split(' ', 1)[1]} is given: pass {arg}")
+        if given and kind not in kinds:
+            raise ValueError(f"{name} is given and the stage list has no '{kind}' stage")
+        if prelut and kind in kinds and kinds[kinds.index(kind) + 1:kinds.index(kind) + 2] == ["lut3d"]:
+            raise ValueError(f"stage 'lut3d' directly behind '{kind}' is not supported with a LUT that carries a .csp prelut: the "
+                             f"prelut's table is indexed by integer codes, and {its} output is not a code")
     return st
 
 
@@ -758,32 +778,19 @@ def check_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = Non
     Returns (parsed stages, source format, output format)."""
     mixed = strength is not None
     matte = matte is not None and matte is not False
-    tail = "a stage stack with strength" if mixed else "a stage stack"
-    noun = "stack (strength)" if mixed else "stack"
-    if matte:
-        tail = "a stage stack with strength and a matte" if mixed else "a stage stack with a matte"
-        noun = "stack (strength, matte)" if mixed else "stack (matte)"
+    # what the mix is called beside an option, and in the name of the pass; None without a strength or a matte
+    what, short = {(True, True): ("strength and a matte", "strength, matte"), (False, True): ("a matte", "matte"),
+                   (True, False): ("strength", "strength"), (False, False): (None, None)}[(mixed, matte)]
+    tail = f"a stage stack with {what}" if what else "a stage stack"
+    noun = f"stack ({short})" if what else "stack"
     st = check_stage_list(stages, cdl=cdl, lut=lut, lut2=lut2, lut1d=lut1d, prelut=prelut, rgb_matrix=rgb_matrix)
-    kinds = [k for k, _m in st]
-    if "matrix" in kinds and (mixed or matte):
-        what = "strength and a matte" if mixed and matte else "a matte" if matte else "strength"
+    if what and "matrix" in [k for k, _m in st]:
         raise ValueError(f"stage 'matrix' is not supported with {what}: the matrix stage has no mix form")
     fin = _pass_side(pix_fmt, "pix_fmt", noun, "both sides", True, alpha_ok=True)
     fout = _pass_side(out_pix_fmt or pix_fmt, "out_pix_fmt", noun, "both sides", True, alpha_ok=True)
-    if dither != "none":
-        raise ValueError(f"dither ('{dither}') is not supported with {tail}")
-    if chroma_loc is not None:
-        raise ValueError(f"sited chroma resampling (chroma_loc) is not supported with {tail}")
-    if out_size is not None:
-        raise ValueError(f"a resize (out_size / resolution) is not supported with {tail}")
-    if out2_pix_fmt is not None:
-        raise ValueError(f"the two-output pass (out2_pix_fmt) is not supported with {tail}")
-    if alpha_mode != "straight":
-        raise ValueError(f"alpha_mode='{alpha_mode}' is not supported with {tail}")
-    if variant == "vec_lds":
-        raise ValueError(f"variant vec_lds is not supported with {tail}: there is no LDS-window kernel for the stack pass")
-    if (mixed or matte) and precision not in (None, "strict"):
-        what = "strength and a matte" if mixed and matte else "a matte" if matte else "strength"
+    _refuse_stack_options(tail, "stack", variant, dict(dither=dither, chroma_loc=chroma_loc, out_size=out_size,
+                                                       out2_pix_fmt=out2_pix_fmt, alpha_mode=alpha_mode))
+    if what and precision not in (None, "strict"):
         raise ValueError(f"precision='{precision}' is not supported with {what}: the mix is defined on the strict path only")
     if mixed:
         check_strength(strength)
@@ -980,7 +987,7 @@ def check_rgb_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] =
     cannot take it (a pyramid / prism stage, an 8-bit source written as 16-bit words).  `out_pix_fmt` None means `gbrp*` at the
     source's depth.
     Returns (parsed stages, source `RgbSource`, destination `PixFmt`)."""
-    tail = "a stage stack on an RGB source (rgb_stages)"
+    tail = RGB_STACK_TAIL
     st = check_stage_list(stages, cdl=cdl, lut=lut, lut2=lut2, lut1d=lut1d, prelut=prelut, rgb_matrix=rgb_matrix)
     fin = parse_rgb_source(pix_fmt)
     if fin is None:
@@ -1009,34 +1016,10 @@ def check_rgb_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] =
         if fout.family == "gbr" and fout.depth != fin.depth:
             raise ValueError(f"a gbrp destination of another depth ('{out_pix_fmt}', {fout.depth} bit, from '{pix_fmt}', "
                              f"{fin.depth} bit) is not supported with {tail}: the final codes are stored at the source's depth")
-    if intermediate_pix_fmt is not None:
-        raise ValueError(f"the full-range two-stage composition (intermediate_pix_fmt) is not supported with {tail}")
-    if dither != "none":
-        raise ValueError(f"dither ('{dither}') is not supported with {tail}")
-    if out_size is not None:
-        raise ValueError(f"a resize (out_size / resolution) is not supported with {tail}")
-    if chroma_loc is not None:
-        raise ValueError(f"sited chroma resampling (chroma_loc) is not supported with {tail}")
-    if strength is not None:
-        raise ValueError(f"a LUT strength (strength) is not supported with {tail}")
-    if matte is not None and matte is not False:
-        raise ValueError(f"a matte (matte) is not supported with {tail}")
-    if alpha_mode != "straight":
-        raise ValueError(f"alpha_mode='{alpha_mode}' is not supported with {tail}")
-    if out2_pix_fmt is not None:
-        raise ValueError(f"the two-output pass (out2_pix_fmt) is not supported with {tail}")
-    if variant == "vec_lds":
-        raise ValueError(f"variant vec_lds is not supported with {tail}: there is no LDS-window kernel for the RGB stack pass")
-    if variant == "vec_global":
-        # what the names of the call say already; sizes, strides and alignment the vector kernel cannot take are the C layer's
-        # (LUTR_EINVAL: it sees the planes)
-        slow = [f"{k}:{m}" for k, m in st if m in ("pyramid", "prism")]
-        if slow:
-            raise ValueError(f"variant vec_global cannot take stage '{slow[0]}' of {tail}: the vector kernel has nearest, trilinear "
-                             f"and tetrahedral")
-        if fin.depth <= 8 and fout.depth > 8:
-            raise ValueError(f"variant vec_global cannot take an 8-bit source ('{pix_fmt}') written as 16-bit words "
-                             f"('{fout.name}') with {tail}: that container mix has no vector kernel")
+    _refuse_stack_options(tail, "RGB stack", variant, dict(
+        intermediate_pix_fmt=intermediate_pix_fmt, dither=dither, out_size=out_size, chroma_loc=chroma_loc, strength=strength,
+        matte=None if matte is False else matte, alpha_mode=alpha_mode, out2_pix_fmt=out2_pix_fmt),
+        vector=(st, fin.depth, fout.depth, pix_fmt, fout.name))
     return st, fin, fout
 
 
@@ -1053,35 +1036,11 @@ def check_yuv2rgb_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[st
     a second output; the vec_lds variant, and vec_global where the names of the call already say that the vector kernel cannot
     take it (a pyramid / prism stage, an 8-bit source written as 16-bit words).
     Returns (parsed stages, source `PixFmt`, destination `PixFmt` | packed `RgbSource`)."""
-    tail = "a stage stack from a YUV source into an RGB frame (rgb_out_stages)"
+    tail = YUV2RGB_STACK_TAIL
     st = check_stage_list(stages, cdl=cdl, lut=lut, lut2=lut2, lut1d=lut1d, prelut=prelut, rgb_matrix=rgb_matrix)
     fin, fout = _yuv2rgb_sides(pix_fmt, out_pix_fmt, "the stage stack from YUV into RGB (apply_yuv_stack_to_rgb)")
-    if chroma_loc is not None:
-        raise ValueError(f"sited chroma resampling (chroma_loc) is not supported with {tail}")
-    if dither != "none":
-        raise ValueError(f"dither ('{dither}') is not supported with {tail}")
-    if engine_dither is not None:
-        raise ValueError(f"dither (engine_dither='{engine_dither}') is not supported with {tail}")
-    if out_size is not None:
-        raise ValueError(f"a resize (out_size / resolution) is not supported with {tail}")
-    if strength is not None:
-        raise ValueError(f"a LUT strength (strength) is not supported with {tail}")
-    if matte is not None and matte is not False:
-        raise ValueError(f"a matte (matte) is not supported with {tail}")
-    if alpha_mode != "straight":
-        raise ValueError(f"alpha_mode='{alpha_mode}' is not supported with {tail}")
-    if out2_pix_fmt is not None:
-        raise ValueError(f"the two-output pass (out2_pix_fmt) is not supported with {tail}")
-    if variant == "vec_lds":
-        raise ValueError(f"variant vec_lds is not supported with {tail}: there is no LDS-window kernel for the YUV -> RGB stack pass")
-    if variant == "vec_global":
-        # what the names of the call say already; sizes, strides and alignment the vector kernel cannot take are the C layer's
-        # (LUTR_EINVAL: it sees the planes)
-        slow = [f"{k}:{m}" for k, m in st if m in ("pyramid", "prism")]
-        if slow:
-            raise ValueError(f"variant vec_global cannot take stage '{slow[0]}' of {tail}: the vector kernel has nearest, trilinear "
-                             f"and tetrahedral")
-        if fin.depth <= 8 and fout.depth > 8:
-            raise ValueError(f"variant vec_global cannot take an 8-bit source ('{pix_fmt}') written as 16-bit words "
-                             f"('{fout.name}') with {tail}: that container mix has no vector kernel")
+    _refuse_stack_options(tail, "YUV -> RGB stack", variant, dict(
+        chroma_loc=chroma_loc, dither=dither, engine_dither=engine_dither, out_size=out_size, strength=strength,
+        matte=None if matte is False else matte, alpha_mode=alpha_mode, out2_pix_fmt=out2_pix_fmt),
+        vector=(st, fin.depth, fout.depth, pix_fmt, fout.name))
     return st, fin, fout

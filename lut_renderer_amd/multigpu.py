@@ -29,11 +29,21 @@ import torch
 from . import _native
 from .cube import CubeLut, read_lut, read_lut1d
 from .engine import LutEngine, _fresh_planes, _new_planes, _yuv_out_dtype, chain_args, dual_args
-from .formats import (RgbSource, check_yuv2rgb_options, check_yuv2rgb_stack_options, check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2, check_matte, check_rgb_stack_options, check_stack_options, check_strength,
-                      check_premul_options,
-                      packed_frame_width, parse_pix_fmt, parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords,
-                      v210_frame_width, yuv_side)
+from .formats import (RgbSource, check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2,
+                      check_matte, check_premul_options, check_rgb_stack_options, check_stack_options, check_strength,
+                      check_yuv2rgb_options, check_yuv2rgb_stack_options, held_resources, packed_frame_width, parse_pix_fmt,
+                      parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords, v210_frame_width, yuv_side)
 from .shard import row_blocks
+
+
+def _stack_opening(group, check, refusable, pix_fmt, out_pix_fmt, stages, cdl, rgb_matrix, kw: dict, variant: bool = True, **told):
+    """How the group's three stack wrappers open, under its lock: the row partition is the group's; then the family's `check`
+    with what the first engine holds -- the 1D LUT as the group's setter left it -- and the keywords of `kw` the check refuses
+    by name (`refusable`).  Returns (parsed stages, source format, destination format)."""
+    if "row0" in kw or "rows" in kw:
+        raise ValueError("the group owns the row partition")
+    return check(pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, rgb_matrix=rgb_matrix is not None,
+                 **held_resources(group.engines[0], variant, lut1d_of=group), **{k: kw[k] for k in refusable if k in kw}, **told)
 
 
 def _row_ranges(fmt, r0: int, r1: int) -> list:
@@ -361,15 +371,9 @@ class LutEngineGroup:
         once per device, and a pixel reads the sample of its own row and column on every shard.  `rgb_matrix`
         travels with the call like the CDL."""
         with self._lock:
-            if "row0" in kw or "rows" in kw:
-                raise ValueError("the group owns the row partition")
-            e0 = self.engines[0]
-            st, fin, fout = check_stack_options(
-                pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(e0, "n", 0)),
-                lut2=bool(getattr(e0, "n2", 0)), lut1d=bool(self.n1d), prelut=bool(getattr(e0, "_has_prelut", False)),
-                dither=kw.get("dither", "none"), chroma_loc=kw.get("chroma_loc"), out_size=kw.get("out_size"),
-                alpha_mode=kw.get("alpha_mode", "straight"), out2_pix_fmt=kw.get("out2_pix_fmt"), strength=kw.get("strength"),
-                matte=kw.get("matte") is not None, rgb_matrix=kw.get("rgb_matrix") is not None)
+            st, fin, fout = _stack_opening(
+                self, check_stack_options, ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength"),
+                pix_fmt, out_pix_fmt, stages, cdl, kw.get("rgb_matrix"), kw, variant=False, matte=kw.get("matte") is not None)
             if kw.get("matte") is not None:
                 check_matte(kw["matte"], kw.get("matte_depth"), kw.get("matte_invert", False), w=src[0].shape[-1], h=src[0].shape[-2],
                             nframes=src[0].shape[0] if len(src[0].shape) == 3 else 1, device=src[0].device)
@@ -469,15 +473,10 @@ class LutEngineGroup:
         multiples of the output chroma block height (any row for a gbrp destination), every source plane (or the packed image)
         and alpha counted in luma rows, no halo."""
         with self._lock:
-            if "row0" in kw or "rows" in kw:
-                raise ValueError("the group owns the row partition")
-            e0 = self.engines[0]
-            refusable = ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength", "matte", "intermediate_pix_fmt")
-            st, fin, fout = check_rgb_stack_options(
-                pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(e0, "n", 0)),
-                lut2=bool(getattr(e0, "n2", 0)), lut1d=bool(self.n1d), prelut=bool(getattr(e0, "_has_prelut", False)),
-                rgb_matrix=rgb_matrix is not None, variant=getattr(e0, "_variant_name", None),
-                **{k: kw[k] for k in refusable if k in kw})
+            st, fin, fout = _stack_opening(
+                self, check_rgb_stack_options,
+                ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength", "matte", "intermediate_pix_fmt"),
+                pix_fmt, out_pix_fmt, stages, cdl, rgb_matrix, kw)
             first = src if fin.packed else src[0]
             h, w = (first.shape[-3], first.shape[-2]) if fin.packed else (first.shape[-2], first.shape[-1])
             lead = tuple(first.shape[:-3]) if fin.packed else tuple(first.shape[:-2])
@@ -543,14 +542,9 @@ class LutEngineGroup:
         `apply_yuv_to_rgb` splits them (shards on multiples of the source's chroma block height 2^icsy, no halo): the lattices
         and the 1D LUT are on every engine through the group's setters, the CDL and the matrix travel with the call."""
         with self._lock:
-            if "row0" in kw or "rows" in kw:
-                raise ValueError("the group owns the row partition")
-            e0 = self.engines[0]
-            refusable = ("dither", "engine_dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength", "matte")
-            st, fin, fout = check_yuv2rgb_stack_options(
-                pix_fmt, out_pix_fmt, stages=stages, cdl=cdl is not None, lut=bool(getattr(e0, "n", 0)),
-                lut2=bool(getattr(e0, "n2", 0)), lut1d=bool(self.n1d), prelut=bool(getattr(e0, "_has_prelut", False)),
-                rgb_matrix=rgb_matrix is not None, variant=getattr(e0, "_variant_name", None),
-                **{k: kw[k] for k in refusable if k in kw})
+            st, fin, fout = _stack_opening(
+                self, check_yuv2rgb_stack_options,
+                ("dither", "engine_dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength", "matte"),
+                pix_fmt, out_pix_fmt, stages, cdl, rgb_matrix, kw)
             names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, stages=st, cdl=cdl, rgb_matrix=rgb_matrix)
             return self._yuv2rgb_shards("apply_yuv_stack_to_rgb", src, dst, fin, fout, names, kw)

@@ -22,10 +22,10 @@ import torch
 
 from .engine import LutEngine
 from .params import strength_keys
-from .formats import (MATTE_PIX_FMTS, RgbSource, check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options,
-                      check_lut1d_options, check_stack_options,
-                      check_premul_options, check_rgb_stack_options, check_yuv2rgb_options, check_yuv2rgb_stack_options, parse_rgb_out, parse_rgb_source, parse_size, premul_to_yuv,
-                      refuse_alpha_resize, yuv_side, _YUV2RGB_NOT_TAKEN)
+from .formats import (MATTE_PIX_FMTS, RGB_STACK_TAIL, YUV2RGB_STACK_TAIL, RgbSource, check_alpha_mode, check_cdl_options,
+                      check_chain_options, check_dual_options, check_lut1d_options, check_premul_options, check_rgb_stack_options,
+                      check_stack_options, check_yuv2rgb_options, check_yuv2rgb_stack_options, held_resources, parse_rgb_out,
+                      parse_rgb_source, parse_size, premul_to_yuv, refuse_alpha_resize, yuv_side, _YUV2RGB_NOT_TAKEN)
 
 
 @dataclass
@@ -197,83 +197,73 @@ class HostPipeline:
     def __init__(self, engine: LutEngine, pix_fmt: str, width: int, height: int, batch: int = 8, slots: int = 3,
                  out_pix_fmt: Optional[str] = None, out_size=None, second_pix_fmt: Optional[str] = None, chain: bool = False, lut1d: bool = False,
                  rgb_out: Optional[str] = None, rgb_out_stages=None, **apply_kw):
-        """`out_size` = (w, h) or "WxH": the engine resizes every frame to it and the output layout has that size.
+        """Settles, once, which engine method every batch goes through (`entry`) and the layouts of its source and destination.
+        `out_size` = (w, h) or "WxH": the engine resizes every frame to it and the output layout has that size.
         `second_pix_fmt`: a second planar YUV output from the same pass with a pinned output ring of its own
         (`fout2`); `run` then takes a second drain.
         `chain`: the engine holds a second LUT (`set_lut2`) and every batch goes through `apply_yuv_chain` (DESIGN.md 3.17);
-        `apply_kw` may carry `interp2`.  Planar YUV without alpha on both sides, no dither, chroma_loc, out_size or second output."""
-        # `apply_kw["stages"]`: every batch goes through `apply_yuv_stack` (DESIGN.md 3.21) with the lattices and the 1D LUT the
-        # engine holds and `apply_kw["cdl"]`; `chain` / `lut1d` are not set then
-        # `apply_kw["strength"]` (a number) or `apply_kw["strength_keys"]` ("F:S,..." or `params.strength_keys`' callable) mix the
-        # graded frame with the source (DESIGN.md 3.22): the keys are read at the frame's number in the stream, counted here
-        # across the batches
-        # `apply_kw["matte"]` (a `MatteReader`; DESIGN.md 3.23) scales the strength per pixel: a still is uploaded once, a matte
-        # per frame is read and uploaded with every input batch; `apply_kw["matte_invert"]` travels to the engine
-        # `rgb_out` (DESIGN.md 3.24): a planar YUV source written as RGB -- gbrp* / gbrap* planes or a packed image -- through
-        # `apply_yuv_to_rgb`; the output ring has that layout (`output_layout`).  Not with `out_pix_fmt` or anything the pass refuses
-        # `apply_kw["rgb_stages"]` (DESIGN.md 3.26): an RGB source through the stage stack -- every batch goes through
-        # `apply_rgb_stack` with the lattices and the 1D LUT the engine holds, `apply_kw["cdl"]` and `apply_kw["rgb_matrix"]`, into
-        # planar YUV or gbrp* / gbrap* at the source's depth (`out_pix_fmt` None: the latter, for a planar source)
-        # `rgb_out_stages` (DESIGN.md 3.27): with `rgb_out`, every batch goes through `apply_yuv_stack_to_rgb` with the lattices and
-        # the 1D LUT the engine holds, `apply_kw["cdl"]` and `apply_kw["rgb_matrix"]`; the output ring is that of `rgb_out`
+        `apply_kw` may carry `interp2`.  Planar YUV without alpha on both sides, no dither, chroma_loc, out_size or second output.
+        `lut1d`: the engine holds a 1D LUT (`set_lut1d`) and every batch goes through `apply_yuv_lut1d` (DESIGN.md 3.20);
+        `apply_kw["interp"]` None is lut1d alone.
+        `rgb_out`: a planar YUV source written as RGB -- gbrp* / gbrap* planes or a packed image -- through
+        `apply_yuv_to_rgb`; the output ring has that layout (`output_layout`).  Not with `out_pix_fmt` or anything the pass refuses.
+        `rgb_out_stages`: with `rgb_out`, every batch goes through `apply_yuv_stack_to_rgb` with the lattices and
+        the 1D LUT the engine holds, `apply_kw["cdl"]` and `apply_kw["rgb_matrix"]`; the output ring is that of `rgb_out`.
+        `apply_kw` travels to the engine with every batch.  Of its keywords:
+        `stages`: every batch goes through `apply_yuv_stack` with the lattices and the 1D LUT the engine holds and
+        `apply_kw["cdl"]`; `chain` / `lut1d` are not set then.
+        `strength` (a number) or `strength_keys` ("F:S,..." or `params.strength_keys`' callable) mix the graded frame with the
+        source: the keys are read at the frame's number in the stream, counted here across the batches.
+        `matte` (a `MatteReader`) scales the strength per pixel: a still is uploaded once, a matte per frame is
+        read and uploaded with every input batch; `matte_invert` travels to the engine.
+        `rgb_matrix` (an `rgbmatrix.RgbMatrix`): the resource of a matrix stage of `stages`, which travels like the
+        CDL; None is not passed on.
+        `rgb_stages`: an RGB source through the stage stack -- every batch goes through `apply_rgb_stack` with
+        the lattices and the 1D LUT the engine holds, `cdl` and `rgb_matrix`, into planar YUV or gbrp* / gbrap* at the source's
+        depth (`out_pix_fmt` None: the latter, for a planar source).
+        `alpha_mode` travels like `chroma_loc`, "straight" is not passed on; `cdl` (a `cdl.Cdl`)
+        likewise, None is not passed on."""
+        self.eng = engine
+        self.batch, self.slots = int(batch), int(slots)
+        self.frames_submitted = 0
         self.rgb_out_stack = rgb_out_stages is not None
-        if self.rgb_out_stack:
-            if rgb_out is None:
-                raise ValueError("rgb_out_stages is the stage list of a YUV source written as RGB: it needs rgb_out")
-            if apply_kw.get("stages") is not None or apply_kw.get("rgb_stages") is not None:
-                raise ValueError("rgb_out_stages and stages / rgb_stages are mutually exclusive")
-            if out_pix_fmt:
-                raise ValueError(f"rgb_out ('{rgb_out}') and out_pix_fmt ('{out_pix_fmt}') are mutually exclusive")
+        self.rgb_stack = not self.rgb_out_stack and apply_kw.get("rgb_stages") is not None
+        if self.rgb_out_stack or self.rgb_stack:
+            # the two newer stack routes: what each refuses of its own, its family's check, then one tail
+            if self.rgb_out_stack:
+                flag, tail, check = "rgb_out_stages", YUV2RGB_STACK_TAIL, check_yuv2rgb_stack_options
+                listed, out_name, carried = rgb_out_stages, rgb_out, ("matrix_in", "range_src", "range_in")
+                refusable = ("dither", "engine_dither", "chroma_loc", "alpha_mode", "strength", "matte")
+                if rgb_out is None:
+                    raise ValueError("rgb_out_stages is the stage list of a YUV source written as RGB: it needs rgb_out")
+                if apply_kw.get("stages") is not None or apply_kw.get("rgb_stages") is not None:
+                    raise ValueError("rgb_out_stages and stages / rgb_stages are mutually exclusive")
+                if out_pix_fmt:
+                    raise ValueError(f"rgb_out ('{rgb_out}') and out_pix_fmt ('{out_pix_fmt}') are mutually exclusive")
+            else:
+                flag, tail, check = "rgb_stages", RGB_STACK_TAIL, check_rgb_stack_options
+                listed, out_name, carried = apply_kw["rgb_stages"], out_pix_fmt, ("matrix_out", "range_out")
+                refusable = ("dither", "chroma_loc", "alpha_mode", "strength", "matte", "intermediate_pix_fmt")
+                if apply_kw.get("stages") is not None:
+                    raise ValueError("stages and rgb_stages are mutually exclusive")
+                if rgb_out is not None:
+                    raise ValueError(f"rgb_out ('{rgb_out}') names the RGB output of a YUV source: with rgb_stages the output is out_pix_fmt")
             if chain or lut1d:
-                raise ValueError("a stage stack names its lut3d2 / lut1d stages itself: chain / lut1d are not set with rgb_out_stages")
-            refusable = ("dither", "engine_dither", "chroma_loc", "alpha_mode", "strength", "matte")
-            st, _fin, _fout = check_yuv2rgb_stack_options(
-                pix_fmt, rgb_out, stages=rgb_out_stages, cdl=apply_kw.get("cdl") is not None,
-                lut=bool(getattr(engine, "n", 0)), lut2=bool(getattr(engine, "n2", 0)), lut1d=bool(getattr(engine, "n1d", 0)),
-                prelut=bool(getattr(engine, "_has_prelut", False)), rgb_matrix=apply_kw.get("rgb_matrix") is not None,
-                out_size=out_size, out2_pix_fmt=second_pix_fmt, **{k: apply_kw[k] for k in refusable if k in apply_kw})
+                raise ValueError(f"a stage stack names its lut3d2 / lut1d stages itself: chain / lut1d are not set with {flag}")
+            st, _fin, fout = check(pix_fmt, out_name, stages=listed, cdl=apply_kw.get("cdl") is not None, **held_resources(engine),
+                                   rgb_matrix=apply_kw.get("rgb_matrix") is not None, out_size=out_size, out2_pix_fmt=second_pix_fmt,
+                                   **{k: apply_kw[k] for k in refusable if k in apply_kw})
             if apply_kw.get("strength_keys") is not None:
-                raise ValueError("a LUT strength (strength_keys) is not supported with a stage stack from a YUV source into an RGB "
-                                 "frame (rgb_out_stages)")
-            self.rgb_stack = self.stack = self.chain = self.lut1d = self.float_out = self.rgb = False
-            self.rgb_out = True
+                raise ValueError(f"a LUT strength (strength_keys) is not supported with {tail}")
+            self.stack = self.chain = self.lut1d = self.float_out = False
+            self.rgb, self.rgb_out = self.rgb_stack, self.rgb_out_stack
             self.matte = self.strength_keys = self.fout2 = None
-            self.frames_submitted = 0
-            self.eng = engine
             self.fin = input_layout(pix_fmt, width, height)
-            self.fout = output_layout(rgb_out, width, height)
-            self.batch, self.slots = int(batch), int(slots)
-            self.kw = dict({k: apply_kw[k] for k in ("cdl", "rgb_matrix", "matrix_in", "range_src", "range_in")
-                            if apply_kw.get(k) is not None}, stages=st, pix_fmt=self.fin.fmt.name, out_pix_fmt=self.fout.fmt.name)
-            self._allocate(engine, slots)
-            return
-        self.rgb_stack = apply_kw.get("rgb_stages") is not None
-        if self.rgb_stack:
-            if apply_kw.get("stages") is not None:
-                raise ValueError("stages and rgb_stages are mutually exclusive")
-            if rgb_out is not None:
-                raise ValueError(f"rgb_out ('{rgb_out}') names the RGB output of a YUV source: with rgb_stages the output is out_pix_fmt")
-            if chain or lut1d:
-                raise ValueError("a stage stack names its lut3d2 / lut1d stages itself: chain / lut1d are not set with rgb_stages")
-            refusable = ("dither", "chroma_loc", "alpha_mode", "strength", "matte", "intermediate_pix_fmt")
-            st, _fin, fout = check_rgb_stack_options(
-                pix_fmt, out_pix_fmt, stages=apply_kw["rgb_stages"], cdl=apply_kw.get("cdl") is not None,
-                lut=bool(getattr(engine, "n", 0)), lut2=bool(getattr(engine, "n2", 0)), lut1d=bool(getattr(engine, "n1d", 0)),
-                prelut=bool(getattr(engine, "_has_prelut", False)), rgb_matrix=apply_kw.get("rgb_matrix") is not None,
-                out_size=out_size, out2_pix_fmt=second_pix_fmt, **{k: apply_kw[k] for k in refusable if k in apply_kw})
-            if apply_kw.get("strength_keys") is not None:
-                raise ValueError("a LUT strength (strength_keys) is not supported with a stage stack on an RGB source (rgb_stages)")
-            self.rgb_out = self.stack = self.chain = self.lut1d = self.float_out = False
-            self.rgb = True
-            self.matte = self.strength_keys = self.fout2 = None
-            self.frames_submitted = 0
-            self.eng = engine
-            self.fin = input_layout(pix_fmt, width, height)
-            self.fout = yuv_layout(fout.name, width, height)
-            self.batch, self.slots = int(batch), int(slots)
-            self.kw = dict({k: apply_kw[k] for k in ("cdl", "rgb_matrix", "matrix_out", "range_out") if apply_kw.get(k) is not None},
-                           stages=st, pix_fmt=pix_fmt, out_pix_fmt=fout.name)
-            self._allocate(engine, slots)
+            self.fout = output_layout(rgb_out, width, height) if self.rgb_out_stack else yuv_layout(fout.name, width, height)
+            names = (self.fin.fmt.name, self.fout.fmt.name) if self.rgb_out_stack else (pix_fmt, fout.name)
+            self.kw = dict({k: apply_kw[k] for k in ("cdl", "rgb_matrix") + carried if apply_kw.get(k) is not None}, stages=st,
+                           pix_fmt=names[0], out_pix_fmt=names[1])
+            self._settle("apply_yuv_stack_to_rgb" if self.rgb_out_stack else "apply_rgb_stack", slots)
             return
         self.rgb_out = rgb_out is not None
         if self.rgb_out:
@@ -283,8 +273,6 @@ class HostPipeline:
                                   lut1d=True if lut1d else None,
                                   **{k: v for k, v in apply_kw.items() if k in _YUV2RGB_NOT_TAKEN and k not in ("out_size", "lut1d")})
             apply_kw = {k: v for k, v in apply_kw.items() if k not in _YUV2RGB_NOT_TAKEN}
-        # `apply_kw["rgb_matrix"]` (an `rgbmatrix.RgbMatrix`): the resource of a matrix stage of `stages`, which
-        # travels to the engine with every batch like the CDL; None is not passed on
         stages = apply_kw.get("stages")
         self.stack = stages is not None
         if apply_kw.get("rgb_matrix") is None:
@@ -302,7 +290,6 @@ class HostPipeline:
         if keys is not None and apply_kw.get("strength") is not None:
             raise ValueError("strength and strength_keys are mutually exclusive")
         self.strength_keys = strength_keys(keys) if isinstance(keys, str) else keys
-        self.frames_submitted = 0
         if apply_kw.get("strength") is None:
             apply_kw.pop("strength", None)
         mixed = keys is not None or "strength" in apply_kw
@@ -311,29 +298,21 @@ class HostPipeline:
         if self.stack:
             if chain or lut1d:
                 raise ValueError("a stage stack names its lut3d2 / lut1d stages itself: chain / lut1d are not set with stages")
-            check_stack_options(pix_fmt, out_pix_fmt, stages=stages, cdl=apply_kw.get("cdl") is not None,
-                                lut=bool(getattr(engine, "n", 0)), lut2=bool(getattr(engine, "n2", 0)),
-                                lut1d=bool(getattr(engine, "n1d", 0)), prelut=bool(getattr(engine, "_has_prelut", False)),
+            check_stack_options(pix_fmt, out_pix_fmt, stages=stages, cdl=apply_kw.get("cdl") is not None, **held_resources(engine),
                                 dither=apply_kw.get("dither", "none"), chroma_loc=apply_kw.get("chroma_loc"), out_size=out_size,
                                 alpha_mode=apply_kw.get("alpha_mode", "straight"), out2_pix_fmt=second_pix_fmt,
                                 strength=apply_kw.get("strength", 1.0 if mixed else None), matte=self.matte is not None,
                                 rgb_matrix="rgb_matrix" in apply_kw)
             apply_kw = {k: v for k, v in apply_kw.items() if k not in ("dither", "alpha_mode", "interp") and
                         not (k == "cdl" and v is None)}
-        self.chain = bool(chain)
-        # `lut1d`: the engine holds a 1D LUT (`set_lut1d`) and every batch goes through `apply_yuv_lut1d`;
-        # `apply_kw["interp"]` None is lut1d alone
-        self.lut1d = bool(lut1d)
-        # premultiplied alpha travels in apply_kw like chroma_loc; "straight" is not passed on (today's calls)
-        premul = check_alpha_mode(apply_kw.get("alpha_mode", "straight"))
-        if premul:
+        self.chain, self.lut1d = bool(chain), bool(lut1d)
+        if check_alpha_mode(apply_kw.get("alpha_mode", "straight")):
             check_premul_options(pix_fmt, out_pix_fmt, dither=apply_kw.get("dither", "none"), chroma_loc=apply_kw.get("chroma_loc"),
                                  out_size=out_size, range_src=apply_kw.get("range_src", "tv"), range_in=apply_kw.get("range_in"),
                                  lut_depth=apply_kw.get("lut_depth"), out2_pix_fmt=second_pix_fmt, lut2=self.chain,
                                  to_yuv=premul_to_yuv(pix_fmt, out_pix_fmt))
         else:
             apply_kw = {k: v for k, v in apply_kw.items() if k != "alpha_mode"}
-        # a CDL in front of the LUT travels in apply_kw too, as a `cdl.Cdl`; None is not passed on
         if self.stack:                                         # (checked above: the CDL is a stage of the stack)
             pass
         elif apply_kw.get("cdl") is not None:
@@ -352,7 +331,6 @@ class HostPipeline:
                                 second_pix_fmt)
             apply_kw = {k: v for k, v in apply_kw.items() if k != "dither"}
         self.fout2 = dual_layout(pix_fmt, out_pix_fmt, second_pix_fmt, width, height, out_size, apply_kw)
-        self.eng = engine
         self.fin = input_layout(pix_fmt, width, height)
         src_rgb = parse_rgb_source(pix_fmt)
         self.rgb = src_rgb is not None                         # an RGB source: apply_rgb_to_yuv
@@ -371,13 +349,41 @@ class HostPipeline:
             self.fout = output_layout(rgb_out, ow, oh)
         else:
             self.fout = yuv_layout(out_pix_fmt or pix_fmt, ow, oh)
-        self.batch, self.slots = int(batch), int(slots)
         self.kw = dict(apply_kw, pix_fmt=self.fin.fmt.name, out_pix_fmt=self.fout.fmt.name)
         if out_size is not None:
             self.kw["out_size"] = (ow, oh)
         if self.fin.fmt.nplanes == 1 or self.fout.fmt.nplanes == 1:
             self.kw["width"] = width                           # (a packed row cannot tell an odd width)
-        self._allocate(engine, slots)
+        self._settle("apply_yuv_to_rgb" if self.rgb_out else "apply_yuv_stack" if self.stack else "apply_yuv_lut1d" if self.lut1d
+                     else "apply_yuv_chain" if self.chain else "apply_yuv_dual" if self.fout2 is not None
+                     else "apply_rgb_float" if self.float_out else "apply_rgb_to_yuv" if self.rgb else "apply_yuv", slots)
+
+    def _settle(self, entry: str, slots: int) -> None:
+        """`entry`, the engine method every batch goes through, and how `_submit` calls it -- with the source and the destination
+        viewed as their layouts say, planes or one packed image, and `kw`; the stack, the second output and the float planes each
+        have a word of their own to add -- then the rings (`_allocate`)."""
+        self.entry = entry
+        self._launch = {"apply_yuv_stack": self._launch_stack, "apply_yuv_dual": self._launch_dual,
+                        "apply_rgb_float": self._launch_float}.get(entry, self._launch_plain)
+        self._allocate(self.eng, slots)
+
+    def _launch_plain(self, src, dst, slot: int, nframes: int, matte) -> None:
+        getattr(self.eng, self.entry)(src, dst, **self.kw)
+
+    def _launch_stack(self, src, dst, slot: int, nframes: int, matte) -> None:
+        self._run_stack(src, dst, nframes, matte)
+
+    def _launch_dual(self, src, dst, slot: int, nframes: int, matte) -> None:
+        self.eng.apply_yuv_dual(src, dst, self.fout2.plane_views(self.d_out2[slot], nframes), **self.kw)
+
+    def _launch_float(self, src, dst, slot: int, nframes: int, matte) -> None:
+        self.eng.apply_rgb_float(src[:self.fout.fmt.nplanes], dst, interp=self.kw.get("interp", "tetrahedral"),
+                                 alpha_mode=self.kw.get("alpha_mode", "straight"))
+
+    @staticmethod
+    def _views(layout, buf: torch.Tensor, nframes: int):
+        """`nframes` frames inside a flat buffer as `layout` says: one [F,H,W,C] image for a packed RGB side, else its planes."""
+        return layout.image_view(buf, nframes) if isinstance(layout, PackedFrameLayout) else layout.plane_views(buf, nframes)
 
     def _allocate(self, engine: LutEngine, slots: int) -> None:
         """The pinned host rings, the device rings and the streams of the layouts `__init__` settled."""
@@ -452,35 +458,9 @@ class HostPipeline:
             self.e_in[slot].record()
         with torch.cuda.stream(self.s_run):
             self.s_run.wait_event(self.e_in[slot])
-            dst = self.fout.image_view(self.d_out[slot], nframes) if isinstance(self.fout, PackedFrameLayout) \
-                else self.fout.plane_views(self.d_out[slot], nframes)
-            if self.rgb_stack:
-                src = self.fin.image_view(self.d_in[slot], nframes) if isinstance(self.fin, PackedFrameLayout) \
-                    else self.fin.plane_views(self.d_in[slot], nframes)
-                self.eng.apply_rgb_stack(src, dst, **self.kw)
-            elif self.rgb_out_stack:
-                self.eng.apply_yuv_stack_to_rgb(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
-            elif self.rgb_out:
-                self.eng.apply_yuv_to_rgb(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
-            elif self.stack:
-                self._run_stack(self.fin.plane_views(self.d_in[slot], nframes), dst, nframes, matte)
-            elif self.lut1d:
-                self.eng.apply_yuv_lut1d(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
-            elif self.chain:
-                self.eng.apply_yuv_chain(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
-            elif self.fout2 is not None:
-                self.eng.apply_yuv_dual(self.fin.plane_views(self.d_in[slot], nframes), dst,
-                                        self.fout2.plane_views(self.d_out2[slot], nframes), **self.kw)
-            elif self.float_out:
-                src = self.fin.plane_views(self.d_in[slot], nframes)[:self.fout.fmt.nplanes]
-                self.eng.apply_rgb_float(src, dst, interp=self.kw.get("interp", "tetrahedral"),
-                                         alpha_mode=self.kw.get("alpha_mode", "straight"))
-            elif self.rgb:                                   # launches on the current (s_run) stream
-                src = self.fin.image_view(self.d_in[slot], nframes) if isinstance(self.fin, PackedFrameLayout) \
-                    else self.fin.plane_views(self.d_in[slot], nframes)
-                self.eng.apply_rgb_to_yuv(src, dst, **self.kw)
-            else:
-                self.eng.apply_yuv(self.fin.plane_views(self.d_in[slot], nframes), dst, **self.kw)
+            # (the engine launches on the current stream: s_run)
+            self._launch(self._views(self.fin, self.d_in[slot], nframes), self._views(self.fout, self.d_out[slot], nframes), slot,
+                         nframes, matte)
             self.e_run[slot].record()
         with torch.cuda.stream(self.s_d2h):
             self.s_d2h.wait_event(self.e_run[slot])
