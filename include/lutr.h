@@ -282,6 +282,14 @@ enum lutr_resize_family { LUTR_RESIZE_YUV = 0, LUTR_RESIZE_GBR = 1 };
 int lutr_resize_planes(lutr_ctx *ctx, int family, int depth, int csx, int csy, int chroma_loc, int sw, int sh, int dw, int dh,
                        int nframes, const lutr_planes *src, lutr_planes *dst);
 
+/* Host only (no context, no GPU): the launch plan lutr_resize_planes makes for this geometry, by the same function and after the
+ * same argument checks (LUTR_EINVAL as there).  out[8] = { th: output rows per tile (64, 32 or 16, the tallest whose LDS stays
+ * within 40 KiB with one staged row); rows: staged source rows per wave and step (8 .. 1, the most whose LDS stays within 64 KiB);
+ * lds: dynamic LDS bytes of the launch; spx, spy: the largest footprint of a tile over the three planes, source columns (even)
+ * and source rows; nx_max, ny_max: the most taps per axis; tiles_per_frame }.  A plan whose lds exceeds 65536 is filled in and
+ * refused with LUTR_EINVAL, as lutr_resize_planes refuses the launch. */
+int lutr_resize_plan(int family, int depth, int csx, int csy, int chroma_loc, int sw, int sh, int dw, int dh, int *out);
+
 /* zscale_dither of the reference (models.py:46; the filter `zscale=dither=error_diffusion`, ffmpeg.py:305-307) */
 enum lutr_dither {
     LUTR_DITHER_NONE = 0,

@@ -54,7 +54,7 @@ SYMBOLS = (
     "lutr_lut1d_parse", "lutr_lut1d_table", "lutr_ctx_set_lut1d", "lutr_apply_yuv_lut1d", "lutr_apply_planar_rgb_lut1d",
     "lutr_apply_yuv_stack", "lutr_apply_yuv_stack_mix", "lutr_apply_yuv_stack_matte",
     "lutr_apply_yuv_stack_matrix", "lutr_apply_rgb_stack", "lutr_apply_yuv_stack_to_rgb",
-    "lutr_resize_filter", "lutr_resize_planes", "lutr_dither_mask",
+    "lutr_resize_filter", "lutr_resize_planes", "lutr_resize_plan", "lutr_dither_mask",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
     "lutr_max_waves_knob", "lutr_max_blocks_knob",
 )
@@ -298,6 +298,7 @@ def load() -> C.CDLL:
     lib.lutr_dither_mask.argtypes = [C.POINTER(C.c_uint16)]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]
+    lib.lutr_resize_plan.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(ci)]
     lib.lutr_ctx_set_variant.argtypes = [vp, ci]
     lib.lutr_ctx_set_precision.argtypes = [vp, ci]
     lib.lutr_ctx_last_kernel.argtypes = [vp]
@@ -373,6 +374,19 @@ def resize_filter(src: int, dst: int, cs: int = 0, cosited: bool = False):
     check(lib.lutr_resize_filter(src, dst, cs, int(cosited), start.ctypes.data_as(C.POINTER(C.c_int)),
                                  w.ctypes.data_as(C.POINTER(C.c_int16)), C.byref(taps)))
     return start, w
+
+
+#: the words of lutr_resize_plan's out[8], in order
+RESIZE_PLAN_FIELDS = ("th", "rows", "lds", "spx", "spy", "nx_max", "ny_max", "tiles_per_frame")
+
+
+def resize_plan(family: str, depth: int, csx: int, csy: int, chroma_loc, sw: int, sh: int, dw: int, dh: int) -> dict:
+    """lutr_resize_plan (host only): the launch plan of lutr_resize_planes for `family` ("yuv" | "gbr") frames of sw x sh resized to
+    dw x dh, as a dict of RESIZE_PLAN_FIELDS.  `chroma_loc` is a CHROMA_LOC name or None."""
+    out = (C.c_int * len(RESIZE_PLAN_FIELDS))()
+    loc = CHROMA_REPLICATE if chroma_loc is None else CHROMA_LOC[chroma_loc]
+    check(load().lutr_resize_plan(RESIZE_FAMILY[family], depth, csx, csy, loc, sw, sh, dw, dh, out))
+    return dict(zip(RESIZE_PLAN_FIELDS, out))
 
 
 def check(rc: int) -> None:

@@ -307,6 +307,57 @@ static int resize_table(int src, int dst, int cs, int cosited, std::vector<int> 
     return LUTR_OK;
 }
 
+// What the launch plan needs of one axis table: its taps, and the most source samples an aligned run of 64 (32, 16) outputs reads.
+// start is non-decreasing: the first and the last sample of a run decide its footprint.
+struct RzAxis {
+    int taps;
+    int span[3];
+};
+
+static RzAxis resize_axis(const std::vector<int> &start, int taps)
+{
+    RzAxis a{taps, {0, 0, 0}};
+    const int m = (int)start.size();
+    for (int e = 0; e < 3; e++)
+        for (int u0 = 0, len = 64 >> e; u0 < m; u0 += len)
+            a.span[e] = std::max(a.span[e], start[std::min(u0 + len, m) - 1] + taps - start[u0]);
+    return a;
+}
+
+// The launch plan of a resize, from the axis tables of the three planes (x, y) and the planes' output sizes: the
+// one place that chooses the footprints, the tile height, the staged rows and the tile counts.  Fills every RzArgs field that is
+// not a pointer, a stride or a plane size.
+static void resize_plan(const RzAxis ax[3], const RzAxis ay[3], const int pdw[3], const int pdh[3], RzArgs *A)
+{
+    A->spx = A->nx_max = A->ny_max = 0;
+    for (int i = 0; i < 3; i++) {
+        A->spx = std::max(A->spx, ax[i].span[0]);
+        A->nx_max = std::max(A->nx_max, ax[i].taps);
+        A->ny_max = std::max(A->ny_max, ay[i].taps);
+    }
+    A->spx = (A->spx + 1) & ~1;
+    A->rows = 1;
+    // the tallest tile whose LDS stays within 40 KiB, so that several workgroups share a CU (64 rows on upscales, 32 for 2:1 and
+    // 3:1, 16 for stronger vertical reductions)
+    for (A->th = kRzTileHMax; ; A->th /= 2) {
+        A->spy = 0;
+        for (int i = 0; i < 3; i++) A->spy = std::max(A->spy, ay[i].span[A->th == 64 ? 0 : A->th == 32 ? 1 : 2]);
+        if (A->th == 16 || resize_lds_bytes(*A) <= 40960) break;
+    }
+    // as many staged rows per wave as fit beside the rest of the LDS (the tables and T), at most kRzRows
+    A->rows = kRzRows;
+    while (A->rows > 1 && resize_lds_bytes(*A) > 65536) A->rows--;
+    int tile0 = 0;
+    for (int i = 0; i < 3; i++) {
+        RzPlane &P = A->p[i];
+        P.nx = ax[i].taps; P.ny = ay[i].taps;
+        P.tiles_x = (pdw[i] + kRzTileW - 1) / kRzTileW;
+        P.tile0 = tile0;
+        tile0 += P.tiles_x * ((pdh[i] + A->th - 1) / A->th);
+    }
+    A->tiles_per_frame = tile0;
+}
+
 }  // namespace lutr
 
 using namespace lutr;
@@ -360,8 +411,8 @@ struct lutr_ctx {
     std::vector<std::pair<int, hipEvent_t>> readers;      // (receiver's device, event)
     // output resize (lutr_resize_planes): Q14 tables per axis geometry, uploaded once and kept
     struct RzTable {
-        int src, dst, cs, cosited, taps;
-        int span64, span32, span16;  // most source samples an output tile of 64 (32, 16) samples reads
+        int src, dst, cs, cosited;
+        RzAxis axis;                 // taps, and the most source samples an output tile of 64 (32, 16) samples reads
         int *dev;                    // dst start words, then dst * taps weights (int32)
     };
     std::vector<RzTable> rz_tables;
@@ -2676,11 +2727,6 @@ static int rz_table(lutr_ctx *c, int src, int dst, int cs, int cosited, lutr_ctx
     std::vector<int> st, w;
     int n = 0;
     if (const int rc = resize_table(src, dst, cs, cosited, &st, &w, &n)) return rc;
-    // start is non-decreasing: the first and the last sample of a tile decide its footprint
-    const int m = (int)st.size();
-    int span[3] = {0, 0, 0};
-    for (int e = 0; e < 3; e++)
-        for (int u0 = 0, len = 64 >> e; u0 < m; u0 += len) span[e] = std::max(span[e], st[std::min(u0 + len, m) - 1] + n - st[u0]);
     std::vector<int> host(st);
     host.insert(host.end(), w.begin(), w.end());
     void *p = nullptr;
@@ -2688,15 +2734,14 @@ static int rz_table(lutr_ctx *c, int src, int dst, int cs, int cosited, lutr_ctx
     if (e != hipSuccess) { set_error("hipMalloc(resize table): %s", hipGetErrorString(e)); return LUTR_ENOMEM; }
     e = hipMemcpy(p, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(p); return hip_fail(e, "hipMemcpy(resize table)"); }
-    c->rz_tables.push_back({src, dst, cs, cosited, n, span[0], span[1], span[2], (int *)p});
+    c->rz_tables.push_back({src, dst, cs, cosited, resize_axis(st, n), (int *)p});
     *out = c->rz_tables.back();
     return LUTR_OK;
 }
 
-int lutr_resize_planes(lutr_ctx *c, int family, int depth, int csx, int csy, int chroma_loc, int sw, int sh, int dw, int dh,
-                       int nframes, const lutr_planes *src, lutr_planes *dst)
+// The geometry checks lutr_resize_planes and lutr_resize_plan share.
+static int check_resize_geometry(int family, int depth, int csx, int csy, int chroma_loc, int sw, int sh, int dw, int dh, int nframes)
 {
-    if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
     if (family != LUTR_RESIZE_YUV && family != LUTR_RESIZE_GBR) { set_error("unknown plane family %d", family); return LUTR_EINVAL; }
     if (depth < 8 || depth > 16) { set_error("unsupported depth %d", depth); return LUTR_EINVAL; }
     if (csx < 0 || csx > 1 || csy < 0 || csy > 1 || (family == LUTR_RESIZE_GBR && (csx || csy))) {
@@ -2715,15 +2760,53 @@ int lutr_resize_planes(lutr_ctx *c, int family, int depth, int csx, int csy, int
         set_error("resize %dx%d -> %dx%d outside the limits 1/8 <= dst/src <= 16 per axis", sw, sh, dw, dh);
         return LUTR_EINVAL;
     }
+    return LUTR_OK;
+}
+
+// The three planes' sizes (luma, chroma, chroma) of a w x h frame subsampled by 2^csx x 2^csy.
+static void plane_dims(int w, int h, int csx, int csy, int pw[3], int ph[3])
+{
+    for (int i = 0; i < 3; i++) { pw[i] = chroma_dim(w, i ? csx : 0); ph[i] = chroma_dim(h, i ? csy : 0); }
+}
+
+int lutr_resize_plan(int family, int depth, int csx, int csy, int chroma_loc, int sw, int sh, int dw, int dh, int *out)
+{
+    if (!out) { set_error("lutr_resize_plan: null out pointer"); return LUTR_EINVAL; }
+    if (const int rc = check_resize_geometry(family, depth, csx, csy, chroma_loc, sw, sh, dw, dh, 1)) return rc;
+    const int cox = chroma_loc == LUTR_CHROMA_LEFT || chroma_loc == LUTR_CHROMA_TOPLEFT;
+    const int coy = chroma_loc == LUTR_CHROMA_TOPLEFT;
+    int pdw[3], pdh[3];
+    plane_dims(dw, dh, csx, csy, pdw, pdh);
+    RzAxis ax[3], ay[3];
+    std::vector<int> st, w;
+    for (int i = 0; i < 3; i++) {
+        const int cx = i ? csx : 0, cy = i ? csy : 0;
+        int n = 0;
+        if (const int rc = resize_table(sw, dw, cx, cx ? cox : 0, &st, &w, &n)) return rc;
+        ax[i] = resize_axis(st, n);
+        if (const int rc = resize_table(sh, dh, cy, cy ? coy : 0, &st, &w, &n)) return rc;
+        ay[i] = resize_axis(st, n);
+    }
+    RzArgs A{};
+    resize_plan(ax, ay, pdw, pdh, &A);
+    const int lds = (int)resize_lds_bytes(A);
+    const int plan[8] = {A.th, A.rows, lds, A.spx, A.spy, A.nx_max, A.ny_max, A.tiles_per_frame};
+    std::memcpy(out, plan, sizeof(plan));
+    if (lds > 65536) { set_error("resize footprint needs %d bytes of LDS (at most 65536)", lds); return LUTR_EINVAL; }
+    return LUTR_OK;
+}
+
+int lutr_resize_planes(lutr_ctx *c, int family, int depth, int csx, int csy, int chroma_loc, int sw, int sh, int dw, int dh,
+                       int nframes, const lutr_planes *src, lutr_planes *dst)
+{
+    if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
+    if (const int rc = check_resize_geometry(family, depth, csx, csy, chroma_loc, sw, sh, dw, dh, nframes)) return rc;
     if (nframes == 0) return LUTR_OK;
     if (const int rc = check_planes_set(src, dst)) return rc;
     const int es = depth > 8 ? 2 : 1;
     int psw[3], psh[3], pdw[3], pdh[3];
-    for (int i = 0; i < 3; i++) {
-        const int cx = i ? csx : 0, cy = i ? csy : 0;
-        psw[i] = chroma_dim(sw, cx); psh[i] = chroma_dim(sh, cy);
-        pdw[i] = chroma_dim(dw, cx); pdh[i] = chroma_dim(dh, cy);
-    }
+    plane_dims(sw, sh, csx, csy, psw, psh);
+    plane_dims(dw, dh, csx, csy, pdw, pdh);
     // every destination sample reads a neighbourhood of source samples: no destination may overlap a source
     Span ss[3], ds[3];
     side_spans(planar_side("source", src, LUTR_FMT(depth, csx, csy)), FrameGeom{sw, sh, 0, sh, nframes}, ss);
@@ -2747,37 +2830,22 @@ int lutr_resize_planes(lutr_ctx *c, int family, int depth, int csx, int csy, int
     RzArgs A{};
     A.depth = depth;
     lutr_ctx::RzTable tx[3], ty[3];
+    RzAxis ax[3], ay[3];
     for (int i = 0; i < 3; i++) {
         const int cx = i ? csx : 0, cy = i ? csy : 0;
         if (const int rc = rz_table(c, sw, dw, cx, cx ? cox : 0, &tx[i])) return rc;
         if (const int rc = rz_table(c, sh, dh, cy, cy ? coy : 0, &ty[i])) return rc;
-        A.spx = std::max(A.spx, tx[i].span64);
-        A.nx_max = std::max(A.nx_max, tx[i].taps);
-        A.ny_max = std::max(A.ny_max, ty[i].taps);
+        ax[i] = tx[i].axis; ay[i] = ty[i].axis;
     }
-    A.spx = (A.spx + 1) & ~1;
-    A.rows = 1;
-    // the tallest tile whose LDS stays within 40 KiB, so that several workgroups share a CU (64 rows on upscales, 32 for 2:1 and
-    // 3:1, 16 for stronger vertical reductions)
-    for (A.th = kRzTileHMax; ; A.th /= 2) {
-        A.spy = 0;
-        for (int i = 0; i < 3; i++) A.spy = std::max(A.spy, A.th == 64 ? ty[i].span64 : A.th == 32 ? ty[i].span32 : ty[i].span16);
-        if (A.th == 16 || resize_lds_bytes(A) <= 40960) break;
-    }
-    int tile0 = 0;
+    resize_plan(ax, ay, pdw, pdh, &A);
     for (int i = 0; i < 3; i++) {
         RzPlane &P = A.p[i];
         P.s = (const uint8_t *)src->data[i]; P.d = (uint8_t *)dst->data[i];
         P.ss = src->stride[i]; P.ds = dst->stride[i]; P.sfs = src->frame_stride[i]; P.dfs = dst->frame_stride[i];
         P.sw = psw[i]; P.sh = psh[i]; P.dw = pdw[i]; P.dh = pdh[i];
-        P.nx = tx[i].taps; P.ny = ty[i].taps;
         P.xs = tx[i].dev; P.xw = tx[i].dev + pdw[i];
         P.ys = ty[i].dev; P.yw = ty[i].dev + pdh[i];
-        P.tiles_x = (pdw[i] + kRzTileW - 1) / kRzTileW;
-        P.tile0 = tile0;
-        tile0 += P.tiles_x * ((pdh[i] + A.th - 1) / A.th);
     }
-    A.tiles_per_frame = tile0;
     const char *name = launch_resize(c->stream, A, nframes);
     if (!name) { set_error("resize launch too large (split the batch)"); return LUTR_EINVAL; }
     return finish_launch(c, name);

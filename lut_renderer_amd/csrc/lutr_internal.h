@@ -550,7 +550,7 @@ struct RzArgs {
     int spx, spy;                    // largest footprint of a tile over the three planes: source columns, source rows
     int nx_max, ny_max;
     int th;                          // output rows per tile
-    int rows;                        // staged source rows per wave and step, 1..kRzRows (set by launch_resize)
+    int rows;                        // staged source rows per wave and step, 1..kRzRows (the most whose LDS fits 64 KiB)
 };
 size_t resize_lds_bytes(const RzArgs &A);
 // nullptr = too many tiles, or a footprint that does not fit the workgroup's LDS

@@ -128,12 +128,10 @@ size_t resize_lds_bytes(const RzArgs &A)
 
 const char *launch_resize(hipStream_t st, RzArgs A, int nframes)
 {
-    // as many staged rows per wave as fit beside the rest of the LDS (the tables and T), at most kRzRows
-    A.rows = kRzRows;
-    while (A.rows > 1 && resize_lds_bytes(A) > 65536) A.rows--;
+    // th, rows and the footprints come from the host's plan (resize_plan, lutr_api.cpp); the kernel's register batch holds kRzRows rows
     const long long blocks = (long long)A.tiles_per_frame * nframes;
     const size_t lds = resize_lds_bytes(A);
-    if (blocks <= 0 || blocks > 0x7fffffffll || lds > 65536) return nullptr;
+    if (blocks <= 0 || blocks > 0x7fffffffll || lds > 65536 || A.rows < 1 || A.rows > kRzRows) return nullptr;
     const dim3 grid((unsigned)blocks), block(256);
     if (A.depth > 8) {
         hipLaunchKernelGGL(k_resize<1>, grid, block, lds, st, A);
