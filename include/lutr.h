@@ -978,6 +978,40 @@ int lutr_apply_yuv_stack_to_rgb(lutr_ctx *ctx, const lutr_yuv_params *p, const l
                                 const lutr_rgb_matrix *mtx, int dst_kind, int w, int h, int nframes, const lutr_planes *src,
                                 const lutr_planes *dst_planar, const lutr_packed *dst_packed, int row0, int rows);
 
+/* ---- the stage stack on semi-planar sides: a hardware-decoded p010le / nv12 file through lut1d,cdl,lut3d into a
+ *      yuv422p10le master or back into p010le / nv12 for a hardware encoder, without a de-interleave pass ahead of the stack and
+ *      an interleave pass behind it ----
+ * lutr_apply_yuv_stack with each side in the container its layout names (lutr_yuv_layout, as lutr_apply_yuv_semi takes it): three
+ * planes, or luma and one plane of (Cb, Cr) pairs -- (Cr, Cb) with swap --, 16-bit codes `shift` bits up in their words.  The
+ * result is bit-identical to lutr_apply_yuv_stack on the same samples held in three planes, put into the destination's
+ * container: the list, its compiled steps, the union block of the two layouts (chroma replicated over its input block, averaged
+ * over its output block), the full-range prologue and everything else *p expresses are that call's arithmetic unchanged.  On
+ * input the code is word >> shift whatever the low bits hold; on output the word is code << shift, low bits zero.
+ * A semi-planar side is 4:2:0 or 4:2:2; the other side may be 4:2:0 / 4:2:2 / 4:4:4, planar or semi-planar, at 8..16 bit: this is
+ * the one call that changes the chroma subsampling of a semi-planar frame.  Stages: 1..4 out of LUT3D, LUT3D_2, LUT1D, CDL, each at
+ * most once, in any order, on lutr_apply_yuv_stack's terms (a .csp prelut where that call allows it).  row0 and rows must be
+ * multiples of the union block height unless row0 + rows == h.  When both layouts are planar with shift 0 this IS
+ * lutr_apply_yuv_stack: same kernels, bits, last kernel.  Always strict precision (fast / fma32 run strict here).
+ * Not in place: no byte range of a source plane may overlap one of a destination plane, over all rows and frames; a plane of
+ * pairs spans 2 * ceil(w / 2) samples a row and a semi-planar side has no plane 2.
+ * LUTR_EINVAL with a message, before anything touches the device: a null layout; everything lutr_apply_yuv_stack refuses about the
+ * list and its resources -- a MATRIX stage with that call's words; everything lutr_apply_yuv_semi refuses about a layout (a wrong
+ * shift, swap without semi, semi / swap outside 0 | 1, a semi-planar side that is 4:4:4, a missing plane, odd 16-bit planes);
+ * variant vec_lds; an overlap as above.
+ * Kernels: "k_yuv_stack_semi_vec<win,wout,icsx,icsy,ocsx,ocsy,tri,lds>[stages]" (nearest / trilinear / tetrahedral stages; 8 -> 8,
+ * 16 -> 16 and 16 -> 8 bit containers; the eight layout pairs with a 4:2:0 / 4:2:2 side; width a multiple of 8 luma samples, 4 for
+ * 16 -> 16; positive strides aligned to the accesses -- a plane of pairs moves twice the bytes of a planar chroma plane per
+ * access; the tables in LDS when they fit 24 KB, LUTR_STACK_LDS=0 | 1 as for lutr_apply_yuv_stack),
+ * "k_yuv_stack_semi_generic[stages]" for everything else (one thread per union block; any depth 8..16, stride, alignment or size;
+ * all five modes), "<vector kernel>+k_yuv_stack_semi_generic[stages]" for a ragged width on aligned rows; [stages] as
+ * lutr_apply_yuv_stack writes it.  vec_global fails with LUTR_EINVAL where the vector kernel cannot take the layout.
+ * Not covered: a matrix stage, a strength or a matte, dither, chroma siting, a resize, a second output, alpha (semi-planar formats
+ * carry none), packed 4:2:2 / v210 / RGB sides, 4:4:4 semi-planar (nv24, p410le), big-endian containers, a tile (LDS window)
+ * kernel. */
+int lutr_apply_yuv_stack_semi(lutr_ctx *ctx, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                              const lutr_yuv_layout *in_layout, const lutr_yuv_layout *out_layout, int w, int h, int nframes,
+                              const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
+
 /* ---- the alpha plane of yuva* / gbrap* frames: ProRes 4444 (yuva444p10le / 12le), VP8 / VP9 with alpha
  *      (yuva420p), PNG / TIFF / EXR sequences with alpha (rgba, rgba64le, gbrap*, gbrapf32le).  In the reference's chain lut3d
  *      copies the alpha plane through and format=<pix_fmt> keeps, converts, drops or makes it (ffmpeg.py:246, :304-310) ---- */

@@ -26,9 +26,9 @@ from .rgbmatrix import as_rgb_matrix
 from .cube import CubeLut, as_lut1d, read_cube, read_lut, read_lut1d
 from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc, check_container_options,
                       check_dual_options, check_lut1d_options, check_lut2, check_premul_options, check_stack_options,
-                      check_rgb_stack_options, check_yuv2rgb_options, check_yuv2rgb_stack_options, implied_stages, packed_frame_width, parse_packed_yuv_fmt,
+                      SEMI_STAGES_EXCLUSIVE, check_rgb_stack_options, check_semi_stack_options, check_yuv2rgb_options, check_yuv2rgb_stack_options, implied_stages, packed_frame_width, parse_packed_yuv_fmt,
                       parse_pix_fmt, parse_rgb_source, parse_semi_fmt, parse_size, parse_stages, parse_v210_fmt, premul_to_yuv,
-                      refuse_alpha_resize, source_bit_depth, v210_frame_width, yuv_side)
+                      refuse_alpha_resize, semi_stack_side, source_bit_depth, v210_frame_width, yuv_side)
 from .params import ProcessingParams, VideoInfo
 from .plan import LutPlan, output_color_tags, resolve_lut_plan
 
@@ -93,7 +93,7 @@ def _parsed_lut(cube) -> Optional[CubeLut]:
 
 
 def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = None, alpha_mode: str = "straight",
-                    rgb_out: Optional[str] = None) -> dict:
+                    rgb_out: Optional[str] = None, semi_stack: bool = False) -> dict:
     """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv (`pix_fmt` / `out_pix_fmt` planar YUV -- yuva* too, DESIGN.md
     3.16: without `out_pix_fmt` the source's format, alpha included, is kept; a named output without alpha drops it, one with alpha
     on a source without is filled opaque; the full-range prologue's default output stays the 8-bit yuv4xxp -- , semi-planar names
@@ -106,7 +106,9 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
     float call and is a ValueError for every other call; "straight" (the default) returns what it always returned.
     `rgb_out` (gbrp .. gbrp16le, gbrap*, or a packed name) asks for an RGB output from a planar YUV `pix_fmt`: the
     arguments are then those of LutEngine.apply_yuv_to_rgb (`is_rgb_out_call(kw)`), the LUT runs at that format's depth, and a plan
-    with the full-range prologue (which lands at 8 bit) takes an 8-bit `rgb_out` only.  Not together with `out_pix_fmt`."""
+    with the full-range prologue (which lands at 8 bit) takes an 8-bit `rgb_out` only.  Not together with `out_pix_fmt`.
+    `semi_stack`: the call is `LutEngine.apply_yuv_stack_semi`'s -- the sides are checked as that pass takes them
+    (semi-planar or planar YUV, any pair of subsamplings) and not as `apply_yuv` does."""
     if plan.interp not in _ENGINE_INTERP:
         raise ValueError(f"lut3d has no interpolation mode '{plan.interp}'")
     premul = check_alpha_mode(alpha_mode)
@@ -125,6 +127,10 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
         else:
             kw.update(range_src="tv", range_in="tv")
         return kw
+    if semi_stack:
+        # (the sides of the stack on semi-planar frames: its own refusals of a name, and any pair of subsamplings)
+        semi_stack_side(pix_fmt, "pix_fmt")
+        semi_stack_side(out_pix_fmt or pix_fmt, "out_pix_fmt")
     rgb = parse_rgb_source(pix_fmt)
     if premul and rgb is not None:
         check_premul_options(pix_fmt, out_pix_fmt, to_yuv=premul_to_yuv(pix_fmt, out_pix_fmt))
@@ -161,7 +167,8 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
     # a semi-planar source or output (nv12, p010le, ..) is the same chain on another container
     # (so is a packed 4:2:2 one: uyvy422, y210le, ..)
     # (and v210)
-    check_container_options(pix_fmt, out_pix_fmt, kinds=("v210", "packed"))     # names the packings this path does not take
+    if not semi_stack:
+        check_container_options(pix_fmt, out_pix_fmt, kinds=("v210", "packed"))     # names the packings this path does not take
     semi_src = parse_semi_fmt(pix_fmt) or parse_packed_yuv_fmt(pix_fmt) or parse_v210_fmt(pix_fmt)
     src = semi_src or parse_pix_fmt(pix_fmt)
     if src.family != "yuv":
@@ -181,7 +188,8 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
         kw.update(range_src="tv", range_in="tv", lut_depth=src.depth)
         default_out = kw["pix_fmt"]
     kw["out_pix_fmt"] = out_pix_fmt or default_out
-    check_container_options(kw["pix_fmt"], kw["out_pix_fmt"])    # (one subsampling on both sides of a semi-planar call)
+    if not semi_stack:
+        check_container_options(kw["pix_fmt"], kw["out_pix_fmt"])    # (one subsampling on both sides of a semi-planar call)
     if premul:
         check_premul_options(kw["pix_fmt"], kw["out_pix_fmt"], range_src=kw["range_src"], range_in=kw["range_in"],
                              lut_depth=kw["lut_depth"])
@@ -327,7 +335,8 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               resolution: Optional[str] = None, second_pix_fmt: Optional[str] = None, engine_dither: Optional[str] = None,
               cube2=None, interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None, cdl_id: Optional[str] = None,
               lut1d=None, interp1d: str = "linear", stages=None, strength=None, matte=None, matte_depth: Optional[int] = None,
-              matte_invert: bool = False, rgb_out: Optional[str] = None, rgb_matrix=None, rgb_stages=None, rgb_out_stages=None):
+              matte_invert: bool = False, rgb_out: Optional[str] = None, rgb_matrix=None, rgb_stages=None, rgb_out_stages=None,
+              semi_stages=None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -457,7 +466,14 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     between the conversion to integer RGB and the stores, e.g. rgb_out="rgb48le", rgb_out_stages="lut1d,cdl,lut3d".  It needs
     `rgb_out`; `stages` or `rgb_stages` together with it, dither, resolution, chroma_loc, strength, matte, premultiplied alpha
     and a second output are ValueErrors naming them, and the format rules are those of `rgb_out`.  None (default) leaves every
-    route as it is."""
+    route as it is.
+
+    `semi_stages` is `stages` for a call with a semi-planar side -- `pix_fmt`, `out_pix_fmt` or both one of nv12,
+    nv21, nv16, p010le .. p216le, that side (Y, CbCr) as above: the same lists without the matrix stage, the same resources (`cube`,
+    `cube2`, `lut1d`, `cdl`), in ONE pass (LutEngine.apply_yuv_stack_semi) with no de-interleave ahead of it and no interleave
+    behind it; the other side may be planar 4:2:0 / 4:2:2 / 4:4:4 at 8..16 bit, so p010le -> yuv422p10le is one call.  `stages`,
+    `rgb_stages` or `rgb_out_stages` together with it, two planar sides, a matrix stage, strength, matte, dither, resolution,
+    chroma_loc, premultiplied alpha, yuva*, a second output and a packed / v210 / RGB / float side are ValueErrors naming them."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -478,7 +494,9 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         if stages is not None or rgb_stages is not None:
             raise ValueError("rgb_out_stages and stages / rgb_stages are mutually exclusive: stages is the list of a YUV source with "
                              "a YUV output, rgb_stages that of an RGB source, rgb_out_stages that of a YUV source with rgb_out")
-    if rgb_matrix is not None and stages is None and rgb_stages is None and rgb_out_stages is None:
+    if semi_stages is not None and (stages is not None or rgb_stages is not None or rgb_out_stages is not None):
+        raise ValueError(SEMI_STAGES_EXCLUSIVE)
+    if rgb_matrix is not None and stages is None and rgb_stages is None and rgb_out_stages is None and semi_stages is None:
         raise ValueError("rgb_matrix needs stages: a matrix stage has no implied position (e.g. stages='lut1d,matrix,lut3d')")
     rgb_src = parse_rgb_source(pix_fmt)
     if rgb_stages is not None and rgb_src is None:
@@ -552,13 +570,24 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
             if own:
                 eng.sync()
         return result, output_color_tags(plan.output_policy)
-    kw = engine_call_for(plan, pix_fmt, out_pix_fmt, alpha_mode)
+    # (semi_stages: that pass's own sides; its check below is told the alpha mode)
+    kw = engine_call_for(plan, pix_fmt, out_pix_fmt, alpha_mode) if semi_stages is None else \
+        engine_call_for(plan, pix_fmt, out_pix_fmt, "straight", semi_stack=True)
     refuse_alpha_resize(kw.get("out_pix_fmt"), out_size)        # (the resize takes three planes)
     kw["dither"] = zdither if engine_dither is None else resolve_engine_dither(engine_dither, zdither)
     if precision not in ("strict", "fast", "fma32"):
         raise ValueError(f"unknown precision '{precision}' (strict | fast | fma32)")
     if cube2 is None and interp2 is not None:
         raise ValueError("interp2 is the mode of the second LUT: it needs cube2")
+    if semi_stages is not None:
+        # the stage stack on semi-planar sides: a route of its own, opt-in by name
+        call = {k: v for k, v in kw.items() if k not in ("dither", "interp", "alpha_mode")}
+        result = _stack_route(
+            planes, out, check_semi_stack_options, "apply_yuv_stack_semi", (kw["pix_fmt"], kw["out_pix_fmt"]), semi_stages,
+            kw.get("interp"), *loaded, dict(dither=kw["dither"], chroma_loc=chroma_loc, out_size=out_size, alpha_mode=alpha_mode,
+                                            out2_pix_fmt=second_pix_fmt, strength=strength, precision=precision, matte=matte),
+            lambda: call)
+        return result, output_color_tags(plan.output_policy)
     if "alpha_mode" in kw:
         check_premul_options(kw["pix_fmt"], kw["out_pix_fmt"], dither=kw["dither"], chroma_loc=chroma_loc, out_size=out_size,
                              range_src=kw.get("range_src", "tv"), range_in=kw.get("range_in"), lut_depth=kw.get("lut_depth"),

@@ -125,6 +125,13 @@ def build_parser() -> argparse.ArgumentParser:
                          "--rgb-out rgb48le --rgb-out-stages lut1d,cdl,lut3d; needs --rgb-out; no dither, --chroma-loc, --out-size, "
                          "--strength, --matte, --second-output or --alpha-mode premultiplied; not together with --stages or "
                          "--rgb-stages")
+    ap.add_argument("--semi-stages", default=None, metavar="LIST",
+                    help="engine setting: --stages for a call with a semi-planar side (--pix-fmt, --out-pix-fmt or both one of nv12, "
+                         "nv21, nv16, p010le .. p216le; DESIGN.md 3.28): the same lists and files without the matrix stage, in ONE "
+                         "pass with no de-interleave ahead of it and no interleave behind it; the other side may be planar 4:2:0 / "
+                         "4:2:2 / 4:4:4, e.g. --pix-fmt p010le --out-pix-fmt yuv422p10le --semi-stages lut1d,cdl,lut3d; no dither, "
+                         "--chroma-loc, --out-size, --strength, --matte, --second-output or --alpha-mode premultiplied; not "
+                         "together with --stages, --rgb-stages or --rgb-out-stages")
     ap.add_argument("--rgb-matrix", default=None, metavar="\"M00 M01 M02 M10 .. M22\"",
                     help="engine setting: the nine numbers, row-major, of the RGB matrix a 'matrix' stage of --stages applies "
                          "(DESIGN.md 3.25; a gamut conversion, a white-balance or channel-mixer trim, a channel swap): "
@@ -304,6 +311,26 @@ def rgb_out_stack_call_from_args(args, plan) -> dict:
     return _stack_call(call, r, "rgb_out_stages")
 
 
+def semi_stack_call_from_args(args, plan) -> dict:
+    """The keyword arguments of `apply_yuv_stack_semi` for --semi-stages, with `pix_fmt` / `out_pix_fmt` as every
+    call of `plan_from_args` carries them and the parsed list under `semi_stages`: the list as --stages parses it, every refusal
+    of `check_semi_stack_options`, the matrices and ranges `engine_call_for` gives the plan."""
+    from .api import engine_call_for
+    from .formats import SEMI_STAGES_EXCLUSIVE, check_semi_stack_options
+    if any(getattr(args, k, None) is not None for k in ("stages", "rgb_stages", "rgb_out_stages")):
+        raise ValueError(SEMI_STAGES_EXCLUSIVE)
+    if getattr(args, "rgb_out", None) is not None:
+        raise ValueError("--rgb-out names the RGB output of a planar YUV source: with --semi-stages the output is --out-pix-fmt")
+    r = _stage_list_from_args(args, plan.interp, "--semi-stages", args.semi_stages)
+    _st, fin, fout = check_semi_stack_options(
+        args.pix_fmt, args.out_pix_fmt, stages=r["stages"], **r["list"],
+        dither="error_diffusion" if args.zscale_dither == "error_diffusion" else getattr(args, "engine_dither", None) or "none",
+        precision=getattr(args, "precision", None), **r["options"])
+    kw = engine_call_for(plan, args.pix_fmt, args.out_pix_fmt, "straight", semi_stack=True)
+    call = {k: v for k, v in kw.items() if k not in ("interp", "alpha_mode", "dither")}
+    return _stack_call(call, r, "semi_stages")
+
+
 def matte_from_args(args):
     """None without --matte, else dict(matte=the path, matte_pix_fmt=, matte_invert=); --matte-pix-fmt / --matte-invert without
     --matte, '-' and an unknown format are errors."""
@@ -347,11 +374,15 @@ def plan_from_args(args):
     stages = getattr(args, "stages", None)
     rgb_stages = getattr(args, "rgb_stages", None)
     rgb_out_stages = getattr(args, "rgb_out_stages", None)
-    if args.cube is None and lut1d is None and stages is None and rgb_stages is None and rgb_out_stages is None:
+    semi_stages = getattr(args, "semi_stages", None)
+    if args.cube is None and lut1d is None and stages is None and rgb_stages is None and rgb_out_stages is None and semi_stages is None:
         raise ValueError("--cube is required unless --lut1d is given")
     plan = resolve_lut_plan(params, args.cube if args.cube is not None else "engine.cube", info)
     alpha_mode = getattr(args, "alpha_mode", None) or "straight"
     rgb_out = getattr(args, "rgb_out", None)
+    if semi_stages is not None:
+        # the stage stack on semi-planar sides: a route of its own
+        return plan, semi_stack_call_from_args(args, plan), w, h
     if rgb_out_stages is not None:
         # the stage stack from a YUV source into an RGB frame: a route of its own
         return plan, rgb_out_stack_call_from_args(args, plan), w, h
@@ -455,7 +486,8 @@ def plan_from_args(args):
 def main(argv=None) -> int:
     ap = build_parser()
     args = ap.parse_args(argv)
-    if args.cube is None and args.lut1d is None and args.stages is None and args.rgb_stages is None and args.rgb_out_stages is None:
+    if args.cube is None and args.lut1d is None and args.stages is None and args.rgb_stages is None and args.rgb_out_stages is None \
+            and args.semi_stages is None:
         ap.error("the following arguments are required: --cube (or --lut1d for a 1D LUT alone)")
 
     stop = {"flag": False}
@@ -496,7 +528,7 @@ def main(argv=None) -> int:
         second_fmt = kw.pop("out2_pix_fmt", None)
         if "matte" in kw:
             kw["matte"] = MatteReader(kw.pop("matte"), kw.pop("matte_pix_fmt"), w, h)
-        stacked = any(k in kw for k in ("stages", "rgb_stages", "rgb_out_stages"))   # (the list names its lut3d2 / lut1d stages)
+        stacked = any(k in kw for k in ("stages", "rgb_stages", "rgb_out_stages", "semi_stages"))   # (the list names its lut3d2 / lut1d stages)
         pipe = HostPipeline(eng, pix_fmt, w, h, batch=args.batch, out_pix_fmt=out_fmt, out_size=args.out_size,
                             second_pix_fmt=second_fmt, chain=lut2 is not None and not stacked,
                             lut1d=args.lut1d is not None and not stacked, rgb_out=rgb_out, **kw)

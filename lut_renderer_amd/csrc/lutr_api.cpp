@@ -1269,7 +1269,8 @@ static int check_disjoint(const char *what, bool name_src, const Span *s, int ns
 // One side of a call: the name the messages give it, its planes, and the depth and chroma layout of its format code (depth 32:
 // the float samples of gbrpf32).
 // packed: the side is one plane (a packed 4:2:2 or v210 container) of packed_row bytes a row, not three planes.
-struct Side { const char *name; const lutr_planes *pl; int depth, csx, csy; bool packed; long long packed_row; };
+// semi: the side is two planes, luma and one plane of chroma pairs (2 * ceil(w / 2) samples a row); plane 2 is absent.
+struct Side { const char *name; const lutr_planes *pl; int depth, csx, csy; bool packed; long long packed_row; bool semi = false; };
 
 static Side planar_side(const char *name, const lutr_planes *pl, int fmt)
 {
@@ -1304,6 +1305,11 @@ static int side_spans(const Side &s, const FrameGeom &G, Span out[3])
         return 1;
     }
     planar_spans(s.pl, s.csx, s.csy, G.w, G.h, s.depth > 16 ? 4 : s.depth > 8 ? 2 : 1, G.nframes, out);
+    if (s.semi) {
+        out[1] = plane_span(s.pl->data[1], s.pl->stride[1], s.pl->frame_stride[1], chroma_dim(G.h, s.csy),
+                            2ll * chroma_dim(G.w, 1) * (s.depth > 8 ? 2 : 1), G.nframes);
+        return 2;
+    }
     return 3;
 }
 
@@ -1912,9 +1918,13 @@ static int stack_device_consts(lutr_ctx *c, const StackList &T, const lutr_cdl *
 // `matte` (with `mix`): the matte of lutr_apply_yuv_stack_matte, its pointer, depth and invert already checked.
 // `with_mtx` (without `mix`): the call is lutr_apply_yuv_stack_matrix's, the one entry that takes a matrix stage;
 // `mtx` is its matrix, or nullptr.
+// `iy`, `oy` (without `mix` and `with_mtx`): the containers of the two sides of lutr_apply_yuv_stack_semi, both
+// or neither; with them a side may be two planes, and the kernels are the semi forms.
+static int check_semi_side(const Side &s, const lutr_yuv_layout *y, int nframes);
 static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
                            const MixConsts *mix, const lutr_matte *matte, bool with_mtx, const lutr_rgb_matrix *mtx, int w, int h,
-                           int nframes, const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+                           int nframes, const lutr_planes *src, const lutr_planes *dst, int row0, int rows,
+                           const lutr_yuv_layout *iy = nullptr, const lutr_yuv_layout *oy = nullptr)
 {
     if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
     StackList T;
@@ -1925,9 +1935,17 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
     UnionCall U; const FrameGeom G{w, h, row0, rows, nframes};
     if (const int rc = union_open(*p, src, dst, &U)) return rc;
     const Side &Si = U.side[0], &Di = U.side[1];
+    if (iy) {
+        // each side's layout against its format, the planes it has and their alignment (union_planes_ready's part, per container)
+        if (const int rc = check_semi_side(Si, iy, nframes)) return rc;
+        if (const int rc = check_semi_side(Di, oy, nframes)) return rc;
+        U.side[0].semi = iy->semi != 0;
+        U.side[1].semi = oy->semi != 0;
+    }
     if (const int rc = union_rules(c, U, G, "stack", "the stack pass")) return rc;
     if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
-    if (const int rc = union_planes_ready(U, G)) return rc;
+    if (!iy)
+        if (const int rc = union_planes_ready(U, G)) return rc;
     if (const int rc = check_sides_disjoint("the stack pass", true, Si, Di, G)) return rc;
     MatteConsts A{};
     if (matte) {
@@ -1956,8 +1974,16 @@ static int apply_yuv_stack(lutr_ctx *c, const lutr_yuv_params *p, const lutr_sta
     LutConsts L{}, L2{}; StackConsts S{}; MtxConsts X{}; PlaneSet P;
     if (const int rc = stack_device_consts(c, T, cdl, mtx, p->lut_depth, &L, &L2, &S, &X)) return rc;
     fill_planes(&P, src, dst);
-    const char *name = launch_yuv_stack(c->stream, c->variant, L, L2, S, U.K, P, G, Si.depth, Di.depth, Si.csx, Si.csy, Di.csx, Di.csy, mix,
-                                        matte ? &A : nullptr, with_mtx ? &X : nullptr);
+    const char *name;
+    if (iy) {
+        if (iy->semi) clear_planes(&P, true, 2);
+        if (oy->semi) clear_planes(&P, false, 2);
+        const SemiArgs Y{iy->semi, iy->swap, iy->shift, oy->semi, oy->swap, oy->shift};
+        name = launch_yuv_stack_semi(c->stream, c->variant, L, L2, S, U.K, P, G, Y, Si.depth, Di.depth, Si.csx, Si.csy, Di.csx, Di.csy);
+    } else {
+        name = launch_yuv_stack(c->stream, c->variant, L, L2, S, U.K, P, G, Si.depth, Di.depth, Si.csx, Si.csy, Di.csx, Di.csy, mix,
+                                matte ? &A : nullptr, with_mtx ? &X : nullptr);
+    }
     if (!name) return finish_launch(c, nullptr);
     const std::string full = std::string(name) + "[" + T.list + "]";
     return finish_launch(c, full.c_str());
@@ -2015,6 +2041,18 @@ int lutr_apply_yuv_stack_matte(lutr_ctx *c, const lutr_yuv_params *p, const lutr
     }
     const MixConsts M{frame_strength, frame_strength ? 1.0f : strength};
     return apply_yuv_stack(c, p, stages, nstages, cdl, &M, matte, false, nullptr, w, h, nframes, src, dst, row0, rows);
+}
+
+// ---- the stack on semi-planar sides: the same pass, each side in its own container, the semi kernels
+int lutr_apply_yuv_stack_semi(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                              const lutr_yuv_layout *in_layout, const lutr_yuv_layout *out_layout, int w, int h, int nframes,
+                              const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+{
+    if (!in_layout || !out_layout) { set_error("stack: null layout"); return LUTR_EINVAL; }
+    if (!in_layout->semi && !out_layout->semi && !in_layout->swap && !out_layout->swap && !in_layout->shift && !out_layout->shift)
+        return lutr_apply_yuv_stack(c, p, stages, nstages, cdl, w, h, nframes, src, dst, row0, rows);   // planar both ways: that call itself
+    return apply_yuv_stack(c, p, stages, nstages, cdl, nullptr, nullptr, false, nullptr, w, h, nframes, src, dst, row0, rows, in_layout,
+                           out_layout);
 }
 
 int lutr_apply_planar_rgb_lut1d(lutr_ctx *c, int depth, int w, int h, int nframes, const lutr_planes *src, const lutr_planes *dst,

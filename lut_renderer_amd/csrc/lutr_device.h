@@ -325,6 +325,15 @@ __device__ __forceinline__ void word_put(uint32_t *w, int i, float v)
     else w[i >> 2] |= u << ((i & 3) * 8);
 }
 
+// sample i of a word vector whose 16-bit codes sit `shift` bits up in their container (p010le: 6): the shift rides in the
+// bit-field extract that unpacks the sample anyway (the vector kernels of lutr_semi.hip and the semi form of lutr_stack.hip)
+template <int WIDE>
+__device__ __forceinline__ float word_code(const uint32_t *w, int i, unsigned shift)
+{
+    if constexpr (WIDE) return (float)__builtin_amdgcn_ubfe(w[i >> 1], (unsigned)(i & 1) * 16u + shift, 16u - shift);
+    else return word_sample<0>(w, i);
+}
+
 template <int NW>
 __device__ __forceinline__ void ld_words(uint32_t *w, const uint8_t *p)
 {

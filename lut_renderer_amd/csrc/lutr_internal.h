@@ -321,6 +321,24 @@ const char *launch_yuv_semi(hipStream_t st, int variant, const LutConsts &L, con
 LUTR_SM_DECL(w00) LUTR_SM_DECL(w11) LUTR_SM_DECL(w10)
 #undef LUTR_SM_DECL
 
+// the stage stack on semi-planar sides (lutr_stack.hip's SEMI forms): launch_yuv_stack's plain call for the eight
+// layout pairs with a 4:2:0 / 4:2:2 side, each side in the container A gives it (as launch_yuv_semi's; any pair, planar both ways
+// included, goes to the generic kernel).  nullptr = the variant cannot take the call (vec_lds always; vec_global on layouts the
+// vector kernel cannot take)
+const char *launch_yuv_stack_semi(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
+                                  const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const SemiArgs &A, int din, int dout,
+                                  int icsx, int icsy, int ocsx, int ocsy);
+const char *launch_yuv_stack_semi_generic(hipStream_t st, unsigned grid, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
+                                          const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const SemiArgs &A, int win,
+                                          int wout, int icsx, int icsy, int ocsx, int ocsy);
+// its vector kernels, one translation unit per container mix (w<in wide><out wide>): nullptr = not a layout pair it has
+#define LUTR_SKS_DECL(tag) \
+    const char *launch_yuv_stack_semi_vec_##tag(hipStream_t st, const LutConsts &L, const LutConsts &L2, const StackConsts &S, \
+                                                const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, int icsx, int icsy, \
+                                                int ocsx, int ocsy, bool tri, bool lds, SemiArgs A);
+LUTR_SKS_DECL(w00) LUTR_SKS_DECL(w11) LUTR_SKS_DECL(w10)
+#undef LUTR_SKS_DECL
+
 // packed 4:2:2 frames (lutr_pkyuv.hip): the container of each side -- planar (three planes) or packed (PlaneSet
 // slot 0 holds the groups, slots 1 and 2 are not read); cf: chroma first in a group (uyvy422), csw: Cr ahead of Cb (yvyu422),
 // 16-bit codes `shift` bits up in their words.  The source is 4:2:2; the destination is 4:2:2, or planar with the layout ocsx,

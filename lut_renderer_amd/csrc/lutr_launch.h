@@ -173,11 +173,17 @@ struct UnionLaunch {
     int bh, pxt;               // the unit: bh luma rows of pxt samples, 8 bytes of luma per row (16 for a 16-bit source written as 8 bit)
     long long bsi, bso;        // bytes per sample in / out
     bool mix_ok, batch;        // the container mix has vector kernels (8 -> 16 bit has none); more than one frame
+    bool isemi, osemi;         // the side's chroma is ONE plane of (Cb, Cr) pairs in slot 1 (the stack's semi form)
 
-    UnionLaunch(const FrameGeom &G, int din, int dout, int icsx_, int icsy, int ocsx_, int ocsy)
+    UnionLaunch(const FrameGeom &G, int din, int dout, int icsx_, int icsy, int ocsx_, int ocsy, bool isemi_ = false,
+                bool osemi_ = false)
         : win(din > 8), wout(dout > 8), icsx(icsx_), ocsx(ocsx_), csx(icsx_ > ocsx_ ? icsx_ : ocsx_), csy(icsy > ocsy ? icsy : ocsy),
           bh(1 << csy), pxt((win && !wout) ? 8 : (win ? 4 : 8)), bsi(win ? 2 : 1), bso(wout ? 2 : 1),
-          mix_ok(win == wout || (win && !wout)), batch(G.nframes > 1) {}
+          mix_ok(win == wout || (win && !wout)), batch(G.nframes > 1), isemi(isemi_), osemi(osemi_) {}
+
+    // samples of a chroma plane that go with n luma samples of a row: a plane of pairs holds both components of every block
+    long long chroma_in(long long n) const { return isemi ? n : n >> icsx; }
+    long long chroma_out(long long n) const { return osemi ? n : n >> ocsx; }
 
     // whole units, 32-bit unit indices, and whole aligned words of every plane per thread
     bool fits(const PlaneSet &Q, const FrameGeom &H) const
@@ -188,8 +194,8 @@ struct UnionLaunch {
         if (!plane_ok(Q.s[0], Q.ss[0], Q.sfs[0], pxt * bsi, batch, kStrideAny, false) || !plane_ok(Q.d[0], Q.ds[0], Q.dfs[0], pxt * bso, batch, kStrideAny, false))
             return false;
         for (int c = 1; c < 3; c++)
-            if (!plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], (pxt >> icsx) * bsi, batch, kStrideAny, false) ||
-                !plane_ok(Q.d[c], Q.ds[c], Q.dfs[c], (pxt >> ocsx) * bso, batch, kStrideAny, false))
+            if ((!(isemi && c == 2) && !plane_ok(Q.s[c], Q.ss[c], Q.sfs[c], chroma_in(pxt) * bsi, batch, kStrideAny, false)) ||
+                (!(osemi && c == 2) && !plane_ok(Q.d[c], Q.ds[c], Q.dfs[c], chroma_out(pxt) * bso, batch, kStrideAny, false)))
                 return false;
         return true;
     }
@@ -216,7 +222,7 @@ const char *launch_union(int variant, const PlaneSet &P, const FrameGeom &G, con
         [&](const PlaneSet &Q, const FrameGeom &H) { ran |= 2; return generic(Q, H, x0); },
         [&](int wv) {
             x0 = wv;
-            return advance_planes(P, wv * U.bsi, (wv >> U.icsx) * U.bsi, wv * U.bso, (wv >> U.ocsx) * U.bso);
+            return advance_planes(P, wv * U.bsi, U.chroma_in(wv) * U.bsi, wv * U.bso, U.chroma_out(wv) * U.bso);
         });
     if (!name || ran != 3 || !tail_name) return name;
     static thread_local std::string both;

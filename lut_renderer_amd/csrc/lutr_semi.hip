@@ -25,15 +25,7 @@ namespace lutr {
 // and one chroma row per thread, lattice taps gathered from L1/L2, the thread walks its chroma blocks one after the other.
 // A semi-planar side moves the thread's Cb and Cr in ONE access of twice the width; a planar side in two.  (Frame written out: see
 // k_yuv_vec.)
-// sample i of a word vector whose 16-bit codes sit `shift` bits up in their container: the shift rides in the bit-field extract
-// that unpacks the sample anyway
-template <int WIDE>
-__device__ __forceinline__ float word_code(const uint32_t *w, int i, unsigned shift)
-{
-    if constexpr (WIDE) return (float)__builtin_amdgcn_ubfe(w[i >> 1], (unsigned)(i & 1) * 16u + shift, 16u - shift);
-    else return word_sample<0>(w, i);
-}
-
+// (the shifted codes are unpacked by word_code, lutr_device.h)
 // (a, b) <-> (b, a) in every pair of a word: the two halves of a 16-bit pair, the bytes of each of the two 8-bit pairs
 template <int WIDE>
 __device__ __forceinline__ uint32_t swap_pairs(uint32_t w)

@@ -28,7 +28,7 @@ from .formats import (_ALPHA_RESIZE, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, V
                       check_lut1d_options, check_matte, check_rgb_stack_options, check_stack_options, check_strength, check_yuv2rgb_options, check_yuv2rgb_stack_options,
                       check_container_options,
                       check_dual_options, check_lut2, check_packed_options, check_premul_options, check_semi_options,
-                      chroma_loc_code, dual_side, has_prologue, held_resources, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt,
+                      check_semi_stack_options, chroma_loc_code, dual_side, has_prologue, held_resources, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt,
                       parse_rgb_source, parse_semi_fmt, parse_size, parse_v210_fmt, refuse_alpha_resize, refuse_chain_keywords,
                       refuse_dual_keywords, source_bit_depth, v210_frame_width, yuv_side)
 
@@ -1036,6 +1036,51 @@ class LutEngine:
                 else:
                     _native.check(self._lib.lutr_apply_yuv_stack_mix(
                         self._ctx, C.byref(p), arr, n, k, *mix, w, h, nf, C.byref(s), C.byref(d), row0, rows))
+        return dst
+
+    def apply_yuv_stack_semi(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str,
+                             out_pix_fmt: Optional[str] = None, stages, cdl: Optional[Cdl] = None, matrix_in: str = "bt709",
+                             matrix_out: Optional[str] = None, range_src: str = "tv", range_in: Optional[str] = None,
+                             range_out: str = "tv", lut_depth: Optional[int] = None, row0: int = 0, rows: Optional[int] = None,
+                             **other):
+        """`apply_yuv_stack` on frames whose source side, destination side or both are semi-planar, in one pass
+        (lutr_apply_yuv_stack_semi): a hardware decoder's nv12 / p010le through `stages` into a planar master
+        or back into nv12 / p010le, without a de-interleave pass ahead of the stack and an interleave pass behind it.  A
+        semi-planar side is [y, cbcr], exactly as `apply_yuv(pix_fmt="nv12")` takes it; a planar side is three planes.  The
+        result is bit for bit `semiplanar.to_semi(apply_yuv_stack(semiplanar.to_planar(src)))`.  A semi-planar side is 4:2:0 or
+        4:2:2 (the names of `_native.SEMI_FORMATS`); the other side may be 4:2:0 / 4:2:2 / 4:4:4, planar or semi-planar, at 8..16
+        bit -- the one call that changes the chroma subsampling of a semi-planar frame.  `stages`, `cdl`, the matrices, ranges,
+        `lut_depth` and row0 / rows (on the union block) are `apply_yuv_stack`'s; strict arithmetic, not in place.  No matrix
+        stage, strength, matte, dither, chroma_loc, out_size, premultiplied alpha or second output, no yuva* / RGB / float /
+        packed / v210 side, and at least one semi-planar side: each is a ValueError naming it
+        (`formats.check_semi_stack_options`)."""
+        strength, matte, rgb_matrix = other.pop("strength", None), other.pop("matte", None), other.pop("rgb_matrix", None)
+        st, fin, fout, (arr, n, k, _mtx) = _stack_front(
+            self, "apply_yuv_stack_semi", check_semi_stack_options, ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt"),
+            pix_fmt, out_pix_fmt, stages, cdl, rgb_matrix, other, strength=strength, matte=matte)
+        p = _yuv_call_params(fin, fout, lut_depth, matrix_in, matrix_out, range_src, range_in, range_out)
+        if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
+            raise ValueError(f"'{fin.name}' takes {fin.nplanes} planes")
+        if not isinstance(src[0], torch.Tensor):
+            raise TypeError(_NOT_TENSORS)
+        h, w = src[0].shape[-2], src[0].shape[-1]
+        if dst is None:
+            dst = _fresh_planes(fout, w, h, src[0], self.device)
+        if isinstance(dst, torch.Tensor) or len(dst) != fout.nplanes:
+            raise ValueError(f"'{fout.name}' takes {fout.nplanes} planes")
+        _check_planes(src, fin, w, h, "source")
+        _check_planes(dst, fout, w, h, "destination")
+        _check_not_in_place(src, dst, _STACK_IN_PLACE)
+        s, nf = _planes_struct(src, self.device, fin.nplanes)
+        d, nfd = _planes_struct(dst, self.device, fout.nplanes)
+        if nf != nfd:
+            raise ValueError("src and dst disagree on the number of frames")
+        rows = h - row0 if rows is None else rows
+        with self._lock:
+            self._bind_stream()
+            _native.check(self._lib.lutr_apply_yuv_stack_semi(
+                self._ctx, C.byref(p), arr, n, k, C.byref(fin.layout()), C.byref(fout.layout()), w, h, nf, C.byref(s), C.byref(d),
+                row0, rows))
         return dst
 
     def apply_rgb_lut1d(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, depth: int,

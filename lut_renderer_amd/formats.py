@@ -1044,3 +1044,68 @@ def check_yuv2rgb_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[st
         matte=None if matte is False else matte, alpha_mode=alpha_mode, out2_pix_fmt=out2_pix_fmt),
         vector=(st, fin.depth, fout.depth, pix_fmt, fout.name))
     return st, fin, fout
+
+
+# ---------------------------------------------------------------- the stage stack on semi-planar sides
+SEMI_STACK_TAIL = "a stage stack on semi-planar frames (semi_stages)"
+
+#: what every layer says when the list comes with another one
+SEMI_STAGES_EXCLUSIVE = ("semi_stages and stages / rgb_stages / rgb_out_stages are mutually exclusive: semi_stages is the list of a "
+                         "call with a semi-planar side, stages that of planar YUV on both sides, rgb_stages that of an RGB source, "
+                         "rgb_out_stages that of a YUV source with rgb_out")
+
+#: semi-planar names FFmpeg has that this path does not take: 4:4:4 pairs and big-endian containers
+_SEMI_UNSUPPORTED = ("nv24", "nv42", "p410le", "p412le", "p416le", "p010be", "p012be", "p016be", "p210be", "p212be", "p216be",
+                     "p410be", "p412be", "p416be")
+
+
+def semi_stack_side(name: Optional[str], what: str):
+    """One side of the stack on semi-planar frames: the `SemiFmt` of a semi-planar name or the `PixFmt` of a planar YUV one
+    (yuvj* read as yuv*); ValueError, naming it, for a yuva*, packed 4:2:2, v210, RGB or float name and for a semi-planar name
+    this path does not take (4:4:4 and big-endian ones)."""
+    tail = SEMI_STACK_TAIL
+    if name in _SEMI_UNSUPPORTED:
+        raise ValueError(f"'{name}' is not supported with {tail}: a semi-planar side is 4:2:0 or 4:2:2, little-endian "
+                         f"({', '.join(_native.SEMI_FORMATS)})")
+    if parse_packed_yuv_fmt(name) is not None or name in _PACKED_YUV_UNSUPPORTED:
+        raise ValueError(f"a packed 4:2:2 side ({what} '{name}') is not supported with {tail}")
+    if parse_v210_fmt(name) is not None or name in _V210_UNSUPPORTED:
+        raise ValueError(f"a v210 side ({what} '{name}') is not supported with {tail}")
+    rgb = parse_rgb_source(name)
+    if rgb is not None:
+        kind = "a float" if rgb.floating else "an RGB"
+        raise ValueError(f"{kind} side ({what} '{name}') is not supported with {tail}: both sides are YUV, planar or semi-planar")
+    side = yuv_side(name)
+    if getattr(side, "alpha", False):
+        raise ValueError(f"alpha ({what} '{name}') is not supported with {tail}: semi-planar formats carry no alpha")
+    return side
+
+
+def check_semi_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = None, *, stages, cdl: bool = False,
+                             lut: bool = True, lut2: bool = True, lut1d: bool = True, prelut: bool = False, dither: str = "none",
+                             chroma_loc: Optional[str] = None, out_size=None, alpha_mode: str = "straight",
+                             out2_pix_fmt: Optional[str] = None, variant: Optional[str] = None, strength=None,
+                             precision: Optional[str] = None, matte=None, rgb_matrix: bool = False):
+    """The checks every layer makes of a stage stack on semi-planar frames before any GPU work, the one copy of
+    its refusals: a `matrix` stage or an RGB matrix; everything `check_stage_list` refuses; a side that is neither a semi-planar
+    name of `_native.SEMI_FORMATS` nor planar YUV at 4:2:0 / 4:2:2 / 4:4:4 -- yuva*, packed 4:2:2, v210, RGB and float names, and
+    4:4:4 or big-endian semi-planar ones, by name; both sides planar (that is `apply_yuv_stack`'s call); strength / matte; dither,
+    chroma_loc, out_size; a second output; premultiplied alpha; the vec_lds variant, and vec_global where the names of the call
+    already say that the vector kernel cannot take it (a pyramid / prism stage, an 8-bit source written as 16-bit words).  A
+    `precision` other than strict is taken as the stack takes it without a strength: the pass runs strict.
+    Returns (parsed stages, source side, destination side); a side is a `SemiFmt` or a planar `PixFmt`."""
+    tail = SEMI_STACK_TAIL
+    if rgb_matrix or "matrix" in [k for k, _m in parse_stages(stages)]:
+        raise ValueError(f"stage 'matrix' is not supported with {tail}: the matrix stage has no semi-planar form")
+    st = check_stage_list(stages, cdl=cdl, lut=lut, lut2=lut2, lut1d=lut1d, prelut=prelut)
+    if not pix_fmt:
+        raise ValueError(f"{tail} needs pix_fmt")
+    fin = semi_stack_side(pix_fmt, "pix_fmt")
+    fout = semi_stack_side(out_pix_fmt or pix_fmt, "out_pix_fmt")
+    if not isinstance(fin, SemiFmt) and not isinstance(fout, SemiFmt):
+        raise ValueError(f"both sides are planar: use apply_yuv_stack ('{pix_fmt}' -> '{out_pix_fmt or pix_fmt}' has no "
+                         f"semi-planar side)")
+    _refuse_stack_options(tail, "semi-planar stack", variant, dict(
+        strength=strength, matte=None if matte is False else matte, dither=dither, chroma_loc=chroma_loc, out_size=out_size,
+        out2_pix_fmt=out2_pix_fmt, alpha_mode=alpha_mode), vector=(st, fin.depth, fout.depth, pix_fmt, fout.name))
+    return st, fin, fout

@@ -30,8 +30,8 @@ from . import _native
 from .cube import CubeLut, read_lut, read_lut1d
 from .engine import LutEngine, _fresh_planes, _new_planes, _yuv_out_dtype, chain_args, dual_args
 from .formats import (RgbSource, check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2,
-                      check_matte, check_premul_options, check_rgb_stack_options, check_stack_options, check_strength,
-                      check_yuv2rgb_options, check_yuv2rgb_stack_options, held_resources, packed_frame_width, parse_pix_fmt,
+                      check_matte, check_premul_options, check_rgb_stack_options, check_semi_stack_options,
+                      check_stack_options, check_strength, check_yuv2rgb_options, check_yuv2rgb_stack_options, held_resources, packed_frame_width, parse_pix_fmt,
                       parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords, v210_frame_width, yuv_side)
 from .shard import row_blocks
 
@@ -393,6 +393,32 @@ class LutEngineGroup:
             def remote(eng, r0, r1):
                 there = kw if kw.get("matte") is None else dict(kw, matte=_travel([kw["matte"]], [(r0, r1)], eng.device)[0])
                 out = eng.apply_yuv_stack(_travel(src, _row_ranges(fin, r0, r1), eng.device), None, **names, **there)
+                return [(dst, out, _row_ranges(fout, r0, r1))]
+
+            self._shard(h, 1 << max(fin.csy, fout.csy), home, local, remote)
+            return dst
+
+    def apply_yuv_stack_semi(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, pix_fmt: str,
+                             out_pix_fmt: Optional[str] = None, stages, cdl=None, **kw):
+        """`LutEngine.apply_yuv_stack_semi` with the rows of every frame split over the group's devices, by
+        `apply_yuv_stack`'s rule: shards on multiples of the union block height of the two layouts, no halo.  A plane of pairs
+        has the rows of a planar chroma plane, so it travels as one; the shards give the bits of the whole call."""
+        with self._lock:
+            st, fin, fout = _stack_opening(
+                self, check_semi_stack_options,
+                ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength", "matte"),
+                pix_fmt, out_pix_fmt, stages, cdl, kw.get("rgb_matrix"), kw)
+            h, w = src[0].shape[-2], src[0].shape[-1]
+            home = src[0].device
+            if dst is None:
+                dst = _fresh_planes(fout, w, h, src[0], home)
+            names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, stages=st, cdl=cdl)
+
+            def local(eng, r0, r1):
+                eng.apply_yuv_stack_semi(src, dst, row0=r0, rows=r1 - r0, **names, **kw)
+
+            def remote(eng, r0, r1):
+                out = eng.apply_yuv_stack_semi(_travel(src, _row_ranges(fin, r0, r1), eng.device), None, **names, **kw)
                 return [(dst, out, _row_ranges(fout, r0, r1))]
 
             self._shard(h, 1 << max(fin.csy, fout.csy), home, local, remote)

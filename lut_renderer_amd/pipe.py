@@ -53,7 +53,8 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
                           interp1d: Optional[str] = None, stages=None, strength: Optional[float] = None,
                           strength_keys: Optional[str] = None, matte: Optional[Path] = None,
                           matte_pix_fmt: Optional[str] = None, matte_invert: bool = False, rgb_matrix=None,
-                          rgb_stages=None, rgb_out: Optional[str] = None, rgb_out_stages=None) -> StageCommands:
+                          rgb_stages=None, rgb_out: Optional[str] = None, rgb_out_stages=None,
+                          semi_stages=None) -> StageCommands:
     """The three argv lists of one LUT stage.  Raises what `build_command` / `engine_command` raise (copy guard, missing
     geometry).  `chroma_loc` goes to the engine (`--chroma-loc`) and, as `-chroma_sample_location`, to the encoder, so the
     output stream declares the siting the engine assumed.  `gpu_resize` with `params.resolution` set resizes in the engine
@@ -70,7 +71,8 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
     `matrix` stage of `stages`, DESIGN.md 3.25: `--rgb-matrix` / `--rgb-matrix-offset` for an `rgbmatrix.RgbMatrix`,
     `--rgb-matrix-file` for a path, rendered only when given), and for `rgb_stages` (the stack on an RGB source, DESIGN.md 3.26:
     `--rgb-stages`, rendered only when given), and for `rgb_out` with `rgb_out_stages` (the stack from a YUV source into an RGB
-    frame, DESIGN.md 3.27: `--rgb-out` / `--rgb-out-stages`, rendered only when given; the encoder then reads raw `rgb_out` frames)."""
+    frame, DESIGN.md 3.27: `--rgb-out` / `--rgb-out-stages`, rendered only when given; the encoder then reads raw `rgb_out` frames),
+    and for `semi_stages` (the stack on semi-planar sides, DESIGN.md 3.28: `--semi-stages`, rendered only when given)."""
     notes: List[str] = []
     engine = engine_command(Path("-"), Path("-"), params, lut_path, source_info, python_bin=python_bin, device=device, notes=notes,
                             precision=precision, chroma_loc=chroma_loc, gpu_resize=gpu_resize, engine_dither=engine_dither,
@@ -82,7 +84,8 @@ def engine_stage_commands(source: Path, output: Path, params: ProcessingParams, 
                                {"matte": matte, "matte_pix_fmt": matte_pix_fmt, "matte_invert": matte_invert}),
                             **({} if rgb_matrix is None else {"rgb_matrix": rgb_matrix}),
                             **({} if rgb_stages is None else {"rgb_stages": rgb_stages}),
-                            **({} if rgb_out is None and rgb_out_stages is None else {"rgb_out": rgb_out, "rgb_out_stages": rgb_out_stages}))
+                            **({} if rgb_out is None and rgb_out_stages is None else {"rgb_out": rgb_out, "rgb_out_stages": rgb_out_stages}),
+                            **({} if semi_stages is None else {"semi_stages": semi_stages}))
     resized = gpu_resize and bool(params.resolution)
     if source_info.duration:
         engine += ["--duration", f"{float(source_info.duration):.3f}"]
@@ -183,6 +186,8 @@ def main(argv=None) -> int:
     ap.add_argument("--interp1d", default=None, help="interpolation mode of --lut1d, see lut_renderer_amd.cli")
     ap.add_argument("--stages", default=None, help="engine setting: the operators as an ordered stack, see lut_renderer_amd.cli")
     ap.add_argument("--rgb-stages", default=None, help="engine setting: the ordered stack on an RGB source, see lut_renderer_amd.cli")
+    ap.add_argument("--semi-stages", default=None,
+                    help="engine setting: the ordered stack on semi-planar frames (nv12, p010le, ..), see lut_renderer_amd.cli")
     ap.add_argument("--rgb-out", default=None, help="engine setting: the RGB format --rgb-out-stages writes, see lut_renderer_amd.cli")
     ap.add_argument("--rgb-out-stages", default=None,
                     help="engine setting: the ordered stack from a YUV source into --rgb-out, see lut_renderer_amd.cli")
@@ -218,7 +223,7 @@ def main(argv=None) -> int:
                                      stages=a.stages, strength=a.strength, strength_keys=a.strength_keys,
                                      matte=None if a.matte is None else Path(a.matte), matte_pix_fmt=a.matte_pix_fmt,
                                      matte_invert=a.matte_invert, rgb_matrix=mtx, rgb_stages=a.rgb_stages,
-                                     rgb_out=a.rgb_out, rgb_out_stages=a.rgb_out_stages)
+                                     rgb_out=a.rgb_out, rgb_out_stages=a.rgb_out_stages, semi_stages=a.semi_stages)
     except Exception as exc:
         print(f"Error: {exc}", flush=True)
         return 1
