@@ -1012,6 +1012,40 @@ int lutr_apply_yuv_stack_semi(lutr_ctx *ctx, const lutr_yuv_params *p, const lut
                               const lutr_yuv_layout *in_layout, const lutr_yuv_layout *out_layout, int w, int h, int nframes,
                               const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
 
+/* ---- the stage stack on capture frames: v210 / uyvy422 from a capture card through lut1d,cdl,lut3d into v210 /
+ *      uyvy422 for a play-out card or into a yuv422p10le master, without an unpacking pass ahead of the stack and a packing pass
+ *      behind it ----
+ * lutr_apply_yuv_stack with each side planar or packed 4:2:2 (lutr_yuv_packing, as lutr_apply_yuv_packed takes it), or with each
+ * side planar or v210 (in_v210 / out_v210, as lutr_apply_yuv_v210 takes them).  The result is bit-identical to
+ * lutr_apply_yuv_stack on the same samples held in three planes, put into the destination's container: the list, its compiled
+ * steps, the full-range prologue, lut_depth and everything else *p expresses are that call's arithmetic unchanged.  The side rules
+ * and the container rules are lutr_apply_yuv_packed's and lutr_apply_yuv_v210's: a packed / v210 side is 4:2:2 (v210: 10 bit);
+ * with a packed / v210 source the planar destination may be 4:2:2, 4:2:0 or 4:4:4 at 8..16 bit; a packed / v210 destination takes a
+ * 4:2:2 source; low bits under a shift and bits 30-31 of a v210 word are ignored on input and zero on output; slots beyond the
+ * frame are ignored on input and replicated on output; row bytes past the last group are never written.
+ * Stages: 1..4 out of LUT3D, LUT3D_2, LUT1D, CDL, each at most once, in any order, on lutr_apply_yuv_stack's terms.  row0 and rows
+ * must be multiples of the destination's chroma block height unless row0 + rows == h.  With both sides planar either call IS
+ * lutr_apply_yuv_stack.  Always strict precision.  A packed 4:2:2 side and a v210 side in one call are not supported: each entry
+ * takes its own kind.
+ * Not in place: no byte range of a source plane may overlap one of a destination plane, over all rows and frames.
+ * LUTR_EINVAL with a message, before anything touches the device: a null packing; everything lutr_apply_yuv_stack refuses about the
+ * list and its resources -- a MATRIX stage with that call's words; everything lutr_apply_yuv_packed / lutr_apply_yuv_v210 refuses
+ * about a side; variant vec_lds; an overlap as above.
+ * Kernels: "k_yuv_stack_pk_vec<win,wout,pi,po,ocsy,tri,lds>[stages]" / "k_yuv_stack_v210_vec<wp,vi,vo,ocsy,tri,lds>[stages]" under
+ * the layout conditions of k_yuv_pk_vec / k_yuv_v210_vec and nearest / trilinear / tetrahedral stages (the tables in LDS when they
+ * fit 24 KB, LUTR_STACK_LDS=0 | 1 as for lutr_apply_yuv_stack), "k_yuv_stack_pk_generic[stages]" /
+ * "k_yuv_stack_v210_generic[stages]" for everything else, "<vector kernel>+<generic kernel>[stages]" for a ragged width on aligned
+ * rows; [stages] as lutr_apply_yuv_stack writes it.  vec_global fails with LUTR_EINVAL where the vector kernel cannot take the
+ * layout.
+ * Not covered: a matrix stage, a strength or a matte, dither, chroma siting, a resize, a second output, alpha, semi-planar / RGB
+ * sides, v210x / v410 / packed 4:4:4 / big-endian containers, a tile (LDS window) kernel. */
+int lutr_apply_yuv_stack_packed(lutr_ctx *ctx, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                                const lutr_yuv_packing *in, const lutr_yuv_packing *out, int w, int h, int nframes,
+                                const lutr_planes *src, const lutr_planes *dst, int row0, int rows);
+int lutr_apply_yuv_stack_v210(lutr_ctx *ctx, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                              int in_v210, int out_v210, int w, int h, int nframes, const lutr_planes *src, const lutr_planes *dst,
+                              int row0, int rows);
+
 /* ---- the alpha plane of yuva* / gbrap* frames: ProRes 4444 (yuva444p10le / 12le), VP8 / VP9 with alpha
  *      (yuva420p), PNG / TIFF / EXR sequences with alpha (rgba, rgba64le, gbrap*, gbrapf32le).  In the reference's chain lut3d
  *      copies the alpha plane through and format=<pix_fmt> keeps, converts, drops or makes it (ffmpeg.py:246, :304-310) ---- */

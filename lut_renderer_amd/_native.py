@@ -54,6 +54,7 @@ SYMBOLS = (
     "lutr_lut1d_parse", "lutr_lut1d_table", "lutr_ctx_set_lut1d", "lutr_apply_yuv_lut1d", "lutr_apply_planar_rgb_lut1d",
     "lutr_apply_yuv_stack", "lutr_apply_yuv_stack_mix", "lutr_apply_yuv_stack_matte",
     "lutr_apply_yuv_stack_matrix", "lutr_apply_rgb_stack", "lutr_apply_yuv_stack_to_rgb", "lutr_apply_yuv_stack_semi",
+    "lutr_apply_yuv_stack_packed", "lutr_apply_yuv_stack_v210",
     "lutr_resize_filter", "lutr_resize_planes", "lutr_resize_plan", "lutr_dither_mask",
     "lutr_ctx_set_variant", "lutr_ctx_set_precision", "lutr_ctx_last_kernel", "lutr_ctx_tile_stats", "lutr_yuv_constants",
     "lutr_max_waves_knob", "lutr_max_blocks_knob",
@@ -298,6 +299,11 @@ def load() -> C.CDLL:
     lib.lutr_apply_yuv_stack_semi.argtypes = [vp, C.POINTER(YuvParams), C.POINTER(StageStruct), ci, C.POINTER(CdlStruct),
                                               C.POINTER(YuvLayout), C.POINTER(YuvLayout), ci, ci, ci, C.POINTER(Planes),
                                               C.POINTER(Planes), ci, ci]
+    lib.lutr_apply_yuv_stack_packed.argtypes = [vp, C.POINTER(YuvParams), C.POINTER(StageStruct), ci, C.POINTER(CdlStruct),
+                                                C.POINTER(YuvPacking), C.POINTER(YuvPacking), ci, ci, ci, C.POINTER(Planes),
+                                                C.POINTER(Planes), ci, ci]
+    lib.lutr_apply_yuv_stack_v210.argtypes = [vp, C.POINTER(YuvParams), C.POINTER(StageStruct), ci, C.POINTER(CdlStruct), ci, ci,
+                                              ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes), ci, ci]
     lib.lutr_dither_mask.argtypes = [C.POINTER(C.c_uint16)]
     lib.lutr_resize_filter.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(C.c_int16), C.POINTER(ci)]
     lib.lutr_resize_planes.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(Planes), C.POINTER(Planes)]

@@ -26,9 +26,9 @@ from .rgbmatrix import as_rgb_matrix
 from .cube import CubeLut, as_lut1d, read_cube, read_lut, read_lut1d
 from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc, check_container_options,
                       check_dual_options, check_lut1d_options, check_lut2, check_premul_options, check_stack_options,
-                      SEMI_STAGES_EXCLUSIVE, check_rgb_stack_options, check_semi_stack_options, check_yuv2rgb_options, check_yuv2rgb_stack_options, implied_stages, packed_frame_width, parse_packed_yuv_fmt,
+                      PACKED_STAGES_EXCLUSIVE, SEMI_STAGES_EXCLUSIVE, check_packed_stack_options, check_rgb_stack_options, check_semi_stack_options, check_yuv2rgb_options, check_yuv2rgb_stack_options, implied_stages, packed_frame_width, parse_packed_yuv_fmt,
                       parse_pix_fmt, parse_rgb_source, parse_semi_fmt, parse_size, parse_stages, parse_v210_fmt, premul_to_yuv,
-                      refuse_alpha_resize, semi_stack_side, source_bit_depth, v210_frame_width, yuv_side)
+                      packed_stack_side, refuse_alpha_resize, semi_stack_side, source_bit_depth, v210_frame_width, yuv_side)
 from .params import ProcessingParams, VideoInfo
 from .plan import LutPlan, output_color_tags, resolve_lut_plan
 
@@ -93,7 +93,7 @@ def _parsed_lut(cube) -> Optional[CubeLut]:
 
 
 def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = None, alpha_mode: str = "straight",
-                    rgb_out: Optional[str] = None, semi_stack: bool = False) -> dict:
+                    rgb_out: Optional[str] = None, semi_stack: bool = False, packed_stack: bool = False) -> dict:
     """Translate a LutPlan into keyword arguments of LutEngine.apply_yuv (`pix_fmt` / `out_pix_fmt` planar YUV -- yuva* too, DESIGN.md
     3.16: without `out_pix_fmt` the source's format, alpha included, is kept; a named output without alpha drops it, one with alpha
     on a source without is filled opaque; the full-range prologue's default output stays the 8-bit yuv4xxp -- , semi-planar names
@@ -108,7 +108,9 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
     arguments are then those of LutEngine.apply_yuv_to_rgb (`is_rgb_out_call(kw)`), the LUT runs at that format's depth, and a plan
     with the full-range prologue (which lands at 8 bit) takes an 8-bit `rgb_out` only.  Not together with `out_pix_fmt`.
     `semi_stack`: the call is `LutEngine.apply_yuv_stack_semi`'s -- the sides are checked as that pass takes them
-    (semi-planar or planar YUV, any pair of subsamplings) and not as `apply_yuv` does."""
+    (semi-planar or planar YUV, any pair of subsamplings) and not as `apply_yuv` does.
+    `packed_stack`: the call is `LutEngine.apply_yuv_stack_packed`'s -- the sides are checked as that pass takes
+    them (packed 4:2:2, v210 or planar YUV)."""
     if plan.interp not in _ENGINE_INTERP:
         raise ValueError(f"lut3d has no interpolation mode '{plan.interp}'")
     premul = check_alpha_mode(alpha_mode)
@@ -131,6 +133,10 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
         # (the sides of the stack on semi-planar frames: its own refusals of a name, and any pair of subsamplings)
         semi_stack_side(pix_fmt, "pix_fmt")
         semi_stack_side(out_pix_fmt or pix_fmt, "out_pix_fmt")
+    if packed_stack:
+        # (the sides of the stack on packed 4:2:2 / v210 frames: its own refusals of a name)
+        packed_stack_side(pix_fmt, "pix_fmt")
+        packed_stack_side(out_pix_fmt or pix_fmt, "out_pix_fmt")
     rgb = parse_rgb_source(pix_fmt)
     if premul and rgb is not None:
         check_premul_options(pix_fmt, out_pix_fmt, to_yuv=premul_to_yuv(pix_fmt, out_pix_fmt))
@@ -167,7 +173,7 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
     # a semi-planar source or output (nv12, p010le, ..) is the same chain on another container
     # (so is a packed 4:2:2 one: uyvy422, y210le, ..)
     # (and v210)
-    if not semi_stack:
+    if not semi_stack and not packed_stack:
         check_container_options(pix_fmt, out_pix_fmt, kinds=("v210", "packed"))     # names the packings this path does not take
     semi_src = parse_semi_fmt(pix_fmt) or parse_packed_yuv_fmt(pix_fmt) or parse_v210_fmt(pix_fmt)
     src = semi_src or parse_pix_fmt(pix_fmt)
@@ -188,7 +194,7 @@ def engine_call_for(plan: LutPlan, pix_fmt: str, out_pix_fmt: Optional[str] = No
         kw.update(range_src="tv", range_in="tv", lut_depth=src.depth)
         default_out = kw["pix_fmt"]
     kw["out_pix_fmt"] = out_pix_fmt or default_out
-    if not semi_stack:
+    if not semi_stack and not packed_stack:
         check_container_options(kw["pix_fmt"], kw["out_pix_fmt"])    # (one subsampling on both sides of a semi-planar call)
     if premul:
         check_premul_options(kw["pix_fmt"], kw["out_pix_fmt"], range_src=kw["range_src"], range_in=kw["range_in"],
@@ -336,7 +342,7 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
               cube2=None, interp2: Optional[str] = None, alpha_mode: str = "straight", cdl=None, cdl_id: Optional[str] = None,
               lut1d=None, interp1d: str = "linear", stages=None, strength=None, matte=None, matte_depth: Optional[int] = None,
               matte_invert: bool = False, rgb_out: Optional[str] = None, rgb_matrix=None, rgb_stages=None, rgb_out_stages=None,
-              semi_stages=None):
+              semi_stages=None, packed_stages=None):
     """Apply `cube` to planar YUV frames on the GPU.  `planes` = (Y, Cb, Cr) torch tensors on the
     engine's device, each [H,W] or [F,H,W].  A semi-planar `pix_fmt` / `out_pix_fmt` (nv12, nv21, nv16, p010le .. p216le; DESIGN.md
     3.11) makes that side (Y, CbCr): two tensors, the chroma one [..., ch, 2 * cw]; same subsampling on both sides, no dither,
@@ -473,7 +479,15 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
     `cube2`, `lut1d`, `cdl`), in ONE pass (LutEngine.apply_yuv_stack_semi) with no de-interleave ahead of it and no interleave
     behind it; the other side may be planar 4:2:0 / 4:2:2 / 4:4:4 at 8..16 bit, so p010le -> yuv422p10le is one call.  `stages`,
     `rgb_stages` or `rgb_out_stages` together with it, two planar sides, a matrix stage, strength, matte, dither, resolution,
-    chroma_loc, premultiplied alpha, yuva*, a second output and a packed / v210 / RGB / float side are ValueErrors naming them."""
+    chroma_loc, premultiplied alpha, yuva*, a second output and a packed / v210 / RGB / float side are ValueErrors naming them.
+
+    `packed_stages` is `stages` for a call with a packed 4:2:2 or v210 side -- `pix_fmt`, `out_pix_fmt` or both one
+    of yuyv422, uyvy422, yvyu422, y210le, y212le, y216le, or v210, that side ONE tensor as `apply_yuv` takes it (`width` names a
+    width the rows cannot tell): the same lists without the matrix stage, the same resources (`cube`, `cube2`, `lut1d`, `cdl`), in
+    ONE pass (LutEngine.apply_yuv_stack_packed) with no unpacking ahead of it and no packing behind it; a packed / v210 source may
+    go to planar 4:2:2 / 4:2:0 / 4:4:4 at 8..16 bit, a packed / v210 output takes a 4:2:2 source.  Another stage list together
+    with it, two planar sides, a packed 4:2:2 side together with a v210 side, a matrix stage, strength, matte, dither, resolution,
+    chroma_loc, premultiplied alpha, yuva*, a second output and a semi-planar / RGB / float side are ValueErrors naming them."""
     devices = tuple(int(d) for d in devices)
     if not devices:
         raise ValueError("devices must name at least one GPU")
@@ -496,7 +510,11 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
                              "a YUV output, rgb_stages that of an RGB source, rgb_out_stages that of a YUV source with rgb_out")
     if semi_stages is not None and (stages is not None or rgb_stages is not None or rgb_out_stages is not None):
         raise ValueError(SEMI_STAGES_EXCLUSIVE)
-    if rgb_matrix is not None and stages is None and rgb_stages is None and rgb_out_stages is None and semi_stages is None:
+    if packed_stages is not None and (stages is not None or rgb_stages is not None or rgb_out_stages is not None
+                                      or semi_stages is not None):
+        raise ValueError(PACKED_STAGES_EXCLUSIVE)
+    if rgb_matrix is not None and stages is None and rgb_stages is None and rgb_out_stages is None and semi_stages is None \
+            and packed_stages is None:
         raise ValueError("rgb_matrix needs stages: a matrix stage has no implied position (e.g. stages='lut1d,matrix,lut3d')")
     rgb_src = parse_rgb_source(pix_fmt)
     if rgb_stages is not None and rgb_src is None:
@@ -570,9 +588,10 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
             if own:
                 eng.sync()
         return result, output_color_tags(plan.output_policy)
-    # (semi_stages: that pass's own sides; its check below is told the alpha mode)
-    kw = engine_call_for(plan, pix_fmt, out_pix_fmt, alpha_mode) if semi_stages is None else \
-        engine_call_for(plan, pix_fmt, out_pix_fmt, "straight", semi_stack=True)
+    # (semi_stages / packed_stages: that pass's own sides; its check below is told the alpha mode)
+    kw = engine_call_for(plan, pix_fmt, out_pix_fmt, "straight", semi_stack=True) if semi_stages is not None else \
+        engine_call_for(plan, pix_fmt, out_pix_fmt, "straight", packed_stack=True) if packed_stages is not None else \
+        engine_call_for(plan, pix_fmt, out_pix_fmt, alpha_mode)
     refuse_alpha_resize(kw.get("out_pix_fmt"), out_size)        # (the resize takes three planes)
     kw["dither"] = zdither if engine_dither is None else resolve_engine_dither(engine_dither, zdither)
     if precision not in ("strict", "fast", "fma32"):
@@ -584,6 +603,17 @@ def apply_lut(planes: Sequence, *, cube, interp: str = "tetrahedral", pix_fmt: s
         call = {k: v for k, v in kw.items() if k not in ("dither", "interp", "alpha_mode")}
         result = _stack_route(
             planes, out, check_semi_stack_options, "apply_yuv_stack_semi", (kw["pix_fmt"], kw["out_pix_fmt"]), semi_stages,
+            kw.get("interp"), *loaded, dict(dither=kw["dither"], chroma_loc=chroma_loc, out_size=out_size, alpha_mode=alpha_mode,
+                                            out2_pix_fmt=second_pix_fmt, strength=strength, precision=precision, matte=matte),
+            lambda: call)
+        return result, output_color_tags(plan.output_policy)
+    if packed_stages is not None:
+        # the stage stack on packed 4:2:2 / v210 sides: a route of its own, opt-in by name
+        call = {k: v for k, v in kw.items() if k not in ("dither", "interp", "alpha_mode")}
+        if width is not None:
+            call["width"] = width
+        result = _stack_route(
+            planes, out, check_packed_stack_options, "apply_yuv_stack_packed", (kw["pix_fmt"], kw["out_pix_fmt"]), packed_stages,
             kw.get("interp"), *loaded, dict(dither=kw["dither"], chroma_loc=chroma_loc, out_size=out_size, alpha_mode=alpha_mode,
                                             out2_pix_fmt=second_pix_fmt, strength=strength, precision=precision, matte=matte),
             lambda: call)

@@ -132,6 +132,14 @@ def build_parser() -> argparse.ArgumentParser:
                          "4:2:2 / 4:4:4, e.g. --pix-fmt p010le --out-pix-fmt yuv422p10le --semi-stages lut1d,cdl,lut3d; no dither, "
                          "--chroma-loc, --out-size, --strength, --matte, --second-output or --alpha-mode premultiplied; not "
                          "together with --stages, --rgb-stages or --rgb-out-stages")
+    ap.add_argument("--packed-stages", default=None, metavar="LIST",
+                    help="engine setting: --stages for a call with a packed 4:2:2 or v210 side (--pix-fmt, --out-pix-fmt or both one "
+                         "of yuyv422, uyvy422, yvyu422, y210le, y212le, y216le, or v210; DESIGN.md 3.29): the same lists and files "
+                         "without the matrix stage, in ONE pass with no unpacking ahead of it and no packing behind it; a packed / "
+                         "v210 source may go to planar 4:2:2 / 4:2:0 / 4:4:4, e.g. --pix-fmt v210 --out-pix-fmt yuv422p10le "
+                         "--packed-stages lut1d,cdl,lut3d; no dither, --chroma-loc, --out-size, --strength, --matte, "
+                         "--second-output or --alpha-mode premultiplied; not together with --stages, --rgb-stages, "
+                         "--rgb-out-stages or --semi-stages")
     ap.add_argument("--rgb-matrix", default=None, metavar="\"M00 M01 M02 M10 .. M22\"",
                     help="engine setting: the nine numbers, row-major, of the RGB matrix a 'matrix' stage of --stages applies "
                          "(DESIGN.md 3.25; a gamut conversion, a white-balance or channel-mixer trim, a channel swap): "
@@ -331,6 +339,26 @@ def semi_stack_call_from_args(args, plan) -> dict:
     return _stack_call(call, r, "semi_stages")
 
 
+def packed_stack_call_from_args(args, plan) -> dict:
+    """The keyword arguments of `apply_yuv_stack_packed` for --packed-stages, with `pix_fmt` / `out_pix_fmt` as
+    every call of `plan_from_args` carries them and the parsed list under `packed_stages`: the list as --stages parses it, every
+    refusal of `check_packed_stack_options`, the matrices and ranges `engine_call_for` gives the plan."""
+    from .api import engine_call_for
+    from .formats import PACKED_STAGES_EXCLUSIVE, check_packed_stack_options
+    if any(getattr(args, k, None) is not None for k in ("stages", "rgb_stages", "rgb_out_stages", "semi_stages")):
+        raise ValueError(PACKED_STAGES_EXCLUSIVE)
+    if getattr(args, "rgb_out", None) is not None:
+        raise ValueError("--rgb-out names the RGB output of a planar YUV source: with --packed-stages the output is --out-pix-fmt")
+    r = _stage_list_from_args(args, plan.interp, "--packed-stages", args.packed_stages)
+    check_packed_stack_options(
+        args.pix_fmt, args.out_pix_fmt, stages=r["stages"], **r["list"],
+        dither="error_diffusion" if args.zscale_dither == "error_diffusion" else getattr(args, "engine_dither", None) or "none",
+        precision=getattr(args, "precision", None), **r["options"])
+    kw = engine_call_for(plan, args.pix_fmt, args.out_pix_fmt, "straight", packed_stack=True)
+    call = {k: v for k, v in kw.items() if k not in ("interp", "alpha_mode", "dither")}
+    return _stack_call(call, r, "packed_stages")
+
+
 def matte_from_args(args):
     """None without --matte, else dict(matte=the path, matte_pix_fmt=, matte_invert=); --matte-pix-fmt / --matte-invert without
     --matte, '-' and an unknown format are errors."""
@@ -375,11 +403,16 @@ def plan_from_args(args):
     rgb_stages = getattr(args, "rgb_stages", None)
     rgb_out_stages = getattr(args, "rgb_out_stages", None)
     semi_stages = getattr(args, "semi_stages", None)
-    if args.cube is None and lut1d is None and stages is None and rgb_stages is None and rgb_out_stages is None and semi_stages is None:
+    packed_stages = getattr(args, "packed_stages", None)
+    if args.cube is None and lut1d is None and stages is None and rgb_stages is None and rgb_out_stages is None and semi_stages is None \
+            and packed_stages is None:
         raise ValueError("--cube is required unless --lut1d is given")
     plan = resolve_lut_plan(params, args.cube if args.cube is not None else "engine.cube", info)
     alpha_mode = getattr(args, "alpha_mode", None) or "straight"
     rgb_out = getattr(args, "rgb_out", None)
+    if packed_stages is not None:
+        # the stage stack on packed 4:2:2 / v210 sides: a route of its own
+        return plan, packed_stack_call_from_args(args, plan), w, h
     if semi_stages is not None:
         # the stage stack on semi-planar sides: a route of its own
         return plan, semi_stack_call_from_args(args, plan), w, h
@@ -487,7 +520,7 @@ def main(argv=None) -> int:
     ap = build_parser()
     args = ap.parse_args(argv)
     if args.cube is None and args.lut1d is None and args.stages is None and args.rgb_stages is None and args.rgb_out_stages is None \
-            and args.semi_stages is None:
+            and args.semi_stages is None and args.packed_stages is None:
         ap.error("the following arguments are required: --cube (or --lut1d for a 1D LUT alone)")
 
     stop = {"flag": False}
@@ -528,7 +561,7 @@ def main(argv=None) -> int:
         second_fmt = kw.pop("out2_pix_fmt", None)
         if "matte" in kw:
             kw["matte"] = MatteReader(kw.pop("matte"), kw.pop("matte_pix_fmt"), w, h)
-        stacked = any(k in kw for k in ("stages", "rgb_stages", "rgb_out_stages", "semi_stages"))   # (the list names its lut3d2 / lut1d stages)
+        stacked = any(k in kw for k in ("stages", "rgb_stages", "rgb_out_stages", "semi_stages", "packed_stages"))   # (the list names its lut3d2 / lut1d stages)
         pipe = HostPipeline(eng, pix_fmt, w, h, batch=args.batch, out_pix_fmt=out_fmt, out_size=args.out_size,
                             second_pix_fmt=second_fmt, chain=lut2 is not None and not stacked,
                             lut1d=args.lut1d is not None and not stacked, rgb_out=rgb_out, **kw)

@@ -20,7 +20,7 @@ from pathlib import Path
 from typing import List, Optional, Tuple
 
 from .formats import (check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options, check_lut1d_options,
-                      check_premul_options, SEMI_STAGES_EXCLUSIVE, check_rgb_stack_options, check_semi_stack_options, check_stack_options, check_yuv2rgb_stack_options, implied_stages, parse_stages, stages_string, parse_rgb_source, premul_to_yuv)
+                      check_premul_options, PACKED_STAGES_EXCLUSIVE, SEMI_STAGES_EXCLUSIVE, check_packed_stack_options, check_rgb_stack_options, check_semi_stack_options, check_stack_options, check_yuv2rgb_stack_options, implied_stages, parse_stages, stages_string, parse_rgb_source, premul_to_yuv)
 from .params import ProcessingParams, Task, VideoInfo
 from .plan import LutPlan, output_color_tags, resolve_lut_plan, resolve_pix_fmt
 
@@ -260,7 +260,7 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                    interp1d: Optional[str] = None, stages=None, strength: Optional[float] = None,
                    strength_keys: Optional[str] = None, matte: Optional[Path] = None, matte_pix_fmt: Optional[str] = None,
                    matte_invert: bool = False, rgb_matrix=None, rgb_stages=None, rgb_out: Optional[str] = None,
-                   rgb_out_stages=None, semi_stages=None) -> List[str]:
+                   rgb_out_stages=None, semi_stages=None, packed_stages=None) -> List[str]:
     """`build_command`'s twin for the LUT stage alone: the argv of the ENGINE CLI (`python -m lut_renderer_amd.cli`)
     that applies exactly the chain `build_command` would put into `-vf` -- the same `LutPlan`, rendered as CLI options
     instead of as a filter string (ffmpeg.py:195-247, :287-310).  `source` / `output` are rawvideo files (or `-`) in
@@ -317,7 +317,12 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     `semi_stages` is `stages` for a stage with a semi-planar side (`--semi-stages`, rendered only when given:
     without it the argv is what it was): the same lists and files, without the matrix stage, on nv12 / p010le .. frames into the
     resolved output format -- semi-planar, or planar YUV at 4:2:0 / 4:2:2 / 4:4:4 -- or from planar YUV into a semi-planar one;
-    the refusals are `formats.check_semi_stack_options`'s.  Not together with `stages` / `rgb_stages` / `rgb_out_stages`."""
+    the refusals are `formats.check_semi_stack_options`'s.  Not together with `stages` / `rgb_stages` / `rgb_out_stages`.
+    `packed_stages` is `stages` for a stage with a packed 4:2:2 or v210 side (`--packed-stages`, rendered only
+    when given: without it the argv is what it was): the same lists and files, without the matrix stage, on uyvy422 / y210le / v210 ..
+    frames into the resolved output format -- the same kind of container, or planar YUV at 4:2:2 / 4:2:0 / 4:4:4 -- or from planar
+    4:2:2 into a packed 4:2:2 / v210 one; the refusals are `formats.check_packed_stack_options`'s.  Not together with another
+    stage list."""
     import sys as _sys
     premul = check_alpha_mode(alpha_mode)
     if precision not in ("strict", "fast", "fma32"):
@@ -341,6 +346,9 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     pix_fmt = resolve_pix_fmt(params, source_info, notes) if params.video_codec else ""
     if semi_stages is not None and (stages is not None or rgb_stages is not None or rgb_out_stages is not None):
         raise ValueError(SEMI_STAGES_EXCLUSIVE)
+    if packed_stages is not None and (stages is not None or rgb_stages is not None or rgb_out_stages is not None
+                                      or semi_stages is not None):
+        raise ValueError(PACKED_STAGES_EXCLUSIVE)
     if rgb_out_stages is not None:
         if rgb_out is None:
             raise ValueError("rgb_out_stages is the stage list of a YUV source written as RGB: it needs rgb_out")
@@ -425,11 +433,12 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
     if rgb_stages is not None and stages is not None:
         raise ValueError("stages and rgb_stages are mutually exclusive: stages is the list of a YUV source, rgb_stages that of an "
                          "RGB source")
-    if rgb_matrix is not None and stages is None and rgb_stages is None and rgb_out_stages is None and semi_stages is None:
+    if rgb_matrix is not None and stages is None and rgb_stages is None and rgb_out_stages is None and semi_stages is None \
+            and packed_stages is None:
         raise ValueError("rgb_matrix needs stages: a matrix stage has no implied position (e.g. stages='lut1d,matrix,lut3d')")
     # the pairwise refusals below give way to check_stack_options / check_rgb_stack_options / check_yuv2rgb_stack_options at the end
     stack = stages is not None or mixed or matte is not None or rgb_stages is not None or rgb_out_stages is not None or \
-        semi_stages is not None
+        semi_stages is not None or packed_stages is not None
     if cube2 is not None:
         from .plan import INTERP_WHITELIST
         if not stack:
@@ -482,7 +491,7 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
         from . import _native
         from .plan import INTERP_WHITELIST
         mode2 = None if interp2 is None else interp2 if interp2 in INTERP_WHITELIST else "tetrahedral"
-        listed = semi_stages if semi_stages is not None else rgb_out_stages if rgb_out_stages is not None else \
+        listed = packed_stages if packed_stages is not None else semi_stages if semi_stages is not None else rgb_out_stages if rgb_out_stages is not None else \
             rgb_stages if rgb_stages is not None else stages if stages is not None else \
             implied_stages(True, cube2 is not None, lut1d is not None, cdl is not None)
         st = parse_stages(listed, interp=plan.interp, interp2=mode2)
@@ -499,7 +508,9 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                     alpha_mode=alpha_mode, out2_pix_fmt=second_pix_fmt,
                     strength=(strength if strength_keys is None else 1.0) if mixed else None, matte=matte is not None)
         src_fmt = str(source_info.pix_fmt)
-        if semi_stages is not None:
+        if packed_stages is not None:
+            check_packed_stack_options(src_fmt, pix_fmt or None, dither=dither, precision=precision, **told)
+        elif semi_stages is not None:
             check_semi_stack_options(src_fmt, pix_fmt or None, dither=dither, precision=precision, **told)
         elif rgb_out_stages is not None:
             from .api import engine_call_for
@@ -521,7 +532,9 @@ def engine_command(source: Path, output: Path, params: ProcessingParams, lut_pat
                 cmd += ["--rgb-matrix-file", str(rgb_matrix)]
             else:
                 raise TypeError(f"rgb_matrix must be an RgbMatrix or the path of a .spimtx file, not {type(rgb_matrix).__name__}")
-        if semi_stages is not None:
+        if packed_stages is not None:
+            cmd += ["--packed-stages", stages_string(st)]
+        elif semi_stages is not None:
             cmd += ["--semi-stages", stages_string(st)]
         elif rgb_out_stages is not None:
             cmd += ["--rgb-out", rgb_out, "--rgb-out-stages", stages_string(st)]

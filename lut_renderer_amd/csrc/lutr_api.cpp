@@ -2280,6 +2280,97 @@ int lutr_apply_yuv_v210(lutr_ctx *c, const lutr_yuv_params *p, int interp, int i
                                             LUTR_FMT_DEPTH(p->fmt_out), ocsx, ocsy, interp));
 }
 
+// ---- the stage stack on packed 4:2:2 and v210 frames: lutr_apply_yuv_stack's list, constants and resources between
+// the container checks of lutr_apply_yuv_packed / lutr_apply_yuv_v210 and the kernels of lutr_pkstack.hip.
+// `in` / `out`: the packings of lutr_apply_yuv_stack_packed; null for lutr_apply_yuv_stack_v210, whose sides are in_v210 / out_v210.
+static int apply_yuv_stack_capture(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                                   const lutr_yuv_packing *in, const lutr_yuv_packing *out, int in_v210, int out_v210, int w, int h,
+                                   int nframes, const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+{
+    if (!c || !src || !dst) { set_error("null argument"); return LUTR_EINVAL; }
+    StackList T;
+    if (const int rc = stack_check_list(c, stages, nstages, cdl, false, nullptr, &T)) return rc;
+    if (const int rc = check_geometry(w, h, nframes, row0, rows)) return rc;
+    if (const int rc = stack_compile_steps(c, stages, nstages, &T)) return rc;
+    if (!p) { set_error("null yuv params"); return LUTR_EINVAL; }
+    UnionCall U; const FrameGeom G{w, h, row0, rows, nframes};
+    U.nsides = 2;
+    U.lut_depth = p->lut_depth;
+    const int ocsx = LUTR_FMT_CSX(p->fmt_out), ocsy = LUTR_FMT_CSY(p->fmt_out);
+    const bool src_422 = LUTR_FMT_CSX(p->fmt_in) == 1 && LUTR_FMT_CSY(p->fmt_in) == 0;
+    if (in) {
+        // lutr_apply_yuv_packed's order: the constants, the layouts, then each side's packing
+        if (const int rc = make_yuv_consts_xsub(*p, &U.K)) return rc;
+        if (!src_422) {
+            set_error(out->packed ? "a packed destination takes a 4:2:2 source (no subsampling change into a packed frame)"
+                                  : "the source of a packed call is 4:2:2");
+            return LUTR_EINVAL;
+        }
+        if (!((ocsx == 1 && ocsy <= 1) || (ocsx == 0 && ocsy == 0))) { set_error("the destination is 4:2:2, 4:2:0 or 4:4:4"); return LUTR_EINVAL; }
+        U.side[0] = packed_side("source", src, p->fmt_in, in, w);
+        U.side[1] = packed_side("destination", dst, p->fmt_out, out, w);
+        if (const int rc = check_packed_side(U.side[0], in, nframes)) return rc;
+        if (const int rc = check_packed_side(U.side[1], out, nframes)) return rc;
+    } else {
+        // lutr_apply_yuv_v210's order: the container's own refusals first, then the constants
+        U.side[0] = v210_side("source", src, p->fmt_in, in_v210, w);
+        U.side[1] = v210_side("destination", dst, p->fmt_out, out_v210, w);
+        if (const int rc = check_v210_side(U.side[0], p->fmt_in, w, nframes)) return rc;
+        if (!src_422) {
+            set_error("a v210 destination takes a 4:2:2 source (no subsampling change into a v210 frame)");
+            return LUTR_EINVAL;
+        }
+        if (const int rc = check_v210_side(U.side[1], p->fmt_out, w, nframes)) return rc;
+        if (const int rc = make_yuv_consts_xsub(*p, &U.K)) return rc;
+        if (!((ocsx == 1 && ocsy <= 1) || (ocsx == 0 && ocsy == 0))) { set_error("the destination is 4:2:2, 4:2:0 or 4:4:4"); return LUTR_EINVAL; }
+    }
+    const Side &Si = U.side[0], &Di = U.side[1];
+    if (const int rc = union_rules(c, U, G, "stack", "the stack pass")) return rc;
+    if (w == 0 || rows == 0 || nframes == 0) return LUTR_OK;
+    if (const int rc = check_sides_disjoint("the stack pass", true, Si, Di, G)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    LutConsts L{}, L2{}; StackConsts S{}; MtxConsts X{}; PlaneSet P;
+    if (const int rc = stack_device_consts(c, T, cdl, nullptr, p->lut_depth, &L, &L2, &S, &X)) return rc;
+    fill_planes(&P, src, dst);
+    if (Si.packed) clear_planes(&P, true, 1);
+    if (Di.packed) clear_planes(&P, false, 1);
+    const char *name;
+    if (in) {
+        const PkArgs A{in->packed, in->order == LUTR_PK_UYVY, in->order == LUTR_PK_YVYU, in->shift,
+                       out->packed, out->order == LUTR_PK_UYVY, out->order == LUTR_PK_YVYU, out->shift};
+        name = launch_yuv_stack_packed(c->stream, c->variant, L, L2, S, U.K, P, G, A, Si.depth, Di.depth, ocsx, ocsy);
+    } else {
+        const V210Args A{in_v210, out_v210};
+        name = launch_yuv_stack_v210(c->stream, c->variant, L, L2, S, U.K, P, G, A, Si.depth, Di.depth, ocsx, ocsy);
+    }
+    if (!name) return finish_launch(c, nullptr);
+    const std::string full = std::string(name) + "[" + T.list + "]";
+    return finish_launch(c, full.c_str());
+}
+
+int lutr_apply_yuv_stack_packed(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                                const lutr_yuv_packing *in, const lutr_yuv_packing *out, int w, int h, int nframes,
+                                const lutr_planes *src, const lutr_planes *dst, int row0, int rows)
+{
+    if (!in || !out) { set_error("stack: null packing"); return LUTR_EINVAL; }
+    if (!in->packed && !out->packed && !in->order && !out->order && !in->shift && !out->shift)
+        return lutr_apply_yuv_stack(c, p, stages, nstages, cdl, w, h, nframes, src, dst, row0, rows);   // planar both ways: that call itself
+    return apply_yuv_stack_capture(c, p, stages, nstages, cdl, in, out, 0, 0, w, h, nframes, src, dst, row0, rows);
+}
+
+int lutr_apply_yuv_stack_v210(lutr_ctx *c, const lutr_yuv_params *p, const lutr_stage *stages, int nstages, const lutr_cdl *cdl,
+                              int in_v210, int out_v210, int w, int h, int nframes, const lutr_planes *src, const lutr_planes *dst,
+                              int row0, int rows)
+{
+    if ((in_v210 != 0 && in_v210 != 1) || (out_v210 != 0 && out_v210 != 1)) {
+        set_error("in_v210 and out_v210 are 0 or 1 (got %d, %d)", in_v210, out_v210);
+        return LUTR_EINVAL;
+    }
+    if (!in_v210 && !out_v210)
+        return lutr_apply_yuv_stack(c, p, stages, nstages, cdl, w, h, nframes, src, dst, row0, rows);   // planar both ways: that call itself
+    return apply_yuv_stack_capture(c, p, stages, nstages, cdl, nullptr, nullptr, in_v210, out_v210, w, h, nframes, src, dst, row0, rows);
+}
+
 // ---- the RGB side of lutr_apply_rgb_to_yuv / lutr_apply_yuv_to_rgb (`side`: "source" | "destination"): gbrp planes at lut_depth
 // (kind 0), or the packed format `kind`, whose depth lut_depth must be
 static int rgb_side_layout(int kind, int lut_depth, const char *side, RgbLayout *Y)

@@ -376,6 +376,30 @@ const char *launch_yuv_v210(hipStream_t st, int variant, const LutConsts &L, con
 LUTR_V2_DECL(w11) LUTR_V2_DECL(w10)
 #undef LUTR_V2_DECL
 
+// the stage stack on packed 4:2:2 and v210 frames (lutr_pkstack.hip): launch_yuv_packed's / launch_yuv_v210's call
+// with launch_yuv_stack's plain step list in place of the one lattice.  nullptr = the variant cannot take the call (vec_lds always;
+// vec_global on layouts the vector kernel cannot take and on pyramid / prism stages)
+const char *launch_yuv_stack_packed(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
+                                    const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const PkArgs &A, int din, int dout,
+                                    int ocsx, int ocsy);
+const char *launch_yuv_stack_v210(hipStream_t st, int variant, const LutConsts &L, const LutConsts &L2, const StackConsts &S,
+                                  const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const V210Args &A, int din, int dout,
+                                  int ocsx, int ocsy);
+// their vector kernels, one translation unit per container mix (w<in wide><out wide>, a v210 side counted as wide); tri: some
+// lattice step is trilinear; lds: stage the tables per workgroup; nullptr = not a side pair it has
+#define LUTR_PKS_DECL(tag) \
+    const char *launch_yuv_stack_pk_vec_##tag(hipStream_t st, const LutConsts &L, const LutConsts &L2, const StackConsts &S, \
+                                              const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const PkArgs &A, int ocsy, \
+                                              bool tri, bool lds);
+LUTR_PKS_DECL(w00) LUTR_PKS_DECL(w11) LUTR_PKS_DECL(w10)
+#undef LUTR_PKS_DECL
+#define LUTR_VKS_DECL(tag) \
+    const char *launch_yuv_stack_v210_vec_##tag(hipStream_t st, const LutConsts &L, const LutConsts &L2, const StackConsts &S, \
+                                                const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const V210Args &A, \
+                                                int ocsy, bool tri, bool lds);
+LUTR_VKS_DECL(w11) LUTR_VKS_DECL(w10)
+#undef LUTR_VKS_DECL
+
 // pass 2 of the dither path alone (k_dither_ed on the float planes F, chroma planes in the output layout); false = rows too wide
 bool launch_dither_ed(hipStream_t st, const YuvConsts &K, const PlaneSet &P, const FrameGeom &G, const FloatPlanes &F, int wout,
                       int ocsx, int ocsy);

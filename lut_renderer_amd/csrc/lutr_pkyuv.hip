@@ -18,6 +18,7 @@
 //   LUTR_PK_WI / _WO     the vector kernels of one container mix (8 -> 8, 16 -> 16, 16 -> 8): 4 side pairs x 3 modes
 #include "lutr_device.h"
 #include "lutr_launch.h"
+#include "lutr_pkcodes.h"
 
 namespace lutr {
 
@@ -28,62 +29,7 @@ namespace lutr {
 // thread's luma and chroma of a row in ONE run of 16 bytes (two for the 16-bit side of 16 -> 8); a planar side in the three
 // accesses of k_yuv_vec.  Group order and shift are wave-uniform kernel arguments: they end up in the offset operand of the
 // bit-field extract that unpacks the sample anyway.
-template <int NW>
-__device__ __forceinline__ void ld_run(uint32_t *w, const uint8_t *p)
-{
-    if constexpr (NW == 8) { ld_words<4>(w, p); ld_words<4>(w + 4, p + 16); }
-    else ld_words<NW>(w, p);
-}
-
-template <int NW>
-__device__ __forceinline__ void st_run(uint8_t *p, const uint32_t *w)
-{
-    if constexpr (NW == 8) { st_words<4>(p, w); st_words<4>(p + 16, w + 4); }
-    else st_words<NW>(p, w);
-}
-
-// luma sample dx of group j of a packed row: 8 bit -- byte 2 dx + cf of word j; 16 bit -- half cf of word 2 j + dx
-template <int WIDE>
-__device__ __forceinline__ float pk_luma(const uint32_t *w, int j, int dx, unsigned cf, unsigned shift)
-{
-    if constexpr (WIDE) return (float)__builtin_amdgcn_ubfe(w[2 * j + dx], cf * 16u + shift, 16u - shift);
-    else return (float)__builtin_amdgcn_ubfe(w[j], (2u * dx + cf) * 8u, 8u);
-}
-
-// chroma component k (0: Cb, 1: Cr) of group j: the first or the second chroma sample of the group, by `csw`
-template <int WIDE>
-__device__ __forceinline__ float pk_chroma(const uint32_t *w, int j, unsigned k, unsigned cf, unsigned csw, unsigned shift)
-{
-    if constexpr (WIDE) {
-        const unsigned off = (1u - cf) * 16u + shift;
-        const uint32_t a = __builtin_amdgcn_ubfe(w[2 * j], off, 16u - shift), b = __builtin_amdgcn_ubfe(w[2 * j + 1], off, 16u - shift);
-        return (float)((k ^ csw) ? b : a);
-    } else {
-        return (float)__builtin_amdgcn_ubfe(w[j], ((1u - cf) + 2u * (k ^ csw)) * 8u, 8u);
-    }
-}
-
-template <int WIDE>
-__device__ __forceinline__ void pk_put_luma(uint32_t *w, int j, int dx, unsigned cf, float v)
-{
-    const uint32_t u = (uint32_t)v;
-    if constexpr (WIDE) w[2 * j + dx] |= u << (cf * 16u);
-    else w[j] |= u << ((2u * dx + cf) * 8u);
-}
-
-template <int WIDE>
-__device__ __forceinline__ void pk_put_chroma(uint32_t *w, int j, unsigned cf, unsigned csw, float cb, float cr)
-{
-    const uint32_t ub = (uint32_t)cb, ur = (uint32_t)cr;
-    const uint32_t a = csw ? ur : ub, b = csw ? ub : ur;
-    if constexpr (WIDE) {
-        w[2 * j] |= a << ((1u - cf) * 16u);
-        w[2 * j + 1] |= b << ((1u - cf) * 16u);
-    } else {
-        w[j] |= (a << ((1u - cf) * 8u)) | (b << ((3u - cf) * 8u));
-    }
-}
-
+// (ld_run / st_run and the pk_* code positions: lutr_pkcodes.h)
 // PI / PO: the source / destination is packed.  The source is always 4:2:2; OCSY = 1 is a planar 4:2:0 destination.
 template <int WIN, int WOUT, int PI, int PO, int OCSY, int INTERP>
 __global__ __launch_bounds__(256) void k_yuv_pk_vec(LutConsts L, YuvConsts K, PlaneSet P, FrameGeom G, PkArgs A)

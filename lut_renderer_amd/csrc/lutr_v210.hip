@@ -16,18 +16,11 @@
 //                        planar 16 bit (4:2:2, 4:2:0), planar 16 bit -> v210; w10 -- v210 -> planar 8 bit (4:2:2, 4:2:0)
 #include "lutr_device.h"
 #include "lutr_launch.h"
+#include "lutr_pkcodes.h"
 
 namespace lutr {
 
-// where the samples of a group sit: word and bit offset of luma sample l (0..5) and of Cb / Cr of pair k (0..2)
-__device__ constexpr int kV2YW[6] = {0, 1, 1, 2, 3, 3}, kV2YO[6] = {10, 0, 20, 10, 0, 20};
-__device__ constexpr int kV2BW[3] = {0, 1, 2}, kV2BO[3] = {0, 10, 20};
-__device__ constexpr int kV2RW[3] = {0, 2, 3}, kV2RO[3] = {20, 0, 10};
-
-// one code of a word (a v_bfe_u32 with a compile-time offset once the caller's loop is unrolled); a code into a zeroed word
-__device__ __forceinline__ float v2_get(uint32_t w, int off) { return (float)__builtin_amdgcn_ubfe(w, (unsigned)off, 10u); }
-__device__ __forceinline__ void v2_put(uint32_t *w, int off, float v) { *w |= (uint32_t)v << off; }
-
+// (where the samples of a group sit, v2_get / v2_put and the word-by-word runs: lutr_pkcodes.h)
 #ifdef LUTR_V2_WI
 // ================================================================= vector kernel, global gather
 // k_yuv_pk_vec's structure (lutr_pkyuv.hip): whole-word loads and stores, 2^OCSY luma rows per thread, lattice taps gathered from
@@ -35,20 +28,6 @@ __device__ __forceinline__ void v2_put(uint32_t *w, int off, float v) { *w |= (u
 // as many groups as make whole words on the planar side: 1 (v210 -> v210), 2 (16-bit planes: 12 luma samples = 6 words, 6 chroma
 // samples = 3 words) or 4 (8-bit planes: 24 luma samples = 6 words, 12 chroma samples = 3 words).  The planar runs of 6 and 3
 // words start on a 4-byte boundary and no better (24 and 12 bytes per thread), so they move word by word.
-template <int NW>
-__device__ __forceinline__ void ld_dwords(uint32_t *w, const uint8_t *p)
-{
-#pragma unroll
-    for (int k = 0; k < NW; k++) ld_words<1>(w + k, p + 4 * k);
-}
-
-template <int NW>
-__device__ __forceinline__ void st_dwords(uint8_t *p, const uint32_t *w)
-{
-#pragma unroll
-    for (int k = 0; k < NW; k++) st_words<1>(p + 4 * k, w + k);
-}
-
 // WP: the planar side is 16 bit (ignored for v210 -> v210).  VI / VO: the source / destination is v210.  The source is always
 // 4:2:2; OCSY = 1 is a planar 4:2:0 destination.
 template <int WP, int VI, int VO, int OCSY, int INTERP>

@@ -27,7 +27,7 @@ from .formats import (_ALPHA_RESIZE, PackedYuvFmt, PixFmt, RgbSource, SemiFmt, V
                       changes_subsampling, check_alpha_mode, check_cdl_options, check_chain_options, check_chroma_loc,
                       check_lut1d_options, check_matte, check_rgb_stack_options, check_stack_options, check_strength, check_yuv2rgb_options, check_yuv2rgb_stack_options,
                       check_container_options,
-                      check_dual_options, check_lut2, check_packed_options, check_premul_options, check_semi_options,
+                      check_dual_options, check_lut2, check_packed_options, check_packed_stack_options, check_premul_options, check_semi_options,
                       check_semi_stack_options, chroma_loc_code, dual_side, has_prologue, held_resources, packed_frame_width, parse_packed_yuv_fmt, parse_pix_fmt,
                       parse_rgb_source, parse_semi_fmt, parse_size, parse_v210_fmt, refuse_alpha_resize, refuse_chain_keywords,
                       refuse_dual_keywords, source_bit_depth, v210_frame_width, yuv_side)
@@ -1082,6 +1082,60 @@ class LutEngine:
                 self._ctx, C.byref(p), arr, n, k, C.byref(fin.layout()), C.byref(fout.layout()), w, h, nf, C.byref(s), C.byref(d),
                 row0, rows))
         return dst
+
+    def apply_yuv_stack_packed(self, src, dst=None, *, pix_fmt: str, out_pix_fmt: Optional[str] = None, stages,
+                               cdl: Optional[Cdl] = None, width: Optional[int] = None, matrix_in: str = "bt709",
+                               matrix_out: Optional[str] = None, range_src: str = "tv", range_in: Optional[str] = None,
+                               range_out: str = "tv", lut_depth: Optional[int] = None, row0: int = 0, rows: Optional[int] = None,
+                               **other):
+        """`apply_yuv_stack` on capture frames -- a source side, a destination side or both packed 4:2:2 (yuyv422, uyvy422, yvyu422,
+        y210le, y212le, y216le) or v210 -- in one pass (lutr_apply_yuv_stack_packed / lutr_apply_yuv_stack_v210):
+        a capture card's v210 / uyvy422 through `stages` into v210 / uyvy422 for a play-out card or into a planar master, without
+        an unpacking pass ahead of the stack and a packing pass behind it.  The sides are what `apply_yuv` takes for these
+        containers: a packed side ONE tensor [..., h, 4 * ceil(w / 2)], a v210 side ONE int32 tensor [..., h, 32 * ceil(w / 48)],
+        bare or in a one-element list (`width` names a width the rows cannot tell); a planar side three planes.  The result is
+        bit for bit `packedyuv.to_packed` / `v210.to_v210` of `apply_yuv_stack` on the planar samples of `src`.  A packed or v210
+        source may go to planar 4:2:2, 4:2:0 or 4:4:4 at 8..16 bit; a packed or v210 destination takes a 4:2:2 source.  `stages`,
+        `cdl`, the matrices, ranges, `lut_depth` and row0 / rows (on the destination's chroma block) are `apply_yuv_stack`'s;
+        strict arithmetic, not in place.  No matrix stage, strength, matte, dither, chroma_loc, out_size, premultiplied alpha or
+        second output, no yuva* / semi-planar / RGB / float side, no packed 4:2:2 side together with a v210 side, and at least one
+        packed 4:2:2 or v210 side: each is a ValueError naming it (`formats.check_packed_stack_options`)."""
+        strength, matte, rgb_matrix = other.pop("strength", None), other.pop("matte", None), other.pop("rgb_matrix", None)
+        st, fin, fout, (arr, n, k, _mtx) = _stack_front(
+            self, "apply_yuv_stack_packed", check_packed_stack_options,
+            ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt"), pix_fmt, out_pix_fmt, stages, cdl, rgb_matrix, other,
+            strength=strength, matte=matte)
+        p = _yuv_call_params(fin, fout, lut_depth, matrix_in, matrix_out, range_src, range_in, range_out)
+        v210 = isinstance(fin, V210Fmt) or isinstance(fout, V210Fmt)
+        bare = fout.nplanes == 1 and isinstance(dst, torch.Tensor)
+        if fin.nplanes == 1 and isinstance(src, torch.Tensor):
+            src = [src]
+        if bare:
+            dst = [dst]
+        if isinstance(src, torch.Tensor) or len(src) != fin.nplanes:
+            raise ValueError(f"'{fin.name}' takes {fin.nplanes} plane{'s' if fin.nplanes > 1 else ''}")
+        if not isinstance(src[0], torch.Tensor):
+            raise TypeError(_NOT_TENSORS)
+        w = v210_frame_width(fin, fout, src, dst, width) if v210 else packed_frame_width(fin, src, width)
+        h = src[0].shape[-2]
+        if dst is None:
+            dst = _fresh_planes(fout, w, h, src[0], self.device)
+        _check_planes(src, fin, w, h, "source")
+        _check_planes(dst, fout, w, h, "destination")
+        _check_not_in_place(src, dst, _STACK_IN_PLACE)
+        s, nf = _planes_struct(src, self.device, fin.nplanes)
+        d, nfd = _planes_struct(dst, self.device, fout.nplanes)
+        if nf != nfd:
+            raise ValueError("src and dst disagree on the number of frames")
+        if v210:
+            entry, sides = self._lib.lutr_apply_yuv_stack_v210, (int(isinstance(fin, V210Fmt)), int(isinstance(fout, V210Fmt)))
+        else:
+            entry, sides = self._lib.lutr_apply_yuv_stack_packed, (C.byref(fin.packing()), C.byref(fout.packing()))
+        rows = h - row0 if rows is None else rows
+        with self._lock:
+            self._bind_stream()
+            _native.check(entry(self._ctx, C.byref(p), arr, n, k, *sides, w, h, nf, C.byref(s), C.byref(d), row0, rows))
+        return dst[0] if bare else dst
 
     def apply_rgb_lut1d(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, depth: int,
                         interp: Optional[str] = None, row0: int = 0, rows: Optional[int] = None):

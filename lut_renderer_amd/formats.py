@@ -1109,3 +1109,77 @@ def check_semi_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] 
         strength=strength, matte=None if matte is False else matte, dither=dither, chroma_loc=chroma_loc, out_size=out_size,
         out2_pix_fmt=out2_pix_fmt, alpha_mode=alpha_mode), vector=(st, fin.depth, fout.depth, pix_fmt, fout.name))
     return st, fin, fout
+
+
+# ---------------------------------------------------------------- the stage stack on packed 4:2:2 / v210 frames
+PACKED_STACK_TAIL = "a stage stack on packed 4:2:2 / v210 frames (packed_stages)"
+
+#: what every layer says when the list comes with another one
+PACKED_STAGES_EXCLUSIVE = ("packed_stages and stages / rgb_stages / rgb_out_stages / semi_stages are mutually exclusive: packed_stages "
+                           "is the list of a call with a packed 4:2:2 or v210 side, stages that of planar YUV on both sides, rgb_stages "
+                           "that of an RGB source, rgb_out_stages that of a YUV source with rgb_out, semi_stages that of a call with "
+                           "a semi-planar side")
+
+
+def packed_stack_side(name: Optional[str], what: str):
+    """One side of the stack on capture frames: the `PackedYuvFmt` of a packed 4:2:2 name, the `V210Fmt` of v210 or the `PixFmt`
+    of a planar YUV one (yuvj* read as yuv*); ValueError, naming it, for a yuva*, semi-planar, RGB or float name and for a packed
+    name this path does not take (v210x, v410, packed 4:4:4 and big-endian ones)."""
+    tail = PACKED_STACK_TAIL
+    if name in _PACKED_YUV_UNSUPPORTED:
+        raise ValueError(f"'{name}' is not supported with {tail}: packed YUV frames are taken as little-endian 4:2:2 "
+                         f"({', '.join(_native.PACKED_YUV_FORMATS)})")
+    if name in _V210_UNSUPPORTED:
+        raise ValueError(f"'{name}' is not supported with {tail}: of this family only v210 is taken")
+    if parse_semi_fmt(name) is not None or name in _SEMI_UNSUPPORTED:
+        raise ValueError(f"a semi-planar side ({what} '{name}') is not supported with {tail}")
+    rgb = parse_rgb_source(name)
+    if rgb is not None:
+        kind = "a float" if rgb.floating else "an RGB"
+        raise ValueError(f"{kind} side ({what} '{name}') is not supported with {tail}: both sides are YUV, planar, packed 4:2:2 "
+                         f"or v210")
+    side = yuv_side(name)
+    if getattr(side, "alpha", False):
+        raise ValueError(f"alpha ({what} '{name}') is not supported with {tail}: packed 4:2:2 and v210 frames carry no alpha")
+    return side
+
+
+def check_packed_stack_options(pix_fmt: Optional[str], out_pix_fmt: Optional[str] = None, *, stages, cdl: bool = False,
+                               lut: bool = True, lut2: bool = True, lut1d: bool = True, prelut: bool = False, dither: str = "none",
+                               chroma_loc: Optional[str] = None, out_size=None, alpha_mode: str = "straight",
+                               out2_pix_fmt: Optional[str] = None, variant: Optional[str] = None, strength=None,
+                               precision: Optional[str] = None, matte=None, rgb_matrix: bool = False):
+    """The checks every layer makes of a stage stack on packed 4:2:2 / v210 frames before any GPU work, the one
+    copy of its refusals: a `matrix` stage or an RGB matrix; everything `check_stage_list` refuses; a side that is neither packed
+    4:2:2, v210 nor planar YUV -- yuva*, semi-planar, RGB and float names, and v210x / v410 / packed 4:4:4 / big-endian ones, by
+    name; both sides planar (that is `apply_yuv_stack`'s call); a packed 4:2:2 side together with a v210 side; a source that is not
+    4:2:2 (the side rule of `apply_yuv` on these containers); strength / matte; dither, chroma_loc, out_size; a second output;
+    premultiplied alpha; the vec_lds variant, and vec_global where the names of the call already say that the vector kernel
+    cannot take it.  A `precision` other than strict is taken as the stack takes it without a strength: the pass runs strict.
+    Returns (parsed stages, source side, destination side); a side is a `PackedYuvFmt`, a `V210Fmt` or a planar `PixFmt`."""
+    tail = PACKED_STACK_TAIL
+    if rgb_matrix or "matrix" in [k for k, _m in parse_stages(stages)]:
+        raise ValueError(f"stage 'matrix' is not supported with {tail}: the matrix stage has no packed 4:2:2 / v210 form")
+    st = check_stage_list(stages, cdl=cdl, lut=lut, lut2=lut2, lut1d=lut1d, prelut=prelut)
+    if not pix_fmt:
+        raise ValueError(f"{tail} needs pix_fmt")
+    out_name = out_pix_fmt or pix_fmt
+    fin = packed_stack_side(pix_fmt, "pix_fmt")
+    fout = packed_stack_side(out_name, "out_pix_fmt")
+    kinds = {type(s) for s in (fin, fout)}
+    if not kinds & {PackedYuvFmt, V210Fmt}:
+        raise ValueError(f"both sides are planar: use apply_yuv_stack ('{pix_fmt}' -> '{out_name}' has no packed 4:2:2 or v210 "
+                         f"side)")
+    if PackedYuvFmt in kinds and V210Fmt in kinds:
+        raise ValueError(f"a packed 4:2:2 side together with a v210 side is not supported with {tail} ('{pix_fmt}' -> '{out_name}'): "
+                         f"go through yuv422p10le")
+    if fin.family != "yuv" or fout.family != "yuv":
+        raise ValueError(f"packed 4:2:2 / v210 frames go with YUV formats on both sides ('{pix_fmt}' -> '{out_name}')")
+    if (fin.csx, fin.csy) != (1, 0):
+        short = "v210" if V210Fmt in kinds else "packed"
+        raise ValueError(f"a {short} destination takes a 4:2:2 source: no chroma subsampling change into '{out_name}' "
+                         f"('{pix_fmt}' -> '{out_name}')")
+    _refuse_stack_options(tail, "packed 4:2:2 / v210 stack", variant, dict(
+        strength=strength, matte=None if matte is False else matte, dither=dither, chroma_loc=chroma_loc, out_size=out_size,
+        out2_pix_fmt=out2_pix_fmt, alpha_mode=alpha_mode), vector=(st, fin.depth, fout.depth, pix_fmt, fout.name))
+    return st, fin, fout

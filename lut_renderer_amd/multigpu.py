@@ -30,7 +30,7 @@ from . import _native
 from .cube import CubeLut, read_lut, read_lut1d
 from .engine import LutEngine, _fresh_planes, _new_planes, _yuv_out_dtype, chain_args, dual_args
 from .formats import (RgbSource, check_alpha_mode, check_cdl_options, check_container_options, check_lut1d_options, check_lut2,
-                      check_matte, check_premul_options, check_rgb_stack_options, check_semi_stack_options,
+                      check_matte, check_packed_stack_options, check_premul_options, check_rgb_stack_options, check_semi_stack_options,
                       check_stack_options, check_strength, check_yuv2rgb_options, check_yuv2rgb_stack_options, held_resources, packed_frame_width, parse_pix_fmt,
                       parse_rgb_source, refuse_chain_keywords, refuse_dual_keywords, v210_frame_width, yuv_side)
 from .shard import row_blocks
@@ -423,6 +423,39 @@ class LutEngineGroup:
 
             self._shard(h, 1 << max(fin.csy, fout.csy), home, local, remote)
             return dst
+
+    def apply_yuv_stack_packed(self, src, dst=None, *, pix_fmt: str, out_pix_fmt: Optional[str] = None, stages, cdl=None, **kw):
+        """`LutEngine.apply_yuv_stack_packed` with the rows of every frame split over the group's devices, by
+        `apply_yuv_stack`'s rule: shards on multiples of the union block height of the two layouts (1 row, 2 with a 4:2:0
+        destination), no halo.  A packed 4:2:2 or v210 side is one buffer with the frame's rows; the shards give the bits of the
+        whole call."""
+        with self._lock:
+            st, fin, fout = _stack_opening(
+                self, check_packed_stack_options,
+                ("dither", "chroma_loc", "out_size", "alpha_mode", "out2_pix_fmt", "strength", "matte"),
+                pix_fmt, out_pix_fmt, stages, cdl, kw.get("rgb_matrix"), kw)
+            bare = fout.nplanes == 1 and isinstance(dst, torch.Tensor)
+            src = [src] if isinstance(src, torch.Tensor) else src
+            dst = [dst] if bare else dst
+            if "v210" in (fin.name, fout.name):
+                h, w = src[0].shape[-2], v210_frame_width(fin, fout, src, dst, kw.get("width"))
+            else:
+                h, w = src[0].shape[-2], packed_frame_width(fin, src, kw.get("width"))
+            kw = dict(kw, width=w)
+            home = src[0].device
+            if dst is None:
+                dst = _fresh_planes(fout, w, h, src[0], home)
+            names = dict(pix_fmt=pix_fmt, out_pix_fmt=out_pix_fmt, stages=st, cdl=cdl)
+
+            def local(eng, r0, r1):
+                eng.apply_yuv_stack_packed(src, dst, row0=r0, rows=r1 - r0, **names, **kw)
+
+            def remote(eng, r0, r1):
+                out = eng.apply_yuv_stack_packed(_travel(src, _row_ranges(fin, r0, r1), eng.device), None, **names, **kw)
+                return [(dst, out, _row_ranges(fout, r0, r1))]
+
+            self._shard(h, 1 << max(fin.csy, fout.csy), home, local, remote)
+            return dst[0] if bare else dst
 
     def apply_rgb_lut1d(self, src: Sequence[torch.Tensor], dst: Optional[Sequence[torch.Tensor]] = None, *, depth: int,
                         interp: Optional[str] = None, **kw):

@@ -22,7 +22,8 @@ import torch
 
 from .engine import LutEngine
 from .params import strength_keys
-from .formats import (MATTE_PIX_FMTS, RGB_STACK_TAIL, SEMI_STACK_TAIL, SEMI_STAGES_EXCLUSIVE, YUV2RGB_STACK_TAIL, RgbSource,
+from .formats import (MATTE_PIX_FMTS, PACKED_STACK_TAIL, PACKED_STAGES_EXCLUSIVE, RGB_STACK_TAIL, SEMI_STACK_TAIL, SEMI_STAGES_EXCLUSIVE,
+                      YUV2RGB_STACK_TAIL, RgbSource, check_packed_stack_options,
                       check_alpha_mode, check_cdl_options, check_chain_options, check_dual_options, check_lut1d_options,
                       check_premul_options, check_rgb_stack_options, check_semi_stack_options, check_stack_options, check_yuv2rgb_options, check_yuv2rgb_stack_options, held_resources, parse_rgb_out,
                       parse_rgb_source, parse_size, premul_to_yuv, refuse_alpha_resize, yuv_side, _YUV2RGB_NOT_TAKEN)
@@ -224,6 +225,8 @@ class HostPipeline:
         `semi_stages`: a call with a semi-planar side through the stage stack -- every batch goes through
         `apply_yuv_stack_semi` with the lattices and the 1D LUT the engine holds and `cdl`; the rings are laid out as the two names
         say.  Not with `stages`, `rgb_stages`, `rgb_out_stages` or `rgb_out`.
+        `packed_stages`: a call with a packed 4:2:2 or v210 side through the stage stack -- every batch goes
+        through `apply_yuv_stack_packed` the same way.  Not with another stage list or `rgb_out`.
         `alpha_mode` travels like `chroma_loc`, "straight" is not passed on; `cdl` (a `cdl.Cdl`)
         likewise, None is not passed on."""
         self.eng = engine
@@ -231,10 +234,24 @@ class HostPipeline:
         self.frames_submitted = 0
         self.rgb_out_stack = rgb_out_stages is not None
         self.semi_stack = apply_kw.get("semi_stages") is not None
-        self.rgb_stack = not self.rgb_out_stack and not self.semi_stack and apply_kw.get("rgb_stages") is not None
-        if self.rgb_out_stack or self.rgb_stack or self.semi_stack:
-            # the three newer stack routes: what each refuses of its own, its family's check, then one tail
-            if self.semi_stack:
+        self.packed_stack = apply_kw.get("packed_stages") is not None
+        self.rgb_stack = not self.rgb_out_stack and not self.semi_stack and not self.packed_stack and \
+            apply_kw.get("rgb_stages") is not None
+        if self.rgb_out_stack or self.rgb_stack or self.semi_stack or self.packed_stack:
+            # the four newer stack routes: what each refuses of its own, its family's check, then one tail
+            if self.packed_stack:
+                flag, tail, check = "packed_stages", PACKED_STACK_TAIL, check_packed_stack_options
+                listed, out_name = apply_kw["packed_stages"], out_pix_fmt
+                carried = ("matrix_in", "matrix_out", "range_src", "range_in", "range_out", "lut_depth")
+                refusable = ("dither", "chroma_loc", "alpha_mode", "strength", "matte")
+                if self.rgb_out_stack or self.semi_stack or apply_kw.get("stages") is not None or \
+                        apply_kw.get("rgb_stages") is not None:
+                    raise ValueError(PACKED_STAGES_EXCLUSIVE)
+                if rgb_out is not None:
+                    raise ValueError(f"rgb_out ('{rgb_out}') names the RGB output of a planar YUV source: with packed_stages the "
+                                     f"output is out_pix_fmt")
+                self.rgb_out_stack = False
+            elif self.semi_stack:
                 flag, tail, check = "semi_stages", SEMI_STACK_TAIL, check_semi_stack_options
                 listed, out_name = apply_kw["semi_stages"], out_pix_fmt
                 carried = ("matrix_in", "matrix_out", "range_src", "range_in", "range_out", "lut_depth")
@@ -278,8 +295,10 @@ class HostPipeline:
             names = (self.fin.fmt.name, self.fout.fmt.name) if self.rgb_out_stack else (pix_fmt, fout.name)
             self.kw = dict({k: apply_kw[k] for k in ("cdl", "rgb_matrix") + carried if apply_kw.get(k) is not None}, stages=st,
                            pix_fmt=names[0], out_pix_fmt=names[1])
-            self._settle("apply_yuv_stack_semi" if self.semi_stack else "apply_yuv_stack_to_rgb" if self.rgb_out_stack
-                         else "apply_rgb_stack", slots)
+            if self.packed_stack:
+                self.kw["width"] = width                       # (a packed row cannot tell an odd width, a v210 row none)
+            self._settle("apply_yuv_stack_packed" if self.packed_stack else "apply_yuv_stack_semi" if self.semi_stack
+                         else "apply_yuv_stack_to_rgb" if self.rgb_out_stack else "apply_rgb_stack", slots)
             return
         self.rgb_out = rgb_out is not None
         if self.rgb_out:
